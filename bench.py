@@ -15,7 +15,11 @@ Printed JSON (rank 0, one line) also carries
   roofline     -- the dominant kernel group, its algorithmic FLOP/s from HIP events recorded around
                   every launch in the timed region, against the dense bf16 MFMA peak;
   cpu_baseline -- the CPU oracle (plain-torch restatement of the reference, oracle/) running the same
-                  train step on this host's cores on a bounded sample (B=2 clips), reported only.
+                  train step on this host's cores on a bounded sample (B=2 clips), reported only;
+  summary      -- ms per step, frames/s and roofline fraction of every extra operating point.
+The line stays short (a few KB); the per-kernel maps and the full objects of the extra operating points go to
+--detail-json FILE.  --dump-outputs DIR writes what the last timed step returned (loss terms, per-frame outputs) as DIR/<name>.npy;
+that step then starts from the seeded initial state, so two runs with the same arguments write the same values up to rounding.
 """
 import argparse
 import json
@@ -372,6 +376,33 @@ def order_line(out):
     return line
 
 
+def compact_line(line):
+    """The printed result line: `line` (order_line) without the per-kernel maps and without the operating points' full
+    objects -- `summary` carries their numbers -- so that it stays a few KB (the full line is ~20 KB)."""
+    dropped = ('c3', 'c3_clstm', 'c5', 'b8', 'fp32', 'fp16', 'kernels_ms_per_step', 'kernel_groups_ms_per_step',
+               'kernel_groups_tflops', 'roofline_other_bound')
+    return {k_: v for k_, v in line.items() if k_ not in dropped}
+
+
+DUMP_LIMIT_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(terms, out_dir, limit_bytes=DUMP_LIMIT_BYTES):
+    """Write every tensor of `terms` (what the trainer's step returned for the last timed step) as out_dir/<name>.npy in
+    float64.  An array larger than its share of `limit_bytes` is replaced by a fixed sample of its flattened elements
+    (indices drawn once from a seeded generator), so two builds write the same elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k_: v.detach().cpu().double().numpy() for k_, v in sorted(terms.items()) if isinstance(v, torch.Tensor)}
+    share = limit_bytes // max(1, len(arrays))
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            flat = a.reshape(-1)
+            idx = np.sort(np.random.default_rng(0).choice(flat.size, share // flat.itemsize, replace=False))
+            a = flat[idx]
+        np.save(os.path.join(out_dir, name.replace('/', '_') + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -395,6 +426,10 @@ def main():
     ap.add_argument('--no-c3', action='store_true', help='skip the configs[2] (EyeNet + RefineNet pipeline) measurement')
     ap.add_argument('--no-c5', action='store_true', help='skip the configs[4] (T=120, 256x256, fp16) measurement')
     ap.add_argument('--no-points', action='store_true', help='skip the extra operating points (fp32 parity mode, B=8 per GPU, fp16)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the arrays the last timed step returned (loss terms, per-frame outputs) as DIR/<name>.npy (float64)')
+    ap.add_argument('--detail-json', metavar='FILE', default=None,
+                    help='write the full result object (per-kernel maps, every operating point) to FILE')
     args = ap.parse_args()
     c5 = args.workload == 'c5'
     args.batch = args.batch if args.batch is not None else (8 if c5 else 32)
@@ -460,14 +495,24 @@ def main():
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
+    # --dump-outputs: the weight-gradient kernels sum with float atomics, so two runs differ in the last bits of every
+    # gradient, and a few Adam steps on the one resident batch amplify that until the parameters -- and all outputs -- of
+    # the two runs have nothing in common.  The LAST timed step therefore starts from the seeded initial state (parameters,
+    # Adam moments and guard, taken here before any step): what it computes from that state and the batch is the same in
+    # every run up to rounding.  The restore is one device copy inside the timed region, once per run.
+    initial_state = trainer._snapshot() if args.dump_outputs else None
     for _ in range(args.warmup):
         terms = trainer.step(batch)
     barrier()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if initial_state is not None and i == args.steps - 1:
+            trainer._restore(initial_state)
         terms = trainer.step(batch)
     barrier()
     elapsed = time.perf_counter() - t0
+    # under hipGraph replay `terms` are the graph's static outputs: copy them before any later launch overwrites them
+    last_terms = {k_: v.detach().clone() for k_, v in terms.items() if isinstance(v, torch.Tensor)} if args.dump_outputs else None
     # per-launch kernel durations for the roofline: the same step launched eagerly with a HIP event pair around
     # every conv launch (a graph replay has no per-kernel events; the kernels and shapes are identical)
     prof, event_overhead = {}, None
@@ -565,7 +610,13 @@ def main():
             out['cpu_baseline'] = cpu_baseline(args.seq if args.workload == 'c2' else 30, args.size if args.workload == 'c2' else 128)
             if 'c3' in out:
                 out['c3']['cpu_baseline'] = cpu_baseline_c3(args.seq)
-        print(json.dumps(order_line(out)), flush=True)
+        if args.dump_outputs:
+            dump_outputs(last_terms, args.dump_outputs)
+        line = order_line(out)
+        if args.detail_json:
+            with open(args.detail_json, 'w') as f:
+                json.dump(line, f)
+        print(json.dumps(compact_line(line)), flush=True)
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()

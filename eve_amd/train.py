@@ -270,6 +270,12 @@ class Trainer(object):
         # process down -- seen as a rare crash of the one-rank RCCL tests (c10d::ProcessGroupNCCL::Watchdog, HIPEvent query).
         # 'thread_local' confines the capture rules to the capturing thread.
         mode = 'thread_local' if self.sync is not None else 'global'
+        if self.graph_collectives:
+            # ... and with the collectives captured, the process group's stream joins the capture: the watchdog's next query
+            # of a warm-up collective's event (recorded on that stream) fails with hipErrorCapturedEvent, whatever the mode.
+            # Wait until the watchdog has retired every warm-up collective; captured ones are never handed to it.
+            import torch.distributed as dist
+            (self.sync.group or dist.distributed_c10d._get_default_group())._wait_for_pending_works()
         with torch.cuda.graph(self._graph, capture_error_mode=mode):
             if self.sync is not None and self.graph_collectives:
                 # the whole distributed step in the graph: every bucket's all-reduce is captured where its gradient

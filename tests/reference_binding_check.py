@@ -11,7 +11,7 @@
 
 The drop-ins read the reference's config singleton here (`eve_amd.config.get_config()` finds `core.DefaultConfig`).
 Kernels: tests/fake_kernels.py (CPU) -- this checks the binding, constructor / forward contracts and state_dict, not
-the HIP arithmetic.  Run by tests/test_reference_binding.py in a fresh process; prints `binding ok`.
+the HIP arithmetic.  Run by hand in a fresh process (it needs the reference checkout); prints `binding ok`.
 """
 import os
 import sys
