@@ -77,6 +77,8 @@ SIGNATURES = {
     'eve_stem_bwd_dx': [I, I, I, I, P, P, P, P, P, P, P, P, P],
     'eve_stem_bwd_wgrad': [I, I, I, I, P, P, P, P, P, P, P, P, P, ctypes.c_ulonglong, P],
     'eve_stem_bwd_wgrad_workspace': [I, I, I],
+    'eve_stem_dgrad_pack': [I, I, P, P, P],
+    'eve_stem_dgrad': [I, I, I, I, I, P, P, P, P],
     'eve_bias_grad': [I, L, I, P, P, P],
     'eve_cgru_scan_fwd': [I, I, I, P, P, P, P, P, P, P, P, P, P, P, P],
     'eve_cgru_scan_bwd': [I, I, I, P, P, P, P, P, P, P, P, P, P, P, P],

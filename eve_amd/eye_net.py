@@ -32,6 +32,10 @@ from .ops import PackedWeight
 half_pi = 0.5 * math.pi
 
 
+def _wants_grad(t):
+    return torch.is_grad_enabled() and t.dtype.is_floating_point and t.requires_grad
+
+
 def default_compute_dtype():
     name = os.environ.get('EVE_AMD_DTYPE', 'fp32').lower()
     if name in ('bf16', 'bfloat16'):
@@ -137,6 +141,7 @@ class EyeNet(nn.Module):
             if blk.downsample is not None:
                 P[name + '.downsample.0'] = PackedWeight(blk.downsample[0].weight, dt, defer=True)
         PackedWeight.pack_many(list(P.values()), dt)          # all trunk weights in one launch
+        P['conv1.dgrad'] = ops.StemDgradPack(cnn.conv1.weight, dt)   # packed only when patches require a gradient
         # the tail (linears + GRU) always runs in float32: < 0.03 % of the FLOPs, and it carries the recurrence
         T = {}
         T['fc'] = PackedWeight(cnn.fc.weight, f32, defer=True)
@@ -160,15 +165,17 @@ class EyeNet(nn.Module):
         return P
 
     # ------------------------------------------------------------------ trunk
-    def _trunk(self, x, P, x_padded=None):
+    def _trunk(self, x, P, x_padded=None, patches=None):
         """x: [N, H, W, Cpad] NHWC compute dtype -> [N, 512] float32 (torchvision ResNet._forward_impl).
-        x_padded: optional [N, H+6, W+8, 4] bf16 repack for the dedicated stem kernel."""
-        y = self._trunk_layers(x, P, x_padded)
+        x_padded: optional [N, H+6, W+8, 4] bf16 repack for the dedicated stem kernel.
+        patches: None, or the float NCHW patch batches x / x_padded were made from (concatenated along the batch), when their
+        gradient is wanted: the stem's data gradient (stem_dgrad) is then returned to them."""
+        y = self._trunk_layers(x, P, x_padded, patches)
         if hasattr(ops.default_kernels(), 'avgpool_fwd_f32'):
             return ops.AvgPoolF32Fn.apply(y)                  # pool + cast in one launch each way (same bits)
         return ops.cast(ops.AvgPoolFn.apply(y), torch.float32)
 
-    def _trunk_layers(self, x, P, x_padded=None):
+    def _trunk_layers(self, x, P, x_padded=None, patches=None):
         """conv1 .. layer4 of the trunk: -> [N, H/32, W/32, 512] NHWC compute dtype."""
         cnn = self.cnn_layers
         blocks, weights = [], []
@@ -179,12 +186,20 @@ class EyeNet(nn.Module):
             weights += [blk.conv1.weight, blk.conv2.weight] + ([ds[0].weight] if ds is not None else [])
         if x_padded is not None and x_padded.shape[2] == 136 and x_padded.shape[1] % 4 == 2:
             # 128-wide patches: conv1 -> bn1 -> relu -> maxpool in one launch, inside the trunk node
-            y = ops.ResNetTrunkFn.apply(None, x, x_padded, (P['conv1'], tuple(blocks)), 1e-5, cnn.conv1.weight, *weights)
+            if patches is not None:             # (the two patch batches in the node's x / x8 slots: their gradient comes back there)
+                assert len(patches) == 2
+                P['conv1.dgrad'].get()
+                y = ops.ResNetTrunkFn.apply(patches[0], patches[1], x_padded, (P['conv1'], tuple(blocks), P['conv1.dgrad']), 1e-5,
+                                            cnn.conv1.weight, *weights)
+            else:
+                y = ops.ResNetTrunkFn.apply(None, x, x_padded, (P['conv1'], tuple(blocks)), 1e-5, cnn.conv1.weight, *weights)
         else:
             if x_padded is not None:
                 y = ops.StemConvFn.apply(x, x_padded, cnn.conv1.weight, P['conv1'])
             else:
                 y = ops.conv2d(x, cnn.conv1.weight, None, P['conv1'], stride=2, pad=3)
+            if patches is not None:
+                y = ops.StemPatchGradFn.apply(y, P['conv1.dgrad'], *patches)
             y = ops.InReluMaxPoolFn.apply(y, 1e-5)      # bn1 -> relu -> maxpool, fused
             y = ops.ResNetTrunkFn.apply(y, None, None, (None, tuple(blocks)), 1e-5, *weights)
         return y
@@ -246,6 +261,8 @@ class EyeNet(nn.Module):
             # (frozen trunk + trainable tail: the node takes the tail parameters through `self`, not as autograd inputs, so
             # its outputs would carry no graph -- the per-layer path handles that configuration)
             return False
+        if batch['left_h'].requires_grad or batch['right_h'].requires_grad:
+            return False                        # the node returns no head-pose gradient: the per-layer path does
         k = default_kernels()
         on = self.tail_loss_node if self.tail_loss_node is not None else bool(dispatch_flag(k, 'tail_loss_node', 1))
         if not (on and hasattr(k, 'tail_outputs_fwd') and torch.is_grad_enabled() and cfg.eye_net_use_rnn and
@@ -292,8 +309,13 @@ class EyeNet(nn.Module):
         image = output_dict[key] if key in output_dict else input_dict[key]
         P = self._get_packs()
         dt = self.compute_dtype
-        x = ops.ToNHWCFn.apply(image, dt, pad_channels(image.shape[1], dt))
-        feats = self._trunk(x, P)
+        if _wants_grad(image):
+            # the patch's gradient from the stem's data-gradient kernel, like the clip path's (not through the padded NHWC copy)
+            x = default_kernels().nchw_to_nhwc(image.detach().contiguous().float(), dt, pad_channels(image.shape[1], dt))
+            feats = self._trunk(x, P, patches=(image,))
+        else:
+            x = ops.ToNHWCFn.apply(image, dt, pad_channels(image.shape[1], dt))
+            feats = self._trunk(x, P)
         head_pose = input_dict[side + '_h'] if self.config.eye_net_use_head_pose_input else None
         h0 = None
         ncell = len(self.rnn_cells) if self.config.eye_net_use_rnn else 0
@@ -339,6 +361,12 @@ class EyeNet(nn.Module):
         if x_padded is None:
             B, T, C, Hh, Ww = left.shape
         cpad = pad_channels(C, dt)
+        # float patches that require a gradient (a gaze loss for a generator, saliency, adversarial inputs) get it from the
+        # stem's data-gradient kernel in every stem route; the default path below is unchanged when none does
+        patches = None
+        if _wants_grad(left) or _wants_grad(right):
+            patches = (left.reshape(B * T, C, Hh, Ww), right.reshape(B * T, C, Hh, Ww))
+            left, right = left.detach(), right.detach()         # (the packing launches below are outside the graph)
         if x_padded is not None:                                                   # packed from the uint8 frames above
             pass
         elif dt in HALF_DTYPES and C <= 4 and Hh % 4 == 0 and Ww == 128:        # fused stem: packed patches only
@@ -358,7 +386,7 @@ class EyeNet(nn.Module):
                 x_padded = torch.empty((2 * B * T, Hh + 6, Ww + 8, 4), dtype=dt, device=left.device)
                 k.stem_pack_input(left.reshape(B * T, C, Hh, Ww), out=x_padded[:B * T])
                 k.stem_pack_input(right.reshape(B * T, C, Hh, Ww), out=x_padded[B * T:])
-        return self._trunk(x, P, x_padded), B, T
+        return self._trunk(x, P, x_padded, patches), B, T
 
     def _sequence_tail(self, feats, batch, B, T, initial_states, P):
         head_pose = None

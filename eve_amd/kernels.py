@@ -325,6 +325,27 @@ class HipKernels(object):
             self._p(dy_pool2), self._p(y_pool), self._p(idx), self._p(dx), self._stream())))
         return dx
 
+    def stem_dgrad_pack(self, w_oihw, dtype):
+        """conv1's float OIHW weight [64, C, 7, 7] -> the filter operand of stem_dgrad in `dtype` (1024 x 16 elements)."""
+        w = self._f32(w_oihw.detach().contiguous(), 'w_oihw')
+        assert w.dim() == 4 and w.shape[0] == 64 and 1 <= w.shape[1] <= 4 and tuple(w.shape[2:]) == (7, 7)
+        out = torch.empty((1024, 16), dtype=dtype, device=w.device)
+        self._ck(self.lib.eve_stem_dgrad_pack(dt_code(dtype), w.shape[1], self._p(w), self._p(out), self._stream()))
+        return out
+
+    def stem_dgrad(self, dconv, w_packed, C, out=None):
+        """d(conv1 out) [N, IH/2, IW/2, 64] NHWC (float32 / bf16 / f16) -> the patch gradient [N, C, IH, IW] float32 NCHW
+        (include/eve_hip.h eve_stem_dgrad); w_packed from stem_dgrad_pack in dconv's dtype."""
+        N, OH, OW, co = dconv.shape
+        assert co == 64 and dconv.is_contiguous() and w_packed.dtype == dconv.dtype and tuple(w_packed.shape) == (1024, 16)
+        dx = out if out is not None else torch.empty((N, C, 2 * OH, 2 * OW), dtype=torch.float32, device=dconv.device)
+        assert tuple(dx.shape) == (N, C, 2 * OH, 2 * OW) and dx.dtype == torch.float32
+        flops = 2.0 * N * OH * OW * 64 * 49 * C
+        self._timed('stem_dgrad', flops, lambda: self._ck(self.lib.eve_stem_dgrad(
+            dt_code(dconv.dtype), N, 2 * OH, 2 * OW, C, self._p(dconv), self._p(w_packed), self._p(dx), self._stream())),
+            (dconv, dx))
+        return dx
+
     def stem_bwd_wgrad(self, x_padded, w_ohwi8, mr, dy_pool, y_pool, idx, dw, dy_pool2=None):
         """dw [64, 7, 8, 4] float32 += the stem's weight gradient straight from d(pooled output): backward of the fused stem and
         its weight gradient in one launch, d(conv1 out) never written (include/eve_hip.h eve_stem_bwd_wgrad)."""

@@ -343,7 +343,7 @@ class Conv2dFn(torch.autograd.Function):
 class StemConvFn(torch.autograd.Function):
     """ResNet stem conv (7x7/2, 3 -> 64) through the dedicated bf16 kernel.  x8 is the NHWC patch batch with
     channels padded to 8 (used by the weight gradient), x_padded the [N, H+6, W+8, 4] repack the forward kernel
-    reads.  The patches are inputs, so there is no data gradient."""
+    reads.  The patches' data gradient, when one is wanted, is taken from this node's output by StemPatchGradFn."""
 
     @staticmethod
     def forward(ctx, x8, x_padded, weight, pack):
@@ -397,6 +397,47 @@ class StemFusedFn(torch.autograd.Function):
         k.conv2d_wgrad(x8, dconv, KH, KW, 2, 3, dwp, algo=pack.algo)
         O, I = pack.shape_oihw[0], pack.shape_oihw[1]
         return None, None, dwp[:O, :, :, :I].permute(0, 3, 1, 2), None, None
+
+
+class StemDgradPack(object):
+    """conv1's filter as the operand of the stem's data-gradient kernel (eve_stem_dgrad_pack), made on first use: only a step
+    whose patches require a gradient packs it, and it lives with the other per-step packs (EyeNet._get_packs)."""
+    __slots__ = ('weight', 'dtype', 'w')
+
+    def __init__(self, weight, dtype):
+        self.weight, self.dtype, self.w = weight, dtype, None
+
+    def get(self):
+        if self.w is None:
+            self.w = default_kernels().stem_dgrad_pack(self.weight.detach().float(), self.dtype)
+        return self.w
+
+    def patch_grads(self, dconv, rows):
+        """d(conv1 out) [sum(rows), H/2, W/2, 64] -> the float NCHW gradients of the patch batches it was computed from, one
+        per entry of `rows` (slices of one stem_dgrad output)."""
+        dx = default_kernels().stem_dgrad(dconv.contiguous(), self.get(), self.weight.shape[1])
+        out, r = [], 0
+        for n in rows:
+            out.append(dx[r:r + n])
+            r += n
+        return out
+
+
+class StemPatchGradFn(torch.autograd.Function):
+    """Identity on the stem convolution's output y whose backward also hands d(y) to the stem's data-gradient kernel: the float
+    NCHW patch batches `patches` (concatenated along the batch, the convolution's input) receive their gradient from it.  The
+    convolution node itself keeps its weight gradient and sees the patches as constants."""
+
+    @staticmethod
+    def forward(ctx, y, dgrad_pack, *patches):
+        dgrad_pack.get()                      # packed now, from the weight the forward used
+        ctx.dgrad_pack, ctx.rows = dgrad_pack, tuple(p.shape[0] for p in patches)
+        return y.view_as(y)
+
+    @staticmethod
+    def backward(ctx, dy):
+        grads = ctx.dgrad_pack.patch_grads(dy, ctx.rows)
+        return (dy, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:]))
 
 
 def conv2d(x, weight, bias, pack, stride=1, pad=0, act=ACT_NONE, acc=None, want_stats=False):
@@ -743,13 +784,15 @@ class ResNetTrunkFn(torch.autograd.Function):
     weight gradients go straight into the flat gradient buffer.
 
     apply(x, x8, x_padded, spec, eps, *weights):
-      spec = (stem_pack or None, ((p1, p2, pd), stride) per block); weights = [conv1 if stem] + per block (w1, w2[, wd]).
-      With a stem, x and x8 are ignored and the input is x_padded (no data gradient); without, x is the block input."""
+      spec = (stem_pack or None, ((p1, p2, pd), stride) per block[, StemDgradPack]); weights = [conv1 if stem] + per block
+      (w1, w2[, wd]).  With a stem the input is x_padded; x and x8 are then None, or the two float NCHW patch batches whose
+      concatenation x_padded was packed from (left eyes, right eyes), and receive their data gradient (stem_dgrad, from the
+      same d(conv1 out) the weight gradient is formed from; spec[2] holds the filter).  Without a stem, x is the block input."""
 
     @staticmethod
     def forward(ctx, x, x8, x_padded, spec, eps, *weights):
         k = default_kernels()
-        stem_pack, blocks = spec
+        stem_pack, blocks = spec[:2]
         saved = []
         if stem_pack is not None:
             y, idx, mr = k.stem_fwd_fused(x_padded, stem_pack.ohwi, eps)
@@ -760,6 +803,7 @@ class ResNetTrunkFn(torch.autograd.Function):
             y, sv = _block_forward(k, y, packs, stride, eps)
             saved += list(sv)
         ctx.spec, ctx.weights = spec, weights
+        ctx.patch_rows = tuple(t.shape[0] for t in (x, x8) if t is not None) if stem_pack is not None else ()
         # weight gradients written in place into the flat buffer: count this use, so that a trunk applied several times
         # per step (the per-frame contract) reports each parameter to the data-parallel bookkeeping after its LAST backward
         for i, w in enumerate(weights):
@@ -771,7 +815,7 @@ class ResNetTrunkFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         k = default_kernels()
-        stem_pack, blocks = ctx.spec
+        stem_pack, blocks = ctx.spec[:2]
         saved = list(ctx.saved_tensors)
         weights = list(ctx.weights)
         need_w = list(ctx.needs_input_grad[5:])
@@ -789,8 +833,18 @@ class ResNetTrunkFn(torch.autograd.Function):
             grads[wpos], grads[wpos + 1] = dw1, dw2
             if nw == 3:
                 grads[wpos + 2] = dwd
-        dx = None
-        if stem_pack is not None:
+        dx = dx8 = None
+        if stem_pack is not None and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            # gradient of the patches as well: d(conv1 out) is formed once and read by both the weight and the data gradient
+            x_padded, y, idx, mr = saved[:4]
+            dconv = k.stem_bwd_dx(x_padded, stem_pack.ohwi, mr, d_a, y, idx, dy_pool2=d_b)
+            if need_w[0]:
+                dwp = torch.zeros((64, 7, 8, 4), dtype=torch.float32, device=x_padded.device)
+                k.stem_wgrad(x_padded, dconv, dwp)
+                O, I = stem_pack.shape_oihw[0], stem_pack.shape_oihw[1]
+                grads[0] = dwp[:O, :, :7, :I].permute(0, 3, 1, 2)
+            dx, dx8 = (ctx.spec[2].patch_grads(dconv, ctx.patch_rows) + [None, None])[:2]
+        elif stem_pack is not None:
             x_padded, y, idx, mr = saved[:4]
             if need_w[0]:
                 dwp = torch.zeros((64, 7, 8, 4), dtype=torch.float32, device=x_padded.device)
@@ -804,7 +858,7 @@ class ResNetTrunkFn(torch.autograd.Function):
                 grads[0] = dwp[:O, :, :7, :I].permute(0, 3, 1, 2)
         elif ctx.needs_input_grad[0]:
             dx = k.add(d_a, d_b) if d_b is not None else d_a
-        return (dx, None, None, None, None) + tuple(grads)
+        return (dx, dx8, None, None, None) + tuple(grads)
 
 
 def _affine_direct(k, gamma_p, beta_p):

@@ -182,6 +182,15 @@ unsigned long long eve_stem_bwd_wgrad_workspace(int dtype, int N, int IH);
 int eve_stem_wgrad(int dtype, int N, int IH, int IW, const void* x_padded, const void* dconv, float* dw, eve_stream_t stream);
 int eve_stem_bwd_dx(int dtype, int N, int IH, int IW, const void* x_padded, const void* w_ohwi8, const float* mean_rstd,
                     const void* dy_pool, const void* dy_pool2 /* nullable second summand */, const void* y_pool, const uint8_t* idx, void* dx, eve_stream_t stream);
+/* Data gradient of the stem convolution back to the patch (autograd of conv1 w.r.t. its input, eye_net.py:48,106):
+ *   dx_nchw[n][c][y][x] (float) = sum_{co,ky,kx} dconv[n][oy][ox][co] * W[co][c][ky][kx],  y = 2 oy - 3 + ky, x = 2 ox - 3 + kx,
+ * dconv [N][IH/2][IW/2][64] in `dtype` (F32 / BF16 / F16: what eve_stem_bwd_dx, the stem conv's autograd or the generic conv's
+ * backward hands over), accumulated in float32 and stored in float32, the patch's own layout and type.  IH, IW even, C <= 4.
+ * w_packed is the filter re-packed by eve_stem_dgrad_pack from the float OIHW weight [64][C][7][7]: 1024 x 16 elements of
+ * `dtype` (32 KB in 16-bit, 64 KB in float32), 16-byte aligned like dconv.  Both entries added in ABI v10 (additive).   */
+int eve_stem_dgrad_pack(int dtype, int C, const float* w_oihw, void* w_packed, eve_stream_t stream);
+int eve_stem_dgrad(int dtype, int N, int IH, int IW, int C, const void* dconv, const void* w_packed, float* dx_nchw,
+                   eve_stream_t stream);
 /* Small float32 linear layers (nn.Linear of the EyeNet tail, eye_net.py:52-90: fc, fc_common, GRU input
  * projection, gaze / pupil heads) with M rows and K, N <= 4096:
  *   fwd:   y[M][N]   = act(x[M][K] . w_in_out[K][N] + bias)
