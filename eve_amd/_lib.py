@@ -54,6 +54,12 @@ class VecTerm(Structure):
     _fields_ = [('pred', c_void_p), ('tgt', c_void_p), ('valid', c_void_p), ('dpred', c_void_p), ('D', c_int), ('kind', c_int)]
 
 
+class EyeTailWeights(Structure):
+    """include/eve_hip.h eve_eye_tail_weights"""
+    _fields_ = [(n, c_void_p) for n in ('fc_w', 'fc_b', 'c0_w', 'c0_b', 'c2_w', 'c2_b', 'ih_w', 'ih_b', 'hh_w', 'hh_b', 'g0_w', 'g0_b',
+                                        'g2_w', 'p0_w', 'p0_b', 'p2_w', 'p2_b')]
+
+
 VEC_TERMS_MAX = 32
 PACK_BATCH_MAX = 48
 ABI_VERSION = 10         # include/eve_hip.h EVE_ABI_VERSION
@@ -150,6 +156,8 @@ SIGNATURES = {
     'eve_heatmap_loss_bwd': [I, I, I, P, P, P, P, P, P],
     'eve_sumsq': [L, P, P, P, P],
     'eve_adam_step': [L, P, P, P, P, P, F, F, F, F, F, F, F, I, P, I, P, P, P],
+    'eve_eye_tail_stream_fwd': [I, I, P, P, POINTER(EyeTailWeights), P, P, P, P, P, P],
+    'eve_stream_state_rows': [I, I, L, L, L, P, P, P, P],
 }
 EXPORTS = sorted(list(SIGNATURES) + ['eve_abi_version', 'eve_last_error', 'eve_last_kernel'])
 

@@ -249,13 +249,7 @@ class EVE(nn.Module):
             for i, st in enumerate(states):
                 if not isinstance(st, tuple):
                     inter['refinenet_rnn_states_%d' % i] = st
-            h, w = hf.shape[-2:]
-            px = ops.SoftArgmaxFn.apply(hf.reshape(B * T, 1, h, w).float(), tuple(cfg.actual_screen_size)).view(B, T, 2)
-            inter['PoG_px_final'] = px
-            inter['PoG_cm_final'] = px * (0.1 * d['millimeters_per_pixel'])
-            inter['g_final'] = default_kernels().combined_gaze(
-                d['o'].reshape(B * T, 3).float(), (10.0 * inter['PoG_cm_final']).detach().reshape(B * T, 2),
-                d['left_R'].reshape(B * T, 3, 3).float(), d['camera_transformation'].reshape(B * T, 4, 4).float()).view(B, T, 2)
+            self._final_block(d, inter, hf)
             if create_images and 'PoG_px_tobii' in d:
                 refined_history = self._history_maps(d['timestamps'], hf.detach().float(), d['PoG_px_tobii_validity'])
 
@@ -293,6 +287,46 @@ class EVE(nn.Module):
             if 'heatmap_final' in d:
                 output_dict['gt_heatmap'] = d['heatmap_final'][:, -1]
         return output_dict
+
+    def _final_block(self, d, inter, hf):
+        """eve.py:155-166: the refined PoG by soft-argmax of heatmap_final [B, T, 1, h, w], in px and cm, and the combined gaze."""
+        cfg = self.config
+        B, T = hf.shape[:2]
+        h, w = hf.shape[-2:]
+        px = ops.SoftArgmaxFn.apply(hf.reshape(B * T, 1, h, w).float(), tuple(cfg.actual_screen_size)).view(B, T, 2)
+        inter['PoG_px_final'] = px
+        inter['PoG_cm_final'] = px * (0.1 * d['millimeters_per_pixel'])
+        inter['g_final'] = default_kernels().combined_gaze(
+            d['o'].reshape(B * T, 3).float(), (10.0 * inter['PoG_cm_final']).detach().reshape(B * T, 2),
+            d['left_R'].reshape(B * T, 3, 3).float(), d['camera_transformation'].reshape(B * T, 4, 4).float()).view(B, T, 2)
+
+    # ------------------------------------------------------------------------------------------ streaming (stream.py)
+    PREDICTION_KEYS = ('left_g_initial', 'right_g_initial', 'left_pupil_size', 'right_pupil_size', 'g_initial', 'PoG_px_initial',
+                       'PoG_cm_initial', 'g_final', 'PoG_px_final', 'PoG_cm_final')
+
+    def _predict_sequence(self, d, eye_states, refine_states, reset=None, return_heatmaps=False):
+        """The prediction part of forward() for one chunk of an EVEStream: eval only, no labels, no losses.  d: the chunk's
+        inputs [B, Tc, ...] (not modified); eye_states / refine_states: the carried state buffers of the two networks
+        (EyeNet._stream_state_buffers, RefineNet._stream_state_buffers), read as the state before the chunk and overwritten with
+        the state after it; reset: None or int32 [2B] device flags (stream b's flag at b and B + b) -- flagged streams start from
+        zero.  Same kernels and the same _pog_block / _final_block as forward().  -> the PREDICTION_KEYS present (the PoG keys
+        need the camera geometry), plus heatmap_final when asked."""
+        assert not self.training, 'EVE._predict_sequence is eval-only'
+        B = d['left_eye_patch'].shape[0]
+        d = dict(d)
+        if 'left_o' in d:
+            d['o'] = _mean2(d['left_o'], d['right_o'])
+        inter = dict(self.eye_net._stream_sequence(d, eye_states, reset))
+        self._pog_block(d, inter, 'initial', 'initial')
+        if self.refine_net is not None and 'heatmap_initial' in inter:
+            hf = self.refine_net._stream_sequence(inter['heatmap_initial'], d.get('screen_frame'), refine_states,
+                                                  None if reset is None else reset[:B])
+            inter['heatmap_final'] = hf
+            self._final_block(d, inter, hf)
+        out = {k_: inter[k_] for k_ in self.PREDICTION_KEYS if k_ in inter}
+        if return_heatmaps and 'heatmap_final' in inter:
+            out['heatmap_final'] = inter['heatmap_final']
+        return out
 
     # ------------------------------------------------------------------------------------------ eve.py:286-439
     def calculate_losses_and_metrics(self, d, inter, out):

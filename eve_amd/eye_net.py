@@ -418,3 +418,72 @@ class EyeNet(nn.Module):
                 cut = slice(si * B, (si + 1) * B)
                 out[side + '_eye_rnn_states_%d' % i] = tuple(s_[cut] for s_ in st) if isinstance(st, tuple) else st[cut]
         return out
+
+    # ------------------------------------------------------------------ streaming (eve_amd/stream.py)
+    # The shipped tail (one GRU cell, H = 128, head-pose input) can run as ONE eve_eye_tail_stream_fwd launch per chunk.  Off by
+    # default: one workgroup per sequence streams the tail's 0.9 MB of weights through one CU, and that measured slower than the
+    # layer-by-layer launches, which spread each layer over many CUs, at every shape tried (B x Tc = 1x1: 209 us for the kernel
+    # against ~50 us for the 10 launches it replaces; whole steps 0.15-0.7 ms slower at 1x1 .. 32x30, profiles/stream_notes.md).
+    stream_fused_tail = False
+
+    def _stream_tail_fused_ok(self):
+        cfg = self.config
+        return (self.stream_fused_tail and cfg.eye_net_use_rnn and cfg.eye_net_rnn_type == 'GRU' and len(self.rnn_cells) == 1 and
+                cfg.eye_net_use_head_pose_input and self.rnn_cells[0].hidden_size == 128 and
+                self.fc_common[0].in_features == 130 and self.cnn_layers.fc.in_features == 512 and
+                self.cnn_layers.fc.out_features == 128 and hasattr(default_kernels(), 'eye_tail_stream_fwd'))
+
+    def _stream_state_buffers(self, B, device):
+        """Zero-initialised carried states for B streams: per cell [2B, H] float32, the left eyes' rows then the right ones' (a
+        pair (h, c) for LSTM) -- the layout `_tail` and the scans use.  STATIC EyeNet: none."""
+        if not self.config.eye_net_use_rnn:
+            return []
+        z = lambda H: torch.zeros((2 * B, H), dtype=torch.float32, device=device)
+        return [(z(c.hidden_size), z(c.hidden_size)) if self.config.eye_net_rnn_type == 'LSTM' else z(c.hidden_size)
+                for c in self.rnn_cells]
+
+    def _stream_tail_weights(self, P):
+        """The 17 float32 tensors of include/eve_hip.h eve_eye_tail_weights, from the packs P (cached with them)."""
+        cached = getattr(self, '_stream_w', None)
+        if cached is not None and cached[0] is P:
+            return cached[1]
+        b = lambda t: t.detach().float().contiguous()
+        cell = self.rnn_cells[0]
+        w = (P['fc'].ihwo, b(self.cnn_layers.fc.bias), P['fc_common.0'].ihwo, b(self.fc_common[0].bias),
+             P['fc_common.2'].ihwo, b(self.fc_common[2].bias), P['rnn.0.ih'].ihwo, b(cell.bias_ih), P['rnn.0.hh'].ihwo,
+             b(cell.bias_hh), P['fc_to_gaze.0'].ihwo, b(self.fc_to_gaze[0].bias), P['fc_to_gaze.2'].ihwo,
+             P['fc_to_pupil.0'].ihwo, b(self.fc_to_pupil[0].bias), P['fc_to_pupil.2'].ihwo, b(self.fc_to_pupil[2].bias))
+        self._stream_w = (P, w)
+        return w
+
+    def _stream_sequence(self, batch, states, reset=None):
+        """One chunk of B streams (eval, no labels): batch as for forward_sequence ([B, Tc, ...]); states: the carried buffers of
+        _stream_state_buffers, read as the state before the chunk's first frame -- zeroed first where reset[s] != 0 (int32 [2B], a
+        stream's flag repeated for its two eyes) -- and overwritten with the state after its last frame.  `_tail` runs with the
+        buffers as h0 and one eve_stream_state_rows launch per state each way; with stream_fused_tail the shipped tail is one
+        eve_eye_tail_stream_fwd launch that reads and writes its state in place.  Returns the forward_sequence prediction keys (<side>_g_initial, <side>_pupil_size)."""
+        k = default_kernels()
+        P = self._get_packs()
+        feats, B, T = self._sequence_features(batch, P)
+        head_pose = None
+        if self.config.eye_net_use_head_pose_input:
+            head_pose = torch.cat([batch['left_h'].reshape(B * T, 2), batch['right_h'].reshape(B * T, 2)], dim=0).float()
+        if self._stream_tail_fused_ok():
+            gaze, pupil, _ = k.eye_tail_stream_fwd(feats, head_pose, self._stream_tail_weights(P), states[0], reset)
+            gaze, pupil = gaze.view(2 * B * T, 2), pupil.view(2 * B * T)
+        else:
+            flat = [t for s_ in states for t in (s_ if isinstance(s_, tuple) else (s_,))]
+            if reset is not None:
+                for t in flat:
+                    k.stream_state_rows(t, t, reset)
+            gaze, pupil, out_states = self._tail(feats, head_pose, 2 * B, T, list(states) if states else None, P)
+            for buf, st in zip(states, out_states or []):
+                pairs = zip(buf, st) if isinstance(buf, tuple) else ((buf, st),)
+                for dst, src in pairs:
+                    k.stream_state_rows(src[:, -1], dst)
+        out = {}
+        for si, side in enumerate(('left', 'right')):
+            sl = slice(si * B * T, (si + 1) * B * T)
+            out[side + '_g_initial'] = gaze[sl].reshape(B, T, 2)
+            out[side + '_pupil_size'] = pupil[sl].reshape(B, T)
+        return out

@@ -1084,6 +1084,42 @@ class HipKernels(object):
                                              self._p(self._f32(bias, 'bias')), self._p(hs), self._p(cs), self._stream()))
         return hs, cs
 
+    # ------------------------------------------------------------------ streaming inference (eve_amd/stream.py)
+    def eye_tail_stream_fwd(self, feats, head_pose, weights, h, reset=None, want_hs=False):
+        """The EyeNet tail forward in one launch with the GRU state `h` [S, 128] float32 read and overwritten in place.
+        feats [S*T, 512] float32 (sequence-major), head_pose [S*T, 2]; weights: the 17 float32 tensors of eve_eye_tail_weights in
+        field order; reset: int32 [S] or None.  -> gaze [S, T, 2], pupil [S, T], hs [S, T, 128] or None."""
+        S = h.shape[0]
+        M = feats.shape[0]
+        T = M // S
+        assert tuple(h.shape) == (S, 128) and M == S * T and tuple(feats.shape) == (M, 512) and tuple(head_pose.shape) == (M, 2)
+        for t in (feats, head_pose, h) + tuple(weights):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda
+        assert reset is None or (reset.dtype == torch.int32 and reset.is_contiguous() and reset.numel() >= S)
+        assert len(weights) == len(_lib.EyeTailWeights._fields_)
+        w = _lib.EyeTailWeights(*[t.data_ptr() for t in weights])
+        dev = feats.device
+        gaze = torch.empty((S, T, 2), dtype=torch.float32, device=dev)
+        pupil = torch.empty((S, T), dtype=torch.float32, device=dev)
+        hs = torch.empty((S, T, 128), dtype=torch.float32, device=dev) if want_hs else None
+        self._ck(self.lib.eve_eye_tail_stream_fwd(S, T, self._p(feats), self._p(head_pose), ctypes.byref(w), self._p(h), self._p(reset),
+                                                  self._p(gaze), self._p(pupil), self._p(hs), self._stream()))
+        return gaze, pupil, hs
+
+    def stream_state_rows(self, src, dst, reset=None):
+        """dst[s] = 0 where reset[s] != 0, else src[s], for the S rows (dim 0) of two same-shape tensors whose rows are contiguous
+        (row strides may differ: `src` may be the last frame of a [S, T, ...] scan output).  In place when src is dst."""
+        S = dst.shape[0]
+        assert tuple(src.shape) == tuple(dst.shape) and src.dtype == dst.dtype and src.is_cuda and dst.is_cuda
+        row = dst[0].numel() if S else 0
+        for t in (src, dst):
+            assert t[0].is_contiguous() and (S == 1 or t.stride(0) >= row), 'stream_state_rows: rows must be contiguous'
+        assert reset is None or (reset.dtype == torch.int32 and reset.is_contiguous() and reset.numel() >= S and reset.is_cuda)
+        self._ck(self.lib.eve_stream_state_rows(dt_code(dst.dtype), S, row, src.stride(0) if S > 1 else row,
+                                                dst.stride(0) if S > 1 else row, ctypes.c_void_p(src.data_ptr()),
+                                                ctypes.c_void_p(dst.data_ptr()), self._p(reset), self._stream()))
+        return dst
+
     def cgru_gates1(self, g1, h):
         C = h.shape[-1]
         P = h.numel() // C

@@ -315,9 +315,80 @@ class RefineNet(nn.Module):
         output_dict['heatmap_final'] = y
 
     # ------------------------------------------------------------------ whole clips in one pass
-    def forward_sequence(self, heatmap_initial, screen_frame=None):
+    def _rnn_cells(self):
+        bott = self.network
+        while isinstance(bott, WrapEncoderDecoder):
+            bott = bott.between_module
+        return list(bott.rnn_cells) if self.config.refine_net_use_rnn else []
+
+    @staticmethod
+    def _use_scan(cells, hwc, dtype):
+        # one cell on the model's 5 x 8 x 64 bottleneck: the whole clip goes through it in ONE persistent launch (hidden state
+        # resident in LDS); CGRU in the 16-bit formats on cgru_scan.hip, CGRU in float32 and CRNN / CLSTM in any format on the
+        # float32 scans of cell_scan_f32.hip (round 5; the per-frame loop remains for stacked cells / other geometries)
+        return (len(cells) == 1 and tuple(hwc) == (5, 8, 64) and dispatch_flag(default_kernels(), 'cgru_scan', 1) != 0 and
+                dtype in HALF_DTYPES + (torch.float32,))
+
+    def _carried_dtypes(self):
+        """Per cell, the dtype(s) the bottleneck carries its state in (internal NHWC layout [B, 5, 8, C]): the float32 scans keep
+        CRNN / CLSTM states in float32, everything else is in the compute dtype.  A tuple of two for CLSTM."""
+        cells, dt = self._rnn_cells(), self.compute_dtype
+        hwc = (5, 8, pad_channels(self.config.refine_net_num_features, dt))
+        scan = self._use_scan(cells, hwc, dt)
+        out = []
+        for cell in cells:
+            sdt = torch.float32 if scan and not isinstance(cell, CGRUCell) else dt
+            out.append((sdt, sdt) if isinstance(cell, CLSTMCell) else sdt)
+        return out
+
+    def _initial_states_in(self, initial_states):
+        """initial_states: None, or one entry per cell -- a state (a pair for CLSTM) in the reference layout [B, C, 5, 8] (what
+        `forward` / `forward_sequence` return) or in the internal NHWC layout [B, 5, 8, C] (EVEStream's carried buffers), or
+        None for a zero state.  -> per cell the internal-layout tensor(s) in the dtype the bottleneck carries."""
+        if initial_states is None:
+            return None
+        dts = self._carried_dtypes()
+        assert len(initial_states) == len(dts), 'initial_states: one entry per RefineNet cell (%d)' % len(dts)
+        C = self.config.refine_net_num_features
+
+        def one(t, sdt):
+            if t.dim() == 4 and t.shape[1] == C and tuple(t.shape[2:]) == (5, 8) and t.shape[-1] != C:
+                t = self._state_in(t)                       # reference NCHW -> NHWC, compute dtype
+            return t if t.dtype == sdt and t.is_contiguous() else t.to(sdt).contiguous()
+
+        out = []
+        for st, sdt in zip(initial_states, dts):
+            if st is None:
+                out.append(None)
+            elif isinstance(sdt, tuple):
+                out.append(tuple(one(t, d) for t, d in zip(st, sdt)))
+            else:
+                out.append(one(st, sdt))
+        return out
+
+    def forward_sequence(self, heatmap_initial, screen_frame=None, initial_states=None):
         """heatmap_initial [B,T,1,h,w], screen_frame [B,T,3,H,W] -> (heatmap_final [B,T,1,H,W],
-        list over cells of the stacked states [B,T,C,5,8] (tuple of two for CLSTM))."""
+        list over cells of the stacked states [B,T,C,5,8] (tuple of two for CLSTM)).
+        initial_states: None (zero states), or per cell the state before the first frame -- reference layout [B, C, 5, 8] as
+        returned here (the last frame of a previous call), or the internal NHWC layout [B, 5, 8, C]; (h, c) for CLSTM."""
+        hf, scan, raw, to_ref = self._sequence(heatmap_initial, screen_frame, self._initial_states_in(initial_states))
+        if scan:
+            cell, st = self._rnn_cells()[0], raw[0]
+            return hf, [tuple(to_ref(t) for t in st) if isinstance(cell, CLSTMCell) else to_ref(st)]
+        hist = raw
+        stacked = []
+        for i in range(len(hist[0]) if hist else 0):
+            per_t = [self._state_out(h[i]) for h in hist]
+            if isinstance(per_t[0], tuple):
+                stacked.append(tuple(torch.stack([p[j] for p in per_t], dim=1) for j in range(2)))
+            else:
+                stacked.append(torch.stack(per_t, dim=1))
+        return hf, stacked
+
+    def _sequence(self, heatmap_initial, screen_frame, h0):
+        """The clip pass behind forward_sequence.  h0: None or per cell the internal-layout initial state (_initial_states_in).
+        Returns (heatmap_final [B,T,1,H,W], scan, raw, to_ref): with `scan` raw is the single cell's per-frame states [B,T,5,8,C]
+        (a pair for CLSTM), otherwise raw is the per-frame list of per-cell states; to_ref converts [B,T,5,8,C] to [B,T,C,5,8]."""
         P = self._get_packs()
         B, T = heatmap_initial.shape[:2]
         if screen_frame is not None and screen_frame.dtype == torch.uint8:     # decoded frames [B,T,H,W,3]: normalise here
@@ -328,47 +399,57 @@ class RefineNet(nn.Module):
         x, skips, prefix = self._encode(x, P)
         C = x.shape[-1]
         xs = x.view(B, T, x.shape[1], x.shape[2], C)
-        bott = self.network
-        while isinstance(bott, WrapEncoderDecoder):
-            bott = bott.between_module
-        cells = list(bott.rnn_cells) if self.config.refine_net_use_rnn else []
-        # one cell on the model's 5 x 8 x 64 bottleneck: the whole clip goes through it in ONE persistent launch (hidden state
-        # resident in LDS); CGRU in the 16-bit formats on cgru_scan.hip, CGRU in float32 and CRNN / CLSTM in any format on the
-        # float32 scans of cell_scan_f32.hip (round 5; the per-frame loop below remains for stacked cells / other geometries)
-        scan = (len(cells) == 1 and tuple(xs.shape[2:]) == (5, 8, 64) and dispatch_flag(default_kernels(), 'cgru_scan', 1) != 0 and
-                xs.dtype in HALF_DTYPES + (torch.float32,))
-        if scan:
+        cells = self._rnn_cells()
+        h5, w5 = x.shape[1], x.shape[2]
+        to_ref = lambda t: ops.FromNHWCFn.apply(t.reshape(B * T, h5, w5, C), C).view(B, T, C, h5, w5)
+        if self._use_scan(cells, xs.shape[2:], xs.dtype):
             cell, name = cells[0], '%s.rnn_cells.0' % prefix
-            h5, w5 = x.shape[1], x.shape[2]
-            to_ref = lambda t: ops.FromNHWCFn.apply(t.reshape(B * T, h5, w5, C), C).view(B, T, C, h5, w5)
+            init = h0[0] if h0 is not None else None
             if isinstance(cell, CGRUCell):
                 hs = ops.CGRUScanFn.apply(xs.contiguous(), cell.gates_1.weight, cell.gates_1.bias, cell.gate_2.weight,
-                                          cell.gate_2.bias, None, P[name + '.gates_1'], P[name + '.gate_2'])
-                states = [to_ref(hs)]
+                                          cell.gate_2.bias, init, P[name + '.gates_1'], P[name + '.gate_2'])
+                raw = [hs]
             elif isinstance(cell, CRNNCell):
-                hs = ops.CRNNScanFn.apply(xs.float(), cell.cell.weight, cell.cell.bias, None, P[name + '.cell'])
-                states = [to_ref(hs)]
+                hs = ops.CRNNScanFn.apply(xs.float(), cell.cell.weight, cell.cell.bias, init, P[name + '.cell'])
+                raw = [hs]
                 hs = hs.to(xs.dtype)
             else:                       # CLSTM: the state is computed and stored, the features pass through (refine_net.py:168-174)
-                hcs = ops.clstm_scan(xs, cell.gates.weight, cell.gates.bias, P[name + '.gates'])
-                states = [tuple(to_ref(t) for t in hcs)]
+                h_init, c_init = init if init is not None else (None, None)
+                hcs = ops.clstm_scan(xs, cell.gates.weight, cell.gates.bias, P[name + '.gates'], h_init, c_init)
+                raw = [tuple(hcs)]
                 hs = xs
             x = self._tap('rnn', hs.reshape(B * T, h5, w5, C))
             hf = self._decode(x, skips, P)
-            return hf.view(B, T, 1, hf.shape[2], hf.shape[3]), states
-        else:
-            outs, states, hist = [], None, []
-            for t in range(T):
-                xt, states = self._bottleneck(xs[:, t].contiguous(), states, prefix, P)
-                outs.append(xt)
-                hist.append(states)
-            x = torch.stack(outs, dim=1).view(B * T, x.shape[1], x.shape[2], C)
+            return hf.view(B, T, 1, hf.shape[2], hf.shape[3]), True, raw, to_ref
+        outs, states, hist = [], h0, []
+        for t in range(T):
+            xt, states = self._bottleneck(xs[:, t].contiguous(), states, prefix, P)
+            outs.append(xt)
+            hist.append(states)
+        x = torch.stack(outs, dim=1).view(B * T, x.shape[1], x.shape[2], C)
         hf = self._decode(x, skips, P)
-        stacked = []
-        for i in range(len(hist[0]) if hist else 0):
-            per_t = [self._state_out(h[i]) for h in hist]
-            if isinstance(per_t[0], tuple):
-                stacked.append(tuple(torch.stack([p[j] for p in per_t], dim=1) for j in range(2)))
-            else:
-                stacked.append(torch.stack(per_t, dim=1))
-        return hf.view(B, T, 1, hf.shape[2], hf.shape[3]), stacked
+        return hf.view(B, T, 1, hf.shape[2], hf.shape[3]), False, hist, to_ref
+
+    # ------------------------------------------------------------------ streaming (eve_amd/stream.py)
+    def _stream_state_buffers(self, B, device):
+        """Zero-initialised carried states for B streams, one per cell (a pair for CLSTM), in the internal layout and dtype."""
+        C = pad_channels(self.config.refine_net_num_features, self.compute_dtype)
+        z = lambda dt: torch.zeros((B, 5, 8, C), dtype=dt, device=device)
+        return [tuple(z(d) for d in dt) if isinstance(dt, tuple) else z(dt) for dt in self._carried_dtypes()]
+
+    def _stream_sequence(self, heatmap_initial, screen_frame, buffers, reset=None):
+        """One chunk of a stream: the carried states `buffers` (from _stream_state_buffers) are zeroed where reset[b] != 0, used
+        as the initial states, and overwritten with the chunk's last frame -- one eve_stream_state_rows launch each way, no
+        conversion.  -> heatmap_final [B,T,1,H,W]."""
+        k = default_kernels()
+        flat = [t for b in buffers for t in (b if isinstance(b, tuple) else (b,))]
+        if reset is not None:
+            for t in flat:
+                k.stream_state_rows(t, t, reset)
+        hf, scan, raw, _ = self._sequence(heatmap_initial, screen_frame, buffers if buffers else None)
+        lasts = raw if scan else (raw[-1] if raw else [])
+        for buf, st in zip(buffers, lasts):
+            pairs = zip(buf, st) if isinstance(buf, tuple) else ((buf, st),)
+            for dst, src in pairs:
+                k.stream_state_rows(src[:, -1] if scan else src, dst)
+        return hf

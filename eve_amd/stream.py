@@ -1,0 +1,207 @@
+"""EVEStream: EVE inference over videos longer than one clip, and over live cameras, with both networks' recurrent states
+carried from one call to the next.
+
+    stream = eve_amd.EVEStream(model, num_streams=B)      # model: an eve_amd.EVE in eval mode
+    out = stream.step(chunk)                               # chunk: dict of [B, Tc, ...] GPU tensors, any Tc >= 1
+    stream.reset([3])                                      # stream 3 starts from zero state at the next step()
+    st = stream.get_state(); stream.set_state(st)          # reference layout, e.g. to resume a recording
+
+For any split of a clip into chunks the concatenated outputs equal one eval pass of the whole clip from zero state
+(EVE.forward with output_predictions): EyeNet's GRU / RNN / LSTM state and RefineNet's conv-RNN state are the only coupling
+between frames, and they are handed from the last frame of one chunk to the first of the next.
+
+The carried states live in fixed device buffers in the modules' own layout and dtype (EyeNet [2B, H] float32, the left eyes'
+rows then the right ones'; RefineNet [B, 5, 8, C] NHWC), so a step converts nothing.  Each is zeroed where reset and committed
+from the chunk's last frame by eve_stream_state_rows.  (EyeNet.stream_fused_tail runs the shipped EyeNet tail as one
+eve_eye_tail_stream_fwd launch that updates its GRU state in place; it measured slower, so it is off by default.)
+
+With use_graph (the default) each distinct chunk shape is captured once into a hipGraph on one stream and replayed; the
+chunk is copied into the graph's input buffers first.  Resets are device flags written by the host before the replay.  A
+changed weight (load_state_dict, an optimiser step through torch) is detected through the parameters' versions, as the
+modules' weight packs are, and the graphs are captured again.  Weights changed behind torch's back (a fused optimiser
+kernel) need invalidate(), as the modules need invalidate_packs().
+"""
+import numpy as np
+import torch
+
+from .kernels import default_kernels
+
+_WARMUP_STREAMS = {}
+
+
+def _module_key(m):
+    return (m.compute_dtype,) + tuple((p.data_ptr(), p._version) for p in m.parameters())
+
+
+class EVEStream(object):
+    def __init__(self, model, num_streams, use_graph=True):
+        if model.training:
+            raise ValueError('EVEStream runs inference only: call model.eval() first')
+        self.model = model
+        self.num_streams = B = int(num_streams)
+        if B < 1:
+            raise ValueError('num_streams must be >= 1')
+        self.device = next(model.parameters()).device
+        if use_graph and self.device.type != 'cuda':
+            raise ValueError('use_graph=True needs the model on the GPU')
+        self.use_graph = bool(use_graph)
+        self._eye = model.eye_net._stream_state_buffers(B, self.device)
+        self._ref = model.refine_net._stream_state_buffers(B, self.device) if model.refine_net is not None else []
+        self._flags = torch.zeros((2 * B,), dtype=torch.int32, device=self.device)   # stream b's reset flag at b and B + b
+        self._flags_set = False
+        self._pending = None                     # host bool [B]: resets requested for the next step
+        self._graphs = {}
+        self._graphs_key = None
+
+    # ------------------------------------------------------------------ state
+    def _state_tensors(self):
+        return [t for s_ in self._eye + self._ref for t in (s_ if isinstance(s_, tuple) else (s_,))]
+
+    def reset(self, streams=None):
+        """Start the given streams (None = all; else indices, or a bool mask of length num_streams) from zero state at the
+        next step().  Resets requested before one step accumulate."""
+        B = self.num_streams
+        m = np.zeros(B, dtype=bool) if self._pending is None else self._pending
+        if streams is None:
+            m[:] = True
+        else:
+            a = streams.detach().cpu().numpy() if torch.is_tensor(streams) else np.asarray(streams)
+            if a.dtype == bool:
+                if a.shape != (B,):
+                    raise ValueError('reset: a mask needs num_streams (%d) entries' % B)
+                m |= a
+            else:
+                idx = a.astype(np.int64).reshape(-1)
+                if idx.size and (idx.min() < -B or idx.max() >= B):
+                    raise IndexError('reset: stream index out of range')
+                m[idx] = True
+        self._pending = m
+
+    def get_state(self):
+        """The carried states in the reference layout (fresh tensors): {left,right}_eye_rnn_states_<i> [B, H] float32 ((h, c) for
+        LSTM) and refinenet_rnn_states_<i> [B, C, 5, 8] float32 ((h, c) for CLSTM).  Resets not yet applied by a step are not
+        reflected."""
+        B = self.num_streams
+        st = {}
+        for i, buf in enumerate(self._eye):
+            for si, side in enumerate(('left', 'right')):
+                cut = lambda t: t[si * B:(si + 1) * B].clone()
+                st['%s_eye_rnn_states_%d' % (side, i)] = tuple(cut(t) for t in buf) if isinstance(buf, tuple) else cut(buf)
+        if self._ref:
+            C = self.model.config.refine_net_num_features
+            ref = lambda t: t[..., :C].permute(0, 3, 1, 2).float().contiguous()
+            for i, buf in enumerate(self._ref):
+                st['refinenet_rnn_states_%d' % i] = tuple(ref(t) for t in buf) if isinstance(buf, tuple) else ref(buf)
+        return st
+
+    def set_state(self, state):
+        """Load states in get_state()'s layout (every key it returns); cancels resets requested since the last step."""
+        B = self.num_streams
+        for i, buf in enumerate(self._eye):
+            for si, side in enumerate(('left', 'right')):
+                v = state['%s_eye_rnn_states_%d' % (side, i)]
+                for dst, src in (zip(buf, v) if isinstance(buf, tuple) else ((buf, v),)):
+                    dst[si * B:(si + 1) * B].copy_(src)
+        if self._ref:
+            C = self.model.config.refine_net_num_features
+            for i, buf in enumerate(self._ref):
+                v = state['refinenet_rnn_states_%d' % i]
+                for dst, src in (zip(buf, v) if isinstance(buf, tuple) else ((buf, v),)):
+                    if tuple(src.shape) != (B, C, dst.shape[1], dst.shape[2]):
+                        raise ValueError('set_state: refinenet_rnn_states_%d must be [%d, %d, %d, %d]' % (i, B, C, dst.shape[1], dst.shape[2]))
+                    dst[..., :C].copy_(src.permute(0, 2, 3, 1))
+        self._pending = None
+
+    # ------------------------------------------------------------------ steps
+    def _upload_resets(self):
+        if self._pending is None or not self._pending.any():
+            self._pending = None
+            return
+        m = np.concatenate([self._pending, self._pending]).astype(np.int32)
+        host = torch.from_numpy(m)
+        if self.device.type == 'cuda':
+            # a pinned block of torch's host allocator: the copy is asynchronous and the block is not reused before it has run
+            host = host.pin_memory()
+        self._flags.copy_(host, non_blocking=True)
+        self._flags_set = True
+        self._pending = None
+
+    def _run(self, chunk, return_heatmaps):
+        return self.model._predict_sequence(chunk, self._eye, self._ref, reset=self._flags, return_heatmaps=return_heatmaps)
+
+    def step(self, chunk, return_heatmaps=False):
+        """One chunk of every stream: chunk holds [B, Tc, ...] tensors on the model's device -- the eye patches (float NCHW or
+        uint8 NHWC), {left,right}_h, {left,right}_o, {left,right}_R, head_R, camera_transformation, inv_camera_transformation,
+        pixels_per_millimeter, millimeters_per_pixel, and screen_frame when the config loads screen content.  Returns the
+        prediction keys of EVE(output_predictions=True) as [B, Tc, ...] tensors (heatmap_final [B, Tc, 1, H, W] on request).
+        With use_graph the returned tensors are the graph's output buffers: valid until the next step() of the same chunk
+        shape (clone what you keep).  The host does not wait for the device, except when a new chunk shape is captured."""
+        if self.model.training:
+            raise ValueError('EVEStream runs inference only: the model was switched to training mode')
+        if chunk['left_eye_patch'].shape[0] != self.num_streams:
+            raise ValueError('chunk has %d streams, the EVEStream %d' % (chunk['left_eye_patch'].shape[0], self.num_streams))
+        self._upload_resets()
+        with torch.no_grad():
+            if self.use_graph:
+                entry = self._graph_for(chunk, bool(return_heatmaps))
+                for key, buf in entry['inputs'].items():
+                    buf.copy_(chunk[key], non_blocking=True)
+                entry['graph'].replay()
+                out = dict(entry['outputs'])
+            else:
+                out = self._run(chunk, return_heatmaps)
+        if self._flags_set:
+            self._flags.zero_()
+            self._flags_set = False
+        return out
+
+    # ------------------------------------------------------------------ graphs
+    def invalidate(self):
+        """Drop every captured graph (and the modules' packs): for weights changed without torch seeing it."""
+        self._graphs = {}
+        self.model.eye_net.invalidate_packs()
+        if self.model.refine_net is not None:
+            self.model.refine_net.invalidate_packs()
+
+    def _weights_key(self):
+        return tuple(_module_key(m) for m in (self.model.eye_net, self.model.refine_net) if m is not None)
+
+    def _graph_for(self, chunk, return_heatmaps):
+        wk = self._weights_key()
+        if wk != self._graphs_key:               # new weights: new packs, new graphs (a replay never reads stale packs)
+            self._graphs = {}
+            self._graphs_key = wk
+        key = (return_heatmaps,) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
+        entry = self._graphs.get(key)
+        if entry is None:
+            entry = self._graphs[key] = self._capture(chunk, return_heatmaps)
+            self._graphs_key = self._weights_key()
+        return entry
+
+    def _capture(self, chunk, return_heatmaps):
+        """Capture one step for this chunk shape (train.Trainer._capture's recipe): inputs copied into fixed buffers, two eager
+        warm-up steps off the default stream (packs, lazily built filters, allocator) with the carried states put back
+        afterwards, the kernels' scratch allocated before the capture, one stream, no side branches."""
+        static = {k_: v.clone() for k_, v in chunk.items() if torch.is_tensor(v)}
+        dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        side = _WARMUP_STREAMS.get(dev_index)
+        if side is None:
+            side = _WARMUP_STREAMS[dev_index] = torch.cuda.Stream(device=dev_index)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            snap = [t.clone() for t in self._state_tensors()]
+            for _ in range(2):
+                self._run(static, return_heatmaps)
+            for t, s_ in zip(self._state_tensors(), snap):
+                t.copy_(s_)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        k = default_kernels()
+        if hasattr(k, 'prepare_graph_workspace'):
+            k.prepare_graph_workspace(self.device)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            out = self._run(static, return_heatmaps)
+        m = self.model
+        keep = (m.eye_net._packs, getattr(m.eye_net, '_stream_w', None), m.refine_net._packs if m.refine_net is not None else None)
+        return {'graph': graph, 'inputs': static, 'outputs': out, 'keep': keep}

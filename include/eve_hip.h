@@ -584,6 +584,36 @@ int eve_adam_step(long long n, float* p, const float* g, float* m, float* v, con
                   float weight_decay, int step, eve_adam_guard* guard, int check_finite, const float* lr_dev,
                   const float* poison, eve_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Streaming inference (eve_amd/stream.py: EVEStream carries both networks' recurrent states across calls; forward only).
+ * ------------------------------------------------------------------------------------------------ */
+/* The float32 packs of the EyeNet tail (eye_net.py:109-146 of the shipped configuration: GRU, one cell, H = 128, head-pose
+ * input), each weight as [in][out] (the PackedWeight IHWO of a 1x1 layer).                                                   */
+typedef struct eve_eye_tail_weights {
+    const float* fc_w;  const float* fc_b;   /* cnn_layers.fc  [512][128], [128]                                             */
+    const float* c0_w;  const float* c0_b;   /* fc_common.0    [>= 130][128] (rows 128, 129: head pose), [128]               */
+    const float* c2_w;  const float* c2_b;   /* fc_common.2    [128][128], [128]                                             */
+    const float* ih_w;  const float* ih_b;   /* rnn_cells.0    W_ih^T [128][384], b_ih [384] (gate order r, z, n)            */
+    const float* hh_w;  const float* hh_b;   /*                W_hh^T [128][384], b_hh [384]                                 */
+    const float* g0_w;  const float* g0_b;   /* fc_to_gaze.0   [128][128], [128]                                             */
+    const float* g2_w;                       /* fc_to_gaze.2   [128][4] (columns 2, 3 unused), no bias                       */
+    const float* p0_w;  const float* p0_b;   /* fc_to_pupil.0  [128][128], [128]                                             */
+    const float* p2_w;  const float* p2_b;   /* fc_to_pupil.2  [128][4] (column 0), [1]                                      */
+} eve_eye_tail_weights;
+/* The whole EyeNet tail forward in ONE launch, the GRU state read and written in place: fc -> [. | head pose] -> fc_common
+ * (SELU) -> GRU input projection -> the recurrence -> fc_to_gaze (SELU, tanh, x pi/2) and fc_to_pupil (SELU, ReLU).
+ * feats [S][T][512] float32 (eve_avgpool_fwd_f32's output; 16-byte aligned), head_pose [S][T][2]; h [S][128] in/out: the state
+ * before the first frame, overwritten with the state after the last; reset int [S] or NULL: rows with reset[s] != 0 start
+ * from zero instead.  Outputs gaze [S][T][2] (rad), pupil [S][T], hs [S][T][128] or NULL.  Any T (sub-chunks of 16 frames
+ * inside the kernel).  One workgroup per sequence.                                                                          */
+int eve_eye_tail_stream_fwd(int S, int T, const float* feats, const float* head_pose, const eve_eye_tail_weights* weights,
+                            float* h, const int* reset, float* gaze, float* pupil, float* hs, eve_stream_t stream);
+/* Per-stream state hand-over: dst[s][i] = (reset && reset[s]) ? 0 : src[s][i] for s < S, i < row_elems; row strides in
+ * elements (>= row_elems); dtype f32 / bf16 / f16 (bit copies).  In place (src == dst) it applies resets before a step; from
+ * a scan's last frame (hs + (T-1) * row) into a state buffer it commits the step.  src and dst are equal or disjoint.        */
+int eve_stream_state_rows(int dtype, int S, long long row_elems, long long src_stride, long long dst_stride, const void* src,
+                          void* dst, const int* reset, eve_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,74 @@
+#!/usr/bin/env python
+"""Device time per EVEStream.step under hipGraph replay (eve_amd/stream.py), the shipped refine_net.json pipeline (GRU EyeNet,
+CLSTM RefineNet), synthetic weights and clips.  One JSON line per shape:
+
+    python tools/bench_stream.py --shapes 1x1 32x1 32x30 [--dtype bf16] [--steps 50] [--fused-tail]
+
+B x Tc = streams x frames per step.  For Tc > 1 the same clips also go through one EVE.eval() pass (`eval_ms`): what the
+stream costs over the plain clip pass.  --fused-tail runs the EyeNet tail as one eve_eye_tail_stream_fwd launch
+(EyeNet.stream_fused_tail) instead of layer by layer: the A/B of the fused kernel, e.g. under `rocprofv3 --kernel-trace --stats`."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+import eve_amd  # noqa: E402
+from eve_amd import synthetic as detweights  # noqa: E402
+
+DTYPES = {'fp32': torch.float32, 'bf16': torch.bfloat16, 'fp16': torch.float16}
+INPUT_KEYS = ('left_eye_patch', 'right_eye_patch', 'left_h', 'right_h', 'left_o', 'right_o', 'left_R', 'right_R', 'head_R',
+              'camera_transformation', 'inv_camera_transformation', 'pixels_per_millimeter', 'millimeters_per_pixel', 'screen_frame')
+
+
+def device_ms(fn, steps):
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(steps):
+        fn()
+    end.record()
+    torch.cuda.synchronize()
+    return start.elapsed_time(end) / steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--shapes', nargs='+', default=['1x1', '32x1', '32x30'])
+    ap.add_argument('--dtype', default='bf16', choices=sorted(DTYPES))
+    ap.add_argument('--steps', type=int, default=50)
+    ap.add_argument('--fused-tail', action='store_true')
+    args = ap.parse_args()
+    cfg = eve_amd.reset_standalone_config()
+    cfg.import_json(os.path.join(REPO, 'configs', 'refine_net.json'))
+    cfg.import_dict({'eye_net_load_pretrained': False})
+    model = eve_amd.EVE(output_predictions=True)
+    model.eye_net.compute_dtype = model.refine_net.compute_dtype = DTYPES[args.dtype]
+    detweights.fill_module(model.eye_net, 0)
+    detweights.fill_module(model.refine_net, 1)
+    model = model.cuda().eval()
+    model.eye_net.stream_fused_tail = args.fused_tail
+    for shape in args.shapes:
+        B, Tc = (int(v) for v in shape.split('x'))
+        small = detweights.eve_batch(min(B, 4), Tc, seed=1)
+        full = {k: torch.cat([v] * ((B + 3) // 4), dim=0)[:B].contiguous().cuda() for k, v in small.items()}
+        clip = {k: full[k] for k in INPUT_KEYS if k in full}
+        stream = eve_amd.EVEStream(model, B)
+        for _ in range(3):
+            stream.step(clip)                                # capture + warm replays
+        torch.cuda.synchronize()
+        res = {'B': B, 'Tc': Tc, 'dtype': args.dtype, 'tail': 'fused' if args.fused_tail else 'layers',
+               'step_ms': round(device_ms(lambda: stream.step(clip), args.steps), 4)}
+        res['us_per_frame'] = round(1e3 * res['step_ms'] / (B * Tc), 3)
+        if Tc > 1:
+            with torch.no_grad():
+                for _ in range(2):
+                    model(dict(full))
+                res['eval_ms'] = round(device_ms(lambda: model(dict(full)), max(5, args.steps // 5)), 4)
+        print(json.dumps(res), flush=True)
+
+
+if __name__ == '__main__':
+    main()
