@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- train-step frames/s of the EVE hot path on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
           --master-port P bench.py --gpus N --steps K --warmup W)
 
@@ -11,12 +11,15 @@ backward, [gradient all-reduce], global-norm clip and Adam.  The workload is BAS
 ("EyeNet training on 1xMI355X, bf16, B=32 clips of T=30 synthetic frames"), weak scaling: every rank
 processes its own B=32 clips.  frames/s = world * B * T / max-over-ranks step time.
 
-Printed JSON (rank 0, one line) also carries
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, [dump the outputs], print the
+line.  With --full the printed JSON (rank 0, one line) also carries
   roofline     -- the dominant kernel group, its algorithmic FLOP/s from HIP events recorded around
-                  every launch in the timed region, against the dense bf16 MFMA peak;
+                  every launch of extra eager steps after the timed region, against the dense bf16 MFMA peak;
   cpu_baseline -- the CPU oracle (plain-torch restatement of the reference, oracle/) running the same
                   train step on this host's cores on a bounded sample (B=2 clips), reported only;
-  summary      -- ms per step, frames/s and roofline fraction of every extra operating point.
+  summary      -- ms per step, frames/s and roofline fraction of every extra operating point (configs[2] with the CGRU
+                  and the CLSTM cell, configs[4], B=8, fp32, fp16), each measured in runs of its own after the main one;
+the --no-* options leave parts of that out.
 The line stays short (a few KB); the per-kernel maps and the full objects of the extra operating points go to
 --detail-json FILE.  --dump-outputs DIR writes what the last timed step returned (loss terms, per-frame outputs) as DIR/<name>.npy;
 that step then starts from the seeded initial state, so two runs with the same arguments write the same values up to rounding.
@@ -403,7 +406,7 @@ def dump_outputs(terms, out_dir, limit_bytes=DUMP_LIMIT_BYTES):
         np.save(os.path.join(out_dir, name.replace('/', '_') + '.npy'), a)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=10)
@@ -416,6 +419,10 @@ def main():
     ap.add_argument('--seq', type=int, default=None)
     ap.add_argument('--size', type=int, default=None)
     ap.add_argument('--dtype', default=None, choices=['bf16', 'fp16', 'fp32'])
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: the per-kernel roofline, the extra operating points '
+                         '(configs[2], configs[4], B=8, fp32, fp16) and the CPU oracle baselines; the --no-* options below '
+                         'leave parts of it out again')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-graph', action='store_true', help='launch every kernel eagerly instead of replaying a hipGraph')
@@ -430,13 +437,20 @@ def main():
                     help='write the arrays the last timed step returned (loss terms, per-frame outputs) as DIR/<name>.npy (float64)')
     ap.add_argument('--detail-json', metavar='FILE', default=None,
                     help='write the full result object (per-kernel maps, every operating point) to FILE')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     c5 = args.workload == 'c5'
     args.batch = args.batch if args.batch is not None else (8 if c5 else 32)
     args.seq = args.seq if args.seq is not None else (120 if c5 else 30)
     args.size = args.size if args.size is not None else (256 if c5 else 128)
     args.dtype = args.dtype if args.dtype is not None else ('fp16' if c5 else 'bf16')
+    if not args.full:
+        # a plain run measures the headline figure alone: no profiled steps, no other operating point, no CPU baseline
+        args.no_roofline = args.no_c3 = args.no_c5 = args.no_points = args.no_cpu_baseline = True
+    return args
 
+
+def main():
+    args = parse_args()
     if args.graph_collectives:
         os.environ['EVE_AMD_GRAPH_COLLECTIVES'] = '1'
     import eve_amd

@@ -10,7 +10,7 @@ if [ "$1" = "tests" ]; then
   (cd $R && timeout 3000 python -m pytest tests -m gpu -q -x 2>&1 | tail -30 > $O/pytest_gpu.log)
 fi
 # kernel stats (7 steps in the EyeNet trace incl. warm-up / capture; tools/kstats.py divides by the adam_kernel count)
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_bench -o b --output-format csv -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-c3 --no-c5 --no-points > $O/bench_profiled.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_bench -o b --output-format csv -- python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-c3 --no-c5 --no-points > $O/bench_profiled.log 2>&1
 cp $(find $O/prof_bench -name "*kernel_stats.csv" | head -1) $O/bench_kernel_stats.csv
 timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_c3 -o c --output-format csv -- python $R/tools/bench_eve.py --steps 5 > $O/c3_profiled.log 2>&1
 cp $(find $O/prof_c3 -name "*kernel_stats.csv" | head -1) $O/eve_c3_kernel_stats.csv
@@ -28,11 +28,11 @@ rm -rf $O/pmc_b_* $O/pmc_c_*
 RN=${ROUND:-r06}
 cp $O/pmc_hbm_per_kernel.json profiles/${RN}_pmc_hbm_per_kernel.json
 cp $O/c3_pmc_hbm_per_kernel.json profiles/${RN}_c3_pmc_hbm_per_kernel.json
-python bench.py > $O/bench.json 2> $O/bench.err
-python bench.py --batch 8 --no-cpu-baseline --no-c3 --no-c5 --no-points > $O/bench_b8.json 2>> $O/bench.err
-python bench.py --dtype fp16 --no-cpu-baseline --no-c3 --no-c5 --no-points > $O/bench_fp16.json 2>> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
+python bench.py --full --batch 8 --no-cpu-baseline --no-c3 --no-c5 --no-points > $O/bench_b8.json 2>> $O/bench.err
+python bench.py --full --dtype fp16 --no-cpu-baseline --no-c3 --no-c5 --no-points > $O/bench_fp16.json 2>> $O/bench.err
 # configs[4] as its own line + kernel stats (T = 120, 256 x 256, fp16, both networks trained, B = 8)
-python bench.py --workload c5 --steps 3 --warmup 2 --no-cpu-baseline > $O/bench_c5.json 2>> $O/bench.err
+python bench.py --full --workload c5 --steps 3 --warmup 2 --no-cpu-baseline > $O/bench_c5.json 2>> $O/bench.err
 (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $O/prof_c5 -o c --output-format csv -- python $R/bench.py --workload c5 --steps 2 --warmup 1 --no-cpu-baseline --no-roofline > $O/c5_profiled.log 2>&1)
 cp $(find $O/prof_c5 -name "*kernel_stats.csv" | head -1) $O/c5_kernel_stats.csv; rm -rf $O/prof_c5
 # one-rank RCCL group: eager launches vs hipGraph replay + eager collectives vs collectives captured, B = 8 and B = 32
