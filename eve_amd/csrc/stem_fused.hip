@@ -71,6 +71,42 @@ __device__ __forceinline__ float sf_row_sum16(float v) {          // butterfly o
 }
 __device__ __forceinline__ float sf_fmax3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 
+// Plane statistics from SHIFTED sums (a plain E[v^2] - E[v]^2 in float loses (mean / sigma)^2 x 6e-8 of the variance: a dark or
+// over-exposed patch gives a DC response of hundreds of standard deviations).  A lane sums d = v - k and d^2 about a shift k taken
+// from the plane's values -- convolution column 2 li + 32 (never in the zero padding; the pairs kernel takes column 32 for all
+// lanes of a channel) of the first row of a segment, moved to row 2 (the first whose window misses the padding rows) with
+// S' = S + n e,  Q' = Q + e (2 S + n e),  e = k_old - k_new.  The lanes' sums
+// become (mean, M2) pairs that are merged pairwise (Chan et al.), each merge symmetric in its operands so that the 16 lanes of a
+// row end with the same bits.
+__device__ __forceinline__ void sf_recentre(float& k, float& s, float& q, float k_new, float n) {
+    const float e = k - k_new;
+    q = __builtin_fmaf(e, __builtin_fmaf(n, e, 2.f * s), q);
+    s = __builtin_fmaf(n, e, s);
+    k = k_new;
+}
+__device__ __forceinline__ void sf_lane_moments(float k, float s, float q, float inv_n, float& m, float& m2) {
+    m = __builtin_fmaf(s, inv_n, k);
+    m2 = __builtin_fmaf(-s, s * inv_n, q);
+}
+// (mean, M2) of two parts of n values each -> of the 2n values
+__device__ __forceinline__ void sf_merge_moments(float ma, float m2a, float mb, float m2b, float n, float& m, float& m2) {
+    const float d = mb - ma;
+    m2 = __builtin_fmaf(d * (0.5f * n), d, m2a + m2b);
+    m = 0.5f * (ma + mb);
+}
+template <int CTRL>
+__device__ __forceinline__ void sf_moments_step(float& m, float& m2, float n) {
+    const float mb = __builtin_bit_cast(float, sf_dpp<CTRL>(0u, __builtin_bit_cast(uint32_t, m)));
+    const float m2b = __builtin_bit_cast(float, sf_dpp<CTRL>(0u, __builtin_bit_cast(uint32_t, m2)));
+    sf_merge_moments(m, m2, mb, m2b, n, m, m2);
+}
+__device__ __forceinline__ void sf_row_moments16(float& m, float& m2, float n) {   // n values per lane -> 16 n in every lane
+    sf_moments_step<0xb1>(m, m2, n);              // quad_perm [1,0,3,2]
+    sf_moments_step<0x4e>(m, m2, 2.f * n);        // quad_perm [2,3,0,1]
+    sf_moments_step<0x141>(m, m2, 4.f * n);       // row_half_mirror
+    sf_moments_step<0x140>(m, m2, 8.f * n);       // row_mirror
+}
+
 // Filter bank fill shared by the forward and backward kernels.  LDS row c_lds = nt*16 + 4*g + r holds output
 // channel co = g*16 + nt*4 + r, so that an MFMA lane (rows 4g..4g+3 of tiles nt = 0..3) owns the 16 CONSECUTIVE
 // channels g*16 .. g*16+15 of its pixel: 32-byte stores instead of four 8-byte ones.  64-byte rows, chunk-swizzled
@@ -177,12 +213,12 @@ __global__ __launch_bounds__(64 * SF_WAVES) void stem_fwd_fused_kernel(const int
         }
         const int img_off = n * rows * SF_XROW;
         for (int r = 0; r < 9; ++r) sf_stage_row(rs, ring, 2 * oy_first + r, rows, img_off, lane);
-        float S[4][4], Q[4][4];
+        float S[4][4], Q[4][4], K[4][4];
         uint32_t M[2][4][4];
 #pragma unroll
         for (int a = 0; a < 4; ++a)
 #pragma unroll
-            for (int b = 0; b < 4; ++b) { S[a][b] = 0.f; Q[a][b] = 0.f; M[0][a][b] = SF_NEG; M[1][a][b] = SF_NEG; }
+            for (int b = 0; b < 4; ++b) { S[a][b] = 0.f; Q[a][b] = 0.f; K[a][b] = 0.f; M[0][a][b] = SF_NEG; M[1][a][b] = SF_NEG; }
         H* yimg = yp + (size_t)n * PH * 32 * 64;
         uint8_t* iimg = idx + (size_t)n * PH * 32 * 64;
         int slot0 = (2 * oy_first) % SF_RING;
@@ -196,32 +232,46 @@ __global__ __launch_bounds__(64 * SF_WAVES) void stem_fwd_fused_kernel(const int
             f32x4_t acc[4][4];
             sf_conv_row<H, false>(acc, ring, slot0, xoff, wbase);
             slot0 = slot0 + 2 >= SF_RING ? slot0 + 2 - SF_RING : slot0 + 2;
-            // ---- plane statistics ----
-            // (one wave per image: at the middle row the upper half's sums are reduced and parked in LDS, so that the plane
-            //  sums are formed as (upper half) + (lower half) exactly as the two-waves-per-image form does -- an image's
-            //  outputs must not depend on the batch it arrives in, bit for bit)
-            if (halves == 1 && fold && oy == OH / 2) {
+            // ---- plane statistics (shifted sums, see sf_recentre) ----
+            // (one wave per image: at the middle row the upper half's (mean, M2) is formed and parked in LDS and the lower half
+            //  starts a segment of its own, so that the plane statistics are merged from (upper half) and (lower half) exactly as
+            //  the two-waves-per-image form does -- an image's outputs must not depend on the batch it arrives in, bit for bit)
+            const bool mid = halves == 1 && fold && oy == OH / 2;
+            if (mid) {
 #pragma unroll
                 for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const float su = sf_row_sum16(S[nt][r]), qu = sf_row_sum16(Q[nt][r]);
+                        float mu, m2u;
+                        sf_lane_moments(K[nt][r], S[nt][r], Q[nt][r], 1.f / (float)(2 * OH), mu, m2u);
+                        sf_row_moments16(mu, m2u, (float)(2 * OH));
                         if (li == 0) {
                             float* o = sX + ((wave * 64) + lg * 16 + nt * 4 + r) * 2;
-                            o[0] = su; o[1] = qu;
+                            o[0] = mu; o[1] = m2u;
                         }
                         S[nt][r] = 0.f; Q[nt][r] = 0.f;
                     }
             }
+            // a segment's shift: its first row, moved at row 2 when the segment starts in the padding rows
+            if (oy == oy_own || mid || (oy == 2 && oy_own == 0)) {
+                const float n_prev = (oy == oy_own || mid) ? 0.f : 8.f;
 #pragma unroll
-            for (int nt = 0; nt < 4; ++nt)
+                for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float s = 0.f, q = 0.f;
+                    for (int r = 0; r < 4; ++r) sf_recentre(K[nt][r], S[nt][r], Q[nt][r], acc[2][nt][r], n_prev);
+            }
+            if (oy >= oy_own) {
 #pragma unroll
-                    for (int mt = 0; mt < 4; ++mt) { const float v = acc[mt][nt][r]; s += v; q += v * v; }
-                    if (oy >= oy_own) { S[nt][r] += s; Q[nt][r] += q; }
-                }
+                for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int mt = 0; mt < 4; ++mt) {
+                            const float d = acc[mt][nt][r] - K[nt][r];
+                            S[nt][r] += d;
+                            Q[nt][r] = __builtin_fmaf(d, d, Q[nt][r]);
+                        }
+            }
             // ---- 3x3/2 max-pool on keys = value bits with the low 4 mantissa bits replaced by the window position ----
             const bool odd = oy & 1;
             const uint32_t khbits = odd ? 0u : 4u;                 // filter row 2 (odd rows) or 1 (even rows) of the window
@@ -280,45 +330,48 @@ __global__ __launch_bounds__(64 * SF_WAVES) void stem_fwd_fused_kernel(const int
         }
         // ---- plane statistics -> mean / rstd of the lane's 16 channels ----
         float mean[4][4], rstd[4][4];
-        if (halves == 1 && fold) {                                // (upper half, parked at the middle row) + (lower half)
+        // the lane's own segment -> (mean, M2) of its half (two halves) or of the plane (one segment)
+        const bool two = halves == 2 || fold;
+        const float n_lane = two ? (float)(2 * OH) : (float)(4 * OH);
 #pragma unroll
-            for (int nt = 0; nt < 4; ++nt)
+        for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float* o = sX + ((wave * 64) + lg * 16 + nt * 4 + r) * 2;
-                    S[nt][r] = o[0] + sf_row_sum16(S[nt][r]);
-                    Q[nt][r] = o[1] + sf_row_sum16(Q[nt][r]);
-                }
-        }
-        if (halves == 2) {                                        // the partner's partial sums (channel lg * 16 + nt * 4 + r)
+            for (int r = 0; r < 4; ++r) {
+                sf_lane_moments(K[nt][r], S[nt][r], Q[nt][r], 1.f / n_lane, S[nt][r], Q[nt][r]);
+                sf_row_moments16(S[nt][r], Q[nt][r], n_lane);
+            }
+        if (halves == 2) {                                        // the partner's half (channel lg * 16 + nt * 4 + r)
+            if (li == 0) {
 #pragma unroll
-            for (int nt = 0; nt < 4; ++nt)
+                for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    S[nt][r] = sf_row_sum16(S[nt][r]); Q[nt][r] = sf_row_sum16(Q[nt][r]);
-                    if (li == 0) {
+                    for (int r = 0; r < 4; ++r) {
                         float* o = sX + ((wave * 64) + lg * 16 + nt * 4 + r) * 2;
                         o[0] = S[nt][r]; o[1] = Q[nt][r];
                     }
-                }
+            }
             __syncthreads();
+        }
+        if (two) {                                                // merge (upper half, lower half) in that order in every form
+            const int src = halves == 2 ? (wave ^ 1) : wave;      // the parked / partner's half
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float* o = sX + (((wave ^ 1) * 64) + lg * 16 + nt * 4 + r) * 2;
-                    // (the upper half's sum first in both waves: the two agree bit for bit)
-                    S[nt][r] = hf ? o[0] + S[nt][r] : S[nt][r] + o[0];
-                    Q[nt][r] = hf ? o[1] + Q[nt][r] : Q[nt][r] + o[1];
+                    const float* o = sX + ((src * 64) + lg * 16 + nt * 4 + r) * 2;
+                    const bool upper = halves == 2 && hf == 0;    // this wave holds the upper half
+                    const float mu = upper ? S[nt][r] : o[0], m2u = upper ? Q[nt][r] : o[1];
+                    const float ml = upper ? o[0] : S[nt][r], m2l = upper ? o[1] : Q[nt][r];
+                    sf_merge_moments(mu, m2u, ml, m2l, (float)(OH * 32), S[nt][r], Q[nt][r]);
                 }
-            __syncthreads();                                      // sX may be rewritten in the next turn
+            if (halves == 2) __syncthreads();                     // sX may be rewritten in the next turn
         }
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float s = ((halves == 2 || fold) ? S[nt][r] : sf_row_sum16(S[nt][r])) * inv_hw, q = ((halves == 2 || fold) ? Q[nt][r] : sf_row_sum16(Q[nt][r])) * inv_hw;
-                const float var = fmaxf(q - s * s, 0.f);
+                const float s = S[nt][r];
+                const float var = fmaxf(Q[nt][r] * inv_hw, 0.f);
                 mean[nt][r] = s;
                 rstd[nt][r] = rsqrtf(var + eps);
                 if (li == 0 && hf == 0) {
@@ -371,7 +424,7 @@ __device__ __forceinline__ void sf_pair_sync(uint32_t my_flag, uint32_t partner_
 // byte is 8 - code: one packed subtraction per four channels instead of a 64-bit table shift per value; an odd column's key is
 // prepared once (kw = 2 of its own window) and handed to the right-hand neighbour as key + 2 (kw = 0); an odd row's window
 // maximum h becomes the next window's top row as h + 6 (kh 2 -> 0) instead of a second masking pass and a select; even / odd
-// rows are two straight code paths.  Statistics: S += v, Q = fma(v, v, Q) per value.
+// rows are two straight code paths.  Statistics: d = v - k, S += d, Q = fma(d, d, Q) per value (shifted sums, see sf_recentre).
 template <typename H>
 __global__ __launch_bounds__(1024) void stem_fwd_pairs_kernel(const int N, const int IH, const H* __restrict__ xp, const uint32_t xp_bytes,
                                                               const H* __restrict__ w8, const float eps, H* yp, uint8_t* __restrict__ idx,
@@ -380,6 +433,7 @@ __global__ __launch_bounds__(1024) void stem_fwd_pairs_kernel(const int N, const
     char* const sW = smem + SP_PAIRS * SF_RING * SF_ROWB;
     int* const sFlag = reinterpret_cast<int*>(sW + SF_WBYTES);
     const int tid = threadIdx.x;
+    float* const sK = reinterpret_cast<float*>(sFlag + 16) + (tid >> 6) * 32 + ((tid & 63) >> 4) * 8;   // the lane's 8 shifts
     sf_fill_weights<H>(sW, w8, tid, 1024);
     if (tid < 16) sFlag[tid] = 0;
     __syncthreads();
@@ -465,17 +519,35 @@ __global__ __launch_bounds__(1024) void stem_fwd_pairs_kernel(const int N, const
                     conv_mfma(false, fxb, fwb);
                     conv_mfma(false, fxa, fwa);
                 }
-                // ---- plane statistics ----
+                // ---- plane statistics: sums of v - k and (v - k)^2, the shift k set at row 0 and moved at row 2 ----
+                // (one shift per channel, column 32 of the row, kept in LDS: eight more registers per lane would spill)
+                if (oy == 0 || oy == 2) {
+                    float kn[2][4];
+#pragma unroll
+                    for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            kn[nt][r] = __shfl(acc[2][nt][r], lane & 48);
+                            float k = oy == 0 ? kn[nt][r] : sK[nt * 4 + r];
+                            sf_recentre(k, S[nt][r], Q[nt][r], kn[nt][r], (float)(4 * oy));
+                        }
+                    if (li == 0) {
+#pragma unroll
+                        for (int c = 0; c < 8; ++c) sK[c] = kn[c >> 2][c & 3];
+                    }
+                }
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r)
+                    for (int r = 0; r < 4; ++r) {
+                        const float k = sK[nt * 4 + r];
 #pragma unroll
                         for (int mt = 0; mt < 4; ++mt) {
-                            const float v = acc[mt][nt][r];
-                            S[nt][r] += v;
-                            Q[nt][r] = __builtin_fmaf(v, v, Q[nt][r]);
+                            const float d = acc[mt][nt][r] - k;
+                            S[nt][r] += d;
+                            Q[nt][r] = __builtin_fmaf(d, d, Q[nt][r]);
                         }
+                    }
                 // ---- 3x3/2 max-pool on keys = value bits with the low 4 mantissa bits replaced by 8 - (window position) ----
                 auto pool_row = [&](auto odd_tag) {
                     constexpr bool ODD = decltype(odd_tag)::value;
@@ -545,8 +617,10 @@ __global__ __launch_bounds__(1024) void stem_fwd_pairs_kernel(const int N, const
             for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float s = sf_row_sum16(S[nt][r]) * inv_hw, q = sf_row_sum16(Q[nt][r]) * inv_hw;
-                    const float var = fmaxf(q - s * s, 0.f);
+                    float s, m2;
+                    sf_lane_moments(sK[nt * 4 + r], S[nt][r], Q[nt][r], 1.f / (float)(4 * OH), s, m2);
+                    sf_row_moments16(s, m2, (float)(4 * OH));
+                    const float var = fmaxf(m2 * inv_hw, 0.f);
                     mean[nt][r] = s;
                     rstd[nt][r] = rsqrtf(var + eps);
                     if (li == 0) {
@@ -1141,7 +1215,7 @@ extern "C" int eve_stem_fwd_fused(int dtype, int N, int IH, int IW, const void* 
             (void)hipFuncSetAttribute((const void*)stem_fwd_pairs_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             attr2 = true;
         }
-        const size_t lds2 = (size_t)SP_PAIRS * SF_RING * SF_ROWB + SF_WBYTES + 64;
+        const size_t lds2 = (size_t)SP_PAIRS * SF_RING * SF_ROWB + SF_WBYTES + 64 + 16 * 32 * 4;     // + flags, per-channel shifts
         const unsigned blocks2 = N < 256 ? (unsigned)N : 256u;
         EVE_DISPATCH_H16(dtype, EVE_LAUNCH(EVE_HNAME(H, "stem_fwd_pairs_kernel<", ">"), stem_fwd_pairs_kernel<H>, dim3(blocks2), dim3(1024), lds2,
                                            (hipStream_t)stream, N, IH, (const H*)x_padded, (uint32_t)xb, (const H*)w_ohwi8, eps, (H*)y_pool, idx, mean_rstd));
