@@ -432,14 +432,27 @@ static inline unsigned rgrid(long long items) {
     return (unsigned)b;
 }
 
+// 256 < H <= 1024, H % 16 == 0: the tile-of-16-sequences MFMA scans of recurrent_wide.hip (G = 3 GRU, 1 RNN, 4 LSTM)
+bool scan_wide_ok(int H);
+int scan_wide_fwd(int G, int S, int T, int H, const float* gi, const float* whh_t, const float* bhh, const float* h0, const float* c0,
+                  float* hs, float* cs, float* gates, float* hn_pre, hipStream_t stream);
+int scan_wide_bwd(int G, int S, int T, int H, const float* dhs, const float* dcs, const float* whh, const float* h0, const float* c0,
+                  const float* hs, const float* cs, const float* gates, const float* hn_pre, float* out_a, float* out_b, float* dh0,
+                  float* dc0, hipStream_t stream);
+// the widths the scans take: the one-workgroup-per-sequence kernels up to 256, the wide family beyond
+static inline bool scan_width_ok(int H) { return H > 0 && (H <= 256 || scan_wide_ok(H)); }
+#define SCAN_WIDTH_RULE "H <= 256, or a multiple of 16 up to 1024"
+
 }  // namespace eve
 
 using namespace eve;
 
 extern "C" int eve_gru_scan_fwd(int S, int T, int H, const float* gi, const float* whh_t, const float* bhh,
                                 const float* h0, float* hs, float* gates, float* hn_pre, eve_stream_t stream) {
-    if (S <= 0 || T <= 0 || H <= 0 || H > 256 || !gi || !whh_t || !bhh || !hs || !gates || !hn_pre)
-        return set_error_msg("gru_scan_fwd: bad arguments (H <= 256)");
+    if (S <= 0 || T <= 0 || !scan_width_ok(H) || !gi || !whh_t || !bhh || !hs || !gates || !hn_pre)
+        return set_error_msg("gru_scan_fwd: bad arguments (" SCAN_WIDTH_RULE ")");
+    if (H > 256)
+        return scan_wide_fwd(3, S, T, H, gi, whh_t, bhh, h0, nullptr, hs, nullptr, gates, hn_pre, (hipStream_t)stream);
     if (H == 128) {
         hipLaunchKernelGGL(gru_scan_fwd128_kernel, dim3(S), dim3(384), 0, (hipStream_t)stream, T, gi, whh_t, bhh, h0, hs, gates,
                            hn_pre);
@@ -455,8 +468,11 @@ extern "C" int eve_gru_scan_fwd(int S, int T, int H, const float* gi, const floa
 extern "C" int eve_gru_scan_bwd(int S, int T, int H, const float* dhs, const float* whh, const float* h0,
                                 const float* hs, const float* gates, const float* hn_pre, float* dgi, float* dgh,
                                 float* dh0, eve_stream_t stream) {
-    if (S <= 0 || T <= 0 || H <= 0 || H > 256 || !dhs || !whh || !hs || !gates || !hn_pre || !dgi || !dgh)
-        return set_error_msg("gru_scan_bwd: bad arguments (H <= 256)");
+    if (S <= 0 || T <= 0 || !scan_width_ok(H) || !dhs || !whh || !hs || !gates || !hn_pre || !dgi || !dgh)
+        return set_error_msg("gru_scan_bwd: bad arguments (" SCAN_WIDTH_RULE ")");
+    if (H > 256)
+        return scan_wide_bwd(3, S, T, H, dhs, nullptr, whh, h0, nullptr, hs, nullptr, gates, hn_pre, dgi, dgh, dh0, nullptr,
+                             (hipStream_t)stream);
     if (H == 128) {
         hipLaunchKernelGGL(gru_scan_bwd128_kernel, dim3(S), dim3(384), 0, (hipStream_t)stream, T, dhs, whh, h0, hs, gates, hn_pre,
                            dgi, dgh, dh0);
@@ -472,7 +488,9 @@ extern "C" int eve_gru_scan_bwd(int S, int T, int H, const float* dhs, const flo
 
 extern "C" int eve_rnn_scan_fwd(int S, int T, int H, const float* gi, const float* whh_t, const float* bhh, const float* h0,
                                 float* hs, eve_stream_t stream) {
-    if (S <= 0 || T <= 0 || H <= 0 || H > 256 || !gi || !whh_t || !bhh || !hs) return set_error_msg("rnn_scan_fwd: bad arguments (H <= 256)");
+    if (S <= 0 || T <= 0 || !scan_width_ok(H) || !gi || !whh_t || !bhh || !hs) return set_error_msg("rnn_scan_fwd: bad arguments (" SCAN_WIDTH_RULE ")");
+    if (H > 256)
+        return scan_wide_fwd(1, S, T, H, gi, whh_t, bhh, h0, nullptr, hs, nullptr, nullptr, nullptr, (hipStream_t)stream);
     const int threads = ((H + 63) / 64) * 64;
     hipLaunchKernelGGL(cell_scan_fwd_kernel<1>, dim3(S), dim3(threads), 2 * H * sizeof(float), (hipStream_t)stream, T, H, gi,
                        whh_t, bhh, h0, (const float*)nullptr, hs, (float*)nullptr, (float*)nullptr);
@@ -481,7 +499,10 @@ extern "C" int eve_rnn_scan_fwd(int S, int T, int H, const float* gi, const floa
 }
 extern "C" int eve_rnn_scan_bwd(int S, int T, int H, const float* dhs, const float* whh, const float* hs, float* dpre,
                                 float* dh0, eve_stream_t stream) {
-    if (S <= 0 || T <= 0 || H <= 0 || H > 256 || !dhs || !whh || !hs || !dpre) return set_error_msg("rnn_scan_bwd: bad arguments (H <= 256)");
+    if (S <= 0 || T <= 0 || !scan_width_ok(H) || !dhs || !whh || !hs || !dpre) return set_error_msg("rnn_scan_bwd: bad arguments (" SCAN_WIDTH_RULE ")");
+    if (H > 256)
+        return scan_wide_bwd(1, S, T, H, dhs, nullptr, whh, nullptr, nullptr, hs, nullptr, nullptr, nullptr, nullptr, dpre, dh0,
+                             nullptr, (hipStream_t)stream);
     const int threads = ((H + 63) / 64) * 64;
     hipLaunchKernelGGL(cell_scan_bwd_kernel<1>, dim3(S), dim3(threads), 2 * H * sizeof(float), (hipStream_t)stream, T, H, dhs,
                        (const float*)nullptr, whh, (const float*)nullptr, hs, (const float*)nullptr, (const float*)nullptr, dpre, dh0,
@@ -491,8 +512,10 @@ extern "C" int eve_rnn_scan_bwd(int S, int T, int H, const float* dhs, const flo
 }
 extern "C" int eve_lstm_scan_fwd(int S, int T, int H, const float* gi, const float* whh_t, const float* bhh, const float* h0,
                                  const float* c0, float* hs, float* cs, float* gates, eve_stream_t stream) {
-    if (S <= 0 || T <= 0 || H <= 0 || H > 256 || !gi || !whh_t || !bhh || !hs || !cs || !gates)
-        return set_error_msg("lstm_scan_fwd: bad arguments (H <= 256)");
+    if (S <= 0 || T <= 0 || !scan_width_ok(H) || !gi || !whh_t || !bhh || !hs || !cs || !gates)
+        return set_error_msg("lstm_scan_fwd: bad arguments (" SCAN_WIDTH_RULE ")");
+    if (H > 256)
+        return scan_wide_fwd(4, S, T, H, gi, whh_t, bhh, h0, c0, hs, cs, gates, nullptr, (hipStream_t)stream);
     hipLaunchKernelGGL(cell_scan_fwd_kernel<4>, dim3(S), dim3(((4 * H + 63) / 64) * 64), 5 * H * sizeof(float), (hipStream_t)stream,
                        T, H, gi, whh_t, bhh, h0, c0, hs, cs, gates);
     EVE_CHECK_LAUNCH();
@@ -501,8 +524,11 @@ extern "C" int eve_lstm_scan_fwd(int S, int T, int H, const float* gi, const flo
 extern "C" int eve_lstm_scan_bwd(int S, int T, int H, const float* dhs, const float* dcs, const float* whh, const float* c0,
                                  const float* hs, const float* cs, const float* gates, float* dpre, float* dh0, float* dc0,
                                  eve_stream_t stream) {
-    if (S <= 0 || T <= 0 || H <= 0 || H > 256 || !dhs || !whh || !hs || !cs || !gates || !dpre)
-        return set_error_msg("lstm_scan_bwd: bad arguments (H <= 256)");
+    if (S <= 0 || T <= 0 || !scan_width_ok(H) || !dhs || !whh || !hs || !cs || !gates || !dpre)
+        return set_error_msg("lstm_scan_bwd: bad arguments (" SCAN_WIDTH_RULE ")");
+    if (H > 256)
+        return scan_wide_bwd(4, S, T, H, dhs, dcs, whh, nullptr, c0, hs, cs, gates, nullptr, nullptr, dpre, dh0, dc0,
+                             (hipStream_t)stream);
     hipLaunchKernelGGL(cell_scan_bwd_kernel<4>, dim3(S), dim3(((4 * H + 63) / 64) * 64), 5 * H * sizeof(float), (hipStream_t)stream,
                        T, H, dhs, dcs, whh, c0, hs, cs, gates, dpre, dh0, dc0);
     EVE_CHECK_LAUNCH();

@@ -414,6 +414,8 @@ int eve_pack_weights_batch(int dtype_dst, int count, const eve_pack_item* items 
  *   whh : float [3H][H] (the forward scan takes its transpose whh_t [H][3H]); bhh float [3H];
  *   h0 float [S][H] or NULL (= zeros, eye_net.py:120-122)
  *   hs  : float [S][T][H] all hidden states;  work: float [S][T][3H] (r, z, n) + [S][T][H] (hn) saved
+ *   H   : up to 256 (one workgroup per sequence), or a multiple of 16 up to 1024 (recurrent_wide.hip: one workgroup per
+ *         tile of 16 sequences, float32 MFMA); the same rule holds for the RNN / LSTM scans below; other widths are refused
  * ------------------------------------------------------------------------------------------------ */
 int eve_gru_scan_fwd(int S, int T, int H, const float* gi, const float* whh_t, const float* bhh,
                      const float* h0, float* hs, float* gates, float* hn_pre, eve_stream_t stream);
