@@ -1073,6 +1073,11 @@ extern "C" int eve_conv2d_fwd(const eve_conv_desc* d, const void* x, const void*
         EVE_DISPATCH_H16(d->dtype, done = launch_conv1x1_stream<H>(M, d->Cin, d->Cout, x, w_ohwi, bias, epi_act, y, s));
         if (done) { EVE_CHECK_LAUNCH(); return 0; }
     }
+    if (!in_scale_shift && !bias && epi_act == EVE_ACT_NONE && d->KH == 1 && d->stride == 2 && d->dtype != EVE_DT_F32) {    // the trunk's shortcuts
+        bool done = false;
+        EVE_DISPATCH_H16(d->dtype, done = launch_conv1x1_s2_stream<H>(d, false, x, w_ohwi, y, s));
+        if (done) { EVE_CHECK_LAUNCH(); return 0; }
+    }
     if (!in_scale_shift && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->dtype != EVE_DT_F32) {    // row-streaming 3x3
         bool done = false;
         EVE_DISPATCH_H16(d->dtype, done = launch_conv3x3_stream<H>(d->N, d->IH, d->IW, d->Cin, d->Cout, 0, x, w_ohwi, bias, epi_act, y, s));
@@ -1224,6 +1229,11 @@ extern "C" int eve_conv2d_dgrad_acc(const eve_conv_desc* d, const void* dy, cons
         const long long M = (long long)d->N * d->OH * d->OW;
         bool done = false;
         EVE_DISPATCH_H16(d->dtype, done = launch_conv1x1_stream<H>(M, d->Cout, d->Cin, dy, w_ihwo, nullptr, EVE_EPI_ACC, dx, s));
+        if (done) { EVE_CHECK_LAUNCH(); return 0; }
+    }
+    if (d->KH == 1 && d->stride == 2 && d->dtype != EVE_DT_F32) {    // the trunk's shortcuts: one pixel in four of dx is touched
+        bool done = false;
+        EVE_DISPATCH_H16(d->dtype, done = launch_conv1x1_s2_stream<H>(d, true, dy, w_ihwo, dx, s));
         if (done) { EVE_CHECK_LAUNCH(); return 0; }
     }
     if (d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->dtype != EVE_DT_F32) {

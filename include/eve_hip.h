@@ -77,7 +77,7 @@ typedef struct eve_dispatch_config {
     int in_trunk_kernels;          /* EVE_IN_TRUNK          1   branch-free InstanceNorm kernels for the ResNet trunk's cases */
     int stem_fused_wgrad;          /* EVE_STEM_FUSED_WGRAD  1   stem backward + weight gradient in one launch (eve_stem_bwd_wgrad) */
     int stem_fwd_pairs;            /* EVE_STEM_FWD_PAIRS    1   fused stem forward with two waves per image (32 channels each)       */
-    int conv1x1_stream;            /* EVE_CONV1X1_STREAM    1   1x1 convolutions between 16..128 channels on the streaming kernel (no LDS)    */
+    int conv1x1_stream;            /* EVE_CONV1X1_STREAM    1   1x1 convolutions between 16..128 channels on the streaming kernel (no LDS), and the trunk's 1x1 / stride-2 shortcuts (64 -> 128, 128 -> 256: forward and accumulating data gradient) on its strided sibling; 2: stride 1 only */
     int conv3x3_stream;            /* EVE_CONV3X3_STREAM    1   3x3 / stride 1 between 16..64 channels on 64 / 128-wide images: row-streaming kernel */
     int in_big_planes;             /* EVE_IN_BIG_PLANES     1   register-resident InstanceNorm (no affine) for planes beyond 8 192 vectors, dealt by channels */
     int cgru_seq_max_b;            /* EVE_CGRU_SEQ_MAX_B    384 16-bit conv-GRU clip scans: one sequence per workgroup (cgru_scan1.hip) up to this many sequences, three per workgroup (cgru_scan.hip) beyond */
