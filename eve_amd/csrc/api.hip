@@ -8,6 +8,7 @@
 namespace eve {
 static thread_local char g_err[512] = "";
 thread_local const char* g_last_kernel = "";
+thread_local hipError_t g_launch_error = hipSuccess;
 int set_error(hipError_t e, const char* where) {
     snprintf(g_err, sizeof(g_err), "%s: HIP error %d (%s)", where, (int)e, hipGetErrorString(e));
     return 100 + (int)e;

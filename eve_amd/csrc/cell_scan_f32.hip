@@ -363,17 +363,6 @@ __global__ __launch_bounds__(CS_NT) void clstm_scan_f32_fwd_kernel(const int B, 
 constexpr size_t CS_LDS_128 = (size_t)(CS_HALO + CS_PIX * 128) * sizeof(float);
 constexpr size_t CS_LDS_256 = (size_t)(CS_HALO + CS_PIX * 256) * sizeof(float);
 
-static void cs_set_attrs() {
-    static bool done = false;
-    if (done) return;
-    (void)hipFuncSetAttribute((const void*)cgru_scan_f32_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CS_LDS_128);
-    (void)hipFuncSetAttribute((const void*)cgru_scan_f32_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CS_LDS_128);
-    (void)hipFuncSetAttribute((const void*)crnn_scan_f32_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CS_LDS_128);
-    (void)hipFuncSetAttribute((const void*)crnn_scan_f32_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CS_LDS_128);
-    (void)hipFuncSetAttribute((const void*)clstm_scan_f32_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CS_LDS_256);
-    done = true;
-}
-
 }  // namespace eve
 
 using namespace eve;
@@ -381,7 +370,6 @@ using namespace eve;
 /* float32 instantiation of eve_cgru_scan_fwd / _bwd (cgru_scan.hip dispatches here for EVE_DT_F32): same operands, float. */
 int eve_cgru_scan_f32_fwd(int B, int T, const float* xs, const float* h0, const float* w1, const float* b1, const float* w2,
                           const float* b2, float* hs, float* hs_tm, float* ru, float* rh, float* og, hipStream_t s) {
-    cs_set_attrs();
     EVE_LAUNCH("cgru_scan_f32_fwd_kernel", cgru_scan_f32_fwd_kernel, dim3(B), dim3(CS_NT), CS_LDS_128, s, B, T, xs, h0, w1, b1, w2, b2,
                hs, hs_tm, ru, rh, og);
     EVE_CHECK_LAUNCH();
@@ -391,7 +379,6 @@ int eve_cgru_scan_f32_fwd(int B, int T, const float* xs, const float* h0, const 
 int eve_cgru_scan_f32_bwd(int B, int T, const float* dhs_tm, const float* ru, const float* og, const float* hs_tm, const float* h0,
                           const float* w1t, const float* w2t, float* dg1_all, float* dg2_all, float* dxs_tm, float* dh0,
                           hipStream_t s) {
-    cs_set_attrs();
     EVE_LAUNCH("cgru_scan_f32_bwd_kernel", cgru_scan_f32_bwd_kernel, dim3(B), dim3(CS_NT), CS_LDS_128, s, B, T, dhs_tm, ru, og, hs_tm, h0,
                w1t, w2t, dg1_all, dg2_all, dxs_tm, dh0);
     EVE_CHECK_LAUNCH();
@@ -404,7 +391,6 @@ int eve_cgru_scan_f32_bwd(int B, int T, const float* dhs_tm, const float* ru, co
 extern "C" int eve_crnn_scan_fwd(int B, int T, const float* xs, const float* h0, const float* w, const float* bias, float* hs,
                                  float* hs_tm, eve_stream_t stream) {
     if (B <= 0 || T <= 0 || !xs || !w || !bias || !hs || !hs_tm) return set_error_msg("crnn_scan_fwd: bad arguments");
-    cs_set_attrs();
     EVE_LAUNCH("crnn_scan_f32_fwd_kernel", crnn_scan_f32_fwd_kernel, dim3(B), dim3(CS_NT), CS_LDS_128, (hipStream_t)stream, B, T, xs, h0, w,
                bias, hs, hs_tm);
     EVE_CHECK_LAUNCH();
@@ -417,7 +403,6 @@ extern "C" int eve_crnn_scan_fwd(int B, int T, const float* xs, const float* h0,
 extern "C" int eve_crnn_scan_bwd(int B, int T, const float* dhs_tm, const float* hs_tm, const float* wt, float* dpre_all,
                                  float* dxs_tm, float* dh0, eve_stream_t stream) {
     if (B <= 0 || T <= 0 || !dhs_tm || !hs_tm || !wt || !dpre_all || !dxs_tm) return set_error_msg("crnn_scan_bwd: bad arguments");
-    cs_set_attrs();
     EVE_LAUNCH("crnn_scan_f32_bwd_kernel", crnn_scan_f32_bwd_kernel, dim3(B), dim3(CS_NT), CS_LDS_128, (hipStream_t)stream, B, T, dhs_tm,
                hs_tm, wt, dpre_all, dxs_tm, dh0);
     EVE_CHECK_LAUNCH();
@@ -430,7 +415,6 @@ extern "C" int eve_crnn_scan_bwd(int B, int T, const float* dhs_tm, const float*
 extern "C" int eve_clstm_scan_fwd(int B, int T, const float* xs, const float* h0, const float* c0, const float* w, const float* bias,
                                   float* hs, float* cs, eve_stream_t stream) {
     if (B <= 0 || T <= 0 || !xs || !w || !bias || !hs || !cs) return set_error_msg("clstm_scan_fwd: bad arguments");
-    cs_set_attrs();
     EVE_LAUNCH("clstm_scan_f32_fwd_kernel", clstm_scan_f32_fwd_kernel, dim3(B), dim3(CS_NT), CS_LDS_256, (hipStream_t)stream, B, T, xs, h0,
                c0, w, bias, hs, cs);
     EVE_CHECK_LAUNCH();

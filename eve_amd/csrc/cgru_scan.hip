@@ -594,12 +594,6 @@ extern "C" int eve_cgru_scan_fwd(int dtype, int B, int T, const void* xs, const 
         return set_error_msg("cgru_scan_fwd: bad arguments");
     if ((long long)B * T * CG_PIX * 128 >= (1ll << 31)) return set_error_msg("cgru_scan_fwd: clip too large for 32-bit offsets");
     if (B <= g_cfg.cgru_seq_max_b) return eve_cgru_scan1_fwd(dtype, B, T, xs, h0, w1, b1, w2, b2, hs, hs_tm, ru, rh, og, (hipStream_t)stream);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)cgru_scan_fwd_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)cgru_scan_fwd_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
     EVE_DISPATCH_H16(dtype, EVE_LAUNCH(EVE_HNAME(H, "cgru_scan_fwd_kernel<", ">"), cgru_scan_fwd_kernel<H>, dim3((B + CG_IMG - 1) / CG_IMG), dim3(256), CG_LDS,
                                        (hipStream_t)stream, B, T, (const H*)xs, (const H*)h0, (const H*)w1, b1, (const H*)w2, b2, (H*)hs, (H*)hs_tm,
                                        (H*)ru, (H*)rh, (H*)og));
@@ -625,12 +619,6 @@ extern "C" int eve_cgru_scan_bwd(int dtype, int B, int T, const void* dhs_tm, co
     if ((long long)B * T * CG_PIX * 128 >= (1ll << 31)) return set_error_msg("cgru_scan_bwd: clip too large for 32-bit offsets");
     if (B <= g_cfg.cgru_seq_max_b)
         return eve_cgru_scan1_bwd(dtype, B, T, dhs_tm, ru, og, hs_tm, h0, w1t, w2t, dg1_all, dg2_all, dxs_tm, dh0, (hipStream_t)stream);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)cgru_scan_bwd_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)cgru_scan_bwd_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
     EVE_DISPATCH_H16(dtype, EVE_LAUNCH(EVE_HNAME(H, "cgru_scan_bwd_kernel<", ">"), cgru_scan_bwd_kernel<H>, dim3((B + CG_IMG - 1) / CG_IMG), dim3(256), CG_LDS,
                                        (hipStream_t)stream, B, T, (const H*)dhs_tm, (const H*)ru, (const H*)og, (const H*)hs_tm, (const H*)h0,
                                        (const H*)w1t, (const H*)w2t, (H*)dg1_all, (H*)dg2_all, (H*)dxs_tm, (H*)dh0));

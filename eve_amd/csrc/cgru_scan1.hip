@@ -562,12 +562,6 @@ using namespace eve;
 // one-sequence-per-workgroup instantiations of eve_cgru_scan_fwd / _bwd (dispatched from cgru_scan.hip)
 int eve_cgru_scan1_fwd(int dtype, int B, int T, const void* xs, const void* h0, const void* w1, const float* b1, const void* w2,
                        const float* b2, void* hs, void* hs_tm, void* ru, void* rh, void* og, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)cgru_scan1_fwd_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S1_LDS_FWD);
-        (void)hipFuncSetAttribute((const void*)cgru_scan1_fwd_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S1_LDS_FWD);
-        attr_set = true;
-    }
     EVE_DISPATCH_H16(dtype, EVE_LAUNCH(EVE_HNAME(H, "cgru_scan1_fwd_kernel<", ">"), cgru_scan1_fwd_kernel<H>, dim3(B), dim3(S1_NT), S1_LDS_FWD, s, B, T,
                                        (const H*)xs, (const H*)h0, (const H*)w1, b1, (const H*)w2, b2, (H*)hs, (H*)hs_tm, (H*)ru, (H*)rh, (H*)og));
     EVE_CHECK_LAUNCH();
@@ -576,12 +570,6 @@ int eve_cgru_scan1_fwd(int dtype, int B, int T, const void* xs, const void* h0, 
 
 int eve_cgru_scan1_bwd(int dtype, int B, int T, const void* dhs_tm, const void* ru, const void* og, const void* hs_tm, const void* h0,
                        const void* w1t, const void* w2t, void* dg1_all, void* dg2_all, void* dxs_tm, void* dh0, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)cgru_scan1_bwd_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S1_LDS_BWD);
-        (void)hipFuncSetAttribute((const void*)cgru_scan1_bwd_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S1_LDS_BWD);
-        attr_set = true;
-    }
     EVE_DISPATCH_H16(dtype, EVE_LAUNCH(EVE_HNAME(H, "cgru_scan1_bwd_kernel<", ">"), cgru_scan1_bwd_kernel<H>, dim3(B), dim3(S1_NT), S1_LDS_BWD, s, B, T,
                                        (const H*)dhs_tm, (const H*)ru, (const H*)og, (const H*)hs_tm, (const H*)h0, (const H*)w1t, (const H*)w2t,
                                        (H*)dg1_all, (H*)dg2_all, (H*)dxs_tm, (H*)dh0));

@@ -16,6 +16,8 @@ template <typename F, int... I>
 __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
 template <int N, typename F>
 __device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
+// a compile-time int as a value (what host-side generic lambdas take to pick a kernel instantiation)
+template <int I> using ic = std::integral_constant<int, I>;
 
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
@@ -122,6 +124,14 @@ template <> struct Elem<f16_t> {
         else { using H = eve::f16_t; __VA_ARGS__; }                         \
     } while (0)
 
+// the same over all three element types, bound to T (sites whose arms differ in nothing but the type)
+#define EVE_DISPATCH_T(dtype, ...)                                               \
+    do {                                                                         \
+        if ((dtype) == EVE_DT_BF16) { using T = eve::bf16_t; __VA_ARGS__; }      \
+        else if ((dtype) == EVE_DT_F16) { using T = eve::f16_t; __VA_ARGS__; }   \
+        else { using T = float; __VA_ARGS__; }                                   \
+    } while (0)
+
 // ---------------------------------------------------------------------------------------------
 // activations (the set the reference uses: ReLU, LeakyReLU(0.01), SELU, tanh, sigmoid)
 // ---------------------------------------------------------------------------------------------
@@ -210,9 +220,10 @@ __device__ __forceinline__ uint32_t xcd_remap(uint32_t bid, uint32_t nblk) {
 
 }  // namespace eve
 
+// end of an entry point's launches: a launch the helper below refused, else whatever HIP recorded
 #define EVE_CHECK_LAUNCH()                                             \
     do {                                                               \
-        hipError_t e__ = hipGetLastError();                            \
+        hipError_t e__ = eve::take_launch_error();                     \
         if (e__ != hipSuccess) return eve::set_error(e__, __func__);   \
     } while (0)
 
@@ -251,5 +262,47 @@ extern thread_local const char* g_last_kernel;
 // kernel selection, resolved once at library load (api.hip; include/eve_hip.h: eve_dispatch_config)
 extern eve_dispatch_config g_cfg;
 }  // namespace eve
-#define EVE_MARK_KERNEL(name) (eve::g_last_kernel = (name))
-#define EVE_LAUNCH(name, ...) do { EVE_MARK_KERNEL(name); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
+namespace eve {
+// ---------------------------------------------------------------------------------------------
+// the one launch path of every kernel that takes part in the benchmark's attribution or needs more than the default LDS
+// ---------------------------------------------------------------------------------------------
+// error of a launch that launch() did not issue, kept for the entry point's EVE_CHECK_LAUNCH (launchers return "launched", not a status)
+extern thread_local hipError_t g_launch_error;
+inline hipError_t take_launch_error() {
+    const hipError_t e = g_launch_error;
+    g_launch_error = hipSuccess;
+    return e != hipSuccess ? e : hipGetLastError();
+}
+constexpr size_t LDS_DEFAULT_LIMIT = 64 * 1024;     // dynamic LDS a kernel may ask for without the attribute
+constexpr int LDS_CU = 160 * 1024;                  // a gfx950 CU's whole LDS
+// a kernel instantiation together with the symbol the attribution knows it by (what a generic lambda passes around)
+template <auto Kernel> struct Named { const char* name; };
+// kernel<H, ...> named as rocprofv3 prints it: one spelling for the instantiation and for its name
+#define EVE_KERNEL_H(H, kernel, ...) eve::Named<kernel<H, __VA_ARGS__>>{EVE_HNAME(H, #kernel "<", ", " #__VA_ARGS__ ">")}
+
+// Launch `Kernel` under `name`, in this order:
+//  1. more dynamic LDS than the default limit: hipFuncAttributeMaxDynamicSharedMemorySize of THIS instantiation is raised, once
+//     per process (the initialisation of a function-local static: thread-safe) and to one value for everyone, the CU's whole
+//     LDS -- no kernel here asks for more, and the limit only admits a launch, it reserves nothing.  A failed call is kept in
+//     g_launch_error, nothing is launched, and the entry point's EVE_CHECK_LAUNCH reports it through set_error.
+//  2. g_last_kernel = name (eve_last_kernel(): the benchmark and the tests key on these strings, so they never change)
+//  3. hipLaunchKernelGGL
+template <auto Kernel>
+inline hipError_t raise_lds_limit() {
+    static const hipError_t attr = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CU);
+    return attr;
+}
+template <auto Kernel, typename... Args>
+inline void launch(const char* name, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const Args&... args) {
+    if (lds_bytes > LDS_DEFAULT_LIMIT) {
+        if (const hipError_t attr = raise_lds_limit<Kernel>(); attr != hipSuccess) { g_launch_error = attr; return; }
+    }
+    g_last_kernel = name;
+    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, stream, args...);
+}
+template <auto Kernel, typename... Args>
+inline void launch(Named<Kernel> k, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const Args&... args) {
+    launch<Kernel>(k.name, grid, block, lds_bytes, stream, args...);
+}
+}  // namespace eve
+#define EVE_LAUNCH(name, kernel, ...) eve::launch<kernel>(name, __VA_ARGS__)

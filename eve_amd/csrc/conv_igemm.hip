@@ -19,8 +19,11 @@
 //
 // The optional prologue x' = act(x*scale[n,c] + shift[n,c]) is applied between the global load and the
 // LDS write, i.e. the consumer normalises InstanceNorm'ed inputs on the fly (padding stays exactly 0).
+#include <limits.h>
+#include <stdio.h>
 #include <stdlib.h>
 
+#include <initializer_list>
 #include <type_traits>
 #include "common.h"
 
@@ -591,19 +594,13 @@ static bool launch_halo(const GatherParams& p, const void* src, const void* w, c
         ((epi_act & 0xff) == EVE_ACT_NONE || (epi_act & 0xff) == EVE_ACT_RELU) && (unsigned long long)p.N * W * W * 128ull < (1ull << 31)) {
         Ws64Params q;
         q.N = p.N; q.flip = bwd ? 1 : 0; q.x_bytes = (uint32_t)((unsigned long long)p.N * W * W * 128ull); q.w_bytes = 64u * 576u * 2u;
-        static bool attr_done = false;
-        if (!attr_done) {
-            (void)hipFuncSetAttribute((const void*)conv3x3_ws64_kernel<HT, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)conv3x3_ws64_kernel<HT, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr_done = true;
-        }
         const uint32_t T64 = (uint32_t)(W * W / 512) * (uint32_t)p.N;
         if (W == 32)
-            EVE_LAUNCH(EVE_HNAME(HT, "conv3x3_ws64_kernel<", ", 32>"), (conv3x3_ws64_kernel<HT, 32>), dim3(T64 < 256u ? T64 : 256u), dim3(512),
-                       (size_t)Ws64Geom<32>::LDS, s, q, (const HT*)src, (const HT*)w, bias, epi_act, (HT*)out);
+            launch(EVE_KERNEL_H(HT, conv3x3_ws64_kernel, 32), dim3(T64 < 256u ? T64 : 256u), dim3(512), (size_t)Ws64Geom<32>::LDS, s, q,
+                   (const HT*)src, (const HT*)w, bias, epi_act, (HT*)out);
         else
-            EVE_LAUNCH(EVE_HNAME(HT, "conv3x3_ws64_kernel<", ", 64>"), (conv3x3_ws64_kernel<HT, 64>), dim3(T64 < 256u ? T64 : 256u), dim3(512),
-                       (size_t)Ws64Geom<64>::LDS, s, q, (const HT*)src, (const HT*)w, bias, epi_act, (HT*)out);
+            launch(EVE_KERNEL_H(HT, conv3x3_ws64_kernel, 64), dim3(T64 < 256u ? T64 : 256u), dim3(512), (size_t)Ws64Geom<64>::LDS, s, q,
+                   (const HT*)src, (const HT*)w, bias, epi_act, (HT*)out);
         return true;
     }
     // ---- eight-wave workgroups, 32x32x16 MFMA, staggered wave groups (conv_wg8.h): whole square images per tile ----
@@ -616,48 +613,31 @@ static bool launch_halo(const GatherParams& p, const void* src, const void* w, c
         const unsigned long long xb8 = (unsigned long long)p.N * H * W * p.Cin * 2, wb8 = (unsigned long long)p.Cout * p.K * 2;
         Wg8Params g;
         g.N = p.N; g.Cin = p.Cin; g.Cout = p.Cout; g.flip = bwd ? 1 : 0; g.K = p.K; g.x_bytes = (uint32_t)xb8; g.w_bytes = (uint32_t)wb8; g.s2_py = 0;
-#define EVE_WG8_LAUNCH(WM_, WN_, W_)                                                                                      \
-        do {                                                                                                             \
-            using G8 = Wg8Geom<WM_, WN_, W_>;                                                                              \
-            static bool attr_done = false;                                                                               \
-            if (!attr_done) {                                                                                            \
-                (void)hipFuncSetAttribute((const void*)conv3x3_wg8_kernel<HT, WM_, WN_, W_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                attr_done = true;                                                                                        \
-            }                                                                                                            \
-            g.tiles_n = (uint32_t)(p.Cout / G8::COUT_T);                                                                   \
-            const uint32_t tiles8 = (uint32_t)((p.N + G8::TI - 1) / G8::TI) * g.tiles_n;                                     \
-            if ((int)tiles8 < wg8_min_tiles) break;      /* too few whole-CU workgroups (small batches): four-wave kernels */ \
-            EVE_LAUNCH(EVE_HNAME(HT, "conv3x3_wg8_kernel<", ", " #WM_ ", " #WN_ ", " #W_ ">"), (conv3x3_wg8_kernel<HT, WM_, WN_, W_>), dim3(tiles8), \
-                       dim3(512), G8::LDS, s, g, (const HT*)src, (const HT*)w, bias, epi_act, (HT*)out);                   \
-            return true;                                                                                                 \
-        } while (0)
+        // one tile shape (`units` images or bands, G8::TI of them per tile).  false: too few whole-CU workgroups (small batches), the
+        // four-wave kernels take the layer
+        auto wg8_tile = [&](auto kernel, auto geom, uint32_t units) {
+            using G8 = decltype(geom);
+            g.tiles_n = (uint32_t)(p.Cout / G8::COUT_T);
+            const uint32_t tiles8 = (units + G8::TI - 1) / G8::TI * g.tiles_n;
+            if ((int)tiles8 < wg8_min_tiles) return false;
+            launch(kernel, dim3(tiles8), dim3(512), G8::LDS, s, g, (const HT*)src, (const HT*)w, bias, epi_act, (HT*)out);
+            return true;
+        };
+        const uint32_t imgs = (uint32_t)p.N;
         if (xb8 < (1ull << 31) && wb8 < (1ull << 31)) {
             // 16 x 16 images x 128 channels (512-pixel tiles, 36 steps each): a one-tile workgroup per CU spends ~15 % of its
             // time in the un-overlapped prologue / epilogue; since the epilogue stores 64 contiguous bytes per lane quad it is
             // ahead of the four-wave kernel there too (0.141 against 0.151-0.166 ms; EVE_CONV_WG8=3 keeps the four-wave kernel)
-            if (wg8 != 3 && W == 16 && p.Cout % 128 == 0 && p.Cout % 256 != 0) EVE_WG8_LAUNCH(4, 2, 16);
+            if (wg8 != 3 && W == 16 && p.Cout % 128 == 0 && p.Cout % 256 != 0 &&
+                wg8_tile(EVE_KERNEL_H(HT, conv3x3_wg8_kernel, 4, 2, 16), Wg8Geom<4, 2, 16>{}, imgs)) return true;
             // 16 x 16 x 256 (the trunk's layer 3 on 256 x 256 patches, BASELINE configs[4]): one image x 256 channels per tile
-            if (W == 16 && p.Cout % 256 == 0) EVE_WG8_LAUNCH(2, 4, 16);
-            if (W == 8 && p.Cout % 256 == 0) EVE_WG8_LAUNCH(2, 4, 8);
-            if (W == 4 && p.Cout % 256 == 0) EVE_WG8_LAUNCH(2, 4, 4);
+            if (W == 16 && p.Cout % 256 == 0 && wg8_tile(EVE_KERNEL_H(HT, conv3x3_wg8_kernel, 2, 4, 16), Wg8Geom<2, 4, 16>{}, imgs)) return true;
+            if (W == 8 && p.Cout % 256 == 0 && wg8_tile(EVE_KERNEL_H(HT, conv3x3_wg8_kernel, 2, 4, 8), Wg8Geom<2, 4, 8>{}, imgs)) return true;
+            if (W == 4 && p.Cout % 256 == 0 && wg8_tile(EVE_KERNEL_H(HT, conv3x3_wg8_kernel, 2, 4, 4), Wg8Geom<2, 4, 4>{}, imgs)) return true;
             // 32 x 32 x 128 (the trunk's layer 2 on 256 x 256 patches, BASELINE configs[4]): half-image bands of 16 rows x 128 channels
-            if (W == 32 && p.Cout % 128 == 0) {
-                using G8 = Wg8Geom<4, 2, 32, 2>;
-                static bool attr_done = false;
-                if (!attr_done) {
-                    (void)hipFuncSetAttribute((const void*)conv3x3_wg8_kernel<HT, 4, 2, 32, 9, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                    attr_done = true;
-                }
-                g.tiles_n = (uint32_t)(p.Cout / G8::COUT_T);
-                const uint32_t tiles8 = (uint32_t)p.N * 2u * g.tiles_n;
-                if ((int)tiles8 >= wg8_min_tiles) {
-                    EVE_LAUNCH(EVE_HNAME(HT, "conv3x3_wg8_kernel<", ", 4, 2, 32, 9, 2>"), (conv3x3_wg8_kernel<HT, 4, 2, 32, 9, 2>), dim3(tiles8),
-                               dim3(512), G8::LDS, s, g, (const HT*)src, (const HT*)w, bias, epi_act, (HT*)out);
-                    return true;
-                }
-            }
+            if (W == 32 && p.Cout % 128 == 0 &&
+                wg8_tile(EVE_KERNEL_H(HT, conv3x3_wg8_kernel, 4, 2, 32, 9, 2), Wg8Geom<4, 2, 32, 2>{}, 2u * imgs)) return true;
         }
-#undef EVE_WG8_LAUNCH
     }
     const bool narrow = p.Cout <= 64;               // 256 pixels x 64 channels (4x1 waves) instead of 128 x 128 (2x2)
     const int BMp = narrow ? 256 : 128;
@@ -675,37 +655,21 @@ static bool launch_halo(const GatherParams& p, const void* src, const void* w, c
     h.tiles_n = narrow ? 1 : (p.Cout + 127) / 128;
     h.fd_w2 = make_fastdiv(W + 2); h.fd_hpi = make_fastdiv((h.TH + 2) * (W + 2)); h.fd_w = make_fastdiv(W); h.fd_th = make_fastdiv(h.TH);
     const size_t lds = 2 * (size_t)h.a_pieces * 4096 + 4 * (narrow ? 4096 : 8192);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)conv3x3_halo_kernel<HT, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv3x3_halo_kernel<HT, 4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
     const int persist = g_cfg.halo_persist;
     const uint32_t tiles = h.tiles_m * h.tiles_n;
     // (pays where a tile is short -- 18 steps at 64 channels; from 128 channels on the one-tile kernel is as fast)
     if (persist && tiles > 512 && p.Cin <= 64 && p.Cout % 8 == 0 && (epi_act == EVE_ACT_NONE || epi_act == EVE_ACT_RELU)) {           // two resident workgroups per CU walk the tiles as one stream
         const size_t plds = lds + (bias ? (size_t)h.tiles_n * (narrow ? 64 : 128) * 4 : 0);
-        static bool pattr = false;
-        if (!pattr) {
-            (void)hipFuncSetAttribute((const void*)conv3x3_halo_pkernel<HT, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)conv3x3_halo_pkernel<HT, 4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            pattr = true;
-        }
         if (narrow)
-            EVE_LAUNCH(EVE_HNAME(HT, "conv3x3_halo_pkernel<", ", 4, 1>"), (conv3x3_halo_pkernel<HT, 4, 1>), dim3(512), dim3(256), plds, s, h, (const HT*)src,
-                               (const HT*)w, bias, epi_act, (HT*)out);
+            launch(EVE_KERNEL_H(HT, conv3x3_halo_pkernel, 4, 1), dim3(512), dim3(256), plds, s, h, (const HT*)src, (const HT*)w, bias, epi_act, (HT*)out);
         else
-            EVE_LAUNCH(EVE_HNAME(HT, "conv3x3_halo_pkernel<", ", 2, 2>"), (conv3x3_halo_pkernel<HT, 2, 2>), dim3(512), dim3(256), plds, s, h, (const HT*)src,
-                               (const HT*)w, bias, epi_act, (HT*)out);
+            launch(EVE_KERNEL_H(HT, conv3x3_halo_pkernel, 2, 2), dim3(512), dim3(256), plds, s, h, (const HT*)src, (const HT*)w, bias, epi_act, (HT*)out);
         return true;
     }
     if (narrow)
-        EVE_LAUNCH(EVE_HNAME(HT, "conv3x3_halo_kernel<", ", 4, 1>"), (conv3x3_halo_kernel<HT, 4, 1>), dim3(tiles), dim3(256), lds, s, h, (const HT*)src,
-                           (const HT*)w, bias, epi_act, (HT*)out);
+        launch(EVE_KERNEL_H(HT, conv3x3_halo_kernel, 4, 1), dim3(tiles), dim3(256), lds, s, h, (const HT*)src, (const HT*)w, bias, epi_act, (HT*)out);
     else
-        EVE_LAUNCH(EVE_HNAME(HT, "conv3x3_halo_kernel<", ", 2, 2>"), (conv3x3_halo_kernel<HT, 2, 2>), dim3(tiles), dim3(256), lds, s, h, (const HT*)src,
-                           (const HT*)w, bias, epi_act, (HT*)out);
+        launch(EVE_KERNEL_H(HT, conv3x3_halo_kernel, 2, 2), dim3(tiles), dim3(256), lds, s, h, (const HT*)src, (const HT*)w, bias, epi_act, (HT*)out);
     return true;
 }
 
@@ -857,23 +821,8 @@ static bool launch_wgrad_halo(const GatherParams& p, const void* x, const void* 
     const unsigned per_cu = (unsigned)((160 * 1024) / lds);
     unsigned grid = 256 * (per_cu > occ ? occ : per_cu);
     if (grid > h.total_bands) grid = h.total_bands;
-#define EVE_WGRAD_HALO_LAUNCH(MT_, CT_, KS_)                                                                            \
-    do {                                                                                                                \
-        static bool attr_done = false;                                                                                  \
-        if (!attr_done) {                                                                                               \
-            (void)hipFuncSetAttribute((const void*)wgrad_halo_kernel<HT, MT_, CT_, KS_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            attr_done = true;                                                                                           \
-        }                                                                                                               \
-        EVE_LAUNCH(EVE_HNAME(HT, "wgrad_halo_kernel<", ", " #MT_ ", " #CT_ ", " #KS_ ">"), (wgrad_halo_kernel<HT, MT_, CT_, KS_>), dim3(grid), dim3(256), lds, s, h, \
-                   (const HT*)x, (const HT*)dy, dw, db);                                                                    \
-    } while (0)
+    auto band_tile = [&](auto kernel) { launch(kernel, dim3(grid), dim3(256), lds, s, h, (const HT*)x, (const HT*)dy, dw, db); };
     if (split) {
-        static bool attr_done = false;
-        if (!attr_done) {
-            (void)hipFuncSetAttribute((const void*)wgrad_halo64_kernel<HT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)wgrad_halo64_kernel<HT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr_done = true;
-        }
         const unsigned g64 = h.total_bands < 256u ? h.total_bands : 256u;
         const int fixed64 = g_cfg.wg64_fixed;
         if (fixed64 && W == 32 && TH == 8 && H % 8 == 0)     // ResNet layer 1: unrolled band loop, immediate fragment addresses
@@ -881,21 +830,24 @@ static bool launch_wgrad_halo(const GatherParams& p, const void* x, const void* 
         else
             EVE_LAUNCH(EVE_HNAME(HT, "wgrad_halo64_kernel<", ">"), (wgrad_halo64_kernel<HT, false>), dim3(g64), dim3(512), lds, s, h, (const HT*)x, (const HT*)dy, dw, db);
     } else if (ks == 3) {
-        if (MT == 1 && CT == 1) EVE_WGRAD_HALO_LAUNCH(1, 1, 3);
-        else if (MT == 1 && CT == 2) EVE_WGRAD_HALO_LAUNCH(1, 2, 3);
-        else if (MT == 1 && CT == 4) EVE_WGRAD_HALO_LAUNCH(1, 4, 3);
-        else if (MT == 2 && CT == 1) EVE_WGRAD_HALO_LAUNCH(2, 1, 3);
-        else EVE_WGRAD_HALO_LAUNCH(2, 2, 3);
+        if (MT == 1 && CT == 1) band_tile(EVE_KERNEL_H(HT, wgrad_halo_kernel, 1, 1, 3));
+        else if (MT == 1 && CT == 2) band_tile(EVE_KERNEL_H(HT, wgrad_halo_kernel, 1, 2, 3));
+        else if (MT == 1 && CT == 4) band_tile(EVE_KERNEL_H(HT, wgrad_halo_kernel, 1, 4, 3));
+        else if (MT == 2 && CT == 1) band_tile(EVE_KERNEL_H(HT, wgrad_halo_kernel, 2, 1, 3));
+        else band_tile(EVE_KERNEL_H(HT, wgrad_halo_kernel, 2, 2, 3));
     } else {
-        if (MT == 2 && CT == 1) EVE_WGRAD_HALO_LAUNCH(2, 1, 1);
-        else if (MT == 1 && CT == 4) EVE_WGRAD_HALO_LAUNCH(1, 4, 1);
-        else if (MT == 1 && CT == 2) EVE_WGRAD_HALO_LAUNCH(1, 2, 1);
-        else if (MT == 4 && CT == 2) EVE_WGRAD_HALO_LAUNCH(4, 2, 1);
-        else EVE_WGRAD_HALO_LAUNCH(2, 4, 1);
+        if (MT == 2 && CT == 1) band_tile(EVE_KERNEL_H(HT, wgrad_halo_kernel, 2, 1, 1));
+        else if (MT == 1 && CT == 4) band_tile(EVE_KERNEL_H(HT, wgrad_halo_kernel, 1, 4, 1));
+        else if (MT == 1 && CT == 2) band_tile(EVE_KERNEL_H(HT, wgrad_halo_kernel, 1, 2, 1));
+        else if (MT == 4 && CT == 2) band_tile(EVE_KERNEL_H(HT, wgrad_halo_kernel, 4, 2, 1));
+        else band_tile(EVE_KERNEL_H(HT, wgrad_halo_kernel, 2, 4, 1));
     }
-#undef EVE_WGRAD_HALO_LAUNCH
     return true;
 }
+
+// a tile shape of wgrad_tr_kernel as tr_tile (launch_wgrad) takes it: the name the attribution has always used for it (MT as
+// "mtN"; the bias flag is not part of it) and the shape as compile-time constants
+#define EVE_WGRAD_TR(T, WCO, WK, P2, MT) EVE_HNAME(T, "wgrad_tr_kernel<", ", " #WCO ", " #WK ", " #P2 ", mt" #MT ">"), ic<WCO>{}, ic<WK>{}, ic<P2>{}, ic<MT>{}
 
 template <typename T>
 static int launch_wgrad(const GatherParams& p, const void* x, const void* dy, const float* ss, int pro_act,
@@ -910,24 +862,16 @@ static int launch_wgrad(const GatherParams& p, const void* x, const void* dy, co
             const bool pow2 = ((p.OW & (p.OW - 1)) == 0) && ((p.OH & (p.OH - 1)) == 0);
             // dynamic LDS = RING (3 or 4, as in wgrad_tr_kernel) stages of 32 pixels x (BCO + BKK) bf16
             auto lds_bytes = [](int bco, int bkk, int mode) { return (size_t)((bco == 128 || (bkk == 256 && mode == 2)) ? 3 : 4) * 32 * (bco + bkk) * 2; };
-#define EVE_WGRAD_LAUNCH2(WCO_, WK_, P2_, B_, MT_, TK, TC)                                                              \
-    do {                                                                                                                \
-        static bool attr_done = false;                                                                                  \
-        if (!attr_done) {                                                                                               \
-            (void)hipFuncSetAttribute((const void*)wgrad_tr_kernel<T, WCO_, WK_, P2_, B_, MT_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                      160 * 1024);                                                                      \
-            attr_done = true;                                                                                           \
-        }                                                                                                               \
-        EVE_LAUNCH(EVE_HNAME(T, "wgrad_tr_kernel<", ", " #WCO_ ", " #WK_ ", " #P2_ ", mt" #MT_ ">"), (wgrad_tr_kernel<T, WCO_, WK_, P2_, B_, MT_>), \
-                   dim3((TK) * (TC) * splits), dim3(64 * WCO_ * WK_), lds_bytes(64 * WCO_, 64 * WK_, P2_), s, p, (const T*)x, \
-                   (const T*)dy, dw, rows, (uint32_t)x_bytes, (uint32_t)dy_bytes, db);                               \
-    } while (0)
-#define EVE_WGRAD_LAUNCH1(WCO_, WK_, P2_, MT_, TK, TC)                                                                  \
-    do {                                                                                                                \
-        if (db) EVE_WGRAD_LAUNCH2(WCO_, WK_, P2_, true, MT_, TK, TC);                                                   \
-        else    EVE_WGRAD_LAUNCH2(WCO_, WK_, P2_, false, MT_, TK, TC);                                                  \
-    } while (0)
-#define EVE_WGRAD_LAUNCH(WCO_, WK_, P2_, TK, TC) EVE_WGRAD_LAUNCH1(WCO_, WK_, P2_, 4, TK, TC)
+            // wgrad_tr_kernel of one tile shape over tk x tc x splits workgroups (EVE_WGRAD_TR: name and shape), with or without the bias sums
+            auto tr_tile = [&](const char* name, auto wco, auto wk, auto p2, auto mt, uint32_t tk, uint32_t tc) {
+                constexpr int WCO = decltype(wco)::value, WK = decltype(wk)::value, P2 = decltype(p2)::value, MT = decltype(mt)::value;
+                auto go = [&](auto kernel) {
+                    launch(kernel, dim3(tk * tc * splits), dim3(64 * WCO * WK), lds_bytes(64 * WCO, 64 * WK, P2), s, p, (const T*)x, (const T*)dy, dw,
+                           rows, (uint32_t)x_bytes, (uint32_t)dy_bytes, db);
+                };
+                if (db) go(Named<wgrad_tr_kernel<T, WCO, WK, P2, true, MT>>{name});
+                else    go(Named<wgrad_tr_kernel<T, WCO, WK, P2, false, MT>>{name});
+            };
             // address-decode mode of the gather (see wgrad_tr_kernel): both sizes powers of two / width only / neither
             const bool pow2w = (p.OW & (p.OW - 1)) == 0;
             const int mode = pow2 ? 1 : ((pow2w && p.OH * p.OW >= 32) ? 2 : 0);
@@ -936,12 +880,6 @@ static int launch_wgrad(const GatherParams& p, const void* x, const void* dy, co
                 // 256 x 256 tiles, eight waves of 128 x 64, role-split wave pairs (wgrad_wg8.h): one workgroup per CU
                 const uint32_t tk = p.K / 256, tc = p.Cout / 256;
                 wgrad_split(p, tk, tc, (size_t)128 * 1024, splits, rows);
-                static bool attr_done = false;
-                if (!attr_done) {
-                    (void)hipFuncSetAttribute((const void*)wgrad_wg8_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                    (void)hipFuncSetAttribute((const void*)wgrad_wg8_kernel<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                    attr_done = true;
-                }
                 const unsigned long long n = (unsigned long long)p.Cout * p.K;
                 // (the caller's scratch for THIS call: partial filters, consumed by the reduce launch that follows on the same stream)
                 const bool slab = splits > 1 && workspace && (unsigned long long)splits * n * 4 <= workspace_bytes && ((uintptr_t)dw & 15) == 0 &&
@@ -960,9 +898,9 @@ static int launch_wgrad(const GatherParams& p, const void* x, const void* dy, co
             } else if (p.Cout > 64) {
                 const uint32_t tk = (p.K + 127) / 128, tc = (p.Cout + 127) / 128;
                 wgrad_split(p, tk, tc, lds_bytes(128, 128, mode), splits, rows);
-                if (mode == 1)      EVE_WGRAD_LAUNCH(2, 2, 1, tk, tc);
-                else if (mode == 2) EVE_WGRAD_LAUNCH(2, 2, 2, tk, tc);
-                else                EVE_WGRAD_LAUNCH(2, 2, 0, tk, tc);
+                if (mode == 1)      tr_tile(EVE_WGRAD_TR(T, 2, 2, 1, 4), tk, tc);
+                else if (mode == 2) tr_tile(EVE_WGRAD_TR(T, 2, 2, 2, 4), tk, tc);
+                else                tr_tile(EVE_WGRAD_TR(T, 2, 2, 0, 4), tk, tc);
             // (one 9-wave workgroup covering the whole 576-wide filter of the 64-channel layers -- operands fetched once
             //  instead of once per K tile -- measured SLOWER: 0.292 vs 0.237 ms; the surplus fetches hit the Infinity Cache)
             } else if (mode == 1 && p.K % 192 == 0 && p.K <= 1152) {
@@ -970,22 +908,19 @@ static int launch_wgrad(const GatherParams& p, const void* x, const void* dy, co
                 // (0.235 vs 0.246 ms on layer 1; a 3-stage ring for it measured 0.242)
                 const uint32_t tk = p.K / 192;
                 wgrad_split(p, tk, 1, lds_bytes(64, 192, mode), splits, rows);
-                EVE_WGRAD_LAUNCH(1, 3, 1, tk, 1);
+                tr_tile(EVE_WGRAD_TR(T, 1, 3, 1, 4), tk, 1);
             } else {
                 const uint32_t tk = (p.K + 255) / 256, tc = 1;
                 wgrad_split(p, tk, tc, lds_bytes(64, 256, mode), splits, rows);
-                if (mode == 1)      EVE_WGRAD_LAUNCH(1, 4, 1, tk, tc);
+                if (mode == 1)      tr_tile(EVE_WGRAD_TR(T, 1, 4, 1, 4), tk, tc);
                 else if (mode == 2) {
                     // RefineNet's planes (72x128 .. 5x8); its outer levels have 16 / 32 output channels
-                    if (p.Cout <= 16)      EVE_WGRAD_LAUNCH1(1, 4, 2, 1, tk, tc);
-                    else if (p.Cout <= 32) EVE_WGRAD_LAUNCH1(1, 4, 2, 2, tk, tc);
-                    else                   EVE_WGRAD_LAUNCH(1, 4, 2, tk, tc);
+                    if (p.Cout <= 16)      tr_tile(EVE_WGRAD_TR(T, 1, 4, 2, 1), tk, tc);
+                    else if (p.Cout <= 32) tr_tile(EVE_WGRAD_TR(T, 1, 4, 2, 2), tk, tc);
+                    else                   tr_tile(EVE_WGRAD_TR(T, 1, 4, 2, 4), tk, tc);
                 }
-                else                EVE_WGRAD_LAUNCH(1, 4, 0, tk, tc);
+                else                tr_tile(EVE_WGRAD_TR(T, 1, 4, 0, 4), tk, tc);
             }
-#undef EVE_WGRAD_LAUNCH
-#undef EVE_WGRAD_LAUNCH1
-#undef EVE_WGRAD_LAUNCH2
             return db ? 1 : 0;                              // 1: the bias gradient has been taken care of
         }
     }
@@ -1014,12 +949,6 @@ static int launch_wgrad(const GatherParams& p, const void* x, const void* dy, co
     return 0;
 }
 
-}  // namespace eve
-
-using namespace eve;
-
-namespace eve {
-
 // 3x3 / stride 2 / pad 1 forward of the trunk's down-sampling blocks on conv3x3s2_wg8_kernel (conv_wg8s2.h).  true: launched.
 template <typename HT>
 static bool launch_s2_fwd_wg8(const eve_conv_desc* d, const void* x, const void* w, const float* bias, int epi_act, void* y, hipStream_t s) {
@@ -1039,83 +968,14 @@ static bool launch_s2_fwd_wg8(const eve_conv_desc* d, const void* x, const void*
     Wg8Params g;
     g.N = d->N; g.Cin = d->Cin; g.Cout = d->Cout; g.flip = 0; g.K = 9 * d->Cin; g.x_bytes = (uint32_t)xb; g.w_bytes = (uint32_t)wb;
     g.tiles_n = (uint32_t)(d->Cout / cout_t); g.s2_py = 0;
-#define EVE_S2F_LAUNCH(WM_, WN_, W_)                                                                                       \
-    do {                                                                                                                  \
-        using G8 = Wg8S2Geom<WM_, WN_, W_>;                                                                                 \
-        static bool attr_done = false;                                                                                    \
-        if (!attr_done) {                                                                                                 \
-            (void)hipFuncSetAttribute((const void*)conv3x3s2_wg8_kernel<HT, WM_, WN_, W_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            attr_done = true;                                                                                             \
-        }                                                                                                                 \
-        EVE_LAUNCH(EVE_HNAME(HT, "conv3x3s2_wg8_kernel<", ", " #WM_ ", " #WN_ ", " #W_ ">"), (conv3x3s2_wg8_kernel<HT, WM_, WN_, W_>), \
-                   dim3(tiles), dim3(512), G8::LDS, s, g, (const HT*)x, (const HT*)w, bias, epi_act, (HT*)y);                   \
-    } while (0)
-    if (W == 16) EVE_S2F_LAUNCH(4, 2, 16);
-    else if (W == 8) EVE_S2F_LAUNCH(2, 4, 8);
-    else EVE_S2F_LAUNCH(2, 4, 4);
-#undef EVE_S2F_LAUNCH
+    auto s2_tile = [&](auto kernel, auto geom) {
+        launch(kernel, dim3(tiles), dim3(512), decltype(geom)::LDS, s, g, (const HT*)x, (const HT*)w, bias, epi_act, (HT*)y);
+    };
+    if (W == 16) s2_tile(EVE_KERNEL_H(HT, conv3x3s2_wg8_kernel, 4, 2, 16), Wg8S2Geom<4, 2, 16>{});
+    else if (W == 8) s2_tile(EVE_KERNEL_H(HT, conv3x3s2_wg8_kernel, 2, 4, 8), Wg8S2Geom<2, 4, 8>{});
+    else s2_tile(EVE_KERNEL_H(HT, conv3x3s2_wg8_kernel, 2, 4, 4), Wg8S2Geom<2, 4, 4>{});
     return true;
 }
-
-}  // namespace eve
-
-extern "C" int eve_conv2d_fwd(const eve_conv_desc* d, const void* x, const void* w_ohwi, const float* bias,
-                              int epi_act, const float* in_scale_shift, int pro_act, void* y,
-                              eve_stream_t stream) {
-    const int vec = (d && d->dtype != EVE_DT_F32) ? 8 : 4;
-    if (int e = check_desc(d, vec)) return e;
-    if (!x || !w_ohwi || !y) return set_error_msg("conv2d_fwd: null pointer");
-    GatherParams p = fwd_params(d);
-    hipStream_t s = (hipStream_t)stream;
-    if (!in_scale_shift && d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->dtype != EVE_DT_F32) {    // streaming 1x1
-        const long long M = (long long)d->N * d->OH * d->OW;
-        bool done = false;
-        EVE_DISPATCH_H16(d->dtype, done = launch_conv1x1_stream<H>(M, d->Cin, d->Cout, x, w_ohwi, bias, epi_act, y, s));
-        if (done) { EVE_CHECK_LAUNCH(); return 0; }
-    }
-    if (!in_scale_shift && !bias && epi_act == EVE_ACT_NONE && d->KH == 1 && d->stride == 2 && d->dtype != EVE_DT_F32) {    // the trunk's shortcuts
-        bool done = false;
-        EVE_DISPATCH_H16(d->dtype, done = launch_conv1x1_s2_stream<H>(d, false, x, w_ohwi, y, s));
-        if (done) { EVE_CHECK_LAUNCH(); return 0; }
-    }
-    if (!in_scale_shift && d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->dtype != EVE_DT_F32) {    // row-streaming 3x3
-        bool done = false;
-        EVE_DISPATCH_H16(d->dtype, done = launch_conv3x3_stream<H>(d->N, d->IH, d->IW, d->Cin, d->Cout, 0, x, w_ohwi, bias, epi_act, y, s));
-        if (done) { EVE_CHECK_LAUNCH(); return 0; }
-    }
-    if (!in_scale_shift) {          // the trunk's stride-2 3x3 layers: parity planes of the input as rotating halo stages
-        if (d->dtype == EVE_DT_BF16 && launch_s2_fwd_wg8<bf16_t>(d, x, w_ohwi, bias, epi_act, y, s)) { EVE_CHECK_LAUNCH(); return 0; }
-        if (d->dtype == EVE_DT_F16 && launch_s2_fwd_wg8<f16_t>(d, x, w_ohwi, bias, epi_act, y, s)) { EVE_CHECK_LAUNCH(); return 0; }
-    }
-    if (d->dtype == EVE_DT_BF16) launch_igemm<bf16_t>(p, x, w_ohwi, bias, in_scale_shift, pro_act, epi_act, y, s);
-    else if (d->dtype == EVE_DT_F16) launch_igemm<f16_t>(p, x, w_ohwi, bias, in_scale_shift, pro_act, epi_act, y, s);
-    else                         launch_igemm<float>(p, x, w_ohwi, bias, in_scale_shift, pro_act, epi_act, y, s);
-    EVE_CHECK_LAUNCH();
-    return 0;
-}
-
-/* eve_conv2d_fwd that ALSO emits the InstanceNorm2d statistics of its output (mean, rstd per (n, c); biased variance) when the
-   kernel it dispatches walks whole images -- the row-streaming 3x3 kernel (conv_3x3s.h): RefineNet's pre-activation blocks
-   normalise every convolution's output (refine_net.py:45-53), and on the big planes that statistics pass was a launch of its
-   own.  *stats_written = 1 when mean_rstd [N][Cout][2] was filled, 0 when the shape went to another kernel (the caller then
-   runs eve_instnorm_stats as before). */
-extern "C" int eve_conv2d_fwd_stats(const eve_conv_desc* d, const void* x, const void* w_ohwi, const float* bias, int epi_act,
-                                    void* y, float* mean_rstd, float eps, int* stats_written, eve_stream_t stream) {
-    if (!stats_written || !mean_rstd) return set_error_msg("conv2d_fwd_stats: null pointer");
-    *stats_written = 0;
-    const int vec = (d && d->dtype != EVE_DT_F32) ? 8 : 4;
-    if (int e = check_desc(d, vec)) return e;
-    if (!x || !w_ohwi || !y) return set_error_msg("conv2d_fwd_stats: null pointer");
-    if (d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->dtype != EVE_DT_F32 && !(epi_act & EVE_EPI_ACC)) {
-        bool done = false;
-        EVE_DISPATCH_H16(d->dtype, done = launch_conv3x3_stream<H>(d->N, d->IH, d->IW, d->Cin, d->Cout, 0, x, w_ohwi, bias, epi_act, y,
-                                                                   (hipStream_t)stream, mean_rstd, eps));
-        if (done) { *stats_written = 1; EVE_CHECK_LAUNCH(); return 0; }
-    }
-    return eve_conv2d_fwd(d, x, w_ohwi, bias, epi_act, nullptr, 0, y, stream);
-}
-
-namespace eve {
 
 // Filters of the stride-2 data gradient as conv3x3_wg8_kernel<.., NT> wants them (see there): for output row parity py,
 // W'[px * Cdx + ci][t][co] = w_ihwo[ci][kh][kw][co] with kh = py + 1 - 2 dy, kw = px + 1 - 2 dx for the window position
@@ -1138,6 +998,10 @@ __global__ __launch_bounds__(256) void s2_dgrad_pack_kernel(const H* __restrict_
         reinterpret_cast<uint4*>(py ? w1 : w0)[r] = q;
     }
 }
+
+// conv3x3_wg8_kernel<.., NT> as row_parity (launch_s2_dgrad_wg8) takes it: under the name the attribution has always used for it
+// ("s2dgradNT"), with its tile geometry and NT
+#define EVE_S2_DGRAD(H, WM, WN, W, NT) eve::Named<conv3x3_wg8_kernel<H, WM, WN, W, NT>>{EVE_HNAME(H, "conv3x3_wg8_kernel<", ", " #WM ", " #WN ", " #W ", s2dgrad" #NT ">")}, Wg8Geom<WM, WN, W>{}, ic<NT>{}
 
 // true: launched.  dy [N][OW][OW][Cout] -> dx [N][2 OW][2 OW][Cdx]
 template <typename HT>
@@ -1165,96 +1029,144 @@ static bool launch_s2_dgrad_wg8(const eve_conv_desc* d, const void* dy, const vo
                        (const HT*)w_ihwo, w0, w1, Cdx, Co);
     Wg8Params g;
     g.N = d->N; g.Cin = Co; g.Cout = 2 * Cdx; g.flip = 0; g.x_bytes = (uint32_t)xb; g.tiles_n = (uint32_t)(2 * Cdx / cout_t);
-#define EVE_S2_LAUNCH(WM_, WN_, W_, NT_, WPTR, PY)                                                                          \
-    do {                                                                                                                  \
-        using G8 = Wg8Geom<WM_, WN_, W_>;                                                                                   \
-        static bool attr_done = false;                                                                                    \
-        if (!attr_done) {                                                                                                 \
-            (void)hipFuncSetAttribute((const void*)conv3x3_wg8_kernel<HT, WM_, WN_, W_, NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            attr_done = true;                                                                                             \
-        }                                                                                                                 \
-        g.K = NT_ * Co; g.w_bytes = (uint32_t)((unsigned long long)2 * Cdx * NT_ * Co * 2); g.s2_py = PY;                   \
-        EVE_LAUNCH(EVE_HNAME(HT, "conv3x3_wg8_kernel<", ", " #WM_ ", " #WN_ ", " #W_ ", s2dgrad" #NT_ ">"), (conv3x3_wg8_kernel<HT, WM_, WN_, W_, NT_>), \
-                   dim3(tiles), dim3(512), G8::LDS, s, g, (const HT*)dy, (const HT*)(WPTR), (const float*)nullptr, (int)EVE_ACT_NONE, (HT*)dx); \
-    } while (0)
-    if (W == 16) { EVE_S2_LAUNCH(4, 2, 16, 2, w0, 0); EVE_S2_LAUNCH(4, 2, 16, 4, w1, 1); }
-    else if (W == 8) { EVE_S2_LAUNCH(2, 4, 8, 2, w0, 0); EVE_S2_LAUNCH(2, 4, 8, 4, w1, 1); }
-    else { EVE_S2_LAUNCH(2, 4, 4, 2, w0, 0); EVE_S2_LAUNCH(2, 4, 4, 4, w1, 1); }
-#undef EVE_S2_LAUNCH
+    // the output rows of parity py, from the NT-position filters wp
+    auto row_parity = [&](auto kernel, auto geom, auto nt, const HT* wp, int py) {
+        constexpr int NT = decltype(nt)::value;
+        g.K = NT * Co; g.w_bytes = (uint32_t)((unsigned long long)2 * Cdx * NT * Co * 2); g.s2_py = py;
+        launch(kernel, dim3(tiles), dim3(512), decltype(geom)::LDS, s, g, (const HT*)dy, wp, (const float*)nullptr, (int)EVE_ACT_NONE, (HT*)dx);
+    };
+    if (W == 16) { row_parity(EVE_S2_DGRAD(HT, 4, 2, 16, 2), w0, 0); row_parity(EVE_S2_DGRAD(HT, 4, 2, 16, 4), w1, 1); }
+    else if (W == 8) { row_parity(EVE_S2_DGRAD(HT, 2, 4, 8, 2), w0, 0); row_parity(EVE_S2_DGRAD(HT, 2, 4, 8, 4), w1, 1); }
+    else { row_parity(EVE_S2_DGRAD(HT, 2, 4, 4, 2), w0, 0); row_parity(EVE_S2_DGRAD(HT, 2, 4, 4, 4), w1, 1); }
     return true;
+}
+
+// ---- the entry points' shared head and their ladders of specialised kernels ----
+// Descriptor, Cout where it is a vector dimension too (cout_msg: what to say; null = the forward, not checked; at most max_cout_vecs
+// vectors), operands present.  `who` names the entry in the messages.
+static int conv_entry(const char* who, const eve_conv_desc* d, const char* cout_msg, bool operands, int max_cout_vecs = INT_MAX) {
+    const int vec = (d && d->dtype != EVE_DT_F32) ? 8 : 4;
+    if (int e = check_desc(d, vec)) return e;
+    char msg[128];
+    if (cout_msg && (d->Cout % vec || d->Cout / vec > max_cout_vecs)) { snprintf(msg, sizeof(msg), "%s: %s", who, cout_msg); return set_error_msg(msg); }
+    if (!operands) { snprintf(msg, sizeof(msg), "%s: null pointer", who); return set_error_msg(msg); }
+    return 0;
+}
+
+// One convolution as the rungs see it: out = conv(in, w) (+ bias, epilogue), the forward or -- dgrad -- the data gradient, whose input is
+// dy with Cout channels and whose filters are IHWO.  A rung launches and returns true, or returns false: not its shape.
+struct ConvCall {
+    const char* who;                      // the entry point, for error messages
+    const eve_conv_desc* d;
+    bool dgrad;
+    const void* in; const void* w; const float* bias; int epi_act; void* out;
+    const float* in_scale_shift; int pro_act;                    // forward only: the (tested, unused) prologue, implicit GEMM alone has it
+    void* workspace; unsigned long long workspace_bytes;         // data gradient only
+    hipStream_t s;
+    int cin() const { return dgrad ? d->Cout : d->Cin; }
+    int cout() const { return dgrad ? d->Cin : d->Cout; }
+};
+typedef bool (*ConvRung)(const ConvCall&);
+
+// streaming 1x1 (the data gradient is a 1x1 convolution by [Cin][Cout])
+static bool rung_1x1_stream(const ConvCall& c) {
+    const eve_conv_desc* d = c.d;
+    if (!(d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0)) return false;
+    const long long M = (long long)d->N * d->OH * d->OW;
+    bool done = false;
+    EVE_DISPATCH_H16(d->dtype, done = launch_conv1x1_stream<H>(M, c.cin(), c.cout(), c.in, c.w, c.bias, c.epi_act, c.out, c.s));
+    return done;
+}
+// the trunk's 1x1 / stride-2 shortcuts; accumulating data gradient: one pixel in four of dx is touched
+static bool rung_1x1_s2_stream(const ConvCall& c) {
+    const eve_conv_desc* d = c.d;
+    if (!(!c.bias && c.epi_act == (c.dgrad ? (int)EVE_EPI_ACC : (int)EVE_ACT_NONE) && d->KH == 1 && d->stride == 2)) return false;
+    bool done = false;
+    EVE_DISPATCH_H16(d->dtype, done = launch_conv1x1_s2_stream<H>(d, c.dgrad, c.in, c.w, c.out, c.s));
+    return done;
+}
+// row-streaming 3x3 (data gradient: mirrored taps)
+static bool rung_3x3_stream(const ConvCall& c) {
+    const eve_conv_desc* d = c.d;
+    if (!(d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1)) return false;
+    bool done = false;
+    EVE_DISPATCH_H16(d->dtype, done = launch_conv3x3_stream<H>(d->N, d->IH, d->IW, c.cin(), c.cout(), c.dgrad ? 1 : 0, c.in, c.w, c.bias, c.epi_act,
+                                                               c.out, c.s));
+    return done;
+}
+// the trunk's stride-2 3x3 layers on eight-wave workgroups.  Forward: parity planes of the input as rotating halo stages; data gradient:
+// two launches over the dy halo tile instead of four per-tap parity-class launches
+static bool rung_s2_wg8(const ConvCall& c) {
+    bool done = false;
+    if (c.dgrad) EVE_DISPATCH_H16(c.d->dtype, done = launch_s2_dgrad_wg8<H>(c.d, c.in, c.w, c.out, c.workspace, c.workspace_bytes, c.s));
+    else         EVE_DISPATCH_H16(c.d->dtype, done = launch_s2_fwd_wg8<H>(c.d, c.in, c.w, c.bias, c.epi_act, c.out, c.s));
+    return done;
+}
+// The rungs in order (16-bit types without a prologue only: every one of them is a streaming or LDS-DMA kernel), then implicit GEMM.
+static int conv_ladder(const ConvCall& c, std::initializer_list<ConvRung> rungs) {
+    bool done = false;
+    if (!c.in_scale_shift && c.d->dtype != EVE_DT_F32)
+        for (ConvRung rung : rungs)
+            if ((done = rung(c))) break;
+    if (!done) {
+        const GatherParams p = c.dgrad ? dgrad_params(c.d) : fwd_params(c.d);
+        EVE_DISPATCH_T(c.d->dtype, launch_igemm<T>(p, c.in, c.w, c.bias, c.in_scale_shift, c.pro_act, c.epi_act, c.out, c.s));
+    }
+    const hipError_t e = take_launch_error();
+    return e == hipSuccess ? 0 : set_error(e, c.who);
 }
 
 }  // namespace eve
 
+using namespace eve;
+
+extern "C" int eve_conv2d_fwd(const eve_conv_desc* d, const void* x, const void* w_ohwi, const float* bias,
+                              int epi_act, const float* in_scale_shift, int pro_act, void* y,
+                              eve_stream_t stream) {
+    if (int e = conv_entry("conv2d_fwd", d, nullptr, x && w_ohwi && y)) return e;
+    const ConvCall c = {__func__, d, false, x, w_ohwi, bias, epi_act, y, in_scale_shift, pro_act, nullptr, 0, (hipStream_t)stream};
+    return conv_ladder(c, {rung_1x1_stream, rung_1x1_s2_stream, rung_3x3_stream, rung_s2_wg8});
+}
+
+/* eve_conv2d_fwd that ALSO emits the InstanceNorm2d statistics of its output (mean, rstd per (n, c); biased variance) when the
+   kernel it dispatches walks whole images -- the row-streaming 3x3 kernel (conv_3x3s.h): RefineNet's pre-activation blocks
+   normalise every convolution's output (refine_net.py:45-53), and on the big planes that statistics pass was a launch of its
+   own.  *stats_written = 1 when mean_rstd [N][Cout][2] was filled, 0 when the shape went to another kernel (the caller then
+   runs eve_instnorm_stats as before). */
+extern "C" int eve_conv2d_fwd_stats(const eve_conv_desc* d, const void* x, const void* w_ohwi, const float* bias, int epi_act,
+                                    void* y, float* mean_rstd, float eps, int* stats_written, eve_stream_t stream) {
+    if (!stats_written || !mean_rstd) return set_error_msg("conv2d_fwd_stats: null pointer");
+    *stats_written = 0;
+    if (int e = conv_entry("conv2d_fwd_stats", d, nullptr, x && w_ohwi && y)) return e;
+    if (d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->dtype != EVE_DT_F32 && !(epi_act & EVE_EPI_ACC)) {
+        bool done = false;
+        EVE_DISPATCH_H16(d->dtype, done = launch_conv3x3_stream<H>(d->N, d->IH, d->IW, d->Cin, d->Cout, 0, x, w_ohwi, bias, epi_act, y,
+                                                                   (hipStream_t)stream, mean_rstd, eps));
+        if (done) { *stats_written = 1; EVE_CHECK_LAUNCH(); return 0; }
+    }
+    return eve_conv2d_fwd(d, x, w_ohwi, bias, epi_act, nullptr, 0, y, stream);
+}
+
 extern "C" int eve_conv2d_dgrad(const eve_conv_desc* d, const void* dy, const void* w_ihwo, void* dx,
                                 void* workspace, unsigned long long workspace_bytes, eve_stream_t stream) {
-    const int vec = (d && d->dtype != EVE_DT_F32) ? 8 : 4;
-    if (int e = check_desc(d, vec)) return e;
-    if (d->Cout % vec) return set_error_msg("conv2d_dgrad: Cout must be a multiple of the 16-byte vector");
-    if (!dy || !w_ihwo || !dx) return set_error_msg("conv2d_dgrad: null pointer");
-    GatherParams p = dgrad_params(d);
-    hipStream_t s = (hipStream_t)stream;
-    if (d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->dtype != EVE_DT_F32) {    // 1x1: a 1x1 convolution by [Cin][Cout]
-        const long long M = (long long)d->N * d->OH * d->OW;
-        bool done = false;
-        EVE_DISPATCH_H16(d->dtype, done = launch_conv1x1_stream<H>(M, d->Cout, d->Cin, dy, w_ihwo, nullptr, 0, dx, s));
-        if (done) { EVE_CHECK_LAUNCH(); return 0; }
-    }
-    if (d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->dtype != EVE_DT_F32) {    // row-streaming 3x3, mirrored taps
-        bool done = false;
-        EVE_DISPATCH_H16(d->dtype, done = launch_conv3x3_stream<H>(d->N, d->IH, d->IW, d->Cout, d->Cin, 1, dy, w_ihwo, nullptr, 0, dx, s));
-        if (done) { EVE_CHECK_LAUNCH(); return 0; }
-    }
-    // stride-2 3x3 layers: two eight-wave launches over the dy halo tile instead of four per-tap parity-class launches
-    if (d->dtype == EVE_DT_BF16 && launch_s2_dgrad_wg8<bf16_t>(d, dy, w_ihwo, dx, workspace, workspace_bytes, s)) { EVE_CHECK_LAUNCH(); return 0; }
-    if (d->dtype == EVE_DT_F16 && launch_s2_dgrad_wg8<f16_t>(d, dy, w_ihwo, dx, workspace, workspace_bytes, s)) { EVE_CHECK_LAUNCH(); return 0; }
-    if (d->dtype == EVE_DT_BF16) launch_igemm<bf16_t>(p, dy, w_ihwo, nullptr, nullptr, 0, 0, dx, s);
-    else if (d->dtype == EVE_DT_F16) launch_igemm<f16_t>(p, dy, w_ihwo, nullptr, nullptr, 0, 0, dx, s);
-    else                         launch_igemm<float>(p, dy, w_ihwo, nullptr, nullptr, 0, 0, dx, s);
-    EVE_CHECK_LAUNCH();
-    return 0;
+    if (int e = conv_entry("conv2d_dgrad", d, "Cout must be a multiple of the 16-byte vector", dy && w_ihwo && dx)) return e;
+    const ConvCall c = {__func__, d, true, dy, w_ihwo, nullptr, 0, dx, nullptr, 0, workspace, workspace_bytes, (hipStream_t)stream};
+    return conv_ladder(c, {rung_1x1_stream, rung_3x3_stream, rung_s2_wg8});
 }
 
 /* dx += data gradient: the residual join of a ResNet block (autograd's add of the two branch gradients) fused
    into the convolution's epilogue.  dx must already hold the other branch's gradient. */
 extern "C" int eve_conv2d_dgrad_acc(const eve_conv_desc* d, const void* dy, const void* w_ihwo, void* dx,
                                     eve_stream_t stream) {
-    const int vec = (d && d->dtype != EVE_DT_F32) ? 8 : 4;
-    if (int e = check_desc(d, vec)) return e;
-    if (d->Cout % vec) return set_error_msg("conv2d_dgrad_acc: Cout must be a multiple of the 16-byte vector");
-    if (!dy || !w_ihwo || !dx) return set_error_msg("conv2d_dgrad_acc: null pointer");
-    GatherParams p = dgrad_params(d);
-    hipStream_t s = (hipStream_t)stream;
-    if (d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->dtype != EVE_DT_F32) {
-        const long long M = (long long)d->N * d->OH * d->OW;
-        bool done = false;
-        EVE_DISPATCH_H16(d->dtype, done = launch_conv1x1_stream<H>(M, d->Cout, d->Cin, dy, w_ihwo, nullptr, EVE_EPI_ACC, dx, s));
-        if (done) { EVE_CHECK_LAUNCH(); return 0; }
-    }
-    if (d->KH == 1 && d->stride == 2 && d->dtype != EVE_DT_F32) {    // the trunk's shortcuts: one pixel in four of dx is touched
-        bool done = false;
-        EVE_DISPATCH_H16(d->dtype, done = launch_conv1x1_s2_stream<H>(d, true, dy, w_ihwo, dx, s));
-        if (done) { EVE_CHECK_LAUNCH(); return 0; }
-    }
-    if (d->KH == 3 && d->KW == 3 && d->stride == 1 && d->pad == 1 && d->dtype != EVE_DT_F32) {
-        bool done = false;
-        EVE_DISPATCH_H16(d->dtype, done = launch_conv3x3_stream<H>(d->N, d->IH, d->IW, d->Cout, d->Cin, 1, dy, w_ihwo, nullptr, EVE_EPI_ACC, dx, s));
-        if (done) { EVE_CHECK_LAUNCH(); return 0; }
-    }
-    if (d->dtype == EVE_DT_BF16) launch_igemm<bf16_t>(p, dy, w_ihwo, nullptr, nullptr, 0, EVE_EPI_ACC, dx, s);
-    else if (d->dtype == EVE_DT_F16) launch_igemm<f16_t>(p, dy, w_ihwo, nullptr, nullptr, 0, EVE_EPI_ACC, dx, s);
-    else                         launch_igemm<float>(p, dy, w_ihwo, nullptr, nullptr, 0, EVE_EPI_ACC, dx, s);
-    EVE_CHECK_LAUNCH();
-    return 0;
+    if (int e = conv_entry("conv2d_dgrad_acc", d, "Cout must be a multiple of the 16-byte vector", dy && w_ihwo && dx)) return e;
+    const ConvCall c = {__func__, d, true, dy, w_ihwo, nullptr, EVE_EPI_ACC, dx, nullptr, 0, nullptr, 0, (hipStream_t)stream};
+    return conv_ladder(c, {rung_1x1_stream, rung_1x1_s2_stream, rung_3x3_stream});
 }
 
 extern "C" int eve_conv2d_wgrad(const eve_conv_desc* d, const void* x, const void* dy,
                                 const float* in_scale_shift, int pro_act, float* dw_ohwi,
                                 void* workspace, unsigned long long workspace_bytes, eve_stream_t stream) {
-    const int vec = (d && d->dtype != EVE_DT_F32) ? 8 : 4;
-    if (int e = check_desc(d, vec)) return e;
-    if (d->Cout % vec) return set_error_msg("conv2d_wgrad: Cout must be a multiple of the 16-byte vector");
-    if (!x || !dy || !dw_ohwi) return set_error_msg("conv2d_wgrad: null pointer");
+    if (int e = conv_entry("conv2d_wgrad", d, "Cout must be a multiple of the 16-byte vector", x && dy && dw_ohwi)) return e;
     GatherParams p = fwd_params(d);
     hipStream_t s = (hipStream_t)stream;
     if (d->dtype == EVE_DT_BF16) launch_wgrad<bf16_t>(p, x, dy, in_scale_shift, pro_act, dw_ohwi, s, nullptr, workspace, workspace_bytes);
@@ -1308,12 +1220,7 @@ static void launch_bias_grad(int dtype, long long M, int C, const void* dy, floa
     if (blocks > 2048) blocks = 2048;
     const long long rows = (M + blocks - 1) / blocks;
     blocks = (M + rows - 1) / rows;
-    if (dtype == EVE_DT_BF16)
-        hipLaunchKernelGGL(bias_grad_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, s, (const bf16_t*)dy, db, M, C, rows);
-    else if (dtype == EVE_DT_F16)
-        hipLaunchKernelGGL(bias_grad_kernel<f16_t>, dim3((unsigned)blocks), dim3(256), 0, s, (const f16_t*)dy, db, M, C, rows);
-    else
-        hipLaunchKernelGGL(bias_grad_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, (const float*)dy, db, M, C, rows);
+    EVE_DISPATCH_T(dtype, hipLaunchKernelGGL(bias_grad_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, s, (const T*)dy, db, M, C, rows));
 }
 
 extern "C" int eve_bias_grad(int dtype, long long M, int C, const void* dy, float* db, eve_stream_t stream) {
@@ -1330,10 +1237,7 @@ extern "C" int eve_bias_grad(int dtype, long long M, int C, const void* dy, floa
    dw and db are accumulated into. */
 extern "C" int eve_conv2d_wgrad_bias(const eve_conv_desc* d, const void* x, const void* dy, float* dw_ohwi, float* db,
                                      void* workspace, unsigned long long workspace_bytes, eve_stream_t stream) {
-    const int vec = (d && d->dtype != EVE_DT_F32) ? 8 : 4;
-    if (int e = check_desc(d, vec)) return e;
-    if (d->Cout % vec || d->Cout / vec > 256) return set_error_msg("conv2d_wgrad_bias: bad Cout");
-    if (!x || !dy || !dw_ohwi || !db) return set_error_msg("conv2d_wgrad_bias: null pointer");
+    if (int e = conv_entry("conv2d_wgrad_bias", d, "bad Cout", x && dy && dw_ohwi && db, 256)) return e;
     GatherParams p = fwd_params(d);
     hipStream_t s = (hipStream_t)stream;
     int fused = 0;

@@ -740,9 +740,7 @@ extern "C" int eve_act_bwd(int dtype, long long n, const void* dy, const void* y
                            eve_stream_t stream) {
     if (n <= 0 || !dy || !y || !dx) return set_error_msg("act_bwd: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == EVE_DT_BF16) hipLaunchKernelGGL(act_bwd_kernel<bf16_t>, dim3(stream_grid(n / 8 + 1)), dim3(256), 0, s, (const bf16_t*)dy, (const bf16_t*)y, act, (bf16_t*)dx, n);
-    else if (dtype == EVE_DT_F16) hipLaunchKernelGGL(act_bwd_kernel<f16_t>, dim3(stream_grid(n / 8 + 1)), dim3(256), 0, s, (const f16_t*)dy, (const f16_t*)y, act, (f16_t*)dx, n);
-    else                      hipLaunchKernelGGL(act_bwd_kernel<float>, dim3(stream_grid(n / 4 + 1)), dim3(256), 0, s, (const float*)dy, (const float*)y, act, (float*)dx, n);
+    EVE_DISPATCH_T(dtype, hipLaunchKernelGGL(act_bwd_kernel<T>, dim3(stream_grid(n / Elem<T>::VEC + 1)), dim3(256), 0, s, (const T*)dy, (const T*)y, act, (T*)dx, n));
     EVE_CHECK_LAUNCH();
     return 0;
 }
@@ -750,9 +748,7 @@ extern "C" int eve_act_bwd(int dtype, long long n, const void* dy, const void* y
 extern "C" int eve_add(int dtype, long long n, const void* a, const void* b, void* out, eve_stream_t stream) {
     if (n <= 0 || !a || !b || !out) return set_error_msg("add: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == EVE_DT_BF16) hipLaunchKernelGGL(add_kernel<bf16_t>, dim3(stream_grid(n / 8 + 1)), dim3(256), 0, s, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, n);
-    else if (dtype == EVE_DT_F16) hipLaunchKernelGGL(add_kernel<f16_t>, dim3(stream_grid(n / 8 + 1)), dim3(256), 0, s, (const f16_t*)a, (const f16_t*)b, (f16_t*)out, n);
-    else                      hipLaunchKernelGGL(add_kernel<float>, dim3(stream_grid(n / 4 + 1)), dim3(256), 0, s, (const float*)a, (const float*)b, (float*)out, n);
+    EVE_DISPATCH_T(dtype, hipLaunchKernelGGL(add_kernel<T>, dim3(stream_grid(n / Elem<T>::VEC + 1)), dim3(256), 0, s, (const T*)a, (const T*)b, (T*)out, n));
     EVE_CHECK_LAUNCH();
     return 0;
 }

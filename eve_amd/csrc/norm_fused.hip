@@ -908,9 +908,7 @@ extern "C" int eve_in_relu_maxpool_fwd(int dtype, int N, int IH, int IW, int C, 
     long long blocks = (items + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == EVE_DT_BF16) hipLaunchKernelGGL(in_relu_pool_fwd_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, s, (const bf16_t*)x, mean_rstd, (bf16_t*)y, idx, IH, IW, OH, OW, C, items);
-    else if (dtype == EVE_DT_F16) hipLaunchKernelGGL(in_relu_pool_fwd_kernel<f16_t>, dim3((unsigned)blocks), dim3(256), 0, s, (const f16_t*)x, mean_rstd, (f16_t*)y, idx, IH, IW, OH, OW, C, items);
-    else                      hipLaunchKernelGGL(in_relu_pool_fwd_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, (const float*)x, mean_rstd, (float*)y, idx, IH, IW, OH, OW, C, items);
+    EVE_DISPATCH_T(dtype, hipLaunchKernelGGL(in_relu_pool_fwd_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, s, (const T*)x, mean_rstd, (T*)y, idx, IH, IW, OH, OW, C, items));
     EVE_CHECK_LAUNCH();
     return 0;
 }
@@ -924,9 +922,7 @@ extern "C" int eve_in_relu_maxpool_bwd(int dtype, int N, int IH, int IW, int C, 
         return set_error_msg("in_relu_maxpool_bwd: bad arguments");
     const int OH = (IH - 1) / 2 + 1, OW = (IW - 1) / 2 + 1;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == EVE_DT_BF16) hipLaunchKernelGGL(in_relu_pool_bwd_kernel<bf16_t>, dim3(N), dim3(1024), 0, s, (const bf16_t*)dy_pool, (const bf16_t*)y_pool, idx, (const bf16_t*)x, mean_rstd, (bf16_t*)dx, IH, IW, OH, OW, C);
-    else if (dtype == EVE_DT_F16) hipLaunchKernelGGL(in_relu_pool_bwd_kernel<f16_t>, dim3(N), dim3(1024), 0, s, (const f16_t*)dy_pool, (const f16_t*)y_pool, idx, (const f16_t*)x, mean_rstd, (f16_t*)dx, IH, IW, OH, OW, C);
-    else                      hipLaunchKernelGGL(in_relu_pool_bwd_kernel<float>, dim3(N), dim3(1024), 0, s, (const float*)dy_pool, (const float*)y_pool, idx, (const float*)x, mean_rstd, (float*)dx, IH, IW, OH, OW, C);
+    EVE_DISPATCH_T(dtype, hipLaunchKernelGGL(in_relu_pool_bwd_kernel<T>, dim3(N), dim3(1024), 0, s, (const T*)dy_pool, (const T*)y_pool, idx, (const T*)x, mean_rstd, (T*)dx, IH, IW, OH, OW, C));
     EVE_CHECK_LAUNCH();
     return 0;
 }

@@ -440,9 +440,7 @@ extern "C" int eve_maxpool3x3s2_fwd(int dtype, int N, int IH, int IW, int C, con
     const int vec = dtype != EVE_DT_F32 ? 8 : 4;
     const long long items = (long long)N * OH * OW * (C / vec);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == EVE_DT_BF16) hipLaunchKernelGGL(maxpool_fwd_kernel<bf16_t>, dim3(sgrid(items)), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, idx, IH, IW, OH, OW, C, items);
-    else if (dtype == EVE_DT_F16) hipLaunchKernelGGL(maxpool_fwd_kernel<f16_t>, dim3(sgrid(items)), dim3(256), 0, s, (const f16_t*)x, (f16_t*)y, idx, IH, IW, OH, OW, C, items);
-    else                      hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(sgrid(items)), dim3(256), 0, s, (const float*)x, (float*)y, idx, IH, IW, OH, OW, C, items);
+    EVE_DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool_fwd_kernel<T>, dim3(sgrid(items)), dim3(256), 0, s, (const T*)x, (T*)y, idx, IH, IW, OH, OW, C, items));
     EVE_CHECK_LAUNCH();
     return 0;
 }
@@ -454,9 +452,7 @@ extern "C" int eve_maxpool3x3s2_bwd(int dtype, int N, int IH, int IW, int C, con
     const int vec = dtype != EVE_DT_F32 ? 8 : 4;
     const long long items = (long long)N * IH * IW * (C / vec);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == EVE_DT_BF16) hipLaunchKernelGGL(maxpool_bwd_kernel<bf16_t>, dim3(sgrid(items)), dim3(256), 0, s, (const bf16_t*)dy, idx, (bf16_t*)dx, IH, IW, OH, OW, C, items);
-    else if (dtype == EVE_DT_F16) hipLaunchKernelGGL(maxpool_bwd_kernel<f16_t>, dim3(sgrid(items)), dim3(256), 0, s, (const f16_t*)dy, idx, (f16_t*)dx, IH, IW, OH, OW, C, items);
-    else                      hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(sgrid(items)), dim3(256), 0, s, (const float*)dy, idx, (float*)dx, IH, IW, OH, OW, C, items);
+    EVE_DISPATCH_T(dtype, hipLaunchKernelGGL(maxpool_bwd_kernel<T>, dim3(sgrid(items)), dim3(256), 0, s, (const T*)dy, idx, (T*)dx, IH, IW, OH, OW, C, items));
     EVE_CHECK_LAUNCH();
     return 0;
 }
@@ -466,9 +462,7 @@ extern "C" int eve_avgpool_fwd(int dtype, int N, int HW, int C, const void* x, v
     const int vec = dtype != EVE_DT_F32 ? 8 : 4;
     const long long items = (long long)N * (C / vec);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == EVE_DT_BF16) hipLaunchKernelGGL(avgpool_fwd_kernel<bf16_t>, dim3(sgrid(items)), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, HW, C, items);
-    else if (dtype == EVE_DT_F16) hipLaunchKernelGGL(avgpool_fwd_kernel<f16_t>, dim3(sgrid(items)), dim3(256), 0, s, (const f16_t*)x, (f16_t*)y, HW, C, items);
-    else                      hipLaunchKernelGGL(avgpool_fwd_kernel<float>, dim3(sgrid(items)), dim3(256), 0, s, (const float*)x, (float*)y, HW, C, items);
+    EVE_DISPATCH_T(dtype, hipLaunchKernelGGL(avgpool_fwd_kernel<T>, dim3(sgrid(items)), dim3(256), 0, s, (const T*)x, (T*)y, HW, C, items));
     EVE_CHECK_LAUNCH();
     return 0;
 }
@@ -478,9 +472,7 @@ extern "C" int eve_avgpool_bwd(int dtype, int N, int HW, int C, const void* dy, 
     const int vec = dtype != EVE_DT_F32 ? 8 : 4;
     const long long items = (long long)N * HW * (C / vec);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == EVE_DT_BF16) hipLaunchKernelGGL(avgpool_bwd_kernel<bf16_t>, dim3(sgrid(items)), dim3(256), 0, s, (const bf16_t*)dy, (bf16_t*)dx, HW, C, items);
-    else if (dtype == EVE_DT_F16) hipLaunchKernelGGL(avgpool_bwd_kernel<f16_t>, dim3(sgrid(items)), dim3(256), 0, s, (const f16_t*)dy, (f16_t*)dx, HW, C, items);
-    else                      hipLaunchKernelGGL(avgpool_bwd_kernel<float>, dim3(sgrid(items)), dim3(256), 0, s, (const float*)dy, (float*)dx, HW, C, items);
+    EVE_DISPATCH_T(dtype, hipLaunchKernelGGL(avgpool_bwd_kernel<T>, dim3(sgrid(items)), dim3(256), 0, s, (const T*)dy, (T*)dx, HW, C, items));
     EVE_CHECK_LAUNCH();
     return 0;
 }
@@ -515,9 +507,7 @@ extern "C" int eve_adaptive_maxpool_fwd(int dtype, int N, int IH, int IW, int OH
     const int vec = dtype != EVE_DT_F32 ? 8 : 4;
     const long long items = (long long)N * OH * OW * (C / vec);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == EVE_DT_BF16) hipLaunchKernelGGL(adapool_fwd_kernel<bf16_t>, dim3(rgrid((long long)N * OH)), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, idx, IH, IW, OH, OW, C, items);
-    else if (dtype == EVE_DT_F16) hipLaunchKernelGGL(adapool_fwd_kernel<f16_t>, dim3(rgrid((long long)N * OH)), dim3(256), 0, s, (const f16_t*)x, (f16_t*)y, idx, IH, IW, OH, OW, C, items);
-    else                      hipLaunchKernelGGL(adapool_fwd_kernel<float>, dim3(rgrid((long long)N * OH)), dim3(256), 0, s, (const float*)x, (float*)y, idx, IH, IW, OH, OW, C, items);
+    EVE_DISPATCH_T(dtype, hipLaunchKernelGGL(adapool_fwd_kernel<T>, dim3(rgrid((long long)N * OH)), dim3(256), 0, s, (const T*)x, (T*)y, idx, IH, IW, OH, OW, C, items));
     EVE_CHECK_LAUNCH();
     return 0;
 }
@@ -529,9 +519,7 @@ extern "C" int eve_adaptive_maxpool_bwd(int dtype, int N, int IH, int IW, int OH
     const int vec = dtype != EVE_DT_F32 ? 8 : 4;
     const long long items = (long long)N * IH * IW * (C / vec);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == EVE_DT_BF16) hipLaunchKernelGGL(adapool_bwd_kernel<bf16_t>, dim3(rgrid((long long)N * IH)), dim3(256), 0, s, (const bf16_t*)dy, idx, (const bf16_t*)add, (bf16_t*)dx, IH, IW, OH, OW, C, items);
-    else if (dtype == EVE_DT_F16) hipLaunchKernelGGL(adapool_bwd_kernel<f16_t>, dim3(rgrid((long long)N * IH)), dim3(256), 0, s, (const f16_t*)dy, idx, (const f16_t*)add, (f16_t*)dx, IH, IW, OH, OW, C, items);
-    else                      hipLaunchKernelGGL(adapool_bwd_kernel<float>, dim3(rgrid((long long)N * IH)), dim3(256), 0, s, (const float*)dy, idx, (const float*)add, (float*)dx, IH, IW, OH, OW, C, items);
+    EVE_DISPATCH_T(dtype, hipLaunchKernelGGL(adapool_bwd_kernel<T>, dim3(rgrid((long long)N * IH)), dim3(256), 0, s, (const T*)dy, idx, (const T*)add, (T*)dx, IH, IW, OH, OW, C, items));
     EVE_CHECK_LAUNCH();
     return 0;
 }
@@ -542,9 +530,7 @@ extern "C" int eve_bilinear_fwd(int dtype, int N, int IH, int IW, int OH, int OW
     const int vec = dtype != EVE_DT_F32 ? 8 : 4;
     const long long items = (long long)N * OH * OW * (C / vec);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == EVE_DT_BF16) hipLaunchKernelGGL(bilinear_fwd_kernel<bf16_t>, dim3(rgrid((long long)N * OH)), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, IH, IW, OH, OW, C, items);
-    else if (dtype == EVE_DT_F16) hipLaunchKernelGGL(bilinear_fwd_kernel<f16_t>, dim3(rgrid((long long)N * OH)), dim3(256), 0, s, (const f16_t*)x, (f16_t*)y, IH, IW, OH, OW, C, items);
-    else                      hipLaunchKernelGGL(bilinear_fwd_kernel<float>, dim3(rgrid((long long)N * OH)), dim3(256), 0, s, (const float*)x, (float*)y, IH, IW, OH, OW, C, items);
+    EVE_DISPATCH_T(dtype, hipLaunchKernelGGL(bilinear_fwd_kernel<T>, dim3(rgrid((long long)N * OH)), dim3(256), 0, s, (const T*)x, (T*)y, IH, IW, OH, OW, C, items));
     EVE_CHECK_LAUNCH();
     return 0;
 }
@@ -555,9 +541,7 @@ extern "C" int eve_bilinear_bwd(int dtype, int N, int IH, int IW, int OH, int OW
     const int vec = dtype != EVE_DT_F32 ? 8 : 4;
     const long long items = (long long)N * IH * IW * (C / vec);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == EVE_DT_BF16) hipLaunchKernelGGL(bilinear_bwd_kernel<bf16_t>, dim3(rgrid((long long)N * IH)), dim3(256), 0, s, (const bf16_t*)dy, (bf16_t*)dx, IH, IW, OH, OW, C, items);
-    else if (dtype == EVE_DT_F16) hipLaunchKernelGGL(bilinear_bwd_kernel<f16_t>, dim3(rgrid((long long)N * IH)), dim3(256), 0, s, (const f16_t*)dy, (f16_t*)dx, IH, IW, OH, OW, C, items);
-    else                      hipLaunchKernelGGL(bilinear_bwd_kernel<float>, dim3(rgrid((long long)N * IH)), dim3(256), 0, s, (const float*)dy, (float*)dx, IH, IW, OH, OW, C, items);
+    EVE_DISPATCH_T(dtype, hipLaunchKernelGGL(bilinear_bwd_kernel<T>, dim3(rgrid((long long)N * IH)), dim3(256), 0, s, (const T*)dy, (T*)dx, IH, IW, OH, OW, C, items));
     EVE_CHECK_LAUNCH();
     return 0;
 }
@@ -568,9 +552,7 @@ extern "C" int eve_nchw_to_nhwc(int dtype_dst, int N, int C, int H, int W, int C
     const int vec = dtype_dst != EVE_DT_F32 ? 8 : 4;
     const long long items = (long long)N * H * W * (Cpad / vec);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype_dst == EVE_DT_BF16) hipLaunchKernelGGL(nchw_to_nhwc_kernel<bf16_t>, dim3(sgrid(items)), dim3(256), 0, s, src_nchw, (bf16_t*)dst_nhwc, C, H * W, Cpad, items);
-    else if (dtype_dst == EVE_DT_F16) hipLaunchKernelGGL(nchw_to_nhwc_kernel<f16_t>, dim3(sgrid(items)), dim3(256), 0, s, src_nchw, (f16_t*)dst_nhwc, C, H * W, Cpad, items);
-    else                          hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, dim3(sgrid(items)), dim3(256), 0, s, src_nchw, (float*)dst_nhwc, C, H * W, Cpad, items);
+    EVE_DISPATCH_T(dtype_dst, hipLaunchKernelGGL(nchw_to_nhwc_kernel<T>, dim3(sgrid(items)), dim3(256), 0, s, src_nchw, (T*)dst_nhwc, C, H * W, Cpad, items));
     EVE_CHECK_LAUNCH();
     return 0;
 }
@@ -580,9 +562,7 @@ extern "C" int eve_nhwc_to_nchw(int dtype_src, int N, int C, int H, int W, int C
     if (N <= 0 || C <= 0 || C > Cpad || H <= 0 || W <= 0 || !src_nhwc || !dst_nchw) return set_error_msg("nhwc_to_nchw: bad arguments");
     const long long items = (long long)N * C * H * W;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype_src == EVE_DT_BF16) hipLaunchKernelGGL(nhwc_to_nchw_kernel<bf16_t>, dim3(sgrid(items)), dim3(256), 0, s, (const bf16_t*)src_nhwc, dst_nchw, C, H * W, Cpad, items);
-    else if (dtype_src == EVE_DT_F16) hipLaunchKernelGGL(nhwc_to_nchw_kernel<f16_t>, dim3(sgrid(items)), dim3(256), 0, s, (const f16_t*)src_nhwc, dst_nchw, C, H * W, Cpad, items);
-    else                          hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, dim3(sgrid(items)), dim3(256), 0, s, (const float*)src_nhwc, dst_nchw, C, H * W, Cpad, items);
+    EVE_DISPATCH_T(dtype_src, hipLaunchKernelGGL(nhwc_to_nchw_kernel<T>, dim3(sgrid(items)), dim3(256), 0, s, (const T*)src_nhwc, dst_nchw, C, H * W, Cpad, items));
     EVE_CHECK_LAUNCH();
     return 0;
 }
@@ -621,9 +601,7 @@ extern "C" int eve_pack_weights_batch(int dtype_dst, int count, const eve_pack_i
     tb.count = count; tb.total = total;
     hipStream_t s = (hipStream_t)stream;
     const unsigned blocks = (unsigned)(total < 4096 ? total : 4096);
-    if (dtype_dst == EVE_DT_BF16) hipLaunchKernelGGL(pack_weights_batch_kernel<bf16_t>, dim3(blocks), dim3(256), 0, s, tb);
-    else if (dtype_dst == EVE_DT_F16) hipLaunchKernelGGL(pack_weights_batch_kernel<f16_t>, dim3(blocks), dim3(256), 0, s, tb);
-    else                          hipLaunchKernelGGL(pack_weights_batch_kernel<float>, dim3(blocks), dim3(256), 0, s, tb);
+    EVE_DISPATCH_T(dtype_dst, hipLaunchKernelGGL(pack_weights_batch_kernel<T>, dim3(blocks), dim3(256), 0, s, tb));
     EVE_CHECK_LAUNCH();
     return 0;
 }
@@ -633,9 +611,7 @@ extern "C" int eve_pack_weights(int dtype_dst, int Cout, int taps, int Cin, cons
     if (Cout <= 0 || taps <= 0 || Cin <= 0 || !w_ohwi || (!dst_ohwi && !dst_ihwo)) return set_error_msg("pack_weights: bad arguments");
     const long long n = (long long)Cout * taps * Cin;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype_dst == EVE_DT_BF16) hipLaunchKernelGGL(pack_weights_kernel<bf16_t>, dim3(sgrid(n)), dim3(256), 0, s, w_ohwi, (bf16_t*)dst_ohwi, (bf16_t*)dst_ihwo, Cout, taps, Cin, n);
-    else if (dtype_dst == EVE_DT_F16) hipLaunchKernelGGL(pack_weights_kernel<f16_t>, dim3(sgrid(n)), dim3(256), 0, s, w_ohwi, (f16_t*)dst_ohwi, (f16_t*)dst_ihwo, Cout, taps, Cin, n);
-    else                          hipLaunchKernelGGL(pack_weights_kernel<float>, dim3(sgrid(n)), dim3(256), 0, s, w_ohwi, (float*)dst_ohwi, (float*)dst_ihwo, Cout, taps, Cin, n);
+    EVE_DISPATCH_T(dtype_dst, hipLaunchKernelGGL(pack_weights_kernel<T>, dim3(sgrid(n)), dim3(256), 0, s, w_ohwi, (T*)dst_ohwi, (T*)dst_ihwo, Cout, taps, Cin, n));
     EVE_CHECK_LAUNCH();
     return 0;
 }

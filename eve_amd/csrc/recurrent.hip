@@ -545,36 +545,28 @@ extern "C" int eve_lstm_scan_bwd(int S, int T, int H, const float* dhs, const fl
 extern "C" int eve_cgru_gates1(int dtype, long long P, int C, const void* g1, const void* h, void* ru, void* rh,
                                eve_stream_t stream) {
     CG_CHECK("cgru_gates1")
-    if (dtype == EVE_DT_BF16) hipLaunchKernelGGL(cgru_gates1_kernel<bf16_t>, dim3(rgrid(items)), dim3(256), 0, s, (const bf16_t*)g1, (const bf16_t*)h, (bf16_t*)ru, (bf16_t*)rh, C, items);
-    else if (dtype == EVE_DT_F16) hipLaunchKernelGGL(cgru_gates1_kernel<f16_t>, dim3(rgrid(items)), dim3(256), 0, s, (const f16_t*)g1, (const f16_t*)h, (f16_t*)ru, (f16_t*)rh, C, items);
-    else                      hipLaunchKernelGGL(cgru_gates1_kernel<float>, dim3(rgrid(items)), dim3(256), 0, s, (const float*)g1, (const float*)h, (float*)ru, (float*)rh, C, items);
+    EVE_DISPATCH_T(dtype, hipLaunchKernelGGL(cgru_gates1_kernel<T>, dim3(rgrid(items)), dim3(256), 0, s, (const T*)g1, (const T*)h, (T*)ru, (T*)rh, C, items));
     EVE_CHECK_LAUNCH();
     return 0;
 }
 extern "C" int eve_cgru_gates2(int dtype, long long P, int C, const void* g2, const void* ru, const void* h, void* o,
                                void* hnew, eve_stream_t stream) {
     CG_CHECK("cgru_gates2")
-    if (dtype == EVE_DT_BF16) hipLaunchKernelGGL(cgru_gates2_kernel<bf16_t>, dim3(rgrid(items)), dim3(256), 0, s, (const bf16_t*)g2, (const bf16_t*)ru, (const bf16_t*)h, (bf16_t*)o, (bf16_t*)hnew, C, items);
-    else if (dtype == EVE_DT_F16) hipLaunchKernelGGL(cgru_gates2_kernel<f16_t>, dim3(rgrid(items)), dim3(256), 0, s, (const f16_t*)g2, (const f16_t*)ru, (const f16_t*)h, (f16_t*)o, (f16_t*)hnew, C, items);
-    else                      hipLaunchKernelGGL(cgru_gates2_kernel<float>, dim3(rgrid(items)), dim3(256), 0, s, (const float*)g2, (const float*)ru, (const float*)h, (float*)o, (float*)hnew, C, items);
+    EVE_DISPATCH_T(dtype, hipLaunchKernelGGL(cgru_gates2_kernel<T>, dim3(rgrid(items)), dim3(256), 0, s, (const T*)g2, (const T*)ru, (const T*)h, (T*)o, (T*)hnew, C, items));
     EVE_CHECK_LAUNCH();
     return 0;
 }
 extern "C" int eve_cgru_gates2_bwd(int dtype, long long P, int C, const void* dhnew, const void* ru, const void* h,
                                    const void* o, void* dg2, void* du, void* dh, eve_stream_t stream) {
     CG_CHECK("cgru_gates2_bwd")
-    if (dtype == EVE_DT_BF16) hipLaunchKernelGGL(cgru_gates2_bwd_kernel<bf16_t>, dim3(rgrid(items)), dim3(256), 0, s, (const bf16_t*)dhnew, (const bf16_t*)ru, (const bf16_t*)h, (const bf16_t*)o, (bf16_t*)dg2, (bf16_t*)du, (bf16_t*)dh, C, items);
-    else if (dtype == EVE_DT_F16) hipLaunchKernelGGL(cgru_gates2_bwd_kernel<f16_t>, dim3(rgrid(items)), dim3(256), 0, s, (const f16_t*)dhnew, (const f16_t*)ru, (const f16_t*)h, (const f16_t*)o, (f16_t*)dg2, (f16_t*)du, (f16_t*)dh, C, items);
-    else                      hipLaunchKernelGGL(cgru_gates2_bwd_kernel<float>, dim3(rgrid(items)), dim3(256), 0, s, (const float*)dhnew, (const float*)ru, (const float*)h, (const float*)o, (float*)dg2, (float*)du, (float*)dh, C, items);
+    EVE_DISPATCH_T(dtype, hipLaunchKernelGGL(cgru_gates2_bwd_kernel<T>, dim3(rgrid(items)), dim3(256), 0, s, (const T*)dhnew, (const T*)ru, (const T*)h, (const T*)o, (T*)dg2, (T*)du, (T*)dh, C, items));
     EVE_CHECK_LAUNCH();
     return 0;
 }
 extern "C" int eve_cgru_gates1_bwd(int dtype, long long P, int C, const void* drh, const void* du, const void* ru,
                                    const void* h, void* dg1, void* dh_accum, eve_stream_t stream) {
     CG_CHECK("cgru_gates1_bwd")
-    if (dtype == EVE_DT_BF16) hipLaunchKernelGGL(cgru_gates1_bwd_kernel<bf16_t>, dim3(rgrid(items)), dim3(256), 0, s, (const bf16_t*)drh, (const bf16_t*)du, (const bf16_t*)ru, (const bf16_t*)h, (bf16_t*)dg1, (bf16_t*)dh_accum, C, items);
-    else if (dtype == EVE_DT_F16) hipLaunchKernelGGL(cgru_gates1_bwd_kernel<f16_t>, dim3(rgrid(items)), dim3(256), 0, s, (const f16_t*)drh, (const f16_t*)du, (const f16_t*)ru, (const f16_t*)h, (f16_t*)dg1, (f16_t*)dh_accum, C, items);
-    else                      hipLaunchKernelGGL(cgru_gates1_bwd_kernel<float>, dim3(rgrid(items)), dim3(256), 0, s, (const float*)drh, (const float*)du, (const float*)ru, (const float*)h, (float*)dg1, (float*)dh_accum, C, items);
+    EVE_DISPATCH_T(dtype, hipLaunchKernelGGL(cgru_gates1_bwd_kernel<T>, dim3(rgrid(items)), dim3(256), 0, s, (const T*)drh, (const T*)du, (const T*)ru, (const T*)h, (T*)dg1, (T*)dh_accum, C, items));
     EVE_CHECK_LAUNCH();
     return 0;
 }
@@ -582,9 +574,7 @@ extern "C" int eve_cgru_gates1_bwd(int dtype, long long P, int C, const void* dr
 extern "C" int eve_clstm_gates_fwd(int dtype, long long P, int C, const void* gates, const void* c_prev, void* h,
                                    void* c, eve_stream_t stream) {
     CG_CHECK("clstm_gates_fwd")
-    if (dtype == EVE_DT_BF16) hipLaunchKernelGGL(clstm_gates_kernel<bf16_t>, dim3(rgrid(items)), dim3(256), 0, s, (const bf16_t*)gates, (const bf16_t*)c_prev, (bf16_t*)h, (bf16_t*)c, C, items);
-    else if (dtype == EVE_DT_F16) hipLaunchKernelGGL(clstm_gates_kernel<f16_t>, dim3(rgrid(items)), dim3(256), 0, s, (const f16_t*)gates, (const f16_t*)c_prev, (f16_t*)h, (f16_t*)c, C, items);
-    else                      hipLaunchKernelGGL(clstm_gates_kernel<float>, dim3(rgrid(items)), dim3(256), 0, s, (const float*)gates, (const float*)c_prev, (float*)h, (float*)c, C, items);
+    EVE_DISPATCH_T(dtype, hipLaunchKernelGGL(clstm_gates_kernel<T>, dim3(rgrid(items)), dim3(256), 0, s, (const T*)gates, (const T*)c_prev, (T*)h, (T*)c, C, items));
     EVE_CHECK_LAUNCH();
     return 0;
 }

@@ -275,56 +275,41 @@ __global__ __launch_bounds__(WS_THREADS) void scan_wide_bwd_kernel(int S, int T,
 
 static size_t ws_lds(int H, int buffers) { return (size_t)buffers * WS_TILE * (H + WS_PAD) * sizeof(float); }
 
-static void ws_set_attrs() {
-    static bool done = false;
-    if (done) return;
-    const int most = (int)ws_lds(1024, 2);
-    (void)hipFuncSetAttribute((const void*)scan_wide_fwd_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, most);
-    (void)hipFuncSetAttribute((const void*)scan_wide_fwd_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, most);
-    (void)hipFuncSetAttribute((const void*)scan_wide_fwd_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, most);
-    (void)hipFuncSetAttribute((const void*)scan_wide_bwd_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, most);
-    (void)hipFuncSetAttribute((const void*)scan_wide_bwd_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, most);
-    (void)hipFuncSetAttribute((const void*)scan_wide_bwd_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, most);
-    done = true;
-}
-
 bool scan_wide_ok(int H) { return H > 256 && H <= 1024 && H % 16 == 0; }
 
 // gates / hn_pre (GRU), cs / gates (LSTM), c0 (LSTM) as the kernels above name them; unused ones are null
 int scan_wide_fwd(int G, int S, int T, int H, const float* gi, const float* whh_t, const float* bhh, const float* h0, const float* c0,
                   float* hs, float* cs, float* gates, float* hn_pre, hipStream_t stream) {
-    ws_set_attrs();
     const dim3 grid((S + WS_TILE - 1) / WS_TILE), block(WS_THREADS);
     const size_t lds = ws_lds(H, 2);
-    if (G == 3)
-        EVE_LAUNCH("gru_scan_wide_fwd_kernel", scan_wide_fwd_kernel<3>, grid, block, lds, stream, S, T, H, gi, whh_t, bhh, h0, c0, hs, cs,
-                   gates, hn_pre);
-    else if (G == 1)
+    if (G == 1)
         EVE_LAUNCH("rnn_scan_wide_fwd_kernel", scan_wide_fwd_kernel<1>, grid, block, lds, stream, S, T, H, gi, whh_t, bhh, h0, c0, hs, cs,
+                   gates, hn_pre);
+    else if (G == 3)
+        EVE_LAUNCH("gru_scan_wide_fwd_kernel", scan_wide_fwd_kernel<3>, grid, block, lds, stream, S, T, H, gi, whh_t, bhh, h0, c0, hs, cs,
                    gates, hn_pre);
     else
         EVE_LAUNCH("lstm_scan_wide_fwd_kernel", scan_wide_fwd_kernel<4>, grid, block, lds, stream, S, T, H, gi, whh_t, bhh, h0, c0, hs, cs,
                    gates, hn_pre);
-    hipError_t e = hipGetLastError();
+    const hipError_t e = take_launch_error();
     return e == hipSuccess ? 0 : set_error(e, "scan_wide_fwd");
 }
 
 int scan_wide_bwd(int G, int S, int T, int H, const float* dhs, const float* dcs, const float* whh, const float* h0, const float* c0,
                   const float* hs, const float* cs, const float* gates, const float* hn_pre, float* out_a, float* out_b, float* dh0,
                   float* dc0, hipStream_t stream) {
-    ws_set_attrs();
     const dim3 grid((S + WS_TILE - 1) / WS_TILE), block(WS_THREADS);
     const size_t lds = ws_lds(H, G == 4 ? 2 : 1);
-    if (G == 3)
-        EVE_LAUNCH("gru_scan_wide_bwd_kernel", scan_wide_bwd_kernel<3>, grid, block, lds, stream, S, T, H, dhs, dcs, whh, h0, c0, hs, cs,
-                   gates, hn_pre, out_a, out_b, dh0, dc0);
-    else if (G == 1)
+    if (G == 1)
         EVE_LAUNCH("rnn_scan_wide_bwd_kernel", scan_wide_bwd_kernel<1>, grid, block, lds, stream, S, T, H, dhs, dcs, whh, h0, c0, hs, cs,
+                   gates, hn_pre, out_a, out_b, dh0, dc0);
+    else if (G == 3)
+        EVE_LAUNCH("gru_scan_wide_bwd_kernel", scan_wide_bwd_kernel<3>, grid, block, lds, stream, S, T, H, dhs, dcs, whh, h0, c0, hs, cs,
                    gates, hn_pre, out_a, out_b, dh0, dc0);
     else
         EVE_LAUNCH("lstm_scan_wide_bwd_kernel", scan_wide_bwd_kernel<4>, grid, block, lds, stream, S, T, H, dhs, dcs, whh, h0, c0, hs, cs,
                    gates, hn_pre, out_a, out_b, dh0, dc0);
-    hipError_t e = hipGetLastError();
+    const hipError_t e = take_launch_error();
     return e == hipSuccess ? 0 : set_error(e, "scan_wide_bwd");
 }
 

@@ -209,11 +209,6 @@ static int stem_dgrad_launch(int N, int IH, int IW, int C, const void* dconv, co
     if (bands < 1) bands = 1;
     const int band_rows = (OH + bands - 1) / bands;
     bands = (OH + band_rows - 1) / band_rows;
-    if (Tr::LDS_BYTES > 65536) {
-        static const hipError_t attr = hipFuncSetAttribute((const void*)stem_dgrad_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                           Tr::LDS_BYTES);
-        if (attr != hipSuccess) return set_error(attr, "stem_dgrad: LDS attribute");
-    }
     EVE_LAUNCH("stem_dgrad_kernel", stem_dgrad_kernel<T>, dim3((unsigned)(nstrip * bands), (unsigned)N), dim3(SD_THREADS),
                Tr::LDS_BYTES, stream, (const T*)dconv, (const T*)w_packed, dx, IH, IW, C, nstrip, band_rows);
     EVE_CHECK_LAUNCH();

@@ -1202,19 +1202,7 @@ extern "C" int eve_stem_fwd_fused(int dtype, int N, int IH, int IW, const void* 
     const unsigned long long xb = (unsigned long long)N * (IH + 6) * SF_XROW;
     if (xb >= (1ull << 31)) return set_error_msg("stem_fwd_fused: packed input must stay below 2 GiB");
     const size_t lds = (size_t)SF_WAVES * SF_RING * SF_ROWB + SF_WBYTES + SF_WAVES * 64 * 2 * 4;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)stem_fwd_fused_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)stem_fwd_fused_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
     if (g_cfg.stem_fwd_pairs) {      // round 4: two waves per image, 32 channels each, 16 waves per CU
-        static bool attr2 = false;
-        if (!attr2) {
-            (void)hipFuncSetAttribute((const void*)stem_fwd_pairs_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)stem_fwd_pairs_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr2 = true;
-        }
         const size_t lds2 = (size_t)SP_PAIRS * SF_RING * SF_ROWB + SF_WBYTES + 64 + 16 * 32 * 4;     // + flags, per-channel shifts
         const unsigned blocks2 = N < 256 ? (unsigned)N : 256u;
         EVE_DISPATCH_H16(dtype, EVE_LAUNCH(EVE_HNAME(H, "stem_fwd_pairs_kernel<", ">"), stem_fwd_pairs_kernel<H>, dim3(blocks2), dim3(1024), lds2,
@@ -1241,12 +1229,6 @@ extern "C" int eve_stem_bwd_dx(int dtype, int N, int IH, int IW, const void* x_p
     const unsigned long long xb = (unsigned long long)N * (IH + 6) * SF_XROW;
     if (xb >= (1ull << 31)) return set_error_msg("stem_bwd_dx: packed input must stay below 2 GiB");
     const size_t lds = (size_t)SD_WAVES * SF_RING * SF_ROWB + SF_WBYTES + SD_WAVES * SF_KBYTES;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)stem_bwd_dx_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)stem_bwd_dx_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
     // two work items per image while that still fits the 256 x 8 wave slots (B <= 16 clips per GPU): see the kernel
     const int split = g_cfg.stem_split;
     const int halves = (split && 2 * N <= 256 * SD_WAVES && (IH & 7) == 0) ? 2 : 1;
@@ -1268,12 +1250,6 @@ extern "C" int eve_stem_bwd_wgrad(int dtype, int N, int IH, int IW, const void* 
         return set_error_msg("stem_bwd_wgrad: needs IW == 128 and IH a multiple of 4");
     const unsigned long long xb = (unsigned long long)N * (IH + 6) * SF_XROW;
     if (xb >= (1ull << 31)) return set_error_msg("stem_bwd_wgrad: packed input must stay below 2 GiB");
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)stem_bwd_wgrad_kernel<bf16_t, SB_PAIRS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)stem_bwd_wgrad_kernel<f16_t, SB_PAIRS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
     // Two workgroups of two pairs per CU (2 x 77 KB of LDS): the per-row barrier only ties the four waves of a workgroup, so the two
     // waves of a SIMD are in different phases of the row (fragment reads / MFMAs / gradient routing) most of the time (one workgroup
     // of four pairs: 0.866 ms at N = 1 920, two of two: 0.814).  Images are dealt round-robin over the workgroups first (pair p of
