@@ -54,6 +54,38 @@ def close(got, want, dtype, what, scale=None):
         '%s: relative L2 %.3e' % (what, rel)
 
 
+def half_ulp32(v):
+    """Half the float32 spacing at |v| (0 at 0)."""
+    _, e = torch.frexp(v.detach().float().cpu().abs())                 # |v| = m * 2^e, m in [0.5, 1): ulp = 2^(e - 24)
+    return torch.where(v.detach().cpu() == 0, torch.zeros((), dtype=torch.float64), torch.ldexp(torch.ones((), dtype=torch.float64), e - 25))
+
+
+def wgrad_within_the_arithmetic_bound(x, dy, K, stride, pad, results):
+    """The float32 dw / db of the 16-bit kernels were never rounded to 16 bits: products of two 16-bit values are exact in float32,
+    and a sum over the P = N * OH * OW pixels, accumulated in float32 in any order, is off by at most P * 2^-24 * sum |x| |dy| per
+    entry (P - 1 additions, each off by at most 2^-24 of a partial sum that the sum of magnitudes bounds), plus half a float32 ulp
+    of the value it is accumulated onto.  float64 reference and magnitude sum on the CPU, formed once for all `results`:
+    (what, got_dw | None, dw_onto | None, got_db | None, db_onto | None); prints max err / bound."""
+    N, OH, OW, Cout = dy.shape
+    Cin = x.shape[3]
+    P = N * OH * OW
+    x64, dy64 = x.double().permute(0, 3, 1, 2), dy.double().permute(0, 3, 1, 2)
+    dw64 = mag_w = None
+    if any(r[1] is not None for r in results):
+        dw64 = torch.nn.grad.conv2d_weight(x64, (Cout, Cin, K, K), dy64, stride, pad).permute(0, 2, 3, 1)
+        mag_w = torch.nn.grad.conv2d_weight(x64.abs(), (Cout, Cin, K, K), dy64.abs(), stride, pad).permute(0, 2, 3, 1)
+    db64, mag_b = dy.double().sum(dim=(0, 1, 2)), dy.double().abs().sum(dim=(0, 1, 2))
+    for what, got_dw, dw_onto, got_db, db_onto in results:
+        for name, got, onto, want, mag in (('dw', got_dw, dw_onto, dw64, mag_w), ('db', got_db, db_onto, db64, mag_b)):
+            if got is None:
+                continue
+            bound = P * 2.0 ** -24 * mag + (half_ulp32(onto) if onto is not None else 0.0)
+            err = (got.detach().cpu().double() - (want + (onto.detach().cpu().double() if onto is not None else 0.0))).abs()
+            ratio = float(torch.where(err > 0, err / bound, torch.zeros_like(err)).max())
+            print('%-40s %s max|err| %.3e  max err/bound %.4f' % (what, name, float(err.max()), ratio))
+            assert bool((err <= bound).all()), '%s: a %s entry is %.3f x its bound away from float64' % (what, name, ratio)
+
+
 CONV_CASES = [
     # N, IH, IW, Cin, Cout, K, stride, pad
     (3, 32, 32, 64, 64, 3, 1, 1),       # layer1
@@ -127,6 +159,9 @@ def test_conv_fwd_dgrad_wgrad(hip, ref, dtype, case):
     hip.conv2d_wgrad(dev(x), dev(dy), K, K, stride, pad, got_dw2, db=got_db2)
     close(got_dw2, want_dw + dw0, dtype, 'conv wgrad (+bias)')
     close(got_db2, want_db + db0, dtype, 'bias grad fused into wgrad')
+    if dtype != torch.float32:
+        wgrad_within_the_arithmetic_bound(x, dy, K, stride, pad, [('conv wgrad', got_dw, None, got_db, None),
+                                                                  ('conv wgrad (+bias)', got_dw2, dw0, got_db2, db0)])
 
 
 @pytest.mark.parametrize('dtype', DTYPES, ids=DT_IDS)
@@ -1096,6 +1131,8 @@ def test_band_resident_weight_gradient(hip, ref, case):
         close(plain, want_dw + dw0, torch.bfloat16, 'wgrad ' + mode)
         close(fused_dw, want_dw + dw0, torch.bfloat16, 'wgrad+bias ' + mode)
         close(fused_db, want_db + db0, torch.bfloat16, 'bias ' + mode)
+    wgrad_within_the_arithmetic_bound(x, dy, K, 1, pad, [(w + m, res[m][i], dw0, res[m][2] if i else None, db0 if i else None)
+                                                         for m in ('halo', 'tr') for i, w in ((0, 'wgrad '), (1, 'wgrad+bias '))])
     # same bf16 products, float32 accumulation in a different order
     scale = float(want_dw.abs().max())
     assert float((res['halo'][0] - res['tr'][0]).abs().max()) <= 2e-4 * scale + 1e-4
@@ -1155,6 +1192,7 @@ def test_conv_random_shapes_bf16(hip, ref, case):
     hip.conv2d_wgrad(dev(x), dev(dy), K, K, stride, pad, got_dw, db=got_db)
     close(got_dw, want_dw, dtype, 'conv wgrad')
     close(got_db, ref.bias_grad(dy, torch.zeros(Cout)), dtype, 'bias grad')
+    wgrad_within_the_arithmetic_bound(x, dy, K, stride, pad, [('conv wgrad', got_dw, None, got_db, None)])
 
 
 def test_heatmap_head_and_losses_match_aten():
