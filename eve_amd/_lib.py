@@ -94,6 +94,11 @@ SIGNATURES = {
     'eve_crnn_scan_fwd': [I, I, P, P, P, P, P, P, P],
     'eve_crnn_scan_bwd': [I, I, P, P, P, P, P, P, P],
     'eve_clstm_scan_fwd': [I, I, P, P, P, P, P, P, P, P],
+    'eve_cgru_scan_fwd_c': [I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P],
+    'eve_cgru_scan_bwd_c': [I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P],
+    'eve_crnn_scan_fwd_c': [I, I, I, P, P, P, P, P, P, P],
+    'eve_crnn_scan_bwd_c': [I, I, I, P, P, P, P, P, P, P],
+    'eve_clstm_scan_fwd_c': [I, I, I, P, P, P, P, P, P, P, P],
     'eve_rnn_scan_fwd': [I, I, I, P, P, P, P, P, P],
     'eve_rnn_scan_bwd': [I, I, I, P, P, P, P, P, P],
     'eve_lstm_scan_fwd': [I, I, I, P, P, P, P, P, P, P, P, P],

@@ -4,16 +4,22 @@
 // refine_net.py:132-176.  One persistent launch walks all T frames of a clip; before round 5 the float32 parity mode and the
 // CLSTM / CRNN cells ran T x (1-2 convolution launches + gate kernels + concatenations).
 //
-// Geometry is fixed by the model: 5 x 8 pixels, 64 hidden + 64 input channels.  One workgroup (512 threads, 8 waves) per
-// sequence.  In LDS, as floats: the zero-bordered 7 x 10 halo of the 128-channel convolution input (pixel stride 132 floats so
-// that the 16 pixels of a fragment read fall into different banks), the convolution output [40][<= 256], and the state(s).
+// Geometry: 5 x 8 pixels (fixed by the model), C hidden + C input channels with C = refine_net_num_features in {32, 64, 128}
+// as a template parameter (64 is the shipped configuration; its instantiations keep their pre-template kernel names and
+// arithmetic order).  One workgroup (512 threads, 8 waves) per sequence.  In LDS, as floats: the zero-bordered 7 x 10 halo of
+// the 2C-channel convolution input (pixel stride 2C + 4 floats so that the 16 pixels of a fragment read fall into different
+// banks: 68, 132 and 260 are all 4 mod 64, and the halo row stride 10 x (2C + 4) is 40 mod 64 for all three, so the three
+// widths have ONE bank pattern), the convolution output [40][<= 4C], and the state(s).
+//   LDS per workgroup:  C = 32: 19 KB halo + 10 / 20 KB output;  C = 64: 36 KB + 20 / 40 KB;  C = 128: 71 KB + 40 KB (CGRU, CRNN)
+//   or + 80 KB (CLSTM: 151 KB of the CU's 160 KB, all four gates of a frame in one piece).
 // A convolution is an implicit GEMM on v_mfma_f32_16x16x4_f32 (exact float32: an fmaf chain) with A = filter rows (16 output
 // channels x 4 k) straight from global memory / L2 as one 16-byte load per lane and 16-channel K block, B = 16 pixels x 4 k as
 // one ds_read_b128 from the halo; the four words of a lane's vector feed four MFMAs (K permutation: MFMA s takes word s of every
 // lane's vector; a sum is order-free, conv_igemm.hip uses the same trick), so a lane ends up with 4 consecutive output channels
 // of one pixel.  The 40 pixels are 2.5 tiles of 16: the third tile's upper half re-reads pixel 39 and is dropped.
 // Filter blocks are prefetched one K block ahead.  The matrix pipe runs float32 at the vector rate (157 TFLOP/s chip-wide), so
-// a frame is MFMA-time bound at ~13 us (gates_1) + ~7 us (gate_2): the T-sequential floor of this formulation with 8 waves.
+// at C = 64 a frame is MFMA-time bound at ~13 us (gates_1) + ~7 us (gate_2): the T-sequential floor of this formulation with
+// 8 waves; the arithmetic of a frame goes with C^2.
 //
 // Weight / bias gradients are NOT formed here: like the 16-bit scan (cgru_scan.hip) the backward emits the gradients of the
 // pre-activations for all frames and the caller runs ONE batched weight-gradient launch over the T*B frames.
@@ -21,21 +27,45 @@
 
 namespace eve {
 
-constexpr int CS_H = 5, CS_W = 8, CS_PIX = 40, CS_C = 64;
-constexpr int CS_STR = 132;                       // floats per halo pixel (128 channels + 4: bank spread)
-constexpr int CS_HALO = 7 * 10 * CS_STR;          // floats
+constexpr int CS_H = 5, CS_W = 8, CS_PIX = 40;
 constexpr int CS_NT = 512;
+
+// per-width constants: STR = floats per halo pixel (2C channels + 4: bank spread), HALO = the 7 x 10 halo in floats,
+// NE = elements of a [40][C] plane a thread owns in the element-wise phases
+template <int C>
+struct CsGeom {
+    static_assert(C == 32 || C == 64 || C == 128, "bottleneck width");
+    static constexpr int STR = 2 * C + 4;
+    static constexpr int HALO = 7 * 10 * STR;
+    static constexpr int NE = (CS_PIX * C + CS_NT - 1) / CS_NT;
+    static constexpr size_t lds_bytes(int out_ch) { return (size_t)(HALO + CS_PIX * out_ch) * sizeof(float); }
+};
 
 __device__ __forceinline__ float cs_sigmoid(float z) { return 1.f / (1.f + __expf(-z)); }   // = recurrent.hip's sigmoidf_
 
 // halo offset (floats) of pixel p's centre
-__device__ __forceinline__ int cs_halo_at(int p) { return (((p >> 3) + 1) * 10 + (p & 7) + 1) * CS_STR; }
+template <int STR>
+__device__ __forceinline__ int cs_halo_at(int p) { return (((p >> 3) + 1) * 10 + (p & 7) + 1) * STR; }
 
 // acc[nt][pt] += sum over K blocks kb in [kb0, kb1) of W[co][tap][ci] * halo[pixel + tap][ci]
 //   W: [COUT][9][CIN] floats (OHWI for a forward convolution; IHWO with FLIP for a data gradient: out[p] takes dy[p - (tap - 1)])
 //   a K block = 16 consecutive channels of one tap; kb = tap * (CIN / 16) + block
-template <int CIN, int NTILE, bool FLIP>
-__device__ __forceinline__ void cs_conv(const float* halo, const float* __restrict__ W, const int co0, const int kb0, const int kb1,
+// 4 consecutive filter values as floats: one 16-byte load (float32 banks) or one 8-byte load (16-bit banks; exact in float32)
+__device__ __forceinline__ float4 cs_ldw(const float* p) { return *reinterpret_cast<const float4*>(p); }
+template <typename WT>
+__device__ __forceinline__ float4 cs_ldw(const WT* p) {
+    const uint2 q = *reinterpret_cast<const uint2*>(p);
+    return make_float4(Elem<WT>::lo(q.x), Elem<WT>::hi(q.x), Elem<WT>::lo(q.y), Elem<WT>::hi(q.y));
+}
+// a value rounded to the storage format (identity for float32): the 16-bit instantiations round where cgru_scan1.hip does
+template <typename S>
+__device__ __forceinline__ float cs_rnd(float v) {
+    if constexpr (sizeof(S) == 4) return v;
+    else return Elem<S>::round(v);
+}
+
+template <int STR, int CIN, int NTILE, bool FLIP, typename WT>
+__device__ __forceinline__ void cs_conv(const float* halo, const WT* __restrict__ W, const int co0, const int kb0, const int kb1,
                                         f32x4_t (&acc)[NTILE][3], const int lane) {
     constexpr int KB_PER_TAP = CIN / 16;
     const int i = lane & 15, kk = lane >> 4;
@@ -43,25 +73,25 @@ __device__ __forceinline__ void cs_conv(const float* halo, const float* __restri
 #pragma unroll
     for (int pt = 0; pt < 3; ++pt) {
         const int p = min(pt * 16 + i, CS_PIX - 1);
-        boff[pt] = (((p >> 3)) * 10 + (p & 7)) * CS_STR + 4 * kk;          // + tap offset (dy * 10 + dx) * CS_STR
+        boff[pt] = (((p >> 3)) * 10 + (p & 7)) * STR + 4 * kk;             // + tap offset (dy * 10 + dx) * STR
     }
-    const float* wrow[NTILE];
+    const WT* wrow[NTILE];
 #pragma unroll
     for (int nt = 0; nt < NTILE; ++nt) wrow[nt] = W + (size_t)(co0 + nt * 16 + i) * (9 * CIN) + 4 * kk;
     float4 a_next[NTILE];
 #pragma unroll
-    for (int nt = 0; nt < NTILE; ++nt) a_next[nt] = *reinterpret_cast<const float4*>(wrow[nt] + kb0 * 16);
-    for (int kb = kb0; kb < kb1; ++kb) {
+    for (int nt = 0; nt < NTILE; ++nt) a_next[nt] = cs_ldw(wrow[nt] + kb0 * 16);
+    auto step = [&](const int kb) {
         float4 a[NTILE];
 #pragma unroll
         for (int nt = 0; nt < NTILE; ++nt) a[nt] = a_next[nt];
         const int kn = min(kb + 1, kb1 - 1);
 #pragma unroll
-        for (int nt = 0; nt < NTILE; ++nt) a_next[nt] = *reinterpret_cast<const float4*>(wrow[nt] + kn * 16);
+        for (int nt = 0; nt < NTILE; ++nt) a_next[nt] = cs_ldw(wrow[nt] + kn * 16);
         const int tap = kb / KB_PER_TAP, blk = kb - tap * KB_PER_TAP;
         const int kh = tap / 3, kw = tap - kh * 3;
         const int dy = FLIP ? 2 - kh : kh, dx = FLIP ? 2 - kw : kw;
-        const int toff = (dy * 10 + dx) * CS_STR + blk * 16;
+        const int toff = (dy * 10 + dx) * STR + blk * 16;
         float4 b[3];
 #pragma unroll
         for (int pt = 0; pt < 3; ++pt) b[pt] = *reinterpret_cast<const float4*>(halo + boff[pt] + toff);
@@ -74,6 +104,14 @@ __device__ __forceinline__ void cs_conv(const float* halo, const float* __restri
                 acc[nt][pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[nt].z, b[pt].z, acc[nt][pt], 0, 0, 0);
                 acc[nt][pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[nt].w, b[pt].w, acc[nt][pt], 0, 0, 0);
             }
+    };
+    // C = 32 (STR = 68): 9 or 18 K blocks per wave -- left to itself the compiler unrolls the whole loop, hoists every filter load
+    // and spills; one block per iteration, like the longer loops of the wider instantiations
+    if constexpr (STR == 68) {
+#pragma unroll 1
+        for (int kb = kb0; kb < kb1; ++kb) step(kb);
+    } else {
+        for (int kb = kb0; kb < kb1; ++kb) step(kb);
     }
 }
 
@@ -109,89 +147,99 @@ __device__ __forceinline__ void cs_zero(f32x4_t (&acc)[NTILE][3]) {
 }
 
 // A whole convolution of the workgroup's halo into out[40][ostr]:  COUT / 16 tiles over the 8 waves.
-//   COUT = 256: two tiles per wave;  128: one;  64: one tile per wave PAIR, the pair splits K and the second half adds after
-//   a barrier (fixed order: the result does not depend on timing).  Ends with a barrier: `out` is complete, the halo is free.
-template <int CIN, int COUT, bool FLIP>
-__device__ __forceinline__ void cs_conv_all(const float* halo, const float* __restrict__ W, const float* __restrict__ bias,
+//   8 tiles or more (COUT = 128, 256, 512): COUT / 128 tiles per wave, each wave the whole K.
+//   fewer (COUT = 64, 32): a tile belongs to 8 / tiles waves which split K evenly; part 0 stores (with the bias), parts 1..
+//   add one after the other, a barrier between them (fixed order: the result does not depend on timing).
+// Ends with a barrier: `out` is complete, the halo is free.
+template <int STR, int CIN, int COUT, bool FLIP, typename WT>
+__device__ __forceinline__ void cs_conv_all(const float* halo, const WT* __restrict__ W, const float* __restrict__ bias,
                                             float* out, const int ostr, const int wave, const int lane) {
-    constexpr int KB = 9 * CIN / 16;
-    if constexpr (COUT == 256) {
-        f32x4_t acc[2][3];
-        cs_zero<2>(acc);
-        cs_conv<CIN, 2, FLIP>(halo, W, wave * 32, 0, KB, acc, lane);
-        cs_store<2, false>(out, ostr, wave * 32, bias, acc, lane);
-    } else if constexpr (COUT == 128) {
-        f32x4_t acc[1][3];
-        cs_zero<1>(acc);
-        cs_conv<CIN, 1, FLIP>(halo, W, wave * 16, 0, KB, acc, lane);
-        cs_store<1, false>(out, ostr, wave * 16, bias, acc, lane);
+    constexpr int KB = 9 * CIN / 16, TILES = COUT / 16;
+    static_assert(COUT % 16 == 0 && CIN % 16 == 0 && (TILES % 8 == 0 || 8 % TILES == 0), "COUT");
+    if constexpr (TILES >= 8) {
+        constexpr int NT = TILES / 8;
+        f32x4_t acc[NT][3];
+        cs_zero<NT>(acc);
+        cs_conv<STR, CIN, NT, FLIP, WT>(halo, W, wave * 16 * NT, 0, KB, acc, lane);
+        cs_store<NT, false>(out, ostr, wave * 16 * NT, bias, acc, lane);
     } else {
-        static_assert(COUT == 64, "COUT");
-        const int tile = wave & 3, half = wave >> 2;
+        constexpr int KS = 8 / TILES;                 // waves per tile
+        static_assert(KB % KS == 0, "K split");
+        const int tile = wave % TILES, part = wave / TILES;
         f32x4_t acc[1][3];
         cs_zero<1>(acc);
-        cs_conv<CIN, 1, FLIP>(halo, W, tile * 16, half * (KB / 2), half ? KB : KB / 2, acc, lane);
-        if (half == 0) cs_store<1, false>(out, ostr, tile * 16, bias, acc, lane);
-        __syncthreads();
-        if (half == 1) cs_store<1, true>(out, ostr, tile * 16, nullptr, acc, lane);
+        cs_conv<STR, CIN, 1, FLIP, WT>(halo, W, tile * 16, part * (KB / KS), (part + 1) * (KB / KS), acc, lane);
+        if (part == 0) cs_store<1, false>(out, ostr, tile * 16, bias, acc, lane);
+#pragma unroll
+        for (int s = 1; s < KS; ++s) {
+            __syncthreads();
+            if (part == s) cs_store<1, true>(out, ostr, tile * 16, nullptr, acc, lane);
+        }
     }
     __syncthreads();
 }
 
+template <int HALO>
 __device__ __forceinline__ void cs_zero_halo(float* halo, const int tid) {
-    for (int q = tid; q < CS_HALO; q += CS_NT) halo[q] = 0.f;
+    for (int q = tid; q < HALO; q += CS_NT) halo[q] = 0.f;
 }
 
-// the 5 elements a thread owns in every element-wise phase: e = tid + 512 k -> pixel e / 64, channel e % 64
-#define CS_FOR_ELEMS(k, p, c) _Pragma("unroll") for (int k = 0, p = tid >> 6, c = tid & 63; k < 5; ++k, p += 8)
+// the NE elements a thread owns in every element-wise phase: e = tid + 512 k -> pixel e / C, channel e % C (C = 32: 2.5 per
+// thread, the last half-round is masked).  Uses the kernel's `tid`, `C` and `G::NE`.
+#define CS_FOR_ELEMS(k, p, c)                                         \
+    _Pragma("unroll") for (int k = 0; k < G::NE; ++k)                 \
+        if (const int p = (tid + CS_NT * k) / C, c = (tid + CS_NT * k) % C; (CS_PIX * C) % CS_NT == 0 || p < CS_PIX)
 
 // ------------------------------------------------------------------------------------------------------------------------
-// CGRU forward.  xs [B][T][40][64]; h0 [B][40][64] or null; w1 OHWI [128][9][128] (inputs: x then h), w2 OHWI [64][9][128]
-// (inputs: r*h then x).  Outputs: hs [B][T][40][64]; time-major hs_tm, rh, og [T][B][40][64], ru [T][B][40][128].
+// CGRU forward.  xs [B][T][40][C]; h0 [B][40][C] or null; w1 OHWI [2C][9][2C] (inputs: x then h), w2 OHWI [C][9][2C]
+// (inputs: r*h then x).  Outputs: hs [B][T][40][C]; time-major hs_tm, rh, og [T][B][40][C], ru [T][B][40][2C].
 // ------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(CS_NT) void cgru_scan_f32_fwd_kernel(const int B, const int T, const float* __restrict__ xs,
-                                                                  const float* __restrict__ h0, const float* __restrict__ w1,
-                                                                  const float* __restrict__ b1, const float* __restrict__ w2,
-                                                                  const float* __restrict__ b2, float* __restrict__ hs,
-                                                                  float* __restrict__ hs_tm, float* __restrict__ ru,
-                                                                  float* __restrict__ rh, float* __restrict__ og) {
+template <int C, typename S = float>
+__global__ __launch_bounds__(CS_NT) void cgru_scan_f32_fwd_kernel(const int B, const int T, const S* __restrict__ xs,
+                                                                  const S* __restrict__ h0, const S* __restrict__ w1,
+                                                                  const float* __restrict__ b1, const S* __restrict__ w2,
+                                                                  const float* __restrict__ b2, S* __restrict__ hs,
+                                                                  S* __restrict__ hs_tm, S* __restrict__ ru,
+                                                                  S* __restrict__ rh, S* __restrict__ og) {
+    using G = CsGeom<C>;
+    constexpr int STR = G::STR, C2 = 2 * C;
     extern __shared__ __attribute__((aligned(16))) float cs_lds[];
     float* halo = cs_lds;
-    float* g = halo + CS_HALO;                       // [40][128]
+    float* g = halo + G::HALO;                       // [40][2C]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = blockIdx.x;
-    cs_zero_halo(halo, tid);
-    float h[5], x[5], u[5];
-    CS_FOR_ELEMS(k, p, c) h[k] = h0 ? h0[((size_t)b * CS_PIX + p) * CS_C + c] : 0.f;
+    cs_zero_halo<G::HALO>(halo, tid);
+    float h[G::NE], x[G::NE], u[G::NE];
+    CS_FOR_ELEMS(k, p, c) h[k] = h0 ? Elem<S>::ld(h0 + ((size_t)b * CS_PIX + p) * C + c) : 0.f;
     __syncthreads();
     for (int t = 0; t < T; ++t) {
-        const float* xt = xs + ((size_t)b * T + t) * (CS_PIX * CS_C);
+        const S* xt = xs + ((size_t)b * T + t) * (CS_PIX * C);
         const size_t tm = ((size_t)t * B + b) * CS_PIX;
         CS_FOR_ELEMS(k, p, c) {
-            x[k] = xt[p * CS_C + c];
-            halo[cs_halo_at(p) + c] = x[k];
-            halo[cs_halo_at(p) + CS_C + c] = h[k];
+            x[k] = Elem<S>::ld(xt + p * C + c);
+            halo[cs_halo_at<STR>(p) + c] = x[k];
+            halo[cs_halo_at<STR>(p) + C + c] = h[k];
         }
         __syncthreads();
-        cs_conv_all<128, 128, false>(halo, w1, b1, g, 128, wave, lane);
+        cs_conv_all<STR, C2, C2, false>(halo, w1, b1, g, C2, wave, lane);
         CS_FOR_ELEMS(k, p, c) {
-            const float r = cs_sigmoid(g[p * 128 + c]);
-            u[k] = cs_sigmoid(g[p * 128 + CS_C + c]);
-            const float v = r * h[k];
-            ru[(tm + p) * 128 + c] = r;
-            ru[(tm + p) * 128 + CS_C + c] = u[k];
-            rh[(tm + p) * CS_C + c] = v;
-            halo[cs_halo_at(p) + c] = v;
-            halo[cs_halo_at(p) + CS_C + c] = x[k];
+            const float r = cs_rnd<S>(cs_sigmoid(g[p * C2 + c]));       // (16-bit: the stored gate is the one every later stage sees)
+            u[k] = cs_rnd<S>(cs_sigmoid(g[p * C2 + C + c]));
+            const float v = cs_rnd<S>(r * h[k]);
+            Elem<S>::st(ru + (tm + p) * C2 + c, r);
+            Elem<S>::st(ru + (tm + p) * C2 + C + c, u[k]);
+            Elem<S>::st(rh + (tm + p) * C + c, v);
+            halo[cs_halo_at<STR>(p) + c] = v;
+            halo[cs_halo_at<STR>(p) + C + c] = x[k];
         }
         __syncthreads();
-        cs_conv_all<128, 64, false>(halo, w2, b2, g, 128, wave, lane);
+        cs_conv_all<STR, C2, C, false>(halo, w2, b2, g, C2, wave, lane);
         CS_FOR_ELEMS(k, p, c) {
-            const float o = tanhf(g[p * 128 + c]);
-            h[k] = (1.f - u[k]) * o + u[k] * h[k];
-            og[(tm + p) * CS_C + c] = o;
-            hs_tm[(tm + p) * CS_C + c] = h[k];
-            hs[(((size_t)b * T + t) * CS_PIX + p) * CS_C + c] = h[k];
+            const float o = cs_rnd<S>(tanhf(g[p * C2 + c]));
+            h[k] = cs_rnd<S>((1.f - u[k]) * o + u[k] * h[k]);
+            Elem<S>::st(og + (tm + p) * C + c, o);
+            Elem<S>::st(hs_tm + (tm + p) * C + c, h[k]);
+            Elem<S>::st(hs + (((size_t)b * T + t) * CS_PIX + p) * C + c, h[k]);
         }
         // (the next frame's halo writes follow conv_all's closing barrier; its reads of g precede the next conv's writes by the
         //  barrier after the halo fill)
@@ -200,223 +248,300 @@ __global__ __launch_bounds__(CS_NT) void cgru_scan_f32_fwd_kernel(const int B, c
 
 // ------------------------------------------------------------------------------------------------------------------------
 // CGRU backward (common.py:400-415 differentiated; the per-frame kernels are recurrent.hip's cgru_gates{2,1}_bwd).
-// Time-major inputs dhs_tm, og, hs_tm [T][B][40][64], ru [T][B][40][128]; w1t IHWO [128][9][128], w2t IHWO [128][9][64].
-// Outputs dg1_all [T][B][40][128], dg2_all, dxs_tm [T][B][40][64], dh0 [B][40][64] or null.
+// Time-major inputs dhs_tm, og, hs_tm [T][B][40][C], ru [T][B][40][2C]; w1t IHWO [2C][9][2C], w2t IHWO [2C][9][C].
+// Outputs dg1_all [T][B][40][2C], dg2_all, dxs_tm [T][B][40][C], dh0 [B][40][C] or null.
 // ------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(CS_NT) void cgru_scan_f32_bwd_kernel(const int B, const int T, const float* __restrict__ dhs_tm,
-                                                                  const float* __restrict__ ru, const float* __restrict__ og,
-                                                                  const float* __restrict__ hs_tm, const float* __restrict__ h0,
-                                                                  const float* __restrict__ w1t, const float* __restrict__ w2t,
-                                                                  float* __restrict__ dg1_all, float* __restrict__ dg2_all,
-                                                                  float* __restrict__ dxs_tm, float* __restrict__ dh0) {
+template <int C, typename S = float>
+__global__ __launch_bounds__(CS_NT) void cgru_scan_f32_bwd_kernel(const int B, const int T, const S* __restrict__ dhs_tm,
+                                                                  const S* __restrict__ ru, const S* __restrict__ og,
+                                                                  const S* __restrict__ hs_tm, const S* __restrict__ h0,
+                                                                  const S* __restrict__ w1t, const S* __restrict__ w2t,
+                                                                  S* __restrict__ dg1_all, S* __restrict__ dg2_all,
+                                                                  S* __restrict__ dxs_tm, S* __restrict__ dh0) {
+    using G = CsGeom<C>;
+    constexpr int STR = G::STR, C2 = 2 * C;
     extern __shared__ __attribute__((aligned(16))) float cs_lds[];
     float* halo = cs_lds;
-    float* g = halo + CS_HALO;                       // [40][128]
+    float* g = halo + G::HALO;                       // [40][2C]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = blockIdx.x;
-    cs_zero_halo(halo, tid);
-    float carry[5], du[5], dhd[5], r[5], u[5], hp[5], dx2[5];
+    cs_zero_halo<G::HALO>(halo, tid);
+    float carry[G::NE], du[G::NE], dhd[G::NE], r[G::NE], u[G::NE], hp[G::NE], dx2[G::NE];
     CS_FOR_ELEMS(k, p, c) carry[k] = 0.f;
     __syncthreads();
     for (int t = T - 1; t >= 0; --t) {
         const size_t tm = ((size_t)t * B + b) * CS_PIX;
         CS_FOR_ELEMS(k, p, c) {
-            const float d = dhs_tm[(tm + p) * CS_C + c] + carry[k];
-            r[k] = ru[(tm + p) * 128 + c];
-            u[k] = ru[(tm + p) * 128 + CS_C + c];
-            const float o = og[(tm + p) * CS_C + c];
-            hp[k] = t > 0 ? hs_tm[(((size_t)(t - 1) * B + b) * CS_PIX + p) * CS_C + c]
-                          : (h0 ? h0[((size_t)b * CS_PIX + p) * CS_C + c] : 0.f);
-            const float a = d * (1.f - u[k]) * (1.f - o * o);            // d(pre-tanh)
+            const float d = Elem<S>::ld(dhs_tm + (tm + p) * C + c) + carry[k];
+            r[k] = Elem<S>::ld(ru + (tm + p) * C2 + c);
+            u[k] = Elem<S>::ld(ru + (tm + p) * C2 + C + c);
+            const float o = Elem<S>::ld(og + (tm + p) * C + c);
+            hp[k] = t > 0 ? Elem<S>::ld(hs_tm + (((size_t)(t - 1) * B + b) * CS_PIX + p) * C + c)
+                          : (h0 ? Elem<S>::ld(h0 + ((size_t)b * CS_PIX + p) * C + c) : 0.f);
+            const float a = cs_rnd<S>(d * (1.f - u[k]) * (1.f - o * o)); // d(pre-tanh); 16-bit: rounded before the data-gradient GEMM
             du[k] = d * (hp[k] - o);                                     // d(u), post-sigmoid
             dhd[k] = d * u[k];                                           // direct path to h
-            dg2_all[(tm + p) * CS_C + c] = a;
-            halo[cs_halo_at(p) + c] = a;
+            Elem<S>::st(dg2_all + (tm + p) * C + c, a);
+            halo[cs_halo_at<STR>(p) + c] = a;
         }
         __syncthreads();
-        cs_conv_all<64, 128, true>(halo, w2t, nullptr, g, 128, wave, lane);       // d[r*h | x]
+        cs_conv_all<STR, C, C2, true>(halo, w2t, nullptr, g, C2, wave, lane);      // d[r*h | x]
         CS_FOR_ELEMS(k, p, c) {
-            const float drh = g[p * 128 + c];
-            dx2[k] = g[p * 128 + CS_C + c];
-            const float a = drh * hp[k] * r[k] * (1.f - r[k]);           // -> pre-sigmoid reset gate
-            const float bq = du[k] * u[k] * (1.f - u[k]);                // -> pre-sigmoid update gate
+            const float drh = g[p * C2 + c];
+            dx2[k] = g[p * C2 + C + c];
+            const float a = cs_rnd<S>(drh * hp[k] * r[k] * (1.f - r[k]));   // -> pre-sigmoid reset gate
+            const float bq = cs_rnd<S>(du[k] * u[k] * (1.f - u[k]));        // -> pre-sigmoid update gate
             dhd[k] += drh * r[k];                                        // d(rh) -> h
-            dg1_all[(tm + p) * 128 + c] = a;
-            dg1_all[(tm + p) * 128 + CS_C + c] = bq;
-            halo[cs_halo_at(p) + c] = a;
-            halo[cs_halo_at(p) + CS_C + c] = bq;
+            Elem<S>::st(dg1_all + (tm + p) * C2 + c, a);
+            Elem<S>::st(dg1_all + (tm + p) * C2 + C + c, bq);
+            halo[cs_halo_at<STR>(p) + c] = a;
+            halo[cs_halo_at<STR>(p) + C + c] = bq;
         }
         __syncthreads();
-        cs_conv_all<128, 128, true>(halo, w1t, nullptr, g, 128, wave, lane);      // d[x | h]
+        cs_conv_all<STR, C2, C2, true>(halo, w1t, nullptr, g, C2, wave, lane);     // d[x | h]
         CS_FOR_ELEMS(k, p, c) {
-            dxs_tm[(tm + p) * CS_C + c] = g[p * 128 + c] + dx2[k];
-            carry[k] = dhd[k] + g[p * 128 + CS_C + c];
+            Elem<S>::st(dxs_tm + (tm + p) * C + c, g[p * C2 + c] + dx2[k]);
+            carry[k] = dhd[k] + g[p * C2 + C + c];
         }
         __syncthreads();                                                 // g is read above, written by the next frame's first conv
     }
-    if (dh0) CS_FOR_ELEMS(k, p, c) dh0[((size_t)b * CS_PIX + p) * CS_C + c] = carry[k];
+    if (dh0) CS_FOR_ELEMS(k, p, c) Elem<S>::st(dh0 + ((size_t)b * CS_PIX + p) * C + c, carry[k]);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
-// CRNN: h_t = tanh(conv([x_t | h_{t-1}]) + b)   (common.py:331-352).  w OHWI [64][9][128]; wt IHWO [128][9][64].
-// forward: hs [B][T][40][64] (+ time-major copy hs_tm);  backward: dpre_all, dxs_tm [T][B][40][64], dh0.
+// CRNN: h_t = tanh(conv([x_t | h_{t-1}]) + b)   (common.py:331-352).  w OHWI [C][9][2C]; wt IHWO [2C][9][C].
+// forward: hs [B][T][40][C] (+ time-major copy hs_tm);  backward: dpre_all, dxs_tm [T][B][40][C], dh0.
 // ------------------------------------------------------------------------------------------------------------------------
+template <int C>
 __global__ __launch_bounds__(CS_NT) void crnn_scan_f32_fwd_kernel(const int B, const int T, const float* __restrict__ xs,
                                                                   const float* __restrict__ h0, const float* __restrict__ w,
                                                                   const float* __restrict__ bias, float* __restrict__ hs,
                                                                   float* __restrict__ hs_tm) {
+    using G = CsGeom<C>;
+    constexpr int STR = G::STR, C2 = 2 * C;
     extern __shared__ __attribute__((aligned(16))) float cs_lds[];
     float* halo = cs_lds;
-    float* g = halo + CS_HALO;                       // [40][64]
+    float* g = halo + G::HALO;                       // [40][C]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = blockIdx.x;
-    cs_zero_halo(halo, tid);
-    float h[5];
-    CS_FOR_ELEMS(k, p, c) h[k] = h0 ? h0[((size_t)b * CS_PIX + p) * CS_C + c] : 0.f;
+    cs_zero_halo<G::HALO>(halo, tid);
+    float h[G::NE];
+    CS_FOR_ELEMS(k, p, c) h[k] = h0 ? h0[((size_t)b * CS_PIX + p) * C + c] : 0.f;
     __syncthreads();
     for (int t = 0; t < T; ++t) {
-        const float* xt = xs + ((size_t)b * T + t) * (CS_PIX * CS_C);
+        const float* xt = xs + ((size_t)b * T + t) * (CS_PIX * C);
         CS_FOR_ELEMS(k, p, c) {
-            halo[cs_halo_at(p) + c] = xt[p * CS_C + c];
-            halo[cs_halo_at(p) + CS_C + c] = h[k];
+            halo[cs_halo_at<STR>(p) + c] = xt[p * C + c];
+            halo[cs_halo_at<STR>(p) + C + c] = h[k];
         }
         __syncthreads();
-        cs_conv_all<128, 64, false>(halo, w, bias, g, 64, wave, lane);
+        cs_conv_all<STR, C2, C, false>(halo, w, bias, g, C, wave, lane);
         CS_FOR_ELEMS(k, p, c) {
-            h[k] = tanhf(g[p * 64 + c]);
-            hs_tm[(((size_t)t * B + b) * CS_PIX + p) * CS_C + c] = h[k];
-            hs[(((size_t)b * T + t) * CS_PIX + p) * CS_C + c] = h[k];
+            h[k] = tanhf(g[p * C + c]);
+            hs_tm[(((size_t)t * B + b) * CS_PIX + p) * C + c] = h[k];
+            hs[(((size_t)b * T + t) * CS_PIX + p) * C + c] = h[k];
         }
     }
 }
 
+template <int C>
 __global__ __launch_bounds__(CS_NT) void crnn_scan_f32_bwd_kernel(const int B, const int T, const float* __restrict__ dhs_tm,
                                                                   const float* __restrict__ hs_tm, const float* __restrict__ wt,
                                                                   float* __restrict__ dpre_all, float* __restrict__ dxs_tm,
                                                                   float* __restrict__ dh0) {
+    using G = CsGeom<C>;
+    constexpr int STR = G::STR, C2 = 2 * C;
     extern __shared__ __attribute__((aligned(16))) float cs_lds[];
     float* halo = cs_lds;
-    float* g = halo + CS_HALO;                       // [40][128]
+    float* g = halo + G::HALO;                       // [40][2C]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = blockIdx.x;
-    cs_zero_halo(halo, tid);
-    float carry[5];
+    cs_zero_halo<G::HALO>(halo, tid);
+    float carry[G::NE];
     CS_FOR_ELEMS(k, p, c) carry[k] = 0.f;
     __syncthreads();
     for (int t = T - 1; t >= 0; --t) {
         const size_t tm = ((size_t)t * B + b) * CS_PIX;
         CS_FOR_ELEMS(k, p, c) {
-            const float hn = hs_tm[(tm + p) * CS_C + c];
-            const float a = (dhs_tm[(tm + p) * CS_C + c] + carry[k]) * (1.f - hn * hn);
-            dpre_all[(tm + p) * CS_C + c] = a;
-            halo[cs_halo_at(p) + c] = a;
+            const float hn = hs_tm[(tm + p) * C + c];
+            const float a = (dhs_tm[(tm + p) * C + c] + carry[k]) * (1.f - hn * hn);
+            dpre_all[(tm + p) * C + c] = a;
+            halo[cs_halo_at<STR>(p) + c] = a;
         }
         __syncthreads();
-        cs_conv_all<64, 128, true>(halo, wt, nullptr, g, 128, wave, lane);        // d[x | h]
+        cs_conv_all<STR, C, C2, true>(halo, wt, nullptr, g, C2, wave, lane);       // d[x | h]
         CS_FOR_ELEMS(k, p, c) {
-            dxs_tm[(tm + p) * CS_C + c] = g[p * 128 + c];
-            carry[k] = g[p * 128 + CS_C + c];
+            dxs_tm[(tm + p) * C + c] = g[p * C2 + c];
+            carry[k] = g[p * C2 + C + c];
         }
         __syncthreads();
     }
-    if (dh0) CS_FOR_ELEMS(k, p, c) dh0[((size_t)b * CS_PIX + p) * CS_C + c] = carry[k];
+    if (dh0) CS_FOR_ELEMS(k, p, c) dh0[((size_t)b * CS_PIX + p) * C + c] = carry[k];
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
-// CLSTM forward (common.py:355-385; gate order in / forget / out / cell).  w OHWI [256][9][128].  hs, cs [B][T][40][64].
+// CLSTM forward (common.py:355-385; gate order in / forget / out / cell).  w OHWI [4C][9][2C].  hs, cs [B][T][40][C].
 // ------------------------------------------------------------------------------------------------------------------------
+template <int C>
 __global__ __launch_bounds__(CS_NT) void clstm_scan_f32_fwd_kernel(const int B, const int T, const float* __restrict__ xs,
                                                                    const float* __restrict__ h0, const float* __restrict__ c0,
                                                                    const float* __restrict__ w, const float* __restrict__ bias,
                                                                    float* __restrict__ hs, float* __restrict__ cs) {
+    using G = CsGeom<C>;
+    constexpr int STR = G::STR, C2 = 2 * C, C4 = 4 * C;
     extern __shared__ __attribute__((aligned(16))) float cs_lds[];
     float* halo = cs_lds;
-    float* g = halo + CS_HALO;                       // [40][256]
+    float* g = halo + G::HALO;                       // [40][4C]
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int b = blockIdx.x;
-    cs_zero_halo(halo, tid);
-    float h[5], cc[5];
+    cs_zero_halo<G::HALO>(halo, tid);
+    float h[G::NE], cc[G::NE];
     CS_FOR_ELEMS(k, p, c) {
-        h[k] = h0 ? h0[((size_t)b * CS_PIX + p) * CS_C + c] : 0.f;
-        cc[k] = c0 ? c0[((size_t)b * CS_PIX + p) * CS_C + c] : 0.f;
+        h[k] = h0 ? h0[((size_t)b * CS_PIX + p) * C + c] : 0.f;
+        cc[k] = c0 ? c0[((size_t)b * CS_PIX + p) * C + c] : 0.f;
     }
     __syncthreads();
     for (int t = 0; t < T; ++t) {
-        const float* xt = xs + ((size_t)b * T + t) * (CS_PIX * CS_C);
+        const float* xt = xs + ((size_t)b * T + t) * (CS_PIX * C);
         CS_FOR_ELEMS(k, p, c) {
-            halo[cs_halo_at(p) + c] = xt[p * CS_C + c];
-            halo[cs_halo_at(p) + CS_C + c] = h[k];
+            halo[cs_halo_at<STR>(p) + c] = xt[p * C + c];
+            halo[cs_halo_at<STR>(p) + C + c] = h[k];
         }
         __syncthreads();
-        cs_conv_all<128, 256, false>(halo, w, bias, g, 256, wave, lane);
+        cs_conv_all<STR, C2, C4, false>(halo, w, bias, g, C4, wave, lane);
         CS_FOR_ELEMS(k, p, c) {
-            const float gi = g[p * 256 + c], gf = g[p * 256 + CS_C + c], go = g[p * 256 + 2 * CS_C + c], gc = g[p * 256 + 3 * CS_C + c];
+            const float gi = g[p * C4 + c], gf = g[p * C4 + C + c], go = g[p * C4 + 2 * C + c], gc = g[p * C4 + 3 * C + c];
             cc[k] = cs_sigmoid(gf) * cc[k] + cs_sigmoid(gi) * tanhf(gc);
             h[k] = cs_sigmoid(go) * tanhf(cc[k]);
-            const size_t o = (((size_t)b * T + t) * CS_PIX + p) * CS_C + c;
+            const size_t o = (((size_t)b * T + t) * CS_PIX + p) * C + c;
             hs[o] = h[k];
             cs[o] = cc[k];
         }
     }
 }
 
-constexpr size_t CS_LDS_128 = (size_t)(CS_HALO + CS_PIX * 128) * sizeof(float);
-constexpr size_t CS_LDS_256 = (size_t)(CS_HALO + CS_PIX * 256) * sizeof(float);
+static_assert(CsGeom<128>::lds_bytes(4 * 128) <= (size_t)LDS_CU, "the CLSTM scan at C = 128 must fit a CU's LDS");
+
+// the name a width's instantiation reports through eve_last_kernel(): C = 64 keeps the name it had before the template
+#define CS_KNAME(base) (C == 64 ? base : C == 32 ? base "<32>" : base "<128>")
+// run `...` with the compile-time width bound to C; false for a width without an instantiation
+#define CS_DISPATCH_C(width, ...)                                   \
+    switch (width) {                                                \
+        case 32: { constexpr int C = 32; __VA_ARGS__; } break;      \
+        case 64: { constexpr int C = 64; __VA_ARGS__; } break;      \
+        case 128: { constexpr int C = 128; __VA_ARGS__; } break;    \
+        default: break;                                             \
+    }
 
 }  // namespace eve
 
 using namespace eve;
 
-/* float32 instantiation of eve_cgru_scan_fwd / _bwd (cgru_scan.hip dispatches here for EVE_DT_F32): same operands, float. */
-int eve_cgru_scan_f32_fwd(int B, int T, const float* xs, const float* h0, const float* w1, const float* b1, const float* w2,
+bool eve_cell_scan_width_ok(int C) { return C == 32 || C == 64 || C == 128; }
+
+/* float32 instantiations of eve_cgru_scan_fwd_c / _bwd_c (cgru_scan.hip dispatches here for EVE_DT_F32): same operands, float. */
+int eve_cgru_scan_f32_fwd(int B, int T, int width, const float* xs, const float* h0, const float* w1, const float* b1, const float* w2,
                           const float* b2, float* hs, float* hs_tm, float* ru, float* rh, float* og, hipStream_t s) {
-    EVE_LAUNCH("cgru_scan_f32_fwd_kernel", cgru_scan_f32_fwd_kernel, dim3(B), dim3(CS_NT), CS_LDS_128, s, B, T, xs, h0, w1, b1, w2, b2,
-               hs, hs_tm, ru, rh, og);
+    if (!eve_cell_scan_width_ok(width)) return set_error_msg("cgru_scan_fwd: unsupported channel count (float32: 32, 64, 128)");
+    CS_DISPATCH_C(width, EVE_LAUNCH(CS_KNAME("cgru_scan_f32_fwd_kernel"), cgru_scan_f32_fwd_kernel<C>, dim3(B), dim3(CS_NT),
+                                    CsGeom<C>::lds_bytes(2 * C), s, B, T, xs, h0, w1, b1, w2, b2, hs, hs_tm, ru, rh, og));
     EVE_CHECK_LAUNCH();
     return 0;
 }
 
-int eve_cgru_scan_f32_bwd(int B, int T, const float* dhs_tm, const float* ru, const float* og, const float* hs_tm, const float* h0,
-                          const float* w1t, const float* w2t, float* dg1_all, float* dg2_all, float* dxs_tm, float* dh0,
+int eve_cgru_scan_f32_bwd(int B, int T, int width, const float* dhs_tm, const float* ru, const float* og, const float* hs_tm,
+                          const float* h0, const float* w1t, const float* w2t, float* dg1_all, float* dg2_all, float* dxs_tm, float* dh0,
                           hipStream_t s) {
-    EVE_LAUNCH("cgru_scan_f32_bwd_kernel", cgru_scan_f32_bwd_kernel, dim3(B), dim3(CS_NT), CS_LDS_128, s, B, T, dhs_tm, ru, og, hs_tm, h0,
-               w1t, w2t, dg1_all, dg2_all, dxs_tm, dh0);
+    if (!eve_cell_scan_width_ok(width)) return set_error_msg("cgru_scan_bwd: unsupported channel count (float32: 32, 64, 128)");
+    CS_DISPATCH_C(width, EVE_LAUNCH(CS_KNAME("cgru_scan_f32_bwd_kernel"), cgru_scan_f32_bwd_kernel<C>, dim3(B), dim3(CS_NT),
+                                    CsGeom<C>::lds_bytes(2 * C), s, B, T, dhs_tm, ru, og, hs_tm, h0, w1t, w2t, dg1_all, dg2_all, dxs_tm,
+                                    dh0));
     EVE_CHECK_LAUNCH();
     return 0;
 }
 
-/* CRNNCell over a clip in one launch (float32; common.py:331-352).  xs [B][T][5][8][64], h0 [B][5][8][64] or NULL, w OHWI
-   [64][3][3][128] (input channels: x then h), bias [64].  Outputs hs [B][T][5][8][64] and the time-major copy hs_tm
-   [T][B][5][8][64] the backward reads. */
+/* bf16 / f16 storage at the widths the 16-bit MFMA kernels (cgru_scan.hip, cgru_scan1.hip: C = 64) do not serve: the float32
+   scan with 16-bit operands and outputs, every value rounded to the format where cgru_scan1.hip rounds it (gates, r * h, the new
+   state; in the backward the two pre-activation gradients before their data-gradient GEMMs), products on the float32 MFMA. */
+#define CS_HNAME(base, w) (Elem<H>::IS_BF16 ? base "<" w ", eve::bf16_t>" : base "<" w ", eve::f16_t>")
+int eve_cgru_scan_h16_fwd(int dtype, int B, int T, int width, const void* xs, const void* h0, const void* w1, const float* b1,
+                          const void* w2, const float* b2, void* hs, void* hs_tm, void* ru, void* rh, void* og, hipStream_t s) {
+    if (width != 32 && width != 128) return set_error_msg("cgru_scan_fwd: unsupported channel count (bf16 / f16: 32, 64, 128)");
+#define CS_H16_FWD(W_, WS_)                                                                                                       \
+    EVE_DISPATCH_H16(dtype, EVE_LAUNCH(CS_HNAME("cgru_scan_f32_fwd_kernel", WS_), (cgru_scan_f32_fwd_kernel<W_, H>), dim3(B), dim3(CS_NT), \
+                                       CsGeom<W_>::lds_bytes(2 * W_), s, B, T, (const H*)xs, (const H*)h0, (const H*)w1, b1,     \
+                                       (const H*)w2, b2, (H*)hs, (H*)hs_tm, (H*)ru, (H*)rh, (H*)og))
+    if (width == 32) CS_H16_FWD(32, "32"); else CS_H16_FWD(128, "128");
+#undef CS_H16_FWD
+    EVE_CHECK_LAUNCH();
+    return 0;
+}
+
+int eve_cgru_scan_h16_bwd(int dtype, int B, int T, int width, const void* dhs_tm, const void* ru, const void* og, const void* hs_tm,
+                          const void* h0, const void* w1t, const void* w2t, void* dg1_all, void* dg2_all, void* dxs_tm, void* dh0,
+                          hipStream_t s) {
+    if (width != 32 && width != 128) return set_error_msg("cgru_scan_bwd: unsupported channel count (bf16 / f16: 32, 64, 128)");
+#define CS_H16_BWD(W_, WS_)                                                                                                       \
+    EVE_DISPATCH_H16(dtype, EVE_LAUNCH(CS_HNAME("cgru_scan_f32_bwd_kernel", WS_), (cgru_scan_f32_bwd_kernel<W_, H>), dim3(B), dim3(CS_NT), \
+                                       CsGeom<W_>::lds_bytes(2 * W_), s, B, T, (const H*)dhs_tm, (const H*)ru, (const H*)og,     \
+                                       (const H*)hs_tm, (const H*)h0, (const H*)w1t, (const H*)w2t, (H*)dg1_all, (H*)dg2_all,     \
+                                       (H*)dxs_tm, (H*)dh0))
+    if (width == 32) CS_H16_BWD(32, "32"); else CS_H16_BWD(128, "128");
+#undef CS_H16_BWD
+    EVE_CHECK_LAUNCH();
+    return 0;
+}
+
+/* CRNNCell over a clip in one launch (float32; common.py:331-352).  xs [B][T][5][8][C], h0 [B][5][8][C] or NULL, w OHWI
+   [C][3][3][2C] (input channels: x then h), bias [C].  Outputs hs [B][T][5][8][C] and the time-major copy hs_tm
+   [T][B][5][8][C] the backward reads.  C in {32, 64, 128}. */
+extern "C" int eve_crnn_scan_fwd_c(int B, int T, int C, const float* xs, const float* h0, const float* w, const float* bias, float* hs,
+                                   float* hs_tm, eve_stream_t stream) {
+    if (B <= 0 || T <= 0 || !xs || !w || !bias || !hs || !hs_tm) return set_error_msg("crnn_scan_fwd: bad arguments");
+    if (!eve_cell_scan_width_ok(C)) return set_error_msg("crnn_scan_fwd: unsupported channel count (32, 64, 128)");
+    const int width = C;
+    CS_DISPATCH_C(width, EVE_LAUNCH(CS_KNAME("crnn_scan_f32_fwd_kernel"), crnn_scan_f32_fwd_kernel<C>, dim3(B), dim3(CS_NT),
+                                    CsGeom<C>::lds_bytes(2 * C), (hipStream_t)stream, B, T, xs, h0, w, bias, hs, hs_tm));
+    EVE_CHECK_LAUNCH();
+    return 0;
+}
 extern "C" int eve_crnn_scan_fwd(int B, int T, const float* xs, const float* h0, const float* w, const float* bias, float* hs,
                                  float* hs_tm, eve_stream_t stream) {
-    if (B <= 0 || T <= 0 || !xs || !w || !bias || !hs || !hs_tm) return set_error_msg("crnn_scan_fwd: bad arguments");
-    EVE_LAUNCH("crnn_scan_f32_fwd_kernel", crnn_scan_f32_fwd_kernel, dim3(B), dim3(CS_NT), CS_LDS_128, (hipStream_t)stream, B, T, xs, h0, w,
-               bias, hs, hs_tm);
+    return eve_crnn_scan_fwd_c(B, T, 64, xs, h0, w, bias, hs, hs_tm, stream);
+}
+
+/* Backward of eve_crnn_scan_fwd_c.  Time-major dhs_tm, hs_tm [T][B][5][8][C]; wt = the filter bank IHWO [2C][3][3][C].
+   Outputs (time-major): dpre_all = gradient of the pre-activation (what the batched weight / bias gradients read), dxs_tm;
+   dh0 [B][5][8][C] or NULL. */
+extern "C" int eve_crnn_scan_bwd_c(int B, int T, int C, const float* dhs_tm, const float* hs_tm, const float* wt, float* dpre_all,
+                                   float* dxs_tm, float* dh0, eve_stream_t stream) {
+    if (B <= 0 || T <= 0 || !dhs_tm || !hs_tm || !wt || !dpre_all || !dxs_tm) return set_error_msg("crnn_scan_bwd: bad arguments");
+    if (!eve_cell_scan_width_ok(C)) return set_error_msg("crnn_scan_bwd: unsupported channel count (32, 64, 128)");
+    const int width = C;
+    CS_DISPATCH_C(width, EVE_LAUNCH(CS_KNAME("crnn_scan_f32_bwd_kernel"), crnn_scan_f32_bwd_kernel<C>, dim3(B), dim3(CS_NT),
+                                    CsGeom<C>::lds_bytes(2 * C), (hipStream_t)stream, B, T, dhs_tm, hs_tm, wt, dpre_all, dxs_tm, dh0));
     EVE_CHECK_LAUNCH();
     return 0;
 }
-
-/* Backward of eve_crnn_scan_fwd.  Time-major dhs_tm, hs_tm [T][B][5][8][64]; wt = the filter bank IHWO [128][3][3][64].
-   Outputs (time-major): dpre_all = gradient of the pre-activation (what the batched weight / bias gradients read), dxs_tm;
-   dh0 [B][5][8][64] or NULL. */
 extern "C" int eve_crnn_scan_bwd(int B, int T, const float* dhs_tm, const float* hs_tm, const float* wt, float* dpre_all,
                                  float* dxs_tm, float* dh0, eve_stream_t stream) {
-    if (B <= 0 || T <= 0 || !dhs_tm || !hs_tm || !wt || !dpre_all || !dxs_tm) return set_error_msg("crnn_scan_bwd: bad arguments");
-    EVE_LAUNCH("crnn_scan_f32_bwd_kernel", crnn_scan_f32_bwd_kernel, dim3(B), dim3(CS_NT), CS_LDS_128, (hipStream_t)stream, B, T, dhs_tm,
-               hs_tm, wt, dpre_all, dxs_tm, dh0);
-    EVE_CHECK_LAUNCH();
-    return 0;
+    return eve_crnn_scan_bwd_c(B, T, 64, dhs_tm, hs_tm, wt, dpre_all, dxs_tm, dh0, stream);
 }
 
 /* CLSTMCell over a clip in one launch (float32, forward only: the reference drops tuple states from the feature path,
-   refine_net.py:168-174; common.py:355-385).  w OHWI [256][3][3][128] (gate order in / forget / out / cell), bias [256];
-   h0 / c0 [B][5][8][64] or NULL.  Outputs hs, cs [B][T][5][8][64]. */
-extern "C" int eve_clstm_scan_fwd(int B, int T, const float* xs, const float* h0, const float* c0, const float* w, const float* bias,
-                                  float* hs, float* cs, eve_stream_t stream) {
+   refine_net.py:168-174; common.py:355-385).  w OHWI [4C][3][3][2C] (gate order in / forget / out / cell), bias [4C];
+   h0 / c0 [B][5][8][C] or NULL.  Outputs hs, cs [B][T][5][8][C].  C in {32, 64, 128}. */
+extern "C" int eve_clstm_scan_fwd_c(int B, int T, int C, const float* xs, const float* h0, const float* c0, const float* w,
+                                    const float* bias, float* hs, float* cs, eve_stream_t stream) {
     if (B <= 0 || T <= 0 || !xs || !w || !bias || !hs || !cs) return set_error_msg("clstm_scan_fwd: bad arguments");
-    EVE_LAUNCH("clstm_scan_f32_fwd_kernel", clstm_scan_f32_fwd_kernel, dim3(B), dim3(CS_NT), CS_LDS_256, (hipStream_t)stream, B, T, xs, h0,
-               c0, w, bias, hs, cs);
+    if (!eve_cell_scan_width_ok(C)) return set_error_msg("clstm_scan_fwd: unsupported channel count (32, 64, 128)");
+    const int width = C;
+    CS_DISPATCH_C(width, EVE_LAUNCH(CS_KNAME("clstm_scan_f32_fwd_kernel"), clstm_scan_f32_fwd_kernel<C>, dim3(B), dim3(CS_NT),
+                                    CsGeom<C>::lds_bytes(4 * C), (hipStream_t)stream, B, T, xs, h0, c0, w, bias, hs, cs));
     EVE_CHECK_LAUNCH();
     return 0;
+}
+extern "C" int eve_clstm_scan_fwd(int B, int T, const float* xs, const float* h0, const float* c0, const float* w, const float* bias,
+                                  float* hs, float* cs, eve_stream_t stream) {
+    return eve_clstm_scan_fwd_c(B, T, 64, xs, h0, c0, w, bias, hs, cs, stream);
 }

@@ -572,11 +572,18 @@ using namespace eve;
    (input channels: r*h then x), biases float.  Outputs (bf16): hs [B][T][5][8][64] = hidden states in the caller's
    (sequence, frame) order; and TIME-major [T][B][5][8][.] for the backward, which walks frames: hs_tm, ru = the two
    sigmoid gates (128 channels), rh = r * h_{t-1}, og = tanh output gate. */
-// float32 instantiation (cell_scan_f32.hip): one workgroup per sequence, float state in LDS, v_mfma_f32_16x16x4_f32
-int eve_cgru_scan_f32_fwd(int B, int T, const float* xs, const float* h0, const float* w1, const float* b1, const float* w2,
+// float32 instantiation (cell_scan_f32.hip): one workgroup per sequence, float state in LDS, v_mfma_f32_16x16x4_f32; C = 32, 64, 128
+int eve_cgru_scan_f32_fwd(int B, int T, int C, const float* xs, const float* h0, const float* w1, const float* b1, const float* w2,
                           const float* b2, float* hs, float* hs_tm, float* ru, float* rh, float* og, hipStream_t s);
-int eve_cgru_scan_f32_bwd(int B, int T, const float* dhs_tm, const float* ru, const float* og, const float* hs_tm, const float* h0,
-                          const float* w1t, const float* w2t, float* dg1_all, float* dg2_all, float* dxs_tm, float* dh0,
+int eve_cgru_scan_f32_bwd(int B, int T, int C, const float* dhs_tm, const float* ru, const float* og, const float* hs_tm,
+                          const float* h0, const float* w1t, const float* w2t, float* dg1_all, float* dg2_all, float* dxs_tm, float* dh0,
+                          hipStream_t s);
+
+// bf16 / f16 storage at C = 32 / 128 (cell_scan_f32.hip): the float32-MFMA scan with cgru_scan1.hip's 16-bit rounding points
+int eve_cgru_scan_h16_fwd(int dtype, int B, int T, int C, const void* xs, const void* h0, const void* w1, const float* b1,
+                          const void* w2, const float* b2, void* hs, void* hs_tm, void* ru, void* rh, void* og, hipStream_t s);
+int eve_cgru_scan_h16_bwd(int dtype, int B, int T, int C, const void* dhs_tm, const void* ru, const void* og, const void* hs_tm,
+                          const void* h0, const void* w1t, const void* w2t, void* dg1_all, void* dg2_all, void* dxs_tm, void* dh0,
                           hipStream_t s);
 
 // one sequence per workgroup (cgru_scan1.hip): the batches this model sees (B <= g_cfg.cgru_seq_max_b sequences)
@@ -585,13 +592,19 @@ int eve_cgru_scan1_fwd(int dtype, int B, int T, const void* xs, const void* h0, 
 int eve_cgru_scan1_bwd(int dtype, int B, int T, const void* dhs_tm, const void* ru, const void* og, const void* hs_tm, const void* h0,
                        const void* w1t, const void* w2t, void* dg1_all, void* dg2_all, void* dxs_tm, void* dh0, hipStream_t s);
 
-extern "C" int eve_cgru_scan_fwd(int dtype, int B, int T, const void* xs, const void* h0, const void* w1, const float* b1, const void* w2,
-                                 const float* b2, void* hs, void* hs_tm, void* ru, void* rh, void* og, eve_stream_t stream) {
+/* The entry points with the bottleneck width C as an argument (operand shapes as above with 64 -> C, 128 -> 2C).  every format:
+   C in {32, 64, 128}.  float32: cell_scan_f32.hip.  bf16 / f16: the 16-bit MFMA kernels below at C = 64; at 32 / 128 the
+   float32-MFMA scan with 16-bit storage and the same rounding points (cell_scan_f32.hip).  Any other width is refused before
+   anything is launched. */
+extern "C" int eve_cgru_scan_fwd_c(int dtype, int B, int T, int C, const void* xs, const void* h0, const void* w1, const float* b1,
+                                   const void* w2, const float* b2, void* hs, void* hs_tm, void* ru, void* rh, void* og,
+                                   eve_stream_t stream) {
     if (dtype == EVE_DT_F32 && B > 0 && T > 0 && xs && w1 && b1 && w2 && b2 && hs && hs_tm && ru && rh && og)
-        return eve_cgru_scan_f32_fwd(B, T, (const float*)xs, (const float*)h0, (const float*)w1, b1, (const float*)w2, b2, (float*)hs,
+        return eve_cgru_scan_f32_fwd(B, T, C, (const float*)xs, (const float*)h0, (const float*)w1, b1, (const float*)w2, b2, (float*)hs,
                                      (float*)hs_tm, (float*)ru, (float*)rh, (float*)og, (hipStream_t)stream);
     if ((dtype != EVE_DT_BF16 && dtype != EVE_DT_F16) || B <= 0 || T <= 0 || !xs || !w1 || !b1 || !w2 || !b2 || !hs || !hs_tm || !ru || !rh || !og)
         return set_error_msg("cgru_scan_fwd: bad arguments");
+    if (C != 64) return eve_cgru_scan_h16_fwd(dtype, B, T, C, xs, h0, w1, b1, w2, b2, hs, hs_tm, ru, rh, og, (hipStream_t)stream);
     if ((long long)B * T * CG_PIX * 128 >= (1ll << 31)) return set_error_msg("cgru_scan_fwd: clip too large for 32-bit offsets");
     if (B <= g_cfg.cgru_seq_max_b) return eve_cgru_scan1_fwd(dtype, B, T, xs, h0, w1, b1, w2, b2, hs, hs_tm, ru, rh, og, (hipStream_t)stream);
     EVE_DISPATCH_H16(dtype, EVE_LAUNCH(EVE_HNAME(H, "cgru_scan_fwd_kernel<", ">"), cgru_scan_fwd_kernel<H>, dim3((B + CG_IMG - 1) / CG_IMG), dim3(256), CG_LDS,
@@ -600,6 +613,10 @@ extern "C" int eve_cgru_scan_fwd(int dtype, int B, int T, const void* xs, const 
     EVE_CHECK_LAUNCH();
     return 0;
 }
+extern "C" int eve_cgru_scan_fwd(int dtype, int B, int T, const void* xs, const void* h0, const void* w1, const float* b1, const void* w2,
+                                 const float* b2, void* hs, void* hs_tm, void* ru, void* rh, void* og, eve_stream_t stream) {
+    return eve_cgru_scan_fwd_c(dtype, B, T, 64, xs, h0, w1, b1, w2, b2, hs, hs_tm, ru, rh, og, stream);
+}
 
 
 /* Backward of eve_cgru_scan_fwd in one launch (bf16).  Inputs, TIME-major [T][B][5][8][.]: dhs_tm = gradient of the hidden
@@ -607,15 +624,17 @@ extern "C" int eve_cgru_scan_fwd(int dtype, int B, int T, const void* xs, const 
    w2t = gate_2 filter bank IHWO [128][3][3][64].  Outputs (time-major): dg1_all [T][B][5][8][128] and dg2_all [..][64] = the
    gradients of the two pre-activations (what the batched weight / bias gradients read), dxs_tm [..][64] = d xs, and dh0
    [B][5][8][64] (NULL = not wanted).  common.py:400-415 differentiated.                                                   */
-extern "C" int eve_cgru_scan_bwd(int dtype, int B, int T, const void* dhs_tm, const void* ru, const void* og, const void* hs_tm, const void* h0,
-                                 const void* w1t, const void* w2t, void* dg1_all, void* dg2_all, void* dxs_tm, void* dh0,
-                                 eve_stream_t stream) {
+extern "C" int eve_cgru_scan_bwd_c(int dtype, int B, int T, int C, const void* dhs_tm, const void* ru, const void* og, const void* hs_tm,
+                                   const void* h0, const void* w1t, const void* w2t, void* dg1_all, void* dg2_all, void* dxs_tm, void* dh0,
+                                   eve_stream_t stream) {
     if (dtype == EVE_DT_F32 && B > 0 && T > 0 && dhs_tm && ru && og && hs_tm && w1t && w2t && dg1_all && dg2_all && dxs_tm)
-        return eve_cgru_scan_f32_bwd(B, T, (const float*)dhs_tm, (const float*)ru, (const float*)og, (const float*)hs_tm, (const float*)h0,
+        return eve_cgru_scan_f32_bwd(B, T, C, (const float*)dhs_tm, (const float*)ru, (const float*)og, (const float*)hs_tm, (const float*)h0,
                                      (const float*)w1t, (const float*)w2t, (float*)dg1_all, (float*)dg2_all, (float*)dxs_tm, (float*)dh0,
                                      (hipStream_t)stream);
     if ((dtype != EVE_DT_BF16 && dtype != EVE_DT_F16) || B <= 0 || T <= 0 || !dhs_tm || !ru || !og || !hs_tm || !w1t || !w2t || !dg1_all || !dg2_all || !dxs_tm)
         return set_error_msg("cgru_scan_bwd: bad arguments");
+    if (C != 64)
+        return eve_cgru_scan_h16_bwd(dtype, B, T, C, dhs_tm, ru, og, hs_tm, h0, w1t, w2t, dg1_all, dg2_all, dxs_tm, dh0, (hipStream_t)stream);
     if ((long long)B * T * CG_PIX * 128 >= (1ll << 31)) return set_error_msg("cgru_scan_bwd: clip too large for 32-bit offsets");
     if (B <= g_cfg.cgru_seq_max_b)
         return eve_cgru_scan1_bwd(dtype, B, T, dhs_tm, ru, og, hs_tm, h0, w1t, w2t, dg1_all, dg2_all, dxs_tm, dh0, (hipStream_t)stream);
@@ -624,4 +643,9 @@ extern "C" int eve_cgru_scan_bwd(int dtype, int B, int T, const void* dhs_tm, co
                                        (const H*)w1t, (const H*)w2t, (H*)dg1_all, (H*)dg2_all, (H*)dxs_tm, (H*)dh0));
     EVE_CHECK_LAUNCH();
     return 0;
+}
+extern "C" int eve_cgru_scan_bwd(int dtype, int B, int T, const void* dhs_tm, const void* ru, const void* og, const void* hs_tm, const void* h0,
+                                 const void* w1t, const void* w2t, void* dg1_all, void* dg2_all, void* dxs_tm, void* dh0,
+                                 eve_stream_t stream) {
+    return eve_cgru_scan_bwd_c(dtype, B, T, 64, dhs_tm, ru, og, hs_tm, h0, w1t, w2t, dg1_all, dg2_all, dxs_tm, dh0, stream);
 }

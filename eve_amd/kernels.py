@@ -17,6 +17,7 @@ ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SELU, ACT_TANH, ACT_SIGMOID = range(6)
 EPI_ACCUMULATE = 0x100          # include/eve_hip.h EVE_EPI_ACCUMULATE: y += act(conv + bias)
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 HALF_DTYPES = (torch.bfloat16, torch.float16)      # the two 16-bit instantiations of the MFMA kernels
+SCAN_WIDTHS = (32, 64, 128)                        # bottleneck widths the clip-long conv-RNN scans are instantiated for (csrc/cell_scan_f32.hip)
 
 
 def dt_code(dtype):
@@ -1007,12 +1008,13 @@ class HipKernels(object):
         return dpre, dh0, dc0
 
     def cgru_scan_fwd(self, xs, h0, w1_ohwi, b1, w2_ohwi, b2):
-        """CGRUCell over T in one launch.  xs [B, T, 5, 8, 64] bf16 / fp16 / float32 -> hs [B, T, 5, 8, 64] and, time-major
-        [T, B, 5, 8, .] for the backward: hs_tm, ru, rh, og.  (float32: csrc/cell_scan_f32.hip.)"""
+        """CGRUCell over T in one launch.  xs [B, T, 5, 8, C] bf16 / fp16 / float32 -> hs [B, T, 5, 8, C] and, time-major
+        [T, B, 5, 8, .] for the backward: hs_tm, ru, rh, og.  (C in SCAN_WIDTHS; float32 and the 16-bit formats at C = 32 / 128:
+        csrc/cell_scan_f32.hip.)"""
         B, T, H, W, C = xs.shape
-        assert (H, W, C) == (5, 8, 64) and xs.dtype in HALF_DTYPES + (torch.float32,) and xs.is_contiguous()
+        assert (H, W) == (5, 8) and xs.dtype in HALF_DTYPES + (torch.float32,) and xs.is_contiguous()
         assert w1_ohwi.dtype == w2_ohwi.dtype == xs.dtype and w1_ohwi.is_contiguous() and w2_ohwi.is_contiguous()
-        assert tuple(w1_ohwi.shape) == (128, 3, 3, 128) and tuple(w2_ohwi.shape) == (64, 3, 3, 128)
+        assert tuple(w1_ohwi.shape) == (2 * C, 3, 3, 2 * C) and tuple(w2_ohwi.shape) == (C, 3, 3, 2 * C)
         dev = xs.device
         hdt = xs.dtype
         hs = torch.empty((B, T, H, W, C), dtype=hdt, device=dev)
@@ -1020,67 +1022,67 @@ class HipKernels(object):
         ru = torch.empty((T, B, H, W, 2 * C), dtype=hdt, device=dev)
         rh = torch.empty((T, B, H, W, C), dtype=hdt, device=dev)
         og = torch.empty((T, B, H, W, C), dtype=hdt, device=dev)
-        self._ck(self.lib.eve_cgru_scan_fwd(dt_code(hdt), B, T, self._p(xs), self._p(h0), self._p(w1_ohwi), self._p(self._f32(b1, 'b1')),
+        self._ck(self.lib.eve_cgru_scan_fwd_c(dt_code(hdt), B, T, C, self._p(xs), self._p(h0), self._p(w1_ohwi), self._p(self._f32(b1, 'b1')),
                                             self._p(w2_ohwi), self._p(self._f32(b2, 'b2')), self._p(hs), self._p(hs_tm),
                                             self._p(ru), self._p(rh), self._p(og), self._stream()))
         return hs, hs_tm, ru, rh, og
 
     def cgru_scan_bwd(self, dhs_tm, ru, og, hs_tm, h0, w1_ihwo, w2_ihwo, want_dh0=False):
         """Backward of cgru_scan_fwd in one launch.  Time-major [T, B, 5, 8, .] inputs (16-bit or float32); returns (dg1_all
-        [T,B,5,8,128], dg2_all [T,B,5,8,64], dxs_tm [T,B,5,8,64], dh0 [B,5,8,64] or None)."""
+        [T,B,5,8,2C], dg2_all [T,B,5,8,C], dxs_tm [T,B,5,8,C], dh0 [B,5,8,C] or None)."""
         T, B, H, W, C = dhs_tm.shape
-        assert (H, W, C) == (5, 8, 64) and dhs_tm.dtype in HALF_DTYPES + (torch.float32,) and dhs_tm.is_contiguous()
+        assert (H, W) == (5, 8) and dhs_tm.dtype in HALF_DTYPES + (torch.float32,) and dhs_tm.is_contiguous()
         assert w1_ihwo.dtype == w2_ihwo.dtype == dhs_tm.dtype and w1_ihwo.is_contiguous() and w2_ihwo.is_contiguous()
         assert all(t.is_contiguous() and t.dtype == dhs_tm.dtype for t in (ru, og, hs_tm))
         assert tuple(ru.shape) == (T, B, H, W, 2 * C) and tuple(og.shape) == tuple(hs_tm.shape) == (T, B, H, W, C)
-        assert tuple(w1_ihwo.shape) == (128, 3, 3, 128) and tuple(w2_ihwo.shape) == (128, 3, 3, 64)
+        assert tuple(w1_ihwo.shape) == (2 * C, 3, 3, 2 * C) and tuple(w2_ihwo.shape) == (2 * C, 3, 3, C)
         dev = dhs_tm.device
         hdt = dhs_tm.dtype
         dg1 = torch.empty((T, B, H, W, 2 * C), dtype=hdt, device=dev)
         dg2 = torch.empty((T, B, H, W, C), dtype=hdt, device=dev)
         dxs = torch.empty((T, B, H, W, C), dtype=hdt, device=dev)
         dh0 = torch.empty((B, H, W, C), dtype=hdt, device=dev) if want_dh0 else None
-        self._ck(self.lib.eve_cgru_scan_bwd(dt_code(hdt), B, T, self._p(dhs_tm), self._p(ru), self._p(og), self._p(hs_tm), self._p(h0),
+        self._ck(self.lib.eve_cgru_scan_bwd_c(dt_code(hdt), B, T, C, self._p(dhs_tm), self._p(ru), self._p(og), self._p(hs_tm), self._p(h0),
                                             self._p(w1_ihwo), self._p(w2_ihwo), self._p(dg1), self._p(dg2), self._p(dxs),
                                             self._p(dh0), self._stream()))
         return dg1, dg2, dxs, dh0
 
     def crnn_scan_fwd(self, xs, h0, w_ohwi, bias):
-        """CRNNCell over T in one launch (float32, csrc/cell_scan_f32.hip).  xs [B, T, 5, 8, 64] -> (hs [B, T, 5, 8, 64], hs_tm
-        [T, B, 5, 8, 64])."""
+        """CRNNCell over T in one launch (float32, csrc/cell_scan_f32.hip).  xs [B, T, 5, 8, C] -> (hs [B, T, 5, 8, C], hs_tm
+        [T, B, 5, 8, C]), C in SCAN_WIDTHS."""
         B, T, H, W, C = xs.shape
-        assert (H, W, C) == (5, 8, 64) and xs.dtype == torch.float32 and xs.is_contiguous()
-        assert tuple(w_ohwi.shape) == (64, 3, 3, 128) and w_ohwi.dtype == torch.float32 and w_ohwi.is_contiguous()
+        assert (H, W) == (5, 8) and xs.dtype == torch.float32 and xs.is_contiguous()
+        assert tuple(w_ohwi.shape) == (C, 3, 3, 2 * C) and w_ohwi.dtype == torch.float32 and w_ohwi.is_contiguous()
         assert h0 is None or (h0.dtype == torch.float32 and h0.is_contiguous() and tuple(h0.shape) == (B, H, W, C))
         hs = torch.empty((B, T, H, W, C), dtype=torch.float32, device=xs.device)
         hs_tm = torch.empty((T, B, H, W, C), dtype=torch.float32, device=xs.device)
-        self._ck(self.lib.eve_crnn_scan_fwd(B, T, self._p(xs), self._p(h0), self._p(w_ohwi), self._p(self._f32(bias, 'bias')),
+        self._ck(self.lib.eve_crnn_scan_fwd_c(B, T, C, self._p(xs), self._p(h0), self._p(w_ohwi), self._p(self._f32(bias, 'bias')),
                                             self._p(hs), self._p(hs_tm), self._stream()))
         return hs, hs_tm
 
     def crnn_scan_bwd(self, dhs_tm, hs_tm, w_ihwo, want_dh0=False):
-        """Backward of crnn_scan_fwd in one launch: (dpre_all, dxs_tm [T, B, 5, 8, 64], dh0 [B, 5, 8, 64] or None)."""
+        """Backward of crnn_scan_fwd in one launch: (dpre_all, dxs_tm [T, B, 5, 8, C], dh0 [B, 5, 8, C] or None)."""
         T, B, H, W, C = dhs_tm.shape
-        assert (H, W, C) == (5, 8, 64) and dhs_tm.dtype == hs_tm.dtype == torch.float32
+        assert (H, W) == (5, 8) and dhs_tm.dtype == hs_tm.dtype == torch.float32
         assert dhs_tm.is_contiguous() and hs_tm.is_contiguous() and tuple(hs_tm.shape) == (T, B, H, W, C)
-        assert tuple(w_ihwo.shape) == (128, 3, 3, 64) and w_ihwo.dtype == torch.float32 and w_ihwo.is_contiguous()
+        assert tuple(w_ihwo.shape) == (2 * C, 3, 3, C) and w_ihwo.dtype == torch.float32 and w_ihwo.is_contiguous()
         dpre = torch.empty((T, B, H, W, C), dtype=torch.float32, device=dhs_tm.device)
         dxs = torch.empty((T, B, H, W, C), dtype=torch.float32, device=dhs_tm.device)
         dh0 = torch.empty((B, H, W, C), dtype=torch.float32, device=dhs_tm.device) if want_dh0 else None
-        self._ck(self.lib.eve_crnn_scan_bwd(B, T, self._p(dhs_tm), self._p(hs_tm), self._p(w_ihwo), self._p(dpre), self._p(dxs),
+        self._ck(self.lib.eve_crnn_scan_bwd_c(B, T, C, self._p(dhs_tm), self._p(hs_tm), self._p(w_ihwo), self._p(dpre), self._p(dxs),
                                             self._p(dh0), self._stream()))
         return dpre, dxs, dh0
 
     def clstm_scan_fwd(self, xs, h0, c0, w_ohwi, bias):
-        """CLSTMCell over T in one launch (float32, forward only).  xs [B, T, 5, 8, 64] -> (hs, cs) [B, T, 5, 8, 64]."""
+        """CLSTMCell over T in one launch (float32, forward only).  xs [B, T, 5, 8, C] -> (hs, cs) [B, T, 5, 8, C], C in SCAN_WIDTHS."""
         B, T, H, W, C = xs.shape
-        assert (H, W, C) == (5, 8, 64) and xs.dtype == torch.float32 and xs.is_contiguous()
-        assert tuple(w_ohwi.shape) == (256, 3, 3, 128) and w_ohwi.dtype == torch.float32 and w_ohwi.is_contiguous()
+        assert (H, W) == (5, 8) and xs.dtype == torch.float32 and xs.is_contiguous()
+        assert tuple(w_ohwi.shape) == (4 * C, 3, 3, 2 * C) and w_ohwi.dtype == torch.float32 and w_ohwi.is_contiguous()
         for s0 in (h0, c0):
             assert s0 is None or (s0.dtype == torch.float32 and s0.is_contiguous() and tuple(s0.shape) == (B, H, W, C))
         hs = torch.empty((B, T, H, W, C), dtype=torch.float32, device=xs.device)
         cs = torch.empty((B, T, H, W, C), dtype=torch.float32, device=xs.device)
-        self._ck(self.lib.eve_clstm_scan_fwd(B, T, self._p(xs), self._p(h0), self._p(c0), self._p(w_ohwi),
+        self._ck(self.lib.eve_clstm_scan_fwd_c(B, T, C, self._p(xs), self._p(h0), self._p(c0), self._p(w_ohwi),
                                              self._p(self._f32(bias, 'bias')), self._p(hs), self._p(cs), self._stream()))
         return hs, cs
 

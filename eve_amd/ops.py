@@ -1321,7 +1321,7 @@ class CRNNScanFn(torch.autograd.Function):
     """hs[:, t] = CRNNCell(xs[:, t], hs[:, t-1]) = tanh(conv3x3([x_t | h_{t-1}]) + b) for the whole clip in ONE launch, and the
     frame-reversed backward in one more (kernels.crnn_scan_{fwd,bwd}, float32: csrc/cell_scan_f32.hip; common.py:331-352 applied
     per frame by refine_net.py:132-176).  The weight and bias gradients are one batched launch each over all T*B frames.
-    xs float32 [B, T, 5, 8, 64] (16-bit callers convert: the bottleneck is 2 560 values per frame)."""
+    xs float32 [B, T, 5, 8, C], C in kernels.SCAN_WIDTHS (16-bit callers convert: the bottleneck is 40 C values per frame)."""
 
     @staticmethod
     def forward(ctx, xs, w, b, h0, pack):
@@ -1359,7 +1359,7 @@ class CRNNScanFn(torch.autograd.Function):
 def clstm_scan(xs, weight, bias, pack, h0=None, c0=None):
     """CLSTMCell over a clip in one launch, forward only (kernels.clstm_scan_fwd; common.py:355-385): the reference stores
     the (h, c) tuple and never feeds it to the decoder (refine_net.py:168-174), so nothing is differentiated.
-    xs [B, T, 5, 8, 64] any dtype -> (hs, cs) float32 [B, T, 5, 8, 64]."""
+    xs [B, T, 5, 8, C] any dtype -> (hs, cs) float32 [B, T, 5, 8, C]."""
     k = default_kernels()
     with torch.no_grad():
         w_ohwi, _ = _float_banks(weight, pack)

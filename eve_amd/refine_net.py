@@ -13,7 +13,7 @@ Mirrors /root/reference/src/models/refine_net.py:
     its output is NOT used downstream, so its weights get no gradient.
 
 `forward_sequence` folds all T frames into the image batch for the encoder and decoder (InstanceNorm
-is per-sample) and runs only the 64x5x8 conv-RNN sequentially.
+is per-sample) and runs only the Cx5x8 conv-RNN cells sequentially (one clip-long scan per cell where `_use_scan` allows).
 
 nn.Conv2d / nn.InstanceNorm2d objects are PARAMETER HOLDERS; their ATen forward is never called.
 """
@@ -24,7 +24,8 @@ from torch import nn
 from . import ops
 from .config import get_config
 from .eye_net import default_compute_dtype
-from .kernels import ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_TANH, HALF_DTYPES, default_kernels, dispatch_flag, pad_channels
+from .kernels import (ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_TANH, HALF_DTYPES, SCAN_WIDTHS, default_kernels, dispatch_flag,
+                      pad_channels)
 from .ops import PackedWeight
 
 
@@ -323,11 +324,20 @@ class RefineNet(nn.Module):
 
     @staticmethod
     def _use_scan(cells, hwc, dtype):
-        # one cell on the model's 5 x 8 x 64 bottleneck: the whole clip goes through it in ONE persistent launch (hidden state
-        # resident in LDS); CGRU in the 16-bit formats on cgru_scan.hip, CGRU in float32 and CRNN / CLSTM in any format on the
-        # float32 scans of cell_scan_f32.hip (round 5; the per-frame loop remains for stacked cells / other geometries)
-        return (len(cells) == 1 and tuple(hwc) == (5, 8, 64) and dispatch_flag(default_kernels(), 'cgru_scan', 1) != 0 and
-                dtype in HALF_DTYPES + (torch.float32,))
+        # the 5 x 8 x C bottleneck with C in SCAN_WIDTHS (32, 64, 128) and any number of stacked cells: every cell takes the whole
+        # clip in ONE persistent launch (hidden state resident in LDS), cell i scanning cell i-1's states.  CGRU in the 16-bit
+        # formats at C = 64 on cgru_scan.hip / cgru_scan1.hip (16-bit MFMA) and at C = 32 / 128 on the 16-bit-storage
+        # instantiation of the float32 scan (same rounding points); CGRU in float32 and CRNN / CLSTM in any format on the
+        # float32 scans of cell_scan_f32.hip.  Every other width stays on the per-frame loop.
+        # Left per frame by default because their scan measured SLOWER than the per-frame 16-bit MFMA convolutions at B = 32 x
+        # T = 30 (profiles/refine_scan_widths.md): CGRU and CLSTM in bf16 / fp16 at C = 128, whose scans run 4x the C = 64
+        # arithmetic on the float32 MFMA.  eve_dispatch_config.cgru_scan = 3 scans them too (kernels and tests are kept).
+        cells, C = list(cells), tuple(hwc)[-1]
+        flag = dispatch_flag(default_kernels(), 'cgru_scan', 1)
+        if not (cells and tuple(hwc)[:2] == (5, 8) and C in SCAN_WIDTHS and dtype in HALF_DTYPES + (torch.float32,) and flag != 0):
+            return False
+        slower = C == 128 and dtype in HALF_DTYPES and isinstance(cells[0], (CGRUCell, CLSTMCell))
+        return flag == 3 or not slower
 
     def _carried_dtypes(self):
         """Per cell, the dtype(s) the bottleneck carries its state in (internal NHWC layout [B, 5, 8, C]): the float32 scans keep
@@ -373,8 +383,7 @@ class RefineNet(nn.Module):
         returned here (the last frame of a previous call), or the internal NHWC layout [B, 5, 8, C]; (h, c) for CLSTM."""
         hf, scan, raw, to_ref = self._sequence(heatmap_initial, screen_frame, self._initial_states_in(initial_states))
         if scan:
-            cell, st = self._rnn_cells()[0], raw[0]
-            return hf, [tuple(to_ref(t) for t in st) if isinstance(cell, CLSTMCell) else to_ref(st)]
+            return hf, [tuple(to_ref(t) for t in st) if isinstance(st, tuple) else to_ref(st) for st in raw]
         hist = raw
         stacked = []
         for i in range(len(hist[0]) if hist else 0):
@@ -387,7 +396,7 @@ class RefineNet(nn.Module):
 
     def _sequence(self, heatmap_initial, screen_frame, h0):
         """The clip pass behind forward_sequence.  h0: None or per cell the internal-layout initial state (_initial_states_in).
-        Returns (heatmap_final [B,T,1,H,W], scan, raw, to_ref): with `scan` raw is the single cell's per-frame states [B,T,5,8,C]
+        Returns (heatmap_final [B,T,1,H,W], scan, raw, to_ref): with `scan` raw holds per cell its per-frame states [B,T,5,8,C]
         (a pair for CLSTM), otherwise raw is the per-frame list of per-cell states; to_ref converts [B,T,5,8,C] to [B,T,C,5,8]."""
         P = self._get_packs()
         B, T = heatmap_initial.shape[:2]
@@ -403,21 +412,24 @@ class RefineNet(nn.Module):
         h5, w5 = x.shape[1], x.shape[2]
         to_ref = lambda t: ops.FromNHWCFn.apply(t.reshape(B * T, h5, w5, C), C).view(B, T, C, h5, w5)
         if self._use_scan(cells, xs.shape[2:], xs.dtype):
-            cell, name = cells[0], '%s.rnn_cells.0' % prefix
-            init = h0[0] if h0 is not None else None
-            if isinstance(cell, CGRUCell):
-                hs = ops.CGRUScanFn.apply(xs.contiguous(), cell.gates_1.weight, cell.gates_1.bias, cell.gate_2.weight,
-                                          cell.gate_2.bias, init, P[name + '.gates_1'], P[name + '.gate_2'])
-                raw = [hs]
-            elif isinstance(cell, CRNNCell):
-                hs = ops.CRNNScanFn.apply(xs.float(), cell.cell.weight, cell.cell.bias, init, P[name + '.cell'])
-                raw = [hs]
-                hs = hs.to(xs.dtype)
-            else:                       # CLSTM: the state is computed and stored, the features pass through (refine_net.py:168-174)
-                h_init, c_init = init if init is not None else (None, None)
-                hcs = ops.clstm_scan(xs, cell.gates.weight, cell.gates.bias, P[name + '.gates'], h_init, c_init)
-                raw = [tuple(hcs)]
-                hs = xs
+            # a stack is cell 0 scanned over the clip, then cell 1 over cell 0's states, ...: cell i at frame t reads cell i-1 at
+            # frame t and its own state at t-1, which is all the per-frame loop of refine_net.py:154-176 does
+            raw, hs = [], xs
+            for i, cell in enumerate(cells):
+                name = '%s.rnn_cells.%d' % (prefix, i)
+                init = h0[i] if h0 is not None else None
+                if isinstance(cell, CGRUCell):
+                    hs = ops.CGRUScanFn.apply(hs.contiguous(), cell.gates_1.weight, cell.gates_1.bias, cell.gate_2.weight,
+                                              cell.gate_2.bias, init, P[name + '.gates_1'], P[name + '.gate_2'])
+                    raw.append(hs)
+                elif isinstance(cell, CRNNCell):
+                    st = ops.CRNNScanFn.apply(hs.float(), cell.cell.weight, cell.cell.bias, init, P[name + '.cell'])
+                    raw.append(st)
+                    hs = st.to(xs.dtype)
+                else:                   # CLSTM: the state is computed and stored, the features pass through (refine_net.py:168-174),
+                    h_init, c_init = init if init is not None else (None, None)      # so every CLSTM cell of a stack sees xs
+                    hcs = ops.clstm_scan(hs, cell.gates.weight, cell.gates.bias, P[name + '.gates'], h_init, c_init)
+                    raw.append(tuple(hcs))
             x = self._tap('rnn', hs.reshape(B * T, h5, w5, C))
             hf = self._decode(x, skips, P)
             return hf.view(B, T, 1, hf.shape[2], hf.shape[3]), True, raw, to_ref
@@ -427,6 +439,8 @@ class RefineNet(nn.Module):
             outs.append(xt)
             hist.append(states)
         x = torch.stack(outs, dim=1).view(B * T, x.shape[1], x.shape[2], C)
+        if cells:
+            x = self._tap('rnn', x)                 # the same stage boundary as on the scan branch
         hf = self._decode(x, skips, P)
         return hf.view(B, T, 1, hf.shape[2], hf.shape[3]), False, hist, to_ref
 

@@ -81,7 +81,7 @@ typedef struct eve_dispatch_config {
     int conv3x3_stream;            /* EVE_CONV3X3_STREAM    1   3x3 / stride 1 between 16..64 channels on 64 / 128-wide images: row-streaming kernel */
     int in_big_planes;             /* EVE_IN_BIG_PLANES     1   register-resident InstanceNorm (no affine) for planes beyond 8 192 vectors, dealt by channels */
     int cgru_seq_max_b;            /* EVE_CGRU_SEQ_MAX_B    384 16-bit conv-GRU clip scans: one sequence per workgroup (cgru_scan1.hip) up to this many sequences, three per workgroup (cgru_scan.hip) beyond */
-    int cgru_scan;                 /* EVE_CGRU_SCAN         1   conv-RNN bottleneck as ONE clip-long launch per direction (0: per-frame launches; bit 1 cleared = 2: forward scan only, per-frame backward) */
+    int cgru_scan;                 /* EVE_CGRU_SCAN         1   conv-RNN bottleneck as ONE clip-long launch per direction (0: per-frame launches; 2: forward scan only, per-frame backward; 3: also the combinations the default leaves per frame because their scan measured slower: 16-bit CGRU / CLSTM at width 128) */
     int small_linear;              /* EVE_SMALL_LINEAR      1   float32 nn.Linear of the tail on the small-tile FMA kernels (linear_small.hip)  */
     int tail_loss_node;            /* EVE_TAIL_LOSS_NODE    1   EyeNet tail + losses as one autograd node (ops.EyeTailLossFn)                   */
     int bucket_elems;              /* EVE_BUCKET_ELEMS      4194304  floats per data-parallel gradient bucket (parallel.GradSync)              */
@@ -473,6 +473,31 @@ int eve_crnn_scan_bwd(int B, int T, const float* dhs_tm, const float* hs_tm, con
  * reaches the cell.  w OHWI [256][3][3][128]; bias [256]; h0 / c0 or NULL.  Outputs hs, cs [B][T][5][8][64].               */
 int eve_clstm_scan_fwd(int B, int T, const float* xs, const float* h0, const float* c0, const float* w, const float* bias,
                        float* hs, float* cs, eve_stream_t stream);
+/* The five clip scans above with the bottleneck width C (refine_net_num_features) as an argument after T (additive: ABI v10).
+ * Operand shapes are the ones documented above with 64 -> C and 128 -> 2C:
+ *   cgru:  xs [B][T][5][8][C]; h0 [B][5][8][C] or NULL; w1 OHWI [2C][3][3][2C], b1 [2C]; w2 OHWI [C][3][3][2C], b2 [C];
+ *          hs [B][T][5][8][C]; time-major hs_tm, rh, og [T][B][5][8][C], ru [T][B][5][8][2C];
+ *          backward: w1t IHWO [2C][3][3][2C], w2t IHWO [2C][3][3][C]; dg1_all [T][B][5][8][2C]; dg2_all, dxs_tm [T][B][5][8][C];
+ *          dh0 [B][5][8][C] or NULL.
+ *   crnn:  w OHWI [C][3][3][2C], bias [C]; wt IHWO [2C][3][3][C]; hs, hs_tm, dpre_all, dxs_tm as above with C channels.
+ *   clstm: w OHWI [4C][3][3][2C], bias [4C]; h0 / c0 [B][5][8][C] or NULL; hs, cs [B][T][5][8][C].
+ * Widths: C in {32, 64, 128} for every entry and format.  float32 (cgru with dtype f32, crnn, clstm): one workgroup per
+ * sequence at every B (cell_scan_f32.hip, kernel names "<base>" at 64 and "<base><32>" / "<base><128>" otherwise).  cgru with
+ * dtype bf16 / f16: C = 64 on the 16-bit MFMA kernels; C = 32 / 128 on the 16-bit-storage instantiation of the float32 scan
+ * (values rounded to the format where the 16-bit kernels round them, products on the float32 MFMA; names
+ * "cgru_scan_f32_{fwd,bwd}_kernel<C, eve::bf16_t>").  Any other C returns non-zero with a message in eve_last_error() and
+ * launches nothing.  The entry points without `_c` are these with C = 64. */
+int eve_cgru_scan_fwd_c(int dtype, int B, int T, int C, const void* xs, const void* h0, const void* w1, const float* b1,
+                        const void* w2, const float* b2, void* hs, void* hs_tm, void* ru, void* rh, void* og, eve_stream_t stream);
+int eve_cgru_scan_bwd_c(int dtype, int B, int T, int C, const void* dhs_tm, const void* ru, const void* og, const void* hs_tm,
+                        const void* h0, const void* w1t, const void* w2t, void* dg1_all, void* dg2_all, void* dxs_tm, void* dh0,
+                        eve_stream_t stream);
+int eve_crnn_scan_fwd_c(int B, int T, int C, const float* xs, const float* h0, const float* w, const float* bias, float* hs,
+                        float* hs_tm, eve_stream_t stream);
+int eve_crnn_scan_bwd_c(int B, int T, int C, const float* dhs_tm, const float* hs_tm, const float* wt, float* dpre_all,
+                        float* dxs_tm, float* dh0, eve_stream_t stream);
+int eve_clstm_scan_fwd_c(int B, int T, int C, const float* xs, const float* h0, const float* c0, const float* w, const float* bias,
+                         float* hs, float* cs, eve_stream_t stream);
 int eve_cgru_gates1(int dtype, long long P, int C, const void* g1, const void* h, void* ru, void* rh,
                     eve_stream_t stream);
 int eve_cgru_gates2(int dtype, long long P, int C, const void* g2, const void* ru, const void* h,
