@@ -99,6 +99,8 @@ SIGNATURES = {
     'eve_crnn_scan_fwd_c': [I, I, I, P, P, P, P, P, P, P],
     'eve_crnn_scan_bwd_c': [I, I, I, P, P, P, P, P, P, P],
     'eve_clstm_scan_fwd_c': [I, I, I, P, P, P, P, P, P, P, P],
+    'eve_clstm_scan_fwd_train_c': [I, I, I, P, P, P, P, P, P, P, P, P, P, P],
+    'eve_clstm_scan_bwd_c': [I, I, I, P, P, P, P, P, P, P, P, P, P, P],
     'eve_rnn_scan_fwd': [I, I, I, P, P, P, P, P, P],
     'eve_rnn_scan_bwd': [I, I, I, P, P, P, P, P, P],
     'eve_lstm_scan_fwd': [I, I, I, P, P, P, P, P, P, P, P, P],
@@ -155,6 +157,7 @@ SIGNATURES = {
     'eve_cgru_gates2_bwd': [I, L, I, P, P, P, P, P, P, P, P],
     'eve_cgru_gates1_bwd': [I, L, I, P, P, P, P, P, P, P],
     'eve_clstm_gates_fwd': [I, L, I, P, P, P, P, P],
+    'eve_clstm_gates_bwd': [I, L, I, P, P, P, P, P, P, P],
     'eve_heatmap_head_fwd': [I, L, I, P, P, P],
     'eve_heatmap_head_bwd': [I, L, I, P, P, P, P],
     'eve_heatmap_loss_fwd': [I, I, I, I, P, P, P, P, P, P, P],

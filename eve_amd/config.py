@@ -52,6 +52,10 @@ class HotPathConfig(object):
     refine_net_rnn_type = 'CGRU'
     refine_net_rnn_num_cells = 1
     refine_net_num_features = 64
+    # eve_amd only, NOT a reference key: True makes a tuple-state (CLSTM) cell's h the bottleneck features, so the cell refines
+    # and trains.  The reference hands the cell's INPUT on (refine_net.py:168-174) and that stays the default; readers use
+    # getattr(config, 'refine_net_clstm_feeds_features', False) because the reference's own singleton has no such key.
+    refine_net_clstm_feeds_features = False
     loss_coeff_heatmap_ce_initial = 0.0
     loss_coeff_heatmap_ce_final = 1.0
     loss_coeff_heatmap_mse_final = 0.0

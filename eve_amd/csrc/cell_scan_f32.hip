@@ -1,8 +1,10 @@
 // Clip-long scans of RefineNet's conv-RNN bottleneck cells in FLOAT32: CGRUCell (forward + backward), CRNNCell (forward +
-// backward) and CLSTMCell (forward only: the reference never back-propagates through it, refine_net.py:168-174) --
-// /root/reference/src/models/common.py:331-352 (CRNN), :355-385 (CLSTM), :388-415 (CGRU), applied per frame by
-// refine_net.py:132-176.  One persistent launch walks all T frames of a clip; before round 5 the float32 parity mode and the
-// CLSTM / CRNN cells ran T x (1-2 convolution launches + gate kernels + concatenations).
+// backward) and CLSTMCell (forward; training forward + backward) -- /root/reference/src/models/common.py:331-352 (CRNN),
+// :355-385 (CLSTM), :388-415 (CGRU), applied per frame by refine_net.py:132-176.  One persistent launch walks all T frames of a
+// clip; before round 5 the float32 parity mode and the CLSTM / CRNN cells ran T x (1-2 convolution launches + gate kernels +
+// concatenations).  The reference never back-propagates through its CLSTM cell (refine_net.py:168-174 hands the cell's INPUT on):
+// clstm_scan_f32_fwd_kernel serves that default.  The training forward and the backward exist for eve_amd's opt-in config key
+// refine_net_clstm_feeds_features, which departs from the reference on purpose and makes the cell's h the bottleneck features.
 //
 // Geometry: 5 x 8 pixels (fixed by the model), C hidden + C input channels with C = refine_net_num_features in {32, 64, 128}
 // as a template parameter (64 is the shipped configuration; its instantiations keep their pre-template kernel names and
@@ -11,7 +13,8 @@
 // banks: 68, 132 and 260 are all 4 mod 64, and the halo row stride 10 x (2C + 4) is 40 mod 64 for all three, so the three
 // widths have ONE bank pattern), the convolution output [40][<= 4C], and the state(s).
 //   LDS per workgroup:  C = 32: 19 KB halo + 10 / 20 KB output;  C = 64: 36 KB + 20 / 40 KB;  C = 128: 71 KB + 40 KB (CGRU, CRNN)
-//   or + 80 KB (CLSTM: 151 KB of the CU's 160 KB, all four gates of a frame in one piece).
+//   or + 80 KB (CLSTM forward: 151 KB of the CU's 160 KB, all four gates of a frame in one piece; the CLSTM backward's data
+//   gradient contracts the 4C gate channels as two K slices of 2C through the same halo, 71 + 40 KB).
 // A convolution is an implicit GEMM on v_mfma_f32_16x16x4_f32 (exact float32: an fmaf chain) with A = filter rows (16 output
 // channels x 4 k) straight from global memory / L2 as one 16-byte load per lane and 16-channel K block, B = 16 pixels x 4 k as
 // one ds_read_b128 from the halo; the four words of a lane's vector feed four MFMAs (K permutation: MFMA s takes word s of every
@@ -64,7 +67,9 @@ __device__ __forceinline__ float cs_rnd(float v) {
     else return Elem<S>::round(v);
 }
 
-template <int STR, int CIN, int NTILE, bool FLIP, typename WT>
+// WCIN > CIN: the bank holds WCIN channels per tap and W points at the first of the CIN this call contracts (a K slice: the
+// CLSTM data gradient's gate pairs); the halo holds those CIN channels alone
+template <int STR, int CIN, int NTILE, bool FLIP, typename WT, int WCIN = CIN>
 __device__ __forceinline__ void cs_conv(const float* halo, const WT* __restrict__ W, const int co0, const int kb0, const int kb1,
                                         f32x4_t (&acc)[NTILE][3], const int lane) {
     constexpr int KB_PER_TAP = CIN / 16;
@@ -77,17 +82,21 @@ __device__ __forceinline__ void cs_conv(const float* halo, const WT* __restrict_
     }
     const WT* wrow[NTILE];
 #pragma unroll
-    for (int nt = 0; nt < NTILE; ++nt) wrow[nt] = W + (size_t)(co0 + nt * 16 + i) * (9 * CIN) + 4 * kk;
+    for (int nt = 0; nt < NTILE; ++nt) wrow[nt] = W + (size_t)(co0 + nt * 16 + i) * (9 * WCIN) + 4 * kk;
+    auto wofs = [](const int kb) {                                         // floats from a filter row's start to K block kb
+        if constexpr (WCIN == CIN) return kb * 16;
+        else return (kb / KB_PER_TAP) * WCIN + (kb % KB_PER_TAP) * 16;
+    };
     float4 a_next[NTILE];
 #pragma unroll
-    for (int nt = 0; nt < NTILE; ++nt) a_next[nt] = cs_ldw(wrow[nt] + kb0 * 16);
+    for (int nt = 0; nt < NTILE; ++nt) a_next[nt] = cs_ldw(wrow[nt] + wofs(kb0));
     auto step = [&](const int kb) {
         float4 a[NTILE];
 #pragma unroll
         for (int nt = 0; nt < NTILE; ++nt) a[nt] = a_next[nt];
         const int kn = min(kb + 1, kb1 - 1);
 #pragma unroll
-        for (int nt = 0; nt < NTILE; ++nt) a_next[nt] = cs_ldw(wrow[nt] + kn * 16);
+        for (int nt = 0; nt < NTILE; ++nt) a_next[nt] = cs_ldw(wrow[nt] + wofs(kn));
         const int tap = kb / KB_PER_TAP, blk = kb - tap * KB_PER_TAP;
         const int kh = tap / 3, kw = tap - kh * 3;
         const int dy = FLIP ? 2 - kh : kh, dx = FLIP ? 2 - kw : kw;
@@ -150,8 +159,9 @@ __device__ __forceinline__ void cs_zero(f32x4_t (&acc)[NTILE][3]) {
 //   8 tiles or more (COUT = 128, 256, 512): COUT / 128 tiles per wave, each wave the whole K.
 //   fewer (COUT = 64, 32): a tile belongs to 8 / tiles waves which split K evenly; part 0 stores (with the bias), parts 1..
 //   add one after the other, a barrier between them (fixed order: the result does not depend on timing).
+// ACC: the result is added to `out` (a second K slice of the same sum).
 // Ends with a barrier: `out` is complete, the halo is free.
-template <int STR, int CIN, int COUT, bool FLIP, typename WT>
+template <int STR, int CIN, int COUT, bool FLIP, typename WT, int WCIN = CIN, bool ACC = false>
 __device__ __forceinline__ void cs_conv_all(const float* halo, const WT* __restrict__ W, const float* __restrict__ bias,
                                             float* out, const int ostr, const int wave, const int lane) {
     constexpr int KB = 9 * CIN / 16, TILES = COUT / 16;
@@ -160,16 +170,16 @@ __device__ __forceinline__ void cs_conv_all(const float* halo, const WT* __restr
         constexpr int NT = TILES / 8;
         f32x4_t acc[NT][3];
         cs_zero<NT>(acc);
-        cs_conv<STR, CIN, NT, FLIP, WT>(halo, W, wave * 16 * NT, 0, KB, acc, lane);
-        cs_store<NT, false>(out, ostr, wave * 16 * NT, bias, acc, lane);
+        cs_conv<STR, CIN, NT, FLIP, WT, WCIN>(halo, W, wave * 16 * NT, 0, KB, acc, lane);
+        cs_store<NT, ACC>(out, ostr, wave * 16 * NT, bias, acc, lane);
     } else {
         constexpr int KS = 8 / TILES;                 // waves per tile
         static_assert(KB % KS == 0, "K split");
         const int tile = wave % TILES, part = wave / TILES;
         f32x4_t acc[1][3];
         cs_zero<1>(acc);
-        cs_conv<STR, CIN, 1, FLIP, WT>(halo, W, tile * 16, part * (KB / KS), (part + 1) * (KB / KS), acc, lane);
-        if (part == 0) cs_store<1, false>(out, ostr, tile * 16, bias, acc, lane);
+        cs_conv<STR, CIN, 1, FLIP, WT, WCIN>(halo, W, tile * 16, part * (KB / KS), (part + 1) * (KB / KS), acc, lane);
+        if (part == 0) cs_store<1, ACC>(out, ostr, tile * 16, bias, acc, lane);
 #pragma unroll
         for (int s = 1; s < KS; ++s) {
             __syncthreads();
@@ -380,13 +390,18 @@ __global__ __launch_bounds__(CS_NT) void crnn_scan_f32_bwd_kernel(const int B, c
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
-// CLSTM forward (common.py:355-385; gate order in / forget / out / cell).  w OHWI [4C][9][2C].  hs, cs [B][T][40][C].
+// CLSTM (common.py:355-385; gate order in / forget / out / cell).  w OHWI [4C][9][2C]; wt IHWO [2C][9][4C].
+// forward: hs, cs [B][T][40][C].  The training forward computes the same values in the same order and also writes what the
+// backward reads, time-major: the post-activation gates [T][B][40][4C], cs_tm and hs_tm [T][B][40][C].
+// backward: dpre_all [T][B][40][4C], dxs_tm [T][B][40][C], dh0 / dc0 [B][40][C].
 // ------------------------------------------------------------------------------------------------------------------------
-template <int C>
-__global__ __launch_bounds__(CS_NT) void clstm_scan_f32_fwd_kernel(const int B, const int T, const float* __restrict__ xs,
-                                                                   const float* __restrict__ h0, const float* __restrict__ c0,
-                                                                   const float* __restrict__ w, const float* __restrict__ bias,
-                                                                   float* __restrict__ hs, float* __restrict__ cs) {
+template <int C, bool TRAIN>
+__device__ __forceinline__ void clstm_scan_f32_fwd_body(const int B, const int T, const float* __restrict__ xs,
+                                                        const float* __restrict__ h0, const float* __restrict__ c0,
+                                                        const float* __restrict__ w, const float* __restrict__ bias,
+                                                        float* __restrict__ hs, float* __restrict__ cs,
+                                                        float* __restrict__ gates_tm, float* __restrict__ cs_tm,
+                                                        float* __restrict__ hs_tm) {
     using G = CsGeom<C>;
     constexpr int STR = G::STR, C2 = 2 * C, C4 = 4 * C;
     extern __shared__ __attribute__((aligned(16))) float cs_lds[];
@@ -411,8 +426,18 @@ __global__ __launch_bounds__(CS_NT) void clstm_scan_f32_fwd_kernel(const int B, 
         cs_conv_all<STR, C2, C4, false>(halo, w, bias, g, C4, wave, lane);
         CS_FOR_ELEMS(k, p, c) {
             const float gi = g[p * C4 + c], gf = g[p * C4 + C + c], go = g[p * C4 + 2 * C + c], gc = g[p * C4 + 3 * C + c];
-            cc[k] = cs_sigmoid(gf) * cc[k] + cs_sigmoid(gi) * tanhf(gc);
-            h[k] = cs_sigmoid(go) * tanhf(cc[k]);
+            const float si = cs_sigmoid(gi), sf = cs_sigmoid(gf), so = cs_sigmoid(go), tg = tanhf(gc);
+            cc[k] = sf * cc[k] + si * tg;
+            h[k] = so * tanhf(cc[k]);
+            if constexpr (TRAIN) {
+                const size_t tm = ((size_t)t * B + b) * CS_PIX + p;
+                gates_tm[tm * C4 + c] = si;
+                gates_tm[tm * C4 + C + c] = sf;
+                gates_tm[tm * C4 + 2 * C + c] = so;
+                gates_tm[tm * C4 + 3 * C + c] = tg;
+                cs_tm[tm * C + c] = cc[k];
+                hs_tm[tm * C + c] = h[k];
+            }
             const size_t o = (((size_t)b * T + t) * CS_PIX + p) * C + c;
             hs[o] = h[k];
             cs[o] = cc[k];
@@ -420,7 +445,90 @@ __global__ __launch_bounds__(CS_NT) void clstm_scan_f32_fwd_kernel(const int B, 
     }
 }
 
+template <int C>
+__global__ __launch_bounds__(CS_NT) void clstm_scan_f32_fwd_kernel(const int B, const int T, const float* __restrict__ xs,
+                                                                   const float* __restrict__ h0, const float* __restrict__ c0,
+                                                                   const float* __restrict__ w, const float* __restrict__ bias,
+                                                                   float* __restrict__ hs, float* __restrict__ cs) {
+    clstm_scan_f32_fwd_body<C, false>(B, T, xs, h0, c0, w, bias, hs, cs, nullptr, nullptr, nullptr);
+}
+
+template <int C>
+__global__ __launch_bounds__(CS_NT) void clstm_scan_f32_fwd_train_kernel(const int B, const int T, const float* __restrict__ xs,
+                                                                         const float* __restrict__ h0, const float* __restrict__ c0,
+                                                                         const float* __restrict__ w, const float* __restrict__ bias,
+                                                                         float* __restrict__ hs, float* __restrict__ cs,
+                                                                         float* __restrict__ gates_tm, float* __restrict__ cs_tm,
+                                                                         float* __restrict__ hs_tm) {
+    clstm_scan_f32_fwd_body<C, true>(B, T, xs, h0, c0, w, bias, hs, cs, gates_tm, cs_tm, hs_tm);
+}
+
+// Backward (common.py:376-385 differentiated; per frame: recurrent.hip's clstm_gates_bwd_kernel + the gate convolution's data
+// gradient).  dhs_tm, cs_tm [T][B][40][C]; gates_tm [T][B][40][4C] post-activation; dcs_tm (gradient arriving at the stored cell
+// states) or null.  The data gradient contracts 4C gate channels, whose halo would be 144 KB at C = 128: it runs as two K
+// slices of 2C (in + forget, then out + cell) through the 2C-channel halo, the second added to the first in LDS.
+template <int C>
+__global__ __launch_bounds__(CS_NT) void clstm_scan_f32_bwd_kernel(const int B, const int T, const float* __restrict__ dhs_tm,
+                                                                   const float* __restrict__ dcs_tm,
+                                                                   const float* __restrict__ gates_tm,
+                                                                   const float* __restrict__ cs_tm, const float* __restrict__ c0,
+                                                                   const float* __restrict__ wt, float* __restrict__ dpre_all,
+                                                                   float* __restrict__ dxs_tm, float* __restrict__ dh0,
+                                                                   float* __restrict__ dc0) {
+    using G = CsGeom<C>;
+    constexpr int STR = G::STR, C2 = 2 * C, C4 = 4 * C;
+    extern __shared__ __attribute__((aligned(16))) float cs_lds[];
+    float* halo = cs_lds;
+    float* g = halo + G::HALO;                       // [40][2C]
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = blockIdx.x;
+    cs_zero_halo<G::HALO>(halo, tid);
+    float carry_h[G::NE], carry_c[G::NE], dpo[G::NE], dpg[G::NE];
+    CS_FOR_ELEMS(k, p, c) carry_h[k] = carry_c[k] = 0.f;
+    __syncthreads();
+    for (int t = T - 1; t >= 0; --t) {
+        const size_t tm = ((size_t)t * B + b) * CS_PIX;
+        CS_FOR_ELEMS(k, p, c) {
+            const float* gt = gates_tm + (tm + p) * C4 + c;
+            const float gi = gt[0], gf = gt[C], go = gt[2 * C], gg = gt[3 * C];
+            const float cp = t > 0 ? cs_tm[(((size_t)(t - 1) * B + b) * CS_PIX + p) * C + c]
+                                   : (c0 ? c0[((size_t)b * CS_PIX + p) * C + c] : 0.f);
+            const float dh = dhs_tm[(tm + p) * C + c] + carry_h[k];
+            const float tc = tanhf(cs_tm[(tm + p) * C + c]);
+            float dc = carry_c[k] + dh * go * (1.f - tc * tc);
+            if (dcs_tm) dc += dcs_tm[(tm + p) * C + c];
+            const float dpi = dc * gg * gi * (1.f - gi), dpf = dc * cp * gf * (1.f - gf);
+            dpo[k] = dh * tc * go * (1.f - go);
+            dpg[k] = dc * gi * (1.f - gg * gg);
+            carry_c[k] = dc * gf;
+            float* dp = dpre_all + (tm + p) * C4 + c;
+            dp[0] = dpi; dp[C] = dpf; dp[2 * C] = dpo[k]; dp[3 * C] = dpg[k];
+            halo[cs_halo_at<STR>(p) + c] = dpi;
+            halo[cs_halo_at<STR>(p) + C + c] = dpf;
+        }
+        __syncthreads();
+        cs_conv_all<STR, C2, C2, true, float, C4, false>(halo, wt, nullptr, g, C2, wave, lane);          // d[x | h], in + forget
+        CS_FOR_ELEMS(k, p, c) {
+            halo[cs_halo_at<STR>(p) + c] = dpo[k];
+            halo[cs_halo_at<STR>(p) + C + c] = dpg[k];
+        }
+        __syncthreads();
+        cs_conv_all<STR, C2, C2, true, float, C4, true>(halo, wt + C2, nullptr, g, C2, wave, lane);      // += out + cell
+        CS_FOR_ELEMS(k, p, c) {
+            dxs_tm[(tm + p) * C + c] = g[p * C2 + c];
+            carry_h[k] = g[p * C2 + C + c];
+        }
+        __syncthreads();                                                 // g is read above, written by the next frame's first conv
+    }
+    CS_FOR_ELEMS(k, p, c) {
+        if (dh0) dh0[((size_t)b * CS_PIX + p) * C + c] = carry_h[k];
+        if (dc0) dc0[((size_t)b * CS_PIX + p) * C + c] = carry_c[k];
+    }
+}
+
 static_assert(CsGeom<128>::lds_bytes(4 * 128) <= (size_t)LDS_CU, "the CLSTM scan at C = 128 must fit a CU's LDS");
+static_assert(CsGeom<128>::lds_bytes(2 * 128) <= (size_t)LDS_CU,
+              "the CLSTM backward at C = 128 (2C-channel halo + [40][2C] data gradient; a 4C-channel halo alone is 144 KB) must fit");
 
 // the name a width's instantiation reports through eve_last_kernel(): C = 64 keeps the name it had before the template
 #define CS_KNAME(base) (C == 64 ? base : C == 32 ? base "<32>" : base "<128>")
@@ -544,4 +652,38 @@ extern "C" int eve_clstm_scan_fwd_c(int B, int T, int C, const float* xs, const 
 extern "C" int eve_clstm_scan_fwd(int B, int T, const float* xs, const float* h0, const float* c0, const float* w, const float* bias,
                                   float* hs, float* cs, eve_stream_t stream) {
     return eve_clstm_scan_fwd_c(B, T, 64, xs, h0, c0, w, bias, hs, cs, stream);
+}
+
+/* eve_clstm_scan_fwd_c for training: the same hs / cs, bit for bit, plus what eve_clstm_scan_bwd_c reads, time-major:
+   gates_tm [T][B][5][8][4C] (sigmoid(in), sigmoid(forget), sigmoid(out), tanh(cell)), cs_tm and hs_tm [T][B][5][8][C]. */
+extern "C" int eve_clstm_scan_fwd_train_c(int B, int T, int C, const float* xs, const float* h0, const float* c0, const float* w,
+                                          const float* bias, float* hs, float* cs, float* gates_tm, float* cs_tm, float* hs_tm,
+                                          eve_stream_t stream) {
+    if (B <= 0 || T <= 0 || !xs || !w || !bias || !hs || !cs || !gates_tm || !cs_tm || !hs_tm)
+        return set_error_msg("clstm_scan_fwd_train: bad arguments");
+    if (!eve_cell_scan_width_ok(C)) return set_error_msg("clstm_scan_fwd_train: unsupported channel count (32, 64, 128)");
+    const int width = C;
+    CS_DISPATCH_C(width, EVE_LAUNCH(CS_KNAME("clstm_scan_f32_fwd_train_kernel"), clstm_scan_f32_fwd_train_kernel<C>, dim3(B), dim3(CS_NT),
+                                    CsGeom<C>::lds_bytes(4 * C), (hipStream_t)stream, B, T, xs, h0, c0, w, bias, hs, cs, gates_tm, cs_tm,
+                                    hs_tm));
+    EVE_CHECK_LAUNCH();
+    return 0;
+}
+
+/* Backward of eve_clstm_scan_fwd_train_c, one launch walking the frames last to first.  Time-major dhs_tm, cs_tm
+   [T][B][5][8][C] and gates_tm [T][B][5][8][4C]; dcs_tm = gradient arriving at the stored cell states, or NULL; c0 as in the
+   forward or NULL; wt = the filter bank IHWO [2C][3][3][4C].  Outputs (time-major): dpre_all [T][B][5][8][4C] = gradient of the
+   gate pre-activations (what the batched weight / bias gradients read), dxs_tm [T][B][5][8][C]; dh0 / dc0 [B][5][8][C] or NULL. */
+extern "C" int eve_clstm_scan_bwd_c(int B, int T, int C, const float* dhs_tm, const float* dcs_tm, const float* gates_tm,
+                                    const float* cs_tm, const float* c0, const float* wt, float* dpre_all, float* dxs_tm, float* dh0,
+                                    float* dc0, eve_stream_t stream) {
+    if (B <= 0 || T <= 0 || !dhs_tm || !gates_tm || !cs_tm || !wt || !dpre_all || !dxs_tm)
+        return set_error_msg("clstm_scan_bwd: bad arguments");
+    if (!eve_cell_scan_width_ok(C)) return set_error_msg("clstm_scan_bwd: unsupported channel count (32, 64, 128)");
+    const int width = C;
+    CS_DISPATCH_C(width, EVE_LAUNCH(CS_KNAME("clstm_scan_f32_bwd_kernel"), clstm_scan_f32_bwd_kernel<C>, dim3(B), dim3(CS_NT),
+                                    CsGeom<C>::lds_bytes(2 * C), (hipStream_t)stream, B, T, dhs_tm, dcs_tm, gates_tm, cs_tm, c0, wt,
+                                    dpre_all, dxs_tm, dh0, dc0));
+    EVE_CHECK_LAUNCH();
+    return 0;
 }

@@ -425,6 +425,47 @@ __global__ __launch_bounds__(256) void clstm_gates_kernel(const T* __restrict__ 
     }
 }
 
+// its adjoint, for a cell whose output is used (eve_amd's refine_net_clstm_feeds_features): the activations and c' are formed
+// again from the pre-activations (c' unrounded, as the forward's h' saw it)
+template <typename T>
+__global__ __launch_bounds__(256) void clstm_gates_bwd_kernel(const T* __restrict__ dh, const T* __restrict__ dc_in,
+                                                              const T* __restrict__ g, const T* __restrict__ c_prev,
+                                                              T* __restrict__ dg, T* __restrict__ dc_prev, int C,
+                                                              long long items) {
+    constexpr int VEC = Elem<T>::VEC;
+    const int cvecs = C / VEC;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
+        const int cv = (int)(i % cvecs);
+        const long long p = i / cvecs;
+        float gi[VEC], gf[VEC], go[VEC], gc[VEC], cp[VEC], d[VEC], dc[VEC];
+        const T* gp = g + p * 4 * C + cv * VEC;
+        Elem<T>::unpack(*reinterpret_cast<const uint4*>(gp), gi);
+        Elem<T>::unpack(*reinterpret_cast<const uint4*>(gp + C), gf);
+        Elem<T>::unpack(*reinterpret_cast<const uint4*>(gp + 2 * C), go);
+        Elem<T>::unpack(*reinterpret_cast<const uint4*>(gp + 3 * C), gc);
+        Elem<T>::unpack(*reinterpret_cast<const uint4*>(c_prev + p * C + cv * VEC), cp);
+        Elem<T>::unpack(*reinterpret_cast<const uint4*>(dh + p * C + cv * VEC), d);
+        if (dc_in) Elem<T>::unpack(*reinterpret_cast<const uint4*>(dc_in + p * C + cv * VEC), dc);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            const float si = sigmoidf_(gi[e]), sf = sigmoidf_(gf[e]), so = sigmoidf_(go[e]), tg = tanhf(gc[e]);
+            const float tc = tanhf(sf * cp[e] + si * tg);
+            const float dcn = (dc_in ? dc[e] : 0.f) + d[e] * so * (1.f - tc * tc);
+            gi[e] = dcn * tg * si * (1.f - si);
+            gf[e] = dcn * cp[e] * sf * (1.f - sf);
+            go[e] = d[e] * tc * so * (1.f - so);
+            gc[e] = dcn * si * (1.f - tg * tg);
+            dc[e] = dcn * sf;
+        }
+        T* dp = dg + p * 4 * C + cv * VEC;
+        *reinterpret_cast<uint4*>(dp) = Elem<T>::pack(gi);
+        *reinterpret_cast<uint4*>(dp + C) = Elem<T>::pack(gf);
+        *reinterpret_cast<uint4*>(dp + 2 * C) = Elem<T>::pack(go);
+        *reinterpret_cast<uint4*>(dp + 3 * C) = Elem<T>::pack(gc);
+        *reinterpret_cast<uint4*>(dc_prev + p * C + cv * VEC) = Elem<T>::pack(dc);
+    }
+}
+
 static inline unsigned rgrid(long long items) {
     long long b = (items + 255) / 256;
     if (b > 2048) b = 2048;
@@ -575,6 +616,14 @@ extern "C" int eve_clstm_gates_fwd(int dtype, long long P, int C, const void* ga
                                    void* c, eve_stream_t stream) {
     CG_CHECK("clstm_gates_fwd")
     EVE_DISPATCH_T(dtype, hipLaunchKernelGGL(clstm_gates_kernel<T>, dim3(rgrid(items)), dim3(256), 0, s, (const T*)gates, (const T*)c_prev, (T*)h, (T*)c, C, items));
+    EVE_CHECK_LAUNCH();
+    return 0;
+}
+extern "C" int eve_clstm_gates_bwd(int dtype, long long P, int C, const void* dh, const void* dc_in, const void* gates,
+                                   const void* c_prev, void* dgates, void* dc_prev, eve_stream_t stream) {
+    CG_CHECK("clstm_gates_bwd")
+    if (!dh || !gates || !c_prev || !dgates || !dc_prev) return set_error_msg("clstm_gates_bwd: bad arguments");
+    EVE_DISPATCH_T(dtype, hipLaunchKernelGGL(clstm_gates_bwd_kernel<T>, dim3(rgrid(items)), dim3(256), 0, s, (const T*)dh, (const T*)dc_in, (const T*)gates, (const T*)c_prev, (T*)dgates, (T*)dc_prev, C, items));
     EVE_CHECK_LAUNCH();
     return 0;
 }

@@ -1086,6 +1086,40 @@ class HipKernels(object):
                                              self._p(self._f32(bias, 'bias')), self._p(hs), self._p(cs), self._stream()))
         return hs, cs
 
+    def clstm_scan_fwd_train(self, xs, h0, c0, w_ohwi, bias):
+        """clstm_scan_fwd for a cell that trains: the same (hs, cs), plus the time-major tensors clstm_scan_bwd reads --
+        gates_tm [T, B, 5, 8, 4C] (post-activation, in / forget / out / cell), cs_tm, hs_tm [T, B, 5, 8, C]."""
+        B, T, H, W, C = xs.shape
+        assert (H, W) == (5, 8) and xs.dtype == torch.float32 and xs.is_contiguous()
+        assert tuple(w_ohwi.shape) == (4 * C, 3, 3, 2 * C) and w_ohwi.dtype == torch.float32 and w_ohwi.is_contiguous()
+        for s0 in (h0, c0):
+            assert s0 is None or (s0.dtype == torch.float32 and s0.is_contiguous() and tuple(s0.shape) == (B, H, W, C))
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=xs.device)
+        hs, cs = new(B, T, H, W, C), new(B, T, H, W, C)
+        gates_tm, cs_tm, hs_tm = new(T, B, H, W, 4 * C), new(T, B, H, W, C), new(T, B, H, W, C)
+        self._ck(self.lib.eve_clstm_scan_fwd_train_c(B, T, C, self._p(xs), self._p(h0), self._p(c0), self._p(w_ohwi),
+                                                   self._p(self._f32(bias, 'bias')), self._p(hs), self._p(cs), self._p(gates_tm),
+                                                   self._p(cs_tm), self._p(hs_tm), self._stream()))
+        return hs, cs, gates_tm, cs_tm, hs_tm
+
+    def clstm_scan_bwd(self, dhs_tm, dcs_tm, gates_tm, cs_tm, c0, w_ihwo, want_d0=False):
+        """Backward of clstm_scan_fwd_train in one launch.  dhs_tm [T, B, 5, 8, C]; dcs_tm likewise or None (no gradient reached
+        the stored cell states); w_ihwo [2C, 3, 3, 4C].  -> (dpre_all [T, B, 5, 8, 4C], dxs_tm [T, B, 5, 8, C], dh0, dc0
+        [B, 5, 8, C] or None)."""
+        T, B, H, W, C = dhs_tm.shape
+        assert (H, W) == (5, 8)
+        for t, ch in ((dhs_tm, C), (dcs_tm, C), (gates_tm, 4 * C), (cs_tm, C)):
+            assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == (T, B, H, W, ch))
+        assert c0 is None or (c0.dtype == torch.float32 and c0.is_contiguous() and tuple(c0.shape) == (B, H, W, C))
+        assert tuple(w_ihwo.shape) == (2 * C, 3, 3, 4 * C) and w_ihwo.dtype == torch.float32 and w_ihwo.is_contiguous()
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dhs_tm.device)
+        dpre, dxs = new(T, B, H, W, 4 * C), new(T, B, H, W, C)
+        dh0, dc0 = (new(B, H, W, C), new(B, H, W, C)) if want_d0 else (None, None)
+        self._ck(self.lib.eve_clstm_scan_bwd_c(B, T, C, self._p(dhs_tm), self._p(dcs_tm), self._p(gates_tm), self._p(cs_tm),
+                                             self._p(c0), self._p(w_ihwo), self._p(dpre), self._p(dxs), self._p(dh0), self._p(dc0),
+                                             self._stream()))
+        return dpre, dxs, dh0, dc0
+
     # ------------------------------------------------------------------ streaming inference (eve_amd/stream.py)
     def eye_tail_stream_fwd(self, feats, head_pose, weights, h, reset=None, want_hs=False):
         """The EyeNet tail forward in one launch with the GRU state `h` [S, 128] float32 read and overwritten in place.
@@ -1168,6 +1202,16 @@ class HipKernels(object):
         self._ck(self.lib.eve_clstm_gates_fwd(dt_code(c_prev.dtype), P, C, self._p(gates), self._p(c_prev),
                                               self._p(h), self._p(c), self._stream()))
         return h, c
+
+    def clstm_gates_bwd(self, dh, dc_in, gates, c_prev):
+        """Adjoint of clstm_gates_fwd: (dgates [.., 4C] w.r.t. the pre-activations, dc_prev [.., C]); dc_in may be None."""
+        C = c_prev.shape[-1]
+        P = c_prev.numel() // C
+        dgates = torch.empty_like(gates)
+        dc_prev = torch.empty_like(c_prev)
+        self._ck(self.lib.eve_clstm_gates_bwd(dt_code(c_prev.dtype), P, C, self._p(dh), self._p(dc_in), self._p(gates),
+                                              self._p(c_prev), self._p(dgates), self._p(dc_prev), self._stream()))
+        return dgates, dc_prev
 
     # ------------------------------------------------------------------ optimiser
     # ------------------------------------------------------------------ masked [B, T, D] loss / metric terms, batched

@@ -1358,13 +1358,77 @@ class CRNNScanFn(torch.autograd.Function):
 
 def clstm_scan(xs, weight, bias, pack, h0=None, c0=None):
     """CLSTMCell over a clip in one launch, forward only (kernels.clstm_scan_fwd; common.py:355-385): the reference stores
-    the (h, c) tuple and never feeds it to the decoder (refine_net.py:168-174), so nothing is differentiated.
+    the (h, c) tuple and never feeds it to the decoder (refine_net.py:168-174), so nothing is differentiated.  Also what the live
+    cell (CLSTMScanFn) runs under torch.no_grad(): the training forward gives the same hs / cs bit for bit.
     xs [B, T, 5, 8, C] any dtype -> (hs, cs) float32 [B, T, 5, 8, C]."""
     k = default_kernels()
     with torch.no_grad():
         w_ohwi, _ = _float_banks(weight, pack)
         f = lambda t: None if t is None else t.detach().float().contiguous()
         return k.clstm_scan_fwd(xs.detach().float().contiguous(), f(h0), f(c0), w_ohwi, bias.detach().float().contiguous())
+
+
+class CLSTMScanFn(torch.autograd.Function):
+    """(hs, cs)[:, t] = CLSTMCell(xs[:, t], (hs, cs)[:, t-1]) for the whole clip in ONE launch, differentiable: what
+    refine_net_clstm_feeds_features = True runs (the reference never feeds a tuple state on, so it has nothing to differentiate
+    -- that path stays on clstm_scan).  kernels.clstm_scan_fwd_train gives the hs / cs of clstm_scan_fwd bit for bit and keeps
+    the gates; kernels.clstm_scan_bwd walks the frames in reverse in one more launch; like CRNNScanFn the weight and bias
+    gradients are one batched launch each over all T*B frames.  xs float32 [B, T, 5, 8, C], C in kernels.SCAN_WIDTHS."""
+
+    @staticmethod
+    def forward(ctx, xs, w, b, h0, c0, pack):
+        k = default_kernels()
+        f = lambda t: None if t is None else t.detach().float().contiguous()
+        h0c, c0c = f(h0), f(c0)
+        w_ohwi, w_ihwo = _float_banks(w, pack)
+        xs = xs.contiguous()
+        hs, cs, gates_tm, cs_tm, hs_tm = k.clstm_scan_fwd_train(xs, h0c, c0c, w_ohwi, b.detach().float().contiguous())
+        ctx.pack = pack
+        ctx.params = (w, b)
+        ctx.has_0 = (h0 is not None, c0 is not None)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xs, h0c, c0c, gates_tm, cs_tm, hs_tm, w_ihwo)
+        return hs, cs
+
+    @staticmethod
+    def backward(ctx, dhs, dcs):
+        k = default_kernels()
+        xs, h0, c0, gates_tm, cs_tm, hs_tm, w_ihwo = ctx.saved_tensors
+        w, b = ctx.params
+        B, T, H, W, C = xs.shape
+        need = ctx.needs_input_grad
+        tm = lambda d: None if d is None else d.float().transpose(0, 1).contiguous()
+        dhs_tm = tm(dhs) if dhs is not None else torch.zeros_like(hs_tm)
+        want_d0 = bool((ctx.has_0[0] and need[3]) or (ctx.has_0[1] and need[4]))
+        dpre, dxs_tm, dh0, dc0 = k.clstm_scan_bwd(dhs_tm, tm(dcs), gates_tm, cs_tm, c0, w_ihwo, want_d0)
+        dxs = dxs_tm.transpose(0, 1).contiguous() if need[0] else None
+        first = h0 if h0 is not None else torch.zeros_like(hs_tm[0])
+        h_prev_all = torch.cat([first.unsqueeze(0), hs_tm[:-1]], dim=0)
+        cat1 = torch.cat([xs.transpose(0, 1), h_prev_all], dim=-1).reshape(T * B, H, W, 2 * C)
+        gpre = dpre.view(T * B, H, W, 4 * C)
+        dw = _wgrad_into(k, cat1, gpre, w, ctx.pack, 1, 1) if need[1] else None
+        db = _bias_grad_into(k, gpre, b) if need[2] else None
+        return (dxs, dw, db, dh0 if ctx.has_0[0] and need[3] else None, dc0 if ctx.has_0[1] and need[4] else None, None)
+
+
+class CLSTMGatesFn(torch.autograd.Function):
+    """(h', c') = CLSTMCell's gate math on the gate convolution's output [.., 4C] and c [.., C] (common.py:376-385), one frame:
+    the per-frame counterpart of CLSTMScanFn (kernels.clstm_gates_{fwd,bwd}, any format)."""
+
+    @staticmethod
+    def forward(ctx, gates, c_prev):
+        gates, c_prev = gates.contiguous(), c_prev.contiguous()
+        h, c = default_kernels().clstm_gates_fwd(gates, c_prev)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(gates, c_prev)
+        return h, c
+
+    @staticmethod
+    def backward(ctx, dh, dc):
+        gates, c_prev = ctx.saved_tensors
+        dh = torch.zeros_like(c_prev) if dh is None else dh.contiguous()
+        dgates, dc_prev = default_kernels().clstm_gates_bwd(dh, None if dc is None else dc.contiguous(), gates, c_prev)
+        return dgates, dc_prev
 
 
 class CGRUScanFn(torch.autograd.Function):

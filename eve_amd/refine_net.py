@@ -10,7 +10,8 @@ Mirrors /root/reference/src/models/refine_net.py:
     `output_dict['heatmap_initial']` (+ `input_dict['screen_frame']`), writes `heatmap_final` and
     `refinenet_rnn_states_0` (NCHW float at the boundary, like the reference);
   * Bottleneck quirks kept (:132-176): unknown rnn type => no cell; a tuple state (CLSTM) is stored but
-    its output is NOT used downstream, so its weights get no gradient.
+    its output is NOT used downstream, so its weights get no gradient.  `refine_net_clstm_feeds_features = True`
+    (an eve_amd config key, default False) departs from the reference on purpose: the cell's h becomes the features.
 
 `forward_sequence` folds all T frames into the image batch for the encoder and decoder (InstanceNorm
 is per-sample) and runs only the Cx5x8 conv-RNN cells sequentially (one clip-long scan per cell where `_use_scan` allows).
@@ -236,6 +237,11 @@ class RefineNet(nn.Module):
         return ops.HeatmapHeadFn.apply(logits)                                 # [N, 1, H, W] float
 
     # ------------------------------------------------------------------ conv-RNN bottleneck, one step
+    def _clstm_live(self):
+        """config.refine_net_clstm_feeds_features (eve_amd only; absent from the reference's config singleton => False): a
+        tuple state's h becomes the bottleneck features instead of being stored and dropped (refine_net.py:168-174)."""
+        return bool(getattr(self.config, 'refine_net_clstm_feeds_features', False))
+
     def _cell_step(self, x, state, cell, prefix, P):
         """x: [B,5,8,C] NHWC.  state: previous state (tensor, or (h, c) for CLSTM) or None.
         Returns (features for the decoder, new state)."""
@@ -251,6 +257,11 @@ class RefineNet(nn.Module):
             h = torch.zeros_like(x) if state is None else state
             hnew = self._conv(torch.cat([x, h], dim=-1), prefix + '.cell', cell.cell, P, act=ACT_TANH)
             return hnew, hnew
+        if self._clstm_live():         # opt-in departure from the reference: h is the cell's output, gradients flow through it
+            h, c = (torch.zeros_like(x), torch.zeros_like(x)) if state is None else state
+            gates = self._conv(torch.cat([x, h], dim=-1), prefix + '.gates', cell.gates, P)
+            hn, cn = ops.CLSTMGatesFn.apply(gates, c)
+            return hn, (hn, cn)
         # CLSTM: state computed and stored, output dead (refine_net.py:168-174); forward-only kernels
         with torch.no_grad():
             if state is None:
@@ -426,6 +437,14 @@ class RefineNet(nn.Module):
                     st = ops.CRNNScanFn.apply(hs.float(), cell.cell.weight, cell.cell.bias, init, P[name + '.cell'])
                     raw.append(st)
                     hs = st.to(xs.dtype)
+                elif self._clstm_live():     # CLSTM whose h is the features (opt-in): differentiable scan, h feeds on like CRNN's
+                    h_init, c_init = init if init is not None else (None, None)
+                    if torch.is_grad_enabled():
+                        hcs = ops.CLSTMScanFn.apply(hs.float(), cell.gates.weight, cell.gates.bias, h_init, c_init, P[name + '.gates'])
+                    else:               # inference (EVEStream, eval): the same hs / cs bit for bit, nothing kept for a backward
+                        hcs = ops.clstm_scan(hs, cell.gates.weight, cell.gates.bias, P[name + '.gates'], h_init, c_init)
+                    raw.append(tuple(hcs))
+                    hs = hcs[0].to(xs.dtype)
                 else:                   # CLSTM: the state is computed and stored, the features pass through (refine_net.py:168-174),
                     h_init, c_init = init if init is not None else (None, None)      # so every CLSTM cell of a stack sees xs
                     hcs = ops.clstm_scan(hs, cell.gates.weight, cell.gates.bias, P[name + '.gates'], h_init, c_init)

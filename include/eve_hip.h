@@ -498,6 +498,21 @@ int eve_crnn_scan_bwd_c(int B, int T, int C, const float* dhs_tm, const float* h
                         float* dxs_tm, float* dh0, eve_stream_t stream);
 int eve_clstm_scan_fwd_c(int B, int T, int C, const float* xs, const float* h0, const float* c0, const float* w, const float* bias,
                          float* hs, float* cs, eve_stream_t stream);
+/* The CLSTM clip scan for a cell whose output IS used (eve_amd's opt-in config key refine_net_clstm_feeds_features; the
+ * reference drops it, see eve_clstm_scan_fwd).  Float32, C in {32, 64, 128}, one workgroup per sequence (cell_scan_f32.hip,
+ * kernels "clstm_scan_f32_fwd_train_kernel" / "clstm_scan_f32_bwd_kernel", "<32>" / "<128>" appended off 64).
+ * fwd_train: operands and hs / cs of eve_clstm_scan_fwd_c, bit for bit, plus what the backward reads, time-major:
+ *   gates_tm [T][B][5][8][4C] = sigmoid(in), sigmoid(forget), sigmoid(out), tanh(cell); cs_tm, hs_tm [T][B][5][8][C].
+ * bwd: dhs_tm [T][B][5][8][C]; dcs_tm = gradient arriving at the stored cell states, or NULL; gates_tm / cs_tm of the forward;
+ *   c0 as in the forward or NULL; wt = the bank IHWO [2C][3][3][4C].  Outputs (time-major) dpre_all [T][B][5][8][4C] = gradient
+ *   of the gate pre-activations (operand of the batched weight / bias gradient), dxs_tm [T][B][5][8][C]; dh0 / dc0 [B][5][8][C]
+ *   or NULL.  Weight and bias gradients are not formed here.                                                                */
+int eve_clstm_scan_fwd_train_c(int B, int T, int C, const float* xs, const float* h0, const float* c0, const float* w,
+                               const float* bias, float* hs, float* cs, float* gates_tm, float* cs_tm, float* hs_tm,
+                               eve_stream_t stream);
+int eve_clstm_scan_bwd_c(int B, int T, int C, const float* dhs_tm, const float* dcs_tm, const float* gates_tm, const float* cs_tm,
+                         const float* c0, const float* wt, float* dpre_all, float* dxs_tm, float* dh0, float* dc0,
+                         eve_stream_t stream);
 int eve_cgru_gates1(int dtype, long long P, int C, const void* g1, const void* h, void* ru, void* rh,
                     eve_stream_t stream);
 int eve_cgru_gates2(int dtype, long long P, int C, const void* g2, const void* ru, const void* h,
@@ -517,6 +532,11 @@ int eve_cgru_gates1_bwd(int dtype, long long P, int C, const void* drh, const vo
  * The reference never back-propagates through it (refine_net.py:168-174 drops tuple states).         */
 int eve_clstm_gates_fwd(int dtype, long long P, int C, const void* gates, const void* c_prev, void* h,
                         void* c, eve_stream_t stream);
+/* Adjoint of eve_clstm_gates_fwd (for a cell whose output is used: refine_net_clstm_feeds_features): dh, dc_in [P][C] =
+ * gradients arriving at h' and c' (dc_in or NULL), gates [P][4C] = the forward's pre-activations, c_prev [P][C]
+ * -> dgates [P][4C] (gradient of the pre-activations) and dc_prev [P][C] = dc' * sig(f).                    */
+int eve_clstm_gates_bwd(int dtype, long long P, int C, const void* dh, const void* dc_in, const void* gates,
+                        const void* c_prev, void* dgates, void* dc_prev, eve_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * RefineNet output head and the heat-map losses (csrc/heatmap_loss.hip).
