@@ -1280,22 +1280,6 @@ class LSTMScanFn(torch.autograd.Function):
         return dpre, dw, db, dh0, dc0
 
 
-class CGRUGates1Fn(torch.autograd.Function):
-    """(ru, rh) = (sigmoid(g1), sigmoid(g1[..., :C]) * h)   -- common.py:410-411"""
-
-    @staticmethod
-    def forward(ctx, g1, h):
-        ru, rh = default_kernels().cgru_gates1(g1, h)
-        ctx.save_for_backward(ru, h)
-        return ru, rh
-
-    @staticmethod
-    def backward(ctx, dru, drh):
-        ru, h = ctx.saved_tensors
-        dg1, dh = default_kernels().cgru_gates1_bwd(drh.contiguous(), dru.contiguous(), ru, h)
-        return dg1, dh
-
-
 def _bias_grad_into(k, dy, bias):
     """Bias gradient of a convolution whose output gradient is `dy` [..., C]: straight into the flat gradient buffer when the
     parameter lives there (returns None), else a fresh float32 vector."""
@@ -1306,214 +1290,6 @@ def _bias_grad_into(k, dy, bias):
     db = torch.zeros((dy.shape[-1],), dtype=torch.float32, device=dy.device)
     k.bias_grad(dy, db)
     return db
-
-
-def _float_banks(weight, pack):
-    """(OHWI, IHWO) float32 copies of a convolution's filter bank for the float32 clip scans (csrc/cell_scan_f32.hip): the
-    pack's own tensors in the float32 instantiation, otherwise formed from the parameter (295-590 KB)."""
-    if pack is not None and pack.ohwi.dtype == torch.float32 and pack.ihwo is not None:
-        return pack.ohwi, pack.ihwo
-    w = weight.detach().float()
-    return w.permute(0, 2, 3, 1).contiguous(), w.permute(1, 2, 3, 0).contiguous()
-
-
-class CRNNScanFn(torch.autograd.Function):
-    """hs[:, t] = CRNNCell(xs[:, t], hs[:, t-1]) = tanh(conv3x3([x_t | h_{t-1}]) + b) for the whole clip in ONE launch, and the
-    frame-reversed backward in one more (kernels.crnn_scan_{fwd,bwd}, float32: csrc/cell_scan_f32.hip; common.py:331-352 applied
-    per frame by refine_net.py:132-176).  The weight and bias gradients are one batched launch each over all T*B frames.
-    xs float32 [B, T, 5, 8, C], C in kernels.SCAN_WIDTHS (16-bit callers convert: the bottleneck is 40 C values per frame)."""
-
-    @staticmethod
-    def forward(ctx, xs, w, b, h0, pack):
-        k = default_kernels()
-        h0c = h0.detach().contiguous() if h0 is not None else None
-        w_ohwi, w_ihwo = _float_banks(w, pack)
-        xs = xs.contiguous()
-        hs, hs_tm = k.crnn_scan_fwd(xs, h0c, w_ohwi, b.detach().float().contiguous())
-        ctx.pack = pack
-        ctx.params = (w, b)
-        ctx.has_h0 = h0 is not None
-        ctx.save_for_backward(xs, h0c, hs_tm, w_ihwo)
-        return hs
-
-    @staticmethod
-    def backward(ctx, dhs):
-        k = default_kernels()
-        xs, h0, hs_tm, w_ihwo = ctx.saved_tensors
-        w, b = ctx.params
-        B, T, H, W, C = xs.shape
-        need = ctx.needs_input_grad
-        dhs_tm = dhs.float().transpose(0, 1).contiguous()
-        want_dh0 = bool(ctx.has_h0 and need[3])
-        dpre, dxs_tm, dh0 = k.crnn_scan_bwd(dhs_tm, hs_tm, w_ihwo, want_dh0)
-        dxs = dxs_tm.transpose(0, 1).contiguous() if need[0] else None
-        first = h0 if h0 is not None else torch.zeros_like(hs_tm[0])
-        h_prev_all = torch.cat([first.unsqueeze(0), hs_tm[:-1]], dim=0)
-        cat1 = torch.cat([xs.transpose(0, 1), h_prev_all], dim=-1).reshape(T * B, H, W, 2 * C)
-        gpre = dpre.view(T * B, H, W, C)
-        dw = _wgrad_into(k, cat1, gpre, w, ctx.pack, 1, 1) if need[1] else None
-        db = _bias_grad_into(k, gpre, b) if need[2] else None
-        return dxs, dw, db, dh0, None
-
-
-def clstm_scan(xs, weight, bias, pack, h0=None, c0=None):
-    """CLSTMCell over a clip in one launch, forward only (kernels.clstm_scan_fwd; common.py:355-385): the reference stores
-    the (h, c) tuple and never feeds it to the decoder (refine_net.py:168-174), so nothing is differentiated.  Also what the live
-    cell (CLSTMScanFn) runs under torch.no_grad(): the training forward gives the same hs / cs bit for bit.
-    xs [B, T, 5, 8, C] any dtype -> (hs, cs) float32 [B, T, 5, 8, C]."""
-    k = default_kernels()
-    with torch.no_grad():
-        w_ohwi, _ = _float_banks(weight, pack)
-        f = lambda t: None if t is None else t.detach().float().contiguous()
-        return k.clstm_scan_fwd(xs.detach().float().contiguous(), f(h0), f(c0), w_ohwi, bias.detach().float().contiguous())
-
-
-class CLSTMScanFn(torch.autograd.Function):
-    """(hs, cs)[:, t] = CLSTMCell(xs[:, t], (hs, cs)[:, t-1]) for the whole clip in ONE launch, differentiable: what
-    refine_net_clstm_feeds_features = True runs (the reference never feeds a tuple state on, so it has nothing to differentiate
-    -- that path stays on clstm_scan).  kernels.clstm_scan_fwd_train gives the hs / cs of clstm_scan_fwd bit for bit and keeps
-    the gates; kernels.clstm_scan_bwd walks the frames in reverse in one more launch; like CRNNScanFn the weight and bias
-    gradients are one batched launch each over all T*B frames.  xs float32 [B, T, 5, 8, C], C in kernels.SCAN_WIDTHS."""
-
-    @staticmethod
-    def forward(ctx, xs, w, b, h0, c0, pack):
-        k = default_kernels()
-        f = lambda t: None if t is None else t.detach().float().contiguous()
-        h0c, c0c = f(h0), f(c0)
-        w_ohwi, w_ihwo = _float_banks(w, pack)
-        xs = xs.contiguous()
-        hs, cs, gates_tm, cs_tm, hs_tm = k.clstm_scan_fwd_train(xs, h0c, c0c, w_ohwi, b.detach().float().contiguous())
-        ctx.pack = pack
-        ctx.params = (w, b)
-        ctx.has_0 = (h0 is not None, c0 is not None)
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(xs, h0c, c0c, gates_tm, cs_tm, hs_tm, w_ihwo)
-        return hs, cs
-
-    @staticmethod
-    def backward(ctx, dhs, dcs):
-        k = default_kernels()
-        xs, h0, c0, gates_tm, cs_tm, hs_tm, w_ihwo = ctx.saved_tensors
-        w, b = ctx.params
-        B, T, H, W, C = xs.shape
-        need = ctx.needs_input_grad
-        tm = lambda d: None if d is None else d.float().transpose(0, 1).contiguous()
-        dhs_tm = tm(dhs) if dhs is not None else torch.zeros_like(hs_tm)
-        want_d0 = bool((ctx.has_0[0] and need[3]) or (ctx.has_0[1] and need[4]))
-        dpre, dxs_tm, dh0, dc0 = k.clstm_scan_bwd(dhs_tm, tm(dcs), gates_tm, cs_tm, c0, w_ihwo, want_d0)
-        dxs = dxs_tm.transpose(0, 1).contiguous() if need[0] else None
-        first = h0 if h0 is not None else torch.zeros_like(hs_tm[0])
-        h_prev_all = torch.cat([first.unsqueeze(0), hs_tm[:-1]], dim=0)
-        cat1 = torch.cat([xs.transpose(0, 1), h_prev_all], dim=-1).reshape(T * B, H, W, 2 * C)
-        gpre = dpre.view(T * B, H, W, 4 * C)
-        dw = _wgrad_into(k, cat1, gpre, w, ctx.pack, 1, 1) if need[1] else None
-        db = _bias_grad_into(k, gpre, b) if need[2] else None
-        return (dxs, dw, db, dh0 if ctx.has_0[0] and need[3] else None, dc0 if ctx.has_0[1] and need[4] else None, None)
-
-
-class CLSTMGatesFn(torch.autograd.Function):
-    """(h', c') = CLSTMCell's gate math on the gate convolution's output [.., 4C] and c [.., C] (common.py:376-385), one frame:
-    the per-frame counterpart of CLSTMScanFn (kernels.clstm_gates_{fwd,bwd}, any format)."""
-
-    @staticmethod
-    def forward(ctx, gates, c_prev):
-        gates, c_prev = gates.contiguous(), c_prev.contiguous()
-        h, c = default_kernels().clstm_gates_fwd(gates, c_prev)
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(gates, c_prev)
-        return h, c
-
-    @staticmethod
-    def backward(ctx, dh, dc):
-        gates, c_prev = ctx.saved_tensors
-        dh = torch.zeros_like(c_prev) if dh is None else dh.contiguous()
-        dgates, dc_prev = default_kernels().clstm_gates_bwd(dh, None if dc is None else dc.contiguous(), gates, c_prev)
-        return dgates, dc_prev
-
-
-class CGRUScanFn(torch.autograd.Function):
-    """hs[:, t] = CGRUCell(xs[:, t], hs[:, t-1]) for the whole clip in ONE launch (kernels.cgru_scan_fwd: hidden state
-    resident in LDS, both gate convolutions and their sigmoid / tanh / blend epilogues fused; common.py:388-415 applied
-    per frame by refine_net.py:132-176).  The backward is one persistent launch as well (kernels.cgru_scan_bwd: frames in
-    reverse, gate gradients + both data-gradient GEMMs + the carry into the previous state fused; eve_dispatch_config.cgru_scan = 2
-    selects the per-frame kernels on time-major tensors); the two weight gradients and bias gradients are ONE batched
-    launch each over all T*B frames."""
-
-    @staticmethod
-    def forward(ctx, xs, w1, b1, w2, b2, h0, p1, p2):
-        k = default_kernels()
-        h0c = h0.detach().contiguous() if h0 is not None else None
-        hs, hs_tm, ru, rh, og = k.cgru_scan_fwd(xs.contiguous(), h0c, p1.ohwi, b1.detach().float().contiguous(), p2.ohwi,
-                                                b2.detach().float().contiguous())
-        ctx.packs = (p1, p2)
-        ctx.params = (w1, b1, w2, b2)
-        ctx.has_h0 = h0 is not None
-        ctx.save_for_backward(xs, h0c, hs_tm, ru, rh, og)
-        return hs
-
-    @staticmethod
-    def backward(ctx, dhs):
-        k = default_kernels()
-        xs, h0, hs_tm, ru, rh, og = ctx.saved_tensors
-        p1, p2 = ctx.packs
-        w1, b1, w2, b2 = ctx.params
-        B, T, H, W, C = xs.shape
-        need = ctx.needs_input_grad
-        dhs_tm = dhs.transpose(0, 1).contiguous()                       # [T, B, ...]
-        xs_tm = xs.transpose(0, 1).contiguous()
-        first = h0 if h0 is not None else torch.zeros_like(xs_tm[0])
-        want_dh0 = bool(ctx.has_h0 and need[5])
-        if hasattr(k, 'cgru_scan_bwd') and dispatch_flag(k, 'cgru_scan', 1) != 2:
-            # the whole frame-reversed recursion in one persistent launch (kernels.cgru_scan_bwd): gate gradients, both
-            # data-gradient GEMMs, the carry into the previous state; gradients of the two pre-activations come back for
-            # the batched weight / bias gradients below
-            dg1_all, dg2_all, dxs_tm, dh0 = k.cgru_scan_bwd(dhs_tm, ru, og, hs_tm, h0, p1.ihwo, p2.ihwo, want_dh0)
-            dxs = dxs_tm.transpose(0, 1).contiguous()
-        else:
-            dcat1_all = torch.empty((T, B, H, W, 2 * C), dtype=xs.dtype, device=xs.device)      # d[x | h] per frame
-            dcat2_all = torch.empty((T, B, H, W, 2 * C), dtype=xs.dtype, device=xs.device)      # d[r*h | x] per frame
-            dg1_all = torch.empty((T, B, H, W, 2 * C), dtype=xs.dtype, device=xs.device)
-            dg2_all = torch.empty((T, B, H, W, C), dtype=xs.dtype, device=xs.device)
-            carry = None
-            for t in range(T - 1, -1, -1):
-                dhn = dhs_tm[t] if carry is None else k.add(dhs_tm[t], carry)
-                h_prev = hs_tm[t - 1] if t > 0 else first
-                dg2, dru, dh_a = k.cgru_gates2_bwd(dhn, ru[t], h_prev, og[t])
-                dcat2 = k.conv2d_dgrad(dg2, p2.ihwo, (H, W), 1, 1, algo=p2.algo)
-                dg1, dh_b = k.cgru_gates1_bwd(dcat2[..., :C].contiguous(), dru, ru[t], h_prev)
-                dcat1 = k.conv2d_dgrad(dg1, p1.ihwo, (H, W), 1, 1, algo=p1.algo)
-                carry = k.add(k.add(dh_a, dh_b), dcat1[..., C:].contiguous())
-                dcat1_all[t], dcat2_all[t], dg1_all[t], dg2_all[t] = dcat1, dcat2, dg1, dg2
-            # d(xs) = x-halves of the two concatenated-input gradients, for all frames at once
-            dxs = (dcat1_all[..., :C] + dcat2_all[..., C:]).transpose(0, 1).contiguous()
-            dh0 = carry if want_dh0 else None
-        # weight / bias gradients: one launch each over all T*B frames
-        h_prev_all = torch.cat([first.unsqueeze(0), hs_tm[:-1]], dim=0)
-        cat1 = torch.cat([xs_tm, h_prev_all], dim=-1).view(T * B, H, W, 2 * C)
-        cat2 = torch.cat([rh, xs_tm], dim=-1).view(T * B, H, W, 2 * C)
-        g1f, g2f = dg1_all.view(T * B, H, W, 2 * C), dg2_all.view(T * B, H, W, C)
-
-        dw1 = _wgrad_into(k, cat1, g1f, w1, p1, 1, 1) if need[1] else None
-        db1 = _bias_grad_into(k, g1f, b1) if need[2] else None
-        dw2 = _wgrad_into(k, cat2, g2f, w2, p2, 1, 1) if need[3] else None
-        db2 = _bias_grad_into(k, g2f, b2) if need[4] else None
-        return dxs, dw1, db1, dw2, db2, dh0, None, None
-
-
-class CGRUGates2Fn(torch.autograd.Function):
-    """h' = (1 - u) * tanh(g2) + u * h   -- common.py:413-414.  `ru` only contributes through u."""
-
-    @staticmethod
-    def forward(ctx, g2, ru, h):
-        o, hnew = default_kernels().cgru_gates2(g2, ru, h)
-        ctx.save_for_backward(ru, h, o)
-        return hnew
-
-    @staticmethod
-    def backward(ctx, dhnew):
-        ru, h, o = ctx.saved_tensors
-        dg2, dru, dh = default_kernels().cgru_gates2_bwd(dhnew.contiguous(), ru, h, o)
-        return dg2, dru, dh
 
 
 class VectorTermsFn(torch.autograd.Function):

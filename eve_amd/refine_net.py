@@ -15,6 +15,7 @@ Mirrors /root/reference/src/models/refine_net.py:
 
 `forward_sequence` folds all T frames into the image batch for the encoder and decoder (InstanceNorm
 is per-sample) and runs only the Cx5x8 conv-RNN cells sequentially (one clip-long scan per cell where `_use_scan` allows).
+The cells themselves -- holders, one-frame step, clip scan, state dtype per kind -- live in conv_rnn.py; this module walks them.
 
 nn.Conv2d / nn.InstanceNorm2d objects are PARAMETER HOLDERS; their ATen forward is never called.
 """
@@ -22,34 +23,12 @@ nn.Conv2d / nn.InstanceNorm2d objects are PARAMETER HOLDERS; their ATen forward 
 import torch
 from torch import nn
 
-from . import ops
+from . import conv_rnn, ops
 from .config import get_config
+from .conv_rnn import CGRUCell, CLSTMCell, CRNNCell
 from .eye_net import default_compute_dtype
-from .kernels import (ACT_LEAKY, ACT_NONE, ACT_RELU, ACT_TANH, HALF_DTYPES, SCAN_WIDTHS, default_kernels, dispatch_flag,
-                      pad_channels)
+from .kernels import ACT_LEAKY, ACT_NONE, ACT_RELU, default_kernels, pad_channels
 from .ops import PackedWeight
-
-
-class CRNNCell(nn.Module):       # holder, common.py:331-339
-    def __init__(self, input_size, hidden_size):
-        super().__init__()
-        self.input_size, self.hidden_size = input_size, hidden_size
-        self.cell = nn.Conv2d(input_size + hidden_size, hidden_size, kernel_size=3, padding=1)
-
-
-class CLSTMCell(nn.Module):      # holder, common.py:355-363
-    def __init__(self, input_size, hidden_size):
-        super().__init__()
-        self.input_size, self.hidden_size = input_size, hidden_size
-        self.gates = nn.Conv2d(input_size + hidden_size, 4 * hidden_size, kernel_size=3, padding=1)
-
-
-class CGRUCell(nn.Module):       # holder, common.py:388-398
-    def __init__(self, input_size, hidden_size):
-        super().__init__()
-        self.input_size, self.hidden_size = input_size, hidden_size
-        self.gates_1 = nn.Conv2d(input_size + hidden_size, 2 * hidden_size, kernel_size=3, padding=1)
-        self.gate_2 = nn.Conv2d(input_size + hidden_size, hidden_size, kernel_size=3, padding=1)
 
 
 class BasicBlock(nn.Module):     # holder, refine_net.py:35-62
@@ -245,45 +224,21 @@ class RefineNet(nn.Module):
     def _cell_step(self, x, state, cell, prefix, P):
         """x: [B,5,8,C] NHWC.  state: previous state (tensor, or (h, c) for CLSTM) or None.
         Returns (features for the decoder, new state)."""
-        k = default_kernels()
-        if isinstance(cell, CGRUCell):
-            h = torch.zeros_like(x) if state is None else state
-            g1 = self._conv(torch.cat([x, h], dim=-1), prefix + '.gates_1', cell.gates_1, P)
-            ru, rh = ops.CGRUGates1Fn.apply(g1, h)
-            g2 = self._conv(torch.cat([rh, x], dim=-1), prefix + '.gate_2', cell.gate_2, P)
-            hnew = ops.CGRUGates2Fn.apply(g2, ru, h)
-            return hnew, hnew
-        if isinstance(cell, CRNNCell):
-            h = torch.zeros_like(x) if state is None else state
-            hnew = self._conv(torch.cat([x, h], dim=-1), prefix + '.cell', cell.cell, P, act=ACT_TANH)
-            return hnew, hnew
-        if self._clstm_live():         # opt-in departure from the reference: h is the cell's output, gradients flow through it
-            h, c = (torch.zeros_like(x), torch.zeros_like(x)) if state is None else state
-            gates = self._conv(torch.cat([x, h], dim=-1), prefix + '.gates', cell.gates, P)
-            hn, cn = ops.CLSTMGatesFn.apply(gates, c)
-            return hn, (hn, cn)
-        # CLSTM: state computed and stored, output dead (refine_net.py:168-174); forward-only kernels
-        with torch.no_grad():
-            if state is None:
-                h, c = torch.zeros_like(x), torch.zeros_like(x)
-            else:
-                h, c = state
-            gates = k.conv2d_fwd(torch.cat([x.detach(), h], dim=-1).contiguous(), P[prefix + '.gates'].ohwi,
-                                 cell.gates.bias.detach().float().contiguous(), 1, 1)
-            hn, cn = k.clstm_gates_fwd(gates, c.contiguous())
-        return x, (hn, cn)
+        return cell.step(self._conv, x, state, prefix, P, self._clstm_live())
 
-    def _bottleneck(self, x, states, prefix, P):
-        """x: [B,5,8,C].  states: list (one per cell) of previous states or None.  -> (x, new states)"""
+    def _rnn_cells(self):
         bott = self.network
         while isinstance(bott, WrapEncoderDecoder):
             bott = bott.between_module
+        return list(bott.rnn_cells) if self.config.refine_net_use_rnn else []
+
+    def _bottleneck(self, x, states, prefix, P):
+        """x: [B,5,8,C].  states: list (one per cell) of previous states or None.  -> (x, new states)"""
         new_states = []
-        if self.config.refine_net_use_rnn:
-            for i, cell in enumerate(bott.rnn_cells):
-                prev = None if states is None else states[i]
-                x, st = self._cell_step(x, prev, cell, '%s.rnn_cells.%d' % (prefix, i), P)
-                new_states.append(st)
+        for i, cell in enumerate(self._rnn_cells()):
+            prev = None if states is None else states[i]
+            x, st = self._cell_step(x, prev, cell, '%s.rnn_cells.%d' % (prefix, i), P)
+            new_states.append(st)
         return x, new_states
 
     # ------------------------------------------------------------------ boundary helpers
@@ -314,12 +269,9 @@ class RefineNet(nn.Module):
         x = self._input_nhwc(output_dict['heatmap_initial'], screen)
         x, skips, prefix = self._encode(x, P)
         states = None
-        if previous_output_dict is not None and self.config.refine_net_use_rnn:
-            bott = self.network
-            while isinstance(bott, WrapEncoderDecoder):
-                bott = bott.between_module
+        if previous_output_dict is not None:
             states = [self._state_in(previous_output_dict['refinenet_rnn_states_%d' % i])
-                      for i in range(len(bott.rnn_cells))]
+                      for i in range(len(self._rnn_cells()))]
         x, new_states = self._bottleneck(x, states, prefix, P)
         for i, st in enumerate(new_states):
             output_dict['refinenet_rnn_states_%d' % i] = self._state_out(st)
@@ -327,40 +279,13 @@ class RefineNet(nn.Module):
         output_dict['heatmap_final'] = y
 
     # ------------------------------------------------------------------ whole clips in one pass
-    def _rnn_cells(self):
-        bott = self.network
-        while isinstance(bott, WrapEncoderDecoder):
-            bott = bott.between_module
-        return list(bott.rnn_cells) if self.config.refine_net_use_rnn else []
-
-    @staticmethod
-    def _use_scan(cells, hwc, dtype):
-        # the 5 x 8 x C bottleneck with C in SCAN_WIDTHS (32, 64, 128) and any number of stacked cells: every cell takes the whole
-        # clip in ONE persistent launch (hidden state resident in LDS), cell i scanning cell i-1's states.  CGRU in the 16-bit
-        # formats at C = 64 on cgru_scan.hip / cgru_scan1.hip (16-bit MFMA) and at C = 32 / 128 on the 16-bit-storage
-        # instantiation of the float32 scan (same rounding points); CGRU in float32 and CRNN / CLSTM in any format on the
-        # float32 scans of cell_scan_f32.hip.  Every other width stays on the per-frame loop.
-        # Left per frame by default because their scan measured SLOWER than the per-frame 16-bit MFMA convolutions at B = 32 x
-        # T = 30 (profiles/refine_scan_widths.md): CGRU and CLSTM in bf16 / fp16 at C = 128, whose scans run 4x the C = 64
-        # arithmetic on the float32 MFMA.  eve_dispatch_config.cgru_scan = 3 scans them too (kernels and tests are kept).
-        cells, C = list(cells), tuple(hwc)[-1]
-        flag = dispatch_flag(default_kernels(), 'cgru_scan', 1)
-        if not (cells and tuple(hwc)[:2] == (5, 8) and C in SCAN_WIDTHS and dtype in HALF_DTYPES + (torch.float32,) and flag != 0):
-            return False
-        slower = C == 128 and dtype in HALF_DTYPES and isinstance(cells[0], (CGRUCell, CLSTMCell))
-        return flag == 3 or not slower
+    _use_scan = staticmethod(conv_rnn.use_scan)         # (cells, (h, w, C), dtype) -> clip scans or the per-frame loop
 
     def _carried_dtypes(self):
-        """Per cell, the dtype(s) the bottleneck carries its state in (internal NHWC layout [B, 5, 8, C]): the float32 scans keep
-        CRNN / CLSTM states in float32, everything else is in the compute dtype.  A tuple of two for CLSTM."""
+        """Per cell, the dtype(s) the bottleneck carries its state in (internal NHWC layout [B, 5, 8, C]); a pair for CLSTM."""
         cells, dt = self._rnn_cells(), self.compute_dtype
-        hwc = (5, 8, pad_channels(self.config.refine_net_num_features, dt))
-        scan = self._use_scan(cells, hwc, dt)
-        out = []
-        for cell in cells:
-            sdt = torch.float32 if scan and not isinstance(cell, CGRUCell) else dt
-            out.append((sdt, sdt) if isinstance(cell, CLSTMCell) else sdt)
-        return out
+        scan = self._use_scan(cells, (5, 8, pad_channels(self.config.refine_net_num_features, dt)), dt)
+        return [cell.state_dtypes(scan, dt) for cell in cells]
 
     def _initial_states_in(self, initial_states):
         """initial_states: None, or one entry per cell -- a state (a pair for CLSTM) in the reference layout [B, C, 5, 8] (what
@@ -392,23 +317,13 @@ class RefineNet(nn.Module):
         list over cells of the stacked states [B,T,C,5,8] (tuple of two for CLSTM)).
         initial_states: None (zero states), or per cell the state before the first frame -- reference layout [B, C, 5, 8] as
         returned here (the last frame of a previous call), or the internal NHWC layout [B, 5, 8, C]; (h, c) for CLSTM."""
-        hf, scan, raw, to_ref = self._sequence(heatmap_initial, screen_frame, self._initial_states_in(initial_states))
-        if scan:
-            return hf, [tuple(to_ref(t) for t in st) if isinstance(st, tuple) else to_ref(st) for st in raw]
-        hist = raw
-        stacked = []
-        for i in range(len(hist[0]) if hist else 0):
-            per_t = [self._state_out(h[i]) for h in hist]
-            if isinstance(per_t[0], tuple):
-                stacked.append(tuple(torch.stack([p[j] for p in per_t], dim=1) for j in range(2)))
-            else:
-                stacked.append(torch.stack(per_t, dim=1))
-        return hf, stacked
+        hf, states, to_ref = self._sequence(heatmap_initial, screen_frame, self._initial_states_in(initial_states))
+        return hf, [tuple(to_ref(t) for t in st) if isinstance(st, tuple) else to_ref(st) for st in states]
 
     def _sequence(self, heatmap_initial, screen_frame, h0):
         """The clip pass behind forward_sequence.  h0: None or per cell the internal-layout initial state (_initial_states_in).
-        Returns (heatmap_final [B,T,1,H,W], scan, raw, to_ref): with `scan` raw holds per cell its per-frame states [B,T,5,8,C]
-        (a pair for CLSTM), otherwise raw is the per-frame list of per-cell states; to_ref converts [B,T,5,8,C] to [B,T,C,5,8]."""
+        Returns (heatmap_final [B,T,1,H,W], per cell its per-frame states [B,T,5,8,C] (a pair for CLSTM), to_ref); to_ref
+        converts [B,T,5,8,C] to [B,T,C,5,8]."""
         P = self._get_packs()
         B, T = heatmap_initial.shape[:2]
         if screen_frame is not None and screen_frame.dtype == torch.uint8:     # decoded frames [B,T,H,W,3]: normalise here
@@ -417,51 +332,31 @@ class RefineNet(nn.Module):
         fold = lambda t: None if t is None else t.reshape((B * T,) + tuple(t.shape[2:]))
         x = self._input_nhwc(fold(heatmap_initial), fold(screen_frame) if self.config.load_screen_content else None)
         x, skips, prefix = self._encode(x, P)
-        C = x.shape[-1]
-        xs = x.view(B, T, x.shape[1], x.shape[2], C)
-        cells = self._rnn_cells()
-        h5, w5 = x.shape[1], x.shape[2]
+        h5, w5, C = x.shape[1:]
+        xs = x.view(B, T, h5, w5, C)
+        cells, live = self._rnn_cells(), self._clstm_live()
         to_ref = lambda t: ops.FromNHWCFn.apply(t.reshape(B * T, h5, w5, C), C).view(B, T, C, h5, w5)
         if self._use_scan(cells, xs.shape[2:], xs.dtype):
             # a stack is cell 0 scanned over the clip, then cell 1 over cell 0's states, ...: cell i at frame t reads cell i-1 at
             # frame t and its own state at t-1, which is all the per-frame loop of refine_net.py:154-176 does
-            raw, hs = [], xs
+            states, hs = [], xs
             for i, cell in enumerate(cells):
-                name = '%s.rnn_cells.%d' % (prefix, i)
-                init = h0[i] if h0 is not None else None
-                if isinstance(cell, CGRUCell):
-                    hs = ops.CGRUScanFn.apply(hs.contiguous(), cell.gates_1.weight, cell.gates_1.bias, cell.gate_2.weight,
-                                              cell.gate_2.bias, init, P[name + '.gates_1'], P[name + '.gate_2'])
-                    raw.append(hs)
-                elif isinstance(cell, CRNNCell):
-                    st = ops.CRNNScanFn.apply(hs.float(), cell.cell.weight, cell.cell.bias, init, P[name + '.cell'])
-                    raw.append(st)
-                    hs = st.to(xs.dtype)
-                elif self._clstm_live():     # CLSTM whose h is the features (opt-in): differentiable scan, h feeds on like CRNN's
-                    h_init, c_init = init if init is not None else (None, None)
-                    if torch.is_grad_enabled():
-                        hcs = ops.CLSTMScanFn.apply(hs.float(), cell.gates.weight, cell.gates.bias, h_init, c_init, P[name + '.gates'])
-                    else:               # inference (EVEStream, eval): the same hs / cs bit for bit, nothing kept for a backward
-                        hcs = ops.clstm_scan(hs, cell.gates.weight, cell.gates.bias, P[name + '.gates'], h_init, c_init)
-                    raw.append(tuple(hcs))
-                    hs = hcs[0].to(xs.dtype)
-                else:                   # CLSTM: the state is computed and stored, the features pass through (refine_net.py:168-174),
-                    h_init, c_init = init if init is not None else (None, None)      # so every CLSTM cell of a stack sees xs
-                    hcs = ops.clstm_scan(hs, cell.gates.weight, cell.gates.bias, P[name + '.gates'], h_init, c_init)
-                    raw.append(tuple(hcs))
-            x = self._tap('rnn', hs.reshape(B * T, h5, w5, C))
-            hf = self._decode(x, skips, P)
-            return hf.view(B, T, 1, hf.shape[2], hf.shape[3]), True, raw, to_ref
-        outs, states, hist = [], h0, []
-        for t in range(T):
-            xt, states = self._bottleneck(xs[:, t].contiguous(), states, prefix, P)
-            outs.append(xt)
-            hist.append(states)
-        x = torch.stack(outs, dim=1).view(B * T, x.shape[1], x.shape[2], C)
+                st, hs = cell.scan(hs, None if h0 is None else h0[i], '%s.rnn_cells.%d' % (prefix, i), P, live)
+                states.append(st)
+        else:
+            outs, prev, hist = [], h0, []
+            for t in range(T):
+                xt, prev = self._bottleneck(xs[:, t].contiguous(), prev, prefix, P)
+                outs.append(xt)
+                hist.append(prev)
+            hs = torch.stack(outs, dim=1)
+            stack = lambda ts: torch.stack(ts, dim=1)           # a cell's per-frame states as a scan returns them: [B,T,5,8,C]
+            states = [tuple(map(stack, zip(*per_t))) if isinstance(per_t[0], tuple) else stack(per_t) for per_t in zip(*hist)]
+        x = hs.reshape(B * T, h5, w5, C)
         if cells:
-            x = self._tap('rnn', x)                 # the same stage boundary as on the scan branch
+            x = self._tap('rnn', x)
         hf = self._decode(x, skips, P)
-        return hf.view(B, T, 1, hf.shape[2], hf.shape[3]), False, hist, to_ref
+        return hf.view(B, T, 1, hf.shape[2], hf.shape[3]), states, to_ref
 
     # ------------------------------------------------------------------ streaming (eve_amd/stream.py)
     def _stream_state_buffers(self, B, device):
@@ -475,14 +370,11 @@ class RefineNet(nn.Module):
         as the initial states, and overwritten with the chunk's last frame -- one eve_stream_state_rows launch each way, no
         conversion.  -> heatmap_final [B,T,1,H,W]."""
         k = default_kernels()
-        flat = [t for b in buffers for t in (b if isinstance(b, tuple) else (b,))]
+        flat = lambda sts: [t for s in sts for t in (s if isinstance(s, tuple) else (s,))]
         if reset is not None:
-            for t in flat:
+            for t in flat(buffers):
                 k.stream_state_rows(t, t, reset)
-        hf, scan, raw, _ = self._sequence(heatmap_initial, screen_frame, buffers if buffers else None)
-        lasts = raw if scan else (raw[-1] if raw else [])
-        for buf, st in zip(buffers, lasts):
-            pairs = zip(buf, st) if isinstance(buf, tuple) else ((buf, st),)
-            for dst, src in pairs:
-                k.stream_state_rows(src[:, -1] if scan else src, dst)
+        hf, states, _ = self._sequence(heatmap_initial, screen_frame, buffers if buffers else None)
+        for dst, src in zip(flat(buffers), flat(states)):
+            k.stream_state_rows(src[:, -1], dst)
         return hf

@@ -10,7 +10,7 @@ import torch
 
 import eve_amd
 import refine_variants as rv
-from eve_amd import losses, ops
+from eve_amd import conv_rnn, losses, ops
 from eve_amd.kernels import default_kernels
 from oracle import detweights, sequence
 from oracle.config import OracleConfig
@@ -62,7 +62,7 @@ def test_clstm_training_scan_matches_autograd_of_the_unrolled_cell(C, T, with_in
     the forward writes, 3e-5 on what the backward writes (T <= 8), relative to max(1, |reference|max).  The restatement is also
     evaluated in float64 and a tensor is held to max(that bound, 4 x the float32 restatement's own deviation from float64); both
     numbers are printed per tensor.  The backward runs on the float32 restatement's forward tensors, so it is compared on equal
-    inputs; the weight and bias gradients come from ops.CLSTMScanFn (one batched launch each over the T*B frames).  With initial
+    inputs; the weight and bias gradients come from conv_rnn.CLSTMScanFn (one batched launch each over the T*B frames).  With initial
     states the case also feeds a gradient into the stored cell states (dcs), without them that operand is NULL.
     Measured on an MI355X, worst of the 12 cases relative to max(1, |reference|max), kernel error | the float32 restatement's own
     deviation from float64: forward tensors 1.3e-6 | 3.2e-6; dpre 6.1e-7 | 1.2e-6; dxs 3.4e-6 | 2.8e-6; dh0 2.6e-6 | 2.4e-6; dc0
@@ -123,7 +123,7 @@ def test_clstm_training_scan_matches_autograd_of_the_unrolled_cell(C, T, with_in
     pack = ops.PackedWeight(wp, torch.float32, cin_pad=2 * C, cout_pad=4 * C)
     leaf = lambda t: None if t is None else t.cuda().requires_grad_()
     xl, hl, cl = leaf(xs), leaf(h0), leaf(c0)
-    hs_f, cs_f = ops.CLSTMScanFn.apply(xl, wp, bp, hl, cl, pack)
+    hs_f, cs_f = conv_rnn.CLSTMScanFn.apply(xl, wp, bp, hl, cl, pack)
     assert torch.equal(hs_f, hs_i) and torch.equal(cs_f, cs_i)
     loss = (hs_f * cu(dhs).transpose(0, 1)).sum()
     if dcs is not None:
@@ -181,7 +181,7 @@ def test_clstm_gates_bwd_is_the_adjoint_of_the_gate_math(C, dtype, with_dc):
             close_16bit(a, b, dtype, name)
     # and through the autograd shell
     gp, cp = gates.cuda().requires_grad_(), c_prev.cuda().requires_grad_()
-    h2, c2 = ops.CLSTMGatesFn.apply(gp, cp)
+    h2, c2 = conv_rnn.CLSTMGatesFn.apply(gp, cp)
     l2 = (h2.float() * dh.cuda().float()).sum()
     if with_dc:
         l2 = l2 + (c2.float() * dc.cuda().float()).sum()

@@ -209,9 +209,9 @@ def test_eyenet_recurrent_variants_host_logic(fake, over):
 
 
 def test_cgru_scan_function_matches_autograd(fake):
-    """ops.CGRUScanFn (one launch for the clip + manual BPTT with batched weight gradients) == autograd through the
+    """conv_rnn.CGRUScanFn (one launch for the clip + manual BPTT with batched weight gradients) == autograd through the
     CGRUCell formula of common.py:388-415 applied frame by frame."""
-    from eve_amd import ops
+    from eve_amd import conv_rnn, ops
     torch.manual_seed(0)
     B, T, H, W, C = 2, 3, 5, 8, 64
     xs = torch.randn(B, T, H, W, C, requires_grad=True)
@@ -221,7 +221,7 @@ def test_cgru_scan_function_matches_autograd(fake):
     w2 = (torch.randn(C, 2 * C, 3, 3) * 0.03).requires_grad_(True)
     b2 = (torch.randn(C) * 0.1).requires_grad_(True)
     p1, p2 = ops.PackedWeight(w1, torch.float32), ops.PackedWeight(w2, torch.float32)
-    hs = ops.CGRUScanFn.apply(xs, w1, b1, w2, b2, h0, p1, p2)
+    hs = conv_rnn.CGRUScanFn.apply(xs, w1, b1, w2, b2, h0, p1, p2)
     probe = torch.randn_like(hs)
     (hs * probe).sum().backward()
     got = [t.grad.clone() for t in (xs, h0, w1, b1, w2, b2)]
