@@ -166,6 +166,8 @@ SIGNATURES = {
     'eve_adam_step': [L, P, P, P, P, P, F, F, F, F, F, F, F, I, P, I, P, P, P],
     'eve_eye_tail_stream_fwd': [I, I, P, P, POINTER(EyeTailWeights), P, P, P, P, P, P],
     'eve_stream_state_rows': [I, I, L, L, L, P, P, P, P],
+    'eve_eye_tail_stream_fwd_len': [I, I, P, P, POINTER(EyeTailWeights), P, P, P, P, P, P, P],
+    'eve_stream_state_rows_at': [I, I, I, L, L, L, L, P, P, P, P],
 }
 EXPORTS = sorted(list(SIGNATURES) + ['eve_abi_version', 'eve_last_error', 'eve_last_kernel'])
 

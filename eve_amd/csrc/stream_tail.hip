@@ -59,14 +59,17 @@ __device__ __forceinline__ void tail_lin128(const float* in, int ldi, int K, con
 
 __global__ __launch_bounds__(TAIL_THREADS) void eye_tail_stream_fwd_kernel(
         const int T, const float* __restrict__ feats, const float* __restrict__ head_pose, const eve_eye_tail_weights w,
-        float* __restrict__ h_state, const int* __restrict__ reset, float* __restrict__ gaze, float* __restrict__ pupil,
-        float* __restrict__ hs) {
+        float* __restrict__ h_state, const int* __restrict__ reset, const int* __restrict__ lengths, float* __restrict__ gaze,
+        float* __restrict__ pupil, float* __restrict__ hs) {
     __shared__ __attribute__((aligned(16))) float X[TAIL_TS * TAIL_F];        // feats; later fc_common.0, GI, head hidden rows
     __shared__ __attribute__((aligned(16))) float Bf[TAIL_TS * TAIL_LDB];     // [fc | head pose]; fc_common.2; the GRU outputs
     __shared__ __attribute__((aligned(16))) float h[TAIL_H];
     __shared__ float gh[TAIL_H3];
     const int s = blockIdx.x, j = threadIdx.x;
     const bool zero = reset != nullptr && reset[s] != 0;
+    // frames of this sequence that advance the carried state (eve_eye_tail_stream_fwd_len); every frame is still computed, the
+    // ones from `len` on with h held at the state after frame len - 1, so the write-back below needs no second copy of h
+    const int len = lengths != nullptr ? min(max(lengths[s], 0), T) : T;
     if (j < TAIL_H) h[j] = zero ? 0.f : h_state[(size_t)s * TAIL_H + j];
     const float bhh = w.hh_b[j];
     float wr[TAIL_H];                       // column j of W_hh^T, resident for the whole chunk (loaded per sub-chunk it spills)
@@ -132,7 +135,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void eye_tail_stream_fwd_kernel(
                     if (hs) hs[(row0 + t) * TAIL_H + j] = hnew;
                 }
                 __syncthreads();
-                if (j < TAIL_H) h[j] = hnew;
+                if (j < TAIL_H && t0 + t < len) h[j] = hnew;
                 __syncthreads();
             }
         }
@@ -157,6 +160,8 @@ __global__ __launch_bounds__(TAIL_THREADS) void eye_tail_stream_fwd_kernel(
 
 // ---------------------------------------------------------------------------------------------------
 // eve_stream_state_rows: dst[s] = reset[s] ? 0 : src[s], bit copies of 4- or 2-byte elements
+// eve_stream_state_rows_at (lengths != nullptr): dst[s] = src[s][lengths[s] - 1], rows with lengths[s] <= 0 left as they are;
+// the length is clamped to T, so no device value reads outside src
 // ---------------------------------------------------------------------------------------------------
 template <typename U>
 __global__ __launch_bounds__(256) void stream_state_rows_kernel(const long long row_elems, const long long src_stride,
@@ -170,13 +175,27 @@ __global__ __launch_bounds__(256) void stream_state_rows_kernel(const long long 
         b[i] = zero ? U(0) : a[i];
 }
 
+template <typename U>
+__global__ __launch_bounds__(256) void stream_state_rows_at_kernel(const int T, const long long row_elems, const long long frame_stride,
+                                                                   const long long src_stride, const long long dst_stride,
+                                                                   const U* __restrict__ src, U* __restrict__ dst,
+                                                                   const int* __restrict__ lengths) {
+    const int s = blockIdx.y;
+    const int len = min(lengths[s], T);
+    if (len <= 0) return;
+    const U* a = src + (size_t)s * src_stride + (size_t)(len - 1) * frame_stride;
+    U* b = dst + (size_t)s * dst_stride;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < row_elems; i += (long long)gridDim.x * 256) b[i] = a[i];
+}
+
 }  // namespace
 }  // namespace eve
 
 using namespace eve;
 
-extern "C" int eve_eye_tail_stream_fwd(int S, int T, const float* feats, const float* head_pose, const eve_eye_tail_weights* weights,
-                                       float* h, const int* reset, float* gaze, float* pupil, float* hs, eve_stream_t stream) {
+extern "C" int eve_eye_tail_stream_fwd_len(int S, int T, const float* feats, const float* head_pose, const eve_eye_tail_weights* weights,
+                                           float* h, const int* reset, const int* lengths, float* gaze, float* pupil, float* hs,
+                                           eve_stream_t stream) {
     if (S <= 0 || T <= 0 || S > 65535 || !feats || !head_pose || !weights || !h || !gaze || !pupil)
         return set_error_msg("eye_tail_stream_fwd: bad arguments");
     const eve_eye_tail_weights& w = *weights;
@@ -185,9 +204,14 @@ extern "C" int eve_eye_tail_stream_fwd(int S, int T, const float* feats, const f
         return set_error_msg("eye_tail_stream_fwd: a weight pointer is NULL");
     if ((reinterpret_cast<uintptr_t>(feats) & 15) != 0) return set_error_msg("eye_tail_stream_fwd: feats must be 16-byte aligned");
     EVE_LAUNCH("eye_tail_stream_fwd_kernel", eye_tail_stream_fwd_kernel, dim3(S), dim3(TAIL_THREADS), 0, (hipStream_t)stream, T, feats,
-               head_pose, w, h, reset, gaze, pupil, hs);
+               head_pose, w, h, reset, lengths, gaze, pupil, hs);
     EVE_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int eve_eye_tail_stream_fwd(int S, int T, const float* feats, const float* head_pose, const eve_eye_tail_weights* weights,
+                                       float* h, const int* reset, float* gaze, float* pupil, float* hs, eve_stream_t stream) {
+    return eve_eye_tail_stream_fwd_len(S, T, feats, head_pose, weights, h, reset, nullptr, gaze, pupil, hs, stream);
 }
 
 extern "C" int eve_stream_state_rows(int dtype, int S, long long row_elems, long long src_stride, long long dst_stride, const void* src,
@@ -211,6 +235,34 @@ extern "C" int eve_stream_state_rows(int dtype, int S, long long row_elems, long
                    src_stride, dst_stride, (const uint16_t*)src, (uint16_t*)dst, reset);
     else
         return set_error_msg("stream_state_rows: dtype must be f32, bf16 or f16");
+    EVE_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int eve_stream_state_rows_at(int dtype, int S, int T, long long row_elems, long long frame_stride, long long src_stride,
+                                        long long dst_stride, const void* src, void* dst, const int* lengths, eve_stream_t stream) {
+    if (!src || !dst || !lengths) return set_error_msg("stream_state_rows_at: src, dst and lengths must not be NULL");
+    if (T < 1) return set_error_msg("stream_state_rows_at: T must be >= 1");
+    if (S <= 0 || S > 65535 || row_elems <= 0 || frame_stride < row_elems || src_stride < row_elems || dst_stride < row_elems)
+        return set_error_msg("stream_state_rows_at: bad arguments (strides >= row_elems)");
+    if (dtype != EVE_DT_F32 && dtype != EVE_DT_BF16 && dtype != EVE_DT_F16)
+        return set_error_msg("stream_state_rows_at: dtype must be f32, bf16 or f16");
+    {                                // a commit is never in place: the S x T source frames and the S destination rows are disjoint
+        const char* a = (const char*)src;
+        const char* b = (const char*)dst;
+        const size_t es = dtype == EVE_DT_F32 ? 4 : 2;
+        const size_t na = ((size_t)(S - 1) * src_stride + (size_t)(T - 1) * frame_stride + row_elems) * es;
+        const size_t nb = ((size_t)(S - 1) * dst_stride + row_elems) * es;
+        if (a < b + nb && b < a + na) return set_error_msg("stream_state_rows_at: src and dst overlap");
+    }
+    const long long blocks_x = (row_elems + 255) / 256 < 64 ? (row_elems + 255) / 256 : 64;
+    const dim3 grid((unsigned)blocks_x, (unsigned)S);
+    if (dtype == EVE_DT_F32)
+        EVE_LAUNCH("stream_state_rows_at_kernel", stream_state_rows_at_kernel<uint32_t>, grid, dim3(256), 0, (hipStream_t)stream, T,
+                   row_elems, frame_stride, src_stride, dst_stride, (const uint32_t*)src, (uint32_t*)dst, lengths);
+    else
+        EVE_LAUNCH("stream_state_rows_at_kernel", stream_state_rows_at_kernel<uint16_t>, grid, dim3(256), 0, (hipStream_t)stream, T,
+                   row_elems, frame_stride, src_stride, dst_stride, (const uint16_t*)src, (uint16_t*)dst, lengths);
     EVE_CHECK_LAUNCH();
     return 0;
 }

@@ -304,23 +304,25 @@ class EVE(nn.Module):
     PREDICTION_KEYS = ('left_g_initial', 'right_g_initial', 'left_pupil_size', 'right_pupil_size', 'g_initial', 'PoG_px_initial',
                        'PoG_cm_initial', 'g_final', 'PoG_px_final', 'PoG_cm_final')
 
-    def _predict_sequence(self, d, eye_states, refine_states, reset=None, return_heatmaps=False):
+    def _predict_sequence(self, d, eye_states, refine_states, reset=None, return_heatmaps=False, lengths=None):
         """The prediction part of forward() for one chunk of an EVEStream: eval only, no labels, no losses.  d: the chunk's
         inputs [B, Tc, ...] (not modified); eye_states / refine_states: the carried state buffers of the two networks
         (EyeNet._stream_state_buffers, RefineNet._stream_state_buffers), read as the state before the chunk and overwritten with
         the state after it; reset: None or int32 [2B] device flags (stream b's flag at b and B + b) -- flagged streams start from
-        zero.  Same kernels and the same _pog_block / _final_block as forward().  -> the PREDICTION_KEYS present (the PoG keys
-        need the camera geometry), plus heatmap_final when asked."""
+        zero; lengths: None or int32 [2B] device frame counts in the same layout -- stream b consumes its first lengths[b] frames
+        only (states handed over from frame lengths[b] - 1, outputs from lengths[b] on unspecified).  Same kernels and the same
+        _pog_block / _final_block as forward().  -> the PREDICTION_KEYS present (the PoG keys need the camera geometry), plus
+        heatmap_final when asked."""
         assert not self.training, 'EVE._predict_sequence is eval-only'
         B = d['left_eye_patch'].shape[0]
         d = dict(d)
         if 'left_o' in d:
             d['o'] = _mean2(d['left_o'], d['right_o'])
-        inter = dict(self.eye_net._stream_sequence(d, eye_states, reset))
+        inter = dict(self.eye_net._stream_sequence(d, eye_states, reset, lengths))
         self._pog_block(d, inter, 'initial', 'initial')
         if self.refine_net is not None and 'heatmap_initial' in inter:
             hf = self.refine_net._stream_sequence(inter['heatmap_initial'], d.get('screen_frame'), refine_states,
-                                                  None if reset is None else reset[:B])
+                                                  None if reset is None else reset[:B], None if lengths is None else lengths[:B])
             inter['heatmap_final'] = hf
             self._final_block(d, inter, hf)
         out = {k_: inter[k_] for k_ in self.PREDICTION_KEYS if k_ in inter}

@@ -456,12 +456,15 @@ class EyeNet(nn.Module):
         self._stream_w = (P, w)
         return w
 
-    def _stream_sequence(self, batch, states, reset=None):
+    def _stream_sequence(self, batch, states, reset=None, lengths=None):
         """One chunk of B streams (eval, no labels): batch as for forward_sequence ([B, Tc, ...]); states: the carried buffers of
         _stream_state_buffers, read as the state before the chunk's first frame -- zeroed first where reset[s] != 0 (int32 [2B], a
         stream's flag repeated for its two eyes) -- and overwritten with the state after its last frame.  `_tail` runs with the
         buffers as h0 and one eve_stream_state_rows launch per state each way; with stream_fused_tail the shipped tail is one
-        eve_eye_tail_stream_fwd launch that reads and writes its state in place.  Returns the forward_sequence prediction keys (<side>_g_initial, <side>_pupil_size)."""
+        eve_eye_tail_stream_fwd launch that reads and writes its state in place.  lengths: None, or int32 [2B] on the device laid
+        out like reset -- sequence s then consumes only its first lengths[s] frames: its states are committed from frame
+        lengths[s] - 1 (eve_stream_state_rows_at, eve_eye_tail_stream_fwd_len) or kept when that is 0, and its outputs from frame
+        lengths[s] on are unspecified.  Returns the forward_sequence prediction keys (<side>_g_initial, <side>_pupil_size)."""
         k = default_kernels()
         P = self._get_packs()
         feats, B, T = self._sequence_features(batch, P)
@@ -469,7 +472,10 @@ class EyeNet(nn.Module):
         if self.config.eye_net_use_head_pose_input:
             head_pose = torch.cat([batch['left_h'].reshape(B * T, 2), batch['right_h'].reshape(B * T, 2)], dim=0).float()
         if self._stream_tail_fused_ok():
-            gaze, pupil, _ = k.eye_tail_stream_fwd(feats, head_pose, self._stream_tail_weights(P), states[0], reset)
+            if lengths is None:
+                gaze, pupil, _ = k.eye_tail_stream_fwd(feats, head_pose, self._stream_tail_weights(P), states[0], reset)
+            else:
+                gaze, pupil, _ = k.eye_tail_stream_fwd_len(feats, head_pose, self._stream_tail_weights(P), states[0], lengths, reset)
             gaze, pupil = gaze.view(2 * B * T, 2), pupil.view(2 * B * T)
         else:
             flat = [t for s_ in states for t in (s_ if isinstance(s_, tuple) else (s_,))]
@@ -480,7 +486,10 @@ class EyeNet(nn.Module):
             for buf, st in zip(states, out_states or []):
                 pairs = zip(buf, st) if isinstance(buf, tuple) else ((buf, st),)
                 for dst, src in pairs:
-                    k.stream_state_rows(src[:, -1], dst)
+                    if lengths is None:
+                        k.stream_state_rows(src[:, -1], dst)
+                    else:
+                        k.stream_state_rows_at(src, dst, lengths)
         out = {}
         for si, side in enumerate(('left', 'right')):
             sl = slice(si * B * T, (si + 1) * B * T)

@@ -1125,6 +1125,16 @@ class HipKernels(object):
         """The EyeNet tail forward in one launch with the GRU state `h` [S, 128] float32 read and overwritten in place.
         feats [S*T, 512] float32 (sequence-major), head_pose [S*T, 2]; weights: the 17 float32 tensors of eve_eye_tail_weights in
         field order; reset: int32 [S] or None.  -> gaze [S, T, 2], pupil [S, T], hs [S, T, 128] or None."""
+        return self._eye_tail_stream(feats, head_pose, weights, h, reset, None, want_hs)
+
+    def eye_tail_stream_fwd_len(self, feats, head_pose, weights, h, lengths, reset=None, want_hs=False):
+        """eye_tail_stream_fwd for a ragged chunk: lengths int32 [>= S] on the device; `h[s]` becomes the state after frame
+        lengths[s] - 1 (kept for a length of 0, zeroed where reset).  The outputs at t >= lengths[s] are unspecified."""
+        assert lengths is not None and lengths.dtype == torch.int32 and lengths.is_contiguous() and lengths.is_cuda
+        assert lengths.numel() >= h.shape[0]
+        return self._eye_tail_stream(feats, head_pose, weights, h, reset, lengths, want_hs)
+
+    def _eye_tail_stream(self, feats, head_pose, weights, h, reset, lengths, want_hs):
         S = h.shape[0]
         M = feats.shape[0]
         T = M // S
@@ -1138,8 +1148,13 @@ class HipKernels(object):
         gaze = torch.empty((S, T, 2), dtype=torch.float32, device=dev)
         pupil = torch.empty((S, T), dtype=torch.float32, device=dev)
         hs = torch.empty((S, T, 128), dtype=torch.float32, device=dev) if want_hs else None
-        self._ck(self.lib.eve_eye_tail_stream_fwd(S, T, self._p(feats), self._p(head_pose), ctypes.byref(w), self._p(h), self._p(reset),
-                                                  self._p(gaze), self._p(pupil), self._p(hs), self._stream()))
+        if lengths is None:
+            self._ck(self.lib.eve_eye_tail_stream_fwd(S, T, self._p(feats), self._p(head_pose), ctypes.byref(w), self._p(h),
+                                                      self._p(reset), self._p(gaze), self._p(pupil), self._p(hs), self._stream()))
+        else:
+            self._ck(self.lib.eve_eye_tail_stream_fwd_len(S, T, self._p(feats), self._p(head_pose), ctypes.byref(w), self._p(h),
+                                                          self._p(reset), self._p(lengths), self._p(gaze), self._p(pupil),
+                                                          self._p(hs), self._stream()))
         return gaze, pupil, hs
 
     def stream_state_rows(self, src, dst, reset=None):
@@ -1154,6 +1169,22 @@ class HipKernels(object):
         self._ck(self.lib.eve_stream_state_rows(dt_code(dst.dtype), S, row, src.stride(0) if S > 1 else row,
                                                 dst.stride(0) if S > 1 else row, ctypes.c_void_p(src.data_ptr()),
                                                 ctypes.c_void_p(dst.data_ptr()), self._p(reset), self._stream()))
+        return dst
+
+    def stream_state_rows_at(self, src, dst, lengths):
+        """dst[s] = src[s, lengths[s] - 1] where lengths[s] > 0, dst[s] kept otherwise: src [S, T, ...] (a scan's per-frame
+        states; each frame contiguous), dst [S, ...], lengths int32 [>= S] on
+        the device -- the commit of a ragged EVEStream step."""
+        S, T = src.shape[:2]
+        assert tuple(dst.shape) == (S,) + tuple(src.shape[2:]) and src.dtype == dst.dtype and src.is_cuda and dst.is_cuda and S > 0
+        row = dst[0].numel()
+        assert src[0, 0].is_contiguous() and dst[0].is_contiguous(), 'stream_state_rows_at: rows must be contiguous'
+        fs, ss = src.stride(1) if T > 1 else row, src.stride(0) if S > 1 else row
+        assert fs >= row and ss >= row and (S == 1 or dst.stride(0) >= row), 'stream_state_rows_at: strides'
+        assert lengths.dtype == torch.int32 and lengths.is_contiguous() and lengths.numel() >= S and lengths.is_cuda
+        self._ck(self.lib.eve_stream_state_rows_at(dt_code(dst.dtype), S, T, row, fs, ss, dst.stride(0) if S > 1 else row,
+                                                   ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()),
+                                                   self._p(lengths), self._stream()))
         return dst
 
     def cgru_gates1(self, g1, h):

@@ -365,10 +365,11 @@ class RefineNet(nn.Module):
         z = lambda dt: torch.zeros((B, 5, 8, C), dtype=dt, device=device)
         return [tuple(z(d) for d in dt) if isinstance(dt, tuple) else z(dt) for dt in self._carried_dtypes()]
 
-    def _stream_sequence(self, heatmap_initial, screen_frame, buffers, reset=None):
+    def _stream_sequence(self, heatmap_initial, screen_frame, buffers, reset=None, lengths=None):
         """One chunk of a stream: the carried states `buffers` (from _stream_state_buffers) are zeroed where reset[b] != 0, used
         as the initial states, and overwritten with the chunk's last frame -- one eve_stream_state_rows launch each way, no
-        conversion.  -> heatmap_final [B,T,1,H,W]."""
+        conversion.  lengths (None, or int32 [B] on the device): stream b's states are committed from its frame lengths[b] - 1
+        instead (eve_stream_state_rows_at), or kept when that is 0.  -> heatmap_final [B,T,1,H,W]."""
         k = default_kernels()
         flat = lambda sts: [t for s in sts for t in (s if isinstance(s, tuple) else (s,))]
         if reset is not None:
@@ -376,5 +377,8 @@ class RefineNet(nn.Module):
                 k.stream_state_rows(t, t, reset)
         hf, states, _ = self._sequence(heatmap_initial, screen_frame, buffers if buffers else None)
         for dst, src in zip(flat(buffers), flat(states)):
-            k.stream_state_rows(src[:, -1], dst)
+            if lengths is None:
+                k.stream_state_rows(src[:, -1], dst)
+            else:
+                k.stream_state_rows_at(src, dst, lengths)
         return hf

@@ -3,6 +3,7 @@ carried from one call to the next.
 
     stream = eve_amd.EVEStream(model, num_streams=B)      # model: an eve_amd.EVE in eval mode
     out = stream.step(chunk)                               # chunk: dict of [B, Tc, ...] GPU tensors, any Tc >= 1
+    out = stream.step(chunk, lengths=[3, 1, 0, 3])         # ragged: stream b delivered only lengths[b] frames (see step)
     stream.reset([3])                                      # stream 3 starts from zero state at the next step()
     st = stream.get_state(); stream.set_state(st)          # reference layout, e.g. to resume a recording
 
@@ -14,6 +15,11 @@ The carried states live in fixed device buffers in the modules' own layout and d
 rows then the right ones'; RefineNet [B, 5, 8, C] NHWC), so a step converts nothing.  Each is zeroed where reset and committed
 from the chunk's last frame by eve_stream_state_rows.  (EyeNet.stream_fused_tail runs the shipped EyeNet tail as one
 eve_eye_tail_stream_fwd launch that updates its GRU state in place; it measured slower, so it is off by default.)
+
+A ragged step (lengths=...) hands each stream's states over at its own frame count: eve_stream_state_rows_at commits from frame
+lengths[b] - 1 (eve_eye_tail_stream_fwd_len for the fused tail) and leaves a stream with no frames alone.  The counts are a
+device int32 [2B] filled from a pinned block like the reset flags, so the host never waits and one graph per chunk shape serves
+every length pattern.  The chunk keeps its shape: frames past a stream's count cost what real ones cost (no compaction).
 
 With use_graph (the default) each distinct chunk shape is captured once into a hipGraph on one stream and replayed; the
 chunk is copied into the graph's input buffers first.  Resets are device flags written by the host before the replay.  A
@@ -49,6 +55,7 @@ class EVEStream(object):
         self._ref = model.refine_net._stream_state_buffers(B, self.device) if model.refine_net is not None else []
         self._flags = torch.zeros((2 * B,), dtype=torch.int32, device=self.device)   # stream b's reset flag at b and B + b
         self._flags_set = False
+        self._lengths = torch.zeros((2 * B,), dtype=torch.int32, device=self.device)  # a ragged step's frame counts, laid out like _flags
         self._pending = None                     # host bool [B]: resets requested for the next step
         self._graphs = {}
         self._graphs_key = None
@@ -126,30 +133,64 @@ class EVEStream(object):
         self._flags_set = True
         self._pending = None
 
-    def _run(self, chunk, return_heatmaps):
-        return self.model._predict_sequence(chunk, self._eye, self._ref, reset=self._flags, return_heatmaps=return_heatmaps)
+    def _host_lengths(self, lengths, Tc):
+        """step()'s `lengths` checked -> numpy int32 [B]."""
+        B = self.num_streams
+        a = lengths.detach().cpu().numpy() if torch.is_tensor(lengths) else np.asarray(lengths)
+        if a.dtype.kind not in 'iu':
+            raise ValueError('step: lengths must be integers, not %s' % a.dtype)
+        if a.shape != (B,):
+            raise ValueError('step: lengths needs num_streams (%d) entries' % B)
+        if a.min() < 0 or a.max() > Tc:
+            raise ValueError('step: lengths must lie in 0..%d (the chunk\'s frames)' % Tc)
+        return a.astype(np.int32)
 
-    def step(self, chunk, return_heatmaps=False):
+    def _upload_lengths(self, n):
+        host = torch.from_numpy(np.concatenate([n, n]))
+        if self.device.type == 'cuda':
+            host = host.pin_memory()             # as _upload_resets: asynchronous, and never baked into a graph
+        self._lengths.copy_(host, non_blocking=True)
+
+    def _run(self, chunk, return_heatmaps, ragged=False):
+        if not ragged:
+            return self.model._predict_sequence(chunk, self._eye, self._ref, reset=self._flags, return_heatmaps=return_heatmaps)
+        return self.model._predict_sequence(chunk, self._eye, self._ref, reset=self._flags, return_heatmaps=return_heatmaps,
+                                            lengths=self._lengths)
+
+    def step(self, chunk, return_heatmaps=False, lengths=None):
         """One chunk of every stream: chunk holds [B, Tc, ...] tensors on the model's device -- the eye patches (float NCHW or
         uint8 NHWC), {left,right}_h, {left,right}_o, {left,right}_R, head_R, camera_transformation, inv_camera_transformation,
         pixels_per_millimeter, millimeters_per_pixel, and screen_frame when the config loads screen content.  Returns the
         prediction keys of EVE(output_predictions=True) as [B, Tc, ...] tensors (heatmap_final [B, Tc, 1, H, W] on request).
         With use_graph the returned tensors are the graph's output buffers: valid until the next step() of the same chunk
-        shape (clone what you keep).  The host does not wait for the device, except when a new chunk shape is captured."""
+        shape (clone what you keep).  The host does not wait for the device, except when a new chunk shape is captured.
+
+        lengths: None, or num_streams integers in 0..Tc (list, numpy array or CPU tensor) for streams that delivered different
+        numbers of frames: stream b consumes frames 0..lengths[b]-1 of the chunk, and every carried state of it afterwards is the
+        state after exactly that many frames -- untouched for 0 frames, except that a requested reset() is still applied.  The
+        outputs keep their [B, Tc, ...] shapes, their entries at t >= lengths[b] are unspecified, and the result gains `valid`, a
+        bool [B, Tc] device tensor that marks the consumed frames.  The frames past a stream's count are computed like real ones:
+        the step costs what a full chunk of this shape costs."""
         if self.model.training:
             raise ValueError('EVEStream runs inference only: the model was switched to training mode')
         if chunk['left_eye_patch'].shape[0] != self.num_streams:
             raise ValueError('chunk has %d streams, the EVEStream %d' % (chunk['left_eye_patch'].shape[0], self.num_streams))
+        ragged = lengths is not None
+        if ragged:
+            Tc = chunk['left_eye_patch'].shape[1]
+            self._upload_lengths(self._host_lengths(lengths, Tc))
         self._upload_resets()
         with torch.no_grad():
             if self.use_graph:
-                entry = self._graph_for(chunk, bool(return_heatmaps))
+                entry = self._graph_for(chunk, bool(return_heatmaps), ragged)
                 for key, buf in entry['inputs'].items():
                     buf.copy_(chunk[key], non_blocking=True)
                 entry['graph'].replay()
                 out = dict(entry['outputs'])
             else:
-                out = self._run(chunk, return_heatmaps)
+                out = self._run(chunk, return_heatmaps, ragged)
+            if ragged:
+                out['valid'] = torch.arange(Tc, device=self.device)[None, :] < self._lengths[:self.num_streams, None]
         if self._flags_set:
             self._flags.zero_()
             self._flags_set = False
@@ -166,19 +207,19 @@ class EVEStream(object):
     def _weights_key(self):
         return tuple(_module_key(m) for m in (self.model.eye_net, self.model.refine_net) if m is not None)
 
-    def _graph_for(self, chunk, return_heatmaps):
+    def _graph_for(self, chunk, return_heatmaps, ragged=False):
         wk = self._weights_key()
         if wk != self._graphs_key:               # new weights: new packs, new graphs (a replay never reads stale packs)
             self._graphs = {}
             self._graphs_key = wk
-        key = (return_heatmaps,) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
+        key = (return_heatmaps, ragged) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
         entry = self._graphs.get(key)
         if entry is None:
-            entry = self._graphs[key] = self._capture(chunk, return_heatmaps)
+            entry = self._graphs[key] = self._capture(chunk, return_heatmaps, ragged)
             self._graphs_key = self._weights_key()
         return entry
 
-    def _capture(self, chunk, return_heatmaps):
+    def _capture(self, chunk, return_heatmaps, ragged=False):
         """Capture one step for this chunk shape (train.Trainer._capture's recipe): inputs copied into fixed buffers, two eager
         warm-up steps off the default stream (packs, lazily built filters, allocator) with the carried states put back
         afterwards, the kernels' scratch allocated before the capture, one stream, no side branches."""
@@ -191,7 +232,7 @@ class EVEStream(object):
         with torch.cuda.stream(side):
             snap = [t.clone() for t in self._state_tensors()]
             for _ in range(2):
-                self._run(static, return_heatmaps)
+                self._run(static, return_heatmaps, ragged)
             for t, s_ in zip(self._state_tensors(), snap):
                 t.copy_(s_)
         torch.cuda.current_stream().wait_stream(side)
@@ -201,7 +242,7 @@ class EVEStream(object):
             k.prepare_graph_workspace(self.device)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            out = self._run(static, return_heatmaps)
+            out = self._run(static, return_heatmaps, ragged)
         m = self.model
         keep = (m.eye_net._packs, getattr(m.eye_net, '_stream_w', None), m.refine_net._packs if m.refine_net is not None else None)
         return {'graph': graph, 'inputs': static, 'outputs': out, 'keep': keep}

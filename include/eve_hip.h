@@ -660,6 +660,23 @@ int eve_eye_tail_stream_fwd(int S, int T, const float* feats, const float* head_
  * a scan's last frame (hs + (T-1) * row) into a state buffer it commits the step.  src and dst are equal or disjoint.        */
 int eve_stream_state_rows(int dtype, int S, long long row_elems, long long src_stride, long long dst_stride, const void* src,
                           void* dst, const int* reset, eve_stream_t stream);
+/* Ragged steps (EVEStream.step(lengths=...)): sequence s consumes only its first lengths[s] frames of the chunk.
+ * eve_eye_tail_stream_fwd with per-sequence lengths, int [S] on the device or NULL (= every sequence T frames, the call
+ * above, which runs the same kernel): h[s] is overwritten with the state after frame lengths[s] - 1, or left as it is for
+ * lengths[s] == 0 -- zeroed all the same when reset[s] != 0.  A length outside 0..T is clamped.  Every frame is still
+ * computed; gaze, pupil and hs at t >= lengths[s] hold unspecified (finite-input-dependent) values.                          */
+int eve_eye_tail_stream_fwd_len(int S, int T, const float* feats, const float* head_pose, const eve_eye_tail_weights* weights,
+                                float* h, const int* reset, const int* lengths, float* gaze, float* pupil, float* hs,
+                                eve_stream_t stream);
+/* Per-stream commit at a per-stream frame: for s < S with lengths[s] > 0,
+ * dst[s][i] = src[s * src_stride + (lengths[s] - 1) * frame_stride + i], i < row_elems; rows with lengths[s] == 0 keep what
+ * they hold.  src: S sequences of T frames (a scan's per-frame states), strides in elements, each >= row_elems
+ * (sequence-major or time-major); lengths int [S] on the device, read by the kernel and clamped to T there, so
+ * one captured graph serves every length pattern and no value reads outside src; dtype f32 / bf16 / f16 (bit copies).
+ * Refused without a launch: NULL src / dst / lengths, T < 1, src and dst overlapping (resets stay with the in-place
+ * eve_stream_state_rows call before the step).                                                                              */
+int eve_stream_state_rows_at(int dtype, int S, int T, long long row_elems, long long frame_stride, long long src_stride,
+                             long long dst_stride, const void* src, void* dst, const int* lengths, eve_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -2,16 +2,19 @@
 """Device time per EVEStream.step under hipGraph replay (eve_amd/stream.py), the shipped refine_net.json pipeline (GRU EyeNet,
 CLSTM RefineNet), synthetic weights and clips.  One JSON line per shape:
 
-    python tools/bench_stream.py --shapes 1x1 32x1 32x30 [--dtype bf16] [--steps 50] [--fused-tail]
+    python tools/bench_stream.py --shapes 1x1 32x1 32x30 [--dtype bf16] [--steps 50] [--fused-tail] [--ragged] [--repeat N]
 
 B x Tc = streams x frames per step.  For Tc > 1 the same clips also go through one EVE.eval() pass (`eval_ms`): what the
 stream costs over the plain clip pass.  --fused-tail runs the EyeNet tail as one eve_eye_tail_stream_fwd launch
-(EyeNet.stream_fused_tail) instead of layer by layer: the A/B of the fused kernel, e.g. under `rocprofv3 --kernel-trace --stats`."""
+(EyeNet.stream_fused_tail) instead of layer by layer: the A/B of the fused kernel, e.g. under `rocprofv3 --kernel-trace --stats`.
+--ragged steps with seeded random lengths in 0..Tc, a new pattern every step (step(chunk, lengths=...): one graph serves them
+all).  --repeat N measures every shape N times in one process (`step_ms_runs`; `step_ms` is their median): the run-to-run spread."""
 import argparse
 import json
 import os
 import sys
 
+import numpy as np
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -40,6 +43,8 @@ def main():
     ap.add_argument('--dtype', default='bf16', choices=sorted(DTYPES))
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--fused-tail', action='store_true')
+    ap.add_argument('--ragged', action='store_true')
+    ap.add_argument('--repeat', type=int, default=1)
     args = ap.parse_args()
     cfg = eve_amd.reset_standalone_config()
     cfg.import_json(os.path.join(REPO, 'configs', 'refine_net.json'))
@@ -56,11 +61,16 @@ def main():
         full = {k: torch.cat([v] * ((B + 3) // 4), dim=0)[:B].contiguous().cuda() for k, v in small.items()}
         clip = {k: full[k] for k in INPUT_KEYS if k in full}
         stream = eve_amd.EVEStream(model, B)
+        rng = np.random.default_rng(B * 1000 + Tc)
+        step = (lambda: stream.step(clip, lengths=rng.integers(0, Tc + 1, size=B))) if args.ragged else (lambda: stream.step(clip))
         for _ in range(3):
-            stream.step(clip)                                # capture + warm replays
+            step()                                           # capture + warm replays
         torch.cuda.synchronize()
-        res = {'B': B, 'Tc': Tc, 'dtype': args.dtype, 'tail': 'fused' if args.fused_tail else 'layers',
-               'step_ms': round(device_ms(lambda: stream.step(clip), args.steps), 4)}
+        runs = sorted(round(device_ms(step, args.steps), 4) for _ in range(max(1, args.repeat)))
+        res = {'B': B, 'Tc': Tc, 'dtype': args.dtype, 'tail': 'fused' if args.fused_tail else 'layers', 'ragged': args.ragged,
+               'step_ms': runs[len(runs) // 2]}
+        if len(runs) > 1:
+            res['step_ms_runs'] = runs
         res['us_per_frame'] = round(1e3 * res['step_ms'] / (B * Tc), 3)
         if Tc > 1:
             with torch.no_grad():
