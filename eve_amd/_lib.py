@@ -168,6 +168,7 @@ SIGNATURES = {
     'eve_stream_state_rows': [I, I, L, L, L, P, P, P, P],
     'eve_eye_tail_stream_fwd_len': [I, I, P, P, POINTER(EyeTailWeights), P, P, P, P, P, P, P],
     'eve_stream_state_rows_at': [I, I, I, L, L, L, L, P, P, P, P],
+    'eve_screen_u8_area_to_nchw': [L, I, I, I, P, I, I, P, P],
 }
 EXPORTS = sorted(list(SIGNATURES) + ['eve_abi_version', 'eve_last_error', 'eve_last_kernel'])
 

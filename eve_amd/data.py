@@ -8,6 +8,9 @@ uint8 frames is 4x less PCIe traffic, and the float values produced here are bit
 
   preprocess_frames(u8)          [..., H, W, C] uint8 (device) -> [..., C, H, W] float32 in [-1, 1]
   preprocess_screen_frames(u8)   same, [0, 1]
+  preprocess_screen_frames(u8, size=(H, W))
+                                 [..., IH, IW, 3|4] uint8 of any size >= (H, W), e.g. a 1920 x 1080 capture -> [..., 3, H, W]
+                                 float32 in [0, 1] by exact area averaging (RefineNet passes its screen_size for uint8 screens)
   EyeNet.forward_sequence / RefineNet.forward_sequence / EVE accept the uint8 tensors directly (eye patches go straight
   into the stem kernel's packed bf16 layout, no float tensor is ever materialised).
   DevicePrefetcher(iterable)     pinned double-buffered H2D on a side stream
@@ -33,9 +36,19 @@ def preprocess_frames(frames):
     return out.view(lead + tuple(out.shape[1:]))
 
 
-def preprocess_screen_frames(frames):
+def preprocess_screen_frames(frames, size=None):
+    """size: None, or the (H, W) the network takes.  Frames of that size already (and size=None) are normalised as the
+    reference normalises its 128 x 72 video; larger ones -- a live capture of the desktop, [..., IH, IW, 3 | 4] -- are
+    area-averaged down to it by eve_screen_u8_area_to_nchw: the exact mean over each output pixel's footprint, fractional
+    overlaps included, kept in float32.  A fourth channel (BGRA's alpha) is dropped there (so four-channel frames take that
+    kernel at the target size too, where its values are the plain normalisation's bit for bit); the channel ORDER is kept as it
+    comes, so a BGR capture is swapped to RGB by the caller.  The reference's own file was scaled by ffmpeg (bicubic, then
+    lossy video coding): this is what a live stream can do instead, not a reproduction of it."""
     flat, lead = _fold(frames)
-    out = default_kernels().frames_u8_to_nchw(flat, SCREEN_SCALE, None)
+    if size is None or (tuple(size) == tuple(flat.shape[1:3]) and flat.shape[3] == 3):
+        out = default_kernels().frames_u8_to_nchw(flat, SCREEN_SCALE, None)
+    else:
+        out = default_kernels().screen_u8_area_to_nchw(flat, (int(size[0]), int(size[1])))
     return out.view(lead + tuple(out.shape[1:]))
 
 

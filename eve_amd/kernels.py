@@ -404,6 +404,17 @@ class HipKernels(object):
                                                 0 if shift is None else 1, self._p(out), self._stream()))
         return out
 
+    def screen_u8_area_to_nchw(self, frames, out_hw):
+        """uint8 [N,IH,IW,C] (C 3 or 4, a fourth channel ignored, channel order kept) -> float32 [N,3,OH,OW] in [0, 1]: the exact
+        area average over each output pixel's footprint (include/eve_hip.h eve_screen_u8_area_to_nchw).  out_hw = (OH, OW), no
+        larger than the frames; the library refuses upscaling and frames beyond 16 843 009 pixels."""
+        N, IH, IW, C = frames.shape
+        assert frames.dtype == torch.uint8
+        OH, OW = int(out_hw[0]), int(out_hw[1])
+        out = torch.empty((N, 3, OH, OW), dtype=torch.float32, device=frames.device)
+        self._ck(self.lib.eve_screen_u8_area_to_nchw(N, IH, IW, C, self._p(frames), OH, OW, self._p(out), self._stream()))
+        return out
+
     def frames_u8_to_stem(self, frames, scale, shift, out=None, dtype=torch.bfloat16):
         """uint8 [N,H,W,C<=4] -> the stem's packed 16-bit input [N,H+6,W+8,4]."""
         N, H, W, C = frames.shape

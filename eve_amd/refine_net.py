@@ -315,6 +315,8 @@ class RefineNet(nn.Module):
     def forward_sequence(self, heatmap_initial, screen_frame=None, initial_states=None):
         """heatmap_initial [B,T,1,h,w], screen_frame [B,T,3,H,W] -> (heatmap_final [B,T,1,H,W],
         list over cells of the stacked states [B,T,C,5,8] (tuple of two for CLSTM)).
+        screen_frame may also be uint8 [B,T,IH,IW,3|4]: decoded frames at the screen size, or a full-resolution capture that is
+        area-averaged down to config.screen_size on the device (data.preprocess_screen_frames; channel order kept, alpha ignored).
         initial_states: None (zero states), or per cell the state before the first frame -- reference layout [B, C, 5, 8] as
         returned here (the last frame of a previous call), or the internal NHWC layout [B, 5, 8, C]; (h, c) for CLSTM."""
         hf, states, to_ref = self._sequence(heatmap_initial, screen_frame, self._initial_states_in(initial_states))
@@ -327,8 +329,9 @@ class RefineNet(nn.Module):
         P = self._get_packs()
         B, T = heatmap_initial.shape[:2]
         if screen_frame is not None and screen_frame.dtype == torch.uint8:     # decoded frames [B,T,H,W,3]: normalise here
-            from . import data
-            screen_frame = data.preprocess_screen_frames(screen_frame)
+            from . import data                                                 # (a full-resolution capture [B,T,IH,IW,3|4]: area-resized too)
+            cfg = self.config
+            screen_frame = data.preprocess_screen_frames(screen_frame, size=(cfg.screen_size[1], cfg.screen_size[0]))
         fold = lambda t: None if t is None else t.reshape((B * T,) + tuple(t.shape[2:]))
         x = self._input_nhwc(fold(heatmap_initial), fold(screen_frame) if self.config.load_screen_content else None)
         x, skips, prefix = self._encode(x, P)

@@ -165,6 +165,12 @@ class EVEStream(object):
         With use_graph the returned tensors are the graph's output buffers: valid until the next step() of the same chunk
         shape (clone what you keep).  The host does not wait for the device, except when a new chunk shape is captured.
 
+        screen_frame is float [B, Tc, 3, H, W] at the configured screen size, uint8 [B, Tc, H, W, 3] at that size, or a live
+        capture as it comes off the desktop: uint8 [B, Tc, IH, IW, 3 | 4] at any resolution from the screen size up to 16 843 009
+        pixels (3840 x 2160 included), area-averaged down on the device by eve_screen_u8_area_to_nchw inside the step -- and
+        inside the captured graph, whose key holds the capture's shape and dtype.  A fourth channel (BGRA's alpha) is ignored;
+        the channel order is kept, so a BGR capture is swapped by the caller.
+
         lengths: None, or num_streams integers in 0..Tc (list, numpy array or CPU tensor) for streams that delivered different
         numbers of frames: stream b consumes frames 0..lengths[b]-1 of the chunk, and every carried state of it afterwards is the
         state after exactly that many frames -- untouched for 0 frames, except that a requested reset() is still applied.  The

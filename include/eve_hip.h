@@ -677,6 +677,23 @@ int eve_eye_tail_stream_fwd_len(int S, int T, const float* feats, const float* h
  * eve_stream_state_rows call before the step).                                                                              */
 int eve_stream_state_rows_at(int dtype, int S, int T, long long row_elems, long long frame_stride, long long src_stride,
                              long long dst_stride, const void* src, void* dst, const int* lengths, eve_stream_t stream);
+/* Live screen captures: exact area (box) down-sampling of uint8 frames src [N][IH][IW][C] (C = 3, or 4 with the fourth channel
+ * ignored: the alpha of BGRA capture APIs; the channel order is kept, a BGR -> RGB swap stays with the caller) to RefineNet's
+ * screen input dst [N][3][OH][OW] float in [0, 1], OH <= IH and OW <= IW.  The reference never sees a full-resolution screen:
+ * its loader opens screen.128x72.mp4, scaled offline by ffmpeg (datasources/eve_sequences.py:243-245), and normalises it with
+ * preprocess_screen_frames (:205-211); this entry point stands where a live caller has the desktop itself, and is NOT a
+ * reproduction of that (bicubic, lossy) file.  Contract, per frame and channel:
+ *   wy = |[iy*OH, (iy+1)*OH) n [oy*IH, (oy+1)*IH)|   integer overlap of source row iy and output row oy (sums to IH over iy)
+ *   wx = |[ix*OW, (ix+1)*OW) n [ox*IW, (ox+1)*IW)|   the same along the row (sums to IW)
+ *   S  = sum wy * wx * src[iy][ix][c]                 an integer <= 255 * IH * IW, exact in 32 unsigned bits
+ *   dst[c][oy][ox] = (float)((double)S / (double)(IH * IW)) * (float)(1.0 / 255)
+ * so a frame already at the target size gives eve_frames_u8_to_nchw(scale 1/255)'s bits, an integer ratio (1920 x 1080 ->
+ * 128 x 72: 15 x 15) the plain box mean kept in float, and a fractional ratio (1366 x 768) true fractional-overlap weights, not
+ * adaptive_avg_pool2d's floor / ceil windows.  One launch, every source byte loaded once (rows that two output rows share, at
+ * fractional ratios, by both).  Refused without a launch: C other than 3 or 4, upscaling in either direction, IH * IW >
+ * 16 843 009 (covers 3840 x 2160; beyond it S could exceed 32 bits), IW * C > 40 960 bytes (one row of sums is kept in LDS). */
+int eve_screen_u8_area_to_nchw(long long N, int IH, int IW, int C, const uint8_t* src_nhwc, int OH, int OW, float* dst_nchw,
+                               eve_stream_t stream);
 
 #ifdef __cplusplus
 }

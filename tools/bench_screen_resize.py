@@ -1,0 +1,109 @@
+#!/usr/bin/env python
+"""Device time of the screen-capture area resize (eve_screen_u8_area_to_nchw, csrc/screen_resize.hip) next to two yardsticks, the
+three routes interleaved in one process:
+
+    area    HipKernels.screen_u8_area_to_nchw(frames, (72, 128)): reads N*IH*IW*C bytes once, writes 110 KB per frame
+    clone   frames.clone(): a read plus a write of the same bytes -- a read-only kernel's floor is about half of it
+    aten    what a caller had before: permute + float + F.interpolate(mode='area') + scale (a float tensor four times the
+            capture; for fractional ratios not the same values)
+
+    python tools/bench_screen_resize.py [--sizes 1920x1080 2560x1440] [--frames 1 32 240] [--channels 3] [--iters 20] [--rounds 5]
+                                        [--markdown profiles/table.md]
+
+One JSON line per (size, N): per route the median over the rounds of the device time per call (events around `iters` calls), and
+for `area` and `clone` the rate N*IH*IW*C / time as a fraction of the 8 TB/s HBM peak (`clone` moves twice those bytes).  Every
+route rotates over enough separately allocated captures to exceed the 256 MiB Infinity Cache, so the reads come from HBM; a live
+caller whose capture was just copied in may see it served from that cache instead."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+import torch.nn.functional as F
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+from eve_amd.kernels import default_kernels  # noqa: E402
+
+HBM_PEAK = 8.0e12
+OUT_HW = (72, 128)
+ROTATE_BYTES = 512 << 20
+
+
+def device_ms(fn, iters):
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for i in range(iters):
+        fn(i)
+    end.record()
+    torch.cuda.synchronize()
+    return start.elapsed_time(end) / iters
+
+
+def aten_route(frames):
+    x = frames[..., :3].permute(0, 3, 1, 2).float()
+    return F.interpolate(x, size=OUT_HW, mode='area') * (1.0 / 255.0)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--sizes', nargs='+', default=['1920x1080', '2560x1440'])
+    ap.add_argument('--frames', nargs='+', type=int, default=[1, 32, 240])
+    ap.add_argument('--channels', type=int, default=3, choices=(3, 4))
+    ap.add_argument('--iters', type=int, default=20)
+    ap.add_argument('--rounds', type=int, default=5)
+    ap.add_argument('--markdown', default=None, help='also write the table to this file')
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit('bench_screen_resize: no GPU (a time is only measured on one)')
+    k = default_kernels()
+    rows = []
+    for size in args.sizes:
+        IW, IH = (int(v) for v in size.lower().split('x'))
+        for N in args.frames:
+            nbytes = N * IH * IW * args.channels
+            copies = max(1, min(64, -(-ROTATE_BYTES // nbytes)))
+            torch.manual_seed(N + IW)
+            caps = [torch.randint(0, 256, (N, IH, IW, args.channels), dtype=torch.uint8, device='cuda') for _ in range(min(copies, 2))]
+            caps += [caps[i % 2].clone() for i in range(copies - len(caps))]
+            routes = {'area': lambda i: k.screen_u8_area_to_nchw(caps[i % copies], OUT_HW),
+                      'clone': lambda i: caps[i % copies].clone(),
+                      'aten': lambda i: aten_route(caps[i % copies])}
+            with torch.no_grad():
+                for fn in routes.values():               # warm up: code objects, allocator
+                    for i in range(3):
+                        fn(i)
+                torch.cuda.synchronize()
+                times = {name: [] for name in routes}
+                for _ in range(args.rounds):
+                    for name, fn in routes.items():
+                        times[name].append(device_ms(fn, args.iters))
+            med = {name: sorted(t)[len(t) // 2] for name, t in times.items()}
+            res = {'size': size, 'N': N, 'C': args.channels, 'bytes': nbytes, 'captures_rotated': copies,
+                   'area_us': round(1e3 * med['area'], 2), 'clone_us': round(1e3 * med['clone'], 2), 'aten_us': round(1e3 * med['aten'], 2),
+                   'area_us_min_max': [round(1e3 * min(times['area']), 2), round(1e3 * max(times['area']), 2)],
+                   'area_frac_of_8TBps': round(nbytes / (1e-3 * med['area']) / HBM_PEAK, 4),
+                   'clone_frac_of_8TBps_read_plus_write': round(2 * nbytes / (1e-3 * med['clone']) / HBM_PEAK, 4),
+                   'aten_over_area': round(med['aten'] / med['area'], 2)}
+            k.screen_u8_area_to_nchw(caps[0], OUT_HW)
+            res['kernel'] = k.lib.eve_last_kernel().decode()
+            print(json.dumps(res), flush=True)
+            rows.append(res)
+            del caps, routes
+            torch.cuda.empty_cache()
+    lines = ['| size | N | MB in | area us | of 8 TB/s | clone us | (r+w) of 8 TB/s | ATen us | ATen / area |', '|---|---|---|---|---|---|---|---|---|']
+    for r in rows:
+        lines.append('| %s | %d | %.1f | %.2f | %.1f %% | %.2f | %.1f %% | %.2f | %.1fx |' % (
+            r['size'], r['N'], r['bytes'] / 1e6, r['area_us'], 100 * r['area_frac_of_8TBps'], r['clone_us'],
+            100 * r['clone_frac_of_8TBps_read_plus_write'], r['aten_us'], r['aten_over_area']))
+    table = '\n'.join(lines)
+    print(table, flush=True)
+    if args.markdown:
+        os.makedirs(os.path.dirname(os.path.abspath(args.markdown)), exist_ok=True)
+        with open(args.markdown, 'w') as f:
+            f.write(table + '\n')
+
+
+if __name__ == '__main__':
+    main()

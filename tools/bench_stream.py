@@ -3,12 +3,14 @@
 CLSTM RefineNet), synthetic weights and clips.  One JSON line per shape:
 
     python tools/bench_stream.py --shapes 1x1 32x1 32x30 [--dtype bf16] [--steps 50] [--fused-tail] [--ragged] [--repeat N]
+                                 [--screen 1920x1080]
 
 B x Tc = streams x frames per step.  For Tc > 1 the same clips also go through one EVE.eval() pass (`eval_ms`): what the
 stream costs over the plain clip pass.  --fused-tail runs the EyeNet tail as one eve_eye_tail_stream_fwd launch
 (EyeNet.stream_fused_tail) instead of layer by layer: the A/B of the fused kernel, e.g. under `rocprofv3 --kernel-trace --stats`.
 --ragged steps with seeded random lengths in 0..Tc, a new pattern every step (step(chunk, lengths=...): one graph serves them
-all).  --repeat N measures every shape N times in one process (`step_ms_runs`; `step_ms` is their median): the run-to-run spread."""
+all).  --screen WxH feeds uint8 screen captures of that size, [B, Tc, H, W, 3], instead of the pre-resized float screens: the step
+then holds the area resize (eve_screen_u8_area_to_nchw) and the copy of the captures into the graph's input buffer.  --repeat N measures every shape N times in one process (`step_ms_runs`; `step_ms` is their median): the run-to-run spread."""
 import argparse
 import json
 import os
@@ -45,6 +47,7 @@ def main():
     ap.add_argument('--fused-tail', action='store_true')
     ap.add_argument('--ragged', action='store_true')
     ap.add_argument('--repeat', type=int, default=1)
+    ap.add_argument('--screen', default=None, metavar='WxH', help='feed uint8 screen captures of this size, e.g. 1920x1080')
     args = ap.parse_args()
     cfg = eve_amd.reset_standalone_config()
     cfg.import_json(os.path.join(REPO, 'configs', 'refine_net.json'))
@@ -55,10 +58,18 @@ def main():
     detweights.fill_module(model.refine_net, 1)
     model = model.cuda().eval()
     model.eye_net.stream_fused_tail = args.fused_tail
+    screen = None
+    if args.screen:
+        if not cfg.load_screen_content:
+            ap.error('--screen needs a configuration with load_screen_content')
+        screen = tuple(int(v) for v in args.screen.lower().split('x'))
     for shape in args.shapes:
         B, Tc = (int(v) for v in shape.split('x'))
         small = detweights.eve_batch(min(B, 4), Tc, seed=1)
         full = {k: torch.cat([v] * ((B + 3) // 4), dim=0)[:B].contiguous().cuda() for k, v in small.items()}
+        if screen is not None:
+            g = torch.Generator().manual_seed(B * 1000 + Tc)
+            full['screen_frame'] = torch.randint(0, 256, (B, Tc, screen[1], screen[0], 3), generator=g, dtype=torch.uint8).cuda()
         clip = {k: full[k] for k in INPUT_KEYS if k in full}
         stream = eve_amd.EVEStream(model, B)
         rng = np.random.default_rng(B * 1000 + Tc)
@@ -68,7 +79,7 @@ def main():
         torch.cuda.synchronize()
         runs = sorted(round(device_ms(step, args.steps), 4) for _ in range(max(1, args.repeat)))
         res = {'B': B, 'Tc': Tc, 'dtype': args.dtype, 'tail': 'fused' if args.fused_tail else 'layers', 'ragged': args.ragged,
-               'step_ms': runs[len(runs) // 2]}
+               'screen': args.screen or 'float', 'step_ms': runs[len(runs) // 2]}
         if len(runs) > 1:
             res['step_ms_runs'] = runs
         res['us_per_frame'] = round(1e3 * res['step_ms'] / (B * Tc), 3)
