@@ -169,6 +169,8 @@ SIGNATURES = {
     'eve_eye_tail_stream_fwd_len': [I, I, P, P, POINTER(EyeTailWeights), P, P, P, P, P, P, P],
     'eve_stream_state_rows_at': [I, I, I, L, L, L, L, P, P, P, P],
     'eve_screen_u8_area_to_nchw': [L, I, I, I, P, I, I, P, P],
+    'eve_eye_warp_u8_to_nchw': [L, I, I, I, P, P, I, I, P, P],
+    'eve_eye_warp_u8_to_stem': [I, L, I, I, I, P, P, I, I, P, P],
 }
 EXPORTS = sorted(list(SIGNATURES) + ['eve_abi_version', 'eve_last_error', 'eve_last_kernel'])
 

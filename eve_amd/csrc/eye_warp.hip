@@ -1,0 +1,159 @@
+// Live camera frames on the device: the two eye patches cut from whole uint8 N x IH x IW x C frames (C = 3 or 4, a fourth channel
+// ignored) through one 3 x 3 homography per frame, sampled bilinearly and normalised as the reference normalises its pre-cut
+// patches (datasources/eve_sequences.py:196-203).  The contract is in include/eve_hip.h (eve_eye_warp_u8_to_nchw) and in numpy in
+// tests/eye_warp_ref.py; in short, for output pixel (oy, ox) of patch n with matrix m = warps[n] (patch pixel -> camera pixel):
+//   X = (m00*ox + m01*oy) + m02,  Y = (m10*ox + m11*oy) + m12,  Wd = (m20*ox + m21*oy) + m22     in float64
+//   u = X / Wd, v = Y / Wd                                      correctly rounded float64 divisions
+//   inside  iff  Wd > 0 && u > -1 && u < IW && v > -1 && v < IH                   (a NaN fails every comparison)
+//   fu = floor(u*256 + 0.5), x0 = fu >> 8, ax = fu & 255; the same for v          8 fractional bits per axis
+//   S  = (256-ax)(256-ay) p00 + ax(256-ay) p01 + (256-ax)ay p10 + ax ay p11       taps outside the frame read 0; S = 0 outside
+//   out = float(S) * 2^-16 * float(2/255) + (-1.0f)                               one rounded multiply, one rounded add
+// Every product m * o is exact in float64 (24 bits by at most 13), so a fused multiply-add changes nothing as long as the
+// association stays; the coordinate of a pixel is computed from (oy, ox) alone, never stepped along the row.
+//
+// The kernel is a gather stream: a 128 x 128 patch touches 12 bytes per output pixel and channel triple, 197 KB of loads for
+// 196 KB (float) or 147 KB (packed) of stores, out of a frame region the L2 holds.  A workgroup takes one (patch, band of EW_BAND
+// output rows) at a time with its lanes along ox: neighbouring lanes read neighbouring source bytes (as far as the warp keeps
+// neighbours together) and their stores are consecutive -- 4 bytes per lane and plane for the float form, one 8-byte pixel per
+// lane for the stem's packed form, whose rows include the pad ring, written as zeros by the same loop.  The nine matrix entries
+// are uniform over the workgroup.  The taps are single-byte loads, so `frames` needs no alignment.
+#include "common.h"
+
+namespace eve {
+namespace {
+
+constexpr int EW_THREADS = 256;
+constexpr int EW_BAND = 2;               // output rows per item: 256 lanes cover two rows of a 128-wide patch
+constexpr int EW_MAX_BLOCKS = 1024;      // (patch, band) items beyond that are taken in a grid-stride loop
+constexpr int EW_MAX_FRAME = 16384;      // IH, IW: the fixed-point coordinate stays below 2^22
+constexpr int EW_MAX_PATCH = 4096;       // OH, OW: m * o is exact in float64 with room to spare
+
+struct EyeWarpArgs {
+    long long items;                     // N * bands
+    int bands;                           // bands per patch
+    int IH, IW, C, OH, OW;
+};
+
+// the three channels' fixed-point sums S (<= 255 * 65536) of output pixel (oy, ox); all zero outside
+__device__ __forceinline__ void warp_sums(const double (&m)[9], const uint8_t* __restrict__ frame, const int IH, const int IW, const int C,
+                                          const int oy, const int ox, uint32_t (&S)[3]) {
+#pragma clang fp contract(off)
+    const double dx = (double)ox, dy = (double)oy;
+    const double X = (m[0] * dx + m[1] * dy) + m[2];
+    const double Y = (m[3] * dx + m[4] * dy) + m[5];
+    const double Wd = (m[6] * dx + m[7] * dy) + m[8];
+    const double u = X / Wd, v = Y / Wd;
+    S[0] = S[1] = S[2] = 0u;
+    if (!(Wd > 0.0 && u > -1.0 && u < (double)IW && v > -1.0 && v < (double)IH)) return;
+    const int fu = (int)floor(u * 256.0 + 0.5), fv = (int)floor(v * 256.0 + 0.5);      // in [-256, 256 * 16384]
+    const int x0 = fu >> 8, y0 = fv >> 8;                                              // in [-1, IW] / [-1, IH]
+    const uint32_t ax = (uint32_t)(fu & 255), ay = (uint32_t)(fv & 255);
+    const uint32_t w[4] = {(256u - ax) * (256u - ay), ax * (256u - ay), (256u - ax) * ay, ax * ay};
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int y = y0 + (t >> 1), x = x0 + (t & 1);
+        if (y >= 0 && y < IH && x >= 0 && x < IW) {
+            const uint8_t* p = frame + ((size_t)y * IW + x) * C;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) S[c] += w[t] * (uint32_t)p[c];
+        }
+    }
+}
+
+__device__ __forceinline__ float warp_value(uint32_t S) {
+#pragma clang fp contract(off)          // as normalise_u8 (stem_conv.hip): the multiply and the add round separately
+    const float val = (float)S * 0x1p-16f;                  // exact: S < 2^24
+    const float f = val * (float)(2.0 / 255.0);
+    return f + (-1.0f);
+}
+
+// O = float: dst is float [N][3][OH][OW].  O = bf16_t / f16_t: dst is the stem's packed [N][OH+6][OW+8][4], pixel at (y+3, x+4).
+template <typename O>
+__global__ __launch_bounds__(EW_THREADS) void eye_warp_u8_kernel(const EyeWarpArgs a, const uint8_t* __restrict__ src,
+                                                                 const float* __restrict__ warps, void* __restrict__ dst) {
+    constexpr bool PACKED = !std::is_same<O, float>::value;
+    const int rows = PACKED ? a.OH + 6 : a.OH, cols = PACKED ? a.OW + 8 : a.OW;      // of the output image, pad ring included
+    for (long long item = blockIdx.x; item < a.items; item += gridDim.x) {
+        const long long n = item / a.bands;
+        const int r0 = (int)(item - n * a.bands) * EW_BAND;
+        const int nr = rows - r0 < EW_BAND ? rows - r0 : EW_BAND;
+        double m[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) m[i] = (double)warps[n * 9 + i];
+        const uint8_t* frame = src + (size_t)n * a.IH * a.IW * a.C;
+        for (int t = threadIdx.x; t < nr * cols; t += EW_THREADS) {
+            const int r = r0 + t / cols, col = t % cols;
+            const int oy = PACKED ? r - 3 : r, ox = PACKED ? col - 4 : col;
+            const bool pixel = !PACKED || (oy >= 0 && oy < a.OH && ox >= 0 && ox < a.OW);
+            uint32_t S[3] = {0u, 0u, 0u};
+            if (pixel) warp_sums(m, frame, a.IH, a.IW, a.C, oy, ox, S);
+            if constexpr (PACKED) {
+                uint2 q = make_uint2(0u, 0u);
+                if (pixel) {
+                    q.x = Elem<O>::pack2(warp_value(S[0]), warp_value(S[1]));
+                    q.y = Elem<O>::pack2(warp_value(S[2]), 0.f);
+                }
+                reinterpret_cast<uint2*>(dst)[((size_t)n * rows + r) * cols + col] = q;
+            } else {
+                float* out = reinterpret_cast<float*>(dst) + ((size_t)n * 3 * rows + r) * cols + col;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) out[(size_t)c * rows * cols] = warp_value(S[c]);
+            }
+        }
+    }
+}
+
+// the checks both entry points share; -> nullptr or what is wrong
+const char* eye_warp_refusal(long long N, int IH, int IW, int C, const void* frames, const void* warps, int OH, int OW, const void* dst) {
+    if (N <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0 || !frames || !warps || !dst) return "bad arguments";
+    if (C != 3 && C != 4) return "C must be 3 or 4 (a fourth channel is ignored)";
+    if (IH > EW_MAX_FRAME || IW > EW_MAX_FRAME) return "frame too large (IH and IW <= 16384)";
+    if (OH > EW_MAX_PATCH || OW > EW_MAX_PATCH) return "patch too large (OH and OW <= 4096)";
+    if (N > (long long)0x7fffffff / (OH + 6)) return "N * (OH + 6) must fit 31 bits";
+    return nullptr;
+}
+
+EyeWarpArgs eye_warp_args(long long N, int IH, int IW, int C, int OH, int OW, int rows) {
+    EyeWarpArgs a;
+    a.bands = (rows + EW_BAND - 1) / EW_BAND;
+    a.items = N * a.bands;
+    a.IH = IH; a.IW = IW; a.C = C; a.OH = OH; a.OW = OW;
+    return a;
+}
+
+}  // namespace
+}  // namespace eve
+
+using namespace eve;
+
+extern "C" int eve_eye_warp_u8_to_nchw(long long N, int IH, int IW, int C, const uint8_t* frames_nhwc, const float* warps, int OH, int OW,
+                                       float* dst_nchw, eve_stream_t stream) {
+    char msg[128];
+    if (const char* why = eye_warp_refusal(N, IH, IW, C, frames_nhwc, warps, OH, OW, dst_nchw)) {
+        snprintf(msg, sizeof(msg), "eye_warp_u8_to_nchw: %s", why);
+        return set_error_msg(msg);
+    }
+    const EyeWarpArgs a = eye_warp_args(N, IH, IW, C, OH, OW, OH);
+    const dim3 grid((unsigned)(a.items < EW_MAX_BLOCKS ? a.items : EW_MAX_BLOCKS));
+    EVE_LAUNCH("eye_warp_u8_kernel<float>", eye_warp_u8_kernel<float>, grid, dim3(EW_THREADS), 0, (hipStream_t)stream, a, frames_nhwc, warps,
+               (void*)dst_nchw);
+    EVE_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int eve_eye_warp_u8_to_stem(int dtype, long long N, int IH, int IW, int C, const uint8_t* frames_nhwc, const float* warps, int OH,
+                                       int OW, void* x_padded, eve_stream_t stream) {
+    char msg[128];
+    const char* why = eye_warp_refusal(N, IH, IW, C, frames_nhwc, warps, OH, OW, x_padded);
+    if (!why && dtype != EVE_DT_BF16 && dtype != EVE_DT_F16) why = "dtype must be bf16 or f16 (the stem's packed input)";
+    if (why) {
+        snprintf(msg, sizeof(msg), "eye_warp_u8_to_stem: %s", why);
+        return set_error_msg(msg);
+    }
+    const EyeWarpArgs a = eye_warp_args(N, IH, IW, C, OH, OW, OH + 6);
+    const dim3 grid((unsigned)(a.items < EW_MAX_BLOCKS ? a.items : EW_MAX_BLOCKS));
+    EVE_DISPATCH_H16(dtype, EVE_LAUNCH(EVE_HNAME(H, "eye_warp_u8_kernel<", ">"), eye_warp_u8_kernel<H>, grid, dim3(EW_THREADS), 0,
+                                       (hipStream_t)stream, a, frames_nhwc, warps, x_padded));
+    EVE_CHECK_LAUNCH();
+    return 0;
+}

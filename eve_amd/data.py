@@ -11,6 +11,9 @@ uint8 frames is 4x less PCIe traffic, and the float values produced here are bit
   preprocess_screen_frames(u8, size=(H, W))
                                  [..., IH, IW, 3|4] uint8 of any size >= (H, W), e.g. a 1920 x 1080 capture -> [..., 3, H, W]
                                  float32 in [0, 1] by exact area averaging (RefineNet passes its screen_size for uint8 screens)
+  warp_eye_patches(u8, warps)    whole camera frames [..., IH, IW, 3|4] uint8 and per-frame homographies [..., 3, 3] float32
+                                 (patch pixel -> camera pixel) -> one eye's patches [..., 3, H, W] float32 in [-1, 1], cut
+                                 bilinearly on the device (EyeNet / EVE / EVEStream take `camera_frame` + `<side>_eye_warp`)
   EyeNet.forward_sequence / RefineNet.forward_sequence / EVE accept the uint8 tensors directly (eye patches go straight
   into the stem kernel's packed bf16 layout, no float tensor is ever materialised).
   DevicePrefetcher(iterable)     pinned double-buffered H2D on a side stream
@@ -49,6 +52,35 @@ def preprocess_screen_frames(frames, size=None):
         out = default_kernels().frames_u8_to_nchw(flat, SCREEN_SCALE, None)
     else:
         out = default_kernels().screen_u8_area_to_nchw(flat, (int(size[0]), int(size[1])))
+    return out.view(lead + tuple(out.shape[1:]))
+
+
+def eye_patch_hw(config=None):
+    """(H, W) of an eye patch: the config's eyes_size is (W, H), like screen_size."""
+    if config is None:
+        from .config import get_config
+        config = get_config()
+    return int(config.eyes_size[1]), int(config.eyes_size[0])
+
+
+def warp_eye_patches(frames, warps, size=None):
+    """One eye's patches cut from whole camera frames on the device, in place of two cv2.warpPerspective calls per frame on the
+    host: frames uint8 [..., IH, IW, 3 | 4] (a fourth channel ignored, the channel order kept), warps float32 [..., 3, 3] with the
+    same leading dimensions -> float32 [..., 3, H, W] in [-1, 1], the values preprocess_frames gives for the cut patch.  size:
+    (H, W), default the config's eyes_size.
+
+    warps[i] maps a PATCH pixel (x, y, 1) to a CAMERA pixel (X / Wd, Y / Wd) -- the matrix cv2.warpPerspective uses with
+    WARP_INVERSE_MAP.  The EVE pipeline's perspective-normalisation matrix W maps the camera to the patch
+    (cv2.warpPerspective(frame, W, (w, h))): pass inv(W).  Sampling is bilinear with 8 fractional bits per axis and zero outside
+    the frame (which comes out as -1.0), bit-exact by the contract of include/eve_hip.h eve_eye_warp_u8_to_nchw."""
+    flat, lead = _fold(frames)
+    if not torch.is_tensor(warps) or warps.dtype != torch.float32 or tuple(warps.shape) != lead + (3, 3):
+        raise TypeError('expected float32 warps shaped %s, got %s %s' % (lead + (3, 3), getattr(warps, 'dtype', type(warps)),
+                                                                         tuple(getattr(warps, 'shape', ()))))
+    if flat.shape[3] not in (3, 4):
+        raise TypeError('expected camera frames with 3 or 4 channels, got %d' % flat.shape[3])
+    hw = eye_patch_hw() if size is None else (int(size[0]), int(size[1]))
+    out = default_kernels().eye_warp_u8_to_nchw(flat, warps.reshape(-1, 3, 3).contiguous(), hw)
     return out.view(lead + tuple(out.shape[1:]))
 
 

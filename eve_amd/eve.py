@@ -23,7 +23,7 @@ import torch.nn as nn
 
 from . import losses, ops
 from .config import get_config
-from .eye_net import EyeNet
+from .eye_net import EyeNet, eye_input
 from .kernels import default_kernels
 
 
@@ -227,7 +227,7 @@ class EVE(nn.Module):
             full_input_dict = next(iter(full_input_dict.values()))
         d = full_input_dict
         self.calculate_additional_labels(d, current_epoch=current_epoch)
-        B, T = d['left_eye_patch'].shape[:2]
+        B, T = eye_input(d).shape[:2]
 
         inter = dict(self.eye_net.forward_sequence(d))                # eve.py:105-111 for every t
         if self.training and cfg.refine_net_do_offset_augmentation:   # eve.py:114-135
@@ -272,7 +272,7 @@ class EVE(nn.Module):
                     output_dict[key] = inter[key]
 
         self.calculate_losses_and_metrics(d, inter, output_dict)
-        output_dict['full_loss'] = self._full_loss(output_dict, d['left_eye_patch'].device)
+        output_dict['full_loss'] = self._full_loss(output_dict, eye_input(d).device)
 
         if create_images:                                             # eve.py:268-283
             if cfg.load_screen_content:
@@ -314,7 +314,7 @@ class EVE(nn.Module):
         _pog_block / _final_block as forward().  -> the PREDICTION_KEYS present (the PoG keys need the camera geometry), plus
         heatmap_final when asked."""
         assert not self.training, 'EVE._predict_sequence is eval-only'
-        B = d['left_eye_patch'].shape[0]
+        B = eye_input(d).shape[0]
         d = dict(d)
         if 'left_o' in d:
             d['o'] = _mean2(d['left_o'], d['right_o'])

@@ -36,6 +36,36 @@ def _wants_grad(t):
     return torch.is_grad_enabled() and t.dtype.is_floating_point and t.requires_grad
 
 
+EYE_PATCH_KEYS = ('left_eye_patch', 'right_eye_patch')
+EYE_CAMERA_KEYS = ('camera_frame', 'left_eye_warp', 'right_eye_warp')
+
+
+def eye_input(batch):
+    """The tensor that carries a batch's [B, T] and its device: left_eye_patch, or camera_frame when the eyes come as whole
+    camera frames plus per-eye homographies.  Raises on a batch that holds both forms, half of one, or tensors of the wrong
+    dtype or shape for the camera form."""
+    has_patch = [k_ for k_ in EYE_PATCH_KEYS if k_ in batch]
+    has_cam = [k_ for k_ in EYE_CAMERA_KEYS if k_ in batch]
+    if has_patch and has_cam:
+        raise ValueError('give the eyes either as %s or as %s, not both (found %s)' % (
+            ' / '.join(EYE_PATCH_KEYS), ' / '.join(EYE_CAMERA_KEYS), ', '.join(has_patch + has_cam)))
+    if not has_cam:
+        return batch['left_eye_patch']
+    if len(has_cam) != len(EYE_CAMERA_KEYS):
+        raise ValueError('the camera form needs %s: missing %s' % (
+            ', '.join(EYE_CAMERA_KEYS), ', '.join(k_ for k_ in EYE_CAMERA_KEYS if k_ not in batch)))
+    frames = batch['camera_frame']
+    if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[4] not in (3, 4):
+        raise TypeError('camera_frame must be uint8 [B, T, IH, IW, 3 | 4], got %s %s' % (
+            getattr(frames, 'dtype', type(frames)), tuple(getattr(frames, 'shape', ()))))
+    for k_ in EYE_CAMERA_KEYS[1:]:
+        w = batch[k_]
+        if not torch.is_tensor(w) or w.dtype != torch.float32 or tuple(w.shape) != tuple(frames.shape[:2]) + (3, 3):
+            raise TypeError('%s must be float32 %s, got %s %s' % (k_, tuple(frames.shape[:2]) + (3, 3), getattr(w, 'dtype', type(w)),
+                                                                   tuple(getattr(w, 'shape', ()))))
+    return frames
+
+
 def default_compute_dtype():
     name = os.environ.get('EVE_AMD_DTYPE', 'fp32').lower()
     if name in ('bf16', 'bfloat16'):
@@ -268,7 +298,7 @@ class EyeNet(nn.Module):
         if not (on and hasattr(k, 'tail_outputs_fwd') and torch.is_grad_enabled() and cfg.eye_net_use_rnn and
                 cfg.eye_net_rnn_type == 'GRU' and len(self.rnn_cells) == 1 and cfg.eye_net_use_head_pose_input and
                 not cfg.eye_net_frozen and self.rnn_cells[0].hidden_size == 128 and self.fc_common[0].in_features == 130 and
-                self.cnn_layers.fc.in_features == 512 and T <= 256 and batch['left_eye_patch'].is_cuda and
+                self.cnn_layers.fc.in_features == 512 and T <= 256 and eye_input(batch).is_cuda and
                 batch['left_g_tobii'].dtype == torch.float32 and batch['left_h'].dtype == torch.float32):
             return False
         return all(ops._direct_grad_ok(p_) for p_ in ops.EyeTailLossFn.tail_parameters(self))
@@ -333,7 +363,10 @@ class EyeNet(nn.Module):
 
     # ------------------------------------------------------------------ whole clips, both eyes, one pass
     def forward_sequence(self, batch, initial_states=None):
-        """batch: {left,right}_eye_patch [B, T, 3, H, W] float, {left,right}_h [B, T, 2].
+        """batch: {left,right}_eye_patch [B, T, 3, H, W] float (or uint8 [B, T, H, W, C] decoded frames), {left,right}_h [B, T, 2].
+        In place of the two patch keys the batch may hold whole camera frames, camera_frame uint8 [B, T, IH, IW, 3 | 4], and
+        {left,right}_eye_warp float32 [B, T, 3, 3], the homographies from a patch pixel to a camera pixel (data.warp_eye_patches):
+        the patches, of the config's eyes_size, are then cut on the device.
         Returns the B x T x ... tensors eve.py:174-182 would stack: <side>_g_initial [B,T,2],
         <side>_pupil_size [B,T], <side>_eye_rnn_states_<i> [B,T,H] per cell ((h, c) pair of them for LSTM).
         initial_states: {side: h [B,H]} or {side: [per-cell h | (h, c) | None]}."""
@@ -345,9 +378,27 @@ class EyeNet(nn.Module):
         """Both eyes' clips through the trunk: -> feats [2*B*T, 512] float32 (left clips' frames, then the right ones'), B, T."""
         k = default_kernels()
         dt = self.compute_dtype
-        left, right = batch['left_eye_patch'], batch['right_eye_patch']
         x = x_padded = None
-        if left.dtype == torch.uint8:
+        if eye_input(batch) is batch.get('camera_frame'):
+            # whole camera frames and one homography per eye and frame: cut, normalise and lay out in one launch per eye --
+            # straight into the stem's packed layout where the uint8 patches below go there, else to float NCHW patches
+            from . import data
+            frames = batch['camera_frame']
+            B, T, IH, IW, Cc = frames.shape
+            (Hh, Ww), C = data.eye_patch_hw(self.config), 3
+            flat = frames.reshape(B * T, IH, IW, Cc).contiguous()
+            lw, rw = (batch[s_ + '_eye_warp'].reshape(B * T, 3, 3).contiguous() for s_ in ('left', 'right'))
+            if dt in HALF_DTYPES and Hh % 4 == 0 and Ww == 128:
+                x_padded = torch.empty((2 * B * T, Hh + 6, Ww + 8, 4), dtype=dt, device=frames.device)
+                k.eye_warp_u8_to_stem(flat, lw, (Hh, Ww), out=x_padded[:B * T])
+                k.eye_warp_u8_to_stem(flat, rw, (Hh, Ww), out=x_padded[B * T:])
+                left = right = flat                 # (no float patches: nothing below reads them)
+            else:
+                left = k.eye_warp_u8_to_nchw(flat, lw, (Hh, Ww)).view(B, T, C, Hh, Ww)
+                right = k.eye_warp_u8_to_nchw(flat, rw, (Hh, Ww)).view(B, T, C, Hh, Ww)
+        else:
+            left, right = batch['left_eye_patch'], batch['right_eye_patch']
+        if x_padded is None and left.dtype == torch.uint8:
             # decoded frames [B, T, H, W, C] (eve_sequences.py:196-203 not applied yet): normalise on the device --
             # straight into the stem's packed layout when the fused stem takes it, else to the reference's float NCHW
             from . import data

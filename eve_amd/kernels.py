@@ -424,6 +424,42 @@ class HipKernels(object):
         self._ck(self.lib.eve_frames_u8_to_stem(dt_code(dst.dtype), N, C, H, W, self._p(frames), float(scale), float(shift), self._p(dst), self._stream()))
         return dst
 
+    @staticmethod
+    def _eye_warp_args(frames, warps, out_hw):
+        """The checks of the two eye_warp_u8_* calls -> (N, IH, IW, C, OH, OW)."""
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] not in (3, 4):
+            raise TypeError('eye_warp: frames must be uint8 [N, IH, IW, 3 | 4], got %s %s' % (frames.dtype, tuple(frames.shape)))
+        N, IH, IW, C = frames.shape
+        if warps.dtype != torch.float32 or tuple(warps.shape) != (N, 3, 3):
+            raise TypeError('eye_warp: warps must be float32 [%d, 3, 3], got %s %s' % (N, warps.dtype, tuple(warps.shape)))
+        if not (frames.is_contiguous() and warps.is_contiguous()):
+            raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        if warps.device != frames.device:
+            raise RuntimeError('eye_warp: frames and warps are on different devices')
+        OH, OW = int(out_hw[0]), int(out_hw[1])
+        return N, IH, IW, C, OH, OW
+
+    def eye_warp_u8_to_nchw(self, frames, warps, out_hw):
+        """Whole uint8 camera frames [N,IH,IW,C] (C 3 or 4, a fourth channel ignored, channel order kept) and one homography per
+        frame, float32 [N,3,3] mapping a patch pixel to a camera pixel (cv2.warpPerspective's WARP_INVERSE_MAP matrix: inv(W) of
+        the normalisation matrix W) -> the eye patches, float32 [N,3,OH,OW] in [-1, 1]: bilinear with 8 fractional bits, zero
+        outside the frame, normalised as preprocess_frames normalises (include/eve_hip.h eve_eye_warp_u8_to_nchw)."""
+        N, IH, IW, C, OH, OW = self._eye_warp_args(frames, warps, out_hw)
+        out = torch.empty((N, 3, OH, OW), dtype=torch.float32, device=frames.device)
+        self._ck(self.lib.eve_eye_warp_u8_to_nchw(N, IH, IW, C, self._p(frames), self._p(warps), OH, OW, self._p(out), self._stream()))
+        return out
+
+    def eye_warp_u8_to_stem(self, frames, warps, out_hw, out=None, dtype=torch.bfloat16):
+        """The same patches straight into the stem's packed 16-bit input [N,OH+6,OW+8,4] (what frames_u8_to_stem writes from
+        pre-cut patches): the pad ring and the fourth channel zero."""
+        N, IH, IW, C, OH, OW = self._eye_warp_args(frames, warps, out_hw)
+        dst = out if out is not None else torch.empty((N, OH + 6, OW + 8, 4), dtype=dtype, device=frames.device)
+        if tuple(dst.shape) != (N, OH + 6, OW + 8, 4) or dst.dtype not in HALF_DTYPES:
+            raise TypeError('eye_warp: out must be bf16 / f16 [%d, %d, %d, 4], got %s %s' % (N, OH + 6, OW + 8, dst.dtype, tuple(dst.shape)))
+        self._ck(self.lib.eve_eye_warp_u8_to_stem(dt_code(dst.dtype), N, IH, IW, C, self._p(frames), self._p(warps), OH, OW, self._p(dst),
+                                                  self._stream()))
+        return dst
+
     # ------------------------------------------------------------------ gaze geometry / heat-maps / soft-argmax
     def _flat32(self, t, shape, what):
         t = t.contiguous()

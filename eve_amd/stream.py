@@ -30,6 +30,7 @@ kernel) need invalidate(), as the modules need invalidate_packs().
 import numpy as np
 import torch
 
+from .eye_net import eye_input
 from .kernels import default_kernels
 
 _WARMUP_STREAMS = {}
@@ -158,12 +159,20 @@ class EVEStream(object):
                                             lengths=self._lengths)
 
     def step(self, chunk, return_heatmaps=False, lengths=None):
-        """One chunk of every stream: chunk holds [B, Tc, ...] tensors on the model's device -- the eye patches (float NCHW or
-        uint8 NHWC), {left,right}_h, {left,right}_o, {left,right}_R, head_R, camera_transformation, inv_camera_transformation,
-        pixels_per_millimeter, millimeters_per_pixel, and screen_frame when the config loads screen content.  Returns the
+        """One chunk of every stream: chunk holds [B, Tc, ...] tensors on the model's device -- the eyes (below), {left,right}_h,
+        {left,right}_o, {left,right}_R, head_R, camera_transformation, inv_camera_transformation, pixels_per_millimeter, millimeters_per_pixel, and screen_frame when the config loads screen content.  Returns the
         prediction keys of EVE(output_predictions=True) as [B, Tc, ...] tensors (heatmap_final [B, Tc, 1, H, W] on request).
         With use_graph the returned tensors are the graph's output buffers: valid until the next step() of the same chunk
         shape (clone what you keep).  The host does not wait for the device, except when a new chunk shape is captured.
+
+        The eyes come as left_eye_patch / right_eye_patch (float NCHW [B, Tc, 3, H, W] or uint8 NHWC [B, Tc, H, W, C], cut
+        beforehand), or as what a live camera and a face tracker deliver: camera_frame, uint8 [B, Tc, IH, IW, 3 | 4] whole frames
+        up to 16384 x 16384 (a fourth channel ignored, the channel order kept), plus left_eye_warp and right_eye_warp, float32
+        [B, Tc, 3, 3]: per frame and eye the homography from a patch pixel to a camera pixel -- cv2.warpPerspective's
+        WARP_INVERSE_MAP matrix, inv(W) of the perspective-normalisation matrix W.  The patches (the config's eyes_size) are then
+        cut by eve_eye_warp_u8_to_stem / _to_nchw inside the step and inside the captured graph: the frames and the matrices are
+        copied into the graph's input buffers like every other tensor of the chunk, and their shapes and dtypes are part of the
+        graph's key.  A chunk holds one form, not both.
 
         screen_frame is float [B, Tc, 3, H, W] at the configured screen size, uint8 [B, Tc, H, W, 3] at that size, or a live
         capture as it comes off the desktop: uint8 [B, Tc, IH, IW, 3 | 4] at any resolution from the screen size up to 16 843 009
@@ -179,11 +188,11 @@ class EVEStream(object):
         the step costs what a full chunk of this shape costs."""
         if self.model.training:
             raise ValueError('EVEStream runs inference only: the model was switched to training mode')
-        if chunk['left_eye_patch'].shape[0] != self.num_streams:
-            raise ValueError('chunk has %d streams, the EVEStream %d' % (chunk['left_eye_patch'].shape[0], self.num_streams))
+        B, Tc = eye_input(chunk).shape[:2]
+        if B != self.num_streams:
+            raise ValueError('chunk has %d streams, the EVEStream %d' % (B, self.num_streams))
         ragged = lengths is not None
         if ragged:
-            Tc = chunk['left_eye_patch'].shape[1]
             self._upload_lengths(self._host_lengths(lengths, Tc))
         self._upload_resets()
         with torch.no_grad():

@@ -694,6 +694,33 @@ int eve_stream_state_rows_at(int dtype, int S, int T, long long row_elems, long 
  * 16 843 009 (covers 3840 x 2160; beyond it S could exceed 32 bits), IW * C > 40 960 bytes (one row of sums is kept in LDS). */
 int eve_screen_u8_area_to_nchw(long long N, int IH, int IW, int C, const uint8_t* src_nhwc, int OH, int OW, float* dst_nchw,
                                eve_stream_t stream);
+/* Live camera frames: one eye patch per call cut from whole uint8 frames [N][IH][IW][C] (C = 3, or 4 with the fourth channel
+ * ignored; the channel order is kept; IH, IW <= 16384) through a per-frame homography warps [N][3][3] float, row-major m, that
+ * maps a PATCH pixel to a CAMERA pixel -- the matrix cv2.warpPerspective takes with WARP_INVERSE_MAP; a caller who holds the
+ * perspective-normalisation matrix W (camera -> patch) passes inv(W).  Integer coordinates are pixel centres; the patch is
+ * OH x OW, both <= 4096.  The reference reads such patches pre-cut from *_eyes.mp4 and normalises them on the host
+ * (datasources/eve_sequences.py:196-203); its config names whole frames (camera_frame_type = 'full') but no model-side code
+ * consumes them.  Contract, bit-exact, for output pixel (oy, ox):
+ *   X  = (m00*ox + m01*oy) + m02      Y = (m10*ox + m11*oy) + m12      Wd = (m20*ox + m21*oy) + m22        in float64
+ *        (each product of a float and an integer <= 4096 is exact in float64, so fused multiply-adds give the same bits; only
+ *        this association must be kept, and the coordinate is never stepped incrementally along a row)
+ *   u = X / Wd, v = Y / Wd            the correctly rounded float64 division
+ *   inside iff Wd > 0 && u > -1 && u < IW && v > -1 && v < IH       tested in float64 before any conversion to an integer; a
+ *        NaN makes its comparison false, so such a pixel is outside
+ *   fu = floor(u*256 + 0.5), x0 = fu >> 8, ax = fu & 255;  fv, y0, ay the same from v
+ *   taps p00 = (y0, x0), p01 = (y0, x0+1), p10 = (y0+1, x0), p11 = (y0+1, x0+1); a tap outside [0, IH) x [0, IW) reads 0
+ *   S = (256-ax)(256-ay) p00 + ax(256-ay) p01 + (256-ax)ay p10 + ax ay p11      an integer <= 255 * 65536 < 2^24; 0 outside
+ *   value = (float(S) * 2^-16) * float(2/255) + (-1.0f)             the first product exact, then one rounded multiply and one
+ *        rounded add with no contraction: eve_frames_u8_to_nchw(scale 2/255, shift -1) on the sample
+ * Hence an integer translation gives eve_frames_u8_to_nchw / _to_stem's bits on the crop, and everything outside the frame is
+ * -1.0.  eve_eye_warp_u8_to_nchw writes dst [N][3][OH][OW] float; eve_eye_warp_u8_to_stem the stem kernels' packed
+ * x_padded [N][OH+6][OW+8][4] bf16 / f16 (pixel at (y+3, x+4), the pad ring and the fourth channel zero, values rounded to
+ * nearest even as eve_stem_pack_input rounds).  No alignment is asked of `frames`.  Refused without a launch: a null pointer,
+ * N < 1, C other than 3 or 4, IH or IW > 16384, OH or OW > 4096, a dtype other than bf16 / f16 for the packed form.        */
+int eve_eye_warp_u8_to_nchw(long long N, int IH, int IW, int C, const uint8_t* frames_nhwc, const float* warps, int OH, int OW,
+                            float* dst_nchw, eve_stream_t stream);
+int eve_eye_warp_u8_to_stem(int dtype /* EVE_DT_BF16 | EVE_DT_F16 */, long long N, int IH, int IW, int C, const uint8_t* frames_nhwc,
+                            const float* warps, int OH, int OW, void* x_padded, eve_stream_t stream);
 
 #ifdef __cplusplus
 }

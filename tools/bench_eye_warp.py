@@ -1,0 +1,178 @@
+#!/usr/bin/env python
+"""Device time of the eye-patch warp (eve_eye_warp_u8_to_nchw / _to_stem, csrc/eye_warp.hip) next to the launch it stands in for,
+and of one EVEStream step fed whole camera frames next to the same step fed pre-cut uint8 patches.
+
+    python tools/bench_eye_warp.py [--patches 64] [--size 1920x1080] [--iters 500] [--rounds 5] [--shapes 1x1 8x4 32x2]
+                                   [--steps 50] [--dtype bf16] [--markdown profiles/table.md]
+
+Part 1, per launch, the four routes interleaved in one process (the median over the rounds of events around `iters` calls):
+    warp_nchw / warp_stem   N patches of 128 x 128 cut from N frames of the given size, each by its own rotated, scaled warp with a
+                            perspective row; float NCHW and the stem's packed bf16
+    crop_nchw / crop_stem   eve_frames_u8_to_nchw / _to_stem on N pre-cut 128 x 128 x 3 patches: what the caller launched before,
+                            after two cv2.warpPerspective calls per frame on the host and a second upload (neither is timed here)
+The rate quoted for a warp is (bytes its loads ask for: 4 taps x 3 channels per output pixel) + (bytes stored) over the time; the
+taps overlap, so the distinct bytes behind them are about a quarter -- it is a rate of the kernel's traffic, not of HBM.
+
+Part 2, per EVEStream step under graph replay (refine_net config): `camera` feeds camera_frame + two warps per frame, `patches`
+the uint8 [B, Tc, 128, 128, 3] patch pair.  The camera step also copies B * Tc whole frames into the graph's input buffer."""
+import argparse
+import json
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+import eve_amd  # noqa: E402
+from eve_amd import synthetic as detweights  # noqa: E402
+from eve_amd.kernels import default_kernels  # noqa: E402
+
+HW = (128, 128)
+DTYPES = {'fp32': torch.float32, 'bf16': torch.bfloat16, 'fp16': torch.float16}
+STREAM_KEYS = ('left_h', 'right_h', 'left_o', 'right_o', 'left_R', 'right_R', 'head_R', 'camera_transformation',
+               'inv_camera_transformation', 'pixels_per_millimeter', 'millimeters_per_pixel', 'screen_frame')
+
+
+def device_ms(fn, iters):
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(iters):
+        fn()
+    end.record()
+    torch.cuda.synchronize()
+    return start.elapsed_time(end) / iters
+
+
+def warps_for(n, IH, IW, seed):
+    """n homographies (patch pixel -> camera pixel) that keep a 128 x 128 patch inside an IH x IW frame."""
+    g = np.random.default_rng(seed)
+    ms = []
+    for _ in range(n):
+        s, a = g.uniform(1.0, 1.5), math.radians(g.uniform(-15, 15))
+        c, d = s * math.cos(a), s * math.sin(a)
+        ms.append([[c, -d, g.uniform(80, IW - 320)], [d, c, g.uniform(80, IH - 320)], [g.uniform(-1e-4, 1e-4), g.uniform(-1e-4, 1e-4), 1.0]])
+    return torch.tensor(np.array(ms), dtype=torch.float32)
+
+
+def median(v):
+    return sorted(v)[len(v) // 2]
+
+
+def launches(args, IH, IW):
+    k = default_kernels()
+    N = args.patches
+    torch.manual_seed(N)
+    frames = torch.randint(0, 256, (N, IH, IW, 3), dtype=torch.uint8, device='cuda')
+    warps = warps_for(N, IH, IW, seed=N).cuda()
+    crops = torch.randint(0, 256, (N,) + HW + (3,), dtype=torch.uint8, device='cuda')
+    packed = torch.empty((N, HW[0] + 6, HW[1] + 8, 4), dtype=torch.bfloat16, device='cuda')
+    routes = {'warp_nchw': lambda: k.eye_warp_u8_to_nchw(frames, warps, HW),
+              'warp_stem': lambda: k.eye_warp_u8_to_stem(frames, warps, HW, out=packed),
+              'crop_nchw': lambda: k.frames_u8_to_nchw(crops, 2.0 / 255.0, -1.0),
+              'crop_stem': lambda: k.frames_u8_to_stem(crops, 2.0 / 255.0, -1.0, out=packed)}
+    for fn in routes.values():                   # warm up: code objects, allocator
+        for _ in range(5):
+            fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name in routes}
+    for _ in range(args.rounds):
+        for name, fn in routes.items():
+            times[name].append(device_ms(fn, args.iters))
+    pixels = N * HW[0] * HW[1]
+    stored = {'nchw': pixels * 3 * 4, 'stem': packed.numel() * 2}
+    res = {'patches': N, 'frame': '%dx%d' % (IW, IH), 'patch': '%dx%d' % HW, 'iters': args.iters, 'rounds': args.rounds}
+    for name, t in times.items():
+        res[name + '_us'] = round(1e3 * median(t), 2)
+        res[name + '_us_min_max'] = [round(1e3 * min(t), 2), round(1e3 * max(t), 2)]
+    for form in ('nchw', 'stem'):
+        res['warp_%s_bytes' % form] = pixels * 12 + stored[form]
+        res['warp_%s_GBps' % form] = round(res['warp_%s_bytes' % form] / (1e-3 * median(times['warp_' + form])) / 1e9, 1)
+        res['crop_%s_bytes' % form] = pixels * 3 + stored[form]
+        res['crop_%s_GBps' % form] = round(res['crop_%s_bytes' % form] / (1e-3 * median(times['crop_' + form])) / 1e9, 1)
+    k.eye_warp_u8_to_stem(frames, warps, HW, out=packed)
+    res['kernel'] = k.lib.eve_last_kernel().decode()
+    return res
+
+
+def stream_steps(args, IH, IW):
+    cfg = eve_amd.reset_standalone_config()
+    cfg.import_json(os.path.join(REPO, 'configs', 'refine_net.json'))
+    cfg.import_dict({'eye_net_load_pretrained': False})
+    model = eve_amd.EVE(output_predictions=True)
+    model.eye_net.compute_dtype = model.refine_net.compute_dtype = DTYPES[args.dtype]
+    detweights.fill_module(model.eye_net, 0)
+    detweights.fill_module(model.refine_net, 1)
+    model = model.cuda().eval()
+    rows = []
+    for shape in args.shapes:
+        B, Tc = (int(v) for v in shape.split('x'))
+        small = detweights.eve_batch(min(B, 4), Tc, seed=1)
+        rest = {k_: torch.cat([small[k_]] * ((B + 3) // 4), dim=0)[:B].contiguous().cuda() for k_ in STREAM_KEYS if k_ in small}
+        g = torch.Generator().manual_seed(B * 1000 + Tc)
+        cam = dict(rest, camera_frame=torch.randint(0, 256, (B, Tc, IH, IW, 3), generator=g, dtype=torch.uint8).cuda(),
+                   left_eye_warp=warps_for(B * Tc, IH, IW, seed=B).view(B, Tc, 3, 3).cuda(),
+                   right_eye_warp=warps_for(B * Tc, IH, IW, seed=B + 1).view(B, Tc, 3, 3).cuda())
+        pat = dict(rest, left_eye_patch=torch.randint(0, 256, (B, Tc) + HW + (3,), generator=g, dtype=torch.uint8).cuda(),
+                   right_eye_patch=torch.randint(0, 256, (B, Tc) + HW + (3,), generator=g, dtype=torch.uint8).cuda())
+        streams = {'camera': (eve_amd.EVEStream(model, B), cam), 'patches': (eve_amd.EVEStream(model, B), pat)}
+        for s, chunk in streams.values():
+            for _ in range(3):
+                s.step(chunk)                    # capture + warm replays
+        torch.cuda.synchronize()
+        times = {name: [] for name in streams}
+        for _ in range(args.rounds):
+            for name, (s, chunk) in streams.items():
+                times[name].append(device_ms(lambda: s.step(chunk), args.steps))
+        res = {'B': B, 'Tc': Tc, 'dtype': args.dtype, 'frame': '%dx%d' % (IW, IH), 'steps': args.steps, 'rounds': args.rounds}
+        for name, t in times.items():
+            res[name + '_step_ms'] = round(median(t), 4)
+            res[name + '_step_ms_min_max'] = [round(min(t), 4), round(max(t), 4)]
+        res['camera_minus_patches_ms'] = round(res['camera_step_ms'] - res['patches_step_ms'], 4)
+        res['camera_frame_MB_copied'] = round(B * Tc * IH * IW * 3 / 1e6, 1)
+        rows.append(res)
+        print(json.dumps(res), flush=True)
+        del streams, cam, pat
+        torch.cuda.empty_cache()
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--patches', type=int, default=64)
+    ap.add_argument('--size', default='1920x1080', metavar='WxH')
+    ap.add_argument('--iters', type=int, default=500)
+    ap.add_argument('--rounds', type=int, default=5)
+    ap.add_argument('--shapes', nargs='*', default=['1x1', '8x4', '32x2'], help='EVEStream B x Tc shapes (none: skip part 2)')
+    ap.add_argument('--steps', type=int, default=50)
+    ap.add_argument('--dtype', default='bf16', choices=sorted(DTYPES))
+    ap.add_argument('--markdown', default=None, help='also write the tables to this file')
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit('bench_eye_warp: no GPU (a time is only measured on one)')
+    IW, IH = (int(v) for v in args.size.lower().split('x'))
+    with torch.no_grad():
+        one = launches(args, IH, IW)
+        print(json.dumps(one), flush=True)
+        rows = stream_steps(args, IH, IW) if args.shapes else []
+    lines = ['| launch (%d patches, %s frames) | us | min .. max | bytes | GB/s |' % (one['patches'], one['frame']), '|---|---|---|---|---|']
+    for name in ('warp_nchw', 'crop_nchw', 'warp_stem', 'crop_stem'):
+        lines.append('| %s | %.2f | %.2f .. %.2f | %d | %.1f |' % (name, one[name + '_us'], one[name + '_us_min_max'][0], one[name + '_us_min_max'][1],
+                                                                  one[name + '_bytes'], one[name + '_GBps']))
+    if rows:
+        lines += ['', '| B x Tc (%s) | camera step ms | patches step ms | difference ms | frames copied MB |' % args.dtype, '|---|---|---|---|---|']
+        for r in rows:
+            lines.append('| %d x %d | %.4f | %.4f | %.4f | %.1f |' % (r['B'], r['Tc'], r['camera_step_ms'], r['patches_step_ms'],
+                                                                      r['camera_minus_patches_ms'], r['camera_frame_MB_copied']))
+    table = '\n'.join(lines)
+    print(table, flush=True)
+    if args.markdown:
+        os.makedirs(os.path.dirname(os.path.abspath(args.markdown)), exist_ok=True)
+        with open(args.markdown, 'w') as f:
+            f.write(table + '\n')
+
+
+if __name__ == '__main__':
+    main()
