@@ -452,6 +452,14 @@ class FakeKernels(object):
         c = torch.sigmoid(f) * c_prev.float() + torch.sigmoid(i) * torch.tanh(g)
         return (torch.sigmoid(o) * torch.tanh(c)).to(c_prev.dtype), c.to(c_prev.dtype)
 
+    def clstm_gates_bwd(self, dh, dc_in, gates, c_prev):
+        i, f, o, g = gates.float().chunk(4, dim=-1)
+        i, f, o, g = torch.sigmoid(i), torch.sigmoid(f), torch.sigmoid(o), torch.tanh(g)
+        tc = torch.tanh(f * c_prev.float() + i * g)
+        dc = dh.float() * o * (1 - tc * tc) + (0 if dc_in is None else dc_in.float())
+        dg = torch.cat([dc * g * i * (1 - i), dc * c_prev.float() * f * (1 - f), dh.float() * tc * o * (1 - o), dc * i * (1 - g * g)], -1)
+        return dg.to(gates.dtype), (dc * f).to(c_prev.dtype)
+
     def sumsq(self, g, out, workspace=None):
         out += (g.double() ** 2).sum().float()
         return out
