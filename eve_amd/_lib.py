@@ -171,6 +171,8 @@ SIGNATURES = {
     'eve_screen_u8_area_to_nchw': [L, I, I, I, P, I, I, P, P],
     'eve_eye_warp_u8_to_nchw': [L, I, I, I, P, P, I, I, P, P],
     'eve_eye_warp_u8_to_stem': [I, L, I, I, I, P, P, I, I, P, P],
+    'eve_eye_warp_lens_u8_to_nchw': [L, I, I, I, P, P, P, I, I, P, P],
+    'eve_eye_warp_lens_u8_to_stem': [I, L, I, I, I, P, P, P, I, I, P, P],
 }
 EXPORTS = sorted(list(SIGNATURES) + ['eve_abi_version', 'eve_last_error', 'eve_last_kernel'])
 

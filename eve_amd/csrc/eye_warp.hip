@@ -11,6 +11,16 @@
 // Every product m * o is exact in float64 (24 bits by at most 13), so a fused multiply-add changes nothing as long as the
 // association stays; the coordinate of a pixel is computed from (oy, ox) alone, never stepped along the row.
 //
+// The lens variant (eve_eye_warp_lens_u8_to_nchw / _to_stem, tests/eye_warp_lens_ref.py) takes raw frames of a camera with lens
+// distortion: (u, v) is then a pixel of the UNDISTORTED image, and one row L = (fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6) per
+// patch -- OpenCV's pinhole + radial / tangential / rational model -- carries it to the raw frame before the taps are read:
+//   x = (u - cx) / fx, y = (v - cy) / fy, xx = x*x, yy = y*y, xy = x*y, r2 = xx + yy, a = xy + xy
+//   rad = (((k3*r2 + k2)*r2 + k1)*r2 + 1) / (((k6*r2 + k5)*r2 + k4)*r2 + 1)          den, the divisor, must be > 0
+//   xd = (x*rad + p1*a) + p2*(r2 + (xx + xx)),  yd = (y*rad + p1*(r2 + (yy + yy))) + p2*a,  ud = fx*xd + cx,  vd = fy*yd + cy
+// in float64, every operation rounded on its own (no contraction: these products are not exact); (ud, vd) then stands where (u, v)
+// stands above.  A row whose eight coefficients are all zero takes the plain arithmetic (fx*((u - cx)/fx) + cx is not u): the
+// decision is uniform over the patch, so over the workgroup's item.  No undistorted frame ever exists.
+//
 // The kernel is a gather stream: a 128 x 128 patch touches 12 bytes per output pixel and channel triple, 197 KB of loads for
 // 196 KB (float) or 147 KB (packed) of stores, out of a frame region the L2 holds.  A workgroup takes one (patch, band of EW_BAND
 // output rows) at a time with its lanes along ox: neighbouring lanes read neighbouring source bytes (as far as the warp keeps
@@ -34,17 +44,53 @@ struct EyeWarpArgs {
     int IH, IW, C, OH, OW;
 };
 
-// the three channels' fixed-point sums S (<= 255 * 65536) of output pixel (oy, ox); all zero outside
-__device__ __forceinline__ void warp_sums(const double (&m)[9], const uint8_t* __restrict__ frame, const int IH, const int IW, const int C,
-                                          const int oy, const int ox, uint32_t (&S)[3]) {
+// one patch's camera model, widened to float64; `on` is false for a row whose eight coefficients are all +-0 (a NaN is not zero)
+struct Lens {
+    double fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6;
+    bool on;
+};
+
+__device__ __forceinline__ Lens load_lens(const float* __restrict__ row) {
+    Lens L;
+    L.fx = (double)row[0]; L.fy = (double)row[1]; L.cx = (double)row[2]; L.cy = (double)row[3];
+    L.k1 = (double)row[4]; L.k2 = (double)row[5]; L.p1 = (double)row[6]; L.p2 = (double)row[7];
+    L.k3 = (double)row[8]; L.k4 = (double)row[9]; L.k5 = (double)row[10]; L.k6 = (double)row[11];
+    bool zero = true;
+#pragma unroll
+    for (int i = 4; i < 12; ++i) zero = zero && row[i] == 0.0f;
+    L.on = !zero;
+    return L;
+}
+
+// the three channels' fixed-point sums S (<= 255 * 65536) of output pixel (oy, ox); all zero outside.  LENS: (u, v) goes through
+// the distortion model of L first, unless L.on is false.
+template <bool LENS>
+__device__ __forceinline__ void warp_sums(const double (&m)[9], const Lens& L, const uint8_t* __restrict__ frame, const int IH, const int IW,
+                                          const int C, const int oy, const int ox, uint32_t (&S)[3]) {
 #pragma clang fp contract(off)
     const double dx = (double)ox, dy = (double)oy;
     const double X = (m[0] * dx + m[1] * dy) + m[2];
     const double Y = (m[3] * dx + m[4] * dy) + m[5];
     const double Wd = (m[6] * dx + m[7] * dy) + m[8];
-    const double u = X / Wd, v = Y / Wd;
+    double u = X / Wd, v = Y / Wd;
+    bool pole = false;                                   // at or beyond the rational model's pole, where rad changes sign
+    if constexpr (LENS) {
+        if (L.on) {
+            const double x = (u - L.cx) / L.fx, y = (v - L.cy) / L.fy;
+            const double xx = x * x, yy = y * y, xy = x * y;
+            const double r2 = xx + yy;
+            const double num = ((L.k3 * r2 + L.k2) * r2 + L.k1) * r2 + 1.0;
+            const double den = ((L.k6 * r2 + L.k5) * r2 + L.k4) * r2 + 1.0;
+            const double rad = num / den, a = xy + xy;
+            const double xd = (x * rad + L.p1 * a) + L.p2 * (r2 + (xx + xx));
+            const double yd = (y * rad + L.p1 * (r2 + (yy + yy))) + L.p2 * a;
+            u = L.fx * xd + L.cx;
+            v = L.fy * yd + L.cy;
+            pole = !(den > 0.0);
+        }
+    }
     S[0] = S[1] = S[2] = 0u;
-    if (!(Wd > 0.0 && u > -1.0 && u < (double)IW && v > -1.0 && v < (double)IH)) return;
+    if (!(Wd > 0.0 && u > -1.0 && u < (double)IW && v > -1.0 && v < (double)IH) || pole) return;
     const int fu = (int)floor(u * 256.0 + 0.5), fv = (int)floor(v * 256.0 + 0.5);      // in [-256, 256 * 16384]
     const int x0 = fu >> 8, y0 = fv >> 8;                                              // in [-1, IW] / [-1, IH]
     const uint32_t ax = (uint32_t)(fu & 255), ay = (uint32_t)(fv & 255);
@@ -68,9 +114,11 @@ __device__ __forceinline__ float warp_value(uint32_t S) {
 }
 
 // O = float: dst is float [N][3][OH][OW].  O = bf16_t / f16_t: dst is the stem's packed [N][OH+6][OW+8][4], pixel at (y+3, x+4).
-template <typename O>
-__global__ __launch_bounds__(EW_THREADS) void eye_warp_u8_kernel(const EyeWarpArgs a, const uint8_t* __restrict__ src,
-                                                                 const float* __restrict__ warps, void* __restrict__ dst) {
+// LENS: lens is float [N][12], read once per item like the matrix.  The body of both kernels.  Keep the pointers plain here (the
+// kernels' own parameters carry __restrict__) and the arguments by value: qualified pointers or a reference make the compiler
+// schedule the plain kernels differently from a kernel that holds this loop itself.
+template <typename O, bool LENS>
+__device__ __forceinline__ void eye_warp_items(const EyeWarpArgs a, const uint8_t* src, const float* warps, const float* lens, void* dst) {
     constexpr bool PACKED = !std::is_same<O, float>::value;
     const int rows = PACKED ? a.OH + 6 : a.OH, cols = PACKED ? a.OW + 8 : a.OW;      // of the output image, pad ring included
     for (long long item = blockIdx.x; item < a.items; item += gridDim.x) {
@@ -80,13 +128,15 @@ __global__ __launch_bounds__(EW_THREADS) void eye_warp_u8_kernel(const EyeWarpAr
         double m[9];
 #pragma unroll
         for (int i = 0; i < 9; ++i) m[i] = (double)warps[n * 9 + i];
+        Lens L = {};
+        if constexpr (LENS) L = load_lens(lens + n * 12);
         const uint8_t* frame = src + (size_t)n * a.IH * a.IW * a.C;
         for (int t = threadIdx.x; t < nr * cols; t += EW_THREADS) {
             const int r = r0 + t / cols, col = t % cols;
             const int oy = PACKED ? r - 3 : r, ox = PACKED ? col - 4 : col;
             const bool pixel = !PACKED || (oy >= 0 && oy < a.OH && ox >= 0 && ox < a.OW);
             uint32_t S[3] = {0u, 0u, 0u};
-            if (pixel) warp_sums(m, frame, a.IH, a.IW, a.C, oy, ox, S);
+            if (pixel) warp_sums<LENS>(m, L, frame, a.IH, a.IW, a.C, oy, ox, S);
             if constexpr (PACKED) {
                 uint2 q = make_uint2(0u, 0u);
                 if (pixel) {
@@ -103,7 +153,20 @@ __global__ __launch_bounds__(EW_THREADS) void eye_warp_u8_kernel(const EyeWarpAr
     }
 }
 
-// the checks both entry points share; -> nullptr or what is wrong
+template <typename O>
+__global__ __launch_bounds__(EW_THREADS) void eye_warp_u8_kernel(const EyeWarpArgs a, const uint8_t* __restrict__ src,
+                                                                 const float* __restrict__ warps, void* __restrict__ dst) {
+    eye_warp_items<O, false>(a, src, warps, nullptr, dst);
+}
+
+template <typename O>
+__global__ __launch_bounds__(EW_THREADS) void eye_warp_lens_u8_kernel(const EyeWarpArgs a, const uint8_t* __restrict__ src,
+                                                                      const float* __restrict__ warps, const float* __restrict__ lens,
+                                                                      void* __restrict__ dst) {
+    eye_warp_items<O, true>(a, src, warps, lens, dst);
+}
+
+// the checks the entry points share; -> nullptr or what is wrong
 const char* eye_warp_refusal(long long N, int IH, int IW, int C, const void* frames, const void* warps, int OH, int OW, const void* dst) {
     if (N <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0 || !frames || !warps || !dst) return "bad arguments";
     if (C != 3 && C != 4) return "C must be 3 or 4 (a fourth channel is ignored)";
@@ -154,6 +217,41 @@ extern "C" int eve_eye_warp_u8_to_stem(int dtype, long long N, int IH, int IW, i
     const dim3 grid((unsigned)(a.items < EW_MAX_BLOCKS ? a.items : EW_MAX_BLOCKS));
     EVE_DISPATCH_H16(dtype, EVE_LAUNCH(EVE_HNAME(H, "eye_warp_u8_kernel<", ">"), eye_warp_u8_kernel<H>, grid, dim3(EW_THREADS), 0,
                                        (hipStream_t)stream, a, frames_nhwc, warps, x_padded));
+    EVE_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int eve_eye_warp_lens_u8_to_nchw(long long N, int IH, int IW, int C, const uint8_t* frames_nhwc, const float* warps,
+                                            const float* lens, int OH, int OW, float* dst_nchw, eve_stream_t stream) {
+    char msg[128];
+    const char* why = eye_warp_refusal(N, IH, IW, C, frames_nhwc, warps, OH, OW, dst_nchw);
+    if (!why && !lens) why = "bad arguments";
+    if (why) {
+        snprintf(msg, sizeof(msg), "eye_warp_lens_u8_to_nchw: %s", why);
+        return set_error_msg(msg);
+    }
+    const EyeWarpArgs a = eye_warp_args(N, IH, IW, C, OH, OW, OH);
+    const dim3 grid((unsigned)(a.items < EW_MAX_BLOCKS ? a.items : EW_MAX_BLOCKS));
+    EVE_LAUNCH("eye_warp_lens_u8_kernel<float>", eye_warp_lens_u8_kernel<float>, grid, dim3(EW_THREADS), 0, (hipStream_t)stream, a,
+               frames_nhwc, warps, lens, (void*)dst_nchw);
+    EVE_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int eve_eye_warp_lens_u8_to_stem(int dtype, long long N, int IH, int IW, int C, const uint8_t* frames_nhwc, const float* warps,
+                                            const float* lens, int OH, int OW, void* x_padded, eve_stream_t stream) {
+    char msg[128];
+    const char* why = eye_warp_refusal(N, IH, IW, C, frames_nhwc, warps, OH, OW, x_padded);
+    if (!why && !lens) why = "bad arguments";
+    if (!why && dtype != EVE_DT_BF16 && dtype != EVE_DT_F16) why = "dtype must be bf16 or f16 (the stem's packed input)";
+    if (why) {
+        snprintf(msg, sizeof(msg), "eye_warp_lens_u8_to_stem: %s", why);
+        return set_error_msg(msg);
+    }
+    const EyeWarpArgs a = eye_warp_args(N, IH, IW, C, OH, OW, OH + 6);
+    const dim3 grid((unsigned)(a.items < EW_MAX_BLOCKS ? a.items : EW_MAX_BLOCKS));
+    EVE_DISPATCH_H16(dtype, EVE_LAUNCH(EVE_HNAME(H, "eye_warp_lens_u8_kernel<", ">"), eye_warp_lens_u8_kernel<H>, grid, dim3(EW_THREADS), 0,
+                                       (hipStream_t)stream, a, frames_nhwc, warps, lens, x_padded));
     EVE_CHECK_LAUNCH();
     return 0;
 }

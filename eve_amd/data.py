@@ -14,10 +14,13 @@ uint8 frames is 4x less PCIe traffic, and the float values produced here are bit
   warp_eye_patches(u8, warps)    whole camera frames [..., IH, IW, 3|4] uint8 and per-frame homographies [..., 3, 3] float32
                                  (patch pixel -> camera pixel) -> one eye's patches [..., 3, H, W] float32 in [-1, 1], cut
                                  bilinearly on the device (EyeNet / EVE / EVEStream take `camera_frame` + `<side>_eye_warp`)
+  camera_lens(K, dist)           a camera matrix [..., 3, 3] and 4, 5 or 8 OpenCV distortion coefficients -> the float32 [..., 12]
+                                 rows that warp_eye_patches(..., lens=) and the `camera_lens` key take for RAW (distorted) frames
   EyeNet.forward_sequence / RefineNet.forward_sequence / EVE accept the uint8 tensors directly (eye patches go straight
   into the stem kernel's packed bf16 layout, no float tensor is ever materialised).
   DevicePrefetcher(iterable)     pinned double-buffered H2D on a side stream
 """
+import numpy as np
 import torch
 
 from .kernels import default_kernels
@@ -63,7 +66,35 @@ def eye_patch_hw(config=None):
     return int(config.eyes_size[1]), int(config.eyes_size[0])
 
 
-def warp_eye_patches(frames, warps, size=None):
+def camera_lens(camera_matrix, dist_coeffs):
+    """The lens rows of a calibrated camera: camera_matrix [..., 3, 3] = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] and dist_coeffs
+    [..., n] with OpenCV's n = 4, 5 or 8 coefficients in OpenCV's order k1, k2, p1, p2[, k3[, k4, k5, k6]] (cv2.calibrateCamera's
+    result, flattened) -> float32 [..., 12] = (fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6), the missing coefficients zero.
+    numpy arrays or torch tensors; the leading dimensions broadcast against each other (one distortion vector for a batch of
+    matrices, say).  A torch tensor comes back when camera_matrix is one (on its device), else a numpy array.
+
+    ValueError: 12 or 14 coefficients (thin-prism and tilt terms are not offered), any other count, a non-zero skew K[0, 1], a last
+    row other than (0, 0, 1).  All-zero coefficients are fine: such a row takes the plain warp, bit for bit."""
+    as_torch = torch.is_tensor(camera_matrix)
+    to_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    K, d = to_np(camera_matrix).astype(np.float64), to_np(dist_coeffs).astype(np.float64)
+    if K.ndim < 2 or K.shape[-2:] != (3, 3):
+        raise ValueError('camera_lens: camera_matrix must be [..., 3, 3], got %s' % (tuple(K.shape),))
+    if d.ndim < 1 or d.shape[-1] not in (4, 5, 8):
+        raise ValueError('camera_lens: 4, 5 or 8 distortion coefficients (k1, k2, p1, p2[, k3[, k4, k5, k6]]), got %s%s' % (
+            tuple(d.shape), ': thin-prism and tilt coefficients are not offered' if d.ndim and d.shape[-1] in (12, 14) else ''))
+    if (K[..., 0, 1] != 0).any():
+        raise ValueError('camera_lens: a skewed camera matrix (K[0, 1] != 0) is not offered')
+    if (K[..., 2, :] != np.array([0.0, 0.0, 1.0])).any():
+        raise ValueError('camera_lens: the last row of camera_matrix must be (0, 0, 1)')
+    lead = np.broadcast_shapes(K.shape[:-2], d.shape[:-1])
+    out = np.zeros(lead + (12,), dtype=np.float32)
+    out[..., 0], out[..., 1], out[..., 2], out[..., 3] = K[..., 0, 0], K[..., 1, 1], K[..., 0, 2], K[..., 1, 2]
+    out[..., 4:4 + d.shape[-1]] = d
+    return torch.from_numpy(out).to(camera_matrix.device) if as_torch else out
+
+
+def warp_eye_patches(frames, warps, size=None, lens=None):
     """One eye's patches cut from whole camera frames on the device, in place of two cv2.warpPerspective calls per frame on the
     host: frames uint8 [..., IH, IW, 3 | 4] (a fourth channel ignored, the channel order kept), warps float32 [..., 3, 3] with the
     same leading dimensions -> float32 [..., 3, H, W] in [-1, 1], the values preprocess_frames gives for the cut patch.  size:
@@ -72,15 +103,26 @@ def warp_eye_patches(frames, warps, size=None):
     warps[i] maps a PATCH pixel (x, y, 1) to a CAMERA pixel (X / Wd, Y / Wd) -- the matrix cv2.warpPerspective uses with
     WARP_INVERSE_MAP.  The EVE pipeline's perspective-normalisation matrix W maps the camera to the patch
     (cv2.warpPerspective(frame, W, (w, h))): pass inv(W).  Sampling is bilinear with 8 fractional bits per axis and zero outside
-    the frame (which comes out as -1.0), bit-exact by the contract of include/eve_hip.h eve_eye_warp_u8_to_nchw."""
+    the frame (which comes out as -1.0), bit-exact by the contract of include/eve_hip.h eve_eye_warp_u8_to_nchw.
+
+    lens: None for frames that are already undistorted (what the EVE dataset's videos are), or float32 [..., 12] rows from
+    camera_lens with the same leading dimensions for RAW frames: W and inv(W) then refer to the undistorted image as before, and
+    every coordinate goes through the camera's distortion model before the frame is read (eve_eye_warp_lens_u8_to_nchw).  No
+    undistorted frame is made.  A row with zero coefficients gives the lens=None bits."""
     flat, lead = _fold(frames)
     if not torch.is_tensor(warps) or warps.dtype != torch.float32 or tuple(warps.shape) != lead + (3, 3):
         raise TypeError('expected float32 warps shaped %s, got %s %s' % (lead + (3, 3), getattr(warps, 'dtype', type(warps)),
                                                                          tuple(getattr(warps, 'shape', ()))))
     if flat.shape[3] not in (3, 4):
         raise TypeError('expected camera frames with 3 or 4 channels, got %d' % flat.shape[3])
+    if lens is not None and (not torch.is_tensor(lens) or lens.dtype != torch.float32 or tuple(lens.shape) != lead + (12,)):
+        raise TypeError('expected float32 lens rows shaped %s, got %s %s' % (lead + (12,), getattr(lens, 'dtype', type(lens)),
+                                                                             tuple(getattr(lens, 'shape', ()))))
     hw = eye_patch_hw() if size is None else (int(size[0]), int(size[1]))
-    out = default_kernels().eye_warp_u8_to_nchw(flat, warps.reshape(-1, 3, 3).contiguous(), hw)
+    if lens is None:
+        out = default_kernels().eye_warp_u8_to_nchw(flat, warps.reshape(-1, 3, 3).contiguous(), hw)
+    else:
+        out = default_kernels().eye_warp_lens_u8_to_nchw(flat, warps.reshape(-1, 3, 3).contiguous(), lens.reshape(-1, 12).contiguous(), hw)
     return out.view(lead + tuple(out.shape[1:]))
 
 

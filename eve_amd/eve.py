@@ -306,7 +306,8 @@ class EVE(nn.Module):
 
     def _predict_sequence(self, d, eye_states, refine_states, reset=None, return_heatmaps=False, lengths=None):
         """The prediction part of forward() for one chunk of an EVEStream: eval only, no labels, no losses.  d: the chunk's
-        inputs [B, Tc, ...] (not modified); eye_states / refine_states: the carried state buffers of the two networks
+        inputs [B, Tc, ...] (not modified; the eyes as patches, or as camera_frame + {left,right}_eye_warp with an optional
+        camera_lens [B, Tc, 12] for raw frames -- eye_net.eye_input); eye_states / refine_states: the carried state buffers of the two networks
         (EyeNet._stream_state_buffers, RefineNet._stream_state_buffers), read as the state before the chunk and overwritten with
         the state after it; reset: None or int32 [2B] device flags (stream b's flag at b and B + b) -- flagged streams start from
         zero; lengths: None or int32 [2B] device frame counts in the same layout -- stream b consumes its first lengths[b] frames

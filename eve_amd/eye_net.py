@@ -38,18 +38,23 @@ def _wants_grad(t):
 
 EYE_PATCH_KEYS = ('left_eye_patch', 'right_eye_patch')
 EYE_CAMERA_KEYS = ('camera_frame', 'left_eye_warp', 'right_eye_warp')
+EYE_LENS_KEY = 'camera_lens'                 # optional with the camera form: raw frames of a camera with lens distortion
 
 
 def eye_input(batch):
     """The tensor that carries a batch's [B, T] and its device: left_eye_patch, or camera_frame when the eyes come as whole
     camera frames plus per-eye homographies.  Raises on a batch that holds both forms, half of one, or tensors of the wrong
-    dtype or shape for the camera form."""
+    dtype or shape for the camera form.  The camera form may carry camera_lens, float32 [B, T, 12] (data.camera_lens): one
+    camera per frame, for both eyes."""
     has_patch = [k_ for k_ in EYE_PATCH_KEYS if k_ in batch]
     has_cam = [k_ for k_ in EYE_CAMERA_KEYS if k_ in batch]
     if has_patch and has_cam:
         raise ValueError('give the eyes either as %s or as %s, not both (found %s)' % (
             ' / '.join(EYE_PATCH_KEYS), ' / '.join(EYE_CAMERA_KEYS), ', '.join(has_patch + has_cam)))
     if not has_cam:
+        if EYE_LENS_KEY in batch:
+            raise ValueError('%s goes with %s: pre-cut patches were cut from an undistorted frame already' % (
+                EYE_LENS_KEY, ' / '.join(EYE_CAMERA_KEYS)))
         return batch['left_eye_patch']
     if len(has_cam) != len(EYE_CAMERA_KEYS):
         raise ValueError('the camera form needs %s: missing %s' % (
@@ -63,6 +68,11 @@ def eye_input(batch):
         if not torch.is_tensor(w) or w.dtype != torch.float32 or tuple(w.shape) != tuple(frames.shape[:2]) + (3, 3):
             raise TypeError('%s must be float32 %s, got %s %s' % (k_, tuple(frames.shape[:2]) + (3, 3), getattr(w, 'dtype', type(w)),
                                                                    tuple(getattr(w, 'shape', ()))))
+    if EYE_LENS_KEY in batch:
+        lens = batch[EYE_LENS_KEY]
+        if not torch.is_tensor(lens) or lens.dtype != torch.float32 or tuple(lens.shape) != tuple(frames.shape[:2]) + (12,):
+            raise TypeError('%s must be float32 %s, got %s %s' % (EYE_LENS_KEY, tuple(frames.shape[:2]) + (12,),
+                                                                   getattr(lens, 'dtype', type(lens)), tuple(getattr(lens, 'shape', ()))))
     return frames
 
 
@@ -366,7 +376,9 @@ class EyeNet(nn.Module):
         """batch: {left,right}_eye_patch [B, T, 3, H, W] float (or uint8 [B, T, H, W, C] decoded frames), {left,right}_h [B, T, 2].
         In place of the two patch keys the batch may hold whole camera frames, camera_frame uint8 [B, T, IH, IW, 3 | 4], and
         {left,right}_eye_warp float32 [B, T, 3, 3], the homographies from a patch pixel to a camera pixel (data.warp_eye_patches):
-        the patches, of the config's eyes_size, are then cut on the device.
+        the patches, of the config's eyes_size, are then cut on the device.  With camera_lens, float32 [B, T, 12] (data.camera_lens:
+        the intrinsics and OpenCV distortion coefficients of the camera behind each frame), camera_frame is the RAW frame and the
+        warps refer to the undistorted image the networks were trained on: the cut undistorts as it samples.
         Returns the B x T x ... tensors eve.py:174-182 would stack: <side>_g_initial [B,T,2],
         <side>_pupil_size [B,T], <side>_eye_rnn_states_<i> [B,T,H] per cell ((h, c) pair of them for LSTM).
         initial_states: {side: h [B,H]} or {side: [per-cell h | (h, c) | None]}."""
@@ -388,14 +400,21 @@ class EyeNet(nn.Module):
             (Hh, Ww), C = data.eye_patch_hw(self.config), 3
             flat = frames.reshape(B * T, IH, IW, Cc).contiguous()
             lw, rw = (batch[s_ + '_eye_warp'].reshape(B * T, 3, 3).contiguous() for s_ in ('left', 'right'))
+            if EYE_LENS_KEY in batch:               # raw frames: the lens kernels, one camera per frame for both eyes
+                lens = batch[EYE_LENS_KEY].reshape(B * T, 12).contiguous()
+                to_stem = lambda w, out: k.eye_warp_lens_u8_to_stem(flat, w, lens, (Hh, Ww), out=out)
+                to_nchw = lambda w: k.eye_warp_lens_u8_to_nchw(flat, w, lens, (Hh, Ww))
+            else:
+                to_stem = lambda w, out: k.eye_warp_u8_to_stem(flat, w, (Hh, Ww), out=out)
+                to_nchw = lambda w: k.eye_warp_u8_to_nchw(flat, w, (Hh, Ww))
             if dt in HALF_DTYPES and Hh % 4 == 0 and Ww == 128:
                 x_padded = torch.empty((2 * B * T, Hh + 6, Ww + 8, 4), dtype=dt, device=frames.device)
-                k.eye_warp_u8_to_stem(flat, lw, (Hh, Ww), out=x_padded[:B * T])
-                k.eye_warp_u8_to_stem(flat, rw, (Hh, Ww), out=x_padded[B * T:])
+                to_stem(lw, x_padded[:B * T])
+                to_stem(rw, x_padded[B * T:])
                 left = right = flat                 # (no float patches: nothing below reads them)
             else:
-                left = k.eye_warp_u8_to_nchw(flat, lw, (Hh, Ww)).view(B, T, C, Hh, Ww)
-                right = k.eye_warp_u8_to_nchw(flat, rw, (Hh, Ww)).view(B, T, C, Hh, Ww)
+                left = to_nchw(lw).view(B, T, C, Hh, Ww)
+                right = to_nchw(rw).view(B, T, C, Hh, Ww)
         else:
             left, right = batch['left_eye_patch'], batch['right_eye_patch']
         if x_padded is None and left.dtype == torch.uint8:

@@ -460,6 +460,39 @@ class HipKernels(object):
                                                   self._stream()))
         return dst
 
+    def _eye_warp_lens_args(self, frames, warps, lens, out_hw):
+        """_eye_warp_args plus the lens rows: float32 [N, 12], contiguous, on the frames' device."""
+        args = self._eye_warp_args(frames, warps, out_hw)
+        if not torch.is_tensor(lens) or lens.dtype != torch.float32 or tuple(lens.shape) != (args[0], 12):
+            raise TypeError('eye_warp: lens must be float32 [%d, 12], got %s %s' % (args[0], getattr(lens, 'dtype', type(lens)),
+                                                                                  tuple(getattr(lens, 'shape', ()))))
+        if not lens.is_contiguous():
+            raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        if lens.device != frames.device:
+            raise RuntimeError('eye_warp: frames and lens are on different devices')
+        return args
+
+    def eye_warp_lens_u8_to_nchw(self, frames, warps, lens, out_hw):
+        """eye_warp_u8_to_nchw on RAW frames of a camera with lens distortion: `warps` point into the undistorted image, and lens,
+        float32 [N,12] = (fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6) per frame (data.camera_lens; OpenCV's pinhole + radial /
+        tangential / rational model), carries each coordinate to the raw frame before the taps are read.  A row with all eight
+        coefficients zero gives eye_warp_u8_to_nchw's bits (include/eve_hip.h eve_eye_warp_lens_u8_to_nchw)."""
+        N, IH, IW, C, OH, OW = self._eye_warp_lens_args(frames, warps, lens, out_hw)
+        out = torch.empty((N, 3, OH, OW), dtype=torch.float32, device=frames.device)
+        self._ck(self.lib.eve_eye_warp_lens_u8_to_nchw(N, IH, IW, C, self._p(frames), self._p(warps), self._p(lens), OH, OW, self._p(out),
+                                                       self._stream()))
+        return out
+
+    def eye_warp_lens_u8_to_stem(self, frames, warps, lens, out_hw, out=None, dtype=torch.bfloat16):
+        """The same patches straight into the stem's packed 16-bit input [N,OH+6,OW+8,4], as eye_warp_u8_to_stem lays it out."""
+        N, IH, IW, C, OH, OW = self._eye_warp_lens_args(frames, warps, lens, out_hw)
+        dst = out if out is not None else torch.empty((N, OH + 6, OW + 8, 4), dtype=dtype, device=frames.device)
+        if tuple(dst.shape) != (N, OH + 6, OW + 8, 4) or dst.dtype not in HALF_DTYPES:
+            raise TypeError('eye_warp: out must be bf16 / f16 [%d, %d, %d, 4], got %s %s' % (N, OH + 6, OW + 8, dst.dtype, tuple(dst.shape)))
+        self._ck(self.lib.eve_eye_warp_lens_u8_to_stem(dt_code(dst.dtype), N, IH, IW, C, self._p(frames), self._p(warps), self._p(lens), OH, OW,
+                                                       self._p(dst), self._stream()))
+        return dst
+
     # ------------------------------------------------------------------ gaze geometry / heat-maps / soft-argmax
     def _flat32(self, t, shape, what):
         t = t.contiguous()

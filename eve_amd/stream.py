@@ -172,7 +172,12 @@ class EVEStream(object):
         WARP_INVERSE_MAP matrix, inv(W) of the perspective-normalisation matrix W.  The patches (the config's eyes_size) are then
         cut by eve_eye_warp_u8_to_stem / _to_nchw inside the step and inside the captured graph: the frames and the matrices are
         copied into the graph's input buffers like every other tensor of the chunk, and their shapes and dtypes are part of the
-        graph's key.  A chunk holds one form, not both.
+        graph's key.  A chunk holds one form, not both.  The camera form may add camera_lens, float32 [B, Tc, 12] rows
+        (fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6) from data.camera_lens -- the intrinsics and OpenCV distortion coefficients
+        of the camera behind each frame, one row for both eyes: camera_frame is then the RAW frame, the warps keep referring to
+        the undistorted image the networks were trained on, and eve_eye_warp_lens_u8_to_stem / _to_nchw push every coordinate
+        through the lens model before the frame is read (no undistorted frame is made; zero coefficients give the plain bits).
+        A chunk with the key captures a graph of its own, and a replay reads the rows of the chunk at hand.
 
         screen_frame is float [B, Tc, 3, H, W] at the configured screen size, uint8 [B, Tc, H, W, 3] at that size, or a live
         capture as it comes off the desktop: uint8 [B, Tc, IH, IW, 3 | 4] at any resolution from the screen size up to 16 843 009

@@ -721,6 +721,38 @@ int eve_eye_warp_u8_to_nchw(long long N, int IH, int IW, int C, const uint8_t* f
                             float* dst_nchw, eve_stream_t stream);
 int eve_eye_warp_u8_to_stem(int dtype /* EVE_DT_BF16 | EVE_DT_F16 */, long long N, int IH, int IW, int C, const uint8_t* frames_nhwc,
                             const float* warps, int OH, int OW, void* x_padded, eve_stream_t stream);
+/* The same pair for RAW frames of a camera with lens distortion: the networks were trained on undistorted video, and the
+ * normalisation matrix W is defined on the undistorted image, so inv(W) now points into an image that is never made -- the
+ * coordinate goes through the camera's distortion model before the taps are read, in the same single launch.  lens [N][12] float,
+ * one row per patch, widened to float64 on the device:
+ *   L = (fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6)
+ * OpenCV's pinhole + radial / tangential / rational model, in OpenCV's coefficient order behind the four intrinsics (a 4- or
+ * 5-coefficient calibration leaves the rest zero).  Contract, bit-exact: X, Y, Wd, u = X / Wd, v = Y / Wd as above; then in
+ * float64, every operation rounded on its own (no contraction) and in exactly this association
+ *   x  = (u - cx) / fx            y  = (v - cy) / fy
+ *   xx = x*x   yy = y*y   xy = x*y   r2 = xx + yy
+ *   num = ((k3*r2 + k2)*r2 + k1)*r2 + 1.0
+ *   den = ((k6*r2 + k5)*r2 + k4)*r2 + 1.0
+ *   rad = num / den               a = xy + xy
+ *   xd = (x*rad + p1*a) + p2*(r2 + (xx + xx))
+ *   yd = (y*rad + p1*(r2 + (yy + yy))) + p2*a
+ *   ud = fx*xd + cx               vd = fy*yd + cy
+ *   inside iff Wd > 0 && den > 0 && ud > -1 && ud < IW && vd > -1 && vd < IH        (a NaN fails its comparison)
+ * and from (ud, vd) on the plain contract: floor(ud*256 + 0.5), the four integer-weighted taps with zeros outside the frame,
+ * S * 2^-16 * float(2/255) + (-1), -1.0 outside.  Further:
+ *   - a row whose eight coefficients k1..k6, p1, p2 are all +-0 takes the plain path for its patch and gives eve_eye_warp_u8_to_*'s
+ *     bits whatever its intrinsics say (fx*((u - cx)/fx) + cx is not u in floating point), so a calibrated and an uncalibrated
+ *     camera can share a batch; the decision is per patch;
+ *   - degenerate rows are not refused: a NaN among the values used, or fx == 0 / fy == 0 with coefficients, falls out of the
+ *     comparisons as an all-black (-1.0) patch; a negative focal length is a mirrored camera and works;
+ *   - den > 0 blacks everything at and beyond the rational model's pole, where rad would change sign and land inside the frame;
+ *   - far outside the calibrated field a barrel polynomial folds back into the image, as it does in OpenCV: not guarded;
+ *   - not offered: thin-prism and tilt coefficients (OpenCV's 12- and 14-element forms), skew, fisheye models, gradients.
+ * Layouts, limits and refusals are the plain pair's, plus a null `lens`; messages carry the entry point's name.             */
+int eve_eye_warp_lens_u8_to_nchw(long long N, int IH, int IW, int C, const uint8_t* frames_nhwc, const float* warps, const float* lens,
+                                 int OH, int OW, float* dst_nchw, eve_stream_t stream);
+int eve_eye_warp_lens_u8_to_stem(int dtype /* EVE_DT_BF16 | EVE_DT_F16 */, long long N, int IH, int IW, int C, const uint8_t* frames_nhwc,
+                                 const float* warps, const float* lens, int OH, int OW, void* x_padded, eve_stream_t stream);
 
 #ifdef __cplusplus
 }

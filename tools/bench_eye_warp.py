@@ -3,18 +3,21 @@
 and of one EVEStream step fed whole camera frames next to the same step fed pre-cut uint8 patches.
 
     python tools/bench_eye_warp.py [--patches 64] [--size 1920x1080] [--iters 500] [--rounds 5] [--shapes 1x1 8x4 32x2]
-                                   [--steps 50] [--dtype bf16] [--markdown profiles/table.md]
+                                   [--steps 50] [--dtype bf16] [--lens] [--markdown profiles/table.md]
 
 Part 1, per launch, the four routes interleaved in one process (the median over the rounds of events around `iters` calls):
     warp_nchw / warp_stem   N patches of 128 x 128 cut from N frames of the given size, each by its own rotated, scaled warp with a
                             perspective row; float NCHW and the stem's packed bf16
     crop_nchw / crop_stem   eve_frames_u8_to_nchw / _to_stem on N pre-cut 128 x 128 x 3 patches: what the caller launched before,
                             after two cv2.warpPerspective calls per frame on the host and a second upload (neither is timed here)
+    lens_nchw / lens_stem   with --lens: the same patches through eve_eye_warp_lens_u8_to_nchw / _to_stem, every frame behind the
+                            rational eight-coefficient lens of lens_rows() (the arithmetic does not depend on the values)
 The rate quoted for a warp is (bytes its loads ask for: 4 taps x 3 channels per output pixel) + (bytes stored) over the time; the
 taps overlap, so the distinct bytes behind them are about a quarter -- it is a rate of the kernel's traffic, not of HBM.
 
 Part 2, per EVEStream step under graph replay (refine_net config): `camera` feeds camera_frame + two warps per frame, `patches`
-the uint8 [B, Tc, 128, 128, 3] patch pair.  The camera step also copies B * Tc whole frames into the graph's input buffer."""
+the uint8 [B, Tc, 128, 128, 3] patch pair.  The camera step also copies B * Tc whole frames into the graph's input buffer.  With
+--lens a third stream, `lens`, feeds the camera keys plus camera_lens."""
 import argparse
 import json
 import math
@@ -57,6 +60,14 @@ def warps_for(n, IH, IW, seed):
     return torch.tensor(np.array(ms), dtype=torch.float32)
 
 
+def lens_rows(n, IH, IW):
+    """n rows (fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6) of one camera: a 1080p webcam's focal length scaled to the frame, the
+    principal point a little off its centre, a mild rational model."""
+    f = 1400.0 * IW / 1920.0
+    row = [f, f * 1.01, IW / 2 + 3.5, IH / 2 - 2.25, 0.9, 0.1, 2e-3, 1e-3, 0.01, 1.1, 0.15, 0.02]
+    return torch.tensor([row] * n, dtype=torch.float32)
+
+
 def median(v):
     return sorted(v)[len(v) // 2]
 
@@ -73,6 +84,10 @@ def launches(args, IH, IW):
               'warp_stem': lambda: k.eye_warp_u8_to_stem(frames, warps, HW, out=packed),
               'crop_nchw': lambda: k.frames_u8_to_nchw(crops, 2.0 / 255.0, -1.0),
               'crop_stem': lambda: k.frames_u8_to_stem(crops, 2.0 / 255.0, -1.0, out=packed)}
+    if args.lens:
+        lens = lens_rows(N, IH, IW).cuda()
+        routes['lens_nchw'] = lambda: k.eye_warp_lens_u8_to_nchw(frames, warps, lens, HW)
+        routes['lens_stem'] = lambda: k.eye_warp_lens_u8_to_stem(frames, warps, lens, HW, out=packed)
     for fn in routes.values():                   # warm up: code objects, allocator
         for _ in range(5):
             fn()
@@ -92,8 +107,15 @@ def launches(args, IH, IW):
         res['warp_%s_GBps' % form] = round(res['warp_%s_bytes' % form] / (1e-3 * median(times['warp_' + form])) / 1e9, 1)
         res['crop_%s_bytes' % form] = pixels * 3 + stored[form]
         res['crop_%s_GBps' % form] = round(res['crop_%s_bytes' % form] / (1e-3 * median(times['crop_' + form])) / 1e9, 1)
+        if args.lens:
+            res['lens_%s_bytes' % form] = res['warp_%s_bytes' % form]
+            res['lens_%s_GBps' % form] = round(res['lens_%s_bytes' % form] / (1e-3 * median(times['lens_' + form])) / 1e9, 1)
+            res['lens_over_warp_%s' % form] = round(median(times['lens_' + form]) / median(times['warp_' + form]), 3)
     k.eye_warp_u8_to_stem(frames, warps, HW, out=packed)
     res['kernel'] = k.lib.eve_last_kernel().decode()
+    if args.lens:
+        k.eye_warp_lens_u8_to_stem(frames, warps, lens, HW, out=packed)
+        res['lens_kernel'] = k.lib.eve_last_kernel().decode()
     return res
 
 
@@ -118,6 +140,8 @@ def stream_steps(args, IH, IW):
         pat = dict(rest, left_eye_patch=torch.randint(0, 256, (B, Tc) + HW + (3,), generator=g, dtype=torch.uint8).cuda(),
                    right_eye_patch=torch.randint(0, 256, (B, Tc) + HW + (3,), generator=g, dtype=torch.uint8).cuda())
         streams = {'camera': (eve_amd.EVEStream(model, B), cam), 'patches': (eve_amd.EVEStream(model, B), pat)}
+        if args.lens:
+            streams['lens'] = (eve_amd.EVEStream(model, B), dict(cam, camera_lens=lens_rows(B * Tc, IH, IW).view(B, Tc, 12).cuda()))
         for s, chunk in streams.values():
             for _ in range(3):
                 s.step(chunk)                    # capture + warm replays
@@ -131,6 +155,8 @@ def stream_steps(args, IH, IW):
             res[name + '_step_ms'] = round(median(t), 4)
             res[name + '_step_ms_min_max'] = [round(min(t), 4), round(max(t), 4)]
         res['camera_minus_patches_ms'] = round(res['camera_step_ms'] - res['patches_step_ms'], 4)
+        if args.lens:
+            res['lens_minus_camera_ms'] = round(res['lens_step_ms'] - res['camera_step_ms'], 4)
         res['camera_frame_MB_copied'] = round(B * Tc * IH * IW * 3 / 1e6, 1)
         rows.append(res)
         print(json.dumps(res), flush=True)
@@ -148,6 +174,7 @@ def main():
     ap.add_argument('--shapes', nargs='*', default=['1x1', '8x4', '32x2'], help='EVEStream B x Tc shapes (none: skip part 2)')
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--dtype', default='bf16', choices=sorted(DTYPES))
+    ap.add_argument('--lens', action='store_true', help='also time the lens launches and an EVEStream step with camera_lens')
     ap.add_argument('--markdown', default=None, help='also write the tables to this file')
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -158,7 +185,7 @@ def main():
         print(json.dumps(one), flush=True)
         rows = stream_steps(args, IH, IW) if args.shapes else []
     lines = ['| launch (%d patches, %s frames) | us | min .. max | bytes | GB/s |' % (one['patches'], one['frame']), '|---|---|---|---|---|']
-    for name in ('warp_nchw', 'crop_nchw', 'warp_stem', 'crop_stem'):
+    for name in ('warp_nchw', 'lens_nchw', 'crop_nchw', 'warp_stem', 'lens_stem', 'crop_stem') if args.lens else ('warp_nchw', 'crop_nchw', 'warp_stem', 'crop_stem'):
         lines.append('| %s | %.2f | %.2f .. %.2f | %d | %.1f |' % (name, one[name + '_us'], one[name + '_us_min_max'][0], one[name + '_us_min_max'][1],
                                                                   one[name + '_bytes'], one[name + '_GBps']))
     if rows:
@@ -166,6 +193,12 @@ def main():
         for r in rows:
             lines.append('| %d x %d | %.4f | %.4f | %.4f | %.1f |' % (r['B'], r['Tc'], r['camera_step_ms'], r['patches_step_ms'],
                                                                       r['camera_minus_patches_ms'], r['camera_frame_MB_copied']))
+    if rows and args.lens:
+        lines += ['', '| B x Tc (%s) | lens step ms | min .. max | camera step ms | min .. max | lens - camera ms |' % args.dtype, '|---|---|---|---|---|---|']
+        for r in rows:
+            lines.append('| %d x %d | %.4f | %.4f .. %.4f | %.4f | %.4f .. %.4f | %.4f |' % (
+                r['B'], r['Tc'], r['lens_step_ms'], r['lens_step_ms_min_max'][0], r['lens_step_ms_min_max'][1], r['camera_step_ms'],
+                r['camera_step_ms_min_max'][0], r['camera_step_ms_min_max'][1], r['lens_minus_camera_ms']))
     table = '\n'.join(lines)
     print(table, flush=True)
     if args.markdown:
