@@ -173,6 +173,7 @@ SIGNATURES = {
     'eve_eye_warp_u8_to_stem': [I, L, I, I, I, P, P, I, I, P, P],
     'eve_eye_warp_lens_u8_to_nchw': [L, I, I, I, P, P, P, I, I, P, P],
     'eve_eye_warp_lens_u8_to_stem': [I, L, I, I, I, P, P, P, I, I, P, P],
+    'eve_eye_pose_normalize': [L, P, I, I, P, P, P, P, P, P, P],
 }
 EXPORTS = sorted(list(SIGNATURES) + ['eve_abi_version', 'eve_last_error', 'eve_last_kernel'])
 

@@ -16,6 +16,10 @@ uint8 frames is 4x less PCIe traffic, and the float values produced here are bit
                                  bilinearly on the device (EyeNet / EVE / EVEStream take `camera_frame` + `<side>_eye_warp`)
   camera_lens(K, dist)           a camera matrix [..., 3, 3] and 4, 5 or 8 OpenCV distortion coefficients -> the float32 [..., 12]
                                  rows that warp_eye_patches(..., lens=) and the `camera_lens` key take for RAW (distorted) frames
+  eye_pose(K, rvec, tvec, eyes, focal_norm, distance_norm)
+                                 a face tracker's cv2.solvePnP result -> the float32 [..., 18] rows of the `eye_pose` key (EyeNet /
+                                 EVE / EVEStream take `camera_frame` + `eye_pose` and derive the warps, R, o, h and head_R on the device)
+  normalize_eyes(pose)           those rows -> the derived tensors themselves (head_R, <side>_o, _R, _eye_warp, _h, pose_valid)
   EyeNet.forward_sequence / RefineNet.forward_sequence / EVE accept the uint8 tensors directly (eye patches go straight
   into the stem kernel's packed bf16 layout, no float tensor is ever materialised).
   DevicePrefetcher(iterable)     pinned double-buffered H2D on a side stream
@@ -92,6 +96,80 @@ def camera_lens(camera_matrix, dist_coeffs):
     out[..., 0], out[..., 1], out[..., 2], out[..., 3] = K[..., 0, 0], K[..., 1, 1], K[..., 0, 2], K[..., 1, 2]
     out[..., 4:4 + d.shape[-1]] = d
     return torch.from_numpy(out).to(camera_matrix.device) if as_torch else out
+
+
+def eye_pose(camera_matrix, head_rvec, head_tvec, eye_centers, focal_norm, distance_norm):
+    """The pose rows of the `eye_pose` key, from what a face tracker holds per frame: camera_matrix [..., 3, 3] =
+    [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] of the UNDISTORTED image (with camera_lens, normally the same K); head_rvec [..., 3] or
+    [..., 3, 1] and head_tvec likewise, cv2.solvePnP's result for the head model; eye_centers [..., 2, 3], the left and the right
+    eye's centre in the head model's coordinates and in head_tvec's length unit (EVE: millimetres); focal_norm and distance_norm
+    (scalars or [...]): the virtual camera the patches are normalised to -- focal length in patch pixels and distance in that
+    length unit.  Both are required: the reference does not state the values behind its own patches, and no default here
+    pretends to.  -> float32 [..., 18] = (fx, fy, cx, cy, r0, r1, r2, t0, t1, t2, l0, l1, l2, q0, q1, q2, focal_norm,
+    distance_norm).  numpy arrays or torch tensors; the leading dimensions broadcast against each other (one camera matrix
+    and one head model for a clip, say).  A torch tensor comes back when camera_matrix is one (on its device), else a numpy array.
+
+    ValueError: a camera matrix that is not [..., 3, 3], has skew (K[0, 1] != 0) or a last row other than (0, 0, 1); vectors or
+    eye centres of another shape.  Values are not judged here: a NaN or a head behind the camera gives pose_valid False on the
+    device (include/eve_hip.h eve_eye_pose_normalize)."""
+    as_torch = torch.is_tensor(camera_matrix)
+    to_np = lambda a: (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(np.float64)
+    K, r, t, c = to_np(camera_matrix), to_np(head_rvec), to_np(head_tvec), to_np(eye_centers)
+    f, dn = to_np(focal_norm), to_np(distance_norm)
+    if K.ndim < 2 or K.shape[-2:] != (3, 3):
+        raise ValueError('eye_pose: camera_matrix must be [..., 3, 3], got %s' % (tuple(K.shape),))
+    if (K[..., 0, 1] != 0).any():
+        raise ValueError('eye_pose: a skewed camera matrix (K[0, 1] != 0) is not offered')
+    if (K[..., 2, :] != np.array([0.0, 0.0, 1.0])).any():
+        raise ValueError('eye_pose: the last row of camera_matrix must be (0, 0, 1)')
+    vecs = []
+    for name, v in (('head_rvec', r), ('head_tvec', t)):
+        if v.ndim >= 2 and v.shape[-2:] == (3, 1):
+            v = v[..., 0]
+        if v.ndim < 1 or v.shape[-1] != 3:
+            raise ValueError('eye_pose: %s must be [..., 3] or [..., 3, 1], got %s' % (name, tuple(v.shape)))
+        vecs.append(v)
+    if c.ndim < 2 or c.shape[-2:] != (2, 3):
+        raise ValueError('eye_pose: eye_centers must be [..., 2, 3] (left, right), got %s' % (tuple(c.shape),))
+    lead = np.broadcast_shapes(K.shape[:-2], vecs[0].shape[:-1], vecs[1].shape[:-1], c.shape[:-2], f.shape, dn.shape)
+    out = np.zeros(lead + (18,), dtype=np.float32)
+    out[..., 0], out[..., 1], out[..., 2], out[..., 3] = K[..., 0, 0], K[..., 1, 1], K[..., 0, 2], K[..., 1, 2]
+    out[..., 4:7], out[..., 7:10] = vecs
+    out[..., 10:13], out[..., 13:16] = c[..., 0, :], c[..., 1, :]
+    out[..., 16], out[..., 17] = f, dn
+    return torch.from_numpy(out).to(camera_matrix.device) if as_torch else out
+
+
+def normalize_eyes(pose, size=None):
+    """Eye normalisation from pose rows, on the device: pose float32 [..., 18] (eye_pose) -> a dict of head_R [..., 3, 3],
+    left_o / right_o [..., 3], left_R / right_R [..., 3, 3], left_eye_warp / right_eye_warp [..., 3, 3], left_h / right_h [..., 2]
+    (float32) and pose_valid, bool [..., 2] (left, right): what a batch with `camera_frame` + `eye_pose` is given before the
+    networks run.  size: (H, W) of the eye patch, default the config's eyes_size.
+
+    The formulas are the published normalisation procedure the reference cites for the values it ships precomputed (Zhang et al.
+    2018, "Revisiting data normalization for appearance-based gaze estimation"): <side>_R has the rows (right, down, forward)
+    with forward the direction of the eye's origin o = head_R c + t and right orthogonal to the head's x axis; <side>_eye_warp is
+    inv(W) of W = Kn S R K^-1, S = diag(1, 1, distance_norm / |o|), in closed form and not rescaled; <side>_h = (asin M12,
+    atan2(M02, M22)) of M = R head_R, so head_R = Rx(a) seen on the optical axis gives h = (-a, 0) and Ry(b) gives (0, b).  None of
+    it could be compared with the EVE dataset's own values: the dataset is on no machine this package was built on.  An eye with
+    pose_valid False (a NaN, a non-positive focal length or distance, an origin behind the camera, a head x axis along the line
+    of sight) has a zero warp -- a black patch -- R = I, o = 0, h = 0.  The contract is include/eve_hip.h eve_eye_pose_normalize."""
+    if not torch.is_tensor(pose) or pose.dtype != torch.float32 or pose.dim() < 1 or pose.shape[-1] != 18:
+        raise TypeError('expected float32 pose rows shaped [..., 18], got %s %s' % (getattr(pose, 'dtype', type(pose)),
+                                                                                   tuple(getattr(pose, 'shape', ()))))
+    if pose.numel() == 0:
+        raise ValueError('normalize_eyes: no pose rows (shape %s)' % (tuple(pose.shape),))
+    lead = tuple(pose.shape[:-1])
+    hw = eye_patch_hw() if size is None else (int(size[0]), int(size[1]))
+    head_R, o, R, warp, h, valid = default_kernels().eye_pose_normalize(pose.reshape(-1, 18).contiguous(), hw)
+    out = {'head_R': head_R.view(lead + (3, 3))}
+    for e, side in enumerate(('left', 'right')):
+        out[side + '_o'] = o[e].view(lead + (3,))
+        out[side + '_R'] = R[e].view(lead + (3, 3))
+        out[side + '_eye_warp'] = warp[e].view(lead + (3, 3))
+        out[side + '_h'] = h[e].view(lead + (2,))
+    out['pose_valid'] = valid.view((2,) + lead).movedim(0, -1) != 0
+    return out
 
 
 def warp_eye_patches(frames, warps, size=None, lens=None):

@@ -23,7 +23,7 @@ import torch.nn as nn
 
 from . import losses, ops
 from .config import get_config
-from .eye_net import EyeNet, eye_input
+from .eye_net import EyeNet, eye_input, eye_pose_batch
 from .kernels import default_kernels
 
 
@@ -225,7 +225,8 @@ class EVE(nn.Module):
         if self.training:
             assert len(full_input_dict) == 1
             full_input_dict = next(iter(full_input_dict.values()))
-        d = full_input_dict
+        # (the pose form -- camera_frame + eye_pose -- becomes the warp form in a copy, before the labels read left_o and left_R)
+        d = eye_pose_batch(full_input_dict, cfg)
         self.calculate_additional_labels(d, current_epoch=current_epoch)
         B, T = eye_input(d).shape[:2]
 
@@ -256,6 +257,8 @@ class EVE(nn.Module):
         output_dict = {k_: v for k_, v in inter.items() if k_.startswith('output_')}
         output_dict['left_pupil_size'] = inter['left_pupil_size']
         output_dict['right_pupil_size'] = inter['right_pupil_size']
+        if 'eye_pose' in full_input_dict:                             # the pose form: reported, folded into no validity
+            output_dict['pose_valid'] = d['pose_valid']
         if self.output_predictions:                                   # eve.py:194-222
             for key in ('timestamps', 'o', 'left_R', 'head_R', 'millimeters_per_pixel', 'pixels_per_millimeter',
                         'camera_transformation', 'inv_camera_transformation'):
@@ -306,8 +309,9 @@ class EVE(nn.Module):
 
     def _predict_sequence(self, d, eye_states, refine_states, reset=None, return_heatmaps=False, lengths=None):
         """The prediction part of forward() for one chunk of an EVEStream: eval only, no labels, no losses.  d: the chunk's
-        inputs [B, Tc, ...] (not modified; the eyes as patches, or as camera_frame + {left,right}_eye_warp with an optional
-        camera_lens [B, Tc, 12] for raw frames -- eye_net.eye_input); eye_states / refine_states: the carried state buffers of the two networks
+        inputs [B, Tc, ...] (not modified; the eyes as patches, as camera_frame + {left,right}_eye_warp, or as camera_frame +
+        eye_pose [B, Tc, 18], which also stands in for {left,right}_h / _o / _R and head_R and adds pose_valid to the result; both
+        camera forms with an optional camera_lens [B, Tc, 12] for raw frames -- eye_net.eye_input, eye_pose_batch); eye_states / refine_states: the carried state buffers of the two networks
         (EyeNet._stream_state_buffers, RefineNet._stream_state_buffers), read as the state before the chunk and overwritten with
         the state after it; reset: None or int32 [2B] device flags (stream b's flag at b and B + b) -- flagged streams start from
         zero; lengths: None or int32 [2B] device frame counts in the same layout -- stream b consumes its first lengths[b] frames
@@ -316,7 +320,8 @@ class EVE(nn.Module):
         heatmap_final when asked."""
         assert not self.training, 'EVE._predict_sequence is eval-only'
         B = eye_input(d).shape[0]
-        d = dict(d)
+        posed = 'eye_pose' in d
+        d = dict(eye_pose_batch(d, self.config))
         if 'left_o' in d:
             d['o'] = _mean2(d['left_o'], d['right_o'])
         inter = dict(self.eye_net._stream_sequence(d, eye_states, reset, lengths))
@@ -327,6 +332,8 @@ class EVE(nn.Module):
             inter['heatmap_final'] = hf
             self._final_block(d, inter, hf)
         out = {k_: inter[k_] for k_ in self.PREDICTION_KEYS if k_ in inter}
+        if posed:
+            out['pose_valid'] = d['pose_valid']
         if return_heatmaps and 'heatmap_final' in inter:
             out['heatmap_final'] = inter['heatmap_final']
         return out

@@ -39,13 +39,48 @@ def _wants_grad(t):
 EYE_PATCH_KEYS = ('left_eye_patch', 'right_eye_patch')
 EYE_CAMERA_KEYS = ('camera_frame', 'left_eye_warp', 'right_eye_warp')
 EYE_LENS_KEY = 'camera_lens'                 # optional with the camera form: raw frames of a camera with lens distortion
+EYE_POSE_KEY = 'eye_pose'                    # the pose form: camera_frame + one packed row per frame (data.eye_pose)
+# what eye_pose_batch derives from the rows -- a batch holds the rows or these, never both
+EYE_POSE_DERIVED = ('head_R', 'left_o', 'right_o', 'left_R', 'right_R', 'left_eye_warp', 'right_eye_warp', 'left_h', 'right_h', 'pose_valid')
+
+
+def _camera_frame(batch):
+    frames = batch['camera_frame']
+    if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[4] not in (3, 4):
+        raise TypeError('camera_frame must be uint8 [B, T, IH, IW, 3 | 4], got %s %s' % (
+            getattr(frames, 'dtype', type(frames)), tuple(getattr(frames, 'shape', ()))))
+    return frames
+
+
+def _camera_lens(batch, frames):
+    if EYE_LENS_KEY in batch:
+        lens = batch[EYE_LENS_KEY]
+        if not torch.is_tensor(lens) or lens.dtype != torch.float32 or tuple(lens.shape) != tuple(frames.shape[:2]) + (12,):
+            raise TypeError('%s must be float32 %s, got %s %s' % (EYE_LENS_KEY, tuple(frames.shape[:2]) + (12,),
+                                                                   getattr(lens, 'dtype', type(lens)), tuple(getattr(lens, 'shape', ()))))
 
 
 def eye_input(batch):
     """The tensor that carries a batch's [B, T] and its device: left_eye_patch, or camera_frame when the eyes come as whole
-    camera frames plus per-eye homographies.  Raises on a batch that holds both forms, half of one, or tensors of the wrong
-    dtype or shape for the camera form.  The camera form may carry camera_lens, float32 [B, T, 12] (data.camera_lens): one
-    camera per frame, for both eyes."""
+    camera frames plus per-eye homographies (the warp form) or plus eye_pose, float32 [B, T, 18] rows from data.eye_pose (the
+    pose form: the homographies, <side>_R, <side>_o, <side>_h and head_R are derived on the device -- eye_pose_batch).  Raises
+    on a batch that holds two forms, half of one, eye_pose next to a key it derives, or tensors of the wrong dtype or shape for
+    the camera forms.  Both camera forms may carry camera_lens, float32 [B, T, 12] (data.camera_lens): one camera per frame,
+    for both eyes."""
+    if EYE_POSE_KEY in batch:
+        clash = [k_ for k_ in EYE_PATCH_KEYS + EYE_POSE_DERIVED if k_ in batch]
+        if clash:
+            raise ValueError('%s derives %s and stands in for %s: found %s beside it' % (
+                EYE_POSE_KEY, ', '.join(EYE_POSE_DERIVED), ' / '.join(EYE_PATCH_KEYS), ', '.join(clash)))
+        if 'camera_frame' not in batch:
+            raise ValueError('%s goes with camera_frame: the patches are cut from it' % EYE_POSE_KEY)
+        frames = _camera_frame(batch)
+        pose = batch[EYE_POSE_KEY]
+        if not torch.is_tensor(pose) or pose.dtype != torch.float32 or tuple(pose.shape) != tuple(frames.shape[:2]) + (18,):
+            raise TypeError('%s must be float32 %s, got %s %s' % (EYE_POSE_KEY, tuple(frames.shape[:2]) + (18,),
+                                                                   getattr(pose, 'dtype', type(pose)), tuple(getattr(pose, 'shape', ()))))
+        _camera_lens(batch, frames)
+        return frames
     has_patch = [k_ for k_ in EYE_PATCH_KEYS if k_ in batch]
     has_cam = [k_ for k_ in EYE_CAMERA_KEYS if k_ in batch]
     if has_patch and has_cam:
@@ -59,21 +94,40 @@ def eye_input(batch):
     if len(has_cam) != len(EYE_CAMERA_KEYS):
         raise ValueError('the camera form needs %s: missing %s' % (
             ', '.join(EYE_CAMERA_KEYS), ', '.join(k_ for k_ in EYE_CAMERA_KEYS if k_ not in batch)))
-    frames = batch['camera_frame']
-    if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[4] not in (3, 4):
-        raise TypeError('camera_frame must be uint8 [B, T, IH, IW, 3 | 4], got %s %s' % (
-            getattr(frames, 'dtype', type(frames)), tuple(getattr(frames, 'shape', ()))))
+    frames = _camera_frame(batch)
     for k_ in EYE_CAMERA_KEYS[1:]:
         w = batch[k_]
         if not torch.is_tensor(w) or w.dtype != torch.float32 or tuple(w.shape) != tuple(frames.shape[:2]) + (3, 3):
             raise TypeError('%s must be float32 %s, got %s %s' % (k_, tuple(frames.shape[:2]) + (3, 3), getattr(w, 'dtype', type(w)),
                                                                    tuple(getattr(w, 'shape', ()))))
-    if EYE_LENS_KEY in batch:
-        lens = batch[EYE_LENS_KEY]
-        if not torch.is_tensor(lens) or lens.dtype != torch.float32 or tuple(lens.shape) != tuple(frames.shape[:2]) + (12,):
-            raise TypeError('%s must be float32 %s, got %s %s' % (EYE_LENS_KEY, tuple(frames.shape[:2]) + (12,),
-                                                                   getattr(lens, 'dtype', type(lens)), tuple(getattr(lens, 'shape', ()))))
+    _camera_lens(batch, frames)
     return frames
+
+
+def eye_pose_batch(batch, config=None):
+    """The pose form turned into the warp form: a batch without eye_pose comes back as it is; one with it is checked (eye_input)
+    and copied, and in the copy eye_pose is replaced by what ONE eve_eye_pose_normalize launch derives from the rows for the
+    config's eyes_size: head_R [B, T, 3, 3], <side>_o [B, T, 3], <side>_R [B, T, 3, 3], <side>_eye_warp [B, T, 3, 3] (inv(W): what
+    the eye-warp kernels take), <side>_h [B, T, 2] and pose_valid, bool [B, T, 2] (left, right).  An eye whose pose is not usable
+    (a NaN, a head behind the camera, ...) has pose_valid False, a zero warp -- so a black patch -- R = I, o = 0 and h = 0;
+    pose_valid is reported and folded into nothing.  Every entry point that takes the eyes calls this once, before anything
+    reads a derived key; the copy holds no eye_pose, so the modules below it see the warp form."""
+    if EYE_POSE_KEY not in batch:
+        return batch
+    from . import data
+    frames = eye_input(batch)
+    B, T = frames.shape[:2]
+    head_R, o, R, warp, h, valid = default_kernels().eye_pose_normalize(batch[EYE_POSE_KEY].reshape(B * T, 18).contiguous(),
+                                                                        data.eye_patch_hw(config))
+    d = {k_: v for k_, v in batch.items() if k_ != EYE_POSE_KEY}
+    d['head_R'] = head_R.view(B, T, 3, 3)
+    for e, side in enumerate(('left', 'right')):
+        d[side + '_o'] = o[e].view(B, T, 3)
+        d[side + '_R'] = R[e].view(B, T, 3, 3)
+        d[side + '_eye_warp'] = warp[e].view(B, T, 3, 3)
+        d[side + '_h'] = h[e].view(B, T, 2)
+    d['pose_valid'] = valid.view(2, B, T).permute(1, 2, 0) != 0
+    return d
 
 
 def default_compute_dtype():
@@ -321,6 +375,7 @@ class EyeNet(nn.Module):
         configuration takes the per-layer path.  Also returns the predictions (detached) under the forward_sequence keys."""
         from . import losses
         config = config if config is not None else self.config
+        batch = eye_pose_batch(batch, self.config)
         P = self._get_packs()
         feats, B, T = self._sequence_features(batch, P)
         self.last_tail_path = 'node' if self._tail_loss_node_ok(batch, T, feats) else 'layers'
@@ -379,9 +434,12 @@ class EyeNet(nn.Module):
         the patches, of the config's eyes_size, are then cut on the device.  With camera_lens, float32 [B, T, 12] (data.camera_lens:
         the intrinsics and OpenCV distortion coefficients of the camera behind each frame), camera_frame is the RAW frame and the
         warps refer to the undistorted image the networks were trained on: the cut undistorts as it samples.
+        Or the pose form: camera_frame and eye_pose, float32 [B, T, 18] (data.eye_pose), in place of the patches, the warps AND
+        {left,right}_h -- eye_pose_batch derives them on the device.
         Returns the B x T x ... tensors eve.py:174-182 would stack: <side>_g_initial [B,T,2],
         <side>_pupil_size [B,T], <side>_eye_rnn_states_<i> [B,T,H] per cell ((h, c) pair of them for LSTM).
         initial_states: {side: h [B,H]} or {side: [per-cell h | (h, c) | None]}."""
+        batch = eye_pose_batch(batch, self.config)
         P = self._get_packs()
         feats, B, T = self._sequence_features(batch, P)
         return self._sequence_tail(feats, batch, B, T, initial_states, P)
@@ -536,6 +594,7 @@ class EyeNet(nn.Module):
         lengths[s] - 1 (eve_stream_state_rows_at, eve_eye_tail_stream_fwd_len) or kept when that is 0, and its outputs from frame
         lengths[s] on are unspecified.  Returns the forward_sequence prediction keys (<side>_g_initial, <side>_pupil_size)."""
         k = default_kernels()
+        batch = eye_pose_batch(batch, self.config)
         P = self._get_packs()
         feats, B, T = self._sequence_features(batch, P)
         head_pose = None

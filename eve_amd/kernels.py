@@ -493,6 +493,25 @@ class HipKernels(object):
                                                        self._p(dst), self._stream()))
         return dst
 
+    def eye_pose_normalize(self, pose, out_hw):
+        """Eye normalisation derived from the head pose, both eyes of N frames in one launch: pose float32 [N,18] =
+        (fx, fy, cx, cy, rvec, tvec, left eye centre, right eye centre, focal_norm, distance_norm) per frame (data.eye_pose),
+        out_hw = (OH, OW) of the patch -> (head_R [N,3,3], o [2,N,3], R [2,N,3,3], warp [2,N,3,3] = inv(W), h [2,N,2] float32,
+        valid uint8 [2,N]), eye-major: index 0 the left eye, 1 the right one, each a contiguous [N, ...] tensor.  An invalid eye
+        has warp = 0, R = I, o = 0, h = 0 (include/eve_hip.h eve_eye_pose_normalize)."""
+        if not torch.is_tensor(pose) or pose.dtype != torch.float32 or pose.dim() != 2 or pose.shape[1] != 18:
+            raise TypeError('eye_pose_normalize: pose must be float32 [N, 18], got %s %s' % (getattr(pose, 'dtype', type(pose)),
+                                                                                          tuple(getattr(pose, 'shape', ()))))
+        if not pose.is_contiguous():
+            raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        N, (OH, OW) = pose.shape[0], (int(out_hw[0]), int(out_hw[1]))
+        new = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=pose.device)
+        head_R, o, R, warp, h = new(N, 3, 3), new(2, N, 3), new(2, N, 3, 3), new(2, N, 3, 3), new(2, N, 2)
+        valid = new(2, N, dtype=torch.uint8)
+        self._ck(self.lib.eve_eye_pose_normalize(N, self._p(pose), OH, OW, self._p(head_R), self._p(o), self._p(R), self._p(warp), self._p(h),
+                                                 self._p(valid), self._stream()))
+        return head_R, o, R, warp, h, valid
+
     # ------------------------------------------------------------------ gaze geometry / heat-maps / soft-argmax
     def _flat32(self, t, shape, what):
         t = t.contiguous()

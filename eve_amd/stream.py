@@ -179,6 +179,18 @@ class EVEStream(object):
         through the lens model before the frame is read (no undistorted frame is made; zero coefficients give the plain bits).
         A chunk with the key captures a graph of its own, and a replay reads the rows of the chunk at hand.
 
+        Or as the pose form, straight from the face tracker: camera_frame plus eye_pose, float32 [B, Tc, 18] rows from data.eye_pose
+        = (fx, fy, cx, cy, rvec, tvec, left and right eye centre in the head model, focal_norm, distance_norm) -- cv2.solvePnP's
+        result, the camera matrix of the undistorted image and the virtual camera of the patch.  eye_pose then stands in for
+        left_eye_warp / right_eye_warp AND for {left,right}_h, {left,right}_o, {left,right}_R and head_R (a chunk that holds one of
+        them, or patches, beside eye_pose is refused): one eve_eye_pose_normalize launch derives them for the config's eyes_size by
+        the published normalisation procedure the reference cites (data.normalize_eyes has the conventions, the sign of h
+        included; none of it could be compared with the EVE dataset's own values).  The launch sits inside the step and inside
+        the captured graph, the rows are a graph input like every other chunk tensor -- a replay reads the rows of the chunk at
+        hand -- and the key of the graph covers them; ragged steps and camera_lens combine with it unchanged.  The result gains
+        pose_valid, bool [B, Tc, 2] (left, right): False where a pose was not usable (a NaN, a head behind the camera, ...), whose
+        eye then got a black patch, R = I, o = 0 and h = 0.  pose_valid is reported, not folded into any other validity.
+
         screen_frame is float [B, Tc, 3, H, W] at the configured screen size, uint8 [B, Tc, H, W, 3] at that size, or a live
         capture as it comes off the desktop: uint8 [B, Tc, IH, IW, 3 | 4] at any resolution from the screen size up to 16 843 009
         pixels (3840 x 2160 included), area-averaged down on the device by eve_screen_u8_area_to_nchw inside the step -- and

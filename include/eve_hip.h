@@ -753,6 +753,43 @@ int eve_eye_warp_lens_u8_to_nchw(long long N, int IH, int IW, int C, const uint8
                                  int OH, int OW, float* dst_nchw, eve_stream_t stream);
 int eve_eye_warp_lens_u8_to_stem(int dtype /* EVE_DT_BF16 | EVE_DT_F16 */, long long N, int IH, int IW, int C, const uint8_t* frames_nhwc,
                                  const float* warps, const float* lens, int OH, int OW, void* x_padded, eve_stream_t stream);
+/* Eye normalisation derived from the head pose, one launch for both eyes of N frames: everything the pipeline reads per frame and
+ * eye follows from the face tracker's solvePnP result and the camera matrix.  pose [N][18] float, widened to float64:
+ *   (fx, fy, cx, cy,  r0, r1, r2,  t0, t1, t2,  l0, l1, l2,  q0, q1, q2,  focal_norm, distance_norm)
+ * fx..cy: the camera matrix of the UNDISTORTED image (the image the warps refer to); r, t: the head's rvec and tvec; l, q: the left
+ * and right eye centres in head-model coordinates, in t's length unit; focal_norm (f, patch pixels) and distance_norm (dn): the
+ * virtual camera of the OH x OW patch, whose principal point is (OW/2, OH/2).  The procedure is the published one the reference
+ * cites for the values it ships precomputed (Zhang et al. 2018, "Revisiting data normalization for appearance-based gaze
+ * estimation").  Contract: float64, every operation rounded on its own (no contraction), in exactly this association; every stage
+ * is rounded to float32 and the NEXT STAGE CONTINUES FROM THE FLOAT32 VALUES JUST WRITTEN:
+ *   1. head_R   th = sqrt((r0*r0 + r1*r1) + r2*r2); th == 0 or an r that is not finite: head_R = I; else k = r / th,
+ *               c = cos(th), s = sin(th), v = 1.0 - c, vk_i = v*k_i, sk_i = s*k_i,
+ *                   head_R = [[c + vk0*k0, vk0*k1 - sk2, vk0*k2 + sk1], [vk1*k0 + sk2, c + vk1*k1, vk1*k2 - sk0],
+ *                             [vk2*k0 - sk1, vk2*k1 + sk0, c + vk2*k2]]                                  -> float32: H
+ *   2. o_e      o_i = ((H[i][0]*c0 + H[i][1]*c1) + H[i][2]*c2) + t_i, c = l for the left eye, q for the right   -> float32: o
+ *   3. R_e      d = sqrt((o0*o0 + o1*o1) + o2*o2), fw = o / d, hx = H[:, 0]; dn_ = cross(fw, hx), nd = its norm (as d),
+ *               down = dn_ / nd; rt_ = cross(down, fw), nr = its norm, right = rt_ / nr;
+ *               cross(a, b) = (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0); R_e = rows (right, down, fw)       -> float32: R
+ *   4. warp_e   = inv(W) = K R^T diag(1, 1, d / dn) Kn^-1 in closed form (no general inverse): z = d / dn, g = 1.0 / f,
+ *               px = (OW * 0.5) / f, py = (OH * 0.5) / f, A[i] = (R[0][i], R[1][i], R[2][i]*z),
+ *               B[0] = fx*A[0] + cx*A[2], B[1] = fy*A[1] + cy*A[2], B[2] = A[2] (per column),
+ *               warp[i] = (B[i][0]*g, B[i][1]*g, (B[i][2] - B[i][0]*px) - B[i][1]*py)                           -> float32
+ *               Not rescaled: its third row times a patch pixel is positive for a head in front of the camera, which the eye
+ *               warp kernels require (their Wd > 0).
+ *   5. h_e      m_i = (R[i][0]*H[0][2] + R[i][1]*H[1][2]) + R[i][2]*H[2][2] (third column of R_e head_R);
+ *               h_e = (asin(min(max(m_1, -1.0), 1.0)), atan2(m_0, m_2))                                         -> float32
+ *               SIGN CONVENTION: head_R = Rx(a) seen on the optical axis gives h = (-a, 0), head_R = Ry(b) gives h = (0, b).
+ *   6. valid_e  = every one of the 18 inputs finite && fx, fy, f, dn > 0 && o_2 > 0 && d > 0 && nd > 0 && nr > 0 (a NaN fails
+ *               its comparison).  An invalid eye gets warp = 0 (the warp kernels then give a black patch), R = I, o = 0, h = 0.
+ * o, R, warp and valid are bit-exact functions of the head_R written (only + - * / sqrt remain, each correctly rounded); head_R
+ * and h go through sin / cos / asin / atan2 and may sit one float32 ulp from another libm's result.  Layout, eye-major (left, then
+ * right), so that each side is a contiguous [N][...] array the next launch reads without a copy: head_R [N][9], o [2][N][3],
+ * R [2][N][9], warp [2][N][9], h [2][N][2] float; valid [2][N] uint8.  One thread per (frame, eye); the left eye's thread also
+ * writes head_R.  Not offered: gradients, the inverse (rotation matrix -> rvec), skew.  None of it could be compared with the EVE
+ * dataset's own {left,right}_{R,W,h,o} values: the dataset is on no machine this library was built on.  Refused without a
+ * launch: a null pointer, N < 1 or N >= 2^30, OH or OW outside 1..4096.                                                         */
+int eve_eye_pose_normalize(long long N, const float* pose, int OH, int OW, float* head_R, float* o, float* R, float* warp, float* h,
+                           uint8_t* valid, eve_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,7 @@
 and of one EVEStream step fed whole camera frames next to the same step fed pre-cut uint8 patches.
 
     python tools/bench_eye_warp.py [--patches 64] [--size 1920x1080] [--iters 500] [--rounds 5] [--shapes 1x1 8x4 32x2]
-                                   [--steps 50] [--dtype bf16] [--lens] [--markdown profiles/table.md]
+                                   [--steps 50] [--dtype bf16] [--lens] [--pose] [--markdown profiles/table.md]
 
 Part 1, per launch, the four routes interleaved in one process (the median over the rounds of events around `iters` calls):
     warp_nchw / warp_stem   N patches of 128 x 128 cut from N frames of the given size, each by its own rotated, scaled warp with a
@@ -12,12 +12,15 @@ Part 1, per launch, the four routes interleaved in one process (the median over 
                             after two cv2.warpPerspective calls per frame on the host and a second upload (neither is timed here)
     lens_nchw / lens_stem   with --lens: the same patches through eve_eye_warp_lens_u8_to_nchw / _to_stem, every frame behind the
                             rational eight-coefficient lens of lens_rows() (the arithmetic does not depend on the values)
+    pose_normalize          with --pose: eve_eye_pose_normalize on N pose rows (both eyes of N frames: 2 N threads) into preallocated
+                            outputs -- the launch that derives the warps, R, o, h and head_R from the face tracker's solvePnP result
 The rate quoted for a warp is (bytes its loads ask for: 4 taps x 3 channels per output pixel) + (bytes stored) over the time; the
 taps overlap, so the distinct bytes behind them are about a quarter -- it is a rate of the kernel's traffic, not of HBM.
 
 Part 2, per EVEStream step under graph replay (refine_net config): `camera` feeds camera_frame + two warps per frame, `patches`
 the uint8 [B, Tc, 128, 128, 3] patch pair.  The camera step also copies B * Tc whole frames into the graph's input buffer.  With
---lens a third stream, `lens`, feeds the camera keys plus camera_lens."""
+--lens a third stream, `lens`, feeds the camera keys plus camera_lens.  With --pose another stream, `pose`, feeds camera_frame + eye_pose
+and none of the keys the rows derive (warps, <side>_h, <side>_o, <side>_R, head_R): one more launch inside the graph."""
 import argparse
 import json
 import math
@@ -68,6 +71,16 @@ def lens_rows(n, IH, IW):
     return torch.tensor([row] * n, dtype=torch.float32)
 
 
+def pose_rows(n, IH, IW, seed):
+    """n pose rows of a 1080p-like webcam scaled to the frame: the head 500..700 mm in front of it, the patch one camera pixel per
+    patch pixel at the normalised distance, so every 128 x 128 patch stays inside the frame."""
+    g = np.random.default_rng(seed)
+    f = 1400.0 * IW / 1920.0
+    rows = [[f, f, IW / 2, IH / 2] + list(g.uniform(-0.3, 0.3, 3)) + [g.uniform(-60, 60), g.uniform(-40, 40), g.uniform(500, 700)] +
+            [-32.0, -35.0, 25.0, 32.0, -35.0, 25.0, f, 600.0] for _ in range(n)]
+    return torch.tensor(np.array(rows), dtype=torch.float32)
+
+
 def median(v):
     return sorted(v)[len(v) // 2]
 
@@ -88,6 +101,17 @@ def launches(args, IH, IW):
         lens = lens_rows(N, IH, IW).cuda()
         routes['lens_nchw'] = lambda: k.eye_warp_lens_u8_to_nchw(frames, warps, lens, HW)
         routes['lens_stem'] = lambda: k.eye_warp_lens_u8_to_stem(frames, warps, lens, HW, out=packed)
+    if args.pose:
+        import ctypes
+        rows = pose_rows(N, IH, IW, seed=N).cuda()
+        outs = [torch.empty(shape, device='cuda') for shape in ((N, 9), (2, N, 3), (2, N, 9), (2, N, 9), (2, N, 2))]
+        outs.append(torch.empty((2, N), dtype=torch.uint8, device='cuda'))
+        ptrs = [ctypes.c_void_p(t.data_ptr()) for t in [rows] + outs]
+
+        def pose_launch():
+            status = k.lib.eve_eye_pose_normalize(N, ptrs[0], HW[0], HW[1], *ptrs[1:], ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+            assert status == 0, k.lib.eve_last_error()
+        routes['pose_normalize'] = pose_launch
     for fn in routes.values():                   # warm up: code objects, allocator
         for _ in range(5):
             fn()
@@ -111,6 +135,10 @@ def launches(args, IH, IW):
             res['lens_%s_bytes' % form] = res['warp_%s_bytes' % form]
             res['lens_%s_GBps' % form] = round(res['lens_%s_bytes' % form] / (1e-3 * median(times['lens_' + form])) / 1e9, 1)
             res['lens_over_warp_%s' % form] = round(median(times['lens_' + form]) / median(times['warp_' + form]), 3)
+    if args.pose:
+        assert outs[5].all(), 'bench poses must be valid'
+        pose_launch()
+        res['pose_kernel'] = k.lib.eve_last_kernel().decode()
     k.eye_warp_u8_to_stem(frames, warps, HW, out=packed)
     res['kernel'] = k.lib.eve_last_kernel().decode()
     if args.lens:
@@ -142,6 +170,10 @@ def stream_steps(args, IH, IW):
         streams = {'camera': (eve_amd.EVEStream(model, B), cam), 'patches': (eve_amd.EVEStream(model, B), pat)}
         if args.lens:
             streams['lens'] = (eve_amd.EVEStream(model, B), dict(cam, camera_lens=lens_rows(B * Tc, IH, IW).view(B, Tc, 12).cuda()))
+        if args.pose:
+            from eve_amd.eye_net import EYE_POSE_DERIVED
+            streams['pose'] = (eve_amd.EVEStream(model, B), dict({k_: v for k_, v in cam.items() if k_ not in EYE_POSE_DERIVED},
+                                                                 eye_pose=pose_rows(B * Tc, IH, IW, seed=B).view(B, Tc, 18).cuda()))
         for s, chunk in streams.values():
             for _ in range(3):
                 s.step(chunk)                    # capture + warm replays
@@ -157,6 +189,8 @@ def stream_steps(args, IH, IW):
         res['camera_minus_patches_ms'] = round(res['camera_step_ms'] - res['patches_step_ms'], 4)
         if args.lens:
             res['lens_minus_camera_ms'] = round(res['lens_step_ms'] - res['camera_step_ms'], 4)
+        if args.pose:
+            res['pose_minus_camera_ms'] = round(res['pose_step_ms'] - res['camera_step_ms'], 4)
         res['camera_frame_MB_copied'] = round(B * Tc * IH * IW * 3 / 1e6, 1)
         rows.append(res)
         print(json.dumps(res), flush=True)
@@ -175,6 +209,7 @@ def main():
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--dtype', default='bf16', choices=sorted(DTYPES))
     ap.add_argument('--lens', action='store_true', help='also time the lens launches and an EVEStream step with camera_lens')
+    ap.add_argument('--pose', action='store_true', help='also time eve_eye_pose_normalize and an EVEStream step with eye_pose rows')
     ap.add_argument('--markdown', default=None, help='also write the tables to this file')
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -185,7 +220,11 @@ def main():
         print(json.dumps(one), flush=True)
         rows = stream_steps(args, IH, IW) if args.shapes else []
     lines = ['| launch (%d patches, %s frames) | us | min .. max | bytes | GB/s |' % (one['patches'], one['frame']), '|---|---|---|---|---|']
-    for name in ('warp_nchw', 'lens_nchw', 'crop_nchw', 'warp_stem', 'lens_stem', 'crop_stem') if args.lens else ('warp_nchw', 'crop_nchw', 'warp_stem', 'crop_stem'):
+    if args.pose:
+        one['pose_normalize_bytes'] = one['patches'] * (18 * 4 + 9 * 4 + 2 * (3 + 9 + 9 + 2) * 4 + 2)
+        one['pose_normalize_GBps'] = round(one['pose_normalize_bytes'] / (1e-6 * one['pose_normalize_us']) / 1e9, 2)
+    names = ('warp_nchw', 'lens_nchw', 'crop_nchw', 'warp_stem', 'lens_stem', 'crop_stem') if args.lens else ('warp_nchw', 'crop_nchw', 'warp_stem', 'crop_stem')
+    for name in names + (('pose_normalize',) if args.pose else ()):
         lines.append('| %s | %.2f | %.2f .. %.2f | %d | %.1f |' % (name, one[name + '_us'], one[name + '_us_min_max'][0], one[name + '_us_min_max'][1],
                                                                   one[name + '_bytes'], one[name + '_GBps']))
     if rows:
@@ -199,6 +238,12 @@ def main():
             lines.append('| %d x %d | %.4f | %.4f .. %.4f | %.4f | %.4f .. %.4f | %.4f |' % (
                 r['B'], r['Tc'], r['lens_step_ms'], r['lens_step_ms_min_max'][0], r['lens_step_ms_min_max'][1], r['camera_step_ms'],
                 r['camera_step_ms_min_max'][0], r['camera_step_ms_min_max'][1], r['lens_minus_camera_ms']))
+    if rows and args.pose:
+        lines += ['', '| B x Tc (%s) | pose step ms | min .. max | camera step ms | min .. max | pose - camera ms |' % args.dtype, '|---|---|---|---|---|---|']
+        for r in rows:
+            lines.append('| %d x %d | %.4f | %.4f .. %.4f | %.4f | %.4f .. %.4f | %.4f |' % (
+                r['B'], r['Tc'], r['pose_step_ms'], r['pose_step_ms_min_max'][0], r['pose_step_ms_min_max'][1], r['camera_step_ms'],
+                r['camera_step_ms_min_max'][0], r['camera_step_ms_min_max'][1], r['pose_minus_camera_ms']))
     table = '\n'.join(lines)
     print(table, flush=True)
     if args.markdown:
