@@ -44,8 +44,6 @@ struct CsGeom {
     static constexpr size_t lds_bytes(int out_ch) { return (size_t)(HALO + CS_PIX * out_ch) * sizeof(float); }
 };
 
-__device__ __forceinline__ float cs_sigmoid(float z) { return 1.f / (1.f + __expf(-z)); }   // = recurrent.hip's sigmoidf_
-
 // halo offset (floats) of pixel p's centre
 template <int STR>
 __device__ __forceinline__ int cs_halo_at(int p) { return (((p >> 3) + 1) * 10 + (p & 7) + 1) * STR; }
@@ -233,8 +231,8 @@ __global__ __launch_bounds__(CS_NT) void cgru_scan_f32_fwd_kernel(const int B, c
         __syncthreads();
         cs_conv_all<STR, C2, C2, false>(halo, w1, b1, g, C2, wave, lane);
         CS_FOR_ELEMS(k, p, c) {
-            const float r = cs_rnd<S>(cs_sigmoid(g[p * C2 + c]));       // (16-bit: the stored gate is the one every later stage sees)
-            u[k] = cs_rnd<S>(cs_sigmoid(g[p * C2 + C + c]));
+            const float r = cs_rnd<S>(sigmoid_exact(g[p * C2 + c]));       // (16-bit: the stored gate is the one every later stage sees)
+            u[k] = cs_rnd<S>(sigmoid_exact(g[p * C2 + C + c]));
             const float v = cs_rnd<S>(r * h[k]);
             Elem<S>::st(ru + (tm + p) * C2 + c, r);
             Elem<S>::st(ru + (tm + p) * C2 + C + c, u[k]);
@@ -426,7 +424,7 @@ __device__ __forceinline__ void clstm_scan_f32_fwd_body(const int B, const int T
         cs_conv_all<STR, C2, C4, false>(halo, w, bias, g, C4, wave, lane);
         CS_FOR_ELEMS(k, p, c) {
             const float gi = g[p * C4 + c], gf = g[p * C4 + C + c], go = g[p * C4 + 2 * C + c], gc = g[p * C4 + 3 * C + c];
-            const float si = cs_sigmoid(gi), sf = cs_sigmoid(gf), so = cs_sigmoid(go), tg = tanhf(gc);
+            const float si = sigmoid_exact(gi), sf = sigmoid_exact(gf), so = sigmoid_exact(go), tg = tanhf(gc);
             cc[k] = sf * cc[k] + si * tg;
             h[k] = so * tanhf(cc[k]);
             if constexpr (TRAIN) {

@@ -21,17 +21,6 @@ constexpr int CG_SLICE = 224 * 64;              // bytes per 32-channel halo pla
 constexpr int CG_BSLOT = 128 * 64;              // one weight tile: 128 output channels x 32 k
 constexpr int CG_LDS = 6 * CG_SLICE + 4 * CG_BSLOT;
 
-typedef uint32_t cg_u32x2_t __attribute__((ext_vector_type(2)));
-typedef uint32_t cg_u32x4_t __attribute__((ext_vector_type(4)));
-
-// Gate non-linearities of the 16-bit scan.  The results are rounded to 16 bits on the spot, so one-ulp float building blocks
-// (v_exp_f32, v_rcp_f32) are exact enough -- and the epilogues are where this kernel's time is: per frame a wave runs 72 MFMA
-// steps of ~60 instructions and two epilogues that were ~1 750 + ~3 800 instructions with tanhf and IEEE divisions expanded 64
-// times each (round 5; the float32 scan of cell_scan_f32.hip keeps tanhf / the division).
-__device__ __forceinline__ float cg_sigmoid(float z) { return __builtin_amdgcn_rcpf(1.f + __expf(-z)); }
-// tanh(z) = 1 - 2 / (1 + e^(2z)): saturates correctly (e^(2z) = inf -> 1, 0 -> -1); absolute error ~1e-7
-__device__ __forceinline__ float cg_tanh(float z) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * z)); }
-
 template <typename H>
 __global__ __launch_bounds__(256) void cgru_scan_fwd_kernel(const int B, const int T, const H* __restrict__ xs,
                                                             const H* __restrict__ h0, const H* __restrict__ w1,
@@ -174,11 +163,10 @@ __global__ __launch_bounds__(256) void cgru_scan_fwd_kernel(const int B, const i
                 const uint32_t la = lds0 + plane * CG_SLICE, lb = ldsB + (gpos & 3) * CG_BSLOT;
 #pragma unroll
                 for (int mt = 0; mt < 4; ++mt)
-                    fx[mt] = __builtin_bit_cast(uint4, *reinterpret_cast<const EVE_LDS cg_u32x4_t*>((uintptr_t)(la + abase[(tap / 3) & 1][mt] + ((tap / 3) * 10 + tap % 3) * 64)));
+                    fx[mt] = __builtin_bit_cast(uint4, lds_read16(la + abase[(tap / 3) & 1][mt] + ((tap / 3) * 10 + tap % 3) * 64));
 #pragma unroll
                 for (int nt = 0; nt < 4; ++nt)
-                    fw[nt] = __builtin_bit_cast(uint4, *reinterpret_cast<const EVE_LDS cg_u32x4_t*>(
-                        (uintptr_t)(lb + (conv == 0 ? brow1[nt] : brow2[nt]))));
+                    fw[nt] = __builtin_bit_cast(uint4, lds_read16(lb + (conv == 0 ? brow1[nt] : brow2[nt])));
             };
             auto mma = [&](const uint4 (&fx)[4], const uint4 (&fw)[4]) {
 #pragma unroll
@@ -222,8 +210,8 @@ __global__ __launch_bounds__(256) void cgru_scan_fwd_kernel(const int B, const i
                     const float4 bv = *reinterpret_cast<const float4*>(b1 + wn * 64 + c);
 #pragma unroll
                     for (int mt = 0; mt < 4; ++mt) {
-                        float v[4] = {cg_sigmoid(acc[mt][nt][0] + bv.x), cg_sigmoid(acc[mt][nt][1] + bv.y),
-                                      cg_sigmoid(acc[mt][nt][2] + bv.z), cg_sigmoid(acc[mt][nt][3] + bv.w)};
+                        float v[4] = {sigmoid_rcp(acc[mt][nt][0] + bv.x), sigmoid_rcp(acc[mt][nt][1] + bv.y),
+                                      sigmoid_rcp(acc[mt][nt][2] + bv.z), sigmoid_rcp(acc[mt][nt][3] + bv.w)};
                         // the stored (bf16) gate is the one every later stage sees
                         const uint32_t p0 = Elem<H>::pack2(v[0], v[1]), p1 = Elem<H>::pack2(v[2], v[3]);
                         v[0] = Elem<H>::lo(p0); v[1] = Elem<H>::hi(p0);
@@ -233,11 +221,11 @@ __global__ __launch_bounds__(256) void cgru_scan_fwd_kernel(const int B, const i
                         if (pg >= 0)
                             *reinterpret_cast<uint2*>(ru + ptm * 128 + wn * 64 + c) = make_uint2(p0, p1);
                         if (wn == 0) {
-                            const cg_u32x2_t hq = *reinterpret_cast<const EVE_LDS cg_u32x2_t*>((uintptr_t)lds_c4(2, mt, c));
+                            const u32x2_t hq = lds_read8(lds_c4(2, mt, c));
                             const uint32_t q0 = Elem<H>::pack2(v[0] * Elem<H>::lo(hq.x), v[1] * Elem<H>::hi(hq.x));
                             const uint32_t q1 = Elem<H>::pack2(v[2] * Elem<H>::lo(hq.y), v[3] * Elem<H>::hi(hq.y));
                             if (pg >= 0) {
-                                *reinterpret_cast<EVE_LDS cg_u32x2_t*>((uintptr_t)lds_c4(4, mt, c)) = cg_u32x2_t{q0, q1};
+                                lds_write8(lds_c4(4, mt, c), q0, q1);
                                 *reinterpret_cast<uint2*>(rh + ptm * CG_C + c) = make_uint2(q0, q1);
                             }
                         } else {
@@ -258,13 +246,13 @@ __global__ __launch_bounds__(256) void cgru_scan_fwd_kernel(const int B, const i
                 for (int mt = 0; mt < 4; ++mt) {
                     const int pg = pix_glob[mt];
                     if (pg < 0) continue;
-                    float o[4] = {cg_tanh(acc[mt][nt][0] + bv.x), cg_tanh(acc[mt][nt][1] + bv.y), cg_tanh(acc[mt][nt][2] + bv.z),
-                                  cg_tanh(acc[mt][nt][3] + bv.w)};
+                    float o[4] = {tanh_rcp(acc[mt][nt][0] + bv.x), tanh_rcp(acc[mt][nt][1] + bv.y), tanh_rcp(acc[mt][nt][2] + bv.z),
+                                  tanh_rcp(acc[mt][nt][3] + bv.w)};
                     const uint32_t o0 = Elem<H>::pack2(o[0], o[1]), o1 = Elem<H>::pack2(o[2], o[3]);
                     o[0] = Elem<H>::lo(o0); o[1] = Elem<H>::hi(o0);
                     o[2] = Elem<H>::lo(o1); o[3] = Elem<H>::hi(o1);
                     const uint32_t ha = lds_c4(2, mt, c);
-                    const cg_u32x2_t hq = *reinterpret_cast<const EVE_LDS cg_u32x2_t*>((uintptr_t)ha);
+                    const u32x2_t hq = lds_read8(ha);
                     const float hv[4] = {Elem<H>::lo(hq.x), Elem<H>::hi(hq.x),
                                          Elem<H>::lo(hq.y), Elem<H>::hi(hq.y)};
                     const float uv[4] = {Elem<H>::lo(ug[mt][nt].x), Elem<H>::hi(ug[mt][nt].x), Elem<H>::lo(ug[mt][nt].y), Elem<H>::hi(ug[mt][nt].y)};
@@ -272,7 +260,7 @@ __global__ __launch_bounds__(256) void cgru_scan_fwd_kernel(const int B, const i
 #pragma unroll
                     for (int r = 0; r < 4; ++r) hn[r] = (1.f - uv[r]) * o[r] + uv[r] * hv[r];
                     const uint32_t n0 = Elem<H>::pack2(hn[0], hn[1]), n1 = Elem<H>::pack2(hn[2], hn[3]);
-                    *reinterpret_cast<EVE_LDS cg_u32x2_t*>((uintptr_t)ha) = cg_u32x2_t{n0, n1};
+                    lds_write8(ha, n0, n1);
                     const size_t go = ((size_t)pg + (size_t)t * CG_PIX) * CG_C + c;
                     const size_t gtm = ((size_t)t * B * CG_PIX + pix_tm[mt]) * CG_C + c;
                     *reinterpret_cast<uint2*>(og + gtm) = make_uint2(o0, o1);
@@ -430,8 +418,8 @@ __global__ __launch_bounds__(256) void cgru_scan_bwd_kernel(const int B, const i
                     }
                     const uint2 p2 = make_uint2(Elem<H>::pack2(g2[0], g2[1]), Elem<H>::pack2(g2[2], g2[3]));
                     const uint2 p1 = make_uint2(Elem<H>::pack2(g1u[0], g1u[1]), Elem<H>::pack2(g1u[2], g1u[3]));
-                    *reinterpret_cast<EVE_LDS cg_u32x2_t*>((uintptr_t)lds_c4(0, mt, c)) = cg_u32x2_t{p2.x, p2.y};
-                    *reinterpret_cast<EVE_LDS cg_u32x2_t*>((uintptr_t)lds_c4(4, mt, c)) = cg_u32x2_t{p1.x, p1.y};
+                    lds_write8(lds_c4(0, mt, c), p2.x, p2.y);
+                    lds_write8(lds_c4(4, mt, c), p1.x, p1.y);
                     *reinterpret_cast<uint2*>(dg2_all + pt * CG_C + c) = p2;
                     *reinterpret_cast<uint2*>(dg1_all + pt * 128 + 64 + c) = p1;
                 }
@@ -456,10 +444,10 @@ __global__ __launch_bounds__(256) void cgru_scan_bwd_kernel(const int B, const i
                 const uint32_t la = lds0 + (pl0 + sl) * CG_SLICE, lb = ldsB + (gpos & 3) * CG_BSLOT;
 #pragma unroll
                 for (int mt = 0; mt < 4; ++mt)
-                    fx[mt] = __builtin_bit_cast(uint4, *reinterpret_cast<const EVE_LDS cg_u32x4_t*>((uintptr_t)(la + abase[(tap / 3) & 1][mt] + ((tap / 3) * 10 + tap % 3) * 64)));
+                    fx[mt] = __builtin_bit_cast(uint4, lds_read16(la + abase[(tap / 3) & 1][mt] + ((tap / 3) * 10 + tap % 3) * 64));
 #pragma unroll
                 for (int nt = 0; nt < 4; ++nt)
-                    fw[nt] = __builtin_bit_cast(uint4, *reinterpret_cast<const EVE_LDS cg_u32x4_t*>((uintptr_t)(lb + brow[nt])));
+                    fw[nt] = __builtin_bit_cast(uint4, lds_read16(lb + brow[nt]));
             };
             auto mma = [&](const uint4 (&fx)[4], const uint4 (&fw)[4]) {
 #pragma unroll
@@ -514,7 +502,7 @@ __global__ __launch_bounds__(256) void cgru_scan_bwd_kernel(const int B, const i
                                 cy[mt][nt][r] += drh * rr[r];
                             }
                             const uint2 p1 = make_uint2(Elem<H>::pack2(g1r[0], g1r[1]), Elem<H>::pack2(g1r[2], g1r[3]));
-                            *reinterpret_cast<EVE_LDS cg_u32x2_t*>((uintptr_t)lds_c4(2, mt, c)) = cg_u32x2_t{p1.x, p1.y};
+                            lds_write8(lds_c4(2, mt, c), p1.x, p1.y);
                             *reinterpret_cast<uint2*>(dg1_all + pt * 128 + c) = p1;
                         }
                     }

@@ -30,36 +30,11 @@ constexpr int S1_SUB = 128 * 64;                // one filter sub-tile: 128 rows
 constexpr int S1_SLOT = 2 * S1_SUB;             // a step's tile: two slices
 constexpr int S1_NT = 256;
 
-typedef uint32_t s1_u32x2_t __attribute__((ext_vector_type(2)));
-typedef uint32_t s1_u32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float s1_sigmoid(float z) { return __builtin_amdgcn_rcpf(1.f + __expf(-z)); }
-__device__ __forceinline__ float s1_tanh(float z) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * z)); }
-
 // byte offset inside a plane PAIR base of 4 channels c..c+3 (c % 4 == 0, c < 64) of pixel m: plane c >> 5, halo pixel, chunk
 __device__ __forceinline__ int s1_c4(int m, int c) {
     const int hr = (m >> 3) + 1, hc = (m & 7) + 1;
     return (c >> 5) * S1_PLANE + ((hr * 10 + hc) << 6) + (((((c & 31) >> 3)) ^ ((hr & 1) << 1)) << 4) + (c & 7) * 2;
 }
-// A fragment stays one 16-byte VECTOR value from the LDS load to the MFMA operand (round 6: as HIP's uint4 struct the load was
-// split in the middle end and part of the fragments came back as ds_read2_b64 -- twice the LDS cycles of ds_read_b128 and
-// banked differently from what the chunk swizzle is built for; see stem_fused.hip).
-typedef s1_u32x4_t s1_frag_t;
-__device__ __forceinline__ s1_frag_t s1_lds16(uint32_t a) { return *reinterpret_cast<const EVE_LDS s1_u32x4_t*>((uintptr_t)a); }
-template <typename H>
-__device__ __forceinline__ void s1_mfma(f32x4_t& acc, const s1_frag_t& a, const s1_frag_t& b) {
-    if constexpr (Elem<H>::IS_BF16)
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc, 0, 0, 0);
-    else
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), acc, 0, 0, 0);
-}
-__device__ __forceinline__ s1_u32x2_t s1_lds8(uint32_t a) { return *reinterpret_cast<const EVE_LDS s1_u32x2_t*>((uintptr_t)a); }
-__device__ __forceinline__ void s1_st8(uint32_t a, uint32_t x, uint32_t y) {
-    *reinterpret_cast<EVE_LDS s1_u32x2_t*>((uintptr_t)a) = s1_u32x2_t{x, y};
-}
-__device__ __forceinline__ float s1_ldsf(uint32_t a) { return *reinterpret_cast<const EVE_LDS float*>((uintptr_t)a); }
-__device__ __forceinline__ void s1_stf(uint32_t a, float v) { *reinterpret_cast<EVE_LDS float*>((uintptr_t)a) = v; }
-
 // Fragment addresses shared by both kernels.  Lane (li, lg): pixel tile mt -> pixel 16 mt + li (clamped to 39: the surplus
 // columns of the third tile are computed and dropped), K chunk lg.  Tap (dy, dx) adds (dy * 10 + dx) * 64; the chunk key is
 // the halo row's parity, so there is one base per parity of dy.
@@ -77,13 +52,13 @@ struct S1Lane {
 
 // One K = 64 step: acc[mt][nt] += W[rows of this wave][tap, 64 k] x X[pixels][tap, 64 k].  fx / fw: [slice][tile].
 template <typename H, int NTL>
-__device__ __forceinline__ void s1_mma(f32x4_t (&acc)[3][NTL], const s1_frag_t (&fx)[2][3], const s1_frag_t (&fw)[2][NTL]) {
+__device__ __forceinline__ void s1_mma(f32x4_t (&acc)[3][NTL], const frag_t (&fx)[2][3], const frag_t (&fw)[2][NTL]) {
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int nt = 0; nt < NTL; ++nt)
 #pragma unroll
-            for (int mt = 0; mt < 3; ++mt) s1_mfma<H>(acc[mt][nt], fw[j][nt], fx[j][mt]);
+            for (int mt = 0; mt < 3; ++mt) mfma16<H>(acc[mt][nt], fw[j][nt], fx[j][mt]);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -193,17 +168,17 @@ __global__ __launch_bounds__(S1_NT) void cgru_scan1_fwd_kernel(const int B, cons
             for (int a = 0; a < 3; ++a)
 #pragma unroll
                 for (int c = 0; c < 2; ++c) acc[a][c] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-            s1_frag_t fxA[2][3], fwA[2][2], fxB[2][3], fwB[2][2];
-            auto load = [&](int q, uint32_t gpos, s1_frag_t (&fx)[2][3], s1_frag_t (&fw)[2][2]) {
+            frag_t fxA[2][3], fwA[2][2], fxB[2][3], fwB[2][2];
+            auto load = [&](int q, uint32_t gpos, frag_t (&fx)[2][3], frag_t (&fw)[2][2]) {
                 const int pair = q / 9, tap = q - 9 * pair;       // (q is a compile-time constant after unrolling)
                 const int dy = tap / 3, dx = tap - 3 * dy;
                 const uint32_t la = lds0 + (2 * pair) * S1_PLANE + (dy * 10 + dx) * 64, lb = ldsB + (gpos & 3) * S1_SLOT;
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
 #pragma unroll
-                    for (int mt = 0; mt < 3; ++mt) fx[j][mt] = s1_lds16(la + j * S1_PLANE + L.abase[dy & 1][mt]);
+                    for (int mt = 0; mt < 3; ++mt) fx[j][mt] = lds_read16(la + j * S1_PLANE + L.abase[dy & 1][mt]);
 #pragma unroll
-                    for (int nt = 0; nt < 2; ++nt) fw[j][nt] = s1_lds16(lb + j * S1_SUB + brow1[nt]);
+                    for (int nt = 0; nt < 2; ++nt) fw[j][nt] = lds_read16(lb + j * S1_SUB + brow1[nt]);
                 }
             };
             load(0, gs, fxA, fwA);
@@ -233,19 +208,19 @@ __global__ __launch_bounds__(S1_NT) void cgru_scan1_fwd_kernel(const int B, cons
                 for (int mt = 0; mt < 3; ++mt) {
                     if (!pok[mt]) continue;
                     const int m = mt * 16 + li;
-                    float v[4] = {s1_sigmoid(acc[mt][nt][0] + bv.x), s1_sigmoid(acc[mt][nt][1] + bv.y),
-                                  s1_sigmoid(acc[mt][nt][2] + bv.z), s1_sigmoid(acc[mt][nt][3] + bv.w)};
+                    float v[4] = {sigmoid_rcp(acc[mt][nt][0] + bv.x), sigmoid_rcp(acc[mt][nt][1] + bv.y),
+                                  sigmoid_rcp(acc[mt][nt][2] + bv.z), sigmoid_rcp(acc[mt][nt][3] + bv.w)};
                     const uint32_t p0 = Elem<H>::pack2(v[0], v[1]), p1 = Elem<H>::pack2(v[2], v[3]);
                     *reinterpret_cast<uint2*>(ru + (ptm0 + m) * 128 + gch) = make_uint2(p0, p1);
                     if (wave < 2) {                               // the stored (16-bit) gate is the one every later stage sees
                         v[0] = Elem<H>::lo(p0); v[1] = Elem<H>::hi(p0); v[2] = Elem<H>::lo(p1); v[3] = Elem<H>::hi(p1);
-                        const s1_u32x2_t hq = s1_lds8(lds0 + 2 * S1_PLANE + s1_c4(m, gch));
+                        const u32x2_t hq = lds_read8(lds0 + 2 * S1_PLANE + s1_c4(m, gch));
                         const uint32_t q0 = Elem<H>::pack2(v[0] * Elem<H>::lo(hq.x), v[1] * Elem<H>::hi(hq.x));
                         const uint32_t q1 = Elem<H>::pack2(v[2] * Elem<H>::lo(hq.y), v[3] * Elem<H>::hi(hq.y));
-                        s1_st8(lds0 + 4 * S1_PLANE + s1_c4(m, gch), q0, q1);
+                        lds_write8(lds0 + 4 * S1_PLANE + s1_c4(m, gch), q0, q1);
                         *reinterpret_cast<uint2*>(rh + (ptm0 + m) * S1_C + gch) = make_uint2(q0, q1);
                     } else {
-                        s1_st8(lds0 + 6 * S1_PLANE + s1_c4(m, gch - 64), p0, p1);
+                        lds_write8(lds0 + 6 * S1_PLANE + s1_c4(m, gch - 64), p0, p1);
                     }
                 }
             }
@@ -256,8 +231,8 @@ __global__ __launch_bounds__(S1_NT) void cgru_scan1_fwd_kernel(const int B, cons
             f32x4_t acc[3][1];
 #pragma unroll
             for (int a = 0; a < 3; ++a) acc[a][0] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-            s1_frag_t fxA[2][3], fwA[2][1], fxB[2][3], fwB[2][1];
-            auto load = [&](int q, uint32_t gpos, s1_frag_t (&fx)[2][3], s1_frag_t (&fw)[2][1]) {
+            frag_t fxA[2][3], fwA[2][1], fxB[2][3], fwB[2][1];
+            auto load = [&](int q, uint32_t gpos, frag_t (&fx)[2][3], frag_t (&fw)[2][1]) {
                 const int pair = q / 9, tap = q - 9 * pair;
                 const int dy = tap / 3, dx = tap - 3 * dy;
                 const int plane = pair == 0 ? 4 : 0;              // r * h, then x
@@ -265,8 +240,8 @@ __global__ __launch_bounds__(S1_NT) void cgru_scan1_fwd_kernel(const int B, cons
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
 #pragma unroll
-                    for (int mt = 0; mt < 3; ++mt) fx[j][mt] = s1_lds16(la + j * S1_PLANE + L.abase[dy & 1][mt]);
-                    fw[j][0] = s1_lds16(lb + j * S1_SUB + brow2);
+                    for (int mt = 0; mt < 3; ++mt) fx[j][mt] = lds_read16(la + j * S1_PLANE + L.abase[dy & 1][mt]);
+                    fw[j][0] = lds_read16(lb + j * S1_SUB + brow2);
                 }
             };
             load(0, gs, fxA, fwA);
@@ -295,19 +270,19 @@ __global__ __launch_bounds__(S1_NT) void cgru_scan1_fwd_kernel(const int B, cons
             for (int mt = 0; mt < 3; ++mt) {
                 if (!pok[mt]) continue;
                 const int m = mt * 16 + li;
-                float o[4] = {s1_tanh(acc[mt][0][0] + bv.x), s1_tanh(acc[mt][0][1] + bv.y), s1_tanh(acc[mt][0][2] + bv.z),
-                              s1_tanh(acc[mt][0][3] + bv.w)};
+                float o[4] = {tanh_rcp(acc[mt][0][0] + bv.x), tanh_rcp(acc[mt][0][1] + bv.y), tanh_rcp(acc[mt][0][2] + bv.z),
+                              tanh_rcp(acc[mt][0][3] + bv.w)};
                 const uint32_t o0 = Elem<H>::pack2(o[0], o[1]), o1 = Elem<H>::pack2(o[2], o[3]);
                 o[0] = Elem<H>::lo(o0); o[1] = Elem<H>::hi(o0); o[2] = Elem<H>::lo(o1); o[3] = Elem<H>::hi(o1);
                 const int off = s1_c4(m, c);
-                const s1_u32x2_t hq = s1_lds8(lds0 + 2 * S1_PLANE + off), uq = s1_lds8(lds0 + 6 * S1_PLANE + off);
+                const u32x2_t hq = lds_read8(lds0 + 2 * S1_PLANE + off), uq = lds_read8(lds0 + 6 * S1_PLANE + off);
                 const float hv[4] = {Elem<H>::lo(hq.x), Elem<H>::hi(hq.x), Elem<H>::lo(hq.y), Elem<H>::hi(hq.y)};
                 const float uv[4] = {Elem<H>::lo(uq.x), Elem<H>::hi(uq.x), Elem<H>::lo(uq.y), Elem<H>::hi(uq.y)};
                 float hn[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) hn[r] = (1.f - uv[r]) * o[r] + uv[r] * hv[r];
                 const uint32_t n0 = Elem<H>::pack2(hn[0], hn[1]), n1 = Elem<H>::pack2(hn[2], hn[3]);
-                s1_st8(lds0 + 2 * S1_PLANE + off, n0, n1);
+                lds_write8(lds0 + 2 * S1_PLANE + off, n0, n1);
                 *reinterpret_cast<uint2*>(og + (ptm0 + m) * S1_C + c) = make_uint2(o0, o1);
                 *reinterpret_cast<uint2*>(hs_tm + (ptm0 + m) * S1_C + c) = make_uint2(n0, n1);
                 *reinterpret_cast<uint2*>(hs + (pg0 + m) * S1_C + c) = make_uint2(n0, n1);
@@ -408,15 +383,15 @@ __global__ __launch_bounds__(S1_NT) void cgru_scan1_bwd_kernel(const int B, cons
             float g2[4], g1u[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float dhn = d[r] + s1_ldsf(cf + 4 * r);
+                const float dhn = d[r] + lds_read_f32(cf + 4 * r);
                 g2[r] = dhn * (1.f - u[r]) * (1.f - o[r] * o[r]);
                 g1u[r] = dhn * (hp[r] - o[r]) * u[r] * (1.f - u[r]);
-                s1_stf(cf + 4 * r, dhn * u[r]);
+                lds_write_f32(cf + 4 * r, dhn * u[r]);
             }
             const uint2 p2 = make_uint2(Elem<H>::pack2(g2[0], g2[1]), Elem<H>::pack2(g2[2], g2[3]));
             const uint2 p1 = make_uint2(Elem<H>::pack2(g1u[0], g1u[1]), Elem<H>::pack2(g1u[2], g1u[3]));
-            s1_st8(lds0 + s1_c4(m, c), p2.x, p2.y);
-            s1_st8(lds0 + 4 * S1_PLANE + s1_c4(m, c), p1.x, p1.y);
+            lds_write8(lds0 + s1_c4(m, c), p2.x, p2.y);
+            lds_write8(lds0 + 4 * S1_PLANE + s1_c4(m, c), p1.x, p1.y);
             *reinterpret_cast<uint2*>(dg2_all + (ptm0 + m) * S1_C + c) = p2;
             *reinterpret_cast<uint2*>(dg1_all + (ptm0 + m) * 128 + 64 + c) = p1;
         }
@@ -424,16 +399,16 @@ __global__ __launch_bounds__(S1_NT) void cgru_scan1_bwd_kernel(const int B, cons
         asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
         __syncthreads();
         f32x4_t acc[3][2];
-        s1_frag_t fxA[2][3], fwA[2][2], fxB[2][3], fwB[2][2];
-        auto load = [&](int pl0, int tap, uint32_t gpos, s1_frag_t (&fx)[2][3], s1_frag_t (&fw)[2][2]) {
+        frag_t fxA[2][3], fwA[2][2], fxB[2][3], fwB[2][2];
+        auto load = [&](int pl0, int tap, uint32_t gpos, frag_t (&fx)[2][3], frag_t (&fw)[2][2]) {
             const int dy = tap / 3, dx = tap - 3 * dy;
             const uint32_t la = lds0 + pl0 * S1_PLANE + (dy * 10 + dx) * 64, lb = ldsB + (gpos & 3) * S1_SLOT;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
 #pragma unroll
-                for (int mt = 0; mt < 3; ++mt) fx[j][mt] = s1_lds16(la + j * S1_PLANE + L.abase[dy & 1][mt]);
+                for (int mt = 0; mt < 3; ++mt) fx[j][mt] = lds_read16(la + j * S1_PLANE + L.abase[dy & 1][mt]);
 #pragma unroll
-                for (int nt = 0; nt < 2; ++nt) fw[j][nt] = s1_lds16(lb + j * S1_SUB + brow[nt]);
+                for (int nt = 0; nt < 2; ++nt) fw[j][nt] = lds_read16(lb + j * S1_SUB + brow[nt]);
             }
         };
         // ================= conv A: d[r h | x] = conv(dg2, W2^T) =================
@@ -477,14 +452,14 @@ __global__ __launch_bounds__(S1_NT) void cgru_scan1_bwd_kernel(const int B, cons
                     for (int r = 0; r < 4; ++r) {
                         const float drh = acc[mt][nt][r];
                         g1r[r] = drh * hp[r] * rr[r] * (1.f - rr[r]);
-                        s1_stf(cf + 4 * r, s1_ldsf(cf + 4 * r) + drh * rr[r]);
+                        lds_write_f32(cf + 4 * r, lds_read_f32(cf + 4 * r) + drh * rr[r]);
                     }
                     const uint2 p1 = make_uint2(Elem<H>::pack2(g1r[0], g1r[1]), Elem<H>::pack2(g1r[2], g1r[3]));
-                    s1_st8(lds0 + 2 * S1_PLANE + s1_c4(m, c), p1.x, p1.y);
+                    lds_write8(lds0 + 2 * S1_PLANE + s1_c4(m, c), p1.x, p1.y);
                     *reinterpret_cast<uint2*>(dg1_all + (ptm0 + m) * 128 + c) = p1;
                 } else {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) s1_stf(cf + 4 * r, acc[mt][nt][r]);     // dx_2
+                    for (int r = 0; r < 4; ++r) lds_write_f32(cf + 4 * r, acc[mt][nt][r]);     // dx_2
                 }
             }
         }
@@ -526,13 +501,13 @@ __global__ __launch_bounds__(S1_NT) void cgru_scan1_bwd_kernel(const int B, cons
                     const uint32_t xf = ldsF + FPL + (m * S1_C + c) * 4;
                     float v[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = s1_ldsf(xf + 4 * r) + acc[mt][nt][r];
+                    for (int r = 0; r < 4; ++r) v[r] = lds_read_f32(xf + 4 * r) + acc[mt][nt][r];
                     *reinterpret_cast<uint2*>(dxs_tm + (ptm0 + m) * S1_C + c) =
                         make_uint2(Elem<H>::pack2(v[0], v[1]), Elem<H>::pack2(v[2], v[3]));
                 } else {
                     const uint32_t cf = ldsF + (m * S1_C + c) * 4;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) s1_stf(cf + 4 * r, s1_ldsf(cf + 4 * r) + acc[mt][nt][r]);
+                    for (int r = 0; r < 4; ++r) lds_write_f32(cf + 4 * r, lds_read_f32(cf + 4 * r) + acc[mt][nt][r]);
                 }
             }
         }
@@ -546,7 +521,7 @@ __global__ __launch_bounds__(S1_NT) void cgru_scan1_bwd_kernel(const int B, cons
             const int m = e >> 4, c = (e & 15) * 4;
             const uint32_t cf = ldsF + (m * S1_C + c) * 4;
             *reinterpret_cast<uint2*>(dh0 + ((size_t)b * S1_PIX + m) * S1_C + c) =
-                make_uint2(Elem<H>::pack2(s1_ldsf(cf), s1_ldsf(cf + 4)), Elem<H>::pack2(s1_ldsf(cf + 8), s1_ldsf(cf + 12)));
+                make_uint2(Elem<H>::pack2(lds_read_f32(cf), lds_read_f32(cf + 4)), Elem<H>::pack2(lds_read_f32(cf + 8), lds_read_f32(cf + 12)));
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

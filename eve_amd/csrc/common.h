@@ -20,8 +20,12 @@ __device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make
 template <int I> using ic = std::integral_constant<int, I>;
 
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
+// the vector types of the kernels, one name each.  (MFMA accumulators: f32x4_t for 16x16, f32x16_t for 32x32 tiles.)
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
+typedef __attribute__((ext_vector_type(16))) float f32x16_t;
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 
 // ---------------------------------------------------------------------------------------------
 // element types: `float` and the two 16-bit formats `bf16_t` / `f16_t` (raw 16-bit storage, round-to-nearest-even
@@ -138,13 +142,24 @@ template <> struct Elem<f16_t> {
 #define EVE_SELU_ALPHA 1.6732632423543772f
 #define EVE_SELU_SCALE 1.0507009873554805f
 
+// Gate non-linearities, two forms that stay distinct.
+// exact: a true division, with tanhf as its partner -- the float32 scans and activations, which are tested against float64.
+__device__ __forceinline__ float sigmoid_exact(float z) { return 1.f / (1.f + __expf(-z)); }
+// rcp: the 16-bit scans.  The results are rounded to 16 bits on the spot, so one-ulp float building blocks (v_exp_f32, v_rcp_f32)
+// are exact enough -- and the epilogues are where the conv-GRU scan's time is: per frame a wave runs 72 MFMA steps of ~60
+// instructions and two epilogues that were ~1 750 + ~3 800 instructions with tanhf and IEEE divisions expanded 64 times each
+// (round 5; the float32 scan of cell_scan_f32.hip keeps tanhf / the division).
+__device__ __forceinline__ float sigmoid_rcp(float z) { return __builtin_amdgcn_rcpf(1.f + __expf(-z)); }
+// tanh(z) = 1 - 2 / (1 + e^(2z)): saturates correctly (e^(2z) = inf -> 1, 0 -> -1); absolute error ~1e-7
+__device__ __forceinline__ float tanh_rcp(float z) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * z)); }
+
 __device__ __forceinline__ float act_fwd(float z, int act) {
     switch (act) {
         case EVE_ACT_RELU:    return z > 0.f ? z : 0.f;
         case EVE_ACT_LEAKY:   return z > 0.f ? z : 0.01f * z;
         case EVE_ACT_SELU:    return EVE_SELU_SCALE * (z > 0.f ? z : EVE_SELU_ALPHA * (__expf(z) - 1.f));
         case EVE_ACT_TANH:    return tanhf(z);
-        case EVE_ACT_SIGMOID: return 1.f / (1.f + __expf(-z));
+        case EVE_ACT_SIGMOID: return sigmoid_exact(z);
         default:              return z;
     }
 }
@@ -230,7 +245,12 @@ __device__ __forceinline__ uint32_t xcd_remap(uint32_t bid, uint32_t nblk) {
 namespace eve {
 int set_error(hipError_t e, const char* where);
 int set_error_msg(const char* msg);
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
+// one DPP move: lane i gets `src` of the lane CTRL selects inside its row of 16 (0xb1 / 0x4e: quad_perm [1,0,3,2] / [2,3,0,1];
+// 0x141 / 0x140: row_half_mirror / row_mirror), `old` where that lane is disabled
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_mov(uint32_t old, uint32_t src) {
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)src, CTRL, 0xf, 0xf, false);
+}
 // 4 x 4 transpose of 16-byte elements across a lane quad (two DPP butterfly stages, per dword: select, quad_perm move, two
 // selects): in: r[k] of lane q = element (k, q); out: r[m] of lane q = element (q, m).  Epilogues whose lanes hold four
 // 16-byte chunks of ONE pixel use it so that a store instruction writes 64 contiguous bytes per quad (chunk q of the quad's
@@ -242,7 +262,7 @@ __device__ __forceinline__ void quad_transpose4x4(u32x4_t (&r)[4], const int lan
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
             const uint32_t a = r[k][d], b = r[k + 2][d];
-            const uint32_t got = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(q_hi ? a : b), 0x4e, 0xf, 0xf, false);   // quad_perm [2,3,0,1]
+            const uint32_t got = dpp_mov<0x4e>(0u, q_hi ? a : b);   // quad_perm [2,3,0,1]
             r[k][d] = q_hi ? got : a;
             r[k + 2][d] = q_hi ? b : got;
         }
@@ -251,7 +271,7 @@ __device__ __forceinline__ void quad_transpose4x4(u32x4_t (&r)[4], const int lan
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
             const uint32_t a = r[k][d], b = r[k + 1][d];
-            const uint32_t got = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(q_lo ? a : b), 0xb1, 0xf, 0xf, false);   // quad_perm [1,0,3,2]
+            const uint32_t got = dpp_mov<0xb1>(0u, q_lo ? a : b);   // quad_perm [1,0,3,2]
             r[k][d] = q_lo ? got : a;
             r[k + 1][d] = q_lo ? b : got;
         }

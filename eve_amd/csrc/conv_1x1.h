@@ -19,8 +19,6 @@
 
 namespace eve {
 
-typedef unsigned int c1_v4u32 __attribute__((ext_vector_type(4)));
-typedef unsigned int c1_v2u32 __attribute__((ext_vector_type(2)));
 
 template <int CIN, int COUT>
 struct C1Geom {
@@ -89,7 +87,7 @@ __global__ __launch_bounds__(256) void conv1x1_stream_kernel(const H* __restrict
                     if constexpr (NT >= 2) {
                         prev[i][a] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(ro, (int)(p * (uint32_t)(COUT * 2) + 64u * a + 16u * g), 0, 0));
                     } else {
-                        const c1_v2u32 v = __builtin_amdgcn_raw_buffer_load_b64(ro, (int)(p * 32u + 8u * g), 0, 0);
+                        const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(ro, (int)(p * 32u + 8u * g), 0, 0);
                         prev[i][a] = make_uint4(v.x, v.y, 0u, 0u);
                     }
                 }
@@ -135,9 +133,9 @@ __global__ __launch_bounds__(256) void conv1x1_stream_kernel(const H* __restrict
                 const uint4 q = Elem<H>::pack(o);
                 // (the whole offset in the vector operand, immediate 0 as the scalar one: see norm_fused.hip `stv`)
                 if constexpr (NT >= 2) {
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(c1_v4u32, q), ro, (int)(p * (uint32_t)(COUT * 2) + 64u * a + 16u * g), 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, q), ro, (int)(p * (uint32_t)(COUT * 2) + 64u * a + 16u * g), 0, 0);
                 } else {
-                    c1_v2u32 v;
+                    u32x2_t v;
                     v.x = q.x; v.y = q.y;
                     __builtin_amdgcn_raw_buffer_store_b64(v, ro, (int)(p * 32u + 8u * g), 0, 0);
                 }
@@ -278,7 +276,7 @@ __global__ __launch_bounds__((64 * C1S2Geom<CIN, COUT>::WAVES)) void conv1x1_s2_
 #pragma unroll
                     for (int e = 0; e < 8; ++e) o[e] += pv[e];
                 }
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(c1_v4u32, Elem<H>::pack(o)), ro, (int)(oo[i] + 64u * a), 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, Elem<H>::pack(o)), ro, (int)(oo[i] + 64u * a), 0, 0);
             }
     }
 }

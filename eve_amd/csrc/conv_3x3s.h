@@ -167,7 +167,7 @@ __global__ __launch_bounds__(256) void conv3x3_stream_kernel(const C3Params p, c
                         for (int e = 0; e < 8; ++e) o[e] += pv[e];
                     }
                     const uint4 qo = Elem<H_>::pack(o);
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(c1_v4u32, qo), ro, off, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, qo), ro, off, 0, 0);
                     if (p.stats) {
                         float ro8[8];
                         Elem<H_>::unpack(qo, ro8);
@@ -181,14 +181,14 @@ __global__ __launch_bounds__(256) void conv3x3_stream_kernel(const C3Params p, c
                 } else {
                     const int off = (int)(pix * 32u + 8u * g);
                     if constexpr (ACC) {
-                        const c1_v2u32 v = __builtin_amdgcn_raw_buffer_load_b64(ro, off, 0, 0);
+                        const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(ro, off, 0, 0);
                         float pv[8];
                         Elem<H_>::unpack(make_uint4(v.x, v.y, 0u, 0u), pv);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) o[e] += pv[e];
                     }
                     const uint4 q = Elem<H_>::pack(o);
-                    c1_v2u32 v;
+                    u32x2_t v;
                     v.x = q.x; v.y = q.y;
                     __builtin_amdgcn_raw_buffer_store_b64(v, ro, off, 0, 0);
                     if (p.stats) {

@@ -240,148 +240,6 @@ __global__ __launch_bounds__(64 * WM * WN) void igemm_dma_kernel(const GatherPar
     else epilogue(std::false_type{});
 }
 
-// 16 MFMAs (4 x 4 accumulator tiles, one K=32 chunk) as ONE asm statement with every accumulator tied in place
-// ("+a": AGPR, D == C).  Left to itself hipcc ping-pongs loop-carried accumulators between two register sets
-// when each gets a single MFMA per trip, and copies them back with v_accvgpr_mov/read/write at the loop edge
-// (10 VALU per MFMA measured in the weight-gradient loop).  The leading s_nop covers a VALU-assembled operand
-// tuple; consecutive MFMAs here never share an accumulator.
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-__device__ __forceinline__ void mma16_bf16_inplace(f32x4_t (&acc)[4][4], const uint4 (&a4)[4], const uint4 (&b4)[4]) {
-    u32x4_t a[4], b[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { a[i] = __builtin_bit_cast(u32x4_t, a4[i]); b[i] = __builtin_bit_cast(u32x4_t, b4[i]); }
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_mfma_f32_16x16x32_bf16 %0, %16, %20, %0\n\t"
-        "v_mfma_f32_16x16x32_bf16 %1, %16, %21, %1\n\t"
-        "v_mfma_f32_16x16x32_bf16 %2, %16, %22, %2\n\t"
-        "v_mfma_f32_16x16x32_bf16 %3, %16, %23, %3\n\t"
-        "v_mfma_f32_16x16x32_bf16 %4, %17, %20, %4\n\t"
-        "v_mfma_f32_16x16x32_bf16 %5, %17, %21, %5\n\t"
-        "v_mfma_f32_16x16x32_bf16 %6, %17, %22, %6\n\t"
-        "v_mfma_f32_16x16x32_bf16 %7, %17, %23, %7\n\t"
-        "v_mfma_f32_16x16x32_bf16 %8, %18, %20, %8\n\t"
-        "v_mfma_f32_16x16x32_bf16 %9, %18, %21, %9\n\t"
-        "v_mfma_f32_16x16x32_bf16 %10, %18, %22, %10\n\t"
-        "v_mfma_f32_16x16x32_bf16 %11, %18, %23, %11\n\t"
-        "v_mfma_f32_16x16x32_bf16 %12, %19, %20, %12\n\t"
-        "v_mfma_f32_16x16x32_bf16 %13, %19, %21, %13\n\t"
-        "v_mfma_f32_16x16x32_bf16 %14, %19, %22, %14\n\t"
-        "v_mfma_f32_16x16x32_bf16 %15, %19, %23, %15"
-        : "+a"(acc[0][0]), "+a"(acc[0][1]), "+a"(acc[0][2]), "+a"(acc[0][3]), "+a"(acc[1][0]), "+a"(acc[1][1]),
-          "+a"(acc[1][2]), "+a"(acc[1][3]), "+a"(acc[2][0]), "+a"(acc[2][1]), "+a"(acc[2][2]), "+a"(acc[2][3]),
-          "+a"(acc[3][0]), "+a"(acc[3][1]), "+a"(acc[3][2]), "+a"(acc[3][3])
-        : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]));
-}
-__device__ __forceinline__ void mma16_f16_inplace(f32x4_t (&acc)[4][4], const uint4 (&a4)[4], const uint4 (&b4)[4]) {
-    u32x4_t a[4], b[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { a[i] = __builtin_bit_cast(u32x4_t, a4[i]); b[i] = __builtin_bit_cast(u32x4_t, b4[i]); }
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_mfma_f32_16x16x32_f16 %0, %16, %20, %0\n\t"
-        "v_mfma_f32_16x16x32_f16 %1, %16, %21, %1\n\t"
-        "v_mfma_f32_16x16x32_f16 %2, %16, %22, %2\n\t"
-        "v_mfma_f32_16x16x32_f16 %3, %16, %23, %3\n\t"
-        "v_mfma_f32_16x16x32_f16 %4, %17, %20, %4\n\t"
-        "v_mfma_f32_16x16x32_f16 %5, %17, %21, %5\n\t"
-        "v_mfma_f32_16x16x32_f16 %6, %17, %22, %6\n\t"
-        "v_mfma_f32_16x16x32_f16 %7, %17, %23, %7\n\t"
-        "v_mfma_f32_16x16x32_f16 %8, %18, %20, %8\n\t"
-        "v_mfma_f32_16x16x32_f16 %9, %18, %21, %9\n\t"
-        "v_mfma_f32_16x16x32_f16 %10, %18, %22, %10\n\t"
-        "v_mfma_f32_16x16x32_f16 %11, %18, %23, %11\n\t"
-        "v_mfma_f32_16x16x32_f16 %12, %19, %20, %12\n\t"
-        "v_mfma_f32_16x16x32_f16 %13, %19, %21, %13\n\t"
-        "v_mfma_f32_16x16x32_f16 %14, %19, %22, %14\n\t"
-        "v_mfma_f32_16x16x32_f16 %15, %19, %23, %15"
-        : "+a"(acc[0][0]), "+a"(acc[0][1]), "+a"(acc[0][2]), "+a"(acc[0][3]), "+a"(acc[1][0]), "+a"(acc[1][1]),
-          "+a"(acc[1][2]), "+a"(acc[1][3]), "+a"(acc[2][0]), "+a"(acc[2][1]), "+a"(acc[2][2]), "+a"(acc[2][3]),
-          "+a"(acc[3][0]), "+a"(acc[3][1]), "+a"(acc[3][2]), "+a"(acc[3][3])
-        : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]));
-}
-// wait states between the last asm MFMA and compiler-generated reads of the accumulators
-__device__ __forceinline__ void mma_drain() { asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); }
-// four in-place MFMAs sharing the A operand: c[i] += a x b[i]
-__device__ __forceinline__ void mma4_bf16_inplace(f32x4_t& c0, f32x4_t& c1, f32x4_t& c2, f32x4_t& c3, const uint4& a4,
-                                                  const uint4 (&b4)[4]) {
-    u32x4_t b[4];
-    const u32x4_t a = __builtin_bit_cast(u32x4_t, a4);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) b[i] = __builtin_bit_cast(u32x4_t, b4[i]);
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_mfma_f32_16x16x32_bf16 %0, %4, %5, %0\n\t"
-        "v_mfma_f32_16x16x32_bf16 %1, %4, %6, %1\n\t"
-        "v_mfma_f32_16x16x32_bf16 %2, %4, %7, %2\n\t"
-        "v_mfma_f32_16x16x32_bf16 %3, %4, %8, %3"
-        : "+a"(c0), "+a"(c1), "+a"(c2), "+a"(c3)
-        : "v"(a), "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]));
-}
-
-// four in-place MFMAs sharing the B operand: c[i] += a[i] x b
-__device__ __forceinline__ void mma4_bf16_inplace_b(f32x4_t (&c)[4], const uint4 (&a4)[4], const uint4& b4) {
-    u32x4_t a[4];
-    const u32x4_t b = __builtin_bit_cast(u32x4_t, b4);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) a[i] = __builtin_bit_cast(u32x4_t, a4[i]);
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_mfma_f32_16x16x32_bf16 %0, %4, %8, %0\n\t"
-        "v_mfma_f32_16x16x32_bf16 %1, %5, %8, %1\n\t"
-        "v_mfma_f32_16x16x32_bf16 %2, %6, %8, %2\n\t"
-        "v_mfma_f32_16x16x32_bf16 %3, %7, %8, %3"
-        : "+a"(c[0]), "+a"(c[1]), "+a"(c[2]), "+a"(c[3])
-        : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(b));
-}
-
-// four in-place MFMAs sharing the A operand: c[i] += a x b[i]
-__device__ __forceinline__ void mma4_f16_inplace(f32x4_t& c0, f32x4_t& c1, f32x4_t& c2, f32x4_t& c3, const uint4& a4,
-                                                  const uint4 (&b4)[4]) {
-    u32x4_t b[4];
-    const u32x4_t a = __builtin_bit_cast(u32x4_t, a4);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) b[i] = __builtin_bit_cast(u32x4_t, b4[i]);
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_mfma_f32_16x16x32_f16 %0, %4, %5, %0\n\t"
-        "v_mfma_f32_16x16x32_f16 %1, %4, %6, %1\n\t"
-        "v_mfma_f32_16x16x32_f16 %2, %4, %7, %2\n\t"
-        "v_mfma_f32_16x16x32_f16 %3, %4, %8, %3"
-        : "+a"(c0), "+a"(c1), "+a"(c2), "+a"(c3)
-        : "v"(a), "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]));
-}
-
-// four in-place MFMAs sharing the B operand: c[i] += a[i] x b
-__device__ __forceinline__ void mma4_f16_inplace_b(f32x4_t (&c)[4], const uint4 (&a4)[4], const uint4& b4) {
-    u32x4_t a[4];
-    const u32x4_t b = __builtin_bit_cast(u32x4_t, b4);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) a[i] = __builtin_bit_cast(u32x4_t, a4[i]);
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_mfma_f32_16x16x32_f16 %0, %4, %8, %0\n\t"
-        "v_mfma_f32_16x16x32_f16 %1, %5, %8, %1\n\t"
-        "v_mfma_f32_16x16x32_f16 %2, %6, %8, %2\n\t"
-        "v_mfma_f32_16x16x32_f16 %3, %7, %8, %3"
-        : "+a"(c[0]), "+a"(c[1]), "+a"(c[2]), "+a"(c[3])
-        : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(b));
-}
-
-// format-generic entry points of the in-place groups
-template <typename H>
-__device__ __forceinline__ void mma16_inplace(f32x4_t (&acc)[4][4], const uint4 (&a4)[4], const uint4 (&b4)[4]) {
-    if constexpr (Elem<H>::IS_BF16) mma16_bf16_inplace(acc, a4, b4); else mma16_f16_inplace(acc, a4, b4);
-}
-template <typename H>
-__device__ __forceinline__ void mma4_inplace(f32x4_t& c0, f32x4_t& c1, f32x4_t& c2, f32x4_t& c3, const uint4& a4, const uint4 (&b4)[4]) {
-    if constexpr (Elem<H>::IS_BF16) mma4_bf16_inplace(c0, c1, c2, c3, a4, b4); else mma4_f16_inplace(c0, c1, c2, c3, a4, b4);
-}
-template <typename H>
-__device__ __forceinline__ void mma4_inplace_b(f32x4_t (&c)[4], const uint4 (&a4)[4], const uint4& b4) {
-    if constexpr (Elem<H>::IS_BF16) mma4_bf16_inplace_b(c, a4, b4); else mma4_f16_inplace_b(c, a4, b4);
-}
-
 // =================================================================================================
 // bf16 weight gradient.  Block tile = (64*WCO output channels) x (64*WK filter-K values); every wave owns
 // a 64 x 64 piece; each step consumes 64 pixels (two MFMA K=32 chunks).

@@ -48,8 +48,6 @@
 
 namespace eve {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-
 struct Wg8Params {
     int N, Cin, Cout;             // x: [N][W][W][Cin]  out: [N][W][W][Cout]  (W is a template parameter)
     int flip;                     // 0: forward taps (kh-1, kw-1);  1: data-gradient taps (1-kh, 1-kw)
@@ -67,12 +65,6 @@ __device__ __forceinline__ int wg8_key(int hy, int hx) {
 __device__ __forceinline__ int wg8_row_channel(int r64) {
     const int ct = r64 >> 5, i = r64 & 31;
     return 32 * ((i >> 2) & 1) + 16 * ct + 4 * (i >> 3) + (i & 3);
-}
-
-// LDS-DMA with the uniform part of the source address in the scalar offset (no VALU work per piece)
-__device__ __forceinline__ void wg8_dma(const eve_int4& rsrc, uint32_t lds, int voff, int soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                 :: "s"(lds), "v"(voff), "s"(rsrc), "s"(soff) : "memory", "m0");
 }
 
 // 16 MFMAs of one step: acc[ct][pt] += Wf[ct][kh] x Xf[pt][kh], K half outermost (8 MFMAs between two uses of an accumulator)
@@ -93,20 +85,6 @@ __device__ __forceinline__ void wg8_mma16(f32x16_t (&acc)[2][4], const u32x4_t (
     else { EVE_WG8_MMA_BODY("v_mfma_f32_32x32x16_f16"); }
 }
 #undef EVE_WG8_MMA_BODY
-
-template <int N> __device__ __forceinline__ void wg8_wait_vm() {
-    static_assert(N >= 0 && N <= 9, "pieces per phase");
-    if (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else if (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else if (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    else if (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else if (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if (N == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-    else if (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-}
 
 // BANDS > 1 (round 5: 32 x 32 x 128, layer 2 on 256 x 256 patches): the tile's unit is a band of W / BANDS rows of one image instead
 // of a whole image (its halo rows above / below come from the neighbouring bands or are the image border).
@@ -217,15 +195,15 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wg8_kernel(const Wg8Params p, 
     auto issue_b = [&](int s, int t, int slot) {                // this wave's BP pieces of the tile of (slice s, position t)
         const int soff = tap_base + t * tap_step + s * 64;
 #pragma unroll
-        for (int j = 0; j < BP; ++j) wg8_dma(rs_w, ldsB + slot * BSLOT + (j * 8 + wave) * 1024, b_goff[j], soff);
+        for (int j = 0; j < BP; ++j) lds_dma16_asm(rs_w, ldsB + slot * BSLOT + (j * 8 + wave) * 1024, b_goff[j], soff);
     };
 
     // ---- prologue: halo of slice 0, weight tiles of steps 0 and 1 ----
 #pragma unroll
-    for (int j = 0; j < AP; ++j) wg8_dma(rs_x, ldsA + (j * 8 + wave) * 1024, a_goff[j], 0);
+    for (int j = 0; j < AP; ++j) lds_dma16_asm(rs_x, ldsA + (j * 8 + wave) * 1024, a_goff[j], 0);
     issue_b(0, 0, 0);
     issue_b(0, 1, 1);
-    wg8_wait_vm<0>();
+    wait_vm<0>();
     __builtin_amdgcn_s_barrier();
 
     // One barrier per step.  Between two barriers group 0 runs [read step g, multiply step g] and group 1 runs
@@ -266,36 +244,36 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wg8_kernel(const Wg8Params p, 
                 for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
                     for (int kh = 0; kh < 2; ++kh)
-                        wf[ct][kh] = *reinterpret_cast<const EVE_LDS u32x4_t*>((uintptr_t)(wrd[ct][kh] + slot_off));
+                        wf[ct][kh] = lds_read16(wrd[ct][kh] + slot_off);
                 const int imm = ss * ASTAGE + (W >= 8 ? dy * W2 * 64 : dx * 64);
                 const int q = W >= 8 ? dx : dy;
 #pragma unroll
                 for (int pt = 0; pt < 4; ++pt)
 #pragma unroll
                     for (int kh = 0; kh < 2; ++kh)
-                        xf[pt][kh] = *reinterpret_cast<const EVE_LDS u32x4_t*>((uintptr_t)(xrd[pt][q][kh] + imm));
+                        xf[pt][kh] = lds_read16(xrd[pt][q][kh] + imm);
                 // ---- DMAs of this step (issued while the fragment reads are in flight): weight tile of step g + 2, halo
                 //      pieces of the next slice ----
                 if (more_b) issue_b(s + sd, t2, (NT * s + t + 2) & 3);
                 if (!last) {
 #pragma unroll
                     for (int jj = 0; jj < PPS; ++jj)
-                        if (jj < np) wg8_dma(rs_x, ldsA + (ss ^ 1) * ASTAGE + ((j0 + jj) * 8 + wave) * 1024, a_goff[jj < np ? j0 + jj : 0], (s + 1) * 64);
+                        if (jj < np) lds_dma16_asm(rs_x, ldsA + (ss ^ 1) * ASTAGE + ((j0 + jj) * 8 + wave) * 1024, a_goff[jj < np ? j0 + jj : 0], (s + 1) * 64);
                 }
                 if (lead) wg8_mma16<H>(acc, wf, xf);
                 // everything this wave issued BEFORE this step has landed once only this step's pieces are outstanding
                 if (more_b) {
                     if (!last) {
-                        if (np == 0) wg8_wait_vm<BP>();
-                        else if (np == 1) wg8_wait_vm<BP + 1>();
-                        else if (np == 2) wg8_wait_vm<BP + 2>();
-                        else if (np == 3) wg8_wait_vm<BP + 3>();
-                        else if (np == 4) wg8_wait_vm<BP + 4>();
-                        else if (np == 5) wg8_wait_vm<BP + 5>();
-                        else wg8_wait_vm<BP + 6>();
-                    } else wg8_wait_vm<BP>();
+                        if (np == 0) wait_vm<BP>();
+                        else if (np == 1) wait_vm<BP + 1>();
+                        else if (np == 2) wait_vm<BP + 2>();
+                        else if (np == 3) wait_vm<BP + 3>();
+                        else if (np == 4) wait_vm<BP + 4>();
+                        else if (np == 5) wait_vm<BP + 5>();
+                        else wait_vm<BP + 6>();
+                    } else wait_vm<BP>();
                 } else {
-                    wg8_wait_vm<0>();
+                    wait_vm<0>();
                 }
                 __builtin_amdgcn_s_barrier();
             }

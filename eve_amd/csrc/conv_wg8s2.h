@@ -123,14 +123,14 @@ __global__ __launch_bounds__(512, 2) void conv3x3s2_wg8_kernel(const Wg8Params p
         const int tap = t == 0 ? 0 : t == 1 ? 2 : t == 2 ? 6 : t == 3 ? 8 : t == 4 ? 1 : t == 5 ? 7 : t == 6 ? 3 : t == 7 ? 5 : 4;
         const int soff = tap * cin2 + s * 64;
 #pragma unroll
-        for (int j = 0; j < BP; ++j) wg8_dma(rs_w, ldsB + slot * BSLOT + (j * 8 + wave) * 1024, b_goff[j], soff);
+        for (int j = 0; j < BP; ++j) lds_dma16_asm(rs_w, ldsB + slot * BSLOT + (j * 8 + wave) * 1024, b_goff[j], soff);
     };
     // pieces [j0, j0 + cnt) of plane (pp, pq) of slice s into stage `st`
     auto issue_a = [&](int s, int pp, int pq, uint32_t st_bytes, int j0, int cnt) {
         const int soff = s * 64 + (pp * WIN + pq) * cin2;
 #pragma unroll
         for (int j = 0; j < AP; ++j)
-            if (j >= j0 && j < j0 + cnt) wg8_dma(rs_x, ldsA + st_bytes + (j * 8 + wave) * 1024, a_goff[j], soff);
+            if (j >= j0 && j < j0 + cnt) lds_dma16_asm(rs_x, ldsA + st_bytes + (j * 8 + wave) * 1024, a_goff[j], soff);
     };
     constexpr int PA = (AP + 1) / 2, PB = AP - PA;               // pieces in the first / second step of a plane's fetch window
 
@@ -138,7 +138,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3s2_wg8_kernel(const Wg8Params p
     issue_a(0, 1, 1, 0, 0, AP);
     issue_b(0, 0, 0);
     issue_b(0, 1, 1);
-    wg8_wait_vm<0>();
+    wait_vm<0>();
     __builtin_amdgcn_s_barrier();
 
     const bool lead = wave < 4;
@@ -177,14 +177,14 @@ __global__ __launch_bounds__(512, 2) void conv3x3s2_wg8_kernel(const Wg8Params p
             for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
                 for (int kh = 0; kh < 2; ++kh)
-                    wf[ct][kh] = *reinterpret_cast<const EVE_LDS u32x4_t*>((uintptr_t)(wrd[ct][kh] + slot_off));
+                    wf[ct][kh] = lds_read16(wrd[ct][kh] + slot_off);
             const int imm = W >= 8 ? a * W2 * 64 : b * 64;
             const int q = W >= 8 ? b : a;
 #pragma unroll
             for (int pt = 0; pt < 4; ++pt)
 #pragma unroll
                 for (int kh = 0; kh < 2; ++kh)
-                    xf[pt][kh] = *reinterpret_cast<const EVE_LDS u32x4_t*>((uintptr_t)(xrd[pt][q][kh] + stg + imm));
+                    xf[pt][kh] = lds_read16(xrd[pt][q][kh] + stg + imm);
             if (more_b) issue_b(s + sd, t2, (s + t + 2) & 3);
             if (fetch) {
                 // (1,0) -> st1, (0,1) -> st2, (0,0) -> st0 (plane 3 = 0 mod 3: the stage (1,1) left after step 3);
@@ -195,12 +195,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3s2_wg8_kernel(const Wg8Params p
             }
             if (lead) wg8_mma16<H>(acc, wf, xf);
             if (more_b) {
-                if (np == 0) wg8_wait_vm<BP>();
-                else if (np == 1) wg8_wait_vm<BP + 1>();
-                else if (np == 2) wg8_wait_vm<BP + 2>();
-                else wg8_wait_vm<BP + 3>();
+                if (np == 0) wait_vm<BP>();
+                else if (np == 1) wait_vm<BP + 1>();
+                else if (np == 2) wait_vm<BP + 2>();
+                else wait_vm<BP + 3>();
             } else {
-                wg8_wait_vm<0>();
+                wait_vm<0>();
             }
             __builtin_amdgcn_s_barrier();
         }

@@ -223,11 +223,10 @@ __global__ __launch_bounds__(512, 2) void conv3x3_ws64_kernel(const Ws64Params p
                 const int t = h >> 1, kh = h & 1, dy = t / 3, dx = t % 3;
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct)
-                    wf[buf][ct] = *reinterpret_cast<const EVE_LDS u32x4_t*>((uintptr_t)(wrd[s][kh] + t * 4096 + ct * 2048));
+                    wf[buf][ct] = lds_read16(wrd[s][kh] + t * 4096 + ct * 2048);
 #pragma unroll
                 for (int pt = 0; pt < 2; ++pt)
-                    xf[buf][pt] = *reinterpret_cast<const EVE_LDS u32x4_t*>((uintptr_t)(xrd[dx][kh] + s * ASTAGE +
-                                                                                         (W == 32 ? (dy + pt) * W2 * 64 : dy * W2 * 64 + pt * 2048)));
+                    xf[buf][pt] = lds_read16(xrd[dx][kh] + s * ASTAGE + (W == 32 ? (dy + pt) * W2 * 64 : dy * W2 * 64 + pt * 2048));
             };
 #pragma unroll
             for (int h = 0; h < NB - 1; ++h) read_step(h, h);

@@ -280,7 +280,6 @@ __device__ __forceinline__ void fence_sums(float* s) {
 // Addresses: one buffer resource per tensor and plane part (wave-uniform: four SGPRs), ONE 32-bit lane offset, and the
 // vector index j as the instruction's scalar offset j * step -- no address arithmetic per load or store at all.  (nthreads is
 // a multiple of cvecs, so vector i = tid + j * nthreads sits nthreads / cvecs pixels below vector tid.)
-typedef unsigned int v4u32_t __attribute__((ext_vector_type(4)));
 struct TrunkAddr {
     size_t base;            // byte offset of this plane part inside the tensor (uniform)
     uint32_t bytes;         // bytes from there to the end of the plane (buffer bound)
@@ -308,7 +307,7 @@ __device__ __forceinline__ uint4 ldv(__amdgpu_buffer_rsrc_t r, uint32_t voff, ui
 // gfx950 it has one: dword 1 of ~12 lanes of dres went out with the new value, a few times per launch, run-to-run different
 // (tools/dbg_in.py; found by test_instnorm_fwd_bwd's bit-equality of the mask and y paths).  The immediate form is protected.
 __device__ __forceinline__ void stv(const uint4& q, __amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t uniform_off) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u32_t, q), r, (int)(voff + uniform_off), 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, q), r, (int)(voff + uniform_off), 0, 0);
 }
 
 template <typename T, int VPT, int ACT, bool RES, bool MASK>

@@ -9,8 +9,6 @@
 
 namespace eve {
 
-__device__ __forceinline__ float sigmoidf_(float z) { return 1.f / (1.f + __expf(-z)); }
-
 // grid = S sequences, block = 3H threads (H <= 256).  whh_t is [H][3H] (transposed for coalescing).
 __global__ void gru_scan_fwd_kernel(int T, int H, const float* __restrict__ gi, const float* __restrict__ whh_t,
                                     const float* __restrict__ bhh, const float* __restrict__ h0,
@@ -31,8 +29,8 @@ __global__ void gru_scan_fwd_kernel(int T, int H, const float* __restrict__ gi, 
         float hnew = 0.f;
         if (j < H) {
             const float* g = gi + ((size_t)s * T + t) * H3;
-            const float r = sigmoidf_(g[j] + gh[j]);
-            const float z = sigmoidf_(g[H + j] + gh[H + j]);
+            const float r = sigmoid_exact(g[j] + gh[j]);
+            const float z = sigmoid_exact(g[H + j] + gh[H + j]);
             const float n = tanhf(g[2 * H + j] + r * gh[2 * H + j]);
             hnew = (1.f - z) * n + z * h[j];
             float* go = gates + ((size_t)s * T + t) * H3;
@@ -119,8 +117,8 @@ __global__ void cell_scan_fwd_kernel(int T, int H, const float* __restrict__ gi,
             if (G == 1) {
                 hnew = tanhf(pre[j]);
             } else {
-                const float ig = sigmoidf_(pre[j]), fg = sigmoidf_(pre[H + j]), gg = tanhf(pre[2 * H + j]);
-                const float og = sigmoidf_(pre[3 * H + j]);
+                const float ig = sigmoid_exact(pre[j]), fg = sigmoid_exact(pre[H + j]), gg = tanhf(pre[2 * H + j]);
+                const float og = sigmoid_exact(pre[3 * H + j]);
                 c = fg * c + ig * gg;
                 hnew = og * tanhf(c);
                 float* go = gates + o * HG;
@@ -221,8 +219,8 @@ __global__ __launch_bounds__(384) void gru_scan_fwd128_kernel(int T, const float
         __syncthreads();
         float hnew = 0.f;
         if (j < H) {
-            const float r = sigmoidf_(g0 + gh[j]);
-            const float z = sigmoidf_(g1 + gh[H + j]);
+            const float r = sigmoid_exact(g0 + gh[j]);
+            const float z = sigmoid_exact(g1 + gh[H + j]);
             const float n = tanhf(g2 + r * gh[2 * H + j]);
             hnew = (1.f - z) * n + z * h[j];
             const size_t o = (size_t)s * T + t;
@@ -314,7 +312,7 @@ __global__ __launch_bounds__(256) void cgru_gates1_kernel(const T* __restrict__ 
         Elem<T>::unpack(*reinterpret_cast<const uint4*>(g1 + p * 2 * C + C + cv * VEC), u);
         Elem<T>::unpack(*reinterpret_cast<const uint4*>(h + p * C + cv * VEC), hh);
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) { r[e] = sigmoidf_(r[e]); u[e] = sigmoidf_(u[e]); hh[e] *= r[e]; }
+        for (int e = 0; e < VEC; ++e) { r[e] = sigmoid_exact(r[e]); u[e] = sigmoid_exact(u[e]); hh[e] *= r[e]; }
         *reinterpret_cast<uint4*>(ru + p * 2 * C + cv * VEC) = Elem<T>::pack(r);
         *reinterpret_cast<uint4*>(ru + p * 2 * C + C + cv * VEC) = Elem<T>::pack(u);
         *reinterpret_cast<uint4*>(rh + p * C + cv * VEC) = Elem<T>::pack(hh);
@@ -417,8 +415,8 @@ __global__ __launch_bounds__(256) void clstm_gates_kernel(const T* __restrict__ 
         Elem<T>::unpack(*reinterpret_cast<const uint4*>(c_prev + p * C + cv * VEC), cp);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
-            cp[e] = sigmoidf_(gf[e]) * cp[e] + sigmoidf_(gi[e]) * tanhf(gc[e]);
-            hh[e] = sigmoidf_(go[e]) * tanhf(cp[e]);
+            cp[e] = sigmoid_exact(gf[e]) * cp[e] + sigmoid_exact(gi[e]) * tanhf(gc[e]);
+            hh[e] = sigmoid_exact(go[e]) * tanhf(cp[e]);
         }
         *reinterpret_cast<uint4*>(c + p * C + cv * VEC) = Elem<T>::pack(cp);
         *reinterpret_cast<uint4*>(h + p * C + cv * VEC) = Elem<T>::pack(hh);
@@ -448,7 +446,7 @@ __global__ __launch_bounds__(256) void clstm_gates_bwd_kernel(const T* __restric
         if (dc_in) Elem<T>::unpack(*reinterpret_cast<const uint4*>(dc_in + p * C + cv * VEC), dc);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
-            const float si = sigmoidf_(gi[e]), sf = sigmoidf_(gf[e]), so = sigmoidf_(go[e]), tg = tanhf(gc[e]);
+            const float si = sigmoid_exact(gi[e]), sf = sigmoid_exact(gf[e]), so = sigmoid_exact(go[e]), tg = tanhf(gc[e]);
             const float tc = tanhf(sf * cp[e] + si * tg);
             const float dcn = (dc_in ? dc[e] : 0.f) + d[e] * so * (1.f - tc * tc);
             gi[e] = dcn * tg * si * (1.f - si);

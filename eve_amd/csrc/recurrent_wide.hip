@@ -26,20 +26,17 @@
 
 namespace eve {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
 constexpr int WS_TILE = 16;        // sequences per workgroup = rows of the MFMA
 constexpr int WS_THREADS = 512;
 constexpr int WS_WAVES = WS_THREADS / 64;
 constexpr int WS_PAD = 4;          // floats; LDS rows of H + 4: the 16 rows of one 16-byte read group start 4 banks apart
 
-__device__ __forceinline__ float ws_sigmoid(float z) { return 1.f / (1.f + __expf(-z)); }
-__device__ __forceinline__ f32x4 ws_ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void ws_st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ f32x4 ws_zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
+__device__ __forceinline__ f32x4_t ws_ld4(const float* p) { return *reinterpret_cast<const f32x4_t*>(p); }
+__device__ __forceinline__ void ws_st4(float* p, f32x4_t v) { *reinterpret_cast<f32x4_t*>(p) = v; }
+__device__ __forceinline__ f32x4_t ws_zero4() { return f32x4_t{0.f, 0.f, 0.f, 0.f}; }
 
 // acc[c] += A(16 x 16 k) . B(16 k x columns j + c, c = 0..3): a = the lane's four A values, b[i] = row i of its B block
-__device__ __forceinline__ void ws_mfma16(f32x4 (&acc)[4], const f32x4 a, const f32x4 (&b)[4]) {
+__device__ __forceinline__ void ws_mfma16(f32x4_t (&acc)[4], const f32x4_t a, const f32x4_t (&b)[4]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[i].x, acc[0], 0, 0, 0);
@@ -63,7 +60,7 @@ __global__ __launch_bounds__(WS_THREADS) void scan_wide_fwd_kernel(int S, int T,
     const int s0 = blockIdx.x * WS_TILE;
     for (int i = tid; i < WS_TILE * H4; i += WS_THREADS) {
         const int row = i / H4, c4 = (i - row * H4) * 4;
-        f32x4 v = ws_zero4();
+        f32x4_t v = ws_zero4();
         if (h0 && s0 + row < S) v = ws_ld4(h0 + (size_t)(s0 + row) * H + c4);
         ws_st4(sm + row * ld + c4, v);
     }
@@ -75,7 +72,7 @@ __global__ __launch_bounds__(WS_THREADS) void scan_wide_fwd_kernel(int S, int T,
         for (int sl = wave; sl < nsl; sl += WS_WAVES) {
             const int j0 = sl * 64 + 4 * r;                       // this lane's columns j0 .. j0 + 3 of every gate
             const bool jok = j0 < H;                              // H % 64 != 0: the last slice is ragged (in units of 16)
-            f32x4 acc[G][4];
+            f32x4_t acc[G][4];
 #pragma unroll
             for (int g = 0; g < G; ++g)
 #pragma unroll
@@ -83,15 +80,15 @@ __global__ __launch_bounds__(WS_THREADS) void scan_wide_fwd_kernel(int S, int T,
             const float* arow = hc + r * ld + 4 * q;
             const float* bcol = whh_t + (size_t)(4 * q) * GH + (jok ? j0 : 0);
             // the operands of k-block kb + 16 are in flight during the MFMAs of block kb (the last block re-reads itself)
-            f32x4 a = ws_ld4(arow), b[G][4];
+            f32x4_t a = ws_ld4(arow), b[G][4];
 #pragma unroll
             for (int g = 0; g < G; ++g)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) b[g][i] = ws_ld4(bcol + (size_t)i * GH + g * H);
             for (int kb = 0; kb < H; kb += 16) {
                 const int kn = min(kb + 16, H - 16);
-                const f32x4 an = ws_ld4(arow + kn);
-                f32x4 bn[G][4];
+                const f32x4_t an = ws_ld4(arow + kn);
+                f32x4_t bn[G][4];
 #pragma unroll
                 for (int g = 0; g < G; ++g)
 #pragma unroll
@@ -105,16 +102,16 @@ __global__ __launch_bounds__(WS_THREADS) void scan_wide_fwd_kernel(int S, int T,
                     for (int i = 0; i < 4; ++i) b[g][i] = bn[g][i];
             }
             if (!jok) continue;
-            f32x4 bias[G];
+            f32x4_t bias[G];
 #pragma unroll
             for (int g = 0; g < G; ++g) bias[g] = ws_ld4(bhh + g * H + j0);
 #pragma unroll
             for (int reg = 0; reg < 4; ++reg) {
                 const int seq = 4 * q + reg, s = s0 + seq;
-                f32x4 hnew = ws_zero4();
+                f32x4_t hnew = ws_zero4();
                 if (s < S) {
                     const size_t o = (size_t)s * T + t;
-                    f32x4 pre[G];
+                    f32x4_t pre[G];
 #pragma unroll
                     for (int g = 0; g < G; ++g) {
                         pre[g] = ws_ld4(gi + o * GH + g * H + j0);
@@ -125,12 +122,12 @@ __global__ __launch_bounds__(WS_THREADS) void scan_wide_fwd_kernel(int S, int T,
 #pragma unroll
                         for (int c = 0; c < 4; ++c) hnew[c] = tanhf(pre[0][c]);
                     } else if (G == 3) {
-                        const f32x4 hp = ws_ld4(hc + seq * ld + j0);
-                        f32x4 rg, zg, ng, ghn;
+                        const f32x4_t hp = ws_ld4(hc + seq * ld + j0);
+                        f32x4_t rg, zg, ng, ghn;
 #pragma unroll
                         for (int c = 0; c < 4; ++c) {
-                            rg[c] = ws_sigmoid(pre[0][c] + (acc[0][c][reg] + bias[0][c]));
-                            zg[c] = ws_sigmoid(pre[1][c] + (acc[1][c][reg] + bias[1][c]));
+                            rg[c] = sigmoid_exact(pre[0][c] + (acc[0][c][reg] + bias[0][c]));
+                            zg[c] = sigmoid_exact(pre[1][c] + (acc[1][c][reg] + bias[1][c]));
                             ghn[c] = acc[2][c][reg] + bias[2][c];
                             ng[c] = tanhf(pre[2][c] + rg[c] * ghn[c]);
                             hnew[c] = (1.f - zg[c]) * ng[c] + zg[c] * hp[c];
@@ -139,14 +136,14 @@ __global__ __launch_bounds__(WS_THREADS) void scan_wide_fwd_kernel(int S, int T,
                         ws_st4(go, rg); ws_st4(go + H, zg); ws_st4(go + 2 * H, ng);
                         ws_st4(hn_pre + o * H + j0, ghn);
                     } else {
-                        f32x4 cp = ws_zero4();
+                        f32x4_t cp = ws_zero4();
                         if (t > 0) cp = ws_ld4(cs + (o - 1) * H + j0);             // this lane's own store of the step before
                         else if (c0) cp = ws_ld4(c0 + (size_t)s * H + j0);
-                        f32x4 ig, fg, gg, og, cn;
+                        f32x4_t ig, fg, gg, og, cn;
 #pragma unroll
                         for (int c = 0; c < 4; ++c) {
-                            ig[c] = ws_sigmoid(pre[0][c]); fg[c] = ws_sigmoid(pre[1][c]);
-                            gg[c] = tanhf(pre[2][c]); og[c] = ws_sigmoid(pre[3][c]);
+                            ig[c] = sigmoid_exact(pre[0][c]); fg[c] = sigmoid_exact(pre[1][c]);
+                            gg[c] = tanhf(pre[2][c]); og[c] = sigmoid_exact(pre[3][c]);
                             cn[c] = fg[c] * cp[c] + ig[c] * gg[c];
                             hnew[c] = og[c] * tanhf(cn[c]);
                         }
@@ -193,20 +190,20 @@ __global__ __launch_bounds__(WS_THREADS) void scan_wide_bwd_kernel(int S, int T,
             const int row = i / H4, c4 = (i - row * H4) * 4, s = s0 + row;
             if (s >= S) continue;
             const size_t o = (size_t)s * T + t;
-            f32x4 d = ws_ld4(dh + row * ld + c4) + ws_ld4(dhs + o * H + c4);
-            f32x4 carry = ws_zero4();
+            f32x4_t d = ws_ld4(dh + row * ld + c4) + ws_ld4(dhs + o * H + c4);
+            f32x4_t carry = ws_zero4();
             if (G == 1) {
-                const f32x4 hv = ws_ld4(hs + o * H + c4);
+                const f32x4_t hv = ws_ld4(hs + o * H + c4);
                 ws_st4(out_b + o * H + c4, d * (1.f - hv * hv));
             } else if (G == 3) {
                 const float* g = gates + o * GH + c4;
-                const f32x4 rg = ws_ld4(g), zg = ws_ld4(g + H), ng = ws_ld4(g + 2 * H);
-                f32x4 hp = ws_zero4();
+                const f32x4_t rg = ws_ld4(g), zg = ws_ld4(g + H), ng = ws_ld4(g + 2 * H);
+                f32x4_t hp = ws_zero4();
                 if (t > 0) hp = ws_ld4(hs + (o - 1) * H + c4);
                 else if (h0) hp = ws_ld4(h0 + (size_t)s * H + c4);
-                const f32x4 dn_pre = d * (1.f - zg) * (1.f - ng * ng);
-                const f32x4 dz_pre = d * (hp - ng) * zg * (1.f - zg);
-                const f32x4 dr_pre = dn_pre * ws_ld4(hn_pre + o * H + c4) * rg * (1.f - rg);
+                const f32x4_t dn_pre = d * (1.f - zg) * (1.f - ng * ng);
+                const f32x4_t dz_pre = d * (hp - ng) * zg * (1.f - zg);
+                const f32x4_t dr_pre = dn_pre * ws_ld4(hn_pre + o * H + c4) * rg * (1.f - rg);
                 float* ga = out_a + o * GH + c4;
                 float* gb = out_b + o * GH + c4;
                 ws_st4(ga, dr_pre); ws_st4(ga + H, dz_pre); ws_st4(ga + 2 * H, dn_pre);
@@ -214,14 +211,14 @@ __global__ __launch_bounds__(WS_THREADS) void scan_wide_bwd_kernel(int S, int T,
                 carry = d * zg;
             } else {
                 const float* g = gates + o * GH + c4;
-                const f32x4 ig = ws_ld4(g), fg = ws_ld4(g + H), gg = ws_ld4(g + 2 * H), og = ws_ld4(g + 3 * H);
-                const f32x4 cv = ws_ld4(cs + o * H + c4);
-                f32x4 tc, cp = ws_zero4();
+                const f32x4_t ig = ws_ld4(g), fg = ws_ld4(g + H), gg = ws_ld4(g + 2 * H), og = ws_ld4(g + 3 * H);
+                const f32x4_t cv = ws_ld4(cs + o * H + c4);
+                f32x4_t tc, cp = ws_zero4();
 #pragma unroll
                 for (int c = 0; c < 4; ++c) tc[c] = tanhf(cv[c]);
                 if (t > 0) cp = ws_ld4(cs + (o - 1) * H + c4);
                 else if (c0) cp = ws_ld4(c0 + (size_t)s * H + c4);
-                f32x4 dcv = ws_ld4(dc + row * ld + c4) + d * og * (1.f - tc * tc);
+                f32x4_t dcv = ws_ld4(dc + row * ld + c4) + d * og * (1.f - tc * tc);
                 if (dcs) dcv += ws_ld4(dcs + o * H + c4);
                 float* gb = out_b + o * GH + c4;
                 ws_st4(gb, dcv * gg * ig * (1.f - ig));
@@ -238,17 +235,17 @@ __global__ __launch_bounds__(WS_THREADS) void scan_wide_bwd_kernel(int S, int T,
         for (int sl = wave; sl < nsl; sl += WS_WAVES) {
             const int j0 = sl * 64 + 4 * r;
             const bool jok = j0 < H;
-            f32x4 acc[4];
+            f32x4_t acc[4];
 #pragma unroll
             for (int c = 0; c < 4; ++c) acc[c] = ws_zero4();
             const float* bcol = whh + (size_t)(4 * q) * H + (jok ? j0 : 0);
-            f32x4 a = ws_ld4(arow), b[4];
+            f32x4_t a = ws_ld4(arow), b[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) b[i] = ws_ld4(bcol + (size_t)i * H);
             for (int kb = 0; kb < GH; kb += 16) {
                 const int kn = min(kb + 16, GH - 16);
-                const f32x4 an = ws_ld4(arow + kn);
-                f32x4 bn[4];
+                const f32x4_t an = ws_ld4(arow + kn);
+                f32x4_t bn[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) bn[i] = ws_ld4(bcol + (size_t)(kn + i) * H);
                 ws_mfma16(acc, aok ? a : ws_zero4(), b);
@@ -260,7 +257,7 @@ __global__ __launch_bounds__(WS_THREADS) void scan_wide_bwd_kernel(int S, int T,
 #pragma unroll
             for (int reg = 0; reg < 4; ++reg) {
                 float* p = dh + (4 * q + reg) * ld + j0;
-                ws_st4(p, ws_ld4(p) + f32x4{acc[0][reg], acc[1][reg], acc[2][reg], acc[3][reg]});
+                ws_st4(p, ws_ld4(p) + f32x4_t{acc[0][reg], acc[1][reg], acc[2][reg], acc[3][reg]});
             }
         }
         __syncthreads();

@@ -18,6 +18,7 @@
 // accumulator holds the 4 channels of one pixel per lane, so every store is a 128-byte row segment of the NCHW output:
 // float32 straight from the accumulators, no 16-bit rounding and no unpack pass.
 #include "common.h"
+#include "lds_dma.h"
 
 namespace eve {
 
@@ -70,11 +71,9 @@ __global__ __launch_bounds__(256) void stem_dgrad_pack_kernel(const float* __res
     else reinterpret_cast<uint16_t*>(out)[i] = Elem<T>::IS_BF16 ? (uint16_t)f32_to_bf16_bits(v) : (uint16_t)(pack2_f16(v, 0.f) & 0xffffu);
 }
 
-typedef uint32_t sd_u32x4_t __attribute__((ext_vector_type(4)));
-
 // One dconv row (all 64 channels of SD_COLS columns starting at gx0) into registers; zeros outside the image.
 template <typename T>
-__device__ __forceinline__ void sd_load_row(sd_u32x4_t (&v)[SdTraits<T>::LOADS], const sd_u32x4_t* __restrict__ src, int n, int oy,
+__device__ __forceinline__ void sd_load_row(u32x4_t (&v)[SdTraits<T>::LOADS], const u32x4_t* __restrict__ src, int n, int oy,
                                             int OH, int OW, int gx0, int tid) {
     constexpr int CH = SdTraits<T>::CHUNKS;
     const bool row_ok = oy >= 0 && oy < OH;
@@ -82,7 +81,7 @@ __device__ __forceinline__ void sd_load_row(sd_u32x4_t (&v)[SdTraits<T>::LOADS],
     for (int i = 0; i < SdTraits<T>::LOADS; ++i) {
         const int id = tid + i * SD_THREADS;
         const int col = id / CH, ch = id % CH, gx = gx0 + col;
-        sd_u32x4_t q = {0u, 0u, 0u, 0u};
+        u32x4_t q = {0u, 0u, 0u, 0u};
         if (row_ok && id < SD_COLS * CH && gx >= 0 && gx < OW) q = src[(((size_t)n * OH + oy) * OW + gx) * CH + ch];
         v[i] = q;
     }
@@ -90,29 +89,21 @@ __device__ __forceinline__ void sd_load_row(sd_u32x4_t (&v)[SdTraits<T>::LOADS],
 // ... and into its ring slot.  The 16-byte chunk index is XORed with the column so that the 8 lanes of one ds_read_b128
 // (consecutive columns, same chunk) fall on distinct banks.
 template <typename T>
-__device__ __forceinline__ void sd_store_row(char* slot, const sd_u32x4_t (&v)[SdTraits<T>::LOADS], int tid) {
+__device__ __forceinline__ void sd_store_row(char* slot, const u32x4_t (&v)[SdTraits<T>::LOADS], int tid) {
     constexpr int CH = SdTraits<T>::CHUNKS;
 #pragma unroll
     for (int i = 0; i < SdTraits<T>::LOADS; ++i) {
         const int id = tid + i * SD_THREADS;
         if (id < SD_COLS * CH) {
             const int col = id / CH, ch = id % CH;
-            *reinterpret_cast<sd_u32x4_t*>(slot + col * SdTraits<T>::PIX_BYTES + ((ch ^ (col & (CH - 1))) << 4)) = v[i];
+            *reinterpret_cast<u32x4_t*>(slot + col * SdTraits<T>::PIX_BYTES + ((ch ^ (col & (CH - 1))) << 4)) = v[i];
         }
     }
 }
 template <typename T>
-__device__ __forceinline__ sd_u32x4_t sd_lds_chunk(const char* slot, int col, int ch) {
+__device__ __forceinline__ u32x4_t sd_lds_chunk(const char* slot, int col, int ch) {
     constexpr int CH = SdTraits<T>::CHUNKS;
-    return *reinterpret_cast<const sd_u32x4_t*>(slot + col * SdTraits<T>::PIX_BYTES + ((ch ^ (col & (CH - 1))) << 4));
-}
-
-template <typename T>
-__device__ __forceinline__ void sd_mfma16(f32x4_t& acc, const sd_u32x4_t& a, const sd_u32x4_t& b) {
-    if constexpr (Elem<T>::IS_BF16)
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc, 0, 0, 0);
-    else
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), acc, 0, 0, 0);
+    return *reinterpret_cast<const u32x4_t*>(slot + col * SdTraits<T>::PIX_BYTES + ((ch ^ (col & (CH - 1))) << 4));
 }
 
 // grid: (strips * bands, N); band_rows quad rows per band.
@@ -130,23 +121,23 @@ __global__ __launch_bounds__(256) void stem_dgrad_kernel(const T* __restrict__ d
     const int r0 = strip * SD_QUADS;
     const int q0 = band * band_rows;
     const int q1 = min(q0 + band_rows, OH);
-    const sd_u32x4_t* src = reinterpret_cast<const sd_u32x4_t*>(dconv);
+    const u32x4_t* src = reinterpret_cast<const u32x4_t*>(dconv);
     char* ring = sd_lds;
     auto slot = [&](int oy) { return ring + ((oy + 1) & 3) * Tr::ROW_BYTES; };
 
     // filter: 16-bit -> registers (32 fragments), float32 -> LDS behind the ring
-    sd_u32x4_t wreg[F32 ? 1 : SD_KSTEPS16];
+    u32x4_t wreg[F32 ? 1 : SD_KSTEPS16];
     if constexpr (F32) {
-        const sd_u32x4_t* w4 = reinterpret_cast<const sd_u32x4_t*>(wpk);
-        sd_u32x4_t* wl = reinterpret_cast<sd_u32x4_t*>(sd_lds + Tr::RING_BYTES);
+        const u32x4_t* w4 = reinterpret_cast<const u32x4_t*>(wpk);
+        u32x4_t* wl = reinterpret_cast<u32x4_t*>(sd_lds + Tr::RING_BYTES);
         for (int i = tid; i < SD_KSTEPS32 * 64 / 4; i += SD_THREADS) wl[i] = w4[i];
     } else {
-        const sd_u32x4_t* w4 = reinterpret_cast<const sd_u32x4_t*>(wpk);
+        const u32x4_t* w4 = reinterpret_cast<const u32x4_t*>(wpk);
 #pragma unroll
         for (int s = 0; s < SD_KSTEPS16; ++s) wreg[s] = w4[s * 64 + lane];
     }
 
-    sd_u32x4_t nxt[Tr::LOADS];
+    u32x4_t nxt[Tr::LOADS];
     for (int oy = q0 - 1; oy <= q0 + 1; ++oy) {
         sd_load_row<T>(nxt, src, n, oy, OH, OW, r0 - 1, tid);
         sd_store_row<T>(slot(oy), nxt, tid);
@@ -181,8 +172,8 @@ __global__ __launch_bounds__(256) void stem_dgrad_kernel(const T* __restrict__ d
                         acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wl[(s + 3) * 64 + lane], v.w, acc1, 0, 0, 0);
                     }
                 } else {
-                    sd_mfma16<T>(acc0, wreg[2 * p], sd_lds_chunk<T>(sl, col, 2 * g));
-                    sd_mfma16<T>(acc1, wreg[2 * p + 1], sd_lds_chunk<T>(sl, col, 2 * g + 1));
+                    mfma16<T>(acc0, wreg[2 * p], sd_lds_chunk<T>(sl, col, 2 * g));
+                    mfma16<T>(acc1, wreg[2 * p + 1], sd_lds_chunk<T>(sl, col, 2 * g + 1));
                 }
             }
         }

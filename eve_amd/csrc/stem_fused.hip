@@ -33,40 +33,11 @@ constexpr int SF_XROW = 136 * 8;                 // bytes per packed input row (
 constexpr int SF_KBYTES = 64 * 3 * 4;               // backward: {rstd, B, C} per channel and wave
 constexpr uint32_t SF_NEG = 0xff61b1e0u;         // -3.0e38 with the four key bits clear
 
-__device__ __forceinline__ void sf_dma16(const eve_int4& rsrc, uint32_t lds, int voff, int soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                 :: "s"(lds), "v"(voff), "s"(rsrc), "s"(soff) : "memory", "m0");
-}
-__device__ __forceinline__ void sf_dma4(const eve_int4& rsrc, uint32_t lds, int voff, int soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, %3 offen lds"
-                 :: "s"(lds), "v"(voff), "s"(rsrc), "s"(soff) : "memory", "m0");
-}
-typedef uint32_t sf_u32x4_t __attribute__((ext_vector_type(4)));
-typedef uint32_t sf_u32x2_t __attribute__((ext_vector_type(2)));
-// A 16-byte fragment stays ONE vector value from the LDS load to the MFMA operand.  (Round 6: as HIP's uint4 -- a struct -- the
-// load was split into two 8-byte halves by the middle end and the back end re-merged the filter fragments as ds_read2_b64: twice
-// the LDS cycles of ds_read_b128 and banked differently from what the swizzle is built for.  SQ counters of the forward: 59 % of
-// the LDS-array cycles were bank conflicts, the array 70 % busy, 23 % of the wave cycles stalled on LDS issue.)
-typedef sf_u32x4_t sf_frag_t;
-__device__ __forceinline__ sf_frag_t sf_lds_read(uint32_t addr) {
-    return *reinterpret_cast<const EVE_LDS sf_u32x4_t*>((uintptr_t)addr);
-}
-template <typename H>
-__device__ __forceinline__ void sf_mfma(f32x4_t& acc, const sf_frag_t& a, const sf_frag_t& b) {
-    if constexpr (Elem<H>::IS_BF16)
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc, 0, 0, 0);
-    else
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), acc, 0, 0, 0);
-}
-template <int CTRL>
-__device__ __forceinline__ uint32_t sf_dpp(uint32_t old, uint32_t src) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)src, CTRL, 0xf, 0xf, false);
-}
 __device__ __forceinline__ float sf_row_sum16(float v) {          // butterfly over the 16 lanes of a DPP row
-    v += __builtin_bit_cast(float, sf_dpp<0xb1>(0u, __builtin_bit_cast(uint32_t, v)));     // quad_perm [1,0,3,2]
-    v += __builtin_bit_cast(float, sf_dpp<0x4e>(0u, __builtin_bit_cast(uint32_t, v)));     // quad_perm [2,3,0,1]
-    v += __builtin_bit_cast(float, sf_dpp<0x141>(0u, __builtin_bit_cast(uint32_t, v)));    // row_half_mirror
-    v += __builtin_bit_cast(float, sf_dpp<0x140>(0u, __builtin_bit_cast(uint32_t, v)));    // row_mirror
+    v += __builtin_bit_cast(float, dpp_mov<0xb1>(0u, __builtin_bit_cast(uint32_t, v)));     // quad_perm [1,0,3,2]
+    v += __builtin_bit_cast(float, dpp_mov<0x4e>(0u, __builtin_bit_cast(uint32_t, v)));     // quad_perm [2,3,0,1]
+    v += __builtin_bit_cast(float, dpp_mov<0x141>(0u, __builtin_bit_cast(uint32_t, v)));    // row_half_mirror
+    v += __builtin_bit_cast(float, dpp_mov<0x140>(0u, __builtin_bit_cast(uint32_t, v)));    // row_mirror
     return v;
 }
 __device__ __forceinline__ float sf_fmax3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
@@ -96,8 +67,8 @@ __device__ __forceinline__ void sf_merge_moments(float ma, float m2a, float mb, 
 }
 template <int CTRL>
 __device__ __forceinline__ void sf_moments_step(float& m, float& m2, float n) {
-    const float mb = __builtin_bit_cast(float, sf_dpp<CTRL>(0u, __builtin_bit_cast(uint32_t, m)));
-    const float m2b = __builtin_bit_cast(float, sf_dpp<CTRL>(0u, __builtin_bit_cast(uint32_t, m2)));
+    const float mb = __builtin_bit_cast(float, dpp_mov<CTRL>(0u, __builtin_bit_cast(uint32_t, m)));
+    const float m2b = __builtin_bit_cast(float, dpp_mov<CTRL>(0u, __builtin_bit_cast(uint32_t, m2)));
     sf_merge_moments(m, m2, mb, m2b, n, m, m2);
 }
 __device__ __forceinline__ void sf_row_moments16(float& m, float& m2, float n) {   // n values per lane -> 16 n in every lane
@@ -131,11 +102,11 @@ __device__ __forceinline__ void sf_conv_tap_row(f32x4_t (&acc)[4][4], uint32_t r
     int slot = slot0 + kh;
     slot = slot >= SF_RING ? slot - SF_RING : slot;
     const uint32_t xa = ring + slot * SF_ROWB + xoff, wa = wbase + kh * 4096;
-    sf_frag_t fx[4], fw[4];
+    frag_t fx[4], fw[4];
 #pragma unroll
-    for (int mt = 0; mt < 4; ++mt) fx[mt] = sf_lds_read(xa + (mt & 1) * 16 + (mt >> 1) * 512);
+    for (int mt = 0; mt < 4; ++mt) fx[mt] = lds_read16(xa + (mt & 1) * 16 + (mt >> 1) * 512);
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt) fw[nt] = sf_lds_read(wa + nt * 1024);
+    for (int nt = 0; nt < 4; ++nt) fw[nt] = lds_read16(wa + nt * 1024);
     const f32x4_t zero = {0.f, 0.f, 0.f, 0.f};             // first filter row: C = 0 is an inline MFMA operand, no zero-fill
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt)
@@ -143,7 +114,7 @@ __device__ __forceinline__ void sf_conv_tap_row(f32x4_t (&acc)[4][4], uint32_t r
         for (int mt = 0; mt < 4; ++mt)
         {
             if (FIRST) acc[mt][nt] = zero;
-            sf_mfma<H>(acc[mt][nt], fw[nt], fx[mt]);
+            mfma16<H>(acc[mt][nt], fw[nt], fx[mt]);
         }
 }
 // COMPACT keeps the filter-row loop rolled (one set of fragment registers) for the register-hungry backward
@@ -165,8 +136,8 @@ __device__ __forceinline__ void sf_stage_row(const eve_int4& rs, uint32_t ring, 
     const int slot = row % SF_RING;
     const bool live = row < rows;
     const int soff = live ? img_off + row * SF_XROW : 0;
-    sf_dma16(rs, ring + slot * SF_ROWB, live ? lane * 16 + 8 : EVE_OOB, soff);
-    sf_dma4(rs, ring + slot * SF_ROWB + 1024, live ? lane * 4 + 8 + 1024 : EVE_OOB, soff);
+    lds_dma16_asm(rs, ring + slot * SF_ROWB, live ? lane * 16 + 8 : EVE_OOB, soff);
+    lds_dma4_asm(rs, ring + slot * SF_ROWB + 1024, live ? lane * 4 + 8 + 1024 : EVE_OOB, soff);
 }
 
 template <typename H>
@@ -289,8 +260,8 @@ __global__ __launch_bounds__(64 * SF_WAVES) void stem_fwd_fused_kernel(const int
                         const uint32_t o = (__builtin_bit_cast(uint32_t, of) & 0xfffffff0u) | khbits;
                         const uint32_t ol = (__builtin_bit_cast(uint32_t, of) & 0xfffffff0u) | (khbits | 2u);
                         // column 2q-1 = the odd column of lane li-1 (lane 0: the last lane of the previous tile / padding)
-                        const uint32_t edge = j == 0 ? SF_NEG : sf_dpp<0x121>(0u, carry);          // row_ror:1
-                        const uint32_t l = sf_dpp<0x111>(edge, ol);                                  // row_shr:1
+                        const uint32_t edge = j == 0 ? SF_NEG : dpp_mov<0x121>(0u, carry);          // row_ror:1
+                        const uint32_t l = dpp_mov<0x111>(edge, ol);                                  // row_shr:1
                         carry = ol;
                         const float h = sf_fmax3(__builtin_bit_cast(float, l), __builtin_bit_cast(float, e),
                                                  __builtin_bit_cast(float, o));
@@ -486,25 +457,25 @@ __global__ __launch_bounds__(1024) void stem_fwd_pairs_kernel(const int N, const
             if (live) {
                 f32x4_t acc[4][2];
                 {
-                    auto conv_frags = [&](int kh, sf_frag_t (&x4)[4], sf_frag_t (&w2)[2]) {
+                    auto conv_frags = [&](int kh, frag_t (&x4)[4], frag_t (&w2)[2]) {
                         int slot = slot0 + kh;
                         slot = slot >= SF_RING ? slot - SF_RING : slot;
                         const uint32_t xa = ring + slot * SF_ROWB + xoff, wa = wbase + kh * 4096;
 #pragma unroll
-                        for (int mt = 0; mt < 4; ++mt) x4[mt] = sf_lds_read(xa + (mt & 1) * 16 + (mt >> 1) * 512);
+                        for (int mt = 0; mt < 4; ++mt) x4[mt] = lds_read16(xa + (mt & 1) * 16 + (mt >> 1) * 512);
 #pragma unroll
-                        for (int nt = 0; nt < 2; ++nt) w2[nt] = sf_lds_read(wa + nt * 1024);
+                        for (int nt = 0; nt < 2; ++nt) w2[nt] = lds_read16(wa + nt * 1024);
                     };
-                    auto conv_mfma = [&](bool first, const sf_frag_t (&x4)[4], const sf_frag_t (&w2)[2]) {
+                    auto conv_mfma = [&](bool first, const frag_t (&x4)[4], const frag_t (&w2)[2]) {
 #pragma unroll
                         for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
                             for (int mt = 0; mt < 4; ++mt) {
                                 if (first) acc[mt][nt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-                                sf_mfma<H>(acc[mt][nt], w2[nt], x4[mt]);
+                                mfma16<H>(acc[mt][nt], w2[nt], x4[mt]);
                             }
                     };
-                    sf_frag_t fxa[4], fwa[2], fxb[4], fwb[2];
+                    frag_t fxa[4], fwa[2], fxb[4], fwb[2];
                     conv_frags(0, fxa, fwa);
                     conv_frags(1, fxb, fwb);
                     conv_mfma(true, fxa, fwa);
@@ -562,8 +533,8 @@ __global__ __launch_bounds__(1024) void stem_fwd_pairs_kernel(const int N, const
                             const uint32_t kl0 = ko0 + 2u, kl1 = ko1 + 2u;          // the same columns as kw = 0 of the windows to their right
                             // column 2q - 1 = the odd column of lane li - 1; lane 0 of the first tile: the padding (its own even key
                             // stands in: no maximum changes), of the second tile: the last lane of the first
-                            const uint32_t l0 = sf_dpp<0x111>(ke0, kl0);                                   // row_shr:1
-                            const uint32_t l1 = sf_dpp<0x111>(sf_dpp<0x121>(0u, kl0), kl1);                // row_ror:1, row_shr:1 over it
+                            const uint32_t l0 = dpp_mov<0x111>(ke0, kl0);                                   // row_shr:1
+                            const uint32_t l1 = dpp_mov<0x111>(dpp_mov<0x121>(0u, kl0), kl1);                // row_ror:1, row_shr:1 over it
                             const float h0 = sf_fmax3(__builtin_bit_cast(float, l0), __builtin_bit_cast(float, ke0), __builtin_bit_cast(float, ko0));
                             const float h1 = sf_fmax3(__builtin_bit_cast(float, l1), __builtin_bit_cast(float, ke1), __builtin_bit_cast(float, ko1));
                             const float m0 = fmaxf(__builtin_bit_cast(float, M[0][nt][r]), h0), m1 = fmaxf(__builtin_bit_cast(float, M[1][nt][r]), h1);
@@ -598,8 +569,8 @@ __global__ __launch_bounds__(1024) void stem_fwd_pairs_kernel(const int N, const
                             //  column tile as the scalar offset -- the per-lane 64-bit addresses of the plain stores were spilled)
                             (void)o;
                             const int so = (py * 32 + 16 * j) * 64;
-                            sf_u32x4_t pv = {pk[0], pk[1], pk[2], pk[3]};
-                            sf_u32x2_t iv = {ib[0], ib[1]};
+                            u32x4_t pv = {pk[0], pk[1], pk[2], pk[3]};
+                            u32x2_t iv = {ib[0], ib[1]};
                             __builtin_amdgcn_raw_buffer_store_b128(pv, ry, lane_off * 2, so * 2, 0);
                             __builtin_amdgcn_raw_buffer_store_b64(iv, ri, lane_off, so, 0);
                         }
@@ -637,7 +608,7 @@ __global__ __launch_bounds__(1024) void stem_fwd_pairs_kernel(const int N, const
                     Elem<H>::unpack(__builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(ry, lane_off * 2, so, 0)), f);
 #pragma unroll
                     for (int c = 0; c < 8; ++c) f[c] = fmaxf((f[c] - mean[c >> 2][c & 3]) * rstd[c >> 2][c & 3], 0.f);
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(sf_u32x4_t, Elem<H>::pack(f)), ry, lane_off * 2, so, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, Elem<H>::pack(f)), ry, lane_off * 2, so, 0);
                 }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -708,11 +679,11 @@ __device__ __forceinline__ void sf_chunk(const SfPooledRow& P, int j, int nt, ui
     eg[0] = P.eg[j][2 * nt]; eg[1] = P.eg[j][2 * nt + 1]; cd = P.code[j][nt];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-        const uint32_t edge = j == 0 ? sf_dpp<0x12f>(0u, P.eg[1][2 * nt + k]) : 0u;    // row_ror:15 = rotate left by one
-        neg[k] = sf_dpp<0x101>(edge, eg[k]);                                            // row_shl:1
+        const uint32_t edge = j == 0 ? dpp_mov<0x12f>(0u, P.eg[1][2 * nt + k]) : 0u;    // row_ror:15 = rotate left by one
+        neg[k] = dpp_mov<0x101>(edge, eg[k]);                                            // row_shl:1
     }
-    const uint32_t edge = j == 0 ? sf_dpp<0x12f>(0u, P.code[1][nt]) : 0u;
-    ncd = sf_dpp<0x101>(edge, cd);
+    const uint32_t edge = j == 0 ? dpp_mov<0x12f>(0u, P.code[1][nt]) : 0u;
+    ncd = dpp_mov<0x101>(edge, cd);
 }
 
 // (fallback / test reference since round 4: four-wave workgroups, one wave per SIMD -- with eight the 256-register budget spilled)
@@ -900,11 +871,11 @@ __device__ __forceinline__ void sb_chunk(const SbPooledRow& P, int j, int ntl, u
     eg[0] = P.eg[j][2 * ntl]; eg[1] = P.eg[j][2 * ntl + 1]; cd = P.code[j][ntl];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-        const uint32_t edge = j == 0 ? sf_dpp<0x12f>(0u, P.eg[1][2 * ntl + k]) : 0u;   // row_ror:15 = rotate left by one
-        neg[k] = sf_dpp<0x101>(edge, eg[k]);                                            // row_shl:1
+        const uint32_t edge = j == 0 ? dpp_mov<0x12f>(0u, P.eg[1][2 * ntl + k]) : 0u;   // row_ror:15 = rotate left by one
+        neg[k] = dpp_mov<0x101>(edge, eg[k]);                                            // row_shl:1
     }
-    const uint32_t edge = j == 0 ? sf_dpp<0x12f>(0u, P.code[1][ntl]) : 0u;
-    ncd = sf_dpp<0x101>(edge, cd);
+    const uint32_t edge = j == 0 ? dpp_mov<0x12f>(0u, P.code[1][ntl]) : 0u;
+    ncd = dpp_mov<0x101>(edge, cd);
 }
 __device__ __forceinline__ uint2 sb_tr_read(uint32_t lds_byte_addr) {
     EVE_LDS char* base = (EVE_LDS char*)(size_t)lds_byte_addr;
@@ -1059,26 +1030,26 @@ __global__ __launch_bounds__(128 * PAIRS, 2) void stem_bwd_wgrad_kernel(const in
                     //    fragments requested before the first row's MFMAs (a full double buffer over all seven rows spills: the
                     //    112 weight-gradient accumulators leave ~90 registers for everything else) --
                     f32x4_t acc[4][2];
-                    auto conv_frags = [&](int kh, sf_frag_t (&x4)[4], sf_frag_t (&w2)[2]) {
+                    auto conv_frags = [&](int kh, frag_t (&x4)[4], frag_t (&w2)[2]) {
                         int slot = slot0 + kh;
                         slot = slot >= SF_RING ? slot - SF_RING : slot;
                         const uint32_t xa = ring + slot * SF_ROWB + xoff, wa = wbase + kh * 4096;
 #pragma unroll
-                        for (int mt = 0; mt < 4; ++mt) x4[mt] = sf_lds_read(xa + (mt & 1) * 16 + (mt >> 1) * 512);
+                        for (int mt = 0; mt < 4; ++mt) x4[mt] = lds_read16(xa + (mt & 1) * 16 + (mt >> 1) * 512);
 #pragma unroll
-                        for (int nt = 0; nt < 2; ++nt) w2[nt] = sf_lds_read(wa + nt * 1024);
+                        for (int nt = 0; nt < 2; ++nt) w2[nt] = lds_read16(wa + nt * 1024);
                     };
-                    auto conv_mfma = [&](bool first, const sf_frag_t (&x4)[4], const sf_frag_t (&w2)[2]) {
+                    auto conv_mfma = [&](bool first, const frag_t (&x4)[4], const frag_t (&w2)[2]) {
 #pragma unroll
                         for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
                             for (int mt = 0; mt < 4; ++mt) {
                                 if (first) acc[mt][nt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-                                sf_mfma<H>(acc[mt][nt], w2[nt], x4[mt]);
+                                mfma16<H>(acc[mt][nt], w2[nt], x4[mt]);
                             }
                     };
                     {
-                        sf_frag_t fxa[4], fwa[2], fxb[4], fwb[2];
+                        frag_t fxa[4], fwa[2], fxb[4], fwb[2];
                         conv_frags(0, fxa, fwa);
                         conv_frags(1, fxb, fwb);
                         conv_mfma(true, fxa, fwa);
@@ -1137,11 +1108,8 @@ __global__ __launch_bounds__(128 * PAIRS, 2) void stem_bwd_wgrad_kernel(const in
                             // pixel x = 2 (li + 16 j) (+ 1), local channels nt * 16 + 4 lg + 0..3: one 8-byte slot, swizzled by
                             // the pixel row so that the 16 lanes of a store / the 32 of a transposing read spread over the banks
                             const int xe_row = 2 * (li + 16 * j), slot8 = nt * 4 + lg;
-                            typedef uint32_t sb_u32x2_t __attribute__((ext_vector_type(2)));
-                            EVE_LDS sb_u32x2_t* pe = (EVE_LDS sb_u32x2_t*)(size_t)(sD + xe_row * SB_DROW + ((slot8 ^ ((xe_row >> 1) & 7)) << 3));
-                            EVE_LDS sb_u32x2_t* po = (EVE_LDS sb_u32x2_t*)(size_t)(sD + (xe_row + 1) * SB_DROW + ((slot8 ^ (((xe_row + 1) >> 1) & 7)) << 3));
-                            *pe = sb_u32x2_t{Elem<H>::pack2(de[0], de[1]), Elem<H>::pack2(de[2], de[3])};
-                            *po = sb_u32x2_t{Elem<H>::pack2(dd[0], dd[1]), Elem<H>::pack2(dd[2], dd[3])};
+                            lds_write8(sD + xe_row * SB_DROW + ((slot8 ^ ((xe_row >> 1) & 7)) << 3), Elem<H>::pack2(de[0], de[1]), Elem<H>::pack2(de[2], de[3]));
+                            lds_write8(sD + (xe_row + 1) * SB_DROW + ((slot8 ^ (((xe_row + 1) >> 1) & 7)) << 3), Elem<H>::pack2(dd[0], dd[1]), Elem<H>::pack2(dd[2], dd[3]));
                         }
                     }
                     // -- dW += dconv^T x patches: K = the row's 64 pixels in two chunks of 32; 28 patch fragments, each used by two

@@ -6,8 +6,6 @@
 namespace eve {
 namespace {
 
-__device__ __forceinline__ float tail_sigmoid(float z) { return 1.f / (1.f + __expf(-z)); }
-
 // ---------------------------------------------------------------------------------------------------
 // eve_eye_tail_stream_fwd: one workgroup (384 threads = six waves) per sequence.  A chunk of Tc frames is processed in
 // sub-chunks of TAIL_TS frames whose activations stay in LDS; every non-recurrent layer reads its weights once per
@@ -127,8 +125,8 @@ __global__ __launch_bounds__(TAIL_THREADS) void eye_tail_stream_fwd_kernel(
                 float hnew = 0.f;
                 if (j < TAIL_H) {
                     const float* gi = X + t * TAIL_F;
-                    const float r = tail_sigmoid(gi[j] + gh[j]);
-                    const float z = tail_sigmoid(gi[TAIL_H + j] + gh[TAIL_H + j]);
+                    const float r = sigmoid_exact(gi[j] + gh[j]);
+                    const float z = sigmoid_exact(gi[TAIL_H + j] + gh[TAIL_H + j]);
                     const float n = tanhf(gi[2 * TAIL_H + j] + r * gh[2 * TAIL_H + j]);
                     hnew = (1.f - z) * n + z * h[j];
                     Bf[t * TAIL_LDB + j] = hnew;

@@ -21,46 +21,6 @@ struct WgradHaloParams {
     int nreg;                          // wgrad_halo64_kernel: bands resident in LDS (2 or 3)
 };
 
-// three in-place MFMAs sharing the A operand (one filter row): c[i] += a x b[i]
-__device__ __forceinline__ void mma3_bf16_inplace(f32x4_t& c0, f32x4_t& c1, f32x4_t& c2, const uint4& a4, const uint4 (&b4)[3]) {
-    const u32x4_t a = __builtin_bit_cast(u32x4_t, a4);
-    const u32x4_t b0 = __builtin_bit_cast(u32x4_t, b4[0]), b1 = __builtin_bit_cast(u32x4_t, b4[1]), b2 = __builtin_bit_cast(u32x4_t, b4[2]);
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_mfma_f32_16x16x32_bf16 %0, %3, %4, %0\n\t"
-        "v_mfma_f32_16x16x32_bf16 %1, %3, %5, %1\n\t"
-        "v_mfma_f32_16x16x32_bf16 %2, %3, %6, %2"
-        : "+v"(c0), "+v"(c1), "+v"(c2)                       // accumulators in architectural VGPRs (unified file on gfx950):
-        : "v"(a), "v"(b0), "v"(b1), "v"(b2));                 // the epilogue reads them without a copy out of the AGPRs
-}
-__device__ __forceinline__ void mma1_bf16_inplace(f32x4_t& c, const uint4& a4, const uint4& b4) {
-    const u32x4_t a = __builtin_bit_cast(u32x4_t, a4), b = __builtin_bit_cast(u32x4_t, b4);
-    asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ void mma3_f16_inplace(f32x4_t& c0, f32x4_t& c1, f32x4_t& c2, const uint4& a4, const uint4 (&b4)[3]) {
-    const u32x4_t a = __builtin_bit_cast(u32x4_t, a4);
-    const u32x4_t b0 = __builtin_bit_cast(u32x4_t, b4[0]), b1 = __builtin_bit_cast(u32x4_t, b4[1]), b2 = __builtin_bit_cast(u32x4_t, b4[2]);
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_mfma_f32_16x16x32_f16 %0, %3, %4, %0\n\t"
-        "v_mfma_f32_16x16x32_f16 %1, %3, %5, %1\n\t"
-        "v_mfma_f32_16x16x32_f16 %2, %3, %6, %2"
-        : "+v"(c0), "+v"(c1), "+v"(c2)                       // accumulators in architectural VGPRs (unified file on gfx950):
-        : "v"(a), "v"(b0), "v"(b1), "v"(b2));                 // the epilogue reads them without a copy out of the AGPRs
-}
-__device__ __forceinline__ void mma1_f16_inplace(f32x4_t& c, const uint4& a4, const uint4& b4) {
-    const u32x4_t a = __builtin_bit_cast(u32x4_t, a4), b = __builtin_bit_cast(u32x4_t, b4);
-    asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-}
-template <typename H>
-__device__ __forceinline__ void mma3_inplace(f32x4_t& c0, f32x4_t& c1, f32x4_t& c2, const uint4& a4, const uint4 (&b4)[3]) {
-    if constexpr (Elem<H>::IS_BF16) mma3_bf16_inplace(c0, c1, c2, a4, b4); else mma3_f16_inplace(c0, c1, c2, a4, b4);
-}
-template <typename H>
-__device__ __forceinline__ void mma1_inplace(f32x4_t& c, const uint4& a4, const uint4& b4) {
-    if constexpr (Elem<H>::IS_BF16) mma1_bf16_inplace(c, a4, b4); else mma1_f16_inplace(c, a4, b4);
-}
-
 // KS = 3: the 3x3 / pad 1 case above.  KS = 1: 1x1 convolutions of the same planes (skip layers): no halo, one tap --
 // a plain [Cout][Cin] += dy^T x over the band, where the gather kernel's 256-wide K tile is 6-25 % occupied.
 template <typename H, int MT, int CT, int KS = 3>
