@@ -168,6 +168,8 @@ SIGNATURES = {
     'eve_stream_state_rows': [I, I, L, L, L, P, P, P, P],
     'eve_eye_tail_stream_fwd_len': [I, I, P, P, POINTER(EyeTailWeights), P, P, P, P, P, P, P],
     'eve_stream_state_rows_at': [I, I, I, L, L, L, L, P, P, P, P],
+    'eve_stream_mask_plan': [I, I, P, P, P, P, P, P, P, P, P],
+    'eve_stream_permute_rows': [I, I, L, L, L, P, P, P, P],
     'eve_screen_u8_area_to_nchw': [L, I, I, I, P, I, I, P, P],
     'eve_eye_warp_u8_to_nchw': [L, I, I, I, P, P, I, I, P, P],
     'eve_eye_warp_u8_to_stem': [I, L, I, I, I, P, P, I, I, P, P],

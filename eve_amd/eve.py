@@ -31,6 +31,14 @@ def _mean2(a, b):
     return torch.stack([a, b], dim=-1).mean(dim=-1)
 
 
+def _fuse2(a, b, eye_valid):
+    """The binocular value of a masked EVEStream step, a, b [B, T, ...] for the left and the right eye, eye_valid bool [B, T, 2]:
+    _mean2's bits where both eyes are usable, the usable eye's own value where one is (the right one's where none is: such a
+    frame is invalid).  Selects only: whatever the other eye holds -- a NaN included -- does not reach the result."""
+    left, right = (eye_valid[:, :, e].reshape(eye_valid.shape[:2] + (1,) * (a.dim() - 2)) for e in (0, 1))
+    return torch.where(left & right, _mean2(a, b), torch.where(left, a, b))
+
+
 class EVE(nn.Module):
     def __init__(self, output_predictions=False):
         super(EVE, self).__init__()
@@ -147,10 +155,11 @@ class EVE(nn.Module):
             d['g_validity'] = d['PoG_cm_tobii_validity']
 
     # ------------------------------------------------------------------------------------------ eve.py:545-601
-    def _pog_block(self, d, inter, g_key, out_suffix, kappa_suffix=None, heatmap_history=False):
+    def _pog_block(self, d, inter, g_key, out_suffix, kappa_suffix=None, heatmap_history=False, eye_valid=None):
         """Per-eye PoG from `<side>_g_<g_key>`, their mean, the combined gaze, the heat-map -- for all B*T frames.  With
         `kappa_suffix` the offset augmentation is applied first and the augmented angles are stored back under
-        `<side>_g_<kappa_suffix>`."""
+        `<side>_g_<kappa_suffix>`.  eye_valid (a masked EVEStream step: bool [B, T, 2]): the binocular PoG is the usable eye's own
+        where only one is (_fuse2), and the combined gaze is rotated by d['combined_R'] (_predict_sequence)."""
         if 'inv_camera_transformation' not in d:                      # GazeCapture / MPIIGaze style inputs
             if kappa_suffix is not None:
                 self._augment_only(d, inter, g_key, kappa_suffix)
@@ -174,11 +183,11 @@ class EVE(nn.Module):
             inter['%s_PoG_cm_%s' % (side, out_suffix)] = (0.1 * mm).view(B, T, 2)
             inter['%s_PoG_px_%s' % (side, out_suffix)] = px.view(B, T, 2)
         for unit in ('px', 'cm'):
-            inter['PoG_%s_%s' % (unit, out_suffix)] = _mean2(inter['left_PoG_%s_%s' % (unit, out_suffix)],
-                                                            inter['right_PoG_%s_%s' % (unit, out_suffix)])
+            both = inter['left_PoG_%s_%s' % (unit, out_suffix)], inter['right_PoG_%s_%s' % (unit, out_suffix)]
+            inter['PoG_%s_%s' % (unit, out_suffix)] = _mean2(*both) if eye_valid is None else _fuse2(both[0], both[1], eye_valid)
         inter['PoG_mm_' + out_suffix] = 10.0 * inter['PoG_cm_' + out_suffix]
         inter['g_' + out_suffix] = default_kernels().combined_gaze(
-            flat('o', 3), inter['PoG_mm_' + out_suffix].detach().reshape(N, 2), flat('left_R', 3, 3),
+            flat('o', 3), inter['PoG_mm_' + out_suffix].detach().reshape(N, 2), flat('left_R' if eye_valid is None else 'combined_R', 3, 3),
             flat('camera_transformation', 4, 4)).view(B, T, 2)
         if cfg.refine_net_enabled:
             w, h = cfg.gaze_heatmap_size
@@ -292,7 +301,8 @@ class EVE(nn.Module):
         return output_dict
 
     def _final_block(self, d, inter, hf):
-        """eve.py:155-166: the refined PoG by soft-argmax of heatmap_final [B, T, 1, h, w], in px and cm, and the combined gaze."""
+        """eve.py:155-166: the refined PoG by soft-argmax of heatmap_final [B, T, 1, h, w], in px and cm, and the combined gaze
+        (rotated by d['combined_R'] where a masked EVEStream step has put one, by left_R as in the reference otherwise)."""
         cfg = self.config
         B, T = hf.shape[:2]
         h, w = hf.shape[-2:]
@@ -301,13 +311,14 @@ class EVE(nn.Module):
         inter['PoG_cm_final'] = px * (0.1 * d['millimeters_per_pixel'])
         inter['g_final'] = default_kernels().combined_gaze(
             d['o'].reshape(B * T, 3).float(), (10.0 * inter['PoG_cm_final']).detach().reshape(B * T, 2),
-            d['left_R'].reshape(B * T, 3, 3).float(), d['camera_transformation'].reshape(B * T, 4, 4).float()).view(B, T, 2)
+            d.get('combined_R', d['left_R']).reshape(B * T, 3, 3).float(), d['camera_transformation'].reshape(B * T, 4, 4).float()).view(B, T, 2)
 
     # ------------------------------------------------------------------------------------------ streaming (stream.py)
     PREDICTION_KEYS = ('left_g_initial', 'right_g_initial', 'left_pupil_size', 'right_pupil_size', 'g_initial', 'PoG_px_initial',
                        'PoG_cm_initial', 'g_final', 'PoG_px_final', 'PoG_cm_final')
 
-    def _predict_sequence(self, d, eye_states, refine_states, reset=None, return_heatmaps=False, lengths=None):
+    def _predict_sequence(self, d, eye_states, refine_states, reset=None, return_heatmaps=False, lengths=None, masked=False,
+                          eye_mask=None, pose_gate=None):
         """The prediction part of forward() for one chunk of an EVEStream: eval only, no labels, no losses.  d: the chunk's
         inputs [B, Tc, ...] (not modified; the eyes as patches, as camera_frame + {left,right}_eye_warp, or as camera_frame +
         eye_pose [B, Tc, 18], which also stands in for {left,right}_h / _o / _R and head_R and adds pose_valid to the result; both
@@ -317,23 +328,43 @@ class EVE(nn.Module):
         zero; lengths: None or int32 [2B] device frame counts in the same layout -- stream b consumes its first lengths[b] frames
         only (states handed over from frame lengths[b] - 1, outputs from lengths[b] on unspecified).  Same kernels and the same
         _pog_block / _final_block as forward().  -> the PREDICTION_KEYS present (the PoG keys need the camera geometry), plus
-        heatmap_final when asked."""
+        heatmap_final when asked.
+        masked (EVEStream.step(eye_mask=..., skip_invalid_pose=...)): eye_mask None or uint8 / bool [B, Tc, 2] on the device
+        (left, right; non-zero = usable); pose_gate None, or with the pose form a bool [1] device tensor -- pose_valid is ANDed
+        into the mask where it holds False (a device value, so one captured graph serves both settings).  One
+        eve_stream_mask_plan launch turns mask, pose_valid and lengths into the plan both networks compact their sequences by
+        (EyeNet._stream_sequence, RefineNet._stream_sequence); the binocular quantities come from the usable eyes by selects:
+        PoG_*_initial and o through _fuse2 (both usable: the mean's bits), and the combined gaze g_initial / g_final is rotated by
+        left_R where the left eye is usable, else by right_R -- an approximation the reference never needed (it always has
+        both eyes and rotates by left_R).  The result gains valid [B, Tc] and eye_valid [B, Tc, 2], bool."""
         assert not self.training, 'EVE._predict_sequence is eval-only'
         B = eye_input(d).shape[0]
         posed = 'eye_pose' in d
         d = dict(eye_pose_batch(d, self.config))
+        plan = eye_valid = None
+        if masked:
+            T = eye_input(d).shape[1]
+            pose_ok = None
+            if pose_gate is not None:
+                pose_ok = (d['pose_valid'] | pose_gate).contiguous()
+            plan = default_kernels().stream_mask_plan(B, T, eye_mask, pose_ok, lengths, device=eye_input(d).device)
+            eye_valid = plan['eye_valid'].view(torch.bool)
         if 'left_o' in d:
-            d['o'] = _mean2(d['left_o'], d['right_o'])
-        inter = dict(self.eye_net._stream_sequence(d, eye_states, reset, lengths))
-        self._pog_block(d, inter, 'initial', 'initial')
+            d['o'] = _mean2(d['left_o'], d['right_o']) if plan is None else _fuse2(d['left_o'], d['right_o'], eye_valid)
+        if plan is not None and 'left_R' in d:
+            d['combined_R'] = torch.where(eye_valid[:, :, 0, None, None], d['left_R'], d['right_R'])
+        inter = dict(self.eye_net._stream_sequence(d, eye_states, reset, lengths, plan))
+        self._pog_block(d, inter, 'initial', 'initial', eye_valid=eye_valid)
         if self.refine_net is not None and 'heatmap_initial' in inter:
             hf = self.refine_net._stream_sequence(inter['heatmap_initial'], d.get('screen_frame'), refine_states,
-                                                  None if reset is None else reset[:B], None if lengths is None else lengths[:B])
+                                                  None if reset is None else reset[:B], None if lengths is None else lengths[:B], plan)
             inter['heatmap_final'] = hf
             self._final_block(d, inter, hf)
         out = {k_: inter[k_] for k_ in self.PREDICTION_KEYS if k_ in inter}
         if posed:
             out['pose_valid'] = d['pose_valid']
+        if plan is not None:
+            out['valid'], out['eye_valid'] = plan['valid'].view(torch.bool), eye_valid
         if return_heatmaps and 'heatmap_final' in inter:
             out['heatmap_final'] = inter['heatmap_final']
         return out

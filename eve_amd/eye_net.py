@@ -584,7 +584,7 @@ class EyeNet(nn.Module):
         self._stream_w = (P, w)
         return w
 
-    def _stream_sequence(self, batch, states, reset=None, lengths=None):
+    def _stream_sequence(self, batch, states, reset=None, lengths=None, plan=None):
         """One chunk of B streams (eval, no labels): batch as for forward_sequence ([B, Tc, ...]); states: the carried buffers of
         _stream_state_buffers, read as the state before the chunk's first frame -- zeroed first where reset[s] != 0 (int32 [2B], a
         stream's flag repeated for its two eyes) -- and overwritten with the state after its last frame.  `_tail` runs with the
@@ -592,7 +592,11 @@ class EyeNet(nn.Module):
         eve_eye_tail_stream_fwd launch that reads and writes its state in place.  lengths: None, or int32 [2B] on the device laid
         out like reset -- sequence s then consumes only its first lengths[s] frames: its states are committed from frame
         lengths[s] - 1 (eve_stream_state_rows_at, eve_eye_tail_stream_fwd_len) or kept when that is 0, and its outputs from frame
-        lengths[s] on are unspecified.  Returns the forward_sequence prediction keys (<side>_g_initial, <side>_pupil_size)."""
+        lengths[s] on are unspecified.  plan: None, or kernels.stream_mask_plan's result for this chunk (a masked step; it holds
+        the lengths already) -- sequence s then consumes exactly its usable frames, in order: the trunk's features and the head
+        pose are gathered through the plan's perm (usable frames first), the tail runs as in a ragged step with the usable
+        counts as lengths, and gaze and pupil are gathered back through inv; entries at unusable eyes are unspecified.
+        Returns the forward_sequence prediction keys (<side>_g_initial, <side>_pupil_size)."""
         k = default_kernels()
         batch = eye_pose_batch(batch, self.config)
         P = self._get_packs()
@@ -600,6 +604,11 @@ class EyeNet(nn.Module):
         head_pose = None
         if self.config.eye_net_use_head_pose_input:
             head_pose = torch.cat([batch['left_h'].reshape(B * T, 2), batch['right_h'].reshape(B * T, 2)], dim=0).float()
+        if plan is not None:
+            perm, lengths = plan['perm'][:2 * B], plan['count'][:2 * B]
+            feats = k.stream_permute_rows(feats.view(2 * B, T, -1), perm).view(2 * B * T, -1)
+            if head_pose is not None:
+                head_pose = k.stream_permute_rows(head_pose.view(2 * B, T, 2), perm).view(2 * B * T, 2)
         if self._stream_tail_fused_ok():
             if lengths is None:
                 gaze, pupil, _ = k.eye_tail_stream_fwd(feats, head_pose, self._stream_tail_weights(P), states[0], reset)
@@ -619,6 +628,10 @@ class EyeNet(nn.Module):
                         k.stream_state_rows(src[:, -1], dst)
                     else:
                         k.stream_state_rows_at(src, dst, lengths)
+        if plan is not None:
+            back = plan['inv'][:2 * B]
+            gaze = k.stream_permute_rows(gaze.view(2 * B, T, 2), back).view(2 * B * T, 2)
+            pupil = k.stream_permute_rows(pupil.view(2 * B, T), back).view(2 * B * T)
         out = {}
         for si, side in enumerate(('left', 'right')):
             sl = slice(si * B * T, (si + 1) * B * T)

@@ -1286,6 +1286,39 @@ class HipKernels(object):
                                                    self._p(lengths), self._stream()))
         return dst
 
+    def stream_mask_plan(self, B, T, mask=None, pose_valid=None, lengths=None, device=None):
+        """The plan of a masked EVEStream step, one launch: mask, pose_valid uint8 or bool [B, T, 2] (left, right) or None,
+        lengths int32 [2B] (the ragged layout) or None, all on the device.  -> dict: count int32 [3B], perm, inv int32 [3B, T] --
+        the 2B eye sequences (left rows, then right rows), then the B frame sequences; perm lists a sequence's usable frames
+        ascending and then the others -- and eye_valid [B, T, 2], valid [B, T] uint8 (include/eve_hip.h eve_stream_mask_plan)."""
+        given = [t for t in (mask, pose_valid, lengths) if t is not None]
+        device = given[0].device if given else device
+        for t in (mask, pose_valid):
+            assert t is None or (t.dtype in (torch.uint8, torch.bool) and tuple(t.shape) == (B, T, 2) and t.is_cuda)
+        assert lengths is None or (lengths.dtype == torch.int32 and lengths.numel() >= 2 * B and lengths.is_cuda)
+        new = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)
+        plan = {'count': new((3 * B,), torch.int32), 'perm': new((3 * B, T), torch.int32), 'inv': new((3 * B, T), torch.int32),
+                'eye_valid': new((B, T, 2), torch.uint8), 'valid': new((B, T), torch.uint8)}
+        self._ck(self.lib.eve_stream_mask_plan(B, T, self._p(mask), self._p(pose_valid), self._p(lengths), self._p(plan['count']),
+                                               self._p(plan['perm']), self._p(plan['inv']), self._p(plan['eye_valid']),
+                                               self._p(plan['valid']), self._stream()))
+        return plan
+
+    def stream_permute_rows(self, src, index):
+        """-> dst [S, T, ...] dense with dst[s, j] = src[s, index[s, j]]: src [S, T, ...] whose frames are contiguous (the frame
+        and sequence strides are free: a view into wider rows, a scan's output), index int32 [S, T] on the device (a plan's perm
+        or inv; clamped to 0..T-1 by the kernel).  A frame holds a multiple of 4 bytes."""
+        S, T = src.shape[:2]
+        assert src.is_cuda and S > 0 and T > 0 and (src.dim() == 2 or src[0, 0].is_contiguous()), 'stream_permute_rows: rows must be contiguous'
+        assert index.dtype == torch.int32 and tuple(index.shape) == (S, T) and index.is_cuda
+        es = src.element_size()
+        row = src[0, 0].numel() * es
+        fs, ss = src.stride(1) * es if T > 1 else row, src.stride(0) * es if S > 1 else row
+        dst = torch.empty(src.shape, dtype=src.dtype, device=src.device)
+        self._ck(self.lib.eve_stream_permute_rows(S, T, row, fs, ss, ctypes.c_void_p(src.data_ptr()), self._p(dst), self._p(index),
+                                                  self._stream()))
+        return dst
+
     def cgru_gates1(self, g1, h):
         C = h.shape[-1]
         P = h.numel() // C

@@ -322,8 +322,11 @@ class RefineNet(nn.Module):
         hf, states, to_ref = self._sequence(heatmap_initial, screen_frame, self._initial_states_in(initial_states))
         return hf, [tuple(to_ref(t) for t in st) if isinstance(st, tuple) else to_ref(st) for st in states]
 
-    def _sequence(self, heatmap_initial, screen_frame, h0):
+    def _sequence(self, heatmap_initial, screen_frame, h0, plan=None):
         """The clip pass behind forward_sequence.  h0: None or per cell the internal-layout initial state (_initial_states_in).
+        plan: None, or kernels.stream_mask_plan's result (a masked EVEStream step): the bottleneck input is gathered through the
+        frame sequences' perm, so the cells see every stream's valid frames first and in order, and the last cell's features are
+        gathered back through inv before the decoder; the per-frame states returned are then in the compacted order.
         Returns (heatmap_final [B,T,1,H,W], per cell its per-frame states [B,T,5,8,C] (a pair for CLSTM), to_ref); to_ref
         converts [B,T,5,8,C] to [B,T,C,5,8]."""
         P = self._get_packs()
@@ -337,6 +340,8 @@ class RefineNet(nn.Module):
         x, skips, prefix = self._encode(x, P)
         h5, w5, C = x.shape[1:]
         xs = x.view(B, T, h5, w5, C)
+        if plan is not None:
+            xs = default_kernels().stream_permute_rows(xs, plan['perm'][2 * B:])
         cells, live = self._rnn_cells(), self._clstm_live()
         to_ref = lambda t: ops.FromNHWCFn.apply(t.reshape(B * T, h5, w5, C), C).view(B, T, C, h5, w5)
         if self._use_scan(cells, xs.shape[2:], xs.dtype):
@@ -355,6 +360,8 @@ class RefineNet(nn.Module):
             hs = torch.stack(outs, dim=1)
             stack = lambda ts: torch.stack(ts, dim=1)           # a cell's per-frame states as a scan returns them: [B,T,5,8,C]
             states = [tuple(map(stack, zip(*per_t))) if isinstance(per_t[0], tuple) else stack(per_t) for per_t in zip(*hist)]
+        if plan is not None:
+            hs = default_kernels().stream_permute_rows(hs, plan['inv'][2 * B:])
         x = hs.reshape(B * T, h5, w5, C)
         if cells:
             x = self._tap('rnn', x)
@@ -368,17 +375,22 @@ class RefineNet(nn.Module):
         z = lambda dt: torch.zeros((B, 5, 8, C), dtype=dt, device=device)
         return [tuple(z(d) for d in dt) if isinstance(dt, tuple) else z(dt) for dt in self._carried_dtypes()]
 
-    def _stream_sequence(self, heatmap_initial, screen_frame, buffers, reset=None, lengths=None):
+    def _stream_sequence(self, heatmap_initial, screen_frame, buffers, reset=None, lengths=None, plan=None):
         """One chunk of a stream: the carried states `buffers` (from _stream_state_buffers) are zeroed where reset[b] != 0, used
         as the initial states, and overwritten with the chunk's last frame -- one eve_stream_state_rows launch each way, no
         conversion.  lengths (None, or int32 [B] on the device): stream b's states are committed from its frame lengths[b] - 1
-        instead (eve_stream_state_rows_at), or kept when that is 0.  -> heatmap_final [B,T,1,H,W]."""
+        instead (eve_stream_state_rows_at), or kept when that is 0.  plan (None, or kernels.stream_mask_plan's result, which holds
+        the lengths already): stream b consumes exactly its valid frames -- _sequence compacts them to the front, and the states
+        are committed from the last valid one (the plan's frame counts as lengths), held when there is none; heatmap_final at
+        the other frames is unspecified.  -> heatmap_final [B,T,1,H,W]."""
         k = default_kernels()
         flat = lambda sts: [t for s in sts for t in (s if isinstance(s, tuple) else (s,))]
         if reset is not None:
             for t in flat(buffers):
                 k.stream_state_rows(t, t, reset)
-        hf, states, _ = self._sequence(heatmap_initial, screen_frame, buffers if buffers else None)
+        if plan is not None:
+            lengths = plan['count'][2 * heatmap_initial.shape[0]:]
+        hf, states, _ = self._sequence(heatmap_initial, screen_frame, buffers if buffers else None, plan)
         for dst, src in zip(flat(buffers), flat(states)):
             if lengths is None:
                 k.stream_state_rows(src[:, -1], dst)

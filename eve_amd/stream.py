@@ -4,6 +4,7 @@ carried from one call to the next.
     stream = eve_amd.EVEStream(model, num_streams=B)      # model: an eve_amd.EVE in eval mode
     out = stream.step(chunk)                               # chunk: dict of [B, Tc, ...] GPU tensors, any Tc >= 1
     out = stream.step(chunk, lengths=[3, 1, 0, 3])         # ragged: stream b delivered only lengths[b] frames (see step)
+    out = stream.step(chunk, eye_mask=usable)              # masked: usable [B, Tc, 2] marks the eyes to consume, frame by frame
     stream.reset([3])                                      # stream 3 starts from zero state at the next step()
     st = stream.get_state(); stream.set_state(st)          # reference layout, e.g. to resume a recording
 
@@ -20,6 +21,12 @@ A ragged step (lengths=...) hands each stream's states over at its own frame cou
 lengths[b] - 1 (eve_eye_tail_stream_fwd_len for the fused tail) and leaves a stream with no frames alone.  The counts are a
 device int32 [2B] filled from a pinned block like the reset flags, so the host never waits and one graph per chunk shape serves
 every length pattern.  The chunk keeps its shape: frames past a stream's count cost what real ones cost (no compaction).
+
+A masked step (eye_mask=..., skip_invalid_pose=True) skips frames in the middle of a chunk, per eye: one eve_stream_mask_plan
+launch turns the mask (ANDed with the lengths and, on request, the pose form's pose_valid) into a stable partition per
+sequence, eve_stream_permute_rows moves every sequence's usable frames to the front, the ragged machinery above runs with the
+usable counts as lengths, and the per-frame results are moved back.  The binocular quantities of a frame with one usable eye
+come from that eye alone (EVE._predict_sequence).  The mask is a graph input like the chunk: one masked graph per chunk shape.
 
 With use_graph (the default) each distinct chunk shape is captured once into a hipGraph on one stream and replayed; the
 chunk is copied into the graph's input buffers first.  Resets are device flags written by the host before the replay.  A
@@ -57,6 +64,8 @@ class EVEStream(object):
         self._flags = torch.zeros((2 * B,), dtype=torch.int32, device=self.device)   # stream b's reset flag at b and B + b
         self._flags_set = False
         self._lengths = torch.zeros((2 * B,), dtype=torch.int32, device=self.device)  # a ragged step's frame counts, laid out like _flags
+        self._pose_gate = torch.ones((1,), dtype=torch.bool, device=self.device)     # False: a masked step ANDs pose_valid into its mask
+        self._pose_gate_host = True
         self._pending = None                     # host bool [B]: resets requested for the next step
         self._graphs = {}
         self._graphs_key = None
@@ -152,13 +161,41 @@ class EVEStream(object):
             host = host.pin_memory()             # as _upload_resets: asynchronous, and never baked into a graph
         self._lengths.copy_(host, non_blocking=True)
 
-    def _run(self, chunk, return_heatmaps, ragged=False):
+    def _eye_mask(self, eye_mask, Tc):
+        """step()'s `eye_mask` checked -> (uint8 [B, Tc, 2] tensor, on the device or on the host (then pinned where the model is on
+        the GPU)).  A device tensor is taken as it is: its shape and dtype are host knowledge, its values are never read here."""
+        shape = (self.num_streams, Tc, 2)
+        if torch.is_tensor(eye_mask) and eye_mask.device.type != 'cpu':
+            if eye_mask.device != self.device or eye_mask.dtype not in (torch.bool, torch.uint8):
+                raise ValueError('step: a device eye_mask must be a bool or uint8 tensor on %s' % (self.device,))
+            if tuple(eye_mask.shape) != shape:
+                raise ValueError('step: eye_mask must be [num_streams, Tc, 2] = %s, got %s' % (shape, tuple(eye_mask.shape)))
+            eye_mask = eye_mask.contiguous()
+            return eye_mask.view(torch.uint8) if eye_mask.dtype == torch.bool else eye_mask
+        a = eye_mask.detach().numpy() if torch.is_tensor(eye_mask) else np.asarray(eye_mask)
+        if a.dtype.kind not in 'biu':
+            raise ValueError('step: eye_mask must be bool or integers, not %s' % a.dtype)
+        if a.shape != shape:
+            raise ValueError('step: eye_mask must be [num_streams, Tc, 2] = %s, got %s' % (shape, a.shape))
+        host = torch.from_numpy((a != 0).astype(np.uint8))
+        return host.pin_memory() if self.device.type == 'cuda' else host     # as _upload_resets: asynchronous, never baked into a graph
+
+    def _set_pose_gate(self, skip_invalid_pose):
+        if self._pose_gate_host != (not skip_invalid_pose):
+            self._pose_gate_host = not skip_invalid_pose
+            self._pose_gate.fill_(self._pose_gate_host)              # a device value: the captured graphs read it, the host never waits
+
+    def _run(self, chunk, return_heatmaps, ragged=False, eye_mask=None, masked=False):
+        if masked:
+            return self.model._predict_sequence(chunk, self._eye, self._ref, reset=self._flags, return_heatmaps=return_heatmaps,
+                                                lengths=self._lengths if ragged else None, masked=True, eye_mask=eye_mask,
+                                                pose_gate=self._pose_gate if 'eye_pose' in chunk else None)
         if not ragged:
             return self.model._predict_sequence(chunk, self._eye, self._ref, reset=self._flags, return_heatmaps=return_heatmaps)
         return self.model._predict_sequence(chunk, self._eye, self._ref, reset=self._flags, return_heatmaps=return_heatmaps,
                                             lengths=self._lengths)
 
-    def step(self, chunk, return_heatmaps=False, lengths=None):
+    def step(self, chunk, return_heatmaps=False, lengths=None, eye_mask=None, skip_invalid_pose=False):
         """One chunk of every stream: chunk holds [B, Tc, ...] tensors on the model's device -- the eyes (below), {left,right}_h,
         {left,right}_o, {left,right}_R, head_R, camera_transformation, inv_camera_transformation, pixels_per_millimeter, millimeters_per_pixel, and screen_frame when the config loads screen content.  Returns the
         prediction keys of EVE(output_predictions=True) as [B, Tc, ...] tensors (heatmap_final [B, Tc, 1, H, W] on request).
@@ -189,7 +226,8 @@ class EVEStream(object):
         the captured graph, the rows are a graph input like every other chunk tensor -- a replay reads the rows of the chunk at
         hand -- and the key of the graph covers them; ragged steps and camera_lens combine with it unchanged.  The result gains
         pose_valid, bool [B, Tc, 2] (left, right): False where a pose was not usable (a NaN, a head behind the camera, ...), whose
-        eye then got a black patch, R = I, o = 0 and h = 0.  pose_valid is reported, not folded into any other validity.
+        eye then got a black patch, R = I, o = 0 and h = 0.  pose_valid is reported, not folded into any other validity -- unless
+        skip_invalid_pose (below) asks for it.
 
         screen_frame is float [B, Tc, 3, H, W] at the configured screen size, uint8 [B, Tc, H, W, 3] at that size, or a live
         capture as it comes off the desktop: uint8 [B, Tc, IH, IW, 3 | 4] at any resolution from the screen size up to 16 843 009
@@ -202,26 +240,67 @@ class EVEStream(object):
         state after exactly that many frames -- untouched for 0 frames, except that a requested reset() is still applied.  The
         outputs keep their [B, Tc, ...] shapes, their entries at t >= lengths[b] are unspecified, and the result gains `valid`, a
         bool [B, Tc] device tensor that marks the consumed frames.  The frames past a stream's count are computed like real ones:
-        the step costs what a full chunk of this shape costs."""
+        the step costs what a full chunk of this shape costs.
+
+        eye_mask: None, or [B, Tc, 2] with columns (left, right), True / non-zero = the eye is usable in that frame: a bool or
+        uint8 tensor on the model's device (used as it is: a tracker on the GPU causes no host sync), or a CPU tensor, a numpy
+        array or nested lists of bools / integers (checked on the host -- a wrong shape or a float dtype raises ValueError -- and
+        uploaded like lengths and resets: a pinned block, an asynchronous copy, never baked into a graph).  skip_invalid_pose=True
+        (the pose form only: ValueError without eye_pose in the chunk) ANDs pose_valid into the mask on the device.  Eye (b, t,
+        side) is usable iff mask[b, t, side] and t < lengths[b] (and pose_valid[b, t, side] with skip_invalid_pose); frame (b, t)
+        is valid iff at least one of its eyes is usable.  The contract of a masked step:
+          * EyeNet: sequence (b, side) consumes exactly its usable frames, in order; its carried state afterwards is the state
+            after those frames -- untouched for none, except that a requested reset() is still applied.  Every tail variant
+            (GRU / RNN / LSTM, stacked, wide, STATIC, stream_fused_tail).
+          * RefineNet: stream b consumes exactly its valid frames; its cell states are held across the others and committed
+            from the last valid one (every cell type, stacked cells, every width, refine_net_clstm_feeds_features).
+          * On a valid frame PoG_px_initial / PoG_cm_initial are the two eyes' mean where both are usable (today's bits) and the
+            usable eye's own PoG where one is; o is the mean of the usable origins; the rotation behind g_initial and g_final is
+            left_R where the left eye is usable, else right_R -- an approximation the reference never needed.  Nothing a
+            masked-out eye supplied (patch, h, o, R, warp, pose) reaches a valid output: the choice is made by selects on the
+            device, so not even a NaN there does.
+          * The outputs keep their [B, Tc, ...] shapes; entries at invalid frames, and per-eye entries (<side>_g_initial,
+            <side>_pupil_size) at unusable eyes, are unspecified.  The result gains valid, bool [B, Tc], and eye_valid, bool [B,
+            Tc, 2]: the effective mask after lengths and pose_valid.
+          * Masked frames are computed like real ones (no compute is skipped): the step costs a full chunk plus one plan launch,
+            six small row gathers and ten elementwise selects (profiles/stream_mask_notes.md).  The mask is one more input
+            buffer of the graph: one masked graph per chunk shape serves every mask pattern.
+        A step with neither argument issues exactly the kernel calls it always did."""
         if self.model.training:
             raise ValueError('EVEStream runs inference only: the model was switched to training mode')
         B, Tc = eye_input(chunk).shape[:2]
         if B != self.num_streams:
             raise ValueError('chunk has %d streams, the EVEStream %d' % (B, self.num_streams))
         ragged = lengths is not None
+        masked = eye_mask is not None or bool(skip_invalid_pose)
+        if skip_invalid_pose and 'eye_pose' not in chunk:
+            raise ValueError('step: skip_invalid_pose needs the pose form (eye_pose in the chunk): there is no pose_valid to fold in')
         if ragged:
-            self._upload_lengths(self._host_lengths(lengths, Tc))
+            lengths = self._host_lengths(lengths, Tc)
+        if eye_mask is not None:
+            eye_mask = self._eye_mask(eye_mask, Tc)
+        if ragged:
+            self._upload_lengths(lengths)
+        if masked and 'eye_pose' in chunk:
+            self._set_pose_gate(bool(skip_invalid_pose))
         self._upload_resets()
         with torch.no_grad():
             if self.use_graph:
-                entry = self._graph_for(chunk, bool(return_heatmaps), ragged)
+                entry = self._graph_for(chunk, bool(return_heatmaps), ragged, masked)
                 for key, buf in entry['inputs'].items():
                     buf.copy_(chunk[key], non_blocking=True)
+                if masked:
+                    if eye_mask is None:
+                        entry['eye_mask'].fill_(1)
+                    else:
+                        entry['eye_mask'].copy_(eye_mask, non_blocking=True)
                 entry['graph'].replay()
                 out = dict(entry['outputs'])
             else:
-                out = self._run(chunk, return_heatmaps, ragged)
-            if ragged:
+                if eye_mask is not None and eye_mask.device != self.device:
+                    eye_mask = torch.empty(eye_mask.shape, dtype=torch.uint8, device=self.device).copy_(eye_mask, non_blocking=True)
+                out = self._run(chunk, return_heatmaps, ragged, eye_mask, masked)
+            if ragged and not masked:
                 out['valid'] = torch.arange(Tc, device=self.device)[None, :] < self._lengths[:self.num_streams, None]
         if self._flags_set:
             self._flags.zero_()
@@ -239,23 +318,26 @@ class EVEStream(object):
     def _weights_key(self):
         return tuple(_module_key(m) for m in (self.model.eye_net, self.model.refine_net) if m is not None)
 
-    def _graph_for(self, chunk, return_heatmaps, ragged=False):
+    def _graph_for(self, chunk, return_heatmaps, ragged=False, masked=False):
         wk = self._weights_key()
         if wk != self._graphs_key:               # new weights: new packs, new graphs (a replay never reads stale packs)
             self._graphs = {}
             self._graphs_key = wk
-        key = (return_heatmaps, ragged) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
+        key = (return_heatmaps, ragged, masked) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
         entry = self._graphs.get(key)
         if entry is None:
-            entry = self._graphs[key] = self._capture(chunk, return_heatmaps, ragged)
+            entry = self._graphs[key] = self._capture(chunk, return_heatmaps, ragged, masked)
             self._graphs_key = self._weights_key()
         return entry
 
-    def _capture(self, chunk, return_heatmaps, ragged=False):
+    def _capture(self, chunk, return_heatmaps, ragged=False, masked=False):
         """Capture one step for this chunk shape (train.Trainer._capture's recipe): inputs copied into fixed buffers, two eager
         warm-up steps off the default stream (packs, lazily built filters, allocator) with the carried states put back
-        afterwards, the kernels' scratch allocated before the capture, one stream, no side branches."""
+        afterwards, the kernels' scratch allocated before the capture, one stream, no side branches.  A masked graph has one more
+        input buffer, eye_mask uint8 [B, Tc, 2] (all ones while it is captured; step() fills it before every replay)."""
         static = {k_: v.clone() for k_, v in chunk.items() if torch.is_tensor(v)}
+        B, Tc = eye_input(chunk).shape[:2]
+        eye_mask = torch.ones((B, Tc, 2), dtype=torch.uint8, device=self.device) if masked else None
         dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         side = _WARMUP_STREAMS.get(dev_index)
         if side is None:
@@ -264,7 +346,7 @@ class EVEStream(object):
         with torch.cuda.stream(side):
             snap = [t.clone() for t in self._state_tensors()]
             for _ in range(2):
-                self._run(static, return_heatmaps, ragged)
+                self._run(static, return_heatmaps, ragged, eye_mask, masked)
             for t, s_ in zip(self._state_tensors(), snap):
                 t.copy_(s_)
         torch.cuda.current_stream().wait_stream(side)
@@ -274,7 +356,7 @@ class EVEStream(object):
             k.prepare_graph_workspace(self.device)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            out = self._run(static, return_heatmaps, ragged)
+            out = self._run(static, return_heatmaps, ragged, eye_mask, masked)
         m = self.model
         keep = (m.eye_net._packs, getattr(m.eye_net, '_stream_w', None), m.refine_net._packs if m.refine_net is not None else None)
-        return {'graph': graph, 'inputs': static, 'outputs': out, 'keep': keep}
+        return {'graph': graph, 'inputs': static, 'outputs': out, 'keep': keep, 'eye_mask': eye_mask}

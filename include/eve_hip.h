@@ -677,6 +677,34 @@ int eve_eye_tail_stream_fwd_len(int S, int T, const float* feats, const float* h
  * eve_stream_state_rows call before the step).                                                                              */
 int eve_stream_state_rows_at(int dtype, int S, int T, long long row_elems, long long frame_stride, long long src_stride,
                              long long dst_stride, const void* src, void* dst, const int* lengths, eve_stream_t stream);
+/* Masked steps (EVEStream.step(eye_mask=..., skip_invalid_pose=...); both entries additive: ABI v10): a sequence skips frames
+ * in the MIDDLE of a chunk.  No scan takes a mask; instead every sequence's usable frames are moved to the front of the chunk,
+ * the sequences run through the ragged entry points above with their usable counts as lengths, and the per-frame outputs are
+ * moved back.  The plan, one launch per step, for B streams of T frames:
+ *   eye (b, t, e) is usable iff t < clamp(lengths[e*B + b], 0, T) && mask[b][t][e] != 0 && pose_valid[b][t][e] != 0
+ * e = 0 left, 1 right; mask, pose_valid uint8 (or bool) [B][T][2] on the device, lengths int [2B] in the ragged layout; each of
+ * the three may be NULL and then does not restrict.  There are 3B sequences: the eye sequences s = e*B + b < 2B (EyeNet's row
+ * order), whose frame t is usable iff eye (b, t, e) is, and the frame sequences s = 2B + b (RefineNet's), whose frame t is
+ * usable iff either eye of (b, t) is.  Written for every s:
+ *   count[s]      the number of usable frames
+ *   perm[s][T]    a STABLE PARTITION of 0..T-1: the usable t ascending, then the unusable t ascending -- always a permutation,
+ *                 so a gather through it writes every destination row and reads only rows of its own sequence
+ *   inv[s][T]     its inverse: inv[s][perm[s][j]] = j
+ * and eye_valid [B][T][2], valid [B][T] uint8 (1 / 0): the effective eye mask and whether either eye of the frame is usable.
+ * One thread per sequence walks its T frames serially (no ballot or prefix scan: nothing depends on the wave size).  Refused
+ * without a launch: a NULL output, B outside 1..2^20, T < 1, 3*B*T >= 2^31.                                                  */
+int eve_stream_mask_plan(int B, int T, const uint8_t* mask, const uint8_t* pose_valid, const int* lengths, int* count, int* perm,
+                         int* inv, uint8_t* eye_valid, uint8_t* valid, eve_stream_t stream);
+/* Row gather that applies a plan: dst[s][j] = src[s][index[s][j]] for s < S, j < T -- through perm it compacts a sequence's
+ * usable frames to the front, through inv it puts per-frame results back.  Rows are row_bytes bytes (a multiple of 4), bit
+ * copies; src: frame and sequence strides in bytes (multiples of 4, each >= row_bytes: a view into wider rows works); dst is
+ * dense [S][T][row_bytes]; index int [S][T] on the device, clamped to 0..T-1 by the kernel, so no value reads outside src (a
+ * plan's perm / inv need no clamping; a stray value costs a wrong row, not a fault).  16-byte vector copies when both base
+ * pointers, both strides and row_bytes are multiples of 16, dword copies otherwise (pointers must be 4-byte aligned).
+ * Refused without a launch: NULL src / dst / index, T < 1, S < 1 or S*T >= 2^31, row_bytes <= 0 or not a multiple of 4, a
+ * stride below row_bytes or a stride or pointer that is no multiple of 4, src and dst overlapping (never in place).         */
+int eve_stream_permute_rows(int S, int T, long long row_bytes, long long frame_stride_bytes, long long seq_stride_bytes,
+                            const void* src, void* dst, const int* index, eve_stream_t stream);
 /* Live screen captures: exact area (box) down-sampling of uint8 frames src [N][IH][IW][C] (C = 3, or 4 with the fourth channel
  * ignored: the alpha of BGRA capture APIs; the channel order is kept, a BGR -> RGB swap stays with the caller) to RefineNet's
  * screen input dst [N][3][OH][OW] float in [0, 1], OH <= IH and OW <= IW.  The reference never sees a full-resolution screen:

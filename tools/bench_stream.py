@@ -2,14 +2,18 @@
 """Device time per EVEStream.step under hipGraph replay (eve_amd/stream.py), the shipped refine_net.json pipeline (GRU EyeNet,
 CLSTM RefineNet), synthetic weights and clips.  One JSON line per shape:
 
-    python tools/bench_stream.py --shapes 1x1 32x1 32x30 [--dtype bf16] [--steps 50] [--fused-tail] [--ragged] [--repeat N]
+    python tools/bench_stream.py --shapes 1x1 32x1 32x30 [--dtype bf16] [--steps 50] [--fused-tail] [--ragged | --masked] [--repeat N]
                                  [--screen 1920x1080]
 
 B x Tc = streams x frames per step.  For Tc > 1 the same clips also go through one EVE.eval() pass (`eval_ms`): what the
 stream costs over the plain clip pass.  --fused-tail runs the EyeNet tail as one eve_eye_tail_stream_fwd launch
 (EyeNet.stream_fused_tail) instead of layer by layer: the A/B of the fused kernel, e.g. under `rocprofv3 --kernel-trace --stats`.
 --ragged steps with seeded random lengths in 0..Tc, a new pattern every step (step(chunk, lengths=...): one graph serves them
-all).  --screen WxH feeds uint8 screen captures of that size, [B, Tc, H, W, 3], instead of the pre-resized float screens: the step
+all).  --masked steps with a seeded random eye mask with about 20 % holes, a new pattern every step, handed over as a host array
+(step(chunk, eye_mask=...): the plan launch, the row gathers and the pinned upload of the mask are in the step); the line then
+also holds `launch_floor_us`, the device time per launch of a captured chain of 64 smallest launches (eve_stream_state_rows on 16
+floats) in the same process: what one more launch in the graph costs at the least.
+--screen WxH feeds uint8 screen captures of that size, [B, Tc, H, W, 3], instead of the pre-resized float screens: the step
 then holds the area resize (eve_screen_u8_area_to_nchw) and the copy of the captures into the graph's input buffer.  --repeat N measures every shape N times in one process (`step_ms_runs`; `step_ms` is their median): the run-to-run spread."""
 import argparse
 import json
@@ -39,6 +43,25 @@ def device_ms(fn, steps):
     return start.elapsed_time(end) / steps
 
 
+def launch_floor_us(n=64, reps=50):
+    """Device time per launch of a replayed hipGraph of n dependent eve_stream_state_rows launches on a [2, 8] tensor."""
+    k = eve_amd.kernels.default_kernels()
+    a, b = torch.zeros((2, 8), device='cuda'), torch.zeros((2, 8), device='cuda')
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        k.stream_state_rows(a, b)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for _ in range(n):
+            k.stream_state_rows(a, b)
+    graph.replay()
+    torch.cuda.synchronize()
+    return round(1e3 * device_ms(graph.replay, reps) / n, 3)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--shapes', nargs='+', default=['1x1', '32x1', '32x30'])
@@ -46,9 +69,12 @@ def main():
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--fused-tail', action='store_true')
     ap.add_argument('--ragged', action='store_true')
+    ap.add_argument('--masked', action='store_true', help='step with a random eye mask, about 20 %% of the eyes masked out')
     ap.add_argument('--repeat', type=int, default=1)
     ap.add_argument('--screen', default=None, metavar='WxH', help='feed uint8 screen captures of this size, e.g. 1920x1080')
     args = ap.parse_args()
+    if args.ragged and args.masked:
+        ap.error('--ragged and --masked are two measurements: give one')
     cfg = eve_amd.reset_standalone_config()
     cfg.import_json(os.path.join(REPO, 'configs', 'refine_net.json'))
     cfg.import_dict({'eye_net_load_pretrained': False})
@@ -74,14 +100,18 @@ def main():
         stream = eve_amd.EVEStream(model, B)
         rng = np.random.default_rng(B * 1000 + Tc)
         step = (lambda: stream.step(clip, lengths=rng.integers(0, Tc + 1, size=B))) if args.ragged else (lambda: stream.step(clip))
+        if args.masked:
+            step = lambda: stream.step(clip, eye_mask=rng.random((B, Tc, 2)) >= 0.2)
         for _ in range(3):
             step()                                           # capture + warm replays
         torch.cuda.synchronize()
         runs = sorted(round(device_ms(step, args.steps), 4) for _ in range(max(1, args.repeat)))
-        res = {'B': B, 'Tc': Tc, 'dtype': args.dtype, 'tail': 'fused' if args.fused_tail else 'layers', 'ragged': args.ragged,
+        res = {'B': B, 'Tc': Tc, 'dtype': args.dtype, 'tail': 'fused' if args.fused_tail else 'layers', 'ragged': args.ragged, 'masked': args.masked,
                'screen': args.screen or 'float', 'step_ms': runs[len(runs) // 2]}
         if len(runs) > 1:
             res['step_ms_runs'] = runs
+        if args.masked:
+            res['launch_floor_us'] = launch_floor_us()
         res['us_per_frame'] = round(1e3 * res['step_ms'] / (B * Tc), 3)
         if Tc > 1:
             with torch.no_grad():
