@@ -27,6 +27,13 @@
 // neighbours together) and their stores are consecutive -- 4 bytes per lane and plane for the float form, one 8-byte pixel per
 // lane for the stem's packed form, whose rows include the pad ring, written as zeros by the same loop.  The nine matrix entries
 // are uniform over the workgroup.  The taps are single-byte loads, so `frames` needs no alignment.
+//
+// The format variant (eve_eye_warp_fmt_to_nchw / _to_stem, tests/pixel_format_ref.py) takes the frames as cameras and decoders
+// deliver them -- BGR(A), NV12, I420, YUYV -- and converts ONLY the four taps of an output pixel, in the same launch: tap_rgb<FMT>
+// stands where the three byte loads of the RGB tap stand, everything before it (coordinates, lens) and behind it (weights, blend,
+// warp_value, layouts) is the same code.  A YUV tap is three single-byte loads (luma, and the nearest chroma sample of its 2 x 2
+// block or pair) and the integer matrix of include/eve_hip.h; a tap outside the frame adds nothing, as before.  The plain
+// kernels are the FMT = PIX_RGB instantiation of the same templates and compile to the instructions they had without them.
 #include "common.h"
 
 namespace eve {
@@ -43,6 +50,55 @@ struct EyeWarpArgs {
     int bands;                           // bands per patch
     int IH, IW, C, OH, OW;
 };
+
+// what a frame holds (EVE_PIX_* of include/eve_hip.h; PIX_RGB is the four existing entry points' layout, C = 3 or 4)
+constexpr int PIX_RGB = -1;
+
+// the integer YUV -> RGB matrix of one launch, by value in the kernel's arguments (unused by the BGR formats)
+struct YuvCoef {
+    int y0, cy, cvr, cug, cvg, cub;
+};
+
+struct EyeWarpFmtArgs {
+    EyeWarpArgs a;                       // a.C: 3, or 4 for BGRA; the YUV formats do not read it
+    YuvCoef coef;
+};
+
+// bytes of one frame
+template <int FMT>
+__device__ __forceinline__ size_t frame_bytes(const int IH, const int IW, const int C) {
+    if constexpr (FMT == EVE_PIX_NV12 || FMT == EVE_PIX_I420) return (size_t)IH * IW / 2 * 3;
+    else if constexpr (FMT == EVE_PIX_YUYV) return (size_t)IH * IW * 2;
+    else return (size_t)IH * IW * C;
+}
+
+// the 8-bit (r, g, b) of pixel (y, x), 0 <= y < IH, 0 <= x < IW, of one frame: single-byte loads, chroma the nearest sample
+template <int FMT>
+__device__ __forceinline__ void tap_rgb(const uint8_t* __restrict__ frame, const int IH, const int IW, const int y, const int x,
+                                        const YuvCoef& k, uint32_t (&rgb)[3]) {
+    if constexpr (FMT == EVE_PIX_BGR || FMT == EVE_PIX_BGRA) {
+        const uint8_t* p = frame + ((size_t)y * IW + x) * (FMT == EVE_PIX_BGRA ? 4 : 3);
+        rgb[0] = p[2]; rgb[1] = p[1]; rgb[2] = p[0];
+    } else {
+        int Y, U, V;
+        if constexpr (FMT == EVE_PIX_NV12) {
+            const uint8_t* c = frame + (size_t)IH * IW + (size_t)(y >> 1) * IW + (x & ~1);
+            Y = frame[(size_t)y * IW + x]; U = c[0]; V = c[1];
+        } else if constexpr (FMT == EVE_PIX_I420) {
+            const size_t plane = (size_t)(IH >> 1) * (IW >> 1);
+            const uint8_t* c = frame + (size_t)IH * IW + (size_t)(y >> 1) * (IW >> 1) + (x >> 1);
+            Y = frame[(size_t)y * IW + x]; U = c[0]; V = c[plane];
+        } else {                         // YUYV: Y0 U Y1 V per pixel pair
+            const uint8_t* row = frame + (size_t)y * IW * 2;
+            Y = row[2 * x]; U = row[2 * (x & ~1) + 1]; V = row[2 * (x | 1) + 1];
+        }
+        const int yy = (Y - k.y0 > 0 ? Y - k.y0 : 0) * k.cy + (1 << 19), u = U - 128, v = V - 128;    // |sums| < 2^30
+        const int r = (yy + k.cvr * v) >> 20, g = (yy - k.cvg * v - k.cug * u) >> 20, b = (yy + k.cub * u) >> 20;
+        rgb[0] = (uint32_t)(r < 0 ? 0 : r > 255 ? 255 : r);
+        rgb[1] = (uint32_t)(g < 0 ? 0 : g > 255 ? 255 : g);
+        rgb[2] = (uint32_t)(b < 0 ? 0 : b > 255 ? 255 : b);
+    }
+}
 
 // one patch's camera model, widened to float64; `on` is false for a row whose eight coefficients are all +-0 (a NaN is not zero)
 struct Lens {
@@ -63,10 +119,10 @@ __device__ __forceinline__ Lens load_lens(const float* __restrict__ row) {
 }
 
 // the three channels' fixed-point sums S (<= 255 * 65536) of output pixel (oy, ox); all zero outside.  LENS: (u, v) goes through
-// the distortion model of L first, unless L.on is false.
-template <bool LENS>
+// the distortion model of L first, unless L.on is false.  FMT: the taps come through tap_rgb<FMT> (coef: its matrix).
+template <bool LENS, int FMT = PIX_RGB>
 __device__ __forceinline__ void warp_sums(const double (&m)[9], const Lens& L, const uint8_t* __restrict__ frame, const int IH, const int IW,
-                                          const int C, const int oy, const int ox, uint32_t (&S)[3]) {
+                                          const int C, const int oy, const int ox, uint32_t (&S)[3], const YuvCoef& coef = YuvCoef()) {
 #pragma clang fp contract(off)
     const double dx = (double)ox, dy = (double)oy;
     const double X = (m[0] * dx + m[1] * dy) + m[2];
@@ -99,9 +155,16 @@ __device__ __forceinline__ void warp_sums(const double (&m)[9], const Lens& L, c
     for (int t = 0; t < 4; ++t) {
         const int y = y0 + (t >> 1), x = x0 + (t & 1);
         if (y >= 0 && y < IH && x >= 0 && x < IW) {
-            const uint8_t* p = frame + ((size_t)y * IW + x) * C;
+            if constexpr (FMT == PIX_RGB) {
+                const uint8_t* p = frame + ((size_t)y * IW + x) * C;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) S[c] += w[t] * (uint32_t)p[c];
+                for (int c = 0; c < 3; ++c) S[c] += w[t] * (uint32_t)p[c];
+            } else {
+                uint32_t rgb[3];
+                tap_rgb<FMT>(frame, IH, IW, y, x, coef, rgb);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) S[c] += w[t] * rgb[c];
+            }
         }
     }
 }
@@ -117,8 +180,9 @@ __device__ __forceinline__ float warp_value(uint32_t S) {
 // LENS: lens is float [N][12], read once per item like the matrix.  The body of both kernels.  Keep the pointers plain here (the
 // kernels' own parameters carry __restrict__) and the arguments by value: qualified pointers or a reference make the compiler
 // schedule the plain kernels differently from a kernel that holds this loop itself.
-template <typename O, bool LENS>
-__device__ __forceinline__ void eye_warp_items(const EyeWarpArgs a, const uint8_t* src, const float* warps, const float* lens, void* dst) {
+template <typename O, bool LENS, int FMT = PIX_RGB>
+__device__ __forceinline__ void eye_warp_items(const EyeWarpArgs a, const uint8_t* src, const float* warps, const float* lens, void* dst,
+                                               const YuvCoef coef = YuvCoef()) {
     constexpr bool PACKED = !std::is_same<O, float>::value;
     const int rows = PACKED ? a.OH + 6 : a.OH, cols = PACKED ? a.OW + 8 : a.OW;      // of the output image, pad ring included
     for (long long item = blockIdx.x; item < a.items; item += gridDim.x) {
@@ -130,13 +194,13 @@ __device__ __forceinline__ void eye_warp_items(const EyeWarpArgs a, const uint8_
         for (int i = 0; i < 9; ++i) m[i] = (double)warps[n * 9 + i];
         Lens L = {};
         if constexpr (LENS) L = load_lens(lens + n * 12);
-        const uint8_t* frame = src + (size_t)n * a.IH * a.IW * a.C;
+        const uint8_t* frame = src + (FMT == PIX_RGB ? (size_t)n * a.IH * a.IW * a.C : (size_t)n * frame_bytes<FMT>(a.IH, a.IW, a.C));
         for (int t = threadIdx.x; t < nr * cols; t += EW_THREADS) {
             const int r = r0 + t / cols, col = t % cols;
             const int oy = PACKED ? r - 3 : r, ox = PACKED ? col - 4 : col;
             const bool pixel = !PACKED || (oy >= 0 && oy < a.OH && ox >= 0 && ox < a.OW);
             uint32_t S[3] = {0u, 0u, 0u};
-            if (pixel) warp_sums<LENS>(m, L, frame, a.IH, a.IW, a.C, oy, ox, S);
+            if (pixel) warp_sums<LENS, FMT>(m, L, frame, a.IH, a.IW, a.C, oy, ox, S, coef);
             if constexpr (PACKED) {
                 uint2 q = make_uint2(0u, 0u);
                 if (pixel) {
@@ -166,6 +230,14 @@ __global__ __launch_bounds__(EW_THREADS) void eye_warp_lens_u8_kernel(const EyeW
     eye_warp_items<O, true>(a, src, warps, lens, dst);
 }
 
+// FMT: one of EVE_PIX_*; lens is read only with LENS
+template <int FMT, bool LENS, typename O>
+__global__ __launch_bounds__(EW_THREADS) void eye_warp_fmt_kernel(const EyeWarpFmtArgs fa, const uint8_t* __restrict__ src,
+                                                                  const float* __restrict__ warps, const float* __restrict__ lens,
+                                                                  void* __restrict__ dst) {
+    eye_warp_items<O, LENS, FMT>(fa.a, src, warps, lens, dst, fa.coef);
+}
+
 // the checks the entry points share; -> nullptr or what is wrong
 const char* eye_warp_refusal(long long N, int IH, int IW, int C, const void* frames, const void* warps, int OH, int OW, const void* dst) {
     if (N <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0 || !frames || !warps || !dst) return "bad arguments";
@@ -182,6 +254,61 @@ EyeWarpArgs eye_warp_args(long long N, int IH, int IW, int C, int OH, int OW, in
     a.items = N * a.bands;
     a.IH = IH; a.IW = IW; a.C = C; a.OH = OH; a.OW = OW;
     return a;
+}
+
+// (y0, CY, CVR, CUG, CVG, CUB), each constant floor(c * 2^20 + 0.5) of its coefficient (include/eve_hip.h), indexed by EVE_YUV_*
+constexpr YuvCoef YUV_MATRICES[3] = {
+    {16, 1220542, 1673527, 409993, 852492, 2116026},      // bt601: 1.164, 1.596, 0.391, 0.813, 2.018 (OpenCV's COLOR_YUV2RGB_NV12)
+    {16, 1220542, 1880097, 223347, 558891, 2214593},      // bt709: 1.164, 1.793, 0.213, 0.533, 2.112
+    {0, 1048576, 1470104, 360853, 748826, 1858077},       // jfif:  1, 1.402, 0.344136, 0.714136, 1.772
+};
+
+// the format entry points' checks on top of eye_warp_refusal; -> nullptr or what is wrong
+const char* eye_warp_fmt_refusal(int format, int matrix, long long N, int IH, int IW, const void* frames, const void* warps, int OH, int OW,
+                                 const void* dst) {
+    if (format < EVE_PIX_BGR || format > EVE_PIX_YUYV) return "unknown format (EVE_PIX_BGR, _BGRA, _NV12, _I420 or _YUYV)";
+    const bool yuv = format != EVE_PIX_BGR && format != EVE_PIX_BGRA;
+    if (yuv && (matrix < EVE_YUV_BT601 || matrix > EVE_YUV_JFIF)) return "unknown matrix (EVE_YUV_BT601, _BT709 or _JFIF)";
+    if (const char* why = eye_warp_refusal(N, IH, IW, format == EVE_PIX_BGRA ? 4 : 3, frames, warps, OH, OW, dst)) return why;
+    if ((format == EVE_PIX_NV12 || format == EVE_PIX_I420) && ((IH | IW) & 1)) return "IH and IW must be even (2 x 2 chroma blocks)";
+    if (format == EVE_PIX_YUYV && (IW & 1)) return "IW must be even (chroma pairs)";
+    return nullptr;
+}
+
+EyeWarpFmtArgs eye_warp_fmt_args(int format, int matrix, long long N, int IH, int IW, int OH, int OW, int rows) {
+    EyeWarpFmtArgs fa;
+    fa.a = eye_warp_args(N, IH, IW, format == EVE_PIX_BGRA ? 4 : 3, OH, OW, rows);
+    fa.coef = YUV_MATRICES[format == EVE_PIX_BGR || format == EVE_PIX_BGRA ? 0 : matrix];
+    return fa;
+}
+
+// one launch of eye_warp_fmt_kernel<FMT, lens != NULL, O> under its name, "eye_warp_fmt_kernel<nv12,lens,eve::bf16_t>"
+#define EW_FMT_NAME(fmt, lens, O) "eye_warp_fmt_kernel<" fmt "," lens "," O ">"
+#define EW_FMT_CASE(FMT, fmt)                                                                                                      \
+    case FMT:                                                                                                                      \
+        if (lens) {                                                                                                                \
+            if (dtype == EVE_DT_F32) EVE_LAUNCH(EW_FMT_NAME(fmt, "lens", "float"), (eye_warp_fmt_kernel<FMT, true, float>), EW_FMT_ARGS);   \
+            else if (dtype == EVE_DT_BF16) EVE_LAUNCH(EW_FMT_NAME(fmt, "lens", "eve::bf16_t"), (eye_warp_fmt_kernel<FMT, true, bf16_t>), EW_FMT_ARGS); \
+            else EVE_LAUNCH(EW_FMT_NAME(fmt, "lens", "eve::f16_t"), (eye_warp_fmt_kernel<FMT, true, f16_t>), EW_FMT_ARGS);         \
+        } else {                                                                                                                   \
+            if (dtype == EVE_DT_F32) EVE_LAUNCH(EW_FMT_NAME(fmt, "plain", "float"), (eye_warp_fmt_kernel<FMT, false, float>), EW_FMT_ARGS); \
+            else if (dtype == EVE_DT_BF16) EVE_LAUNCH(EW_FMT_NAME(fmt, "plain", "eve::bf16_t"), (eye_warp_fmt_kernel<FMT, false, bf16_t>), EW_FMT_ARGS); \
+            else EVE_LAUNCH(EW_FMT_NAME(fmt, "plain", "eve::f16_t"), (eye_warp_fmt_kernel<FMT, false, f16_t>), EW_FMT_ARGS);       \
+        }                                                                                                                          \
+        break;
+#define EW_FMT_ARGS grid, dim3(EW_THREADS), 0, stream, fa, frames, warps, lens, dst
+
+// dtype: EVE_DT_F32 for the float form (rows = OH), EVE_DT_BF16 / EVE_DT_F16 for the packed one (rows = OH + 6)
+void eye_warp_fmt_launch(int dtype, int format, const EyeWarpFmtArgs& fa, const uint8_t* frames, const float* warps, const float* lens,
+                         void* dst, hipStream_t stream) {
+    const dim3 grid((unsigned)(fa.a.items < EW_MAX_BLOCKS ? fa.a.items : EW_MAX_BLOCKS));
+    switch (format) {
+        EW_FMT_CASE(EVE_PIX_BGR, "bgr")
+        EW_FMT_CASE(EVE_PIX_BGRA, "bgra")
+        EW_FMT_CASE(EVE_PIX_NV12, "nv12")
+        EW_FMT_CASE(EVE_PIX_I420, "i420")
+        EW_FMT_CASE(EVE_PIX_YUYV, "yuyv")
+    }
 }
 
 }  // namespace
@@ -252,6 +379,34 @@ extern "C" int eve_eye_warp_lens_u8_to_stem(int dtype, long long N, int IH, int 
     const dim3 grid((unsigned)(a.items < EW_MAX_BLOCKS ? a.items : EW_MAX_BLOCKS));
     EVE_DISPATCH_H16(dtype, EVE_LAUNCH(EVE_HNAME(H, "eye_warp_lens_u8_kernel<", ">"), eye_warp_lens_u8_kernel<H>, grid, dim3(EW_THREADS), 0,
                                        (hipStream_t)stream, a, frames_nhwc, warps, lens, x_padded));
+    EVE_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int eve_eye_warp_fmt_to_nchw(int format, int matrix, long long N, int IH, int IW, const uint8_t* frames, const float* warps,
+                                        const float* lens, int OH, int OW, float* dst_nchw, eve_stream_t stream) {
+    char msg[160];
+    if (const char* why = eye_warp_fmt_refusal(format, matrix, N, IH, IW, frames, warps, OH, OW, dst_nchw)) {
+        snprintf(msg, sizeof(msg), "eye_warp_fmt_to_nchw: %s", why);
+        return set_error_msg(msg);
+    }
+    eye_warp_fmt_launch(EVE_DT_F32, format, eye_warp_fmt_args(format, matrix, N, IH, IW, OH, OW, OH), frames, warps, lens, dst_nchw,
+                        (hipStream_t)stream);
+    EVE_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int eve_eye_warp_fmt_to_stem(int dtype, int format, int matrix, long long N, int IH, int IW, const uint8_t* frames,
+                                        const float* warps, const float* lens, int OH, int OW, void* x_padded, eve_stream_t stream) {
+    char msg[160];
+    const char* why = eye_warp_fmt_refusal(format, matrix, N, IH, IW, frames, warps, OH, OW, x_padded);
+    if (!why && dtype != EVE_DT_BF16 && dtype != EVE_DT_F16) why = "dtype must be bf16 or f16 (the stem's packed input)";
+    if (why) {
+        snprintf(msg, sizeof(msg), "eye_warp_fmt_to_stem: %s", why);
+        return set_error_msg(msg);
+    }
+    eye_warp_fmt_launch(dtype, format, eye_warp_fmt_args(format, matrix, N, IH, IW, OH, OW, OH + 6), frames, warps, lens, x_padded,
+                        (hipStream_t)stream);
     EVE_CHECK_LAUNCH();
     return 0;
 }

@@ -33,7 +33,8 @@ __device__ __forceinline__ uint32_t overlap(long long i, long long o, long long 
     return (uint32_t)(hi - lo);
 }
 
-template <bool VEC>
+// BGR: output plane c reads source channel 2 - c (eve_screen_u8_area_bgr_to_nchw); nothing else differs
+template <bool VEC, bool BGR = false>
 __global__ __launch_bounds__(SR_THREADS) void screen_u8_area_kernel(const long long items, const int IH, const int IW, const int C,
                                                                     const uint8_t* __restrict__ src, const int OH, const int OW,
                                                                     float* __restrict__ dst) {
@@ -93,7 +94,7 @@ __global__ __launch_bounds__(SR_THREADS) void screen_u8_area_kernel(const long l
             const int ix0 = (int)((long long)ox * IW / OW);
             const int ix1 = (int)((((long long)ox + 1) * IW + OW - 1) / OW);  // <= IW
             uint32_t s = 0u;
-            for (int ix = ix0; ix < ix1; ++ix) s += overlap(ix, ox, IW, OW) * colsum[(size_t)ix * C + c];
+            for (int ix = ix0; ix < ix1; ++ix) s += overlap(ix, ox, IW, OW) * colsum[(size_t)ix * C + (BGR ? 2 - c : c)];
             dst[((n * 3 + c) * OH + oy) * OW + ox] = (float)((double)s / area) * scale;
         }
         __syncthreads();                 // the next item overwrites colsum
@@ -105,22 +106,34 @@ __global__ __launch_bounds__(SR_THREADS) void screen_u8_area_kernel(const long l
 
 using namespace eve;
 
-extern "C" int eve_screen_u8_area_to_nchw(long long N, int IH, int IW, int C, const uint8_t* src_nhwc, int OH, int OW, float* dst_nchw,
-                                          eve_stream_t stream) {
-    if (N <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0 || !src_nhwc || !dst_nchw)
-        return set_error_msg("screen_u8_area_to_nchw: bad arguments");
-    if (C != 3 && C != 4) return set_error_msg("screen_u8_area_to_nchw: C must be 3 or 4 (a fourth channel is ignored)");
-    if (OH > IH || OW > IW) return set_error_msg("screen_u8_area_to_nchw: upscaling is not supported (OH <= IH and OW <= IW)");
-    if ((long long)IH * IW > SR_MAX_PIXELS)
-        return set_error_msg("screen_u8_area_to_nchw: frame too large (IH * IW <= 16843009 keeps the 32-bit sums exact)");
+// both entry points; `who` names the caller in a refusal
+static int screen_u8_area(const char* who, bool bgr, long long N, int IH, int IW, int C, const uint8_t* src_nhwc, int OH, int OW,
+                          float* dst_nchw, eve_stream_t stream) {
+    char msg[192];
+    const char* why = nullptr;
     const long long pitch = (long long)IW * C;
     const size_t lds = (size_t)pitch * sizeof(uint32_t);
-    if (lds > (size_t)LDS_CU) return set_error_msg("screen_u8_area_to_nchw: row too wide (IW * C <= 40960 bytes: one row of sums in LDS)");
-    if (N > (long long)0x7fffffff / OH) return set_error_msg("screen_u8_area_to_nchw: N * OH must fit 31 bits");
+    if (N <= 0 || IH <= 0 || IW <= 0 || OH <= 0 || OW <= 0 || !src_nhwc || !dst_nchw) why = "bad arguments";
+    else if (C != 3 && C != 4) why = "C must be 3 or 4 (a fourth channel is ignored)";
+    else if (OH > IH || OW > IW) why = "upscaling is not supported (OH <= IH and OW <= IW)";
+    else if ((long long)IH * IW > SR_MAX_PIXELS) why = "frame too large (IH * IW <= 16843009 keeps the 32-bit sums exact)";
+    else if (lds > (size_t)LDS_CU) why = "row too wide (IW * C <= 40960 bytes: one row of sums in LDS)";
+    else if (N > (long long)0x7fffffff / OH) why = "N * OH must fit 31 bits";
+    if (why) {
+        snprintf(msg, sizeof(msg), "%s: %s", who, why);
+        return set_error_msg(msg);
+    }
     const long long items = N * OH;
     const dim3 grid((unsigned)(items < SR_MAX_BLOCKS ? items : SR_MAX_BLOCKS));
     const bool vec = pitch % 16 == 0 && (reinterpret_cast<uintptr_t>(src_nhwc) & 15) == 0;
-    if (vec)
+    if (bgr) {
+        if (vec)
+            EVE_LAUNCH("screen_u8_area_bgr_kernel<true>", (screen_u8_area_kernel<true, true>), grid, dim3(SR_THREADS), lds, (hipStream_t)stream,
+                       items, IH, IW, C, src_nhwc, OH, OW, dst_nchw);
+        else
+            EVE_LAUNCH("screen_u8_area_bgr_kernel<false>", (screen_u8_area_kernel<false, true>), grid, dim3(SR_THREADS), lds, (hipStream_t)stream,
+                       items, IH, IW, C, src_nhwc, OH, OW, dst_nchw);
+    } else if (vec)
         EVE_LAUNCH("screen_u8_area_kernel<true>", screen_u8_area_kernel<true>, grid, dim3(SR_THREADS), lds, (hipStream_t)stream, items, IH, IW,
                    C, src_nhwc, OH, OW, dst_nchw);
     else
@@ -128,4 +141,14 @@ extern "C" int eve_screen_u8_area_to_nchw(long long N, int IH, int IW, int C, co
                    IW, C, src_nhwc, OH, OW, dst_nchw);
     EVE_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int eve_screen_u8_area_to_nchw(long long N, int IH, int IW, int C, const uint8_t* src_nhwc, int OH, int OW, float* dst_nchw,
+                                          eve_stream_t stream) {
+    return screen_u8_area("screen_u8_area_to_nchw", false, N, IH, IW, C, src_nhwc, OH, OW, dst_nchw, stream);
+}
+
+extern "C" int eve_screen_u8_area_bgr_to_nchw(long long N, int IH, int IW, int C, const uint8_t* src_nhwc, int OH, int OW, float* dst_nchw,
+                                              eve_stream_t stream) {
+    return screen_u8_area("screen_u8_area_bgr_to_nchw", true, N, IH, IW, C, src_nhwc, OH, OW, dst_nchw, stream);
 }

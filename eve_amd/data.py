@@ -11,9 +11,16 @@ uint8 frames is 4x less PCIe traffic, and the float values produced here are bit
   preprocess_screen_frames(u8, size=(H, W))
                                  [..., IH, IW, 3|4] uint8 of any size >= (H, W), e.g. a 1920 x 1080 capture -> [..., 3, H, W]
                                  float32 in [0, 1] by exact area averaging (RefineNet passes its screen_size for uint8 screens)
+  preprocess_screen_frames(u8, size=(H, W), bgr=True)
+                                 the same from a BGR(A) capture: the planes come out in RGB order, no swapped copy is made
   warp_eye_patches(u8, warps)    whole camera frames [..., IH, IW, 3|4] uint8 and per-frame homographies [..., 3, 3] float32
                                  (patch pixel -> camera pixel) -> one eye's patches [..., 3, H, W] float32 in [-1, 1], cut
                                  bilinearly on the device (EyeNet / EVE / EVEStream take `camera_frame` + `<side>_eye_warp`)
+  warp_eye_patches(u8, warps, format='nv12', matrix='bt601')
+                                 the same from frames as cameras and decoders deliver them: format 'bgr' [..., IH, IW, 3|4], 'nv12' /
+                                 'i420' [..., IH*3/2, IW], 'yuyv' [..., IH, IW, 2]; only the taps read are converted, by a bit-exact
+                                 integer matrix ('bt601', 'bt709' limited range, 'jfif' full range) -- the keys `camera_frame_bgr`,
+                                 `camera_frame_nv12`, `camera_frame_i420`, `camera_frame_yuyv` in place of `camera_frame`
   camera_lens(K, dist)           a camera matrix [..., 3, 3] and 4, 5 or 8 OpenCV distortion coefficients -> the float32 [..., 12]
                                  rows that warp_eye_patches(..., lens=) and the `camera_lens` key take for RAW (distorted) frames
   eye_pose(K, rvec, tvec, eyes, focal_norm, distance_norm)
@@ -46,16 +53,21 @@ def preprocess_frames(frames):
     return out.view(lead + tuple(out.shape[1:]))
 
 
-def preprocess_screen_frames(frames, size=None):
+def preprocess_screen_frames(frames, size=None, bgr=False):
     """size: None, or the (H, W) the network takes.  Frames of that size already (and size=None) are normalised as the
     reference normalises its 128 x 72 video; larger ones -- a live capture of the desktop, [..., IH, IW, 3 | 4] -- are
     area-averaged down to it by eve_screen_u8_area_to_nchw: the exact mean over each output pixel's footprint, fractional
     overlaps included, kept in float32.  A fourth channel (BGRA's alpha) is dropped there (so four-channel frames take that
     kernel at the target size too, where its values are the plain normalisation's bit for bit); the channel ORDER is kept as it
-    comes, so a BGR capture is swapped to RGB by the caller.  The reference's own file was scaled by ffmpeg (bicubic, then
-    lossy video coding): this is what a live stream can do instead, not a reproduction of it."""
+    comes unless bgr says otherwise.  The reference's own file was scaled by ffmpeg (bicubic, then
+    lossy video coding): this is what a live stream can do instead, not a reproduction of it.
+    bgr=True: the frames are BGR(A), as capture APIs and OpenCV deliver them; the planes come out in RGB order, bit for bit what
+    the channel-reversed capture gives (eve_screen_u8_area_bgr_to_nchw, at every size: size=None takes the frames' own)."""
     flat, lead = _fold(frames)
-    if size is None or (tuple(size) == tuple(flat.shape[1:3]) and flat.shape[3] == 3):
+    if bgr:
+        hw = tuple(flat.shape[1:3]) if size is None else (int(size[0]), int(size[1]))
+        out = default_kernels().screen_u8_area_bgr_to_nchw(flat, hw)
+    elif size is None or (tuple(size) == tuple(flat.shape[1:3]) and flat.shape[3] == 3):
         out = default_kernels().frames_u8_to_nchw(flat, SCREEN_SCALE, None)
     else:
         out = default_kernels().screen_u8_area_to_nchw(flat, (int(size[0]), int(size[1])))
@@ -172,7 +184,7 @@ def normalize_eyes(pose, size=None):
     return out
 
 
-def warp_eye_patches(frames, warps, size=None, lens=None):
+def warp_eye_patches(frames, warps, size=None, lens=None, format='rgb', matrix='bt601'):
     """One eye's patches cut from whole camera frames on the device, in place of two cv2.warpPerspective calls per frame on the
     host: frames uint8 [..., IH, IW, 3 | 4] (a fourth channel ignored, the channel order kept), warps float32 [..., 3, 3] with the
     same leading dimensions -> float32 [..., 3, H, W] in [-1, 1], the values preprocess_frames gives for the cut patch.  size:
@@ -186,21 +198,40 @@ def warp_eye_patches(frames, warps, size=None, lens=None):
     lens: None for frames that are already undistorted (what the EVE dataset's videos are), or float32 [..., 12] rows from
     camera_lens with the same leading dimensions for RAW frames: W and inv(W) then refer to the undistorted image as before, and
     every coordinate goes through the camera's distortion model before the frame is read (eve_eye_warp_lens_u8_to_nchw).  No
-    undistorted frame is made.  A row with zero coefficients gives the lens=None bits."""
-    flat, lead = _fold(frames)
+    undistorted frame is made.  A row with zero coefficients gives the lens=None bits.
+
+    format: 'rgb' (above), or the layout a camera or decoder delivers: 'bgr' [..., IH, IW, 3 | 4], 'nv12' / 'i420' [..., IH*3/2, IW]
+    (IH and IW even) or 'yuyv' [..., IH, IW, 2] (IW even), byte-linear per frame.  The four taps of an output pixel are converted
+    as they are read -- chroma the nearest sample, the integer matrix `matrix` ('bt601' or 'bt709', limited range, or 'jfif', full
+    range) of include/eve_hip.h eve_eye_warp_fmt_to_nchw -- so the result equals the 'rgb' call on the converted frame bit for
+    bit, and no RGB frame is made."""
+    if format == 'rgb':
+        flat, lead = _fold(frames)
+        if flat.shape[3] not in (3, 4):
+            raise TypeError('expected camera frames with 3 or 4 channels, got %d' % flat.shape[3])
+    else:
+        from .kernels import pixel_format_shape
+        dims = 2 if format in ('nv12', 'i420') else 3          # the planar layouts are [rows, IW]
+        if not torch.is_tensor(frames) or frames.dim() < dims + 1:
+            raise TypeError('expected uint8 %s frames with at least one leading dimension, got %s' % (format, tuple(getattr(frames, 'shape', ()))))
+        lead = tuple(frames.shape[:-dims])
+        flat = frames.reshape((-1,) + tuple(frames.shape[-dims:])).contiguous()
+        pixel_format_shape(flat, format, lead=1)
     if not torch.is_tensor(warps) or warps.dtype != torch.float32 or tuple(warps.shape) != lead + (3, 3):
         raise TypeError('expected float32 warps shaped %s, got %s %s' % (lead + (3, 3), getattr(warps, 'dtype', type(warps)),
                                                                          tuple(getattr(warps, 'shape', ()))))
-    if flat.shape[3] not in (3, 4):
-        raise TypeError('expected camera frames with 3 or 4 channels, got %d' % flat.shape[3])
     if lens is not None and (not torch.is_tensor(lens) or lens.dtype != torch.float32 or tuple(lens.shape) != lead + (12,)):
         raise TypeError('expected float32 lens rows shaped %s, got %s %s' % (lead + (12,), getattr(lens, 'dtype', type(lens)),
                                                                              tuple(getattr(lens, 'shape', ()))))
     hw = eye_patch_hw() if size is None else (int(size[0]), int(size[1]))
-    if lens is None:
-        out = default_kernels().eye_warp_u8_to_nchw(flat, warps.reshape(-1, 3, 3).contiguous(), hw)
+    warps = warps.reshape(-1, 3, 3).contiguous()
+    lens = None if lens is None else lens.reshape(-1, 12).contiguous()
+    if format != 'rgb':
+        out = default_kernels().eye_warp_fmt_to_nchw(flat, warps, hw, format, matrix=matrix, lens=lens)
+    elif lens is None:
+        out = default_kernels().eye_warp_u8_to_nchw(flat, warps, hw)
     else:
-        out = default_kernels().eye_warp_lens_u8_to_nchw(flat, warps.reshape(-1, 3, 3).contiguous(), lens.reshape(-1, 12).contiguous(), hw)
+        out = default_kernels().eye_warp_lens_u8_to_nchw(flat, warps, lens, hw)
     return out.view(lead + tuple(out.shape[1:]))
 
 

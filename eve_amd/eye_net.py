@@ -26,7 +26,8 @@ from torch import nn
 
 from . import ops
 from .config import get_config
-from .kernels import ACT_NONE, ACT_RELU, ACT_SELU, ACT_TANH, HALF_DTYPES, default_kernels, dispatch_flag, pad_channels
+from .kernels import (ACT_NONE, ACT_RELU, ACT_SELU, ACT_TANH, HALF_DTYPES, YUV_MATRICES, default_kernels, dispatch_flag, pad_channels,
+                      pixel_format_shape)
 from .ops import PackedWeight
 
 half_pi = 0.5 * math.pi
@@ -38,14 +39,30 @@ def _wants_grad(t):
 
 EYE_PATCH_KEYS = ('left_eye_patch', 'right_eye_patch')
 EYE_CAMERA_KEYS = ('camera_frame', 'left_eye_warp', 'right_eye_warp')
+# the frame key of a camera form and its pixel format: a batch holds exactly one (camera_frame is RGB(A), the others are what
+# cameras and decoders deliver -- kernels.pixel_format_shape has the layouts)
+EYE_FRAME_KEYS = {'camera_frame': 'rgb', 'camera_frame_bgr': 'bgr', 'camera_frame_nv12': 'nv12', 'camera_frame_i420': 'i420',
+                  'camera_frame_yuyv': 'yuyv'}
 EYE_LENS_KEY = 'camera_lens'                 # optional with the camera form: raw frames of a camera with lens distortion
 EYE_POSE_KEY = 'eye_pose'                    # the pose form: camera_frame + one packed row per frame (data.eye_pose)
 # what eye_pose_batch derives from the rows -- a batch holds the rows or these, never both
 EYE_POSE_DERIVED = ('head_R', 'left_o', 'right_o', 'left_R', 'right_R', 'left_eye_warp', 'right_eye_warp', 'left_h', 'right_h', 'pose_valid')
 
 
+def camera_frame_key(batch):
+    """The one frame key of EYE_FRAME_KEYS the batch holds, or None; two of them raise ValueError."""
+    found = [k_ for k_ in EYE_FRAME_KEYS if k_ in batch]
+    if len(found) > 1:
+        raise ValueError('a batch holds one camera frame key, found %s' % ', '.join(found))
+    return found[0] if found else None
+
+
 def _camera_frame(batch):
-    frames = batch['camera_frame']
+    key = camera_frame_key(batch)
+    frames = batch[key]
+    if key != 'camera_frame':
+        pixel_format_shape(frames, EYE_FRAME_KEYS[key], lead=2, name=key)
+        return frames
     if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[4] not in (3, 4):
         raise TypeError('camera_frame must be uint8 [B, T, IH, IW, 3 | 4], got %s %s' % (
             getattr(frames, 'dtype', type(frames)), tuple(getattr(frames, 'shape', ()))))
@@ -66,13 +83,15 @@ def eye_input(batch):
     pose form: the homographies, <side>_R, <side>_o, <side>_h and head_R are derived on the device -- eye_pose_batch).  Raises
     on a batch that holds two forms, half of one, eye_pose next to a key it derives, or tensors of the wrong dtype or shape for
     the camera forms.  Both camera forms may carry camera_lens, float32 [B, T, 12] (data.camera_lens): one camera per frame,
-    for both eyes."""
+    for both eyes.  In both, camera_frame may be replaced by ONE of camera_frame_bgr [B, T, IH, IW, 3 | 4], camera_frame_nv12 /
+    camera_frame_i420 [B, T, IH*3/2, IW] or camera_frame_yuyv [B, T, IH, IW, 2] (EYE_FRAME_KEYS; two frame keys raise ValueError,
+    odd sizes too): that tensor is then returned -- its shape[:2] and device are the batch's whatever the format."""
     if EYE_POSE_KEY in batch:
         clash = [k_ for k_ in EYE_PATCH_KEYS + EYE_POSE_DERIVED if k_ in batch]
         if clash:
             raise ValueError('%s derives %s and stands in for %s: found %s beside it' % (
                 EYE_POSE_KEY, ', '.join(EYE_POSE_DERIVED), ' / '.join(EYE_PATCH_KEYS), ', '.join(clash)))
-        if 'camera_frame' not in batch:
+        if camera_frame_key(batch) is None:
             raise ValueError('%s goes with camera_frame: the patches are cut from it' % EYE_POSE_KEY)
         frames = _camera_frame(batch)
         pose = batch[EYE_POSE_KEY]
@@ -82,10 +101,12 @@ def eye_input(batch):
         _camera_lens(batch, frames)
         return frames
     has_patch = [k_ for k_ in EYE_PATCH_KEYS if k_ in batch]
-    has_cam = [k_ for k_ in EYE_CAMERA_KEYS if k_ in batch]
+    frame_key = camera_frame_key(batch)
+    has_cam = [k_ for k_ in EYE_CAMERA_KEYS if k_ in batch or (k_ == 'camera_frame' and frame_key is not None)]
     if has_patch and has_cam:
         raise ValueError('give the eyes either as %s or as %s, not both (found %s)' % (
-            ' / '.join(EYE_PATCH_KEYS), ' / '.join(EYE_CAMERA_KEYS), ', '.join(has_patch + has_cam)))
+            ' / '.join(EYE_PATCH_KEYS), ' / '.join(EYE_CAMERA_KEYS), ', '.join(has_patch + [frame_key if k_ == 'camera_frame' else k_
+                                                                                             for k_ in has_cam])))
     if not has_cam:
         if EYE_LENS_KEY in batch:
             raise ValueError('%s goes with %s: pre-cut patches were cut from an undistorted frame already' % (
@@ -93,7 +114,7 @@ def eye_input(batch):
         return batch['left_eye_patch']
     if len(has_cam) != len(EYE_CAMERA_KEYS):
         raise ValueError('the camera form needs %s: missing %s' % (
-            ', '.join(EYE_CAMERA_KEYS), ', '.join(k_ for k_ in EYE_CAMERA_KEYS if k_ not in batch)))
+            ', '.join(EYE_CAMERA_KEYS), ', '.join(k_ for k_ in EYE_CAMERA_KEYS if k_ not in has_cam)))
     frames = _camera_frame(batch)
     for k_ in EYE_CAMERA_KEYS[1:]:
         w = batch[k_]
@@ -427,6 +448,10 @@ class EyeNet(nn.Module):
             output_dict[side + '_g_initial'] = output_dict[side + '_g_initial'].detach()
 
     # ------------------------------------------------------------------ whole clips, both eyes, one pass
+    # The YUV -> RGB matrix of camera_frame_nv12 / _i420 / _yuyv batches: 'bt601' (limited range: webcams, OpenCV's cvtColor),
+    # 'bt709' (limited range: HD decoders) or 'jfif' (full range: MJPEG).  Anything else raises ValueError at use.
+    yuv_matrix = 'bt601'
+
     def forward_sequence(self, batch, initial_states=None):
         """batch: {left,right}_eye_patch [B, T, 3, H, W] float (or uint8 [B, T, H, W, C] decoded frames), {left,right}_h [B, T, 2].
         In place of the two patch keys the batch may hold whole camera frames, camera_frame uint8 [B, T, IH, IW, 3 | 4], and
@@ -436,6 +461,10 @@ class EyeNet(nn.Module):
         warps refer to the undistorted image the networks were trained on: the cut undistorts as it samples.
         Or the pose form: camera_frame and eye_pose, float32 [B, T, 18] (data.eye_pose), in place of the patches, the warps AND
         {left,right}_h -- eye_pose_batch derives them on the device.
+        In every camera form the frames may come as the camera or decoder delivers them, under ONE of camera_frame_bgr,
+        camera_frame_nv12, camera_frame_i420, camera_frame_yuyv in place of camera_frame (eye_input has the shapes): the cut then
+        converts the taps it reads by the integer matrix self.yuv_matrix names, and equals the cut from the converted RGB frame bit
+        for bit (eve_eye_warp_fmt_to_nchw).  The per-frame forward() takes patches only.
         Returns the B x T x ... tensors eve.py:174-182 would stack: <side>_g_initial [B,T,2],
         <side>_pupil_size [B,T], <side>_eye_rnn_states_<i> [B,T,H] per cell ((h, c) pair of them for LSTM).
         initial_states: {side: h [B,H]} or {side: [per-cell h | (h, c) | None]}."""
@@ -449,16 +478,24 @@ class EyeNet(nn.Module):
         k = default_kernels()
         dt = self.compute_dtype
         x = x_padded = None
-        if eye_input(batch) is batch.get('camera_frame'):
+        frame_key = camera_frame_key(batch)
+        if eye_input(batch) is batch.get(frame_key):
             # whole camera frames and one homography per eye and frame: cut, normalise and lay out in one launch per eye --
             # straight into the stem's packed layout where the uint8 patches below go there, else to float NCHW patches
             from . import data
-            frames = batch['camera_frame']
-            B, T, IH, IW, Cc = frames.shape
+            frames = batch[frame_key]
+            B, T = frames.shape[:2]
             (Hh, Ww), C = data.eye_patch_hw(self.config), 3
-            flat = frames.reshape(B * T, IH, IW, Cc).contiguous()
+            flat = frames.reshape((B * T,) + tuple(frames.shape[2:])).contiguous()
             lw, rw = (batch[s_ + '_eye_warp'].reshape(B * T, 3, 3).contiguous() for s_ in ('left', 'right'))
-            if EYE_LENS_KEY in batch:               # raw frames: the lens kernels, one camera per frame for both eyes
+            if frame_key != 'camera_frame':         # BGR / NV12 / I420 / YUYV: the taps are converted inside the same launch
+                fmt, matrix = EYE_FRAME_KEYS[frame_key], self.yuv_matrix
+                if matrix not in YUV_MATRICES:
+                    raise ValueError('EyeNet.yuv_matrix must be one of %s, got %r' % (', '.join(YUV_MATRICES), matrix))
+                lens = batch[EYE_LENS_KEY].reshape(B * T, 12).contiguous() if EYE_LENS_KEY in batch else None
+                to_stem = lambda w, out: k.eye_warp_fmt_to_stem(flat, w, (Hh, Ww), fmt, matrix=matrix, lens=lens, out=out)
+                to_nchw = lambda w: k.eye_warp_fmt_to_nchw(flat, w, (Hh, Ww), fmt, matrix=matrix, lens=lens)
+            elif EYE_LENS_KEY in batch:             # raw frames: the lens kernels, one camera per frame for both eyes
                 lens = batch[EYE_LENS_KEY].reshape(B * T, 12).contiguous()
                 to_stem = lambda w, out: k.eye_warp_lens_u8_to_stem(flat, w, lens, (Hh, Ww), out=out)
                 to_nchw = lambda w: k.eye_warp_lens_u8_to_nchw(flat, w, lens, (Hh, Ww))

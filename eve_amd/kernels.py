@@ -30,6 +30,35 @@ def dt_code(dtype):
     raise TypeError('eve_amd kernels support float32, bfloat16 and float16, got %s' % dtype)
 
 
+# include/eve_hip.h EVE_PIX_* / EVE_YUV_*: the frame layouts and YUV matrices of eve_eye_warp_fmt_to_nchw / _to_stem
+PIXEL_FORMATS = {'bgr': 0, 'bgra': 1, 'nv12': 2, 'i420': 3, 'yuyv': 4}
+YUV_MATRICES = {'bt601': 0, 'bt709': 1, 'jfif': 2}
+
+
+def pixel_format_shape(frames, format, lead=1, name='frames'):
+    """The frame tensor of one pixel format checked -> (IH, IW, C): uint8 with `lead` leading dimensions, then [IH, IW, 3 | 4] for
+    'bgr' (and 'rgb'), [IH*3/2, IW] for 'nv12' / 'i420' (IH and IW even), [IH, IW, 2] for 'yuyv' (IW even); C is the last
+    dimension, 1 for the planar forms.  TypeError for a wrong dtype or shape, ValueError for odd sizes or an unknown format."""
+    if format not in ('rgb', 'bgr', 'nv12', 'i420', 'yuyv'):
+        raise ValueError('%s: the format must be rgb, bgr, nv12, i420 or yuyv, got %r' % (name, format))
+    dims = {'rgb': 3, 'bgr': 3, 'yuyv': 3, 'nv12': 2, 'i420': 2}[format]
+    last = {'rgb': (3, 4), 'bgr': (3, 4), 'yuyv': (2,)}.get(format)
+    layout = {'rgb': '[IH, IW, 3 | 4]', 'bgr': '[IH, IW, 3 | 4]', 'yuyv': '[IH, IW, 2]', 'nv12': '[IH*3/2, IW]', 'i420': '[IH*3/2, IW]'}[format]
+    if (not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() != lead + dims or
+            (last is not None and frames.shape[-1] not in last)):
+        raise TypeError('%s must be uint8 with %d leading dimension%s and %s (%s), got %s %s' % (
+            name, lead, '' if lead == 1 else 's', layout, format, getattr(frames, 'dtype', type(frames)), tuple(getattr(frames, 'shape', ()))))
+    if dims == 3:
+        IH, IW, C = (int(v) for v in frames.shape[lead:])
+        if format == 'yuyv' and IW % 2:
+            raise ValueError('%s: yuyv frames need an even width (chroma pairs), got %d' % (name, IW))
+        return IH, IW, C
+    rows, IW = (int(v) for v in frames.shape[lead:])
+    if rows % 3 or IW % 2:                     # (IH = two thirds of the rows is then even)
+        raise ValueError('%s: %s frames are [IH*3/2, IW] with IH and IW even, got %d rows of %d' % (name, format, rows, IW))
+    return rows // 3 * 2, IW, 1
+
+
 def vec_of(dtype):
     return 4 if dtype == torch.float32 else 8
 
@@ -415,6 +444,16 @@ class HipKernels(object):
         self._ck(self.lib.eve_screen_u8_area_to_nchw(N, IH, IW, C, self._p(frames), OH, OW, self._p(out), self._stream()))
         return out
 
+    def screen_u8_area_bgr_to_nchw(self, frames, out_hw):
+        """screen_u8_area_to_nchw for a BGR(A) capture: plane c of the result comes from source channel 2 - c, so it equals
+        screen_u8_area_to_nchw on the channel-reversed capture bit for bit (include/eve_hip.h eve_screen_u8_area_bgr_to_nchw)."""
+        N, IH, IW, C = frames.shape
+        assert frames.dtype == torch.uint8
+        OH, OW = int(out_hw[0]), int(out_hw[1])
+        out = torch.empty((N, 3, OH, OW), dtype=torch.float32, device=frames.device)
+        self._ck(self.lib.eve_screen_u8_area_bgr_to_nchw(N, IH, IW, C, self._p(frames), OH, OW, self._p(out), self._stream()))
+        return out
+
     def frames_u8_to_stem(self, frames, scale, shift, out=None, dtype=torch.bfloat16):
         """uint8 [N,H,W,C<=4] -> the stem's packed 16-bit input [N,H+6,W+8,4]."""
         N, H, W, C = frames.shape
@@ -491,6 +530,47 @@ class HipKernels(object):
             raise TypeError('eye_warp: out must be bf16 / f16 [%d, %d, %d, 4], got %s %s' % (N, OH + 6, OW + 8, dst.dtype, tuple(dst.shape)))
         self._ck(self.lib.eve_eye_warp_lens_u8_to_stem(dt_code(dst.dtype), N, IH, IW, C, self._p(frames), self._p(warps), self._p(lens), OH, OW,
                                                        self._p(dst), self._stream()))
+        return dst
+
+    @staticmethod
+    def _eye_warp_fmt_args(frames, warps, out_hw, format, matrix, lens):
+        """The checks of the two eye_warp_fmt_* calls -> (format code, matrix code, N, IH, IW, OH, OW): the frame's shape per
+        pixel_format_shape (TypeError for a wrong dtype or shape, ValueError for odd sizes or an unknown format or matrix)."""
+        IH, IW, C = pixel_format_shape(frames, format, lead=1)
+        N = frames.shape[0]
+        if matrix not in YUV_MATRICES:
+            raise ValueError('eye_warp: matrix must be one of %s, got %r' % (', '.join(YUV_MATRICES), matrix))
+        if warps.dtype != torch.float32 or tuple(warps.shape) != (N, 3, 3):
+            raise TypeError('eye_warp: warps must be float32 [%d, 3, 3], got %s %s' % (N, warps.dtype, tuple(warps.shape)))
+        if lens is not None and (not torch.is_tensor(lens) or lens.dtype != torch.float32 or tuple(lens.shape) != (N, 12)):
+            raise TypeError('eye_warp: lens must be float32 [%d, 12], got %s %s' % (N, getattr(lens, 'dtype', type(lens)),
+                                                                                  tuple(getattr(lens, 'shape', ()))))
+        if not (frames.is_contiguous() and warps.is_contiguous() and (lens is None or lens.is_contiguous())):
+            raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        if warps.device != frames.device or (lens is not None and lens.device != frames.device):
+            raise RuntimeError('eye_warp: frames, warps and lens are on different devices')
+        code = PIXEL_FORMATS['bgra' if format == 'bgr' and C == 4 else format]
+        return code, YUV_MATRICES[matrix], N, IH, IW, int(out_hw[0]), int(out_hw[1])
+
+    def eye_warp_fmt_to_nchw(self, frames, warps, out_hw, format, matrix='bt601', lens=None):
+        """eye_warp_u8_to_nchw (lens=None) / eye_warp_lens_u8_to_nchw on frames as cameras and decoders deliver them, uint8 and
+        contiguous: format 'bgr' [N,IH,IW,3|4], 'nv12' / 'i420' [N,IH*3/2,IW], 'yuyv' [N,IH,IW,2]; matrix 'bt601' | 'bt709' | 'jfif'
+        for the YUV formats.  Only the taps read are converted, by the integer matrix of include/eve_hip.h
+        eve_eye_warp_fmt_to_nchw: the result is the RGB call's on the converted frame, bit for bit."""
+        fmt, mat, N, IH, IW, OH, OW = self._eye_warp_fmt_args(frames, warps, out_hw, format, matrix, lens)
+        out = torch.empty((N, 3, OH, OW), dtype=torch.float32, device=frames.device)
+        self._ck(self.lib.eve_eye_warp_fmt_to_nchw(fmt, mat, N, IH, IW, self._p(frames), self._p(warps),
+                                                   None if lens is None else self._p(lens), OH, OW, self._p(out), self._stream()))
+        return out
+
+    def eye_warp_fmt_to_stem(self, frames, warps, out_hw, format, matrix='bt601', lens=None, out=None, dtype=torch.bfloat16):
+        """The same patches straight into the stem's packed 16-bit input [N,OH+6,OW+8,4], as eye_warp_u8_to_stem lays it out."""
+        fmt, mat, N, IH, IW, OH, OW = self._eye_warp_fmt_args(frames, warps, out_hw, format, matrix, lens)
+        dst = out if out is not None else torch.empty((N, OH + 6, OW + 8, 4), dtype=dtype, device=frames.device)
+        if tuple(dst.shape) != (N, OH + 6, OW + 8, 4) or dst.dtype not in HALF_DTYPES:
+            raise TypeError('eye_warp: out must be bf16 / f16 [%d, %d, %d, 4], got %s %s' % (N, OH + 6, OW + 8, dst.dtype, tuple(dst.shape)))
+        self._ck(self.lib.eve_eye_warp_fmt_to_stem(dt_code(dst.dtype), fmt, mat, N, IH, IW, self._p(frames), self._p(warps),
+                                                   None if lens is None else self._p(lens), OH, OW, self._p(dst), self._stream()))
         return dst
 
     def eye_pose_normalize(self, pose, out_hw):

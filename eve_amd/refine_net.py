@@ -312,15 +312,32 @@ class RefineNet(nn.Module):
                 out.append(one(st, sdt))
         return out
 
-    def forward_sequence(self, heatmap_initial, screen_frame=None, initial_states=None):
+    def forward_sequence(self, heatmap_initial, screen_frame=None, initial_states=None, screen_frame_bgr=None):
         """heatmap_initial [B,T,1,h,w], screen_frame [B,T,3,H,W] -> (heatmap_final [B,T,1,H,W],
         list over cells of the stacked states [B,T,C,5,8] (tuple of two for CLSTM)).
         screen_frame may also be uint8 [B,T,IH,IW,3|4]: decoded frames at the screen size, or a full-resolution capture that is
         area-averaged down to config.screen_size on the device (data.preprocess_screen_frames; channel order kept, alpha ignored).
+        screen_frame_bgr: in place of screen_frame, a uint8 [B,T,IH,IW,3|4] BGR(A) capture as capture APIs and OpenCV deliver it;
+        the result is that of the channel-reversed capture as screen_frame, bit for bit.  Both together raise ValueError.
         initial_states: None (zero states), or per cell the state before the first frame -- reference layout [B, C, 5, 8] as
         returned here (the last frame of a previous call), or the internal NHWC layout [B, 5, 8, C]; (h, c) for CLSTM."""
+        screen_frame = self._screen_input(screen_frame, screen_frame_bgr)
         hf, states, to_ref = self._sequence(heatmap_initial, screen_frame, self._initial_states_in(initial_states))
         return hf, [tuple(to_ref(t) for t in st) if isinstance(st, tuple) else to_ref(st) for st in states]
+
+    def _screen_input(self, screen_frame, screen_frame_bgr):
+        """screen_frame as it is, or the float [B,T,3,H,W] screen input made from a BGR(A) capture (one area-resize launch)."""
+        if screen_frame_bgr is None:
+            return screen_frame
+        if screen_frame is not None:
+            raise ValueError('give the screen as screen_frame or as screen_frame_bgr, not both')
+        if not torch.is_tensor(screen_frame_bgr) or screen_frame_bgr.dtype != torch.uint8 or screen_frame_bgr.dim() != 5 or \
+                screen_frame_bgr.shape[4] not in (3, 4):
+            raise TypeError('screen_frame_bgr must be uint8 [B, T, IH, IW, 3 | 4], got %s %s' % (
+                getattr(screen_frame_bgr, 'dtype', type(screen_frame_bgr)), tuple(getattr(screen_frame_bgr, 'shape', ()))))
+        from . import data
+        cfg = self.config
+        return data.preprocess_screen_frames(screen_frame_bgr, size=(cfg.screen_size[1], cfg.screen_size[0]), bgr=True)
 
     def _sequence(self, heatmap_initial, screen_frame, h0, plan=None):
         """The clip pass behind forward_sequence.  h0: None or per cell the internal-layout initial state (_initial_states_in).
@@ -375,7 +392,7 @@ class RefineNet(nn.Module):
         z = lambda dt: torch.zeros((B, 5, 8, C), dtype=dt, device=device)
         return [tuple(z(d) for d in dt) if isinstance(dt, tuple) else z(dt) for dt in self._carried_dtypes()]
 
-    def _stream_sequence(self, heatmap_initial, screen_frame, buffers, reset=None, lengths=None, plan=None):
+    def _stream_sequence(self, heatmap_initial, screen_frame, buffers, reset=None, lengths=None, plan=None, screen_frame_bgr=None):
         """One chunk of a stream: the carried states `buffers` (from _stream_state_buffers) are zeroed where reset[b] != 0, used
         as the initial states, and overwritten with the chunk's last frame -- one eve_stream_state_rows launch each way, no
         conversion.  lengths (None, or int32 [B] on the device): stream b's states are committed from its frame lengths[b] - 1
@@ -390,6 +407,7 @@ class RefineNet(nn.Module):
                 k.stream_state_rows(t, t, reset)
         if plan is not None:
             lengths = plan['count'][2 * heatmap_initial.shape[0]:]
+        screen_frame = self._screen_input(screen_frame, screen_frame_bgr)
         hf, states, _ = self._sequence(heatmap_initial, screen_frame, buffers if buffers else None, plan)
         for dst, src in zip(flat(buffers), flat(states)):
             if lengths is None:

@@ -722,6 +722,11 @@ int eve_stream_permute_rows(int S, int T, long long row_bytes, long long frame_s
  * 16 843 009 (covers 3840 x 2160; beyond it S could exceed 32 bits), IW * C > 40 960 bytes (one row of sums is kept in LDS). */
 int eve_screen_u8_area_to_nchw(long long N, int IH, int IW, int C, const uint8_t* src_nhwc, int OH, int OW, float* dst_nchw,
                                eve_stream_t stream);
+/* The same for a BGR(A) capture (what capture APIs and OpenCV deliver): dst[c] is taken from source channel 2 - c, so the result
+ * equals eve_screen_u8_area_to_nchw on the channel-reversed capture bit for bit, without that copy.  Kernel names:
+ * screen_u8_area_bgr_kernel<true | false>.  Same limits and refusals.                                                       */
+int eve_screen_u8_area_bgr_to_nchw(long long N, int IH, int IW, int C, const uint8_t* src_nhwc, int OH, int OW, float* dst_nchw,
+                                   eve_stream_t stream);
 /* Live camera frames: one eye patch per call cut from whole uint8 frames [N][IH][IW][C] (C = 3, or 4 with the fourth channel
  * ignored; the channel order is kept; IH, IW <= 16384) through a per-frame homography warps [N][3][3] float, row-major m, that
  * maps a PATCH pixel to a CAMERA pixel -- the matrix cv2.warpPerspective takes with WARP_INVERSE_MAP; a caller who holds the
@@ -781,6 +786,43 @@ int eve_eye_warp_lens_u8_to_nchw(long long N, int IH, int IW, int C, const uint8
                                  int OH, int OW, float* dst_nchw, eve_stream_t stream);
 int eve_eye_warp_lens_u8_to_stem(int dtype /* EVE_DT_BF16 | EVE_DT_F16 */, long long N, int IH, int IW, int C, const uint8_t* frames_nhwc,
                                  const float* warps, const float* lens, int OH, int OW, void* x_padded, eve_stream_t stream);
+/* The same patches from frames in the layouts cameras and decoders deliver, converted tap by tap inside the same launch: no RGB
+ * frame is ever made.  `frames` holds N frames back to back, each byte-linear (no row pitch, one pointer):
+ *   EVE_PIX_BGR    [IH][IW][3]          channel 2 is red, channel 0 blue
+ *   EVE_PIX_BGRA   [IH][IW][4]          the same, a fourth channel ignored
+ *   EVE_PIX_NV12   [IH*3/2][IW]         IH rows of luma, then IH/2 rows of interleaved U, V: for pixel (y, x), U is byte
+ *                                       IH*IW + (y>>1)*IW + (x & ~1) of the frame and V the next byte
+ *   EVE_PIX_I420   [IH*3/2][IW]         luma, then the U plane of (IH/2)*(IW/2) bytes, then the V plane: U is byte
+ *                                       IH*IW + (y>>1)*(IW/2) + (x>>1), V is (IH/2)*(IW/2) bytes further
+ *   EVE_PIX_YUYV   [IH][IW][2]          Y is [y][x][0], U is [y][x & ~1][1], V is [y][x | 1][1]
+ * NV12 and I420 need IH and IW even, YUYV IW even; IH, IW <= 16384 as before.  Chroma is the NEAREST sample, replicated over its
+ * 2 x 2 block (YUYV: its pair), as OpenCV's cvtColor replicates it.  Conversion, bit-exact, per tap and BEFORE the blend, in
+ * int32 with arithmetic shifts (every intermediate is below 2^30 in magnitude):
+ *   yy = max(0, Y - y0) * CY;   u = U - 128;   v = V - 128
+ *   R = clamp((yy + 2^19 + CVR*v)         >> 20, 0, 255)
+ *   G = clamp((yy + 2^19 - CVG*v - CUG*u) >> 20, 0, 255)
+ *   B = clamp((yy + 2^19 + CUB*u)         >> 20, 0, 255)
+ * with each constant floor(c * 2^20 + 0.5) of its coefficient:
+ *   matrix          y0   CY       CVR      CUG     CVG     CUB
+ *   EVE_YUV_BT601   16   1220542  1673527  409993  852492  2116026    limited range; OpenCV's COLOR_YUV2RGB_NV12 numbers
+ *   EVE_YUV_BT709   16   1220542  1880097  223347  558891  2214593    limited range
+ *   EVE_YUV_JFIF     0   1048576  1470104  360853  748826  1858077    full range (MJPEG)
+ * `matrix` is ignored for BGR(A).  A tap outside the frame adds 0 to all three sums (it is NOT the conversion of Y = U = V = 0).
+ * From the three 8-bit values on, everything is the contract above: hence, for every format F and matrix M,
+ *   warp_F(buf) == eve_eye_warp_u8_to_*(to_rgb_F,M(buf))        bit for bit, in the float form and in both packed forms,
+ * with to_rgb the per-pixel conversion applied to the whole frame (tests/pixel_format_ref.py).  lens: NULL for the plain
+ * contract, or [N][12] rows for the lens contract (eve_eye_warp_lens_u8_to_*).  No alignment is asked of `frames`.  Kernel names:
+ * eye_warp_fmt_kernel<F,L,T> with F in bgr, bgra, nv12, i420, yuyv; L plain or lens; T float, eve::bf16_t or eve::f16_t.
+ * Refused without a launch: an unknown format, an unknown matrix with a YUV format, odd dimensions as above, and what the
+ * plain pair refuses.  Not offered: row pitches or separate plane pointers, UYVY / NV21 / P010 or any 10-bit layout, bilinear
+ * chroma up-sampling, gradients.                                                                                           */
+enum { EVE_PIX_BGR = 0, EVE_PIX_BGRA = 1, EVE_PIX_NV12 = 2, EVE_PIX_I420 = 3, EVE_PIX_YUYV = 4 };
+enum { EVE_YUV_BT601 = 0, EVE_YUV_BT709 = 1, EVE_YUV_JFIF = 2 };
+int eve_eye_warp_fmt_to_nchw(int format, int matrix, long long N, int IH, int IW, const uint8_t* frames, const float* warps,
+                             const float* lens /* may be NULL */, int OH, int OW, float* dst_nchw, eve_stream_t stream);
+int eve_eye_warp_fmt_to_stem(int dtype /* EVE_DT_BF16 | EVE_DT_F16 */, int format, int matrix, long long N, int IH, int IW,
+                             const uint8_t* frames, const float* warps, const float* lens /* may be NULL */, int OH, int OW,
+                             void* x_padded, eve_stream_t stream);
 /* Eye normalisation derived from the head pose, one launch for both eyes of N frames: everything the pipeline reads per frame and
  * eye follows from the face tracker's solvePnP result and the camera matrix.  pose [N][18] float, widened to float64:
  *   (fx, fy, cx, cy,  r0, r1, r2,  t0, t1, t2,  l0, l1, l2,  q0, q1, q2,  focal_norm, distance_norm)

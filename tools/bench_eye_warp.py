@@ -3,7 +3,7 @@
 and of one EVEStream step fed whole camera frames next to the same step fed pre-cut uint8 patches.
 
     python tools/bench_eye_warp.py [--patches 64] [--size 1920x1080] [--iters 500] [--rounds 5] [--shapes 1x1 8x4 32x2]
-                                   [--steps 50] [--dtype bf16] [--lens] [--pose] [--markdown profiles/table.md]
+                                   [--steps 50] [--dtype bf16] [--lens] [--pose] [--format nv12] [--markdown profiles/table.md]
 
 Part 1, per launch, the four routes interleaved in one process (the median over the rounds of events around `iters` calls):
     warp_nchw / warp_stem   N patches of 128 x 128 cut from N frames of the given size, each by its own rotated, scaled warp with a
@@ -14,13 +14,19 @@ Part 1, per launch, the four routes interleaved in one process (the median over 
                             rational eight-coefficient lens of lens_rows() (the arithmetic does not depend on the values)
     pose_normalize          with --pose: eve_eye_pose_normalize on N pose rows (both eyes of N frames: 2 N threads) into preallocated
                             outputs -- the launch that derives the warps, R, o, h and head_R from the face tracker's solvePnP result
+    fmt_nchw / fmt_stem     with --format {bgr,nv12,i420,yuyv}: the same patches from frames in that layout through
+                            eve_eye_warp_fmt_to_nchw / _to_stem (bt601), which convert only the taps they read
+    conv_nchw / conv_stem   with --format: what a caller did before -- convert the WHOLE frames to RGB on the device with torch
+                            (to_rgb_device: the same integer matrix, several elementwise passes), then the RGB launch; conv_only
+                            is the conversion alone.  These three run iters / 20 times per round.
 The rate quoted for a warp is (bytes its loads ask for: 4 taps x 3 channels per output pixel) + (bytes stored) over the time; the
 taps overlap, so the distinct bytes behind them are about a quarter -- it is a rate of the kernel's traffic, not of HBM.
 
 Part 2, per EVEStream step under graph replay (refine_net config): `camera` feeds camera_frame + two warps per frame, `patches`
 the uint8 [B, Tc, 128, 128, 3] patch pair.  The camera step also copies B * Tc whole frames into the graph's input buffer.  With
 --lens a third stream, `lens`, feeds the camera keys plus camera_lens.  With --pose another stream, `pose`, feeds camera_frame + eye_pose
-and none of the keys the rows derive (warps, <side>_h, <side>_o, <side>_R, head_R): one more launch inside the graph."""
+and none of the keys the rows derive (warps, <side>_h, <side>_o, <side>_R, head_R): one more launch inside the graph.  With --format
+a stream `fmt` feeds camera_frame_<format> in place of camera_frame: fewer bytes copied into the graph, the taps converted inside."""
 import argparse
 import json
 import math
@@ -81,6 +87,38 @@ def pose_rows(n, IH, IW, seed):
     return torch.tensor(np.array(rows), dtype=torch.float32)
 
 
+def format_frames(fmt, lead, IH, IW, gen=None, device='cuda'):
+    """Random bytes in the layout of fmt with leading dimensions `lead`."""
+    shape = {'bgr': (IH, IW, 3), 'nv12': (IH * 3 // 2, IW), 'i420': (IH * 3 // 2, IW), 'yuyv': (IH, IW, 2)}[fmt]
+    if gen is None:
+        return torch.randint(0, 256, tuple(lead) + shape, dtype=torch.uint8, device=device)
+    return torch.randint(0, 256, tuple(lead) + shape, generator=gen, dtype=torch.uint8).to(device)
+
+
+def to_rgb_device(buf, fmt, IH, IW):
+    """Whole frames [N, ...] of fmt -> RGB uint8 [N, IH, IW, 3] with torch on the device: the bt601 integer matrix of
+    include/eve_hip.h, chroma replicated -- the pass a caller ran before the RGB launch."""
+    if fmt == 'bgr':
+        return buf.flip(-1).contiguous()
+    N = buf.shape[0]
+    if fmt == 'yuyv':
+        Y, U, V = buf[..., 0], buf[:, :, 0::2, 1].repeat_interleave(2, dim=2), buf[:, :, 1::2, 1].repeat_interleave(2, dim=2)
+    else:
+        flat = buf.reshape(N, -1)
+        Y = flat[:, :IH * IW].view(N, IH, IW)
+        if fmt == 'nv12':
+            uv = flat[:, IH * IW:].view(N, IH // 2, IW // 2, 2)
+            U, V = uv[..., 0], uv[..., 1]
+        else:
+            q = (IH // 2) * (IW // 2)
+            U, V = flat[:, IH * IW:IH * IW + q].view(N, IH // 2, IW // 2), flat[:, IH * IW + q:].view(N, IH // 2, IW // 2)
+        U, V = (c.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2) for c in (U, V))
+    yy = (Y.int() - 16).clamp_(min=0) * 1220542 + (1 << 19)
+    u, v = U.int() - 128, V.int() - 128
+    rgb = [(yy + 1673527 * v) >> 20, (yy - 852492 * v - 409993 * u) >> 20, (yy + 2116026 * u) >> 20]
+    return torch.stack([c.clamp_(0, 255) for c in rgb], dim=-1).to(torch.uint8)
+
+
 def median(v):
     return sorted(v)[len(v) // 2]
 
@@ -112,6 +150,17 @@ def launches(args, IH, IW):
             status = k.lib.eve_eye_pose_normalize(N, ptrs[0], HW[0], HW[1], *ptrs[1:], ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
             assert status == 0, k.lib.eve_last_error()
         routes['pose_normalize'] = pose_launch
+    slow = set()
+    if args.format:
+        fmt = args.format
+        raw = format_frames(fmt, (N,), IH, IW)
+        routes['fmt_nchw'] = lambda: k.eye_warp_fmt_to_nchw(raw, warps, HW, fmt)
+        routes['fmt_stem'] = lambda: k.eye_warp_fmt_to_stem(raw, warps, HW, fmt, out=packed)
+        routes['conv_only'] = lambda: to_rgb_device(raw, fmt, IH, IW)
+        routes['conv_nchw'] = lambda: k.eye_warp_u8_to_nchw(to_rgb_device(raw, fmt, IH, IW), warps, HW)
+        routes['conv_stem'] = lambda: k.eye_warp_u8_to_stem(to_rgb_device(raw, fmt, IH, IW), warps, HW, out=packed)
+        slow = {'conv_only', 'conv_nchw', 'conv_stem'}
+        assert torch.equal(routes['fmt_nchw'](), routes['conv_nchw']()), 'the direct launch and convert-then-warp disagree'
     for fn in routes.values():                   # warm up: code objects, allocator
         for _ in range(5):
             fn()
@@ -119,7 +168,7 @@ def launches(args, IH, IW):
     times = {name: [] for name in routes}
     for _ in range(args.rounds):
         for name, fn in routes.items():
-            times[name].append(device_ms(fn, args.iters))
+            times[name].append(device_ms(fn, max(1, args.iters // 20) if name in slow else args.iters))
     pixels = N * HW[0] * HW[1]
     stored = {'nchw': pixels * 3 * 4, 'stem': packed.numel() * 2}
     res = {'patches': N, 'frame': '%dx%d' % (IW, IH), 'patch': '%dx%d' % HW, 'iters': args.iters, 'rounds': args.rounds}
@@ -135,6 +184,14 @@ def launches(args, IH, IW):
             res['lens_%s_bytes' % form] = res['warp_%s_bytes' % form]
             res['lens_%s_GBps' % form] = round(res['lens_%s_bytes' % form] / (1e-3 * median(times['lens_' + form])) / 1e9, 1)
             res['lens_over_warp_%s' % form] = round(median(times['lens_' + form]) / median(times['warp_' + form]), 3)
+    if args.format:
+        res['format'] = args.format
+        res['frame_bytes'] = {'rgb': frames[0].numel(), args.format: raw[0].numel()}
+        for form in ('nchw', 'stem'):
+            res['fmt_over_warp_%s' % form] = round(median(times['fmt_' + form]) / median(times['warp_' + form]), 3)
+            res['conv_over_fmt_%s' % form] = round(median(times['conv_' + form]) / median(times['fmt_' + form]), 2)
+        k.eye_warp_fmt_to_stem(raw, warps, HW, args.format, out=packed)
+        res['fmt_kernel'] = k.lib.eve_last_kernel().decode()
     if args.pose:
         assert outs[5].all(), 'bench poses must be valid'
         pose_launch()
@@ -174,6 +231,10 @@ def stream_steps(args, IH, IW):
             from eve_amd.eye_net import EYE_POSE_DERIVED
             streams['pose'] = (eve_amd.EVEStream(model, B), dict({k_: v for k_, v in cam.items() if k_ not in EYE_POSE_DERIVED},
                                                                  eye_pose=pose_rows(B * Tc, IH, IW, seed=B).view(B, Tc, 18).cuda()))
+        if args.format:
+            fmt_chunk = {k_: v for k_, v in cam.items() if k_ != 'camera_frame'}
+            fmt_chunk['camera_frame_' + args.format] = format_frames(args.format, (B, Tc), IH, IW, gen=g)
+            streams['fmt'] = (eve_amd.EVEStream(model, B), fmt_chunk)
         for s, chunk in streams.values():
             for _ in range(3):
                 s.step(chunk)                    # capture + warm replays
@@ -192,6 +253,9 @@ def stream_steps(args, IH, IW):
         if args.pose:
             res['pose_minus_camera_ms'] = round(res['pose_step_ms'] - res['camera_step_ms'], 4)
         res['camera_frame_MB_copied'] = round(B * Tc * IH * IW * 3 / 1e6, 1)
+        if args.format:
+            res['fmt_minus_camera_ms'] = round(res['fmt_step_ms'] - res['camera_step_ms'], 4)
+            res['fmt_frame_MB_copied'] = round(fmt_chunk['camera_frame_' + args.format].numel() / 1e6, 1)
         rows.append(res)
         print(json.dumps(res), flush=True)
         del streams, cam, pat
@@ -210,6 +274,8 @@ def main():
     ap.add_argument('--dtype', default='bf16', choices=sorted(DTYPES))
     ap.add_argument('--lens', action='store_true', help='also time the lens launches and an EVEStream step with camera_lens')
     ap.add_argument('--pose', action='store_true', help='also time eve_eye_pose_normalize and an EVEStream step with eye_pose rows')
+    ap.add_argument('--format', default=None, choices=['bgr', 'nv12', 'i420', 'yuyv'],
+                    help='also time the launches and an EVEStream step on frames in this layout, and convert-then-warp beside them')
     ap.add_argument('--markdown', default=None, help='also write the tables to this file')
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -244,6 +310,18 @@ def main():
             lines.append('| %d x %d | %.4f | %.4f .. %.4f | %.4f | %.4f .. %.4f | %.4f |' % (
                 r['B'], r['Tc'], r['pose_step_ms'], r['pose_step_ms_min_max'][0], r['pose_step_ms_min_max'][1], r['camera_step_ms'],
                 r['camera_step_ms_min_max'][0], r['camera_step_ms_min_max'][1], r['pose_minus_camera_ms']))
+    if args.format:
+        lines += ['', '| %s launch (%d patches, %s frames) | us | min .. max |' % (args.format, one['patches'], one['frame']), '|---|---|---|']
+        for name in ('warp_nchw', 'fmt_nchw', 'conv_nchw', 'warp_stem', 'fmt_stem', 'conv_stem', 'conv_only'):
+            lines.append('| %s | %.2f | %.2f .. %.2f |' % (name, one[name + '_us'], one[name + '_us_min_max'][0], one[name + '_us_min_max'][1]))
+    if rows and args.format:
+        lines += ['', '| B x Tc (%s) | %s step ms | min .. max | camera step ms | min .. max | %s - camera ms | MB copied %s | MB copied rgb |' % (
+            args.dtype, args.format, args.format, args.format), '|---|---|---|---|---|---|---|---|']
+        for r in rows:
+            lines.append('| %d x %d | %.4f | %.4f .. %.4f | %.4f | %.4f .. %.4f | %.4f | %.1f | %.1f |' % (
+                r['B'], r['Tc'], r['fmt_step_ms'], r['fmt_step_ms_min_max'][0], r['fmt_step_ms_min_max'][1], r['camera_step_ms'],
+                r['camera_step_ms_min_max'][0], r['camera_step_ms_min_max'][1], r['fmt_minus_camera_ms'], r['fmt_frame_MB_copied'],
+                r['camera_frame_MB_copied']))
     table = '\n'.join(lines)
     print(table, flush=True)
     if args.markdown:
