@@ -176,6 +176,8 @@ SIGNATURES = {
     'eve_eye_warp_lens_u8_to_nchw': [L, I, I, I, P, P, P, I, I, P, P],
     'eve_eye_warp_lens_u8_to_stem': [I, L, I, I, I, P, P, P, I, I, P, P],
     'eve_eye_pose_normalize': [L, P, I, I, P, P, P, P, P, P, P],
+    'eve_eye_pose_normalize_rt': [L, I, P, I, P, P, P, I, I, P, P, P, P, P, P],
+    'eve_face_pose_solve': [L, I, I, I, P, P, P, P, P, P, P, P, P, P],
     'eve_screen_u8_area_bgr_to_nchw': [L, I, I, I, P, I, I, P, P],
     'eve_eye_warp_fmt_to_nchw': [I, I, L, I, I, P, P, P, I, I, P, P],
     'eve_eye_warp_fmt_to_stem': [I, I, I, L, I, I, P, P, P, I, I, P, P],

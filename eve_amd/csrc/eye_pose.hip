@@ -34,52 +34,21 @@ __device__ __forceinline__ void cross3(const double (&a)[3], const double (&b)[3
 
 __device__ __forceinline__ bool finite64(const double x) { return fabs(x) <= 1.79769313486231570815e308; }      // false for a NaN
 
-__global__ __launch_bounds__(EP_THREADS) void eye_pose_normalize_kernel(const int N, const float* __restrict__ pose, const int OH, const int OW,
-                                                                        float* __restrict__ head_R, float* __restrict__ o_out,
-                                                                        float* __restrict__ R_out, float* __restrict__ warp_out,
-                                                                        float* __restrict__ h_out, uint8_t* __restrict__ valid_out) {
+// Stages 2-6 of the contract for eye i = e * N + n, from H = the float32 head_R just written (widened) and the translation tv:
+// shared by the pose form (stage 1 = Rodrigues) and by eve_eye_pose_normalize_rt (head_R and head_t as they come).
+__device__ __forceinline__ void eye_normalize_from_rt(const long long i, const int e, const double (&H)[3][3], const double (&tv)[3], const double fx,
+                                                      const double fy, const double cx, const double cy, const double (&cl)[3],
+                                                      const double (&cr)[3], const double f, const double dn, const bool row_ok, const int OH,
+                                                      const int OW, float* __restrict__ o_out, float* __restrict__ R_out,
+                                                      float* __restrict__ warp_out, float* __restrict__ h_out, uint8_t* __restrict__ valid_out) {
 #pragma clang fp contract(off)
-    const long long i = (long long)blockIdx.x * EP_THREADS + threadIdx.x;
-    if (i >= 2LL * N) return;
-    const int e = i >= N ? 1 : 0, n = (int)(i - (long long)e * N);
-    double p[18];
-    bool row_ok = true;
-#pragma unroll
-    for (int j = 0; j < 18; ++j) {
-        p[j] = (double)pose[(size_t)n * 18 + j];
-        row_ok = row_ok && finite64(p[j]);
-    }
-    const double fx = p[0], fy = p[1], cx = p[2], cy = p[3], f = p[16], dn = p[17];
-    row_ok = row_ok && fx > 0.0 && fy > 0.0 && f > 0.0 && dn > 0.0;
-
-    // 1. head_R (Rodrigues), rounded to float32
-    double H[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
-    const double th = norm3(p[4], p[5], p[6]);
-    if (finite64(p[4]) && finite64(p[5]) && finite64(p[6]) && th != 0.0) {
-        const double k0 = p[4] / th, k1 = p[5] / th, k2 = p[6] / th;
-        const double c = cos(th), s = sin(th);
-        const double v = 1.0 - c;
-        const double vk0 = v * k0, vk1 = v * k1, vk2 = v * k2, sk0 = s * k0, sk1 = s * k1, sk2 = s * k2;
-        H[0][0] = c + vk0 * k0;   H[0][1] = vk0 * k1 - sk2; H[0][2] = vk0 * k2 + sk1;
-        H[1][0] = vk1 * k0 + sk2; H[1][1] = c + vk1 * k1;   H[1][2] = vk1 * k2 - sk0;
-        H[2][0] = vk2 * k0 - sk1; H[2][1] = vk2 * k1 + sk0; H[2][2] = c + vk2 * k2;
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) {
-            const float r = (float)H[a][b];
-            if (e == 0) head_R[(size_t)n * 9 + a * 3 + b] = r;
-            H[a][b] = (double)r;
-        }
-
     // 2. o = head_R c + t, rounded to float32
-    const double c0 = e ? p[13] : p[10], c1 = e ? p[14] : p[11], c2 = e ? p[15] : p[12];
+    const double c0 = e ? cr[0] : cl[0], c1 = e ? cr[1] : cl[1], c2 = e ? cr[2] : cl[2];
     float o32[3];
     double o[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        o32[a] = (float)(((H[a][0] * c0 + H[a][1] * c1) + H[a][2] * c2) + p[7 + a]);
+        o32[a] = (float)(((H[a][0] * c0 + H[a][1] * c1) + H[a][2] * c2) + tv[a]);
         o[a] = (double)o32[a];
     }
 
@@ -155,6 +124,84 @@ __global__ __launch_bounds__(EP_THREADS) void eye_pose_normalize_kernel(const in
     valid_out[i] = valid ? 1 : 0;
 }
 
+__global__ __launch_bounds__(EP_THREADS) void eye_pose_normalize_kernel(const int N, const float* __restrict__ pose, const int OH, const int OW,
+                                                                        float* __restrict__ head_R, float* __restrict__ o_out,
+                                                                        float* __restrict__ R_out, float* __restrict__ warp_out,
+                                                                        float* __restrict__ h_out, uint8_t* __restrict__ valid_out) {
+#pragma clang fp contract(off)
+    const long long i = (long long)blockIdx.x * EP_THREADS + threadIdx.x;
+    if (i >= 2LL * N) return;
+    const int e = i >= N ? 1 : 0, n = (int)(i - (long long)e * N);
+    double p[18];
+    bool row_ok = true;
+#pragma unroll
+    for (int j = 0; j < 18; ++j) {
+        p[j] = (double)pose[(size_t)n * 18 + j];
+        row_ok = row_ok && finite64(p[j]);
+    }
+    const double fx = p[0], fy = p[1], cx = p[2], cy = p[3], f = p[16], dn = p[17];
+    row_ok = row_ok && fx > 0.0 && fy > 0.0 && f > 0.0 && dn > 0.0;
+
+    // 1. head_R (Rodrigues), rounded to float32
+    double H[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+    const double th = norm3(p[4], p[5], p[6]);
+    if (finite64(p[4]) && finite64(p[5]) && finite64(p[6]) && th != 0.0) {
+        const double k0 = p[4] / th, k1 = p[5] / th, k2 = p[6] / th;
+        const double c = cos(th), s = sin(th);
+        const double v = 1.0 - c;
+        const double vk0 = v * k0, vk1 = v * k1, vk2 = v * k2, sk0 = s * k0, sk1 = s * k1, sk2 = s * k2;
+        H[0][0] = c + vk0 * k0;   H[0][1] = vk0 * k1 - sk2; H[0][2] = vk0 * k2 + sk1;
+        H[1][0] = vk1 * k0 + sk2; H[1][1] = c + vk1 * k1;   H[1][2] = vk1 * k2 - sk0;
+        H[2][0] = vk2 * k0 - sk1; H[2][1] = vk2 * k1 + sk0; H[2][2] = c + vk2 * k2;
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            const float r = (float)H[a][b];
+            if (e == 0) head_R[(size_t)n * 9 + a * 3 + b] = r;
+            H[a][b] = (double)r;
+        }
+
+    const double tv[3] = {p[7], p[8], p[9]}, cl[3] = {p[10], p[11], p[12]}, cr[3] = {p[13], p[14], p[15]};
+    eye_normalize_from_rt(i, e, H, tv, fx, fy, cx, cy, cl, cr, f, dn, row_ok, OH, OW, o_out, R_out, warp_out, h_out, valid_out);
+}
+
+// eve_eye_pose_normalize_rt: the same threads, head_R and head_t read instead of derived.  Frame n reads row n / T of `rows`.
+__global__ __launch_bounds__(EP_THREADS) void eye_pose_normalize_rt_kernel(const int N, const int T, const float* __restrict__ rows, const int stride,
+                                                                           const float* __restrict__ head_R, const float* __restrict__ head_t,
+                                                                           const uint8_t* __restrict__ valid_in, const int OH, const int OW,
+                                                                           float* __restrict__ o_out, float* __restrict__ R_out,
+                                                                           float* __restrict__ warp_out, float* __restrict__ h_out,
+                                                                           uint8_t* __restrict__ valid_out) {
+#pragma clang fp contract(off)
+    const long long i = (long long)blockIdx.x * EP_THREADS + threadIdx.x;
+    if (i >= 2LL * N) return;
+    const int e = i >= N ? 1 : 0, n = (int)(i - (long long)e * N);
+    const float* row = rows + (size_t)(n / T) * stride;
+    double p[12], H[3][3], tv[3];
+    bool row_ok = valid_in == nullptr || valid_in[n] != 0;
+#pragma unroll
+    for (int j = 0; j < 12; ++j) {
+        p[j] = (double)row[j];
+        row_ok = row_ok && finite64(p[j]);
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            H[a][b] = (double)head_R[(size_t)n * 9 + a * 3 + b];
+            row_ok = row_ok && finite64(H[a][b]);
+        }
+        tv[a] = (double)head_t[(size_t)n * 3 + a];
+        row_ok = row_ok && finite64(tv[a]);
+    }
+    const double fx = p[0], fy = p[1], cx = p[2], cy = p[3], f = p[10], dn = p[11];
+    row_ok = row_ok && fx > 0.0 && fy > 0.0 && f > 0.0 && dn > 0.0;
+    const double cl[3] = {p[4], p[5], p[6]}, cr[3] = {p[7], p[8], p[9]};
+    eye_normalize_from_rt(i, e, H, tv, fx, fy, cx, cy, cl, cr, f, dn, row_ok, OH, OW, o_out, R_out, warp_out, h_out, valid_out);
+}
+
 }  // namespace
 }  // namespace eve
 
@@ -174,6 +221,26 @@ extern "C" int eve_eye_pose_normalize(long long N, const float* pose, int OH, in
     const dim3 grid((unsigned)((2 * N + EP_THREADS - 1) / EP_THREADS));
     EVE_LAUNCH("eye_pose_normalize_kernel", eye_pose_normalize_kernel, grid, dim3(EP_THREADS), 0, (hipStream_t)stream, (int)N, pose, OH, OW, head_R, o,
                R, warp, h, valid);
+    EVE_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int eve_eye_pose_normalize_rt(long long N, int frames_per_row, const float* rows, int row_stride, const float* head_R, const float* head_t,
+                                         const uint8_t* valid_in, int OH, int OW, float* o, float* R, float* warp, float* h, uint8_t* valid,
+                                         eve_stream_t stream) {
+    const char* why = nullptr;
+    if (N <= 0 || frames_per_row <= 0 || OH <= 0 || OW <= 0 || !rows || !head_R || !head_t || !o || !R || !warp || !h || !valid) why = "bad arguments";
+    else if (row_stride < 12) why = "a row has at least 12 entries";
+    else if (OH > EP_MAX_PATCH || OW > EP_MAX_PATCH) why = "patch too large (OH and OW <= 4096)";
+    else if (N > (long long)0x3fffffff) why = "2 N must fit 31 bits";
+    if (why) {
+        char msg[128];
+        snprintf(msg, sizeof(msg), "eye_pose_normalize_rt: %s", why);
+        return set_error_msg(msg);
+    }
+    const dim3 grid((unsigned)((2 * N + EP_THREADS - 1) / EP_THREADS));
+    EVE_LAUNCH("eye_pose_normalize_rt_kernel", eye_pose_normalize_rt_kernel, grid, dim3(EP_THREADS), 0, (hipStream_t)stream, (int)N, frames_per_row,
+               rows, row_stride, head_R, head_t, valid_in, OH, OW, o, R, warp, h, valid);
     EVE_CHECK_LAUNCH();
     return 0;
 }

@@ -27,6 +27,10 @@ uint8 frames is 4x less PCIe traffic, and the float values produced here are bit
                                  a face tracker's cv2.solvePnP result -> the float32 [..., 18] rows of the `eye_pose` key (EyeNet /
                                  EVE / EVEStream take `camera_frame` + `eye_pose` and derive the warps, R, o, h and head_R on the device)
   normalize_eyes(pose)           those rows -> the derived tensors themselves (head_R, <side>_o, _R, _eye_warp, _h, pose_valid)
+  face_rig(K, model, eyes, focal_norm, distance_norm)
+                                 a camera and a head model -> the float32 [..., 12 + 3L] rows of the `face_rig` key (EyeNet / EVE /
+                                 EVEStream take `camera_frame` + `face_landmarks` + `face_rig` and solve the head pose on the device)
+  solve_head_pose(landmarks, rig) 2-D landmarks -> head_R, head_t, reproj_rms, valid (in place of cv2.solvePnP per frame)
   EyeNet.forward_sequence / RefineNet.forward_sequence / EVE accept the uint8 tensors directly (eye patches go straight
   into the stem kernel's packed bf16 layout, no float tensor is ever materialised).
   DevicePrefetcher(iterable)     pinned double-buffered H2D on a side stream
@@ -182,6 +186,75 @@ def normalize_eyes(pose, size=None):
         out[side + '_h'] = h[e].view(lead + (2,))
     out['pose_valid'] = valid.view((2,) + lead).movedim(0, -1) != 0
     return out
+
+
+def face_rig(camera_matrix, face_model, eye_centers, focal_norm, distance_norm):
+    """The rows of the `face_rig` key, one per sequence: camera_matrix [..., 3, 3] = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] of the
+    UNDISTORTED image the landmarks refer to; face_model [..., L, 3], the head model's points in the order the tracker delivers
+    its landmarks, 4 <= L <= 68; eye_centers [..., 2, 3], left and right, in the same frame and length unit (EVE: millimetres);
+    focal_norm and distance_norm (scalars or [...]) as for eye_pose.  -> float32 [..., 12 + 3L] = (fx, fy, cx, cy, left eye
+    centre, right eye centre, focal_norm, distance_norm, the L model points).  numpy arrays or torch tensors; the leading
+    dimensions broadcast against each other.  A torch tensor comes back when camera_matrix is one (on its device), else a numpy
+    array.
+
+    ValueError: a camera matrix that is not [..., 3, 3], has skew (K[0, 1] != 0) or a last row other than (0, 0, 1); a model
+    that is not [..., L, 3] with L in 4..68; eye centres of another shape.  Values are not judged here: a NaN, or model points
+    on one line, give valid False on the device (include/eve_hip.h eve_face_pose_solve)."""
+    as_torch = torch.is_tensor(camera_matrix)
+    to_np = lambda a: (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(np.float64)
+    K, m, c, f, dn = to_np(camera_matrix), to_np(face_model), to_np(eye_centers), to_np(focal_norm), to_np(distance_norm)
+    if K.ndim < 2 or K.shape[-2:] != (3, 3):
+        raise ValueError('face_rig: camera_matrix must be [..., 3, 3], got %s' % (tuple(K.shape),))
+    if (K[..., 0, 1] != 0).any():
+        raise ValueError('face_rig: a skewed camera matrix (K[0, 1] != 0) is not offered')
+    if (K[..., 2, :] != np.array([0.0, 0.0, 1.0])).any():
+        raise ValueError('face_rig: the last row of camera_matrix must be (0, 0, 1)')
+    if m.ndim < 2 or m.shape[-1] != 3 or not 4 <= m.shape[-2] <= 68:
+        raise ValueError('face_rig: face_model must be [..., L, 3] with 4 <= L <= 68, got %s' % (tuple(m.shape),))
+    if c.ndim < 2 or c.shape[-2:] != (2, 3):
+        raise ValueError('face_rig: eye_centers must be [..., 2, 3] (left, right), got %s' % (tuple(c.shape),))
+    L = m.shape[-2]
+    lead = np.broadcast_shapes(K.shape[:-2], m.shape[:-2], c.shape[:-2], f.shape, dn.shape)
+    out = np.zeros(lead + (12 + 3 * L,), dtype=np.float32)
+    out[..., 0], out[..., 1], out[..., 2], out[..., 3] = K[..., 0, 0], K[..., 1, 1], K[..., 0, 2], K[..., 1, 2]
+    out[..., 4:7], out[..., 7:10] = c[..., 0, :], c[..., 1, :]
+    out[..., 10], out[..., 11] = f, dn
+    out[..., 12:] = m.reshape(m.shape[:-2] + (3 * L,))
+    return torch.from_numpy(out).to(camera_matrix.device) if as_torch else out
+
+
+def solve_head_pose(landmarks, rig, lengths=None):
+    """The head pose of every frame from its 2-D face landmarks, on the device, in place of one cv2.solvePnP per frame: landmarks
+    float32 [S, T, L, 2 | 3] (or [T, L, 2 | 3] with rig [12 + 3L]: one sequence) = pixel (u, v[, w]) of the undistorted image, w an
+    optional confidence (0 drops the point); rig float32 [S, 12 + 3L] from face_rig, one row per sequence; lengths None, or S
+    integers (a list, a numpy array or a tensor): frames past a sequence's count are not solved.  -> a dict of head_R [S, T, 3, 3],
+    head_t [S, T, 3], reproj_rms [S, T] (pixels) float32 and valid, bool [S, T].  Every sequence starts cold (a closed-form guess),
+    every later frame from the frame before; a frame without a solution (a NaN, fewer than 4 weighted points, model points on a
+    line, no convergence) has valid False, head_R = I, head_t = 0, reproj_rms = 0, and the next one starts cold.  Levenberg-
+    Marquardt on the weighted reprojection error in float64; the contract is include/eve_hip.h eve_face_pose_solve.  Not
+    offered: landmarks of a distorted image (undistort the L points first), outlier rejection beyond the weights, an rvec,
+    gradients, per-frame camera matrices; a planar model runs, but which of its two minima is found is not promised."""
+    ok = lambda t: torch.is_tensor(t) and t.dtype == torch.float32
+    if not ok(landmarks) or landmarks.dim() not in (3, 4) or landmarks.shape[-1] not in (2, 3):
+        raise TypeError('expected float32 landmarks shaped [S, T, L, 2 | 3], got %s %s' % (getattr(landmarks, 'dtype', type(landmarks)),
+                                                                                          tuple(getattr(landmarks, 'shape', ()))))
+    single = landmarks.dim() == 3
+    if single:
+        landmarks = landmarks[None]
+        rig = rig[None] if ok(rig) and rig.dim() == 1 else rig
+    S, T, L = landmarks.shape[:3]
+    if not ok(rig) or tuple(rig.shape) != (S, 12 + 3 * L):
+        raise TypeError('expected float32 rig rows shaped %s, got %s %s' % ((S, 12 + 3 * L), getattr(rig, 'dtype', type(rig)),
+                                                                           tuple(getattr(rig, 'shape', ()))))
+    if landmarks.numel() == 0:
+        raise ValueError('solve_head_pose: no frames (shape %s)' % (tuple(landmarks.shape),))
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths).to(device=landmarks.device, dtype=torch.int32).contiguous()
+        if tuple(lengths.shape) != (S,):
+            raise ValueError('solve_head_pose: lengths needs one entry per sequence (%d)' % S)
+    head_R, head_t, rms, valid = default_kernels().face_pose_solve(landmarks.contiguous(), rig.contiguous(), lengths)
+    out = {'head_R': head_R, 'head_t': head_t, 'reproj_rms': rms, 'valid': valid != 0}
+    return {k_: v[0] for k_, v in out.items()} if single else out
 
 
 def warp_eye_patches(frames, warps, size=None, lens=None, format='rgb', matrix='bt601'):

@@ -23,7 +23,7 @@ import torch.nn as nn
 
 from . import losses, ops
 from .config import get_config
-from .eye_net import EyeNet, eye_input, eye_pose_batch
+from .eye_net import EyeNet, eye_input, eye_pose_batch, has_pose_form
 from .kernels import default_kernels
 
 
@@ -234,7 +234,8 @@ class EVE(nn.Module):
         if self.training:
             assert len(full_input_dict) == 1
             full_input_dict = next(iter(full_input_dict.values()))
-        # (the pose form -- camera_frame + eye_pose -- becomes the warp form in a copy, before the labels read left_o and left_R)
+        # (the pose form -- camera_frame + eye_pose -- becomes the warp form in a copy, before the labels read left_o and left_R;
+        # so does the face-landmark form, camera_frame + face_landmarks + face_rig: every sequence of a clip starts cold at t = 0)
         d = eye_pose_batch(full_input_dict, cfg)
         self.calculate_additional_labels(d, current_epoch=current_epoch)
         B, T = eye_input(d).shape[:2]
@@ -270,8 +271,10 @@ class EVE(nn.Module):
         output_dict = {k_: v for k_, v in inter.items() if k_.startswith('output_')}
         output_dict['left_pupil_size'] = inter['left_pupil_size']
         output_dict['right_pupil_size'] = inter['right_pupil_size']
-        if 'eye_pose' in full_input_dict:                             # the pose form: reported, folded into no validity
+        if has_pose_form(full_input_dict):                            # the pose forms: reported, folded into no validity
             output_dict['pose_valid'] = d['pose_valid']
+            if 'face_landmarks' in full_input_dict:                   # the head pose was solved here: the translation and the fit
+                output_dict['head_t'], output_dict['face_reproj_rms'] = d['head_t'], d['face_reproj_rms']
         if self.output_predictions:                                   # eve.py:194-222
             for key in ('timestamps', 'o', 'left_R', 'head_R', 'millimeters_per_pixel', 'pixels_per_millimeter',
                         'camera_transformation', 'inv_camera_transformation'):
@@ -323,7 +326,7 @@ class EVE(nn.Module):
                        'PoG_cm_initial', 'g_final', 'PoG_px_final', 'PoG_cm_final')
 
     def _predict_sequence(self, d, eye_states, refine_states, reset=None, return_heatmaps=False, lengths=None, masked=False,
-                          eye_mask=None, pose_gate=None):
+                          eye_mask=None, pose_gate=None, face_state=None):
         """The prediction part of forward() for one chunk of an EVEStream: eval only, no labels, no losses.  d: the chunk's
         inputs [B, Tc, ...] (not modified; camera_frame may be any one key of eye_net.EYE_FRAME_KEYS and the screen may come as
         screen_frame_bgr; the eyes as patches, as camera_frame + {left,right}_eye_warp, or as camera_frame +
@@ -342,11 +345,15 @@ class EVE(nn.Module):
         (EyeNet._stream_sequence, RefineNet._stream_sequence); the binocular quantities come from the usable eyes by selects:
         PoG_*_initial and o through _fuse2 (both usable: the mean's bits), and the combined gaze g_initial / g_final is rotated by
         left_R where the left eye is usable, else by right_R -- an approximation the reference never needed (it always has
-        both eyes and rotates by left_R).  The result gains valid [B, Tc] and eye_valid [B, Tc, 2], bool."""
+        both eyes and rotates by left_R).  The result gains valid [B, Tc] and eye_valid [B, Tc, 2], bool.
+        face_state: with the face-landmark form (camera_frame + face_landmarks [B, Tc, L, 2 | 3] + face_rig [B, 12 + 3L]) the
+        stream's carried head pose, float64 [B, 13], read as the pose before the chunk and overwritten with the pose after it by
+        the eve_face_pose_solve launch, which also reads reset[:B] and lengths[:B]; the result gains pose_valid, head_t and
+        face_reproj_rms."""
         assert not self.training, 'EVE._predict_sequence is eval-only'
         B = eye_input(d).shape[0]
-        posed = 'eye_pose' in d
-        d = dict(eye_pose_batch(d, self.config))
+        posed, faced = has_pose_form(d), 'face_landmarks' in d
+        d = dict(eye_pose_batch(d, self.config, face_state, None if reset is None else reset[:B], None if lengths is None else lengths[:B]))
         plan = eye_valid = None
         if masked:
             T = eye_input(d).shape[1]
@@ -371,6 +378,8 @@ class EVE(nn.Module):
         out = {k_: inter[k_] for k_ in self.PREDICTION_KEYS if k_ in inter}
         if posed:
             out['pose_valid'] = d['pose_valid']
+        if faced:
+            out['head_t'], out['face_reproj_rms'] = d['head_t'], d['face_reproj_rms']
         if plan is not None:
             out['valid'], out['eye_valid'] = plan['valid'].view(torch.bool), eye_valid
         if return_heatmaps and 'heatmap_final' in inter:

@@ -46,7 +46,17 @@ EYE_FRAME_KEYS = {'camera_frame': 'rgb', 'camera_frame_bgr': 'bgr', 'camera_fram
 EYE_LENS_KEY = 'camera_lens'                 # optional with the camera form: raw frames of a camera with lens distortion
 EYE_POSE_KEY = 'eye_pose'                    # the pose form: camera_frame + one packed row per frame (data.eye_pose)
 # what eye_pose_batch derives from the rows -- a batch holds the rows or these, never both
+FACE_LANDMARKS_KEY = 'face_landmarks'        # the face-landmark form: camera_frame + 2-D landmarks [B, T, L, 2 | 3] per frame ...
+FACE_RIG_KEY = 'face_rig'                    # ... + one row per sequence [B, 12 + 3L] (data.face_rig): the head pose is solved on the device
 EYE_POSE_DERIVED = ('head_R', 'left_o', 'right_o', 'left_R', 'right_R', 'left_eye_warp', 'right_eye_warp', 'left_h', 'right_h', 'pose_valid')
+# what the face-landmark form adds to them
+FACE_DERIVED = ('head_t', 'face_reproj_rms')
+
+
+def has_pose_form(batch):
+    """True for a batch whose eye normalisation is derived on the device (eye_pose, or face_landmarks + face_rig): its result
+    carries pose_valid."""
+    return EYE_POSE_KEY in batch or FACE_LANDMARKS_KEY in batch
 
 
 def camera_frame_key(batch):
@@ -82,10 +92,37 @@ def eye_input(batch):
     camera frames plus per-eye homographies (the warp form) or plus eye_pose, float32 [B, T, 18] rows from data.eye_pose (the
     pose form: the homographies, <side>_R, <side>_o, <side>_h and head_R are derived on the device -- eye_pose_batch).  Raises
     on a batch that holds two forms, half of one, eye_pose next to a key it derives, or tensors of the wrong dtype or shape for
-    the camera forms.  Both camera forms may carry camera_lens, float32 [B, T, 12] (data.camera_lens): one camera per frame,
+    the camera forms.  A third camera form takes the head pose from the face tracker's 2-D landmarks: camera_frame +
+    face_landmarks, float32 [B, T, L, 2 | 3] = pixel (u, v[, w]) of the undistorted image, + face_rig, float32 [B, 12 + 3L] rows from
+    data.face_rig, one per sequence (the face-landmark form: eve_face_pose_solve solves head_R and head_t on the device and
+    the pose form's normalisation continues from them -- eye_pose_batch).  It is refused beside eye_pose, patches or a derived
+    key; half of the pair raises ValueError, a wrong dtype or shape TypeError.  All camera forms may carry camera_lens, float32 [B, T, 12] (data.camera_lens): one camera per frame,
     for both eyes.  In both, camera_frame may be replaced by ONE of camera_frame_bgr [B, T, IH, IW, 3 | 4], camera_frame_nv12 /
     camera_frame_i420 [B, T, IH*3/2, IW] or camera_frame_yuyv [B, T, IH, IW, 2] (EYE_FRAME_KEYS; two frame keys raise ValueError,
     odd sizes too): that tensor is then returned -- its shape[:2] and device are the batch's whatever the format."""
+    if FACE_LANDMARKS_KEY in batch or FACE_RIG_KEY in batch:
+        if FACE_LANDMARKS_KEY not in batch or FACE_RIG_KEY not in batch:
+            raise ValueError('the face-landmark form needs %s and %s: found only %s' % (
+                FACE_LANDMARKS_KEY, FACE_RIG_KEY, FACE_LANDMARKS_KEY if FACE_LANDMARKS_KEY in batch else FACE_RIG_KEY))
+        clash = [k_ for k_ in (EYE_POSE_KEY,) + EYE_PATCH_KEYS + EYE_POSE_DERIVED + FACE_DERIVED if k_ in batch]
+        if clash:
+            raise ValueError('%s + %s derive %s and stand in for %s and %s: found %s beside them' % (
+                FACE_LANDMARKS_KEY, FACE_RIG_KEY, ', '.join(EYE_POSE_DERIVED + FACE_DERIVED), EYE_POSE_KEY, ' / '.join(EYE_PATCH_KEYS),
+                ', '.join(clash)))
+        if camera_frame_key(batch) is None:
+            raise ValueError('%s goes with camera_frame: the patches are cut from it' % FACE_LANDMARKS_KEY)
+        frames = _camera_frame(batch)
+        lm, rig = batch[FACE_LANDMARKS_KEY], batch[FACE_RIG_KEY]
+        B, T = frames.shape[:2]
+        if (not torch.is_tensor(lm) or lm.dtype != torch.float32 or lm.dim() != 4 or tuple(lm.shape[:2]) != (B, T)
+                or not 4 <= lm.shape[2] <= 68 or lm.shape[3] not in (2, 3)):
+            raise TypeError('%s must be float32 %s with 4 <= L <= 68, got %s %s' % (
+                FACE_LANDMARKS_KEY, (B, T, 'L', '2 | 3'), getattr(lm, 'dtype', type(lm)), tuple(getattr(lm, 'shape', ()))))
+        if not torch.is_tensor(rig) or rig.dtype != torch.float32 or tuple(rig.shape) != (B, 12 + 3 * lm.shape[2]):
+            raise TypeError('%s must be float32 %s (one row per sequence), got %s %s' % (
+                FACE_RIG_KEY, (B, 12 + 3 * lm.shape[2]), getattr(rig, 'dtype', type(rig)), tuple(getattr(rig, 'shape', ()))))
+        _camera_lens(batch, frames)
+        return frames
     if EYE_POSE_KEY in batch:
         clash = [k_ for k_ in EYE_PATCH_KEYS + EYE_POSE_DERIVED if k_ in batch]
         if clash:
@@ -125,14 +162,43 @@ def eye_input(batch):
     return frames
 
 
-def eye_pose_batch(batch, config=None):
+def _face_landmark_batch(batch, config, face_state, reset, lengths):
+    """eye_pose_batch for camera_frame + face_landmarks + face_rig: ONE eve_face_pose_solve launch (every sequence one wavefront,
+    every frame warm-started from the one before, frame 0 from face_state where that holds a pose) and ONE
+    eve_eye_pose_normalize_rt launch that continues from the float32 head_R / head_t just written."""
+    from . import data
+    frames = eye_input(batch)
+    B, T = frames.shape[:2]
+    k = default_kernels()
+    rig = batch[FACE_RIG_KEY].contiguous()
+    head_R, head_t, rms, solved = k.face_pose_solve(batch[FACE_LANDMARKS_KEY].contiguous(), rig, lengths, face_state, reset)
+    o, R, warp, h, valid = k.eye_pose_normalize_rt(rig, head_R, head_t, solved, data.eye_patch_hw(config))
+    d = {k_: v for k_, v in batch.items() if k_ not in (FACE_LANDMARKS_KEY, FACE_RIG_KEY)}
+    d['head_R'], d['head_t'], d['face_reproj_rms'] = head_R, head_t, rms
+    for e, side in enumerate(('left', 'right')):
+        d[side + '_o'] = o[e].view(B, T, 3)
+        d[side + '_R'] = R[e].view(B, T, 3, 3)
+        d[side + '_eye_warp'] = warp[e].view(B, T, 3, 3)
+        d[side + '_h'] = h[e].view(B, T, 2)
+    d['pose_valid'] = valid.view(2, B, T).permute(1, 2, 0) != 0
+    return d
+
+
+def eye_pose_batch(batch, config=None, face_state=None, reset=None, lengths=None):
     """The pose form turned into the warp form: a batch without eye_pose comes back as it is; one with it is checked (eye_input)
     and copied, and in the copy eye_pose is replaced by what ONE eve_eye_pose_normalize launch derives from the rows for the
     config's eyes_size: head_R [B, T, 3, 3], <side>_o [B, T, 3], <side>_R [B, T, 3, 3], <side>_eye_warp [B, T, 3, 3] (inv(W): what
     the eye-warp kernels take), <side>_h [B, T, 2] and pose_valid, bool [B, T, 2] (left, right).  An eye whose pose is not usable
     (a NaN, a head behind the camera, ...) has pose_valid False, a zero warp -- so a black patch -- R = I, o = 0 and h = 0;
     pose_valid is reported and folded into nothing.  Every entry point that takes the eyes calls this once, before anything
-    reads a derived key; the copy holds no eye_pose, so the modules below it see the warp form."""
+    reads a derived key; the copy holds no eye_pose, so the modules below it see the warp form.
+    The face-landmark form (camera_frame + face_landmarks + face_rig) is turned into the warp form the same way, with the head
+    pose solved on the device first (_face_landmark_batch): the copy additionally gains head_t [B, T, 3] and face_reproj_rms
+    [B, T] (pixels), and pose_valid is False for both eyes of a frame with no solution.  face_state: None (every sequence starts
+    cold) or the float64 [B, 13] carried pose of an EVEStream, updated in place; reset, lengths: None or int32 [B] device tensors
+    (flagged sequences start cold; frames past a sequence's count are not solved).  The three are read by this form only."""
+    if FACE_LANDMARKS_KEY in batch or FACE_RIG_KEY in batch:
+        return _face_landmark_batch(batch, config, face_state, reset, lengths)
     if EYE_POSE_KEY not in batch:
         return batch
     from . import data

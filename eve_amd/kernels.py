@@ -592,6 +592,65 @@ class HipKernels(object):
                                                  self._p(valid), self._stream()))
         return head_R, o, R, warp, h, valid
 
+    def eye_pose_normalize_rt(self, rows, head_R, head_t, valid_in, out_hw):
+        """The same normalisation from a head_R and a translation that exist already: rows float32 [S, >= 12], one per sequence,
+        whose first 12 entries are (fx, fy, cx, cy, left eye centre, right eye centre, focal_norm, distance_norm) -- a face rig
+        as it is -- head_R float32 [S, T, 3, 3], head_t float32 [S, T, 3], valid_in uint8 [S, T] or None (ANDed into valid) ->
+        (o [2,N,3], R [2,N,3,3], warp [2,N,3,3], h [2,N,2] float32, valid uint8 [2,N]) for the N = S * T frames, eye-major like
+        eye_pose_normalize (include/eve_hip.h eve_eye_pose_normalize_rt)."""
+        ok = lambda t, dtype: torch.is_tensor(t) and t.dtype == dtype
+        if not ok(head_R, torch.float32) or head_R.dim() != 4 or tuple(head_R.shape[2:]) != (3, 3):
+            raise TypeError('eye_pose_normalize_rt: head_R must be float32 [S, T, 3, 3], got %s %s' % (
+                getattr(head_R, 'dtype', type(head_R)), tuple(getattr(head_R, 'shape', ()))))
+        S, T = head_R.shape[:2]
+        if not ok(rows, torch.float32) or rows.dim() != 2 or rows.shape[0] != S or rows.shape[1] < 12:
+            raise TypeError('eye_pose_normalize_rt: rows must be float32 [%d, >= 12], got %s %s' % (
+                S, getattr(rows, 'dtype', type(rows)), tuple(getattr(rows, 'shape', ()))))
+        if not ok(head_t, torch.float32) or tuple(head_t.shape) != (S, T, 3):
+            raise TypeError('eye_pose_normalize_rt: head_t must be float32 [%d, %d, 3], got %s %s' % (
+                S, T, getattr(head_t, 'dtype', type(head_t)), tuple(getattr(head_t, 'shape', ()))))
+        if valid_in is not None and (not ok(valid_in, torch.uint8) or tuple(valid_in.shape) != (S, T)):
+            raise TypeError('eye_pose_normalize_rt: valid_in must be uint8 [%d, %d], got %s %s' % (
+                S, T, getattr(valid_in, 'dtype', type(valid_in)), tuple(getattr(valid_in, 'shape', ()))))
+        if not all(t.is_contiguous() for t in (rows, head_R, head_t) + (() if valid_in is None else (valid_in,))):
+            raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        N, (OH, OW) = S * T, (int(out_hw[0]), int(out_hw[1]))
+        new = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=rows.device)
+        o, R, warp, h, valid = new(2, N, 3), new(2, N, 3, 3), new(2, N, 3, 3), new(2, N, 2), new(2, N, dtype=torch.uint8)
+        self._ck(self.lib.eve_eye_pose_normalize_rt(N, T, self._p(rows), rows.shape[1], self._p(head_R), self._p(head_t),
+                                                    None if valid_in is None else self._p(valid_in), OH, OW, self._p(o), self._p(R),
+                                                    self._p(warp), self._p(h), self._p(valid), self._stream()))
+        return o, R, warp, h, valid
+
+    def face_pose_solve(self, landmarks, rig, lengths=None, state=None, reset=None):
+        """Head pose from face landmarks, one wavefront per sequence, every frame warm-started from the one before: landmarks
+        float32 [S, T, L, 2 | 3] = pixel (u, v[, w]) of the undistorted image, 4 <= L <= 68; rig float32 [S, 12 + 3L] (data.face_rig);
+        lengths None or int32 [S] (frames past it are not solved); state None or float64 [S, 13] = (R, t, has_pose), read and
+        UPDATED IN PLACE; reset None or int32 [S] -> (head_R [S,T,3,3], head_t [S,T,3], reproj_rms [S,T] float32, valid uint8
+        [S,T]).  An invalid frame has head_R = I, head_t = 0, reproj_rms = 0 (include/eve_hip.h eve_face_pose_solve)."""
+        ok = lambda t, dtype: torch.is_tensor(t) and t.dtype == dtype
+        if not ok(landmarks, torch.float32) or landmarks.dim() != 4 or landmarks.shape[3] not in (2, 3):
+            raise TypeError('face_pose_solve: landmarks must be float32 [S, T, L, 2 | 3], got %s %s' % (
+                getattr(landmarks, 'dtype', type(landmarks)), tuple(getattr(landmarks, 'shape', ()))))
+        S, T, L, C = landmarks.shape
+        if not ok(rig, torch.float32) or tuple(rig.shape) != (S, 12 + 3 * L):
+            raise TypeError('face_pose_solve: rig must be float32 [%d, %d], got %s %s' % (
+                S, 12 + 3 * L, getattr(rig, 'dtype', type(rig)), tuple(getattr(rig, 'shape', ()))))
+        for name, t, dtype, shape in (('lengths', lengths, torch.int32, (S,)), ('state', state, torch.float64, (S, 13)),
+                                      ('reset', reset, torch.int32, (S,))):
+            if t is not None and (not ok(t, dtype) or tuple(t.shape) != shape):
+                raise TypeError('face_pose_solve: %s must be %s %s, got %s %s' % (
+                    name, str(dtype).replace('torch.', ''), list(shape), getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ()))))
+        given = [t for t in (landmarks, rig, lengths, state, reset) if t is not None]
+        if not all(t.is_contiguous() for t in given):
+            raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        new = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=landmarks.device)
+        head_R, head_t, rms, valid = new(S, T, 3, 3), new(S, T, 3), new(S, T), new(S, T, dtype=torch.uint8)
+        opt = lambda t: None if t is None else self._p(t)
+        self._ck(self.lib.eve_face_pose_solve(S, T, L, C, self._p(landmarks), self._p(rig), opt(lengths), opt(state), opt(reset),
+                                              self._p(head_R), self._p(head_t), self._p(rms), self._p(valid), self._stream()))
+        return head_R, head_t, rms, valid
+
     # ------------------------------------------------------------------ gaze geometry / heat-maps / soft-argmax
     def _flat32(self, t, shape, what):
         t = t.contiguous()

@@ -37,7 +37,7 @@ kernel) need invalidate(), as the modules need invalidate_packs().
 import numpy as np
 import torch
 
-from .eye_net import eye_input
+from .eye_net import eye_input, has_pose_form
 from .kernels import default_kernels
 
 _WARMUP_STREAMS = {}
@@ -67,6 +67,9 @@ class EVEStream(object):
         self._pose_gate = torch.ones((1,), dtype=torch.bool, device=self.device)     # False: a masked step ANDs pose_valid into its mask
         self._pose_gate_host = True
         self._pending = None                     # host bool [B]: resets requested for the next step
+        # the face-landmark form's carried head pose, float64 (R row-major, t, has_pose) per stream: eve_face_pose_solve reads and
+        # writes it inside the step (and the graph), and clears it where the reset flag is set
+        self._face_pose = torch.zeros((B, 13), dtype=torch.float64, device=self.device)
         self._graphs = {}
         self._graphs_key = None
 
@@ -129,6 +132,25 @@ class EVEStream(object):
                     dst[..., :C].copy_(src.permute(0, 2, 3, 1))
         self._pending = None
 
+    def get_head_pose(self):
+        """The head pose the face-landmark form carries from one step to the next (fresh tensors): R float64 [B, 3, 3], t float64
+        [B, 3] and has_pose bool [B] -- False where the stream's next frame starts cold (no frame yet, a reset applied, a last
+        frame without a solution).  Resets not yet applied by a step are not reflected.  get_state() / set_state() do not hold
+        it: a resumed recording re-acquires the pose from a cold start within one frame."""
+        s = self._face_pose
+        return s[:, :9].reshape(-1, 3, 3).clone(), s[:, 9:12].clone(), s[:, 12] != 0
+
+    def set_head_pose(self, R, t, has_pose=True):
+        """Load a carried head pose in get_head_pose()'s layout: R [B, 3, 3], t [B, 3] (converted to float64), has_pose a bool or B
+        of them.  The next face-landmark step starts stream b from (R[b], t[b]) where has_pose[b], cold elsewhere."""
+        B = self.num_streams
+        R = torch.as_tensor(R, dtype=torch.float64).to(self.device)
+        t = torch.as_tensor(t, dtype=torch.float64).to(self.device)
+        if tuple(R.shape) != (B, 3, 3) or tuple(t.shape) != (B, 3):
+            raise ValueError('set_head_pose: R must be [%d, 3, 3] and t [%d, 3], got %s and %s' % (B, B, tuple(R.shape), tuple(t.shape)))
+        has = torch.as_tensor(has_pose, dtype=torch.bool).to(self.device).expand(B)
+        self._face_pose.copy_(torch.cat([R.reshape(B, 9), t, has.to(torch.float64)[:, None]], dim=1))
+
     # ------------------------------------------------------------------ steps
     def _upload_resets(self):
         if self._pending is None or not self._pending.any():
@@ -186,6 +208,10 @@ class EVEStream(object):
             self._pose_gate.fill_(self._pose_gate_host)              # a device value: the captured graphs read it, the host never waits
 
     def _run(self, chunk, return_heatmaps, ragged=False, eye_mask=None, masked=False):
+        if 'face_landmarks' in chunk:            # the face-landmark form: the carried head pose goes along
+            return self.model._predict_sequence(chunk, self._eye, self._ref, reset=self._flags, return_heatmaps=return_heatmaps,
+                                                lengths=self._lengths if ragged else None, masked=masked, eye_mask=eye_mask,
+                                                pose_gate=self._pose_gate if masked else None, face_state=self._face_pose)
         if masked:
             return self.model._predict_sequence(chunk, self._eye, self._ref, reset=self._flags, return_heatmaps=return_heatmaps,
                                                 lengths=self._lengths if ragged else None, masked=True, eye_mask=eye_mask,
@@ -228,6 +254,19 @@ class EVEStream(object):
         pose_valid, bool [B, Tc, 2] (left, right): False where a pose was not usable (a NaN, a head behind the camera, ...), whose
         eye then got a black patch, R = I, o = 0 and h = 0.  pose_valid is reported, not folded into any other validity -- unless
         skip_invalid_pose (below) asks for it.
+
+        Or as the face-landmark form, which needs no solvePnP on the host: camera_frame plus face_landmarks, float32 [B, Tc, L, 2 | 3]
+        = pixel (u, v[, w]) of the tracker's L landmarks in the undistorted image (w an optional confidence, 0 drops the point;
+        4 <= L <= 68), plus face_rig, float32 [B, 12 + 3L] rows from data.face_rig, ONE PER STREAM (camera matrix, eye centres,
+        virtual camera, the L model points).  One eve_face_pose_solve launch inside the step and the graph solves every frame's
+        head pose -- a wavefront per stream, each frame started from the one before, the chunk's first frame from the pose this
+        EVEStream carries in a float64 [B, 13] buffer (get_head_pose / set_head_pose; reset() clears it through the same device
+        flags, inside the same graph) -- and eve_eye_pose_normalize_rt derives what eye_pose derives.  The result gains
+        pose_valid as above (False for both eyes of a frame without a solution: a NaN, fewer than 4 weighted points, no
+        convergence), head_t [B, Tc, 3] and face_reproj_rms [B, Tc] (pixels).  lengths, eye_mask, skip_invalid_pose, camera_lens and
+        the pixel-format keys combine with it; frames past lengths[b] are not solved and leave the carried pose alone.  A split
+        of a clip into chunks gives the poses of one pass over the clip, bit for bit.  Not offered: landmarks of the distorted
+        frame (undistort the L points; camera_lens applies to the pixels), outlier rejection beyond the weights, per-frame rigs.
 
         screen_frame is float [B, Tc, 3, H, W] at the configured screen size, uint8 [B, Tc, H, W, 3] at that size, or a live
         capture as it comes off the desktop: uint8 [B, Tc, IH, IW, 3 | 4] at any resolution from the screen size up to 16 843 009
@@ -288,7 +327,7 @@ class EVEStream(object):
             raise ValueError('chunk has %d streams, the EVEStream %d' % (B, self.num_streams))
         ragged = lengths is not None
         masked = eye_mask is not None or bool(skip_invalid_pose)
-        if skip_invalid_pose and 'eye_pose' not in chunk:
+        if skip_invalid_pose and not has_pose_form(chunk):
             raise ValueError('step: skip_invalid_pose needs the pose form (eye_pose in the chunk): there is no pose_valid to fold in')
         if ragged:
             lengths = self._host_lengths(lengths, Tc)
@@ -296,7 +335,7 @@ class EVEStream(object):
             eye_mask = self._eye_mask(eye_mask, Tc)
         if ragged:
             self._upload_lengths(lengths)
-        if masked and 'eye_pose' in chunk:
+        if masked and has_pose_form(chunk):
             self._set_pose_gate(bool(skip_invalid_pose))
         self._upload_resets()
         with torch.no_grad():
@@ -359,10 +398,11 @@ class EVEStream(object):
             side = _WARMUP_STREAMS[dev_index] = torch.cuda.Stream(device=dev_index)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            snap = [t.clone() for t in self._state_tensors()]
+            carried = self._state_tensors() + [self._face_pose]
+            snap = [t.clone() for t in carried]
             for _ in range(2):
                 self._run(static, return_heatmaps, ragged, eye_mask, masked)
-            for t, s_ in zip(self._state_tensors(), snap):
+            for t, s_ in zip(carried, snap):
                 t.copy_(s_)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()

@@ -860,6 +860,72 @@ int eve_eye_warp_fmt_to_stem(int dtype /* EVE_DT_BF16 | EVE_DT_F16 */, int forma
  * launch: a null pointer, N < 1 or N >= 2^30, OH or OW outside 1..4096.                                                         */
 int eve_eye_pose_normalize(long long N, const float* pose, int OH, int OW, float* head_R, float* o, float* R, float* warp, float* h,
                            uint8_t* valid, eve_stream_t stream);
+/* The stages 2..6 above from a head_R and a translation that exist already (eve_face_pose_solve's, say), N frames, both eyes: frame n
+ * reads row n / frames_per_row of `rows` [.][row_stride] float, whose first 12 entries are (fx, fy, cx, cy, l0, l1, l2, q0, q1, q2,
+ * focal_norm, distance_norm) -- a face rig's head, or one row per frame with frames_per_row = 1 -- head_R [N][9] and head_t [N][3]
+ * float.  H = head_R widened, t = head_t widened, and everything from stage 2 on is the contract above, operation for operation
+ * (one device function serves both kernels); no head_R is written.  valid_e additionally needs the 12 row entries, head_R and
+ * head_t finite and, where valid_in [N] uint8 is not NULL, valid_in[n] != 0.  Outputs and layout as above (o, R, warp, h, valid).
+ * Refused without a launch: a null pointer other than valid_in, N < 1 or N >= 2^30, frames_per_row < 1, row_stride < 12, OH or
+ * OW outside 1..4096.  Kernel name eye_pose_normalize_rt_kernel.  (Additive: ABI v10.)                                        */
+int eve_eye_pose_normalize_rt(long long N, int frames_per_row, const float* rows, int row_stride, const float* head_R, const float* head_t,
+                              const uint8_t* valid_in /* may be NULL */, int OH, int OW, float* o, float* R, float* warp, float* h,
+                              uint8_t* valid, eve_stream_t stream);
+/* Head pose from face landmarks: a weighted perspective-n-point solve for S sequences of T frames, in place of one cv2.solvePnP per
+ * frame on the host.  One wavefront per sequence walks its frames in time order, each warm-started from the one before.
+ *   landmarks [S][T][L][landmark_cols] float, landmark_cols 2 or 3: pixel (u, v[, w]) in the UNDISTORTED image that fx..cy describe;
+ *             w is a confidence, 1.0 without the column; a point is used iff w > 0.  4 <= L <= 68.
+ *   rig       [S][12 + 3L] float, one row per sequence: (fx, fy, cx, cy, left eye centre, right eye centre, focal_norm,
+ *             distance_norm, X_0 .. X_{L-1}), the model points X_l in the head model's frame and length unit.  Entries 4..11 are
+ *             only checked for being finite here; eve_eye_pose_normalize_rt reads them (rows = rig, row_stride = 12 + 3L).
+ *   lengths   NULL or [S] int, clamped to 0..T: frames f >= lengths[s] are not solved, are reported invalid and leave the carried
+ *             pose alone.
+ *   state     NULL or [S][13] double = (R row-major, t, has_pose), read and written in place: frame 0 starts from it where
+ *             has_pose != 0 and reset[s] == 0.  Afterwards (R, t, 1.0) of the last solved frame if that was valid, (I, 0, 0.0) if it
+ *             was not or if reset[s] != 0 and no frame was solved; untouched if nothing was solved and no reset was flagged.
+ *   reset     NULL or [S] int (read only).
+ * Contract: float64, every operation rounded on its own (no contraction), only + - * / sqrt, in exactly this association; every
+ * sum over the landmarks is taken in landmark order 0 .. L-1 starting from 0.0 (tests/face_pose_ref.py restates all of it):
+ *   x = (u - cx) / fx, y = (v - cy) / fy.
+ *   eval(R, t), per used point: q_i = (R[i][0]*X0 + R[i][1]*X1) + R[i][2]*X2, P = q + t, iz = 1.0 / P2, px = P0 / P2, py = P1 / P2,
+ *     ex = px - x, ey = py - y, a = px*iz, b = py*iz,
+ *     Jx = (-(a*q1), iz*q2 + a*q0, -(iz*q1), iz, 0.0, -a),  Jy = (-(iz*q2 + b*q1), b*q0, iz*q0, 0.0, iz, -b)
+ *     -- the derivatives of (px, py) by (d, dt) of the update R <- C(d) R, t <- t + dt at d = 0 -- and the 29 sums of
+ *     A_ij = w*(Jx_i*Jx_j + Jy_i*Jy_j) for i <= j row-major (21), g_i = w*(Jx_i*ex + Jy_i*ey) (6), cost = w*(ex*ex + ey*ey),
+ *     pix = w*((fx*ex)*(fx*ex) + (fy*ey)*(fy*ey)); an unused point adds 0.0 to each.  behind = a used point with not P2 > 0.
+ *   Initial pose: the previous frame's float64 solution if that frame was valid, else the carried state as above, else cold:
+ *     sw = sum w, (mx, my, MX, MY, MZ) = sum(w*(x, y, X0, X1, X2)) / sw, sl = sum w*((x-mx)*(x-mx) + (y-my)*(y-my)),
+ *     sm = sum w*((X0-MX)*(X0-MX) + (X1-MY)*(X1-MY)); not (sl > 0 && sm > 0): invalid; Z = sqrt(sm / sl), R = I,
+ *     t = (mx*Z - MX, my*Z - MY, Z - MZ).
+ *   lam = 1e-3, accepted = 0, S = eval(R, t); behind or a cost that is not finite: invalid.  Then, repeated:
+ *     M = A with M_ii = A_ii + lam*A_ii; Cholesky, thr = 0: for j: s = M_jj; for k < j: s = s - L_jk*L_jk; not s > thr*M_jj: the
+ *     pivot fails (invalid); L_jj = sqrt(s); for i > j: s = M_ij; for k < j: s = s - L_ik*L_jk; L_ij = s / L_jj.
+ *     y_i = (-g_i - sum_{k<i} L_ik*y_k) / L_ii, d_i = (y_i - sum_{k>i} L_ki*d_k) / L_ii (subtracted one by one, k rising; i falling).
+ *     a = 0.5*d[0:3], s = (a0*a0 + a1*a1) + a2*a2, den = 1.0 + s, e = 1.0 - s, the Cayley map (I - [a]x)^-1 (I + [a]x) in closed form
+ *       C = [[(e + 2.0*(a0*a0))/den, (2.0*(a0*a1 - a2))/den, (2.0*(a0*a2 + a1))/den],
+ *            [(2.0*(a0*a1 + a2))/den, (e + 2.0*(a1*a1))/den, (2.0*(a1*a2 - a0))/den],
+ *            [(2.0*(a0*a2 - a1))/den, (2.0*(a1*a2 + a0))/den, (e + 2.0*(a2*a2))/den]],
+ *     Rc[i][j] = (C[i][0]*R[0][j] + C[i][1]*R[1][j]) + C[i][2]*R[2][j], tc = t + d[3:6], Sc = eval(Rc, tc).
+ *     small = every d_i finite && max|d_i| < 1e-10 * max(1.0, max|t_i|) (t before the update).
+ *     Accepted iff every d_i finite && !behind && cost_c <= cost: (R, t, S) = (Rc, tc, Sc), lam = lam / 10.0, ++accepted; small:
+ *     converged; else accepted == 32: invalid.  Rejected: small: converged with the pose as it was; else lam = lam * 10.0,
+ *     lam > 1e12: invalid.
+ *   Converged: one Cholesky of the undamped A with thr = 1e-10; a failed pivot: invalid -- the landmarks do not determine the pose
+ *     (collinear model points, say; damping alone would hide that).  reproj_rms = sqrt(pix / sw), in pixels.
+ *   Invalid before any of it: a rig entry or a landmark entry (u, v, w; used or not) that is not finite, fx <= 0 or fy <= 0, fewer
+ *     than 4 used points.
+ * Outputs per frame: head_R [S][T][9] and head_t [S][T][3] float, rounded ONCE from float64; reproj_rms [S][T] float; valid [S][T]
+ * uint8.  An invalid frame has head_R = I, head_t = 0, reproj_rms = 0 and the next frame starts cold.  The carried state stays
+ * float64, so T frames in one call and the same frames in several calls through `state` give the same bits.  The Cayley update
+ * keeps R orthogonal up to rounding (about 1e-16 per accepted step); it is not re-orthonormalised.  Each frame of a sequence
+ * depends on the one before: the launch takes T times one frame's latency, S sequences side by side.  Kernel name
+ * face_pose_solve_kernel.  Refused without a launch: S < 1, T < 1, S * T >= 2^31, L outside 4..68, landmark_cols other than 2 or 3,
+ * a null landmarks, rig or output pointer.  Not offered: landmarks of a distorted image, RANSAC or any outlier rejection beyond the
+ * weights, an rvec, gradients, per-frame camera matrices; a planar model runs, but which of its two minima is found is not
+ * promised.  (Additive: ABI v10.)                                                                                              */
+int eve_face_pose_solve(long long S, int T, int L, int landmark_cols, const float* landmarks, const float* rig,
+                        const int* lengths /* may be NULL */, double* state /* may be NULL */, const int* reset /* may be NULL */,
+                        float* head_R, float* head_t, float* reproj_rms, uint8_t* valid, eve_stream_t stream);
 
 #ifdef __cplusplus
 }

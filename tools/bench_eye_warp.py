@@ -3,7 +3,8 @@
 and of one EVEStream step fed whole camera frames next to the same step fed pre-cut uint8 patches.
 
     python tools/bench_eye_warp.py [--patches 64] [--size 1920x1080] [--iters 500] [--rounds 5] [--shapes 1x1 8x4 32x2]
-                                   [--steps 50] [--dtype bf16] [--lens] [--pose] [--format nv12] [--markdown profiles/table.md]
+                                   [--steps 50] [--dtype bf16] [--lens] [--pose] [--format nv12] [--landmarks]
+                                   [--markdown profiles/table.md]
 
 Part 1, per launch, the four routes interleaved in one process (the median over the rounds of events around `iters` calls):
     warp_nchw / warp_stem   N patches of 128 x 128 cut from N frames of the given size, each by its own rotated, scaled warp with a
@@ -26,7 +27,17 @@ Part 2, per EVEStream step under graph replay (refine_net config): `camera` feed
 the uint8 [B, Tc, 128, 128, 3] patch pair.  The camera step also copies B * Tc whole frames into the graph's input buffer.  With
 --lens a third stream, `lens`, feeds the camera keys plus camera_lens.  With --pose another stream, `pose`, feeds camera_frame + eye_pose
 and none of the keys the rows derive (warps, <side>_h, <side>_o, <side>_R, head_R): one more launch inside the graph.  With --format
-a stream `fmt` feeds camera_frame_<format> in place of camera_frame: fewer bytes copied into the graph, the taps converted inside."""
+a stream `fmt` feeds camera_frame_<format> in place of camera_frame: fewer bytes copied into the graph, the taps converted inside.
+
+--landmarks (implies --pose): the face-landmark form.  Before part 1, eve_face_pose_solve alone on 32 x 2 and 32 x 30 frames at L = 6
+and L = 68 into preallocated outputs: `cold` without a state (every sequence's first frame starts from the closed-form guess, the
+later ones from the frame before), `warm` with a carried state that holds the pose of the chunk's last frame (every frame warm), and
+`all_cold` on T = 1 chunks of the same sequences for the price of a cold frame alone; beside them the accepted-step counts of
+the first 8 sequences, taken from the contract in numpy (tests/face_pose_ref.py: the same arithmetic, so the same counts), and the
+fraction of frames that got a solution (a frame that reaches the contract's cap of 32 accepted steps has none).  In
+part 2 a stream `face` feeds camera_frame + face_landmarks [B, Tc, 68, 3] + face_rig and none of the derived keys, next to `pose`.
+The eye_pose step of ANOTHER checkout (the parent commit's) is measured by running that checkout's own `--pose --shapes 32x2` in
+alternating rounds with this one, process by process; this file only measures the tree it lies in."""
 import argparse
 import json
 import math
@@ -85,6 +96,63 @@ def pose_rows(n, IH, IW, seed):
     rows = [[f, f, IW / 2, IH / 2] + list(g.uniform(-0.3, 0.3, 3)) + [g.uniform(-60, 60), g.uniform(-40, 40), g.uniform(500, 700)] +
             [-32.0, -35.0, 25.0, 32.0, -35.0, 25.0, f, 600.0] for _ in range(n)]
     return torch.tensor(np.array(rows), dtype=torch.float32)
+
+
+def face_sequences(B, Tc, L, IH, IW, seed):
+    """Landmarks and rigs of B frontal heads 500..700 mm in front of pose_rows' camera, moving by up to 2 degrees and 4 mm a frame,
+    with the noise of tests/face_pose_ref.py's cases (1 px at f = 1000) -> numpy (landmarks [B, Tc, L, 3], rig [B, 12 + 3L])."""
+    sys.path.insert(0, os.path.join(REPO, 'tests'))
+    import face_pose_ref as fr
+    f = 1400.0 * IW / 1920.0
+    return fr.sequences(B, Tc, L, seed, weights=True, K=(f, f, IW / 2, IH / 2), frontal=True, focal_norm=f, step_deg=2.0, step_mm=4.0,
+                        noise=f / 1000.0)
+
+
+def solve_launches(args, IH, IW):
+    """eve_face_pose_solve alone (see the module docstring) -> rows of dicts."""
+    import ctypes
+    sys.path.insert(0, os.path.join(REPO, 'tests'))
+    import face_pose_ref as fr
+    k = default_kernels()
+    rows = []
+    for S_, T_ in ((32, 2), (32, 30)):
+        for L in (6, 68):
+            lm_np, rig_np = face_sequences(S_, T_, L, IH, IW, seed=L)
+            ref = fr.solve(lm_np[:8], rig_np[:8])
+            lm, rig = torch.from_numpy(lm_np).cuda(), torch.from_numpy(rig_np).cuda()
+            lm1 = lm[:, :1].contiguous()
+            outs = [torch.empty((S_, T_, n), device='cuda') for n in (9, 3, 1)] + [torch.empty((S_, T_), dtype=torch.uint8, device='cuda')]
+            state = torch.zeros((S_, 13), dtype=torch.float64, device='cuda')
+            ptrs = [ctypes.c_void_p(t.data_ptr()) for t in outs]
+            stream = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+            def launch(T=T_, lm_=lm, st=None):
+                status = k.lib.eve_face_pose_solve(S_, T, L, 3, ctypes.c_void_p(lm_.data_ptr()), ctypes.c_void_p(rig.data_ptr()), None,
+                                                   None if st is None else ctypes.c_void_p(st.data_ptr()), None, *ptrs, stream())
+                assert status == 0, k.lib.eve_last_error()
+            routes = {'cold': lambda: launch(), 'warm': lambda: launch(st=state), 'all_cold': lambda: launch(T=1, lm_=lm1)}
+            for fn in routes.values():
+                for _ in range(5):
+                    fn()
+            torch.cuda.synchronize()
+            launch()
+            torch.cuda.synchronize()
+            solved = float(outs[3].float().mean())       # a frame that reaches the cap of 32 accepted steps has no solution
+            times = {name: [] for name in routes}
+            for _ in range(args.rounds):
+                for name, fn in routes.items():
+                    times[name].append(device_ms(fn, args.iters))
+            res = {'S': S_, 'T': T_, 'L': L, 'iters': args.iters, 'rounds': args.rounds, 'kernel': k.lib.eve_last_kernel().decode(),
+                   'frames_solved': round(solved, 4), 'frames_solved_contract_first_8': round(float(ref['valid'].mean()), 4),
+                   'accepted_cold_first_frame': [int(ref['accepted'][:, 0].min()), int(ref['accepted'][:, 0].max())],
+                   'accepted_warm_frames': [int(ref['accepted'][:, 1:].min()), int(ref['accepted'][:, 1:].max())]}
+            for name, t in times.items():
+                res[name + '_us'] = round(1e3 * median(t), 2)
+                res[name + '_us_min_max'] = [round(1e3 * min(t), 2), round(1e3 * max(t), 2)]
+            res['warm_us_per_frame'] = round(res['warm_us'] / T_, 2)
+            rows.append(res)
+            print(json.dumps(res), flush=True)
+    return rows
 
 
 def format_frames(fmt, lead, IH, IW, gen=None, device='cuda'):
@@ -231,6 +299,11 @@ def stream_steps(args, IH, IW):
             from eve_amd.eye_net import EYE_POSE_DERIVED
             streams['pose'] = (eve_amd.EVEStream(model, B), dict({k_: v for k_, v in cam.items() if k_ not in EYE_POSE_DERIVED},
                                                                  eye_pose=pose_rows(B * Tc, IH, IW, seed=B).view(B, Tc, 18).cuda()))
+        if args.landmarks:
+            from eve_amd.eye_net import EYE_POSE_DERIVED
+            lm, rig = face_sequences(B, Tc, 68, IH, IW, seed=B)
+            streams['face'] = (eve_amd.EVEStream(model, B), dict({k_: v for k_, v in cam.items() if k_ not in EYE_POSE_DERIVED},
+                                                                 face_landmarks=torch.from_numpy(lm).cuda(), face_rig=torch.from_numpy(rig).cuda()))
         if args.format:
             fmt_chunk = {k_: v for k_, v in cam.items() if k_ != 'camera_frame'}
             fmt_chunk['camera_frame_' + args.format] = format_frames(args.format, (B, Tc), IH, IW, gen=g)
@@ -253,6 +326,9 @@ def stream_steps(args, IH, IW):
         if args.pose:
             res['pose_minus_camera_ms'] = round(res['pose_step_ms'] - res['camera_step_ms'], 4)
         res['camera_frame_MB_copied'] = round(B * Tc * IH * IW * 3 / 1e6, 1)
+        if args.landmarks:
+            res['face_minus_pose_ms'] = round(res['face_step_ms'] - res['pose_step_ms'], 4)
+            res['face_pose_valid'] = round(float(streams['face'][0].step(streams['face'][1])['pose_valid'].float().mean()), 4)
         if args.format:
             res['fmt_minus_camera_ms'] = round(res['fmt_step_ms'] - res['camera_step_ms'], 4)
             res['fmt_frame_MB_copied'] = round(fmt_chunk['camera_frame_' + args.format].numel() / 1e6, 1)
@@ -276,12 +352,16 @@ def main():
     ap.add_argument('--pose', action='store_true', help='also time eve_eye_pose_normalize and an EVEStream step with eye_pose rows')
     ap.add_argument('--format', default=None, choices=['bgr', 'nv12', 'i420', 'yuyv'],
                     help='also time the launches and an EVEStream step on frames in this layout, and convert-then-warp beside them')
+    ap.add_argument('--landmarks', action='store_true',
+                    help='also time eve_face_pose_solve and an EVEStream step with face_landmarks + face_rig (implies --pose)')
     ap.add_argument('--markdown', default=None, help='also write the tables to this file')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit('bench_eye_warp: no GPU (a time is only measured on one)')
     IW, IH = (int(v) for v in args.size.lower().split('x'))
+    args.pose = args.pose or args.landmarks
     with torch.no_grad():
+        solves = solve_launches(args, IH, IW) if args.landmarks else []
         one = launches(args, IH, IW)
         print(json.dumps(one), flush=True)
         rows = stream_steps(args, IH, IW) if args.shapes else []
@@ -322,6 +402,20 @@ def main():
                 r['B'], r['Tc'], r['fmt_step_ms'], r['fmt_step_ms_min_max'][0], r['fmt_step_ms_min_max'][1], r['camera_step_ms'],
                 r['camera_step_ms_min_max'][0], r['camera_step_ms_min_max'][1], r['fmt_minus_camera_ms'], r['fmt_frame_MB_copied'],
                 r['camera_frame_MB_copied']))
+    if solves:
+        lines += ['', '| face_pose_solve S x T, L | cold us | min .. max | warm us | min .. max | warm us / frame | T = 1 all cold us | accepted steps cold | warm | frames solved |',
+                  '|---|---|---|---|---|---|---|---|---|---|']
+        for r in solves:
+            lines.append('| %d x %d, %d | %.2f | %.2f .. %.2f | %.2f | %.2f .. %.2f | %.2f | %.2f | %d .. %d | %d .. %d | %.4f |' % (
+                r['S'], r['T'], r['L'], r['cold_us'], r['cold_us_min_max'][0], r['cold_us_min_max'][1], r['warm_us'], r['warm_us_min_max'][0],
+                r['warm_us_min_max'][1], r['warm_us_per_frame'], r['all_cold_us'], r['accepted_cold_first_frame'][0],
+                r['accepted_cold_first_frame'][1], r['accepted_warm_frames'][0], r['accepted_warm_frames'][1], r['frames_solved']))
+    if rows and args.landmarks:
+        lines += ['', '| B x Tc (%s) | face step ms | min .. max | pose step ms | min .. max | face - pose ms |' % args.dtype, '|---|---|---|---|---|---|']
+        for r in rows:
+            lines.append('| %d x %d | %.4f | %.4f .. %.4f | %.4f | %.4f .. %.4f | %.4f |' % (
+                r['B'], r['Tc'], r['face_step_ms'], r['face_step_ms_min_max'][0], r['face_step_ms_min_max'][1], r['pose_step_ms'],
+                r['pose_step_ms_min_max'][0], r['pose_step_ms_min_max'][1], r['face_minus_pose_ms']))
     table = '\n'.join(lines)
     print(table, flush=True)
     if args.markdown:
