@@ -181,6 +181,7 @@ SIGNATURES = {
     'eve_screen_u8_area_bgr_to_nchw': [L, I, I, I, P, I, I, P, P],
     'eve_eye_warp_fmt_to_nchw': [I, I, L, I, I, P, P, P, I, I, P, P],
     'eve_eye_warp_fmt_to_stem': [I, I, I, L, I, I, P, P, P, I, I, P, P],
+    'eve_screen_area_fmt_to_nchw': [I, I, L, I, I, P, I, I, P, P],
 }
 EXPORTS = sorted(list(SIGNATURES) + ['eve_abi_version', 'eve_last_error', 'eve_last_kernel'])
 

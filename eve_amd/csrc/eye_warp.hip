@@ -35,6 +35,7 @@
 // block or pair) and the integer matrix of include/eve_hip.h; a tap outside the frame adds nothing, as before.  The plain
 // kernels are the FMT = PIX_RGB instantiation of the same templates and compile to the instructions they had without them.
 #include "common.h"
+#include "yuv_rgb.h"
 
 namespace eve {
 namespace {
@@ -54,14 +55,9 @@ struct EyeWarpArgs {
 // what a frame holds (EVE_PIX_* of include/eve_hip.h; PIX_RGB is the four existing entry points' layout, C = 3 or 4)
 constexpr int PIX_RGB = -1;
 
-// the integer YUV -> RGB matrix of one launch, by value in the kernel's arguments (unused by the BGR formats)
-struct YuvCoef {
-    int y0, cy, cvr, cug, cvg, cub;
-};
-
 struct EyeWarpFmtArgs {
     EyeWarpArgs a;                       // a.C: 3, or 4 for BGRA; the YUV formats do not read it
-    YuvCoef coef;
+    YuvCoef coef;                        // the integer YUV -> RGB matrix of the launch (yuv_rgb.h; unused by the BGR formats)
 };
 
 // bytes of one frame
@@ -92,11 +88,7 @@ __device__ __forceinline__ void tap_rgb(const uint8_t* __restrict__ frame, const
             const uint8_t* row = frame + (size_t)y * IW * 2;
             Y = row[2 * x]; U = row[2 * (x & ~1) + 1]; V = row[2 * (x | 1) + 1];
         }
-        const int yy = (Y - k.y0 > 0 ? Y - k.y0 : 0) * k.cy + (1 << 19), u = U - 128, v = V - 128;    // |sums| < 2^30
-        const int r = (yy + k.cvr * v) >> 20, g = (yy - k.cvg * v - k.cug * u) >> 20, b = (yy + k.cub * u) >> 20;
-        rgb[0] = (uint32_t)(r < 0 ? 0 : r > 255 ? 255 : r);
-        rgb[1] = (uint32_t)(g < 0 ? 0 : g > 255 ? 255 : g);
-        rgb[2] = (uint32_t)(b < 0 ? 0 : b > 255 ? 255 : b);
+        yuv_to_rgb(Y, U, V, k, rgb);
     }
 }
 
@@ -255,13 +247,6 @@ EyeWarpArgs eye_warp_args(long long N, int IH, int IW, int C, int OH, int OW, in
     a.IH = IH; a.IW = IW; a.C = C; a.OH = OH; a.OW = OW;
     return a;
 }
-
-// (y0, CY, CVR, CUG, CVG, CUB), each constant floor(c * 2^20 + 0.5) of its coefficient (include/eve_hip.h), indexed by EVE_YUV_*
-constexpr YuvCoef YUV_MATRICES[3] = {
-    {16, 1220542, 1673527, 409993, 852492, 2116026},      // bt601: 1.164, 1.596, 0.391, 0.813, 2.018 (OpenCV's COLOR_YUV2RGB_NV12)
-    {16, 1220542, 1880097, 223347, 558891, 2214593},      // bt709: 1.164, 1.793, 0.213, 0.533, 2.112
-    {0, 1048576, 1470104, 360853, 748826, 1858077},       // jfif:  1, 1.402, 0.344136, 0.714136, 1.772
-};
 
 // the format entry points' checks on top of eye_warp_refusal; -> nullptr or what is wrong
 const char* eye_warp_fmt_refusal(int format, int matrix, long long N, int IH, int IW, const void* frames, const void* warps, int OH, int OW,

@@ -13,6 +13,10 @@ uint8 frames is 4x less PCIe traffic, and the float values produced here are bit
                                  float32 in [0, 1] by exact area averaging (RefineNet passes its screen_size for uint8 screens)
   preprocess_screen_frames(u8, size=(H, W), bgr=True)
                                  the same from a BGR(A) capture: the planes come out in RGB order, no swapped copy is made
+  preprocess_screen_frames(u8, size=(H, W), format='nv12', matrix='bt601')
+                                 the same from a decoder's or capture path's NV12 / I420 [..., IH*3/2, IW] or YUYV [..., IH, IW, 2]
+                                 surface: converted pixel by pixel as it is read, then averaged -- the keys `screen_frame_nv12`,
+                                 `screen_frame_i420`, `screen_frame_yuyv` in place of `screen_frame`
   warp_eye_patches(u8, warps)    whole camera frames [..., IH, IW, 3|4] uint8 and per-frame homographies [..., 3, 3] float32
                                  (patch pixel -> camera pixel) -> one eye's patches [..., 3, H, W] float32 in [-1, 1], cut
                                  bilinearly on the device (EyeNet / EVE / EVEStream take `camera_frame` + `<side>_eye_warp`)
@@ -57,7 +61,7 @@ def preprocess_frames(frames):
     return out.view(lead + tuple(out.shape[1:]))
 
 
-def preprocess_screen_frames(frames, size=None, bgr=False):
+def preprocess_screen_frames(frames, size=None, bgr=False, format=None, matrix='bt601'):
     """size: None, or the (H, W) the network takes.  Frames of that size already (and size=None) are normalised as the
     reference normalises its 128 x 72 video; larger ones -- a live capture of the desktop, [..., IH, IW, 3 | 4] -- are
     area-averaged down to it by eve_screen_u8_area_to_nchw: the exact mean over each output pixel's footprint, fractional
@@ -66,7 +70,27 @@ def preprocess_screen_frames(frames, size=None, bgr=False):
     comes unless bgr says otherwise.  The reference's own file was scaled by ffmpeg (bicubic, then
     lossy video coding): this is what a live stream can do instead, not a reproduction of it.
     bgr=True: the frames are BGR(A), as capture APIs and OpenCV deliver them; the planes come out in RGB order, bit for bit what
-    the channel-reversed capture gives (eve_screen_u8_area_bgr_to_nchw, at every size: size=None takes the frames' own)."""
+    the channel-reversed capture gives (eve_screen_u8_area_bgr_to_nchw, at every size: size=None takes the frames' own).
+    format: None, or the layout a decoder or capture path delivers -- 'nv12' / 'i420' [..., IH*3/2, IW] (IH and IW even) or 'yuyv'
+    [..., IH, IW, 2] (IW even), byte-linear per frame, with the integer matrix `matrix` ('bt601' or 'bt709', limited range, or
+    'jfif', full range): every pixel is converted as it is read and the converted values are averaged, so the result equals the
+    RGB call on the converted frame bit for bit and no RGB frame is made (eve_screen_area_fmt_to_nchw, at every size: size=None
+    takes the frames' own).  bgr=True together with a format raises ValueError."""
+    if format is not None:
+        if bgr:
+            raise ValueError('preprocess_screen_frames: bgr=True and format=%r exclude each other' % (format,))
+        if format not in ('nv12', 'i420', 'yuyv'):
+            raise ValueError("preprocess_screen_frames: format must be 'nv12', 'i420' or 'yuyv', got %r" % (format,))
+        from .kernels import pixel_format_shape
+        dims = 3 if format == 'yuyv' else 2                    # the planar layouts are [rows, IW]
+        if not torch.is_tensor(frames) or frames.dim() < dims + 1:
+            raise TypeError('expected uint8 %s frames with at least one leading dimension, got %s' % (format, tuple(getattr(frames, 'shape', ()))))
+        lead = tuple(frames.shape[:-dims])
+        flat = frames.reshape((-1,) + tuple(frames.shape[-dims:])).contiguous()
+        IH, IW, _ = pixel_format_shape(flat, format, lead=1)
+        hw = (IH, IW) if size is None else (int(size[0]), int(size[1]))
+        out = default_kernels().screen_area_fmt_to_nchw(flat, hw, format, matrix=matrix)
+        return out.view(lead + tuple(out.shape[1:]))
     flat, lead = _fold(frames)
     if bgr:
         hw = tuple(flat.shape[1:3]) if size is None else (int(size[0]), int(size[1]))

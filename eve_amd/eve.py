@@ -25,6 +25,7 @@ from . import losses, ops
 from .config import get_config
 from .eye_net import EyeNet, eye_input, eye_pose_batch, has_pose_form
 from .kernels import default_kernels
+from .refine_net import screen_capture
 
 
 def _mean2(a, b):
@@ -255,11 +256,8 @@ class EVE(nn.Module):
 
         refined_history = None
         if self.refine_net is not None:                               # eve.py:146-166
-            if 'screen_frame_bgr' in d:                               # a BGR(A) capture: reordered inside the area resize
-                hf, states = self.refine_net.forward_sequence(inter['heatmap_initial'], d.get('screen_frame'),
-                                                              screen_frame_bgr=d['screen_frame_bgr'])
-            else:
-                hf, states = self.refine_net.forward_sequence(inter['heatmap_initial'], d.get('screen_frame'))
+            # (a BGR(A), NV12, I420 or YUYV capture goes in under its own key: reordered / converted inside the area resize)
+            hf, states = self.refine_net.forward_sequence(inter['heatmap_initial'], d.get('screen_frame'), **screen_capture(d))
             inter['heatmap_final'] = hf
             for i, st in enumerate(states):
                 if not isinstance(st, tuple):
@@ -295,7 +293,7 @@ class EVE(nn.Module):
 
         if create_images:                                             # eve.py:268-283
             if cfg.load_screen_content:
-                if 'screen_frame' in d:                               # (a screen_frame_bgr capture is not echoed)
+                if 'screen_frame' in d:                               # (a screen_frame_bgr / _nv12 / _i420 / _yuyv capture is not echoed)
                     output_dict['screen_frame'] = d['screen_frame'][:, -1]
             if 'history_initial' in inter:
                 output_dict['initial_gaze_history'] = inter['history_initial']
@@ -328,8 +326,8 @@ class EVE(nn.Module):
     def _predict_sequence(self, d, eye_states, refine_states, reset=None, return_heatmaps=False, lengths=None, masked=False,
                           eye_mask=None, pose_gate=None, face_state=None):
         """The prediction part of forward() for one chunk of an EVEStream: eval only, no labels, no losses.  d: the chunk's
-        inputs [B, Tc, ...] (not modified; camera_frame may be any one key of eye_net.EYE_FRAME_KEYS and the screen may come as
-        screen_frame_bgr; the eyes as patches, as camera_frame + {left,right}_eye_warp, or as camera_frame +
+        inputs [B, Tc, ...] (not modified; camera_frame may be any one key of eye_net.EYE_FRAME_KEYS and the screen any one key of
+        refine_net.SCREEN_FRAME_KEYS; the eyes as patches, as camera_frame + {left,right}_eye_warp, or as camera_frame +
         eye_pose [B, Tc, 18], which also stands in for {left,right}_h / _o / _R and head_R and adds pose_valid to the result; both
         camera forms with an optional camera_lens [B, Tc, 12] for raw frames -- eye_net.eye_input, eye_pose_batch); eye_states / refine_states: the carried state buffers of the two networks
         (EyeNet._stream_state_buffers, RefineNet._stream_state_buffers), read as the state before the chunk and overwritten with
@@ -369,10 +367,9 @@ class EVE(nn.Module):
         inter = dict(self.eye_net._stream_sequence(d, eye_states, reset, lengths, plan))
         self._pog_block(d, inter, 'initial', 'initial', eye_valid=eye_valid)
         if self.refine_net is not None and 'heatmap_initial' in inter:
-            bgr = dict(screen_frame_bgr=d['screen_frame_bgr']) if 'screen_frame_bgr' in d else {}
             hf = self.refine_net._stream_sequence(inter['heatmap_initial'], d.get('screen_frame'), refine_states,
                                                   None if reset is None else reset[:B], None if lengths is None else lengths[:B], plan,
-                                                  **bgr)
+                                                  **screen_capture(d))
             inter['heatmap_final'] = hf
             self._final_block(d, inter, hf)
         out = {k_: inter[k_] for k_ in self.PREDICTION_KEYS if k_ in inter}

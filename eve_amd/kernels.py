@@ -454,6 +454,26 @@ class HipKernels(object):
         self._ck(self.lib.eve_screen_u8_area_bgr_to_nchw(N, IH, IW, C, self._p(frames), OH, OW, self._p(out), self._stream()))
         return out
 
+    def screen_area_fmt_to_nchw(self, frames, out_hw, format, matrix='bt601'):
+        """screen_u8_area_to_nchw for a capture as decoders and capture paths deliver it, uint8 and contiguous: format 'nv12' /
+        'i420' [N,IH*3/2,IW], 'yuyv' [N,IH,IW,2] or 'bgr' [N,IH,IW,3|4]; matrix 'bt601' | 'bt709' | 'jfif' for the YUV formats.
+        Every pixel is converted as it is read, by the integer matrix of include/eve_hip.h eve_eye_warp_fmt_to_nchw, and the
+        converted values are averaged: the result is screen_u8_area_to_nchw's on the converted frame, bit for bit, and no RGB frame
+        is made (include/eve_hip.h eve_screen_area_fmt_to_nchw)."""
+        IH, IW, C = pixel_format_shape(frames, format, lead=1)
+        if format == 'rgb':
+            raise ValueError('screen_area_fmt_to_nchw takes bgr, nv12, i420 or yuyv; an RGB capture goes to screen_u8_area_to_nchw')
+        if matrix not in YUV_MATRICES:
+            raise ValueError('screen_area_fmt_to_nchw: matrix must be one of %s, got %r' % (', '.join(YUV_MATRICES), matrix))
+        if not frames.is_contiguous():
+            raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        N, (OH, OW) = frames.shape[0], (int(out_hw[0]), int(out_hw[1]))
+        out = torch.empty((N, 3, OH, OW), dtype=torch.float32, device=frames.device)
+        code = PIXEL_FORMATS['bgra' if format == 'bgr' and C == 4 else format]
+        self._ck(self.lib.eve_screen_area_fmt_to_nchw(code, YUV_MATRICES[matrix], N, IH, IW, self._p(frames), OH, OW, self._p(out),
+                                                      self._stream()))
+        return out
+
     def frames_u8_to_stem(self, frames, scale, shift, out=None, dtype=torch.bfloat16):
         """uint8 [N,H,W,C<=4] -> the stem's packed 16-bit input [N,H+6,W+8,4]."""
         N, H, W, C = frames.shape

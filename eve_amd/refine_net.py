@@ -30,6 +30,27 @@ from .eye_net import default_compute_dtype
 from .kernels import ACT_LEAKY, ACT_NONE, ACT_RELU, default_kernels, pad_channels
 from .ops import PackedWeight
 
+# the screen key of a batch and its pixel format: a batch holds at most one (screen_frame is the float screen input or an
+# RGB(A) capture, the others are what capture APIs, decoders and OpenCV deliver -- kernels.pixel_format_shape has the layouts);
+# the mirror of eye_net.EYE_FRAME_KEYS
+SCREEN_FRAME_KEYS = {'screen_frame': 'rgb', 'screen_frame_bgr': 'bgr', 'screen_frame_nv12': 'nv12', 'screen_frame_i420': 'i420',
+                     'screen_frame_yuyv': 'yuyv'}
+
+
+def screen_frame_key(batch):
+    """The one screen key of SCREEN_FRAME_KEYS the batch holds, or None; two of them raise ValueError."""
+    found = [k_ for k_ in SCREEN_FRAME_KEYS if k_ in batch]
+    if len(found) > 1:
+        raise ValueError('give the screen under one key, not both: found %s' % ', '.join(found))
+    return found[0] if found else None
+
+
+def screen_capture(batch):
+    """The keyword arguments RefineNet.forward_sequence / _stream_sequence take for the batch's screen beside screen_frame:
+    {} or {its key: the capture} for one of the capture keys."""
+    key = screen_frame_key(batch)
+    return {} if key in (None, 'screen_frame') else {key: batch[key]}
+
 
 class BasicBlock(nn.Module):     # holder, refine_net.py:35-62
     def __init__(self, in_shape, out_shape, act_func=nn.ReLU):
@@ -312,32 +333,53 @@ class RefineNet(nn.Module):
                 out.append(one(st, sdt))
         return out
 
-    def forward_sequence(self, heatmap_initial, screen_frame=None, initial_states=None, screen_frame_bgr=None):
+    # The YUV -> RGB matrix of screen_frame_nv12 / _i420 / _yuyv captures: 'bt601' (limited range: OpenCV's cvtColor, SD video),
+    # 'bt709' (limited range: what HD recordings and hardware decoders of HD video usually are) or 'jfif' (full range).  Anything
+    # else raises ValueError at use.
+    yuv_matrix = 'bt601'
+
+    def forward_sequence(self, heatmap_initial, screen_frame=None, initial_states=None, screen_frame_bgr=None, screen_frame_nv12=None,
+                         screen_frame_i420=None, screen_frame_yuyv=None):
         """heatmap_initial [B,T,1,h,w], screen_frame [B,T,3,H,W] -> (heatmap_final [B,T,1,H,W],
         list over cells of the stacked states [B,T,C,5,8] (tuple of two for CLSTM)).
         screen_frame may also be uint8 [B,T,IH,IW,3|4]: decoded frames at the screen size, or a full-resolution capture that is
         area-averaged down to config.screen_size on the device (data.preprocess_screen_frames; channel order kept, alpha ignored).
         screen_frame_bgr: in place of screen_frame, a uint8 [B,T,IH,IW,3|4] BGR(A) capture as capture APIs and OpenCV deliver it;
         the result is that of the channel-reversed capture as screen_frame, bit for bit.  Both together raise ValueError.
+        screen_frame_nv12 / screen_frame_i420 (uint8 [B,T,IH*3/2,IW], IH and IW even) / screen_frame_yuyv (uint8 [B,T,IH,IW,2], IW
+        even): in place of screen_frame, the capture as a decoder or a capture path delivers it; every pixel is converted by the
+        integer matrix self.yuv_matrix names as the area resize reads it (eve_screen_area_fmt_to_nchw), and the result is that of
+        the converted RGB capture as screen_frame, bit for bit.  One screen argument at a time: two raise ValueError.
         initial_states: None (zero states), or per cell the state before the first frame -- reference layout [B, C, 5, 8] as
         returned here (the last frame of a previous call), or the internal NHWC layout [B, 5, 8, C]; (h, c) for CLSTM."""
-        screen_frame = self._screen_input(screen_frame, screen_frame_bgr)
+        screen_frame = self._screen_input(screen_frame, screen_frame_bgr=screen_frame_bgr, screen_frame_nv12=screen_frame_nv12,
+                                          screen_frame_i420=screen_frame_i420, screen_frame_yuyv=screen_frame_yuyv)
         hf, states, to_ref = self._sequence(heatmap_initial, screen_frame, self._initial_states_in(initial_states))
         return hf, [tuple(to_ref(t) for t in st) if isinstance(st, tuple) else to_ref(st) for st in states]
 
-    def _screen_input(self, screen_frame, screen_frame_bgr):
-        """screen_frame as it is, or the float [B,T,3,H,W] screen input made from a BGR(A) capture (one area-resize launch)."""
-        if screen_frame_bgr is None:
+    def _screen_input(self, screen_frame, **captures):
+        """screen_frame as it is, or the float [B,T,3,H,W] screen input made from the one capture given under a key of
+        SCREEN_FRAME_KEYS other than screen_frame -- BGR(A), NV12, I420 or YUYV (one area-resize launch)."""
+        given = {k_: v for k_, v in captures.items() if v is not None}
+        assert all(k_ in SCREEN_FRAME_KEYS and k_ != 'screen_frame' for k_ in given), sorted(given)
+        if not given:
             return screen_frame
-        if screen_frame is not None:
-            raise ValueError('give the screen as screen_frame or as screen_frame_bgr, not both')
-        if not torch.is_tensor(screen_frame_bgr) or screen_frame_bgr.dtype != torch.uint8 or screen_frame_bgr.dim() != 5 or \
-                screen_frame_bgr.shape[4] not in (3, 4):
-            raise TypeError('screen_frame_bgr must be uint8 [B, T, IH, IW, 3 | 4], got %s %s' % (
-                getattr(screen_frame_bgr, 'dtype', type(screen_frame_bgr)), tuple(getattr(screen_frame_bgr, 'shape', ()))))
+        if screen_frame is not None or len(given) > 1:
+            raise ValueError('give the screen as screen_frame or under one of %s, not both' % ', '.join(k_ for k_ in SCREEN_FRAME_KEYS if k_ != 'screen_frame'))
+        (key, capture), = given.items()
         from . import data
         cfg = self.config
-        return data.preprocess_screen_frames(screen_frame_bgr, size=(cfg.screen_size[1], cfg.screen_size[0]), bgr=True)
+        size = (cfg.screen_size[1], cfg.screen_size[0])
+        if key == 'screen_frame_bgr':
+            if not torch.is_tensor(capture) or capture.dtype != torch.uint8 or capture.dim() != 5 or capture.shape[4] not in (3, 4):
+                raise TypeError('screen_frame_bgr must be uint8 [B, T, IH, IW, 3 | 4], got %s %s' % (
+                    getattr(capture, 'dtype', type(capture)), tuple(getattr(capture, 'shape', ()))))
+            return data.preprocess_screen_frames(capture, size=size, bgr=True)
+        from .kernels import YUV_MATRICES, pixel_format_shape
+        pixel_format_shape(capture, SCREEN_FRAME_KEYS[key], lead=2, name=key)
+        if self.yuv_matrix not in YUV_MATRICES:
+            raise ValueError('RefineNet.yuv_matrix must be one of %s, got %r' % (', '.join(YUV_MATRICES), self.yuv_matrix))
+        return data.preprocess_screen_frames(capture, size=size, format=SCREEN_FRAME_KEYS[key], matrix=self.yuv_matrix)
 
     def _sequence(self, heatmap_initial, screen_frame, h0, plan=None):
         """The clip pass behind forward_sequence.  h0: None or per cell the internal-layout initial state (_initial_states_in).
@@ -392,14 +434,15 @@ class RefineNet(nn.Module):
         z = lambda dt: torch.zeros((B, 5, 8, C), dtype=dt, device=device)
         return [tuple(z(d) for d in dt) if isinstance(dt, tuple) else z(dt) for dt in self._carried_dtypes()]
 
-    def _stream_sequence(self, heatmap_initial, screen_frame, buffers, reset=None, lengths=None, plan=None, screen_frame_bgr=None):
+    def _stream_sequence(self, heatmap_initial, screen_frame, buffers, reset=None, lengths=None, plan=None, **captures):
         """One chunk of a stream: the carried states `buffers` (from _stream_state_buffers) are zeroed where reset[b] != 0, used
         as the initial states, and overwritten with the chunk's last frame -- one eve_stream_state_rows launch each way, no
         conversion.  lengths (None, or int32 [B] on the device): stream b's states are committed from its frame lengths[b] - 1
         instead (eve_stream_state_rows_at), or kept when that is 0.  plan (None, or kernels.stream_mask_plan's result, which holds
         the lengths already): stream b consumes exactly its valid frames -- _sequence compacts them to the front, and the states
         are committed from the last valid one (the plan's frame counts as lengths), held when there is none; heatmap_final at
-        the other frames is unspecified.  -> heatmap_final [B,T,1,H,W]."""
+        the other frames is unspecified.  captures: the screen under one of forward_sequence's capture keywords (screen_frame_bgr,
+        _nv12, _i420, _yuyv) in place of screen_frame.  -> heatmap_final [B,T,1,H,W]."""
         k = default_kernels()
         flat = lambda sts: [t for s in sts for t in (s if isinstance(s, tuple) else (s,))]
         if reset is not None:
@@ -407,7 +450,7 @@ class RefineNet(nn.Module):
                 k.stream_state_rows(t, t, reset)
         if plan is not None:
             lengths = plan['count'][2 * heatmap_initial.shape[0]:]
-        screen_frame = self._screen_input(screen_frame, screen_frame_bgr)
+        screen_frame = self._screen_input(screen_frame, **captures)
         hf, states, _ = self._sequence(heatmap_initial, screen_frame, buffers if buffers else None, plan)
         for dst, src in zip(flat(buffers), flat(states)):
             if lengths is None:

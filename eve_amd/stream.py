@@ -274,7 +274,17 @@ class EVEStream(object):
         inside the captured graph, whose key holds the capture's shape and dtype.  A fourth channel (BGRA's alpha) is ignored;
         the channel order is kept.  A BGR(A) capture, what capture APIs and OpenCV deliver, goes under screen_frame_bgr instead
         (uint8 [B, Tc, IH, IW, 3 | 4], never beside screen_frame): eve_screen_u8_area_bgr_to_nchw reads channel 2 - c into plane c, and
-        the step equals the one on the channel-reversed capture bit for bit.
+        the step equals the one on the channel-reversed capture bit for bit.  A decoder's or a capture path's YUV surface goes
+        under ONE of these keys in place of screen_frame (uint8, contiguous, byte-linear per frame; two screen keys raise ValueError):
+          screen_frame_nv12  [B, Tc, IH*3/2, IW]      luma rows, then IH/2 rows of interleaved U, V (hardware decoders); IH, IW even
+          screen_frame_i420  [B, Tc, IH*3/2, IW]      luma, the U plane, the V plane (ffmpeg's yuv420p); IH, IW even
+          screen_frame_yuyv  [B, Tc, IH, IW, 2]       Y U Y V per pixel pair; IW even
+        eve_screen_area_fmt_to_nchw converts every pixel as the area resize reads it -- chroma the nearest sample, the bit-exact
+        integer matrix model.refine_net.yuv_matrix names ('bt601' default; HD recordings are usually 'bt709'; 'jfif') -- and
+        averages the converted values, inside the step and the captured graph, whose input buffer holds the surface as it came
+        (NV12 / I420: 3.1 MB per 1080p frame where RGB has 6.2 MB, YUYV 4.1 MB) and whose key holds the matrix.  The step equals the
+        screen_frame step on the converted RGB capture bit for bit; lengths, eye_mask, every camera form and the camera
+        pixel-format keys combine with these keys unchanged.
 
         In both camera forms the frames may come in the layout the camera or decoder delivers, under ONE of these keys in place of
         camera_frame (uint8, contiguous, byte-linear per frame; two frame keys raise ValueError):
@@ -287,7 +297,7 @@ class EVEStream(object):
         and the captured graph, whose input buffer holds the frame as it came (NV12 / I420: half of RGB's bytes, YUYV two thirds)
         and whose key holds the matrix.  The step equals the camera_frame step on the converted frame bit for bit; camera_lens,
         eye_pose, lengths, eye_mask and skip_invalid_pose combine with these keys unchanged.  Not offered: row pitches or separate
-        plane pointers, UYVY / NV21 / P010 / 10-bit layouts, bilinear chroma up-sampling, YUV screen captures.
+        plane pointers, UYVY / NV21 / P010 / 10-bit layouts, bilinear chroma up-sampling -- for the camera and for the screen alike.
 
         lengths: None, or num_streams integers in 0..Tc (list, numpy array or CPU tensor) for streams that delivered different
         numbers of frames: stream b consumes frames 0..lengths[b]-1 of the chunk, and every carried state of it afterwards is the
@@ -377,7 +387,8 @@ class EVEStream(object):
         if wk != self._graphs_key:               # new weights: new packs, new graphs (a replay never reads stale packs)
             self._graphs = {}
             self._graphs_key = wk
-        key = (return_heatmaps, ragged, masked, self.model.eye_net.yuv_matrix) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
+        ref = self.model.refine_net
+        key = (return_heatmaps, ragged, masked, self.model.eye_net.yuv_matrix, None if ref is None else ref.yuv_matrix) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
         entry = self._graphs.get(key)
         if entry is None:
             entry = self._graphs[key] = self._capture(chunk, return_heatmaps, ragged, masked)

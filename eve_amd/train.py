@@ -381,7 +381,8 @@ def eyenet_trainer(eye_net, config, distributed=False, use_graph=False, lr_sched
 
 def refinenet_trainer(refine_net, config, distributed=False, use_graph=False, lr_schedule=None, steps_per_epoch=None):
     def loss_fn(batch):
-        hf, _ = refine_net.forward_sequence(batch['heatmap_initial'], batch.get('screen_frame'))
+        from .refine_net import screen_capture               # (the screen under whichever key of SCREEN_FRAME_KEYS the batch holds)
+        hf, _ = refine_net.forward_sequence(batch['heatmap_initial'], batch.get('screen_frame'), **screen_capture(batch))
         return losses.refinenet_loss_terms(hf, batch['heatmap_final_gt'], batch['validity'], config)
     return Trainer([refine_net], config, loss_fn, distributed=distributed, use_graph=use_graph,
                    lr_schedule=_resolve_schedule(config, lr_schedule, steps_per_epoch))

@@ -823,6 +823,27 @@ int eve_eye_warp_fmt_to_nchw(int format, int matrix, long long N, int IH, int IW
 int eve_eye_warp_fmt_to_stem(int dtype /* EVE_DT_BF16 | EVE_DT_F16 */, int format, int matrix, long long N, int IH, int IW,
                              const uint8_t* frames, const float* warps, const float* lens /* may be NULL */, int OH, int OW,
                              void* x_padded, eve_stream_t stream);
+/* Live screen captures as decoders and capture paths deliver them: eve_screen_u8_area_to_nchw's area average of a frame in one of
+ * the layouts above, converted pixel by pixel inside the same launch -- no RGB frame is ever made, and an NV12 / I420 capture is
+ * half of RGB's bytes to read (YUYV two thirds).  src holds N frames back to back, byte-linear as for eve_eye_warp_fmt_to_nchw
+ * (no pitches, one pointer); NV12 and I420 need IH and IW even, YUYV IW even.  Contract, for F in NV12, I420, YUYV and every
+ * matrix M:
+ *   screen_area_F(buf) == eve_screen_u8_area_to_nchw(to_rgb_F,M(buf))          bit for bit
+ * with to_rgb the per-pixel integer conversion stated above (chroma the nearest sample) and the area average the one stated at
+ * eve_screen_u8_area_to_nchw: S = sum wy * wx * v over the CONVERTED 8-bit values, an exact 32-bit integer, then
+ * (float)((double)S / (double)(IH * IW)) * (float)(1.0 / 255).  The order is convert, then average: the clamps make the
+ * conversion non-linear, so averaging Y, U and V first gives other bits (tests/screen_format_ref.py).  EVE_PIX_BGR and
+ * EVE_PIX_BGRA are handed to eve_screen_u8_area_bgr_to_nchw's kernel (`matrix` ignored): one entry point serves every code.
+ * A workgroup takes one (frame, output row); a thread owns 8 luma columns (one 8-byte load per row, the chroma bytes under
+ * them once per row pair) and keeps 24 column sums in registers; a width that is no multiple of 8 or a base that is not
+ * 16-byte aligned takes a byte-column form with the same bits.  Kernel names: screen_area_fmt_kernel<F,true | false> with F in
+ * nv12, i420, yuyv (true: the vector form), screen_u8_area_bgr_kernel<true | false> for BGR(A).  Refused without a launch,
+ * the message beginning "screen_area_fmt_to_nchw:": bad arguments, an unknown format, an unknown matrix with a YUV format, odd
+ * dimensions as above, upscaling in either direction, IH * IW > 16 843 009, IW * 12 > 163 840 bytes (one row of three 32-bit
+ * column sums is kept in LDS; BGR(A): IW * C * 4), N * OH >= 2^31.  Not offered: row pitches or separate plane pointers,
+ * UYVY / NV21 / P010 or any 10-bit layout, bilinear chroma up-sampling.                                                      */
+int eve_screen_area_fmt_to_nchw(int format, int matrix, long long N, int IH, int IW, const uint8_t* src, int OH, int OW,
+                                float* dst_nchw, eve_stream_t stream);
 /* Eye normalisation derived from the head pose, one launch for both eyes of N frames: everything the pipeline reads per frame and
  * eye follows from the face tracker's solvePnP result and the camera matrix.  pose [N][18] float, widened to float64:
  *   (fx, fy, cx, cy,  r0, r1, r2,  t0, t1, t2,  l0, l1, l2,  q0, q1, q2,  focal_norm, distance_norm)

@@ -8,12 +8,21 @@ three routes interleaved in one process:
             capture; for fractional ratios not the same values)
 
     python tools/bench_screen_resize.py [--sizes 1920x1080 2560x1440] [--frames 1 32 240] [--channels 3] [--iters 20] [--rounds 5]
-                                        [--markdown profiles/table.md]
+                                        [--markdown profiles/table.md] [--format rgb|bgr|nv12|i420|yuyv]
 
 One JSON line per (size, N): per route the median over the rounds of the device time per call (events around `iters` calls), and
 for `area` and `clone` the rate N*IH*IW*C / time as a fraction of the 8 TB/s HBM peak (`clone` moves twice those bytes).  Every
 route rotates over enough separately allocated captures to exceed the 256 MiB Infinity Cache, so the reads come from HBM; a live
-caller whose capture was just copied in may see it served from that cache instead."""
+caller whose capture was just copied in may see it served from that cache instead.
+
+--format bgr times eve_screen_u8_area_bgr_to_nchw as `area`.  --format nv12 | i420 | yuyv measures the capture as a decoder
+delivers it (eve_screen_area_fmt_to_nchw), three other routes interleaved round by round in one process:
+
+    fmt        HipKernels.screen_area_fmt_to_nchw(buf, (72, 128), format): N*IH*IW*3/2 bytes (YUYV: *2) read once, converted in registers
+    rgb        HipKernels.screen_u8_area_to_nchw on the SAME frames converted beforehand (conversion not timed): the launch the new one stands beside
+    torch+rgb  what a caller had before: a whole-frame conversion with torch (the same integer matrix), then the RGB launch
+
+One JSON line per (size, N) with each route's median, minimum and maximum over the rounds."""
 import argparse
 import json
 import os
@@ -46,6 +55,47 @@ def aten_route(frames):
     return F.interpolate(x, size=OUT_HW, mode='area') * (1.0 / 255.0)
 
 
+def bench_format(args, k):
+    """The --format nv12 | i420 | yuyv measurement: one JSON line per (size, N)."""
+    sys.path.insert(0, os.path.join(REPO, 'tools'))
+    from bench_eye_warp import format_frames, to_rgb_device
+    fmt = args.format
+    for size in args.sizes:
+        IW, IH = (int(v) for v in size.lower().split('x'))
+        for N in args.frames:
+            nbytes = N * IH * IW * (2 if fmt == 'yuyv' else 3) // (1 if fmt == 'yuyv' else 2)
+            copies = max(2, min(64, -(-ROTATE_BYTES // nbytes)))
+            torch.manual_seed(N + IW)
+            bufs = [format_frames(fmt, (N,), IH, IW) for _ in range(2)]
+            bufs += [bufs[i % 2].clone() for i in range(copies - 2)]
+            rgbs = [to_rgb_device(b, fmt, IH, IW) for b in bufs[:2]]
+            rgbs += [rgbs[i % 2].clone() for i in range(2 * copies - 2)]                    # twice the captures: the same bytes rotated
+            routes = {'fmt': lambda i: k.screen_area_fmt_to_nchw(bufs[i % copies], OUT_HW, fmt),
+                      'rgb': lambda i: k.screen_u8_area_to_nchw(rgbs[i % len(rgbs)], OUT_HW),
+                      'torch+rgb': lambda i: k.screen_u8_area_to_nchw(to_rgb_device(bufs[i % copies], fmt, IH, IW), OUT_HW)}
+            with torch.no_grad():
+                assert torch.equal(routes['fmt'](0), routes['rgb'](0)) and torch.equal(routes['fmt'](1), routes['torch+rgb'](1))
+                for fn in routes.values():               # warm up: code objects, allocator
+                    for i in range(3):
+                        fn(i)
+                torch.cuda.synchronize()
+                times = {name: [] for name in routes}
+                for _ in range(args.rounds):
+                    for name, fn in routes.items():
+                        times[name].append(device_ms(fn, max(2, args.iters // 4) if name == 'torch+rgb' else args.iters))
+            res = {'size': size, 'N': N, 'format': fmt, 'bytes': nbytes, 'rgb_bytes': N * IH * IW * 3, 'captures_rotated': copies}
+            for name, t in times.items():
+                res[name + '_us'] = round(1e3 * sorted(t)[len(t) // 2], 2)
+                res[name + '_us_min_max'] = [round(1e3 * min(t), 2), round(1e3 * max(t), 2)]
+            res['fmt_frac_of_8TBps'] = round(nbytes / (1e-6 * res['fmt_us']) / HBM_PEAK, 4)
+            res['rgb_frac_of_8TBps'] = round(res['rgb_bytes'] / (1e-6 * res['rgb_us']) / HBM_PEAK, 4)
+            k.screen_area_fmt_to_nchw(bufs[0], OUT_HW, fmt)
+            res['kernel'] = k.lib.eve_last_kernel().decode()
+            print(json.dumps(res), flush=True)
+            del bufs, rgbs, routes
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--sizes', nargs='+', default=['1920x1080', '2560x1440'])
@@ -54,10 +104,14 @@ def main():
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--markdown', default=None, help='also write the table to this file')
+    ap.add_argument('--format', default='rgb', choices=('rgb', 'bgr', 'nv12', 'i420', 'yuyv'), help='the capture\'s layout (see above)')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit('bench_screen_resize: no GPU (a time is only measured on one)')
     k = default_kernels()
+    if args.format in ('nv12', 'i420', 'yuyv'):
+        return bench_format(args, k)
+    area = k.screen_u8_area_bgr_to_nchw if args.format == 'bgr' else k.screen_u8_area_to_nchw
     rows = []
     for size in args.sizes:
         IW, IH = (int(v) for v in size.lower().split('x'))
@@ -67,7 +121,7 @@ def main():
             torch.manual_seed(N + IW)
             caps = [torch.randint(0, 256, (N, IH, IW, args.channels), dtype=torch.uint8, device='cuda') for _ in range(min(copies, 2))]
             caps += [caps[i % 2].clone() for i in range(copies - len(caps))]
-            routes = {'area': lambda i: k.screen_u8_area_to_nchw(caps[i % copies], OUT_HW),
+            routes = {'area': lambda i: area(caps[i % copies], OUT_HW),
                       'clone': lambda i: caps[i % copies].clone(),
                       'aten': lambda i: aten_route(caps[i % copies])}
             with torch.no_grad():
@@ -80,13 +134,13 @@ def main():
                     for name, fn in routes.items():
                         times[name].append(device_ms(fn, args.iters))
             med = {name: sorted(t)[len(t) // 2] for name, t in times.items()}
-            res = {'size': size, 'N': N, 'C': args.channels, 'bytes': nbytes, 'captures_rotated': copies,
+            res = {'size': size, 'N': N, 'C': args.channels, 'format': args.format, 'bytes': nbytes, 'captures_rotated': copies,
                    'area_us': round(1e3 * med['area'], 2), 'clone_us': round(1e3 * med['clone'], 2), 'aten_us': round(1e3 * med['aten'], 2),
                    'area_us_min_max': [round(1e3 * min(times['area']), 2), round(1e3 * max(times['area']), 2)],
                    'area_frac_of_8TBps': round(nbytes / (1e-3 * med['area']) / HBM_PEAK, 4),
                    'clone_frac_of_8TBps_read_plus_write': round(2 * nbytes / (1e-3 * med['clone']) / HBM_PEAK, 4),
                    'aten_over_area': round(med['aten'] / med['area'], 2)}
-            k.screen_u8_area_to_nchw(caps[0], OUT_HW)
+            area(caps[0], OUT_HW)
             res['kernel'] = k.lib.eve_last_kernel().decode()
             print(json.dumps(res), flush=True)
             rows.append(res)

@@ -3,7 +3,7 @@
 CLSTM RefineNet), synthetic weights and clips.  One JSON line per shape:
 
     python tools/bench_stream.py --shapes 1x1 32x1 32x30 [--dtype bf16] [--steps 50] [--fused-tail] [--ragged | --masked] [--repeat N]
-                                 [--screen 1920x1080]
+                                 [--screen 1920x1080 [--screen-format nv12]]
 
 B x Tc = streams x frames per step.  For Tc > 1 the same clips also go through one EVE.eval() pass (`eval_ms`): what the
 stream costs over the plain clip pass.  --fused-tail runs the EyeNet tail as one eve_eye_tail_stream_fwd launch
@@ -14,7 +14,9 @@ all).  --masked steps with a seeded random eye mask with about 20 % holes, a new
 also holds `launch_floor_us`, the device time per launch of a captured chain of 64 smallest launches (eve_stream_state_rows on 16
 floats) in the same process: what one more launch in the graph costs at the least.
 --screen WxH feeds uint8 screen captures of that size, [B, Tc, H, W, 3], instead of the pre-resized float screens: the step
-then holds the area resize (eve_screen_u8_area_to_nchw) and the copy of the captures into the graph's input buffer.  --repeat N measures every shape N times in one process (`step_ms_runs`; `step_ms` is their median): the run-to-run spread."""
+then holds the area resize (eve_screen_u8_area_to_nchw) and the copy of the captures into the graph's input buffer; with
+--screen-format nv12 | i420 | yuyv the captures go in as a decoder delivers them, under screen_frame_<format> (eve_screen_area_fmt_to_nchw;
+`screen_bytes` is what one step copies into the graph for the screen).  --repeat N measures every shape N times in one process (`step_ms_runs`; `step_ms` is their median): the run-to-run spread."""
 import argparse
 import json
 import os
@@ -72,7 +74,10 @@ def main():
     ap.add_argument('--masked', action='store_true', help='step with a random eye mask, about 20 %% of the eyes masked out')
     ap.add_argument('--repeat', type=int, default=1)
     ap.add_argument('--screen', default=None, metavar='WxH', help='feed uint8 screen captures of this size, e.g. 1920x1080')
+    ap.add_argument('--screen-format', default='rgb', choices=('rgb', 'nv12', 'i420', 'yuyv'), help='the layout of the --screen captures')
     args = ap.parse_args()
+    if args.screen_format != 'rgb' and not args.screen:
+        ap.error('--screen-format needs --screen WxH')
     if args.ragged and args.masked:
         ap.error('--ragged and --masked are two measurements: give one')
     cfg = eve_amd.reset_standalone_config()
@@ -95,8 +100,12 @@ def main():
         full = {k: torch.cat([v] * ((B + 3) // 4), dim=0)[:B].contiguous().cuda() for k, v in small.items()}
         if screen is not None:
             g = torch.Generator().manual_seed(B * 1000 + Tc)
-            full['screen_frame'] = torch.randint(0, 256, (B, Tc, screen[1], screen[0], 3), generator=g, dtype=torch.uint8).cuda()
-        clip = {k: full[k] for k in INPUT_KEYS if k in full}
+            W, H = screen
+            shape = {'rgb': (H, W, 3), 'nv12': (H * 3 // 2, W), 'i420': (H * 3 // 2, W), 'yuyv': (H, W, 2)}[args.screen_format]
+            del full['screen_frame']
+            screen_key = 'screen_frame' if args.screen_format == 'rgb' else 'screen_frame_' + args.screen_format
+            full[screen_key] = torch.randint(0, 256, (B, Tc) + shape, generator=g, dtype=torch.uint8).cuda()
+        clip = {k: full[k] for k in INPUT_KEYS + ('screen_frame_nv12', 'screen_frame_i420', 'screen_frame_yuyv') if k in full}
         stream = eve_amd.EVEStream(model, B)
         rng = np.random.default_rng(B * 1000 + Tc)
         step = (lambda: stream.step(clip, lengths=rng.integers(0, Tc + 1, size=B))) if args.ragged else (lambda: stream.step(clip))
@@ -108,6 +117,8 @@ def main():
         runs = sorted(round(device_ms(step, args.steps), 4) for _ in range(max(1, args.repeat)))
         res = {'B': B, 'Tc': Tc, 'dtype': args.dtype, 'tail': 'fused' if args.fused_tail else 'layers', 'ragged': args.ragged, 'masked': args.masked,
                'screen': args.screen or 'float', 'step_ms': runs[len(runs) // 2]}
+        if screen is not None:
+            res['screen_format'], res['screen_bytes'] = args.screen_format, full[screen_key].numel()
         if len(runs) > 1:
             res['step_ms_runs'] = runs
         if args.masked:
