@@ -4,7 +4,7 @@ kernels (libeve_hip.so, C ABI in include/eve_hip.h)."""
 from .config import HotPathConfig, get_config, reset_standalone_config  # noqa: F401
 from .eye_net import EyeNet  # noqa: F401
 
-__all__ = ['EyeNet', 'RefineNet', 'EVE', 'EVEStream', 'get_config', 'HotPathConfig', 'reset_standalone_config']
+__all__ = ['EyeNet', 'RefineNet', 'EVE', 'EVEStream', 'OverlaySpec', 'get_config', 'HotPathConfig', 'reset_standalone_config']
 
 
 def __getattr__(name):
@@ -17,4 +17,7 @@ def __getattr__(name):
     if name == 'EVEStream':
         from .stream import EVEStream
         return EVEStream
+    if name == 'OverlaySpec':
+        from .data import OverlaySpec
+        return OverlaySpec
     raise AttributeError(name)

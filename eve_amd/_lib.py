@@ -182,6 +182,7 @@ SIGNATURES = {
     'eve_eye_warp_fmt_to_nchw': [I, I, L, I, I, P, P, P, I, I, P, P],
     'eve_eye_warp_fmt_to_stem': [I, I, I, L, I, I, P, P, P, I, I, P, P],
     'eve_screen_area_fmt_to_nchw': [I, I, L, I, I, P, I, I, P, P],
+    'eve_overlay_render': [I, I, I, L, I, I, P, P, I, P, P, P, F, F, P, I, I, I, I, P, I, I, I, I, I, I, P, P],
 }
 EXPORTS = sorted(list(SIGNATURES) + ['eve_abi_version', 'eve_last_error', 'eve_last_kernel'])
 

@@ -65,4 +65,30 @@ __device__ __forceinline__ void yuv_to_rgb(const int Y, const int U, const int V
     yuv_pixel(Y, yuv_chroma(U, V, k), k, rgb);
 }
 
+// The forward direction, RGB -> YUV, of the overlay's output (include/eve_hip.h eve_overlay_render; tests/overlay_ref.py):
+//   Y = clamp((KYR*R + KYG*G + KYB*B + (y0  << 20) + 2^19) >> 20, 0, 255)
+//   U = clamp((KUR*R + KUG*G + KUB*B + (128 << 20) + 2^19) >> 20, 0, 255)        V likewise with its row
+// in int32 with arithmetic shifts (every sum stays below 2^29 in magnitude); Y per pixel, U and V from a 2 x 2 block's rounded mean.
+struct RgbYuvCoef {
+    int y0, y[3], u[3], v[3];
+};
+
+// each constant sign(c) * floor(|c| * 2^20 + 0.5) of its coefficient, indexed by EVE_YUV_*
+constexpr RgbYuvCoef RGB_YUV_MATRICES[3] = {
+    {16, {269484, 528482, 102760}, {-155189, -305136, 460325}, {460325, -385876, -74449}},   // bt601: (0.257, 0.504, 0.098), (-0.148, -0.291, 0.439), (0.439, -0.368, -0.071)
+    {16, {191889, 643826, 65012}, {-105906, -355467, 460325}, {460325, -418382, -41943}},    // bt709: (0.183, 0.614, 0.062), (-0.101, -0.339, 0.439), (0.439, -0.399, -0.040)
+    {0, {313524, 615514, 119538}, {-176933, -347355, 524288}, {524288, -439026, -85262}},    // jfif:  (0.299, 0.587, 0.114), (-0.168736, -0.331264, 0.5), (0.5, -0.418688, -0.081312)
+};
+
+// one row of the forward matrix applied to 8-bit (r, g, b); offset is y0 for the Y row and 128 for U and V.
+// The empty asm hides the clamped value's origin from the compiler.  Callers OR these values into dwords byte by byte, and hipcc
+// (ROCm 7's clang for gfx950) then fuses two "shift right, clamp to 0..255" results into one v_ashr_pk_u8_i32 and ORs the other
+// bytes on top of its destination as if the instruction had cleared bits 31:16 -- the hardware leaves them as they were, so the
+// old register contents bled into bytes 2 and 3 of every packed dword (seen on an MI355X: NV12 / I420 output of the vector form).
+__device__ __forceinline__ uint32_t rgb_yuv_row(const int (&k)[3], const int offset, const uint32_t r, const uint32_t g, const uint32_t b) {
+    uint32_t v = yuv_clamp(k[0] * (int)r + k[1] * (int)g + k[2] * (int)b + (offset << 20) + (1 << 19));
+    asm("" : "+v"(v));
+    return v;
+}
+
 }  // namespace eve

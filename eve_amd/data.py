@@ -332,6 +332,130 @@ def warp_eye_patches(frames, warps, size=None, lens=None, format='rgb', matrix='
     return out.view(lead + tuple(out.shape[1:]))
 
 
+def quantise_patches(patches):
+    """Float eye patches [..., 3, H, W] in [-1, 1] -> uint8 [..., H, W, 3]: clamp(rint((p + 1) * 127.5), 0, 255) in float32, the
+    inverse of preprocess_frames on every value it produces."""
+    q = torch.clamp(torch.round((patches.float() + 1.0) * 127.5), 0.0, 255.0).to(torch.uint8)
+    return q.movedim(-3, -1).contiguous()
+
+
+def _color(c, what):
+    if isinstance(c, int):
+        c = ((c >> 16) & 255, (c >> 8) & 255, c & 255) if 0 <= c <= 0xffffff else None
+    if c is None or len(c) != 3 or not all(isinstance(v, (int, np.integer)) and 0 <= int(v) <= 255 for v in c):
+        raise ValueError('%s must be (r, g, b) with values in 0..255 or 0xRRGGBB' % what)
+    return tuple(int(v) for v in c)
+
+
+class OverlaySpec(object):
+    """What EVEStream.step(chunk, render=spec) draws onto the chunk's full-resolution screen capture (eve_overlay_render).
+      out_format   'nv12' (default, what a hardware encoder reads), 'i420', 'rgb' or 'bgr'
+      matrix       the matrix of the output, 'bt601' | 'bt709' | 'jfif'; None: the capture's (model.refine_net.yuv_matrix)
+      markers      a list of dicts: key -- a [B, Tc, 2] entry of the step's result or of the chunk, in actual_screen_size pixels
+                   ('PoG_px_initial', 'PoG_px_final', a caller's 'PoG_px_gt'); valid -- None or the key of a [B, Tc] bool / uint8
+                   entry; r_fill, r_outline -- radii in output pixels, 0..255; fill, outline -- (r, g, b) or 0xRRGGBB.  At most 8,
+                   drawn in list order.  The default is the reference's look at 1080p: the initial estimate (180, 180, 0), then the
+                   refined one (0, 180, 0), radii 10 / 14, a black outline.
+      heat         True: blend heatmap_final in heat_color (default red) up to alpha heat_amax (0..255, default 128)
+      inset        None, 'eyes' (the step's eye patches as [right | left]) or the key of a uint8 [B, Tc, h, w, 3] RGB chunk entry;
+                   inset_xy (x0, y0) of its top-left pixel, None: flush in the bottom-right corner; inset_zoom 1..4 (nearest);
+                   inset_mirror (default True, as the reference shows the eyes)
+    Instances compare and hash by value: the spec is part of a captured graph's key."""
+    DEFAULT_MARKERS = (dict(key='PoG_px_initial', fill=(180, 180, 0)), dict(key='PoG_px_final', fill=(0, 180, 0)))
+
+    def __init__(self, out_format='nv12', matrix=None, markers=DEFAULT_MARKERS, heat=False, heat_color=(255, 0, 0), heat_amax=128,
+                 inset='eyes', inset_xy=None, inset_zoom=1, inset_mirror=True):
+        from .kernels import OVERLAY_MAX_MARKERS, OVERLAY_OUT_FORMATS, YUV_MATRICES
+        if out_format not in OVERLAY_OUT_FORMATS:
+            raise ValueError('OverlaySpec: out_format must be rgb, bgr, nv12 or i420, got %r' % (out_format,))
+        if matrix is not None and matrix not in YUV_MATRICES:
+            raise ValueError('OverlaySpec: matrix must be None or one of %s, got %r' % (', '.join(YUV_MATRICES), matrix))
+        markers = list(markers or ())
+        if len(markers) > OVERLAY_MAX_MARKERS:
+            raise ValueError('OverlaySpec: markers holds %d entries, at most %d are drawn' % (len(markers), OVERLAY_MAX_MARKERS))
+        rows = []
+        for i, m in enumerate(markers):
+            unknown = set(m) - {'key', 'valid', 'r_fill', 'r_outline', 'fill', 'outline'}
+            if unknown or 'key' not in m:
+                raise ValueError('OverlaySpec: markers[%d] needs key and may hold valid, r_fill, r_outline, fill, outline; got %s' % (i, sorted(m)))
+            r_fill, r_out = int(m.get('r_fill', 10)), int(m.get('r_outline', 14))
+            if not (0 <= r_fill <= 255 and 0 <= r_out <= 255):
+                raise ValueError('OverlaySpec: markers[%d] radii must be in 0..255' % i)
+            rows.append((str(m['key']), None if m.get('valid') is None else str(m['valid']), r_fill, r_out,
+                         _color(m.get('fill', (0, 180, 0)), 'OverlaySpec: markers[%d] fill' % i),
+                         _color(m.get('outline', (0, 0, 0)), 'OverlaySpec: markers[%d] outline' % i)))
+        if not 0 <= int(heat_amax) <= 255:
+            raise ValueError('OverlaySpec: heat_amax must be in 0..255, got %r' % (heat_amax,))
+        if inset is not None and not isinstance(inset, str):
+            raise ValueError("OverlaySpec: inset must be None, 'eyes' or the key of a uint8 [B, Tc, h, w, 3] chunk entry")
+        if not 1 <= int(inset_zoom) <= 4:
+            raise ValueError('OverlaySpec: inset_zoom must be in 1..4, got %r' % (inset_zoom,))
+        self.out_format, self.matrix, self.markers = out_format, matrix, tuple(rows)
+        self.heat, self.heat_color, self.heat_amax = bool(heat), _color(heat_color, 'OverlaySpec: heat_color'), int(heat_amax)
+        self.inset, self.inset_zoom, self.inset_mirror = inset, int(inset_zoom), bool(inset_mirror)
+        self.inset_xy = None if inset_xy is None else (int(inset_xy[0]), int(inset_xy[1]))
+
+    def key(self):
+        return (self.out_format, self.matrix, self.markers, self.heat, self.heat_color, self.heat_amax, self.inset, self.inset_xy,
+                self.inset_zoom, self.inset_mirror)
+
+    def __eq__(self, other):
+        return isinstance(other, OverlaySpec) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def marker_table(self):
+        """-> the int32 [M, 4] rows (r_fill, r_outline, fill 0xRRGGBB, outline 0xRRGGBB) of eve_overlay_render, as nested lists."""
+        rgb = lambda c: (c[0] << 16) | (c[1] << 8) | c[2]
+        return [[r_fill, r_out, rgb(fill), rgb(outline)] for _, _, r_fill, r_out, fill, outline in self.markers]
+
+
+def render_overlay(frames, format='rgb', out_format='nv12', matrix='bt601', markers=None, heat=None, inset=None, frame_valid=None, out=None):
+    """The tracking overlay on the device, stand-alone: frames uint8 [N, ...] in `format` ('rgb' | 'bgr' [N, IH, IW, 3 | 4], 'rgba',
+    'bgra', 'nv12' | 'i420' [N, IH*3/2, IW], 'yuyv' [N, IH, IW, 2]) -> the annotated frames, uint8 [N, IH, IW, 3] for out_format 'rgb' |
+    'bgr' or [N, IH*3/2, IW] for 'nv12' | 'i420' (IH and IW even).  One launch (eve_overlay_render), bit for bit tests/overlay_ref.py.
+      markers      None or a dict: centres float32 [N, M, 2] (x, y), table int32 [M, 4] tensor or nested lists of (r_fill, r_outline,
+                   fill 0xRRGGBB, outline 0xRRGGBB), valid None or uint8 [N, M], sx, sy (default 1: the centres are output pixels)
+      heat         None, a float32 [N, HH, HW] tensor, or a dict: heat, color (r, g, b) (default red), amax 0..255 (default 128)
+      inset        None, a uint8 [N, h, w, 3] RGB tensor (drawn flush in the bottom-right corner), or a dict: inset, xy (x0, y0),
+                   zoom 1..4, mirror
+      frame_valid  None or uint8 [N]: a 0 gives the converted capture with no layer drawn
+    Not offered: the reference's residual lines from an estimate to the ground truth, its legend text, gaze-ray arrows on the eye
+    image, row pitches, 10-bit surfaces, a gradient."""
+    from .kernels import pixel_format_shape
+    kw = {}
+    if markers is not None:
+        unknown = set(markers) - {'centres', 'table', 'valid', 'sx', 'sy'}
+        if unknown or 'centres' not in markers or 'table' not in markers:
+            raise ValueError('render_overlay: markers needs centres and table and may hold valid, sx, sy; got %s' % sorted(markers))
+        table = markers['table']
+        if not torch.is_tensor(table):
+            table = torch.tensor(table, dtype=torch.int32).reshape(-1, 4).to(frames.device)
+        kw.update(centres=markers['centres'], marker_table=table, marker_valid=markers.get('valid'), sx=float(markers.get('sx', 1.0)),
+                  sy=float(markers.get('sy', 1.0)))
+    if heat is not None:
+        h = heat if isinstance(heat, dict) else {'heat': heat}
+        if set(h) - {'heat', 'color', 'amax'} or 'heat' not in h:
+            raise ValueError('render_overlay: heat needs heat and may hold color, amax; got %s' % sorted(h))
+        kw.update(heat=h['heat'], heat_color=_color(h.get('color', (255, 0, 0)), 'render_overlay: heat color'), amax=h.get('amax', 128))
+    if inset is not None:
+        p = inset if isinstance(inset, dict) else {'inset': inset}
+        if set(p) - {'inset', 'xy', 'zoom', 'mirror'} or 'inset' not in p:
+            raise ValueError('render_overlay: inset needs inset and may hold xy, zoom, mirror; got %s' % sorted(p))
+        zoom, xy = int(p.get('zoom', 1)), p.get('xy')
+        if xy is None:
+            if not torch.is_tensor(p['inset']) or p['inset'].dim() != 4:
+                raise ValueError('render_overlay: inset must be a uint8 tensor [N, h, w, 3]')
+            try:
+                IH, IW, _ = pixel_format_shape(frames, {'rgba': 'rgb', 'bgra': 'bgr'}.get(format, format), lead=1)
+            except TypeError as e:
+                raise ValueError('render_overlay: %s' % e)
+            xy = (IW - zoom * int(p['inset'].shape[2]), IH - zoom * int(p['inset'].shape[1]))
+        kw.update(inset=p['inset'], inset_xy=xy, zoom=zoom, mirror=bool(p.get('mirror', False)))
+    return default_kernels().overlay_render(frames, format, out_format, matrix, frame_valid=frame_valid, out=out, **kw)
+
+
 class DevicePrefetcher(object):
     """Iterates `iterable` (dicts of CPU tensors, e.g. a DataLoader) and yields the same dicts on `device`.
 

@@ -324,7 +324,7 @@ class EVE(nn.Module):
                        'PoG_cm_initial', 'g_final', 'PoG_px_final', 'PoG_cm_final')
 
     def _predict_sequence(self, d, eye_states, refine_states, reset=None, return_heatmaps=False, lengths=None, masked=False,
-                          eye_mask=None, pose_gate=None, face_state=None):
+                          eye_mask=None, pose_gate=None, face_state=None, render=None):
         """The prediction part of forward() for one chunk of an EVEStream: eval only, no labels, no losses.  d: the chunk's
         inputs [B, Tc, ...] (not modified; camera_frame may be any one key of eye_net.EYE_FRAME_KEYS and the screen any one key of
         refine_net.SCREEN_FRAME_KEYS; the eyes as patches, as camera_frame + {left,right}_eye_warp, or as camera_frame +
@@ -347,7 +347,10 @@ class EVE(nn.Module):
         face_state: with the face-landmark form (camera_frame + face_landmarks [B, Tc, L, 2 | 3] + face_rig [B, 12 + 3L]) the
         stream's carried head pose, float64 [B, 13], read as the pose before the chunk and overwritten with the pose after it by
         the eve_face_pose_solve launch, which also reads reset[:B] and lengths[:B]; the result gains pose_valid, head_t and
-        face_reproj_rms."""
+        face_reproj_rms.
+        render: None, or EVEStream's overlay hook render(d, inter, out), called last with the chunk after eye_pose_batch (the derived
+        warps included), the intermediate results (heatmap_final whether returned or not) and the result, to which it adds
+        `rendered`; None issues no launch."""
         assert not self.training, 'EVE._predict_sequence is eval-only'
         B = eye_input(d).shape[0]
         posed, faced = has_pose_form(d), 'face_landmarks' in d
@@ -381,6 +384,8 @@ class EVE(nn.Module):
             out['valid'], out['eye_valid'] = plan['valid'].view(torch.bool), eye_valid
         if return_heatmaps and 'heatmap_final' in inter:
             out['heatmap_final'] = inter['heatmap_final']
+        if render is not None:
+            render(d, inter, out)
         return out
 
     # ------------------------------------------------------------------------------------------ eve.py:286-439

@@ -539,6 +539,34 @@ class EyeNet(nn.Module):
         feats, B, T = self._sequence_features(batch, P)
         return self._sequence_tail(feats, batch, B, T, initial_states, P)
 
+    def _camera_cutters(self, batch):
+        """The camera forms' patch cut as closures over the batch's frames, lens rows and pixel format -> (B, T, Hh, Ww, lw, rw,
+        to_stem, to_nchw): lw, rw the two eyes' homographies [B*T, 3, 3]; to_stem(w, out) cuts into the stem's packed layout,
+        to_nchw(w) to float NCHW patches [B*T, 3, Hh, Ww] in [-1, 1] (EVEStream's overlay inset cuts its patches through it)."""
+        k = default_kernels()
+        frame_key = camera_frame_key(batch)
+        from . import data
+        frames = batch[frame_key]
+        B, T = frames.shape[:2]
+        Hh, Ww = data.eye_patch_hw(self.config)
+        flat = frames.reshape((B * T,) + tuple(frames.shape[2:])).contiguous()
+        lw, rw = (batch[s_ + '_eye_warp'].reshape(B * T, 3, 3).contiguous() for s_ in ('left', 'right'))
+        if frame_key != 'camera_frame':         # BGR / NV12 / I420 / YUYV: the taps are converted inside the same launch
+            fmt, matrix = EYE_FRAME_KEYS[frame_key], self.yuv_matrix
+            if matrix not in YUV_MATRICES:
+                raise ValueError('EyeNet.yuv_matrix must be one of %s, got %r' % (', '.join(YUV_MATRICES), matrix))
+            lens = batch[EYE_LENS_KEY].reshape(B * T, 12).contiguous() if EYE_LENS_KEY in batch else None
+            to_stem = lambda w, out: k.eye_warp_fmt_to_stem(flat, w, (Hh, Ww), fmt, matrix=matrix, lens=lens, out=out)
+            to_nchw = lambda w: k.eye_warp_fmt_to_nchw(flat, w, (Hh, Ww), fmt, matrix=matrix, lens=lens)
+        elif EYE_LENS_KEY in batch:             # raw frames: the lens kernels, one camera per frame for both eyes
+            lens = batch[EYE_LENS_KEY].reshape(B * T, 12).contiguous()
+            to_stem = lambda w, out: k.eye_warp_lens_u8_to_stem(flat, w, lens, (Hh, Ww), out=out)
+            to_nchw = lambda w: k.eye_warp_lens_u8_to_nchw(flat, w, lens, (Hh, Ww))
+        else:
+            to_stem = lambda w, out: k.eye_warp_u8_to_stem(flat, w, (Hh, Ww), out=out)
+            to_nchw = lambda w: k.eye_warp_u8_to_nchw(flat, w, (Hh, Ww))
+        return B, T, Hh, Ww, lw, rw, to_stem, to_nchw
+
     def _sequence_features(self, batch, P):
         """Both eyes' clips through the trunk: -> feats [2*B*T, 512] float32 (left clips' frames, then the right ones'), B, T."""
         k = default_kernels()
@@ -548,26 +576,9 @@ class EyeNet(nn.Module):
         if eye_input(batch) is batch.get(frame_key):
             # whole camera frames and one homography per eye and frame: cut, normalise and lay out in one launch per eye --
             # straight into the stem's packed layout where the uint8 patches below go there, else to float NCHW patches
-            from . import data
             frames = batch[frame_key]
-            B, T = frames.shape[:2]
-            (Hh, Ww), C = data.eye_patch_hw(self.config), 3
-            flat = frames.reshape((B * T,) + tuple(frames.shape[2:])).contiguous()
-            lw, rw = (batch[s_ + '_eye_warp'].reshape(B * T, 3, 3).contiguous() for s_ in ('left', 'right'))
-            if frame_key != 'camera_frame':         # BGR / NV12 / I420 / YUYV: the taps are converted inside the same launch
-                fmt, matrix = EYE_FRAME_KEYS[frame_key], self.yuv_matrix
-                if matrix not in YUV_MATRICES:
-                    raise ValueError('EyeNet.yuv_matrix must be one of %s, got %r' % (', '.join(YUV_MATRICES), matrix))
-                lens = batch[EYE_LENS_KEY].reshape(B * T, 12).contiguous() if EYE_LENS_KEY in batch else None
-                to_stem = lambda w, out: k.eye_warp_fmt_to_stem(flat, w, (Hh, Ww), fmt, matrix=matrix, lens=lens, out=out)
-                to_nchw = lambda w: k.eye_warp_fmt_to_nchw(flat, w, (Hh, Ww), fmt, matrix=matrix, lens=lens)
-            elif EYE_LENS_KEY in batch:             # raw frames: the lens kernels, one camera per frame for both eyes
-                lens = batch[EYE_LENS_KEY].reshape(B * T, 12).contiguous()
-                to_stem = lambda w, out: k.eye_warp_lens_u8_to_stem(flat, w, lens, (Hh, Ww), out=out)
-                to_nchw = lambda w: k.eye_warp_lens_u8_to_nchw(flat, w, lens, (Hh, Ww))
-            else:
-                to_stem = lambda w, out: k.eye_warp_u8_to_stem(flat, w, (Hh, Ww), out=out)
-                to_nchw = lambda w: k.eye_warp_u8_to_nchw(flat, w, (Hh, Ww))
+            B, T, Hh, Ww, lw, rw, to_stem, to_nchw = self._camera_cutters(batch)
+            C, flat = 3, frames
             if dt in HALF_DTYPES and Hh % 4 == 0 and Ww == 128:
                 x_padded = torch.empty((2 * B * T, Hh + 6, Ww + 8, 4), dtype=dt, device=frames.device)
                 to_stem(lw, x_padded[:B * T])

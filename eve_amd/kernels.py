@@ -59,6 +59,100 @@ def pixel_format_shape(frames, format, lead=1, name='frames'):
     return rows // 3 * 2, IW, 1
 
 
+# include/eve_hip.h eve_overlay_render: the capture formats it reads (EVE_PIX_RGB / _RGBA are its own two codes) and writes
+OVERLAY_IN_FORMATS = dict(PIXEL_FORMATS, rgb=5, rgba=6)
+OVERLAY_OUT_FORMATS = {'rgb': 5, 'bgr': 0, 'nv12': 2, 'i420': 3}
+OVERLAY_MAX_MARKERS = 8
+OVERLAY_MAX_HEAT = 1024
+
+
+def overlay_out_shape(out_format, N, IH, IW):
+    return (N, IH, IW, 3) if out_format in ('rgb', 'bgr') else (N, IH * 3 // 2, IW)
+
+
+def overlay_check(frames, format, out_format, matrix, centres=None, marker_valid=None, marker_table=None, sx=1.0, sy=1.0, heat=None,
+                  heat_color=(255, 0, 0), amax=128, inset=None, inset_xy=(0, 0), zoom=1, mirror=False, frame_valid=None, out=None):
+    """The argument checks of overlay_render, shared with the torch-CPU stand-in of the tests -> a dict of the C call's scalars.
+    Every failure is a ValueError that names the argument."""
+    import math
+    if format not in OVERLAY_IN_FORMATS:
+        raise ValueError('overlay_render: format must be one of %s, got %r' % (', '.join(sorted(OVERLAY_IN_FORMATS)), format))
+    if out_format not in OVERLAY_OUT_FORMATS:
+        raise ValueError('overlay_render: out_format must be rgb, bgr, nv12 or i420, got %r' % (out_format,))
+    if matrix not in YUV_MATRICES:
+        raise ValueError('overlay_render: matrix must be one of %s, got %r' % (', '.join(YUV_MATRICES), matrix))
+    try:
+        IH, IW, C = pixel_format_shape(frames, {'rgba': 'rgb', 'bgra': 'bgr'}.get(format, format), lead=1)
+    except TypeError as e:
+        raise ValueError('overlay_render: %s' % e)
+    if format in ('rgba', 'bgra') and C != 4:
+        raise ValueError('overlay_render: frames of format %s must have four channels, got %d' % (format, C))
+    if not frames.is_contiguous():
+        raise ValueError('overlay_render: frames must be contiguous')
+    name = format + 'a' if format in ('rgb', 'bgr') and C == 4 else format
+    N, dev = int(frames.shape[0]), frames.device
+    if N < 1 or IH < 1 or IW < 1 or IH > 16384 or IW > 16384:
+        raise ValueError('overlay_render: frames must hold at least one frame of at most 16384 x 16384, got %s' % (tuple(frames.shape),))
+    if out_format in ('nv12', 'i420') and (IH % 2 or IW % 2):
+        raise ValueError('overlay_render: out_format %s needs even IH and IW (2 x 2 chroma blocks), got %d x %d' % (out_format, IH, IW))
+
+    def tensor(t, what, dtype, shape):
+        if (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev):
+            raise ValueError('overlay_render: %s must be a contiguous %s tensor %s on the frames\' device, got %s %s' % (
+                what, str(dtype).replace('torch.', ''), list(shape), getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ()))))
+
+    M = 0
+    if centres is not None or marker_table is not None:
+        if centres is None or marker_table is None:
+            raise ValueError('overlay_render: centres and marker_table come together')
+        if not torch.is_tensor(marker_table) or marker_table.dim() != 2:
+            raise ValueError('overlay_render: marker_table must be an int32 tensor [M, 4]')
+        M = int(marker_table.shape[0])
+        if M > OVERLAY_MAX_MARKERS:
+            raise ValueError('overlay_render: marker_table holds %d markers, at most %d are drawn' % (M, OVERLAY_MAX_MARKERS))
+        tensor(marker_table, 'marker_table', torch.int32, (M, 4))
+        tensor(centres, 'centres', torch.float32, (N, M, 2))
+        if marker_valid is not None:
+            tensor(marker_valid, 'marker_valid', torch.uint8, (N, M))
+        if not (math.isfinite(sx) and math.isfinite(sy)):
+            raise ValueError('overlay_render: sx and sy must be finite, got %r, %r' % (sx, sy))
+    elif marker_valid is not None:
+        raise ValueError('overlay_render: marker_valid without centres')
+    HH = HW = 0
+    color = 0
+    if heat is not None:
+        if not torch.is_tensor(heat) or heat.dim() != 3:
+            raise ValueError('overlay_render: heat must be a float32 tensor [N, HH, HW]')
+        HH, HW = int(heat.shape[1]), int(heat.shape[2])
+        if not (1 <= HH <= OVERLAY_MAX_HEAT and 1 <= HW <= OVERLAY_MAX_HEAT):
+            raise ValueError('overlay_render: heat must be at most %d x %d, got %d x %d' % (OVERLAY_MAX_HEAT, OVERLAY_MAX_HEAT, HH, HW))
+        tensor(heat, 'heat', torch.float32, (N, HH, HW))
+        if not 0 <= int(amax) <= 255:
+            raise ValueError('overlay_render: amax must be in 0..255, got %r' % (amax,))
+        if len(heat_color) != 3 or not all(0 <= int(c) <= 255 for c in heat_color):
+            raise ValueError('overlay_render: heat_color must be three values in 0..255, got %r' % (heat_color,))
+        color = (int(heat_color[0]) << 16) | (int(heat_color[1]) << 8) | int(heat_color[2])
+    ih = iw = 0
+    ix0, iy0 = int(inset_xy[0]), int(inset_xy[1])
+    if inset is not None:
+        if not torch.is_tensor(inset) or inset.dim() != 4:
+            raise ValueError('overlay_render: inset must be a uint8 tensor [N, h, w, 3]')
+        ih, iw = int(inset.shape[1]), int(inset.shape[2])
+        tensor(inset, 'inset', torch.uint8, (N, ih, iw, 3))
+        if not 1 <= int(zoom) <= 4:
+            raise ValueError('overlay_render: zoom must be in 1..4, got %r' % (zoom,))
+        if ih < 1 or iw < 1 or ix0 < 0 or iy0 < 0 or ix0 + int(zoom) * iw > IW or iy0 + int(zoom) * ih > IH:
+            raise ValueError('overlay_render: the inset rectangle (inset_xy %s, %d x %d at zoom %d) does not lie inside the %d x %d frame' % (
+                (ix0, iy0), ih, iw, int(zoom), IH, IW))
+    if frame_valid is not None:
+        tensor(frame_valid, 'frame_valid', torch.uint8, (N,))
+    if out is not None:
+        tensor(out, 'out', torch.uint8, overlay_out_shape(out_format, N, IH, IW))
+    return dict(in_code=OVERLAY_IN_FORMATS[name], out_code=OVERLAY_OUT_FORMATS[out_format], matrix=YUV_MATRICES[matrix], N=N, IH=IH, IW=IW,
+                M=M, HH=HH, HW=HW, heat_rgb=color, amax=int(amax), ih=ih, iw=iw, ix0=ix0, iy0=iy0, zoom=int(zoom), mirror=int(bool(mirror)),
+                in_name=name)
+
+
 def vec_of(dtype):
     return 4 if dtype == torch.float32 else 8
 
@@ -472,6 +566,26 @@ class HipKernels(object):
         code = PIXEL_FORMATS['bgra' if format == 'bgr' and C == 4 else format]
         self._ck(self.lib.eve_screen_area_fmt_to_nchw(code, YUV_MATRICES[matrix], N, IH, IW, self._p(frames), OH, OW, self._p(out),
                                                       self._stream()))
+        return out
+
+    def overlay_render(self, frames, format, out_format='nv12', matrix='bt601', centres=None, marker_valid=None, marker_table=None,
+                       sx=1.0, sy=1.0, heat=None, heat_color=(255, 0, 0), amax=128, inset=None, inset_xy=(0, 0), zoom=1, mirror=False,
+                       frame_valid=None, out=None):
+        """The tracking overlay in one launch (include/eve_hip.h eve_overlay_render; tests/overlay_ref.py is the contract): frames
+        uint8 [N, ...] of `format` ('rgb' | 'bgr' [N,IH,IW,3|4], 'rgba' | 'bgra', 'nv12' | 'i420' [N,IH*3/2,IW], 'yuyv' [N,IH,IW,2])
+        -> uint8 [N,IH,IW,3] for out_format 'rgb' | 'bgr', [N,IH*3/2,IW] for 'nv12' | 'i420'.  Layers, each optional: heat float32
+        [N,HH,HW] blended in heat_color up to alpha amax; inset uint8 [N,h,w,3] RGB replacing the zoom*h x zoom*w rectangle at
+        inset_xy = (x0, y0); discs at centres float32 [N,M,2] (scaled by sx, sy to output pixels) where marker_valid uint8 [N,M] is
+        not 0, by marker_table int32 [M,4] = (r_fill, r_outline, fill 0xRRGGBB, outline 0xRRGGBB).  frame_valid uint8 [N]: a 0
+        gives the converted capture alone.  out: the buffer to write (a graph's output).  ValueError names a bad argument."""
+        a = overlay_check(frames, format, out_format, matrix, centres, marker_valid, marker_table, sx, sy, heat, heat_color, amax, inset,
+                          inset_xy, zoom, mirror, frame_valid, out)
+        if out is None:
+            out = torch.empty(overlay_out_shape(out_format, a['N'], a['IH'], a['IW']), dtype=torch.uint8, device=frames.device)
+        self._ck(self.lib.eve_overlay_render(a['in_code'], a['out_code'], a['matrix'], a['N'], a['IH'], a['IW'], self._p(frames), self._p(out),
+                                             a['M'], self._p(centres), self._p(marker_valid), self._p(marker_table), float(sx), float(sy),
+                                             self._p(heat), a['HH'], a['HW'], a['heat_rgb'], a['amax'], self._p(inset), a['ih'], a['iw'],
+                                             a['ix0'], a['iy0'], a['zoom'], a['mirror'], self._p(frame_valid), self._stream()))
         return out
 
     def frames_u8_to_stem(self, frames, scale, shift, out=None, dtype=torch.bfloat16):

@@ -72,6 +72,7 @@ class EVEStream(object):
         self._face_pose = torch.zeros((B, 13), dtype=torch.float64, device=self.device)
         self._graphs = {}
         self._graphs_key = None
+        self._render_tables = {}                 # OverlaySpec.key() -> its marker table, int32 [M, 4] on the device
 
     # ------------------------------------------------------------------ state
     def _state_tensors(self):
@@ -207,21 +208,145 @@ class EVEStream(object):
             self._pose_gate_host = not skip_invalid_pose
             self._pose_gate.fill_(self._pose_gate_host)              # a device value: the captured graphs read it, the host never waits
 
-    def _run(self, chunk, return_heatmaps, ragged=False, eye_mask=None, masked=False):
+    def _run(self, chunk, return_heatmaps, ragged=False, eye_mask=None, masked=False, render=None):
+        # render: None or a _render_plan; the keyword reaches _predict_sequence only then, so a step without it calls what it always did
+        extra = {} if render is None else {'render': self._render_hook(render, ragged, masked)}
         if 'face_landmarks' in chunk:            # the face-landmark form: the carried head pose goes along
             return self.model._predict_sequence(chunk, self._eye, self._ref, reset=self._flags, return_heatmaps=return_heatmaps,
                                                 lengths=self._lengths if ragged else None, masked=masked, eye_mask=eye_mask,
-                                                pose_gate=self._pose_gate if masked else None, face_state=self._face_pose)
+                                                pose_gate=self._pose_gate if masked else None, face_state=self._face_pose, **extra)
         if masked:
             return self.model._predict_sequence(chunk, self._eye, self._ref, reset=self._flags, return_heatmaps=return_heatmaps,
                                                 lengths=self._lengths if ragged else None, masked=True, eye_mask=eye_mask,
-                                                pose_gate=self._pose_gate if 'eye_pose' in chunk else None)
+                                                pose_gate=self._pose_gate if 'eye_pose' in chunk else None, **extra)
         if not ragged:
-            return self.model._predict_sequence(chunk, self._eye, self._ref, reset=self._flags, return_heatmaps=return_heatmaps)
+            return self.model._predict_sequence(chunk, self._eye, self._ref, reset=self._flags, return_heatmaps=return_heatmaps, **extra)
         return self.model._predict_sequence(chunk, self._eye, self._ref, reset=self._flags, return_heatmaps=return_heatmaps,
-                                            lengths=self._lengths)
+                                            lengths=self._lengths, **extra)
 
-    def step(self, chunk, return_heatmaps=False, lengths=None, eye_mask=None, skip_invalid_pose=False):
+    # ------------------------------------------------------------------ the overlay (step(chunk, render=spec))
+    def _render_plan(self, chunk, spec):
+        """step()'s `render` checked against the chunk -> what the launch needs beside the step's own results: the capture's key,
+        format and size, the matrix, sx and sy, the marker table on the device, the inset's place.  Every refusal is a ValueError
+        raised before anything is launched or captured."""
+        from .data import OverlaySpec, eye_patch_hw
+        from .kernels import pixel_format_shape
+        from .refine_net import SCREEN_FRAME_KEYS, screen_frame_key
+        if not isinstance(spec, OverlaySpec):
+            raise ValueError('step: render must be an eve_amd.OverlaySpec, got %s' % type(spec).__name__)
+        cfg = self.model.config
+        key = screen_frame_key(chunk)
+        if key is None:
+            raise ValueError('step: render draws onto the screen capture, and the chunk holds none (screen_frame, or one of %s)' %
+                             ', '.join(k_ for k_ in SCREEN_FRAME_KEYS if k_ != 'screen_frame'))
+        frames = chunk[key]
+        net_hw = (int(cfg.screen_size[1]), int(cfg.screen_size[0]))
+        if key == 'screen_frame' and (not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() != 5 or
+                                      frames.shape[4] not in (3, 4) or tuple(frames.shape[2:4]) == net_hw):
+            raise ValueError('step: render needs a full-resolution uint8 capture [B, Tc, IH, IW, 3 | 4] to draw onto; screen_frame is %s %s '
+                             '(a float or %d x %d screen_frame is the network\'s input, not a capture)' % (
+                                 getattr(frames, 'dtype', type(frames)), tuple(getattr(frames, 'shape', ())), net_hw[0], net_hw[1]))
+        fmt = SCREEN_FRAME_KEYS[key]
+        try:
+            IH, IW, _ = pixel_format_shape(frames, fmt, lead=2, name=key)
+        except TypeError as e:
+            raise ValueError('step: render: %s' % e)
+        if spec.out_format in ('nv12', 'i420') and (IH % 2 or IW % 2):
+            raise ValueError('step: render: out_format %s needs a capture of even size, got %d x %d' % (spec.out_format, IH, IW))
+        ref = self.model.refine_net
+        wants_final = spec.heat or any(m[0] == 'PoG_px_final' for m in spec.markers)
+        if wants_final and ref is None:
+            raise ValueError('step: render uses %s, which RefineNet produces, and the model has no RefineNet' % (
+                'the heat map (heatmap_final)' if spec.heat else 'PoG_px_final'))
+        results = tuple(getattr(self.model, 'PREDICTION_KEYS', ())) + ('valid', 'eye_valid', 'pose_valid')
+        for m in spec.markers:
+            for k_ in (m[0], m[1]):
+                if k_ is not None and k_ not in chunk and k_ not in results:
+                    raise ValueError('step: render: marker key %r is neither in the chunk nor a result of the step' % (k_,))
+        B, Tc = frames.shape[:2]
+        inset_hw = None
+        if spec.inset == 'eyes':
+            if 'left_eye_patch' in chunk:
+                p = chunk['left_eye_patch']
+                ph, pw = (int(p.shape[2]), int(p.shape[3])) if p.dtype == torch.uint8 else (int(p.shape[3]), int(p.shape[4]))
+            else:
+                ph, pw = eye_patch_hw(cfg)
+            inset_hw = (ph, 2 * pw)
+        elif spec.inset is not None:
+            p = chunk.get(spec.inset)
+            if (not torch.is_tensor(p) or p.dtype != torch.uint8 or p.dim() != 5 or tuple(p.shape[:2]) != (B, Tc) or p.shape[4] != 3):
+                raise ValueError('step: render: inset %r must be a uint8 [B, Tc, h, w, 3] entry of the chunk, got %s %s' % (
+                    spec.inset, getattr(p, 'dtype', type(p)), tuple(getattr(p, 'shape', ()))))
+            inset_hw = (int(p.shape[2]), int(p.shape[3]))
+        inset_xy = None
+        if inset_hw is not None:
+            z = spec.inset_zoom
+            inset_xy = spec.inset_xy if spec.inset_xy is not None else (IW - z * inset_hw[1], IH - z * inset_hw[0])
+            if inset_xy[0] < 0 or inset_xy[1] < 0 or inset_xy[0] + z * inset_hw[1] > IW or inset_xy[1] + z * inset_hw[0] > IH:
+                raise ValueError('step: render: the inset (%d x %d at zoom %d, top-left %s) does not lie inside the %d x %d capture' % (
+                    inset_hw[0], inset_hw[1], z, tuple(inset_xy), IH, IW))
+        table = None
+        if spec.markers:
+            table = self._render_tables.get(spec.key())
+            if table is None:                    # made here, before any capture: a host-to-device copy
+                table = self._render_tables[spec.key()] = torch.tensor(spec.marker_table(), dtype=torch.int32).reshape(-1, 4).to(self.device)
+        matrix = spec.matrix if spec.matrix is not None else (ref.yuv_matrix if ref is not None else 'bt601')
+        return {'spec': spec, 'key': key, 'format': fmt, 'matrix': matrix, 'table': table, 'inset_xy': inset_xy,
+                'sx': IW / float(cfg.actual_screen_size[0]), 'sy': IH / float(cfg.actual_screen_size[1])}
+
+    def _render_hook(self, plan, ragged, masked):
+        """The closure EVE._predict_sequence calls last: gathers the layers from the step's own tensors and issues the one
+        eve_overlay_render launch on the capture where it lies (the chunk tensor; under a graph, its input buffer)."""
+        from .data import quantise_patches
+        spec = plan['spec']
+
+        def render(d, inter, out):
+            frames = d[plan['key']]
+            B, Tc = frames.shape[:2]
+            N = B * Tc
+            flat = frames.reshape((N,) + tuple(frames.shape[2:]))
+
+            def look(key):
+                for src in (out, inter, d):
+                    if key in src:
+                        return src[key]
+                raise ValueError('step: render: %r is neither in the chunk nor a result of this step' % (key,))
+
+            kw = {}
+            if spec.markers:
+                kw['centres'] = torch.stack([look(m[0]).reshape(N, 2).float() for m in spec.markers], dim=1).contiguous()
+                kw['marker_table'], kw['sx'], kw['sy'] = plan['table'], plan['sx'], plan['sy']
+                if any(m[1] is not None for m in spec.markers):
+                    ones = torch.ones((N,), dtype=torch.bool, device=frames.device)
+                    kw['marker_valid'] = torch.stack([ones if m[1] is None else look(m[1]).reshape(N) != 0 for m in spec.markers],
+                                                     dim=1).to(torch.uint8).contiguous()
+            if spec.heat:
+                hm = look('heatmap_final')
+                kw.update(heat=hm.reshape((N,) + tuple(hm.shape[-2:])).float().contiguous(), heat_color=spec.heat_color, amax=spec.heat_amax)
+            if spec.inset == 'eyes':
+                if 'left_eye_patch' in d:
+                    left, right = d['left_eye_patch'], d['right_eye_patch']
+                    left, right = (left[..., :3], right[..., :3]) if left.dtype == torch.uint8 else (quantise_patches(left), quantise_patches(right))
+                    h, w = left.shape[2:4]
+                    inset = torch.cat([right, left], dim=3).reshape(N, h, 2 * w, 3)
+                else:                            # a camera form: the patches once more, in the float form (two launches)
+                    _, _, _, _, lw, rw, _, to_nchw = self.model.eye_net._camera_cutters(d)
+                    inset = torch.cat([quantise_patches(to_nchw(rw)), quantise_patches(to_nchw(lw))], dim=2)
+                kw['inset'] = inset.contiguous()
+            elif spec.inset is not None:
+                p = d[spec.inset]
+                kw['inset'] = p.reshape((N,) + tuple(p.shape[2:]))
+            if 'inset' in kw:
+                kw.update(inset_xy=plan['inset_xy'], zoom=spec.inset_zoom, mirror=spec.inset_mirror)
+            if masked:
+                kw['frame_valid'] = out['valid'].reshape(N).to(torch.uint8).contiguous()
+            elif ragged:
+                kw['frame_valid'] = (torch.arange(Tc, device=frames.device)[None, :] < self._lengths[:B, None]).reshape(N).to(torch.uint8).contiguous()
+            rendered = default_kernels().overlay_render(flat, plan['format'], spec.out_format, plan['matrix'], **kw)
+            out['rendered'] = rendered.view((B, Tc) + tuple(rendered.shape[1:]))
+        return render
+
+    def step(self, chunk, return_heatmaps=False, lengths=None, eye_mask=None, skip_invalid_pose=False, render=None):
         """One chunk of every stream: chunk holds [B, Tc, ...] tensors on the model's device -- the eyes (below), {left,right}_h,
         {left,right}_o, {left,right}_R, head_R, camera_transformation, inv_camera_transformation, pixels_per_millimeter, millimeters_per_pixel, and screen_frame when the config loads screen content.  Returns the
         prediction keys of EVE(output_predictions=True) as [B, Tc, ...] tensors (heatmap_final [B, Tc, 1, H, W] on request).
@@ -329,7 +454,22 @@ class EVEStream(object):
           * Masked frames are computed like real ones (no compute is skipped): the step costs a full chunk plus one plan launch,
             six small row gathers and ten elementwise selects (profiles/stream_mask_notes.md).  The mask is one more input
             buffer of the graph: one masked graph per chunk shape serves every mask pattern.
-        A step with neither argument issues exactly the kernel calls it always did."""
+        A step with neither argument issues exactly the kernel calls it always did.
+
+        render: None, or an eve_amd.OverlaySpec -- the result gains `rendered`, the chunk's full-resolution screen capture
+        (whichever screen_frame* key holds it; a float or network-sized screen_frame is refused: a capture is needed) annotated
+        on the device by one eve_overlay_render launch at the end of the step and inside the captured graph: uint8 [B, Tc, IH, IW, 3]
+        for out_format 'rgb' / 'bgr', [B, Tc, IH*3/2, IW] for 'nv12' / 'i420', a graph output buffer like the others.  The launch
+        reads the capture where it lies (the graph's input buffer: nothing is copied).  Markers are read from the step's own result
+        (PoG_px_initial, PoG_px_final) or the chunk (a caller's PoG_px_gt), in actual_screen_size pixels, and scaled by the capture's
+        size over actual_screen_size; heat=True blends this step's heatmap_final (returned or not); inset='eyes' shows the eye
+        patches as [right | left]: uint8 patch chunks as they are, float patches quantised by clamp(rint((p + 1) * 127.5), 0, 255),
+        and in the camera forms the patches cut once more in the float form (two more eye-warp launches) and quantised the same
+        way.  On a ragged or masked step `valid` is the launch's frame_valid: a frame that was not consumed comes out as the bare
+        converted capture.  PoG_px_final and the heat map need RefineNet (ValueError without).  The spec is part of the graph's
+        key; tests/overlay_ref.py states the arithmetic, exact to the bit.  Not offered: the reference's residual lines from an
+        estimate to the ground truth, its legend text, gaze-ray arrows on the eye image, row pitches, 10-bit surfaces, a gradient.
+        render=None issues exactly the launches the step always issued."""
         if self.model.training:
             raise ValueError('EVEStream runs inference only: the model was switched to training mode')
         B, Tc = eye_input(chunk).shape[:2]
@@ -343,6 +483,8 @@ class EVEStream(object):
             lengths = self._host_lengths(lengths, Tc)
         if eye_mask is not None:
             eye_mask = self._eye_mask(eye_mask, Tc)
+        if render is not None:
+            render = self._render_plan(chunk, render)
         if ragged:
             self._upload_lengths(lengths)
         if masked and has_pose_form(chunk):
@@ -350,7 +492,7 @@ class EVEStream(object):
         self._upload_resets()
         with torch.no_grad():
             if self.use_graph:
-                entry = self._graph_for(chunk, bool(return_heatmaps), ragged, masked)
+                entry = self._graph_for(chunk, bool(return_heatmaps), ragged, masked, render)
                 for key, buf in entry['inputs'].items():
                     buf.copy_(chunk[key], non_blocking=True)
                 if masked:
@@ -363,7 +505,7 @@ class EVEStream(object):
             else:
                 if eye_mask is not None and eye_mask.device != self.device:
                     eye_mask = torch.empty(eye_mask.shape, dtype=torch.uint8, device=self.device).copy_(eye_mask, non_blocking=True)
-                out = self._run(chunk, return_heatmaps, ragged, eye_mask, masked)
+                out = self._run(chunk, return_heatmaps, ragged, eye_mask, masked, render)
             if ragged and not masked:
                 out['valid'] = torch.arange(Tc, device=self.device)[None, :] < self._lengths[:self.num_streams, None]
         if self._flags_set:
@@ -382,20 +524,26 @@ class EVEStream(object):
     def _weights_key(self):
         return tuple(_module_key(m) for m in (self.model.eye_net, self.model.refine_net) if m is not None)
 
-    def _graph_for(self, chunk, return_heatmaps, ragged=False, masked=False):
+    def _graph_key(self, chunk, return_heatmaps, ragged=False, masked=False, render=None):
+        """What a captured graph is good for: the step's mode, both YUV matrices, the overlay (render: None or a _render_plan -- its
+        OverlaySpec by value) and every chunk tensor's key, shape and dtype."""
+        ref = self.model.refine_net
+        spec = None if render is None else render['spec'].key()
+        return (return_heatmaps, ragged, masked, self.model.eye_net.yuv_matrix, None if ref is None else ref.yuv_matrix, spec) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
+
+    def _graph_for(self, chunk, return_heatmaps, ragged=False, masked=False, render=None):
         wk = self._weights_key()
         if wk != self._graphs_key:               # new weights: new packs, new graphs (a replay never reads stale packs)
             self._graphs = {}
             self._graphs_key = wk
-        ref = self.model.refine_net
-        key = (return_heatmaps, ragged, masked, self.model.eye_net.yuv_matrix, None if ref is None else ref.yuv_matrix) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
+        key = self._graph_key(chunk, return_heatmaps, ragged, masked, render)
         entry = self._graphs.get(key)
         if entry is None:
-            entry = self._graphs[key] = self._capture(chunk, return_heatmaps, ragged, masked)
+            entry = self._graphs[key] = self._capture(chunk, return_heatmaps, ragged, masked, render)
             self._graphs_key = self._weights_key()
         return entry
 
-    def _capture(self, chunk, return_heatmaps, ragged=False, masked=False):
+    def _capture(self, chunk, return_heatmaps, ragged=False, masked=False, render=None):
         """Capture one step for this chunk shape (train.Trainer._capture's recipe): inputs copied into fixed buffers, two eager
         warm-up steps off the default stream (packs, lazily built filters, allocator) with the carried states put back
         afterwards, the kernels' scratch allocated before the capture, one stream, no side branches.  A masked graph has one more
@@ -412,7 +560,7 @@ class EVEStream(object):
             carried = self._state_tensors() + [self._face_pose]
             snap = [t.clone() for t in carried]
             for _ in range(2):
-                self._run(static, return_heatmaps, ragged, eye_mask, masked)
+                self._run(static, return_heatmaps, ragged, eye_mask, masked, render)
             for t, s_ in zip(carried, snap):
                 t.copy_(s_)
         torch.cuda.current_stream().wait_stream(side)
@@ -422,7 +570,7 @@ class EVEStream(object):
             k.prepare_graph_workspace(self.device)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            out = self._run(static, return_heatmaps, ragged, eye_mask, masked)
+            out = self._run(static, return_heatmaps, ragged, eye_mask, masked, render)
         m = self.model
         keep = (m.eye_net._packs, getattr(m.eye_net, '_stream_w', None), m.refine_net._packs if m.refine_net is not None else None)
         return {'graph': graph, 'inputs': static, 'outputs': out, 'keep': keep, 'eye_mask': eye_mask}

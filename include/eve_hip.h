@@ -844,6 +844,51 @@ int eve_eye_warp_fmt_to_stem(int dtype /* EVE_DT_BF16 | EVE_DT_F16 */, int forma
  * UYVY / NV21 / P010 or any 10-bit layout, bilinear chroma up-sampling.                                                      */
 int eve_screen_area_fmt_to_nchw(int format, int matrix, long long N, int IH, int IW, const uint8_t* src, int OH, int OW,
                                 float* dst_nchw, eve_stream_t stream);
+/* The tracking overlay: one launch that turns N full-resolution captures into the annotated frames an encoder or a display reads.
+ * src: N frames back to back in `in_format`, byte-linear as above (EVE_PIX_RGB / _RGBA: [IH][IW][3 | 4], channel 0 red; these two
+ * codes are taken here only).  dst: `out_format` EVE_PIX_RGB or _BGR ([IH][IW][3]), EVE_PIX_NV12 or _I420 ([IH*3/2][IW], IH and IW
+ * even).  `matrix` serves both directions.  Per output pixel (X, Y), in 8-bit RGB, the layers in this order
+ * (tests/overlay_ref.py is the contract in numpy; the result equals it bit for bit -- after the three float32 quantisations
+ * below everything is integer arithmetic):
+ *   1. source   the capture pixel converted exactly as eve_eye_warp_fmt_to_nchw converts a tap (chroma the nearest sample).
+ *   2. heat     heat float [N][HH][HW] (NULL: no layer), colour heat_rgb = 0xRRGGBB, amax in 0..255, HH, HW <= 1024:
+ *                 q = (int)rint(min(max(h, 0), 1) * 255) in float32, NaN -> 0;
+ *                 nx = (2X+1)*HW - IW;  fx = max(nx, 0)*128 / IW;  x0 = min(fx >> 8, HW-1);  x1 = min(x0+1, HW-1);  wx = fx & 255
+ *                 (the same in y: bilinear, align_corners = false, 8 fractional bits);
+ *                 a = (q00*(256-wx)*(256-wy) + q01*wx*(256-wy) + q10*(256-wx)*wy + q11*wx*wy + 32768) >> 16;
+ *                 alpha = (a*amax + 127) / 255;   per channel v = (v*(255-alpha) + c*alpha + 127) / 255.
+ *   3. inset    inset uint8 [N][ih][iw][3] RGB (NULL: no layer): an opaque replace of the zoom*ih x zoom*iw rectangle whose top-left
+ *               pixel is (ix0, iy0) by inset[(Y-iy0)/zoom][(X-ix0)/zoom] (mirror != 0: column iw-1-j); zoom in 1..4.
+ *   4. markers  M <= 8, in index order: centres float [N][M][2] in the caller's pixel units, marker_valid uint8 [N][M] (NULL: all
+ *               valid), marker_table int [M][4] = (r_fill, r_outline, fill 0xRRGGBB, outline 0xRRGGBB), radii in output pixels,
+ *               0..255.  qx = rint((x * sx) * 8) in float32, each product rounded (qy with sy), ties to even: sx = IW / (the width
+ *               the centres refer to).  Not drawn: marker_valid == 0, a coordinate that is not finite, |q| > 2^20.  A disc of
+ *               radius r covers n = #{(i, j) in 0..3 : (8X+2i+1-qx)^2 + (8Y+2j+1-qy)^2 <= 64 r^2} of a pixel's 4 x 4 sub-samples
+ *               and v = (v*(16-n) + c*n + 8) >> 4; the outline disc first (r_outline > 0 only), then the fill disc.
+ *   5. output   EVE_PIX_RGB / _BGR: the three bytes.  NV12 / I420, with K = sign(c) * floor(|c| * 2^20 + 0.5) of each coefficient:
+ *                 Y = clamp((KYR*R + KYG*G + KYB*B + (y0 << 20) + 2^19) >> 20, 0, 255) per pixel (arithmetic shift);
+ *                 U, V likewise with offset 128 from the 2 x 2 block's (sum of four + 2) >> 2 per channel.
+ *                 matrix          y0   Y row                    U row                           V row
+ *                 EVE_YUV_BT601   16   0.257  0.504  0.098      -0.148    -0.291    0.439       0.439  -0.368    -0.071
+ *                 EVE_YUV_BT709   16   0.183  0.614  0.062      -0.101    -0.339    0.439       0.439  -0.399    -0.040
+ *                 EVE_YUV_JFIF     0   0.299  0.587  0.114      -0.168736 -0.331264 0.5         0.5    -0.418688 -0.081312
+ *               A round trip through eve_eye_warp_fmt_to_nchw's inverse is off by at most (2, 1, 2) in (R, G, B) under BT601 and
+ *               BT709 and by at most (1, 1, 1) under JFIF, over all 2^24 colours.
+ * frame_valid uint8 [N] (NULL: all valid): a 0 gives layers 1 and 5 alone, the converted capture.
+ * One launch; a workgroup takes a (frame, row pair), a thread 2 rows x 8 columns in registers (csrc/overlay.hip).  Kernel names:
+ * overlay_kernel<I,O,true | false> with I in rgb, rgba, bgr, bgra, nv12, i420, yuyv and O in rgb, bgr, nv12, i420; true is the vector
+ * form (IW a multiple of 8, IH even, src and dst 16-byte aligned), false the byte form with the same bits.  No address is computed
+ * from a marker coordinate.  Refused without a launch, the message beginning "overlay_render:": bad arguments, unknown formats or
+ * matrix, IH or IW > 16384, odd sizes of a YUV side, N * ceil(IH/2) >= 2^31, M outside 0..8, markers without centres or table,
+ * sx or sy not finite, HH or HW outside 1..1024, amax or heat_rgb out of range, zoom outside 1..4, an inset rectangle that does
+ * not lie inside the frame.  Not offered: the reference's residual lines from an estimate to the ground truth, its legend text,
+ * gaze-ray arrows on the eye image, row pitches, 10-bit surfaces, a gradient.                                                 */
+enum { EVE_PIX_RGB = 5, EVE_PIX_RGBA = 6 };
+int eve_overlay_render(int in_format, int out_format, int matrix, long long N, int IH, int IW, const uint8_t* src, uint8_t* dst,
+                       int M, const float* centres, const uint8_t* marker_valid, const int* marker_table, float sx, float sy,
+                       const float* heat /* may be NULL */, int HH, int HW, int heat_rgb, int amax,
+                       const uint8_t* inset /* may be NULL */, int ih, int iw, int ix0, int iy0, int zoom, int mirror,
+                       const uint8_t* frame_valid /* may be NULL */, eve_stream_t stream);
 /* Eye normalisation derived from the head pose, one launch for both eyes of N frames: everything the pipeline reads per frame and
  * eye follows from the face tracker's solvePnP result and the camera matrix.  pose [N][18] float, widened to float64:
  *   (fx, fy, cx, cy,  r0, r1, r2,  t0, t1, t2,  l0, l1, l2,  q0, q1, q2,  focal_norm, distance_norm)

@@ -3,7 +3,7 @@
 CLSTM RefineNet), synthetic weights and clips.  One JSON line per shape:
 
     python tools/bench_stream.py --shapes 1x1 32x1 32x30 [--dtype bf16] [--steps 50] [--fused-tail] [--ragged | --masked] [--repeat N]
-                                 [--screen 1920x1080 [--screen-format nv12]]
+                                 [--screen 1920x1080 [--screen-format nv12] [--render]]
 
 B x Tc = streams x frames per step.  For Tc > 1 the same clips also go through one EVE.eval() pass (`eval_ms`): what the
 stream costs over the plain clip pass.  --fused-tail runs the EyeNet tail as one eve_eye_tail_stream_fwd launch
@@ -16,7 +16,9 @@ floats) in the same process: what one more launch in the graph costs at the leas
 --screen WxH feeds uint8 screen captures of that size, [B, Tc, H, W, 3], instead of the pre-resized float screens: the step
 then holds the area resize (eve_screen_u8_area_to_nchw) and the copy of the captures into the graph's input buffer; with
 --screen-format nv12 | i420 | yuyv the captures go in as a decoder delivers them, under screen_frame_<format> (eve_screen_area_fmt_to_nchw;
-`screen_bytes` is what one step copies into the graph for the screen).  --repeat N measures every shape N times in one process (`step_ms_runs`; `step_ms` is their median): the run-to-run spread."""
+`screen_bytes` is what one step copies into the graph for the screen).  --render (with --screen) steps with render=OverlaySpec(heat=True):
+the default two markers, the heat map and the eyes inset drawn onto the capture by one eve_overlay_render launch inside the graph, NV12
+out (`rendered_bytes` per step); the A/B of the overlay is the same command line without it.  --repeat N measures every shape N times in one process (`step_ms_runs`; `step_ms` is their median): the run-to-run spread."""
 import argparse
 import json
 import os
@@ -75,9 +77,12 @@ def main():
     ap.add_argument('--repeat', type=int, default=1)
     ap.add_argument('--screen', default=None, metavar='WxH', help='feed uint8 screen captures of this size, e.g. 1920x1080')
     ap.add_argument('--screen-format', default='rgb', choices=('rgb', 'nv12', 'i420', 'yuyv'), help='the layout of the --screen captures')
+    ap.add_argument('--render', action='store_true', help='step with render=OverlaySpec(heat=True): the overlay launch inside the graph')
     args = ap.parse_args()
     if args.screen_format != 'rgb' and not args.screen:
         ap.error('--screen-format needs --screen WxH')
+    if args.render and not args.screen:
+        ap.error('--render draws onto a capture: it needs --screen WxH')
     if args.ragged and args.masked:
         ap.error('--ragged and --masked are two measurements: give one')
     cfg = eve_amd.reset_standalone_config()
@@ -108,9 +113,10 @@ def main():
         clip = {k: full[k] for k in INPUT_KEYS + ('screen_frame_nv12', 'screen_frame_i420', 'screen_frame_yuyv') if k in full}
         stream = eve_amd.EVEStream(model, B)
         rng = np.random.default_rng(B * 1000 + Tc)
-        step = (lambda: stream.step(clip, lengths=rng.integers(0, Tc + 1, size=B))) if args.ragged else (lambda: stream.step(clip))
+        extra = {'render': eve_amd.OverlaySpec(heat=True)} if args.render else {}
+        step = (lambda: stream.step(clip, lengths=rng.integers(0, Tc + 1, size=B), **extra)) if args.ragged else (lambda: stream.step(clip, **extra))
         if args.masked:
-            step = lambda: stream.step(clip, eye_mask=rng.random((B, Tc, 2)) >= 0.2)
+            step = lambda: stream.step(clip, eye_mask=rng.random((B, Tc, 2)) >= 0.2, **extra)
         for _ in range(3):
             step()                                           # capture + warm replays
         torch.cuda.synchronize()
@@ -119,6 +125,8 @@ def main():
                'screen': args.screen or 'float', 'step_ms': runs[len(runs) // 2]}
         if screen is not None:
             res['screen_format'], res['screen_bytes'] = args.screen_format, full[screen_key].numel()
+        if args.render:
+            res['render'], res['rendered_bytes'] = 'nv12', step()['rendered'].numel()
         if len(runs) > 1:
             res['step_ms_runs'] = runs
         if args.masked:
