@@ -60,6 +60,14 @@ class EyeTailWeights(Structure):
                                         'g2_w', 'p0_w', 'p0_b', 'p2_w', 'p2_b')]
 
 
+class Surface(Structure):
+    """include/eve_hip.h eve_surface: a frame addressed through plane offsets, pitches and sample steps (data.SurfaceLayout
+    computes it)"""
+    _fields_ = [('struct_bytes', c_int), ('kind', c_int), ('width', c_int), ('height', c_int), ('frame_stride', c_longlong),
+                ('frame_bytes', c_longlong), ('offset', c_longlong * 3), ('pitch', c_int * 3), ('step', c_int * 3),
+                ('xshift', c_int), ('yshift', c_int)]
+
+
 VEC_TERMS_MAX = 32
 PACK_BATCH_MAX = 48
 ABI_VERSION = 10         # include/eve_hip.h EVE_ABI_VERSION
@@ -182,6 +190,9 @@ SIGNATURES = {
     'eve_eye_warp_fmt_to_nchw': [I, I, L, I, I, P, P, P, I, I, P, P],
     'eve_eye_warp_fmt_to_stem': [I, I, I, L, I, I, P, P, P, I, I, P, P],
     'eve_screen_area_fmt_to_nchw': [I, I, L, I, I, P, I, I, P, P],
+    'eve_eye_warp_surface_to_nchw': [POINTER(Surface), I, L, P, P, P, I, I, P, P],
+    'eve_eye_warp_surface_to_stem': [I, POINTER(Surface), I, L, P, P, P, I, I, P, P],
+    'eve_screen_area_surface_to_nchw': [POINTER(Surface), I, L, P, I, I, P, P],
     'eve_overlay_render': [I, I, I, L, I, I, P, P, I, P, P, P, F, F, P, I, I, I, I, P, I, I, I, I, I, I, P, P],
 }
 EXPORTS = sorted(list(SIGNATURES) + ['eve_abi_version', 'eve_last_error', 'eve_last_kernel'])

@@ -34,7 +34,15 @@
 // warp_value, layouts) is the same code.  A YUV tap is three single-byte loads (luma, and the nearest chroma sample of its 2 x 2
 // block or pair) and the integer matrix of include/eve_hip.h; a tap outside the frame adds nothing, as before.  The plain
 // kernels are the FMT = PIX_RGB instantiation of the same templates and compile to the instructions they had without them.
+//
+// The surface variant (eve_eye_warp_surface_to_nchw / _to_stem, surface.h, tests/surface_ref.py) takes the frames as a decoder or a
+// capture API leaves them in memory -- rows with a pitch, coded rows, aligned planes, a crop; NV21, YV12, UYVY, P010's high bytes,
+// pitched BGRA -- through the descriptor's address rule: where tap_rgb<FMT> stands, three byte loads at
+// offset[c] + (y >> ys) * pitch[c] + (x >> xs) * step[c] in 64-bit arithmetic (surf_tap_terms: a row term and a column term per
+// component, shared by the four taps), the descriptor by value in the kernel's arguments.
+// The two surface codes are two more values of FMT; the kernels above keep their instructions (compared in the assembly).
 #include "common.h"
+#include "surface.h"
 #include "yuv_rgb.h"
 
 namespace eve {
@@ -54,6 +62,9 @@ struct EyeWarpArgs {
 
 // what a frame holds (EVE_PIX_* of include/eve_hip.h; PIX_RGB is the four existing entry points' layout, C = 3 or 4)
 constexpr int PIX_RGB = -1;
+// a surface (surface.h): the taps go through the descriptor's address rule; components R, G, B or Y, U, V
+constexpr int PIX_SURF_RGB = -2, PIX_SURF_YUV = -3;
+constexpr bool is_surface(const int FMT) { return FMT == PIX_SURF_RGB || FMT == PIX_SURF_YUV; }
 
 struct EyeWarpFmtArgs {
     EyeWarpArgs a;                       // a.C: 3, or 4 for BGRA; the YUV formats do not read it
@@ -111,10 +122,12 @@ __device__ __forceinline__ Lens load_lens(const float* __restrict__ row) {
 }
 
 // the three channels' fixed-point sums S (<= 255 * 65536) of output pixel (oy, ox); all zero outside.  LENS: (u, v) goes through
-// the distortion model of L first, unless L.on is false.  FMT: the taps come through tap_rgb<FMT> (coef: its matrix).
+// the distortion model of L first, unless L.on is false.  FMT: the taps come through tap_rgb<FMT> (coef: its matrix), or through
+// the address terms of the descriptor sf for the two surface codes.
 template <bool LENS, int FMT = PIX_RGB>
 __device__ __forceinline__ void warp_sums(const double (&m)[9], const Lens& L, const uint8_t* __restrict__ frame, const int IH, const int IW,
-                                          const int C, const int oy, const int ox, uint32_t (&S)[3], const YuvCoef& coef = YuvCoef()) {
+                                          const int C, const int oy, const int ox, uint32_t (&S)[3], const YuvCoef& coef = YuvCoef(),
+                                          const Surf& sf = Surf()) {
 #pragma clang fp contract(off)
     const double dx = (double)ox, dy = (double)oy;
     const double X = (m[0] * dx + m[1] * dy) + m[2];
@@ -143,6 +156,8 @@ __device__ __forceinline__ void warp_sums(const double (&m)[9], const Lens& L, c
     const int x0 = fu >> 8, y0 = fv >> 8;                                              // in [-1, IW] / [-1, IH]
     const uint32_t ax = (uint32_t)(fu & 255), ay = (uint32_t)(fv & 255);
     const uint32_t w[4] = {(256u - ax) * (256u - ay), ax * (256u - ay), (256u - ax) * ay, ax * ay};
+    long long row[2][3], col[2][3];                      // a surface's address terms, shared by the four taps
+    if constexpr (is_surface(FMT)) surf_tap_terms<FMT == PIX_SURF_YUV>(sf, y0, x0, row, col);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const int y = y0 + (t >> 1), x = x0 + (t & 1);
@@ -151,6 +166,13 @@ __device__ __forceinline__ void warp_sums(const double (&m)[9], const Lens& L, c
                 const uint8_t* p = frame + ((size_t)y * IW + x) * C;
 #pragma unroll
                 for (int c = 0; c < 3; ++c) S[c] += w[t] * (uint32_t)p[c];
+            } else if constexpr (is_surface(FMT)) {
+                uint32_t rgb[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) rgb[c] = frame[row[t >> 1][c] + col[t & 1][c]];
+                if constexpr (FMT == PIX_SURF_YUV) yuv_to_rgb((int)rgb[0], (int)rgb[1], (int)rgb[2], coef, rgb);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) S[c] += w[t] * rgb[c];
             } else {
                 uint32_t rgb[3];
                 tap_rgb<FMT>(frame, IH, IW, y, x, coef, rgb);
@@ -174,7 +196,7 @@ __device__ __forceinline__ float warp_value(uint32_t S) {
 // schedule the plain kernels differently from a kernel that holds this loop itself.
 template <typename O, bool LENS, int FMT = PIX_RGB>
 __device__ __forceinline__ void eye_warp_items(const EyeWarpArgs a, const uint8_t* src, const float* warps, const float* lens, void* dst,
-                                               const YuvCoef coef = YuvCoef()) {
+                                               const YuvCoef coef = YuvCoef(), const Surf sf = Surf()) {
     constexpr bool PACKED = !std::is_same<O, float>::value;
     const int rows = PACKED ? a.OH + 6 : a.OH, cols = PACKED ? a.OW + 8 : a.OW;      // of the output image, pad ring included
     for (long long item = blockIdx.x; item < a.items; item += gridDim.x) {
@@ -186,13 +208,15 @@ __device__ __forceinline__ void eye_warp_items(const EyeWarpArgs a, const uint8_
         for (int i = 0; i < 9; ++i) m[i] = (double)warps[n * 9 + i];
         Lens L = {};
         if constexpr (LENS) L = load_lens(lens + n * 12);
-        const uint8_t* frame = src + (FMT == PIX_RGB ? (size_t)n * a.IH * a.IW * a.C : (size_t)n * frame_bytes<FMT>(a.IH, a.IW, a.C));
+        const uint8_t* frame;
+        if constexpr (is_surface(FMT)) frame = src + n * sf.frame_stride;
+        else frame = src + (FMT == PIX_RGB ? (size_t)n * a.IH * a.IW * a.C : (size_t)n * frame_bytes<FMT>(a.IH, a.IW, a.C));
         for (int t = threadIdx.x; t < nr * cols; t += EW_THREADS) {
             const int r = r0 + t / cols, col = t % cols;
             const int oy = PACKED ? r - 3 : r, ox = PACKED ? col - 4 : col;
             const bool pixel = !PACKED || (oy >= 0 && oy < a.OH && ox >= 0 && ox < a.OW);
             uint32_t S[3] = {0u, 0u, 0u};
-            if (pixel) warp_sums<LENS, FMT>(m, L, frame, a.IH, a.IW, a.C, oy, ox, S, coef);
+            if (pixel) warp_sums<LENS, FMT>(m, L, frame, a.IH, a.IW, a.C, oy, ox, S, coef, sf);
             if constexpr (PACKED) {
                 uint2 q = make_uint2(0u, 0u);
                 if (pixel) {
@@ -228,6 +252,20 @@ __global__ __launch_bounds__(EW_THREADS) void eye_warp_fmt_kernel(const EyeWarpF
                                                                   const float* __restrict__ warps, const float* __restrict__ lens,
                                                                   void* __restrict__ dst) {
     eye_warp_items<O, LENS, FMT>(fa.a, src, warps, lens, dst, fa.coef);
+}
+
+// YUV: the surface's kind; sa.a.IH x sa.a.IW is its visible region; lens is read only with LENS
+struct EyeWarpSurfArgs {
+    EyeWarpArgs a;
+    YuvCoef coef;
+    Surf sf;
+};
+
+template <bool YUV, bool LENS, typename O>
+__global__ __launch_bounds__(EW_THREADS) void eye_warp_surface_kernel(const EyeWarpSurfArgs sa, const uint8_t* __restrict__ src,
+                                                                      const float* __restrict__ warps, const float* __restrict__ lens,
+                                                                      void* __restrict__ dst) {
+    eye_warp_items<O, LENS, YUV ? PIX_SURF_YUV : PIX_SURF_RGB>(sa.a, src, warps, lens, dst, sa.coef, sa.sf);
 }
 
 // the checks the entry points share; -> nullptr or what is wrong
@@ -294,6 +332,39 @@ void eye_warp_fmt_launch(int dtype, int format, const EyeWarpFmtArgs& fa, const 
         EW_FMT_CASE(EVE_PIX_I420, "i420")
         EW_FMT_CASE(EVE_PIX_YUYV, "yuyv")
     }
+}
+
+// one launch of eye_warp_surface_kernel<kind == YUV, lens != NULL, O> under its name, "eye_warp_surface_kernel<yuv,plain,float>"
+#define EW_SURF_NAME(kind, lens, O) "eye_warp_surface_kernel<" kind "," lens "," O ">"
+#define EW_SURF_ARGS grid, dim3(EW_THREADS), 0, stream, sa, frames, warps, lens, dst
+#define EW_SURF_CASE(YUV, kind, LENS, lname)                                                                                       \
+    if (dtype == EVE_DT_F32) EVE_LAUNCH(EW_SURF_NAME(kind, lname, "float"), (eye_warp_surface_kernel<YUV, LENS, float>), EW_SURF_ARGS);            \
+    else if (dtype == EVE_DT_BF16) EVE_LAUNCH(EW_SURF_NAME(kind, lname, "eve::bf16_t"), (eye_warp_surface_kernel<YUV, LENS, bf16_t>), EW_SURF_ARGS); \
+    else EVE_LAUNCH(EW_SURF_NAME(kind, lname, "eve::f16_t"), (eye_warp_surface_kernel<YUV, LENS, f16_t>), EW_SURF_ARGS);
+
+// both surface entry points behind their checks: dtype EVE_DT_F32 is the float form, the other two the packed one
+int eye_warp_surface(const char* who, int dtype, bool packed, const eve_surface* surface, int matrix, long long N, const uint8_t* frames,
+                     const float* warps, const float* lens, int OH, int OW, void* dst, hipStream_t stream) {
+    char msg[192];
+    const char* why = surface_refusal(surface, matrix, N);
+    if (!why) why = eye_warp_refusal(N, surface->height, surface->width, 3, frames, warps, OH, OW, dst);
+    if (!why && packed && dtype != EVE_DT_BF16 && dtype != EVE_DT_F16) why = "dtype must be bf16 or f16 (the stem's packed input)";
+    if (why) {
+        snprintf(msg, sizeof(msg), "%s: %s", who, why);
+        return set_error_msg(msg);
+    }
+    const bool yuv = surface->kind == EVE_SURF_YUV;
+    EyeWarpSurfArgs sa;
+    sa.a = eye_warp_args(N, surface->height, surface->width, 3, OH, OW, packed ? OH + 6 : OH);
+    sa.coef = YUV_MATRICES[yuv ? matrix : 0];
+    sa.sf = surf_of(*surface);
+    const dim3 grid((unsigned)(sa.a.items < EW_MAX_BLOCKS ? sa.a.items : EW_MAX_BLOCKS));
+    if (yuv) {
+        if (lens) { EW_SURF_CASE(true, "yuv", true, "lens") } else { EW_SURF_CASE(true, "yuv", false, "plain") }
+    } else {
+        if (lens) { EW_SURF_CASE(false, "rgb", true, "lens") } else { EW_SURF_CASE(false, "rgb", false, "plain") }
+    }
+    return 0;
 }
 
 }  // namespace
@@ -392,6 +463,24 @@ extern "C" int eve_eye_warp_fmt_to_stem(int dtype, int format, int matrix, long 
     }
     eye_warp_fmt_launch(dtype, format, eye_warp_fmt_args(format, matrix, N, IH, IW, OH, OW, OH + 6), frames, warps, lens, x_padded,
                         (hipStream_t)stream);
+    EVE_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int eve_eye_warp_surface_to_nchw(const eve_surface* surface, int matrix, long long N, const uint8_t* frames, const float* warps,
+                                            const float* lens, int OH, int OW, float* dst_nchw, eve_stream_t stream) {
+    if (const int rc = eye_warp_surface("eye_warp_surface_to_nchw", EVE_DT_F32, false, surface, matrix, N, frames, warps, lens, OH, OW, dst_nchw,
+                                        (hipStream_t)stream))
+        return rc;
+    EVE_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int eve_eye_warp_surface_to_stem(int dtype, const eve_surface* surface, int matrix, long long N, const uint8_t* frames,
+                                            const float* warps, const float* lens, int OH, int OW, void* x_padded, eve_stream_t stream) {
+    if (const int rc = eye_warp_surface("eye_warp_surface_to_stem", dtype, true, surface, matrix, N, frames, warps, lens, OH, OW, x_padded,
+                                        (hipStream_t)stream))
+        return rc;
     EVE_CHECK_LAUNCH();
     return 0;
 }

@@ -17,7 +17,9 @@
 // A row pitch IW * C that is no multiple of 16 (1366 x 768 x 3), or an unaligned base, takes the byte-column form of step 1:
 // thread j owns byte columns j, j + 256, ...; the loads are single bytes, still consecutive across the lanes.
 // NV12, I420 and YUYV captures (eve_screen_area_fmt_to_nchw) have a kernel of the same shape further down.
+// Surfaces -- pitched, cropped, NV21 / YV12 / UYVY / P010 / pitched BGRA (eve_screen_area_surface_to_nchw) -- have two behind it.
 #include "common.h"
+#include "surface.h"
 #include "yuv_rgb.h"
 
 namespace eve {
@@ -315,6 +317,235 @@ __global__ __launch_bounds__(SR_THREADS) void screen_area_fmt_kernel(const long 
     }
 }
 
+// ---------------------------------------------------------------------------------------------- surfaces (surface.h)
+// eve_screen_area_surface_to_nchw: the same area average of the VISIBLE region of a decoder's or capture API's surface, every
+// pixel read through the descriptor's address rule, converted (EVE_SURF_YUV), then averaged.  Shape, LDS and phase 2 are
+// screen_area_fmt_kernel's.  Two kernels:
+//   yuv420   8-bit 4:2:0 with luma step 1, chroma semi-planar in either order (NV12, NV21) or planar (I420, YV12), any pitches
+//            and plane offsets: screen_area_fmt_kernel's phase 1 with the row, plane and frame strides taken from the
+//            descriptor.  The vector form loads 8 luma bytes per row and 8 interleaved (or 4 + 4 planar) chroma bytes per row
+//            pair; the chroma words are sorted into a U word and a V word after the load, so one instantiation serves the four
+//            layouts.  A crop puts pixel (0, 0) `skew` bytes (even, < 8) behind an 8-byte boundary: the thread's eight columns are
+//            then the ALIGNED group, 8v - skew .. 8v - skew + 7, and the columns of the first and last group that lie outside
+//            the visible region are loaded (they are bytes of the same row of the same frame: the host checks it) but never
+//            stored.  The byte form gives a thread one pixel pair and single-byte loads through the address rule.
+//   generic  everything else (packed YUV, P010's high bytes, RGB kinds, 4:2:2, 4:4:4): a thread owns one column, three byte loads
+//            per pixel, SR_ROWS rows in flight.
+struct SurfAreaArgs {
+    long long items;
+    int IH, IW, OH, OW;
+    int yuv;                             // generic: the kind is EVE_SURF_YUV
+    int planar;                          // yuv420: U and V in planes of their own (step 1); else interleaved (step 2)
+    int skew;                            // yuv420 vector form: bytes from the 8-byte boundary below pixel (0, 0) to it, even
+    YuvCoef coef;
+    Surf sf;
+};
+
+// phase 2 of both kernels: colsum[IW][3] -> the three planes of output row oy of frame n
+__device__ __forceinline__ void surf_area_row_out(const uint32_t* colsum, const long long n, const int oy, const int IH, const int IW,
+                                                  const int OH, const int OW, float* __restrict__ dst) {
+    const double area = (double)((long long)IH * IW);
+    const float scale = (float)(1.0 / 255.0);
+    for (int t = threadIdx.x; t < 3 * OW; t += SR_THREADS) {
+        const int c = t / OW, ox = t - c * OW;
+        const int ix0 = (int)((uint32_t)ox * (uint32_t)IW / (uint32_t)OW);
+        const int ix1 = (int)((((uint32_t)ox + 1u) * (uint32_t)IW + (uint32_t)OW - 1u) / (uint32_t)OW);      // <= IW
+        uint32_t s = 0u;
+        for (int ix = ix0; ix < ix1; ++ix) s += overlap_x(ix, ox, IW, OW) * colsum[ix * 3 + c];
+        dst[((n * 3 + c) * OH + oy) * OW + ox] = (float)((double)s / area) * scale;
+    }
+}
+
+// bytes 0 and 2 of lo, then of hi (ODD: bytes 1 and 3): every second byte of eight
+template <bool ODD>
+__device__ __forceinline__ uint32_t every_second_byte(const uint32_t lo, const uint32_t hi) {
+    constexpr int s = ODD ? 8 : 0;
+    return ((lo >> s) & 0xffu) | (((lo >> (16 + s)) & 0xffu) << 8) | (((hi >> s) & 0xffu) << 16) | (((hi >> (16 + s)) & 0xffu) << 24);
+}
+
+template <bool VEC>
+__device__ __forceinline__ void surf_area_yuv420_items(const SurfAreaArgs& a, const uint8_t* __restrict__ src, float* __restrict__ dst,
+                                                       uint32_t* colsum) {
+    const int tid = threadIdx.x;
+    const int IH = a.IH, IW = a.IW, OH = a.OH;
+    const YuvCoef coef = a.coef;
+    const long long oY = a.sf.offset[0], oU = a.sf.offset[1], oV = a.sf.offset[2];
+    const long long pY = a.sf.pitch[0], pU = a.sf.pitch[1], pV = a.sf.pitch[2];
+    const bool planar = a.planar != 0;
+    const bool v_first = oV < oU;                                            // interleaved: NV21's order
+    const long long oC = v_first ? oV : oU;                                  // interleaved: where a row's chroma pairs begin
+    for (long long item = blockIdx.x; item < a.items; item += gridDim.x) {
+        const long long n = item / OH;
+        const int oy = (int)(item - n * OH);
+        const int iy0 = (int)((long long)oy * IH / OH);
+        const int iy1 = (int)((((long long)oy + 1) * IH + OH - 1) / OH);      // <= IH
+        const int g0 = iy0 / 2, g1 = (iy1 + 1) / 2;                           // row pairs: <= (IH + 1) / 2
+        const uint8_t* frame = src + n * a.sf.frame_stride;
+        if (VEC) {
+            const int skew = a.skew;
+            for (int v = tid; v < (skew + IW + YR_COLS - 1) / YR_COLS; v += SR_THREADS) {
+                const long long x0 = (long long)v * YR_COLS - skew;           // the group's first column: >= -6, even
+                uint32_t acc[3 * YR_COLS];
+#pragma unroll
+                for (int k = 0; k < 3 * YR_COLS; ++k) acc[k] = 0u;
+                for (int g = g0; g < g1; g += YR_GROUPS) {
+                    uint32_t yq[YR_GROUPS][2][2];                             // the group's two luma rows, 8 columns each
+                    uint32_t cq[YR_GROUPS][2];                                // interleaved: 4 chroma pairs; planar: 4 U bytes, 4 V bytes
+#pragma unroll
+                    for (int i = 0; i < YR_GROUPS; ++i)
+                        if (g + i < g1) {
+#pragma unroll
+                            for (int r = 0; r < 2; ++r) {
+                                const int iy = (g + i) * 2 + r;
+                                if (iy >= iy0 && iy < iy1) {
+                                    load_words(frame + oY + iy * pY + x0, yq[i][r]);
+                                } else {                                      // the other output row's: weight 0 below
+                                    yq[i][r][0] = yq[i][r][1] = 0u;
+                                }
+                            }
+                            if (planar) {
+                                uint32_t u[1], w[1];
+                                load_words(frame + oU + (g + i) * pU + x0 / 2, u);
+                                load_words(frame + oV + (g + i) * pV + x0 / 2, w);
+                                cq[i][0] = u[0]; cq[i][1] = w[0];
+                            } else {
+                                load_words(frame + oC + (g + i) * pU + x0, cq[i]);
+                            }
+                        }
+#pragma unroll
+                    for (int i = 0; i < YR_GROUPS; ++i)
+                        if (g + i < g1) {
+                            const int iya = (g + i) * 2;
+                            const uint32_t wa = iya >= iy0 ? overlap(iya, oy, IH, OH) : 0u, wb = iya + 1 < iy1 ? overlap(iya + 1, oy, IH, OH) : 0u;
+                            const uint32_t even = every_second_byte<false>(cq[i][0], cq[i][1]), odd = every_second_byte<true>(cq[i][0], cq[i][1]);
+                            const uint32_t uw = planar ? cq[i][0] : v_first ? odd : even;
+                            const uint32_t vw = planar ? cq[i][1] : v_first ? even : odd;
+#pragma unroll
+                            for (int j = 0; j < YR_COLS / 2; ++j) {           // chroma sample j: luma columns 2j, 2j + 1 of both rows
+                                const YuvChroma c = yuv_chroma<true>((int)((uw >> (8 * j)) & 0xffu), (int)((vw >> (8 * j)) & 0xffu), coef);
+#pragma unroll
+                                for (int e = 0; e < 2; ++e) {
+                                    add_pixel(acc + 3 * (2 * j + e), wa, (int)byte_of(yq[i][0], 2 * j + e), c, coef);
+                                    add_pixel(acc + 3 * (2 * j + e), wb, (int)byte_of(yq[i][1], 2 * j + e), c, coef);
+                                }
+                            }
+                        }
+                }
+                if (skew == 0 && x0 + YR_COLS <= IW) {
+                    uint4* out = reinterpret_cast<uint4*>(colsum + (size_t)v * (3 * YR_COLS));
+#pragma unroll
+                    for (int k = 0; k < 3 * YR_COLS / 4; ++k) out[k] = make_uint4(acc[4 * k], acc[4 * k + 1], acc[4 * k + 2], acc[4 * k + 3]);
+                } else {                                                      // a skewed or partial group: the visible columns only
+#pragma unroll
+                    for (int k = 0; k < YR_COLS; ++k)
+                        if (x0 + k >= 0 && x0 + k < IW) {
+#pragma unroll
+                            for (int c = 0; c < 3; ++c) colsum[(x0 + k) * 3 + c] = acc[3 * k + c];
+                        }
+                }
+            }
+        } else {
+            const long long sY = a.sf.step[0], sU = a.sf.step[1], sV = a.sf.step[2];
+            for (int p = tid; p < ((IW + 1) >> 1); p += SR_THREADS) {         // pixel pair p: columns 2p, 2p + 1, one chroma sample
+                const bool second = 2 * p + 1 < IW;                           // an odd width's last pair is one column
+                uint32_t acc[6];
+#pragma unroll
+                for (int k = 0; k < 6; ++k) acc[k] = 0u;
+                for (int g = g0; g < g1; g += YR_GROUPS) {
+                    uint32_t yb[YR_GROUPS][2][2], ub[YR_GROUPS], vb[YR_GROUPS];
+#pragma unroll
+                    for (int i = 0; i < YR_GROUPS; ++i)
+                        if (g + i < g1) {
+#pragma unroll
+                            for (int r = 0; r < 2; ++r) {
+                                const int iy = (g + i) * 2 + r;
+                                yb[i][r][0] = yb[i][r][1] = 0u;
+                                if (iy >= iy0 && iy < iy1) {
+                                    const uint8_t* q = frame + oY + iy * pY + (long long)(2 * p) * sY;
+                                    yb[i][r][0] = q[0];
+                                    if (second) yb[i][r][1] = q[sY];
+                                }
+                            }
+                            ub[i] = frame[oU + (g + i) * pU + p * sU];
+                            vb[i] = frame[oV + (g + i) * pV + p * sV];
+                        }
+#pragma unroll
+                    for (int i = 0; i < YR_GROUPS; ++i)
+                        if (g + i < g1) {
+                            const YuvChroma c = yuv_chroma<true>((int)ub[i], (int)vb[i], coef);
+#pragma unroll
+                            for (int r = 0; r < 2; ++r) {
+                                const int iy = (g + i) * 2 + r;
+                                if (iy >= iy0 && iy < iy1) {
+                                    const uint32_t wy = overlap(iy, oy, IH, OH);
+                                    add_pixel(acc, wy, (int)yb[i][r][0], c, coef);
+                                    add_pixel(acc + 3, wy, (int)yb[i][r][1], c, coef);
+                                }
+                            }
+                        }
+                }
+#pragma unroll
+                for (int k = 0; k < 3; ++k) colsum[(size_t)p * 6 + k] = acc[k];
+                if (second) {
+#pragma unroll
+                    for (int k = 3; k < 6; ++k) colsum[(size_t)p * 6 + k] = acc[k];
+                }
+            }
+        }
+        __syncthreads();
+        surf_area_row_out(colsum, n, oy, IH, IW, OH, a.OW, dst);
+        __syncthreads();                 // the next item overwrites colsum
+    }
+}
+
+__device__ __forceinline__ void surf_area_generic_items(const SurfAreaArgs& a, const uint8_t* __restrict__ src, float* __restrict__ dst,
+                                                        uint32_t* colsum) {
+    const int IH = a.IH, IW = a.IW, OH = a.OH;
+    const YuvCoef coef = a.coef;
+    const Surf sf = a.sf;
+    for (long long item = blockIdx.x; item < a.items; item += gridDim.x) {
+        const long long n = item / OH;
+        const int oy = (int)(item - n * OH);
+        const int iy0 = (int)((long long)oy * IH / OH);
+        const int iy1 = (int)((((long long)oy + 1) * IH + OH - 1) / OH);      // <= IH
+        const uint8_t* frame = src + n * sf.frame_stride;
+        for (int x = threadIdx.x; x < IW; x += SR_THREADS) {
+            uint32_t acc[3] = {0u, 0u, 0u};
+            for (int iy = iy0; iy < iy1; iy += SR_ROWS) {
+                uint32_t b[SR_ROWS][3];
+#pragma unroll
+                for (int r = 0; r < SR_ROWS; ++r)
+                    if (iy + r < iy1) surf_components(frame, sf, iy + r, x, b[r]);
+#pragma unroll
+                for (int r = 0; r < SR_ROWS; ++r)
+                    if (iy + r < iy1) {
+                        const uint32_t wy = overlap(iy + r, oy, IH, OH);
+                        uint32_t rgb[3] = {b[r][0], b[r][1], b[r][2]};
+                        if (a.yuv) yuv_pixel<true>((int)b[r][0], yuv_chroma<true>((int)b[r][1], (int)b[r][2], coef), coef, rgb);
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) acc[c] += wy * rgb[c];
+                    }
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) colsum[(size_t)x * 3 + c] = acc[c];
+        }
+        __syncthreads();
+        surf_area_row_out(colsum, n, oy, IH, IW, OH, a.OW, dst);
+        __syncthreads();                 // the next item overwrites colsum
+    }
+}
+
+constexpr int SURF_YUV420 = 0, SURF_GENERIC = 1;
+
+// FORM: SURF_YUV420 (VEC: its vector form) or SURF_GENERIC (the byte form only)
+template <int FORM, bool VEC>
+__global__ __launch_bounds__(SR_THREADS) void screen_area_surface_kernel(const SurfAreaArgs a, const uint8_t* __restrict__ src,
+                                                                         float* __restrict__ dst) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t colsum[];        // [IW][3]: sum over the rows of wy * (r, g, b)
+    if constexpr (FORM == SURF_YUV420) surf_area_yuv420_items<VEC>(a, src, dst, colsum);
+    else surf_area_generic_items(a, src, dst, colsum);
+}
+
 }  // namespace
 }  // namespace eve
 
@@ -404,6 +635,70 @@ extern "C" int eve_screen_area_fmt_to_nchw(int format, int matrix, long long N, 
         SR_FMT_CASE(EVE_PIX_NV12, "nv12")
         SR_FMT_CASE(EVE_PIX_I420, "i420")
         SR_FMT_CASE(EVE_PIX_YUYV, "yuyv")
+    }
+    EVE_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int eve_screen_area_surface_to_nchw(const eve_surface* surface, int matrix, long long N, const uint8_t* src, int OH, int OW,
+                                               float* dst_nchw, eve_stream_t stream) {
+    static const char who[] = "screen_area_surface_to_nchw";
+    char msg[192];
+    const char* why = surface_refusal(surface, matrix, N);
+    const int IH = why ? 0 : surface->height, IW = why ? 0 : surface->width;
+    const size_t lds = (size_t)IW * 3 * sizeof(uint32_t);
+    if (why) {}
+    else if (N <= 0 || OH <= 0 || OW <= 0 || !src || !dst_nchw) why = "bad arguments";
+    else if (OH > IH || OW > IW) why = "upscaling is not supported (OH <= height and OW <= width)";
+    else if ((long long)IH * IW > SR_MAX_PIXELS) why = "frame too large (width * height <= 16843009 keeps the 32-bit sums exact)";
+    else if (lds > (size_t)LDS_CU) why = "row too wide (width * 12 <= 163840 bytes: one row of three sums per column in LDS)";
+    else if (N > (long long)0x7fffffff / OH) why = "N * OH must fit 31 bits";
+    if (why) {
+        snprintf(msg, sizeof(msg), "%s: %s", who, why);
+        return set_error_msg(msg);
+    }
+    const eve_surface& s = *surface;
+    SurfAreaArgs a;
+    a.items = N * OH;
+    a.IH = IH; a.IW = IW; a.OH = OH; a.OW = OW;
+    a.yuv = s.kind == EVE_SURF_YUV;
+    a.coef = YUV_MATRICES[a.yuv ? matrix : 0];
+    a.sf = surf_of(s);
+    // 8-bit 4:2:0 with luma step 1: interleaved chroma (U and V one byte apart, step 2, one pitch) or two planes (step 1)
+    const long long duv = s.offset[2] - s.offset[1];
+    const bool semi = s.step[1] == 2 && s.step[2] == 2 && (duv == 1 || duv == -1) && s.pitch[1] == s.pitch[2];
+    const bool planar = s.step[1] == 1 && s.step[2] == 1;
+    const bool yuv420 = a.yuv && s.xshift == 1 && s.yshift == 1 && s.step[0] == 1 && (semi || planar) && IW >= 2;
+    a.planar = planar;
+    a.skew = 0;
+    const dim3 grid((unsigned)(a.items < SR_MAX_BLOCKS ? a.items : SR_MAX_BLOCKS));
+    if (yuv420) {
+        // the vector form: 8 luma bytes and 8 interleaved chroma bytes (planar: 4 + 4) per load, each load on its own size in every
+        // row of every frame.  The loads start `skew` bytes below pixel (0, 0) and end on the boundary behind the row's last pixel:
+        // every plane must hold those bytes inside [0, frame_bytes), and luma and chroma must share the skew.
+        const uintptr_t base = reinterpret_cast<uintptr_t>(src);
+        const int skew = (int)((base + (uintptr_t)s.offset[0]) & (YR_COLS - 1));
+        const long long span = (skew + (long long)IW + YR_COLS - 1) / YR_COLS * YR_COLS;      // bytes of luma a row's groups cover
+        const long long crows = (IH + 1) / 2;
+        const auto plane_ok = [&](long long offset, int pitch, long long rows, int bytes, int skew_c, long long span_c) {
+            return (int)((base + (uintptr_t)offset) & (bytes - 1)) == skew_c && pitch % bytes == 0 && (N == 1 || s.frame_stride % bytes == 0) &&
+                   offset >= skew_c && offset - skew_c + (rows - 1) * pitch + span_c <= s.frame_bytes;
+        };
+        const long long oc = duv > 0 ? s.offset[1] : s.offset[2];
+        const bool vec = skew % 2 == 0 && plane_ok(s.offset[0], s.pitch[0], IH, YR_COLS, skew, span) &&
+                         (planar ? plane_ok(s.offset[1], s.pitch[1], crows, YR_COLS / 2, skew / 2, span / 2) &&
+                                       plane_ok(s.offset[2], s.pitch[2], crows, YR_COLS / 2, skew / 2, span / 2)
+                                 : plane_ok(oc, s.pitch[1], crows, YR_COLS, skew, span));
+        if (vec) a.skew = skew;
+        if (vec)
+            EVE_LAUNCH("screen_area_surface_kernel<yuv420,true>", (screen_area_surface_kernel<SURF_YUV420, true>), grid, dim3(SR_THREADS), lds,
+                       (hipStream_t)stream, a, src, dst_nchw);
+        else
+            EVE_LAUNCH("screen_area_surface_kernel<yuv420,false>", (screen_area_surface_kernel<SURF_YUV420, false>), grid, dim3(SR_THREADS), lds,
+                       (hipStream_t)stream, a, src, dst_nchw);
+    } else {
+        EVE_LAUNCH("screen_area_surface_kernel<generic,false>", (screen_area_surface_kernel<SURF_GENERIC, false>), grid, dim3(SR_THREADS), lds,
+                   (hipStream_t)stream, a, src, dst_nchw);
     }
     EVE_CHECK_LAUNCH();
     return 0;

@@ -25,6 +25,11 @@ uint8 frames is 4x less PCIe traffic, and the float values produced here are bit
                                  'i420' [..., IH*3/2, IW], 'yuyv' [..., IH, IW, 2]; only the taps read are converted, by a bit-exact
                                  integer matrix ('bt601', 'bt709' limited range, 'jfif' full range) -- the keys `camera_frame_bgr`,
                                  `camera_frame_nv12`, `camera_frame_i420`, `camera_frame_yuyv` in place of `camera_frame`
+  SurfaceLayout(format, width, height, pitch=, coded_height=, x0=, y0=, plane_offsets=)
+                                 how a decoder's or capture API's surface lies in memory (pitched rows, coded rows, a crop; NV21,
+                                 YV12, UYVY, P010, pitched BGRA, ...): warp_eye_patches(..., layout=) and preprocess_screen_frames(...,
+                                 layout=) read the visible region where it lies -- the keys `camera_surface` / `screen_surface` with
+                                 model.eye_net.camera_layout / model.refine_net.screen_layout
   camera_lens(K, dist)           a camera matrix [..., 3, 3] and 4, 5 or 8 OpenCV distortion coefficients -> the float32 [..., 12]
                                  rows that warp_eye_patches(..., lens=) and the `camera_lens` key take for RAW (distorted) frames
   eye_pose(K, rvec, tvec, eyes, focal_norm, distance_norm)
@@ -55,13 +60,162 @@ def _fold(frames):
     return frames.reshape((-1,) + tuple(frames.shape[-3:])).contiguous(), lead
 
 
+# SurfaceLayout formats -> (kind 'rgb' | 'yuv', bytes per pixel of the first plane, planes after it, xshift, yshift)
+SURFACE_FORMATS = {'rgb': ('rgb', 3, 0, 0, 0), 'rgba': ('rgb', 4, 0, 0, 0), 'bgr': ('rgb', 3, 0, 0, 0), 'bgra': ('rgb', 4, 0, 0, 0),
+                   'nv12': ('yuv', 1, 1, 1, 1), 'nv21': ('yuv', 1, 1, 1, 1), 'i420': ('yuv', 1, 2, 1, 1), 'yv12': ('yuv', 1, 2, 1, 1),
+                   'yuyv': ('yuv', 2, 0, 1, 0), 'uyvy': ('yuv', 2, 0, 1, 0), 'p010': ('yuv', 2, 1, 1, 1)}
+
+
+class SurfaceLayout(object):
+    """How a decoder's or capture API's surface lies in memory: the descriptor of include/eve_hip.h eve_surface, computed from what
+    such an API reports.  A frame is one byte range; component c of visible pixel (x, y) is the byte
+    offset[c] + (y >> ys) * pitch[c] + (x >> xs) * step[c] of it -- nothing else is read, so padding, coded rows below the picture
+    and a fourth channel never reach a result.
+      format         'rgb' | 'rgba' | 'bgr' | 'bgra' (packed, 3 or 4 bytes per pixel), 'nv12' | 'nv21' (luma plane, then one plane of
+                     interleaved U, V | V, U), 'i420' | 'yv12' (luma, then the U, V | V, U planes at half the pitch), 'yuyv' | 'uyvy'
+                     (Y U Y V | U Y V Y per pixel pair), 'p010' (NV12's shape in 16-bit little-endian words, read as their high
+                     byte: the sample >> 8, a truncation to 8 bits)
+      width, height  the visible region in pixels
+      pitch          bytes from one row of the first plane to the next; None: the tight row, (x0 + width) pixels
+      coded_height   rows each plane was allocated for (the chroma planes of the 4:2:0 formats: half of it); None: height + y0
+      x0, y0         the visible region's top-left pixel inside the surface: a crop, or a window of a captured desktop.  Odd along
+                     a subsampled axis is a ValueError: the chroma phase would shift
+      plane_offsets  None, or the byte where each plane after the first begins (one value for nv12 / nv21 / p010, two for i420 /
+                     yv12, in memory order), for allocators that align planes; None: each plane follows the one before
+    frame_bytes is what one frame occupies, and frame_stride the same: the tensor handed over with the layout is a contiguous
+    uint8 [..., rows, pitch] or [..., frame_bytes] whose trailing dimensions multiply to it.  Instances compare and hash by value."""
+
+    def __init__(self, format, width, height, pitch=None, coded_height=None, x0=0, y0=0, plane_offsets=None):
+        if format not in SURFACE_FORMATS:
+            raise ValueError('SurfaceLayout: format must be one of %s, got %r' % (', '.join(SURFACE_FORMATS), format))
+        kind, bpp, nplanes, xs, ys = SURFACE_FORMATS[format]
+        ints = dict(width=width, height=height, x0=x0, y0=y0)
+        if pitch is not None:
+            ints['pitch'] = pitch
+        if coded_height is not None:
+            ints['coded_height'] = coded_height
+        for name, v in ints.items():
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+                raise ValueError('SurfaceLayout: %s must be an integer, got %r' % (name, v))
+        width, height, x0, y0 = int(width), int(height), int(x0), int(y0)
+        if width < 1 or height < 1 or x0 < 0 or y0 < 0:
+            raise ValueError('SurfaceLayout: width and height must be >= 1 and x0, y0 >= 0, got %d x %d at (%d, %d)' % (width, height, x0, y0))
+        if (xs and (x0 % 2 or width % 2)) or (ys and (y0 % 2 or height % 2)):
+            raise ValueError('SurfaceLayout: %s subsamples chroma: the crop origin and size must be even along %s, got %d x %d at (%d, %d) '
+                             '(an odd origin would shift the chroma phase)' % (format, 'x and y' if ys else 'x', width, height, x0, y0))
+        tight = (x0 + width) * bpp
+        pitch = tight if pitch is None else int(pitch)
+        coded = y0 + height if coded_height is None else int(coded_height)
+        if pitch < tight:
+            raise ValueError('SurfaceLayout: pitch %d is shorter than the %d bytes of x0 + width = %d pixels' % (pitch, tight, x0 + width))
+        if pitch >= 2 ** 31:
+            raise ValueError('SurfaceLayout: pitch must fit 31 bits, got %d' % pitch)
+        if coded < y0 + height:
+            raise ValueError('SurfaceLayout: coded_height %d is less than y0 + height = %d' % (coded, y0 + height))
+        if nplanes == 2 and pitch % 2:
+            raise ValueError('SurfaceLayout: %s chroma planes have half the pitch: pitch must be even, got %d' % (format, pitch))
+        cpitch = pitch // 2 if nplanes == 2 else pitch                    # of the planes after the first
+        crows = (coded + 1) // 2
+        if plane_offsets is None:
+            starts = [pitch * coded + i * cpitch * crows for i in range(nplanes)]
+        else:
+            starts = [int(v) for v in plane_offsets]
+            if len(starts) != nplanes or any(v < 0 for v in starts):
+                raise ValueError('SurfaceLayout: %s takes %d non-negative plane_offsets, got %r' % (format, nplanes, plane_offsets))
+        first = y0 * pitch + x0 * bpp                                     # pixel (0, 0) in the first plane
+        if kind == 'rgb':
+            order = (2, 1, 0) if format.startswith('bgr') else (0, 1, 2)
+            offset, pitches, step = [first + c for c in order], [pitch] * 3, [bpp] * 3
+        elif nplanes == 0:                                               # yuyv / uyvy: x0 is even
+            y_at, u_at, v_at = (0, 1, 3) if format == 'yuyv' else (1, 0, 2)
+            offset, pitches, step = [first + y_at, first + u_at, first + v_at], [pitch] * 3, [2, 4, 4]
+        elif nplanes == 1:                                               # nv12 / nv21 / p010: x0 and y0 are even
+            at = starts[0] + (y0 // 2) * pitch + x0 * bpp                 # (x0 / 2 pairs of 2 * bpp bytes)
+            u_at, v_at = (bpp, 0) if format == 'nv21' else (0, bpp)
+            hi = bpp - 1                                                  # p010: the high byte of the little-endian word
+            offset, pitches, step = [first + hi, at + u_at + hi, at + v_at + hi], [pitch] * 3, [bpp, 2 * bpp, 2 * bpp]
+        else:                                                            # i420 / yv12
+            at = [s_ + (y0 // 2) * cpitch + x0 // 2 for s_ in starts]
+            u_at, v_at = (at[1], at[0]) if format == 'yv12' else (at[0], at[1])
+            offset, pitches, step = [first, u_at, v_at], [pitch, cpitch, cpitch], [1, 1, 1]
+        ends = [pitch * coded] + [s_ + cpitch * crows for s_ in starts]
+        self.format, self.width, self.height, self.pitch, self.coded_height, self.x0, self.y0 = format, width, height, pitch, coded, x0, y0
+        self.plane_offsets = tuple(starts)
+        self.kind, self.xshift, self.yshift = kind, xs, ys
+        self.offset, self.pitches, self.step = tuple(offset), tuple(pitches), tuple(step)
+        self.frame_bytes = self.frame_stride = max(ends)
+        for c in range(3):                                               # (plane_offsets can put a plane anywhere: the library's bound check)
+            last = self.offset[c] + ((height - 1) >> (ys if c else 0)) * self.pitches[c] + ((width - 1) >> (xs if c else 0)) * self.step[c]
+            if last >= self.frame_bytes:
+                raise ValueError('SurfaceLayout: component %d reaches byte %d of a frame of %d bytes' % (c, last, self.frame_bytes))
+
+    def descriptor(self):
+        """-> the fields of eve_surface as a dict (struct_bytes left to the ctypes mirror)."""
+        return dict(kind=0 if self.kind == 'rgb' else 1, width=self.width, height=self.height, frame_stride=self.frame_stride,
+                    frame_bytes=self.frame_bytes, offset=self.offset, pitch=self.pitches, step=self.step, xshift=self.xshift,
+                    yshift=self.yshift)
+
+    def as_ctypes(self):
+        """-> the _lib.Surface the entry points take."""
+        import ctypes
+        from ._lib import Surface
+        d = self.descriptor()
+        s = Surface()
+        s.struct_bytes = ctypes.sizeof(Surface)
+        for name in ('kind', 'width', 'height', 'frame_stride', 'frame_bytes', 'xshift', 'yshift'):
+            setattr(s, name, d[name])
+        for c in range(3):
+            s.offset[c], s.pitch[c], s.step[c] = d['offset'][c], d['pitch'][c], d['step'][c]
+        return s
+
+    def key(self):
+        return (self.format, self.width, self.height, self.pitch, self.coded_height, self.x0, self.y0, self.plane_offsets)
+
+    def __eq__(self, other):
+        return isinstance(other, SurfaceLayout) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'SurfaceLayout(%r, %d, %d, pitch=%d, coded_height=%d, x0=%d, y0=%d, plane_offsets=%r)' % self.key()
+
+
+def surface_frames(frames, layout, lead, name='frames'):
+    """A surface tensor checked against its layout -> (the frames as uint8 [N, frame_stride], the `lead` leading dimensions):
+    contiguous uint8 whose trailing dimensions -- [rows, pitch], or flat -- multiply to layout.frame_stride.  lead=None: as many
+    leading dimensions as leave such trailing ones (at least one).  TypeError for a wrong dtype, layout or number of dimensions,
+    ValueError for a wrong size."""
+    if not isinstance(layout, SurfaceLayout):
+        raise TypeError('%s: the layout must be a data.SurfaceLayout, got %s' % (name, type(layout).__name__))
+    if lead is None:
+        lead, prod = 1, 1
+        for i in range(getattr(frames, 'ndim', 0) - 1, 0, -1):
+            prod *= int(frames.shape[i])
+            if prod == layout.frame_stride:
+                lead = i
+                break
+    if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() <= lead:
+        raise TypeError('%s must be uint8 with %d leading dimension%s and one frame\'s bytes behind them, got %s %s' % (
+            name, lead, '' if lead == 1 else 's', getattr(frames, 'dtype', type(frames)), tuple(getattr(frames, 'shape', ()))))
+    per_frame = 1
+    for v in frames.shape[lead:]:
+        per_frame *= int(v)
+    if per_frame != layout.frame_stride:
+        raise ValueError('%s: a frame holds %d bytes %s, the layout\'s frame_stride is %d (%r)' % (
+            name, per_frame, tuple(frames.shape[lead:]), layout.frame_stride, layout))
+    if not frames.is_contiguous():
+        raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+    return frames.reshape(-1, per_frame), tuple(frames.shape[:lead])
+
+
 def preprocess_frames(frames):
     flat, lead = _fold(frames)
     out = default_kernels().frames_u8_to_nchw(flat, EYE_SCALE, EYE_SHIFT)
     return out.view(lead + tuple(out.shape[1:]))
 
 
-def preprocess_screen_frames(frames, size=None, bgr=False, format=None, matrix='bt601'):
+def preprocess_screen_frames(frames, size=None, bgr=False, format=None, matrix='bt601', layout=None):
     """size: None, or the (H, W) the network takes.  Frames of that size already (and size=None) are normalised as the
     reference normalises its 128 x 72 video; larger ones -- a live capture of the desktop, [..., IH, IW, 3 | 4] -- are
     area-averaged down to it by eve_screen_u8_area_to_nchw: the exact mean over each output pixel's footprint, fractional
@@ -75,7 +229,21 @@ def preprocess_screen_frames(frames, size=None, bgr=False, format=None, matrix='
     [..., IH, IW, 2] (IW even), byte-linear per frame, with the integer matrix `matrix` ('bt601' or 'bt709', limited range, or
     'jfif', full range): every pixel is converted as it is read and the converted values are averaged, so the result equals the
     RGB call on the converted frame bit for bit and no RGB frame is made (eve_screen_area_fmt_to_nchw, at every size: size=None
-    takes the frames' own).  bgr=True together with a format raises ValueError."""
+    takes the frames' own).  bgr=True together with a format raises ValueError.
+    layout: None, or a SurfaceLayout: the frames are then a decoder's or capture API's surface as it lies in memory, uint8
+    [..., rows, pitch] or [..., frame_bytes] -- pitched rows, coded rows below the picture, a crop, NV21 / YV12 / UYVY / P010 or a
+    pitched BGRA texture -- and the visible region is read through the layout's address rule inside the same launch
+    (eve_screen_area_surface_to_nchw): the result equals the call on the de-pitched, cropped, byte-linear frame bit for bit and
+    that copy is never made.  `matrix` applies to the YUV formats; bgr and format stay at their defaults (ValueError)."""
+    if layout is not None:
+        if bgr or format is not None:
+            raise ValueError('preprocess_screen_frames: a layout names the format itself: leave bgr and format at their defaults')
+        if not torch.is_tensor(frames) or frames.dim() < 2:
+            raise TypeError('expected uint8 surface frames with at least one leading dimension, got %s' % (tuple(getattr(frames, 'shape', ())),))
+        flat, lead = surface_frames(frames, layout, None)
+        hw = (layout.height, layout.width) if size is None else (int(size[0]), int(size[1]))
+        out = default_kernels().screen_area_surface_to_nchw(flat, hw, layout, matrix=matrix)
+        return out.view(lead + tuple(out.shape[1:]))
     if format is not None:
         if bgr:
             raise ValueError('preprocess_screen_frames: bgr=True and format=%r exclude each other' % (format,))
@@ -281,7 +449,7 @@ def solve_head_pose(landmarks, rig, lengths=None):
     return {k_: v[0] for k_, v in out.items()} if single else out
 
 
-def warp_eye_patches(frames, warps, size=None, lens=None, format='rgb', matrix='bt601'):
+def warp_eye_patches(frames, warps, size=None, lens=None, format='rgb', matrix='bt601', layout=None):
     """One eye's patches cut from whole camera frames on the device, in place of two cv2.warpPerspective calls per frame on the
     host: frames uint8 [..., IH, IW, 3 | 4] (a fourth channel ignored, the channel order kept), warps float32 [..., 3, 3] with the
     same leading dimensions -> float32 [..., 3, H, W] in [-1, 1], the values preprocess_frames gives for the cut patch.  size:
@@ -301,8 +469,19 @@ def warp_eye_patches(frames, warps, size=None, lens=None, format='rgb', matrix='
     (IH and IW even) or 'yuyv' [..., IH, IW, 2] (IW even), byte-linear per frame.  The four taps of an output pixel are converted
     as they are read -- chroma the nearest sample, the integer matrix `matrix` ('bt601' or 'bt709', limited range, or 'jfif', full
     range) of include/eve_hip.h eve_eye_warp_fmt_to_nchw -- so the result equals the 'rgb' call on the converted frame bit for
-    bit, and no RGB frame is made."""
-    if format == 'rgb':
+    bit, and no RGB frame is made.
+
+    layout: None, or a SurfaceLayout: the frames are then surfaces as they lie in memory, uint8 [..., rows, pitch] or
+    [..., frame_bytes] with the warps' leading dimensions, and the taps are read through the layout's address rule
+    (eve_eye_warp_surface_to_nchw): the result equals the call on the de-pitched, cropped, byte-linear frame bit for bit.  `format`
+    stays at its default (ValueError): the layout names it."""
+    if layout is not None:
+        if format != 'rgb':
+            raise ValueError('warp_eye_patches: a layout names the format itself: leave format at its default')
+        if not torch.is_tensor(warps) or warps.dim() < 3:
+            raise TypeError('expected float32 warps shaped [..., 3, 3], got %s' % (tuple(getattr(warps, 'shape', ())),))
+        flat, lead = surface_frames(frames, layout, warps.dim() - 2)
+    elif format == 'rgb':
         flat, lead = _fold(frames)
         if flat.shape[3] not in (3, 4):
             raise TypeError('expected camera frames with 3 or 4 channels, got %d' % flat.shape[3])
@@ -323,7 +502,9 @@ def warp_eye_patches(frames, warps, size=None, lens=None, format='rgb', matrix='
     hw = eye_patch_hw() if size is None else (int(size[0]), int(size[1]))
     warps = warps.reshape(-1, 3, 3).contiguous()
     lens = None if lens is None else lens.reshape(-1, 12).contiguous()
-    if format != 'rgb':
+    if layout is not None:
+        out = default_kernels().eye_warp_surface_to_nchw(flat, warps, hw, layout, matrix=matrix, lens=lens)
+    elif format != 'rgb':
         out = default_kernels().eye_warp_fmt_to_nchw(flat, warps, hw, format, matrix=matrix, lens=lens)
     elif lens is None:
         out = default_kernels().eye_warp_u8_to_nchw(flat, warps, hw)

@@ -326,8 +326,8 @@ class EVE(nn.Module):
     def _predict_sequence(self, d, eye_states, refine_states, reset=None, return_heatmaps=False, lengths=None, masked=False,
                           eye_mask=None, pose_gate=None, face_state=None, render=None):
         """The prediction part of forward() for one chunk of an EVEStream: eval only, no labels, no losses.  d: the chunk's
-        inputs [B, Tc, ...] (not modified; camera_frame may be any one key of eye_net.EYE_FRAME_KEYS and the screen any one key of
-        refine_net.SCREEN_FRAME_KEYS; the eyes as patches, as camera_frame + {left,right}_eye_warp, or as camera_frame +
+        inputs [B, Tc, ...] (not modified; camera_frame may be any one key of eye_net.EYE_FRAME_KEYS or camera_surface, and the screen any one
+        key of refine_net.SCREEN_FRAME_KEYS or screen_surface; the eyes as patches, as camera_frame + {left,right}_eye_warp, or as camera_frame +
         eye_pose [B, Tc, 18], which also stands in for {left,right}_h / _o / _R and head_R and adds pose_valid to the result; both
         camera forms with an optional camera_lens [B, Tc, 12] for raw frames -- eye_net.eye_input, eye_pose_batch); eye_states / refine_states: the carried state buffers of the two networks
         (EyeNet._stream_state_buffers, RefineNet._stream_state_buffers), read as the state before the chunk and overwritten with

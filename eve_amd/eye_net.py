@@ -43,6 +43,9 @@ EYE_CAMERA_KEYS = ('camera_frame', 'left_eye_warp', 'right_eye_warp')
 # cameras and decoders deliver -- kernels.pixel_format_shape has the layouts)
 EYE_FRAME_KEYS = {'camera_frame': 'rgb', 'camera_frame_bgr': 'bgr', 'camera_frame_nv12': 'nv12', 'camera_frame_i420': 'i420',
                   'camera_frame_yuyv': 'yuyv'}
+# one more frame key: the frame as a decoder's or capture API's surface lies in memory, uint8 [B, T, rows, pitch] or [B, T, frame_bytes],
+# read through EyeNet.camera_layout (a data.SurfaceLayout: pitch, coded rows, crop, NV21 / YV12 / UYVY / P010 / pitched BGRA ...)
+EYE_SURFACE_KEY = 'camera_surface'
 EYE_LENS_KEY = 'camera_lens'                 # optional with the camera form: raw frames of a camera with lens distortion
 EYE_POSE_KEY = 'eye_pose'                    # the pose form: camera_frame + one packed row per frame (data.eye_pose)
 # what eye_pose_batch derives from the rows -- a batch holds the rows or these, never both
@@ -60,8 +63,8 @@ def has_pose_form(batch):
 
 
 def camera_frame_key(batch):
-    """The one frame key of EYE_FRAME_KEYS the batch holds, or None; two of them raise ValueError."""
-    found = [k_ for k_ in EYE_FRAME_KEYS if k_ in batch]
+    """The one frame key of EYE_FRAME_KEYS (or EYE_SURFACE_KEY) the batch holds, or None; two of them raise ValueError."""
+    found = [k_ for k_ in tuple(EYE_FRAME_KEYS) + (EYE_SURFACE_KEY,) if k_ in batch]
     if len(found) > 1:
         raise ValueError('a batch holds one camera frame key, found %s' % ', '.join(found))
     return found[0] if found else None
@@ -70,6 +73,11 @@ def camera_frame_key(batch):
 def _camera_frame(batch):
     key = camera_frame_key(batch)
     frames = batch[key]
+    if key == EYE_SURFACE_KEY:                   # (its size is checked against EyeNet.camera_layout where the patches are cut)
+        if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() < 3:
+            raise TypeError('%s must be uint8 [B, T, rows, pitch] or [B, T, frame_bytes], got %s %s' % (
+                key, getattr(frames, 'dtype', type(frames)), tuple(getattr(frames, 'shape', ()))))
+        return frames
     if key != 'camera_frame':
         pixel_format_shape(frames, EYE_FRAME_KEYS[key], lead=2, name=key)
         return frames
@@ -99,7 +107,9 @@ def eye_input(batch):
     key; half of the pair raises ValueError, a wrong dtype or shape TypeError.  All camera forms may carry camera_lens, float32 [B, T, 12] (data.camera_lens): one camera per frame,
     for both eyes.  In both, camera_frame may be replaced by ONE of camera_frame_bgr [B, T, IH, IW, 3 | 4], camera_frame_nv12 /
     camera_frame_i420 [B, T, IH*3/2, IW] or camera_frame_yuyv [B, T, IH, IW, 2] (EYE_FRAME_KEYS; two frame keys raise ValueError,
-    odd sizes too): that tensor is then returned -- its shape[:2] and device are the batch's whatever the format."""
+    odd sizes too): that tensor is then returned -- its shape[:2] and device are the batch's whatever the format.  camera_surface,
+    uint8 [B, T, rows, pitch] or [B, T, frame_bytes], is one more such key: the frame as a decoder's surface lies in memory, read
+    through EyeNet.camera_layout."""
     if FACE_LANDMARKS_KEY in batch or FACE_RIG_KEY in batch:
         if FACE_LANDMARKS_KEY not in batch or FACE_RIG_KEY not in batch:
             raise ValueError('the face-landmark form needs %s and %s: found only %s' % (
@@ -517,6 +527,9 @@ class EyeNet(nn.Module):
     # The YUV -> RGB matrix of camera_frame_nv12 / _i420 / _yuyv batches: 'bt601' (limited range: webcams, OpenCV's cvtColor),
     # 'bt709' (limited range: HD decoders) or 'jfif' (full range: MJPEG).  Anything else raises ValueError at use.
     yuv_matrix = 'bt601'
+    # How camera_surface batches lie in memory: a data.SurfaceLayout (format, visible size, pitch, coded rows, crop origin, plane
+    # offsets).  A camera_surface batch without it raises ValueError.
+    camera_layout = None
 
     def forward_sequence(self, batch, initial_states=None):
         """batch: {left,right}_eye_patch [B, T, 3, H, W] float (or uint8 [B, T, H, W, C] decoded frames), {left,right}_h [B, T, 2].
@@ -530,7 +543,10 @@ class EyeNet(nn.Module):
         In every camera form the frames may come as the camera or decoder delivers them, under ONE of camera_frame_bgr,
         camera_frame_nv12, camera_frame_i420, camera_frame_yuyv in place of camera_frame (eye_input has the shapes): the cut then
         converts the taps it reads by the integer matrix self.yuv_matrix names, and equals the cut from the converted RGB frame bit
-        for bit (eve_eye_warp_fmt_to_nchw).  The per-frame forward() takes patches only.
+        for bit (eve_eye_warp_fmt_to_nchw).  Or under camera_surface, uint8 [B, T, rows, pitch] or [B, T, frame_bytes]: the surface
+        as it lies in memory -- pitched rows, coded rows, a crop, NV21 / YV12 / UYVY / P010 / pitched BGRA -- read through
+        self.camera_layout, a data.SurfaceLayout (eve_eye_warp_surface_to_nchw): the cut equals the one from the de-pitched, cropped,
+        byte-linear frame bit for bit, and that copy is never made.  The per-frame forward() takes patches only.
         Returns the B x T x ... tensors eve.py:174-182 would stack: <side>_g_initial [B,T,2],
         <side>_pupil_size [B,T], <side>_eye_rnn_states_<i> [B,T,H] per cell ((h, c) pair of them for LSTM).
         initial_states: {side: h [B,H]} or {side: [per-cell h | (h, c) | None]}."""
@@ -551,7 +567,17 @@ class EyeNet(nn.Module):
         Hh, Ww = data.eye_patch_hw(self.config)
         flat = frames.reshape((B * T,) + tuple(frames.shape[2:])).contiguous()
         lw, rw = (batch[s_ + '_eye_warp'].reshape(B * T, 3, 3).contiguous() for s_ in ('left', 'right'))
-        if frame_key != 'camera_frame':         # BGR / NV12 / I420 / YUYV: the taps are converted inside the same launch
+        if frame_key == EYE_SURFACE_KEY:        # a surface as it lies in memory: the taps go through the layout's address rule
+            layout, matrix = self.camera_layout, self.yuv_matrix
+            if layout is None:
+                raise ValueError('%s needs EyeNet.camera_layout, a data.SurfaceLayout that says how the frames lie in memory' % EYE_SURFACE_KEY)
+            if matrix not in YUV_MATRICES:
+                raise ValueError('EyeNet.yuv_matrix must be one of %s, got %r' % (', '.join(YUV_MATRICES), matrix))
+            flat, _ = data.surface_frames(frames, layout, 2, name=EYE_SURFACE_KEY)
+            lens = batch[EYE_LENS_KEY].reshape(B * T, 12).contiguous() if EYE_LENS_KEY in batch else None
+            to_stem = lambda w, out: k.eye_warp_surface_to_stem(flat, w, (Hh, Ww), layout, matrix=matrix, lens=lens, out=out)
+            to_nchw = lambda w: k.eye_warp_surface_to_nchw(flat, w, (Hh, Ww), layout, matrix=matrix, lens=lens)
+        elif frame_key != 'camera_frame':       # BGR / NV12 / I420 / YUYV: the taps are converted inside the same launch
             fmt, matrix = EYE_FRAME_KEYS[frame_key], self.yuv_matrix
             if matrix not in YUV_MATRICES:
                 raise ValueError('EyeNet.yuv_matrix must be one of %s, got %r' % (', '.join(YUV_MATRICES), matrix))

@@ -707,6 +707,78 @@ class HipKernels(object):
                                                    None if lens is None else self._p(lens), OH, OW, self._p(dst), self._stream()))
         return dst
 
+    # ------------------------------------------------------------------ surfaces (data.SurfaceLayout; include/eve_hip.h eve_surface)
+    @staticmethod
+    def _surface_args(who, frames, layout, matrix):
+        """The checks the three surface calls share -> (N, matrix code): frames uint8, contiguous, [N, ...] holding
+        (N - 1) * frame_stride + frame_bytes bytes with frame_stride bytes per frame."""
+        from .data import SurfaceLayout
+        if not isinstance(layout, SurfaceLayout):
+            raise TypeError('%s: layout must be a data.SurfaceLayout, got %s' % (who, type(layout).__name__))
+        if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() < 2:
+            raise TypeError('%s: frames must be uint8 [N, one frame\'s bytes], got %s %s' % (
+                who, getattr(frames, 'dtype', type(frames)), tuple(getattr(frames, 'shape', ()))))
+        if matrix not in YUV_MATRICES:
+            raise ValueError('%s: matrix must be one of %s, got %r' % (who, ', '.join(YUV_MATRICES), matrix))
+        N = int(frames.shape[0])
+        per_frame = frames.numel() // max(N, 1)
+        if N < 1 or per_frame != layout.frame_stride or frames.numel() < (N - 1) * layout.frame_stride + layout.frame_bytes:
+            raise ValueError('%s: frames %s hold %d bytes per frame, the layout needs a stride of %d and %d readable bytes (%r)' % (
+                who, tuple(frames.shape), per_frame, layout.frame_stride, layout.frame_bytes, layout))
+        if not frames.is_contiguous():
+            raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        return N, YUV_MATRICES[matrix]
+
+    @staticmethod
+    def _surface_warp_args(who, frames, warps, lens, N):
+        if not torch.is_tensor(warps) or warps.dtype != torch.float32 or tuple(warps.shape) != (N, 3, 3):
+            raise TypeError('%s: warps must be float32 [%d, 3, 3], got %s %s' % (who, N, getattr(warps, 'dtype', type(warps)),
+                                                                                  tuple(getattr(warps, 'shape', ()))))
+        if lens is not None and (not torch.is_tensor(lens) or lens.dtype != torch.float32 or tuple(lens.shape) != (N, 12)):
+            raise TypeError('%s: lens must be float32 [%d, 12], got %s %s' % (who, N, getattr(lens, 'dtype', type(lens)),
+                                                                               tuple(getattr(lens, 'shape', ()))))
+        if not (warps.is_contiguous() and (lens is None or lens.is_contiguous())):
+            raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        if warps.device != frames.device or (lens is not None and lens.device != frames.device):
+            raise RuntimeError('%s: frames, warps and lens are on different devices' % who)
+
+    def eye_warp_surface_to_nchw(self, frames, warps, out_hw, layout, matrix='bt601', lens=None):
+        """eye_warp_fmt_to_nchw on surfaces as they lie in memory: frames uint8 [N, ...] with layout.frame_stride bytes per frame,
+        layout a data.SurfaceLayout; the four taps of an output pixel are read through its address rule, so the result is the
+        format call's on the de-pitched, cropped, byte-linear frame, bit for bit (include/eve_hip.h eve_eye_warp_surface_to_nchw)."""
+        N, mat = self._surface_args('eye_warp_surface_to_nchw', frames, layout, matrix)
+        self._surface_warp_args('eye_warp_surface_to_nchw', frames, warps, lens, N)
+        OH, OW = int(out_hw[0]), int(out_hw[1])
+        out = torch.empty((N, 3, OH, OW), dtype=torch.float32, device=frames.device)
+        surf = layout.as_ctypes()
+        self._ck(self.lib.eve_eye_warp_surface_to_nchw(ctypes.byref(surf), mat, N, self._p(frames), self._p(warps),
+                                                       None if lens is None else self._p(lens), OH, OW, self._p(out), self._stream()))
+        return out
+
+    def eye_warp_surface_to_stem(self, frames, warps, out_hw, layout, matrix='bt601', lens=None, out=None, dtype=torch.bfloat16):
+        """The same patches straight into the stem's packed 16-bit input [N,OH+6,OW+8,4], as eye_warp_u8_to_stem lays it out."""
+        N, mat = self._surface_args('eye_warp_surface_to_stem', frames, layout, matrix)
+        self._surface_warp_args('eye_warp_surface_to_stem', frames, warps, lens, N)
+        OH, OW = int(out_hw[0]), int(out_hw[1])
+        dst = out if out is not None else torch.empty((N, OH + 6, OW + 8, 4), dtype=dtype, device=frames.device)
+        if tuple(dst.shape) != (N, OH + 6, OW + 8, 4) or dst.dtype not in HALF_DTYPES:
+            raise TypeError('eye_warp: out must be bf16 / f16 [%d, %d, %d, 4], got %s %s' % (N, OH + 6, OW + 8, dst.dtype, tuple(dst.shape)))
+        surf = layout.as_ctypes()
+        self._ck(self.lib.eve_eye_warp_surface_to_stem(dt_code(dst.dtype), ctypes.byref(surf), mat, N, self._p(frames), self._p(warps),
+                                                       None if lens is None else self._p(lens), OH, OW, self._p(dst), self._stream()))
+        return dst
+
+    def screen_area_surface_to_nchw(self, frames, out_hw, layout, matrix='bt601'):
+        """screen_area_fmt_to_nchw on surfaces as they lie in memory (frames and layout as for eye_warp_surface_to_nchw): every
+        visible pixel is read through the layout's address rule, converted, then averaged -- the format call's bits on the
+        de-pitched, cropped, byte-linear frame (include/eve_hip.h eve_screen_area_surface_to_nchw)."""
+        N, mat = self._surface_args('screen_area_surface_to_nchw', frames, layout, matrix)
+        OH, OW = int(out_hw[0]), int(out_hw[1])
+        out = torch.empty((N, 3, OH, OW), dtype=torch.float32, device=frames.device)
+        surf = layout.as_ctypes()
+        self._ck(self.lib.eve_screen_area_surface_to_nchw(ctypes.byref(surf), mat, N, self._p(frames), OH, OW, self._p(out), self._stream()))
+        return out
+
     def eye_pose_normalize(self, pose, out_hw):
         """Eye normalisation derived from the head pose, both eyes of N frames in one launch: pose float32 [N,18] =
         (fx, fy, cx, cy, rvec, tvec, left eye centre, right eye centre, focal_norm, distance_norm) per frame (data.eye_pose),

@@ -37,9 +37,14 @@ SCREEN_FRAME_KEYS = {'screen_frame': 'rgb', 'screen_frame_bgr': 'bgr', 'screen_f
                      'screen_frame_yuyv': 'yuyv'}
 
 
+# one more screen key: the capture as a decoder's or capture API's surface lies in memory, uint8 [B, T, rows, pitch] or
+# [B, T, frame_bytes], read through RefineNet.screen_layout (a data.SurfaceLayout); the mirror of eye_net.EYE_SURFACE_KEY
+SCREEN_SURFACE_KEY = 'screen_surface'
+
+
 def screen_frame_key(batch):
-    """The one screen key of SCREEN_FRAME_KEYS the batch holds, or None; two of them raise ValueError."""
-    found = [k_ for k_ in SCREEN_FRAME_KEYS if k_ in batch]
+    """The one screen key of SCREEN_FRAME_KEYS (or SCREEN_SURFACE_KEY) the batch holds, or None; two of them raise ValueError."""
+    found = [k_ for k_ in tuple(SCREEN_FRAME_KEYS) + (SCREEN_SURFACE_KEY,) if k_ in batch]
     if len(found) > 1:
         raise ValueError('give the screen under one key, not both: found %s' % ', '.join(found))
     return found[0] if found else None
@@ -337,9 +342,12 @@ class RefineNet(nn.Module):
     # 'bt709' (limited range: what HD recordings and hardware decoders of HD video usually are) or 'jfif' (full range).  Anything
     # else raises ValueError at use.
     yuv_matrix = 'bt601'
+    # How screen_surface captures lie in memory: a data.SurfaceLayout (format, visible size, pitch, coded rows, crop origin, plane
+    # offsets).  A screen_surface capture without it raises ValueError.
+    screen_layout = None
 
     def forward_sequence(self, heatmap_initial, screen_frame=None, initial_states=None, screen_frame_bgr=None, screen_frame_nv12=None,
-                         screen_frame_i420=None, screen_frame_yuyv=None):
+                         screen_frame_i420=None, screen_frame_yuyv=None, screen_surface=None):
         """heatmap_initial [B,T,1,h,w], screen_frame [B,T,3,H,W] -> (heatmap_final [B,T,1,H,W],
         list over cells of the stacked states [B,T,C,5,8] (tuple of two for CLSTM)).
         screen_frame may also be uint8 [B,T,IH,IW,3|4]: decoded frames at the screen size, or a full-resolution capture that is
@@ -350,10 +358,15 @@ class RefineNet(nn.Module):
         even): in place of screen_frame, the capture as a decoder or a capture path delivers it; every pixel is converted by the
         integer matrix self.yuv_matrix names as the area resize reads it (eve_screen_area_fmt_to_nchw), and the result is that of
         the converted RGB capture as screen_frame, bit for bit.  One screen argument at a time: two raise ValueError.
+        screen_surface (uint8 [B,T,rows,pitch] or [B,T,frame_bytes]): in place of screen_frame, the capture as a decoder's or capture
+        API's surface lies in memory -- pitched rows, coded rows, a window of a larger texture, NV21 / YV12 / UYVY / P010 / pitched
+        BGRA -- read through self.screen_layout, a data.SurfaceLayout (eve_screen_area_surface_to_nchw): the result is that of the
+        de-pitched, cropped, byte-linear capture under its format's key, bit for bit.
         initial_states: None (zero states), or per cell the state before the first frame -- reference layout [B, C, 5, 8] as
         returned here (the last frame of a previous call), or the internal NHWC layout [B, 5, 8, C]; (h, c) for CLSTM."""
         screen_frame = self._screen_input(screen_frame, screen_frame_bgr=screen_frame_bgr, screen_frame_nv12=screen_frame_nv12,
-                                          screen_frame_i420=screen_frame_i420, screen_frame_yuyv=screen_frame_yuyv)
+                                          screen_frame_i420=screen_frame_i420, screen_frame_yuyv=screen_frame_yuyv,
+                                          screen_surface=screen_surface)
         hf, states, to_ref = self._sequence(heatmap_initial, screen_frame, self._initial_states_in(initial_states))
         return hf, [tuple(to_ref(t) for t in st) if isinstance(st, tuple) else to_ref(st) for st in states]
 
@@ -361,11 +374,12 @@ class RefineNet(nn.Module):
         """screen_frame as it is, or the float [B,T,3,H,W] screen input made from the one capture given under a key of
         SCREEN_FRAME_KEYS other than screen_frame -- BGR(A), NV12, I420 or YUYV (one area-resize launch)."""
         given = {k_: v for k_, v in captures.items() if v is not None}
-        assert all(k_ in SCREEN_FRAME_KEYS and k_ != 'screen_frame' for k_ in given), sorted(given)
+        assert all((k_ in SCREEN_FRAME_KEYS and k_ != 'screen_frame') or k_ == SCREEN_SURFACE_KEY for k_ in given), sorted(given)
         if not given:
             return screen_frame
         if screen_frame is not None or len(given) > 1:
-            raise ValueError('give the screen as screen_frame or under one of %s, not both' % ', '.join(k_ for k_ in SCREEN_FRAME_KEYS if k_ != 'screen_frame'))
+            raise ValueError('give the screen as screen_frame or under one of %s, not both' % ', '.join(
+                [k_ for k_ in SCREEN_FRAME_KEYS if k_ != 'screen_frame'] + [SCREEN_SURFACE_KEY]))
         (key, capture), = given.items()
         from . import data
         cfg = self.config
@@ -376,6 +390,14 @@ class RefineNet(nn.Module):
                     getattr(capture, 'dtype', type(capture)), tuple(getattr(capture, 'shape', ()))))
             return data.preprocess_screen_frames(capture, size=size, bgr=True)
         from .kernels import YUV_MATRICES, pixel_format_shape
+        if key == SCREEN_SURFACE_KEY:
+            if self.screen_layout is None:
+                raise ValueError('%s needs RefineNet.screen_layout, a data.SurfaceLayout that says how the capture lies in memory' % key)
+            if self.yuv_matrix not in YUV_MATRICES:
+                raise ValueError('RefineNet.yuv_matrix must be one of %s, got %r' % (', '.join(YUV_MATRICES), self.yuv_matrix))
+            flat, lead = data.surface_frames(capture, self.screen_layout, 2, name=key)
+            out = data.preprocess_screen_frames(flat, size=size, layout=self.screen_layout, matrix=self.yuv_matrix)
+            return out.view(lead + tuple(out.shape[1:]))
         pixel_format_shape(capture, SCREEN_FRAME_KEYS[key], lead=2, name=key)
         if self.yuv_matrix not in YUV_MATRICES:
             raise ValueError('RefineNet.yuv_matrix must be one of %s, got %r' % (', '.join(YUV_MATRICES), self.yuv_matrix))

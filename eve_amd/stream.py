@@ -231,7 +231,7 @@ class EVEStream(object):
         raised before anything is launched or captured."""
         from .data import OverlaySpec, eye_patch_hw
         from .kernels import pixel_format_shape
-        from .refine_net import SCREEN_FRAME_KEYS, screen_frame_key
+        from .refine_net import SCREEN_FRAME_KEYS, SCREEN_SURFACE_KEY, screen_frame_key
         if not isinstance(spec, OverlaySpec):
             raise ValueError('step: render must be an eve_amd.OverlaySpec, got %s' % type(spec).__name__)
         cfg = self.model.config
@@ -239,6 +239,9 @@ class EVEStream(object):
         if key is None:
             raise ValueError('step: render draws onto the screen capture, and the chunk holds none (screen_frame, or one of %s)' %
                              ', '.join(k_ for k_ in SCREEN_FRAME_KEYS if k_ != 'screen_frame'))
+        if key == SCREEN_SURFACE_KEY:
+            raise ValueError('step: render does not draw onto a %s capture: the overlay reads byte-linear frames (hand the capture over '
+                             'under one of %s to render)' % (key, ', '.join(SCREEN_FRAME_KEYS)))
         frames = chunk[key]
         net_hw = (int(cfg.screen_size[1]), int(cfg.screen_size[0]))
         if key == 'screen_frame' and (not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() != 5 or
@@ -421,8 +424,23 @@ class EVEStream(object):
         sample, the bit-exact integer matrix model.eye_net.yuv_matrix names ('bt601' default, 'bt709', 'jfif') -- inside the step
         and the captured graph, whose input buffer holds the frame as it came (NV12 / I420: half of RGB's bytes, YUYV two thirds)
         and whose key holds the matrix.  The step equals the camera_frame step on the converted frame bit for bit; camera_lens,
-        eye_pose, lengths, eye_mask and skip_invalid_pose combine with these keys unchanged.  Not offered: row pitches or separate
-        plane pointers, UYVY / NV21 / P010 / 10-bit layouts, bilinear chroma up-sampling -- for the camera and for the screen alike.
+        eye_pose, lengths, eye_mask and skip_invalid_pose combine with these keys unchanged.
+
+        A decoder's or a capture API's SURFACE goes in as it lies in memory -- rows with a pitch, more coded rows than visible
+        ones, chroma planes at aligned offsets, a window of a larger texture; NV21, YV12, UYVY, P010 (read as its high byte: the
+        sample >> 8, a truncation) and pitched RGB(A) / BGR(A) beside the formats above -- under one more key on each side:
+          camera_surface     [B, Tc, rows, pitch] or [B, Tc, frame_bytes]   with model.eye_net.camera_layout
+          screen_surface     [B, Tc, rows, pitch] or [B, Tc, frame_bytes]   with model.refine_net.screen_layout
+        each layout a data.SurfaceLayout(format, width, height, pitch=, coded_height=, x0=, y0=, plane_offsets=); a surface key
+        without its layout is a ValueError, two frame keys on one side too.  eve_eye_warp_surface_to_stem / _to_nchw read the
+        four taps of an output pixel, and eve_screen_area_surface_to_nchw every visible pixel, through the layout's address rule
+        inside the step and the captured graph: the graph's input buffer is the surface copied whole, padding included (no
+        de-pitch, crop or byte-shuffle pass runs before the step), and both layouts are part of the graph's key.  The step equals
+        the one on the de-pitched, cropped, byte-linear frames under their format's key bit for bit; camera_lens, eye_pose,
+        face_landmarks, lengths, eye_mask and skip_invalid_pose combine unchanged.  render= with a screen_surface chunk is
+        refused (ValueError): the overlay reads byte-linear captures.  Not offered: planes in separate allocations, bottom-up
+        (negative-pitch) images, tiled or compressed surfaces, 10-bit arithmetic, bilinear chroma up-sampling -- for the camera
+        and for the screen alike.
 
         lengths: None, or num_streams integers in 0..Tc (list, numpy array or CPU tensor) for streams that delivered different
         numbers of frames: stream b consumes frames 0..lengths[b]-1 of the chunk, and every carried state of it afterwards is the
@@ -525,11 +543,12 @@ class EVEStream(object):
         return tuple(_module_key(m) for m in (self.model.eye_net, self.model.refine_net) if m is not None)
 
     def _graph_key(self, chunk, return_heatmaps, ragged=False, masked=False, render=None):
-        """What a captured graph is good for: the step's mode, both YUV matrices, the overlay (render: None or a _render_plan -- its
-        OverlaySpec by value) and every chunk tensor's key, shape and dtype."""
+        """What a captured graph is good for: the step's mode, both YUV matrices, both surface layouts (by value), the overlay
+        (render: None or a _render_plan -- its OverlaySpec by value) and every chunk tensor's key, shape and dtype."""
         ref = self.model.refine_net
         spec = None if render is None else render['spec'].key()
-        return (return_heatmaps, ragged, masked, self.model.eye_net.yuv_matrix, None if ref is None else ref.yuv_matrix, spec) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
+        layouts = (self.model.eye_net.camera_layout, None if ref is None else ref.screen_layout)
+        return (return_heatmaps, ragged, masked, self.model.eye_net.yuv_matrix, None if ref is None else ref.yuv_matrix, spec, layouts) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
 
     def _graph_for(self, chunk, return_heatmaps, ragged=False, masked=False, render=None):
         wk = self._weights_key()

@@ -814,8 +814,8 @@ int eve_eye_warp_lens_u8_to_stem(int dtype /* EVE_DT_BF16 | EVE_DT_F16 */, long 
  * contract, or [N][12] rows for the lens contract (eve_eye_warp_lens_u8_to_*).  No alignment is asked of `frames`.  Kernel names:
  * eye_warp_fmt_kernel<F,L,T> with F in bgr, bgra, nv12, i420, yuyv; L plain or lens; T float, eve::bf16_t or eve::f16_t.
  * Refused without a launch: an unknown format, an unknown matrix with a YUV format, odd dimensions as above, and what the
- * plain pair refuses.  Not offered: row pitches or separate plane pointers, UYVY / NV21 / P010 or any 10-bit layout, bilinear
- * chroma up-sampling, gradients.                                                                                           */
+ * plain pair refuses.  Row pitches, crops, UYVY / NV21 / YV12 and P010's high bytes go through eve_eye_warp_surface_to_nchw
+ * below.  Not offered: planes in separate allocations, 10-bit arithmetic, bilinear chroma up-sampling, gradients.            */
 enum { EVE_PIX_BGR = 0, EVE_PIX_BGRA = 1, EVE_PIX_NV12 = 2, EVE_PIX_I420 = 3, EVE_PIX_YUYV = 4 };
 enum { EVE_YUV_BT601 = 0, EVE_YUV_BT709 = 1, EVE_YUV_JFIF = 2 };
 int eve_eye_warp_fmt_to_nchw(int format, int matrix, long long N, int IH, int IW, const uint8_t* frames, const float* warps,
@@ -840,10 +840,64 @@ int eve_eye_warp_fmt_to_stem(int dtype /* EVE_DT_BF16 | EVE_DT_F16 */, int forma
  * nv12, i420, yuyv (true: the vector form), screen_u8_area_bgr_kernel<true | false> for BGR(A).  Refused without a launch,
  * the message beginning "screen_area_fmt_to_nchw:": bad arguments, an unknown format, an unknown matrix with a YUV format, odd
  * dimensions as above, upscaling in either direction, IH * IW > 16 843 009, IW * 12 > 163 840 bytes (one row of three 32-bit
- * column sums is kept in LDS; BGR(A): IW * C * 4), N * OH >= 2^31.  Not offered: row pitches or separate plane pointers,
- * UYVY / NV21 / P010 or any 10-bit layout, bilinear chroma up-sampling.                                                      */
+ * column sums is kept in LDS; BGR(A): IW * C * 4), N * OH >= 2^31.  Row pitches, crops, UYVY / NV21 / YV12 and P010's high
+ * bytes go through eve_screen_area_surface_to_nchw below.  Not offered: planes in separate allocations, 10-bit arithmetic,
+ * bilinear chroma up-sampling.                                                                                              */
 int eve_screen_area_fmt_to_nchw(int format, int matrix, long long N, int IH, int IW, const uint8_t* src, int OH, int OW,
                                 float* dst_nchw, eve_stream_t stream);
+/* Surfaces: frames as a hardware decoder or a capture API leaves them in memory -- rows with a pitch, more coded rows than visible
+ * ones, chroma planes at aligned offsets, a window of a larger texture -- addressed through one small descriptor, so that no
+ * de-pitch, crop or byte-shuffle copy runs before the step.  The address rule is the whole contract: component c of pixel (x, y)
+ * of the visible region is the single byte at
+ *   frame + offset[c] + (y >> ys) * pitch[c] + (x >> xs) * step[c]
+ * with xs = ys = 0 for component 0 and for EVE_SURF_RGB, xs = xshift and ys = yshift for components 1 and 2 of EVE_SURF_YUV, all in
+ * 64-bit arithmetic; frame n begins n * frame_stride bytes behind the pointer.  That covers packed and planar RGB / BGR / RGBA /
+ * BGRA / ARGB with a pitch (for BGRA: offset = {2, 1, 0}, step 4); NV12, NV21, I420, YV12, YUYV, UYVY, YVYU, NV16, I422, I444; any
+ * crop (a crop is other offsets; on a subsampled axis its origin must be even, or the chroma phase shifts); and P010 / P016 read
+ * as their most significant byte (offset + 1 within the little-endian word, step 2 for luma and 4 for chroma): that sample is the
+ * 16-bit word >> 8, a TRUNCATION to 8 bits, not a rounding.  Chroma is the nearest sample.  From the three 8-bit values on --
+ * the integer matrix for EVE_SURF_YUV, everything behind it -- the contracts are those of the format entry points above, so with
+ * linear() the gather of the visible region into the byte-linear layout (tests/surface_ref.py),
+ *   eye_warp_surface(buf, S)    == eve_eye_warp_fmt_to_* (or _u8_to_*) on linear(buf, S)
+ *   screen_area_surface(buf, S) == eve_screen_area_fmt_to_nchw (or eve_screen_u8_area_to_nchw) on linear(buf, S)
+ * bit for bit.  No byte outside the addresses the rule names is read: padding, coded rows below the picture and a fourth channel
+ * never reach a result.  All planes lie inside one frame's byte range [0, frame_bytes).                                         */
+enum { EVE_SURF_RGB = 0, EVE_SURF_YUV = 1 };
+typedef struct eve_surface {
+    int struct_bytes;        /* sizeof(eve_surface); a mismatch is refused                                    */
+    int kind;                /* EVE_SURF_RGB: components are R, G, B.  EVE_SURF_YUV: Y, U, V                     */
+    int width, height;       /* the VISIBLE region, IW x IH; pixel (0, 0) is its top-left                      */
+    long long frame_stride;  /* bytes from one frame to the next                                               */
+    long long frame_bytes;   /* bytes of a frame that may be read: the limit of the bound check                */
+    long long offset[3];     /* byte, within its frame, of component c's sample for pixel (0, 0)               */
+    int pitch[3];            /* bytes from a row of component c to the next, >= 1                              */
+    int step[3];             /* bytes from a sample of component c to the next along a row, >= 1               */
+    int xshift, yshift;      /* YUV only, 0 or 1: components 1, 2 are read at (x >> xshift, y >> yshift)        */
+} eve_surface;
+/* The eye-patch warp from a surface: eve_eye_warp_fmt_to_nchw / _to_stem with the four taps of an output pixel read through the
+ * address rule; coordinates, lens model (lens NULL or [N][12]), weights, blend, value and both output layouts are the same code.
+ * The descriptor travels by value in the kernel's arguments.  matrix: EVE_YUV_* for EVE_SURF_YUV, ignored for EVE_SURF_RGB.
+ * Kernel names: eye_warp_surface_kernel<K,L,T> with K rgb or yuv; L plain or lens; T float, eve::bf16_t or eve::f16_t.  Refused
+ * without a launch, the message beginning with the entry point's name: a null descriptor, a wrong struct_bytes, an unknown kind, an
+ * unknown matrix with EVE_SURF_YUV, shifts outside 0..1 or non-zero for EVE_SURF_RGB, a pitch or step < 1, a negative offset, any
+ * component whose last addressed byte offset + ((height-1) >> ys) * pitch + ((width-1) >> xs) * step is >= frame_bytes,
+ * frame_bytes > frame_stride with N > 1, and what the plain pair refuses (width, height <= 16384).                             */
+int eve_eye_warp_surface_to_nchw(const eve_surface* surface, int matrix, long long N, const uint8_t* frames, const float* warps,
+                                 const float* lens /* may be NULL */, int OH, int OW, float* dst_nchw, eve_stream_t stream);
+int eve_eye_warp_surface_to_stem(int dtype /* EVE_DT_BF16 | EVE_DT_F16 */, const eve_surface* surface, int matrix, long long N,
+                                 const uint8_t* frames, const float* warps, const float* lens /* may be NULL */, int OH, int OW,
+                                 void* x_padded, eve_stream_t stream);
+/* The screen area resize from a surface, in eve_screen_area_fmt_to_nchw's order: convert every visible pixel, the exact integer
+ * area sum, one division.  8-bit 4:2:0 with luma step 1 and chroma either interleaved in one plane (NV12, NV21) or in two planes
+ * (I420, YV12) keeps the wide loads: 8 luma bytes per row and 8 (4 + 4) chroma bytes per row pair when width is a multiple of 8
+ * and base pointer, offsets, pitches and frame_stride put every such load on its own size; otherwise a byte form with the same
+ * bits.  Every other descriptor (packed YUV, RGB kinds, P010, 4:2:2, 4:4:4) takes a generic form of three byte loads per pixel.
+ * Kernel names: screen_area_surface_kernel<yuv420,true | false> (true: the vector form) and screen_area_surface_kernel<generic,false>.
+ * One row of three 32-bit column sums is kept in LDS (width * 12 <= 163 840 bytes) and width * height <= 16 843 009, as above.
+ * Refused without a launch, the message beginning "screen_area_surface_to_nchw:": what eve_eye_warp_surface_to_nchw refuses of
+ * the descriptor, bad arguments, upscaling in either direction, those two limits, N * OH >= 2^31.                              */
+int eve_screen_area_surface_to_nchw(const eve_surface* surface, int matrix, long long N, const uint8_t* src, int OH, int OW,
+                                    float* dst_nchw, eve_stream_t stream);
 /* The tracking overlay: one launch that turns N full-resolution captures into the annotated frames an encoder or a display reads.
  * src: N frames back to back in `in_format`, byte-linear as above (EVE_PIX_RGB / _RGBA: [IH][IW][3 | 4], channel 0 red; these two
  * codes are taken here only).  dst: `out_format` EVE_PIX_RGB or _BGR ([IH][IW][3]), EVE_PIX_NV12 or _I420 ([IH*3/2][IW], IH and IW

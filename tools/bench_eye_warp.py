@@ -3,7 +3,7 @@
 and of one EVEStream step fed whole camera frames next to the same step fed pre-cut uint8 patches.
 
     python tools/bench_eye_warp.py [--patches 64] [--size 1920x1080] [--iters 500] [--rounds 5] [--shapes 1x1 8x4 32x2]
-                                   [--steps 50] [--dtype bf16] [--lens] [--pose] [--format nv12] [--landmarks]
+                                   [--steps 50] [--dtype bf16] [--lens] [--pose] [--format nv12] [--landmarks] [--surface]
                                    [--markdown profiles/table.md]
 
 Part 1, per launch, the four routes interleaved in one process (the median over the rounds of events around `iters` calls):
@@ -37,7 +37,17 @@ the first 8 sequences, taken from the contract in numpy (tests/face_pose_ref.py:
 fraction of frames that got a solution (a frame that reaches the contract's cap of 32 accepted steps has none).  In
 part 2 a stream `face` feeds camera_frame + face_landmarks [B, Tc, 68, 3] + face_rig and none of the derived keys, next to `pose`.
 The eye_pose step of ANOTHER checkout (the parent commit's) is measured by running that checkout's own `--pose --shapes 32x2` in
-alternating rounds with this one, process by process; this file only measures the tree it lies in."""
+alternating rounds with this one, process by process; this file only measures the tree it lies in.
+
+--surface: nothing of the above; instead the surface launches (eve_eye_warp_surface_to_nchw / _to_stem) on N frames of the given
+size as a decoder leaves them -- NV12 in rows of 2048 bytes and 1088 coded rows, then P010 in rows of 4096 -- three routes
+interleaved in one process:
+    linear_*    the byte-linear launch (eve_eye_warp_fmt_to_*) on the linearised NV12 frames: what the surface launch stands beside
+    surface_*   the surface launch on the padded buffer
+    copy_*      what a caller did before: a torch de-pitch copy (P010: the high bytes) into a byte-linear NV12 frame, then linear_*;
+                copy_only is that pass alone
+and, per --shapes, an EVEStream step fed camera_surface + screen_surface (both NV12 in 2048 x 1088) next to the same step fed
+camera_frame_nv12 + screen_frame_nv12 on the linearised frames."""
 import argparse
 import json
 import math
@@ -189,6 +199,111 @@ def to_rgb_device(buf, fmt, IH, IW):
 
 def median(v):
     return sorted(v)[len(v) // 2]
+
+
+def surface_pair(fmt, lead, IH, IW, pitch_px=2048, coded=1088, gen=None):
+    """A decoder's surface and its content -> (SurfaceLayout, buf uint8 lead + [coded * 3 / 2, pitch] of random bytes, padding
+    included, and the byte-linear NV12 frames lead + [IH * 3 / 2, IW] it holds).  fmt: 'nv12' or 'p010' (2 bytes per sample)."""
+    from eve_amd.data import SurfaceLayout
+    bpp = 2 if fmt == 'p010' else 1
+    L = SurfaceLayout(fmt, IW, IH, pitch=pitch_px * bpp, coded_height=coded)
+    shape = tuple(lead) + (coded * 3 // 2, pitch_px * bpp)
+    buf = torch.randint(0, 256, shape, dtype=torch.uint8, device='cuda') if gen is None else torch.randint(0, 256, shape, generator=gen, dtype=torch.uint8).cuda()
+    return L, buf, depitch(buf, fmt, IH, IW, coded)
+
+
+def depitch(buf, fmt, IH, IW, coded):
+    """The pass a caller ran before the byte-linear launch: the visible luma and chroma rows of a padded NV12 / P010 surface
+    [..., coded * 3 / 2, pitch] gathered into one byte-linear NV12 frame [..., IH * 3 / 2, IW] (P010: the high byte of each word)."""
+    v = buf.view(buf.shape[:-1] + (buf.shape[-1] // 2, 2))[..., 1] if fmt == 'p010' else buf
+    return torch.cat([v[..., :IH, :IW], v[..., coded:coded + IH // 2, :IW]], dim=-2).contiguous()
+
+
+def surface_launches(args, IH, IW):
+    k = default_kernels()
+    N = args.patches
+    torch.manual_seed(N)
+    warps = warps_for(N, IH, IW, seed=N).cuda()
+    packed = torch.empty((N, HW[0] + 6, HW[1] + 8, 4), dtype=torch.bfloat16, device='cuda')
+    rows = []
+    for fmt in ('nv12', 'p010'):
+        L, buf, lin = surface_pair(fmt, (N,), IH, IW)
+        routes = {'linear_nchw': lambda: k.eye_warp_fmt_to_nchw(lin, warps, HW, 'nv12'),
+                  'surface_nchw': lambda: k.eye_warp_surface_to_nchw(buf, warps, HW, L),
+                  'copy_nchw': lambda: k.eye_warp_fmt_to_nchw(depitch(buf, fmt, IH, IW, L.coded_height), warps, HW, 'nv12'),
+                  'linear_stem': lambda: k.eye_warp_fmt_to_stem(lin, warps, HW, 'nv12', out=packed),
+                  'surface_stem': lambda: k.eye_warp_surface_to_stem(buf, warps, HW, L, out=packed),
+                  'copy_stem': lambda: k.eye_warp_fmt_to_stem(depitch(buf, fmt, IH, IW, L.coded_height), warps, HW, 'nv12', out=packed),
+                  'copy_only': lambda: depitch(buf, fmt, IH, IW, L.coded_height)}
+        slow = {'copy_nchw', 'copy_stem', 'copy_only'}
+        assert torch.equal(routes['surface_nchw'](), routes['linear_nchw']()) and torch.equal(routes['copy_nchw'](), routes['linear_nchw']())
+        for fn in routes.values():
+            for _ in range(5):
+                fn()
+        torch.cuda.synchronize()
+        times = {name: [] for name in routes}
+        for _ in range(args.rounds):
+            for name, fn in routes.items():
+                times[name].append(device_ms(fn, max(1, args.iters // 10) if name in slow else args.iters))
+        res = {'surface': fmt, 'patches': N, 'frame': '%dx%d' % (IW, IH), 'pitch': L.pitch, 'coded_height': L.coded_height, 'iters': args.iters,
+               'rounds': args.rounds, 'frame_bytes': {'surface': L.frame_bytes, 'linear': lin[0].numel()}}
+        for name, t in times.items():
+            res[name + '_us'] = round(1e3 * median(t), 2)
+            res[name + '_us_min_max'] = [round(1e3 * min(t), 2), round(1e3 * max(t), 2)]
+        for form in ('nchw', 'stem'):
+            res['surface_over_linear_' + form] = round(median(times['surface_' + form]) / median(times['linear_' + form]), 3)
+            res['copy_over_surface_' + form] = round(median(times['copy_' + form]) / median(times['surface_' + form]), 2)
+        routes['surface_stem']()
+        res['kernel'] = k.lib.eve_last_kernel().decode()
+        print(json.dumps(res), flush=True)
+        rows.append(res)
+        del routes, buf, lin
+    return rows
+
+
+def surface_steps(args, IH, IW):
+    cfg = eve_amd.reset_standalone_config()
+    cfg.import_json(os.path.join(REPO, 'configs', 'refine_net.json'))
+    cfg.import_dict({'eye_net_load_pretrained': False})
+    model = eve_amd.EVE(output_predictions=True)
+    model.eye_net.compute_dtype = model.refine_net.compute_dtype = DTYPES[args.dtype]
+    detweights.fill_module(model.eye_net, 0)
+    detweights.fill_module(model.refine_net, 1)
+    model = model.cuda().eval()
+    rows = []
+    for shape in args.shapes:
+        B, Tc = (int(v) for v in shape.split('x'))
+        small = detweights.eve_batch(min(B, 4), Tc, seed=1)
+        rest = {k_: torch.cat([small[k_]] * ((B + 3) // 4), dim=0)[:B].contiguous().cuda() for k_ in STREAM_KEYS if k_ in small and k_ != 'screen_frame'}
+        rest.update(left_eye_warp=warps_for(B * Tc, IH, IW, seed=B).view(B, Tc, 3, 3).cuda(),
+                    right_eye_warp=warps_for(B * Tc, IH, IW, seed=B + 1).view(B, Tc, 3, 3).cuda())
+        g = torch.Generator().manual_seed(B * 1000 + Tc)
+        cl, cam, cam_lin = surface_pair('nv12', (B, Tc), IH, IW, gen=g)
+        sl, scr, scr_lin = surface_pair('nv12', (B, Tc), IH, IW, gen=g)
+        model.eye_net.camera_layout, model.refine_net.screen_layout = cl, sl
+        streams = {'surface': (eve_amd.EVEStream(model, B), dict(rest, camera_surface=cam, screen_surface=scr)),
+                   'nv12': (eve_amd.EVEStream(model, B), dict(rest, camera_frame_nv12=cam_lin, screen_frame_nv12=scr_lin))}
+        outs = {}
+        for name, (s, chunk) in streams.items():
+            for _ in range(3):
+                outs[name] = s.step(chunk)       # capture + warm replays
+        torch.cuda.synchronize()
+        assert all(torch.equal(outs['surface'][k_], outs['nv12'][k_]) for k_ in outs['nv12']), 'the two steps disagree'
+        times = {name: [] for name in streams}
+        for _ in range(args.rounds):
+            for name, (s, chunk) in streams.items():
+                times[name].append(device_ms(lambda: s.step(chunk), args.steps))
+        res = {'B': B, 'Tc': Tc, 'dtype': args.dtype, 'frame': '%dx%d' % (IW, IH), 'steps': args.steps, 'rounds': args.rounds}
+        for name, t in times.items():
+            res[name + '_step_ms'] = round(median(t), 4)
+            res[name + '_step_ms_min_max'] = [round(min(t), 4), round(max(t), 4)]
+        res['surface_minus_nv12_ms'] = round(res['surface_step_ms'] - res['nv12_step_ms'], 4)
+        res['MB_copied'] = {'surface': round((cam.numel() + scr.numel()) / 1e6, 1), 'nv12': round((cam_lin.numel() + scr_lin.numel()) / 1e6, 1)}
+        rows.append(res)
+        print(json.dumps(res), flush=True)
+        del streams, cam, scr, cam_lin, scr_lin
+        torch.cuda.empty_cache()
+    return rows
 
 
 def launches(args, IH, IW):
@@ -354,11 +469,18 @@ def main():
                     help='also time the launches and an EVEStream step on frames in this layout, and convert-then-warp beside them')
     ap.add_argument('--landmarks', action='store_true',
                     help='also time eve_face_pose_solve and an EVEStream step with face_landmarks + face_rig (implies --pose)')
+    ap.add_argument('--surface', action='store_true',
+                    help='time the surface launches and an EVEStream step with camera_surface + screen_surface instead (NV12 / P010 in 2048 x 1088)')
     ap.add_argument('--markdown', default=None, help='also write the tables to this file')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit('bench_eye_warp: no GPU (a time is only measured on one)')
     IW, IH = (int(v) for v in args.size.lower().split('x'))
+    if args.surface:
+        with torch.no_grad():
+            surface_launches(args, IH, IW)
+            surface_steps(args, IH, IW)
+        return
     args.pose = args.pose or args.landmarks
     with torch.no_grad():
         solves = solve_launches(args, IH, IW) if args.landmarks else []

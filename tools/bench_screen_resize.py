@@ -8,7 +8,7 @@ three routes interleaved in one process:
             capture; for fractional ratios not the same values)
 
     python tools/bench_screen_resize.py [--sizes 1920x1080 2560x1440] [--frames 1 32 240] [--channels 3] [--iters 20] [--rounds 5]
-                                        [--markdown profiles/table.md] [--format rgb|bgr|nv12|i420|yuyv]
+                                        [--markdown profiles/table.md] [--format rgb|bgr|nv12|i420|yuyv] [--surface]
 
 One JSON line per (size, N): per route the median over the rounds of the device time per call (events around `iters` calls), and
 for `area` and `clone` the rate N*IH*IW*C / time as a fraction of the 8 TB/s HBM peak (`clone` moves twice those bytes).  Every
@@ -22,7 +22,15 @@ delivers it (eve_screen_area_fmt_to_nchw), three other routes interleaved round 
     rgb        HipKernels.screen_u8_area_to_nchw on the SAME frames converted beforehand (conversion not timed): the launch the new one stands beside
     torch+rgb  what a caller had before: a whole-frame conversion with torch (the same integer matrix), then the RGB launch
 
-One JSON line per (size, N) with each route's median, minimum and maximum over the rounds."""
+One JSON line per (size, N) with each route's median, minimum and maximum over the rounds.
+
+--surface measures the capture as it lies in a decoder's memory (eve_screen_area_surface_to_nchw): NV12 in rows of 2048 bytes and
+1088 coded rows, then P010 in rows of 4096 -- the routes interleaved round by round in one process:
+
+    linear       HipKernels.screen_area_fmt_to_nchw on the linearised NV12 frames: the launch the new one stands beside
+    surface      HipKernels.screen_area_surface_to_nchw on the padded buffer (NV12: the vector form; P010: the generic form)
+    copy+linear  what a caller had before: a torch de-pitch copy (P010: the high bytes) into byte-linear NV12, then `linear`;
+                 copy_only is that pass alone"""
 import argparse
 import json
 import os
@@ -96,6 +104,51 @@ def bench_format(args, k):
             torch.cuda.empty_cache()
 
 
+def bench_surface(args, k):
+    """The --surface measurement: one JSON line per (size, N, layout)."""
+    sys.path.insert(0, os.path.join(REPO, 'tools'))
+    from bench_eye_warp import depitch, surface_pair
+    for size in args.sizes:
+        IW, IH = (int(v) for v in size.lower().split('x'))
+        pitch_px, coded = -(-IW // 256) * 256 + (256 if IW % 256 == 0 else 0), -(-IH // 16) * 16 + (16 if IH % 16 == 0 else 0)
+        for N in args.frames:
+            for fmt in ('nv12', 'p010'):
+                torch.manual_seed(N + IW)
+                L, first, _ = surface_pair(fmt, (N,), IH, IW, pitch_px, coded)
+                copies = max(2, min(64, -(-ROTATE_BYTES // first.numel())))
+                bufs = [first] + [surface_pair(fmt, (N,), IH, IW, pitch_px, coded)[1]]
+                bufs += [bufs[i % 2].clone() for i in range(copies - 2)]
+                lins = [depitch(b, fmt, IH, IW, coded) for b in bufs]
+                routes = {'linear': lambda i: k.screen_area_fmt_to_nchw(lins[i % copies], OUT_HW, 'nv12'),
+                          'surface': lambda i: k.screen_area_surface_to_nchw(bufs[i % copies], OUT_HW, L),
+                          'copy+linear': lambda i: k.screen_area_fmt_to_nchw(depitch(bufs[i % copies], fmt, IH, IW, coded), OUT_HW, 'nv12'),
+                          'copy_only': lambda i: depitch(bufs[i % copies], fmt, IH, IW, coded)}
+                slow = {'copy+linear', 'copy_only'}
+                with torch.no_grad():
+                    assert torch.equal(routes['surface'](0), routes['linear'](0)) and torch.equal(routes['surface'](1), routes['copy+linear'](1))
+                    for fn in routes.values():               # warm up: code objects, allocator
+                        for i in range(3):
+                            fn(i)
+                    torch.cuda.synchronize()
+                    times = {name: [] for name in routes}
+                    for _ in range(args.rounds):
+                        for name, fn in routes.items():
+                            times[name].append(device_ms(fn, max(2, args.iters // 4) if name in slow else args.iters))
+                res = {'size': size, 'N': N, 'surface': fmt, 'pitch': L.pitch, 'coded_height': coded, 'surface_bytes': first.numel(),
+                       'visible_bytes': N * IH * IW * 3 // 2 * (2 if fmt == 'p010' else 1), 'linear_bytes': lins[0].numel(), 'captures_rotated': copies}
+                for name, t in times.items():
+                    res[name + '_us'] = round(1e3 * sorted(t)[len(t) // 2], 2)
+                    res[name + '_us_min_max'] = [round(1e3 * min(t), 2), round(1e3 * max(t), 2)]
+                res['surface_over_linear'] = round(res['surface_us'] / res['linear_us'], 3)
+                res['pitch_over_width'] = round(pitch_px / IW, 3)
+                res['copy_plus_linear_over_surface'] = round(res['copy+linear_us'] / res['surface_us'], 2)
+                routes['surface'](0)
+                res['kernel'] = k.lib.eve_last_kernel().decode()
+                print(json.dumps(res), flush=True)
+                del bufs, lins, routes, first
+                torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--sizes', nargs='+', default=['1920x1080', '2560x1440'])
@@ -105,10 +158,13 @@ def main():
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--markdown', default=None, help='also write the table to this file')
     ap.add_argument('--format', default='rgb', choices=('rgb', 'bgr', 'nv12', 'i420', 'yuyv'), help='the capture\'s layout (see above)')
+    ap.add_argument('--surface', action='store_true', help='measure eve_screen_area_surface_to_nchw on padded NV12 / P010 surfaces instead (see above)')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit('bench_screen_resize: no GPU (a time is only measured on one)')
     k = default_kernels()
+    if args.surface:
+        return bench_surface(args, k)
     if args.format in ('nv12', 'i420', 'yuyv'):
         return bench_format(args, k)
     area = k.screen_u8_area_bgr_to_nchw if args.format == 'bgr' else k.screen_u8_area_to_nchw
