@@ -194,6 +194,8 @@ SIGNATURES = {
     'eve_eye_warp_surface_to_stem': [I, POINTER(Surface), I, L, P, P, P, I, I, P, P],
     'eve_screen_area_surface_to_nchw': [POINTER(Surface), I, L, P, I, I, P, P],
     'eve_overlay_render': [I, I, I, L, I, I, P, P, I, P, P, P, F, F, P, I, I, I, I, P, I, I, I, I, I, I, P, P],
+    'eve_face_pose_solve_ex': [L, I, I, I, P, P, P, ctypes.c_double, P, P, P, P, P, P, P, P, P],
+    'eve_undistort_points': [L, P, P, L, P, P, P],
 }
 EXPORTS = sorted(list(SIGNATURES) + ['eve_abi_version', 'eve_last_error', 'eve_last_kernel'])
 

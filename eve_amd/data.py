@@ -39,7 +39,9 @@ uint8 frames is 4x less PCIe traffic, and the float values produced here are bit
   face_rig(K, model, eyes, focal_norm, distance_norm)
                                  a camera and a head model -> the float32 [..., 12 + 3L] rows of the `face_rig` key (EyeNet / EVE /
                                  EVEStream take `camera_frame` + `face_landmarks` + `face_rig` and solve the head pose on the device)
-  solve_head_pose(landmarks, rig) 2-D landmarks -> head_R, head_t, reproj_rms, valid (in place of cv2.solvePnP per frame)
+  solve_head_pose(landmarks, rig) 2-D landmarks -> head_R, head_t, reproj_rms, valid (in place of cv2.solvePnP per frame); lens= takes
+                                 landmarks of the RAW frame, huber_px= a Huber loss against landmarks that are confidently wrong
+  undistort_points(points, lens) raw-frame pixels -> pixels of the undistorted image (in place of cv2.undistortPoints)
   EyeNet.forward_sequence / RefineNet.forward_sequence / EVE accept the uint8 tensors directly (eye patches go straight
   into the stem kernel's packed bf16 layout, no float tensor is ever materialised).
   DevicePrefetcher(iterable)     pinned double-buffered H2D on a side stream
@@ -415,7 +417,41 @@ def face_rig(camera_matrix, face_model, eye_centers, focal_norm, distance_norm):
     return torch.from_numpy(out).to(camera_matrix.device) if as_torch else out
 
 
-def solve_head_pose(landmarks, rig, lengths=None):
+def check_huber_px(huber_px, where):
+    """None or a finite number > 0 (pixels) -> None or float; anything else raises ValueError."""
+    if huber_px is None:
+        return None
+    if isinstance(huber_px, bool) or not isinstance(huber_px, (int, float)) or not 0 < huber_px < float('inf'):
+        raise ValueError('%s: huber_px must be None or a finite number > 0 (pixels), got %r' % (where, huber_px))
+    return float(huber_px)
+
+
+def undistort_points(points, lens):
+    """Raw-frame pixels -> pixels of the undistorted image, on the device, in place of cv2.undistortPoints(..., P=K) on the host:
+    points float32 [..., 2] = (u, v); lens float32 [..., 12] rows from camera_lens with the same leading dimensions, or one row
+    [12] for all points.  -> (float64 [..., 2] = (fx*x + cx, fy*y + cy) with the row's own intrinsics, ok bool [...]).  Newton's
+    method on the forward model of the eye-warp kernels (include/eve_hip.h eve_undistort_points): exact to a few 1e-16 in
+    normalised coordinates after at most 5 steps on ordinary lenses, where OpenCV's five fixed-point passes leave up to 1e-4.
+    ok False (and a zero point): the iteration gave up (12 steps), the point lies at or beyond a pole of the rational model, a
+    NaN.  Beyond the fold-back radius of a strong barrel polynomial the model is not invertible and which pre-image is found is
+    not promised."""
+    ok = lambda t: torch.is_tensor(t) and t.dtype == torch.float32
+    if not ok(points) or points.dim() < 1 or points.shape[-1] != 2 or points.numel() == 0:
+        raise TypeError('expected float32 points shaped [..., 2], got %s %s' % (getattr(points, 'dtype', type(points)),
+                                                                                tuple(getattr(points, 'shape', ()))))
+    lead = tuple(points.shape[:-1])
+    if not ok(lens) or (tuple(lens.shape) != (12,) and tuple(lens.shape) != lead + (12,)):
+        raise TypeError('expected float32 lens rows shaped %s or (12,), got %s %s' % (lead + (12,), getattr(lens, 'dtype', type(lens)),
+                                                                                    tuple(getattr(lens, 'shape', ()))))
+    rows = lens.reshape(-1, 12).contiguous()
+    xy, good = default_kernels().undistort_points(points.reshape(-1, 2).contiguous(), rows)
+    rows = rows.to(torch.float64)
+    px = torch.stack([rows[:, 0] * xy[:, 0] + rows[:, 2], rows[:, 1] * xy[:, 1] + rows[:, 3]], dim=-1)
+    good = good != 0
+    return torch.where(good[:, None], px, torch.zeros_like(px)).view(lead + (2,)), good.view(lead)
+
+
+def solve_head_pose(landmarks, rig, lengths=None, lens=None, huber_px=None):
     """The head pose of every frame from its 2-D face landmarks, on the device, in place of one cv2.solvePnP per frame: landmarks
     float32 [S, T, L, 2 | 3] (or [T, L, 2 | 3] with rig [12 + 3L]: one sequence) = pixel (u, v[, w]) of the undistorted image, w an
     optional confidence (0 drops the point); rig float32 [S, 12 + 3L] from face_rig, one row per sequence; lengths None, or S
@@ -424,8 +460,18 @@ def solve_head_pose(landmarks, rig, lengths=None):
     every later frame from the frame before; a frame without a solution (a NaN, fewer than 4 weighted points, model points on a
     line, no convergence) has valid False, head_R = I, head_t = 0, reproj_rms = 0, and the next one starts cold.  Levenberg-
     Marquardt on the weighted reprojection error in float64; the contract is include/eve_hip.h eve_face_pose_solve.  Not
-    offered: landmarks of a distorted image (undistort the L points first), outlier rejection beyond the weights, an rvec,
-    gradients, per-frame camera matrices; a planar model runs, but which of its two minima is found is not promised."""
+    offered: RANSAC, an rvec, gradients, per-frame camera matrices; a planar model runs, but which of its two minima is found is
+    not promised.
+
+    lens: None, or float32 [S, T, 12] rows from camera_lens ([T, 12] for one sequence) -- the landmarks are then pixels of the RAW
+    frame, as a tracker fed the raw frame reports them: each is undistorted on the device (undistort_points' iteration; a point
+    it cannot invert is dropped like one of weight 0) and the rig keeps describing the undistorted image.  huber_px: None, or
+    k > 0 in pixels -- a Huber loss: a landmark further than k from its reprojection pulls with k / distance of its weight, so a
+    few landmarks that are confidently wrong (a hand, hair) no longer tilt the head; k = 3 suits 1 px of landmark noise.  A
+    frame that ends with fewer than 4 landmarks within k is invalid.  With either argument the result gains inliers, uint8
+    [S, T]: the landmarks within k, or the used ones without the loss, 0 where invalid (include/eve_hip.h
+    eve_face_pose_solve_ex); reproj_rms stays the weighted rms over ALL used landmarks.  Not promised: very few landmarks (L = 6)
+    with an outlier among them.  Without both, exactly what this function always returned."""
     ok = lambda t: torch.is_tensor(t) and t.dtype == torch.float32
     if not ok(landmarks) or landmarks.dim() not in (3, 4) or landmarks.shape[-1] not in (2, 3):
         raise TypeError('expected float32 landmarks shaped [S, T, L, 2 | 3], got %s %s' % (getattr(landmarks, 'dtype', type(landmarks)),
@@ -444,8 +490,19 @@ def solve_head_pose(landmarks, rig, lengths=None):
         lengths = torch.as_tensor(lengths).to(device=landmarks.device, dtype=torch.int32).contiguous()
         if tuple(lengths.shape) != (S,):
             raise ValueError('solve_head_pose: lengths needs one entry per sequence (%d)' % S)
-    head_R, head_t, rms, valid = default_kernels().face_pose_solve(landmarks.contiguous(), rig.contiguous(), lengths)
-    out = {'head_R': head_R, 'head_t': head_t, 'reproj_rms': rms, 'valid': valid != 0}
+    if lens is None and huber_px is None:
+        head_R, head_t, rms, valid = default_kernels().face_pose_solve(landmarks.contiguous(), rig.contiguous(), lengths)
+        out = {'head_R': head_R, 'head_t': head_t, 'reproj_rms': rms, 'valid': valid != 0}
+        return {k_: v[0] for k_, v in out.items()} if single else out
+    if lens is not None:
+        lens = lens[None] if single and ok(lens) and lens.dim() == 2 else lens
+        if not ok(lens) or tuple(lens.shape) != (S, T, 12):
+            raise TypeError('expected float32 lens rows shaped %s, got %s %s' % ((S, T, 12), getattr(lens, 'dtype', type(lens)),
+                                                                                tuple(getattr(lens, 'shape', ()))))
+        lens = lens.contiguous()
+    head_R, head_t, rms, valid, inliers = default_kernels().face_pose_solve_ex(landmarks.contiguous(), rig.contiguous(), lens,
+                                                                               check_huber_px(huber_px, 'solve_head_pose'), lengths)
+    out = {'head_R': head_R, 'head_t': head_t, 'reproj_rms': rms, 'valid': valid != 0, 'inliers': inliers}
     return {k_: v[0] for k_, v in out.items()} if single else out
 
 

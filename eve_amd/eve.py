@@ -23,7 +23,7 @@ import torch.nn as nn
 
 from . import losses, ops
 from .config import get_config
-from .eye_net import EyeNet, eye_input, eye_pose_batch, has_pose_form
+from .eye_net import EyeNet, eye_input, eye_pose_batch, face_landmarks_key, has_pose_form
 from .kernels import default_kernels
 from .refine_net import screen_capture
 
@@ -237,7 +237,7 @@ class EVE(nn.Module):
             full_input_dict = next(iter(full_input_dict.values()))
         # (the pose form -- camera_frame + eye_pose -- becomes the warp form in a copy, before the labels read left_o and left_R;
         # so does the face-landmark form, camera_frame + face_landmarks + face_rig: every sequence of a clip starts cold at t = 0)
-        d = eye_pose_batch(full_input_dict, cfg)
+        d = eye_pose_batch(full_input_dict, cfg, huber_px=self.eye_net.face_huber_px)
         self.calculate_additional_labels(d, current_epoch=current_epoch)
         B, T = eye_input(d).shape[:2]
 
@@ -271,8 +271,10 @@ class EVE(nn.Module):
         output_dict['right_pupil_size'] = inter['right_pupil_size']
         if has_pose_form(full_input_dict):                            # the pose forms: reported, folded into no validity
             output_dict['pose_valid'] = d['pose_valid']
-            if 'face_landmarks' in full_input_dict:                   # the head pose was solved here: the translation and the fit
+            if face_landmarks_key(full_input_dict) is not None:       # the head pose was solved here: the translation and the fit
                 output_dict['head_t'], output_dict['face_reproj_rms'] = d['head_t'], d['face_reproj_rms']
+                if 'face_inliers' in d:                               # (face_landmarks_raw or face_huber_px: eve_face_pose_solve_ex ran)
+                    output_dict['face_inliers'] = d['face_inliers']
         if self.output_predictions:                                   # eve.py:194-222
             for key in ('timestamps', 'o', 'left_R', 'head_R', 'millimeters_per_pixel', 'pixels_per_millimeter',
                         'camera_transformation', 'inv_camera_transformation'):
@@ -347,14 +349,16 @@ class EVE(nn.Module):
         face_state: with the face-landmark form (camera_frame + face_landmarks [B, Tc, L, 2 | 3] + face_rig [B, 12 + 3L]) the
         stream's carried head pose, float64 [B, 13], read as the pose before the chunk and overwritten with the pose after it by
         the eve_face_pose_solve launch, which also reads reset[:B] and lengths[:B]; the result gains pose_valid, head_t and
-        face_reproj_rms.
+        face_reproj_rms.  face_landmarks_raw (raw-frame pixels, with camera_lens) in place of face_landmarks, or
+        eye_net.face_huber_px, make it the eve_face_pose_solve_ex launch, and the result gains face_inliers [B, Tc].
         render: None, or EVEStream's overlay hook render(d, inter, out), called last with the chunk after eye_pose_batch (the derived
         warps included), the intermediate results (heatmap_final whether returned or not) and the result, to which it adds
         `rendered`; None issues no launch."""
         assert not self.training, 'EVE._predict_sequence is eval-only'
         B = eye_input(d).shape[0]
-        posed, faced = has_pose_form(d), 'face_landmarks' in d
-        d = dict(eye_pose_batch(d, self.config, face_state, None if reset is None else reset[:B], None if lengths is None else lengths[:B]))
+        posed, faced = has_pose_form(d), face_landmarks_key(d) is not None
+        d = dict(eye_pose_batch(d, self.config, face_state, None if reset is None else reset[:B], None if lengths is None else lengths[:B],
+                                huber_px=self.eye_net.face_huber_px))
         plan = eye_valid = None
         if masked:
             T = eye_input(d).shape[1]
@@ -380,6 +384,8 @@ class EVE(nn.Module):
             out['pose_valid'] = d['pose_valid']
         if faced:
             out['head_t'], out['face_reproj_rms'] = d['head_t'], d['face_reproj_rms']
+            if 'face_inliers' in d:
+                out['face_inliers'] = d['face_inliers']
         if plan is not None:
             out['valid'], out['eye_valid'] = plan['valid'].view(torch.bool), eye_valid
         if return_heatmaps and 'heatmap_final' in inter:

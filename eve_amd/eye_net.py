@@ -51,15 +51,24 @@ EYE_POSE_KEY = 'eye_pose'                    # the pose form: camera_frame + one
 # what eye_pose_batch derives from the rows -- a batch holds the rows or these, never both
 FACE_LANDMARKS_KEY = 'face_landmarks'        # the face-landmark form: camera_frame + 2-D landmarks [B, T, L, 2 | 3] per frame ...
 FACE_RIG_KEY = 'face_rig'                    # ... + one row per sequence [B, 12 + 3L] (data.face_rig): the head pose is solved on the device
+FACE_LANDMARKS_RAW_KEY = 'face_landmarks_raw'  # in place of face_landmarks: pixels of the RAW frame, undistorted on the device by camera_lens' rows
 EYE_POSE_DERIVED = ('head_R', 'left_o', 'right_o', 'left_R', 'right_R', 'left_eye_warp', 'right_eye_warp', 'left_h', 'right_h', 'pose_valid')
 # what the face-landmark form adds to them
-FACE_DERIVED = ('head_t', 'face_reproj_rms')
+FACE_DERIVED = ('head_t', 'face_reproj_rms', 'face_inliers')
 
 
 def has_pose_form(batch):
     """True for a batch whose eye normalisation is derived on the device (eye_pose, or face_landmarks + face_rig): its result
     carries pose_valid."""
-    return EYE_POSE_KEY in batch or FACE_LANDMARKS_KEY in batch
+    return EYE_POSE_KEY in batch or FACE_LANDMARKS_KEY in batch or FACE_LANDMARKS_RAW_KEY in batch
+
+
+def face_landmarks_key(batch):
+    """face_landmarks or face_landmarks_raw, whichever the batch holds, or None; both raise ValueError."""
+    if FACE_LANDMARKS_KEY in batch and FACE_LANDMARKS_RAW_KEY in batch:
+        raise ValueError('a batch holds %s (pixels of the undistorted image) or %s (pixels of the raw frame), not both' % (
+            FACE_LANDMARKS_KEY, FACE_LANDMARKS_RAW_KEY))
+    return FACE_LANDMARKS_KEY if FACE_LANDMARKS_KEY in batch else FACE_LANDMARKS_RAW_KEY if FACE_LANDMARKS_RAW_KEY in batch else None
 
 
 def camera_frame_key(batch):
@@ -104,30 +113,37 @@ def eye_input(batch):
     face_landmarks, float32 [B, T, L, 2 | 3] = pixel (u, v[, w]) of the undistorted image, + face_rig, float32 [B, 12 + 3L] rows from
     data.face_rig, one per sequence (the face-landmark form: eve_face_pose_solve solves head_R and head_t on the device and
     the pose form's normalisation continues from them -- eye_pose_batch).  It is refused beside eye_pose, patches or a derived
-    key; half of the pair raises ValueError, a wrong dtype or shape TypeError.  All camera forms may carry camera_lens, float32 [B, T, 12] (data.camera_lens): one camera per frame,
+    key; half of the pair raises ValueError, a wrong dtype or shape TypeError.  face_landmarks_raw, same shape, stands in for
+    face_landmarks with pixels of the RAW frame (what a tracker fed the raw frame reports): it REQUIRES camera_lens, whose rows
+    undistort both the pixels and the points (ValueError without it, and with both landmark keys); face_landmarks + camera_lens
+    keeps meaning landmarks of the undistorted image.  All camera forms may carry camera_lens, float32 [B, T, 12] (data.camera_lens): one camera per frame,
     for both eyes.  In both, camera_frame may be replaced by ONE of camera_frame_bgr [B, T, IH, IW, 3 | 4], camera_frame_nv12 /
     camera_frame_i420 [B, T, IH*3/2, IW] or camera_frame_yuyv [B, T, IH, IW, 2] (EYE_FRAME_KEYS; two frame keys raise ValueError,
     odd sizes too): that tensor is then returned -- its shape[:2] and device are the batch's whatever the format.  camera_surface,
     uint8 [B, T, rows, pitch] or [B, T, frame_bytes], is one more such key: the frame as a decoder's surface lies in memory, read
     through EyeNet.camera_layout."""
-    if FACE_LANDMARKS_KEY in batch or FACE_RIG_KEY in batch:
-        if FACE_LANDMARKS_KEY not in batch or FACE_RIG_KEY not in batch:
+    lm_key = face_landmarks_key(batch)
+    if lm_key is not None or FACE_RIG_KEY in batch:
+        if lm_key is None or FACE_RIG_KEY not in batch:
             raise ValueError('the face-landmark form needs %s and %s: found only %s' % (
-                FACE_LANDMARKS_KEY, FACE_RIG_KEY, FACE_LANDMARKS_KEY if FACE_LANDMARKS_KEY in batch else FACE_RIG_KEY))
+                lm_key or FACE_LANDMARKS_KEY, FACE_RIG_KEY, lm_key or FACE_RIG_KEY))
         clash = [k_ for k_ in (EYE_POSE_KEY,) + EYE_PATCH_KEYS + EYE_POSE_DERIVED + FACE_DERIVED if k_ in batch]
         if clash:
             raise ValueError('%s + %s derive %s and stand in for %s and %s: found %s beside them' % (
-                FACE_LANDMARKS_KEY, FACE_RIG_KEY, ', '.join(EYE_POSE_DERIVED + FACE_DERIVED), EYE_POSE_KEY, ' / '.join(EYE_PATCH_KEYS),
+                lm_key, FACE_RIG_KEY, ', '.join(EYE_POSE_DERIVED + FACE_DERIVED), EYE_POSE_KEY, ' / '.join(EYE_PATCH_KEYS),
                 ', '.join(clash)))
         if camera_frame_key(batch) is None:
-            raise ValueError('%s goes with camera_frame: the patches are cut from it' % FACE_LANDMARKS_KEY)
+            raise ValueError('%s goes with camera_frame: the patches are cut from it' % lm_key)
+        if lm_key == FACE_LANDMARKS_RAW_KEY and EYE_LENS_KEY not in batch:
+            raise ValueError('%s holds pixels of the raw frame and needs %s, whose rows undistort both the pixels and the points '
+                             '(landmarks of an undistorted image go in as %s)' % (lm_key, EYE_LENS_KEY, FACE_LANDMARKS_KEY))
         frames = _camera_frame(batch)
-        lm, rig = batch[FACE_LANDMARKS_KEY], batch[FACE_RIG_KEY]
+        lm, rig = batch[lm_key], batch[FACE_RIG_KEY]
         B, T = frames.shape[:2]
         if (not torch.is_tensor(lm) or lm.dtype != torch.float32 or lm.dim() != 4 or tuple(lm.shape[:2]) != (B, T)
                 or not 4 <= lm.shape[2] <= 68 or lm.shape[3] not in (2, 3)):
             raise TypeError('%s must be float32 %s with 4 <= L <= 68, got %s %s' % (
-                FACE_LANDMARKS_KEY, (B, T, 'L', '2 | 3'), getattr(lm, 'dtype', type(lm)), tuple(getattr(lm, 'shape', ()))))
+                lm_key, (B, T, 'L', '2 | 3'), getattr(lm, 'dtype', type(lm)), tuple(getattr(lm, 'shape', ()))))
         if not torch.is_tensor(rig) or rig.dtype != torch.float32 or tuple(rig.shape) != (B, 12 + 3 * lm.shape[2]):
             raise TypeError('%s must be float32 %s (one row per sequence), got %s %s' % (
                 FACE_RIG_KEY, (B, 12 + 3 * lm.shape[2]), getattr(rig, 'dtype', type(rig)), tuple(getattr(rig, 'shape', ()))))
@@ -172,19 +188,30 @@ def eye_input(batch):
     return frames
 
 
-def _face_landmark_batch(batch, config, face_state, reset, lengths):
+def _face_landmark_batch(batch, config, face_state, reset, lengths, huber_px=None):
     """eye_pose_batch for camera_frame + face_landmarks + face_rig: ONE eve_face_pose_solve launch (every sequence one wavefront,
     every frame warm-started from the one before, frame 0 from face_state where that holds a pose) and ONE
-    eve_eye_pose_normalize_rt launch that continues from the float32 head_R / head_t just written."""
+    eve_eye_pose_normalize_rt launch that continues from the float32 head_R / head_t just written.  With face_landmarks_raw
+    (camera_lens' rows undistort the points inside the launch) or huber_px (a Huber loss) the launch is eve_face_pose_solve_ex
+    and the copy gains face_inliers, uint8 [B, T]."""
     from . import data
     frames = eye_input(batch)
     B, T = frames.shape[:2]
     k = default_kernels()
     rig = batch[FACE_RIG_KEY].contiguous()
-    head_R, head_t, rms, solved = k.face_pose_solve(batch[FACE_LANDMARKS_KEY].contiguous(), rig, lengths, face_state, reset)
+    lm_key = face_landmarks_key(batch)
+    huber_px = data.check_huber_px(huber_px, 'face_huber_px')
+    inliers = None
+    if lm_key == FACE_LANDMARKS_RAW_KEY or huber_px is not None:
+        lens = batch[EYE_LENS_KEY].contiguous() if lm_key == FACE_LANDMARKS_RAW_KEY else None
+        head_R, head_t, rms, solved, inliers = k.face_pose_solve_ex(batch[lm_key].contiguous(), rig, lens, huber_px, lengths, face_state, reset)
+    else:
+        head_R, head_t, rms, solved = k.face_pose_solve(batch[lm_key].contiguous(), rig, lengths, face_state, reset)
     o, R, warp, h, valid = k.eye_pose_normalize_rt(rig, head_R, head_t, solved, data.eye_patch_hw(config))
-    d = {k_: v for k_, v in batch.items() if k_ not in (FACE_LANDMARKS_KEY, FACE_RIG_KEY)}
+    d = {k_: v for k_, v in batch.items() if k_ not in (lm_key, FACE_RIG_KEY)}
     d['head_R'], d['head_t'], d['face_reproj_rms'] = head_R, head_t, rms
+    if inliers is not None:
+        d['face_inliers'] = inliers
     for e, side in enumerate(('left', 'right')):
         d[side + '_o'] = o[e].view(B, T, 3)
         d[side + '_R'] = R[e].view(B, T, 3, 3)
@@ -194,7 +221,7 @@ def _face_landmark_batch(batch, config, face_state, reset, lengths):
     return d
 
 
-def eye_pose_batch(batch, config=None, face_state=None, reset=None, lengths=None):
+def eye_pose_batch(batch, config=None, face_state=None, reset=None, lengths=None, huber_px=None):
     """The pose form turned into the warp form: a batch without eye_pose comes back as it is; one with it is checked (eye_input)
     and copied, and in the copy eye_pose is replaced by what ONE eve_eye_pose_normalize launch derives from the rows for the
     config's eyes_size: head_R [B, T, 3, 3], <side>_o [B, T, 3], <side>_R [B, T, 3, 3], <side>_eye_warp [B, T, 3, 3] (inv(W): what
@@ -206,9 +233,12 @@ def eye_pose_batch(batch, config=None, face_state=None, reset=None, lengths=None
     pose solved on the device first (_face_landmark_batch): the copy additionally gains head_t [B, T, 3] and face_reproj_rms
     [B, T] (pixels), and pose_valid is False for both eyes of a frame with no solution.  face_state: None (every sequence starts
     cold) or the float64 [B, 13] carried pose of an EVEStream, updated in place; reset, lengths: None or int32 [B] device tensors
-    (flagged sequences start cold; frames past a sequence's count are not solved).  The three are read by this form only."""
-    if FACE_LANDMARKS_KEY in batch or FACE_RIG_KEY in batch:
-        return _face_landmark_batch(batch, config, face_state, reset, lengths)
+    (flagged sequences start cold; frames past a sequence's count are not solved).  The three are read by this form only.
+    face_landmarks_raw in place of face_landmarks holds pixels of the RAW frame and needs camera_lens, whose rows undistort the
+    points inside the solve's launch; huber_px (EyeNet.face_huber_px: None or k > 0 pixels) gives the solve a Huber loss.  With
+    either the copy gains face_inliers, uint8 [B, T] (include/eve_hip.h eve_face_pose_solve_ex)."""
+    if face_landmarks_key(batch) is not None or FACE_RIG_KEY in batch:
+        return _face_landmark_batch(batch, config, face_state, reset, lengths, huber_px)
     if EYE_POSE_KEY not in batch:
         return batch
     from . import data
@@ -472,7 +502,7 @@ class EyeNet(nn.Module):
         configuration takes the per-layer path.  Also returns the predictions (detached) under the forward_sequence keys."""
         from . import losses
         config = config if config is not None else self.config
-        batch = eye_pose_batch(batch, self.config)
+        batch = eye_pose_batch(batch, self.config, huber_px=self.face_huber_px)
         P = self._get_packs()
         feats, B, T = self._sequence_features(batch, P)
         self.last_tail_path = 'node' if self._tail_loss_node_ok(batch, T, feats) else 'layers'
@@ -530,6 +560,10 @@ class EyeNet(nn.Module):
     # How camera_surface batches lie in memory: a data.SurfaceLayout (format, visible size, pitch, coded rows, crop origin, plane
     # offsets).  A camera_surface batch without it raises ValueError.
     camera_layout = None
+    # The face-landmark forms' Huber loss: None, or k > 0 in pixels (3 suits 1 px of landmark noise) -- landmarks further than k from
+    # their reprojection are down-weighted by k / distance, so a few confidently wrong ones (a hand, hair) no longer tilt the head.
+    # Anything else raises ValueError where a face-landmark batch is used.  An EVEStream captures one graph per value.
+    face_huber_px = None
 
     def forward_sequence(self, batch, initial_states=None):
         """batch: {left,right}_eye_patch [B, T, 3, H, W] float (or uint8 [B, T, H, W, C] decoded frames), {left,right}_h [B, T, 2].
@@ -550,7 +584,7 @@ class EyeNet(nn.Module):
         Returns the B x T x ... tensors eve.py:174-182 would stack: <side>_g_initial [B,T,2],
         <side>_pupil_size [B,T], <side>_eye_rnn_states_<i> [B,T,H] per cell ((h, c) pair of them for LSTM).
         initial_states: {side: h [B,H]} or {side: [per-cell h | (h, c) | None]}."""
-        batch = eye_pose_batch(batch, self.config)
+        batch = eye_pose_batch(batch, self.config, huber_px=self.face_huber_px)
         P = self._get_packs()
         feats, B, T = self._sequence_features(batch, P)
         return self._sequence_tail(feats, batch, B, T, initial_states, P)
@@ -738,7 +772,7 @@ class EyeNet(nn.Module):
         counts as lengths, and gaze and pupil are gathered back through inv; entries at unusable eyes are unspecified.
         Returns the forward_sequence prediction keys (<side>_g_initial, <side>_pupil_size)."""
         k = default_kernels()
-        batch = eye_pose_batch(batch, self.config)
+        batch = eye_pose_batch(batch, self.config, huber_px=self.face_huber_px)
         P = self._get_packs()
         feats, B, T = self._sequence_features(batch, P)
         head_pose = None

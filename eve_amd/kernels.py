@@ -857,6 +857,59 @@ class HipKernels(object):
                                               self._p(head_R), self._p(head_t), self._p(rms), self._p(valid), self._stream()))
         return head_R, head_t, rms, valid
 
+    def face_pose_solve_ex(self, landmarks, rig, lens=None, huber_px=None, lengths=None, state=None, reset=None):
+        """face_pose_solve with landmarks of the RAW frame and / or a Huber loss: lens None, or float32 [S, T, 12] rows (data.camera_lens),
+        one per frame -- every landmark is undistorted on the device first, an unusable point is dropped; huber_px None, or k > 0
+        pixels.  -> (head_R, head_t, reproj_rms, valid as face_pose_solve, inliers uint8 [S,T]: the points within k pixels, the used
+        points without the loss, 0 on an invalid frame).  Neither given: face_pose_solve's bits (include/eve_hip.h
+        eve_face_pose_solve_ex)."""
+        ok = lambda t, dtype: torch.is_tensor(t) and t.dtype == dtype
+        if not ok(landmarks, torch.float32) or landmarks.dim() != 4 or landmarks.shape[3] not in (2, 3):
+            raise TypeError('face_pose_solve_ex: landmarks must be float32 [S, T, L, 2 | 3], got %s %s' % (
+                getattr(landmarks, 'dtype', type(landmarks)), tuple(getattr(landmarks, 'shape', ()))))
+        S, T, L, C = landmarks.shape
+        if not ok(rig, torch.float32) or tuple(rig.shape) != (S, 12 + 3 * L):
+            raise TypeError('face_pose_solve_ex: rig must be float32 [%d, %d], got %s %s' % (
+                S, 12 + 3 * L, getattr(rig, 'dtype', type(rig)), tuple(getattr(rig, 'shape', ()))))
+        for name, t, dtype, shape in (('lens', lens, torch.float32, (S, T, 12)), ('lengths', lengths, torch.int32, (S,)),
+                                      ('state', state, torch.float64, (S, 13)), ('reset', reset, torch.int32, (S,))):
+            if t is not None and (not ok(t, dtype) or tuple(t.shape) != shape):
+                raise TypeError('face_pose_solve_ex: %s must be %s %s, got %s %s' % (
+                    name, str(dtype).replace('torch.', ''), list(shape), getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ()))))
+        if huber_px is not None and not (isinstance(huber_px, (int, float)) and not isinstance(huber_px, bool) and 0 < huber_px < float('inf')):
+            raise ValueError('face_pose_solve_ex: huber_px must be None or a finite number > 0, got %r' % (huber_px,))
+        given = [t for t in (landmarks, rig, lens, lengths, state, reset) if t is not None]
+        if not all(t.is_contiguous() for t in given):
+            raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        new = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=landmarks.device)
+        head_R, head_t, rms, valid = new(S, T, 3, 3), new(S, T, 3), new(S, T), new(S, T, dtype=torch.uint8)
+        inliers = new(S, T, dtype=torch.uint8)
+        opt = lambda t: None if t is None else self._p(t)
+        self._ck(self.lib.eve_face_pose_solve_ex(S, T, L, C, self._p(landmarks), self._p(rig), opt(lens), 0.0 if huber_px is None else float(huber_px),
+                                                 opt(lengths), opt(state), opt(reset), self._p(head_R), self._p(head_t), self._p(rms),
+                                                 self._p(valid), self._p(inliers), self._stream()))
+        return head_R, head_t, rms, valid, inliers
+
+    def undistort_points(self, points, lens):
+        """Raw pixels -> normalised points of the undistorted image: points float32 [N, 2], lens float32 [N, 12] (one row per
+        point) or [1, 12] (one for all) -> (xy float64 [N, 2], ok uint8 [N]); ok = 0 and xy = 0 for a point the iteration cannot
+        invert, a point or a lens row that is not finite (include/eve_hip.h eve_undistort_points)."""
+        ok = lambda t: torch.is_tensor(t) and t.dtype == torch.float32
+        if not ok(points) or points.dim() != 2 or points.shape[1] != 2 or points.shape[0] < 1:
+            raise TypeError('undistort_points: points must be float32 [N, 2] with N >= 1, got %s %s' % (
+                getattr(points, 'dtype', type(points)), tuple(getattr(points, 'shape', ()))))
+        N = points.shape[0]
+        if not ok(lens) or tuple(lens.shape) not in ((N, 12), (1, 12)):
+            raise TypeError('undistort_points: lens must be float32 [%d, 12] or [1, 12], got %s %s' % (
+                N, getattr(lens, 'dtype', type(lens)), tuple(getattr(lens, 'shape', ()))))
+        if not (points.is_contiguous() and lens.is_contiguous()):
+            raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        xy = torch.empty((N, 2), dtype=torch.float64, device=points.device)
+        good = torch.empty((N,), dtype=torch.uint8, device=points.device)
+        stride = 12 if lens.shape[0] == N and N > 1 else 0
+        self._ck(self.lib.eve_undistort_points(N, self._p(points), self._p(lens), stride, self._p(xy), self._p(good), self._stream()))
+        return xy, good
+
     # ------------------------------------------------------------------ gaze geometry / heat-maps / soft-argmax
     def _flat32(self, t, shape, what):
         t = t.contiguous()

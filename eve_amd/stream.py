@@ -37,7 +37,7 @@ kernel) need invalidate(), as the modules need invalidate_packs().
 import numpy as np
 import torch
 
-from .eye_net import eye_input, has_pose_form
+from .eye_net import eye_input, face_landmarks_key, has_pose_form
 from .kernels import default_kernels
 
 _WARMUP_STREAMS = {}
@@ -211,7 +211,7 @@ class EVEStream(object):
     def _run(self, chunk, return_heatmaps, ragged=False, eye_mask=None, masked=False, render=None):
         # render: None or a _render_plan; the keyword reaches _predict_sequence only then, so a step without it calls what it always did
         extra = {} if render is None else {'render': self._render_hook(render, ragged, masked)}
-        if 'face_landmarks' in chunk:            # the face-landmark form: the carried head pose goes along
+        if face_landmarks_key(chunk) is not None:      # the face-landmark form: the carried head pose goes along
             return self.model._predict_sequence(chunk, self._eye, self._ref, reset=self._flags, return_heatmaps=return_heatmaps,
                                                 lengths=self._lengths if ragged else None, masked=masked, eye_mask=eye_mask,
                                                 pose_gate=self._pose_gate if masked else None, face_state=self._face_pose, **extra)
@@ -393,8 +393,20 @@ class EVEStream(object):
         pose_valid as above (False for both eyes of a frame without a solution: a NaN, fewer than 4 weighted points, no
         convergence), head_t [B, Tc, 3] and face_reproj_rms [B, Tc] (pixels).  lengths, eye_mask, skip_invalid_pose, camera_lens and
         the pixel-format keys combine with it; frames past lengths[b] are not solved and leave the carried pose alone.  A split
-        of a clip into chunks gives the poses of one pass over the clip, bit for bit.  Not offered: landmarks of the distorted
-        frame (undistort the L points; camera_lens applies to the pixels), outlier rejection beyond the weights, per-frame rigs.
+        of a clip into chunks gives the poses of one pass over the clip, bit for bit.
+        A tracker fed the RAW frame of a camera with lens distortion reports raw pixels: pass them as face_landmarks_raw (same
+        shape) in place of face_landmarks.  It requires camera_lens, whose rows then undistort both the pixels (inside the warp)
+        and the points (inside the solve's launch, by Newton's method: a few 1e-16 in normalised coordinates; a point it cannot
+        invert is dropped); both landmark keys together, or the raw key without camera_lens, raise ValueError; face_landmarks +
+        camera_lens keeps meaning landmarks of the undistorted image.  model.eye_net.face_huber_px = k (None, or pixels > 0;
+        anything else raises ValueError) gives the solve a Huber loss: landmarks further than k from their reprojection are
+        down-weighted, so a few that are confidently wrong (a hand, hair across the face) no longer tilt the head -- at L = 68
+        with 7 of them moved 30..80 px, 0.35 degrees median where the plain solve has 3.1.  A frame that ends with fewer than 4
+        landmarks within k is invalid.  With either, the launch is eve_face_pose_solve_ex and the result gains face_inliers,
+        uint8 [B, Tc]: the landmarks within k (the used ones without the loss), 0 where invalid; face_reproj_rms stays the rms
+        over all used landmarks.  The value is part of the graph's key: changing the attribute captures a new graph.  Not
+        promised: six landmarks with an outlier among them.  Not offered: RANSAC, per-frame rigs, fisheye / thin-prism / tilt
+        lens models.
 
         screen_frame is float [B, Tc, 3, H, W] at the configured screen size, uint8 [B, Tc, H, W, 3] at that size, or a live
         capture as it comes off the desktop: uint8 [B, Tc, IH, IW, 3 | 4] at any resolution from the screen size up to 16 843 009
@@ -544,11 +556,16 @@ class EVEStream(object):
 
     def _graph_key(self, chunk, return_heatmaps, ragged=False, masked=False, render=None):
         """What a captured graph is good for: the step's mode, both YUV matrices, both surface layouts (by value), the overlay
-        (render: None or a _render_plan -- its OverlaySpec by value) and every chunk tensor's key, shape and dtype."""
+        (render: None or a _render_plan -- its OverlaySpec by value), with a face-landmark form eye_net.face_huber_px (a launch
+        argument, so baked in), and every chunk tensor's key, shape and dtype -- which of the two landmark keys among them."""
         ref = self.model.refine_net
         spec = None if render is None else render['spec'].key()
         layouts = (self.model.eye_net.camera_layout, None if ref is None else ref.screen_layout)
-        return (return_heatmaps, ragged, masked, self.model.eye_net.yuv_matrix, None if ref is None else ref.yuv_matrix, spec, layouts) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
+        huber = None
+        if face_landmarks_key(chunk) is not None:      # (checked here too: a value that is refused never becomes a key)
+            from .data import check_huber_px
+            huber = check_huber_px(self.model.eye_net.face_huber_px, 'face_huber_px')
+        return (return_heatmaps, ragged, masked, self.model.eye_net.yuv_matrix, None if ref is None else ref.yuv_matrix, spec, layouts, huber) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
 
     def _graph_for(self, chunk, return_heatmaps, ragged=False, masked=False, render=None):
         wk = self._weights_key()

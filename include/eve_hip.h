@@ -1040,12 +1040,61 @@ int eve_eye_pose_normalize_rt(long long N, int frames_per_row, const float* rows
  * keeps R orthogonal up to rounding (about 1e-16 per accepted step); it is not re-orthonormalised.  Each frame of a sequence
  * depends on the one before: the launch takes T times one frame's latency, S sequences side by side.  Kernel name
  * face_pose_solve_kernel.  Refused without a launch: S < 1, T < 1, S * T >= 2^31, L outside 4..68, landmark_cols other than 2 or 3,
- * a null landmarks, rig or output pointer.  Not offered: landmarks of a distorted image, RANSAC or any outlier rejection beyond the
- * weights, an rvec, gradients, per-frame camera matrices; a planar model runs, but which of its two minima is found is not
- * promised.  (Additive: ABI v10.)                                                                                              */
+ * a null landmarks, rig or output pointer.  Landmarks of a distorted image and a loss against outliers: eve_face_pose_solve_ex
+ * below.  Not offered: RANSAC, an rvec, gradients, per-frame camera matrices; a planar model runs, but which of its two minima is
+ * found is not promised.  (Additive: ABI v10.)                                                                                 */
 int eve_face_pose_solve(long long S, int T, int L, int landmark_cols, const float* landmarks, const float* rig,
                         const int* lengths /* may be NULL */, double* state /* may be NULL */, const int* reset /* may be NULL */,
                         float* head_R, float* head_t, float* reproj_rms, uint8_t* valid, eve_stream_t stream);
+/* The raw pixels of a camera with lens distortion -> the normalised points (x, y) of the undistorted image, one thread per point:
+ * what cv2.undistortPoints does on the host, by Newton's method instead of five fixed-point passes.
+ *   points [N][2] float: raw pixel (u, v).   lens: float rows (fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6) as for
+ *   eve_eye_warp_lens_u8_to_nchw; lens_stride 12: [N][12], one row per point; 0: [1][12], one row for all.
+ *   xy [N][2] double: (x, y); the pixel of the undistorted image is (fx*x + cx, fy*y + cy).   ok [N] uint8.
+ * Contract: float64, every operation rounded on its own (no contraction), only + - * /, in exactly this association
+ * (tests/face_pose_raw_ref.py restates it):
+ *   xd = (u - cx) / fx, yd = (v - cy) / fy.  A row whose eight coefficients are all +-0: x = xd, y = yd, no iteration (the warp
+ *   kernels' rule).  Else from (x, y) = (xd, yd), at most 12 times:
+ *     xx = x*x, yy = y*y, xy = x*y, r2 = xx + yy,
+ *     N = ((k3*r2 + k2)*r2 + k1)*r2 + 1.0, D = ((k6*r2 + k5)*r2 + k4)*r2 + 1.0, rad = N / D, a = xy + xy,
+ *     gx = (x*rad + p1*a) + p2*(r2 + (xx + xx)), gy = (y*rad + p1*(r2 + (yy + yy))) + p2*a       -- the warp kernels' forward model --
+ *     N' = ((3.0*k3)*r2 + 2.0*k2)*r2 + k1, D' = ((3.0*k6)*r2 + 2.0*k5)*r2 + k4, rp = (N' - rad*D') / D, tw = rp + rp,
+ *     j00 = ((rad + xx*tw) + 2.0*(p1*y)) + 6.0*(p2*x), j01 = (xy*tw + 2.0*(p1*x)) + 2.0*(p2*y),
+ *     j11 = ((rad + yy*tw) + 6.0*(p1*y)) + 2.0*(p2*x)                                            -- the Jacobian, j10 = j01 --
+ *     ex = gx - xd, ey = gy - yd, det = j00*j11 - j01*j01, dx = (j11*ex - j01*ey) / det, dy = (j00*ey - j01*ex) / det;
+ *     dx or dy not finite: unusable.  x = x - dx, y = y - dy; max(|dx|, |dy|) <= 4e-15 * max(1.0, |x|, |y|): done.
+ *   Twelve steps without that: unusable.  D once more at the result (xx, yy, r2, D as above); not D > 0: unusable.
+ * ok = 0 and xy = (0, 0): an unusable point, a point that is not finite, a lens row with an entry that is not finite or fx <= 0 or
+ * fy <= 0.  Beyond the fold-back radius of a barrel polynomial the forward model is not injective and which pre-image is found is
+ * not promised -- the pixel warp's unguarded case.  Measured on four lenses over +-0.64 x +-0.36: 5 steps at most, 4.4e-16 from
+ * the truth.  Kernel name undistort_points_kernel.  Refused without a launch: N < 1, a null pointer, lens_stride other than 0 or 12.
+ * Not offered: fisheye, thin-prism and tilt models.  (Additive: ABI v10.)                                                        */
+int eve_undistort_points(long long N, const float* points, const float* lens, long long lens_stride, double* xy, uint8_t* ok,
+                         eve_stream_t stream);
+/* eve_face_pose_solve with two optional additions: landmarks of the RAW frame of a camera with lens distortion, and a Huber loss
+ * against landmarks that are confidently wrong.  Arguments, outputs, the carried state and every refusal as there, plus
+ *   lens      NULL, or [S*T][12] float, one row per frame as above: landmarks are then raw pixels.  When a frame's landmarks are
+ *             loaded each is undistorted by the iteration above and the solve continues from (x, y) directly; the rig's fx .. cy
+ *             keep their roles (the pix column, the normalisation that follows).  An unusable point is dropped -- w = 0, x = y =
+ *             0.0, not used -- and a row that is not usable makes the frame invalid, like a landmark that is not finite.  `used`,
+ *             the count of at least 4 and sw follow from the points that survived.
+ *   huber_px  k; <= 0: no loss.  k > 0 (pixels): per used point, from ex, ey, Jx, Jy of eval,
+ *               p2 = (fx*ex)*(fx*ex) + (fy*ey)*(fy*ey), r = sqrt(p2), inlier iff not r > k, s = 1.0 for an inlier, else k / r, ws = w*s,
+ *               A_ij = ws*(Jx_i*Jx_j + Jy_i*Jy_j), g_i = ws*(Jx_i*ex + Jy_i*ey), cost = w*(inlier ? p2 : k*((r + r) - k)) -- the
+ *               Huber cost in pixels^2; the accept test only compares costs -- pix = w*p2, and a 30th sum of 1.0 per inlier.
+ *             The iteration, the damping, small, the cap of 32 accepted steps and the observability Cholesky (on the weighted A)
+ *             are unchanged; a frame that converges with fewer than 4 inliers is invalid.  Without the loss the 29 sums stand.
+ *   inliers   [S][T] uint8: the 30th sum with the loss, the number of used points without, 0 on an invalid frame.
+ * reproj_rms keeps its meaning: sqrt(pix / sw) over all used points, weighted by w.  lens NULL and huber_px <= 0 give
+ * eve_face_pose_solve's bits; a lens row with zero coefficients and the rig's intrinsics too.  tests/face_pose_raw_ref.py restates
+ * the contract.  Measured (k = 3, L = 68, 1 px noise, 7 / 14 landmarks moved 30..80 px, 40 cases each): rotation error 0.35 / 0.39
+ * degrees median and 1.17 / 1.05 at most, where the plain solve has 3.06 / 4.02 and 10.4 / 10.8.  Not promised: L = 6 with an
+ * outlier.  Kernel name face_pose_solve_ex_kernel.  Refused without a launch, beyond the plain refusals: a null inliers, a NaN
+ * huber_px.  Not offered: RANSAC, a gradient, per-frame rigs.  (Additive: ABI v10.)                                               */
+int eve_face_pose_solve_ex(long long S, int T, int L, int landmark_cols, const float* landmarks, const float* rig,
+                           const float* lens /* may be NULL */, double huber_px, const int* lengths /* may be NULL */,
+                           double* state /* may be NULL */, const int* reset /* may be NULL */, float* head_R, float* head_t,
+                           float* reproj_rms, uint8_t* valid, uint8_t* inliers, eve_stream_t stream);
 
 #ifdef __cplusplus
 }

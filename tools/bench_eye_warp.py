@@ -39,6 +39,10 @@ part 2 a stream `face` feeds camera_frame + face_landmarks [B, Tc, 68, 3] + face
 The eye_pose step of ANOTHER checkout (the parent commit's) is measured by running that checkout's own `--pose --shapes 32x2` in
 alternating rounds with this one, process by process; this file only measures the tree it lies in.
 
+--landmarks --raw [--huber K]: eve_face_pose_solve_ex at 32 x 2 x 68 next to the plain launch in the same process, route by route
+in alternating rounds (raw_solve_launches), and in part 2 a stream `raw` that feeds camera_frame + face_landmarks_raw + face_rig +
+camera_lens (with face_huber_px = K) next to `face`; with --lens also `face_lens`, the face stream with the same camera_lens rows.
+
 --surface: nothing of the above; instead the surface launches (eve_eye_warp_surface_to_nchw / _to_stem) on N frames of the given
 size as a decoder leaves them -- NV12 in rows of 2048 bytes and 1088 coded rows, then P010 in rows of 4096 -- three routes
 interleaved in one process:
@@ -163,6 +167,64 @@ def solve_launches(args, IH, IW):
             rows.append(res)
             print(json.dumps(res), flush=True)
     return rows
+
+
+def raw_face_sequences(B, Tc, L, IH, IW, seed):
+    """face_sequences seen through a raw camera: lens_rows' mild rational model with the rig's own intrinsics -> numpy (raw landmarks
+    [B, Tc, L, 3], rig, lens [B, Tc, 12], the undistorted landmarks)."""
+    sys.path.insert(0, os.path.join(REPO, 'tests'))
+    import face_pose_raw_ref as rr
+    lm, rig = face_sequences(B, Tc, L, IH, IW, seed)
+    f = 1400.0 * IW / 1920.0
+    row = np.array([f, f, IW / 2, IH / 2, 0.9, 0.1, 2e-3, 1e-3, 0.01, 1.1, 0.15, 0.02], dtype=np.float32)
+    return rr.distort_landmarks(lm, row), rig, np.broadcast_to(row, (B, Tc, 12)).copy(), lm
+
+
+def raw_solve_launches(args, IH, IW):
+    """--landmarks --raw: eve_face_pose_solve_ex at 32 x 2 x 68 into preallocated outputs, next to the plain launch on the same
+    heads' undistorted landmarks in the same process, the routes interleaved round by round: `plain` (eve_face_pose_solve), `ex_off`
+    (the new entry, no lens, no loss), `ex_lens` (raw landmarks + lens rows), and with --huber K `ex_huber` and `ex_lens_huber`;
+    every one cold (no carried state) and warm (a carried state that holds the chunk's last pose) -> one dict."""
+    import ctypes
+    k = default_kernels()
+    S_, T_, L = 32, 2, 68
+    raw_np, rig_np, lens_np, lm_np = raw_face_sequences(S_, T_, L, IH, IW, seed=L)
+    raw, rig, lens, lm = (torch.from_numpy(a).cuda() for a in (raw_np, rig_np, lens_np, lm_np))
+    outs = [torch.empty((S_, T_, n), device='cuda') for n in (9, 3, 1)] + [torch.empty((S_, T_), dtype=torch.uint8, device='cuda') for _ in range(2)]
+    ptrs = [ctypes.c_void_p(t.data_ptr()) for t in outs]
+    p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+    stream = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    states = {}
+
+    def plain(st=None):
+        assert k.lib.eve_face_pose_solve(S_, T_, L, 3, p(lm), p(rig), None, p(st), None, *ptrs[:4], stream()) == 0, k.lib.eve_last_error()
+
+    def ex(pts, rows, huber, st=None):
+        assert k.lib.eve_face_pose_solve_ex(S_, T_, L, 3, p(pts), p(rig), p(rows), huber, None, p(st), None, *ptrs, stream()) == 0, k.lib.eve_last_error()
+    routes = {'plain': plain, 'ex_off': lambda st=None: ex(lm, None, 0.0, st), 'ex_lens': lambda st=None: ex(raw, lens, 0.0, st)}
+    if args.huber:
+        routes['ex_huber'] = lambda st=None: ex(lm, None, args.huber, st)
+        routes['ex_lens_huber'] = lambda st=None: ex(raw, lens, args.huber, st)
+    res = {'S': S_, 'T': T_, 'L': L, 'iters': args.iters, 'rounds': args.rounds, 'huber_px': args.huber}
+    for name, fn in routes.items():
+        states[name] = torch.zeros((S_, 13), dtype=torch.float64, device='cuda')
+        for _ in range(5):
+            fn()
+            fn(states[name])
+        torch.cuda.synchronize()
+        res[name + '_frames_solved'] = round(float(outs[3].float().mean()), 4)
+        if name != 'plain':
+            res[name + '_inliers_min_max'] = [int(outs[4].min()), int(outs[4].max())]
+    times = {(name, mode): [] for name in routes for mode in ('cold', 'warm')}
+    for _ in range(args.rounds):
+        for name, fn in routes.items():
+            times[name, 'cold'].append(device_ms(fn, args.iters))
+            times[name, 'warm'].append(device_ms(lambda: fn(states[name]), args.iters))
+    for (name, mode), t in times.items():
+        res['%s_%s_us' % (name, mode)] = round(1e3 * median(t), 2)
+        res['%s_%s_us_min_max' % (name, mode)] = [round(1e3 * min(t), 2), round(1e3 * max(t), 2)]
+    print(json.dumps(res), flush=True)
+    return res
 
 
 def format_frames(fmt, lead, IH, IW, gen=None, device='cuda'):
@@ -387,6 +449,21 @@ def launches(args, IH, IW):
     return res
 
 
+class _HuberStream:
+    """An EVEStream whose steps run with model.eye_net.face_huber_px = k (the graph's key holds the value, so the other streams of
+    the same model keep theirs)."""
+
+    def __init__(self, stream, model, k):
+        self.stream, self.model, self.k = stream, model, k
+
+    def step(self, chunk):
+        self.model.eye_net.face_huber_px = self.k
+        try:
+            return self.stream.step(chunk)
+        finally:
+            self.model.eye_net.face_huber_px = None
+
+
 def stream_steps(args, IH, IW):
     cfg = eve_amd.reset_standalone_config()
     cfg.import_json(os.path.join(REPO, 'configs', 'refine_net.json'))
@@ -419,6 +496,13 @@ def stream_steps(args, IH, IW):
             lm, rig = face_sequences(B, Tc, 68, IH, IW, seed=B)
             streams['face'] = (eve_amd.EVEStream(model, B), dict({k_: v for k_, v in cam.items() if k_ not in EYE_POSE_DERIVED},
                                                                  face_landmarks=torch.from_numpy(lm).cuda(), face_rig=torch.from_numpy(rig).cuda()))
+        if args.landmarks and args.raw:
+            raw_np, rig_np, lens_np, _ = raw_face_sequences(B, Tc, 68, IH, IW, seed=B)
+            streams['raw'] = (_HuberStream(eve_amd.EVEStream(model, B), model, args.huber),
+                              dict({k_: v for k_, v in cam.items() if k_ not in EYE_POSE_DERIVED}, face_landmarks_raw=torch.from_numpy(raw_np).cuda(),
+                                   face_rig=torch.from_numpy(rig_np).cuda(), camera_lens=torch.from_numpy(lens_np).cuda()))
+            if args.lens:                        # what `raw` stands beside: the same pixels' undistortion, landmarks of the undistorted image
+                streams['face_lens'] = (eve_amd.EVEStream(model, B), dict(streams['face'][1], camera_lens=torch.from_numpy(lens_np).cuda()))
         if args.format:
             fmt_chunk = {k_: v for k_, v in cam.items() if k_ != 'camera_frame'}
             fmt_chunk['camera_frame_' + args.format] = format_frames(args.format, (B, Tc), IH, IW, gen=g)
@@ -444,6 +528,14 @@ def stream_steps(args, IH, IW):
         if args.landmarks:
             res['face_minus_pose_ms'] = round(res['face_step_ms'] - res['pose_step_ms'], 4)
             res['face_pose_valid'] = round(float(streams['face'][0].step(streams['face'][1])['pose_valid'].float().mean()), 4)
+        if args.landmarks and args.raw:
+            res['raw_huber_px'] = args.huber
+            res['raw_minus_face_ms'] = round(res['raw_step_ms'] - res['face_step_ms'], 4)
+            if args.lens:
+                res['raw_minus_face_lens_ms'] = round(res['raw_step_ms'] - res['face_lens_step_ms'], 4)
+            last = streams['raw'][0].step(streams['raw'][1])
+            res['raw_pose_valid'] = round(float(last['pose_valid'].float().mean()), 4)
+            res['raw_inliers_min_max'] = [int(last['face_inliers'].min()), int(last['face_inliers'].max())]
         if args.format:
             res['fmt_minus_camera_ms'] = round(res['fmt_step_ms'] - res['camera_step_ms'], 4)
             res['fmt_frame_MB_copied'] = round(fmt_chunk['camera_frame_' + args.format].numel() / 1e6, 1)
@@ -469,6 +561,9 @@ def main():
                     help='also time the launches and an EVEStream step on frames in this layout, and convert-then-warp beside them')
     ap.add_argument('--landmarks', action='store_true',
                     help='also time eve_face_pose_solve and an EVEStream step with face_landmarks + face_rig (implies --pose)')
+    ap.add_argument('--raw', action='store_true',
+                    help='with --landmarks: also time eve_face_pose_solve_ex next to the plain launch and an EVEStream step with face_landmarks_raw + camera_lens')
+    ap.add_argument('--huber', type=float, default=None, metavar='K', help='with --raw: the Huber loss of K pixels (face_huber_px) in those')
     ap.add_argument('--surface', action='store_true',
                     help='time the surface launches and an EVEStream step with camera_surface + screen_surface instead (NV12 / P010 in 2048 x 1088)')
     ap.add_argument('--markdown', default=None, help='also write the tables to this file')
@@ -484,6 +579,7 @@ def main():
     args.pose = args.pose or args.landmarks
     with torch.no_grad():
         solves = solve_launches(args, IH, IW) if args.landmarks else []
+        raw_solves = raw_solve_launches(args, IH, IW) if args.landmarks and args.raw else None
         one = launches(args, IH, IW)
         print(json.dumps(one), flush=True)
         rows = stream_steps(args, IH, IW) if args.shapes else []
@@ -538,6 +634,20 @@ def main():
             lines.append('| %d x %d | %.4f | %.4f .. %.4f | %.4f | %.4f .. %.4f | %.4f |' % (
                 r['B'], r['Tc'], r['face_step_ms'], r['face_step_ms_min_max'][0], r['face_step_ms_min_max'][1], r['pose_step_ms'],
                 r['pose_step_ms_min_max'][0], r['pose_step_ms_min_max'][1], r['face_minus_pose_ms']))
+    if raw_solves:
+        r = raw_solves
+        lines += ['', '| launch, %d x %d, L = %d | cold us | min .. max | warm us | min .. max | frames solved |' % (r['S'], r['T'], r['L']), '|---|---|---|---|---|---|']
+        for name in ('plain', 'ex_off', 'ex_lens') + (('ex_huber', 'ex_lens_huber') if args.huber else ()):
+            lines.append('| %s | %.2f | %.2f .. %.2f | %.2f | %.2f .. %.2f | %.4f |' % (
+                name, r[name + '_cold_us'], r[name + '_cold_us_min_max'][0], r[name + '_cold_us_min_max'][1], r[name + '_warm_us'],
+                r[name + '_warm_us_min_max'][0], r[name + '_warm_us_min_max'][1], r[name + '_frames_solved']))
+    if rows and args.landmarks and args.raw:
+        lines += ['', '| B x Tc (%s) | raw step ms (huber %s) | min .. max | face step ms | min .. max | raw - face ms |' % (args.dtype, args.huber),
+                  '|---|---|---|---|---|---|']
+        for r in rows:
+            lines.append('| %d x %d | %.4f | %.4f .. %.4f | %.4f | %.4f .. %.4f | %.4f |' % (
+                r['B'], r['Tc'], r['raw_step_ms'], r['raw_step_ms_min_max'][0], r['raw_step_ms_min_max'][1], r['face_step_ms'],
+                r['face_step_ms_min_max'][0], r['face_step_ms_min_max'][1], r['raw_minus_face_ms']))
     table = '\n'.join(lines)
     print(table, flush=True)
     if args.markdown:
