@@ -76,6 +76,7 @@ template <> struct Mma<float> {
 #include "conv_3x3s.h"
 #include "wgrad_halo.h"
 #include "wgrad_wg8.h"
+#include "wgrad_wg8_t128.h"
 namespace eve {
 
 // =================================================================================================
@@ -849,6 +850,14 @@ static bool launch_wgrad_halo(const GatherParams& p, const void* x, const void* 
 // "mtN"; the bias flag is not part of it) and the shape as compile-time constants
 #define EVE_WGRAD_TR(T, WCO, WK, P2, MT) EVE_HNAME(T, "wgrad_tr_kernel<", ", " #WCO ", " #WK ", " #P2 ", mt" #MT ">"), ic<WCO>{}, ic<WK>{}, ic<P2>{}, ic<MT>{}
 
+// pixel floor of the 128 x 384 eight-wave tile (wgrad_wg8 = 1): the measured crossover against wgrad_tr_kernel on the layer-2 shape
+// (16 x 16 x 128 -> 128, back to back, us warm | cold: M = 49 152: 36.1 | 44 against 37.3 | 47; M = 65 536: 40.8 | 46 against
+// 38.9 | 47; M = 98 304: 58.5 | 67 against 43.0 | 52).  With wgrad_min_rows = 1 536 pixels per range, 65 536 pixels are 43 ranges x 3
+// K tiles = 129 workgroups, half the CUs: below that the one-per-CU grid is too empty and wgrad_tr_kernel's three-per-CU grid wins.
+// Layer 3's stride-2 shape (two channel tiles) crosses at ~36 000 pixels (30 720: 38.5 against 38.0, 40 960: 40.8 against 45.7) and
+// is served from the same floor.  profiles/r08_wgrad_wg8_tile128.md
+static constexpr uint32_t WGRAD_WG8_T128_MIN_M = 65536;
+
 template <typename T>
 static int launch_wgrad(const GatherParams& p, const void* x, const void* dy, const float* ss, int pro_act,
                         float* dw, hipStream_t s, float* db = nullptr, void* workspace = nullptr, unsigned long long workspace_bytes = 0) {
@@ -894,6 +903,25 @@ static int launch_wgrad(const GatherParams& p, const void* x, const void* dy, co
                 } else {
                     EVE_LAUNCH(EVE_HNAME(T, "wgrad_wg8_kernel<", ", false>"), (wgrad_wg8_kernel<T, false>), dim3(tk * tc * splits), dim3(512), (size_t)128 * 1024, s, p,
                                (const T*)x, (const T*)dy, dw, rows, (uint32_t)x_bytes, (uint32_t)dy_bytes);
+                }
+            } else if ((wg8w == 1 || wg8w == 2) && !db && mode == 1 && p.KH == 3 && p.KW == 3 && p.Cin == 128 && p.Cout % 128 == 0 &&
+                       (wg8w == 2 || p.M >= WGRAD_WG8_T128_MIN_M)) {
+                // 128 x 384 tiles (one filter row), eight waves of 64 x 96 (wgrad_wg8_t128.h): layer 2 stride 1, layer 3's stride-2 conv
+                const uint32_t tk = 3, tc = p.Cout / 128;
+                wgrad_split(p, tk, tc, (size_t)128 * 1024, splits, rows);
+                const unsigned long long n = (unsigned long long)p.Cout * p.K;
+                const bool slab = splits > 1 && workspace && (unsigned long long)splits * n * 4 <= workspace_bytes && ((uintptr_t)dw & 15) == 0 &&
+                                  ((uintptr_t)workspace & 15) == 0;
+                if (slab) {
+                    EVE_LAUNCH(EVE_HNAME(T, "wgrad_wg8_t128_kernel<", ", true>"), (wgrad_wg8_t128_kernel<T, true>), dim3(tk * tc * splits), dim3(512), (size_t)128 * 1024,
+                               s, p, (const T*)x, (const T*)dy, (float*)workspace, rows, (uint32_t)x_bytes, (uint32_t)dy_bytes);
+                    // (up to 85 slabs of a 0.6 / 1.2 MB filter: the reduce that spreads the slabs over a workgroup's waves)
+                    const long long n4 = (long long)(n / 4);
+                    hipLaunchKernelGGL(wgrad_slab_reduce_wide_kernel, dim3((unsigned)((n4 + 31) / 32)), dim3(256), 0, s, (const float*)workspace, dw, n4,
+                                       (int)splits);
+                } else {
+                    EVE_LAUNCH(EVE_HNAME(T, "wgrad_wg8_t128_kernel<", ", false>"), (wgrad_wg8_t128_kernel<T, false>), dim3(tk * tc * splits), dim3(512), (size_t)128 * 1024,
+                               s, p, (const T*)x, (const T*)dy, dw, rows, (uint32_t)x_bytes, (uint32_t)dy_bytes);
                 }
             } else if (p.Cout > 64) {
                 const uint32_t tk = (p.K + 127) / 128, tc = (p.Cout + 127) / 128;

@@ -67,7 +67,7 @@ typedef struct eve_dispatch_config {
     int wgrad_target_wgs;          /* EVE_WGRAD_TARGET_WGS  0   (0: 256 x resident workgroups per CU)                      */
     int wgrad_min_rows;            /* EVE_WGRAD_MIN_ROWS    1536 shortest pixel range of a weight-gradient split          */
     int wgrad_halo;                /* EVE_WGRAD_HALO        1   band-resident weight gradients (wgrad_halo.h)              */
-    int wgrad_wg8;                 /* EVE_WGRAD_WG8         1   256 x 256 eight-wave weight gradient (wgrad_wg8.h)         */
+    int wgrad_wg8;                 /* EVE_WGRAD_WG8         1   eight-wave weight gradients: the 256 x 256 tile (wgrad_wg8.h) and, for 3x3 layers with 128 input channels from 65 536 pixels up, the 128 x 384 tile (wgrad_wg8_t128.h); 2: the 128 x 384 tile at any pixel count (tests); 3: the 256 x 256 tile only (A/B); 0: neither */
     int wg64_th, wg64_nreg;        /* EVE_WG64_TH / _NREG   0 0 (0: largest band / region count that fits LDS)             */
     int wg64_fixed;                /* EVE_WG64_FIXED        1   unrolled wgrad_halo64_kernel for 32-wide planes            */
     int in_split;                  /* EVE_IN_SPLIT          1   64 Ki-element InstanceNorm planes as two channel halves    */

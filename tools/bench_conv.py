@@ -60,5 +60,47 @@ def main():
     print('trunk totals per step (ms): fwd %.2f dgrad %.2f wgrad %.2f' % (tot['fwd'], tot['dgrad'], tot['wgrad']))
 
 
+def wgrad_ab(args):
+    """python tools/bench_conv.py wgrad-ab [N ...] [f16]: the 128-input-channel 3x3 weight gradients (layer 2 stride 1, layer 3's
+    stride-2 convolution) on wgrad_tr_kernel (dispatch_override(wgrad_wg8=3)) and on the 128 x 384 eight-wave tile (wgrad_wg8=2), the
+    latter with slab partials (the process's workspace) and with float atomics (no workspace).  Warm: 20 launches between one event
+    pair; cold: one launch after a 1 GB fill has displaced the operands from L2 and the Infinity Cache.  min..max of 5 repeats, us."""
+    dt = torch.float16 if 'f16' in args else torch.bfloat16
+    Ns = [int(a) for a in args if a.isdigit()] or [1920, 480]
+    k = HipKernels()
+    flush = torch.empty(1 << 30, dtype=torch.uint8, device='cuda')
+    variants = (('wgrad_tr_kernel', 3, True), ('tile128 slab', 2, True), ('tile128 atomic', 2, False))
+    print('%-12s %5s %-16s %-34s %17s %17s' % ('shape', 'N', 'variant', 'kernel', 'warm us min..max', 'cold us min..max'))
+    for N in Ns:
+        for name, IH, Cin, Cout, K, s, p in [r for r in SHAPES if r[0] in ('l2_3x3', 'l3.0_3x3s2')]:
+            x = torch.randn((N, IH, IH, Cin), device='cuda').to(dt)
+            OH = (IH + 2 * p - K) // s + 1
+            dy = torch.randn((N, OH, OH, Cout), device='cuda').to(dt)
+            dw = torch.zeros((Cout, K, K, Cin), device='cuda')
+            for label, mode, use_ws in variants:
+                ws_bytes = k.WORKSPACE_BYTES
+                with k.dispatch_override(wgrad_wg8=mode):
+                    if not use_ws:
+                        k.WORKSPACE_BYTES = 0
+                    try:
+                        fn = lambda: k.conv2d_wgrad(x, dy, K, K, s, p, dw)
+                        warm = [timeit(fn, 20) * 1e3 for _ in range(5)]
+                        used = k.lib.eve_last_kernel().decode()
+                        cold = []
+                        for _ in range(5):
+                            flush.fill_(1)
+                            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                            e0.record(); fn(); e1.record()
+                            torch.cuda.synchronize()
+                            cold.append(e0.elapsed_time(e1) * 1e3)
+                    finally:
+                        k.WORKSPACE_BYTES = ws_bytes
+                print('%-12s %5d %-16s %-34s %7.1f..%-7.1f  %7.1f..%-7.1f' % (name, N, label, used.replace('eve::', ''), min(warm), max(warm),
+                                                                            min(cold), max(cold)), flush=True)
+
+
 if __name__ == '__main__':
-    main()
+    if len(sys.argv) > 1 and sys.argv[1] == 'wgrad-ab':
+        wgrad_ab(sys.argv[2:])
+    else:
+        main()
