@@ -196,6 +196,8 @@ SIGNATURES = {
     'eve_overlay_render': [I, I, I, L, I, I, P, P, I, P, P, P, F, F, P, I, I, I, I, P, I, I, I, I, I, I, P, P],
     'eve_face_pose_solve_ex': [L, I, I, I, P, P, P, ctypes.c_double, P, P, P, P, P, P, P, P, P],
     'eve_undistort_points': [L, P, P, L, P, P, P],
+    'eve_calib_append': [L, I, I, P, P, P, P, P, P, P, P, P, P, I, P, P, P, P],
+    'eve_calib_fit': [L, I, P, P, P, ctypes.c_double, I, P, P, P, P, P, P, P, P],
 }
 EXPORTS = sorted(list(SIGNATURES) + ['eve_abi_version', 'eve_last_error', 'eve_last_kernel'])
 

@@ -506,6 +506,79 @@ def solve_head_pose(landmarks, rig, lengths=None, lens=None, huber_px=None):
     return {k_: v[0] for k_, v in out.items()} if single else out
 
 
+def check_huber_mm(huber_mm, where):
+    """None or a finite number > 0 (millimetres on the screen) -> None or float; anything else raises ValueError."""
+    if huber_mm is None:
+        return None
+    if isinstance(huber_mm, bool) or not isinstance(huber_mm, (int, float)) or not 0 < huber_mm < float('inf'):
+        raise ValueError('%s: huber_mm must be None or a finite number > 0 (millimetres), got %r' % (where, huber_mm))
+    return float(huber_mm)
+
+
+def check_min_samples(min_samples, where):
+    if isinstance(min_samples, bool) or not isinstance(min_samples, int) or min_samples < 1:
+        raise ValueError('%s: min_samples must be an integer >= 1, got %r' % (where, min_samples))
+    return min_samples
+
+
+def calibration_samples(g, head_R, origin, R, inv_camera_transformation, pixels_per_millimeter, target_px):
+    """What the per-person offset fit needs of N frames of ONE eye, reduced on the device: g float32 [N, 2] (the network's
+    <side>_g_initial), head_R [N, 3, 3], origin [N, 3] (<side>_o), R [N, 3, 3] (<side>_R), inv_camera_transformation [N, 4, 4],
+    pixels_per_millimeter [N, 2] and target_px [N, 2], the dot the person looked at in actual_screen_size pixels.  -> float64
+    [N, 16], row i for frame i: A (9), e (3), the target in millimetres (2), the weight 1.0, 0.0 (include/eve_hip.h
+    eve_calib_append).  A frame that is not usable -- a value that is not finite, a target behind the eye -- gives a row of zeros,
+    which fit_gaze_offset passes over (its weight is 0)."""
+    ok = lambda t: torch.is_tensor(t) and t.dtype == torch.float32
+    if not ok(g) or g.dim() != 2 or g.shape[1] != 2 or g.shape[0] < 1:
+        raise TypeError('calibration_samples: g must be float32 [N, 2] with N >= 1, got %s %s' % (getattr(g, 'dtype', type(g)),
+                                                                                                 tuple(getattr(g, 'shape', ()))))
+    N = g.shape[0]
+    for name, t, shape in (('head_R', head_R, (N, 3, 3)), ('origin', origin, (N, 3)), ('R', R, (N, 3, 3)),
+                           ('inv_camera_transformation', inv_camera_transformation, (N, 4, 4)),
+                           ('pixels_per_millimeter', pixels_per_millimeter, (N, 2)), ('target_px', target_px, (N, 2))):
+        if not ok(t) or tuple(t.shape) != shape:
+            raise TypeError('calibration_samples: %s must be float32 %s, got %s %s' % (name, list(shape), getattr(t, 'dtype', type(t)),
+                                                                                      tuple(getattr(t, 'shape', ()))))
+    dev = g.device
+    samples = torch.zeros((N, 1, 1, 16), dtype=torch.float64, device=dev)
+    count, dropped = torch.zeros((N, 1), dtype=torch.int32, device=dev), torch.zeros((N, 1), dtype=torch.int32, device=dev)
+    c = lambda t, *s: t.reshape((N, 1) + s).contiguous()
+    default_kernels().calib_append(c(g, 2)[None], c(head_R, 3, 3), c(origin, 3)[None], c(R, 3, 3)[None], c(inv_camera_transformation, 4, 4),
+                                   c(pixels_per_millimeter, 2), c(target_px, 2), samples, count, dropped)
+    return samples.view(N, 16)
+
+
+def fit_gaze_offset(samples, counts=None, huber_mm=None, min_samples=5):
+    """The per-person offset kappa = (pitch, yaw) between the optical axis EyeNet sees and the visual axis, fitted on the device to
+    calibration samples: samples float64 [S, C, 16] ([C, 16]: one sequence) as calibration_samples or an EVEStream's store holds
+    them; counts None (all C rows) or S integers (a list, a numpy array or a tensor): the rows in use.  Levenberg-Marquardt from
+    kappa = 0 on sum rho(|PoG_i(kappa) - target_i|) in millimetres, rho the square, or with huber_mm a Huber loss whose threshold
+    is that many millimetres on the screen (25 suits 8 mm of fixation noise).  -> a dict of kappa float64 [S, 2] (radians), rms_mm
+    float64 [S] (over all used samples), used and inliers int32 [S] (the samples within huber_mm; used without the loss) and ok
+    bool [S].  ok False (kappa, rms_mm, inliers 0): fewer than min_samples rows with weight > 0, a system that is not positive
+    definite (every target on one line through the eye, say), no convergence, or |kappa| above 0.35 rad (20 degrees: the fit
+    diverged).  One launch, a wavefront per sequence; the host does not wait.  The contract, summation order included, is
+    include/eve_hip.h eve_calib_fit and tests/calib_ref.py.  Not offered: screen-space polynomial or affine calibration,
+    per-sample weights (entry 14 of a row is 1.0, or 0.0 for an absent row), gradients."""
+    if not torch.is_tensor(samples) or samples.dtype != torch.float64 or samples.dim() not in (2, 3) or samples.shape[-1] != 16:
+        raise TypeError('fit_gaze_offset: samples must be float64 [S, C, 16], got %s %s' % (getattr(samples, 'dtype', type(samples)),
+                                                                                          tuple(getattr(samples, 'shape', ()))))
+    single = samples.dim() == 2
+    if single:
+        samples = samples[None]
+    if samples.numel() == 0:
+        raise ValueError('fit_gaze_offset: no samples (shape %s)' % (tuple(samples.shape),))
+    S = samples.shape[0]
+    huber_mm, min_samples = check_huber_mm(huber_mm, 'fit_gaze_offset'), check_min_samples(min_samples, 'fit_gaze_offset')
+    if counts is not None:
+        counts = torch.as_tensor(counts).to(device=samples.device, dtype=torch.int32).contiguous()
+        if tuple(counts.shape) != (S,):
+            raise ValueError('fit_gaze_offset: counts needs one entry per sequence (%d)' % S)
+    kappa, rms, used, inliers, good = default_kernels().calib_fit(samples.contiguous(), counts, None, huber_mm, min_samples)
+    out = {'kappa': kappa, 'rms_mm': rms, 'used': used, 'inliers': inliers, 'ok': good != 0}
+    return {k_: v[0] for k_, v in out.items()} if single else out
+
+
 def warp_eye_patches(frames, warps, size=None, lens=None, format='rgb', matrix='bt601', layout=None):
     """One eye's patches cut from whole camera frames on the device, in place of two cv2.warpPerspective calls per frame on the
     host: frames uint8 [..., IH, IW, 3 | 4] (a fourth channel ignored, the channel order kept), warps float32 [..., 3, 3] with the

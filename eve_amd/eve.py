@@ -156,11 +156,16 @@ class EVE(nn.Module):
             d['g_validity'] = d['PoG_cm_tobii_validity']
 
     # ------------------------------------------------------------------------------------------ eve.py:545-601
-    def _pog_block(self, d, inter, g_key, out_suffix, kappa_suffix=None, heatmap_history=False, eye_valid=None):
+    def _pog_block(self, d, inter, g_key, out_suffix, kappa_suffix=None, heatmap_history=False, eye_valid=None, calib=None):
         """Per-eye PoG from `<side>_g_<g_key>`, their mean, the combined gaze, the heat-map -- for all B*T frames.  With
         `kappa_suffix` the offset augmentation is applied first and the augmented angles are stored back under
         `<side>_g_<kappa_suffix>`.  eye_valid (a masked EVEStream step: bool [B, T, 2]): the binocular PoG is the usable eye's own
-        where only one is (_fuse2), and the combined gaze is rotated by d['combined_R'] (_predict_sequence)."""
+        where only one is (_fuse2), and the combined gaze is rotated by d['combined_R'] (_predict_sequence).  calib (a calibrated
+        EVEStream step): {'kappa': float32 [B, 2, 2] (stream, eye, (pitch, yaw)), 'calibrated': bool [B]} -- per eye a second
+        eve_gaze_to_pog launch applies the stream's kappa row through the kernel's offset path, and a select per stream keeps the
+        plain launch's bits where the stream is not calibrated (a zero row through the trigonometric round trip is not the
+        identity in float32); `<side>_g_<g_key>` becomes the calibrated angles and the network's own stay under
+        `<side>_g_<g_key>_raw`."""
         if 'inv_camera_transformation' not in d:                      # GazeCapture / MPIIGaze style inputs
             if kappa_suffix is not None:
                 self._augment_only(d, inter, g_key, kappa_suffix)
@@ -181,6 +186,18 @@ class EVE(nn.Module):
                 head_R, kappa)
             if kappa_suffix is not None:
                 inter['%s_g_%s' % (side, kappa_suffix)] = g_out.view(B, T, 2)
+            if calib is not None:
+                g_raw = inter['%s_g_%s' % (side, g_key)]
+                kap = calib['kappa'][:, 0 if side == 'left' else 1, None, :].expand(B, T, 2).reshape(N, 2).contiguous()
+                g_c, mm_c, px_c = ops.GazeToPoGFn.apply(
+                    g_raw.reshape(N, 2), origin.reshape(N, 3).float(), rot.reshape(N, 3, 3).float(),
+                    flat('inv_camera_transformation', 4, 4), flat('pixels_per_millimeter', 2), tuple(cfg.actual_screen_size),
+                    flat('head_R', 3, 3), kap)
+                sel = calib['calibrated'][:, None, None]
+                pick = lambda a, b: torch.where(sel, a.view(B, T, 2), b.view(B, T, 2))
+                inter['%s_g_%s_raw' % (side, g_key)] = g_raw
+                inter['%s_g_%s' % (side, g_key)] = pick(g_c, g_raw)
+                mm, px = pick(mm_c, mm), pick(px_c, px)
             inter['%s_PoG_cm_%s' % (side, out_suffix)] = (0.1 * mm).view(B, T, 2)
             inter['%s_PoG_px_%s' % (side, out_suffix)] = px.view(B, T, 2)
         for unit in ('px', 'cm'):
@@ -326,7 +343,7 @@ class EVE(nn.Module):
                        'PoG_cm_initial', 'g_final', 'PoG_px_final', 'PoG_cm_final')
 
     def _predict_sequence(self, d, eye_states, refine_states, reset=None, return_heatmaps=False, lengths=None, masked=False,
-                          eye_mask=None, pose_gate=None, face_state=None, render=None):
+                          eye_mask=None, pose_gate=None, face_state=None, render=None, calibration=None):
         """The prediction part of forward() for one chunk of an EVEStream: eval only, no labels, no losses.  d: the chunk's
         inputs [B, Tc, ...] (not modified; camera_frame may be any one key of eye_net.EYE_FRAME_KEYS or camera_surface, and the screen any one
         key of refine_net.SCREEN_FRAME_KEYS or screen_surface; the eyes as patches, as camera_frame + {left,right}_eye_warp, or as camera_frame +
@@ -353,7 +370,13 @@ class EVE(nn.Module):
         eye_net.face_huber_px, make it the eve_face_pose_solve_ex launch, and the result gains face_inliers [B, Tc].
         render: None, or EVEStream's overlay hook render(d, inter, out), called last with the chunk after eye_pose_batch (the derived
         warps included), the intermediate results (heatmap_final whether returned or not) and the result, to which it adds
-        `rendered`; None issues no launch."""
+        `rendered`; None issues no launch.
+        calibration: None, or EVEStream's per-person calibration {'kappa': float32 [B, 2, 2], 'ok': uint8 [B, 2], 'apply': bool,
+        'store': None or (samples float64 [B, 2, C, 16], count int32 [B, 2], dropped int32 [B, 2])}.  With a store and
+        calibration_target [B, Tc, 2] (and optionally calibration_valid [B, Tc]) in d, one eve_calib_append launch reduces every
+        usable (frame, eye) -- calibration_valid, t < lengths[b], eye_valid -- from the network's own angles and appends it.  With
+        apply, _pog_block applies the kappa rows where both flags of a stream are set; the result gains <side>_g_initial_raw and
+        calibrated, bool [B].  None issues no launch."""
         assert not self.training, 'EVE._predict_sequence is eval-only'
         B = eye_input(d).shape[0]
         posed, faced = has_pose_form(d), face_landmarks_key(d) is not None
@@ -372,7 +395,16 @@ class EVE(nn.Module):
         if plan is not None and 'left_R' in d:
             d['combined_R'] = torch.where(eye_valid[:, :, 0, None, None], d['left_R'], d['right_R'])
         inter = dict(self.eye_net._stream_sequence(d, eye_states, reset, lengths, plan))
-        self._pog_block(d, inter, 'initial', 'initial', eye_valid=eye_valid)
+        calib = None
+        if calibration is not None:
+            if calibration['store'] is not None and 'calibration_target' in d:
+                self._calibration_append(d, inter, calibration['store'], None if lengths is None else lengths[:B], plan)
+            if calibration['apply']:
+                calib = {'kappa': calibration['kappa'], 'calibrated': (calibration['ok'] != 0).all(dim=1)}
+        if calib is None:
+            self._pog_block(d, inter, 'initial', 'initial', eye_valid=eye_valid)
+        else:
+            self._pog_block(d, inter, 'initial', 'initial', eye_valid=eye_valid, calib=calib)
         if self.refine_net is not None and 'heatmap_initial' in inter:
             hf = self.refine_net._stream_sequence(inter['heatmap_initial'], d.get('screen_frame'), refine_states,
                                                   None if reset is None else reset[:B], None if lengths is None else lengths[:B], plan,
@@ -380,6 +412,11 @@ class EVE(nn.Module):
             inter['heatmap_final'] = hf
             self._final_block(d, inter, hf)
         out = {k_: inter[k_] for k_ in self.PREDICTION_KEYS if k_ in inter}
+        if calib is not None:
+            out['calibrated'] = calib['calibrated']
+            for side in ('left', 'right'):
+                if side + '_g_initial_raw' in inter:
+                    out[side + '_g_initial_raw'] = inter[side + '_g_initial_raw']
         if posed:
             out['pose_valid'] = d['pose_valid']
         if faced:
@@ -393,6 +430,21 @@ class EVE(nn.Module):
         if render is not None:
             render(d, inter, out)
         return out
+
+    def _calibration_append(self, d, inter, store, lengths, plan):
+        """The collecting stage of a calibrated EVEStream step: one eve_calib_append launch over both eyes, from the network's own
+        <side>_g_initial (before any calibration is applied, so collecting while calibrated does not compound)."""
+        B, T = d['calibration_target'].shape[:2]
+        both = lambda key, *s_: torch.stack([(inter[side + key] if side + key in inter else d[side + key]).reshape((B, T) + s_).float()
+                                             for side in ('left', 'right')]).contiguous()
+        f32 = lambda key, *s_: d[key].reshape((B, T) + s_).float().contiguous()
+        valid = d.get('calibration_valid')
+        if valid is not None:
+            valid = valid.contiguous()
+            valid = valid.view(torch.uint8) if valid.dtype == torch.bool else valid
+        default_kernels().calib_append(both('_g_initial', 2), f32('head_R', 3, 3), both('_o', 3), both('_R', 3, 3),
+                                       f32('inv_camera_transformation', 4, 4), f32('pixels_per_millimeter', 2), f32('calibration_target', 2),
+                                       store[0], store[1], store[2], valid, lengths, None if plan is None else plan['eye_valid'])
 
     # ------------------------------------------------------------------------------------------ eve.py:286-439
     def calculate_losses_and_metrics(self, d, inter, out):

@@ -910,6 +910,62 @@ class HipKernels(object):
         self._ck(self.lib.eve_undistort_points(N, self._p(points), self._p(lens), stride, self._p(xy), self._p(good), self._stream()))
         return xy, good
 
+    # ------------------------------------------------------------------ per-person gaze calibration
+    def calib_append(self, g, head_R, origin, R, inv_cam, ppm, target, samples, count, dropped, valid=None, lengths=None, eye_valid=None):
+        """Reduce the usable frames of B streams x T frames x E eyes to the offset fit's 16 doubles and append them, in frame order,
+        to the stores: g [E, B, T, 2], origin [E, B, T, 3], R [E, B, T, 3, 3] (eye-major), head_R [B, T, 3, 3], inv_cam [B, T, 4, 4],
+        ppm [B, T, 2], target [B, T, 2] float32; samples float64 [B, E, C, 16], count and dropped int32 [B, E], UPDATED IN PLACE;
+        valid uint8 [B, T], lengths int32 [B], eye_valid uint8 [B, T, E] or None (include/eve_hip.h eve_calib_append)."""
+        ok = lambda t, dtype: torch.is_tensor(t) and t.dtype == dtype
+        if not ok(g, torch.float32) or g.dim() != 4 or g.shape[0] not in (1, 2) or g.shape[3] != 2:
+            raise TypeError('calib_append: g must be float32 [E, B, T, 2] with E = 1 or 2, got %s %s' % (
+                getattr(g, 'dtype', type(g)), tuple(getattr(g, 'shape', ()))))
+        E, B, T = g.shape[:3]
+        if not ok(samples, torch.float64) or samples.dim() != 4 or tuple(samples.shape[:2]) != (B, E) or samples.shape[3] != 16:
+            raise TypeError('calib_append: samples must be float64 [%d, %d, C, 16], got %s %s' % (
+                B, E, getattr(samples, 'dtype', type(samples)), tuple(getattr(samples, 'shape', ()))))
+        C = samples.shape[2]
+        for name, t, dtype, shape in (('head_R', head_R, torch.float32, (B, T, 3, 3)), ('origin', origin, torch.float32, (E, B, T, 3)),
+                                      ('R', R, torch.float32, (E, B, T, 3, 3)), ('inv_cam', inv_cam, torch.float32, (B, T, 4, 4)),
+                                      ('ppm', ppm, torch.float32, (B, T, 2)), ('target', target, torch.float32, (B, T, 2)),
+                                      ('count', count, torch.int32, (B, E)), ('dropped', dropped, torch.int32, (B, E)),
+                                      ('valid', valid, torch.uint8, (B, T)), ('lengths', lengths, torch.int32, (B,)),
+                                      ('eye_valid', eye_valid, torch.uint8, (B, T, E))):
+            if (t is not None or name not in ('valid', 'lengths', 'eye_valid')) and (not ok(t, dtype) or tuple(t.shape) != shape):
+                raise TypeError('calib_append: %s must be %s %s, got %s %s' % (
+                    name, str(dtype).replace('torch.', ''), list(shape), getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ()))))
+        self._ck(self.lib.eve_calib_append(B, T, E, self._p(g), self._p(head_R), self._p(origin), self._p(R), self._p(inv_cam), self._p(ppm),
+                                           self._p(target), self._p(valid), self._p(lengths), self._p(eye_valid), C, self._p(samples),
+                                           self._p(count), self._p(dropped), self._stream()))
+
+    def calib_fit(self, samples, count=None, select=None, huber_mm=None, min_samples=5, kappa_store=None, ok_store=None):
+        """The offset fit, one wavefront per sequence: samples float64 [S, C, 16]; count int32 [S] or None (all C rows); select uint8
+        [S] or None (0: the sequence is not fitted); huber_mm None or millimetres > 0; kappa_store float32 [S, 2] and ok_store uint8
+        [S] (both or neither), written where the fit is ok and only there.  -> (kappa float64 [S, 2], rms_mm float64 [S], used int32
+        [S], inliers int32 [S], ok uint8 [S]) (include/eve_hip.h eve_calib_fit)."""
+        ok = lambda t, dtype: torch.is_tensor(t) and t.dtype == dtype
+        if not ok(samples, torch.float64) or samples.dim() != 3 or samples.shape[2] != 16 or samples.shape[0] < 1 or samples.shape[1] < 1:
+            raise TypeError('calib_fit: samples must be float64 [S, C, 16], got %s %s' % (
+                getattr(samples, 'dtype', type(samples)), tuple(getattr(samples, 'shape', ()))))
+        S, C = samples.shape[:2]
+        for name, t, dtype, shape in (('count', count, torch.int32, (S,)), ('select', select, torch.uint8, (S,)),
+                                      ('kappa_store', kappa_store, torch.float32, (S, 2)), ('ok_store', ok_store, torch.uint8, (S,))):
+            if t is not None and (not ok(t, dtype) or tuple(t.shape) != shape):
+                raise TypeError('calib_fit: %s must be %s %s, got %s %s' % (
+                    name, str(dtype).replace('torch.', ''), list(shape), getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ()))))
+        if (kappa_store is None) != (ok_store is None):
+            raise TypeError('calib_fit: kappa_store and ok_store come together')
+        if huber_mm is not None and not (isinstance(huber_mm, (int, float)) and not isinstance(huber_mm, bool) and 0 < huber_mm < float('inf')):
+            raise ValueError('calib_fit: huber_mm must be None or a finite number > 0, got %r' % (huber_mm,))
+        if isinstance(min_samples, bool) or not isinstance(min_samples, int) or min_samples < 1:
+            raise ValueError('calib_fit: min_samples must be an integer >= 1, got %r' % (min_samples,))
+        new = lambda *shape, dtype=torch.float64: torch.empty(shape, dtype=dtype, device=samples.device)
+        kappa, rms, used, inliers, good = new(S, 2), new(S), new(S, dtype=torch.int32), new(S, dtype=torch.int32), new(S, dtype=torch.uint8)
+        self._ck(self.lib.eve_calib_fit(S, C, self._p(samples), self._p(count), self._p(select), 0.0 if huber_mm is None else float(huber_mm),
+                                        int(min_samples), self._p(kappa), self._p(rms), self._p(used), self._p(inliers), self._p(good),
+                                        self._p(kappa_store), self._p(ok_store), self._stream()))
+        return kappa, rms, used, inliers, good
+
     # ------------------------------------------------------------------ gaze geometry / heat-maps / soft-argmax
     def _flat32(self, t, shape, what):
         t = t.contiguous()

@@ -6,6 +6,8 @@ carried from one call to the next.
     out = stream.step(chunk, lengths=[3, 1, 0, 3])         # ragged: stream b delivered only lengths[b] frames (see step)
     out = stream.step(chunk, eye_mask=usable)              # masked: usable [B, Tc, 2] marks the eyes to consume, frame by frame
     stream.reset([3])                                      # stream 3 starts from zero state at the next step()
+    stream.step(dict(chunk, calibration_target=dots))      # collect per-person calibration samples (see "Calibration" below)
+    fit = stream.fit_calibration(huber_mm=25.0)            # fit each eye's offset on the device; later steps apply it
     st = stream.get_state(); stream.set_state(st)          # reference layout, e.g. to resume a recording
 
 For any split of a clip into chunks the concatenated outputs equal one eval pass of the whole clip from zero state
@@ -33,6 +35,22 @@ chunk is copied into the graph's input buffers first.  Resets are device flags w
 changed weight (load_state_dict, an optimiser step through torch) is detected through the parameters' versions, as the
 modules' weight packs are, and the graphs are captured again.  Weights changed behind torch's back (a fused optimiser
 kernel) need invalidate(), as the modules need invalidate_packs().
+
+Calibration.  Every person's visual axis sits a few degrees off the optical axis EyeNet sees; the reference trains RefineNet
+under random offsets of that kind (kappa_fake) for this reason.  An EVEStream can collect, fit and apply that offset per
+stream and eye, all on the device and stream-ordered.  A chunk with calibration_target, float32 [B, Tc, 2] -- the dot the person
+was asked to look at, in actual_screen_size pixels -- and optionally calibration_valid, bool or uint8 [B, Tc], makes the step
+append what the fit needs of every usable (frame, eye) to this EVEStream's sample store (one eve_calib_append launch inside
+the step and the graph; float64 [B, 2, C, 16], C = calibration_capacity; a full store drops and counts).  fit_calibration() fits
+each eye's kappa = (pitch, yaw) by one eve_calib_fit launch, and from then on the step applies the stream's rows through the
+offset path of eve_gaze_to_pog: <side>_g_initial, PoG_*_initial, g_initial, heatmap_initial and everything RefineNet derives
+follow from the calibrated angles, the network's own angles appear as <side>_g_initial_raw, and the result gains calibrated,
+bool [B].  A stream that is not calibrated keeps the bits of an uncalibrated EVEStream (a select per stream, not a kappa of
+zero), and an EVEStream on which no calibration call was ever made issues exactly the launches it always issued.  Samples are
+always collected from the raw angles, so collecting while calibrated does not compound.  The offset and the store belong to the
+person, not to the clip: reset() touches neither, and get_state() / set_state() do not hold them (get_calibration /
+set_calibration do).  Not offered: screen-space polynomial or affine calibration, per-sample weights from the caller (entry 14
+of a sample is reserved at 1.0), automatic or continuous recalibration, gradients, application in EVE.forward.
 """
 import numpy as np
 import torch
@@ -48,7 +66,7 @@ def _module_key(m):
 
 
 class EVEStream(object):
-    def __init__(self, model, num_streams, use_graph=True):
+    def __init__(self, model, num_streams, use_graph=True, calibration_capacity=1024):
         if model.training:
             raise ValueError('EVEStream runs inference only: call model.eval() first')
         self.model = model
@@ -70,6 +88,16 @@ class EVEStream(object):
         # the face-landmark form's carried head pose, float64 (R row-major, t, has_pose) per stream: eve_face_pose_solve reads and
         # writes it inside the step (and the graph), and clears it where the reset flag is set
         self._face_pose = torch.zeros((B, 13), dtype=torch.float64, device=self.device)
+        # per-person calibration: the sample store (eve_calib_append appends inside the step), each eye's kappa row and flag
+        # (eve_calib_fit writes them; a stream is calibrated where both flags are set).  _calib_apply: a fit or a set_calibration
+        # has happened, so the steps run the applying graphs.
+        if isinstance(calibration_capacity, bool) or not isinstance(calibration_capacity, int) or calibration_capacity < 1:
+            raise ValueError('calibration_capacity must be an integer >= 1, got %r' % (calibration_capacity,))
+        self.calibration_capacity = C = calibration_capacity
+        self._calib_store = None                 # made at the first collecting step or calibration call: B * 2 * C * 128 bytes
+        self._calib_kappa = torch.zeros((B, 2, 2), dtype=torch.float32, device=self.device)
+        self._calib_ok = torch.zeros((B, 2), dtype=torch.uint8, device=self.device)
+        self._calib_apply = False
         self._graphs = {}
         self._graphs_key = None
         self._render_tables = {}                 # OverlaySpec.key() -> its marker table, int32 [M, 4] on the device
@@ -80,23 +108,114 @@ class EVEStream(object):
 
     def reset(self, streams=None):
         """Start the given streams (None = all; else indices, or a bool mask of length num_streams) from zero state at the
-        next step().  Resets requested before one step accumulate."""
+        next step().  Resets requested before one step accumulate.  The per-person calibration -- each eye's kappa and the
+        sample store -- is not touched: it belongs to the person, not to the clip (clear_calibration,
+        clear_calibration_samples)."""
+        m = np.zeros(self.num_streams, dtype=bool) if self._pending is None else self._pending
+        m |= self._stream_mask(streams, 'reset')
+        self._pending = m
+
+    def _stream_mask(self, streams, where):
+        """None (all), indices, or a bool mask of length num_streams -> numpy bool [B]."""
         B = self.num_streams
-        m = np.zeros(B, dtype=bool) if self._pending is None else self._pending
+        m = np.zeros(B, dtype=bool)
         if streams is None:
             m[:] = True
         else:
             a = streams.detach().cpu().numpy() if torch.is_tensor(streams) else np.asarray(streams)
             if a.dtype == bool:
                 if a.shape != (B,):
-                    raise ValueError('reset: a mask needs num_streams (%d) entries' % B)
+                    raise ValueError('%s: a mask needs num_streams (%d) entries' % (where, B))
                 m |= a
             else:
                 idx = a.astype(np.int64).reshape(-1)
                 if idx.size and (idx.min() < -B or idx.max() >= B):
-                    raise IndexError('reset: stream index out of range')
+                    raise IndexError('%s: stream index out of range' % where)
                 m[idx] = True
-        self._pending = m
+        return m
+
+    # ------------------------------------------------------------------ calibration
+    def _store(self):
+        if self._calib_store is None:
+            B, C = self.num_streams, self.calibration_capacity
+            self._calib_store = (torch.zeros((B, 2, C, 16), dtype=torch.float64, device=self.device),
+                                 torch.zeros((B, 2), dtype=torch.int32, device=self.device),
+                                 torch.zeros((B, 2), dtype=torch.int32, device=self.device))
+        return self._calib_store
+
+    def _device_mask(self, streams, where):
+        m = torch.from_numpy(self._stream_mask(streams, where))
+        return m.to(self.device, non_blocking=True) if self.device.type != 'cuda' else m.pin_memory().to(self.device, non_blocking=True)
+
+    def fit_calibration(self, streams=None, huber_mm=None, min_samples=5):
+        """Fit the offset kappa = (pitch, yaw) of both eyes of the given streams (None = all; indices or a bool mask) to the samples
+        collected so far: one eve_calib_fit launch, a wavefront per (stream, eye), Levenberg-Marquardt from kappa = 0 on every call
+        (a refit never depends on history) on sum rho(|PoG_i(kappa) - target_i|) in millimetres on the screen -- rho the square,
+        or with huber_mm a Huber loss of that many millimetres, which keeps a few frames in which the person looked elsewhere
+        from tilting the result.  -> a dict of device tensors (the host does not wait): kappa float64 [B, 2, 2] (stream, eye,
+        (pitch, yaw)), rms_mm float64 [B, 2] over all used samples, used and inliers int32 [B, 2] (the samples within huber_mm;
+        used without the loss), ok bool [B, 2], calibrated bool [B].  ok is False -- and that eye's stored kappa and flag stay what
+        they were -- with fewer than min_samples samples, a system that is not positive definite, no convergence, or |kappa|
+        above 0.35 rad (20 degrees, four times any physiological offset: a divergence guard).  A stream is calibrated when both
+        of its eyes have been fitted (or set); streams not named are left alone and report ok False.  The following steps apply
+        the stored rows (a new graph per chunk shape).  tests/calib_ref.py states the fit in numpy."""
+        from .data import check_huber_mm, check_min_samples
+        huber_mm, min_samples = check_huber_mm(huber_mm, 'fit_calibration'), check_min_samples(min_samples, 'fit_calibration')
+        B, C = self.num_streams, self.calibration_capacity
+        select = None if streams is None else self._device_mask(streams, 'fit_calibration')[:, None].expand(B, 2).to(torch.uint8).reshape(-1).contiguous()
+        samples, count, _ = self._store()
+        kappa, rms, used, inliers, ok = default_kernels().calib_fit(
+            samples.view(2 * B, C, 16), count.view(-1), select, huber_mm, min_samples, self._calib_kappa.view(2 * B, 2), self._calib_ok.view(-1))
+        self._calib_apply = True
+        return {'kappa': kappa.view(B, 2, 2), 'rms_mm': rms.view(B, 2), 'used': used.view(B, 2), 'inliers': inliers.view(B, 2),
+                'ok': ok.view(B, 2) != 0, 'calibrated': (self._calib_ok != 0).all(dim=1)}
+
+    def get_calibration(self):
+        """The stored offsets (fresh tensors): kappa float32 [B, 2, 2] (stream, eye, (pitch, yaw)) -- the rows the steps apply --
+        and calibrated bool [B].  Rows of eyes never fitted or set are zero."""
+        return self._calib_kappa.clone(), (self._calib_ok != 0).all(dim=1)
+
+    def set_calibration(self, kappa, streams=None):
+        """Load offsets known from an earlier session: kappa [B, 2, 2] in get_calibration()'s layout (converted to float32; the
+        rows of the given streams are used, None = all), which become calibrated.  Values are not judged."""
+        B = self.num_streams
+        kappa = torch.as_tensor(kappa, dtype=torch.float32).to(self.device)
+        if tuple(kappa.shape) != (B, 2, 2):
+            raise ValueError('set_calibration: kappa must be [%d, 2, 2] (stream, eye, (pitch, yaw)), got %s' % (B, tuple(kappa.shape)))
+        m = self._device_mask(streams, 'set_calibration')
+        self._calib_kappa.copy_(torch.where(m[:, None, None], kappa, self._calib_kappa))
+        self._calib_ok.copy_(torch.where(m[:, None], torch.ones_like(self._calib_ok), self._calib_ok))
+        self._calib_apply = True
+
+    def clear_calibration(self, streams=None):
+        """Forget the offsets of the given streams (None = all): they are uncalibrated again and get the plain bits.  The sample
+        store stays."""
+        m = self._device_mask(streams, 'clear_calibration')
+        self._calib_kappa.copy_(torch.where(m[:, None, None], torch.zeros_like(self._calib_kappa), self._calib_kappa))
+        self._calib_ok.copy_(torch.where(m[:, None], torch.zeros_like(self._calib_ok), self._calib_ok))
+        if streams is None:
+            self._calib_apply = False            # nothing left to apply: back to the launches of an uncalibrated EVEStream
+
+    def clear_calibration_samples(self, streams=None):
+        """Empty the sample store of the given streams (None = all), both eyes, and their dropped counters."""
+        if self._calib_store is None:
+            self._stream_mask(streams, 'clear_calibration_samples')
+            return
+        m = self._device_mask(streams, 'clear_calibration_samples')
+        _, count, dropped = self._calib_store
+        count.copy_(torch.where(m[:, None], torch.zeros_like(count), count))
+        dropped.copy_(torch.where(m[:, None], torch.zeros_like(dropped), dropped))
+
+    def calibration_counts(self):
+        """-> (count, dropped), int32 [B, 2] device tensors (fresh): the samples each (stream, eye) holds, and those a full store
+        (calibration_capacity) turned away."""
+        _, count, dropped = self._store()
+        return count.clone(), dropped.clone()
+
+    def calibration_samples(self):
+        """The sample store itself, float64 [B, 2, C, 16] (fresh): rows 0 .. count - 1 of (stream, eye) in the order the frames
+        came, in the layout of data.calibration_samples / data.fit_gaze_offset."""
+        return self._store()[0].clone()
 
     def get_state(self):
         """The carried states in the reference layout (fresh tensors): {left,right}_eye_rnn_states_<i> [B, H] float32 ((h, c) for
@@ -203,6 +322,30 @@ class EVEStream(object):
         host = torch.from_numpy((a != 0).astype(np.uint8))
         return host.pin_memory() if self.device.type == 'cuda' else host     # as _upload_resets: asynchronous, never baked into a graph
 
+    def _check_calibration(self, chunk, B, Tc):
+        """step()'s calibration keys, and what an applying step needs, checked before anything is launched or captured."""
+        target, valid = chunk.get('calibration_target'), chunk.get('calibration_valid')
+        if target is None and valid is None and not self._calib_apply:
+            return
+        if target is None and valid is not None:
+            raise ValueError('step: calibration_valid comes with calibration_target')
+        what = 'calibration_target' if target is not None else 'an applied calibration'
+        if 'inv_camera_transformation' not in chunk:
+            raise ValueError('step: %s needs the camera geometry (inv_camera_transformation) in the chunk' % what)
+        if 'head_R' not in chunk and not has_pose_form(chunk):
+            raise ValueError('step: %s needs head_R in the chunk: the offset is applied in the head\'s frame' % what)
+        if target is not None:
+            if (not torch.is_tensor(target) or target.dtype != torch.float32 or tuple(target.shape) != (B, Tc, 2) or
+                    target.device != self.device):
+                raise ValueError('step: calibration_target must be a float32 [%d, %d, 2] tensor on %s, got %s %s' % (
+                    B, Tc, self.device, getattr(target, 'dtype', type(target)), tuple(getattr(target, 'shape', ()))))
+            self._store()                        # allocated here, before any capture
+        if valid is not None:
+            if (not torch.is_tensor(valid) or valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) != (B, Tc) or
+                    valid.device != self.device):
+                raise ValueError('step: calibration_valid must be a bool or uint8 [%d, %d] tensor on %s, got %s %s' % (
+                    B, Tc, self.device, getattr(valid, 'dtype', type(valid)), tuple(getattr(valid, 'shape', ()))))
+
     def _set_pose_gate(self, skip_invalid_pose):
         if self._pose_gate_host != (not skip_invalid_pose):
             self._pose_gate_host = not skip_invalid_pose
@@ -211,6 +354,9 @@ class EVEStream(object):
     def _run(self, chunk, return_heatmaps, ragged=False, eye_mask=None, masked=False, render=None):
         # render: None or a _render_plan; the keyword reaches _predict_sequence only then, so a step without it calls what it always did
         extra = {} if render is None else {'render': self._render_hook(render, ragged, masked)}
+        if self._calib_apply or 'calibration_target' in chunk:       # (neither: the call an uncalibrated EVEStream always made)
+            extra['calibration'] = {'kappa': self._calib_kappa, 'ok': self._calib_ok, 'apply': self._calib_apply,
+                                    'store': self._store() if 'calibration_target' in chunk else None}
         if face_landmarks_key(chunk) is not None:      # the face-landmark form: the carried head pose goes along
             return self.model._predict_sequence(chunk, self._eye, self._ref, reset=self._flags, return_heatmaps=return_heatmaps,
                                                 lengths=self._lengths if ragged else None, masked=masked, eye_mask=eye_mask,
@@ -499,7 +645,18 @@ class EVEStream(object):
         converted capture.  PoG_px_final and the heat map need RefineNet (ValueError without).  The spec is part of the graph's
         key; tests/overlay_ref.py states the arithmetic, exact to the bit.  Not offered: the reference's residual lines from an
         estimate to the ground truth, its legend text, gaze-ray arrows on the eye image, row pitches, 10-bit surfaces, a gradient.
-        render=None issues exactly the launches the step always issued."""
+        render=None issues exactly the launches the step always issued.
+
+        calibration_target, float32 [B, Tc, 2] on the model's device -- the dot the person was asked to look at, in
+        actual_screen_size pixels -- and optionally calibration_valid, bool or uint8 [B, Tc] (default: every frame), make this a
+        collecting step: one eve_calib_append launch inside the step and the graph appends every usable (frame, eye) to this
+        EVEStream's sample store -- usable iff calibration_valid, t < lengths[b], eye_valid[b, t, side] on a masked step, every
+        input finite and the target in front of the eye -- in frame order, from the network's own angles.  The keys' shapes
+        and dtypes are part of the graph's key like any chunk tensor's, so a collecting step has a graph of its own; lengths,
+        eye_mask, skip_invalid_pose, every camera and screen form and render combine with it.  Needs inv_camera_transformation and
+        head_R in the chunk (the pose forms derive head_R): ValueError otherwise, as for calibration_valid without a target.
+        Once fit_calibration or set_calibration has been called the step applies the stored offsets (module docstring,
+        "Calibration"): the result gains calibrated [B] and <side>_g_initial_raw, and needs head_R too."""
         if self.model.training:
             raise ValueError('EVEStream runs inference only: the model was switched to training mode')
         B, Tc = eye_input(chunk).shape[:2]
@@ -515,6 +672,7 @@ class EVEStream(object):
             eye_mask = self._eye_mask(eye_mask, Tc)
         if render is not None:
             render = self._render_plan(chunk, render)
+        self._check_calibration(chunk, B, Tc)
         if ragged:
             self._upload_lengths(lengths)
         if masked and has_pose_form(chunk):
@@ -557,7 +715,7 @@ class EVEStream(object):
     def _graph_key(self, chunk, return_heatmaps, ragged=False, masked=False, render=None):
         """What a captured graph is good for: the step's mode, both YUV matrices, both surface layouts (by value), the overlay
         (render: None or a _render_plan -- its OverlaySpec by value), with a face-landmark form eye_net.face_huber_px (a launch
-        argument, so baked in), and every chunk tensor's key, shape and dtype -- which of the two landmark keys among them."""
+        argument, so baked in), whether a calibration is applied (`calibrated`; a collecting step differs by its chunk keys), and every chunk tensor's key, shape and dtype -- which of the two landmark keys among them."""
         ref = self.model.refine_net
         spec = None if render is None else render['spec'].key()
         layouts = (self.model.eye_net.camera_layout, None if ref is None else ref.screen_layout)
@@ -565,7 +723,8 @@ class EVEStream(object):
         if face_landmarks_key(chunk) is not None:      # (checked here too: a value that is refused never becomes a key)
             from .data import check_huber_px
             huber = check_huber_px(self.model.eye_net.face_huber_px, 'face_huber_px')
-        return (return_heatmaps, ragged, masked, self.model.eye_net.yuv_matrix, None if ref is None else ref.yuv_matrix, spec, layouts, huber) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
+        return (return_heatmaps, ragged, masked, self.model.eye_net.yuv_matrix, None if ref is None else ref.yuv_matrix, spec, layouts, huber,
+                self._calib_apply) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
 
     def _graph_for(self, chunk, return_heatmaps, ragged=False, masked=False, render=None):
         wk = self._weights_key()
@@ -593,7 +752,9 @@ class EVEStream(object):
             side = _WARMUP_STREAMS[dev_index] = torch.cuda.Stream(device=dev_index)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            carried = self._state_tensors() + [self._face_pose]
+            # the calibration store, its counters and the kappa rows too: the warm-up steps of a collecting graph would otherwise
+            # append every sample three times
+            carried = self._state_tensors() + [self._face_pose, self._calib_kappa, self._calib_ok] + list(self._calib_store or ())
             snap = [t.clone() for t in carried]
             for _ in range(2):
                 self._run(static, return_heatmaps, ragged, eye_mask, masked, render)

@@ -1096,6 +1096,64 @@ int eve_face_pose_solve_ex(long long S, int T, int L, int landmark_cols, const f
                            double* state /* may be NULL */, const int* reset /* may be NULL */, float* head_R, float* head_t,
                            float* reproj_rms, uint8_t* valid, uint8_t* inliers, eve_stream_t stream);
 
+/* Per-person gaze calibration: the constant offset kappa = (pitch, yaw) of a person's visual axis against the optical axis EyeNet
+ * sees, in the offset model eve_gaze_to_pog applies when it is given a kappa row.  Two launches: collect, fit.  Float64, every
+ * operation rounded on its own (no contraction); tests/calib_ref.py restates both in numpy.
+ *
+ * eve_calib_append: B streams x T frames x E eyes (E = 1, or 2 = left, right).  One THREAD per sequence q = b*E + e walks frames
+ * f = 0 .. T-1 in order (n = b*T + f), reduces every usable frame to a row of 16 doubles and appends it to the sequence's store:
+ *   g [E][B*T][2], origin [E][B*T][3], R [E][B*T][9] float, eye-major; head_R [B*T][9], inv_cam [B*T][16], ppm [B*T][2], target
+ *   [B*T][2] float (the target in screen pixels), shared by the eyes.  valid [B*T] uint8, lengths [B] int (clamped to 0 .. T),
+ *   eye_valid [B*T][E] uint8: each may be NULL (all frames, T frames, both eyes).
+ *   samples [B*E][C][16] double, count [B*E] int, dropped [B*E] int: read and UPDATED IN PLACE.
+ * The row, inputs widened to double first: (p, y) = g; v = (cos p sin y, sin p, cos p cos y); u = Rh^T v, each entry
+ * (a*b + c*d) + e*f, divided by sqrt((u0*u0 + u1*u1) + u2*u2); c0 = sqrt(ux*ux + uz*uz), s0 = uy, s1 = ux / c0, c1 = uz / c0;
+ * Q = Ry Rx = [[c1, -(s1*s0), s1*c0], [0, c0, s0], [-s1, -(c1*s0), c1*c0]] (the rotation eve_gaze_to_pog applies to the kappa
+ * vector); M = T3 (R^T (Rh Q)), T3 the upper-left 3 x 3 of inv_cam, every 3 x 3 product entry (a0*b0 + a1*b1) + a2*b2, the
+ * products taken in the order the brackets show; A = -M; e_i = ((T_i0*o0 + T_i1*o1) + T_i2*o2) + T_i3; m = target / ppm.
+ *   row = A (9, row-major), e (3), m (2), 1.0 (the weight), 0.0 (reserved)
+ * With k(kappa) = (cos kp sin ky, sin kp, cos kp cos ky) and d = A k the modelled point of gaze in millimetres is
+ * (e0 - e2*d0/d2, e1 - e2*d1/d2): what eve_gaze_to_pog computes with that kappa, without its 1e-7 guards and its screen clamp.
+ * A frame is usable iff valid[n], f < lengths[b], eye_valid[n][e], every input and every entry of the row is finite, c0 > 0 and
+ * -e2 / A[8] > 0 (the target lies in front of the eye at kappa = 0).  A usable frame goes to row count[q] and count[q] grows; with
+ * count[q] == C the sample is dropped and dropped[q] grows.  No atomics: the store is a deterministic function of the calls.
+ * Kernel name calib_append_kernel.  Refused without a launch: a null pointer, B, T or C < 1, E other than 1 or 2, index ranges past
+ * 31 bits.
+ *
+ * eve_calib_fit: S sequences, one wavefront each: Levenberg-Marquardt on kappa from (0, 0), always, over rows 0 .. n-1 of
+ * samples [S][C][16], n = count[q] clamped to 0 .. C (count NULL: C).  A row whose weight w (entry 14) is not > 0 is absent.
+ *   eval(kappa): k as above, a = dk/dkp = (-(sin kp sin ky), cos kp, -(sin kp cos ky)), (b0, b2) = (cos kp cos ky, -(cos kp sin ky))
+ *   (dk/dky; its middle entry is 0).  Per row: d_j = (A_j0*k0 + A_j1*k1) + A_j2*k2, dp_j the same with a, dy_j = A_j0*b0 + A_j2*b2;
+ *   z2 = d2*d2; rx = (e0 - e2*(d0/d2)) - m0, ry = (e1 - e2*(d1/d2)) - m1; Jxp = -(e2*((dp0*d2 - d0*dp2)/z2)), Jxy the same with dy,
+ *   Jyp, Jyy with index 1 for 0; r2 = rx*rx + ry*ry.  Without a loss ws = w, cost = w*r2, inl = 1.  With huber_mm = h > 0:
+ *   r = sqrt(r2), inlier iff not r > h, ws = w*(inlier ? 1 : h/r), cost = w*(inlier ? r2 : h*((r + r) - h)), inl = inlier.
+ *   The 9 contributions: ws*(Jxp*Jxp + Jyp*Jyp), ws*(Jxp*Jxy + Jyp*Jyy), ws*(Jxy*Jxy + Jyy*Jyy), ws*(Jxp*rx + Jyp*ry),
+ *   ws*(Jxy*rx + Jyy*ry), cost, w*r2, inl, 1.0.
+ *   SUMMATION ORDER: lane l starts 9 partial sums at 0.0 and adds its rows l, l + 64, l + 128, ... in that order; then column j is
+ *   summed from 0.0 over the partial sums of lanes 0, 1, .. 63 in that order.  -> S[0..8], the same bits in every lane; nothing
+ *   depends on timing, so two launches on one store give the same bits.
+ *   used = S[8].  Fails at once when used < min_samples or the first cost is not finite.  lam = 1e-3; then, at most 64 evaluations
+ *   in all: factor [[S0 + lam*S0, S1], [S1, S2 + lam*S2]] by Cholesky (l00 = sqrt(m00), l10 = m01/l00, s = m11 - l10*l10, l11 =
+ *   sqrt(s); fails unless m00 > 0 and s > 0), y0 = -S3/l00, y1 = (-S4 - l10*y0)/l11, d1 = y1/l11, d0 = (y0 - l10*d1)/l00;
+ *   small = d finite and max(|d0|, |d1|) <= 1e-12; evaluate at kappa + d; if d is finite and its cost <= the current cost: accept,
+ *   lam /= 10, converged if small, failed at the 32nd accepted step otherwise; else converged if small; else lam *= 10, failed
+ *   when lam > 1e12.  After convergence the undamped matrix must factor with m00 > 0 and s > 1e-10*m11, and sqrt(kp*kp + ky*ky)
+ *   must not exceed 0.35 rad (20 degrees, four times any physiological offset: a divergence guard).
+ * Outputs per sequence: kappa [S][2] double, rms_mm [S] double = sqrt(S6 / S8), used [S] int, inliers [S] int = S7, ok [S] uint8.
+ * Where ok is 0, kappa, rms_mm and inliers are 0 and used is still reported.  select [S] uint8 or NULL: a sequence with select[q]
+ * == 0 is not fitted (ok = 0, used = 0).  kappa_store [S][2] float and ok_store [S] uint8 (both or neither): where ok, and only
+ * there, kappa_store[q] = (float)kappa and ok_store[q] = 1 -- a failed fit leaves what that eye had.  A stream counts as
+ * calibrated where the flags of both its eyes are set.  Kernel name calib_fit_kernel.  Refused without a launch: a null pointer,
+ * S or C < 1, min_samples < 1, a NaN huber_mm, one store without the other.  Not offered: per-sample weights (entry 14 is 1.0, or
+ * 0.0 for an absent row), screen-space polynomial calibration, a gradient.  (Additive: ABI v10.)                                 */
+int eve_calib_append(long long B, int T, int E, const float* g, const float* head_R, const float* origin, const float* R,
+                     const float* inv_cam, const float* ppm, const float* target, const uint8_t* valid /* may be NULL */,
+                     const int* lengths /* may be NULL */, const uint8_t* eye_valid /* may be NULL */, int C, double* samples, int* count,
+                     int* dropped, eve_stream_t stream);
+int eve_calib_fit(long long S, int C, const double* samples, const int* count /* may be NULL */, const uint8_t* select /* may be NULL */,
+                  double huber_mm, int min_samples, double* kappa, double* rms_mm, int* used, int* inliers, uint8_t* ok,
+                  float* kappa_store /* may be NULL */, uint8_t* ok_store /* may be NULL */, eve_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
