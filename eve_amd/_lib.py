@@ -198,6 +198,7 @@ SIGNATURES = {
     'eve_undistort_points': [L, P, P, L, P, P, P],
     'eve_calib_append': [L, I, I, P, P, P, P, P, P, P, P, P, P, I, P, P, P, P],
     'eve_calib_fit': [L, I, P, P, P, ctypes.c_double, I, P, P, P, P, P, P, P, P],
+    'eve_gaze_events': [L, I, P, P, P, P, P, P, P, P, P] + [ctypes.c_double] * 4 + [I] + [ctypes.c_double] * 3 + [P, I, P, P, P] + [P] * 8,
 }
 EXPORTS = sorted(list(SIGNATURES) + ['eve_abi_version', 'eve_last_error', 'eve_last_kernel'])
 

@@ -722,6 +722,106 @@ class OverlaySpec(object):
         return [[r_fill, r_out, rgb(fill), rgb(outline)] for _, _, r_fill, r_out, fill, outline in self.markers]
 
 
+GAZE_EVENT_KEYS = ('PoG_px_filtered', 'gaze_velocity', 'gaze_event', 'fixation_id', 'fixation_px', 'fixation_ms', 'fixating')
+GAZE_EVENT_SOURCES = ('PoG_px_initial', 'PoG_px_final')
+
+
+class GazeEventSpec(object):
+    """What EVEStream.step(chunk, events=spec) adds at the end of the step (eve_gaze_events): the point of gaze smoothed by a one-euro
+    filter, the angular gaze velocity, fixation / saccade labels by a velocity threshold (I-VT), the running fixation, and completed
+    fixations in the EVEStream's store.
+      source           'PoG_px_initial', 'PoG_px_final' (needs a RefineNet) or None: PoG_px_final with a RefineNet, else PoG_px_initial
+      fps              frames per second of the streams, for chunks without frame_time (float64 [B, Tc] seconds, which wins when
+                       both are there): frame i since the stream's last reset then has t = i / fps
+      min_cutoff_hz, beta, d_cutoff_hz   the one-euro filter's parameters, on pixels and pixels / second
+      velocity_from    'filtered' (default) or 'raw': the point of gaze behind the velocity
+      saccade_deg_s    above this angular velocity (degrees / second) a frame is a saccade (2), else a fixation (1)
+      min_fixation_s   a fixation counts (`fixating`, the store) once it has lasted this long
+      max_gap_s        two samples further apart than this are not connected: the filter and the fixation start afresh
+    Instances compare and hash by value: the spec is part of a captured graph's key.  Not offered: dispersion (I-DT) or other
+    classifiers, windowed velocity, merging of adjacent fixations and retroactive relabelling, smooth-pursuit and blink classes,
+    per-eye events, gradients, EVE.forward."""
+
+    def __init__(self, source=None, fps=None, min_cutoff_hz=1.0, beta=0.007, d_cutoff_hz=1.0, velocity_from='filtered', saccade_deg_s=30.0,
+                 min_fixation_s=0.06, max_gap_s=0.075):
+        number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and np.isfinite(v)
+        if source is not None and source not in GAZE_EVENT_SOURCES:
+            raise ValueError('GazeEventSpec: source must be None or one of %s, got %r' % (', '.join(GAZE_EVENT_SOURCES), source))
+        if velocity_from not in ('filtered', 'raw'):
+            raise ValueError("GazeEventSpec: velocity_from must be 'filtered' or 'raw', got %r" % (velocity_from,))
+        values = {'min_cutoff_hz': min_cutoff_hz, 'd_cutoff_hz': d_cutoff_hz, 'saccade_deg_s': saccade_deg_s, 'min_fixation_s': min_fixation_s,
+                  'max_gap_s': max_gap_s}
+        if fps is not None:
+            values['fps'] = fps
+        for name, v in values.items():
+            if not number(v) or not v > 0:
+                raise ValueError('GazeEventSpec: %s must be a finite number > 0, got %r' % (name, v))
+        if not number(beta) or beta < 0:
+            raise ValueError('GazeEventSpec: beta must be a finite number >= 0, got %r' % (beta,))
+        self.source, self.velocity_from = source, velocity_from
+        self.fps = None if fps is None else float(fps)
+        self.min_cutoff_hz, self.beta, self.d_cutoff_hz = float(min_cutoff_hz), float(beta), float(d_cutoff_hz)
+        self.saccade_deg_s, self.min_fixation_s, self.max_gap_s = float(saccade_deg_s), float(min_fixation_s), float(max_gap_s)
+
+    def key(self):
+        return (self.source, self.fps, self.min_cutoff_hz, self.beta, self.d_cutoff_hz, self.velocity_from, self.saccade_deg_s,
+                self.min_fixation_s, self.max_gap_s)
+
+    def __eq__(self, other):
+        return isinstance(other, GazeEventSpec) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'GazeEventSpec(source=%r, fps=%r, min_cutoff_hz=%r, beta=%r, d_cutoff_hz=%r, velocity_from=%r, saccade_deg_s=%r, ' \
+               'min_fixation_s=%r, max_gap_s=%r)' % self.key()
+
+
+def gaze_events(pog_px, o, inv_camera_transformation, pixels_per_millimeter, spec, frame_time=None, valid=None, fixation_capacity=256):
+    """The gaze filter and the fixation / saccade events of S recorded streams, stand-alone and from fresh state: pog_px float32
+    [S, T, 2] (actual_screen_size pixels), o [S, T, 3] (the binocular origin), inv_camera_transformation [S, T, 4, 4],
+    pixels_per_millimeter [S, T, 2], device tensors; spec a GazeEventSpec (its source is not looked at); frame_time None (then
+    spec.fps) or float64 [S, T] seconds; valid None or bool / uint8 [S, T].  One eve_gaze_events launch, which also closes the
+    fixations still open at the clip's end.  -> the seven per-frame keys of EVEStream.step(events=...) plus fixations (float64
+    [S, fixation_capacity, 8], rows (id, t_start, t_last, n, cx, cy, rms_px, 0)), fixation_count and fixation_dropped (int32 [S]);
+    the host does not wait.  Not offered: dispersion classifiers, windowed velocity, merging of adjacent fixations, smooth-pursuit
+    and blink classes, per-eye events, gradients."""
+    if not isinstance(spec, GazeEventSpec):
+        raise ValueError('gaze_events: spec must be an eve_amd.GazeEventSpec, got %s' % type(spec).__name__)
+    if not torch.is_tensor(pog_px) or pog_px.dtype != torch.float32 or pog_px.dim() != 3 or pog_px.shape[2] != 2 or pog_px.numel() == 0:
+        raise TypeError('gaze_events: pog_px must be float32 [S, T, 2], got %s %s' % (getattr(pog_px, 'dtype', type(pog_px)),
+                                                                                     tuple(getattr(pog_px, 'shape', ()))))
+    S, T = pog_px.shape[:2]
+    for name, t, shape in (('o', o, (S, T, 3)), ('inv_camera_transformation', inv_camera_transformation, (S, T, 4, 4)),
+                           ('pixels_per_millimeter', pixels_per_millimeter, (S, T, 2))):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != shape:
+            raise TypeError('gaze_events: %s must be float32 %s, got %s %s' % (name, list(shape), getattr(t, 'dtype', type(t)),
+                                                                              tuple(getattr(t, 'shape', ()))))
+    if frame_time is None and spec.fps is None:
+        raise ValueError('gaze_events: frame_time, or a spec with fps')
+    if frame_time is not None and (not torch.is_tensor(frame_time) or frame_time.dtype != torch.float64 or tuple(frame_time.shape) != (S, T)):
+        raise TypeError('gaze_events: frame_time must be float64 [%d, %d] seconds' % (S, T))
+    if valid is not None:
+        if not torch.is_tensor(valid) or valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) != (S, T):
+            raise TypeError('gaze_events: valid must be bool or uint8 [%d, %d]' % (S, T))
+        valid = valid.contiguous()
+        valid = valid.view(torch.uint8) if valid.dtype == torch.bool else valid
+    if isinstance(fixation_capacity, bool) or not isinstance(fixation_capacity, int) or fixation_capacity < 1:
+        raise ValueError('gaze_events: fixation_capacity must be an integer >= 1, got %r' % (fixation_capacity,))
+    dev = pog_px.device
+    state = torch.zeros((S, 32), dtype=torch.float64, device=dev)
+    store = torch.zeros((S, fixation_capacity, 8), dtype=torch.float64, device=dev)
+    count, dropped = torch.zeros((S,), dtype=torch.int32, device=dev), torch.zeros((S,), dtype=torch.int32, device=dev)
+    out = default_kernels().gaze_events(pog_px.contiguous(), o.contiguous(), inv_camera_transformation.contiguous(),
+                                        pixels_per_millimeter.contiguous(), spec, state, store, count, dropped,
+                                        frame_time=None if frame_time is None else frame_time.contiguous(), valid=valid,
+                                        flush=torch.ones((S,), dtype=torch.int32, device=dev))
+    out = dict(out)
+    out.update(fixations=store, fixation_count=count, fixation_dropped=dropped)
+    return out
+
+
 def render_overlay(frames, format='rgb', out_format='nv12', matrix='bt601', markers=None, heat=None, inset=None, frame_valid=None, out=None):
     """The tracking overlay on the device, stand-alone: frames uint8 [N, ...] in `format` ('rgb' | 'bgr' [N, IH, IW, 3 | 4], 'rgba',
     'bgra', 'nv12' | 'i420' [N, IH*3/2, IW], 'yuyv' [N, IH, IW, 2]) -> the annotated frames, uint8 [N, IH, IW, 3] for out_format 'rgb' |

@@ -343,7 +343,7 @@ class EVE(nn.Module):
                        'PoG_cm_initial', 'g_final', 'PoG_px_final', 'PoG_cm_final')
 
     def _predict_sequence(self, d, eye_states, refine_states, reset=None, return_heatmaps=False, lengths=None, masked=False,
-                          eye_mask=None, pose_gate=None, face_state=None, render=None, calibration=None):
+                          eye_mask=None, pose_gate=None, face_state=None, render=None, calibration=None, events=None):
         """The prediction part of forward() for one chunk of an EVEStream: eval only, no labels, no losses.  d: the chunk's
         inputs [B, Tc, ...] (not modified; camera_frame may be any one key of eye_net.EYE_FRAME_KEYS or camera_surface, and the screen any one
         key of refine_net.SCREEN_FRAME_KEYS or screen_surface; the eyes as patches, as camera_frame + {left,right}_eye_warp, or as camera_frame +
@@ -376,7 +376,11 @@ class EVE(nn.Module):
         calibration_target [B, Tc, 2] (and optionally calibration_valid [B, Tc]) in d, one eve_calib_append launch reduces every
         usable (frame, eye) -- calibration_valid, t < lengths[b], eye_valid -- from the network's own angles and appends it.  With
         apply, _pog_block applies the kappa rows where both flags of a stream are set; the result gains <side>_g_initial_raw and
-        calibrated, bool [B].  None issues no launch."""
+        calibrated, bool [B].  None issues no launch.
+        events: None, or EVEStream's gaze filter and fixation / saccade stage {'spec': a data.GazeEventSpec, 'source': the result key
+        it filters, 'state': float64 [B, 32], 'store': float64 [B, F, 8], 'count', 'dropped': int32 [B]}: one eve_gaze_events launch,
+        last before the render hook, over the step's own source PoG and d['o'], with frame_time from d when it is there, the step's
+        lengths, `valid` (masked) and reset flags; the result gains data.GAZE_EVENT_KEYS.  None issues no launch."""
         assert not self.training, 'EVE._predict_sequence is eval-only'
         B = eye_input(d).shape[0]
         posed, faced = has_pose_form(d), face_landmarks_key(d) is not None
@@ -427,6 +431,14 @@ class EVE(nn.Module):
             out['valid'], out['eye_valid'] = plan['valid'].view(torch.bool), eye_valid
         if return_heatmaps and 'heatmap_final' in inter:
             out['heatmap_final'] = inter['heatmap_final']
+        if events is not None:
+            T = eye_input(d).shape[1]
+            f32 = lambda t, *s_: t.reshape((B, T) + s_).float().contiguous()
+            out.update(default_kernels().gaze_events(
+                f32(inter[events['source']], 2), f32(d['o'], 3), f32(d['inv_camera_transformation'], 4, 4), f32(d['pixels_per_millimeter'], 2),
+                events['spec'], events['state'], events['store'], events['count'], events['dropped'],
+                frame_time=d['frame_time'].contiguous() if 'frame_time' in d else None, valid=None if plan is None else plan['valid'],
+                lengths=None if lengths is None else lengths[:B], reset=None if reset is None else reset[:B]))
         if render is not None:
             render(d, inter, out)
         return out

@@ -966,6 +966,68 @@ class HipKernels(object):
                                         self._p(kappa_store), self._p(ok_store), self._stream()))
         return kappa, rms, used, inliers, good
 
+    # ------------------------------------------------------------------ gaze filtering, fixation / saccade events
+    GAZE_EVENT_KEYS = ('PoG_px_filtered', 'gaze_velocity', 'gaze_event', 'fixation_id', 'fixation_px', 'fixation_ms', 'fixating')
+
+    def gaze_events(self, pog, origin, inv_cam, ppm, spec, state, store, count, dropped, frame_time=None, valid=None, lengths=None,
+                    reset=None, flush=None):
+        """The one-euro filter, the angular gaze velocity, the I-VT labels and the running fixation of B streams x T frames: pog
+        [B, T, 2], origin [B, T, 3], inv_cam [B, T, 4, 4], ppm [B, T, 2] float32; spec an eve_amd.GazeEventSpec (its numbers are the
+        launch's scalars); state float64 [B, 32], store float64 [B, F, 8], count and dropped int32 [B], UPDATED IN PLACE; frame_time
+        float64 [B, T], valid uint8 [B, T], lengths, reset and flush int32 [B], or None.  -> a dict of GAZE_EVENT_KEYS.  pog None
+        (then origin, inv_cam, ppm, frame_time and valid are None too): T = 0, a launch that only resets and flushes, -> {}
+        (include/eve_hip.h eve_gaze_events)."""
+        ok = lambda t, dtype: torch.is_tensor(t) and t.dtype == dtype
+        if not ok(state, torch.float64) or state.dim() != 2 or state.shape[1] != 32 or state.shape[0] < 1:
+            raise TypeError('gaze_events: state must be float64 [B, 32], got %s %s' % (getattr(state, 'dtype', type(state)),
+                                                                                      tuple(getattr(state, 'shape', ()))))
+        B = state.shape[0]
+        if not ok(store, torch.float64) or store.dim() != 3 or store.shape[0] != B or store.shape[1] < 1 or store.shape[2] != 8:
+            raise TypeError('gaze_events: store must be float64 [%d, F, 8], got %s %s' % (B, getattr(store, 'dtype', type(store)),
+                                                                                         tuple(getattr(store, 'shape', ()))))
+        F = store.shape[1]
+        T = 0
+        if pog is not None:
+            if not ok(pog, torch.float32) or pog.dim() != 3 or pog.shape[0] != B or pog.shape[1] < 1 or pog.shape[2] != 2:
+                raise TypeError('gaze_events: pog must be float32 [%d, T, 2], got %s %s' % (B, getattr(pog, 'dtype', type(pog)),
+                                                                                           tuple(getattr(pog, 'shape', ()))))
+            T = pog.shape[1]
+        checks = [('count', count, torch.int32, (B,), True), ('dropped', dropped, torch.int32, (B,), True),
+                  ('lengths', lengths, torch.int32, (B,), False), ('reset', reset, torch.int32, (B,), False),
+                  ('flush', flush, torch.int32, (B,), False)]
+        if T:
+            checks += [('origin', origin, torch.float32, (B, T, 3), True), ('inv_cam', inv_cam, torch.float32, (B, T, 4, 4), True),
+                       ('ppm', ppm, torch.float32, (B, T, 2), True), ('frame_time', frame_time, torch.float64, (B, T), False),
+                       ('valid', valid, torch.uint8, (B, T), False)]
+        elif any(t is not None for t in (origin, inv_cam, ppm, frame_time, valid)):
+            raise TypeError('gaze_events: without pog (T = 0) there are no frame inputs')
+        tensors = [state, store] + ([pog] if T else [])
+        for name, t, dtype, shape, needed in checks:
+            if (t is not None or needed) and (not ok(t, dtype) or tuple(t.shape) != shape):
+                raise TypeError('gaze_events: %s must be %s %s, got %s %s' % (
+                    name, str(dtype).replace('torch.', ''), list(shape), getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ()))))
+            if t is not None:
+                tensors.append(t)
+        if not all(t.is_contiguous() for t in tensors):
+            raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        if T and frame_time is None and spec.fps is None:
+            raise ValueError('gaze_events: without frame_time the spec needs fps')
+        dev = state.device
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+        out = {}
+        if T:
+            out = {'PoG_px_filtered': new((B, T, 2), torch.float32), 'gaze_velocity': new((B, T), torch.float32),
+                   'gaze_event': new((B, T), torch.uint8), 'fixation_id': new((B, T), torch.int32),
+                   'fixation_px': new((B, T, 2), torch.float32), 'fixation_ms': new((B, T), torch.float32),
+                   'fixating': new((B, T), torch.uint8)}
+        self._ck(self.lib.eve_gaze_events(
+            B, T, self._p(pog), self._p(origin), self._p(inv_cam), self._p(ppm), self._p(frame_time), self._p(valid), self._p(lengths),
+            self._p(reset), self._p(flush), 0.0 if spec.fps is None else float(spec.fps), float(spec.min_cutoff_hz), float(spec.beta),
+            float(spec.d_cutoff_hz), 1 if spec.velocity_from == 'raw' else 0, float(spec.saccade_deg_s), float(spec.min_fixation_s),
+            float(spec.max_gap_s), self._p(state), F, self._p(store), self._p(count), self._p(dropped),
+            *([self._p(out[k_]) for k_ in self.GAZE_EVENT_KEYS] if T else [None] * 7), self._stream()))
+        return out
+
     # ------------------------------------------------------------------ gaze geometry / heat-maps / soft-argmax
     def _flat32(self, t, shape, what):
         t = t.contiguous()

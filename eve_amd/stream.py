@@ -8,6 +8,8 @@ carried from one call to the next.
     stream.reset([3])                                      # stream 3 starts from zero state at the next step()
     stream.step(dict(chunk, calibration_target=dots))      # collect per-person calibration samples (see "Calibration" below)
     fit = stream.fit_calibration(huber_mm=25.0)            # fit each eye's offset on the device; later steps apply it
+    out = stream.step(chunk, events=eve_amd.GazeEventSpec(fps=60))   # + the filtered PoG, gaze velocity, fixation / saccade events
+    rows = stream.fixations()                              # the completed fixations of every stream (see "Gaze events" below)
     st = stream.get_state(); stream.set_state(st)          # reference layout, e.g. to resume a recording
 
 For any split of a clip into chunks the concatenated outputs equal one eval pass of the whole clip from zero state
@@ -51,6 +53,20 @@ always collected from the raw angles, so collecting while calibrated does not co
 person, not to the clip: reset() touches neither, and get_state() / set_state() do not hold them (get_calibration /
 set_calibration do).  Not offered: screen-space polynomial or affine calibration, per-sample weights from the caller (entry 14
 of a sample is reserved at 1.0), automatic or continuous recalibration, gradients, application in EVE.forward.
+
+Gaze events.  What comes out of the networks is a raw per-frame point of gaze, and every consumer of an eye tracker then smooths
+it, differentiates it and cuts it into fixations and saccades -- on the host that is a sync per chunk and a loop per stream, with
+state that has to survive chunk boundaries, ragged lengths, masked eyes and reset(): what an EVEStream owns.  step(chunk,
+events=eve_amd.GazeEventSpec(...)) adds one eve_gaze_events launch at the end of the step and inside the graph: a one-euro filter
+on the source PoG (PoG_px_filtered), the angular velocity of the gaze vector at the eye between consecutive samples
+(gaze_velocity, degrees / second), a velocity-threshold label per frame (gaze_event: 1 fixation, 2 saccade, 0 none), the running
+fixation (fixation_id, fixation_px, fixation_ms, fixating), and completed fixations appended to a per-stream store on the device
+(float64 [B, fixation_capacity, 8]; fixations(), fixation_counts(), clear_fixations(), flush_fixations()).  The filter's and the
+events' state is a float64 [B, 32] row per stream, carried from step to step like the recurrent states and reset through the same
+device flags (get_event_state / set_event_state; get_state / set_state do not hold it).  Float64 throughout;
+tests/gaze_events_ref.py states the arithmetic.  A step without events issues exactly the launches it always issued.  Not offered:
+dispersion (I-DT) or other classifiers, windowed velocity, merging of adjacent fixations and retroactive relabelling,
+smooth-pursuit and blink classes, per-eye events, gradients, EVE.forward.
 """
 import numpy as np
 import torch
@@ -66,7 +82,7 @@ def _module_key(m):
 
 
 class EVEStream(object):
-    def __init__(self, model, num_streams, use_graph=True, calibration_capacity=1024):
+    def __init__(self, model, num_streams, use_graph=True, calibration_capacity=1024, fixation_capacity=256):
         if model.training:
             raise ValueError('EVEStream runs inference only: call model.eval() first')
         self.model = model
@@ -98,6 +114,13 @@ class EVEStream(object):
         self._calib_kappa = torch.zeros((B, 2, 2), dtype=torch.float32, device=self.device)
         self._calib_ok = torch.zeros((B, 2), dtype=torch.uint8, device=self.device)
         self._calib_apply = False
+        # gaze events (step(chunk, events=spec)): the filter's and the running fixation's state row per stream, the store of completed
+        # fixations and its counters -- eve_gaze_events reads and writes them inside the step (and the graph)
+        if isinstance(fixation_capacity, bool) or not isinstance(fixation_capacity, int) or fixation_capacity < 1:
+            raise ValueError('fixation_capacity must be an integer >= 1, got %r' % (fixation_capacity,))
+        self.fixation_capacity = fixation_capacity
+        self._events = None                      # made at the first events step or fixation call: (state, store, count, dropped)
+        self._events_spec = None                 # the spec of the last events step: what closes a fixation outside a step
         self._graphs = {}
         self._graphs_key = None
         self._render_tables = {}                 # OverlaySpec.key() -> its marker table, int32 [M, 4] on the device
@@ -108,7 +131,9 @@ class EVEStream(object):
 
     def reset(self, streams=None):
         """Start the given streams (None = all; else indices, or a bool mask of length num_streams) from zero state at the
-        next step().  Resets requested before one step accumulate.  The per-person calibration -- each eye's kappa and the
+        next step().  Resets requested before one step accumulate.  A stream that has run gaze events (step(events=...)) closes its
+        open fixation into the store -- if it lasted min_fixation_s -- and starts its filter, its events and its frame count afresh,
+        by the same device flags; only its fixation id counter runs on, so ids stay unique within a recording.  The per-person calibration -- each eye's kappa and the
         sample store -- is not touched: it belongs to the person, not to the clip (clear_calibration,
         clear_calibration_samples)."""
         m = np.zeros(self.num_streams, dtype=bool) if self._pending is None else self._pending
@@ -216,6 +241,97 @@ class EVEStream(object):
         """The sample store itself, float64 [B, 2, C, 16] (fresh): rows 0 .. count - 1 of (stream, eye) in the order the frames
         came, in the layout of data.calibration_samples / data.fit_gaze_offset."""
         return self._store()[0].clone()
+
+    # ------------------------------------------------------------------ gaze events
+    def _event_buffers(self):
+        if self._events is None:
+            B, F = self.num_streams, self.fixation_capacity
+            self._events = (torch.zeros((B, 32), dtype=torch.float64, device=self.device),
+                            torch.zeros((B, F, 8), dtype=torch.float64, device=self.device),
+                            torch.zeros((B,), dtype=torch.int32, device=self.device), torch.zeros((B,), dtype=torch.int32, device=self.device))
+        return self._events
+
+    def _closing_spec(self):
+        from .data import GazeEventSpec
+        return self._events_spec if self._events_spec is not None else GazeEventSpec()
+
+    def fixations(self, streams=None, include_open=False):
+        """The completed fixations of the given streams (None = all; indices or a bool mask), one numpy float64 [n, 8] array per
+        stream in index order, rows (id, t_start, t_last, n samples, centroid x, centroid y, rms_px, 0) in the order they closed;
+        times in the clock of the steps (frame_time, or frames / fps since the stream's last reset), pixels of the source PoG.  This
+        call waits for the device.  include_open appends the fixation still running, as it stands, where it has lasted the last
+        events step's min_fixation_s."""
+        m = self._stream_mask(streams, 'fixations')
+        state, store, count, _ = (t.cpu().numpy() for t in self._event_buffers())
+        min_fix = self._closing_spec().min_fixation_s
+        out = []
+        for b in np.flatnonzero(m):
+            rows = store[b, :min(max(int(count[b]), 0), self.fixation_capacity)].copy()
+            r = state[b]
+            if include_open and r[12] != 0 and r[22] - r[21] >= min_fix:
+                n, mx, my = r[17], r[18] / r[17], r[19] / r[17]
+                var = r[20] / n - (mx * mx + my * my)
+                rows = np.concatenate([rows, np.array([[r[13], r[21], r[22], n, r[15] + mx, r[16] + my, np.sqrt(var) if var > 0 else 0.0, 0.0]])])
+            out.append(rows)
+        return out
+
+    def fixation_counts(self):
+        """-> (count, dropped), int32 [B] device tensors (fresh): the completed fixations each stream's store holds, and those a
+        full store (fixation_capacity) turned away."""
+        _, _, count, dropped = self._event_buffers()
+        return count.clone(), dropped.clone()
+
+    def clear_fixations(self, streams=None):
+        """Empty the fixation store of the given streams (None = all) and their dropped counters.  The running fixation and the
+        filter are state, not store: reset() ends them."""
+        m = self._device_mask(streams, 'clear_fixations')
+        _, _, count, dropped = self._event_buffers()
+        count.copy_(torch.where(m, torch.zeros_like(count), count))
+        dropped.copy_(torch.where(m, torch.zeros_like(dropped), dropped))
+
+    def flush_fixations(self, streams=None):
+        """Close the open fixations of the given streams (None = all) on the device, as the end of a recording does: one
+        eve_gaze_events launch with no frames.  A fixation that has lasted the last events step's min_fixation_s goes to the store."""
+        flush = self._device_mask(streams, 'flush_fixations').to(torch.int32)
+        state, store, count, dropped = self._event_buffers()
+        default_kernels().gaze_events(None, None, None, None, self._closing_spec(), state, store, count, dropped, flush=flush)
+
+    def get_event_state(self):
+        """The gaze events' carried state, float64 [B, 32] (fresh; include/eve_hip.h eve_gaze_events has the layout): the filter, the
+        last sample, the running fixation, the frame and id counters.  Resets not yet applied by a step are not reflected.
+        get_state() / set_state() do not hold it."""
+        return self._event_buffers()[0].clone()
+
+    def set_event_state(self, state):
+        """Load a state in get_event_state()'s layout, [B, 32] (converted to float64)."""
+        state = torch.as_tensor(state, dtype=torch.float64).to(self.device)
+        if tuple(state.shape) != (self.num_streams, 32):
+            raise ValueError('set_event_state: state must be [%d, 32], got %s' % (self.num_streams, tuple(state.shape)))
+        self._event_buffers()[0].copy_(state)
+
+    def _check_events(self, chunk, spec, B, Tc):
+        """step()'s `events` checked against the chunk and the model -> what _predict_sequence needs beside the buffers.  Every
+        refusal is a ValueError raised before anything is launched or captured."""
+        from .data import GazeEventSpec
+        if not isinstance(spec, GazeEventSpec):
+            raise ValueError('step: events must be an eve_amd.GazeEventSpec, got %s' % type(spec).__name__)
+        has_ref = self.model.refine_net is not None
+        source = spec.source if spec.source is not None else ('PoG_px_final' if has_ref else 'PoG_px_initial')
+        if source == 'PoG_px_final' and not has_ref:
+            raise ValueError('step: events filters PoG_px_final, which RefineNet produces, and the model has no RefineNet')
+        for key in ('inv_camera_transformation', 'pixels_per_millimeter'):
+            if key not in chunk:
+                raise ValueError('step: events needs %s in the chunk: the gaze velocity is an angle at the eye' % key)
+        if 'left_o' not in chunk and not has_pose_form(chunk):
+            raise ValueError('step: events needs the eyes\' origins (left_o, right_o, or a pose form) in the chunk')
+        ft = chunk.get('frame_time')
+        if ft is None and spec.fps is None:
+            raise ValueError('step: events needs frame_time in the chunk (float64 [B, Tc] seconds) or a spec with fps')
+        if ft is not None and (not torch.is_tensor(ft) or ft.dtype != torch.float64 or tuple(ft.shape) != (B, Tc) or ft.device != self.device):
+            raise ValueError('step: frame_time must be a float64 [%d, %d] tensor on %s, got %s %s' % (
+                B, Tc, self.device, getattr(ft, 'dtype', type(ft)), tuple(getattr(ft, 'shape', ()))))
+        self._event_buffers()                    # allocated here, before any capture
+        return {'spec': spec, 'source': source}
 
     def get_state(self):
         """The carried states in the reference layout (fresh tensors): {left,right}_eye_rnn_states_<i> [B, H] float32 ((h, c) for
@@ -351,12 +467,15 @@ class EVEStream(object):
             self._pose_gate_host = not skip_invalid_pose
             self._pose_gate.fill_(self._pose_gate_host)              # a device value: the captured graphs read it, the host never waits
 
-    def _run(self, chunk, return_heatmaps, ragged=False, eye_mask=None, masked=False, render=None):
+    def _run(self, chunk, return_heatmaps, ragged=False, eye_mask=None, masked=False, render=None, events=None):
         # render: None or a _render_plan; the keyword reaches _predict_sequence only then, so a step without it calls what it always did
         extra = {} if render is None else {'render': self._render_hook(render, ragged, masked)}
         if self._calib_apply or 'calibration_target' in chunk:       # (neither: the call an uncalibrated EVEStream always made)
             extra['calibration'] = {'kappa': self._calib_kappa, 'ok': self._calib_ok, 'apply': self._calib_apply,
                                     'store': self._store() if 'calibration_target' in chunk else None}
+        if events is not None:                   # events: None or a _check_events plan; the keyword goes along only then
+            state, store, count, dropped = self._event_buffers()
+            extra['events'] = dict(events, state=state, store=store, count=count, dropped=dropped)
         if face_landmarks_key(chunk) is not None:      # the face-landmark form: the carried head pose goes along
             return self.model._predict_sequence(chunk, self._eye, self._ref, reset=self._flags, return_heatmaps=return_heatmaps,
                                                 lengths=self._lengths if ragged else None, masked=masked, eye_mask=eye_mask,
@@ -371,7 +490,7 @@ class EVEStream(object):
                                             lengths=self._lengths, **extra)
 
     # ------------------------------------------------------------------ the overlay (step(chunk, render=spec))
-    def _render_plan(self, chunk, spec):
+    def _render_plan(self, chunk, spec, events=None):
         """step()'s `render` checked against the chunk -> what the launch needs beside the step's own results: the capture's key,
         format and size, the matrix, sx and sy, the marker table on the device, the inset's place.  Every refusal is a ValueError
         raised before anything is launched or captured."""
@@ -408,6 +527,9 @@ class EVEStream(object):
             raise ValueError('step: render uses %s, which RefineNet produces, and the model has no RefineNet' % (
                 'the heat map (heatmap_final)' if spec.heat else 'PoG_px_final'))
         results = tuple(getattr(self.model, 'PREDICTION_KEYS', ())) + ('valid', 'eye_valid', 'pose_valid')
+        if events is not None:                   # the gaze events' keys: dict(key='fixation_px', valid='fixating'), key='PoG_px_filtered'
+            from .data import GAZE_EVENT_KEYS
+            results += GAZE_EVENT_KEYS
         for m in spec.markers:
             for k_ in (m[0], m[1]):
                 if k_ is not None and k_ not in chunk and k_ not in results:
@@ -495,7 +617,7 @@ class EVEStream(object):
             out['rendered'] = rendered.view((B, Tc) + tuple(rendered.shape[1:]))
         return render
 
-    def step(self, chunk, return_heatmaps=False, lengths=None, eye_mask=None, skip_invalid_pose=False, render=None):
+    def step(self, chunk, return_heatmaps=False, lengths=None, eye_mask=None, skip_invalid_pose=False, render=None, events=None):
         """One chunk of every stream: chunk holds [B, Tc, ...] tensors on the model's device -- the eyes (below), {left,right}_h,
         {left,right}_o, {left,right}_R, head_R, camera_transformation, inv_camera_transformation, pixels_per_millimeter, millimeters_per_pixel, and screen_frame when the config loads screen content.  Returns the
         prediction keys of EVE(output_predictions=True) as [B, Tc, ...] tensors (heatmap_final [B, Tc, 1, H, W] on request).
@@ -656,7 +778,32 @@ class EVEStream(object):
         eye_mask, skip_invalid_pose, every camera and screen form and render combine with it.  Needs inv_camera_transformation and
         head_R in the chunk (the pose forms derive head_R): ValueError otherwise, as for calibration_valid without a target.
         Once fit_calibration or set_calibration has been called the step applies the stored offsets (module docstring,
-        "Calibration"): the result gains calibrated [B] and <side>_g_initial_raw, and needs head_R too."""
+        "Calibration"): the result gains calibrated [B] and <side>_g_initial_raw, and needs head_R too.
+
+        events: None, or an eve_amd.GazeEventSpec -- one eve_gaze_events launch at the end of the step (before the overlay) and inside
+        the captured graph post-processes the step's point of gaze (spec.source: PoG_px_final with a RefineNet, else
+        PoG_px_initial) the way every consumer of an eye tracker does, with no host sync and with state carried from step to step
+        like the recurrent states.  The result gains PoG_px_filtered float32 [B, Tc, 2] (a one-euro filter, x and y on their own),
+        gaze_velocity float32 [B, Tc] (degrees / second: the angle at the eye -- the step's binocular origin o -- between the gaze
+        vectors of consecutive samples over their time difference; NaN where there is none), gaze_event uint8 [B, Tc] (0 none, 1
+        fixation, 2 saccade: velocity above spec.saccade_deg_s), fixation_id int32 [B, Tc] (-1 outside a fixation; a counter per
+        stream that reset() leaves running), fixation_px float32 [B, Tc, 2] (the running fixation's centroid of the unfiltered
+        source), fixation_ms float32 [B, Tc] and fixating uint8 [B, Tc] (a fixation that has lasted spec.min_fixation_s).  A frame
+        is a sample iff it was delivered (lengths), is valid (eye_mask, skip_invalid_pose), its PoG, o, inv_camera_transformation and
+        pixels_per_millimeter are finite, the eye is off the screen plane and its time is later than the last sample's; any other
+        frame is event 0 and moves nothing.  Time is the chunk's frame_time, float64 [B, Tc] seconds on the model's device, or
+        frames / spec.fps counted over the delivered frames since the stream's last reset (frame_time wins).  Two samples more
+        than spec.max_gap_s apart are not connected: the open fixation ends at its last sample and the filter restarts (so does the
+        first sample after a reset()).  A fixation that ends -- a saccade, a gap, reset(), flush_fixations() -- after at least
+        min_fixation_s goes to this EVEStream's store (fixation_capacity rows per stream; a full store drops and counts):
+        fixations(), fixation_counts(), clear_fixations(); get_event_state() / set_event_state() hold the carried row.  Needs
+        inv_camera_transformation, pixels_per_millimeter, the origins (or a pose form), and frame_time or spec.fps: ValueError
+        otherwise, as for PoG_px_final without a RefineNet.  The spec by value and frame_time's presence are part of the graph's
+        key; lengths, eye_mask, skip_invalid_pose, every camera and screen form, an applied calibration and render combine with it,
+        and render's markers may name the new keys (dict(key='fixation_px', valid='fixating'), key='PoG_px_filtered').
+        tests/gaze_events_ref.py states the arithmetic.  Not offered: dispersion (I-DT) or other classifiers, windowed velocity,
+        merging of adjacent fixations and retroactive relabelling, smooth-pursuit and blink classes, per-eye events, gradients,
+        EVE.forward.  events=None issues exactly the launches the step always issued."""
         if self.model.training:
             raise ValueError('EVEStream runs inference only: the model was switched to training mode')
         B, Tc = eye_input(chunk).shape[:2]
@@ -670,17 +817,26 @@ class EVEStream(object):
             lengths = self._host_lengths(lengths, Tc)
         if eye_mask is not None:
             eye_mask = self._eye_mask(eye_mask, Tc)
+        if events is not None:
+            events = self._check_events(chunk, events, B, Tc)
         if render is not None:
-            render = self._render_plan(chunk, render)
+            render = self._render_plan(chunk, render) if events is None else self._render_plan(chunk, render, events)
         self._check_calibration(chunk, B, Tc)
         if ragged:
             self._upload_lengths(lengths)
         if masked and has_pose_form(chunk):
             self._set_pose_gate(bool(skip_invalid_pose))
         self._upload_resets()
+        if events is not None:
+            self._events_spec = events['spec']
+        elif self._events is not None and self._flags_set:
+            # a reset before a step without events: the gaze events' state still ends its fixation and starts afresh (no frames)
+            state, store, count, dropped = self._events
+            default_kernels().gaze_events(None, None, None, None, self._closing_spec(), state, store, count, dropped,
+                                          reset=self._flags[:self.num_streams])
         with torch.no_grad():
             if self.use_graph:
-                entry = self._graph_for(chunk, bool(return_heatmaps), ragged, masked, render)
+                entry = self._graph_for(chunk, bool(return_heatmaps), ragged, masked, render, events)
                 for key, buf in entry['inputs'].items():
                     buf.copy_(chunk[key], non_blocking=True)
                 if masked:
@@ -693,7 +849,8 @@ class EVEStream(object):
             else:
                 if eye_mask is not None and eye_mask.device != self.device:
                     eye_mask = torch.empty(eye_mask.shape, dtype=torch.uint8, device=self.device).copy_(eye_mask, non_blocking=True)
-                out = self._run(chunk, return_heatmaps, ragged, eye_mask, masked, render)
+                out = self._run(chunk, return_heatmaps, ragged, eye_mask, masked, render) if events is None else \
+                    self._run(chunk, return_heatmaps, ragged, eye_mask, masked, render, events)
             if ragged and not masked:
                 out['valid'] = torch.arange(Tc, device=self.device)[None, :] < self._lengths[:self.num_streams, None]
         if self._flags_set:
@@ -712,10 +869,11 @@ class EVEStream(object):
     def _weights_key(self):
         return tuple(_module_key(m) for m in (self.model.eye_net, self.model.refine_net) if m is not None)
 
-    def _graph_key(self, chunk, return_heatmaps, ragged=False, masked=False, render=None):
+    def _graph_key(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None):
         """What a captured graph is good for: the step's mode, both YUV matrices, both surface layouts (by value), the overlay
         (render: None or a _render_plan -- its OverlaySpec by value), with a face-landmark form eye_net.face_huber_px (a launch
-        argument, so baked in), whether a calibration is applied (`calibrated`; a collecting step differs by its chunk keys), and every chunk tensor's key, shape and dtype -- which of the two landmark keys among them."""
+        argument, so baked in), the gaze events (events: None or a _check_events plan -- its GazeEventSpec by value and its source;
+        frame_time's presence is a chunk key), whether a calibration is applied (`calibrated`; a collecting step differs by its chunk keys), and every chunk tensor's key, shape and dtype -- which of the two landmark keys among them."""
         ref = self.model.refine_net
         spec = None if render is None else render['spec'].key()
         layouts = (self.model.eye_net.camera_layout, None if ref is None else ref.screen_layout)
@@ -724,21 +882,22 @@ class EVEStream(object):
             from .data import check_huber_px
             huber = check_huber_px(self.model.eye_net.face_huber_px, 'face_huber_px')
         return (return_heatmaps, ragged, masked, self.model.eye_net.yuv_matrix, None if ref is None else ref.yuv_matrix, spec, layouts, huber,
-                self._calib_apply) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
+                self._calib_apply) + (() if events is None else ((events['spec'].key(), events['source']),)) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
 
-    def _graph_for(self, chunk, return_heatmaps, ragged=False, masked=False, render=None):
+    def _graph_for(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None):
         wk = self._weights_key()
         if wk != self._graphs_key:               # new weights: new packs, new graphs (a replay never reads stale packs)
             self._graphs = {}
             self._graphs_key = wk
-        key = self._graph_key(chunk, return_heatmaps, ragged, masked, render)
+        key = self._graph_key(chunk, return_heatmaps, ragged, masked, render, events)
         entry = self._graphs.get(key)
         if entry is None:
-            entry = self._graphs[key] = self._capture(chunk, return_heatmaps, ragged, masked, render)
+            entry = self._graphs[key] = self._capture(chunk, return_heatmaps, ragged, masked, render) if events is None else \
+                self._capture(chunk, return_heatmaps, ragged, masked, render, events)
             self._graphs_key = self._weights_key()
         return entry
 
-    def _capture(self, chunk, return_heatmaps, ragged=False, masked=False, render=None):
+    def _capture(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None):
         """Capture one step for this chunk shape (train.Trainer._capture's recipe): inputs copied into fixed buffers, two eager
         warm-up steps off the default stream (packs, lazily built filters, allocator) with the carried states put back
         afterwards, the kernels' scratch allocated before the capture, one stream, no side branches.  A masked graph has one more
@@ -754,10 +913,12 @@ class EVEStream(object):
         with torch.cuda.stream(side):
             # the calibration store, its counters and the kappa rows too: the warm-up steps of a collecting graph would otherwise
             # append every sample three times
-            carried = self._state_tensors() + [self._face_pose, self._calib_kappa, self._calib_ok] + list(self._calib_store or ())
+            # (and the gaze events' state, store and counters: a capture would otherwise tick the filter three times)
+            carried = self._state_tensors() + [self._face_pose, self._calib_kappa, self._calib_ok] + list(self._calib_store or ()) + \
+                list(self._events or ())
             snap = [t.clone() for t in carried]
             for _ in range(2):
-                self._run(static, return_heatmaps, ragged, eye_mask, masked, render)
+                self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events)
             for t, s_ in zip(carried, snap):
                 t.copy_(s_)
         torch.cuda.current_stream().wait_stream(side)
@@ -767,7 +928,7 @@ class EVEStream(object):
             k.prepare_graph_workspace(self.device)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            out = self._run(static, return_heatmaps, ragged, eye_mask, masked, render)
+            out = self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events)
         m = self.model
         keep = (m.eye_net._packs, getattr(m.eye_net, '_stream_w', None), m.refine_net._packs if m.refine_net is not None else None)
         return {'graph': graph, 'inputs': static, 'outputs': out, 'keep': keep, 'eye_mask': eye_mask}

@@ -1154,6 +1154,53 @@ int eve_calib_fit(long long S, int C, const double* samples, const int* count /*
                   double huber_mm, int min_samples, double* kappa, double* rms_mm, int* used, int* inliers, uint8_t* ok,
                   float* kappa_store /* may be NULL */, uint8_t* ok_store /* may be NULL */, eve_stream_t stream);
 
+/* Gaze filtering and fixation / saccade events: the post-processing every consumer of an eye tracker runs on the per-frame point of
+ * gaze -- a one-euro filter (Casiez et al. 2012), the angular velocity of the gaze vector, velocity-threshold labels (I-VT), the
+ * running fixation and a store of completed fixations -- for B streams x T frames, with the state carried in `state` from one call
+ * to the next.  Float64, every operation rounded on its own (no contraction), in the order written here; tests/gaze_events_ref.py
+ * restates it in numpy.  One wavefront per stream, passes of 64 frames; the bits do not depend on that structure.
+ *   pog [B*T][2] (the source point of gaze, screen pixels), origin [B*T][3], inv_cam [B*T][16], ppm [B*T][2] float;
+ *   frame_time [B*T] double seconds or NULL (then t = ticks / fps); valid [B*T] uint8, lengths [B] int (clamped to 0 .. T), reset [B]
+ *   int, flush [B] int: each may be NULL (all frames, T frames, no reset, no flush).
+ *   state [B][32] double, store [B][F][8] double, count [B] and dropped [B] int: read and UPDATED IN PLACE.
+ * The state row: 0 ticks (the delivered frames since the last reset), 1 has_prev, 2 t_prev (the last sample's time), 3-4 its raw
+ * (x, y), 5-6 its filtered (x, y), 7-8 the filtered derivative (px/s), 9-11 its gaze vector, 12 fix_open, 13 the open fixation's id,
+ * 14 next_id (the ids handed out so far), 15-16 the open fixation's first sample (x0, y0), 17 n, 18 sum(x - x0), 19 sum(y - y0),
+ * 20 sum((x - x0)^2 + (y - y0)^2), 21 t_start, 22 t_last, 23-31 reserved (0).
+ * A stream with reset[b] != 0 first closes its open fixation (below) and zeroes its row except entry 14.  Then frames f = 0 ..
+ * lengths[b] - 1 are walked in order.  t = frame_time[b][f], or (ticks + f) / fps.  With (x, y) = pog, (sx, sy) = ppm widened to double
+ * and e_i = ((T_i0*o0 + T_i1*o1) + T_i2*o2) + T_i3 the frame is a SAMPLE iff valid[b][f], t, x, y, sx, sy, o and all 16 entries of
+ * inv_cam are finite, e_2 != 0, and (has_prev == 0 or t > t_prev).  Any other frame changes nothing: event 0, id -1, velocity NaN,
+ * PoG_px_filtered = pog as it came, the rest 0 (so do the frames from lengths[b] on).  For a sample, dt = t - t_prev and
+ *   restart = has_prev == 0 or dt > max_gap_s: the filtered value is (x, y) itself, the derivative 0, no velocity (NaN), event 0, and
+ *   the open fixation is closed;
+ *   otherwise, with alpha(fc) = 1 / (1 + (1 / (6.283185307179586*fc)) / dt): ad = alpha(d_cutoff_hz); dxh = ad*((x - x_prev)/dt) +
+ *   (1 - ad)*dxh_prev (x_prev the previous sample's RAW x, as in the authors' implementation); ax = alpha(min_cutoff_hz +
+ *   beta*fabs(dxh)); xh = ax*x + (1 - ax)*xh_prev; y alike and on its own.
+ *   v = (p_x/sx - e_0, p_y/sy - e_1, -e_2) with p the filtered point, or the raw one with velocity_from_raw; the state takes t, (x, y),
+ *   (xh, yh), (dxh, dyh) and v.  Unless restart: c = v_prev x v (c0 = p1*v2 - p2*v1, ...), angle = atan2(sqrt((c0*c0 + c1*c1) + c2*c2),
+ *   (p0*v0 + p1*v1) + p2*v2), velocity = angle * 57.29577951308232 / dt (deg/s).  velocity > saccade_deg_s: event 2, and the open
+ *   fixation is closed (at its previous sample).  Otherwise event 1: where none is open one opens -- id = next_id, next_id += 1, (x0, y0)
+ *   = the raw (x, y), the sums 0, t_start = t -- and then n += 1, the three sums take dx = x - x0 and dy = y - y0 (the third dx*dx +
+ *   dy*dy), t_last = t; fixation_id = id, fixation_px = (x0 + sdx/n, y0 + sdy/n), fixation_ms = 1000*(t - t_start), fixating = t -
+ *   t_start >= min_fixation_s.
+ * Closing: fix_open = 0, and where t_last - t_start >= min_fixation_s the row (id, t_start, t_last, n, x0 + mx, y0 + my, rms_px, 0.0),
+ * mx = sdx/n, my = sdy/n, rms_px = sqrt of sd2/n - (mx*mx + my*my) where that is > 0, else 0, goes to store[b][count[b]] and count[b]
+ * grows; with count[b] == F it is dropped and dropped[b] grows.  After the frames ticks += lengths[b], and a stream with flush[b] != 0
+ * closes its open fixation.  T = 0 is a call that only resets and flushes (the frame pointers may then be NULL).
+ * Outputs per frame, float values rounded from double once: filtered [B*T][2] float, velocity [B*T] float, event [B*T] uint8,
+ * fixation_id [B*T] int, fixation_px [B*T][2] float, fixation_ms [B*T] float, fixating [B*T] uint8.  Kernel name gaze_events_kernel.
+ * Refused without a launch: a null state, store or counter, with T > 0 a null frame input or output, B or F < 1, T < 0, index ranges
+ * past 31 bits, fps not a finite number > 0 where frame_time is NULL and T > 0, a cutoff, threshold or time that is not a finite
+ * number > 0, a beta that is not a finite number >= 0.  Not offered: dispersion (I-DT) classifiers, windowed velocity, merging of
+ * adjacent fixations, smooth-pursuit and blink classes, per-eye events, a gradient.  (Additive: ABI v10.)                        */
+int eve_gaze_events(long long B, int T, const float* pog, const float* origin, const float* inv_cam, const float* ppm,
+                    const double* frame_time /* may be NULL */, const uint8_t* valid /* may be NULL */, const int* lengths /* may be NULL */,
+                    const int* reset /* may be NULL */, const int* flush /* may be NULL */, double fps, double min_cutoff_hz, double beta,
+                    double d_cutoff_hz, int velocity_from_raw, double saccade_deg_s, double min_fixation_s, double max_gap_s, double* state,
+                    int F, double* store, int* count, int* dropped, float* filtered, float* velocity, uint8_t* event, int* fixation_id,
+                    float* fixation_px, float* fixation_ms, uint8_t* fixating, eve_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

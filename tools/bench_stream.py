@@ -3,7 +3,7 @@
 CLSTM RefineNet), synthetic weights and clips.  One JSON line per shape:
 
     python tools/bench_stream.py --shapes 1x1 32x1 32x30 [--dtype bf16] [--steps 50] [--fused-tail] [--ragged | --masked] [--repeat N]
-                                 [--screen 1920x1080 [--screen-format nv12] [--render]]
+                                 [--screen 1920x1080 [--screen-format nv12] [--render]] [--events]
 
 B x Tc = streams x frames per step.  For Tc > 1 the same clips also go through one EVE.eval() pass (`eval_ms`): what the
 stream costs over the plain clip pass.  --fused-tail runs the EyeNet tail as one eve_eye_tail_stream_fwd launch
@@ -18,7 +18,11 @@ then holds the area resize (eve_screen_u8_area_to_nchw) and the copy of the capt
 --screen-format nv12 | i420 | yuyv the captures go in as a decoder delivers them, under screen_frame_<format> (eve_screen_area_fmt_to_nchw;
 `screen_bytes` is what one step copies into the graph for the screen).  --render (with --screen) steps with render=OverlaySpec(heat=True):
 the default two markers, the heat map and the eyes inset drawn onto the capture by one eve_overlay_render launch inside the graph, NV12
-out (`rendered_bytes` per step); the A/B of the overlay is the same command line without it.  --repeat N measures every shape N times in one process (`step_ms_runs`; `step_ms` is their median): the run-to-run spread."""
+out (`rendered_bytes` per step); the A/B of the overlay is the same command line without it.  --events steps with
+events=GazeEventSpec(fps=30): the one-euro filter, the gaze velocity and the fixation / saccade events by one eve_gaze_events launch
+at the end of the graph.  The line then also holds `plain_step_ms`, the same step without events in the same process (windows of the
+two alternate, `plain_step_ms_runs` with --repeat), `events_delta_us`, their difference, `events_kernel_us`, the device time per launch
+of a captured chain of 64 eve_gaze_events launches on the step's own PoG_px_final (the kernel alone), and `launch_floor_us`.  --repeat N measures every shape N times in one process (`step_ms_runs`; `step_ms` is their median): the run-to-run spread."""
 import argparse
 import json
 import os
@@ -66,6 +70,33 @@ def launch_floor_us(n=64, reps=50):
     return round(1e3 * device_ms(graph.replay, reps) / n, 3)
 
 
+def events_kernel_us(clip, out, spec, n=64, reps=50):
+    """Device time per launch of a replayed hipGraph of n dependent eve_gaze_events launches on one step's results: every launch
+    carries the state on (the counted time keeps running, the store fills and then drops)."""
+    k = eve_amd.kernels.default_kernels()
+    B, Tc = out['PoG_px_final'].shape[:2]
+    pog = out['PoG_px_final'].float().contiguous().clone()
+    o = torch.stack([clip['left_o'], clip['right_o']], dim=-1).mean(dim=-1).float().contiguous()
+    cam, ppm = clip['inv_camera_transformation'].float().contiguous(), clip['pixels_per_millimeter'].float().contiguous()
+    state = torch.zeros((B, 32), dtype=torch.float64, device='cuda')
+    store = torch.zeros((B, 256, 8), dtype=torch.float64, device='cuda')
+    count, dropped = torch.zeros((B,), dtype=torch.int32, device='cuda'), torch.zeros((B,), dtype=torch.int32, device='cuda')
+    run = lambda: k.gaze_events(pog, o, cam, ppm, spec, state, store, count, dropped)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        run()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for _ in range(n):
+            run()
+    graph.replay()
+    torch.cuda.synchronize()
+    return round(1e3 * device_ms(graph.replay, reps) / n, 3)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--shapes', nargs='+', default=['1x1', '32x1', '32x30'])
@@ -78,6 +109,7 @@ def main():
     ap.add_argument('--screen', default=None, metavar='WxH', help='feed uint8 screen captures of this size, e.g. 1920x1080')
     ap.add_argument('--screen-format', default='rgb', choices=('rgb', 'nv12', 'i420', 'yuyv'), help='the layout of the --screen captures')
     ap.add_argument('--render', action='store_true', help='step with render=OverlaySpec(heat=True): the overlay launch inside the graph')
+    ap.add_argument('--events', action='store_true', help='step with events=GazeEventSpec(fps=30): the gaze filter and the fixation / saccade events')
     args = ap.parse_args()
     if args.screen_format != 'rgb' and not args.screen:
         ap.error('--screen-format needs --screen WxH')
@@ -114,13 +146,29 @@ def main():
         stream = eve_amd.EVEStream(model, B)
         rng = np.random.default_rng(B * 1000 + Tc)
         extra = {'render': eve_amd.OverlaySpec(heat=True)} if args.render else {}
+        plain_extra = dict(extra)
+        if args.events:
+            extra['events'] = eve_amd.GazeEventSpec(fps=30)
         step = (lambda: stream.step(clip, lengths=rng.integers(0, Tc + 1, size=B), **extra)) if args.ragged else (lambda: stream.step(clip, **extra))
         if args.masked:
             step = lambda: stream.step(clip, eye_mask=rng.random((B, Tc, 2)) >= 0.2, **extra)
         for _ in range(3):
             step()                                           # capture + warm replays
         torch.cuda.synchronize()
-        runs = sorted(round(device_ms(step, args.steps), 4) for _ in range(max(1, args.repeat)))
+        plain_runs = []
+        if args.events:                                      # the same step without events, in windows that alternate with the timed ones
+            assert not args.ragged and not args.masked, '--events measures the uniform step'
+            plain_step = lambda: stream.step(clip, **plain_extra)
+            for _ in range(3):
+                plain_step()
+            torch.cuda.synchronize()
+            runs = []
+            for _ in range(max(1, args.repeat)):
+                plain_runs.append(round(device_ms(plain_step, args.steps), 4))
+                runs.append(round(device_ms(step, args.steps), 4))
+            runs, plain_runs = sorted(runs), sorted(plain_runs)
+        else:
+            runs = sorted(round(device_ms(step, args.steps), 4) for _ in range(max(1, args.repeat)))
         res = {'B': B, 'Tc': Tc, 'dtype': args.dtype, 'tail': 'fused' if args.fused_tail else 'layers', 'ragged': args.ragged, 'masked': args.masked,
                'screen': args.screen or 'float', 'step_ms': runs[len(runs) // 2]}
         if screen is not None:
@@ -130,6 +178,13 @@ def main():
         if len(runs) > 1:
             res['step_ms_runs'] = runs
         if args.masked:
+            res['launch_floor_us'] = launch_floor_us()
+        if args.events:
+            res['events'], res['plain_step_ms'] = True, plain_runs[len(plain_runs) // 2]
+            res['events_delta_us'] = round(1e3 * (res['step_ms'] - res['plain_step_ms']), 2)
+            if len(plain_runs) > 1:
+                res['plain_step_ms_runs'] = plain_runs
+            res['events_kernel_us'] = events_kernel_us(clip, {k_: v.clone() for k_, v in step().items()}, extra['events'])
             res['launch_floor_us'] = launch_floor_us()
         res['us_per_frame'] = round(1e3 * res['step_ms'] / (B * Tc), 3)
         if Tc > 1:
