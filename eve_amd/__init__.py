@@ -4,7 +4,7 @@ kernels (libeve_hip.so, C ABI in include/eve_hip.h)."""
 from .config import HotPathConfig, get_config, reset_standalone_config  # noqa: F401
 from .eye_net import EyeNet  # noqa: F401
 
-__all__ = ['EyeNet', 'RefineNet', 'EVE', 'EVEStream', 'OverlaySpec', 'GazeEventSpec', 'SurfaceLayout', 'get_config', 'HotPathConfig', 'reset_standalone_config']
+__all__ = ['EyeNet', 'RefineNet', 'EVE', 'EVEStream', 'OverlaySpec', 'GazeEventSpec', 'EyeGateSpec', 'BlinkSpec', 'SurfaceLayout', 'get_config', 'HotPathConfig', 'reset_standalone_config']
 
 
 def __getattr__(name):
@@ -23,6 +23,12 @@ def __getattr__(name):
     if name == 'GazeEventSpec':
         from .data import GazeEventSpec
         return GazeEventSpec
+    if name == 'EyeGateSpec':
+        from .data import EyeGateSpec
+        return EyeGateSpec
+    if name == 'BlinkSpec':
+        from .data import BlinkSpec
+        return BlinkSpec
     if name == 'SurfaceLayout':
         from .data import SurfaceLayout
         return SurfaceLayout

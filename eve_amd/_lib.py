@@ -38,6 +38,14 @@ class WgradProblem(Structure):
 
 WGRAD_BATCH_MAX = 12
 
+class EyeGateParams(Structure):
+    """include/eve_hip.h eve_eye_gate_params"""
+    _fields_ = [('max_reproj_px', ctypes.c_double), ('pitch_lo', ctypes.c_double), ('pitch_hi', ctypes.c_double),
+                ('yaw_lo', ctypes.c_double * 2), ('yaw_hi', ctypes.c_double * 2), ('close_ratio', ctypes.c_double),
+                ('open_ratio', ctypes.c_double), ('baseline_rate', ctypes.c_double), ('baseline_rise', ctypes.c_double),
+                ('min_inliers', c_int), ('min_inside', c_int), ('hold_frames', c_int), ('max_closed_frames', c_int)]
+
+
 P = c_void_p
 I = c_int
 L = c_longlong
@@ -199,6 +207,7 @@ SIGNATURES = {
     'eve_calib_append': [L, I, I, P, P, P, P, P, P, P, P, P, P, I, P, P, P, P],
     'eve_calib_fit': [L, I, P, P, P, ctypes.c_double, I, P, P, P, P, P, P, P, P],
     'eve_gaze_events': [L, I, P, P, P, P, P, P, P, P, P] + [ctypes.c_double] * 4 + [I] + [ctypes.c_double] * 3 + [P, I, P, P, P] + [P] * 8,
+    'eve_eye_gate': [L, I, P, P, P, P, P, P, I, P, P, I, I, I, I, POINTER(EyeGateParams), P, I, P, P, P, P, P, P, P, P],
 }
 EXPORTS = sorted(list(SIGNATURES) + ['eve_abi_version', 'eve_last_error', 'eve_last_kernel'])
 

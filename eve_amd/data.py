@@ -822,6 +822,170 @@ def gaze_events(pog_px, o, inv_camera_transformation, pixels_per_millimeter, spe
     return out
 
 
+EYE_GATE_KEYS = ('eye_gate_reason', 'eye_openness', 'blink')
+EYE_CONTOURS_KEY = 'eye_contours'
+
+
+def _gate_number(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and not np.isnan(v)
+
+
+class BlinkSpec(object):
+    """The blink detector of an EyeGateSpec, on the eyelid aspect ratio (the mean of the two lid openings over the eye's width, from
+    six eyelid points per eye: the chunk's eye_contours) relative to a baseline that follows the open eye.
+      close_ratio        the eye closes when aspect ratio / baseline falls below this
+      open_ratio         ... and reopens when it rises above this (> close_ratio: a hysteresis)
+      baseline_rate      how fast the baseline follows a falling open-eye ratio, per frame (0 .. 1)
+      baseline_rise      how fast it follows a rising one (0 .. 1): a peak follower, so that a first frame taken in the middle of a
+                         blink does not keep the baseline down
+      hold_frames        frames withheld after a blink, from the reopening frame on (the lid is still moving)
+      max_closed_frames  a closure longer than this is a wrong baseline, not a blink: the baseline starts over, nothing is stored
+    The defaults are conventional -- closing near two thirds of the open ratio, reopening at three quarters, two frames of
+    hold-off, three seconds at 30 frames per second; no recording was available to tune them on.  Compares and hashes by value."""
+
+    def __init__(self, close_ratio=0.65, open_ratio=0.75, baseline_rate=0.02, baseline_rise=0.5, hold_frames=2, max_closed_frames=90):
+        for name, v in (('close_ratio', close_ratio), ('open_ratio', open_ratio)):
+            if not _gate_number(v) or not 0 < v < np.inf:
+                raise ValueError('BlinkSpec: %s must be a finite number > 0, got %r' % (name, v))
+        if not open_ratio > close_ratio:
+            raise ValueError('BlinkSpec: open_ratio must be above close_ratio, got %r and %r' % (open_ratio, close_ratio))
+        for name, v in (('baseline_rate', baseline_rate), ('baseline_rise', baseline_rise)):
+            if not _gate_number(v) or not 0 <= v <= 1:
+                raise ValueError('BlinkSpec: %s must be a number in 0 .. 1, got %r' % (name, v))
+        for name, v, least in (('hold_frames', hold_frames, 0), ('max_closed_frames', max_closed_frames, 1)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not least <= v <= 1 << 20:
+                raise ValueError('BlinkSpec: %s must be an integer in %d .. %d, got %r' % (name, least, 1 << 20, v))
+        self.close_ratio, self.open_ratio = float(close_ratio), float(open_ratio)
+        self.baseline_rate, self.baseline_rise = float(baseline_rate), float(baseline_rise)
+        self.hold_frames, self.max_closed_frames = int(hold_frames), int(max_closed_frames)
+
+    def key(self):
+        return (self.close_ratio, self.open_ratio, self.baseline_rate, self.baseline_rise, self.hold_frames, self.max_closed_frames)
+
+    def __eq__(self, other):
+        return isinstance(other, BlinkSpec) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'BlinkSpec(close_ratio=%r, open_ratio=%r, baseline_rate=%r, baseline_rise=%r, hold_frames=%r, max_closed_frames=%r)' % self.key()
+
+
+class EyeGateSpec(object):
+    """What EVEStream.step(chunk, gate=spec) decides on the device, per frame and eye, before the masked step consumes it
+    (eve_eye_gate): an eye is usable iff no criterion vetoes it.  pose_valid is always a criterion where a pose form is in the
+    chunk; every other one is off (None) by default:
+      max_reproj_px    the face-landmark solve's face_reproj_rms must not exceed this many pixels
+      min_inliers      ... and its face_inliers must reach this count (needs face_huber_px or face_landmarks_raw)
+      min_coverage     the share (0 .. 1] of an 8 x 8 lattice over the eye patch that must fall inside the camera frame; with
+                       camera_lens the test is made in the undistorted coordinates the warp refers to (an approximation at the edge)
+      head_pitch       (lo, hi) radians for <side>_h[..., 0], the head's pitch in the eye's normalised space; an open side: +-inf
+      head_yaw_left, head_yaw_right   (lo, hi) for <side>_h[..., 1], PER EYE, so the far eye of a turned head can be dropped before the
+                       near one; the signs are eve_eye_pose_normalize's (data.normalize_eyes)
+      blink            None or a BlinkSpec: eyelid closure from the chunk's eye_contours, with state carried across steps
+    Instances compare and hash by value: the spec is part of a captured graph's key.  Not offered: thresholds learnt per person, a
+    closure announced before its first closed frame, blink times in seconds, a mid-chunk reset of stale recurrent state after a long
+    gap, coverage through the lens model, gradients, EVE.forward."""
+
+    def __init__(self, max_reproj_px=None, min_inliers=None, min_coverage=None, head_pitch=None, head_yaw_left=None, head_yaw_right=None,
+                 blink=None):
+        if max_reproj_px is not None and (not _gate_number(max_reproj_px) or not 0 < max_reproj_px < np.inf):
+            raise ValueError('EyeGateSpec: max_reproj_px must be None or a finite number > 0, got %r' % (max_reproj_px,))
+        if min_inliers is not None and (isinstance(min_inliers, bool) or not isinstance(min_inliers, (int, np.integer)) or
+                                        not 1 <= min_inliers <= 255):
+            raise ValueError('EyeGateSpec: min_inliers must be None or an integer in 1 .. 255, got %r' % (min_inliers,))
+        if min_coverage is not None and (not _gate_number(min_coverage) or not 0 < min_coverage <= 1):
+            raise ValueError('EyeGateSpec: min_coverage must be None or a number in (0, 1], got %r' % (min_coverage,))
+        ranges = []
+        for name, r in (('head_pitch', head_pitch), ('head_yaw_left', head_yaw_left), ('head_yaw_right', head_yaw_right)):
+            if r is not None:
+                if (not isinstance(r, (tuple, list)) or len(r) != 2 or not all(_gate_number(v) for v in r) or not r[0] <= r[1]):
+                    raise ValueError('EyeGateSpec: %s must be None or (lo, hi) radians with lo <= hi, got %r' % (name, r))
+                r = (float(r[0]), float(r[1]))
+            ranges.append(r)
+        if blink is not None and not isinstance(blink, BlinkSpec):
+            raise ValueError('EyeGateSpec: blink must be None or an eve_amd.BlinkSpec, got %s' % type(blink).__name__)
+        self.max_reproj_px = None if max_reproj_px is None else float(max_reproj_px)
+        self.min_inliers = None if min_inliers is None else int(min_inliers)
+        self.min_coverage = None if min_coverage is None else float(min_coverage)
+        self.head_pitch, self.head_yaw_left, self.head_yaw_right = ranges
+        self.blink = blink
+
+    @property
+    def min_inside(self):
+        """The lattice points (1 .. 64) that min_coverage asks for: ceil(min_coverage * 64)."""
+        return None if self.min_coverage is None else min(max(int(np.ceil(self.min_coverage * 64.0)), 1), 64)
+
+    @property
+    def head_angles(self):
+        return self.head_pitch is not None or self.head_yaw_left is not None or self.head_yaw_right is not None
+
+    def key(self):
+        return (self.max_reproj_px, self.min_inliers, self.min_coverage, self.head_pitch, self.head_yaw_left, self.head_yaw_right,
+                None if self.blink is None else self.blink.key())
+
+    def __eq__(self, other):
+        return isinstance(other, EyeGateSpec) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'EyeGateSpec(max_reproj_px=%r, min_inliers=%r, min_coverage=%r, head_pitch=%r, head_yaw_left=%r, head_yaw_right=%r, ' \
+               'blink=%r)' % (self.max_reproj_px, self.min_inliers, self.min_coverage, self.head_pitch, self.head_yaw_left,
+                              self.head_yaw_right, self.blink)
+
+
+def check_eye_contours(contours, B, T, device, where):
+    """The chunk's eye_contours: float32 [B, T, 2, 6, 2 | 3] on `device` (ValueError otherwise)."""
+    if (not torch.is_tensor(contours) or contours.dtype != torch.float32 or contours.dim() != 5 or
+            tuple(contours.shape[:4]) != (B, T, 2, 6) or contours.shape[4] not in (2, 3) or contours.device != device):
+        raise ValueError('%s: %s must be a float32 [%d, %d, 2, 6, 2 | 3] tensor on %s (the six eyelid points p1 .. p6 of the left and the '
+                         'right eye), got %s %s' % (where, EYE_CONTOURS_KEY, B, T, device, getattr(contours, 'dtype', type(contours)),
+                                                   tuple(getattr(contours, 'shape', ()))))
+
+
+def eye_gate(spec, num_streams, num_frames, pose_valid=None, reproj_rms=None, inliers=None, warps=None, h=None, eye_contours=None,
+             frame_size=None, patch_size=None, lengths=None, blink_capacity=256, device=None):
+    """The eye gate of S recorded streams x T frames, stand-alone and from fresh state: one eve_eye_gate launch.  spec an
+    EyeGateSpec; pose_valid bool / uint8 [S, T, 2]; reproj_rms float32 [S, T]; inliers uint8 [S, T]; warps float32 [2, S, T, 3, 3] (left,
+    right; inv(W)) with frame_size (IW, IH) and patch_size (OW, OH); h float32 [2, S, T, 2]; eye_contours float32 [S, T, 2, 6, 2 | 3];
+    lengths int32 [S]: device tensors, each None where it is not known.  A criterion of the spec whose input is missing is a
+    ValueError.  -> usable, eye_gate_reason, blink (uint8 [S, T, 2]), eye_openness (float32 [S, T, 2]), blinks (float64
+    [S, blink_capacity, 4], rows (eye, first tick, last tick, minimum openness)), blink_count, blink_dropped (int32 [S]) and
+    gate_state (float64 [S, 2, 8]); the host does not wait."""
+    if not isinstance(spec, EyeGateSpec):
+        raise ValueError('eye_gate: spec must be an eve_amd.EyeGateSpec, got %s' % type(spec).__name__)
+    S, T = int(num_streams), int(num_frames)
+    for name, on, t in (('max_reproj_px', spec.max_reproj_px is not None, reproj_rms), ('min_inliers', spec.min_inliers is not None, inliers),
+                        ('min_coverage', spec.min_coverage is not None, warps), ('head_pitch / head_yaw', spec.head_angles, h),
+                        ('blink', spec.blink is not None, eye_contours)):
+        if on and t is None:
+            raise ValueError('eye_gate: the spec\'s %s has no input to test' % name)
+    if spec.min_coverage is not None and (frame_size is None or patch_size is None):
+        raise ValueError('eye_gate: min_coverage needs frame_size (IW, IH) and patch_size (OW, OH)')
+    if isinstance(blink_capacity, bool) or not isinstance(blink_capacity, int) or blink_capacity < 1:
+        raise ValueError('eye_gate: blink_capacity must be an integer >= 1, got %r' % (blink_capacity,))
+    tensors = [t for t in (pose_valid, reproj_rms, inliers, warps, h, eye_contours, lengths) if t is not None]
+    dev = tensors[0].device if tensors else torch.device(device if device is not None else 'cuda')
+    if pose_valid is not None:
+        pose_valid = pose_valid.contiguous()
+        pose_valid = pose_valid.view(torch.uint8) if pose_valid.dtype == torch.bool else pose_valid
+    state = torch.zeros((S, 2, 8), dtype=torch.float64, device=dev)
+    store = torch.zeros((S, blink_capacity, 4), dtype=torch.float64, device=dev)
+    count, dropped = torch.zeros((S,), dtype=torch.int32, device=dev), torch.zeros((S,), dtype=torch.int32, device=dev)
+    flat = lambda t, n: None if t is None else t.reshape(2, S * T, n).contiguous()
+    out = default_kernels().eye_gate(
+        spec, S, T, state, store, count, dropped, pose_valid=pose_valid,
+        reproj_rms=reproj_rms.contiguous() if spec.max_reproj_px is not None else None,
+        inliers=inliers.contiguous() if spec.min_inliers is not None else None,
+        warp=flat(warps, 9) if spec.min_coverage is not None else None, h=flat(h, 2) if spec.head_angles else None,
+        contours=eye_contours.contiguous() if spec.blink is not None else None, lengths=lengths, frame_size=frame_size, patch_size=patch_size)
+    return {'usable': out['usable'], 'eye_gate_reason': out['reason'], 'eye_openness': out['openness'], 'blink': out['blink'],
+            'blinks': store, 'blink_count': count, 'blink_dropped': dropped, 'gate_state': state}
+
+
 def render_overlay(frames, format='rgb', out_format='nv12', matrix='bt601', markers=None, heat=None, inset=None, frame_valid=None, out=None):
     """The tracking overlay on the device, stand-alone: frames uint8 [N, ...] in `format` ('rgb' | 'bgr' [N, IH, IW, 3 | 4], 'rgba',
     'bgra', 'nv12' | 'i420' [N, IH*3/2, IW], 'yuyv' [N, IH, IW, 2]) -> the annotated frames, uint8 [N, IH, IW, 3] for out_format 'rgb' |

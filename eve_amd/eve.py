@@ -343,7 +343,7 @@ class EVE(nn.Module):
                        'PoG_cm_initial', 'g_final', 'PoG_px_final', 'PoG_cm_final')
 
     def _predict_sequence(self, d, eye_states, refine_states, reset=None, return_heatmaps=False, lengths=None, masked=False,
-                          eye_mask=None, pose_gate=None, face_state=None, render=None, calibration=None, events=None):
+                          eye_mask=None, pose_gate=None, face_state=None, render=None, calibration=None, events=None, gate=None):
         """The prediction part of forward() for one chunk of an EVEStream: eval only, no labels, no losses.  d: the chunk's
         inputs [B, Tc, ...] (not modified; camera_frame may be any one key of eye_net.EYE_FRAME_KEYS or camera_surface, and the screen any one
         key of refine_net.SCREEN_FRAME_KEYS or screen_surface; the eyes as patches, as camera_frame + {left,right}_eye_warp, or as camera_frame +
@@ -380,13 +380,23 @@ class EVE(nn.Module):
         events: None, or EVEStream's gaze filter and fixation / saccade stage {'spec': a data.GazeEventSpec, 'source': the result key
         it filters, 'state': float64 [B, 32], 'store': float64 [B, F, 8], 'count', 'dropped': int32 [B]}: one eve_gaze_events launch,
         last before the render hook, over the step's own source PoG and d['o'], with frame_time from d when it is there, the step's
-        lengths, `valid` (masked) and reset flags; the result gains data.GAZE_EVENT_KEYS.  None issues no launch."""
+        lengths, `valid` (masked) and reset flags; the result gains data.GAZE_EVENT_KEYS.  None issues no launch.
+        gate: None, or EVEStream's eye gate {'spec': a data.EyeGateSpec, 'state': float64 [B, 2, 8], 'store': float64 [B, capacity, 4],
+        'count', 'dropped': int32 [B], 'frame_size': None or the camera frame's (IW, IH)}: one eve_eye_gate launch between eye_pose_batch and
+        the mask plan, over pose_valid, face_reproj_rms, face_inliers, the (derived) warps and head angles and d['eye_contours'] -- each
+        where the spec has a criterion for it -- with the step's lengths and reset flags.  Its `usable` becomes eye_mask, or is ANDed
+        into it, so a gated step is a masked step; the result gains data.EYE_GATE_KEYS.  None issues no launch."""
         assert not self.training, 'EVE._predict_sequence is eval-only'
         B = eye_input(d).shape[0]
         posed, faced = has_pose_form(d), face_landmarks_key(d) is not None
+        contours = d.get('eye_contours')
         d = dict(eye_pose_batch(d, self.config, face_state, None if reset is None else reset[:B], None if lengths is None else lengths[:B],
                                 huber_px=self.eye_net.face_huber_px))
-        plan = eye_valid = None
+        plan = eye_valid = gated = None
+        if gate is not None:
+            gated = self._eye_gate(d, contours, gate, None if reset is None else reset[:B], None if lengths is None else lengths[:B])
+            eye_mask = gated['usable'] if eye_mask is None else (eye_mask != 0) & (gated['usable'] != 0)
+            masked = True
         if masked:
             T = eye_input(d).shape[1]
             pose_ok = None
@@ -429,6 +439,8 @@ class EVE(nn.Module):
                 out['face_inliers'] = d['face_inliers']
         if plan is not None:
             out['valid'], out['eye_valid'] = plan['valid'].view(torch.bool), eye_valid
+        if gated is not None:
+            out['eye_gate_reason'], out['eye_openness'], out['blink'] = gated['reason'], gated['openness'], gated['blink']
         if return_heatmaps and 'heatmap_final' in inter:
             out['heatmap_final'] = inter['heatmap_final']
         if events is not None:
@@ -442,6 +454,26 @@ class EVE(nn.Module):
         if render is not None:
             render(d, inter, out)
         return out
+
+    def _eye_gate(self, d, contours, gate, reset, lengths):
+        """The gate of a gated EVEStream step: one eve_eye_gate launch over what the spec has a criterion for (d: the chunk after
+        eye_pose_batch, so the derived warps and head angles are there)."""
+        from .data import eye_patch_hw
+        spec = gate['spec']
+        B, T = eye_input(d).shape[:2]
+        both = lambda key, n: torch.stack([d['left' + key], d['right' + key]]).reshape(2, B * T, n).float().contiguous()
+        pose_valid = None
+        if 'pose_valid' in d:
+            pose_valid = d['pose_valid'].contiguous()
+            pose_valid = pose_valid.view(torch.uint8) if pose_valid.dtype == torch.bool else pose_valid
+        ph, pw = eye_patch_hw(self.config)
+        return default_kernels().eye_gate(
+            spec, B, T, gate['state'], gate['store'], gate['count'], gate['dropped'], pose_valid=pose_valid,
+            reproj_rms=d['face_reproj_rms'].contiguous() if spec.max_reproj_px is not None else None,
+            inliers=d['face_inliers'].contiguous() if spec.min_inliers is not None else None,
+            warp=both('_eye_warp', 9) if spec.min_coverage is not None else None, h=both('_h', 2) if spec.head_angles else None,
+            contours=contours.contiguous() if spec.blink is not None else None, lengths=lengths, reset=reset,
+            frame_size=gate['frame_size'], patch_size=(pw, ph))
 
     def _calibration_append(self, d, inter, store, lengths, plan):
         """The collecting stage of a calibrated EVEStream step: one eve_calib_append launch over both eyes, from the network's own

@@ -1028,6 +1028,77 @@ class HipKernels(object):
             *([self._p(out[k_]) for k_ in self.GAZE_EVENT_KEYS] if T else [None] * 7), self._stream()))
         return out
 
+    # ------------------------------------------------------------------ the eye gate
+    def eye_gate(self, spec, B, T, state, store, count, dropped, pose_valid=None, reproj_rms=None, inliers=None, warp=None, h=None,
+                 contours=None, lengths=None, reset=None, frame_size=None, patch_size=None):
+        """Per frame and eye: is the eye usable, and is it blinking?  spec an eve_amd.EyeGateSpec (its numbers are the launch's
+        parameter block); state float64 [B, 2, 8], store float64 [B, capacity, 4], count and dropped int32 [B], UPDATED IN PLACE;
+        pose_valid uint8 [B, T, 2], reproj_rms float32 [B, T], inliers uint8 [B, T], warp float32 [2, B*T, 9] with frame_size (IW, IH)
+        and patch_size (OW, OH), h float32 [2, B*T, 2], contours float32 [B, T, 2, 6, 2 | 3], lengths and reset int32 [B], or None: an
+        input that is None turns its criterion off, and an input whose criterion the spec leaves off must be None.  -> {'usable',
+        'reason', 'blink': uint8 [B, T, 2], 'openness': float32 [B, T, 2]} (include/eve_hip.h eve_eye_gate)."""
+        from ._lib import EyeGateParams
+        ok = lambda t, dtype: torch.is_tensor(t) and t.dtype == dtype
+        B, T = int(B), int(T)
+        if B < 1 or T < 1:
+            raise ValueError('eye_gate: B and T must be >= 1, got %d and %d' % (B, T))
+        if not ok(state, torch.float64) or tuple(state.shape) != (B, 2, 8):
+            raise TypeError('eye_gate: state must be float64 [%d, 2, 8], got %s %s' % (B, getattr(state, 'dtype', type(state)),
+                                                                                        tuple(getattr(state, 'shape', ()))))
+        if not ok(store, torch.float64) or store.dim() != 3 or store.shape[0] != B or store.shape[1] < 1 or store.shape[2] != 4:
+            raise TypeError('eye_gate: store must be float64 [%d, capacity, 4], got %s %s' % (B, getattr(store, 'dtype', type(store)),
+                                                                                               tuple(getattr(store, 'shape', ()))))
+        C = 0
+        if contours is not None:
+            if not ok(contours, torch.float32) or contours.dim() != 5 or tuple(contours.shape[:4]) != (B, T, 2, 6) or contours.shape[4] not in (2, 3):
+                raise TypeError('eye_gate: contours must be float32 [%d, %d, 2, 6, 2 | 3], got %s %s' % (
+                    B, T, getattr(contours, 'dtype', type(contours)), tuple(getattr(contours, 'shape', ()))))
+            C = contours.shape[4]
+        checks = [('count', count, torch.int32, (B,), True), ('dropped', dropped, torch.int32, (B,), True),
+                  ('pose_valid', pose_valid, torch.uint8, (B, T, 2), False), ('reproj_rms', reproj_rms, torch.float32, (B, T), False),
+                  ('inliers', inliers, torch.uint8, (B, T), False), ('warp', warp, torch.float32, (2, B * T, 9), False),
+                  ('h', h, torch.float32, (2, B * T, 2), False), ('lengths', lengths, torch.int32, (B,), False),
+                  ('reset', reset, torch.int32, (B,), False)]
+        tensors = [state, store] + ([contours] if contours is not None else [])
+        for name, t, dtype, shape, needed in checks:
+            if (t is not None or needed) and (not ok(t, dtype) or tuple(t.shape) != shape):
+                raise TypeError('eye_gate: %s must be %s %s, got %s %s' % (
+                    name, str(dtype).replace('torch.', ''), list(shape), getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ()))))
+            if t is not None:
+                tensors.append(t)
+        if not all(t.is_contiguous() for t in tensors):
+            raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        for name, t, on in (('reproj_rms', reproj_rms, spec.max_reproj_px is not None), ('inliers', inliers, spec.min_inliers is not None),
+                            ('warp', warp, spec.min_coverage is not None), ('h', h, spec.head_angles), ('contours', contours, spec.blink is not None)):
+            if (t is not None) != bool(on):
+                raise ValueError('eye_gate: %s goes with its criterion in the spec, and only with it' % name)
+        IW = IH = OW = OH = 0
+        if warp is not None:
+            if frame_size is None or patch_size is None:
+                raise ValueError('eye_gate: warp needs frame_size (IW, IH) and patch_size (OW, OH)')
+            (IW, IH), (OW, OH) = (int(v) for v in frame_size), (int(v) for v in patch_size)
+        inf = float('inf')
+        rng = lambda r: (-inf, inf) if r is None else r
+        P = EyeGateParams()
+        P.max_reproj_px = inf if spec.max_reproj_px is None else spec.max_reproj_px
+        P.pitch_lo, P.pitch_hi = rng(spec.head_pitch)
+        for e, r in enumerate((spec.head_yaw_left, spec.head_yaw_right)):
+            P.yaw_lo[e], P.yaw_hi[e] = rng(r)
+        P.min_inliers = 0 if spec.min_inliers is None else spec.min_inliers
+        P.min_inside = 1 if spec.min_coverage is None else spec.min_inside
+        bl = spec.blink
+        P.close_ratio, P.open_ratio = (0.0, 1.0) if bl is None else (bl.close_ratio, bl.open_ratio)
+        P.baseline_rate, P.baseline_rise = (0.0, 0.0) if bl is None else (bl.baseline_rate, bl.baseline_rise)
+        P.hold_frames, P.max_closed_frames = (0, 1) if bl is None else (bl.hold_frames, bl.max_closed_frames)
+        dev = state.device
+        out = {'usable': torch.empty((B, T, 2), dtype=torch.uint8, device=dev), 'reason': torch.empty((B, T, 2), dtype=torch.uint8, device=dev),
+               'openness': torch.empty((B, T, 2), dtype=torch.float32, device=dev), 'blink': torch.empty((B, T, 2), dtype=torch.uint8, device=dev)}
+        self._ck(self.lib.eve_eye_gate(
+            B, T, self._p(pose_valid), self._p(reproj_rms), self._p(inliers), self._p(warp), self._p(h), self._p(contours), C, self._p(lengths),
+            self._p(reset), IW, IH, OW, OH, ctypes.byref(P), self._p(state), store.shape[1], self._p(store), self._p(count), self._p(dropped),
+            self._p(out['usable']), self._p(out['reason']), self._p(out['openness']), self._p(out['blink']), self._stream()))
+        return out
+
     # ------------------------------------------------------------------ gaze geometry / heat-maps / soft-argmax
     def _flat32(self, t, shape, what):
         t = t.contiguous()

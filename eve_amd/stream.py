@@ -10,6 +10,7 @@ carried from one call to the next.
     fit = stream.fit_calibration(huber_mm=25.0)            # fit each eye's offset on the device; later steps apply it
     out = stream.step(chunk, events=eve_amd.GazeEventSpec(fps=60))   # + the filtered PoG, gaze velocity, fixation / saccade events
     rows = stream.fixations()                              # the completed fixations of every stream (see "Gaze events" below)
+    out = stream.step(chunk, gate=eve_amd.EyeGateSpec(blink=eve_amd.BlinkSpec()))   # the mask made on the device (see "The eye gate" below)
     st = stream.get_state(); stream.set_state(st)          # reference layout, e.g. to resume a recording
 
 For any split of a clip into chunks the concatenated outputs equal one eval pass of the whole clip from zero state
@@ -67,6 +68,22 @@ device flags (get_event_state / set_event_state; get_state / set_state do not ho
 tests/gaze_events_ref.py states the arithmetic.  A step without events issues exactly the launches it always issued.  Not offered:
 dispersion (I-DT) or other classifiers, windowed velocity, merging of adjacent fixations and retroactive relabelling,
 smooth-pursuit and blink classes, per-eye events, gradients, EVE.forward.
+
+The eye gate.  The masked step keeps an unusable eye out of the states and the fused gaze, but it needs the mask, and what should
+veto an eye -- pose_valid, face_reproj_rms, face_inliers, the derived warps and head angles, a closed lid -- are results of the same
+step: a host that acts on them waits for the device every chunk, or is one chunk late.  step(chunk, gate=eve_amd.EyeGateSpec(...))
+adds one eve_eye_gate launch between the pose derivation and eve_stream_mask_plan, inside the graph, whose verdict becomes the
+step's eye_mask (ANDed into the caller's where there is one): a gated step is a masked step, and the scans, the fusion, the
+calibration samples, the gaze events and the overlay follow through eye_valid / valid.  The result gains eye_gate_reason uint8
+[B, Tc, 2] (bits: 1 pose, 2 reprojection, 4 inliers, 8 coverage, 16 head angle, 32 eyelid closed, 64 hold-off after a blink),
+eye_openness float32 [B, Tc, 2] (the eyelid aspect ratio of the chunk's eye_contours over a baseline that follows the open eye; NaN
+where unknown) and blink uint8 [B, Tc, 2]; completed blinks go to a per-stream store (float64 [B, blink_capacity, 4]: eye, first
+tick, last tick, minimum openness; blinks(), blink_counts(), clear_blinks()).  The blink state is a float64 [B, 2, 8] row per eye,
+carried from step to step and reset through the same device flags, also before a step without gate (get_gate_state /
+set_gate_state; get_state / set_state do not hold it).  Float64 throughout; tests/eye_gate_ref.py states the arithmetic.  A step
+without gate issues exactly the launches it always issued.  Not offered: adaptive thresholds learnt per person, a closure announced
+before its first closed frame, blink times in seconds, a mid-chunk reset of stale recurrent state after a long gap, coverage
+through the lens model, gradients, EVE.forward.
 """
 import numpy as np
 import torch
@@ -82,7 +99,7 @@ def _module_key(m):
 
 
 class EVEStream(object):
-    def __init__(self, model, num_streams, use_graph=True, calibration_capacity=1024, fixation_capacity=256):
+    def __init__(self, model, num_streams, use_graph=True, calibration_capacity=1024, fixation_capacity=256, blink_capacity=256):
         if model.training:
             raise ValueError('EVEStream runs inference only: call model.eval() first')
         self.model = model
@@ -121,6 +138,12 @@ class EVEStream(object):
         self.fixation_capacity = fixation_capacity
         self._events = None                      # made at the first events step or fixation call: (state, store, count, dropped)
         self._events_spec = None                 # the spec of the last events step: what closes a fixation outside a step
+        # the eye gate (step(chunk, gate=spec)): each eye's blink state row, the store of completed blinks and its counters --
+        # eve_eye_gate reads and writes them inside the step (and the graph)
+        if isinstance(blink_capacity, bool) or not isinstance(blink_capacity, int) or blink_capacity < 1:
+            raise ValueError('blink_capacity must be an integer >= 1, got %r' % (blink_capacity,))
+        self.blink_capacity = blink_capacity
+        self._gate = None                        # made at the first gated step or blink call: (state, store, count, dropped)
         self._graphs = {}
         self._graphs_key = None
         self._render_tables = {}                 # OverlaySpec.key() -> its marker table, int32 [M, 4] on the device
@@ -131,7 +154,8 @@ class EVEStream(object):
 
     def reset(self, streams=None):
         """Start the given streams (None = all; else indices, or a bool mask of length num_streams) from zero state at the
-        next step().  Resets requested before one step accumulate.  A stream that has run gaze events (step(events=...)) closes its
+        next step().  Resets requested before one step accumulate.  A stream that has run the eye gate (step(gate=...)) has both
+        eyes' blink rows and its tick cleared; an eye closed at that moment stores no blink.  A stream that has run gaze events (step(events=...)) closes its
         open fixation into the store -- if it lasted min_fixation_s -- and starts its filter, its events and its frame count afresh,
         by the same device flags; only its fixation id counter runs on, so ids stay unique within a recording.  The per-person calibration -- each eye's kappa and the
         sample store -- is not touched: it belongs to the person, not to the clip (clear_calibration,
@@ -333,6 +357,89 @@ class EVEStream(object):
         self._event_buffers()                    # allocated here, before any capture
         return {'spec': spec, 'source': source}
 
+    # ------------------------------------------------------------------ the eye gate
+    def _gate_buffers(self):
+        if self._gate is None:
+            B, C = self.num_streams, self.blink_capacity
+            self._gate = (torch.zeros((B, 2, 8), dtype=torch.float64, device=self.device),
+                          torch.zeros((B, C, 4), dtype=torch.float64, device=self.device),
+                          torch.zeros((B,), dtype=torch.int32, device=self.device), torch.zeros((B,), dtype=torch.int32, device=self.device))
+        return self._gate
+
+    def blinks(self, streams=None):
+        """The completed blinks of the given streams (None = all; indices or a bool mask), one numpy float64 [n, 4] array per stream
+        in index order, rows (eye: 0 left, 1 right; the tick of the first closed frame; the tick of the last one; the minimum
+        openness) in the order they ended; a tick counts the stream's delivered frames since its last reset.  This call waits for
+        the device.  A closure still running, one that a reset() cut short and one longer than max_closed_frames are not blinks."""
+        m = self._stream_mask(streams, 'blinks')
+        _, store, count, _ = (t.cpu().numpy() for t in self._gate_buffers())
+        return [store[b, :min(max(int(count[b]), 0), self.blink_capacity)].copy() for b in np.flatnonzero(m)]
+
+    def blink_counts(self):
+        """-> (count, dropped), int32 [B] device tensors (fresh): the completed blinks each stream's store holds, and those a full
+        store (blink_capacity) turned away."""
+        _, _, count, dropped = self._gate_buffers()
+        return count.clone(), dropped.clone()
+
+    def clear_blinks(self, streams=None):
+        """Empty the blink store of the given streams (None = all) and their dropped counters.  The running closure, the baseline
+        and the hold-off are state, not store: reset() ends them."""
+        m = self._device_mask(streams, 'clear_blinks')
+        _, _, count, dropped = self._gate_buffers()
+        count.copy_(torch.where(m, torch.zeros_like(count), count))
+        dropped.copy_(torch.where(m, torch.zeros_like(dropped), dropped))
+
+    def get_gate_state(self):
+        """The eye gate's carried state, float64 [B, 2, 8] (fresh; include/eve_hip.h eve_eye_gate has the layout): per stream and eye
+        the baseline, the running closure, the hold-off and the stream's frame count.  Resets not yet applied by a step are not
+        reflected.  get_state() / set_state() do not hold it."""
+        return self._gate_buffers()[0].clone()
+
+    def set_gate_state(self, state):
+        """Load a state in get_gate_state()'s layout, [B, 2, 8] (converted to float64)."""
+        state = torch.as_tensor(state, dtype=torch.float64).to(self.device)
+        if tuple(state.shape) != (self.num_streams, 2, 8):
+            raise ValueError('set_gate_state: state must be [%d, 2, 8], got %s' % (self.num_streams, tuple(state.shape)))
+        self._gate_buffers()[0].copy_(state)
+
+    def _check_gate(self, chunk, spec, B, Tc):
+        """step()'s `gate` checked against the chunk and the model -> what _predict_sequence needs beside the buffers.  Every
+        refusal is a ValueError raised before anything is launched or captured."""
+        from .data import EYE_CONTOURS_KEY, EyeGateSpec, check_eye_contours
+        from .eye_net import EYE_FRAME_KEYS, EYE_SURFACE_KEY, FACE_LANDMARKS_RAW_KEY, camera_frame_key
+        from .kernels import pixel_format_shape
+        if not isinstance(spec, EyeGateSpec):
+            raise ValueError('step: gate must be an eve_amd.EyeGateSpec, got %s' % type(spec).__name__)
+        frame_key, lm_key = camera_frame_key(chunk), face_landmarks_key(chunk)
+        if frame_key is None and (spec.min_coverage is not None or spec.head_angles):
+            raise ValueError('step: gate: %s needs a camera form (a camera frame with warps, eye_pose or face_landmarks): pre-cut patches '
+                             'have no warp and no derived head angles to test' % ('min_coverage' if spec.min_coverage is not None else
+                                                                                   'head_pitch / head_yaw_left / head_yaw_right'))
+        if spec.max_reproj_px is not None and lm_key is None:
+            raise ValueError('step: gate: max_reproj_px tests face_reproj_rms, which the face-landmark form produces')
+        if spec.min_inliers is not None and (lm_key is None or (lm_key != FACE_LANDMARKS_RAW_KEY and self.model.eye_net.face_huber_px is None)):
+            raise ValueError('step: gate: min_inliers tests face_inliers, which the face-landmark form produces with eye_net.face_huber_px '
+                             'or face_landmarks_raw')
+        if spec.blink is not None and EYE_CONTOURS_KEY not in chunk:
+            raise ValueError('step: gate: blink needs %s in the chunk (float32 [B, Tc, 2, 6, 2 | 3])' % EYE_CONTOURS_KEY)
+        if EYE_CONTOURS_KEY in chunk:
+            check_eye_contours(chunk[EYE_CONTOURS_KEY], B, Tc, self.device, 'step: gate')
+        frame_size = None
+        if spec.min_coverage is not None:
+            if frame_key == EYE_SURFACE_KEY:
+                layout = self.model.eye_net.camera_layout
+                if layout is None:
+                    raise ValueError('step: gate: min_coverage needs the frame size, and %s comes without eye_net.camera_layout' % frame_key)
+                frame_size = (int(layout.width), int(layout.height))
+            else:
+                try:
+                    IH, IW, _ = pixel_format_shape(chunk[frame_key], EYE_FRAME_KEYS[frame_key], lead=2, name=frame_key)
+                except TypeError as e:
+                    raise ValueError('step: gate: %s' % e)
+                frame_size = (int(IW), int(IH))
+        self._gate_buffers()                     # allocated here, before any capture
+        return {'spec': spec, 'frame_size': frame_size}
+
     def get_state(self):
         """The carried states in the reference layout (fresh tensors): {left,right}_eye_rnn_states_<i> [B, H] float32 ((h, c) for
         LSTM) and refinenet_rnn_states_<i> [B, C, 5, 8] float32 ((h, c) for CLSTM).  Resets not yet applied by a step are not
@@ -467,7 +574,7 @@ class EVEStream(object):
             self._pose_gate_host = not skip_invalid_pose
             self._pose_gate.fill_(self._pose_gate_host)              # a device value: the captured graphs read it, the host never waits
 
-    def _run(self, chunk, return_heatmaps, ragged=False, eye_mask=None, masked=False, render=None, events=None):
+    def _run(self, chunk, return_heatmaps, ragged=False, eye_mask=None, masked=False, render=None, events=None, gate=None):
         # render: None or a _render_plan; the keyword reaches _predict_sequence only then, so a step without it calls what it always did
         extra = {} if render is None else {'render': self._render_hook(render, ragged, masked)}
         if self._calib_apply or 'calibration_target' in chunk:       # (neither: the call an uncalibrated EVEStream always made)
@@ -476,6 +583,9 @@ class EVEStream(object):
         if events is not None:                   # events: None or a _check_events plan; the keyword goes along only then
             state, store, count, dropped = self._event_buffers()
             extra['events'] = dict(events, state=state, store=store, count=count, dropped=dropped)
+        if gate is not None:                     # gate: None or a _check_gate plan; the keyword goes along only then
+            state, store, count, dropped = self._gate_buffers()
+            extra['gate'] = dict(gate, state=state, store=store, count=count, dropped=dropped)
         if face_landmarks_key(chunk) is not None:      # the face-landmark form: the carried head pose goes along
             return self.model._predict_sequence(chunk, self._eye, self._ref, reset=self._flags, return_heatmaps=return_heatmaps,
                                                 lengths=self._lengths if ragged else None, masked=masked, eye_mask=eye_mask,
@@ -617,7 +727,7 @@ class EVEStream(object):
             out['rendered'] = rendered.view((B, Tc) + tuple(rendered.shape[1:]))
         return render
 
-    def step(self, chunk, return_heatmaps=False, lengths=None, eye_mask=None, skip_invalid_pose=False, render=None, events=None):
+    def step(self, chunk, return_heatmaps=False, lengths=None, eye_mask=None, skip_invalid_pose=False, render=None, events=None, gate=None):
         """One chunk of every stream: chunk holds [B, Tc, ...] tensors on the model's device -- the eyes (below), {left,right}_h,
         {left,right}_o, {left,right}_R, head_R, camera_transformation, inv_camera_transformation, pixels_per_millimeter, millimeters_per_pixel, and screen_frame when the config loads screen content.  Returns the
         prediction keys of EVE(output_predictions=True) as [B, Tc, ...] tensors (heatmap_final [B, Tc, 1, H, W] on request).
@@ -803,14 +913,40 @@ class EVEStream(object):
         and render's markers may name the new keys (dict(key='fixation_px', valid='fixating'), key='PoG_px_filtered').
         tests/gaze_events_ref.py states the arithmetic.  Not offered: dispersion (I-DT) or other classifiers, windowed velocity,
         merging of adjacent fixations and retroactive relabelling, smooth-pursuit and blink classes, per-eye events, gradients,
-        EVE.forward.  events=None issues exactly the launches the step always issued."""
+        EVE.forward.  events=None issues exactly the launches the step always issued.
+
+        gate: None, or an eve_amd.EyeGateSpec -- one eve_eye_gate launch after the pose derivation and before the mask plan, inside the
+        captured graph, decides per frame and eye whether the eye is usable, and that verdict is the step's eye_mask (ANDed with
+        an eye_mask of the caller's): the step is a masked step with everything that says (valid, eye_valid, the contract above),
+        and pose_valid always counts where a pose form is in the chunk, as with skip_invalid_pose.  The criteria (data.EyeGateSpec;
+        all off by default): face_reproj_rms <= max_reproj_px and face_inliers >= min_inliers (the face-landmark form; the latter
+        with eye_net.face_huber_px or face_landmarks_raw), at least min_coverage of an 8 x 8 lattice over the patch inside the
+        camera frame (any camera form; the size comes from the frame key's shape or eye_net.camera_layout; with camera_lens in
+        the undistorted coordinates the warp refers to, an approximation at the edge), <side>_h within head_pitch and the eye's
+        own head_yaw_left / head_yaw_right (any camera form), and blink, a data.BlinkSpec: the chunk's eye_contours, float32
+        [B, Tc, 2, 6, 2 | 3] on the model's device -- pixel (u, v[, w]) of the six eyelid points p1 .. p6 of the (left, right) eye,
+        p1 and p4 the corners, p2 and p3 on the upper lid, p6 and p5 below them -- give the aspect ratio ear = (|p2-p6| + |p3-p5|) /
+        (2 |p1-p4|), unknown with a non-finite coordinate, a weight <= 0 or no width.  The first known ear is the baseline, which
+        follows the open eye (baseline_rise upwards, baseline_rate downwards); eye_openness = ear / baseline; below close_ratio
+        the eye closes, above open_ratio it reopens, the blink (eye, first tick, last tick, minimum openness) goes to the store
+        and hold_frames frames from the reopening one on are withheld; a closure longer than max_closed_frames starts the
+        baseline over and stores nothing; an unknown ear moves nothing.  A tick counts the stream's delivered frames since its
+        last reset(); frames past lengths[b] are not delivered.  The result gains eye_gate_reason uint8 [B, Tc, 2] (1 pose, 2
+        reprojection, 4 inliers, 8 coverage, 16 head angle, 32 closed, 64 hold-off; 0 = usable), eye_openness float32 [B, Tc, 2] and
+        blink uint8 [B, Tc, 2].  eye_contours works with pre-cut patches too.  A criterion whose input the chunk or the model does
+        not provide, a blink without eye_contours, and eye_contours of another dtype, shape or device are ValueErrors raised
+        before anything is launched or captured.  The spec by value and eye_contours' shape are part of the graph's key; lengths,
+        eye_mask, every camera and screen form, calibration, events and render combine with it.  Not offered: adaptive thresholds
+        learnt per person, a closure announced before its first closed frame, blink times in seconds, a mid-chunk reset of stale
+        recurrent state after a long gap, coverage through the lens model, gradients, EVE.forward.  gate=None issues exactly the
+        launches the step always issued."""
         if self.model.training:
             raise ValueError('EVEStream runs inference only: the model was switched to training mode')
         B, Tc = eye_input(chunk).shape[:2]
         if B != self.num_streams:
             raise ValueError('chunk has %d streams, the EVEStream %d' % (B, self.num_streams))
         ragged = lengths is not None
-        masked = eye_mask is not None or bool(skip_invalid_pose)
+        masked = eye_mask is not None or bool(skip_invalid_pose) or gate is not None
         if skip_invalid_pose and not has_pose_form(chunk):
             raise ValueError('step: skip_invalid_pose needs the pose form (eye_pose in the chunk): there is no pose_valid to fold in')
         if ragged:
@@ -819,6 +955,9 @@ class EVEStream(object):
             eye_mask = self._eye_mask(eye_mask, Tc)
         if events is not None:
             events = self._check_events(chunk, events, B, Tc)
+        if gate is not None:
+            gate = self._check_gate(chunk, gate, B, Tc)
+        more = {} if gate is None else {'gate': gate}      # the keyword goes along only then: a step without it calls what it always did
         if render is not None:
             render = self._render_plan(chunk, render) if events is None else self._render_plan(chunk, render, events)
         self._check_calibration(chunk, B, Tc)
@@ -834,9 +973,13 @@ class EVEStream(object):
             state, store, count, dropped = self._events
             default_kernels().gaze_events(None, None, None, None, self._closing_spec(), state, store, count, dropped,
                                           reset=self._flags[:self.num_streams])
+        if gate is None and self._gate is not None and self._flags_set:
+            # a reset before a step without gate: the gate's rows of the flagged streams are still cleared (the launch refuses T = 0)
+            state = self._gate[0]
+            state.copy_(torch.where(self._flags[:self.num_streams, None, None] != 0, torch.zeros_like(state), state))
         with torch.no_grad():
             if self.use_graph:
-                entry = self._graph_for(chunk, bool(return_heatmaps), ragged, masked, render, events)
+                entry = self._graph_for(chunk, bool(return_heatmaps), ragged, masked, render, events, **more)
                 for key, buf in entry['inputs'].items():
                     buf.copy_(chunk[key], non_blocking=True)
                 if masked:
@@ -849,8 +992,8 @@ class EVEStream(object):
             else:
                 if eye_mask is not None and eye_mask.device != self.device:
                     eye_mask = torch.empty(eye_mask.shape, dtype=torch.uint8, device=self.device).copy_(eye_mask, non_blocking=True)
-                out = self._run(chunk, return_heatmaps, ragged, eye_mask, masked, render) if events is None else \
-                    self._run(chunk, return_heatmaps, ragged, eye_mask, masked, render, events)
+                out = self._run(chunk, return_heatmaps, ragged, eye_mask, masked, render, **more) if events is None else \
+                    self._run(chunk, return_heatmaps, ragged, eye_mask, masked, render, events, **more)
             if ragged and not masked:
                 out['valid'] = torch.arange(Tc, device=self.device)[None, :] < self._lengths[:self.num_streams, None]
         if self._flags_set:
@@ -869,11 +1012,12 @@ class EVEStream(object):
     def _weights_key(self):
         return tuple(_module_key(m) for m in (self.model.eye_net, self.model.refine_net) if m is not None)
 
-    def _graph_key(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None):
+    def _graph_key(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None):
         """What a captured graph is good for: the step's mode, both YUV matrices, both surface layouts (by value), the overlay
         (render: None or a _render_plan -- its OverlaySpec by value), with a face-landmark form eye_net.face_huber_px (a launch
         argument, so baked in), the gaze events (events: None or a _check_events plan -- its GazeEventSpec by value and its source;
-        frame_time's presence is a chunk key), whether a calibration is applied (`calibrated`; a collecting step differs by its chunk keys), and every chunk tensor's key, shape and dtype -- which of the two landmark keys among them."""
+        frame_time's presence is a chunk key), the eye gate (gate: None or a _check_gate plan -- its EyeGateSpec by value and the frame size;
+        eye_contours' presence and shape are a chunk key), whether a calibration is applied (`calibrated`; a collecting step differs by its chunk keys), and every chunk tensor's key, shape and dtype -- which of the two landmark keys among them."""
         ref = self.model.refine_net
         spec = None if render is None else render['spec'].key()
         layouts = (self.model.eye_net.camera_layout, None if ref is None else ref.screen_layout)
@@ -882,22 +1026,24 @@ class EVEStream(object):
             from .data import check_huber_px
             huber = check_huber_px(self.model.eye_net.face_huber_px, 'face_huber_px')
         return (return_heatmaps, ragged, masked, self.model.eye_net.yuv_matrix, None if ref is None else ref.yuv_matrix, spec, layouts, huber,
-                self._calib_apply) + (() if events is None else ((events['spec'].key(), events['source']),)) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
+                self._calib_apply) + (() if events is None else ((events['spec'].key(), events['source']),)) + \
+            (() if gate is None else (('gate', gate['spec'].key(), gate['frame_size']),)) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
 
-    def _graph_for(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None):
+    def _graph_for(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None):
         wk = self._weights_key()
         if wk != self._graphs_key:               # new weights: new packs, new graphs (a replay never reads stale packs)
             self._graphs = {}
             self._graphs_key = wk
-        key = self._graph_key(chunk, return_heatmaps, ragged, masked, render, events)
+        more = {} if gate is None else {'gate': gate}
+        key = self._graph_key(chunk, return_heatmaps, ragged, masked, render, events, **more)
         entry = self._graphs.get(key)
         if entry is None:
-            entry = self._graphs[key] = self._capture(chunk, return_heatmaps, ragged, masked, render) if events is None else \
-                self._capture(chunk, return_heatmaps, ragged, masked, render, events)
+            entry = self._graphs[key] = self._capture(chunk, return_heatmaps, ragged, masked, render, **more) if events is None else \
+                self._capture(chunk, return_heatmaps, ragged, masked, render, events, **more)
             self._graphs_key = self._weights_key()
         return entry
 
-    def _capture(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None):
+    def _capture(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None):
         """Capture one step for this chunk shape (train.Trainer._capture's recipe): inputs copied into fixed buffers, two eager
         warm-up steps off the default stream (packs, lazily built filters, allocator) with the carried states put back
         afterwards, the kernels' scratch allocated before the capture, one stream, no side branches.  A masked graph has one more
@@ -915,10 +1061,10 @@ class EVEStream(object):
             # append every sample three times
             # (and the gaze events' state, store and counters: a capture would otherwise tick the filter three times)
             carried = self._state_tensors() + [self._face_pose, self._calib_kappa, self._calib_ok] + list(self._calib_store or ()) + \
-                list(self._events or ())
+                list(self._events or ()) + list(self._gate or ())          # (and the eye gate's: its ticks, baselines and blinks)
             snap = [t.clone() for t in carried]
             for _ in range(2):
-                self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events)
+                self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate)
             for t, s_ in zip(carried, snap):
                 t.copy_(s_)
         torch.cuda.current_stream().wait_stream(side)
@@ -928,7 +1074,7 @@ class EVEStream(object):
             k.prepare_graph_workspace(self.device)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            out = self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events)
+            out = self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate)
         m = self.model
         keep = (m.eye_net._packs, getattr(m.eye_net, '_stream_w', None), m.refine_net._packs if m.refine_net is not None else None)
         return {'graph': graph, 'inputs': static, 'outputs': out, 'keep': keep, 'eye_mask': eye_mask}

@@ -1201,6 +1201,65 @@ int eve_gaze_events(long long B, int T, const float* pog, const float* origin, c
                     int F, double* store, int* count, int* dropped, float* filtered, float* velocity, uint8_t* event, int* fixation_id,
                     float* fixation_px, float* fixation_ms, uint8_t* fixating, eve_stream_t stream);
 
+/* The eye gate: per frame and eye, is the eye usable?  One launch between the pose derivation and eve_stream_mask_plan turns the
+ * results of the same step -- the pose flags, the solve's reprojection error and inlier count, the derived warps and head angles --
+ * and the tracker's eyelid points into the mask the masked step consumes, and detects blinks with state carried in `state` from one
+ * call to the next.  B streams x T frames.  Float64, every operation rounded on its own (no contraction), in the order written
+ * here; tests/eye_gate_ref.py restates it in numpy.  One wavefront per stream, passes of 64 frames; the bits do not depend on that.
+ *   pose_valid [B*T][2] uint8, reproj_rms [B*T] float, inliers [B*T] uint8, warp [2][B*T][9] float (inv(W), what the eye-warp kernels
+ *   take), h [2][B*T][2] float (pitch, yaw of the head in each eye's normalised space, eve_eye_pose_normalize's convention),
+ *   contours [B*T][2][6][C] float, C = 2 or 3: pixel (u, v[, w]) of the six eyelid points p1 .. p6 of the (left, right) eye in
+ *   eye-aspect-ratio order -- p1, p4 the corners, p2, p3 on the upper lid, p6, p5 below them; lengths [B] int (clamped to 0 .. T),
+ *   reset [B] int.  EACH MAY BE NULL, which turns its criterion off (all T frames, no reset).
+ *   state [B][2][8] double, blinks [B][capacity][4] double, count [B] and dropped [B] int: read and UPDATED IN PLACE.
+ * The state row of (stream, eye): 0 has_base, 1 base (the open eye's aspect ratio), 2 closed, 3 run (the closed frames so far),
+ * 4 min_open, 5 start (the tick of the first closed frame), 6 hold (frames still withheld), 7 tick (the stream's delivered frames
+ * since its last reset; both eyes' rows hold it).  A stream with reset[b] != 0 first zeroes both rows; an eye closed then stores
+ * nothing.  Frames f >= lengths[b]: usable 0, reason 0, openness NaN, blink 0, and no state moves.  For the others, per eye e:
+ *   reason bits (a NaN fails every comparison, towards unusable):
+ *      1 pose         pose_valid[f][e] == 0
+ *      2 reprojection not (rms <= max_reproj_px)
+ *      4 inliers      not (inliers >= min_inliers)
+ *      8 coverage     the 8 x 8 lattice of patch pixels ox_i = ((2i+1)*OW) >> 4, oy_j = ((2j+1)*OH) >> 4 goes through the eye's warp
+ *                     as in eve_eye_warp_u8_to_nchw: X = (m00*ox + m01*oy) + m02, Y, Wd alike, u = X/Wd, v = Y/Wd; a point is inside
+ *                     iff Wd > 0 && u > -1 && u < IW && v > -1 && v < IH; the bit is set iff fewer than min_inside points are.  (With
+ *                     camera_lens upstream the test is made in the undistorted coordinates inv(W) refers to.)
+ *     16 head angle   not (pitch_lo <= h[e][f][0] <= pitch_hi && yaw_lo[e] <= h[e][f][1] <= yaw_hi[e]); an open side is +-infinity
+ *     32 closed, 64 hold-off: the blink machine below (contours != NULL), one walk per eye over the delivered frames in order, with
+ *        tick = state tick + f:
+ *      d(a, b) = sqrt(dx*dx + dy*dy) of the widened pixels; ear = (d(p2,p6) + d(p3,p5)) / (2*d(p1,p4)); KNOWN iff all twelve
+ *      coordinates are finite, every w > 0 (C = 3) and d(p1,p4) != 0.
+ *      known and has_base == 0: base = ear, has_base = 1.  open = ear / base where known, NaN else.
+ *      closed != 0: run += 1; known and open < min_open: min_open = open; then
+ *         known and open > open_ratio: the blink ends -- the row (e, start, tick - 1, min_open) goes to blinks[b][count[b]] and
+ *            count[b] grows, or with count[b] == capacity dropped[b] grows; closed = 0, run = 0, hold = hold_frames;
+ *         else run > max_closed_frames (a wrong baseline): has_base = known, base = ear where known (0 else), closed = 0, run = 0,
+ *            open = ear / base again where known; no row, no hold-off.
+ *      closed == 0: known and open < close_ratio: closed = 1, run = 1, min_open = open, start = tick;
+ *         else known and open >= open_ratio: base = base + r*(ear - base), r = baseline_rise if ear > base else baseline_rate (a peak
+ *            follower: a first frame taken in the middle of a blink does not keep the baseline down).
+ *      Then: closed != 0 sets bit 32 and blink = 1; else hold > 0 sets bit 64 and hold -= 1 (so hold_frames frames from the reopening
+ *      one on are withheld).  Rows of one frame are stored left eye first.  After the frames tick += lengths[b].
+ * Outputs [B*T][2]: usable uint8 (1 iff reason == 0), reason uint8, openness float (open rounded once; NaN where unknown or contours is
+ * NULL), blink uint8.  Kernel name eye_gate_kernel.  Refused without a launch: a null params, state, store, counter or output; B, T or
+ * capacity < 1; contours with C other than 2 or 3; warp without sizes in 1 .. 16384; B*T*36 or B*capacity*4 past 31 bits; a NaN among
+ * the floating-point parameters; with warp, min_inside outside 1 .. 64; with contours, open_ratio <= close_ratio, hold_frames < 0 or
+ * max_closed_frames < 1.  Not offered: thresholds learnt per person, a closure announced before its first closed frame, blink times in
+ * seconds, coverage through the lens model, a gradient.  (Additive: ABI v10.)                                                      */
+typedef struct eve_eye_gate_params {
+    double max_reproj_px;                       /* read where reproj_rms != NULL */
+    double pitch_lo, pitch_hi, yaw_lo[2], yaw_hi[2];   /* read where h != NULL; yaw per eye (left, right) */
+    double close_ratio, open_ratio, baseline_rate, baseline_rise;   /* read where contours != NULL */
+    int min_inliers;                            /* read where inliers != NULL */
+    int min_inside;                             /* read where warp != NULL: ceil(min_coverage * 64) */
+    int hold_frames, max_closed_frames;         /* read where contours != NULL */
+} eve_eye_gate_params;
+int eve_eye_gate(long long B, int T, const uint8_t* pose_valid /* may be NULL */, const float* reproj_rms /* may be NULL */,
+                 const uint8_t* inliers /* may be NULL */, const float* warp /* may be NULL */, const float* h /* may be NULL */,
+                 const float* contours /* may be NULL */, int C, const int* lengths /* may be NULL */, const int* reset /* may be NULL */,
+                 int IW, int IH, int OW, int OH, const eve_eye_gate_params* params, double* state, int capacity, double* blinks, int* count,
+                 int* dropped, uint8_t* usable, uint8_t* reason, float* openness, uint8_t* blink, eve_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
