@@ -206,6 +206,9 @@ SIGNATURES = {
     'eve_undistort_points': [L, P, P, L, P, P, P],
     'eve_calib_append': [L, I, I, P, P, P, P, P, P, P, P, P, P, I, P, P, P, P],
     'eve_calib_fit': [L, I, P, P, P, ctypes.c_double, I, P, P, P, P, P, P, P, P],
+    'eve_screen_calib_append': [L, I, P, P, P, P, P, P, P, P, ctypes.c_double, ctypes.c_double, I, P, P, P, P],
+    'eve_screen_calib_fit': [L, I, P, P, P, I, I, ctypes.c_double, I, ctypes.c_double, P, P, P, P, P, P, P, P, P],
+    'eve_screen_calib_apply': [L, I, P, P, P, P, ctypes.c_double, ctypes.c_double, P, P],
     'eve_gaze_events': [L, I, P, P, P, P, P, P, P, P, P] + [ctypes.c_double] * 4 + [I] + [ctypes.c_double] * 3 + [P, I, P, P, P] + [P] * 8,
     'eve_eye_gate': [L, I, P, P, P, P, P, P, I, P, P, I, I, I, I, POINTER(EyeGateParams), P, I, P, P, P, P, P, P, P, P],
 }

@@ -558,8 +558,8 @@ def fit_gaze_offset(samples, counts=None, huber_mm=None, min_samples=5):
     bool [S].  ok False (kappa, rms_mm, inliers 0): fewer than min_samples rows with weight > 0, a system that is not positive
     definite (every target on one line through the eye, say), no convergence, or |kappa| above 0.35 rad (20 degrees: the fit
     diverged).  One launch, a wavefront per sequence; the host does not wait.  The contract, summation order included, is
-    include/eve_hip.h eve_calib_fit and tests/calib_ref.py.  Not offered: screen-space polynomial or affine calibration,
-    per-sample weights (entry 14 of a row is 1.0, or 0.0 for an absent row), gradients."""
+    include/eve_hip.h eve_calib_fit and tests/calib_ref.py.  Not offered: per-sample weights (entry 14 of a row is 1.0, or 0.0 for
+    an absent row), gradients; the residual that depends on the position on the screen is fit_screen_map's."""
     if not torch.is_tensor(samples) or samples.dtype != torch.float64 or samples.dim() not in (2, 3) or samples.shape[-1] != 16:
         raise TypeError('fit_gaze_offset: samples must be float64 [S, C, 16], got %s %s' % (getattr(samples, 'dtype', type(samples)),
                                                                                           tuple(getattr(samples, 'shape', ()))))
@@ -577,6 +577,157 @@ def fit_gaze_offset(samples, counts=None, huber_mm=None, min_samples=5):
     kappa, rms, used, inliers, good = default_kernels().calib_fit(samples.contiguous(), counts, None, huber_mm, min_samples)
     out = {'kappa': kappa, 'rms_mm': rms, 'used': used, 'inliers': inliers, 'ok': good != 0}
     return {k_: v[0] for k_, v in out.items()} if single else out
+
+
+# ---------------------------------------------------------------------------------------------------------------- the screen-space map
+SCREEN_MODELS = {'offset': 1, 'affine': 2, 'quadratic': 3}      # the kind byte (0: no map) -> 1, 3, 6 terms of (1, u, v, u*u, u*v, v*v)
+SCREEN_CALIB_REPORT = ('rms_mm', 'mean_mm', 'max_mm', 'mean_deg', 'rms_mm_raw', 'mean_mm_raw', 'max_mm_raw', 'mean_deg_raw')
+
+
+def check_screen_model(model, where):
+    """'offset', 'affine' or 'quadratic' -> the kind byte 1, 2, 3; anything else raises ValueError."""
+    if not isinstance(model, str) or model not in SCREEN_MODELS:
+        raise ValueError("%s: model must be 'offset', 'affine' or 'quadratic', got %r" % (where, model))
+    return SCREEN_MODELS[model]
+
+
+def check_max_shift_mm(max_shift_mm, where):
+    """A finite number > 0 (millimetres on the screen) -> float; anything else raises ValueError."""
+    if isinstance(max_shift_mm, bool) or not isinstance(max_shift_mm, (int, float)) or not 0 < max_shift_mm < float('inf'):
+        raise ValueError('%s: max_shift_mm must be a finite number > 0 (millimetres), got %r' % (where, max_shift_mm))
+    return float(max_shift_mm)
+
+
+def check_screen_min_samples(min_samples, where):
+    """None (the model's number of terms decides) or an integer >= 1 -> int."""
+    return 1 if min_samples is None else check_min_samples(min_samples, where)
+
+
+def check_screen_size(screen_size, where):
+    """(W, H), two finite numbers > 0 -> (float, float); anything else raises ValueError."""
+    try:
+        W, H = screen_size
+        ok = all(not isinstance(v, bool) and isinstance(v, (int, float)) and 0 < v < float('inf') for v in (W, H))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('%s: screen_size must be (W, H), two finite numbers > 0 (actual_screen_size), got %r' % (where, screen_size))
+    return float(W), float(H)
+
+
+def screen_calibration_samples(pog_px, o, inv_camera_transformation, pixels_per_millimeter, target_px, screen_size):
+    """What the screen-space map's fit needs of N frames, reduced on the device: pog_px float32 [N, 2] (the pipeline's output point,
+    PoG_px_final or PoG_px_initial, uncorrected), o [N, 3] (the binocular origin), inv_camera_transformation [N, 4, 4],
+    pixels_per_millimeter [N, 2], target_px [N, 2] (the dot the person looked at) and screen_size = actual_screen_size (W, H).
+    -> float64 [N, 12], row i for frame i: u, v, the point and the target in millimetres (2 + 2), the eye in screen coordinates
+    (3), the weight 1.0, two reserved 0.0 (include/eve_hip.h eve_screen_calib_append).  A frame that is not usable -- a value that
+    is not finite, a pixels_per_millimeter that is not > 0, an eye in the screen plane -- gives a row of zeros, which fit_screen_map
+    passes over (its weight is 0)."""
+    ok = lambda t: torch.is_tensor(t) and t.dtype == torch.float32
+    if not ok(pog_px) or pog_px.dim() != 2 or pog_px.shape[1] != 2 or pog_px.shape[0] < 1:
+        raise TypeError('screen_calibration_samples: pog_px must be float32 [N, 2] with N >= 1, got %s %s' % (
+            getattr(pog_px, 'dtype', type(pog_px)), tuple(getattr(pog_px, 'shape', ()))))
+    N = pog_px.shape[0]
+    for name, t, shape in (('o', o, (N, 3)), ('inv_camera_transformation', inv_camera_transformation, (N, 4, 4)),
+                           ('pixels_per_millimeter', pixels_per_millimeter, (N, 2)), ('target_px', target_px, (N, 2))):
+        if not ok(t) or tuple(t.shape) != shape:
+            raise TypeError('screen_calibration_samples: %s must be float32 %s, got %s %s' % (name, list(shape), getattr(t, 'dtype', type(t)),
+                                                                                             tuple(getattr(t, 'shape', ()))))
+    size = check_screen_size(screen_size, 'screen_calibration_samples')
+    dev = pog_px.device
+    samples = torch.zeros((N, 1, 12), dtype=torch.float64, device=dev)
+    count, dropped = torch.zeros((N,), dtype=torch.int32, device=dev), torch.zeros((N,), dtype=torch.int32, device=dev)
+    c = lambda t, *s: t.reshape((N, 1) + s).contiguous()
+    default_kernels().screen_calib_append(c(pog_px, 2), c(o, 3), c(inv_camera_transformation, 4, 4), c(pixels_per_millimeter, 2),
+                                          c(target_px, 2), size, samples, count, dropped)
+    return samples.view(N, 12)
+
+
+def _screen_samples_arg(samples, counts, where):
+    if not torch.is_tensor(samples) or samples.dtype != torch.float64 or samples.dim() not in (2, 3) or samples.shape[-1] != 12:
+        raise TypeError('%s: samples must be float64 [S, C, 12], got %s %s' % (where, getattr(samples, 'dtype', type(samples)),
+                                                                              tuple(getattr(samples, 'shape', ()))))
+    single = samples.dim() == 2
+    if single:
+        samples = samples[None]
+    if samples.numel() == 0:
+        raise ValueError('%s: no samples (shape %s)' % (where, tuple(samples.shape)))
+    if counts is not None:
+        counts = torch.as_tensor(counts).to(device=samples.device, dtype=torch.int32).contiguous()
+        if tuple(counts.shape) != (samples.shape[0],):
+            raise ValueError('%s: counts needs one entry per stream (%d)' % (where, samples.shape[0]))
+    return samples.contiguous(), counts, single
+
+
+def _screen_fit_result(res, kind, single):
+    coef, report, used, inliers, solves, good = res
+    out = {'coef': coef, 'kind': kind, 'ok': good != 0, 'used': used, 'inliers': inliers, 'solves': solves}
+    out.update({name: report[:, i] for i, name in enumerate(SCREEN_CALIB_REPORT)})
+    return {k_: v[0] for k_, v in out.items()} if single else out
+
+
+def fit_screen_map(samples, counts=None, model='affine', huber_mm=None, min_samples=None, max_shift_mm=100.0):
+    """The screen-space map fitted on the device to calibration samples: samples float64 [S, C, 12] ([C, 12]: one stream) as
+    screen_calibration_samples or an EVEStream's store holds them; counts None (all C rows) or S integers: the rows in use.  model:
+    'offset', 'affine' (default) or 'quadratic'; huber_mm None (least squares) or a Huber threshold in millimetres (25 suits 8 mm of
+    fixation noise); min_samples None (the model's number of terms) or more; max_shift_mm: the longest correction at a sample the
+    fit may produce.  -> a dict of coef float64 [S, 2, 6] (axis, term; millimetres), kind uint8 [S] (the model's byte where ok, else
+    0), ok bool [S], used, inliers, solves int32 [S] and the report float64 [S]: rms_mm, mean_mm, max_mm, mean_deg of the corrected
+    point and the same with _raw of the uncorrected one.  ok False (everything but used 0): too few rows with weight > 0, dots that
+    do not determine the model, no convergence within 64 solves, a correction above max_shift_mm.  One launch, a wavefront per
+    stream; the host does not wait.  The contract, summation order included, is include/eve_hip.h eve_screen_calib_fit and
+    tests/screen_calib_ref.py.  Not offered: per-sample weights from the caller (entry 9 of a row is 1.0, or 0.0 for an absent
+    row), cubic or higher models, automatic recalibration, gradients."""
+    samples, counts, single = _screen_samples_arg(samples, counts, 'fit_screen_map')
+    kind = check_screen_model(model, 'fit_screen_map')
+    huber_mm, max_shift_mm = check_huber_mm(huber_mm, 'fit_screen_map'), check_max_shift_mm(max_shift_mm, 'fit_screen_map')
+    min_samples = check_screen_min_samples(min_samples, 'fit_screen_map')
+    res = default_kernels().screen_calib_fit(samples, counts, None, 0, kind, huber_mm, min_samples, max_shift_mm)
+    return _screen_fit_result(res, (res[5] != 0).to(torch.uint8) * kind, single)
+
+
+def _screen_map_arg(coef, kind, S, device, where):
+    coef = torch.as_tensor(coef, dtype=torch.float64).to(device)
+    kind = torch.as_tensor(kind)
+    if coef.dim() == 2 and kind.dim() == 0:
+        coef, kind = coef[None].expand(S, 2, 6), kind[None].expand(S)
+    if tuple(coef.shape) != (S, 2, 6):
+        raise ValueError('%s: coef must be [%d, 2, 6] (stream, axis, term), got %s' % (where, S, tuple(coef.shape)))
+    if tuple(kind.shape) != (S,) or kind.dtype.is_floating_point or kind.dtype == torch.bool:
+        raise ValueError('%s: kind must be %d integers in 0 .. 3 (none, offset, affine, quadratic)' % (where, S))
+    return coef.contiguous(), kind.to(device=device, dtype=torch.uint8).contiguous()
+
+
+def evaluate_screen_map(samples, coef, kind, counts=None):
+    """The accuracy of given maps over samples -- the validation pass -- on the device: samples and counts as fit_screen_map takes
+    them, coef [S, 2, 6] and kind S integers in 0 .. 3 (or one [2, 6] map and one kind for every stream).  -> fit_screen_map's dict
+    with solves 0, inliers = used and ok where a row is present; a map of kind 0 reports the raw numbers in both sets.  Nothing is
+    solved (eve_screen_calib_fit in mode 1)."""
+    samples, counts, single = _screen_samples_arg(samples, counts, 'evaluate_screen_map')
+    coef, kind = _screen_map_arg(coef, kind, samples.shape[0], samples.device, 'evaluate_screen_map')
+    res = default_kernels().screen_calib_fit(samples, counts, None, 1, 0, None, 1, 100.0, coef, kind)
+    return _screen_fit_result(res, kind, single)
+
+
+def apply_screen_map(pog_px, pixels_per_millimeter, coef, kind, screen_size):
+    """The screen-space map applied on the device: pog_px float32 [B, T, 2] ([T, 2]: one stream), pixels_per_millimeter the same
+    shape, coef [B, 2, 6] and kind B integers in 0 .. 3 (one [2, 6] map and one kind for one stream), screen_size (W, H) -> the
+    corrected point, float32 of pog_px's shape, clamped to the screen; a stream of kind 0 gets its input bits
+    (include/eve_hip.h eve_screen_calib_apply)."""
+    ok = lambda t: torch.is_tensor(t) and t.dtype == torch.float32
+    if not ok(pog_px) or pog_px.dim() not in (2, 3) or pog_px.shape[-1] != 2 or pog_px.numel() == 0:
+        raise TypeError('apply_screen_map: pog_px must be float32 [B, T, 2], got %s %s' % (getattr(pog_px, 'dtype', type(pog_px)),
+                                                                                         tuple(getattr(pog_px, 'shape', ()))))
+    if not ok(pixels_per_millimeter) or tuple(pixels_per_millimeter.shape) != tuple(pog_px.shape):
+        raise TypeError('apply_screen_map: pixels_per_millimeter must be float32 %s, got %s %s' % (
+            list(pog_px.shape), getattr(pixels_per_millimeter, 'dtype', type(pixels_per_millimeter)),
+            tuple(getattr(pixels_per_millimeter, 'shape', ()))))
+    size = check_screen_size(screen_size, 'apply_screen_map')
+    single = pog_px.dim() == 2
+    px, ppm = (pog_px[None], pixels_per_millimeter[None]) if single else (pog_px, pixels_per_millimeter)
+    coef, kind = _screen_map_arg(coef, kind, px.shape[0], px.device, 'apply_screen_map')
+    out = default_kernels().screen_calib_apply(px.contiguous(), ppm.contiguous(), coef, kind, size)
+    return out[0] if single else out
 
 
 def warp_eye_patches(frames, warps, size=None, lens=None, format='rgb', matrix='bt601', layout=None):

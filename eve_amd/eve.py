@@ -204,9 +204,7 @@ class EVE(nn.Module):
             both = inter['left_PoG_%s_%s' % (unit, out_suffix)], inter['right_PoG_%s_%s' % (unit, out_suffix)]
             inter['PoG_%s_%s' % (unit, out_suffix)] = _mean2(*both) if eye_valid is None else _fuse2(both[0], both[1], eye_valid)
         inter['PoG_mm_' + out_suffix] = 10.0 * inter['PoG_cm_' + out_suffix]
-        inter['g_' + out_suffix] = default_kernels().combined_gaze(
-            flat('o', 3), inter['PoG_mm_' + out_suffix].detach().reshape(N, 2), flat('left_R' if eye_valid is None else 'combined_R', 3, 3),
-            flat('camera_transformation', 4, 4)).view(B, T, 2)
+        inter['g_' + out_suffix] = self._combined_gaze(d, inter['PoG_mm_' + out_suffix], B, T)
         if cfg.refine_net_enabled:
             w, h = cfg.gaze_heatmap_size
             centres = inter['PoG_px_' + out_suffix].reshape(N, 2)
@@ -333,9 +331,20 @@ class EVE(nn.Module):
         h, w = hf.shape[-2:]
         px = ops.SoftArgmaxFn.apply(hf.reshape(B * T, 1, h, w).float(), tuple(cfg.actual_screen_size)).view(B, T, 2)
         inter['PoG_px_final'] = px
-        inter['PoG_cm_final'] = px * (0.1 * d['millimeters_per_pixel'])
-        inter['g_final'] = default_kernels().combined_gaze(
-            d['o'].reshape(B * T, 3).float(), (10.0 * inter['PoG_cm_final']).detach().reshape(B * T, 2),
+        inter['PoG_cm_final'] = self._px_to_cm(d, px)
+        inter['g_final'] = self._combined_gaze(d, 10.0 * inter['PoG_cm_final'], B, T)
+
+    @staticmethod
+    def _px_to_cm(d, px):
+        """A point in screen pixels [B, T, 2] -> centimetres (eve.py:160)."""
+        return px * (0.1 * d['millimeters_per_pixel'])
+
+    @staticmethod
+    def _combined_gaze(d, pog_mm, B, T):
+        """The combined gaze angles [B, T, 2] towards a point in millimetres on the screen, from the binocular origin d['o'], rotated
+        by d['combined_R'] where a masked EVEStream step has put one, by left_R as in the reference otherwise."""
+        return default_kernels().combined_gaze(
+            d['o'].reshape(B * T, 3).float(), pog_mm.detach().reshape(B * T, 2),
             d.get('combined_R', d['left_R']).reshape(B * T, 3, 3).float(), d['camera_transformation'].reshape(B * T, 4, 4).float()).view(B, T, 2)
 
     # ------------------------------------------------------------------------------------------ streaming (stream.py)
@@ -343,7 +352,8 @@ class EVE(nn.Module):
                        'PoG_cm_initial', 'g_final', 'PoG_px_final', 'PoG_cm_final')
 
     def _predict_sequence(self, d, eye_states, refine_states, reset=None, return_heatmaps=False, lengths=None, masked=False,
-                          eye_mask=None, pose_gate=None, face_state=None, render=None, calibration=None, events=None, gate=None):
+                          eye_mask=None, pose_gate=None, face_state=None, render=None, calibration=None, events=None, gate=None,
+                          screen_calibration=None):
         """The prediction part of forward() for one chunk of an EVEStream: eval only, no labels, no losses.  d: the chunk's
         inputs [B, Tc, ...] (not modified; camera_frame may be any one key of eye_net.EYE_FRAME_KEYS or camera_surface, and the screen any one
         key of refine_net.SCREEN_FRAME_KEYS or screen_surface; the eyes as patches, as camera_frame + {left,right}_eye_warp, or as camera_frame +
@@ -385,7 +395,15 @@ class EVE(nn.Module):
         'count', 'dropped': int32 [B], 'frame_size': None or the camera frame's (IW, IH)}: one eve_eye_gate launch between eye_pose_batch and
         the mask plan, over pose_valid, face_reproj_rms, face_inliers, the (derived) warps and head angles and d['eye_contours'] -- each
         where the spec has a criterion for it -- with the step's lengths and reset flags.  Its `usable` becomes eye_mask, or is ANDed
-        into it, so a gated step is a masked step; the result gains data.EYE_GATE_KEYS.  None issues no launch."""
+        into it, so a gated step is a masked step; the result gains data.EYE_GATE_KEYS.  None issues no launch.
+        screen_calibration: None, or EVEStream's screen-space map {'coef': float64 [B, 2, 6], 'kind': uint8 [B], 'apply': bool, 'store':
+        None or (samples float64 [B, C, 12], count int32 [B], dropped int32 [B])}, a stage on the step's OUTPUT point PoG_px_<out>
+        (<out> = final with a RefineNet, else initial) that runs before the events stage and the render hook.  With a store and
+        screen_calibration_target [B, Tc, 2] (and optionally screen_calibration_valid [B, Tc]) in d, one eve_screen_calib_append launch
+        appends every usable frame -- screen_calibration_valid, t < lengths[b], the masked plan's valid -- from the UNCORRECTED point.
+        With apply, one eve_screen_calib_apply launch corrects the point: PoG_px_<out> becomes the corrected one, PoG_cm_<out> and
+        g_<out> follow by _px_to_cm / _combined_gaze (selected per stream, so a stream of kind 0 keeps its bits), and the result gains
+        PoG_px_<out>_raw and screen_calibrated, bool [B].  None issues no launch."""
         assert not self.training, 'EVE._predict_sequence is eval-only'
         B = eye_input(d).shape[0]
         posed, faced = has_pose_form(d), face_landmarks_key(d) is not None
@@ -425,7 +443,13 @@ class EVE(nn.Module):
                                                   **screen_capture(d))
             inter['heatmap_final'] = hf
             self._final_block(d, inter, hf)
+        if screen_calibration is not None:
+            self._screen_calibration(d, inter, screen_calibration, None if lengths is None else lengths[:B], plan)
         out = {k_: inter[k_] for k_ in self.PREDICTION_KEYS if k_ in inter}
+        if screen_calibration is not None and screen_calibration['apply']:
+            suffix = 'final' if 'PoG_px_final' in inter else 'initial'
+            out['PoG_px_%s_raw' % suffix] = inter['PoG_px_%s_raw' % suffix]
+            out['screen_calibrated'] = inter['screen_calibrated']
         if calib is not None:
             out['calibrated'] = calib['calibrated']
             for side in ('left', 'right'):
@@ -489,6 +513,36 @@ class EVE(nn.Module):
         default_kernels().calib_append(both('_g_initial', 2), f32('head_R', 3, 3), both('_o', 3), both('_R', 3, 3),
                                        f32('inv_camera_transformation', 4, 4), f32('pixels_per_millimeter', 2), f32('calibration_target', 2),
                                        store[0], store[1], store[2], valid, lengths, None if plan is None else plan['eye_valid'])
+
+    def _screen_calibration(self, d, inter, sc, lengths, plan):
+        """The screen-space map's stage of an EVEStream step, on the output point PoG_px_<out>: the collecting launch
+        (eve_screen_calib_append, on the uncorrected point, so collecting while the map is applied does not compound), then the
+        applying one (eve_screen_calib_apply), after which PoG_cm_<out> and g_<out> are the expressions of _final_block on the
+        corrected point where the stream has a map."""
+        suffix = 'final' if 'PoG_px_final' in inter else 'initial'
+        raw = inter['PoG_px_' + suffix]
+        B, T = raw.shape[:2]
+        f32 = lambda t, *s_: t.reshape((B, T) + s_).float().contiguous()
+        size = tuple(self.config.actual_screen_size)
+        ppm = f32(d['pixels_per_millimeter'], 2)
+        if sc['store'] is not None and 'screen_calibration_target' in d:
+            valid = d.get('screen_calibration_valid')
+            if valid is not None:
+                valid = valid.contiguous()
+                valid = valid.view(torch.uint8) if valid.dtype == torch.bool else valid
+            default_kernels().screen_calib_append(f32(raw, 2), f32(d['o'], 3), f32(d['inv_camera_transformation'], 4, 4), ppm,
+                                                  f32(d['screen_calibration_target'], 2), size, sc['store'][0], sc['store'][1], sc['store'][2],
+                                                  valid, lengths, None if plan is None else plan['valid'])
+        if sc['apply']:
+            px = default_kernels().screen_calib_apply(f32(raw, 2), ppm, sc['coef'], sc['kind'], size).view(B, T, 2)
+            mapped = sc['kind'] != 0
+            sel = mapped[:, None, None]
+            cm = self._px_to_cm(d, px)
+            inter['PoG_px_%s_raw' % suffix] = raw
+            inter['PoG_px_' + suffix] = px
+            inter['PoG_cm_' + suffix] = torch.where(sel, cm, inter['PoG_cm_' + suffix])
+            inter['g_' + suffix] = torch.where(sel, self._combined_gaze(d, 10.0 * cm, B, T), inter['g_' + suffix])
+            inter['screen_calibrated'] = mapped
 
     # ------------------------------------------------------------------------------------------ eve.py:286-439
     def calculate_losses_and_metrics(self, d, inter, out):

@@ -966,6 +966,100 @@ class HipKernels(object):
                                         self._p(kappa_store), self._p(ok_store), self._stream()))
         return kappa, rms, used, inliers, good
 
+    # ------------------------------------------------------------------ screen-space gaze calibration
+    def screen_calib_append(self, pog, origin, inv_cam, ppm, target, screen_size, samples, count, dropped, valid=None, lengths=None,
+                            frame_valid=None):
+        """Reduce the usable frames of B streams x T frames to the screen map fit's 12 doubles and append them, in frame order, to
+        the stores: pog [B, T, 2] (the output point before the map), origin [B, T, 3], inv_cam [B, T, 4, 4], ppm [B, T, 2], target
+        [B, T, 2] float32; screen_size (W, H); samples float64 [B, C, 12], count and dropped int32 [B], UPDATED IN PLACE; valid uint8
+        [B, T], lengths int32 [B], frame_valid uint8 [B, T] or None (include/eve_hip.h eve_screen_calib_append)."""
+        ok = lambda t, dtype: torch.is_tensor(t) and t.dtype == dtype
+        if not ok(pog, torch.float32) or pog.dim() != 3 or pog.shape[2] != 2:
+            raise TypeError('screen_calib_append: pog must be float32 [B, T, 2], got %s %s' % (
+                getattr(pog, 'dtype', type(pog)), tuple(getattr(pog, 'shape', ()))))
+        B, T = pog.shape[:2]
+        if not ok(samples, torch.float64) or samples.dim() != 3 or samples.shape[0] != B or samples.shape[2] != 12:
+            raise TypeError('screen_calib_append: samples must be float64 [%d, C, 12], got %s %s' % (
+                B, getattr(samples, 'dtype', type(samples)), tuple(getattr(samples, 'shape', ()))))
+        C = samples.shape[1]
+        for name, t, dtype, shape in (('origin', origin, torch.float32, (B, T, 3)), ('inv_cam', inv_cam, torch.float32, (B, T, 4, 4)),
+                                      ('ppm', ppm, torch.float32, (B, T, 2)), ('target', target, torch.float32, (B, T, 2)),
+                                      ('count', count, torch.int32, (B,)), ('dropped', dropped, torch.int32, (B,)),
+                                      ('valid', valid, torch.uint8, (B, T)), ('lengths', lengths, torch.int32, (B,)),
+                                      ('frame_valid', frame_valid, torch.uint8, (B, T))):
+            if (t is not None or name not in ('valid', 'lengths', 'frame_valid')) and (not ok(t, dtype) or tuple(t.shape) != shape):
+                raise TypeError('screen_calib_append: %s must be %s %s, got %s %s' % (
+                    name, str(dtype).replace('torch.', ''), list(shape), getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ()))))
+        for t in (pog, origin, inv_cam, ppm, target, samples, count, dropped, valid, lengths, frame_valid):
+            if t is not None and not t.is_contiguous():
+                raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        self._ck(self.lib.eve_screen_calib_append(B, T, self._p(pog), self._p(origin), self._p(inv_cam), self._p(ppm), self._p(target),
+                                                  self._p(valid), self._p(lengths), self._p(frame_valid), float(screen_size[0]),
+                                                  float(screen_size[1]), C, self._p(samples), self._p(count), self._p(dropped), self._stream()))
+
+    def screen_calib_fit(self, samples, count=None, select=None, mode=0, kind=2, huber_mm=None, min_samples=1, max_shift_mm=100.0,
+                         coef_store=None, kind_store=None):
+        """The screen map fit (mode 0) or the evaluation of the stored map (mode 1), one wavefront per stream: samples float64
+        [S, C, 12]; count int32 [S] or None (all C rows); select uint8 [S] or None (0: the stream is not touched); kind 1 offset, 2
+        affine, 3 quadratic; huber_mm None or millimetres > 0; coef_store float64 [S, 2, 6] and kind_store uint8 [S] (both or
+        neither; mode 1 reads them), written in mode 0 where the fit is ok and only there.  -> (coef float64 [S, 2, 6], report
+        float64 [S, 8] in the order of data.SCREEN_CALIB_REPORT, used, inliers, solves int32 [S], ok uint8 [S]) (include/eve_hip.h
+        eve_screen_calib_fit)."""
+        ok = lambda t, dtype: torch.is_tensor(t) and t.dtype == dtype
+        if not ok(samples, torch.float64) or samples.dim() != 3 or samples.shape[2] != 12 or samples.shape[0] < 1 or samples.shape[1] < 1:
+            raise TypeError('screen_calib_fit: samples must be float64 [S, C, 12], got %s %s' % (
+                getattr(samples, 'dtype', type(samples)), tuple(getattr(samples, 'shape', ()))))
+        S, C = samples.shape[:2]
+        for name, t, dtype, shape in (('count', count, torch.int32, (S,)), ('select', select, torch.uint8, (S,)),
+                                      ('coef_store', coef_store, torch.float64, (S, 2, 6)), ('kind_store', kind_store, torch.uint8, (S,))):
+            if t is not None and (not ok(t, dtype) or tuple(t.shape) != shape):
+                raise TypeError('screen_calib_fit: %s must be %s %s, got %s %s' % (
+                    name, str(dtype).replace('torch.', ''), list(shape), getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ()))))
+        if (coef_store is None) != (kind_store is None):
+            raise TypeError('screen_calib_fit: coef_store and kind_store come together')
+        if mode not in (0, 1) or (mode == 1 and coef_store is None):
+            raise ValueError('screen_calib_fit: mode is 0 (fit) or 1 (evaluate coef_store / kind_store), got %r' % (mode,))
+        if mode == 0 and kind not in (1, 2, 3):
+            raise ValueError('screen_calib_fit: kind is 1 (offset), 2 (affine) or 3 (quadratic), got %r' % (kind,))
+        if huber_mm is not None and not (isinstance(huber_mm, (int, float)) and not isinstance(huber_mm, bool) and 0 < huber_mm < float('inf')):
+            raise ValueError('screen_calib_fit: huber_mm must be None or a finite number > 0, got %r' % (huber_mm,))
+        if isinstance(min_samples, bool) or not isinstance(min_samples, int) or min_samples < 1:
+            raise ValueError('screen_calib_fit: min_samples must be an integer >= 1, got %r' % (min_samples,))
+        if isinstance(max_shift_mm, bool) or not isinstance(max_shift_mm, (int, float)) or not max_shift_mm > 0:
+            raise ValueError('screen_calib_fit: max_shift_mm must be a number > 0, got %r' % (max_shift_mm,))
+        for t in (samples, count, select, coef_store, kind_store):
+            if t is not None and not t.is_contiguous():
+                raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        new = lambda *shape, dtype=torch.float64: torch.empty(shape, dtype=dtype, device=samples.device)
+        coef, report = new(S, 2, 6), new(S, 8)
+        used, inliers, solves, good = (new(S, dtype=torch.int32), new(S, dtype=torch.int32), new(S, dtype=torch.int32),
+                                       new(S, dtype=torch.uint8))
+        self._ck(self.lib.eve_screen_calib_fit(S, C, self._p(samples), self._p(count), self._p(select), int(mode), int(kind),
+                                               0.0 if huber_mm is None else float(huber_mm), int(min_samples), float(max_shift_mm),
+                                               self._p(coef), self._p(report), self._p(used), self._p(inliers), self._p(solves), self._p(good),
+                                               self._p(coef_store), self._p(kind_store), self._stream()))
+        return coef, report, used, inliers, solves, good
+
+    def screen_calib_apply(self, px, ppm, coef, kind, screen_size):
+        """The screen map applied: px float32 [B, T, 2], ppm float32 [B, T, 2], coef float64 [B, 2, 6], kind uint8 [B], screen_size
+        (W, H) -> float32 [B, T, 2]; a stream of kind 0 gets its input bits (include/eve_hip.h eve_screen_calib_apply)."""
+        ok = lambda t, dtype: torch.is_tensor(t) and t.dtype == dtype
+        if not ok(px, torch.float32) or px.dim() != 3 or px.shape[2] != 2 or px.shape[0] < 1 or px.shape[1] < 1:
+            raise TypeError('screen_calib_apply: px must be float32 [B, T, 2], got %s %s' % (
+                getattr(px, 'dtype', type(px)), tuple(getattr(px, 'shape', ()))))
+        B, T = px.shape[:2]
+        for name, t, dtype, shape in (('ppm', ppm, torch.float32, (B, T, 2)), ('coef', coef, torch.float64, (B, 2, 6)),
+                                      ('kind', kind, torch.uint8, (B,))):
+            if not ok(t, dtype) or tuple(t.shape) != shape:
+                raise TypeError('screen_calib_apply: %s must be %s %s, got %s %s' % (
+                    name, str(dtype).replace('torch.', ''), list(shape), getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ()))))
+        if not (px.is_contiguous() and ppm.is_contiguous() and coef.is_contiguous() and kind.is_contiguous()):
+            raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        out = torch.empty_like(px)
+        self._ck(self.lib.eve_screen_calib_apply(B, T, self._p(px), self._p(ppm), self._p(coef), self._p(kind), float(screen_size[0]),
+                                                 float(screen_size[1]), self._p(out), self._stream()))
+        return out
+
     # ------------------------------------------------------------------ gaze filtering, fixation / saccade events
     GAZE_EVENT_KEYS = ('PoG_px_filtered', 'gaze_velocity', 'gaze_event', 'fixation_id', 'fixation_px', 'fixation_ms', 'fixating')
 

@@ -8,6 +8,8 @@ carried from one call to the next.
     stream.reset([3])                                      # stream 3 starts from zero state at the next step()
     stream.step(dict(chunk, calibration_target=dots))      # collect per-person calibration samples (see "Calibration" below)
     fit = stream.fit_calibration(huber_mm=25.0)            # fit each eye's offset on the device; later steps apply it
+    stream.step(dict(chunk, screen_calibration_target=dots))          # collect for the screen-space map ("Screen-space calibration")
+    fit = stream.fit_screen_calibration(model='affine')    # fit it on the device; later steps correct their output point
     out = stream.step(chunk, events=eve_amd.GazeEventSpec(fps=60))   # + the filtered PoG, gaze velocity, fixation / saccade events
     rows = stream.fixations()                              # the completed fixations of every stream (see "Gaze events" below)
     out = stream.step(chunk, gate=eve_amd.EyeGateSpec(blink=eve_amd.BlinkSpec()))   # the mask made on the device (see "The eye gate" below)
@@ -52,8 +54,38 @@ bool [B].  A stream that is not calibrated keeps the bits of an uncalibrated EVE
 zero), and an EVEStream on which no calibration call was ever made issues exactly the launches it always issued.  Samples are
 always collected from the raw angles, so collecting while calibrated does not compound.  The offset and the store belong to the
 person, not to the clip: reset() touches neither, and get_state() / set_state() do not hold them (get_calibration /
-set_calibration do).  Not offered: screen-space polynomial or affine calibration, per-sample weights from the caller (entry 14
-of a sample is reserved at 1.0), automatic or continuous recalibration, gradients, application in EVE.forward.
+set_calibration do).  Not offered: per-sample weights from the caller (entry 14 of a sample is reserved at 1.0), automatic or
+continuous recalibration, gradients, application in EVE.forward.
+
+Screen-space calibration.  What remains after kappa depends on the position on the screen -- a camera-to-screen transform a little
+off, a head-pose dependent bias, a cornea that is not the average one -- and is what a tracker's five- or nine-dot procedure removes:
+a low-order map of the OUTPUT point.  <out> is final with a RefineNet, else initial (the rule GazeEventSpec(source=None) uses).  With
+(x, y) = PoG_px_<out>, u = 2x / W - 1, v = 2y / H - 1 over actual_screen_size and phi = (1, u, v, u*u, u*v, v*v), the models 'offset',
+'affine' (default) and 'quadratic' use 1, 3 and 6 terms; the correction is coef[axis][term] in MILLIMETRES on the screen, and the
+corrected pixel x + s_x * pixels_per_millimeter is clamped to the screen.  A chunk with screen_calibration_target, float32
+[B, Tc, 2], and optionally screen_calibration_valid, bool or uint8 [B, Tc], makes the step append what the fit needs of every usable
+frame (one eve_screen_calib_append launch after the point is known, inside the graph; float64 [B, C, 12], C =
+screen_calibration_capacity, 96 bytes a row; a full store drops and counts) -- always from the UNCORRECTED point, so collecting while a
+map is applied does not compound.  The keys are deliberately not calibration_target: kappa's collector reads the networks' raw
+angles, this one the pipeline's output under whatever kappa is applied at that step, so the two rounds of dots are separate data (one
+chunk may carry both), and A MAP BELONGS TO THE KAPPA IT WAS COLLECTED UNDER: fit kappa first, and after a new kappa collect and fit
+the map again.  fit_screen_calibration() fits by one eve_screen_calib_fit launch (linear least squares by Cholesky, float64, fixed
+summation order; with huber_mm re-weighted until no coefficient moves, at most 64 solves) and reports accuracy the way trackers do:
+rms_mm, mean_mm, max_mm on the screen and mean_deg at the eye, for the corrected point and (with _raw) the uncorrected one.
+evaluate_screen_calibration() reports the same for the STORED map over the current store and changes nothing: the validation pass
+(clear_screen_calibration_samples, show other dots, collect, evaluate).  From the first fit or set_screen_calibration on, the step
+runs one eve_screen_calib_apply launch right after the point it corrects: PoG_px_<out> is the corrected point, PoG_cm_<out> and g_<out>
+are recomputed from it by the expressions _final_block uses, the uncorrected point appears as PoG_px_<out>_raw, and the result gains
+screen_calibrated, bool [B]; heat maps, every *_initial key under a RefineNet, the per-eye angles and the kappa collector are
+untouched.  The stage runs before the events stage and the render hook, so filtering, fixations and overlay markers that name
+PoG_px_<out> see the corrected point.  A stream without a map (kind 0) keeps its bits, and an EVEStream on which none of these calls was
+made and whose chunks carry no such key issues exactly the launches it always issued.  lengths, eye_mask, gate= and every camera and
+screen form combine; collection honours lengths and the masked plan's valid.  Needs inv_camera_transformation, pixels_per_millimeter
+and the origins (applying also millimeters_per_pixel and camera_transformation): ValueError otherwise, as for
+screen_calibration_valid without its target.  reset(), get_state() and set_state() do not touch any of it (get_screen_calibration /
+set_screen_calibration / clear_screen_calibration / clear_screen_calibration_samples / screen_calibration_counts /
+screen_calibration_samples do).  tests/screen_calib_ref.py states the arithmetic, exact to the bit.  Not offered: per-sample weights
+from the caller (entry 9 of a sample is reserved at 1.0), cubic or higher models, automatic recalibration, a gradient, EVE.forward.
 
 Gaze events.  What comes out of the networks is a raw per-frame point of gaze, and every consumer of an eye tracker then smooths
 it, differentiates it and cuts it into fixations and saccades -- on the host that is a sync per chunk and a loop per stream, with
@@ -99,7 +131,8 @@ def _module_key(m):
 
 
 class EVEStream(object):
-    def __init__(self, model, num_streams, use_graph=True, calibration_capacity=1024, fixation_capacity=256, blink_capacity=256):
+    def __init__(self, model, num_streams, use_graph=True, calibration_capacity=1024, fixation_capacity=256, blink_capacity=256,
+                 screen_calibration_capacity=1024):
         if model.training:
             raise ValueError('EVEStream runs inference only: call model.eval() first')
         self.model = model
@@ -131,6 +164,16 @@ class EVEStream(object):
         self._calib_kappa = torch.zeros((B, 2, 2), dtype=torch.float32, device=self.device)
         self._calib_ok = torch.zeros((B, 2), dtype=torch.uint8, device=self.device)
         self._calib_apply = False
+        # the screen-space map: the sample store (eve_screen_calib_append appends inside the step), each stream's coefficients
+        # (axis, term) in millimetres and its kind byte (0 none, 1 offset, 2 affine, 3 quadratic; eve_screen_calib_fit writes them).
+        # _screen_apply: a fit or a set_screen_calibration has happened, so the steps run the applying graphs.
+        if isinstance(screen_calibration_capacity, bool) or not isinstance(screen_calibration_capacity, int) or screen_calibration_capacity < 1:
+            raise ValueError('screen_calibration_capacity must be an integer >= 1, got %r' % (screen_calibration_capacity,))
+        self.screen_calibration_capacity = screen_calibration_capacity
+        self._screen_store = None                # made at the first collecting step or screen calibration call: B * C * 96 bytes
+        self._screen_coef = torch.zeros((B, 2, 6), dtype=torch.float64, device=self.device)
+        self._screen_kind = torch.zeros((B,), dtype=torch.uint8, device=self.device)
+        self._screen_apply = False
         # gaze events (step(chunk, events=spec)): the filter's and the running fixation's state row per stream, the store of completed
         # fixations and its counters -- eve_gaze_events reads and writes them inside the step (and the graph)
         if isinstance(fixation_capacity, bool) or not isinstance(fixation_capacity, int) or fixation_capacity < 1:
@@ -159,7 +202,8 @@ class EVEStream(object):
         open fixation into the store -- if it lasted min_fixation_s -- and starts its filter, its events and its frame count afresh,
         by the same device flags; only its fixation id counter runs on, so ids stay unique within a recording.  The per-person calibration -- each eye's kappa and the
         sample store -- is not touched: it belongs to the person, not to the clip (clear_calibration,
-        clear_calibration_samples)."""
+        clear_calibration_samples); neither are the screen-space map and its sample store (clear_screen_calibration,
+        clear_screen_calibration_samples)."""
         m = np.zeros(self.num_streams, dtype=bool) if self._pending is None else self._pending
         m |= self._stream_mask(streams, 'reset')
         self._pending = m
@@ -265,6 +309,139 @@ class EVEStream(object):
         """The sample store itself, float64 [B, 2, C, 16] (fresh): rows 0 .. count - 1 of (stream, eye) in the order the frames
         came, in the layout of data.calibration_samples / data.fit_gaze_offset."""
         return self._store()[0].clone()
+
+    # ------------------------------------------------------------------ screen-space calibration
+    def _screen_samples(self):
+        if self._screen_store is None:
+            B, C = self.num_streams, self.screen_calibration_capacity
+            self._screen_store = (torch.zeros((B, C, 12), dtype=torch.float64, device=self.device),
+                                  torch.zeros((B,), dtype=torch.int32, device=self.device),
+                                  torch.zeros((B,), dtype=torch.int32, device=self.device))
+        return self._screen_store
+
+    def _screen_result(self, res):
+        from .data import SCREEN_CALIB_REPORT
+        coef, report, used, inliers, solves, ok = res
+        out = {'coef': coef, 'kind': self._screen_kind.clone(), 'ok': ok != 0, 'used': used, 'inliers': inliers, 'solves': solves,
+               'screen_calibrated': self._screen_kind != 0}
+        out.update({name: report[:, i] for i, name in enumerate(SCREEN_CALIB_REPORT)})
+        return out
+
+    def fit_screen_calibration(self, streams=None, model='affine', huber_mm=None, min_samples=None, max_shift_mm=100.0):
+        """Fit the screen-space map of the given streams (None = all; indices or a bool mask) to the samples collected so far: one
+        eve_screen_calib_fit launch, a wavefront per stream.  model: 'offset' (one constant shift), 'affine' (1, u, v: the default) or
+        'quadratic' (+ u*u, u*v, v*v), u, v the output point over the screen in -1 .. 1; the map gives the correction in millimetres
+        that brings the pipeline's output point onto the dots -- linear least squares, or with huber_mm a Huber loss of that many
+        millimetres by re-weighting (at most 64 solves), which keeps frames in which the person looked elsewhere from bending the
+        map.  -> a dict of device tensors (the host does not wait): coef float64 [B, 2, 6] (axis, term; millimetres), kind uint8
+        [B] (the stored kinds after the fit), ok bool [B], used, inliers, solves int32 [B], the accuracy report float64 [B] --
+        rms_mm, mean_mm, max_mm, mean_deg (the angle at the eye) of the corrected point against the dots, and rms_mm_raw,
+        mean_mm_raw, max_mm_raw, mean_deg_raw of the uncorrected one -- and screen_calibrated bool [B].  ok is False -- and the
+        stream's stored map stays what it was -- with fewer usable samples than max(min_samples, the model's terms), dots that do
+        not determine the model (on one line for 'affine'; fewer than six positions, or a 5 x 1 row, for 'quadratic'), no
+        convergence, or a correction above max_shift_mm at a sample (a divergence guard).  Streams not named are left alone and
+        report ok False.  The following steps apply the stored maps (a new graph per chunk shape).  A map belongs to the kappa it
+        was collected under: after fit_calibration / set_calibration / clear_calibration collect and fit it again.
+        tests/screen_calib_ref.py states the fit in numpy."""
+        from .data import check_huber_mm, check_max_shift_mm, check_screen_min_samples, check_screen_model
+        kind = check_screen_model(model, 'fit_screen_calibration')
+        huber_mm, max_shift_mm = check_huber_mm(huber_mm, 'fit_screen_calibration'), check_max_shift_mm(max_shift_mm, 'fit_screen_calibration')
+        min_samples = check_screen_min_samples(min_samples, 'fit_screen_calibration')
+        select = None if streams is None else self._device_mask(streams, 'fit_screen_calibration').to(torch.uint8).contiguous()
+        samples, count, _ = self._screen_samples()
+        res = default_kernels().screen_calib_fit(samples, count, select, 0, kind, huber_mm, min_samples, max_shift_mm,
+                                                 self._screen_coef, self._screen_kind)
+        self._screen_apply = True
+        return self._screen_result(res)
+
+    def evaluate_screen_calibration(self, streams=None):
+        """The validation pass: the accuracy of the STORED maps over the samples the store holds now -- clear the samples
+        (clear_screen_calibration_samples), show other dots, collect, call this.  One eve_screen_calib_fit launch in mode 1; nothing
+        is solved and nothing changes.  -> fit_screen_calibration's dict (solves 0, inliers = used, ok where the stream holds a
+        sample); a stream without a map reports the raw numbers in both sets."""
+        select = None if streams is None else self._device_mask(streams, 'evaluate_screen_calibration').to(torch.uint8).contiguous()
+        samples, count, _ = self._screen_samples()
+        return self._screen_result(default_kernels().screen_calib_fit(samples, count, select, 1, 0, None, 1, 100.0,
+                                                                      self._screen_coef, self._screen_kind))
+
+    def get_screen_calibration(self):
+        """The stored maps (fresh tensors): coef float64 [B, 2, 6] (axis, term; millimetres) and kind uint8 [B] (0 none, 1 offset, 2
+        affine, 3 quadratic)."""
+        return self._screen_coef.clone(), self._screen_kind.clone()
+
+    def set_screen_calibration(self, coef, kind, streams=None):
+        """Load maps known from an earlier session, in get_screen_calibration()'s layout: coef [B, 2, 6] (converted to float64), kind
+        B integers in 0 .. 3; the rows of the given streams are used (None = all).  Terms the kind does not use are stored as 0.
+        Values are not judged."""
+        B = self.num_streams
+        coef = torch.as_tensor(coef, dtype=torch.float64)
+        kind_host = kind.detach().cpu() if torch.is_tensor(kind) else torch.as_tensor(np.asarray(kind))
+        if tuple(coef.shape) != (B, 2, 6):
+            raise ValueError('set_screen_calibration: coef must be [%d, 2, 6] (stream, axis, term), got %s' % (B, tuple(coef.shape)))
+        if tuple(kind_host.shape) != (B,) or kind_host.dtype.is_floating_point or kind_host.dtype == torch.bool or \
+                int(kind_host.min()) < 0 or int(kind_host.max()) > 3:
+            raise ValueError('set_screen_calibration: kind must be %d integers in 0 .. 3 (none, offset, affine, quadratic)' % B)
+        terms = torch.tensor([0, 1, 3, 6])[kind_host.long()]
+        coef = coef.to(self.device) * (torch.arange(6)[None, :] < terms[:, None]).to(torch.float64)[:, None, :].to(self.device)
+        m = self._device_mask(streams, 'set_screen_calibration')
+        self._screen_coef.copy_(torch.where(m[:, None, None], coef, self._screen_coef))
+        self._screen_kind.copy_(torch.where(m, kind_host.to(torch.uint8).to(self.device), self._screen_kind))
+        self._screen_apply = True
+
+    def clear_screen_calibration(self, streams=None):
+        """Forget the maps of the given streams (None = all): they get the uncorrected bits again.  The sample store stays."""
+        m = self._device_mask(streams, 'clear_screen_calibration')
+        self._screen_coef.copy_(torch.where(m[:, None, None], torch.zeros_like(self._screen_coef), self._screen_coef))
+        self._screen_kind.copy_(torch.where(m, torch.zeros_like(self._screen_kind), self._screen_kind))
+        if streams is None:
+            self._screen_apply = False           # nothing left to apply: back to the launches of an EVEStream without a map
+
+    def clear_screen_calibration_samples(self, streams=None):
+        """Empty the screen map's sample store of the given streams (None = all), and their dropped counters."""
+        if self._screen_store is None:
+            self._stream_mask(streams, 'clear_screen_calibration_samples')
+            return
+        m = self._device_mask(streams, 'clear_screen_calibration_samples')
+        _, count, dropped = self._screen_store
+        count.copy_(torch.where(m, torch.zeros_like(count), count))
+        dropped.copy_(torch.where(m, torch.zeros_like(dropped), dropped))
+
+    def screen_calibration_counts(self):
+        """-> (count, dropped), int32 [B] device tensors (fresh): the samples each stream holds, and those a full store
+        (screen_calibration_capacity) turned away."""
+        _, count, dropped = self._screen_samples()
+        return count.clone(), dropped.clone()
+
+    def screen_calibration_samples(self):
+        """The sample store itself, float64 [B, C, 12] (fresh): rows 0 .. count - 1 of a stream in the order the frames came, in
+        the layout of data.screen_calibration_samples / data.fit_screen_map."""
+        return self._screen_samples()[0].clone()
+
+    def _check_screen_calibration(self, chunk, B, Tc):
+        """step()'s screen calibration keys, and what an applying step needs, checked before anything is launched or captured."""
+        target, valid = chunk.get('screen_calibration_target'), chunk.get('screen_calibration_valid')
+        if target is None and valid is None and not self._screen_apply:
+            return
+        if target is None and valid is not None:
+            raise ValueError('step: screen_calibration_valid comes with screen_calibration_target')
+        what = 'screen_calibration_target' if target is not None else 'an applied screen calibration'
+        for key in ('inv_camera_transformation', 'pixels_per_millimeter') + (() if target is not None and not self._screen_apply else
+                                                                           ('millimeters_per_pixel', 'camera_transformation')):
+            if key not in chunk:
+                raise ValueError('step: %s needs the screen geometry (%s) in the chunk' % (what, key))
+        if 'left_o' not in chunk and not has_pose_form(chunk):
+            raise ValueError('step: %s needs the eyes\' origins o (left_o, right_o, or a pose form) in the chunk' % what)
+        if target is not None:
+            if (not torch.is_tensor(target) or target.dtype != torch.float32 or tuple(target.shape) != (B, Tc, 2) or
+                    target.device != self.device):
+                raise ValueError('step: screen_calibration_target must be a float32 [%d, %d, 2] tensor on %s, got %s %s' % (
+                    B, Tc, self.device, getattr(target, 'dtype', type(target)), tuple(getattr(target, 'shape', ()))))
+            self._screen_samples()               # allocated here, before any capture
+        if valid is not None:
+            if (not torch.is_tensor(valid) or valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) != (B, Tc) or
+                    valid.device != self.device):
+                raise ValueError('step: screen_calibration_valid must be a bool or uint8 [%d, %d] tensor on %s, got %s %s' % (
+                    B, Tc, self.device, getattr(valid, 'dtype', type(valid)), tuple(getattr(valid, 'shape', ()))))
 
     # ------------------------------------------------------------------ gaze events
     def _event_buffers(self):
@@ -580,6 +757,9 @@ class EVEStream(object):
         if self._calib_apply or 'calibration_target' in chunk:       # (neither: the call an uncalibrated EVEStream always made)
             extra['calibration'] = {'kappa': self._calib_kappa, 'ok': self._calib_ok, 'apply': self._calib_apply,
                                     'store': self._store() if 'calibration_target' in chunk else None}
+        if self._screen_apply or 'screen_calibration_target' in chunk:      # (neither: no keyword, no launch)
+            extra['screen_calibration'] = {'coef': self._screen_coef, 'kind': self._screen_kind, 'apply': self._screen_apply,
+                                           'store': self._screen_samples() if 'screen_calibration_target' in chunk else None}
         if events is not None:                   # events: None or a _check_events plan; the keyword goes along only then
             state, store, count, dropped = self._event_buffers()
             extra['events'] = dict(events, state=state, store=store, count=count, dropped=dropped)
@@ -640,6 +820,8 @@ class EVEStream(object):
         if events is not None:                   # the gaze events' keys: dict(key='fixation_px', valid='fixating'), key='PoG_px_filtered'
             from .data import GAZE_EVENT_KEYS
             results += GAZE_EVENT_KEYS
+        if self._screen_apply:                   # an applied screen map: the uncorrected point can be drawn beside the corrected one
+            results += ('PoG_px_final_raw' if ref is not None else 'PoG_px_initial_raw', 'screen_calibrated')
         for m in spec.markers:
             for k_ in (m[0], m[1]):
                 if k_ is not None and k_ not in chunk and k_ not in results:
@@ -890,6 +1072,19 @@ class EVEStream(object):
         Once fit_calibration or set_calibration has been called the step applies the stored offsets (module docstring,
         "Calibration"): the result gains calibrated [B] and <side>_g_initial_raw, and needs head_R too.
 
+        screen_calibration_target, float32 [B, Tc, 2] on the model's device -- the dot the person was asked to look at, in
+        actual_screen_size pixels -- and optionally screen_calibration_valid, bool or uint8 [B, Tc] (default: every frame), make this
+        a collecting step of the screen-space map (module docstring, "Screen-space calibration"): one eve_screen_calib_append launch
+        after the step's output point PoG_px_<out> is known (<out>: final with a RefineNet, else initial), inside the graph, appends
+        every usable frame -- usable iff screen_calibration_valid, t < lengths[b], valid[b, t] on a masked step, every input finite,
+        pixels_per_millimeter > 0 and the eye off the screen plane -- in frame order, from the UNCORRECTED point.  The keys are part
+        of the graph's key like any chunk tensor's; they are not calibration_target (kappa's collector reads the raw angles; one
+        chunk may carry both).  Needs inv_camera_transformation, pixels_per_millimeter and the origins (left_o, right_o, or a pose
+        form): ValueError otherwise, as for screen_calibration_valid without its target.  Once fit_screen_calibration or
+        set_screen_calibration has been called the step corrects its output point by one eve_screen_calib_apply launch, before the
+        events stage and the render hook: PoG_px_<out> is the corrected point, PoG_cm_<out> and g_<out> follow, and the result gains
+        PoG_px_<out>_raw and screen_calibrated [B]; it then needs millimeters_per_pixel and camera_transformation too.
+
         events: None, or an eve_amd.GazeEventSpec -- one eve_gaze_events launch at the end of the step (before the overlay) and inside
         the captured graph post-processes the step's point of gaze (spec.source: PoG_px_final with a RefineNet, else
         PoG_px_initial) the way every consumer of an eye tracker does, with no host sync and with state carried from step to step
@@ -961,6 +1156,7 @@ class EVEStream(object):
         if render is not None:
             render = self._render_plan(chunk, render) if events is None else self._render_plan(chunk, render, events)
         self._check_calibration(chunk, B, Tc)
+        self._check_screen_calibration(chunk, B, Tc)
         if ragged:
             self._upload_lengths(lengths)
         if masked and has_pose_form(chunk):
@@ -1017,7 +1213,7 @@ class EVEStream(object):
         (render: None or a _render_plan -- its OverlaySpec by value), with a face-landmark form eye_net.face_huber_px (a launch
         argument, so baked in), the gaze events (events: None or a _check_events plan -- its GazeEventSpec by value and its source;
         frame_time's presence is a chunk key), the eye gate (gate: None or a _check_gate plan -- its EyeGateSpec by value and the frame size;
-        eye_contours' presence and shape are a chunk key), whether a calibration is applied (`calibrated`; a collecting step differs by its chunk keys), and every chunk tensor's key, shape and dtype -- which of the two landmark keys among them."""
+        eye_contours' presence and shape are a chunk key), whether a calibration is applied (`calibrated`; a collecting step differs by its chunk keys), whether a screen-space map is applied (likewise), and every chunk tensor's key, shape and dtype -- which of the two landmark keys among them."""
         ref = self.model.refine_net
         spec = None if render is None else render['spec'].key()
         layouts = (self.model.eye_net.camera_layout, None if ref is None else ref.screen_layout)
@@ -1026,7 +1222,7 @@ class EVEStream(object):
             from .data import check_huber_px
             huber = check_huber_px(self.model.eye_net.face_huber_px, 'face_huber_px')
         return (return_heatmaps, ragged, masked, self.model.eye_net.yuv_matrix, None if ref is None else ref.yuv_matrix, spec, layouts, huber,
-                self._calib_apply) + (() if events is None else ((events['spec'].key(), events['source']),)) + \
+                self._calib_apply, self._screen_apply) + (() if events is None else ((events['spec'].key(), events['source']),)) + \
             (() if gate is None else (('gate', gate['spec'].key(), gate['frame_size']),)) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
 
     def _graph_for(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None):
@@ -1061,7 +1257,8 @@ class EVEStream(object):
             # append every sample three times
             # (and the gaze events' state, store and counters: a capture would otherwise tick the filter three times)
             carried = self._state_tensors() + [self._face_pose, self._calib_kappa, self._calib_ok] + list(self._calib_store or ()) + \
-                list(self._events or ()) + list(self._gate or ())          # (and the eye gate's: its ticks, baselines and blinks)
+                list(self._events or ()) + list(self._gate or ()) + \
+                list(self._screen_store or ())                             # (the eye gate's ticks, baselines and blinks; the screen map's samples)
             snap = [t.clone() for t in carried]
             for _ in range(2):
                 self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate)

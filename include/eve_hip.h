@@ -1145,7 +1145,8 @@ int eve_face_pose_solve_ex(long long S, int T, int L, int landmark_cols, const f
  * there, kappa_store[q] = (float)kappa and ok_store[q] = 1 -- a failed fit leaves what that eye had.  A stream counts as
  * calibrated where the flags of both its eyes are set.  Kernel name calib_fit_kernel.  Refused without a launch: a null pointer,
  * S or C < 1, min_samples < 1, a NaN huber_mm, one store without the other.  Not offered: per-sample weights (entry 14 is 1.0, or
- * 0.0 for an absent row), screen-space polynomial calibration, a gradient.  (Additive: ABI v10.)                                 */
+ * 0.0 for an absent row), a gradient; the residual that depends on the position on the screen is eve_screen_calib_*'s, below.
+ * (Additive: ABI v10.)                                                                                                            */
 int eve_calib_append(long long B, int T, int E, const float* g, const float* head_R, const float* origin, const float* R,
                      const float* inv_cam, const float* ppm, const float* target, const uint8_t* valid /* may be NULL */,
                      const int* lengths /* may be NULL */, const uint8_t* eye_valid /* may be NULL */, int C, double* samples, int* count,
@@ -1153,6 +1154,81 @@ int eve_calib_append(long long B, int T, int E, const float* g, const float* hea
 int eve_calib_fit(long long S, int C, const double* samples, const int* count /* may be NULL */, const uint8_t* select /* may be NULL */,
                   double huber_mm, int min_samples, double* kappa, double* rms_mm, int* used, int* inliers, uint8_t* ok,
                   float* kappa_store /* may be NULL */, uint8_t* ok_store /* may be NULL */, eve_stream_t stream);
+
+/* Screen-space gaze calibration: the residual that depends on the position on the screen -- a camera-to-screen transform a little
+ * off, a head-pose dependent bias, a cornea that is not the average one: what a tracker's five- or nine-dot procedure removes --
+ * as a low-order map of the pipeline's OUTPUT point.  With W x H the screen in pixels and (x, y) the output point in pixels:
+ *   u = (x + x) / W - 1, v = (y + y) / H - 1, phi = (1, u, v, u*u, u*v, v*v) cut to K terms
+ *   kind 0: no map; 1 'offset' K = 1; 2 'affine' K = 3; 3 'quadratic' K = 6 (any other kind byte is read as 0)
+ *   the correction in MILLIMETRES on the screen, axis a = x, y:  s_a = C[a][0];  s_a = s_a + phi_k * C[a][k], k = 1 .. K-1
+ *   the corrected pixel  x' = x + s_x * ppm_x, clamped by x' < 0 ? 0 : (x' > W ? W : x') (a NaN stays a NaN), rounded to float
+ * Coefficients are double [2][6] per stream (axis, term), unused terms 0.  Three launches: collect, fit (or evaluate), apply.
+ * Float64, every operation rounded on its own (no contraction); tests/screen_calib_ref.py restates all three in numpy.
+ *
+ * eve_screen_calib_append: B streams x T frames.  One THREAD per stream walks frames f = 0 .. T-1 in order (n = b*T + f), reduces
+ * every usable frame to a row of 12 doubles and appends it to the stream's store (eve_calib_append's scheme without the eye axis):
+ *   pog [B*T][2] (the output point BEFORE this map, pixels), origin [B*T][3] (o), inv_cam [B*T][16], ppm [B*T][2], target [B*T][2]
+ *   (pixels) float.  valid [B*T] uint8, lengths [B] int (clamped to 0 .. T), frame_valid [B*T] uint8 (a masked step's valid): each
+ *   may be NULL.  samples [B][C][12] double, count [B] int, dropped [B] int: read and UPDATED IN PLACE.
+ * The row, inputs widened to double first:
+ *   u, v as above; xm = x / ppm_x, ym = y / ppm_y; tmx = tx / ppm_x, tmy = ty / ppm_y;
+ *   e_i = ((T_i0*o0 + T_i1*o1) + T_i2*o2) + T_i3, i = 0 .. 2 (the eye in screen coordinates); 1.0 (the weight); 0.0, 0.0 (reserved)
+ * A frame is usable iff valid[n], f < lengths[b], frame_valid[n], every input and every entry of the row is finite, both ppm > 0
+ * and e_2 != 0.  A usable frame goes to row count[b] and count[b] grows; with count[b] == C it is dropped and dropped[b] grows.
+ * Kernel name screen_calib_append_kernel.  Refused without a launch: a null pointer, B, T or C < 1, W or H not > 0, index ranges
+ * past 31 bits.
+ *
+ * eve_screen_calib_fit: S streams, one wavefront each, over rows 0 .. n-1 of samples [S][C][12], n = count[q] clamped to 0 .. C
+ * (count NULL: C).  A row whose weight w (entry 9) is not > 0 is absent.  mode 0 fits a map of `kind` (1 .. 3); mode 1 evaluates
+ * the STORED map (coef_store, kind_store) and solves nothing.
+ *   One pass at coefficients C, per row: p_a by the sum above; ex = tmx - xm, ey = tmy - ym; rx = p_x - ex, ry = p_y - ey;
+ *   r2 = rx*rx + ry*ry, r = sqrt(r2).  Without a loss ws = w, cost = w*r2, inl = 1.  With huber_mm = h > 0: inlier iff not r > h,
+ *   ws = w*(inlier ? 1 : h/r), cost = w*(inlier ? r2 : h*((r + r) - h)), inl = inlier (eve_calib_fit's definitions).
+ *   The contributions: (ws*phi_i)*phi_j for i = 0 .. K-1, j = 0 .. i (the lower triangle of G); (ws*phi_i)*ex (bx); (ws*phi_i)*ey
+ *   (by); cost, w*r2, w*r, inl, 1.0.
+ *   SUMMATION ORDER: lane l starts its partial sums at 0.0 and adds its rows l, l + 64, l + 128, ... in that order; then every
+ *   column is summed from 0.0 over the partial sums of lanes 0, 1, .. 63 in that order: the same bits in every lane.
+ *   Solve: Cholesky of G row by row -- for j = 0 .. K-1: s = G_jj; s = s - L_jk*L_jk, k = 0 .. j-1; the pivot fails unless
+ *   G_jj > 0 and s > 1e-10*G_jj; L_jj = sqrt(s); for i > j: t = G_ij; t = t - L_ik*L_jk, k = 0 .. j-1; L_ij = t / L_jj.  Per axis:
+ *   y_i = (b_i - sum_{k<i} L_ik*y_k) / L_ii for i = 0 .. K-1, then C_i = (y_i - sum_{k>i} L_ki*C_k) / L_ii for i = K-1 .. 0, each
+ *   sum subtracted term by term in ascending k.
+ *   Schedule: used = the sum of 1.0.  From C = 0: pass, solve -> the solution without a loss.  With huber_mm > 0 repeat (pass at
+ *   the current C, solve) until every new coefficient is finite and max |C_new - C_old| <= 1e-6 mm; failed after the 64th solve.
+ *   The final pass at the solution takes, per present row: w*r2, w*r, inl, 1.0 and w*deg as ordered sums; the maxima of r and of
+ *   the correction's length sqrt(p_x*p_x + p_y*p_y) (each from 0.0 by m = r > m ? r : m, so independent of the order); and the
+ *   same sums and maximum at C = 0 (p_x = p_y = 0.0): the error of the uncorrected point.  deg is the angle at the eye between
+ *   a = ((xm + p_x) - e0, (ym + p_y) - e1, -e2), towards the corrected point, and b = (tmx - e0, tmy - e1, -e2), towards the target:
+ *     a x b = (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0), |a x b| = sqrt((c0*c0 + c1*c1) + c2*c2), a . b = (a0*b0 + a1*b1) + a2*b2,
+ *     deg = atan2(|a x b|, a . b) * 57.29577951308232
+ *   The fit fails (ok = 0) when used < max(min_samples, K), the first cost is not finite, a pivot fails (dots on one line for
+ *   'affine'; fewer than six distinct dot positions, or a 5 x 1 row, for 'quadratic'), no convergence, or the longest correction
+ *   over the present rows exceeds max_shift_mm (a divergence guard, as 0.35 rad is for kappa).  Mode 1 is the final pass alone
+ *   (no loss; inliers = used; ok iff used >= 1); a stored map of kind 0 has p = 0 and reports the raw numbers in both sets.
+ * Outputs per stream: coef [S][2][6] double; report [S][8] double = rms_mm = sqrt(sum w*r2 / used), mean_mm = sum w*r / used,
+ * max_mm, mean_deg = sum w*deg / used, then the same four at C = 0 (rms_mm_raw, mean_mm_raw, max_mm_raw, mean_deg_raw); used,
+ * inliers, solves [S] int; ok [S] uint8.  Where ok is 0 every output but used is 0.  select [S] uint8 or NULL: a stream with
+ * select[q] == 0 is not touched (ok = 0, used = 0).  coef_store [S][2][6] double and kind_store [S] uint8 (both or neither; mode 1
+ * needs them): in mode 0, where ok and only there, coef_store[q] = coef and kind_store[q] = kind -- a failed fit leaves the map
+ * the stream had; mode 1 reads them and writes neither.  The two degree outputs go through atan2, whose last bits belong to the
+ * maths library; everything else is fixed to the bit.  Kernel name screen_calib_fit_kernel.  Refused without a launch: a null
+ * pointer, S or C < 1, a mode other than 0 or 1, one store without the other, mode 1 without stores, and in mode 0 a kind outside
+ * 1 .. 3, min_samples < 1, a NaN huber_mm, max_shift_mm not > 0.
+ *
+ * eve_screen_calib_apply: one thread per frame n of B*T; stream b = n / T reads coef [B][2][6] and kind [B]: px_out [B*T][2] float
+ * from px_in [B*T][2] and ppm [B*T][2] float by the expressions at the top; a stream of kind 0 gets its input BITS.  Kernel name
+ * screen_calib_apply_kernel.  Refused without a launch: a null pointer, B or T < 1, W or H not > 0, index ranges past 31 bits.
+ * Not offered: per-sample weights from the caller (entry 9 is 1.0, or 0.0 for an absent row), cubic or higher models, automatic
+ * recalibration, a gradient.  (All three additive: ABI v10.)                                                                      */
+int eve_screen_calib_append(long long B, int T, const float* pog, const float* origin, const float* inv_cam, const float* ppm,
+                            const float* target, const uint8_t* valid /* may be NULL */, const int* lengths /* may be NULL */,
+                            const uint8_t* frame_valid /* may be NULL */, double W, double H, int C, double* samples, int* count,
+                            int* dropped, eve_stream_t stream);
+int eve_screen_calib_fit(long long S, int C, const double* samples, const int* count /* may be NULL */,
+                         const uint8_t* select /* may be NULL */, int mode, int kind, double huber_mm, int min_samples, double max_shift_mm,
+                         double* coef, double* report, int* used, int* inliers, int* solves, uint8_t* ok,
+                         double* coef_store /* may be NULL */, uint8_t* kind_store /* may be NULL */, eve_stream_t stream);
+int eve_screen_calib_apply(long long B, int T, const float* px_in, const float* ppm, const double* coef, const uint8_t* kind, double W,
+                           double H, float* px_out, eve_stream_t stream);
 
 /* Gaze filtering and fixation / saccade events: the post-processing every consumer of an eye tracker runs on the per-frame point of
  * gaze -- a one-euro filter (Casiez et al. 2012), the angular velocity of the gaze vector, velocity-threshold labels (I-VT), the
