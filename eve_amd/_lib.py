@@ -211,6 +211,9 @@ SIGNATURES = {
     'eve_screen_calib_apply': [L, I, P, P, P, P, ctypes.c_double, ctypes.c_double, P, P],
     'eve_gaze_events': [L, I, P, P, P, P, P, P, P, P, P] + [ctypes.c_double] * 4 + [I] + [ctypes.c_double] * 3 + [P, I, P, P, P] + [P] * 8,
     'eve_eye_gate': [L, I, P, P, P, P, P, P, I, P, P, I, I, I, I, POINTER(EyeGateParams), P, I, P, P, P, P, P, P, P, P],
+    'eve_gaze_history_plan': [L, I, P, P, P, P, P, P, ctypes.c_double, ctypes.c_double, I, ctypes.c_double, ctypes.c_double, I, I,
+                              ctypes.c_double, ctypes.c_double, P, P, P, P],
+    'eve_gaze_history_update': [L, I, I, I, P, P, P, ctypes.c_double, ctypes.c_double, P, P, P],
 }
 EXPORTS = sorted(list(SIGNATURES) + ['eve_abi_version', 'eve_last_error', 'eve_last_kernel'])
 

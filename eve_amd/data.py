@@ -819,6 +819,8 @@ class OverlaySpec(object):
                    drawn in list order.  The default is the reference's look at 1080p: the initial estimate (180, 180, 0), then the
                    refined one (0, 180, 0), radii 10 / 14, a black outline.
       heat         True: blend heatmap_final in heat_color (default red) up to alpha heat_amax (0..255, default 128)
+      heat_key     None, or the name of a per_frame=True GazeHistorySpec of the same step (history=...): that map's frame is blended
+                   in place of heatmap_final (axes up to 1024; not together with heat=True)
       inset        None, 'eyes' (the step's eye patches as [right | left]) or the key of a uint8 [B, Tc, h, w, 3] RGB chunk entry;
                    inset_xy (x0, y0) of its top-left pixel, None: flush in the bottom-right corner; inset_zoom 1..4 (nearest);
                    inset_mirror (default True, as the reference shows the eyes)
@@ -826,7 +828,7 @@ class OverlaySpec(object):
     DEFAULT_MARKERS = (dict(key='PoG_px_initial', fill=(180, 180, 0)), dict(key='PoG_px_final', fill=(0, 180, 0)))
 
     def __init__(self, out_format='nv12', matrix=None, markers=DEFAULT_MARKERS, heat=False, heat_color=(255, 0, 0), heat_amax=128,
-                 inset='eyes', inset_xy=None, inset_zoom=1, inset_mirror=True):
+                 inset='eyes', inset_xy=None, inset_zoom=1, inset_mirror=True, heat_key=None):
         from .kernels import OVERLAY_MAX_MARKERS, OVERLAY_OUT_FORMATS, YUV_MATRICES
         if out_format not in OVERLAY_OUT_FORMATS:
             raise ValueError('OverlaySpec: out_format must be rgb, bgr, nv12 or i420, got %r' % (out_format,))
@@ -848,6 +850,10 @@ class OverlaySpec(object):
                          _color(m.get('outline', (0, 0, 0)), 'OverlaySpec: markers[%d] outline' % i)))
         if not 0 <= int(heat_amax) <= 255:
             raise ValueError('OverlaySpec: heat_amax must be in 0..255, got %r' % (heat_amax,))
+        if heat_key is not None and (not isinstance(heat_key, str) or not heat_key):
+            raise ValueError('OverlaySpec: heat_key must be None or the name of a per_frame GazeHistorySpec, got %r' % (heat_key,))
+        if heat_key is not None and heat:
+            raise ValueError('OverlaySpec: heat_key blends a gaze history map in place of heatmap_final: not together with heat=True')
         if inset is not None and not isinstance(inset, str):
             raise ValueError("OverlaySpec: inset must be None, 'eyes' or the key of a uint8 [B, Tc, h, w, 3] chunk entry")
         if not 1 <= int(inset_zoom) <= 4:
@@ -856,10 +862,11 @@ class OverlaySpec(object):
         self.heat, self.heat_color, self.heat_amax = bool(heat), _color(heat_color, 'OverlaySpec: heat_color'), int(heat_amax)
         self.inset, self.inset_zoom, self.inset_mirror = inset, int(inset_zoom), bool(inset_mirror)
         self.inset_xy = None if inset_xy is None else (int(inset_xy[0]), int(inset_xy[1]))
+        self.heat_key = heat_key
 
     def key(self):
         return (self.out_format, self.matrix, self.markers, self.heat, self.heat_color, self.heat_amax, self.inset, self.inset_xy,
-                self.inset_zoom, self.inset_mirror)
+                self.inset_zoom, self.inset_mirror, self.heat_key)
 
     def __eq__(self, other):
         return isinstance(other, OverlaySpec) and self.key() == other.key()
@@ -970,6 +977,154 @@ def gaze_events(pog_px, o, inv_camera_transformation, pixels_per_millimeter, spe
                                         flush=torch.ones((S,), dtype=torch.int32, device=dev))
     out = dict(out)
     out.update(fixations=store, fixation_count=count, fixation_dropped=dropped)
+    return out
+
+
+GAZE_HISTORY_SOURCES = ('PoG_px_initial', 'PoG_px_final', 'PoG_px_filtered', 'fixation_px', 'heatmap_final')
+GAZE_HISTORY_MAX_AXIS = 2048
+
+
+class GazeHistorySpec(object):
+    """What EVEStream.step(chunk, history=spec) adds to the step (eve_gaze_history_plan + eve_gaze_history_update): the time-decayed
+    history of the point of gaze -- per stream the map M_t = decay_per_ms^(ms since the previous frame) * M_{t-1} + w_t * G_t, which is
+    the reference's windowed sum (its initial_gaze_history / refined_gaze_history) as a recurrence, carried from step to step.
+      name            the result key: <name> float32 [B, MH, MW], and with per_frame <name>_frames float32 [B, Tc, MH, MW]
+      source          'PoG_px_initial', 'PoG_px_final', 'PoG_px_filtered', 'fixation_px' (the last two need events= in the same step),
+                      'heatmap_final' (the network's own maps: needs a RefineNet and size == gaze_heatmap_size), or None: PoG_px_final
+                      with a RefineNet, else PoG_px_initial
+      valid_key       None or the key of a bool / uint8 [B, Tc] entry of the result or the chunk, ANDed into the frame's usability
+                      (source='fixation_px', valid_key='fixating': the fixation heat map)
+      size            (MW, MH), each 1 .. 2048; None: config.gaze_heatmap_size
+      sigma           of the Gaussian, in map pixels, > 0; None: config.gaze_heatmap_sigma_history
+      decay_per_ms    in (0, 1]; None: config.gaze_history_map_decay_per_ms; 1.0: no decay
+      weight          'frame': every usable frame deposits 1 (the reference's); 'seconds': the time since the previous tick, capped by
+                      max_gap_s (with decay_per_ms=1: a dwell map in seconds)
+      fps             for chunks without frame_time (float64 [B, Tc] seconds, which wins when both are there)
+      floor           added to every Gaussian; 1e-8 reproduces the reference's maps
+      normalize       True: every deposit times 1 / (2 pi sigma^2), so the map integrates to the weight deposited
+      per_frame       True: also the map after every frame
+    Instances compare and hash by value: the spec is part of a captured graph's key, and a map is tied to its spec.  Not offered:
+    areas of interest and dwell-per-region tables, per-eye maps, a windowed history (as opposed to the decayed one), anisotropic or
+    screen-millimetre sigmas, gradients, EVE.forward (its create_images path keeps the torch restatement), maps larger than 2048 per
+    axis."""
+
+    def __init__(self, name='gaze_history', source=None, valid_key=None, size=None, sigma=None, decay_per_ms=None, weight='frame',
+                 max_gap_s=0.075, fps=None, floor=0.0, normalize=False, per_frame=False):
+        number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and np.isfinite(v)
+        if not isinstance(name, str) or not name:
+            raise ValueError('GazeHistorySpec: name must be a non-empty string, got %r' % (name,))
+        if source is not None and source not in GAZE_HISTORY_SOURCES:
+            raise ValueError('GazeHistorySpec: source must be None or one of %s, got %r' % (', '.join(GAZE_HISTORY_SOURCES), source))
+        if valid_key is not None and (not isinstance(valid_key, str) or not valid_key):
+            raise ValueError('GazeHistorySpec: valid_key must be None or the key of a [B, Tc] entry, got %r' % (valid_key,))
+        if size is not None:
+            axis = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 1 <= int(v) <= GAZE_HISTORY_MAX_AXIS
+            if not isinstance(size, (tuple, list)) or len(size) != 2 or not axis(size[0]) or not axis(size[1]):
+                raise ValueError('GazeHistorySpec: size must be (MW, MH), integers in 1 .. %d, got %r' % (GAZE_HISTORY_MAX_AXIS, size))
+            size = (int(size[0]), int(size[1]))
+        if sigma is not None and (not number(sigma) or not sigma > 0):
+            raise ValueError('GazeHistorySpec: sigma must be a finite number > 0, got %r' % (sigma,))
+        if decay_per_ms is not None and (not number(decay_per_ms) or not 0 < decay_per_ms <= 1):
+            raise ValueError('GazeHistorySpec: decay_per_ms must lie in (0, 1], got %r' % (decay_per_ms,))
+        if weight not in ('frame', 'seconds'):
+            raise ValueError("GazeHistorySpec: weight must be 'frame' or 'seconds', got %r" % (weight,))
+        if not number(max_gap_s) or not max_gap_s > 0:
+            raise ValueError('GazeHistorySpec: max_gap_s must be a finite number > 0, got %r' % (max_gap_s,))
+        if fps is not None and (not number(fps) or not fps > 0):
+            raise ValueError('GazeHistorySpec: fps must be a finite number > 0, got %r' % (fps,))
+        if not number(floor) or floor < 0:
+            raise ValueError('GazeHistorySpec: floor must be a finite number >= 0, got %r' % (floor,))
+        self.name, self.source, self.valid_key, self.size, self.weight = name, source, valid_key, size, weight
+        self.sigma = None if sigma is None else float(sigma)
+        self.decay_per_ms = None if decay_per_ms is None else float(decay_per_ms)
+        self.max_gap_s, self.fps, self.floor = float(max_gap_s), None if fps is None else float(fps), float(floor)
+        self.normalize, self.per_frame = bool(normalize), bool(per_frame)
+
+    def key(self):
+        return (self.name, self.source, self.valid_key, self.size, self.sigma, self.decay_per_ms, self.weight, self.max_gap_s, self.fps,
+                self.floor, self.normalize, self.per_frame)
+
+    def __eq__(self, other):
+        return isinstance(other, GazeHistorySpec) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'GazeHistorySpec(name=%r, source=%r, valid_key=%r, size=%r, sigma=%r, decay_per_ms=%r, weight=%r, max_gap_s=%r, fps=%r, ' \
+               'floor=%r, normalize=%r, per_frame=%r)' % self.key()
+
+    def resolved(self, config=None):
+        """-> (size (MW, MH), sigma, decay_per_ms) with the config's values where the spec leaves them open."""
+        from .config import get_config
+        cfg = config if config is not None else get_config()
+        size = self.size if self.size is not None else (int(cfg.gaze_heatmap_size[0]), int(cfg.gaze_heatmap_size[1]))
+        sigma = self.sigma if self.sigma is not None else float(cfg.gaze_heatmap_sigma_history)
+        decay = self.decay_per_ms if self.decay_per_ms is not None else float(cfg.gaze_history_map_decay_per_ms)
+        if not (1 <= size[0] <= GAZE_HISTORY_MAX_AXIS and 1 <= size[1] <= GAZE_HISTORY_MAX_AXIS) or not sigma > 0 or not 0 < decay <= 1:
+            raise ValueError('GazeHistorySpec: the config gives size %r, sigma %r, decay_per_ms %r' % (size, sigma, decay))
+        return size, sigma, decay
+
+    def launch_params(self, config=None):
+        """-> the two launches' scalars, computed here in double: size, alpha = -0.5 / sigma^2, ln_decay = log(decay_per_ms), gain = 1
+        or 1 / (2 pi sigma^2), and the spec's own numbers."""
+        import math
+        size, sigma, decay = self.resolved(config)
+        return {'size': size, 'alpha': -0.5 / (sigma * sigma), 'ln_decay': math.log(decay), 'seconds': self.weight == 'seconds',
+                'max_gap_s': self.max_gap_s, 'fps': self.fps, 'floor': self.floor,
+                'gain': 1.0 / (2.0 * math.pi * sigma * sigma) if self.normalize else 1.0}
+
+
+def _bool_rows(t, shape, what):
+    if not torch.is_tensor(t) or t.dtype not in (torch.bool, torch.uint8) or tuple(t.shape) != shape:
+        raise TypeError('%s must be bool or uint8 %s' % (what, list(shape)))
+    t = t.contiguous()
+    return t.view(torch.uint8) if t.dtype == torch.bool else t
+
+
+def gaze_history(spec, screen_size, pog_px=None, heatmaps=None, frame_time=None, valid=None, lengths=None):
+    """The gaze history of S recorded streams, stand-alone and from fresh state: spec a GazeHistorySpec (its source and valid_key are
+    not looked at); screen_size (W, H) of the pixels pog_px is in; pog_px float32 [S, T, 2], or heatmaps float32 [S, T, MH, MW] or
+    [S, T, 1, MH, MW] (the heat source) -- one of the two; frame_time None (then spec.fps) or float64 [S, T] seconds; valid None or bool /
+    uint8 [S, T]; lengths None or int32 [S] on the device.  The two launches of EVEStream.step(history=...).  -> {<name>: float32
+    [S, MH, MW], <name>_frames: float32 [S, T, MH, MW] (with per_frame), 'state': float64 [S, 8]} as device tensors; the host does not
+    wait.  Not offered: see GazeHistorySpec."""
+    if not isinstance(spec, GazeHistorySpec):
+        raise ValueError('gaze_history: spec must be an eve_amd.GazeHistorySpec, got %s' % type(spec).__name__)
+    if (pog_px is None) == (heatmaps is None):
+        raise ValueError('gaze_history: pog_px or heatmaps, one of the two')
+    P = spec.launch_params()
+    MW, MH = P['size']
+    if pog_px is not None:
+        if not torch.is_tensor(pog_px) or pog_px.dtype != torch.float32 or pog_px.dim() != 3 or pog_px.shape[2] != 2 or pog_px.numel() == 0:
+            raise TypeError('gaze_history: pog_px must be float32 [S, T, 2], got %s %s' % (getattr(pog_px, 'dtype', type(pog_px)),
+                                                                                          tuple(getattr(pog_px, 'shape', ()))))
+        S, T = pog_px.shape[:2]
+        dev, pog_px = pog_px.device, pog_px.contiguous()
+    else:
+        if (not torch.is_tensor(heatmaps) or heatmaps.dtype != torch.float32 or heatmaps.dim() not in (4, 5) or heatmaps.numel() == 0 or
+                tuple(heatmaps.shape[-2:]) != (MH, MW) or (heatmaps.dim() == 5 and heatmaps.shape[2] != 1)):
+            raise TypeError('gaze_history: heatmaps must be float32 [S, T, %d, %d] (the spec\'s size), got %s %s' % (
+                MH, MW, getattr(heatmaps, 'dtype', type(heatmaps)), tuple(getattr(heatmaps, 'shape', ()))))
+        S, T = heatmaps.shape[:2]
+        dev, heatmaps = heatmaps.device, heatmaps.reshape(S, T, MH, MW).contiguous()
+    if frame_time is None and spec.fps is None:
+        raise ValueError('gaze_history: frame_time, or a spec with fps')
+    if frame_time is not None and (not torch.is_tensor(frame_time) or frame_time.dtype != torch.float64 or tuple(frame_time.shape) != (S, T)):
+        raise TypeError('gaze_history: frame_time must be float64 [%d, %d] seconds' % (S, T))
+    if valid is not None:
+        valid = _bool_rows(valid, (S, T), 'gaze_history: valid')
+    if lengths is not None and (not torch.is_tensor(lengths) or lengths.dtype != torch.int32 or tuple(lengths.shape) != (S,)):
+        raise TypeError('gaze_history: lengths must be an int32 [%d] tensor' % S)
+    k = default_kernels()
+    state = torch.zeros((S, 8), dtype=torch.float64, device=dev)
+    maps = torch.zeros((S, MH, MW), dtype=torch.float32, device=dev)
+    coef, clear = k.gaze_history_plan(P, screen_size, state, T, pog=pog_px, frame_time=None if frame_time is None else frame_time.contiguous(),
+                                      valid=valid, lengths=None if lengths is None else lengths.contiguous())
+    frames = k.gaze_history_update(P, coef, clear, maps, heat=heatmaps, per_frame=spec.per_frame)
+    out = {spec.name: maps, 'state': state}
+    if spec.per_frame:
+        out[spec.name + '_frames'] = frames
     return out
 
 

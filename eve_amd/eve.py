@@ -353,7 +353,7 @@ class EVE(nn.Module):
 
     def _predict_sequence(self, d, eye_states, refine_states, reset=None, return_heatmaps=False, lengths=None, masked=False,
                           eye_mask=None, pose_gate=None, face_state=None, render=None, calibration=None, events=None, gate=None,
-                          screen_calibration=None):
+                          screen_calibration=None, history=None):
         """The prediction part of forward() for one chunk of an EVEStream: eval only, no labels, no losses.  d: the chunk's
         inputs [B, Tc, ...] (not modified; camera_frame may be any one key of eye_net.EYE_FRAME_KEYS or camera_surface, and the screen any one
         key of refine_net.SCREEN_FRAME_KEYS or screen_surface; the eyes as patches, as camera_frame + {left,right}_eye_warp, or as camera_frame +
@@ -403,7 +403,12 @@ class EVE(nn.Module):
         appends every usable frame -- screen_calibration_valid, t < lengths[b], the masked plan's valid -- from the UNCORRECTED point.
         With apply, one eve_screen_calib_apply launch corrects the point: PoG_px_<out> becomes the corrected one, PoG_cm_<out> and
         g_<out> follow by _px_to_cm / _combined_gaze (selected per stream, so a stream of kind 0 keeps its bits), and the result gains
-        PoG_px_<out>_raw and screen_calibrated, bool [B].  None issues no launch."""
+        PoG_px_<out>_raw and screen_calibrated, bool [B].  None issues no launch.
+        history: None, or EVEStream's gaze history stage, a list of {'spec': a data.GazeHistorySpec, 'source': the result key it
+        accumulates, 'P': the launches' scalars, 'state': float64 [B, 8], 'maps': float32 [B, MH, MW]}: per entry one
+        eve_gaze_history_plan and one eve_gaze_history_update launch, after the events stage and before the render hook, over the step's
+        own source (a point of gaze, or heatmap_final), with frame_time from d when it is there, the step's lengths, `valid` (masked)
+        and reset flags; the result gains <name> (a copy of the carried map) and with per_frame <name>_frames.  None issues no launch."""
         assert not self.training, 'EVE._predict_sequence is eval-only'
         B = eye_input(d).shape[0]
         posed, faced = has_pose_form(d), face_landmarks_key(d) is not None
@@ -475,9 +480,43 @@ class EVE(nn.Module):
                 events['spec'], events['state'], events['store'], events['count'], events['dropped'],
                 frame_time=d['frame_time'].contiguous() if 'frame_time' in d else None, valid=None if plan is None else plan['valid'],
                 lengths=None if lengths is None else lengths[:B], reset=None if reset is None else reset[:B]))
+        if history is not None:
+            self._gaze_history(d, inter, out, history, None if lengths is None else lengths[:B], None if reset is None else reset[:B], plan)
         if render is not None:
             render(d, inter, out)
         return out
+
+    def _gaze_history(self, d, inter, out, history, lengths, reset, plan):
+        """The gaze history stage of an EVEStream step: per spec the time chain's launch (eve_gaze_history_plan) and the maps' launch
+        (eve_gaze_history_update) on the carried buffers."""
+        B, T = eye_input(d).shape[:2]
+        k = default_kernels()
+        screen = tuple(self.config.actual_screen_size)
+
+        def look(key):
+            for src in (out, inter, d):
+                if key in src:
+                    return src[key]
+            raise ValueError('step: history: %r is neither in the chunk nor a result of this step' % (key,))
+
+        frame_time = d['frame_time'].contiguous() if 'frame_time' in d else None
+        for h in history:
+            spec, P = h['spec'], h['P']
+            valid_key = None
+            if spec.valid_key is not None:
+                valid_key = look(spec.valid_key).reshape(B, T).contiguous()
+                valid_key = valid_key.view(torch.uint8) if valid_key.dtype == torch.bool else valid_key
+            pog = heat = None
+            if h['source'] == 'heatmap_final':
+                heat = inter['heatmap_final'].reshape((B, T) + tuple(inter['heatmap_final'].shape[-2:])).float().contiguous()
+            else:
+                pog = look(h['source']).reshape(B, T, 2).float().contiguous()
+            coef, clear = k.gaze_history_plan(P, screen, h['state'], T, pog=pog, frame_time=frame_time,
+                                              valid=None if plan is None else plan['valid'], valid_key=valid_key, lengths=lengths, reset=reset)
+            frames = k.gaze_history_update(P, coef, clear, h['maps'], heat=heat, per_frame=spec.per_frame)
+            out[spec.name] = h['maps'].clone()
+            if spec.per_frame:
+                out[spec.name + '_frames'] = frames
 
     def _eye_gate(self, d, contours, gate, reset, lengths):
         """The gate of a gated EVEStream step: one eve_eye_gate launch over what the spec has a criterion for (d: the chunk after

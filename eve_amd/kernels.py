@@ -1122,6 +1122,66 @@ class HipKernels(object):
             *([self._p(out[k_]) for k_ in self.GAZE_EVENT_KEYS] if T else [None] * 7), self._stream()))
         return out
 
+    # ------------------------------------------------------------------ the time-decayed gaze history
+    def gaze_history_plan(self, P, screen_size, state, T, pog=None, frame_time=None, valid=None, valid_key=None, lengths=None, reset=None):
+        """The time chain of the gaze history for B streams x T frames: P the launch's scalars (data.GazeHistorySpec.launch_params:
+        size (MW, MH), ln_decay, seconds, max_gap_s, fps or None, gain, ...), screen_size (W, H); state float64 [B, 8], UPDATED IN PLACE;
+        pog float32 [B, T, 2] or None (the heat source), frame_time float64 [B, T], valid and valid_key uint8 [B, T], lengths and reset
+        int32 [B], or None.  -> (coef float64 [B, T, 4], clear int32 [B]) for gaze_history_update (include/eve_hip.h
+        eve_gaze_history_plan)."""
+        ok = lambda t, dtype: torch.is_tensor(t) and t.dtype == dtype
+        if not ok(state, torch.float64) or state.dim() != 2 or state.shape[1] != 8 or state.shape[0] < 1:
+            raise TypeError('gaze_history_plan: state must be float64 [B, 8], got %s %s' % (getattr(state, 'dtype', type(state)),
+                                                                                          tuple(getattr(state, 'shape', ()))))
+        B, T = state.shape[0], int(T)
+        tensors = [state]
+        for name, t, dtype, shape in (('pog', pog, torch.float32, (B, T, 2)), ('frame_time', frame_time, torch.float64, (B, T)),
+                                      ('valid', valid, torch.uint8, (B, T)), ('valid_key', valid_key, torch.uint8, (B, T)),
+                                      ('lengths', lengths, torch.int32, (B,)), ('reset', reset, torch.int32, (B,))):
+            if t is not None:
+                if not ok(t, dtype) or tuple(t.shape) != shape:
+                    raise TypeError('gaze_history_plan: %s must be %s %s, got %s %s' % (
+                        name, str(dtype).replace('torch.', ''), list(shape), getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ()))))
+                tensors.append(t)
+        if not all(t.is_contiguous() for t in tensors):
+            raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        if T and frame_time is None and P['fps'] is None:
+            raise ValueError('gaze_history_plan: without frame_time the spec needs fps')
+        coef = torch.empty((B, T, 4), dtype=torch.float64, device=state.device)
+        clear = torch.empty((B,), dtype=torch.int32, device=state.device)
+        self._ck(self.lib.eve_gaze_history_plan(
+            B, T, self._p(pog), self._p(frame_time), self._p(valid), self._p(valid_key), self._p(lengths), self._p(reset),
+            0.0 if P['fps'] is None else float(P['fps']), float(P['ln_decay']), 1 if P['seconds'] else 0, float(P['max_gap_s']), float(P['gain']),
+            int(P['size'][0]), int(P['size'][1]), float(screen_size[0]), float(screen_size[1]), self._p(state), self._p(coef) if T else None,
+            self._p(clear), self._stream()))
+        return coef, clear
+
+    def gaze_history_update(self, P, coef, clear, maps, heat=None, per_frame=False):
+        """The plan's rows applied to the maps: coef float64 [B, T, 4] and clear int32 [B] from gaze_history_plan, maps float32
+        [B, MH, MW], UPDATED IN PLACE, heat None or float32 [B, T, MH, MW].  -> the map after every frame, float32 [B, T, MH, MW], where
+        per_frame, else None (include/eve_hip.h eve_gaze_history_update)."""
+        ok = lambda t, dtype: torch.is_tensor(t) and t.dtype == dtype
+        MW, MH = int(P['size'][0]), int(P['size'][1])
+        if not ok(maps, torch.float32) or maps.dim() != 3 or tuple(maps.shape[1:]) != (MH, MW) or maps.shape[0] < 1:
+            raise TypeError('gaze_history_update: maps must be float32 [B, %d, %d], got %s %s' % (MH, MW, getattr(maps, 'dtype', type(maps)),
+                                                                                                tuple(getattr(maps, 'shape', ()))))
+        B = maps.shape[0]
+        if not ok(coef, torch.float64) or coef.dim() != 3 or coef.shape[0] != B or coef.shape[2] != 4:
+            raise TypeError('gaze_history_update: coef must be float64 [%d, T, 4], got %s %s' % (B, getattr(coef, 'dtype', type(coef)),
+                                                                                               tuple(getattr(coef, 'shape', ()))))
+        T = coef.shape[1]
+        if not ok(clear, torch.int32) or tuple(clear.shape) != (B,):
+            raise TypeError('gaze_history_update: clear must be int32 [%d]' % B)
+        if heat is not None and (not ok(heat, torch.float32) or tuple(heat.shape) != (B, T, MH, MW)):
+            raise TypeError('gaze_history_update: heat must be float32 [%d, %d, %d, %d], got %s %s' % (
+                B, T, MH, MW, getattr(heat, 'dtype', type(heat)), tuple(getattr(heat, 'shape', ()))))
+        if not all(t.is_contiguous() for t in (maps, coef, clear) + (() if heat is None else (heat,))):
+            raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        frames = torch.empty((B, T, MH, MW), dtype=torch.float32, device=maps.device) if per_frame else None
+        self._ck(self.lib.eve_gaze_history_update(B, T, MH, MW, self._p(coef) if T else None, self._p(clear), self._p(heat), float(P['alpha']),
+                                                  float(P['floor']), self._p(maps), self._p(frames), self._stream()))
+        return frames
+
     # ------------------------------------------------------------------ the eye gate
     def eye_gate(self, spec, B, T, state, store, count, dropped, pose_valid=None, reproj_rms=None, inliers=None, warp=None, h=None,
                  contours=None, lengths=None, reset=None, frame_size=None, patch_size=None):

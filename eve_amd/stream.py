@@ -13,6 +13,7 @@ carried from one call to the next.
     out = stream.step(chunk, events=eve_amd.GazeEventSpec(fps=60))   # + the filtered PoG, gaze velocity, fixation / saccade events
     rows = stream.fixations()                              # the completed fixations of every stream (see "Gaze events" below)
     out = stream.step(chunk, gate=eve_amd.EyeGateSpec(blink=eve_amd.BlinkSpec()))   # the mask made on the device (see "The eye gate" below)
+    out = stream.step(chunk, history=eve_amd.GazeHistorySpec(fps=60))                # + the time-decayed map of where the gaze has been
     st = stream.get_state(); stream.set_state(st)          # reference layout, e.g. to resume a recording
 
 For any split of a clip into chunks the concatenated outputs equal one eval pass of the whole clip from zero state
@@ -116,6 +117,30 @@ set_gate_state; get_state / set_state do not hold it).  Float64 throughout; test
 without gate issues exactly the launches it always issued.  Not offered: adaptive thresholds learnt per person, a closure announced
 before its first closed frame, blink times in seconds, a mid-chunk reset of stale recurrent state after a long gap, coverage
 through the lens model, gradients, EVE.forward.
+
+Gaze history.  "Where has this person been looking" -- over the last seconds, or over the whole session -- is the picture every
+consumer of an eye tracker builds next (an attention map, a dwell map, a fixation heat map), and what the reference's
+EVE.forward(create_images=True) returns as initial_gaze_history / refined_gaze_history: per clip the sum over frames of validity *
+decay_per_ms^(ms before the last frame) * heat map.  That sum is the recurrence M_t = decay^(dt_ms) * M_{t-1} + w_t * G_t, and a map
+per stream that survives chunk boundaries, ragged lengths, masked eyes and reset() is state of the kind an EVEStream owns.
+step(chunk, history=eve_amd.GazeHistorySpec(...)) -- one spec, or two with distinct names -- adds two launches per spec after the
+events stage and before the render hook, inside the graph: eve_gaze_history_plan (a wavefront per stream walks the time chain and
+writes one coefficient row per frame) and eve_gaze_history_update (each map tile is loaded once, taken through the chunk's frames in
+registers and stored once).  The result gains <name>, float32 [B, MH, MW] (a copy of the carried map after the stream's last consumed
+frame), and with per_frame <name>_frames [B, Tc, MH, MW].  The source is a point of gaze of the step (PoG_px_initial / _final; with
+events= PoG_px_filtered or fixation_px, the latter with valid_key='fixating' the fixation heat map) rendered as a Gaussian of sigma map
+pixels, or heatmap_final, the network's own maps (the reference's refined_gaze_history); weight='seconds' with decay_per_ms=1 gives
+a dwell map in seconds.  Time is the chunk's frame_time or frames / spec.fps, as for the events.  A frame that is not usable (lengths,
+the masked plan's valid, valid_key, a non-finite point) decays the map and deposits nothing; one whose time is not finite or runs
+backwards is ignored.  The map and its float64 [B, 8] time-chain row are carried from step to step, cleared by reset() through the same
+device flags (also before a step that does not run the spec), and tied to the spec: the same name under another spec is refused until
+clear_gaze_history().  gaze_history(), clear_gaze_history(), get_gaze_history_state() / set_gaze_history_state(); get_state() /
+set_state() do not hold them.  OverlaySpec(heat_key=<name>) blends a per_frame map in place of heatmap_final.  Float64 arithmetic on a
+float32 map that is rounded after every frame, with an exp the contract owns: tests/gaze_history_ref.py states it, and the device
+equals it bit for bit, so a clip cut into chunks gives the bits of one pass.  A step without history= issues exactly the launches it
+always issued and allocates nothing.  Not offered: areas of interest and dwell-per-region tables, per-eye maps, a windowed history
+(as opposed to the decayed one), anisotropic or screen-millimetre sigmas, gradients, EVE.forward (its create_images path keeps the
+torch restatement), maps larger than 2048 per axis.
 """
 import numpy as np
 import torch
@@ -187,6 +212,9 @@ class EVEStream(object):
             raise ValueError('blink_capacity must be an integer >= 1, got %r' % (blink_capacity,))
         self.blink_capacity = blink_capacity
         self._gate = None                        # made at the first gated step or blink call: (state, store, count, dropped)
+        # the gaze history (step(chunk, history=spec)): name -> {'spec', 'P' (the launches' scalars), 'state' float64 [B, 8], 'maps'
+        # float32 [B, MH, MW], 'free'} -- the two eve_gaze_history launches read and write them inside the step (and the graph)
+        self._history = {}
         self._graphs = {}
         self._graphs_key = None
         self._render_tables = {}                 # OverlaySpec.key() -> its marker table, int32 [M, 4] on the device
@@ -534,6 +562,141 @@ class EVEStream(object):
         self._event_buffers()                    # allocated here, before any capture
         return {'spec': spec, 'source': source}
 
+    # ------------------------------------------------------------------ the gaze history
+    def _history_entry(self, spec, P):
+        """The carried map and time chain of spec.name, made at the first step that names it.  A map is tied to its spec."""
+        e = self._history.get(spec.name)
+        if e is not None and (e['spec'].key() != spec.key() or e['P'] != P):
+            if not e['free']:
+                raise ValueError('step: history: the map %r was accumulated under another spec (%r); clear_gaze_history(%r) first' % (
+                    spec.name, e['spec'], spec.name))
+            e = None
+            self._graphs = {}                    # (graphs captured on the old buffers)
+        if e is None:
+            B, (MW, MH) = self.num_streams, P['size']
+            e = self._history[spec.name] = {'spec': spec, 'P': P, 'state': torch.zeros((B, 8), dtype=torch.float64, device=self.device),
+                                            'maps': torch.zeros((B, MH, MW), dtype=torch.float32, device=self.device), 'free': False}
+        e['free'] = False
+        return e
+
+    def _history_named(self, name, where):
+        if name not in self._history:
+            raise ValueError('%s: no gaze history map named %r (known: %s)' % (where, name, ', '.join(sorted(self._history)) or 'none'))
+        return self._history[name]
+
+    def gaze_history(self, name='gaze_history'):
+        """The carried map of the history spec of that name, float32 [B, MH, MW] (a copy): the map after every stream's last consumed
+        frame.  Resets not yet applied by a step are not reflected."""
+        return self._history_named(name, 'gaze_history')['maps'].clone()
+
+    def clear_gaze_history(self, name=None, streams=None):
+        """Zero the maps and the time chains of the given streams (None = all) of one history spec, or of all of them (name=None).
+        Cleared for all streams, a name may be taken by another spec at the next step."""
+        entries = list(self._history.values()) if name is None else [self._history_named(name, 'clear_gaze_history')]
+        if streams is None:
+            for e in entries:
+                e['maps'].zero_(), e['state'].zero_()
+                e['free'] = True
+            return
+        m = self._device_mask(streams, 'clear_gaze_history')
+        for e in entries:
+            e['maps'].copy_(torch.where(m[:, None, None], torch.zeros_like(e['maps']), e['maps']))
+            e['state'].copy_(torch.where(m[:, None], torch.zeros_like(e['state']), e['state']))
+
+    def get_gaze_history_state(self):
+        """The gaze history's carried state: {name: {'spec': the GazeHistorySpec, 'maps': float32 [B, MH, MW], 'rows': float64 [B, 8]
+        (has_prev, t_prev, ticks, reserved; include/eve_hip.h eve_gaze_history_plan)}}, fresh tensors.  Resets not yet applied by a
+        step are not reflected.  get_state() / set_state() do not hold it."""
+        return {name: {'spec': e['spec'], 'maps': e['maps'].clone(), 'rows': e['state'].clone()} for name, e in self._history.items()}
+
+    def set_gaze_history_state(self, state):
+        """Load maps and time chains in get_gaze_history_state()'s layout, e.g. to resume a recording.  A name that is known must come
+        with the spec its map was accumulated under (or be cleared first)."""
+        from .data import GazeHistorySpec
+        B = self.num_streams
+        loaded = []
+        for name, s_ in state.items():
+            spec = s_.get('spec') if isinstance(s_, dict) else None
+            if not isinstance(spec, GazeHistorySpec) or spec.name != name:
+                raise ValueError('set_gaze_history_state: %r needs its GazeHistorySpec under \'spec\'' % (name,))
+            P = spec.launch_params(self.model.config)
+            MW, MH = P['size']
+            maps = torch.as_tensor(s_['maps'], dtype=torch.float32).to(self.device)
+            rows = torch.as_tensor(s_['rows'], dtype=torch.float64).to(self.device)
+            if tuple(maps.shape) != (B, MH, MW) or tuple(rows.shape) != (B, 8):
+                raise ValueError('set_gaze_history_state: %r must hold maps [%d, %d, %d] and rows [%d, 8], got %s and %s' % (
+                    name, B, MH, MW, B, tuple(maps.shape), tuple(rows.shape)))
+            loaded.append((spec, P, maps, rows))
+        for spec, P, maps, rows in loaded:
+            e = self._history_entry(spec, P)
+            e['maps'].copy_(maps), e['state'].copy_(rows)
+
+    def _check_history(self, chunk, history, events, masked, B, Tc):
+        """step()'s `history` checked against the chunk, the model and the step's other stages -> the plans _predict_sequence needs,
+        buffers included.  Every refusal is a ValueError raised before anything is launched or captured."""
+        from .data import GAZE_EVENT_KEYS, GazeHistorySpec
+        specs = list(history) if isinstance(history, (list, tuple)) else [history]
+        if not 1 <= len(specs) <= 2 or not all(isinstance(s_, GazeHistorySpec) for s_ in specs):
+            raise ValueError('step: history must be an eve_amd.GazeHistorySpec or a list of one or two of them, got %s' % (
+                ', '.join(type(s_).__name__ for s_ in specs) or 'an empty list'))
+        if len({s_.name for s_ in specs}) != len(specs):
+            raise ValueError('step: history: two specs share the name %r' % (specs[0].name,))
+        cfg, has_ref = self.model.config, self.model.refine_net is not None
+        taken = set(getattr(self.model, 'PREDICTION_KEYS', ())) | set(GAZE_EVENT_KEYS) | {'valid', 'eye_valid', 'pose_valid', 'rendered', 'heatmap_final'}
+        ft = chunk.get('frame_time')
+        if ft is not None and (not torch.is_tensor(ft) or ft.dtype != torch.float64 or tuple(ft.shape) != (B, Tc) or ft.device != self.device):
+            raise ValueError('step: frame_time must be a float64 [%d, %d] tensor on %s, got %s %s' % (
+                B, Tc, self.device, getattr(ft, 'dtype', type(ft)), tuple(getattr(ft, 'shape', ()))))
+        plans = []
+        for spec in specs:
+            if spec.name in taken or spec.name in chunk or any(spec.name == s_.name + '_frames' for s_ in specs):
+                raise ValueError('step: history: the name %r is a key of the chunk or of the step\'s result already' % (spec.name,))
+            source = spec.source if spec.source is not None else ('PoG_px_final' if has_ref else 'PoG_px_initial')
+            if source in ('PoG_px_final', 'heatmap_final') and not has_ref:
+                raise ValueError('step: history accumulates %s, which RefineNet produces, and the model has no RefineNet' % source)
+            if source in ('PoG_px_filtered', 'fixation_px') and events is None:
+                raise ValueError('step: history accumulates %s, which the events stage produces: pass events= in the same step' % source)
+            P = spec.launch_params(cfg)
+            if source == 'heatmap_final' and tuple(P['size']) != (int(cfg.gaze_heatmap_size[0]), int(cfg.gaze_heatmap_size[1])):
+                raise ValueError('step: history accumulates heatmap_final, so its size %r must be the config\'s gaze_heatmap_size %r' % (
+                    tuple(P['size']), tuple(cfg.gaze_heatmap_size)))
+            if 'inv_camera_transformation' not in chunk:
+                raise ValueError('step: history accumulates %s, and the point of gaze needs the camera geometry '
+                                 '(inv_camera_transformation) in the chunk' % source)
+            vk = spec.valid_key
+            if vk is not None:
+                entry = chunk.get(vk)
+                known = (vk == 'fixating' and events is not None) or (vk == 'valid' and masked)
+                if entry is None and not known:
+                    raise ValueError('step: history: valid_key %r is neither in the chunk nor a [B, Tc] result of this step' % (vk,))
+                if entry is not None and (not torch.is_tensor(entry) or entry.dtype not in (torch.bool, torch.uint8) or
+                                          tuple(entry.shape) != (B, Tc) or entry.device != self.device):
+                    raise ValueError('step: history: valid_key %r must be a bool or uint8 [%d, %d] tensor on %s' % (vk, B, Tc, self.device))
+            if ft is None and spec.fps is None:
+                raise ValueError('step: history needs frame_time in the chunk (float64 [B, Tc] seconds) or a spec with fps')
+            e = self._history.get(spec.name)
+            if e is not None and not e['free'] and (e['spec'].key() != spec.key() or e['P'] != P):
+                self._history_entry(spec, P)     # (raises: the map is tied to another spec)
+            plans.append({'spec': spec, 'source': source, 'P': P})
+        return plans
+
+    def _history_buffers(self, plans):
+        """The plans' carried buffers, made here: after every refusal of the step, before any capture."""
+        for plan in plans:
+            e = self._history_entry(plan['spec'], plan['P'])
+            plan['state'], plan['maps'] = e['state'], e['maps']
+
+    def _reset_idle_histories(self, plans):
+        """A reset before a step that does not run some map's spec: that map and its time chain are still cleared where flagged, by
+        the two launches with no frames."""
+        running = set() if plans is None else {p['spec'].name for p in plans}
+        k = default_kernels()
+        for name, e in self._history.items():
+            if name not in running:
+                coef, clear = k.gaze_history_plan(e['P'], tuple(self.model.config.actual_screen_size), e['state'], 0,
+                                                  reset=self._flags[:self.num_streams])
+                k.gaze_history_update(e['P'], coef, clear, e['maps'])
+
     # ------------------------------------------------------------------ the eye gate
     def _gate_buffers(self):
         if self._gate is None:
@@ -751,9 +914,11 @@ class EVEStream(object):
             self._pose_gate_host = not skip_invalid_pose
             self._pose_gate.fill_(self._pose_gate_host)              # a device value: the captured graphs read it, the host never waits
 
-    def _run(self, chunk, return_heatmaps, ragged=False, eye_mask=None, masked=False, render=None, events=None, gate=None):
+    def _run(self, chunk, return_heatmaps, ragged=False, eye_mask=None, masked=False, render=None, events=None, gate=None, history=None):
         # render: None or a _render_plan; the keyword reaches _predict_sequence only then, so a step without it calls what it always did
         extra = {} if render is None else {'render': self._render_hook(render, ragged, masked)}
+        if history is not None:                  # history: None or _check_history's plans; the keyword goes along only then
+            extra['history'] = history
         if self._calib_apply or 'calibration_target' in chunk:       # (neither: the call an uncalibrated EVEStream always made)
             extra['calibration'] = {'kappa': self._calib_kappa, 'ok': self._calib_ok, 'apply': self._calib_apply,
                                     'store': self._store() if 'calibration_target' in chunk else None}
@@ -780,7 +945,7 @@ class EVEStream(object):
                                             lengths=self._lengths, **extra)
 
     # ------------------------------------------------------------------ the overlay (step(chunk, render=spec))
-    def _render_plan(self, chunk, spec, events=None):
+    def _render_plan(self, chunk, spec, events=None, history=None):
         """step()'s `render` checked against the chunk -> what the launch needs beside the step's own results: the capture's key,
         format and size, the matrix, sx and sy, the marker table on the device, the inset's place.  Every refusal is a ValueError
         raised before anything is launched or captured."""
@@ -822,6 +987,15 @@ class EVEStream(object):
             results += GAZE_EVENT_KEYS
         if self._screen_apply:                   # an applied screen map: the uncorrected point can be drawn beside the corrected one
             results += ('PoG_px_final_raw' if ref is not None else 'PoG_px_initial_raw', 'screen_calibrated')
+        if spec.heat_key is not None:            # a gaze history map of this step in place of heatmap_final
+            named = [h for h in (history or ()) if h['spec'].name == spec.heat_key]
+            if not named:
+                raise ValueError('step: render: heat_key %r names no history spec of this step (history=...)' % (spec.heat_key,))
+            if not named[0]['spec'].per_frame:
+                raise ValueError('step: render: heat_key %r needs a per_frame=True history spec: the overlay blends a map per frame' % (spec.heat_key,))
+            if max(named[0]['P']['size']) > 1024:
+                raise ValueError('step: render: heat_key %r: the overlay blends maps of up to 1024 per axis, this one is %d x %d' % (
+                    (spec.heat_key,) + tuple(named[0]['P']['size'])))
         for m in spec.markers:
             for k_ in (m[0], m[1]):
                 if k_ is not None and k_ not in chunk and k_ not in results:
@@ -886,6 +1060,9 @@ class EVEStream(object):
             if spec.heat:
                 hm = look('heatmap_final')
                 kw.update(heat=hm.reshape((N,) + tuple(hm.shape[-2:])).float().contiguous(), heat_color=spec.heat_color, amax=spec.heat_amax)
+            elif spec.heat_key is not None:
+                hm = out[spec.heat_key + '_frames']
+                kw.update(heat=hm.reshape((N,) + tuple(hm.shape[-2:])), heat_color=spec.heat_color, amax=spec.heat_amax)
             if spec.inset == 'eyes':
                 if 'left_eye_patch' in d:
                     left, right = d['left_eye_patch'], d['right_eye_patch']
@@ -909,7 +1086,8 @@ class EVEStream(object):
             out['rendered'] = rendered.view((B, Tc) + tuple(rendered.shape[1:]))
         return render
 
-    def step(self, chunk, return_heatmaps=False, lengths=None, eye_mask=None, skip_invalid_pose=False, render=None, events=None, gate=None):
+    def step(self, chunk, return_heatmaps=False, lengths=None, eye_mask=None, skip_invalid_pose=False, render=None, events=None, gate=None,
+             history=None):
         """One chunk of every stream: chunk holds [B, Tc, ...] tensors on the model's device -- the eyes (below), {left,right}_h,
         {left,right}_o, {left,right}_R, head_R, camera_transformation, inv_camera_transformation, pixels_per_millimeter, millimeters_per_pixel, and screen_frame when the config loads screen content.  Returns the
         prediction keys of EVE(output_predictions=True) as [B, Tc, ...] tensors (heatmap_final [B, Tc, 1, H, W] on request).
@@ -1134,7 +1312,27 @@ class EVEStream(object):
         eye_mask, every camera and screen form, calibration, events and render combine with it.  Not offered: adaptive thresholds
         learnt per person, a closure announced before its first closed frame, blink times in seconds, a mid-chunk reset of stale
         recurrent state after a long gap, coverage through the lens model, gradients, EVE.forward.  gate=None issues exactly the
-        launches the step always issued."""
+        launches the step always issued.
+
+        history: None, an eve_amd.GazeHistorySpec, or a list of up to two with distinct names -- per spec one eve_gaze_history_plan and
+        one eve_gaze_history_update launch after the screen-space map and the events stage and before the overlay, inside the captured
+        graph, accumulate the time-decayed history of the point of gaze (module docstring, "Gaze history"): M_t = decay_per_ms^(ms
+        since the previous frame) * M_{t-1} + w_t * G_t per stream.  The result gains <name>, float32 [B, MH, MW] -- the map after the
+        stream's last consumed frame of the chunk -- and with per_frame <name>_frames, float32 [B, Tc, MH, MW] (frames past a ragged
+        length hold unspecified values).  spec.source: PoG_px_final with a RefineNet, else PoG_px_initial; PoG_px_filtered and
+        fixation_px need events= in the same step; heatmap_final needs a RefineNet and size == gaze_heatmap_size.  spec.valid_key names
+        a bool / uint8 [B, Tc] entry of the chunk, or `fixating` (with events=) or `valid` (a masked step).  A frame is usable iff it
+        was delivered (lengths), is valid (eye_mask, gate=, skip_invalid_pose), its valid_key holds and its point is finite; a frame
+        that is not decays the map and deposits nothing.  Time is the chunk's frame_time, float64 [B, Tc] seconds, or frames /
+        spec.fps counted over the delivered frames since the stream's last reset (frame_time wins); a frame whose time is not finite
+        or lies before the previous one's is ignored.  The map is carried from step to step and cleared by reset(); it is tied to
+        its spec (ValueError for a known name under another spec: clear_gaze_history first).  The specs by value, the config's
+        defaults resolved, are part of the graph's key; lengths, eye_mask, gate=, events=, both calibrations, every camera and screen
+        form and render combine with it, and OverlaySpec(heat_key=<name>) blends the per_frame map of that name in place of
+        heatmap_final (a map with an axis above 1024, one without per_frame, and heat_key beside heat=True are ValueErrors).  The host
+        does not wait.  tests/gaze_history_ref.py states the arithmetic, exact to the bit.  Not offered: areas of interest and
+        dwell-per-region tables, per-eye maps, a windowed history, anisotropic or screen-millimetre sigmas, gradients, EVE.forward,
+        maps larger than 2048 per axis.  history=None issues exactly the launches the step always issued."""
         if self.model.training:
             raise ValueError('EVEStream runs inference only: the model was switched to training mode')
         B, Tc = eye_input(chunk).shape[:2]
@@ -1153,10 +1351,17 @@ class EVEStream(object):
         if gate is not None:
             gate = self._check_gate(chunk, gate, B, Tc)
         more = {} if gate is None else {'gate': gate}      # the keyword goes along only then: a step without it calls what it always did
+        if history is not None:
+            more['history'] = history = self._check_history(chunk, history, events, masked, B, Tc)
         if render is not None:
-            render = self._render_plan(chunk, render) if events is None else self._render_plan(chunk, render, events)
+            if history is not None:
+                render = self._render_plan(chunk, render, events, history)
+            else:
+                render = self._render_plan(chunk, render) if events is None else self._render_plan(chunk, render, events)
         self._check_calibration(chunk, B, Tc)
         self._check_screen_calibration(chunk, B, Tc)
+        if history is not None:
+            self._history_buffers(history)
         if ragged:
             self._upload_lengths(lengths)
         if masked and has_pose_form(chunk):
@@ -1169,6 +1374,8 @@ class EVEStream(object):
             state, store, count, dropped = self._events
             default_kernels().gaze_events(None, None, None, None, self._closing_spec(), state, store, count, dropped,
                                           reset=self._flags[:self.num_streams])
+        if self._history and self._flags_set:
+            self._reset_idle_histories(history)
         if gate is None and self._gate is not None and self._flags_set:
             # a reset before a step without gate: the gate's rows of the flagged streams are still cleared (the launch refuses T = 0)
             state = self._gate[0]
@@ -1208,12 +1415,13 @@ class EVEStream(object):
     def _weights_key(self):
         return tuple(_module_key(m) for m in (self.model.eye_net, self.model.refine_net) if m is not None)
 
-    def _graph_key(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None):
+    def _graph_key(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None):
         """What a captured graph is good for: the step's mode, both YUV matrices, both surface layouts (by value), the overlay
         (render: None or a _render_plan -- its OverlaySpec by value), with a face-landmark form eye_net.face_huber_px (a launch
         argument, so baked in), the gaze events (events: None or a _check_events plan -- its GazeEventSpec by value and its source;
         frame_time's presence is a chunk key), the eye gate (gate: None or a _check_gate plan -- its EyeGateSpec by value and the frame size;
-        eye_contours' presence and shape are a chunk key), whether a calibration is applied (`calibrated`; a collecting step differs by its chunk keys), whether a screen-space map is applied (likewise), and every chunk tensor's key, shape and dtype -- which of the two landmark keys among them."""
+        eye_contours' presence and shape are a chunk key), the gaze history (history: None or _check_history's plans -- each GazeHistorySpec by
+        value, its source and the launches' scalars, the config's defaults resolved), whether a calibration is applied (`calibrated`; a collecting step differs by its chunk keys), whether a screen-space map is applied (likewise), and every chunk tensor's key, shape and dtype -- which of the two landmark keys among them."""
         ref = self.model.refine_net
         spec = None if render is None else render['spec'].key()
         layouts = (self.model.eye_net.camera_layout, None if ref is None else ref.screen_layout)
@@ -1223,14 +1431,18 @@ class EVEStream(object):
             huber = check_huber_px(self.model.eye_net.face_huber_px, 'face_huber_px')
         return (return_heatmaps, ragged, masked, self.model.eye_net.yuv_matrix, None if ref is None else ref.yuv_matrix, spec, layouts, huber,
                 self._calib_apply, self._screen_apply) + (() if events is None else ((events['spec'].key(), events['source']),)) + \
-            (() if gate is None else (('gate', gate['spec'].key(), gate['frame_size']),)) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
+            (() if gate is None else (('gate', gate['spec'].key(), gate['frame_size']),)) + \
+            (() if history is None else (('history',) + tuple((h['spec'].key(), h['source'], tuple(sorted(h['P'].items(), key=lambda kv: kv[0])))
+                                                                for h in history),)) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
 
-    def _graph_for(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None):
+    def _graph_for(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None):
         wk = self._weights_key()
         if wk != self._graphs_key:               # new weights: new packs, new graphs (a replay never reads stale packs)
             self._graphs = {}
             self._graphs_key = wk
         more = {} if gate is None else {'gate': gate}
+        if history is not None:
+            more['history'] = history
         key = self._graph_key(chunk, return_heatmaps, ragged, masked, render, events, **more)
         entry = self._graphs.get(key)
         if entry is None:
@@ -1239,7 +1451,7 @@ class EVEStream(object):
             self._graphs_key = self._weights_key()
         return entry
 
-    def _capture(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None):
+    def _capture(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None):
         """Capture one step for this chunk shape (train.Trainer._capture's recipe): inputs copied into fixed buffers, two eager
         warm-up steps off the default stream (packs, lazily built filters, allocator) with the carried states put back
         afterwards, the kernels' scratch allocated before the capture, one stream, no side branches.  A masked graph has one more
@@ -1258,10 +1470,12 @@ class EVEStream(object):
             # (and the gaze events' state, store and counters: a capture would otherwise tick the filter three times)
             carried = self._state_tensors() + [self._face_pose, self._calib_kappa, self._calib_ok] + list(self._calib_store or ()) + \
                 list(self._events or ()) + list(self._gate or ()) + \
-                list(self._screen_store or ())                             # (the eye gate's ticks, baselines and blinks; the screen map's samples)
+                list(self._screen_store or ()) + \
+                [t for e in self._history.values() for t in (e['state'], e['maps'])]     # (the eye gate's ticks, baselines and blinks; the
+            #                                                                              screen map's samples; the gaze history's maps and time chains)
             snap = [t.clone() for t in carried]
             for _ in range(2):
-                self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate)
+                self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history)
             for t, s_ in zip(carried, snap):
                 t.copy_(s_)
         torch.cuda.current_stream().wait_stream(side)
@@ -1271,7 +1485,7 @@ class EVEStream(object):
             k.prepare_graph_workspace(self.device)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            out = self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate)
+            out = self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history)
         m = self.model
         keep = (m.eye_net._packs, getattr(m.eye_net, '_stream_w', None), m.refine_net._packs if m.refine_net is not None else None)
         return {'graph': graph, 'inputs': static, 'outputs': out, 'keep': keep, 'eye_mask': eye_mask}

@@ -1336,6 +1336,46 @@ int eve_eye_gate(long long B, int T, const uint8_t* pose_valid /* may be NULL */
                  int IW, int IH, int OW, int OH, const eve_eye_gate_params* params, double* state, int capacity, double* blinks, int* count,
                  int* dropped, uint8_t* usable, uint8_t* reason, float* openness, uint8_t* blink, eve_stream_t stream);
 
+/* The time-decayed gaze history: per stream a float32 map m [MH][MW] that follows M_t = decay^(dt_ms) * M_{t-1} + w_t * G_t, G_t the
+ * Gaussian around the frame's point of gaze or a heat map handed in, for B streams x T frames, with the time chain carried in `state`
+ * and the map in `map` from one call to the next.  Two launches: the plan walks the time chain and writes one coefficient row per
+ * frame, the update applies the rows to the map (no workgroup of the map launch reads and writes the state row).  Float64, every
+ * operation rounded on its own (no contraction), in the order written here; tests/gaze_history_ref.py restates it in numpy, and the
+ * device equals it bit for bit because the contract owns its exp:
+ *   gh_exp(x), x <= 0: xc = x < -104 ? -104 : x; k = rint(xc * 1.4426950408889634); r = (xc - k * 6.93147180369123816490e-01) -
+ *   k * 1.90821492927058770002e-10; p = Horner of sum_{j = 0..13} r^j / j! from 1/13! downwards (p = p*r + c_j, the c_j the correctly
+ *   rounded doubles 1/j!); the result is ldexp(p, (int)k), and exactly 0 where x < -104.
+ * eve_gaze_history_plan: pog [B*T][2] float (screen pixels; NULL for the heat source), frame_time [B*T] double seconds or NULL (then
+ *   t = ticks / fps), valid and valid_key [B*T] uint8, lengths [B] int (clamped to 0 .. T), reset [B] int: each may be NULL.  state
+ *   [B][8] double: 0 has_prev, 1 t_prev, 2 ticks (the delivered frames since the last reset), 3-7 reserved (0); UPDATED IN PLACE.
+ *   coef [B*T][4] double and clear [B] int are written.  A stream with reset[b] != 0 zeroes its row and gets clear[b] = 1 (else 0),
+ *   also with no frame.  For f < lengths[b] in order: tt = frame_time[b][f], or ticks / fps; ticks += 1 either way.  tt not finite, or
+ *   has_prev and tt < t_prev: the frame is IGNORED, coef row (-1, 0, ., .) -- so are the frames from lengths[b] on.  Otherwise delta =
+ *   has_prev ? tt - t_prev : 0, d = gh_exp((delta * 1000.0) * ln_decay); usable = valid && valid_key && (pog == NULL or both
+ *   coordinates finite); w = gain * (weight_seconds == 0 ? 1 : has_prev ? min(delta, max_gap_s) : (fps > 0 ? 1 / fps : 0)); then
+ *   has_prev = 1, t_prev = tt.  The row is (d, usable ? w : -1, cx, cy), cx = ((double)MW / screen_w) * (double)pog_x, cy likewise.
+ *   fps = 0 means "not given".  Kernel name gaze_history_plan_kernel, one wavefront per stream.
+ * eve_gaze_history_update: coef and clear as the plan wrote them; heat NULL or [B*T][MH][MW] float; map [B][MH][MW] float UPDATED IN
+ *   PLACE; frames NULL or [B*T][MH][MW] float, the map after every frame.  A stream with clear[b] != 0 starts from a zero map.  Per
+ *   frame in order and per pixel (x, y), pixel centres at integer coordinates: d < 0 leaves the map as it stands; else with ex =
+ *   gh_exp(alpha * ((x - cx) * (x - cx))) and ey likewise, v = (double)m * d + w * (ex * ey + floor), or with heat v = (double)m * d +
+ *   w * (double)heat[b][f][y][x], or with w < 0 v = (double)m * d alone (no multiplication by a zero weight: a NaN point never
+ *   reaches the map); m = fabs(v) < 2^-100 ? 0 : (float)v -- rounded to float after EVERY frame, so the bits do not depend on how a clip
+ *   is cut into chunks, and no float denormal is produced.  T = 0 is legal: a set clear flag zeroes the map, nothing else is written.
+ *   Kernel name gaze_history_update_kernel, grid (tiles of 64 x 32, B), 16-byte loads and stores where MW % 4 == 0 and the buffers
+ *   are 16-byte aligned.
+ * Refused without a launch: a null state, clear or map, with T > 0 a null coef, B < 1 (update: B > 65535), T < 0, a map axis outside
+ * 1 .. 2048, B*T*4 past 31 bits, a screen size, max_gap_s or gain that is not a finite number > 0, fps not a finite number > 0 where
+ * frame_time is NULL and T > 0, ln_decay not a finite number <= 0, alpha not a finite number < 0, floor not a finite number >= 0.
+ * Not offered: areas of interest, per-eye maps, a windowed history, anisotropic sigmas, a gradient.  (Additive: ABI v10.)          */
+int eve_gaze_history_plan(long long B, int T, const float* pog /* may be NULL */, const double* frame_time /* may be NULL */,
+                          const uint8_t* valid /* may be NULL */, const uint8_t* valid_key /* may be NULL */,
+                          const int* lengths /* may be NULL */, const int* reset /* may be NULL */, double fps, double ln_decay,
+                          int weight_seconds, double max_gap_s, double gain, int MW, int MH, double screen_w, double screen_h, double* state,
+                          double* coef, int* clear, eve_stream_t stream);
+int eve_gaze_history_update(long long B, int T, int MH, int MW, const double* coef, const int* clear, const float* heat /* may be NULL */,
+                            double alpha, double floor, float* map, float* frames /* may be NULL */, eve_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
