@@ -40,6 +40,19 @@ def _fuse2(a, b, eye_valid):
     return torch.where(left & right, _mean2(a, b), torch.where(left, a, b))
 
 
+def _u8(t):
+    """A contiguous bool or uint8 tensor (or None) as the uint8 the launches read: a view, no copy."""
+    if t is None:
+        return None
+    t = t.contiguous()
+    return t.view(torch.uint8) if t.dtype == torch.bool else t
+
+
+def _f32(t, B, T, *tail):
+    """t as [B, T] + tail, float32 and contiguous: what the stage launches read."""
+    return t.reshape((B, T) + tail).float().contiguous()
+
+
 class EVE(nn.Module):
     def __init__(self, output_predictions=False):
         super(EVE, self).__init__()
@@ -413,11 +426,12 @@ class EVE(nn.Module):
         B = eye_input(d).shape[0]
         posed, faced = has_pose_form(d), face_landmarks_key(d) is not None
         contours = d.get('eye_contours')
-        d = dict(eye_pose_batch(d, self.config, face_state, None if reset is None else reset[:B], None if lengths is None else lengths[:B],
-                                huber_px=self.eye_net.face_huber_px))
+        # reset and lengths hold a row per eye sequence [2B]; what works per stream reads the first B
+        reset_b, lengths_b = None if reset is None else reset[:B], None if lengths is None else lengths[:B]
+        d = dict(eye_pose_batch(d, self.config, face_state, reset_b, lengths_b, huber_px=self.eye_net.face_huber_px))
         plan = eye_valid = gated = None
         if gate is not None:
-            gated = self._eye_gate(d, contours, gate, None if reset is None else reset[:B], None if lengths is None else lengths[:B])
+            gated = self._eye_gate(d, contours, gate, reset_b, lengths_b)
             eye_mask = gated['usable'] if eye_mask is None else (eye_mask != 0) & (gated['usable'] != 0)
             masked = True
         if masked:
@@ -435,7 +449,7 @@ class EVE(nn.Module):
         calib = None
         if calibration is not None:
             if calibration['store'] is not None and 'calibration_target' in d:
-                self._calibration_append(d, inter, calibration['store'], None if lengths is None else lengths[:B], plan)
+                self._calibration_append(d, inter, calibration['store'], lengths_b, plan)
             if calibration['apply']:
                 calib = {'kappa': calibration['kappa'], 'calibrated': (calibration['ok'] != 0).all(dim=1)}
         if calib is None:
@@ -443,13 +457,12 @@ class EVE(nn.Module):
         else:
             self._pog_block(d, inter, 'initial', 'initial', eye_valid=eye_valid, calib=calib)
         if self.refine_net is not None and 'heatmap_initial' in inter:
-            hf = self.refine_net._stream_sequence(inter['heatmap_initial'], d.get('screen_frame'), refine_states,
-                                                  None if reset is None else reset[:B], None if lengths is None else lengths[:B], plan,
+            hf = self.refine_net._stream_sequence(inter['heatmap_initial'], d.get('screen_frame'), refine_states, reset_b, lengths_b, plan,
                                                   **screen_capture(d))
             inter['heatmap_final'] = hf
             self._final_block(d, inter, hf)
         if screen_calibration is not None:
-            self._screen_calibration(d, inter, screen_calibration, None if lengths is None else lengths[:B], plan)
+            self._screen_calibration(d, inter, screen_calibration, lengths_b, plan)
         out = {k_: inter[k_] for k_ in self.PREDICTION_KEYS if k_ in inter}
         if screen_calibration is not None and screen_calibration['apply']:
             suffix = 'final' if 'PoG_px_final' in inter else 'initial'
@@ -474,14 +487,13 @@ class EVE(nn.Module):
             out['heatmap_final'] = inter['heatmap_final']
         if events is not None:
             T = eye_input(d).shape[1]
-            f32 = lambda t, *s_: t.reshape((B, T) + s_).float().contiguous()
             out.update(default_kernels().gaze_events(
-                f32(inter[events['source']], 2), f32(d['o'], 3), f32(d['inv_camera_transformation'], 4, 4), f32(d['pixels_per_millimeter'], 2),
-                events['spec'], events['state'], events['store'], events['count'], events['dropped'],
+                _f32(inter[events['source']], B, T, 2), _f32(d['o'], B, T, 3), _f32(d['inv_camera_transformation'], B, T, 4, 4),
+                _f32(d['pixels_per_millimeter'], B, T, 2), events['spec'], events['state'], events['store'], events['count'], events['dropped'],
                 frame_time=d['frame_time'].contiguous() if 'frame_time' in d else None, valid=None if plan is None else plan['valid'],
-                lengths=None if lengths is None else lengths[:B], reset=None if reset is None else reset[:B]))
+                lengths=lengths_b, reset=reset_b))
         if history is not None:
-            self._gaze_history(d, inter, out, history, None if lengths is None else lengths[:B], None if reset is None else reset[:B], plan)
+            self._gaze_history(d, inter, out, history, lengths_b, reset_b, plan)
         if render is not None:
             render(d, inter, out)
         return out
@@ -502,15 +514,12 @@ class EVE(nn.Module):
         frame_time = d['frame_time'].contiguous() if 'frame_time' in d else None
         for h in history:
             spec, P = h['spec'], h['P']
-            valid_key = None
-            if spec.valid_key is not None:
-                valid_key = look(spec.valid_key).reshape(B, T).contiguous()
-                valid_key = valid_key.view(torch.uint8) if valid_key.dtype == torch.bool else valid_key
+            valid_key = None if spec.valid_key is None else _u8(look(spec.valid_key).reshape(B, T))
             pog = heat = None
             if h['source'] == 'heatmap_final':
-                heat = inter['heatmap_final'].reshape((B, T) + tuple(inter['heatmap_final'].shape[-2:])).float().contiguous()
+                heat = _f32(inter['heatmap_final'], B, T, *inter['heatmap_final'].shape[-2:])
             else:
-                pog = look(h['source']).reshape(B, T, 2).float().contiguous()
+                pog = _f32(look(h['source']), B, T, 2)
             coef, clear = k.gaze_history_plan(P, screen, h['state'], T, pog=pog, frame_time=frame_time,
                                               valid=None if plan is None else plan['valid'], valid_key=valid_key, lengths=lengths, reset=reset)
             frames = k.gaze_history_update(P, coef, clear, h['maps'], heat=heat, per_frame=spec.per_frame)
@@ -525,13 +534,9 @@ class EVE(nn.Module):
         spec = gate['spec']
         B, T = eye_input(d).shape[:2]
         both = lambda key, n: torch.stack([d['left' + key], d['right' + key]]).reshape(2, B * T, n).float().contiguous()
-        pose_valid = None
-        if 'pose_valid' in d:
-            pose_valid = d['pose_valid'].contiguous()
-            pose_valid = pose_valid.view(torch.uint8) if pose_valid.dtype == torch.bool else pose_valid
         ph, pw = eye_patch_hw(self.config)
         return default_kernels().eye_gate(
-            spec, B, T, gate['state'], gate['store'], gate['count'], gate['dropped'], pose_valid=pose_valid,
+            spec, B, T, gate['state'], gate['store'], gate['count'], gate['dropped'], pose_valid=_u8(d.get('pose_valid')),
             reproj_rms=d['face_reproj_rms'].contiguous() if spec.max_reproj_px is not None else None,
             inliers=d['face_inliers'].contiguous() if spec.min_inliers is not None else None,
             warp=both('_eye_warp', 9) if spec.min_coverage is not None else None, h=both('_h', 2) if spec.head_angles else None,
@@ -544,14 +549,10 @@ class EVE(nn.Module):
         B, T = d['calibration_target'].shape[:2]
         both = lambda key, *s_: torch.stack([(inter[side + key] if side + key in inter else d[side + key]).reshape((B, T) + s_).float()
                                              for side in ('left', 'right')]).contiguous()
-        f32 = lambda key, *s_: d[key].reshape((B, T) + s_).float().contiguous()
-        valid = d.get('calibration_valid')
-        if valid is not None:
-            valid = valid.contiguous()
-            valid = valid.view(torch.uint8) if valid.dtype == torch.bool else valid
-        default_kernels().calib_append(both('_g_initial', 2), f32('head_R', 3, 3), both('_o', 3), both('_R', 3, 3),
-                                       f32('inv_camera_transformation', 4, 4), f32('pixels_per_millimeter', 2), f32('calibration_target', 2),
-                                       store[0], store[1], store[2], valid, lengths, None if plan is None else plan['eye_valid'])
+        default_kernels().calib_append(both('_g_initial', 2), _f32(d['head_R'], B, T, 3, 3), both('_o', 3), both('_R', 3, 3),
+                                       _f32(d['inv_camera_transformation'], B, T, 4, 4), _f32(d['pixels_per_millimeter'], B, T, 2),
+                                       _f32(d['calibration_target'], B, T, 2), store[0], store[1], store[2], _u8(d.get('calibration_valid')),
+                                       lengths, None if plan is None else plan['eye_valid'])
 
     def _screen_calibration(self, d, inter, sc, lengths, plan):
         """The screen-space map's stage of an EVEStream step, on the output point PoG_px_<out>: the collecting launch
@@ -561,19 +562,15 @@ class EVE(nn.Module):
         suffix = 'final' if 'PoG_px_final' in inter else 'initial'
         raw = inter['PoG_px_' + suffix]
         B, T = raw.shape[:2]
-        f32 = lambda t, *s_: t.reshape((B, T) + s_).float().contiguous()
         size = tuple(self.config.actual_screen_size)
-        ppm = f32(d['pixels_per_millimeter'], 2)
+        ppm = _f32(d['pixels_per_millimeter'], B, T, 2)
         if sc['store'] is not None and 'screen_calibration_target' in d:
-            valid = d.get('screen_calibration_valid')
-            if valid is not None:
-                valid = valid.contiguous()
-                valid = valid.view(torch.uint8) if valid.dtype == torch.bool else valid
-            default_kernels().screen_calib_append(f32(raw, 2), f32(d['o'], 3), f32(d['inv_camera_transformation'], 4, 4), ppm,
-                                                  f32(d['screen_calibration_target'], 2), size, sc['store'][0], sc['store'][1], sc['store'][2],
-                                                  valid, lengths, None if plan is None else plan['valid'])
+            default_kernels().screen_calib_append(_f32(raw, B, T, 2), _f32(d['o'], B, T, 3), _f32(d['inv_camera_transformation'], B, T, 4, 4), ppm,
+                                                  _f32(d['screen_calibration_target'], B, T, 2), size, sc['store'][0], sc['store'][1],
+                                                  sc['store'][2], _u8(d.get('screen_calibration_valid')), lengths,
+                                                  None if plan is None else plan['valid'])
         if sc['apply']:
-            px = default_kernels().screen_calib_apply(f32(raw, 2), ppm, sc['coef'], sc['kind'], size).view(B, T, 2)
+            px = default_kernels().screen_calib_apply(_f32(raw, B, T, 2), ppm, sc['coef'], sc['kind'], size).view(B, T, 2)
             mapped = sc['kind'] != 0
             sel = mapped[:, None, None]
             cm = self._px_to_cm(d, px)

@@ -142,6 +142,8 @@ always issued and allocates nothing.  Not offered: areas of interest and dwell-p
 (as opposed to the decayed one), anisotropic or screen-millimetre sigmas, gradients, EVE.forward (its create_images path keeps the
 torch restatement), maps larger than 2048 per axis.
 """
+from collections import namedtuple
+
 import numpy as np
 import torch
 
@@ -150,9 +152,19 @@ from .kernels import default_kernels
 
 _WARMUP_STREAMS = {}
 
+# the lazily made buffer groups (EVEStream._group): a sample store of either calibration, and what the events and the gate carry
+SampleStore = namedtuple('SampleStore', 'samples count dropped')
+StageBuffers = namedtuple('StageBuffers', 'state store count dropped')
+
 
 def _module_key(m):
     return (m.compute_dtype,) + tuple((p.data_ptr(), p._version) for p in m.parameters())
+
+
+def _capacity(name, value):
+    if isinstance(value, bool) or not isinstance(value, int) or value < 1:
+        raise ValueError('%s must be an integer >= 1, got %r' % (name, value))
+    return value
 
 
 class EVEStream(object):
@@ -182,9 +194,7 @@ class EVEStream(object):
         # per-person calibration: the sample store (eve_calib_append appends inside the step), each eye's kappa row and flag
         # (eve_calib_fit writes them; a stream is calibrated where both flags are set).  _calib_apply: a fit or a set_calibration
         # has happened, so the steps run the applying graphs.
-        if isinstance(calibration_capacity, bool) or not isinstance(calibration_capacity, int) or calibration_capacity < 1:
-            raise ValueError('calibration_capacity must be an integer >= 1, got %r' % (calibration_capacity,))
-        self.calibration_capacity = C = calibration_capacity
+        self.calibration_capacity = _capacity('calibration_capacity', calibration_capacity)
         self._calib_store = None                 # made at the first collecting step or calibration call: B * 2 * C * 128 bytes
         self._calib_kappa = torch.zeros((B, 2, 2), dtype=torch.float32, device=self.device)
         self._calib_ok = torch.zeros((B, 2), dtype=torch.uint8, device=self.device)
@@ -192,25 +202,19 @@ class EVEStream(object):
         # the screen-space map: the sample store (eve_screen_calib_append appends inside the step), each stream's coefficients
         # (axis, term) in millimetres and its kind byte (0 none, 1 offset, 2 affine, 3 quadratic; eve_screen_calib_fit writes them).
         # _screen_apply: a fit or a set_screen_calibration has happened, so the steps run the applying graphs.
-        if isinstance(screen_calibration_capacity, bool) or not isinstance(screen_calibration_capacity, int) or screen_calibration_capacity < 1:
-            raise ValueError('screen_calibration_capacity must be an integer >= 1, got %r' % (screen_calibration_capacity,))
-        self.screen_calibration_capacity = screen_calibration_capacity
+        self.screen_calibration_capacity = _capacity('screen_calibration_capacity', screen_calibration_capacity)
         self._screen_store = None                # made at the first collecting step or screen calibration call: B * C * 96 bytes
         self._screen_coef = torch.zeros((B, 2, 6), dtype=torch.float64, device=self.device)
         self._screen_kind = torch.zeros((B,), dtype=torch.uint8, device=self.device)
         self._screen_apply = False
         # gaze events (step(chunk, events=spec)): the filter's and the running fixation's state row per stream, the store of completed
         # fixations and its counters -- eve_gaze_events reads and writes them inside the step (and the graph)
-        if isinstance(fixation_capacity, bool) or not isinstance(fixation_capacity, int) or fixation_capacity < 1:
-            raise ValueError('fixation_capacity must be an integer >= 1, got %r' % (fixation_capacity,))
-        self.fixation_capacity = fixation_capacity
+        self.fixation_capacity = _capacity('fixation_capacity', fixation_capacity)
         self._events = None                      # made at the first events step or fixation call: (state, store, count, dropped)
         self._events_spec = None                 # the spec of the last events step: what closes a fixation outside a step
         # the eye gate (step(chunk, gate=spec)): each eye's blink state row, the store of completed blinks and its counters --
         # eve_eye_gate reads and writes them inside the step (and the graph)
-        if isinstance(blink_capacity, bool) or not isinstance(blink_capacity, int) or blink_capacity < 1:
-            raise ValueError('blink_capacity must be an integer >= 1, got %r' % (blink_capacity,))
-        self.blink_capacity = blink_capacity
+        self.blink_capacity = _capacity('blink_capacity', blink_capacity)
         self._gate = None                        # made at the first gated step or blink call: (state, store, count, dropped)
         # the gaze history (step(chunk, history=spec)): name -> {'spec', 'P' (the launches' scalars), 'state' float64 [B, 8], 'maps'
         # float32 [B, MH, MW], 'free'} -- the two eve_gaze_history launches read and write them inside the step (and the graph)
@@ -220,8 +224,39 @@ class EVEStream(object):
         self._render_tables = {}                 # OverlaySpec.key() -> its marker table, int32 [M, 4] on the device
 
     # ------------------------------------------------------------------ state
-    def _state_tensors(self):
-        return [t for s_ in self._eye + self._ref for t in (s_ if isinstance(s_, tuple) else (s_,))]
+    _GROUPS = ('_calib_store', '_events', '_gate', '_screen_store')      # the attributes _group() may fill: None until first use
+
+    def _group(self, attr, kind, *buffers):
+        """The lazily made buffer group self.<attr>, a `kind` namedtuple of zeroed device tensors, one per (shape, dtype) -- made at
+        the first call, which the step's checks place before any capture.  Every group is named in _GROUPS, so _carried() holds it."""
+        assert attr in self._GROUPS
+        if getattr(self, attr) is None:
+            setattr(self, attr, kind(*(torch.zeros(shape, dtype=dtype, device=self.device) for shape, dtype in buffers)))
+        return getattr(self, attr)
+
+    def _carried(self):
+        """Every tensor a step may write, as they exist now: what _capture's two warm-up steps must put back.  The recurrent states;
+        the face-landmark form's head pose; kappa and its flags; both calibrations' sample stores and counters (the warm-up steps of
+        a collecting graph would otherwise append every sample three times); the gaze events' state, store and counters (a capture
+        would otherwise tick the filter three times); the eye gate's ticks, baselines and blinks; every gaze history's time chain
+        and map.  A carried buffer that is not returned here corrupts its state under use_graph only, and only on the first step
+        of a chunk shape: new ones are made by _group(), or by _history_entry(), and are then here."""
+        states = [t for s_ in self._eye + self._ref for t in (s_ if isinstance(s_, tuple) else (s_,))]
+        groups = [t for attr in self._GROUPS for t in (getattr(self, attr) or ())]
+        return states + [self._face_pose, self._calib_kappa, self._calib_ok] + groups + \
+            [t for e in self._history.values() for t in (e['state'], e['maps'])]
+
+    @staticmethod
+    def _zero_where(mask, *tensors):
+        """Zero the streams' rows of each tensor where mask, a bool [B] device tensor, holds: on the device, the host does not wait."""
+        for t in tensors:
+            t.copy_(torch.where(mask.reshape((-1,) + (1,) * (t.dim() - 1)), torch.zeros_like(t), t))
+
+    def _pinned(self, host):
+        """A host tensor about to be copied to the device: with the model on the GPU a pinned block of torch's host allocator, so the
+        copy is asynchronous and the block is not reused before it has run.  (Resets, lengths and masks go this way and are never
+        baked into a graph.)"""
+        return host.pin_memory() if self.device.type == 'cuda' else host
 
     def reset(self, streams=None):
         """Start the given streams (None = all; else indices, or a bool mask of length num_streams) from zero state at the
@@ -257,16 +292,11 @@ class EVEStream(object):
 
     # ------------------------------------------------------------------ calibration
     def _store(self):
-        if self._calib_store is None:
-            B, C = self.num_streams, self.calibration_capacity
-            self._calib_store = (torch.zeros((B, 2, C, 16), dtype=torch.float64, device=self.device),
-                                 torch.zeros((B, 2), dtype=torch.int32, device=self.device),
-                                 torch.zeros((B, 2), dtype=torch.int32, device=self.device))
-        return self._calib_store
+        B, C = self.num_streams, self.calibration_capacity
+        return self._group('_calib_store', SampleStore, ((B, 2, C, 16), torch.float64), ((B, 2), torch.int32), ((B, 2), torch.int32))
 
     def _device_mask(self, streams, where):
-        m = torch.from_numpy(self._stream_mask(streams, where))
-        return m.to(self.device, non_blocking=True) if self.device.type != 'cuda' else m.pin_memory().to(self.device, non_blocking=True)
+        return self._pinned(torch.from_numpy(self._stream_mask(streams, where))).to(self.device, non_blocking=True)
 
     def fit_calibration(self, streams=None, huber_mm=None, min_samples=5):
         """Fit the offset kappa = (pitch, yaw) of both eyes of the given streams (None = all; indices or a bool mask) to the samples
@@ -311,9 +341,7 @@ class EVEStream(object):
     def clear_calibration(self, streams=None):
         """Forget the offsets of the given streams (None = all): they are uncalibrated again and get the plain bits.  The sample
         store stays."""
-        m = self._device_mask(streams, 'clear_calibration')
-        self._calib_kappa.copy_(torch.where(m[:, None, None], torch.zeros_like(self._calib_kappa), self._calib_kappa))
-        self._calib_ok.copy_(torch.where(m[:, None], torch.zeros_like(self._calib_ok), self._calib_ok))
+        self._zero_where(self._device_mask(streams, 'clear_calibration'), self._calib_kappa, self._calib_ok)
         if streams is None:
             self._calib_apply = False            # nothing left to apply: back to the launches of an uncalibrated EVEStream
 
@@ -322,10 +350,7 @@ class EVEStream(object):
         if self._calib_store is None:
             self._stream_mask(streams, 'clear_calibration_samples')
             return
-        m = self._device_mask(streams, 'clear_calibration_samples')
-        _, count, dropped = self._calib_store
-        count.copy_(torch.where(m[:, None], torch.zeros_like(count), count))
-        dropped.copy_(torch.where(m[:, None], torch.zeros_like(dropped), dropped))
+        self._zero_where(self._device_mask(streams, 'clear_calibration_samples'), self._calib_store.count, self._calib_store.dropped)
 
     def calibration_counts(self):
         """-> (count, dropped), int32 [B, 2] device tensors (fresh): the samples each (stream, eye) holds, and those a full store
@@ -340,12 +365,8 @@ class EVEStream(object):
 
     # ------------------------------------------------------------------ screen-space calibration
     def _screen_samples(self):
-        if self._screen_store is None:
-            B, C = self.num_streams, self.screen_calibration_capacity
-            self._screen_store = (torch.zeros((B, C, 12), dtype=torch.float64, device=self.device),
-                                  torch.zeros((B,), dtype=torch.int32, device=self.device),
-                                  torch.zeros((B,), dtype=torch.int32, device=self.device))
-        return self._screen_store
+        B, C = self.num_streams, self.screen_calibration_capacity
+        return self._group('_screen_store', SampleStore, ((B, C, 12), torch.float64), ((B,), torch.int32), ((B,), torch.int32))
 
     def _screen_result(self, res):
         from .data import SCREEN_CALIB_REPORT
@@ -418,9 +439,7 @@ class EVEStream(object):
 
     def clear_screen_calibration(self, streams=None):
         """Forget the maps of the given streams (None = all): they get the uncorrected bits again.  The sample store stays."""
-        m = self._device_mask(streams, 'clear_screen_calibration')
-        self._screen_coef.copy_(torch.where(m[:, None, None], torch.zeros_like(self._screen_coef), self._screen_coef))
-        self._screen_kind.copy_(torch.where(m, torch.zeros_like(self._screen_kind), self._screen_kind))
+        self._zero_where(self._device_mask(streams, 'clear_screen_calibration'), self._screen_coef, self._screen_kind)
         if streams is None:
             self._screen_apply = False           # nothing left to apply: back to the launches of an EVEStream without a map
 
@@ -429,10 +448,7 @@ class EVEStream(object):
         if self._screen_store is None:
             self._stream_mask(streams, 'clear_screen_calibration_samples')
             return
-        m = self._device_mask(streams, 'clear_screen_calibration_samples')
-        _, count, dropped = self._screen_store
-        count.copy_(torch.where(m, torch.zeros_like(count), count))
-        dropped.copy_(torch.where(m, torch.zeros_like(dropped), dropped))
+        self._zero_where(self._device_mask(streams, 'clear_screen_calibration_samples'), self._screen_store.count, self._screen_store.dropped)
 
     def screen_calibration_counts(self):
         """-> (count, dropped), int32 [B] device tensors (fresh): the samples each stream holds, and those a full store
@@ -447,38 +463,17 @@ class EVEStream(object):
 
     def _check_screen_calibration(self, chunk, B, Tc):
         """step()'s screen calibration keys, and what an applying step needs, checked before anything is launched or captured."""
-        target, valid = chunk.get('screen_calibration_target'), chunk.get('screen_calibration_valid')
-        if target is None and valid is None and not self._screen_apply:
-            return
-        if target is None and valid is not None:
-            raise ValueError('step: screen_calibration_valid comes with screen_calibration_target')
-        what = 'screen_calibration_target' if target is not None else 'an applied screen calibration'
-        for key in ('inv_camera_transformation', 'pixels_per_millimeter') + (() if target is not None and not self._screen_apply else
-                                                                           ('millimeters_per_pixel', 'camera_transformation')):
-            if key not in chunk:
-                raise ValueError('step: %s needs the screen geometry (%s) in the chunk' % (what, key))
-        if 'left_o' not in chunk and not has_pose_form(chunk):
-            raise ValueError('step: %s needs the eyes\' origins o (left_o, right_o, or a pose form) in the chunk' % what)
-        if target is not None:
-            if (not torch.is_tensor(target) or target.dtype != torch.float32 or tuple(target.shape) != (B, Tc, 2) or
-                    target.device != self.device):
-                raise ValueError('step: screen_calibration_target must be a float32 [%d, %d, 2] tensor on %s, got %s %s' % (
-                    B, Tc, self.device, getattr(target, 'dtype', type(target)), tuple(getattr(target, 'shape', ()))))
-            self._screen_samples()               # allocated here, before any capture
-        if valid is not None:
-            if (not torch.is_tensor(valid) or valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) != (B, Tc) or
-                    valid.device != self.device):
-                raise ValueError('step: screen_calibration_valid must be a bool or uint8 [%d, %d] tensor on %s, got %s %s' % (
-                    B, Tc, self.device, getattr(valid, 'dtype', type(valid)), tuple(getattr(valid, 'shape', ()))))
+        keys = ('inv_camera_transformation', 'pixels_per_millimeter')
+        if self._screen_apply or chunk.get('screen_calibration_target') is None:      # applying: the corrected point's PoG_cm and g too
+            keys += ('millimeters_per_pixel', 'camera_transformation')
+        self._check_collecting(chunk, B, Tc, 'screen_calibration', self._screen_apply, self._screen_samples,
+                               [(key, 'the screen geometry (%s)' % key) for key in keys],
+                               ('left_o', 'the eyes\' origins o (left_o, right_o, or a pose form) in the chunk'))
 
     # ------------------------------------------------------------------ gaze events
     def _event_buffers(self):
-        if self._events is None:
-            B, F = self.num_streams, self.fixation_capacity
-            self._events = (torch.zeros((B, 32), dtype=torch.float64, device=self.device),
-                            torch.zeros((B, F, 8), dtype=torch.float64, device=self.device),
-                            torch.zeros((B,), dtype=torch.int32, device=self.device), torch.zeros((B,), dtype=torch.int32, device=self.device))
-        return self._events
+        B, F = self.num_streams, self.fixation_capacity
+        return self._group('_events', StageBuffers, ((B, 32), torch.float64), ((B, F, 8), torch.float64), ((B,), torch.int32), ((B,), torch.int32))
 
     def _closing_spec(self):
         from .data import GazeEventSpec
@@ -514,9 +509,8 @@ class EVEStream(object):
         """Empty the fixation store of the given streams (None = all) and their dropped counters.  The running fixation and the
         filter are state, not store: reset() ends them."""
         m = self._device_mask(streams, 'clear_fixations')
-        _, _, count, dropped = self._event_buffers()
-        count.copy_(torch.where(m, torch.zeros_like(count), count))
-        dropped.copy_(torch.where(m, torch.zeros_like(dropped), dropped))
+        buffers = self._event_buffers()
+        self._zero_where(m, buffers.count, buffers.dropped)
 
     def flush_fixations(self, streams=None):
         """Close the open fixations of the given streams (None = all) on the device, as the end of a recording does: one
@@ -538,15 +532,19 @@ class EVEStream(object):
             raise ValueError('set_event_state: state must be [%d, 32], got %s' % (self.num_streams, tuple(state.shape)))
         self._event_buffers()[0].copy_(state)
 
+    def _output_stage(self):
+        """'final' with a RefineNet, else 'initial': the stage whose point of gaze PoG_px_<out> is the step's output -- what the
+        screen-space map corrects and what events and history take for a source of None."""
+        return 'final' if self.model.refine_net is not None else 'initial'
+
     def _check_events(self, chunk, spec, B, Tc):
         """step()'s `events` checked against the chunk and the model -> what _predict_sequence needs beside the buffers.  Every
         refusal is a ValueError raised before anything is launched or captured."""
         from .data import GazeEventSpec
         if not isinstance(spec, GazeEventSpec):
             raise ValueError('step: events must be an eve_amd.GazeEventSpec, got %s' % type(spec).__name__)
-        has_ref = self.model.refine_net is not None
-        source = spec.source if spec.source is not None else ('PoG_px_final' if has_ref else 'PoG_px_initial')
-        if source == 'PoG_px_final' and not has_ref:
+        source = spec.source if spec.source is not None else 'PoG_px_' + self._output_stage()
+        if source == 'PoG_px_final' and self.model.refine_net is None:
             raise ValueError('step: events filters PoG_px_final, which RefineNet produces, and the model has no RefineNet')
         for key in ('inv_camera_transformation', 'pixels_per_millimeter'):
             if key not in chunk:
@@ -556,9 +554,8 @@ class EVEStream(object):
         ft = chunk.get('frame_time')
         if ft is None and spec.fps is None:
             raise ValueError('step: events needs frame_time in the chunk (float64 [B, Tc] seconds) or a spec with fps')
-        if ft is not None and (not torch.is_tensor(ft) or ft.dtype != torch.float64 or tuple(ft.shape) != (B, Tc) or ft.device != self.device):
-            raise ValueError('step: frame_time must be a float64 [%d, %d] tensor on %s, got %s %s' % (
-                B, Tc, self.device, getattr(ft, 'dtype', type(ft)), tuple(getattr(ft, 'shape', ()))))
+        if ft is not None:
+            self._check_chunk_tensor('frame_time', ft, (torch.float64,), (B, Tc))
         self._event_buffers()                    # allocated here, before any capture
         return {'spec': spec, 'source': source}
 
@@ -600,8 +597,7 @@ class EVEStream(object):
             return
         m = self._device_mask(streams, 'clear_gaze_history')
         for e in entries:
-            e['maps'].copy_(torch.where(m[:, None, None], torch.zeros_like(e['maps']), e['maps']))
-            e['state'].copy_(torch.where(m[:, None], torch.zeros_like(e['state']), e['state']))
+            self._zero_where(m, e['maps'], e['state'])
 
     def get_gaze_history_state(self):
         """The gaze history's carried state: {name: {'spec': the GazeHistorySpec, 'maps': float32 [B, MH, MW], 'rows': float64 [B, 8]
@@ -644,14 +640,13 @@ class EVEStream(object):
         cfg, has_ref = self.model.config, self.model.refine_net is not None
         taken = set(getattr(self.model, 'PREDICTION_KEYS', ())) | set(GAZE_EVENT_KEYS) | {'valid', 'eye_valid', 'pose_valid', 'rendered', 'heatmap_final'}
         ft = chunk.get('frame_time')
-        if ft is not None and (not torch.is_tensor(ft) or ft.dtype != torch.float64 or tuple(ft.shape) != (B, Tc) or ft.device != self.device):
-            raise ValueError('step: frame_time must be a float64 [%d, %d] tensor on %s, got %s %s' % (
-                B, Tc, self.device, getattr(ft, 'dtype', type(ft)), tuple(getattr(ft, 'shape', ()))))
+        if ft is not None:
+            self._check_chunk_tensor('frame_time', ft, (torch.float64,), (B, Tc))
         plans = []
         for spec in specs:
             if spec.name in taken or spec.name in chunk or any(spec.name == s_.name + '_frames' for s_ in specs):
                 raise ValueError('step: history: the name %r is a key of the chunk or of the step\'s result already' % (spec.name,))
-            source = spec.source if spec.source is not None else ('PoG_px_final' if has_ref else 'PoG_px_initial')
+            source = spec.source if spec.source is not None else 'PoG_px_' + self._output_stage()
             if source in ('PoG_px_final', 'heatmap_final') and not has_ref:
                 raise ValueError('step: history accumulates %s, which RefineNet produces, and the model has no RefineNet' % source)
             if source in ('PoG_px_filtered', 'fixation_px') and events is None:
@@ -669,9 +664,8 @@ class EVEStream(object):
                 known = (vk == 'fixating' and events is not None) or (vk == 'valid' and masked)
                 if entry is None and not known:
                     raise ValueError('step: history: valid_key %r is neither in the chunk nor a [B, Tc] result of this step' % (vk,))
-                if entry is not None and (not torch.is_tensor(entry) or entry.dtype not in (torch.bool, torch.uint8) or
-                                          tuple(entry.shape) != (B, Tc) or entry.device != self.device):
-                    raise ValueError('step: history: valid_key %r must be a bool or uint8 [%d, %d] tensor on %s' % (vk, B, Tc, self.device))
+                if entry is not None:
+                    self._check_chunk_tensor('history: valid_key %r' % (vk,), entry, (torch.bool, torch.uint8), (B, Tc), got=False)
             if ft is None and spec.fps is None:
                 raise ValueError('step: history needs frame_time in the chunk (float64 [B, Tc] seconds) or a spec with fps')
             e = self._history.get(spec.name)
@@ -686,25 +680,26 @@ class EVEStream(object):
             e = self._history_entry(plan['spec'], plan['P'])
             plan['state'], plan['maps'] = e['state'], e['maps']
 
-    def _reset_idle_histories(self, plans):
-        """A reset before a step that does not run some map's spec: that map and its time chain are still cleared where flagged, by
-        the two launches with no frames."""
-        running = set() if plans is None else {p['spec'].name for p in plans}
+    def _reset_idle_stages(self, events, gate, history):
+        """A reset before a step that does not run a stage which carries state (events, gate, history: None or this step's plans): the
+        stage's state of the flagged streams still ends."""
+        flags = self._flags[:self.num_streams]
         k = default_kernels()
+        if events is None and self._events is not None:
+            # the gaze events' state ends its fixation and starts afresh: the launch with no frames
+            k.gaze_events(None, None, None, None, self._closing_spec(), *self._events, reset=flags)
+        running = set() if history is None else {p['spec'].name for p in history}
         for name, e in self._history.items():
-            if name not in running:
-                coef, clear = k.gaze_history_plan(e['P'], tuple(self.model.config.actual_screen_size), e['state'], 0,
-                                                  reset=self._flags[:self.num_streams])
+            if name not in running:              # that map and its time chain are cleared by the two launches with no frames
+                coef, clear = k.gaze_history_plan(e['P'], tuple(self.model.config.actual_screen_size), e['state'], 0, reset=flags)
                 k.gaze_history_update(e['P'], coef, clear, e['maps'])
+        if gate is None and self._gate is not None:
+            self._zero_where(flags != 0, self._gate.state)       # the gate's rows (its launch refuses T = 0)
 
     # ------------------------------------------------------------------ the eye gate
     def _gate_buffers(self):
-        if self._gate is None:
-            B, C = self.num_streams, self.blink_capacity
-            self._gate = (torch.zeros((B, 2, 8), dtype=torch.float64, device=self.device),
-                          torch.zeros((B, C, 4), dtype=torch.float64, device=self.device),
-                          torch.zeros((B,), dtype=torch.int32, device=self.device), torch.zeros((B,), dtype=torch.int32, device=self.device))
-        return self._gate
+        B, C = self.num_streams, self.blink_capacity
+        return self._group('_gate', StageBuffers, ((B, 2, 8), torch.float64), ((B, C, 4), torch.float64), ((B,), torch.int32), ((B,), torch.int32))
 
     def blinks(self, streams=None):
         """The completed blinks of the given streams (None = all; indices or a bool mask), one numpy float64 [n, 4] array per stream
@@ -725,9 +720,8 @@ class EVEStream(object):
         """Empty the blink store of the given streams (None = all) and their dropped counters.  The running closure, the baseline
         and the hold-off are state, not store: reset() ends them."""
         m = self._device_mask(streams, 'clear_blinks')
-        _, _, count, dropped = self._gate_buffers()
-        count.copy_(torch.where(m, torch.zeros_like(count), count))
-        dropped.copy_(torch.where(m, torch.zeros_like(dropped), dropped))
+        buffers = self._gate_buffers()
+        self._zero_where(m, buffers.count, buffers.dropped)
 
     def get_gate_state(self):
         """The eye gate's carried state, float64 [B, 2, 8] (fresh; include/eve_hip.h eve_eye_gate has the layout): per stream and eye
@@ -840,11 +834,7 @@ class EVEStream(object):
             self._pending = None
             return
         m = np.concatenate([self._pending, self._pending]).astype(np.int32)
-        host = torch.from_numpy(m)
-        if self.device.type == 'cuda':
-            # a pinned block of torch's host allocator: the copy is asynchronous and the block is not reused before it has run
-            host = host.pin_memory()
-        self._flags.copy_(host, non_blocking=True)
+        self._flags.copy_(self._pinned(torch.from_numpy(m)), non_blocking=True)
         self._flags_set = True
         self._pending = None
 
@@ -861,10 +851,7 @@ class EVEStream(object):
         return a.astype(np.int32)
 
     def _upload_lengths(self, n):
-        host = torch.from_numpy(np.concatenate([n, n]))
-        if self.device.type == 'cuda':
-            host = host.pin_memory()             # as _upload_resets: asynchronous, and never baked into a graph
-        self._lengths.copy_(host, non_blocking=True)
+        self._lengths.copy_(self._pinned(torch.from_numpy(np.concatenate([n, n]))), non_blocking=True)
 
     def _eye_mask(self, eye_mask, Tc):
         """step()'s `eye_mask` checked -> (uint8 [B, Tc, 2] tensor, on the device or on the host (then pinned where the model is on
@@ -882,32 +869,46 @@ class EVEStream(object):
             raise ValueError('step: eye_mask must be bool or integers, not %s' % a.dtype)
         if a.shape != shape:
             raise ValueError('step: eye_mask must be [num_streams, Tc, 2] = %s, got %s' % (shape, a.shape))
-        host = torch.from_numpy((a != 0).astype(np.uint8))
-        return host.pin_memory() if self.device.type == 'cuda' else host     # as _upload_resets: asynchronous, never baked into a graph
+        return self._pinned(torch.from_numpy((a != 0).astype(np.uint8)))
 
     def _check_calibration(self, chunk, B, Tc):
         """step()'s calibration keys, and what an applying step needs, checked before anything is launched or captured."""
-        target, valid = chunk.get('calibration_target'), chunk.get('calibration_valid')
-        if target is None and valid is None and not self._calib_apply:
+        self._check_collecting(chunk, B, Tc, 'calibration', self._calib_apply, self._store,
+                               [('inv_camera_transformation', 'the camera geometry (inv_camera_transformation)')],
+                               ('head_R', 'head_R in the chunk: the offset is applied in the head\'s frame'))
+
+    def _check_collecting(self, chunk, B, Tc, name, applied, allocate, geometry, derived):
+        """What both calibrations check of a step: <name>_target / <name>_valid, and what a collecting or an applying step needs in
+        the chunk -- geometry: (key, its description) pairs; derived: (key, description) of the one a pose form stands in for."""
+        target, valid = chunk.get(name + '_target'), chunk.get(name + '_valid')
+        if target is None and valid is None and not applied:
             return
         if target is None and valid is not None:
-            raise ValueError('step: calibration_valid comes with calibration_target')
-        what = 'calibration_target' if target is not None else 'an applied calibration'
-        if 'inv_camera_transformation' not in chunk:
-            raise ValueError('step: %s needs the camera geometry (inv_camera_transformation) in the chunk' % what)
-        if 'head_R' not in chunk and not has_pose_form(chunk):
-            raise ValueError('step: %s needs head_R in the chunk: the offset is applied in the head\'s frame' % what)
+            raise ValueError('step: %s_valid comes with %s_target' % (name, name))
+        what = name + '_target' if target is not None else 'an applied ' + name.replace('_', ' ')
+        for key, described in geometry:
+            if key not in chunk:
+                raise ValueError('step: %s needs %s in the chunk' % (what, described))
+        if derived[0] not in chunk and not has_pose_form(chunk):
+            raise ValueError('step: %s needs %s' % (what, derived[1]))
         if target is not None:
-            if (not torch.is_tensor(target) or target.dtype != torch.float32 or tuple(target.shape) != (B, Tc, 2) or
-                    target.device != self.device):
-                raise ValueError('step: calibration_target must be a float32 [%d, %d, 2] tensor on %s, got %s %s' % (
-                    B, Tc, self.device, getattr(target, 'dtype', type(target)), tuple(getattr(target, 'shape', ()))))
-            self._store()                        # allocated here, before any capture
+            self._check_chunk_tensor(name + '_target', target, (torch.float32,), (B, Tc, 2))
+            allocate()                           # the sample store: allocated here, before any capture
         if valid is not None:
-            if (not torch.is_tensor(valid) or valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) != (B, Tc) or
-                    valid.device != self.device):
-                raise ValueError('step: calibration_valid must be a bool or uint8 [%d, %d] tensor on %s, got %s %s' % (
-                    B, Tc, self.device, getattr(valid, 'dtype', type(valid)), tuple(getattr(valid, 'shape', ()))))
+            self._check_chunk_tensor(name + '_valid', valid, (torch.bool, torch.uint8), (B, Tc))
+
+    def _check_chunk_tensor(self, name, t, dtypes, shape, got=True, form=None):
+        """One entry of the chunk that a stage reads: a tensor of one of dtypes and of that shape (None: any extent) on the model's
+        device, or ValueError('step: <name> must be ...').  form: the entry in words, for one with free extents -- its device is
+        then left to the launch's wrapper."""
+        if (torch.is_tensor(t) and t.dtype in dtypes and t.dim() == len(shape) and all(n is None or n == m for n, m in zip(shape, t.shape)) and
+                (form is not None or t.device == self.device)):
+            return
+        if form is None:
+            form = 'a %s [%s] tensor on %s' % (' or '.join(str(dtype)[len('torch.'):] for dtype in dtypes), ', '.join('%d' % n for n in shape),
+                                               self.device)
+        raise ValueError('step: %s must be %s%s' % (name, form, ', got %s %s' % (getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ())))
+                                                    if got else ''))
 
     def _set_pose_gate(self, skip_invalid_pose):
         if self._pose_gate_host != (not skip_invalid_pose):
@@ -915,34 +916,32 @@ class EVEStream(object):
             self._pose_gate.fill_(self._pose_gate_host)              # a device value: the captured graphs read it, the host never waits
 
     def _run(self, chunk, return_heatmaps, ragged=False, eye_mask=None, masked=False, render=None, events=None, gate=None, history=None):
-        # render: None or a _render_plan; the keyword reaches _predict_sequence only then, so a step without it calls what it always did
-        extra = {} if render is None else {'render': self._render_hook(render, ragged, masked)}
-        if history is not None:                  # history: None or _check_history's plans; the keyword goes along only then
-            extra['history'] = history
+        """The one call of EVE._predict_sequence, eager or under capture.  render, events, gate, history: None or the plan of that
+        stage's check.  A stage's keyword goes along only when the stage runs, and lengths, the mask's keywords and face_state only
+        on a ragged, a masked and a face-landmark step: a step without them makes the call it always made."""
+        faced = face_landmarks_key(chunk) is not None
+        kw = {'reset': self._flags, 'return_heatmaps': return_heatmaps}
+        if ragged or masked or faced:
+            kw['lengths'] = self._lengths if ragged else None
+        if masked or faced:
+            kw.update(masked=masked, eye_mask=eye_mask, pose_gate=self._pose_gate if masked and has_pose_form(chunk) else None)
+        if faced:                                # the face-landmark form: the carried head pose goes along
+            kw['face_state'] = self._face_pose
+        if render is not None:
+            kw['render'] = self._render_hook(render, ragged, masked)
+        if history is not None:
+            kw['history'] = history
         if self._calib_apply or 'calibration_target' in chunk:       # (neither: the call an uncalibrated EVEStream always made)
-            extra['calibration'] = {'kappa': self._calib_kappa, 'ok': self._calib_ok, 'apply': self._calib_apply,
-                                    'store': self._store() if 'calibration_target' in chunk else None}
+            kw['calibration'] = {'kappa': self._calib_kappa, 'ok': self._calib_ok, 'apply': self._calib_apply,
+                                 'store': self._store() if 'calibration_target' in chunk else None}
         if self._screen_apply or 'screen_calibration_target' in chunk:      # (neither: no keyword, no launch)
-            extra['screen_calibration'] = {'coef': self._screen_coef, 'kind': self._screen_kind, 'apply': self._screen_apply,
-                                           'store': self._screen_samples() if 'screen_calibration_target' in chunk else None}
-        if events is not None:                   # events: None or a _check_events plan; the keyword goes along only then
-            state, store, count, dropped = self._event_buffers()
-            extra['events'] = dict(events, state=state, store=store, count=count, dropped=dropped)
-        if gate is not None:                     # gate: None or a _check_gate plan; the keyword goes along only then
-            state, store, count, dropped = self._gate_buffers()
-            extra['gate'] = dict(gate, state=state, store=store, count=count, dropped=dropped)
-        if face_landmarks_key(chunk) is not None:      # the face-landmark form: the carried head pose goes along
-            return self.model._predict_sequence(chunk, self._eye, self._ref, reset=self._flags, return_heatmaps=return_heatmaps,
-                                                lengths=self._lengths if ragged else None, masked=masked, eye_mask=eye_mask,
-                                                pose_gate=self._pose_gate if masked else None, face_state=self._face_pose, **extra)
-        if masked:
-            return self.model._predict_sequence(chunk, self._eye, self._ref, reset=self._flags, return_heatmaps=return_heatmaps,
-                                                lengths=self._lengths if ragged else None, masked=True, eye_mask=eye_mask,
-                                                pose_gate=self._pose_gate if 'eye_pose' in chunk else None, **extra)
-        if not ragged:
-            return self.model._predict_sequence(chunk, self._eye, self._ref, reset=self._flags, return_heatmaps=return_heatmaps, **extra)
-        return self.model._predict_sequence(chunk, self._eye, self._ref, reset=self._flags, return_heatmaps=return_heatmaps,
-                                            lengths=self._lengths, **extra)
+            kw['screen_calibration'] = {'coef': self._screen_coef, 'kind': self._screen_kind, 'apply': self._screen_apply,
+                                        'store': self._screen_samples() if 'screen_calibration_target' in chunk else None}
+        if events is not None:
+            kw['events'] = dict(events, **self._event_buffers()._asdict())
+        if gate is not None:
+            kw['gate'] = dict(gate, **self._gate_buffers()._asdict())
+        return self.model._predict_sequence(chunk, self._eye, self._ref, **kw)
 
     # ------------------------------------------------------------------ the overlay (step(chunk, render=spec))
     def _render_plan(self, chunk, spec, events=None, history=None):
@@ -986,7 +985,7 @@ class EVEStream(object):
             from .data import GAZE_EVENT_KEYS
             results += GAZE_EVENT_KEYS
         if self._screen_apply:                   # an applied screen map: the uncorrected point can be drawn beside the corrected one
-            results += ('PoG_px_final_raw' if ref is not None else 'PoG_px_initial_raw', 'screen_calibrated')
+            results += ('PoG_px_%s_raw' % self._output_stage(), 'screen_calibrated')
         if spec.heat_key is not None:            # a gaze history map of this step in place of heatmap_final
             named = [h for h in (history or ()) if h['spec'].name == spec.heat_key]
             if not named:
@@ -1011,9 +1010,8 @@ class EVEStream(object):
             inset_hw = (ph, 2 * pw)
         elif spec.inset is not None:
             p = chunk.get(spec.inset)
-            if (not torch.is_tensor(p) or p.dtype != torch.uint8 or p.dim() != 5 or tuple(p.shape[:2]) != (B, Tc) or p.shape[4] != 3):
-                raise ValueError('step: render: inset %r must be a uint8 [B, Tc, h, w, 3] entry of the chunk, got %s %s' % (
-                    spec.inset, getattr(p, 'dtype', type(p)), tuple(getattr(p, 'shape', ()))))
+            self._check_chunk_tensor('render: inset %r' % (spec.inset,), p, (torch.uint8,), (B, Tc, None, None, 3),
+                                     form='a uint8 [B, Tc, h, w, 3] entry of the chunk')
             inset_hw = (int(p.shape[2]), int(p.shape[3]))
         inset_xy = None
         if inset_hw is not None:
@@ -1284,9 +1282,8 @@ class EVEStream(object):
         otherwise, as for PoG_px_final without a RefineNet.  The spec by value and frame_time's presence are part of the graph's
         key; lengths, eye_mask, skip_invalid_pose, every camera and screen form, an applied calibration and render combine with it,
         and render's markers may name the new keys (dict(key='fixation_px', valid='fixating'), key='PoG_px_filtered').
-        tests/gaze_events_ref.py states the arithmetic.  Not offered: dispersion (I-DT) or other classifiers, windowed velocity,
-        merging of adjacent fixations and retroactive relabelling, smooth-pursuit and blink classes, per-eye events, gradients,
-        EVE.forward.  events=None issues exactly the launches the step always issued.
+        tests/gaze_events_ref.py states the arithmetic.  What is not offered: module docstring, "Gaze events".  events=None issues
+        exactly the launches the step always issued.
 
         gate: None, or an eve_amd.EyeGateSpec -- one eve_eye_gate launch after the pose derivation and before the mask plan, inside the
         captured graph, decides per frame and eye whether the eye is usable, and that verdict is the step's eye_mask (ANDed with
@@ -1309,10 +1306,8 @@ class EVEStream(object):
         blink uint8 [B, Tc, 2].  eye_contours works with pre-cut patches too.  A criterion whose input the chunk or the model does
         not provide, a blink without eye_contours, and eye_contours of another dtype, shape or device are ValueErrors raised
         before anything is launched or captured.  The spec by value and eye_contours' shape are part of the graph's key; lengths,
-        eye_mask, every camera and screen form, calibration, events and render combine with it.  Not offered: adaptive thresholds
-        learnt per person, a closure announced before its first closed frame, blink times in seconds, a mid-chunk reset of stale
-        recurrent state after a long gap, coverage through the lens model, gradients, EVE.forward.  gate=None issues exactly the
-        launches the step always issued.
+        eye_mask, every camera and screen form, calibration, events and render combine with it.  What is not offered: module
+        docstring, "The eye gate".  gate=None issues exactly the launches the step always issued.
 
         history: None, an eve_amd.GazeHistorySpec, or a list of up to two with distinct names -- per spec one eve_gaze_history_plan and
         one eve_gaze_history_update launch after the screen-space map and the events stage and before the overlay, inside the captured
@@ -1330,9 +1325,8 @@ class EVEStream(object):
         defaults resolved, are part of the graph's key; lengths, eye_mask, gate=, events=, both calibrations, every camera and screen
         form and render combine with it, and OverlaySpec(heat_key=<name>) blends the per_frame map of that name in place of
         heatmap_final (a map with an axis above 1024, one without per_frame, and heat_key beside heat=True are ValueErrors).  The host
-        does not wait.  tests/gaze_history_ref.py states the arithmetic, exact to the bit.  Not offered: areas of interest and
-        dwell-per-region tables, per-eye maps, a windowed history, anisotropic or screen-millimetre sigmas, gradients, EVE.forward,
-        maps larger than 2048 per axis.  history=None issues exactly the launches the step always issued."""
+        does not wait.  tests/gaze_history_ref.py states the arithmetic, exact to the bit.  What is not offered: module docstring,
+        "Gaze history".  history=None issues exactly the launches the step always issued."""
         if self.model.training:
             raise ValueError('EVEStream runs inference only: the model was switched to training mode')
         B, Tc = eye_input(chunk).shape[:2]
@@ -1354,10 +1348,7 @@ class EVEStream(object):
         if history is not None:
             more['history'] = history = self._check_history(chunk, history, events, masked, B, Tc)
         if render is not None:
-            if history is not None:
-                render = self._render_plan(chunk, render, events, history)
-            else:
-                render = self._render_plan(chunk, render) if events is None else self._render_plan(chunk, render, events)
+            render = self._render_plan(chunk, render, events, history)
         self._check_calibration(chunk, B, Tc)
         self._check_screen_calibration(chunk, B, Tc)
         if history is not None:
@@ -1369,17 +1360,8 @@ class EVEStream(object):
         self._upload_resets()
         if events is not None:
             self._events_spec = events['spec']
-        elif self._events is not None and self._flags_set:
-            # a reset before a step without events: the gaze events' state still ends its fixation and starts afresh (no frames)
-            state, store, count, dropped = self._events
-            default_kernels().gaze_events(None, None, None, None, self._closing_spec(), state, store, count, dropped,
-                                          reset=self._flags[:self.num_streams])
-        if self._history and self._flags_set:
-            self._reset_idle_histories(history)
-        if gate is None and self._gate is not None and self._flags_set:
-            # a reset before a step without gate: the gate's rows of the flagged streams are still cleared (the launch refuses T = 0)
-            state = self._gate[0]
-            state.copy_(torch.where(self._flags[:self.num_streams, None, None] != 0, torch.zeros_like(state), state))
+        if self._flags_set:
+            self._reset_idle_stages(events, gate, history)
         with torch.no_grad():
             if self.use_graph:
                 entry = self._graph_for(chunk, bool(return_heatmaps), ragged, masked, render, events, **more)
@@ -1395,8 +1377,7 @@ class EVEStream(object):
             else:
                 if eye_mask is not None and eye_mask.device != self.device:
                     eye_mask = torch.empty(eye_mask.shape, dtype=torch.uint8, device=self.device).copy_(eye_mask, non_blocking=True)
-                out = self._run(chunk, return_heatmaps, ragged, eye_mask, masked, render, **more) if events is None else \
-                    self._run(chunk, return_heatmaps, ragged, eye_mask, masked, render, events, **more)
+                out = self._run(chunk, return_heatmaps, ragged, eye_mask, masked, render, events, **more)
             if ragged and not masked:
                 out['valid'] = torch.arange(Tc, device=self.device)[None, :] < self._lengths[:self.num_streams, None]
         if self._flags_set:
@@ -1465,14 +1446,7 @@ class EVEStream(object):
             side = _WARMUP_STREAMS[dev_index] = torch.cuda.Stream(device=dev_index)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
-            # the calibration store, its counters and the kappa rows too: the warm-up steps of a collecting graph would otherwise
-            # append every sample three times
-            # (and the gaze events' state, store and counters: a capture would otherwise tick the filter three times)
-            carried = self._state_tensors() + [self._face_pose, self._calib_kappa, self._calib_ok] + list(self._calib_store or ()) + \
-                list(self._events or ()) + list(self._gate or ()) + \
-                list(self._screen_store or ()) + \
-                [t for e in self._history.values() for t in (e['state'], e['maps'])]     # (the eye gate's ticks, baselines and blinks; the
-            #                                                                              screen map's samples; the gaze history's maps and time chains)
+            carried = self._carried()
             snap = [t.clone() for t in carried]
             for _ in range(2):
                 self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history)
