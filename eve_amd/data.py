@@ -1004,9 +1004,9 @@ class GazeHistorySpec(object):
       normalize       True: every deposit times 1 / (2 pi sigma^2), so the map integrates to the weight deposited
       per_frame       True: also the map after every frame
     Instances compare and hash by value: the spec is part of a captured graph's key, and a map is tied to its spec.  Not offered:
-    areas of interest and dwell-per-region tables, per-eye maps, a windowed history (as opposed to the decayed one), anisotropic or
-    screen-millimetre sigmas, gradients, EVE.forward (its create_images path keeps the torch restatement), maps larger than 2048 per
-    axis."""
+    per-eye maps, a windowed history (as opposed to the decayed one), anisotropic or screen-millimetre sigmas, gradients, EVE.forward
+    (its create_images path keeps the torch restatement), maps larger than 2048 per axis.  (Areas of interest and dwell-per-region
+    tables: AoiSpec.)"""
 
     def __init__(self, name='gaze_history', source=None, valid_key=None, size=None, sigma=None, decay_per_ms=None, weight='frame',
                  max_gap_s=0.075, fps=None, floor=0.0, normalize=False, per_frame=False):
@@ -1126,6 +1126,172 @@ def gaze_history(spec, screen_size, pog_px=None, heatmaps=None, frame_time=None,
     if spec.per_frame:
         out[spec.name + '_frames'] = frames
     return out
+
+
+AOI_SOURCES = ('PoG_px_initial', 'PoG_px_final', 'PoG_px_filtered', 'fixation_px')
+AOI_MAX = 64                                     # areas of interest per table
+AOI_ROW = 36                                     # floats per area: kind, vertex count, two reserved, 32 coordinates
+AOI_MAX_VERTICES = 16
+AOI_KEYS = ('id', 'mask', 'visit_ms')            # the per-frame results, as <name>_<key>
+
+
+class AoiSpec(object):
+    """What EVEStream.step(chunk, aoi=spec) adds to the step (eve_gaze_aoi): per frame the area of interest the point of gaze is in,
+    and per stream the visits, the dwell table and the transition matrix over the chunk's aoi_shapes (data.aoi_shapes builds them).
+      name            the prefix of the result keys <name>_id, <name>_mask, <name>_visit_ms, and the name of the tallies
+      num_aois        A, 1 .. 64: the rows of the shape table
+      source          'PoG_px_initial', 'PoG_px_final', 'PoG_px_filtered', 'fixation_px' (the last two need events= in the same step), or
+                      None: PoG_px_final with a RefineNet, else PoG_px_initial (the rule the events use)
+      valid_key       None or the key of a bool / uint8 [B, Tc] entry of the result or the chunk, ANDed into the frame's usability
+                      (source='fixation_px', valid_key='fixating': the fixation-based AOI analysis)
+      fps             for chunks without frame_time (float64 [B, Tc] seconds, which wins when both are there)
+      max_gap_s       two samples further apart than this are not connected: the open visit ends at its last sample
+      use_fixations   True: count fixations per AOI and per visit from the events stage's fixation_id / fixating (needs events=);
+                      False: never; None: where events= runs in the same step
+    Instances compare and hash by value: the spec is part of a captured graph's key, and the tallies are tied to their spec.  Not
+    offered: label-map AOIs, minimum visit durations or border hysteresis, per-eye AOIs, polygon margins, AOI outlines in the overlay,
+    gradients, EVE.forward."""
+
+    def __init__(self, name='aoi', num_aois=None, source=None, valid_key=None, fps=None, max_gap_s=0.075, use_fixations=None):
+        number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and np.isfinite(v)
+        if not isinstance(name, str) or not name:
+            raise ValueError('AoiSpec: name must be a non-empty string, got %r' % (name,))
+        if isinstance(num_aois, bool) or not isinstance(num_aois, (int, np.integer)) or not 1 <= int(num_aois) <= AOI_MAX:
+            raise ValueError('AoiSpec: num_aois must be an integer in 1 .. %d, got %r' % (AOI_MAX, num_aois))
+        if source is not None and source not in AOI_SOURCES:
+            raise ValueError('AoiSpec: source must be None or one of %s, got %r' % (', '.join(AOI_SOURCES), source))
+        if valid_key is not None and (not isinstance(valid_key, str) or not valid_key):
+            raise ValueError('AoiSpec: valid_key must be None or the key of a [B, Tc] entry, got %r' % (valid_key,))
+        if fps is not None and (not number(fps) or not fps > 0):
+            raise ValueError('AoiSpec: fps must be a finite number > 0, got %r' % (fps,))
+        if not number(max_gap_s) or not max_gap_s > 0:
+            raise ValueError('AoiSpec: max_gap_s must be a finite number > 0, got %r' % (max_gap_s,))
+        if use_fixations is not None and not isinstance(use_fixations, bool):
+            raise ValueError('AoiSpec: use_fixations must be None, True or False, got %r' % (use_fixations,))
+        self.name, self.num_aois, self.source, self.valid_key = name, int(num_aois), source, valid_key
+        self.fps, self.max_gap_s, self.use_fixations = None if fps is None else float(fps), float(max_gap_s), use_fixations
+
+    def key(self):
+        return (self.name, self.num_aois, self.source, self.valid_key, self.fps, self.max_gap_s, self.use_fixations)
+
+    def __eq__(self, other):
+        return isinstance(other, AoiSpec) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'AoiSpec(name=%r, num_aois=%r, source=%r, valid_key=%r, fps=%r, max_gap_s=%r, use_fixations=%r)' % self.key()
+
+
+def aoi_shapes(shapes, num_aois, margin_px=0.0):
+    """The shape table of eve_gaze_aoi, float32 [num_aois, 36] (a CPU tensor), from a list of
+      ('rect', x0, y0, x1, y1)          x0 <= x < x1 and y0 <= y < y1 (half open, so tiles that share an edge do not overlap)
+      ('ellipse', cx, cy, rx, ry)       rx, ry > 0
+      ('polygon', [(x, y), ...])        3 .. 16 vertices, even-odd rule
+      None                              a disabled row
+    in actual_screen_size pixels.  The order is the z-order: a frame's AOI is the first row that contains the point.  Rows past the
+    list are disabled.  margin_px >= 0 grows every rectangle and every ellipse's radii by that much on each side (the usual allowance
+    for the tracker's error); with a margin a polygon is refused.  A row is [kind (0 disabled, 1 rectangle, 2 ellipse, 3 polygon), n,
+    0, 0, coordinates ...].  Stack tables to [B, A, 36], or to [B, Tc, A, 36] for regions that move from frame to frame."""
+    number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and np.isfinite(v)
+    if isinstance(num_aois, bool) or not isinstance(num_aois, (int, np.integer)) or not 1 <= int(num_aois) <= AOI_MAX:
+        raise ValueError('aoi_shapes: num_aois must be an integer in 1 .. %d, got %r' % (AOI_MAX, num_aois))
+    if not number(margin_px) or margin_px < 0:
+        raise ValueError('aoi_shapes: margin_px must be a finite number >= 0, got %r' % (margin_px,))
+    shapes = list(shapes)
+    if len(shapes) > num_aois:
+        raise ValueError('aoi_shapes: %d shapes for num_aois = %d' % (len(shapes), num_aois))
+    table = np.zeros((int(num_aois), AOI_ROW), dtype=np.float32)
+    m = float(margin_px)
+    for i, s in enumerate(shapes):
+        if s is None:
+            continue
+        if not isinstance(s, (tuple, list)) or not s or s[0] not in ('rect', 'ellipse', 'polygon'):
+            raise ValueError('aoi_shapes: shape %d must be None or start with \'rect\', \'ellipse\' or \'polygon\', got %r' % (i, s))
+        if s[0] == 'polygon':
+            if m != 0.0:
+                raise ValueError('aoi_shapes: shape %d: a margin on a polygon is not offered' % i)
+            pts = list(s[1]) if len(s) == 2 and isinstance(s[1], (tuple, list, np.ndarray)) else None
+            if pts is None or not 3 <= len(pts) <= AOI_MAX_VERTICES or \
+                    not all(isinstance(p, (tuple, list, np.ndarray)) and len(p) == 2 and number(p[0]) and number(p[1]) for p in pts):
+                raise ValueError('aoi_shapes: shape %d: a polygon is (\'polygon\', [(x, y), ...]) with 3 .. %d finite vertices, got %r' % (
+                    i, AOI_MAX_VERTICES, s))
+            table[i, 0], table[i, 1] = 3, len(pts)
+            table[i, 4:4 + 2 * len(pts)] = np.asarray(pts, dtype=np.float64).reshape(-1)
+            continue
+        if len(s) != 5 or not all(number(v) for v in s[1:]):
+            raise ValueError('aoi_shapes: shape %d: (%r, four finite numbers), got %r' % (i, s[0], s))
+        c = [float(v) for v in s[1:]]
+        if s[0] == 'rect':
+            if not (c[0] < c[2] and c[1] < c[3]):
+                raise ValueError('aoi_shapes: shape %d: a rectangle needs x0 < x1 and y0 < y1, got %r' % (i, s))
+            with np.errstate(over='ignore'):     # (what does not fit float32 is refused below)
+                table[i, 0], table[i, 4:8] = 1, (c[0] - m, c[1] - m, c[2] + m, c[3] + m)
+        else:
+            if not (c[2] > 0 and c[3] > 0):
+                raise ValueError('aoi_shapes: shape %d: an ellipse needs rx > 0 and ry > 0, got %r' % (i, s))
+            table[i, 0], table[i, 4:8] = 2, (c[0], c[1], c[2] + m, c[3] + m)
+    if not np.isfinite(table).all():
+        raise ValueError('aoi_shapes: a coordinate does not fit float32')
+    return torch.from_numpy(table)
+
+
+def gaze_aoi(spec, pog_px, shapes, frame_time=None, valid=None, lengths=None, fixation_id=None, fixating=None, visit_capacity=256):
+    """The areas of interest of S recorded streams, stand-alone and from fresh state: spec an AoiSpec (its name prefixes the per-frame
+    keys; source, valid_key and use_fixations are not looked at); pog_px float32 [S, T, 2] (actual_screen_size pixels); shapes float32
+    [S, A, 36] or [S, T, A, 36] (aoi_shapes), A = spec.num_aois; frame_time None (then spec.fps) or float64 [S, T] seconds; valid None or
+    bool / uint8 [S, T]; lengths None or int32 [S] on the device; fixation_id int32 [S, T] with fixating bool / uint8 [S, T] (the events'
+    outputs), or neither.  One eve_gaze_aoi launch, which also closes the visits still open at the clip's end.  -> <name>_id int32
+    [S, T] (the AOI, -1 outside all, -2 not a sample), <name>_mask int64 [S, T] (bit a: AOI a contains the point), <name>_visit_ms float32
+    [S, T], plus table float64 [S, A + 1, 8] (rows (dwell_s, samples, visits, t_first_entry, t_last, fixations, t_first_fixation, 0);
+    row A: no AOI), transitions int32 [S, A + 1, A] (row A: the first visit), visits float64 [S, visit_capacity, 8] (rows (aoi, t_enter,
+    t_last, samples, fixations, visit_index, 0, 0)), visit_count and visit_dropped int32 [S], and state float64 [S, 16]; the host does
+    not wait.  Not offered: see AoiSpec."""
+    if not isinstance(spec, AoiSpec):
+        raise ValueError('gaze_aoi: spec must be an eve_amd.AoiSpec, got %s' % type(spec).__name__)
+    if not torch.is_tensor(pog_px) or pog_px.dtype != torch.float32 or pog_px.dim() != 3 or pog_px.shape[2] != 2 or pog_px.numel() == 0:
+        raise TypeError('gaze_aoi: pog_px must be float32 [S, T, 2], got %s %s' % (getattr(pog_px, 'dtype', type(pog_px)),
+                                                                                 tuple(getattr(pog_px, 'shape', ()))))
+    S, T = pog_px.shape[:2]
+    A = spec.num_aois
+    if not torch.is_tensor(shapes) or shapes.dtype != torch.float32 or tuple(shapes.shape) not in ((S, A, AOI_ROW), (S, T, A, AOI_ROW)):
+        raise TypeError('gaze_aoi: shapes must be float32 [%d, %d, 36] or [%d, %d, %d, 36], got %s %s' % (
+            S, A, S, T, A, getattr(shapes, 'dtype', type(shapes)), tuple(getattr(shapes, 'shape', ()))))
+    if frame_time is None and spec.fps is None:
+        raise ValueError('gaze_aoi: frame_time, or a spec with fps')
+    if frame_time is not None and (not torch.is_tensor(frame_time) or frame_time.dtype != torch.float64 or tuple(frame_time.shape) != (S, T)):
+        raise TypeError('gaze_aoi: frame_time must be float64 [%d, %d] seconds' % (S, T))
+    if valid is not None:
+        valid = _bool_rows(valid, (S, T), 'gaze_aoi: valid')
+    if lengths is not None and (not torch.is_tensor(lengths) or lengths.dtype != torch.int32 or tuple(lengths.shape) != (S,)):
+        raise TypeError('gaze_aoi: lengths must be an int32 [%d] tensor' % S)
+    if (fixation_id is None) != (fixating is None):
+        raise ValueError('gaze_aoi: fixation_id and fixating come together')
+    if fixation_id is not None:
+        if not torch.is_tensor(fixation_id) or fixation_id.dtype != torch.int32 or tuple(fixation_id.shape) != (S, T):
+            raise TypeError('gaze_aoi: fixation_id must be int32 [%d, %d]' % (S, T))
+        fixation_id, fixating = fixation_id.contiguous(), _bool_rows(fixating, (S, T), 'gaze_aoi: fixating')
+    if isinstance(visit_capacity, bool) or not isinstance(visit_capacity, (int, np.integer)) or visit_capacity < 1:
+        raise ValueError('gaze_aoi: visit_capacity must be an integer >= 1, got %r' % (visit_capacity,))
+    visit_capacity = int(visit_capacity)
+    dev = pog_px.device
+    state, table, trans, visits, count, dropped = aoi_buffers(S, A, visit_capacity, dev)
+    out = default_kernels().gaze_aoi(pog_px.contiguous(), shapes.contiguous(), spec, state, table, trans, visits, count, dropped,
+                                     frame_time=None if frame_time is None else frame_time.contiguous(), valid=valid,
+                                     fixation_id=fixation_id, fixating=fixating, lengths=None if lengths is None else lengths.contiguous(),
+                                     flush=torch.ones((S,), dtype=torch.int32, device=dev))
+    out = {'%s_%s' % (spec.name, k_): v for k_, v in out.items()}
+    out.update(table=table, transitions=trans, visits=visits, visit_count=count, visit_dropped=dropped, state=state)
+    return out
+
+
+def aoi_buffers(S, A, visit_capacity, device):
+    """-> (state float64 [S, 16], table float64 [S, A + 1, 8], trans int32 [S, A + 1, A], visits float64 [S, visit_capacity, 8], count and
+    dropped int32 [S]) of S streams that have seen nothing: what eve_gaze_aoi carries."""
+    z = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=device)
+    return (z((S, 16), torch.float64), z((S, A + 1, 8), torch.float64), z((S, A + 1, A), torch.int32), z((S, visit_capacity, 8), torch.float64),
+            z((S,), torch.int32), z((S,), torch.int32))
 
 
 EYE_GATE_KEYS = ('eye_gate_reason', 'eye_openness', 'blink')

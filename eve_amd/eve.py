@@ -366,7 +366,7 @@ class EVE(nn.Module):
 
     def _predict_sequence(self, d, eye_states, refine_states, reset=None, return_heatmaps=False, lengths=None, masked=False,
                           eye_mask=None, pose_gate=None, face_state=None, render=None, calibration=None, events=None, gate=None,
-                          screen_calibration=None, history=None):
+                          screen_calibration=None, history=None, aoi=None):
         """The prediction part of forward() for one chunk of an EVEStream: eval only, no labels, no losses.  d: the chunk's
         inputs [B, Tc, ...] (not modified; camera_frame may be any one key of eye_net.EYE_FRAME_KEYS or camera_surface, and the screen any one
         key of refine_net.SCREEN_FRAME_KEYS or screen_surface; the eyes as patches, as camera_frame + {left,right}_eye_warp, or as camera_frame +
@@ -421,7 +421,13 @@ class EVE(nn.Module):
         accumulates, 'P': the launches' scalars, 'state': float64 [B, 8], 'maps': float32 [B, MH, MW]}: per entry one
         eve_gaze_history_plan and one eve_gaze_history_update launch, after the events stage and before the render hook, over the step's
         own source (a point of gaze, or heatmap_final), with frame_time from d when it is there, the step's lengths, `valid` (masked)
-        and reset flags; the result gains <name> (a copy of the carried map) and with per_frame <name>_frames.  None issues no launch."""
+        and reset flags; the result gains <name> (a copy of the carried map) and with per_frame <name>_frames.  None issues no launch.
+        aoi: None, or EVEStream's areas-of-interest stage {'spec': a data.AoiSpec, 'source': the result key whose point is tested,
+        'use_fixations': bool, 'state': float64 [B, 16], 'table': float64 [B, A + 1, 8], 'trans': int32 [B, A + 1, A], 'visits': float64
+        [B, V, 8], 'count', 'dropped': int32 [B]}: one eve_gaze_aoi launch, after the history stage and before the render hook, over the
+        step's own source point and d['aoi_shapes'] ([B, A, 36] or [B, Tc, A, 36]), with frame_time from d when it is there, the step's
+        lengths, `valid` (masked) and reset flags, and with use_fixations the events stage's fixation_id / fixating; the result gains
+        <name>_id, <name>_mask and <name>_visit_ms.  None issues no launch."""
         assert not self.training, 'EVE._predict_sequence is eval-only'
         B = eye_input(d).shape[0]
         posed, faced = has_pose_form(d), face_landmarks_key(d) is not None
@@ -494,6 +500,8 @@ class EVE(nn.Module):
                 lengths=lengths_b, reset=reset_b))
         if history is not None:
             self._gaze_history(d, inter, out, history, lengths_b, reset_b, plan)
+        if aoi is not None:
+            self._gaze_aoi(d, inter, out, aoi, lengths_b, reset_b, plan)
         if render is not None:
             render(d, inter, out)
         return out
@@ -526,6 +534,28 @@ class EVE(nn.Module):
             out[spec.name] = h['maps'].clone()
             if spec.per_frame:
                 out[spec.name + '_frames'] = frames
+
+    def _gaze_aoi(self, d, inter, out, aoi, lengths, reset, plan):
+        """The areas-of-interest stage of an EVEStream step: one eve_gaze_aoi launch on the carried buffers."""
+        B, T = eye_input(d).shape[:2]
+        spec = aoi['spec']
+
+        def look(key):
+            for src in (out, inter, d):
+                if key in src:
+                    return src[key]
+            raise ValueError('step: aoi: %r is neither in the chunk nor a result of this step' % (key,))
+
+        fix = {}
+        if aoi['use_fixations']:
+            fix = {'fixation_id': out['fixation_id'].contiguous(), 'fixating': _u8(out['fixating'].reshape(B, T))}
+        res = default_kernels().gaze_aoi(
+            _f32(look(aoi['source']), B, T, 2), d['aoi_shapes'].contiguous(), spec, aoi['state'], aoi['table'], aoi['trans'], aoi['visits'],
+            aoi['count'], aoi['dropped'], frame_time=d['frame_time'].contiguous() if 'frame_time' in d else None,
+            valid=None if plan is None else plan['valid'], valid_key=None if spec.valid_key is None else _u8(look(spec.valid_key).reshape(B, T)),
+            lengths=lengths, reset=reset, **fix)
+        for k_, v in res.items():
+            out['%s_%s' % (spec.name, k_)] = v
 
     def _eye_gate(self, d, contours, gate, reset, lengths):
         """The gate of a gated EVEStream step: one eve_eye_gate launch over what the spec has a criterion for (d: the chunk after

@@ -1182,6 +1182,71 @@ class HipKernels(object):
                                                   float(P['floor']), self._p(maps), self._p(frames), self._stream()))
         return frames
 
+    # ------------------------------------------------------------------ areas of interest
+    GAZE_AOI_KEYS = ('id', 'mask', 'visit_ms')
+
+    def gaze_aoi(self, pog, shapes, spec, state, table, trans, visits, count, dropped, frame_time=None, valid=None, valid_key=None,
+                 fixation_id=None, fixating=None, lengths=None, reset=None, flush=None):
+        """The hit tests, visits, dwell table and transitions of B streams x T frames against A areas of interest: pog float32
+        [B, T, 2]; shapes float32 [B, A, 36], or [B, T, A, 36] with one table per frame (data.aoi_shapes has the rows); spec an
+        eve_amd.AoiSpec (fps and max_gap_s are the launch's scalars); state float64 [B, 16], table float64 [B, A + 1, 8], trans int32
+        [B, A + 1, A], visits float64 [B, V, 8], count and dropped int32 [B], UPDATED IN PLACE; frame_time float64 [B, T], valid and
+        valid_key uint8 [B, T], fixation_id int32 [B, T] with fixating uint8 [B, T], lengths, reset and flush int32 [B], or None.  -> a
+        dict of GAZE_AOI_KEYS: id int32 [B, T], mask int64 [B, T], visit_ms float32 [B, T].  pog None (then every frame input is None
+        too): T = 0, a launch that only resets and flushes, -> {} (include/eve_hip.h eve_gaze_aoi)."""
+        ok = lambda t, dtype: torch.is_tensor(t) and t.dtype == dtype
+        got = lambda t: (getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ())))
+        if not ok(state, torch.float64) or state.dim() != 2 or state.shape[1] != 16 or state.shape[0] < 1:
+            raise TypeError('gaze_aoi: state must be float64 [B, 16], got %s %s' % got(state))
+        B = state.shape[0]
+        if not ok(table, torch.float64) or table.dim() != 3 or table.shape[0] != B or not 2 <= table.shape[1] <= 65 or table.shape[2] != 8:
+            raise TypeError('gaze_aoi: table must be float64 [%d, A + 1, 8] with A in 1 .. 64, got %s %s' % ((B,) + got(table)))
+        A = table.shape[1] - 1
+        if not ok(visits, torch.float64) or visits.dim() != 3 or visits.shape[0] != B or visits.shape[1] < 1 or visits.shape[2] != 8:
+            raise TypeError('gaze_aoi: visits must be float64 [%d, V, 8], got %s %s' % ((B,) + got(visits)))
+        V = visits.shape[1]
+        T = 0
+        if pog is not None:
+            if not ok(pog, torch.float32) or pog.dim() != 3 or pog.shape[0] != B or pog.shape[1] < 1 or pog.shape[2] != 2:
+                raise TypeError('gaze_aoi: pog must be float32 [%d, T, 2], got %s %s' % ((B,) + got(pog)))
+            T = pog.shape[1]
+        checks = [('trans', trans, torch.int32, (B, A + 1, A), True), ('count', count, torch.int32, (B,), True),
+                  ('dropped', dropped, torch.int32, (B,), True), ('lengths', lengths, torch.int32, (B,), False),
+                  ('reset', reset, torch.int32, (B,), False), ('flush', flush, torch.int32, (B,), False)]
+        per_frame = False
+        if T:
+            per_frame = torch.is_tensor(shapes) and shapes.dim() == 4
+            checks += [('shapes', shapes, torch.float32, (B, T, A, 36) if per_frame else (B, A, 36), True),
+                       ('frame_time', frame_time, torch.float64, (B, T), False), ('valid', valid, torch.uint8, (B, T), False),
+                       ('valid_key', valid_key, torch.uint8, (B, T), False), ('fixation_id', fixation_id, torch.int32, (B, T), False),
+                       ('fixating', fixating, torch.uint8, (B, T), False)]
+            if (fixation_id is None) != (fixating is None):
+                raise TypeError('gaze_aoi: fixation_id and fixating come together')
+        elif any(t is not None for t in (shapes, frame_time, valid, valid_key, fixation_id, fixating)):
+            raise TypeError('gaze_aoi: without pog (T = 0) there are no frame inputs')
+        tensors = [state, table, visits] + ([pog] if T else [])
+        for name, t, dtype, shape, needed in checks:
+            if (t is not None or needed) and (not ok(t, dtype) or tuple(t.shape) != shape):
+                raise TypeError('gaze_aoi: %s must be %s %s, got %s %s' % ((name, str(dtype).replace('torch.', ''), list(shape)) + got(t)))
+            if t is not None:
+                tensors.append(t)
+        if not all(t.is_contiguous() for t in tensors):
+            raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        if T and frame_time is None and spec.fps is None:
+            raise ValueError('gaze_aoi: without frame_time the spec needs fps')
+        dev = state.device
+        out = {}
+        if T:
+            out = {'id': torch.empty((B, T), dtype=torch.int32, device=dev), 'mask': torch.empty((B, T), dtype=torch.int64, device=dev),
+                   'visit_ms': torch.empty((B, T), dtype=torch.float32, device=dev)}
+        self._ck(self.lib.eve_gaze_aoi(
+            B, T, A, self._p(pog), self._p(shapes), 1 if per_frame else 0, self._p(frame_time), self._p(valid), self._p(valid_key),
+            self._p(fixation_id), self._p(fixating), self._p(lengths), self._p(reset), self._p(flush),
+            0.0 if spec.fps is None else float(spec.fps), float(spec.max_gap_s), self._p(state), self._p(table), self._p(trans), V,
+            self._p(visits), self._p(count), self._p(dropped), *([self._p(out[k_]) for k_ in self.GAZE_AOI_KEYS] if T else [None] * 3),
+            self._stream()))
+        return out
+
     # ------------------------------------------------------------------ the eye gate
     def eye_gate(self, spec, B, T, state, store, count, dropped, pose_valid=None, reproj_rms=None, inliers=None, warp=None, h=None,
                  contours=None, lengths=None, reset=None, frame_size=None, patch_size=None):

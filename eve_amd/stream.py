@@ -14,6 +14,7 @@ carried from one call to the next.
     rows = stream.fixations()                              # the completed fixations of every stream (see "Gaze events" below)
     out = stream.step(chunk, gate=eve_amd.EyeGateSpec(blink=eve_amd.BlinkSpec()))   # the mask made on the device (see "The eye gate" below)
     out = stream.step(chunk, history=eve_amd.GazeHistorySpec(fps=60))                # + the time-decayed map of where the gaze has been
+    out = stream.step(dict(chunk, aoi_shapes=regions), aoi=eve_amd.AoiSpec(num_aois=8, fps=60))   # + which region is looked at ("Areas of interest")
     st = stream.get_state(); stream.set_state(st)          # reference layout, e.g. to resume a recording
 
 For any split of a clip into chunks the concatenated outputs equal one eval pass of the whole clip from zero state
@@ -138,9 +139,33 @@ clear_gaze_history().  gaze_history(), clear_gaze_history(), get_gaze_history_st
 set_state() do not hold them.  OverlaySpec(heat_key=<name>) blends a per_frame map in place of heatmap_final.  Float64 arithmetic on a
 float32 map that is rounded after every frame, with an exp the contract owns: tests/gaze_history_ref.py states it, and the device
 equals it bit for bit, so a clip cut into chunks gives the bits of one pass.  A step without history= issues exactly the launches it
-always issued and allocates nothing.  Not offered: areas of interest and dwell-per-region tables, per-eye maps, a windowed history
-(as opposed to the decayed one), anisotropic or screen-millimetre sigmas, gradients, EVE.forward (its create_images path keeps the
-torch restatement), maps larger than 2048 per axis.
+always issued and allocates nothing.  Not offered: per-eye maps, a windowed history (as opposed to the decayed one), anisotropic or
+screen-millimetre sigmas, gradients, EVE.forward (its create_images path keeps the torch restatement), maps larger than 2048 per axis.
+
+Areas of interest.  WHAT is the person looking at, for how long, how often, in which order -- the first question a consumer asks of a
+tracker -- is a hit test per frame and a small state machine per stream, whose state has to survive chunk boundaries, ragged lengths,
+masked eyes and reset(): what an EVEStream owns.  step(chunk, aoi=eve_amd.AoiSpec(num_aois=A, ...)) adds one eve_gaze_aoi launch after
+the events and history stages and before the render hook, inside the graph.  The regions come with the chunk as aoi_shapes, float32
+[B, A, 36] or -- for stimuli that move, a video or a scrolling page -- [B, Tc, A, 36], a graph input like the rest of the chunk, so one
+graph serves every layout of the regions; data.aoi_shapes builds a table from rectangles (half open), ellipses and polygons of up to
+16 vertices (even-odd), the order of the rows being the z-order.  The point is a point of gaze of the step (PoG_px_initial / _final,
+the screen-calibrated one where a map is applied; with events= PoG_px_filtered or fixation_px, the latter with valid_key='fixating'
+the fixation-based analysis).  The result gains <name>_id int32 [B, Tc] (the lowest row that contains the point, -1 none, -2 the frame
+is not a sample), <name>_mask int64 [B, Tc] (bit a: row a contains it) and <name>_visit_ms float32 [B, Tc].  Per stream the launch
+keeps a dwell table float64 [B, A + 1, 8] (dwell_s, samples, visits, t_first_entry, t_last, fixations, t_first_fixation, 0; row A: no AOI),
+a transition matrix int32 [B, A + 1, A] (row A: the first visit since a reset; the diagonal: revisits) and a store of completed visits
+float64 [B, visit_capacity, 8] (aoi, t_enter, t_last, samples, fixations, visit_index, 0, 0; a full store drops and counts):
+aoi_table(), aoi_transitions(), aoi_visits(), aoi_visit_counts(), clear_aoi(), flush_aoi_visits().  A frame is a sample iff it was
+delivered (lengths), is valid (eye_mask, gate=, skip_invalid_pose), its valid_key holds, its point and its time are finite and the
+time is later than the last sample's; two samples more than max_gap_s apart are not connected.  With events= in the same step (or
+use_fixations=True) fixations are counted per AOI and per visit from fixation_id / fixating.  Time is the chunk's frame_time or
+frames / spec.fps, as for the events.  The float64 [B, 16] state row is carried from step to step and reset through the same device
+flags (also before a step without aoi=): reset() closes the open visit into the store and starts the row afresh, only the visit
+counter runs on; the tallies stay -- they are a readout like the fixation store, cleared by clear_aoi() -- and are tied to their spec
+as a history map is.  get_aoi_state() / set_aoi_state(); get_state() / set_state() do not hold them.  Float64, + - * / and comparisons
+only: tests/aoi_ref.py states it, and the device equals it bit for bit, so a clip cut into chunks gives the bits of one pass.  A step
+without aoi= issues exactly the launches it always issued and allocates nothing.  Not offered: label-map AOIs, minimum visit
+durations or border hysteresis, per-eye AOIs, polygon margins, AOI outlines in the overlay, gradients, EVE.forward.
 """
 from collections import namedtuple
 
@@ -155,6 +180,7 @@ _WARMUP_STREAMS = {}
 # the lazily made buffer groups (EVEStream._group): a sample store of either calibration, and what the events and the gate carry
 SampleStore = namedtuple('SampleStore', 'samples count dropped')
 StageBuffers = namedtuple('StageBuffers', 'state store count dropped')
+AoiBuffers = namedtuple('AoiBuffers', 'state table trans visits count dropped')      # what eve_gaze_aoi carries, per AoiSpec name
 
 
 def _module_key(m):
@@ -169,7 +195,7 @@ def _capacity(name, value):
 
 class EVEStream(object):
     def __init__(self, model, num_streams, use_graph=True, calibration_capacity=1024, fixation_capacity=256, blink_capacity=256,
-                 screen_calibration_capacity=1024):
+                 screen_calibration_capacity=1024, visit_capacity=256):
         if model.training:
             raise ValueError('EVEStream runs inference only: call model.eval() first')
         self.model = model
@@ -219,6 +245,10 @@ class EVEStream(object):
         # the gaze history (step(chunk, history=spec)): name -> {'spec', 'P' (the launches' scalars), 'state' float64 [B, 8], 'maps'
         # float32 [B, MH, MW], 'free'} -- the two eve_gaze_history launches read and write them inside the step (and the graph)
         self._history = {}
+        # areas of interest (step(chunk, aoi=spec)): name -> {'spec', 'buffers' (an AoiBuffers: the state row, the dwell table, the
+        # transitions, the visit store and its counters), 'free'} -- eve_gaze_aoi reads and writes them inside the step (and the graph)
+        self.visit_capacity = _capacity('visit_capacity', visit_capacity)
+        self._aoi = {}
         self._graphs = {}
         self._graphs_key = None
         self._render_tables = {}                 # OverlaySpec.key() -> its marker table, int32 [M, 4] on the device
@@ -239,12 +269,13 @@ class EVEStream(object):
         the face-landmark form's head pose; kappa and its flags; both calibrations' sample stores and counters (the warm-up steps of
         a collecting graph would otherwise append every sample three times); the gaze events' state, store and counters (a capture
         would otherwise tick the filter three times); the eye gate's ticks, baselines and blinks; every gaze history's time chain
-        and map.  A carried buffer that is not returned here corrupts its state under use_graph only, and only on the first step
-        of a chunk shape: new ones are made by _group(), or by _history_entry(), and are then here."""
+        and map; every AOI spec's state row, tallies and visit store.  A carried buffer that is not returned here corrupts its
+        state under use_graph only, and only on the first step of a chunk shape: new ones are made by _group(), by _history_entry()
+        or by _aoi_entry(), and are then here."""
         states = [t for s_ in self._eye + self._ref for t in (s_ if isinstance(s_, tuple) else (s_,))]
         groups = [t for attr in self._GROUPS for t in (getattr(self, attr) or ())]
         return states + [self._face_pose, self._calib_kappa, self._calib_ok] + groups + \
-            [t for e in self._history.values() for t in (e['state'], e['maps'])]
+            [t for e in self._history.values() for t in (e['state'], e['maps'])] + [t for e in self._aoi.values() for t in e['buffers']]
 
     @staticmethod
     def _zero_where(mask, *tensors):
@@ -680,9 +711,9 @@ class EVEStream(object):
             e = self._history_entry(plan['spec'], plan['P'])
             plan['state'], plan['maps'] = e['state'], e['maps']
 
-    def _reset_idle_stages(self, events, gate, history):
-        """A reset before a step that does not run a stage which carries state (events, gate, history: None or this step's plans): the
-        stage's state of the flagged streams still ends."""
+    def _reset_idle_stages(self, events, gate, history, aoi=None):
+        """A reset before a step that does not run a stage which carries state (events, gate, history, aoi: None or this step's plans):
+        the stage's state of the flagged streams still ends."""
         flags = self._flags[:self.num_streams]
         k = default_kernels()
         if events is None and self._events is not None:
@@ -695,6 +726,168 @@ class EVEStream(object):
                 k.gaze_history_update(e['P'], coef, clear, e['maps'])
         if gate is None and self._gate is not None:
             self._zero_where(flags != 0, self._gate.state)       # the gate's rows (its launch refuses T = 0)
+        for name, e in self._aoi.items():
+            if aoi is None or aoi['spec'].name != name:          # that spec's open visit closes and its row starts afresh: no frames
+                k.gaze_aoi(None, None, e['spec'], *e['buffers'], reset=flags)
+
+    # ------------------------------------------------------------------ areas of interest
+    def _aoi_entry(self, spec):
+        """The carried buffers of spec.name, made at the first step that names it.  The tallies are tied to their spec."""
+        from .data import aoi_buffers
+        e = self._aoi.get(spec.name)
+        if e is not None and e['spec'].key() != spec.key():
+            if not e['free']:
+                raise ValueError('step: aoi: the tallies of %r were accumulated under another spec (%r); clear_aoi(%r) first' % (
+                    spec.name, e['spec'], spec.name))
+            e = None
+            self._graphs = {}                    # (graphs captured on the old buffers)
+        if e is None:
+            e = self._aoi[spec.name] = {'spec': spec, 'free': False,
+                                        'buffers': AoiBuffers(*aoi_buffers(self.num_streams, spec.num_aois, self.visit_capacity, self.device))}
+        e['free'] = False
+        return e
+
+    def _aoi_named(self, name, where):
+        """The entry of that name; None: the only one there is."""
+        if name is None and len(self._aoi) == 1:
+            return next(iter(self._aoi.values()))
+        if name not in self._aoi:
+            raise ValueError('%s: no areas of interest named %r (known: %s)' % (where, name, ', '.join(sorted(self._aoi)) or 'none'))
+        return self._aoi[name]
+
+    def aoi_table(self, name=None):
+        """The dwell table of the AoiSpec of that name (None: the only one), float64 [B, A + 1, 8] (a copy): per stream and AOI the row
+        (dwell_s, samples, visits, t_first_entry, t_last, fixations, t_first_fixation, 0); row A is "no AOI".  dwell_s is the time between
+        connected samples inside the AOI, times in the clock of the steps (frame_time, or frames / fps since the stream's last reset)."""
+        return self._aoi_named(name, 'aoi_table')['buffers'].table.clone()
+
+    def aoi_transitions(self, name=None):
+        """The transition matrix of the AoiSpec of that name (None: the only one), int32 [B, A + 1, A] (a copy): [from][to] counts the
+        visits to `to` that followed a visit to `from`; row A is the first visit since a reset, the diagonal counts revisits (the same
+        AOI after time outside all of them, or after a gap).  Every column sums to the AOI's visits."""
+        return self._aoi_named(name, 'aoi_transitions')['buffers'].trans.clone()
+
+    def aoi_visits(self, streams=None, name=None):
+        """The completed visits of the given streams (None = all; indices or a bool mask), one numpy float64 [n, 8] array per stream in
+        index order, rows (aoi, t_enter, t_last, samples, fixations, visit_index, 0, 0) in the order they ended.  This call waits for
+        the device.  A visit still running is not in the store: flush_aoi_visits() closes it."""
+        m = self._stream_mask(streams, 'aoi_visits')
+        buffers = self._aoi_named(name, 'aoi_visits')['buffers']
+        store, count = buffers.visits.cpu().numpy(), buffers.count.cpu().numpy()
+        return [store[b, :min(max(int(count[b]), 0), self.visit_capacity)].copy() for b in np.flatnonzero(m)]
+
+    def aoi_visit_counts(self, name=None):
+        """-> (count, dropped), int32 [B] device tensors (fresh): the completed visits each stream's store holds, and those a full
+        store (visit_capacity) turned away."""
+        buffers = self._aoi_named(name, 'aoi_visit_counts')['buffers']
+        return buffers.count.clone(), buffers.dropped.clone()
+
+    def clear_aoi(self, name=None, streams=None):
+        """Zero the dwell table, the transitions, the visit store's counters and the state row of the given streams (None = all) of one
+        AoiSpec, or of all of them (name=None): those streams start afresh, a visit still running is forgotten (flush_aoi_visits()
+        first keeps it).  Cleared for all streams, a name may be taken by another spec at the next step."""
+        entries = list(self._aoi.values()) if name is None else [self._aoi_named(name, 'clear_aoi')]
+        m = None if streams is None else self._device_mask(streams, 'clear_aoi')
+        for e in entries:
+            state, table, trans, _, count, dropped = e['buffers']
+            if m is None:
+                for t in (state, table, trans, count, dropped):
+                    t.zero_()
+                e['free'] = True
+            else:
+                self._zero_where(m, state, table, trans, count, dropped)
+
+    def flush_aoi_visits(self, streams=None, name=None):
+        """Close the open visits of the given streams (None = all) on the device, as the end of a recording does: one eve_gaze_aoi launch
+        with no frames per AoiSpec (name=None: every one)."""
+        flush = self._device_mask(streams, 'flush_aoi_visits').to(torch.int32)
+        for e in (list(self._aoi.values()) if name is None else [self._aoi_named(name, 'flush_aoi_visits')]):
+            default_kernels().gaze_aoi(None, None, e['spec'], *e['buffers'], flush=flush)
+
+    def get_aoi_state(self):
+        """What the areas of interest carry: {name: {'spec': the AoiSpec, 'state': float64 [B, 16] (include/eve_hip.h eve_gaze_aoi has the
+        layout), 'table': float64 [B, A + 1, 8], 'transitions': int32 [B, A + 1, A], 'visits': float64 [B, visit_capacity, 8], 'count',
+        'dropped': int32 [B]}}, fresh tensors.  Resets not yet applied by a step are not reflected.  get_state() / set_state() do not
+        hold it."""
+        return {name: dict({'spec': e['spec']}, **{('transitions' if k_ == 'trans' else k_): t.clone() for k_, t in e['buffers']._asdict().items()})
+                for name, e in self._aoi.items()}
+
+    def set_aoi_state(self, state):
+        """Load what get_aoi_state() returned, e.g. to resume a recording.  A name that is known must come with the spec its tallies were
+        accumulated under (or be cleared first)."""
+        from .data import AoiSpec
+        B, V = self.num_streams, self.visit_capacity
+        loaded = []
+        for name, s_ in state.items():
+            spec = s_.get('spec') if isinstance(s_, dict) else None
+            if not isinstance(spec, AoiSpec) or spec.name != name:
+                raise ValueError('set_aoi_state: %r needs its AoiSpec under \'spec\'' % (name,))
+            A = spec.num_aois
+            tensors = []
+            for key, dtype, shape in (('state', torch.float64, (B, 16)), ('table', torch.float64, (B, A + 1, 8)),
+                                      ('transitions', torch.int32, (B, A + 1, A)), ('visits', torch.float64, (B, V, 8)),
+                                      ('count', torch.int32, (B,)), ('dropped', torch.int32, (B,))):
+                t = torch.as_tensor(s_[key], dtype=dtype).to(self.device)
+                if tuple(t.shape) != shape:
+                    raise ValueError('set_aoi_state: %r: %s must be %s, got %s' % (name, key, list(shape), tuple(t.shape)))
+                tensors.append(t)
+            e = self._aoi.get(name)
+            if e is not None and not e['free'] and e['spec'].key() != spec.key():
+                self._aoi_entry(spec)            # (raises: the tallies are tied to another spec -- before anything is loaded)
+            loaded.append((spec, tensors))
+        for spec, tensors in loaded:
+            for dst, src in zip(self._aoi_entry(spec)['buffers'], tensors):
+                dst.copy_(src)
+
+    def _check_aoi(self, chunk, spec, events, history, masked, B, Tc):
+        """step()'s `aoi` checked against the chunk, the model and the step's other stages -> what _predict_sequence needs beside the
+        buffers.  Every refusal is a ValueError raised before anything is launched or captured."""
+        from .data import AOI_KEYS, AOI_ROW, GAZE_EVENT_KEYS, AoiSpec
+        if not isinstance(spec, AoiSpec):
+            raise ValueError('step: aoi must be an eve_amd.AoiSpec, got %s' % type(spec).__name__)
+        A = spec.num_aois
+        taken = set(getattr(self.model, 'PREDICTION_KEYS', ())) | set(GAZE_EVENT_KEYS) | {'valid', 'eye_valid', 'pose_valid', 'rendered', 'heatmap_final'}
+        for h in history or ():
+            taken |= {h['spec'].name, h['spec'].name + '_frames'}
+        for key in AOI_KEYS:
+            if '%s_%s' % (spec.name, key) in taken or '%s_%s' % (spec.name, key) in chunk:
+                raise ValueError('step: aoi: the name %r gives %s_%s, which is a key of the chunk or of the step\'s result already' % (
+                    spec.name, spec.name, key))
+        shapes = chunk.get('aoi_shapes')
+        if shapes is None:
+            raise ValueError('step: aoi needs aoi_shapes in the chunk: float32 [%d, %d, %d] or [%d, %d, %d, %d] (data.aoi_shapes)' % (
+                B, A, AOI_ROW, B, Tc, A, AOI_ROW))
+        if torch.is_tensor(shapes) and shapes.dim() == 4:
+            self._check_chunk_tensor('aoi_shapes', shapes, (torch.float32,), (B, Tc, A, AOI_ROW))
+        else:
+            self._check_chunk_tensor('aoi_shapes', shapes, (torch.float32,), (B, A, AOI_ROW))
+        source = spec.source if spec.source is not None else 'PoG_px_' + self._output_stage()
+        if source == 'PoG_px_final' and self.model.refine_net is None:
+            raise ValueError('step: aoi tests PoG_px_final, which RefineNet produces, and the model has no RefineNet')
+        if source in ('PoG_px_filtered', 'fixation_px') and events is None:
+            raise ValueError('step: aoi tests %s, which the events stage produces: pass events= in the same step' % source)
+        if 'inv_camera_transformation' not in chunk:
+            raise ValueError('step: aoi tests %s, and the point of gaze needs the camera geometry (inv_camera_transformation) in the '
+                             'chunk' % source)
+        vk = spec.valid_key
+        if vk is not None:
+            entry = chunk.get(vk)
+            known = (vk == 'fixating' and events is not None) or (vk == 'valid' and masked)
+            if entry is None and not known:
+                raise ValueError('step: aoi: valid_key %r is neither in the chunk nor a [B, Tc] result of this step' % (vk,))
+            if entry is not None:
+                self._check_chunk_tensor('aoi: valid_key %r' % (vk,), entry, (torch.bool, torch.uint8), (B, Tc), got=False)
+        if spec.use_fixations and events is None:
+            raise ValueError('step: aoi: use_fixations=True counts the events stage\'s fixations: pass events= in the same step')
+        ft = chunk.get('frame_time')
+        if ft is None and spec.fps is None:
+            raise ValueError('step: aoi needs frame_time in the chunk (float64 [B, Tc] seconds) or a spec with fps')
+        if ft is not None:
+            self._check_chunk_tensor('frame_time', ft, (torch.float64,), (B, Tc))
+        e = self._aoi.get(spec.name)
+        if e is not None and not e['free'] and e['spec'].key() != spec.key():
+            self._aoi_entry(spec)                # (raises: the tallies are tied to another spec)
+        return {'spec': spec, 'source': source, 'use_fixations': events is not None if spec.use_fixations is None else spec.use_fixations}
 
     # ------------------------------------------------------------------ the eye gate
     def _gate_buffers(self):
@@ -915,8 +1108,9 @@ class EVEStream(object):
             self._pose_gate_host = not skip_invalid_pose
             self._pose_gate.fill_(self._pose_gate_host)              # a device value: the captured graphs read it, the host never waits
 
-    def _run(self, chunk, return_heatmaps, ragged=False, eye_mask=None, masked=False, render=None, events=None, gate=None, history=None):
-        """The one call of EVE._predict_sequence, eager or under capture.  render, events, gate, history: None or the plan of that
+    def _run(self, chunk, return_heatmaps, ragged=False, eye_mask=None, masked=False, render=None, events=None, gate=None, history=None,
+             aoi=None):
+        """The one call of EVE._predict_sequence, eager or under capture.  render, events, gate, history, aoi: None or the plan of that
         stage's check.  A stage's keyword goes along only when the stage runs, and lengths, the mask's keywords and face_state only
         on a ragged, a masked and a face-landmark step: a step without them makes the call it always made."""
         faced = face_landmarks_key(chunk) is not None
@@ -931,6 +1125,8 @@ class EVEStream(object):
             kw['render'] = self._render_hook(render, ragged, masked)
         if history is not None:
             kw['history'] = history
+        if aoi is not None:
+            kw['aoi'] = dict(aoi, **self._aoi_entry(aoi['spec'])['buffers']._asdict())
         if self._calib_apply or 'calibration_target' in chunk:       # (neither: the call an uncalibrated EVEStream always made)
             kw['calibration'] = {'kappa': self._calib_kappa, 'ok': self._calib_ok, 'apply': self._calib_apply,
                                  'store': self._store() if 'calibration_target' in chunk else None}
@@ -1085,7 +1281,7 @@ class EVEStream(object):
         return render
 
     def step(self, chunk, return_heatmaps=False, lengths=None, eye_mask=None, skip_invalid_pose=False, render=None, events=None, gate=None,
-             history=None):
+             history=None, aoi=None):
         """One chunk of every stream: chunk holds [B, Tc, ...] tensors on the model's device -- the eyes (below), {left,right}_h,
         {left,right}_o, {left,right}_R, head_R, camera_transformation, inv_camera_transformation, pixels_per_millimeter, millimeters_per_pixel, and screen_frame when the config loads screen content.  Returns the
         prediction keys of EVE(output_predictions=True) as [B, Tc, ...] tensors (heatmap_final [B, Tc, 1, H, W] on request).
@@ -1326,7 +1522,27 @@ class EVEStream(object):
         form and render combine with it, and OverlaySpec(heat_key=<name>) blends the per_frame map of that name in place of
         heatmap_final (a map with an axis above 1024, one without per_frame, and heat_key beside heat=True are ValueErrors).  The host
         does not wait.  tests/gaze_history_ref.py states the arithmetic, exact to the bit.  What is not offered: module docstring,
-        "Gaze history".  history=None issues exactly the launches the step always issued."""
+        "Gaze history".  history=None issues exactly the launches the step always issued.
+
+        aoi: None, or an eve_amd.AoiSpec -- one eve_gaze_aoi launch after the events and history stages and before the overlay, inside the
+        captured graph, tests the step's point of gaze against the chunk's aoi_shapes, float32 [B, A, 36] or [B, Tc, A, 36] (one table per
+        frame, for regions that move) on the model's device, A = spec.num_aois (data.aoi_shapes builds a table; module docstring, "Areas
+        of interest").  The result gains <name>_id int32 [B, Tc] (the lowest row that contains the point; -1 none; -2 the frame is not a
+        sample), <name>_mask int64 [B, Tc] (bit a: row a contains the point) and <name>_visit_ms float32 [B, Tc] (the time since the
+        running visit began).  spec.source: PoG_px_final with a RefineNet, else PoG_px_initial -- the corrected point where a screen-space
+        map is applied; PoG_px_filtered and fixation_px need events= in the same step.  spec.valid_key names a bool / uint8 [B, Tc] entry
+        of the chunk, or `fixating` (with events=) or `valid` (a masked step).  A frame is a sample iff it was delivered (lengths), is
+        valid (eye_mask, gate=, skip_invalid_pose), its valid_key holds, its point and time are finite and the time is later than the
+        last sample's.  Time is the chunk's frame_time, float64 [B, Tc] seconds, or frames / spec.fps counted over the delivered frames
+        since the stream's last reset (frame_time wins).  With events= (unless use_fixations=False) fixations are counted per AOI and
+        per visit.  The dwell table, the transitions and the visit store are carried on the device: aoi_table(), aoi_transitions(),
+        aoi_visits(), aoi_visit_counts(), clear_aoi(), flush_aoi_visits(), get_aoi_state() / set_aoi_state(); reset() closes the open
+        visit and keeps the tallies, which are tied to their spec (ValueError for a known name under another spec: clear_aoi first).
+        ValueErrors raised before anything is launched or captured: aoi_shapes missing or of another shape, dtype or device, a source
+        or valid_key the step does not produce, use_fixations=True without events=, neither frame_time nor fps, a name whose keys
+        collide with the chunk's or the result's.  The spec by value and aoi_shapes' shape are part of the graph's key; lengths,
+        eye_mask, gate=, events=, history=, both calibrations, every camera and screen form and render combine with it.
+        tests/aoi_ref.py states the arithmetic, exact to the bit.  aoi=None issues exactly the launches the step always issued."""
         if self.model.training:
             raise ValueError('EVEStream runs inference only: the model was switched to training mode')
         B, Tc = eye_input(chunk).shape[:2]
@@ -1347,12 +1563,16 @@ class EVEStream(object):
         more = {} if gate is None else {'gate': gate}      # the keyword goes along only then: a step without it calls what it always did
         if history is not None:
             more['history'] = history = self._check_history(chunk, history, events, masked, B, Tc)
+        if aoi is not None:
+            more['aoi'] = aoi = self._check_aoi(chunk, aoi, events, history, masked, B, Tc)
         if render is not None:
             render = self._render_plan(chunk, render, events, history)
         self._check_calibration(chunk, B, Tc)
         self._check_screen_calibration(chunk, B, Tc)
         if history is not None:
             self._history_buffers(history)
+        if aoi is not None:
+            self._aoi_entry(aoi['spec'])         # the carried buffers, made here: after every refusal, before any capture
         if ragged:
             self._upload_lengths(lengths)
         if masked and has_pose_form(chunk):
@@ -1361,7 +1581,7 @@ class EVEStream(object):
         if events is not None:
             self._events_spec = events['spec']
         if self._flags_set:
-            self._reset_idle_stages(events, gate, history)
+            self._reset_idle_stages(events, gate, history, aoi)
         with torch.no_grad():
             if self.use_graph:
                 entry = self._graph_for(chunk, bool(return_heatmaps), ragged, masked, render, events, **more)
@@ -1396,13 +1616,14 @@ class EVEStream(object):
     def _weights_key(self):
         return tuple(_module_key(m) for m in (self.model.eye_net, self.model.refine_net) if m is not None)
 
-    def _graph_key(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None):
+    def _graph_key(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None, aoi=None):
         """What a captured graph is good for: the step's mode, both YUV matrices, both surface layouts (by value), the overlay
         (render: None or a _render_plan -- its OverlaySpec by value), with a face-landmark form eye_net.face_huber_px (a launch
         argument, so baked in), the gaze events (events: None or a _check_events plan -- its GazeEventSpec by value and its source;
         frame_time's presence is a chunk key), the eye gate (gate: None or a _check_gate plan -- its EyeGateSpec by value and the frame size;
         eye_contours' presence and shape are a chunk key), the gaze history (history: None or _check_history's plans -- each GazeHistorySpec by
-        value, its source and the launches' scalars, the config's defaults resolved), whether a calibration is applied (`calibrated`; a collecting step differs by its chunk keys), whether a screen-space map is applied (likewise), and every chunk tensor's key, shape and dtype -- which of the two landmark keys among them."""
+        value, its source and the launches' scalars, the config's defaults resolved), the areas of interest (aoi: None or a _check_aoi plan -- its
+        AoiSpec by value, its source and whether fixations are counted; aoi_shapes' shape is a chunk key), whether a calibration is applied (`calibrated`; a collecting step differs by its chunk keys), whether a screen-space map is applied (likewise), and every chunk tensor's key, shape and dtype -- which of the two landmark keys among them."""
         ref = self.model.refine_net
         spec = None if render is None else render['spec'].key()
         layouts = (self.model.eye_net.camera_layout, None if ref is None else ref.screen_layout)
@@ -1414,9 +1635,10 @@ class EVEStream(object):
                 self._calib_apply, self._screen_apply) + (() if events is None else ((events['spec'].key(), events['source']),)) + \
             (() if gate is None else (('gate', gate['spec'].key(), gate['frame_size']),)) + \
             (() if history is None else (('history',) + tuple((h['spec'].key(), h['source'], tuple(sorted(h['P'].items(), key=lambda kv: kv[0])))
-                                                                for h in history),)) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
+                                                                for h in history),)) + \
+            (() if aoi is None else (('aoi', aoi['spec'].key(), aoi['source'], aoi['use_fixations']),)) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
 
-    def _graph_for(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None):
+    def _graph_for(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None, aoi=None):
         wk = self._weights_key()
         if wk != self._graphs_key:               # new weights: new packs, new graphs (a replay never reads stale packs)
             self._graphs = {}
@@ -1424,6 +1646,8 @@ class EVEStream(object):
         more = {} if gate is None else {'gate': gate}
         if history is not None:
             more['history'] = history
+        if aoi is not None:
+            more['aoi'] = aoi
         key = self._graph_key(chunk, return_heatmaps, ragged, masked, render, events, **more)
         entry = self._graphs.get(key)
         if entry is None:
@@ -1432,7 +1656,7 @@ class EVEStream(object):
             self._graphs_key = self._weights_key()
         return entry
 
-    def _capture(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None):
+    def _capture(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None, aoi=None):
         """Capture one step for this chunk shape (train.Trainer._capture's recipe): inputs copied into fixed buffers, two eager
         warm-up steps off the default stream (packs, lazily built filters, allocator) with the carried states put back
         afterwards, the kernels' scratch allocated before the capture, one stream, no side branches.  A masked graph has one more
@@ -1449,7 +1673,7 @@ class EVEStream(object):
             carried = self._carried()
             snap = [t.clone() for t in carried]
             for _ in range(2):
-                self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history)
+                self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history, aoi)
             for t, s_ in zip(carried, snap):
                 t.copy_(s_)
         torch.cuda.current_stream().wait_stream(side)
@@ -1459,7 +1683,7 @@ class EVEStream(object):
             k.prepare_graph_workspace(self.device)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            out = self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history)
+            out = self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history, aoi)
         m = self.model
         keep = (m.eye_net._packs, getattr(m.eye_net, '_stream_w', None), m.refine_net._packs if m.refine_net is not None else None)
         return {'graph': graph, 'inputs': static, 'outputs': out, 'keep': keep, 'eye_mask': eye_mask}

@@ -1367,7 +1367,7 @@ int eve_eye_gate(long long B, int T, const uint8_t* pose_valid /* may be NULL */
  * Refused without a launch: a null state, clear or map, with T > 0 a null coef, B < 1 (update: B > 65535), T < 0, a map axis outside
  * 1 .. 2048, B*T*4 past 31 bits, a screen size, max_gap_s or gain that is not a finite number > 0, fps not a finite number > 0 where
  * frame_time is NULL and T > 0, ln_decay not a finite number <= 0, alpha not a finite number < 0, floor not a finite number >= 0.
- * Not offered: areas of interest, per-eye maps, a windowed history, anisotropic sigmas, a gradient.  (Additive: ABI v10.)          */
+ * Not offered: per-eye maps, a windowed history, anisotropic sigmas, a gradient.  (Additive: ABI v10.)                            */
 int eve_gaze_history_plan(long long B, int T, const float* pog /* may be NULL */, const double* frame_time /* may be NULL */,
                           const uint8_t* valid /* may be NULL */, const uint8_t* valid_key /* may be NULL */,
                           const int* lengths /* may be NULL */, const int* reset /* may be NULL */, double fps, double ln_decay,
@@ -1375,6 +1375,59 @@ int eve_gaze_history_plan(long long B, int T, const float* pog /* may be NULL */
                           double* coef, int* clear, eve_stream_t stream);
 int eve_gaze_history_update(long long B, int T, int MH, int MW, const double* coef, const int* clear, const float* heat /* may be NULL */,
                             double alpha, double floor, float* map, float* frames /* may be NULL */, eve_stream_t stream);
+
+/* Areas of interest: which region of the screen the point of gaze is in, for how long, how often and in which order -- per frame a
+ * hit test against up to 64 shapes, and per stream a state machine that turns the sequence of hits into visits, a dwell table and a
+ * transition matrix -- for B streams x T frames, with the state carried in `state` and the tallies in `table`, `trans` and `visits`
+ * from one call to the next.  Float64, + - * / and comparisons only, every operation rounded on its own (no contraction), in the
+ * order written here; tests/aoi_ref.py restates it in numpy, and the device equals it bit for bit.  One wavefront per stream, passes
+ * of 64 frames, (frame, AOI) pairs tiled over the lanes for the hit tests; the bits do not depend on that structure.
+ *   pog [B*T][2] float (screen pixels); shapes [B][A][36] float, or with shapes_per_frame != 0 [B*T][A][36] (one table per frame:
+ *   moving regions); frame_time [B*T] double seconds or NULL (then t = ticks / fps); valid and valid_key [B*T] uint8, fixation_id
+ *   [B*T] int with fixating [B*T] uint8 (both or neither), lengths [B] int (clamped to 0 .. T), reset [B] int, flush [B] int: each may
+ *   be NULL (all frames, no fixation tallies, T frames, no reset, no flush).
+ *   state [B][16] double, table [B][A+1][8] double, trans [B][A+1][A] int, visits [B][visit_capacity][8] double, count [B] and
+ *   dropped [B] int: read and UPDATED IN PLACE.
+ * An AOI row: 0 kind (0 disabled, 1 rectangle, 2 ellipse, 3 polygon), 1 the polygon's vertex count n, 2-3 reserved (0), 4 .. the
+ * coordinates.  The point (x, y) and the coordinates are widened to double.  Rectangle (x0, y0, x1, y1): x0 <= x && x < x1 && y0 <= y &&
+ * y < y1.  Ellipse (cx, cy, rx, ry), rx > 0 && ry > 0: u = (x - cx) / rx, v = (y - cy) / ry, u*u + v*v <= 1.  Polygon (x_i, y_i), i < n, n
+ * an integer in 3 .. 16, even-odd: for i = 0 .. n - 1 and j = i == 0 ? n - 1 : i - 1, toggle iff ((y_i > y) != (y_j > y)) && x < (x_j -
+ * x_i) * (y - y_i) / (y_j - y_i) + x_i.  A row contains nothing where a coordinate it uses is not finite, for any other kind or n, and
+ * for an ellipse without rx > 0 && ry > 0.  mask has bit a set iff row a contains the point; the frame's AOI is the lowest set bit
+ * (the order of the rows is the z-order), or -1.
+ * The state row, an all-zero row being a fresh stream (AOI indices and fixation ids are held as value + 1, 0 = none): 0 ticks (the
+ * delivered frames since the last reset), 1 has_prev, 2 t_prev (the last sample's time), 3 the last sample's AOI + 1 (0: outside),
+ * 4 visit_open, 5 the open visit's AOI + 1, 6 its t_enter, 7 its t_last, 8 its samples, 9 its fixations, 10 its visit_index, 11
+ * next_visit_index (the visits opened so far), 12 last_aoi + 1 (the AOI of the visit closed last; 0: none since the reset), 13-14 the
+ * (fixation_id + 1, AOI + 1) pair counted last, 15 reserved (0).
+ * A table row: (dwell_s, samples, visits, t_first_entry, t_last, fixations, t_first_fixation, 0); row A is "no AOI".  trans[from][to]
+ * counts visits opened; row A is "first visit since reset", trans[a][a] a revisit.  A visit row: (aoi, t_enter, t_last, samples,
+ * fixations, visit_index, 0, 0).
+ * A stream with reset[b] != 0 first closes its open visit (below) and zeroes its row except entry 11; the tallies stay.  Then frames
+ * f = 0 .. lengths[b] - 1 are walked in order.  tt = frame_time[b][f], or (ticks + f) / fps.  The frame is a SAMPLE iff valid[b][f] and
+ * valid_key[b][f], x, y and tt are finite, and (has_prev == 0 or tt > t_prev).  Any other frame changes nothing: id -2, mask 0,
+ * visit_ms 0 (so do the frames from lengths[b] on).  For a sample: dt = tt - t_prev; restart = has_prev == 0 || dt > max_gap_s; a = the
+ * frame's AOI.  On restart the open visit is closed; otherwise, where one is open and a is not its AOI, it is closed.  a >= 0 and no
+ * visit open: one opens -- t_enter = tt, samples = fixations = 0, visit_index = next_visit_index++, table[a].visits += 1 (at the first,
+ * t_first_entry = tt), trans[last_aoi, or A][a] += 1; a >= 0 and the visit continues: table[a].dwell_s += dt.  Either way for a >= 0
+ * the visit's samples += 1 and t_last = tt, table[a].samples += 1, table[a].t_last = tt, visit_ms = 1000 * (tt - t_enter).  a == -1:
+ * table[A].samples += 1, and where !restart and the last sample was outside too, table[A].dwell_s += dt.  With fixation_id: where a >=
+ * 0, fixating != 0, fixation_id >= 0 and (fixation_id, a) is not the pair counted last, table[a].fixations += 1 (at the first,
+ * t_first_fixation = tt), the visit's fixations += 1 and the pair is remembered.  Finally t_prev = tt, has_prev = 1, entry 3 = a + 1.
+ * Closing: visit_open = 0, last_aoi = the visit's AOI, and its row goes to visits[b][count[b]] and count[b] grows; with count[b] ==
+ * visit_capacity it is dropped and dropped[b] grows.  After the frames ticks += lengths[b], and a stream with flush[b] != 0 closes its
+ * open visit.  T = 0 is a call that only resets and flushes (the frame pointers may then be NULL).
+ * Outputs per frame: id [B*T] int, mask [B*T] int64, visit_ms [B*T] float (rounded from double once).  Kernel name gaze_aoi_kernel.
+ * Refused without a launch: a null carried buffer, B < 1, T < 0, A outside 1 .. 64, visit_capacity < 1, with T > 0 a null frame input or
+ * output, fixation_id without fixating or the reverse, index products past 31 bits, max_gap_s not a finite number > 0, fps not a
+ * finite number > 0 where frame_time is NULL and T > 0.  Not offered: label-map AOIs, minimum visit durations or border hysteresis,
+ * per-eye AOIs, polygon margins, a gradient.  (Additive: ABI v10.)                                                                  */
+int eve_gaze_aoi(long long B, int T, int A, const float* pog, const float* shapes, int shapes_per_frame,
+                 const double* frame_time /* may be NULL */, const uint8_t* valid /* may be NULL */, const uint8_t* valid_key /* may be NULL */,
+                 const int* fixation_id /* may be NULL */, const uint8_t* fixating /* may be NULL */, const int* lengths /* may be NULL */,
+                 const int* reset /* may be NULL */, const int* flush /* may be NULL */, double fps, double max_gap_s, double* state,
+                 double* table, int* trans, int visit_capacity, double* visits, int* count, int* dropped, int* id, long long* mask,
+                 float* visit_ms, eve_stream_t stream);
 
 #ifdef __cplusplus
 }
