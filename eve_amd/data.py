@@ -1294,6 +1294,137 @@ def aoi_buffers(S, A, visit_capacity, device):
             z((S,), torch.int32), z((S,), torch.int32))
 
 
+PUPIL_KEYS = ('mm', 'raw_mm', 'velocity', 'change_mm', 'change_pct', 'valid', 'eye_used', 'eye_reason', 'event')      # as <name>_<key>
+PUPIL_STATE = 32                                 # doubles per stream of eve_pupil_track's state row
+PUPIL_TABLE = 24                                 # ... and of its table
+
+
+class PupilSpec(object):
+    """What EVEStream.step(chunk, pupil=spec) adds to the step (eve_pupil_track): EyeNet's two pupil sizes become one validated,
+    binocularly fused, low-passed, light- and baseline-corrected trace per stream, with a table of tallies and a store of dilation /
+    constriction episodes.
+      name              the prefix of the result keys <name>_mm, _raw_mm, _velocity, _change_mm, _change_pct, _valid, _eye_used,
+                        _eye_reason, _event, and the name of the tallies
+      fps               for chunks without frame_time (float64 [B, Tc] seconds, which wins when both are there)
+      min_mm, max_mm    the accepted range of a size (1.5 .. 9 mm: the range filter of Kret & Sjak-Shie 2019, "Preprocessing pupil
+                        size data", Behav. Res. Methods 51)
+      max_speed_mm_s    an eye whose size moves faster than this against its last accepted one is rejected -- their dilation-speed
+                        criterion with a fixed bound in place of the non-causal MAD (10 mm/s: above the 5 .. 7 mm/s peak constriction
+                        velocity of the light reflex, Bremner 2012, "Pupillometric evaluation of the dynamics of the pupillary
+                        response to a brief light stimulus", IOVS 53)
+      max_gap_s         samples further apart than this are not connected (the filter restarts, an episode ends), and a rejected eye
+                        is re-admitted untested after it (0.25 s: the longest gap Kret & Sjak-Shie bridge)
+      offset_rate       in (0, 1]: how fast the running left - right offset follows, per binocular sample (0.05)
+      cutoff_hz         the one-pole low pass of the fused size (4 Hz: Jackson & Sirois 2009, Kret & Sjak-Shie 2019)
+      light_tau_s       the time constant of the luminance's own low pass, standing for the lag of the light reflex (0.5 s: Ellis
+                        1981, "The pupillary light reflex in normal subjects", Br. J. Ophthalmol. 65)
+      baseline_tau_s    None: no follower; else the time constant of the slow baseline used where the chunk has no pupil_baseline marks
+      dilate_mm_s, constrict_mm_s    the velocity above / below which a sample dilates / constricts (0.15 and 0.3 mm/s)
+      min_amplitude_mm  episodes that move the filtered size by less are not stored (0.1 mm: the lower end of task-evoked responses,
+                        Beatty 1982, "Task-evoked pupillary responses", Psychol. Bull. 91)
+    Instances compare and hash by value: the spec is part of a captured graph's key, and the tallies are tied to their spec.  Not
+    offered: luminance computed from the screen capture (the covariate comes with the chunk as pupil_luminance), non-causal blink
+    padding and interpolation across gaps, foreshortening correction, per-eye filtered traces, wavelet indices (IPA / LHIPA),
+    per-fixation or per-AOI pupil means, gradients, EVE.forward, the overlay."""
+
+    def __init__(self, name='pupil', fps=None, min_mm=1.5, max_mm=9.0, max_speed_mm_s=10.0, max_gap_s=0.25, offset_rate=0.05, cutoff_hz=4.0,
+                 light_tau_s=0.5, baseline_tau_s=None, dilate_mm_s=0.15, constrict_mm_s=0.3, min_amplitude_mm=0.1):
+        number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and np.isfinite(v)
+        if not isinstance(name, str) or not name:
+            raise ValueError('PupilSpec: name must be a non-empty string, got %r' % (name,))
+        if fps is not None and (not number(fps) or not fps > 0):
+            raise ValueError('PupilSpec: fps must be a finite number > 0, got %r' % (fps,))
+        for field, v in (('min_mm', min_mm), ('max_mm', max_mm), ('max_speed_mm_s', max_speed_mm_s), ('max_gap_s', max_gap_s),
+                         ('cutoff_hz', cutoff_hz), ('light_tau_s', light_tau_s), ('dilate_mm_s', dilate_mm_s), ('constrict_mm_s', constrict_mm_s)):
+            if not number(v) or not v > 0:
+                raise ValueError('PupilSpec: %s must be a finite number > 0, got %r' % (field, v))
+        if not min_mm < max_mm:
+            raise ValueError('PupilSpec: min_mm must be below max_mm, got %r and %r' % (min_mm, max_mm))
+        if not number(offset_rate) or not 0 < offset_rate <= 1:
+            raise ValueError('PupilSpec: offset_rate must lie in (0, 1], got %r' % (offset_rate,))
+        if baseline_tau_s is not None and (not number(baseline_tau_s) or not baseline_tau_s > 0):
+            raise ValueError('PupilSpec: baseline_tau_s must be None or a finite number > 0, got %r' % (baseline_tau_s,))
+        if not number(min_amplitude_mm) or not min_amplitude_mm >= 0:
+            raise ValueError('PupilSpec: min_amplitude_mm must be a finite number >= 0, got %r' % (min_amplitude_mm,))
+        self.name, self.fps = name, None if fps is None else float(fps)
+        self.min_mm, self.max_mm, self.max_speed_mm_s, self.max_gap_s = float(min_mm), float(max_mm), float(max_speed_mm_s), float(max_gap_s)
+        self.offset_rate, self.cutoff_hz, self.light_tau_s = float(offset_rate), float(cutoff_hz), float(light_tau_s)
+        self.baseline_tau_s = None if baseline_tau_s is None else float(baseline_tau_s)
+        self.dilate_mm_s, self.constrict_mm_s, self.min_amplitude_mm = float(dilate_mm_s), float(constrict_mm_s), float(min_amplitude_mm)
+
+    def key(self):
+        return (self.name, self.fps, self.min_mm, self.max_mm, self.max_speed_mm_s, self.max_gap_s, self.offset_rate, self.cutoff_hz,
+                self.light_tau_s, self.baseline_tau_s, self.dilate_mm_s, self.constrict_mm_s, self.min_amplitude_mm)
+
+    def __eq__(self, other):
+        return isinstance(other, PupilSpec) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return ('PupilSpec(name=%r, fps=%r, min_mm=%r, max_mm=%r, max_speed_mm_s=%r, max_gap_s=%r, offset_rate=%r, cutoff_hz=%r, light_tau_s=%r, '
+                'baseline_tau_s=%r, dilate_mm_s=%r, constrict_mm_s=%r, min_amplitude_mm=%r)') % self.key()
+
+
+def pupil_buffers(S, capacity, device):
+    """-> (state float64 [S, 32], table float64 [S, 24], light float64 [S, 4], store float64 [S, capacity, 8], count and dropped int32
+    [S]) of S streams that have seen nothing: what eve_pupil_track carries (include/eve_hip.h has the rows)."""
+    z = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=device)
+    return (z((S, PUPIL_STATE), torch.float64), z((S, PUPIL_TABLE), torch.float64), z((S, 4), torch.float64), z((S, capacity, 8), torch.float64),
+            z((S,), torch.int32), z((S,), torch.int32))
+
+
+def pupil_track(spec, left, right, eye_valid=None, frame_time=None, lengths=None, luminance=None, baseline_mark=None, light=None,
+                episode_capacity=256):
+    """The pupillometry of S recorded streams, stand-alone and from fresh state: spec a PupilSpec (its name prefixes the per-frame
+    keys); left, right float32 [S, T] pupil sizes in mm (EyeNet's <side>_pupil_size); eye_valid None or bool / uint8 [S, T, 2];
+    frame_time None (then spec.fps) or float64 [S, T] seconds; lengths None or int32 [S] on the device; luminance None or float32
+    [S, T]; baseline_mark None or bool / uint8 [S, T]; light None or float64 [S, 4] rows (has_gain, gain, ref, 0).  One eve_pupil_track
+    launch, which also closes the episodes still open at the clip's end.  -> <name>_mm, _raw_mm, _velocity, _change_mm, _change_pct
+    float32 [S, T] (NaN where the frame is no sample), <name>_valid uint8 [S, T], <name>_eye_used and _eye_reason uint8 [S, T, 2] (bit 1
+    withheld, 2 not finite, 4 range, 8 speed), <name>_event uint8 [S, T] (1 dilating, 2 constricting), plus table float64 [S, 24],
+    episodes float64 [S, episode_capacity, 8] (rows (phase, t_start, t_end, d_start, d_end, peak |velocity|, samples, Lf at the start)),
+    episode_count and episode_dropped int32 [S], light and state float64 [S, 4] and [S, 32]; the host does not wait.  Not offered: see
+    PupilSpec."""
+    if not isinstance(spec, PupilSpec):
+        raise ValueError('pupil_track: spec must be an eve_amd.PupilSpec, got %s' % type(spec).__name__)
+    for name, t in (('left', left), ('right', right)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2 or t.numel() == 0:
+            raise TypeError('pupil_track: %s must be float32 [S, T], got %s %s' % (name, getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ()))))
+    S, T = left.shape
+    if tuple(right.shape) != (S, T):
+        raise TypeError('pupil_track: right must be float32 [%d, %d] like left, got %s' % (S, T, tuple(right.shape)))
+    if frame_time is None and spec.fps is None:
+        raise ValueError('pupil_track: frame_time, or a spec with fps')
+    if frame_time is not None and (not torch.is_tensor(frame_time) or frame_time.dtype != torch.float64 or tuple(frame_time.shape) != (S, T)):
+        raise TypeError('pupil_track: frame_time must be float64 [%d, %d] seconds' % (S, T))
+    if eye_valid is not None:
+        eye_valid = _bool_rows(eye_valid, (S, T, 2), 'pupil_track: eye_valid')
+    if baseline_mark is not None:
+        baseline_mark = _bool_rows(baseline_mark, (S, T), 'pupil_track: baseline_mark')
+    if luminance is not None and (not torch.is_tensor(luminance) or luminance.dtype != torch.float32 or tuple(luminance.shape) != (S, T)):
+        raise TypeError('pupil_track: luminance must be float32 [%d, %d]' % (S, T))
+    if lengths is not None and (not torch.is_tensor(lengths) or lengths.dtype != torch.int32 or tuple(lengths.shape) != (S,)):
+        raise TypeError('pupil_track: lengths must be an int32 [%d] tensor' % S)
+    if isinstance(episode_capacity, bool) or not isinstance(episode_capacity, (int, np.integer)) or episode_capacity < 1:
+        raise ValueError('pupil_track: episode_capacity must be an integer >= 1, got %r' % (episode_capacity,))
+    dev = left.device
+    state, table, light_, store, count, dropped = pupil_buffers(S, int(episode_capacity), dev)
+    if light is not None:
+        if not torch.is_tensor(light) or light.dtype != torch.float64 or tuple(light.shape) != (S, 4):
+            raise TypeError('pupil_track: light must be float64 [%d, 4] rows (has_gain, gain, ref, 0)' % S)
+        light_.copy_(light)
+    out = default_kernels().pupil_track(torch.stack([left, right]), spec, state, table, light_, store, count, dropped, eye_valid=eye_valid,
+                                        frame_time=None if frame_time is None else frame_time.contiguous(),
+                                        lengths=None if lengths is None else lengths.contiguous(),
+                                        luminance=None if luminance is None else luminance.contiguous(), baseline_mark=baseline_mark,
+                                        flush=torch.ones((S,), dtype=torch.int32, device=dev))
+    out = {'%s_%s' % (spec.name, k_): v for k_, v in out.items()}
+    out.update(table=table, episodes=store, episode_count=count, episode_dropped=dropped, light=light_, state=state)
+    return out
+
+
 EYE_GATE_KEYS = ('eye_gate_reason', 'eye_openness', 'blink')
 EYE_CONTOURS_KEY = 'eye_contours'
 

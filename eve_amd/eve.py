@@ -366,7 +366,7 @@ class EVE(nn.Module):
 
     def _predict_sequence(self, d, eye_states, refine_states, reset=None, return_heatmaps=False, lengths=None, masked=False,
                           eye_mask=None, pose_gate=None, face_state=None, render=None, calibration=None, events=None, gate=None,
-                          screen_calibration=None, history=None, aoi=None):
+                          screen_calibration=None, history=None, aoi=None, pupil=None):
         """The prediction part of forward() for one chunk of an EVEStream: eval only, no labels, no losses.  d: the chunk's
         inputs [B, Tc, ...] (not modified; camera_frame may be any one key of eye_net.EYE_FRAME_KEYS or camera_surface, and the screen any one
         key of refine_net.SCREEN_FRAME_KEYS or screen_surface; the eyes as patches, as camera_frame + {left,right}_eye_warp, or as camera_frame +
@@ -427,7 +427,12 @@ class EVE(nn.Module):
         [B, V, 8], 'count', 'dropped': int32 [B]}: one eve_gaze_aoi launch, after the history stage and before the render hook, over the
         step's own source point and d['aoi_shapes'] ([B, A, 36] or [B, Tc, A, 36]), with frame_time from d when it is there, the step's
         lengths, `valid` (masked) and reset flags, and with use_fixations the events stage's fixation_id / fixating; the result gains
-        <name>_id, <name>_mask and <name>_visit_ms.  None issues no launch."""
+        <name>_id, <name>_mask and <name>_visit_ms.  None issues no launch.
+        pupil: None, or EVEStream's pupillometry stage {'spec': a data.PupilSpec, 'state': float64 [B, 32], 'table': float64 [B, 24],
+        'light': float64 [B, 4], 'store': float64 [B, capacity, 8], 'count', 'dropped': int32 [B]}: one eve_pupil_track launch, after the
+        AOI stage and before the render hook, over the step's own <side>_pupil_size, the mask plan's eye_valid (a masked or gated
+        step), frame_time, pupil_luminance and pupil_baseline from d where they are there, the step's lengths and reset flags; the
+        result gains <name>_<key> for data.PUPIL_KEYS.  None issues no launch."""
         assert not self.training, 'EVE._predict_sequence is eval-only'
         B = eye_input(d).shape[0]
         posed, faced = has_pose_form(d), face_landmarks_key(d) is not None
@@ -502,6 +507,8 @@ class EVE(nn.Module):
             self._gaze_history(d, inter, out, history, lengths_b, reset_b, plan)
         if aoi is not None:
             self._gaze_aoi(d, inter, out, aoi, lengths_b, reset_b, plan)
+        if pupil is not None:
+            self._pupil_track(d, inter, out, pupil, lengths_b, reset_b, plan)
         if render is not None:
             render(d, inter, out)
         return out
@@ -554,6 +561,19 @@ class EVE(nn.Module):
             aoi['count'], aoi['dropped'], frame_time=d['frame_time'].contiguous() if 'frame_time' in d else None,
             valid=None if plan is None else plan['valid'], valid_key=None if spec.valid_key is None else _u8(look(spec.valid_key).reshape(B, T)),
             lengths=lengths, reset=reset, **fix)
+        for k_, v in res.items():
+            out['%s_%s' % (spec.name, k_)] = v
+
+    def _pupil_track(self, d, inter, out, pupil, lengths, reset, plan):
+        """The pupillometry stage of an EVEStream step: one eve_pupil_track launch on the carried buffers."""
+        B, T = eye_input(d).shape[:2]
+        spec = pupil['spec']
+        size = torch.stack([_f32(inter['left_pupil_size'], B, T), _f32(inter['right_pupil_size'], B, T)])
+        res = default_kernels().pupil_track(
+            size, spec, pupil['state'], pupil['table'], pupil['light'], pupil['store'], pupil['count'], pupil['dropped'],
+            eye_valid=None if plan is None else plan['eye_valid'], frame_time=d['frame_time'].contiguous() if 'frame_time' in d else None,
+            lengths=lengths, reset=reset, luminance=d['pupil_luminance'].contiguous() if 'pupil_luminance' in d else None,
+            baseline_mark=_u8(d.get('pupil_baseline')))
         for k_, v in res.items():
             out['%s_%s' % (spec.name, k_)] = v
 

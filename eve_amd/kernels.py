@@ -1247,6 +1247,65 @@ class HipKernels(object):
             self._stream()))
         return out
 
+    # ------------------------------------------------------------------ pupillometry
+    PUPIL_KEYS = ('mm', 'raw_mm', 'velocity', 'change_mm', 'change_pct', 'valid', 'eye_used', 'eye_reason', 'event')
+
+    def pupil_track(self, size, spec, state, table, light, store, count, dropped, eye_valid=None, frame_time=None, lengths=None, reset=None,
+                    flush=None, luminance=None, baseline_mark=None):
+        """The validated, fused, filtered and baseline-corrected pupil trace, its tallies and its dilation / constriction episodes for B
+        streams x T frames: size float32 [2, B, T] (left, right; mm); spec an eve_amd.PupilSpec (its numbers are the launch's scalars);
+        state float64 [B, 32], table float64 [B, 24], store float64 [B, capacity, 8], count and dropped int32 [B], UPDATED IN PLACE;
+        light float64 [B, 4] (has_gain, gain, ref, 0), read; eye_valid uint8 [B, T, 2], frame_time float64 [B, T], luminance float32
+        [B, T], baseline_mark uint8 [B, T], lengths, reset and flush int32 [B], or None.  -> a dict of PUPIL_KEYS: mm, raw_mm, velocity,
+        change_mm, change_pct float32 [B, T], valid and event uint8 [B, T], eye_used and eye_reason uint8 [B, T, 2].  size None (then
+        every frame input is None too): T = 0, a launch that only resets and flushes, -> {} (include/eve_hip.h eve_pupil_track)."""
+        ok = lambda t, dtype: torch.is_tensor(t) and t.dtype == dtype
+        got = lambda t: (getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ())))
+        if not ok(state, torch.float64) or state.dim() != 2 or state.shape[1] != 32 or state.shape[0] < 1:
+            raise TypeError('pupil_track: state must be float64 [B, 32], got %s %s' % got(state))
+        B = state.shape[0]
+        if not ok(store, torch.float64) or store.dim() != 3 or store.shape[0] != B or store.shape[1] < 1 or store.shape[2] != 8:
+            raise TypeError('pupil_track: store must be float64 [%d, capacity, 8], got %s %s' % ((B,) + got(store)))
+        V = store.shape[1]
+        T = 0
+        if size is not None:
+            if not ok(size, torch.float32) or size.dim() != 3 or size.shape[0] != 2 or size.shape[1] != B or size.shape[2] < 1:
+                raise TypeError('pupil_track: size must be float32 [2, %d, T], got %s %s' % ((B,) + got(size)))
+            T = size.shape[2]
+        checks = [('table', table, torch.float64, (B, 24), True), ('light', light, torch.float64, (B, 4), True),
+                  ('count', count, torch.int32, (B,), True), ('dropped', dropped, torch.int32, (B,), True),
+                  ('lengths', lengths, torch.int32, (B,), False), ('reset', reset, torch.int32, (B,), False),
+                  ('flush', flush, torch.int32, (B,), False)]
+        if T:
+            checks += [('eye_valid', eye_valid, torch.uint8, (B, T, 2), False), ('frame_time', frame_time, torch.float64, (B, T), False),
+                       ('luminance', luminance, torch.float32, (B, T), False), ('baseline_mark', baseline_mark, torch.uint8, (B, T), False)]
+        elif any(t is not None for t in (eye_valid, frame_time, luminance, baseline_mark)):
+            raise TypeError('pupil_track: without size (T = 0) there are no frame inputs')
+        tensors = [state, store] + ([size] if T else [])
+        for name, t, dtype, shape, needed in checks:
+            if (t is not None or needed) and (not ok(t, dtype) or tuple(t.shape) != shape):
+                raise TypeError('pupil_track: %s must be %s %s, got %s %s' % ((name, str(dtype).replace('torch.', ''), list(shape)) + got(t)))
+            if t is not None:
+                tensors.append(t)
+        if not all(t.is_contiguous() for t in tensors):
+            raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        if T and frame_time is None and spec.fps is None:
+            raise ValueError('pupil_track: without frame_time the spec needs fps')
+        dev = state.device
+        out = {}
+        if T:
+            out = {k_: torch.empty((B, T), dtype=torch.float32, device=dev) for k_ in self.PUPIL_KEYS[:5]}
+            out.update(valid=torch.empty((B, T), dtype=torch.uint8, device=dev), eye_used=torch.empty((B, T, 2), dtype=torch.uint8, device=dev),
+                       eye_reason=torch.empty((B, T, 2), dtype=torch.uint8, device=dev), event=torch.empty((B, T), dtype=torch.uint8, device=dev))
+        self._ck(self.lib.eve_pupil_track(
+            B, T, self._p(size), self._p(eye_valid), self._p(frame_time), self._p(lengths), self._p(reset), self._p(flush), self._p(luminance),
+            self._p(baseline_mark), 0.0 if spec.fps is None else float(spec.fps), float(spec.min_mm), float(spec.max_mm),
+            float(spec.max_speed_mm_s), float(spec.max_gap_s), float(spec.offset_rate), float(spec.cutoff_hz), float(spec.light_tau_s),
+            0.0 if spec.baseline_tau_s is None else float(spec.baseline_tau_s), float(spec.dilate_mm_s), float(spec.constrict_mm_s),
+            float(spec.min_amplitude_mm), self._p(state), self._p(table), self._p(light), V, self._p(store), self._p(count), self._p(dropped),
+            *([self._p(out[k_]) for k_ in self.PUPIL_KEYS] if T else [None] * 9), self._stream()))
+        return out
+
     # ------------------------------------------------------------------ the eye gate
     def eye_gate(self, spec, B, T, state, store, count, dropped, pose_valid=None, reproj_rms=None, inliers=None, warp=None, h=None,
                  contours=None, lengths=None, reset=None, frame_size=None, patch_size=None):

@@ -15,6 +15,7 @@ carried from one call to the next.
     out = stream.step(chunk, gate=eve_amd.EyeGateSpec(blink=eve_amd.BlinkSpec()))   # the mask made on the device (see "The eye gate" below)
     out = stream.step(chunk, history=eve_amd.GazeHistorySpec(fps=60))                # + the time-decayed map of where the gaze has been
     out = stream.step(dict(chunk, aoi_shapes=regions), aoi=eve_amd.AoiSpec(num_aois=8, fps=60))   # + which region is looked at ("Areas of interest")
+    out = stream.step(chunk, pupil=eve_amd.PupilSpec(fps=60))          # + the validated, fused, baseline-corrected pupil size ("Pupillometry")
     st = stream.get_state(); stream.set_state(st)          # reference layout, e.g. to resume a recording
 
 For any split of a clip into chunks the concatenated outputs equal one eval pass of the whole clip from zero state
@@ -166,6 +167,31 @@ as a history map is.  get_aoi_state() / set_aoi_state(); get_state() / set_state
 only: tests/aoi_ref.py states it, and the device equals it bit for bit, so a clip cut into chunks gives the bits of one pass.  A step
 without aoi= issues exactly the launches it always issued and allocates nothing.  Not offered: label-map AOIs, minimum visit
 durations or border hysteresis, per-eye AOIs, polygon margins, AOI outlines in the overlay, gradients, EVE.forward.
+
+Pupillometry.  EyeNet's second head, the pupil size per eye, leaves the step as the network wrote it: unspecified at unusable eyes,
+noisy, unfused, without a baseline.  step(chunk, pupil=eve_amd.PupilSpec(...)) adds one eve_pupil_track launch after the AOI stage and
+before the render hook, inside the graph, over the step's own <side>_pupil_size and -- on a masked or gated step -- the mask plan's
+eye_valid, so what the mask, the gate, a blink or its hold-off withheld is withheld here too.  Per frame and eye a size is accepted
+iff it was delivered, is finite, lies in min_mm .. max_mm and does not move faster than max_speed_mm_s against that eye's last
+accepted size (the dilation-speed criterion of Kret & Sjak-Shie 2019 with a fixed bound; after max_gap_s the eye is re-admitted
+untested).  The accepted eyes are fused through a running left - right offset, so the trace does not step when one eye drops out;
+the fused size is low-passed (cutoff_hz), optionally corrected for light -- the chunk's pupil_luminance, float32 [B, Tc], is low-passed
+with light_tau_s and, once a gain is set (set_pupil_light_response / fit_pupil_light_response), gain * (Lf - ref) is taken off --
+and referred to a baseline: the running mean of the samples the chunk marks in pupil_baseline, bool / uint8 [B, Tc] (a new run of
+marks starts a new baseline), or without marks a slow follower (baseline_tau_s).  The result gains <name>_mm, _raw_mm, _velocity,
+_change_mm, _change_pct float32 [B, Tc] (NaN where the frame is no sample), _valid and _event uint8 [B, Tc] (1 dilating, 2
+constricting) and _eye_used, _eye_reason uint8 [B, Tc, 2] (1 withheld, 2 not finite, 4 range, 8 speed).  Per stream the launch keeps a
+table float64 [B, 24] (pupil_table() names the entries), and a store of dilation / constriction episodes float64 [B,
+episode_capacity, 8] (phase, t_start, t_end, d_start, d_end, peak |velocity|, samples, Lf at the start; a full store drops and
+counts): pupil_episodes(), pupil_episode_counts(), clear_pupil(), flush_pupil_episodes().  Both chunk keys are graph inputs, their
+presence part of the graph's key.  reset() closes the open episode and starts the float64 [B, 32] state row afresh (only the episode
+counter runs on), also before a step without pupil=; the table and the light response stay, tied to their spec.  get_pupil_state() /
+set_pupil_state(); get_state() / set_state() do not hold them.  Float64, + - * /, abs and comparisons only: tests/pupil_ref.py states
+it, and the device equals it bit for bit, so a clip cut into chunks gives the bits of one pass.  A step without pupil= issues exactly
+the launches it always issued and allocates nothing.  Not offered: luminance computed from the screen capture on the device (the
+covariate comes with the chunk, e.g. from an ambient sensor or the caller's own mean), non-causal blink padding and interpolation
+across gaps, foreshortening correction, per-eye filtered traces, wavelet indices (IPA / LHIPA), per-fixation or per-AOI pupil means,
+the overlay, gradients, EVE.forward.
 """
 from collections import namedtuple
 
@@ -181,6 +207,7 @@ _WARMUP_STREAMS = {}
 SampleStore = namedtuple('SampleStore', 'samples count dropped')
 StageBuffers = namedtuple('StageBuffers', 'state store count dropped')
 AoiBuffers = namedtuple('AoiBuffers', 'state table trans visits count dropped')      # what eve_gaze_aoi carries, per AoiSpec name
+PupilBuffers = namedtuple('PupilBuffers', 'state table light store count dropped')    # what eve_pupil_track carries, per PupilSpec name
 
 
 def _module_key(m):
@@ -195,7 +222,7 @@ def _capacity(name, value):
 
 class EVEStream(object):
     def __init__(self, model, num_streams, use_graph=True, calibration_capacity=1024, fixation_capacity=256, blink_capacity=256,
-                 screen_calibration_capacity=1024, visit_capacity=256):
+                 screen_calibration_capacity=1024, visit_capacity=256, episode_capacity=256):
         if model.training:
             raise ValueError('EVEStream runs inference only: call model.eval() first')
         self.model = model
@@ -249,6 +276,10 @@ class EVEStream(object):
         # transitions, the visit store and its counters), 'free'} -- eve_gaze_aoi reads and writes them inside the step (and the graph)
         self.visit_capacity = _capacity('visit_capacity', visit_capacity)
         self._aoi = {}
+        # pupillometry (step(chunk, pupil=spec)): name -> {'spec', 'buffers' (a PupilBuffers: the state row, the table, the light
+        # response, the episode store and its counters), 'free'} -- eve_pupil_track reads and writes them inside the step (and the graph)
+        self.episode_capacity = _capacity('episode_capacity', episode_capacity)
+        self._pupil = {}
         self._graphs = {}
         self._graphs_key = None
         self._render_tables = {}                 # OverlaySpec.key() -> its marker table, int32 [M, 4] on the device
@@ -269,13 +300,15 @@ class EVEStream(object):
         the face-landmark form's head pose; kappa and its flags; both calibrations' sample stores and counters (the warm-up steps of
         a collecting graph would otherwise append every sample three times); the gaze events' state, store and counters (a capture
         would otherwise tick the filter three times); the eye gate's ticks, baselines and blinks; every gaze history's time chain
-        and map; every AOI spec's state row, tallies and visit store.  A carried buffer that is not returned here corrupts its
-        state under use_graph only, and only on the first step of a chunk shape: new ones are made by _group(), by _history_entry()
-        or by _aoi_entry(), and are then here."""
+        and map; every AOI spec's state row, tallies and visit store; every pupil spec's state row, table, light response and
+        episode store.  A carried buffer that is not returned here corrupts its state under use_graph only, and only on the first
+        step of a chunk shape: new ones are made by _group(), by _history_entry(), by _aoi_entry() or by _pupil_entry(), and are
+        then here."""
         states = [t for s_ in self._eye + self._ref for t in (s_ if isinstance(s_, tuple) else (s_,))]
         groups = [t for attr in self._GROUPS for t in (getattr(self, attr) or ())]
         return states + [self._face_pose, self._calib_kappa, self._calib_ok] + groups + \
-            [t for e in self._history.values() for t in (e['state'], e['maps'])] + [t for e in self._aoi.values() for t in e['buffers']]
+            [t for e in self._history.values() for t in (e['state'], e['maps'])] + [t for e in self._aoi.values() for t in e['buffers']] + \
+            [t for e in self._pupil.values() for t in e['buffers']]
 
     @staticmethod
     def _zero_where(mask, *tensors):
@@ -711,9 +744,9 @@ class EVEStream(object):
             e = self._history_entry(plan['spec'], plan['P'])
             plan['state'], plan['maps'] = e['state'], e['maps']
 
-    def _reset_idle_stages(self, events, gate, history, aoi=None):
-        """A reset before a step that does not run a stage which carries state (events, gate, history, aoi: None or this step's plans):
-        the stage's state of the flagged streams still ends."""
+    def _reset_idle_stages(self, events, gate, history, aoi=None, pupil=None):
+        """A reset before a step that does not run a stage which carries state (events, gate, history, aoi, pupil: None or this
+        step's plans): the stage's state of the flagged streams still ends."""
         flags = self._flags[:self.num_streams]
         k = default_kernels()
         if events is None and self._events is not None:
@@ -729,6 +762,187 @@ class EVEStream(object):
         for name, e in self._aoi.items():
             if aoi is None or aoi['spec'].name != name:          # that spec's open visit closes and its row starts afresh: no frames
                 k.gaze_aoi(None, None, e['spec'], *e['buffers'], reset=flags)
+        for name, e in self._pupil.items():
+            if pupil is None or pupil['spec'].name != name:      # that spec's open episode closes and its row starts afresh: no frames
+                k.pupil_track(None, e['spec'], *e['buffers'], reset=flags)
+
+    # ------------------------------------------------------------------ pupillometry
+    def _pupil_entry(self, spec):
+        """The carried buffers of spec.name, made at the first step that names it.  The tallies are tied to their spec."""
+        from .data import pupil_buffers
+        e = self._pupil.get(spec.name)
+        if e is not None and e['spec'].key() != spec.key():
+            if not e['free']:
+                raise ValueError('step: pupil: the tallies of %r were accumulated under another spec (%r); clear_pupil(%r) first' % (
+                    spec.name, e['spec'], spec.name))
+            e = None
+            self._graphs = {}                    # (graphs captured on the old buffers)
+        if e is None:
+            e = self._pupil[spec.name] = {'spec': spec, 'free': False,
+                                          'buffers': PupilBuffers(*pupil_buffers(self.num_streams, self.episode_capacity, self.device))}
+        e['free'] = False
+        return e
+
+    def _pupil_named(self, name, where):
+        """The entry of that name; None: the only one there is."""
+        if name is None and len(self._pupil) == 1:
+            return next(iter(self._pupil.values()))
+        if name not in self._pupil:
+            raise ValueError('%s: no pupillometry named %r (known: %s)' % (where, name, ', '.join(sorted(self._pupil)) or 'none'))
+        return self._pupil[name]
+
+    def pupil_table(self, name=None):
+        """The table of the PupilSpec of that name (None: the only one), float64 [B, 24] (a copy): 0 covered_s (the time between
+        connected samples) and 1 lost_s (the part of it that bridges frames which were no samples); 2 binocular, 3 left-only and 4
+        right-only samples (the samples are their sum); 5-7 the left eye's rejects for not finite / range / speed, 8-10 the right eye's;
+        11 d0 (the first sample's size), 12 sum(mm - d0), 13 sum((mm - d0)^2), 14 min and 15 max of mm; 16 n, 17 x0, 18 y0, 19 sum(x - x0),
+        20 sum(y - y0), 21 sum((x - x0)^2), 22 sum((x - x0)(y - y0)), 23 sum((y - y0)^2) of the pairs x = the low-passed luminance, y = the
+        filtered size before the light correction.  Times are in the clock of the steps."""
+        return self._pupil_named(name, 'pupil_table')['buffers'].table.clone()
+
+    def pupil_episodes(self, streams=None, name=None):
+        """The completed dilation / constriction episodes of the given streams (None = all; indices or a bool mask), one numpy float64
+        [n, 8] array per stream in index order, rows (phase +1 / -1, t_start, t_end, d_start, d_end, peak |velocity| in mm/s, samples,
+        the low-passed luminance at the start or 0) in the order they ended.  This call waits for the device.  An episode still
+        running is not in the store: flush_pupil_episodes() closes it."""
+        m = self._stream_mask(streams, 'pupil_episodes')
+        buffers = self._pupil_named(name, 'pupil_episodes')['buffers']
+        store, count = buffers.store.cpu().numpy(), buffers.count.cpu().numpy()
+        return [store[b, :min(max(int(count[b]), 0), self.episode_capacity)].copy() for b in np.flatnonzero(m)]
+
+    def pupil_episode_counts(self, name=None):
+        """-> (count, dropped), int32 [B] device tensors (fresh): the episodes each stream's store holds, and those a full store
+        (episode_capacity) turned away."""
+        buffers = self._pupil_named(name, 'pupil_episode_counts')['buffers']
+        return buffers.count.clone(), buffers.dropped.clone()
+
+    def clear_pupil(self, name=None, streams=None):
+        """Zero the table, the episode store's counters and the state row of the given streams (None = all) of one PupilSpec, or of all
+        of them (name=None): those streams start afresh, an episode still running is forgotten (flush_pupil_episodes() first keeps
+        it).  The light response stays (clear_pupil_light_response()).  Cleared for all streams, a name may be taken by another spec
+        at the next step."""
+        entries = list(self._pupil.values()) if name is None else [self._pupil_named(name, 'clear_pupil')]
+        m = None if streams is None else self._device_mask(streams, 'clear_pupil')
+        for e in entries:
+            state, table, _, _, count, dropped = e['buffers']
+            if m is None:
+                for t in (state, table, count, dropped):
+                    t.zero_()
+                e['free'] = True
+            else:
+                self._zero_where(m, state, table, count, dropped)
+
+    def flush_pupil_episodes(self, streams=None, name=None):
+        """Close the open episodes of the given streams (None = all) on the device, as the end of a recording does: one eve_pupil_track
+        launch with no frames per PupilSpec (name=None: every one)."""
+        flush = self._device_mask(streams, 'flush_pupil_episodes').to(torch.int32)
+        for e in (list(self._pupil.values()) if name is None else [self._pupil_named(name, 'flush_pupil_episodes')]):
+            default_kernels().pupil_track(None, e['spec'], *e['buffers'], flush=flush)
+
+    def set_pupil_light_response(self, gain, ref, streams=None, name=None):
+        """Set the light response of the given streams (None = all): from the next step on mm = filtered size - gain * (Lf - ref), Lf the
+        low-passed pupil_luminance.  gain (mm per unit of luminance) and ref: numbers, or [B] (one per stream of the EVEStream)."""
+        e = self._pupil_named(name, 'set_pupil_light_response')
+        m = self._device_mask(streams, 'set_pupil_light_response')
+        B = self.num_streams
+        row = torch.zeros((B, 4), dtype=torch.float64)
+        for col, v in ((1, gain), (2, ref)):
+            v = torch.as_tensor(v, dtype=torch.float64).detach().cpu()
+            if v.dim() > 1 or (v.dim() == 1 and v.shape[0] != B) or not bool(torch.isfinite(v).all()):
+                raise ValueError('set_pupil_light_response: gain and ref must be finite numbers or [%d], got %r' % (B, tuple(v.shape)))
+            row[:, col] = v
+        row[:, 0] = 1.0
+        light = e['buffers'].light
+        light.copy_(torch.where(m[:, None], self._pinned(row).to(self.device, non_blocking=True), light))
+
+    def get_pupil_light_response(self, name=None):
+        """-> float64 [B, 4] (a copy): rows (has_gain, gain, ref, 0)."""
+        return self._pupil_named(name, 'get_pupil_light_response')['buffers'].light.clone()
+
+    def clear_pupil_light_response(self, streams=None, name=None):
+        """The given streams (None = all) go back to the uncorrected trace."""
+        e = self._pupil_named(name, 'clear_pupil_light_response')
+        self._zero_where(self._device_mask(streams, 'clear_pupil_light_response'), e['buffers'].light)
+
+    def fit_pupil_light_response(self, streams=None, min_samples=30, name=None):
+        """Fit the light response of the given streams (None = all) from the table's regression sums of (low-passed luminance, filtered
+        size): gain = Sxy / Sxx, ref = x0 + Sx / n (the mean luminance, so the correction leaves the mean size alone).  A stream with
+        fewer than min_samples pairs, or whose luminance did not move (Sxx == 0), keeps what it had.  A few float64 operations on
+        the device; the host does not wait.  Collect with the response cleared: the sums are of the size BEFORE the correction."""
+        if isinstance(min_samples, bool) or not isinstance(min_samples, (int, np.integer)) or min_samples < 2:
+            raise ValueError('fit_pupil_light_response: min_samples must be an integer >= 2, got %r' % (min_samples,))
+        e = self._pupil_named(name, 'fit_pupil_light_response')
+        m = self._device_mask(streams, 'fit_pupil_light_response')
+        table, light = e['buffers'].table, e['buffers'].light
+        n, x0, sx, sxx, sxy = table[:, 16], table[:, 17], table[:, 19], table[:, 21], table[:, 22]
+        ok = m & (n >= float(min_samples)) & (sxx > 0)
+        one = torch.ones_like(n)
+        fitted = torch.stack([one, sxy / torch.where(ok, sxx, one), x0 + sx / torch.where(ok, n, one), torch.zeros_like(n)], dim=1)
+        light.copy_(torch.where(ok[:, None], fitted, light))
+
+    def get_pupil_state(self):
+        """What the pupillometry carries: {name: {'spec': the PupilSpec, 'state': float64 [B, 32] (include/eve_hip.h eve_pupil_track has
+        the layout), 'table': float64 [B, 24], 'light': float64 [B, 4], 'episodes': float64 [B, episode_capacity, 8], 'count', 'dropped':
+        int32 [B]}}, fresh tensors.  Resets not yet applied by a step are not reflected.  get_state() / set_state() do not hold it."""
+        return {name: dict({'spec': e['spec']}, **{('episodes' if k_ == 'store' else k_): t.clone() for k_, t in e['buffers']._asdict().items()})
+                for name, e in self._pupil.items()}
+
+    def set_pupil_state(self, state):
+        """Load what get_pupil_state() returned, e.g. to resume a recording.  A name that is known must come with the spec its tallies
+        were accumulated under (or be cleared first)."""
+        from .data import PUPIL_STATE, PUPIL_TABLE, PupilSpec
+        B, V = self.num_streams, self.episode_capacity
+        loaded = []
+        for name, s_ in state.items():
+            spec = s_.get('spec') if isinstance(s_, dict) else None
+            if not isinstance(spec, PupilSpec) or spec.name != name:
+                raise ValueError('set_pupil_state: %r needs its PupilSpec under \'spec\'' % (name,))
+            tensors = []
+            for key, dtype, shape in (('state', torch.float64, (B, PUPIL_STATE)), ('table', torch.float64, (B, PUPIL_TABLE)),
+                                      ('light', torch.float64, (B, 4)), ('episodes', torch.float64, (B, V, 8)),
+                                      ('count', torch.int32, (B,)), ('dropped', torch.int32, (B,))):
+                t = torch.as_tensor(s_[key], dtype=dtype).to(self.device)
+                if tuple(t.shape) != shape:
+                    raise ValueError('set_pupil_state: %r: %s must be %s, got %s' % (name, key, list(shape), tuple(t.shape)))
+                tensors.append(t)
+            e = self._pupil.get(name)
+            if e is not None and not e['free'] and e['spec'].key() != spec.key():
+                self._pupil_entry(spec)          # (raises: the tallies are tied to another spec -- before anything is loaded)
+            loaded.append((spec, tensors))
+        for spec, tensors in loaded:
+            for dst, src in zip(self._pupil_entry(spec)['buffers'], tensors):
+                dst.copy_(src)
+
+    def _check_pupil(self, chunk, spec, events, history, aoi, gate, B, Tc):
+        """step()'s `pupil` checked against the chunk and the step's other stages -> what _predict_sequence needs beside the buffers.
+        Every refusal is a ValueError raised before anything is launched or captured."""
+        from .data import AOI_KEYS, EYE_GATE_KEYS, GAZE_EVENT_KEYS, PUPIL_KEYS, PupilSpec
+        if not isinstance(spec, PupilSpec):
+            raise ValueError('step: pupil must be an eve_amd.PupilSpec, got %s' % type(spec).__name__)
+        taken = set(getattr(self.model, 'PREDICTION_KEYS', ())) | set(GAZE_EVENT_KEYS) | {'valid', 'eye_valid', 'pose_valid', 'rendered', 'heatmap_final'}
+        if gate is not None:
+            taken |= set(EYE_GATE_KEYS)
+        for h in history or ():
+            taken |= {h['spec'].name, h['spec'].name + '_frames'}
+        if aoi is not None:
+            taken |= {'%s_%s' % (aoi['spec'].name, k_) for k_ in AOI_KEYS}
+        for key in PUPIL_KEYS:
+            if '%s_%s' % (spec.name, key) in taken or '%s_%s' % (spec.name, key) in chunk:
+                raise ValueError('step: pupil: the name %r gives %s_%s, which is a key of the chunk or of the step\'s result already' % (
+                    spec.name, spec.name, key))
+        if 'pupil_luminance' in chunk:
+            self._check_chunk_tensor('pupil_luminance', chunk['pupil_luminance'], (torch.float32,), (B, Tc))
+        if 'pupil_baseline' in chunk:
+            self._check_chunk_tensor('pupil_baseline', chunk['pupil_baseline'], (torch.bool, torch.uint8), (B, Tc))
+        ft = chunk.get('frame_time')
+        if ft is None and spec.fps is None:
+            raise ValueError('step: pupil needs frame_time in the chunk (float64 [B, Tc] seconds) or a spec with fps')
+        if ft is not None:
+            self._check_chunk_tensor('frame_time', ft, (torch.float64,), (B, Tc))
+        e = self._pupil.get(spec.name)
+        if e is not None and not e['free'] and e['spec'].key() != spec.key():
+            self._pupil_entry(spec)              # (raises: the tallies are tied to another spec)
+        return {'spec': spec}
 
     # ------------------------------------------------------------------ areas of interest
     def _aoi_entry(self, spec):
@@ -1109,9 +1323,9 @@ class EVEStream(object):
             self._pose_gate.fill_(self._pose_gate_host)              # a device value: the captured graphs read it, the host never waits
 
     def _run(self, chunk, return_heatmaps, ragged=False, eye_mask=None, masked=False, render=None, events=None, gate=None, history=None,
-             aoi=None):
-        """The one call of EVE._predict_sequence, eager or under capture.  render, events, gate, history, aoi: None or the plan of that
-        stage's check.  A stage's keyword goes along only when the stage runs, and lengths, the mask's keywords and face_state only
+             aoi=None, pupil=None):
+        """The one call of EVE._predict_sequence, eager or under capture.  render, events, gate, history, aoi, pupil: None or the plan of
+        that stage's check.  A stage's keyword goes along only when the stage runs, and lengths, the mask's keywords and face_state only
         on a ragged, a masked and a face-landmark step: a step without them makes the call it always made."""
         faced = face_landmarks_key(chunk) is not None
         kw = {'reset': self._flags, 'return_heatmaps': return_heatmaps}
@@ -1127,6 +1341,8 @@ class EVEStream(object):
             kw['history'] = history
         if aoi is not None:
             kw['aoi'] = dict(aoi, **self._aoi_entry(aoi['spec'])['buffers']._asdict())
+        if pupil is not None:
+            kw['pupil'] = dict(pupil, **self._pupil_entry(pupil['spec'])['buffers']._asdict())
         if self._calib_apply or 'calibration_target' in chunk:       # (neither: the call an uncalibrated EVEStream always made)
             kw['calibration'] = {'kappa': self._calib_kappa, 'ok': self._calib_ok, 'apply': self._calib_apply,
                                  'store': self._store() if 'calibration_target' in chunk else None}
@@ -1281,7 +1497,7 @@ class EVEStream(object):
         return render
 
     def step(self, chunk, return_heatmaps=False, lengths=None, eye_mask=None, skip_invalid_pose=False, render=None, events=None, gate=None,
-             history=None, aoi=None):
+             history=None, aoi=None, pupil=None):
         """One chunk of every stream: chunk holds [B, Tc, ...] tensors on the model's device -- the eyes (below), {left,right}_h,
         {left,right}_o, {left,right}_R, head_R, camera_transformation, inv_camera_transformation, pixels_per_millimeter, millimeters_per_pixel, and screen_frame when the config loads screen content.  Returns the
         prediction keys of EVE(output_predictions=True) as [B, Tc, ...] tensors (heatmap_final [B, Tc, 1, H, W] on request).
@@ -1542,7 +1758,26 @@ class EVEStream(object):
         or valid_key the step does not produce, use_fixations=True without events=, neither frame_time nor fps, a name whose keys
         collide with the chunk's or the result's.  The spec by value and aoi_shapes' shape are part of the graph's key; lengths,
         eye_mask, gate=, events=, history=, both calibrations, every camera and screen form and render combine with it.
-        tests/aoi_ref.py states the arithmetic, exact to the bit.  aoi=None issues exactly the launches the step always issued."""
+        tests/aoi_ref.py states the arithmetic, exact to the bit.  aoi=None issues exactly the launches the step always issued.
+
+        pupil: None, or an eve_amd.PupilSpec -- one eve_pupil_track launch after the AOI stage and before the overlay, inside the
+        captured graph, turns the step's own left_pupil_size / right_pupil_size into one validated, fused, low-passed, light- and
+        baseline-corrected trace per stream (module docstring, "Pupillometry").  On a masked or gated step the eyes the mask plan
+        withheld (eye_mask, gate=, a blink and its hold-off, skip_invalid_pose) are withheld here; their sizes are never read into
+        any arithmetic.  Optional chunk keys, graph inputs like aoi_shapes: pupil_luminance float32 [B, Tc] (the light covariate, e.g.
+        an ambient sensor's reading or the caller's own screen mean) and pupil_baseline bool / uint8 [B, Tc] (the frames that form the
+        baseline; a new run of marks starts a new one).  The result gains <name>_mm, _raw_mm, _velocity (mm/s), _change_mm, _change_pct
+        float32 [B, Tc] -- NaN where the frame is no sample, and the two changes NaN while there is no baseline -- <name>_valid and
+        <name>_event (0 none, 1 dilating, 2 constricting) uint8 [B, Tc], <name>_eye_used and <name>_eye_reason (1 withheld, 2 not
+        finite, 4 range, 8 speed) uint8 [B, Tc, 2].  Time is the chunk's frame_time or frames / spec.fps, as for the AOI stage.  The
+        table, the light response and the episode store are carried on the device: pupil_table(), pupil_episodes(),
+        pupil_episode_counts(), clear_pupil(), flush_pupil_episodes(), set_ / get_ / clear_ / fit_pupil_light_response(),
+        get_pupil_state() / set_pupil_state(); reset() closes the open episode and keeps the table, which is tied to its spec
+        (ValueError for a known name under another spec: clear_pupil first).  ValueErrors raised before anything is launched or
+        captured: a pupil that is no PupilSpec, a name whose keys collide with the chunk's or the result's, pupil_luminance or
+        pupil_baseline of another shape, dtype or device, neither frame_time nor fps.  The spec by value and the presence of the two
+        chunk keys are part of the graph's key; every other mode of the step combines with it.  tests/pupil_ref.py states the
+        arithmetic, exact to the bit.  pupil=None issues exactly the launches the step always issued."""
         if self.model.training:
             raise ValueError('EVEStream runs inference only: the model was switched to training mode')
         B, Tc = eye_input(chunk).shape[:2]
@@ -1565,6 +1800,8 @@ class EVEStream(object):
             more['history'] = history = self._check_history(chunk, history, events, masked, B, Tc)
         if aoi is not None:
             more['aoi'] = aoi = self._check_aoi(chunk, aoi, events, history, masked, B, Tc)
+        if pupil is not None:
+            more['pupil'] = pupil = self._check_pupil(chunk, pupil, events, history, aoi, gate, B, Tc)
         if render is not None:
             render = self._render_plan(chunk, render, events, history)
         self._check_calibration(chunk, B, Tc)
@@ -1573,6 +1810,8 @@ class EVEStream(object):
             self._history_buffers(history)
         if aoi is not None:
             self._aoi_entry(aoi['spec'])         # the carried buffers, made here: after every refusal, before any capture
+        if pupil is not None:
+            self._pupil_entry(pupil['spec'])     # likewise
         if ragged:
             self._upload_lengths(lengths)
         if masked and has_pose_form(chunk):
@@ -1581,7 +1820,7 @@ class EVEStream(object):
         if events is not None:
             self._events_spec = events['spec']
         if self._flags_set:
-            self._reset_idle_stages(events, gate, history, aoi)
+            self._reset_idle_stages(events, gate, history, aoi, pupil)
         with torch.no_grad():
             if self.use_graph:
                 entry = self._graph_for(chunk, bool(return_heatmaps), ragged, masked, render, events, **more)
@@ -1616,14 +1855,16 @@ class EVEStream(object):
     def _weights_key(self):
         return tuple(_module_key(m) for m in (self.model.eye_net, self.model.refine_net) if m is not None)
 
-    def _graph_key(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None, aoi=None):
+    def _graph_key(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None, aoi=None,
+                   pupil=None):
         """What a captured graph is good for: the step's mode, both YUV matrices, both surface layouts (by value), the overlay
         (render: None or a _render_plan -- its OverlaySpec by value), with a face-landmark form eye_net.face_huber_px (a launch
         argument, so baked in), the gaze events (events: None or a _check_events plan -- its GazeEventSpec by value and its source;
         frame_time's presence is a chunk key), the eye gate (gate: None or a _check_gate plan -- its EyeGateSpec by value and the frame size;
         eye_contours' presence and shape are a chunk key), the gaze history (history: None or _check_history's plans -- each GazeHistorySpec by
         value, its source and the launches' scalars, the config's defaults resolved), the areas of interest (aoi: None or a _check_aoi plan -- its
-        AoiSpec by value, its source and whether fixations are counted; aoi_shapes' shape is a chunk key), whether a calibration is applied (`calibrated`; a collecting step differs by its chunk keys), whether a screen-space map is applied (likewise), and every chunk tensor's key, shape and dtype -- which of the two landmark keys among them."""
+        AoiSpec by value, its source and whether fixations are counted; aoi_shapes' shape is a chunk key), the pupillometry (pupil: None or a
+        _check_pupil plan -- its PupilSpec by value; pupil_luminance's and pupil_baseline's presence are chunk keys), whether a calibration is applied (`calibrated`; a collecting step differs by its chunk keys), whether a screen-space map is applied (likewise), and every chunk tensor's key, shape and dtype -- which of the two landmark keys among them."""
         ref = self.model.refine_net
         spec = None if render is None else render['spec'].key()
         layouts = (self.model.eye_net.camera_layout, None if ref is None else ref.screen_layout)
@@ -1636,9 +1877,11 @@ class EVEStream(object):
             (() if gate is None else (('gate', gate['spec'].key(), gate['frame_size']),)) + \
             (() if history is None else (('history',) + tuple((h['spec'].key(), h['source'], tuple(sorted(h['P'].items(), key=lambda kv: kv[0])))
                                                                 for h in history),)) + \
-            (() if aoi is None else (('aoi', aoi['spec'].key(), aoi['source'], aoi['use_fixations']),)) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
+            (() if aoi is None else (('aoi', aoi['spec'].key(), aoi['source'], aoi['use_fixations']),)) + \
+            (() if pupil is None else (('pupil', pupil['spec'].key()),)) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
 
-    def _graph_for(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None, aoi=None):
+    def _graph_for(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None, aoi=None,
+                   pupil=None):
         wk = self._weights_key()
         if wk != self._graphs_key:               # new weights: new packs, new graphs (a replay never reads stale packs)
             self._graphs = {}
@@ -1648,6 +1891,8 @@ class EVEStream(object):
             more['history'] = history
         if aoi is not None:
             more['aoi'] = aoi
+        if pupil is not None:
+            more['pupil'] = pupil
         key = self._graph_key(chunk, return_heatmaps, ragged, masked, render, events, **more)
         entry = self._graphs.get(key)
         if entry is None:
@@ -1656,7 +1901,8 @@ class EVEStream(object):
             self._graphs_key = self._weights_key()
         return entry
 
-    def _capture(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None, aoi=None):
+    def _capture(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None, aoi=None,
+                 pupil=None):
         """Capture one step for this chunk shape (train.Trainer._capture's recipe): inputs copied into fixed buffers, two eager
         warm-up steps off the default stream (packs, lazily built filters, allocator) with the carried states put back
         afterwards, the kernels' scratch allocated before the capture, one stream, no side branches.  A masked graph has one more
@@ -1673,7 +1919,7 @@ class EVEStream(object):
             carried = self._carried()
             snap = [t.clone() for t in carried]
             for _ in range(2):
-                self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history, aoi)
+                self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history, aoi, pupil)
             for t, s_ in zip(carried, snap):
                 t.copy_(s_)
         torch.cuda.current_stream().wait_stream(side)
@@ -1683,7 +1929,7 @@ class EVEStream(object):
             k.prepare_graph_workspace(self.device)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            out = self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history, aoi)
+            out = self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history, aoi, pupil)
         m = self.model
         keep = (m.eye_net._packs, getattr(m.eye_net, '_stream_w', None), m.refine_net._packs if m.refine_net is not None else None)
         return {'graph': graph, 'inputs': static, 'outputs': out, 'keep': keep, 'eye_mask': eye_mask}

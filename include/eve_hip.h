@@ -1429,6 +1429,81 @@ int eve_gaze_aoi(long long B, int T, int A, const float* pog, const float* shape
                  double* table, int* trans, int visit_capacity, double* visits, int* count, int* dropped, int* id, long long* mask,
                  float* visit_ms, eve_stream_t stream);
 
+/* Pupillometry: EyeNet's two pupil sizes per frame become one validated, binocularly fused, low-passed, light- and baseline-corrected
+ * trace per stream, with a table of tallies and a store of dilation / constriction episodes -- for B streams x T frames, with the
+ * state carried in `state`, the tallies in `table`, the light response in `light` and the episodes in `store` from one call to the
+ * next.  Float64, + - * /, fabs and comparisons only, every operation rounded on its own (no contraction), in the order written
+ * here; tests/pupil_ref.py restates it in numpy, and the device equals it bit for bit.  One wavefront per stream, passes of 64
+ * frames loaded across the lanes, the walk in one lane; the bits do not depend on that structure.
+ *   size [2][B*T] float (left, right; mm as EyeNet gives them), widened to double; eye_valid [B*T][2] uint8 or NULL (every eye
+ *   delivered); frame_time [B*T] double seconds or NULL (then t = (ticks + f) / fps); lengths [B] int (clamped to 0 .. T), reset [B]
+ *   int, flush [B] int, luminance [B*T] float, baseline_mark [B*T] uint8: each may be NULL (T frames, no reset, no flush, no light
+ *   covariate, no marks).
+ *   state [B][32] double, table [B][24] double, light [B][4] double, store [B][capacity][8] double, count [B] and dropped [B] int:
+ *   read and UPDATED IN PLACE (light is only read).
+ * The state row, an all-zero row being a fresh stream: 0 ticks (the delivered frames since the last reset), 1 has_prev, 2 t_prev (the
+ * last sample's time), 3 df_prev (its filtered size), 4 idx_prev (its frame index ticks + f), 5-7 left (has, t, size) and 8-10 right
+ * (has, t, size): each eye's last accepted size, 11 has_off, 12 off, 13 has_lum, 14 t_lum, 15 Lf (the low-passed luminance), 16
+ * has_base, 17 base, 18 the marked samples of the current run, 19 the run's first dc, 20 its sum(dc - first), 21 prev_mark (the mark
+ * of the last timed frame), 22 episode_open, 23 its phase, 24 t_start, 25 t_end, 26 d_start, 27 d_end, 28 peak |velocity|, 29 samples,
+ * 30 Lf at its start or 0, 31 episodes (those closed with enough amplitude since the stream began: stored or dropped).
+ * The table row: 0 covered_s, 1 lost_s, 2 binocular, 3 left-only and 4 right-only samples (the samples are their sum), 5-7 the left
+ * eye's rejects for not finite / range / speed, 8-10 the right eye's, 11 d0 (the first sample's dc), 12 sum(dc - d0), 13 sum((dc -
+ * d0)^2), 14 min dc, 15 max dc, 16 n, 17 x0, 18 y0, 19 sum(x - x0), 20 sum(y - y0), 21 sum((x - x0)^2), 22 sum((x - x0)(y - y0)), 23
+ * sum((y - y0)^2) of the pairs x = Lf, y = df.  (A withheld eye is the withholding stage's tally, not counted here.)  light:
+ * (has_gain, gain, ref, 0).  An episode row: (phase +1 dilation / -1 constriction, t_start, t_end, d_start, d_end, peak |velocity|,
+ * samples, Lf at the start or 0).
+ * A stream with reset[b] != 0 first closes its open episode (below) and zeroes its row except entry 31; table and light stay.  Then
+ * frames f = 0 .. lengths[b] - 1 are walked in order.
+ * 1 Time.  t = frame_time[b][f], or (ticks + f) / fps.  The frame is TIMED iff t is finite and (has_prev == 0 or t > t_prev); any
+ *   other frame, and the frames from lengths[b] on, change nothing and give the outputs of "no sample" with eye_reason 0.
+ * 2 Luminance (luminance != NULL, the value finite, and has_lum == 0 or t > t_lum): dtl = t - t_lum; has_lum == 0 or dtl > max_gap_s:
+ *   Lf = lum; else al = 1 / (1 + light_tau_s / dtl), Lf = al * lum + (1 - al) * Lf.  Then has_lum = 1, t_lum = t.
+ * 3 Acceptance, per eye e, the first test that fails gives the reason: eye_valid[f][e] == 0: 1 (withheld; its size is not read into
+ *   any arithmetic); size not finite: 2; !(min_mm <= size && size <= max_mm): 4; where has_e and t - t_e <= max_gap_s:
+ *   !(fabs(size - size_e) / (t - t_e) <= max_speed_mm_s): 8 (the dilation-speed criterion of Kret & Sjak-Shie 2019 with a fixed
+ *   bound; an eye rejected for longer than max_gap_s is re-admitted untested).  Reasons 2, 4 and 8 count in the table.
+ * 4 Fusion.  Both accepted: off = has_off ? off + offset_rate * ((l - r) - off) : l - r, has_off = 1, d = 0.5 * (l + r).  Left only: d
+ *   = has_off ? l - 0.5 * off : l.  Right only: d = has_off ? r + 0.5 * off : r.  Neither: no SAMPLE -- mm, raw_mm, velocity and both
+ *   changes NaN, valid, eye_used and event 0 -- and nothing moves but what 2, 3 and prev_mark (7) moved.
+ * 5 Filter.  dt = t - t_prev; restart = has_prev == 0 || dt > max_gap_s.  Restart: df = d, velocity = NaN, the open episode closes.
+ *   Else a = 1 / (1 + (1 / (6.283185307179586 * cutoff_hz)) / dt), df = a * d + (1 - a) * df_prev, velocity = (df - df_prev) / dt
+ *   (mm/s), covered_s += dt, and where (ticks + f) - idx_prev != 1 (frames that were no samples lie between) also lost_s += dt.
+ * 6 Light (luminance != NULL and has_lum): at n == 0, x0 = Lf and y0 = df; dx = Lf - x0, dy = df - y0; n += 1 and the five sums grow
+ *   by dx, dy, dx * dx, dx * dy, dy * dy; where has_gain != 0, dc = df - gain * (Lf - ref).  Otherwise dc = df, its bits untouched.
+ * 7 Baseline.  With baseline_mark: a marked sample with prev_mark == 0 starts a run (first = dc, count = sum = 0); every marked sample:
+ *   count += 1, sum += dc - first, base = first + sum / count, has_base = 1.  Without marks and with baseline_tau_s > 0: has_base == 0
+ *   or has_prev == 0: base = dc; else base = base + (1 / (1 + baseline_tau_s / dt)) * (dc - base); has_base = 1.  With either and
+ *   has_base: change_mm = dc - base, change_pct = 100 * (dc - base) / base; else both NaN.  Every TIMED frame, sample or not, ends
+ *   with prev_mark = its mark (only with baseline_mark != NULL).
+ * 8 Episodes.  phase = velocity > dilate_mm_s ? +1 : velocity < -constrict_mm_s ? -1 : 0.  An open episode of another phase closes.
+ *   phase != 0 and none open: one opens at the PREVIOUS sample -- t_start = t_prev, d_start = df_prev, peak = samples = 0, Lf as in
+ *   6 or 0.  Then t_end = t, d_end = df, peak = max(peak, fabs(velocity)), samples += 1.  Closing: episode_open = 0, and where
+ *   fabs(d_end - d_start) >= min_amplitude_mm, entry 31 += 1 and the row goes to store[b][count[b]] and count[b] grows; with count[b]
+ *   == capacity it is dropped and dropped[b] grows.
+ * 9 Table and hand-over.  The sample's count (binocular / left / right) += 1; at the table's first sample d0 = min = max = dc; sum
+ *   += dc - d0, sum2 += (dc - d0)^2, min and max follow.  Each accepted eye's (has, t, size) = (1, t, its size); has_prev = 1, t_prev =
+ *   t, df_prev = df, idx_prev = ticks + f.
+ * After the frames ticks += lengths[b], and a stream with flush[b] != 0 closes its open episode.  T = 0 is a call that only resets
+ * and flushes (the frame pointers may then be NULL).
+ * Outputs per frame, each float rounded from double once: mm (= dc), raw_mm (= d), velocity, change_mm, change_pct float [B*T]; valid
+ * uint8 [B*T]; eye_used and eye_reason uint8 [B*T][2]; event uint8 [B*T] (0 none, 1 dilating, 2 constricting).  Kernel name
+ * pupil_track_kernel.
+ * Refused without a launch: a null carried buffer, B < 1, T < 0, capacity < 1, with T > 0 a null size or output, index products past
+ * 31 bits, min_mm or max_mm not a finite number > 0 or min_mm >= max_mm, offset_rate outside (0, 1], max_speed_mm_s, max_gap_s,
+ * cutoff_hz, light_tau_s, dilate_mm_s or constrict_mm_s not a finite number > 0, baseline_tau_s or min_amplitude_mm not a finite
+ * number >= 0, fps not a finite number > 0 where frame_time is NULL and T > 0.  Not offered: luminance computed from the screen
+ * capture (the covariate comes from the caller), non-causal blink padding and interpolation across gaps, foreshortening correction,
+ * per-eye filtered traces, wavelet indices (IPA / LHIPA), per-fixation or per-AOI pupil means, a gradient.  (Additive: ABI v10.)   */
+int eve_pupil_track(long long B, int T, const float* size, const uint8_t* eye_valid /* may be NULL */,
+                    const double* frame_time /* may be NULL */, const int* lengths /* may be NULL */, const int* reset /* may be NULL */,
+                    const int* flush /* may be NULL */, const float* luminance /* may be NULL */,
+                    const uint8_t* baseline_mark /* may be NULL */, double fps, double min_mm, double max_mm, double max_speed_mm_s,
+                    double max_gap_s, double offset_rate, double cutoff_hz, double light_tau_s, double baseline_tau_s, double dilate_mm_s,
+                    double constrict_mm_s, double min_amplitude_mm, double* state, double* table, double* light, int capacity, double* store,
+                    int* count, int* dropped, float* mm, float* raw_mm, float* velocity, float* change_mm, float* change_pct, uint8_t* valid,
+                    uint8_t* eye_used, uint8_t* eye_reason, uint8_t* event, eve_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
