@@ -216,6 +216,7 @@ SIGNATURES = {
     'eve_gaze_history_update': [L, I, I, I, P, P, P, ctypes.c_double, ctypes.c_double, P, P, P],
     'eve_gaze_aoi': [L, I, I, P, P, I] + [P] * 8 + [ctypes.c_double] * 2 + [P, P, P, I, P, P, P] + [P] * 4,
     'eve_pupil_track': [L, I] + [P] * 8 + [ctypes.c_double] * 12 + [P, P, P, I, P, P, P] + [P] * 9 + [P],
+    'eve_screen_luminance': [POINTER(Surface), I, L, I, P, P, I, I, I, P, I, POINTER(c_int), P, F, F, P, P, P, P, P],
 }
 EXPORTS = sorted(list(SIGNATURES) + ['eve_abi_version', 'eve_last_error', 'eve_last_kernel'])
 

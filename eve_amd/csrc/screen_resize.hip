@@ -134,25 +134,7 @@ __host__ __device__ constexpr size_t yuv_frame_bytes(const int IH, const int IW)
     return FMT == EVE_PIX_YUYV ? (size_t)IH * IW * 2 : (size_t)IH * IW / 2 * 3;
 }
 
-constexpr int YR_COLS = 8;               // luma columns a thread of the vector form owns (8 or 16)
-
-// W = 1, 2 or 4 dwords from p (aligned to 4 * W bytes) as one load
-template <int W>
-__device__ __forceinline__ void load_words(const uint8_t* __restrict__ p, uint32_t (&w)[W]) {
-    static_assert(W == 1 || W == 2 || W == 4, "one dword, dwordx2 or dwordx4 load");
-    if constexpr (W == 4) {
-        const uint4 q = *reinterpret_cast<const uint4*>(p);
-        w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
-    } else if constexpr (W == 2) {
-        const uint2 q = *reinterpret_cast<const uint2*>(p);
-        w[0] = q.x; w[1] = q.y;
-    } else {
-        w[0] = *reinterpret_cast<const uint32_t*>(p);
-    }
-}
-
-template <int W>
-__device__ __forceinline__ uint32_t byte_of(const uint32_t (&w)[W], const int k) { return (w[k >> 2] >> (8 * (k & 3))) & 0xffu; }
+constexpr int YR_COLS = SURF_VEC_COLS;   // luma columns a thread of the vector form owns (8 or 16); load_words, byte_of: surface.h
 
 // acc[0..2] += wy * (r, g, b) of the pixel with luma Y under chroma c
 __device__ __forceinline__ void add_pixel(uint32_t* __restrict__ acc, const uint32_t wy, const int Y, const YuvChroma& c, const YuvCoef& coef) {
@@ -354,13 +336,6 @@ __device__ __forceinline__ void surf_area_row_out(const uint32_t* colsum, const 
         for (int ix = ix0; ix < ix1; ++ix) s += overlap_x(ix, ox, IW, OW) * colsum[ix * 3 + c];
         dst[((n * 3 + c) * OH + oy) * OW + ox] = (float)((double)s / area) * scale;
     }
-}
-
-// bytes 0 and 2 of lo, then of hi (ODD: bytes 1 and 3): every second byte of eight
-template <bool ODD>
-__device__ __forceinline__ uint32_t every_second_byte(const uint32_t lo, const uint32_t hi) {
-    constexpr int s = ODD ? 8 : 0;
-    return ((lo >> s) & 0xffu) | (((lo >> (16 + s)) & 0xffu) << 8) | (((hi >> s) & 0xffu) << 16) | (((hi >> (16 + s)) & 0xffu) << 24);
 }
 
 template <bool VEC>
@@ -664,32 +639,13 @@ extern "C" int eve_screen_area_surface_to_nchw(const eve_surface* surface, int m
     a.yuv = s.kind == EVE_SURF_YUV;
     a.coef = YUV_MATRICES[a.yuv ? matrix : 0];
     a.sf = surf_of(s);
-    // 8-bit 4:2:0 with luma step 1: interleaved chroma (U and V one byte apart, step 2, one pitch) or two planes (step 1)
-    const long long duv = s.offset[2] - s.offset[1];
-    const bool semi = s.step[1] == 2 && s.step[2] == 2 && (duv == 1 || duv == -1) && s.pitch[1] == s.pitch[2];
-    const bool planar = s.step[1] == 1 && s.step[2] == 1;
-    const bool yuv420 = a.yuv && s.xshift == 1 && s.yshift == 1 && s.step[0] == 1 && (semi || planar) && IW >= 2;
-    a.planar = planar;
-    a.skew = 0;
+    // 8-bit 4:2:0 with luma step 1 keeps the wide loads where every load lies on its own size (surface.h surf_form)
+    const SurfForm form = surf_form(s, N, src);
+    a.planar = form.planar;
+    a.skew = form.skew;
     const dim3 grid((unsigned)(a.items < SR_MAX_BLOCKS ? a.items : SR_MAX_BLOCKS));
-    if (yuv420) {
-        // the vector form: 8 luma bytes and 8 interleaved chroma bytes (planar: 4 + 4) per load, each load on its own size in every
-        // row of every frame.  The loads start `skew` bytes below pixel (0, 0) and end on the boundary behind the row's last pixel:
-        // every plane must hold those bytes inside [0, frame_bytes), and luma and chroma must share the skew.
-        const uintptr_t base = reinterpret_cast<uintptr_t>(src);
-        const int skew = (int)((base + (uintptr_t)s.offset[0]) & (YR_COLS - 1));
-        const long long span = (skew + (long long)IW + YR_COLS - 1) / YR_COLS * YR_COLS;      // bytes of luma a row's groups cover
-        const long long crows = (IH + 1) / 2;
-        const auto plane_ok = [&](long long offset, int pitch, long long rows, int bytes, int skew_c, long long span_c) {
-            return (int)((base + (uintptr_t)offset) & (bytes - 1)) == skew_c && pitch % bytes == 0 && (N == 1 || s.frame_stride % bytes == 0) &&
-                   offset >= skew_c && offset - skew_c + (rows - 1) * pitch + span_c <= s.frame_bytes;
-        };
-        const long long oc = duv > 0 ? s.offset[1] : s.offset[2];
-        const bool vec = skew % 2 == 0 && plane_ok(s.offset[0], s.pitch[0], IH, YR_COLS, skew, span) &&
-                         (planar ? plane_ok(s.offset[1], s.pitch[1], crows, YR_COLS / 2, skew / 2, span / 2) &&
-                                       plane_ok(s.offset[2], s.pitch[2], crows, YR_COLS / 2, skew / 2, span / 2)
-                                 : plane_ok(oc, s.pitch[1], crows, YR_COLS, skew, span));
-        if (vec) a.skew = skew;
+    if (form.yuv420) {
+        const bool vec = form.vec;
         if (vec)
             EVE_LAUNCH("screen_area_surface_kernel<yuv420,true>", (screen_area_surface_kernel<SURF_YUV420, true>), grid, dim3(SR_THREADS), lds,
                        (hipStream_t)stream, a, src, dst_nchw);

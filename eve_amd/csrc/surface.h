@@ -2,7 +2,7 @@
 // steps in place of a byte-linear layout.  The whole contract is one address rule -- component c of pixel (x, y) is the byte
 //   frame + offset[c] + (y >> ys) * pitch[c] + (x >> xs) * step[c]         xs = ys = 0 for component 0 and for EVE_SURF_RGB
 // in 64-bit arithmetic -- so NV12 / NV21, I420 / YV12, YUYV / UYVY, P010's high bytes, pitched BGRA and every crop of them are
-// numbers in the descriptor, not kernels.  This header holds what the eye-patch warp and the screen area resize share: the part
+// numbers in the descriptor, not kernels.  This header holds what the eye-patch warp, the screen area resize and the screen luminance share: the part
 // of the descriptor a kernel reads (by value in its arguments, uniform over the launch), the address rule for one pixel and for the 2 x 2 taps of a bilinear sample, and the host-side refusals.
 #pragma once
 #include "common.h"
@@ -54,7 +54,70 @@ __device__ __forceinline__ void surf_tap_terms(const Surf& s, const int y0, cons
     }
 }
 
-constexpr int SURF_MAX_SIDE = 1 << 24;     // keeps every product of the bound check far inside 64 bits; the kernels ask for less
+// ---- the wide loads of the 8-bit 4:2:0 vector form, shared by the screen area resize and the screen luminance
+constexpr int SURF_VEC_COLS = 8;           // luma columns a thread of the vector form owns: one 8-byte load per row
+
+// W = 1, 2 or 4 dwords from p (aligned to 4 * W bytes) as one load
+template <int W>
+__device__ __forceinline__ void load_words(const uint8_t* __restrict__ p, uint32_t (&w)[W]) {
+    static_assert(W == 1 || W == 2 || W == 4, "one dword, dwordx2 or dwordx4 load");
+    if constexpr (W == 4) {
+        const uint4 q = *reinterpret_cast<const uint4*>(p);
+        w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
+    } else if constexpr (W == 2) {
+        const uint2 q = *reinterpret_cast<const uint2*>(p);
+        w[0] = q.x; w[1] = q.y;
+    } else {
+        w[0] = *reinterpret_cast<const uint32_t*>(p);
+    }
+}
+
+template <int W>
+__device__ __forceinline__ uint32_t byte_of(const uint32_t (&w)[W], const int k) { return (w[k >> 2] >> (8 * (k & 3))) & 0xffu; }
+
+// bytes 0 and 2 of lo, then of hi (ODD: bytes 1 and 3): every second byte of eight
+template <bool ODD>
+__device__ __forceinline__ uint32_t every_second_byte(const uint32_t lo, const uint32_t hi) {
+    constexpr int s = ODD ? 8 : 0;
+    return ((lo >> s) & 0xffu) | (((lo >> (16 + s)) & 0xffu) << 8) | (((hi >> s) & 0xffu) << 16) | (((hi >> (16 + s)) & 0xffu) << 24);
+}
+
+// Which load form N frames of a (checked) descriptor at `src` take.  yuv420: 8-bit 4:2:0 with luma step 1 and chroma either
+// interleaved (U and V one byte apart, step 2, one pitch) or in two planes (step 1).  vec: its vector form -- 8 luma bytes and 8
+// interleaved chroma bytes (planar: 4 + 4) per load, each load on its own size in every row of every frame.  The loads start `skew`
+// bytes below pixel (0, 0) and end on the boundary behind the row's last pixel: every plane must hold those bytes inside
+// [0, frame_bytes), and luma and chroma must share the skew.
+struct SurfForm {
+    bool yuv420, planar, vec;
+    int skew;
+};
+
+inline SurfForm surf_form(const eve_surface& s, const long long N, const uint8_t* src) {
+    SurfForm f = {false, false, false, 0};
+    const int IH = s.height, IW = s.width;
+    const long long duv = s.offset[2] - s.offset[1];
+    const bool semi = s.step[1] == 2 && s.step[2] == 2 && (duv == 1 || duv == -1) && s.pitch[1] == s.pitch[2];
+    f.planar = s.step[1] == 1 && s.step[2] == 1;
+    f.yuv420 = s.kind == EVE_SURF_YUV && s.xshift == 1 && s.yshift == 1 && s.step[0] == 1 && (semi || f.planar) && IW >= 2;
+    if (!f.yuv420) return f;
+    const uintptr_t base = reinterpret_cast<uintptr_t>(src);
+    const int skew = (int)((base + (uintptr_t)s.offset[0]) & (SURF_VEC_COLS - 1));
+    const long long span = (skew + (long long)IW + SURF_VEC_COLS - 1) / SURF_VEC_COLS * SURF_VEC_COLS;      // bytes of luma a row's groups cover
+    const long long crows = (IH + 1) / 2;
+    const auto plane_ok = [&](long long offset, int pitch, long long rows, int bytes, int skew_c, long long span_c) {
+        return (int)((base + (uintptr_t)offset) & (bytes - 1)) == skew_c && pitch % bytes == 0 && (N == 1 || s.frame_stride % bytes == 0) &&
+               offset >= skew_c && offset - skew_c + (rows - 1) * pitch + span_c <= s.frame_bytes;
+    };
+    const long long oc = duv > 0 ? s.offset[1] : s.offset[2];
+    f.vec = skew % 2 == 0 && plane_ok(s.offset[0], s.pitch[0], IH, SURF_VEC_COLS, skew, span) &&
+            (f.planar ? plane_ok(s.offset[1], s.pitch[1], crows, SURF_VEC_COLS / 2, skew / 2, span / 2) &&
+                            plane_ok(s.offset[2], s.pitch[2], crows, SURF_VEC_COLS / 2, skew / 2, span / 2)
+                      : plane_ok(oc, s.pitch[1], crows, SURF_VEC_COLS, skew, span));
+    if (f.vec) f.skew = skew;
+    return f;
+}
+
+constexpr int SURF_MAX_SIDE = 1 << 24;    // keeps every product of the bound check far inside 64 bits; the kernels ask for less
 
 // what is wrong with the descriptor itself for N frames, or nullptr: everything that can be told without the kernel's own limits
 inline const char* surface_refusal(const eve_surface* s, const int matrix, const long long N) {

@@ -1322,9 +1322,9 @@ class PupilSpec(object):
       dilate_mm_s, constrict_mm_s    the velocity above / below which a sample dilates / constricts (0.15 and 0.3 mm/s)
       min_amplitude_mm  episodes that move the filtered size by less are not stored (0.1 mm: the lower end of task-evoked responses,
                         Beatty 1982, "Task-evoked pupillary responses", Psychol. Bull. 91)
-    Instances compare and hash by value: the spec is part of a captured graph's key, and the tallies are tied to their spec.  Not
-    offered: luminance computed from the screen capture (the covariate comes with the chunk as pupil_luminance), non-causal blink
-    padding and interpolation across gaps, foreshortening correction, per-eye filtered traces, wavelet indices (IPA / LHIPA),
+    Instances compare and hash by value: the spec is part of a captured graph's key, and the tallies are tied to their spec.  The
+    light covariate comes with the chunk as pupil_luminance, or from luminance=ScreenLuminanceSpec(...) in the same step.  Not
+    offered: non-causal blink padding and interpolation across gaps, foreshortening correction, per-eye filtered traces, wavelet indices (IPA / LHIPA),
     per-fixation or per-AOI pupil means, gradients, EVE.forward, the overlay."""
 
     def __init__(self, name='pupil', fps=None, min_mm=1.5, max_mm=9.0, max_speed_mm_s=10.0, max_gap_s=0.25, offset_rate=0.05, cutoff_hz=4.0,
@@ -1422,6 +1422,215 @@ def pupil_track(spec, left, right, eye_valid=None, frame_time=None, lengths=None
                                         flush=torch.ones((S,), dtype=torch.int32, device=dev))
     out = {'%s_%s' % (spec.name, k_): v for k_, v in out.items()}
     out.update(table=table, episodes=store, episode_count=count, episode_dropped=dropped, light=light_, state=state)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ screen luminance
+LUMINANCE_SOURCES = AOI_SOURCES                  # the points a disc can follow
+LUMINANCE_WEIGHTS = {'rec709': (13933, 46871, 4732)}      # (kr, kg, kb) in 1 / 65536, summing to 65536
+LUMINANCE_MAX_DISCS = 4                          # what eve_screen_luminance takes
+LUMINANCE_MAX_RADIUS = 16384                     # ... in capture pixels
+
+
+def display_response(kind='srgb', gamma=None, measured=None):
+    """The display's linearisation as eve_screen_luminance reads it: a uint16 [3, 256] CPU tensor, entry [c][v] the relative light
+    of channel c at the 8-bit value v, scaled to 65535 -- floor(65535 * f(v / 255) + 0.5) in float64.
+      kind='srgb'      sRGB's EOTF: c / 12.92 up to 0.04045, then ((c + 0.055) / 1.055) ** 2.4
+      kind='gamma'     the power law (v / 255) ** gamma, gamma a finite number > 0
+      kind='measured'  measured: a [256] curve for all three channels or a [3, 256] one per channel, values in 0 .. 1
+    Anything else raises ValueError."""
+    v = np.arange(256, dtype=np.float64) / 255.0
+    if kind == 'srgb':
+        if gamma is not None or measured is not None:
+            raise ValueError("display_response: kind 'srgb' takes neither gamma nor measured")
+        f = np.where(v <= 0.04045, v / 12.92, ((v + 0.055) / 1.055) ** 2.4)
+    elif kind == 'gamma':
+        if measured is not None or isinstance(gamma, bool) or not isinstance(gamma, (int, float, np.integer, np.floating)) or \
+                not np.isfinite(gamma) or not gamma > 0:
+            raise ValueError("display_response: kind 'gamma' takes gamma, a finite number > 0, and no measured curve, got %r" % (gamma,))
+        f = v ** float(gamma)
+    elif kind == 'measured':
+        f = None if measured is None or gamma is not None else np.asarray(measured, dtype=np.float64)
+        if f is None or f.shape not in ((256,), (3, 256)) or not np.isfinite(f).all() or f.min() < 0.0 or f.max() > 1.0:
+            raise ValueError("display_response: kind 'measured' takes measured, a [256] or [3, 256] curve of values in 0 .. 1, and no gamma")
+    else:
+        raise ValueError("display_response: kind must be 'srgb', 'gamma' or 'measured', got %r" % (kind,))
+    table = np.floor(65535.0 * np.broadcast_to(f, (3, 256)) + 0.5).astype(np.uint16)
+    return torch.from_numpy(np.ascontiguousarray(table))
+
+
+class ScreenLuminanceSpec(object):
+    """What EVEStream.step(chunk, luminance=spec) adds to the step (eve_screen_luminance): per frame the mean relative luminance of the
+    screen capture -- every pixel read where it lies, converted, linearised through the display's response, weighted -- over the
+    whole screen and over discs around the point of gaze; the light covariate of the pupil trace.
+      name        the result keys: <name> float32 [B, Tc] (the whole screen), <name>_gaze [B, Tc, R] (the discs), <name>_covariate
+      radii_px    up to four strictly increasing disc radii in actual_screen_size pixels (as aoi_shapes); a radius goes to capture
+                  pixels as max(1, round(r * sx))
+      source      the point the discs follow: 'PoG_px_initial', 'PoG_px_final', 'PoG_px_filtered', 'fixation_px' (the last two need
+                  events= in the same step), or None: PoG_px_final with a RefineNet, else PoG_px_initial
+      valid_key   None or the key of a bool / uint8 [B, Tc] entry of the result or the chunk, ANDed into the discs' validity
+      response    'srgb', ('gamma', g), or a uint16 [3, 256] table (display_response)
+      weights     'rec709', or three integers >= 0 that sum to 65536
+      to_pupil    None, or up to 1 + R weights over the columns (whole screen, then the discs): <name>_covariate = sum of w_k * mean_k,
+                  a left-to-right chain of float32 products and sums that skips columns of weight 0 (so a disc off the screen, whose
+                  mean is NaN, poisons nothing it has no weight in); with pupil= in the same step it is that stage's luminance
+    Instances compare and hash by value: the spec is part of a captured graph's key.  The mean of a frame that is not delivered, and
+    of a disc without a valid centre or off the screen, is NaN.  Not offered: continuous (eccentricity-weighted) kernels beyond
+    concentric discs, per-AOI luminance, 10-bit arithmetic, ambient light, the camera image's luminance, the overlay, gradients,
+    EVE.forward."""
+
+    def __init__(self, name='screen_luminance', radii_px=(), source=None, valid_key=None, response='srgb', weights='rec709', to_pupil=(1.0,)):
+        number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and np.isfinite(v)
+        if not isinstance(name, str) or not name:
+            raise ValueError('ScreenLuminanceSpec: name must be a non-empty string, got %r' % (name,))
+        try:
+            radii = tuple(radii_px)
+        except TypeError:
+            radii = None
+        if radii is None or len(radii) > LUMINANCE_MAX_DISCS or not all(number(r) and r > 0 for r in radii) or \
+                any(b <= a for a, b in zip(radii, radii[1:])):
+            raise ValueError('ScreenLuminanceSpec: radii_px must be up to %d strictly increasing finite numbers > 0, got %r' % (
+                LUMINANCE_MAX_DISCS, radii_px))
+        if source is not None and source not in LUMINANCE_SOURCES:
+            raise ValueError('ScreenLuminanceSpec: source must be None or one of %s, got %r' % (', '.join(LUMINANCE_SOURCES), source))
+        if valid_key is not None and (not isinstance(valid_key, str) or not valid_key):
+            raise ValueError('ScreenLuminanceSpec: valid_key must be None or the key of a [B, Tc] entry, got %r' % (valid_key,))
+        if isinstance(response, str):
+            if response != 'srgb':
+                raise ValueError("ScreenLuminanceSpec: response must be 'srgb', ('gamma', g) or a uint16 [3, 256] table, got %r" % (response,))
+            table, response_key = display_response('srgb').numpy(), 'srgb'
+        elif isinstance(response, tuple) and len(response) == 2 and response[0] == 'gamma':
+            table = display_response('gamma', gamma=response[1]).numpy()
+            response_key = ('gamma', float(response[1]))
+        else:
+            table = response.cpu().numpy() if torch.is_tensor(response) else np.asarray(response)
+            if table.dtype != np.uint16 or table.shape != (3, 256):
+                raise ValueError("ScreenLuminanceSpec: response must be 'srgb', ('gamma', g) or a uint16 [3, 256] table, got %s %s" % (
+                    table.dtype, table.shape))
+            table = np.ascontiguousarray(table)
+            response_key = ('table', table.tobytes())
+        if isinstance(weights, str):
+            if weights not in LUMINANCE_WEIGHTS:
+                raise ValueError('ScreenLuminanceSpec: weights must be one of %s or three integers, got %r' % (', '.join(LUMINANCE_WEIGHTS), weights))
+            weights = LUMINANCE_WEIGHTS[weights]
+        try:
+            weights = tuple(weights)
+        except TypeError:
+            weights = ()
+        if len(weights) != 3 or not all(isinstance(w, (int, np.integer)) and not isinstance(w, bool) and w >= 0 for w in weights) or \
+                sum(int(w) for w in weights) != 65536:
+            raise ValueError("ScreenLuminanceSpec: weights must be 'rec709' or three integers >= 0 that sum to 65536, got %r" % (weights,))
+        if to_pupil is not None:
+            try:
+                to_pupil = tuple(to_pupil)
+            except TypeError:
+                raise ValueError('ScreenLuminanceSpec: to_pupil must be None or a sequence of weights, got %r' % (to_pupil,))
+            if len(to_pupil) > 1 + len(radii):
+                raise ValueError('ScreenLuminanceSpec: to_pupil holds %d weights for %d columns (the whole screen and %d discs)' % (
+                    len(to_pupil), 1 + len(radii), len(radii)))
+            if not to_pupil or not all(number(w) for w in to_pupil) or not any(w != 0 for w in to_pupil):
+                raise ValueError('ScreenLuminanceSpec: to_pupil must be None or finite weights, one of them not 0, got %r' % (to_pupil,))
+            to_pupil = tuple(float(w) for w in to_pupil)
+        self.name, self.radii_px, self.source, self.valid_key = name, tuple(float(r) for r in radii), source, valid_key
+        self.response, self.weights, self.to_pupil = response_key, tuple(int(w) for w in weights), to_pupil
+        self._table = table
+
+    def key(self):
+        return (self.name, self.radii_px, self.source, self.valid_key, self.response, self.weights, self.to_pupil)
+
+    def __eq__(self, other):
+        return isinstance(other, ScreenLuminanceSpec) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        shown = self.response if self.response == 'srgb' or self.response[0] == 'gamma' else '<a [3, 256] table>'
+        return 'ScreenLuminanceSpec(name=%r, radii_px=%r, source=%r, valid_key=%r, response=%r, weights=%r, to_pupil=%r)' % (
+            self.name, self.radii_px, self.source, self.valid_key, shown, self.weights, self.to_pupil)
+
+    def response_table(self):
+        """-> the uint16 [3, 256] table as a CPU tensor (a copy)."""
+        return torch.from_numpy(self._table.copy())
+
+    def result_keys(self):
+        """-> the keys the stage adds to a step's result."""
+        return (self.name,) + ((self.name + '_gaze',) if self.radii_px else ()) + ((self.name + '_covariate',) if self.to_pupil is not None else ())
+
+    def capture_radii(self, sx, where='screen_luminance'):
+        """radii_px in capture pixels, max(1, round(r * sx)) -> a tuple of ints; ValueError where two radii fall together or one
+        exceeds what the library takes."""
+        radii = tuple(max(1, int(round(r * sx))) for r in self.radii_px)
+        if any(b <= a for a, b in zip(radii, radii[1:])) or any(r > LUMINANCE_MAX_RADIUS for r in radii):
+            raise ValueError('%s: radii_px %r are %r capture pixels at this capture\'s scale (%g): they must stay strictly increasing and <= %d' % (
+                where, self.radii_px, radii, sx, LUMINANCE_MAX_RADIUS))
+        return radii
+
+
+def capture_layout(frames, format, lead, name='frames'):
+    """The tight SurfaceLayout of byte-linear frames of one pixel format ('rgb', 'bgr' -- with four channels 'rgba', 'bgra' --, 'nv12',
+    'i420', 'yuyv'; kernels.pixel_format_shape has the shapes) with `lead` leading dimensions.  TypeError / ValueError as there."""
+    from .kernels import pixel_format_shape
+    IH, IW, C = pixel_format_shape(frames, format, lead=lead, name=name)
+    return SurfaceLayout(format + 'a' if C == 4 else format, IW, IH)
+
+
+def luminance_results(spec, mean, B, T):
+    """eve_screen_luminance's mean float32 [B * T, 1 + R] -> the stage's results under spec.result_keys()."""
+    R = len(spec.radii_px)
+    out = {spec.name: mean[:, 0].reshape(B, T)}
+    if R:
+        out[spec.name + '_gaze'] = mean[:, 1:].reshape(B, T, R)
+    if spec.to_pupil is not None:
+        cov = None
+        for k_, w in enumerate(spec.to_pupil):
+            if w == 0:
+                continue
+            term = mean[:, k_] * w
+            cov = term if cov is None else cov + term
+        out[spec.name + '_covariate'] = cov.reshape(B, T)
+    return out
+
+
+def screen_luminance(frames, layout_or_format, spec, screen_size, pog_px=None, valid=None, lengths=None, matrix='bt601'):
+    """The screen luminance of S recorded streams, stand-alone: frames uint8 [S, T, ...], the captures byte-linear in the pixel format
+    layout_or_format names ('rgb', 'bgr', 'nv12', 'i420', 'yuyv') or as surfaces under a SurfaceLayout; spec a ScreenLuminanceSpec
+    (source and valid_key are not looked at); screen_size (W, H) of the pixels pog_px and spec.radii_px are in; pog_px float32 [S, T, 2],
+    needed iff the spec has radii; valid None or bool / uint8 [S, T] (the discs' validity); lengths None or int32 [S] on the device;
+    matrix for the YUV formats.  One eve_screen_luminance launch.  -> the spec's result keys (<name> float32 [S, T], <name>_gaze
+    [S, T, R], <name>_covariate [S, T]) plus sums int64 and counts int32 [S, T, 1 + R]; the host does not wait."""
+    where = 'screen_luminance'
+    if not isinstance(spec, ScreenLuminanceSpec):
+        raise ValueError('%s: spec must be an eve_amd.ScreenLuminanceSpec, got %s' % (where, type(spec).__name__))
+    W, H = check_screen_size(screen_size, where)
+    if not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() < 3:
+        raise TypeError('%s: frames must be uint8 [S, T, one frame], got %s %s' % (where, getattr(frames, 'dtype', type(frames)),
+                                                                                   tuple(getattr(frames, 'shape', ()))))
+    if isinstance(layout_or_format, SurfaceLayout):
+        layout = layout_or_format
+        surface_frames(frames, layout, 2, name=where + ': frames')
+    else:
+        layout = capture_layout(frames, layout_or_format, 2, name=where + ': frames')
+    S, T = int(frames.shape[0]), int(frames.shape[1])
+    R = len(spec.radii_px)
+    sx, sy = layout.width / W, layout.height / H
+    radii = spec.capture_radii(sx, where)
+    if (pog_px is None) != (R == 0):
+        raise ValueError('%s: pog_px comes with a spec that has radii_px, and only then' % where)
+    if pog_px is not None and (not torch.is_tensor(pog_px) or pog_px.dtype != torch.float32 or tuple(pog_px.shape) != (S, T, 2)):
+        raise TypeError('%s: pog_px must be float32 [%d, %d, 2]' % (where, S, T))
+    if valid is not None:
+        valid = _bool_rows(valid, (S, T), where + ': valid').reshape(S * T)
+    if lengths is not None and (not torch.is_tensor(lengths) or lengths.dtype != torch.int32 or tuple(lengths.shape) != (S,)):
+        raise TypeError('%s: lengths must be an int32 [%d] tensor' % (where, S))
+    if not frames.is_contiguous():
+        raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+    sums, counts, mean = default_kernels().screen_luminance(
+        frames.reshape(S * T, -1), layout, spec.response_table().to(frames.device), spec.weights, S, T, radii=radii,
+        centres=None if pog_px is None else pog_px.reshape(S * T, 2).contiguous(), sx=sx, sy=sy, centre_valid=valid,
+        lengths=None if lengths is None else lengths.contiguous(), matrix=matrix)
+    out = luminance_results(spec, mean, S, T)
+    out.update(sums=sums.reshape(S, T, 1 + R), counts=counts.reshape(S, T, 1 + R))
     return out
 
 

@@ -366,7 +366,7 @@ class EVE(nn.Module):
 
     def _predict_sequence(self, d, eye_states, refine_states, reset=None, return_heatmaps=False, lengths=None, masked=False,
                           eye_mask=None, pose_gate=None, face_state=None, render=None, calibration=None, events=None, gate=None,
-                          screen_calibration=None, history=None, aoi=None, pupil=None):
+                          screen_calibration=None, history=None, aoi=None, pupil=None, luminance=None):
         """The prediction part of forward() for one chunk of an EVEStream: eval only, no labels, no losses.  d: the chunk's
         inputs [B, Tc, ...] (not modified; camera_frame may be any one key of eye_net.EYE_FRAME_KEYS or camera_surface, and the screen any one
         key of refine_net.SCREEN_FRAME_KEYS or screen_surface; the eyes as patches, as camera_frame + {left,right}_eye_warp, or as camera_frame +
@@ -432,7 +432,13 @@ class EVE(nn.Module):
         'light': float64 [B, 4], 'store': float64 [B, capacity, 8], 'count', 'dropped': int32 [B]}: one eve_pupil_track launch, after the
         AOI stage and before the render hook, over the step's own <side>_pupil_size, the mask plan's eye_valid (a masked or gated
         step), frame_time, pupil_luminance and pupil_baseline from d where they are there, the step's lengths and reset flags; the
-        result gains <name>_<key> for data.PUPIL_KEYS.  None issues no launch."""
+        result gains <name>_<key> for data.PUPIL_KEYS.  None issues no launch.
+        luminance: None, or EVEStream's screen-luminance stage {'spec': a data.ScreenLuminanceSpec, 'key': the capture's chunk key,
+        'layout': its data.SurfaceLayout, 'matrix', 'source': the result key the discs follow or None, 'radii': capture pixels, 'sx',
+        'sy', 'table': the response table on the device}: one eve_screen_luminance launch, after the AOI stage and before the pupil
+        stage, over the capture where it lies in d, the step's lengths and, for the discs, the masked plan's valid ANDed with the
+        spec's valid_key; the result gains the spec's result_keys(), and with to_pupil and pupil= the covariate is the pupil stage's
+        luminance.  None issues no launch."""
         assert not self.training, 'EVE._predict_sequence is eval-only'
         B = eye_input(d).shape[0]
         posed, faced = has_pose_form(d), face_landmarks_key(d) is not None
@@ -507,7 +513,12 @@ class EVE(nn.Module):
             self._gaze_history(d, inter, out, history, lengths_b, reset_b, plan)
         if aoi is not None:
             self._gaze_aoi(d, inter, out, aoi, lengths_b, reset_b, plan)
-        if pupil is not None:
+        covariate = None
+        if luminance is not None:
+            covariate = self._screen_luminance(d, inter, out, luminance, lengths_b, plan)
+        if pupil is not None and covariate is not None:
+            self._pupil_track(d, inter, out, pupil, lengths_b, reset_b, plan, luminance=covariate)
+        elif pupil is not None:
             self._pupil_track(d, inter, out, pupil, lengths_b, reset_b, plan)
         if render is not None:
             render(d, inter, out)
@@ -564,15 +575,48 @@ class EVE(nn.Module):
         for k_, v in res.items():
             out['%s_%s' % (spec.name, k_)] = v
 
-    def _pupil_track(self, d, inter, out, pupil, lengths, reset, plan):
-        """The pupillometry stage of an EVEStream step: one eve_pupil_track launch on the carried buffers."""
+    def _screen_luminance(self, d, inter, out, lum, lengths, plan):
+        """The screen-luminance stage of an EVEStream step: one eve_screen_luminance launch on the capture where it lies (the chunk
+        tensor; under a graph, its input buffer) -> the covariate float32 [B, T], or None without to_pupil."""
+        from .data import luminance_results
+        B, T = eye_input(d).shape[:2]
+        spec = lum['spec']
+
+        def look(key):
+            for src in (out, inter, d):
+                if key in src:
+                    return src[key]
+            raise ValueError('step: luminance: %r is neither in the chunk nor a result of this step' % (key,))
+
+        centres = valid = None
+        if spec.radii_px:
+            centres = _f32(look(lum['source']), B, T, 2).reshape(B * T, 2)
+            if plan is not None:
+                valid = plan['valid'].reshape(B, T) != 0
+            if spec.valid_key is not None:
+                vk = look(spec.valid_key).reshape(B, T) != 0
+                valid = vk if valid is None else valid & vk
+            if valid is not None:
+                valid = valid.to(torch.uint8).reshape(B * T).contiguous()
+        frames = d[lum['key']]
+        _, _, mean = default_kernels().screen_luminance(
+            frames.reshape(B * T, -1), lum['layout'], lum['table'], spec.weights, B, T, radii=lum['radii'], centres=centres, sx=lum['sx'],
+            sy=lum['sy'], centre_valid=valid, lengths=lengths, matrix=lum['matrix'])
+        res = luminance_results(spec, mean, B, T)
+        out.update(res)
+        return res.get(spec.name + '_covariate')
+
+    def _pupil_track(self, d, inter, out, pupil, lengths, reset, plan, luminance=None):
+        """The pupillometry stage of an EVEStream step: one eve_pupil_track launch on the carried buffers.  luminance: None, or the
+        screen-luminance stage's covariate of this step, in place of the chunk's pupil_luminance (the step refuses both)."""
         B, T = eye_input(d).shape[:2]
         spec = pupil['spec']
         size = torch.stack([_f32(inter['left_pupil_size'], B, T), _f32(inter['right_pupil_size'], B, T)])
         res = default_kernels().pupil_track(
             size, spec, pupil['state'], pupil['table'], pupil['light'], pupil['store'], pupil['count'], pupil['dropped'],
             eye_valid=None if plan is None else plan['eye_valid'], frame_time=d['frame_time'].contiguous() if 'frame_time' in d else None,
-            lengths=lengths, reset=reset, luminance=d['pupil_luminance'].contiguous() if 'pupil_luminance' in d else None,
+            lengths=lengths, reset=reset,
+            luminance=luminance.contiguous() if luminance is not None else d['pupil_luminance'].contiguous() if 'pupil_luminance' in d else None,
             baseline_mark=_u8(d.get('pupil_baseline')))
         for k_, v in res.items():
             out['%s_%s' % (spec.name, k_)] = v

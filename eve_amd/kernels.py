@@ -59,6 +59,11 @@ def pixel_format_shape(frames, format, lead=1, name='frames'):
     return rows // 3 * 2, IW, 1
 
 
+# eve_screen_luminance: the rows of one workgroup's band (csrc/screen_luminance.hip LUM_BAND_ROWS; the tests place discs across it)
+LUM_BAND_ROWS = 32
+LUM_REC709 = (13933, 46871, 4732)         # Rec.709's luminance weights in 1 / 65536, summing to 65536
+
+
 # include/eve_hip.h eve_overlay_render: the capture formats it reads (EVE_PIX_RGB / _RGBA are its own two codes) and writes
 OVERLAY_IN_FORMATS = dict(PIXEL_FORMATS, rgb=5, rgba=6)
 OVERLAY_OUT_FORMATS = {'rgb': 5, 'bgr': 0, 'nv12': 2, 'i420': 3}
@@ -778,6 +783,50 @@ class HipKernels(object):
         surf = layout.as_ctypes()
         self._ck(self.lib.eve_screen_area_surface_to_nchw(ctypes.byref(surf), mat, N, self._p(frames), OH, OW, self._p(out), self._stream()))
         return out
+
+    def screen_luminance(self, frames, layout, response, weights, B, T, radii=(), centres=None, sx=1.0, sy=1.0, centre_valid=None,
+                         lengths=None, matrix='bt601'):
+        """The mean relative luminance of B x T screen captures where they lie, over the whole visible region and over the discs of
+        `radii` capture pixels around `centres`: frames uint8 [B * T, ...] with layout.frame_stride bytes per frame, layout a
+        data.SurfaceLayout (checked as for screen_area_surface_to_nchw); response uint16-valued int16 / uint16 [3, 256] on the device
+        (data.display_response); weights (kr, kg, kb) integers >= 0 that sum to 65536; radii up to four strictly increasing integers
+        in 1 .. 16384; centres float32 [B * T, 2] in the units that sx, sy turn into capture pixels (needed iff there are radii);
+        centre_valid uint8 [B * T] or None; lengths int32 [B] or None.  -> (sums int64 [B * T, 1 + R], counts int32 [B * T, 1 + R],
+        mean float32 [B * T, 1 + R]); column 0 is the whole frame (include/eve_hip.h eve_screen_luminance)."""
+        who = 'screen_luminance'
+        N, mat = self._surface_args(who, frames, layout, matrix)
+        ok = lambda t, dtype: torch.is_tensor(t) and t.dtype == dtype
+        got = lambda t: (getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ())))
+        B, T = int(B), int(T)
+        if B < 1 or T < 1 or B * T != N:
+            raise ValueError('%s: frames hold %d frames, B x T is %d x %d' % (who, N, B, T))
+        if not torch.is_tensor(response) or response.dtype not in (torch.int16, torch.uint16) or tuple(response.shape) != (3, 256):
+            raise TypeError('%s: response must be a 16-bit integer [3, 256] tensor (data.display_response), got %s %s' % ((who,) + got(response)))
+        radii = [int(r) for r in radii]
+        R = len(radii)
+        checks = [('lengths', lengths, torch.int32, (B,), False), ('centres', centres, torch.float32, (N, 2), R > 0),
+                  ('centre_valid', centre_valid, torch.uint8, (N,), False)]
+        tensors = [response]
+        for name, t, dtype, shape, needed in checks:
+            if (t is not None or needed) and (not ok(t, dtype) or tuple(t.shape) != shape):
+                raise TypeError('%s: %s must be %s %s, got %s %s' % ((who, name, str(dtype).replace('torch.', ''), list(shape)) + got(t)))
+            if t is not None:
+                tensors.append(t)
+        if not all(t.is_contiguous() for t in tensors):
+            raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        if any(t.device != frames.device for t in tensors):
+            raise RuntimeError('%s: the tensors are on different devices' % who)
+        kr, kg, kb = (int(w) for w in weights)
+        dev = frames.device
+        sums = torch.empty((N, 1 + R), dtype=torch.int64, device=dev)
+        counts = torch.empty((N, 1 + R), dtype=torch.int32, device=dev)
+        mean = torch.empty((N, 1 + R), dtype=torch.float32, device=dev)
+        surf = layout.as_ctypes()
+        self._ck(self.lib.eve_screen_luminance(
+            ctypes.byref(surf), mat, B, T, self._p(frames), self._p(response), kr, kg, kb, self._p(lengths), R,
+            (ctypes.c_int * R)(*radii) if R else None, self._p(centres), float(sx), float(sy), self._p(centre_valid), self._p(sums),
+            self._p(counts), self._p(mean), self._stream()))
+        return sums, counts, mean
 
     def eye_pose_normalize(self, pose, out_hw):
         """Eye normalisation derived from the head pose, both eyes of N frames in one launch: pose float32 [N,18] =

@@ -16,6 +16,7 @@ carried from one call to the next.
     out = stream.step(chunk, history=eve_amd.GazeHistorySpec(fps=60))                # + the time-decayed map of where the gaze has been
     out = stream.step(dict(chunk, aoi_shapes=regions), aoi=eve_amd.AoiSpec(num_aois=8, fps=60))   # + which region is looked at ("Areas of interest")
     out = stream.step(chunk, pupil=eve_amd.PupilSpec(fps=60))          # + the validated, fused, baseline-corrected pupil size ("Pupillometry")
+    out = stream.step(chunk, luminance=eve_amd.ScreenLuminanceSpec())  # + the screen's mean relative luminance, the pupil's light covariate ("Screen luminance")
     st = stream.get_state(); stream.set_state(st)          # reference layout, e.g. to resume a recording
 
 For any split of a clip into chunks the concatenated outputs equal one eval pass of the whole clip from zero state
@@ -188,10 +189,25 @@ presence part of the graph's key.  reset() closes the open episode and starts th
 counter runs on), also before a step without pupil=; the table and the light response stay, tied to their spec.  get_pupil_state() /
 set_pupil_state(); get_state() / set_state() do not hold them.  Float64, + - * /, abs and comparisons only: tests/pupil_ref.py states
 it, and the device equals it bit for bit, so a clip cut into chunks gives the bits of one pass.  A step without pupil= issues exactly
-the launches it always issued and allocates nothing.  Not offered: luminance computed from the screen capture on the device (the
-covariate comes with the chunk, e.g. from an ambient sensor or the caller's own mean), non-causal blink padding and interpolation
-across gaps, foreshortening correction, per-eye filtered traces, wavelet indices (IPA / LHIPA), per-fixation or per-AOI pupil means,
-the overlay, gradients, EVE.forward.
+the launches it always issued and allocates nothing.  Not offered: non-causal blink padding and interpolation across gaps,
+foreshortening correction, per-eye filtered traces, wavelet indices (IPA / LHIPA), per-fixation or per-AOI pupil means, the overlay,
+gradients, EVE.forward.
+
+Screen luminance.  On a screen-based tracker the pupil's response to the screen's light is the largest confound of the pupil trace,
+and the capture it follows is already in the step's input.  step(chunk, luminance=eve_amd.ScreenLuminanceSpec(...)) adds one
+eve_screen_luminance launch after the AOI stage and before the pupil stage, inside the graph, over the capture where it lies (any
+screen key; screen_surface through refine_net.screen_layout): every visible pixel is converted, linearised through the display's
+response table (sRGB, a power law or a measured curve), weighted (Rec.709) and summed in integers -- over the whole screen, <name>
+float32 [B, Tc], and over up to four discs of radii_px actual_screen_size pixels around the spec's source point, <name>_gaze [B, Tc,
+R].  to_pupil weighs the columns into <name>_covariate, which pupil= in the same step takes as its luminance (ValueError with
+pupil_luminance in the chunk too).  The whole screen follows lengths only; the discs also the masked step's valid and valid_key.  What
+is not delivered, a disc without a valid centre and a disc off the screen are NaN, a light sample the pupil stage ignores.  The mean
+of the linearised pixels is not the linearised mean: a one-pixel checkerboard has 0.5, its mean byte 0.216, so the stage reads the
+capture and not RefineNet's resized screen.  The response table goes to the device before any capture, cached per spec; the spec by
+value is part of the graph's key; the stage carries no state.  Integers up to one float64 division: tests/screen_luminance_ref.py
+states it, and the device equals it bit for bit.  A step without luminance= issues exactly the launches it always issued.  Not
+offered: continuous (eccentricity-weighted) kernels beyond concentric discs, per-AOI luminance, 10-bit arithmetic, ambient light, the
+camera image's luminance, the overlay, gradients, EVE.forward.
 """
 from collections import namedtuple
 
@@ -280,6 +296,9 @@ class EVEStream(object):
         # response, the episode store and its counters), 'free'} -- eve_pupil_track reads and writes them inside the step (and the graph)
         self.episode_capacity = _capacity('episode_capacity', episode_capacity)
         self._pupil = {}
+        # screen luminance (step(chunk, luminance=spec)): the response tables on the device, by spec key -- made before any capture, as
+        # the overlay's marker tables are; the stage carries no state
+        self._luminance_tables = {}
         self._graphs = {}
         self._graphs_key = None
         self._render_tables = {}                 # OverlaySpec.key() -> its marker table, int32 [M, 4] on the device
@@ -944,6 +963,84 @@ class EVEStream(object):
             self._pupil_entry(spec)              # (raises: the tallies are tied to another spec)
         return {'spec': spec}
 
+    # ------------------------------------------------------------------ screen luminance
+    def _check_luminance(self, chunk, spec, events, history, aoi, pupil, gate, masked, B, Tc):
+        """step()'s `luminance` checked against the chunk, the model and the step's other stages -> what _predict_sequence needs: the
+        capture's key, its layout and matrix, the discs' source, radii and scale, the response table on the device.  Every refusal is
+        a ValueError raised before anything is launched or captured."""
+        from .data import AOI_KEYS, EYE_GATE_KEYS, GAZE_EVENT_KEYS, PUPIL_KEYS, ScreenLuminanceSpec, capture_layout, surface_frames
+        from .kernels import YUV_MATRICES
+        from .refine_net import SCREEN_FRAME_KEYS, SCREEN_SURFACE_KEY, screen_frame_key
+        if not isinstance(spec, ScreenLuminanceSpec):
+            raise ValueError('step: luminance must be an eve_amd.ScreenLuminanceSpec, got %s' % type(spec).__name__)
+        taken = set(getattr(self.model, 'PREDICTION_KEYS', ())) | set(GAZE_EVENT_KEYS) | {'valid', 'eye_valid', 'pose_valid', 'rendered', 'heatmap_final'}
+        if gate is not None:
+            taken |= set(EYE_GATE_KEYS)
+        for h in history or ():
+            taken |= {h['spec'].name, h['spec'].name + '_frames'}
+        if aoi is not None:
+            taken |= {'%s_%s' % (aoi['spec'].name, k_) for k_ in AOI_KEYS}
+        if pupil is not None:
+            taken |= {'%s_%s' % (pupil['spec'].name, k_) for k_ in PUPIL_KEYS}
+        for key in spec.result_keys():
+            if key in taken or key in chunk:
+                raise ValueError('step: luminance: the name %r gives %s, which is a key of the chunk or of the step\'s result already' % (spec.name, key))
+        cfg, ref = self.model.config, self.model.refine_net
+        key = screen_frame_key(chunk)
+        if key is None:
+            raise ValueError('step: luminance reads the screen capture, and the chunk holds none (screen_frame, one of %s, or %s)' % (
+                ', '.join(k_ for k_ in SCREEN_FRAME_KEYS if k_ != 'screen_frame'), SCREEN_SURFACE_KEY))
+        frames = chunk[key]
+        net_hw = (int(cfg.screen_size[1]), int(cfg.screen_size[0]))
+        if key == 'screen_frame' and (not torch.is_tensor(frames) or frames.dtype != torch.uint8 or frames.dim() != 5 or
+                                      frames.shape[4] not in (3, 4) or tuple(frames.shape[2:4]) == net_hw):
+            raise ValueError('step: luminance needs a full-resolution uint8 capture [B, Tc, IH, IW, 3 | 4] to read; screen_frame is %s %s '
+                             '(a float or %d x %d screen_frame is the network\'s input, not a capture)' % (
+                                 getattr(frames, 'dtype', type(frames)), tuple(getattr(frames, 'shape', ())), net_hw[0], net_hw[1]))
+        try:
+            if key == SCREEN_SURFACE_KEY:
+                layout = None if ref is None else ref.screen_layout
+                if layout is None:
+                    raise ValueError('%s needs RefineNet.screen_layout, a data.SurfaceLayout that says how the capture lies in memory' % key)
+                surface_frames(frames, layout, 2, name=key)
+            else:
+                layout = capture_layout(frames, SCREEN_FRAME_KEYS[key], 2, name=key)
+        except (TypeError, ValueError) as e:
+            raise ValueError('step: luminance: %s' % e)
+        if tuple(frames.shape[:2]) != (B, Tc) or frames.device != self.device or not frames.is_contiguous():
+            raise ValueError('step: luminance: %s must be a contiguous [%d, %d, ...] tensor on %s, got %s on %s' % (
+                key, B, Tc, self.device, tuple(frames.shape), frames.device))
+        matrix = ref.yuv_matrix if ref is not None else 'bt601'
+        if matrix not in YUV_MATRICES:
+            raise ValueError('step: luminance: RefineNet.yuv_matrix must be one of %s, got %r' % (', '.join(YUV_MATRICES), matrix))
+        if spec.to_pupil is not None and 'pupil_luminance' in chunk:
+            raise ValueError('step: luminance: to_pupil makes the covariate the pupil stage\'s luminance, and the chunk brings pupil_luminance '
+                             'too: drop one of them (to_pupil=None keeps the chunk\'s)')
+        sx, sy = layout.width / float(cfg.actual_screen_size[0]), layout.height / float(cfg.actual_screen_size[1])
+        source, radii = None, ()
+        if spec.radii_px:
+            source = spec.source if spec.source is not None else 'PoG_px_' + self._output_stage()
+            if source == 'PoG_px_final' and ref is None:
+                raise ValueError('step: luminance follows PoG_px_final, which RefineNet produces, and the model has no RefineNet')
+            if source in ('PoG_px_filtered', 'fixation_px') and events is None:
+                raise ValueError('step: luminance follows %s, which the events stage produces: pass events= in the same step' % source)
+            if 'inv_camera_transformation' not in chunk:
+                raise ValueError('step: luminance follows %s, and the point of gaze needs the camera geometry (inv_camera_transformation) '
+                                 'in the chunk' % source)
+            radii = spec.capture_radii(sx, 'step: luminance')
+            vk = spec.valid_key
+            if vk is not None:
+                entry = chunk.get(vk)
+                known = (vk == 'fixating' and events is not None) or (vk == 'valid' and masked)
+                if entry is None and not known:
+                    raise ValueError('step: luminance: valid_key %r is neither in the chunk nor a [B, Tc] result of this step' % (vk,))
+                if entry is not None:
+                    self._check_chunk_tensor('luminance: valid_key %r' % (vk,), entry, (torch.bool, torch.uint8), (B, Tc), got=False)
+        table = self._luminance_tables.get(spec.key())
+        if table is None:                        # made here, before any capture: a host-to-device copy
+            table = self._luminance_tables[spec.key()] = spec.response_table().to(self.device)
+        return {'spec': spec, 'key': key, 'layout': layout, 'matrix': matrix, 'source': source, 'radii': radii, 'sx': sx, 'sy': sy, 'table': table}
+
     # ------------------------------------------------------------------ areas of interest
     def _aoi_entry(self, spec):
         """The carried buffers of spec.name, made at the first step that names it.  The tallies are tied to their spec."""
@@ -1323,8 +1420,8 @@ class EVEStream(object):
             self._pose_gate.fill_(self._pose_gate_host)              # a device value: the captured graphs read it, the host never waits
 
     def _run(self, chunk, return_heatmaps, ragged=False, eye_mask=None, masked=False, render=None, events=None, gate=None, history=None,
-             aoi=None, pupil=None):
-        """The one call of EVE._predict_sequence, eager or under capture.  render, events, gate, history, aoi, pupil: None or the plan of
+             aoi=None, pupil=None, luminance=None):
+        """The one call of EVE._predict_sequence, eager or under capture.  render, events, gate, history, aoi, pupil, luminance: None or the plan of
         that stage's check.  A stage's keyword goes along only when the stage runs, and lengths, the mask's keywords and face_state only
         on a ragged, a masked and a face-landmark step: a step without them makes the call it always made."""
         faced = face_landmarks_key(chunk) is not None
@@ -1343,6 +1440,8 @@ class EVEStream(object):
             kw['aoi'] = dict(aoi, **self._aoi_entry(aoi['spec'])['buffers']._asdict())
         if pupil is not None:
             kw['pupil'] = dict(pupil, **self._pupil_entry(pupil['spec'])['buffers']._asdict())
+        if luminance is not None:
+            kw['luminance'] = luminance
         if self._calib_apply or 'calibration_target' in chunk:       # (neither: the call an uncalibrated EVEStream always made)
             kw['calibration'] = {'kappa': self._calib_kappa, 'ok': self._calib_ok, 'apply': self._calib_apply,
                                  'store': self._store() if 'calibration_target' in chunk else None}
@@ -1497,7 +1596,7 @@ class EVEStream(object):
         return render
 
     def step(self, chunk, return_heatmaps=False, lengths=None, eye_mask=None, skip_invalid_pose=False, render=None, events=None, gate=None,
-             history=None, aoi=None, pupil=None):
+             history=None, aoi=None, pupil=None, luminance=None):
         """One chunk of every stream: chunk holds [B, Tc, ...] tensors on the model's device -- the eyes (below), {left,right}_h,
         {left,right}_o, {left,right}_R, head_R, camera_transformation, inv_camera_transformation, pixels_per_millimeter, millimeters_per_pixel, and screen_frame when the config loads screen content.  Returns the
         prediction keys of EVE(output_predictions=True) as [B, Tc, ...] tensors (heatmap_final [B, Tc, 1, H, W] on request).
@@ -1777,7 +1876,22 @@ class EVEStream(object):
         captured: a pupil that is no PupilSpec, a name whose keys collide with the chunk's or the result's, pupil_luminance or
         pupil_baseline of another shape, dtype or device, neither frame_time nor fps.  The spec by value and the presence of the two
         chunk keys are part of the graph's key; every other mode of the step combines with it.  tests/pupil_ref.py states the
-        arithmetic, exact to the bit.  pupil=None issues exactly the launches the step always issued."""
+        arithmetic, exact to the bit.  pupil=None issues exactly the launches the step always issued.
+        luminance: None, or an eve_amd.ScreenLuminanceSpec -- one eve_screen_luminance launch after the AOI stage and before the pupil
+        stage, inside the captured graph, reads the screen capture where it lies (the chunk tensor; under a graph, its input buffer):
+        every pixel through a tight SurfaceLayout of its key's format (screen_frame with four channels: 'rgba'; screen_surface through
+        model.refine_net.screen_layout), converted with refine_net.yuv_matrix ('bt601' without a RefineNet), linearised through the
+        spec's response table, weighted and summed in integers, over the whole screen and over discs of spec.radii_px around the
+        spec's source point.  The result gains <name> float32 [B, Tc], with radii <name>_gaze [B, Tc, R], and with to_pupil
+        <name>_covariate [B, Tc], which a pupil= stage of the same step takes as its luminance.  The whole-screen column follows
+        lengths only -- the screen does not care about the eyes --, the discs also the masked step's valid and the spec's valid_key;
+        what is not delivered, a disc without a valid centre and a disc off the screen are NaN, which the pupil stage ignores.
+        ValueErrors raised before anything is launched or captured: a luminance that is no ScreenLuminanceSpec, no capture in the
+        chunk, a float or network-size screen_frame, to_pupil together with pupil_luminance in the chunk, PoG_px_filtered or
+        fixation_px as the source without events=, a name whose keys collide with the chunk's or the result's, radii that fall
+        together at the capture's scale.  The spec by value is part of the graph's key; the stage carries no state.
+        tests/screen_luminance_ref.py states the arithmetic, exact to the bit.  luminance=None issues exactly the launches the step
+        always issued."""
         if self.model.training:
             raise ValueError('EVEStream runs inference only: the model was switched to training mode')
         B, Tc = eye_input(chunk).shape[:2]
@@ -1802,6 +1916,8 @@ class EVEStream(object):
             more['aoi'] = aoi = self._check_aoi(chunk, aoi, events, history, masked, B, Tc)
         if pupil is not None:
             more['pupil'] = pupil = self._check_pupil(chunk, pupil, events, history, aoi, gate, B, Tc)
+        if luminance is not None:
+            more['luminance'] = self._check_luminance(chunk, luminance, events, history, aoi, pupil, gate, masked, B, Tc)
         if render is not None:
             render = self._render_plan(chunk, render, events, history)
         self._check_calibration(chunk, B, Tc)
@@ -1856,7 +1972,7 @@ class EVEStream(object):
         return tuple(_module_key(m) for m in (self.model.eye_net, self.model.refine_net) if m is not None)
 
     def _graph_key(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None, aoi=None,
-                   pupil=None):
+                   pupil=None, luminance=None):
         """What a captured graph is good for: the step's mode, both YUV matrices, both surface layouts (by value), the overlay
         (render: None or a _render_plan -- its OverlaySpec by value), with a face-landmark form eye_net.face_huber_px (a launch
         argument, so baked in), the gaze events (events: None or a _check_events plan -- its GazeEventSpec by value and its source;
@@ -1864,7 +1980,9 @@ class EVEStream(object):
         eye_contours' presence and shape are a chunk key), the gaze history (history: None or _check_history's plans -- each GazeHistorySpec by
         value, its source and the launches' scalars, the config's defaults resolved), the areas of interest (aoi: None or a _check_aoi plan -- its
         AoiSpec by value, its source and whether fixations are counted; aoi_shapes' shape is a chunk key), the pupillometry (pupil: None or a
-        _check_pupil plan -- its PupilSpec by value; pupil_luminance's and pupil_baseline's presence are chunk keys), whether a calibration is applied (`calibrated`; a collecting step differs by its chunk keys), whether a screen-space map is applied (likewise), and every chunk tensor's key, shape and dtype -- which of the two landmark keys among them."""
+        _check_pupil plan -- its PupilSpec by value; pupil_luminance's and pupil_baseline's presence are chunk keys), the screen luminance
+        (luminance: None or a _check_luminance plan -- its ScreenLuminanceSpec by value and its source; the capture's shape is a chunk key and its
+        layout and matrix are RefineNet's), whether a calibration is applied (`calibrated`; a collecting step differs by its chunk keys), whether a screen-space map is applied (likewise), and every chunk tensor's key, shape and dtype -- which of the two landmark keys among them."""
         ref = self.model.refine_net
         spec = None if render is None else render['spec'].key()
         layouts = (self.model.eye_net.camera_layout, None if ref is None else ref.screen_layout)
@@ -1878,10 +1996,11 @@ class EVEStream(object):
             (() if history is None else (('history',) + tuple((h['spec'].key(), h['source'], tuple(sorted(h['P'].items(), key=lambda kv: kv[0])))
                                                                 for h in history),)) + \
             (() if aoi is None else (('aoi', aoi['spec'].key(), aoi['source'], aoi['use_fixations']),)) + \
-            (() if pupil is None else (('pupil', pupil['spec'].key()),)) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
+            (() if pupil is None else (('pupil', pupil['spec'].key()),)) + \
+            (() if luminance is None else (('luminance', luminance['spec'].key(), luminance['source']),)) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
 
     def _graph_for(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None, aoi=None,
-                   pupil=None):
+                   pupil=None, luminance=None):
         wk = self._weights_key()
         if wk != self._graphs_key:               # new weights: new packs, new graphs (a replay never reads stale packs)
             self._graphs = {}
@@ -1893,6 +2012,8 @@ class EVEStream(object):
             more['aoi'] = aoi
         if pupil is not None:
             more['pupil'] = pupil
+        if luminance is not None:
+            more['luminance'] = luminance
         key = self._graph_key(chunk, return_heatmaps, ragged, masked, render, events, **more)
         entry = self._graphs.get(key)
         if entry is None:
@@ -1902,7 +2023,7 @@ class EVEStream(object):
         return entry
 
     def _capture(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None, aoi=None,
-                 pupil=None):
+                 pupil=None, luminance=None):
         """Capture one step for this chunk shape (train.Trainer._capture's recipe): inputs copied into fixed buffers, two eager
         warm-up steps off the default stream (packs, lazily built filters, allocator) with the carried states put back
         afterwards, the kernels' scratch allocated before the capture, one stream, no side branches.  A masked graph has one more
@@ -1919,7 +2040,7 @@ class EVEStream(object):
             carried = self._carried()
             snap = [t.clone() for t in carried]
             for _ in range(2):
-                self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history, aoi, pupil)
+                self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history, aoi, pupil, luminance)
             for t, s_ in zip(carried, snap):
                 t.copy_(s_)
         torch.cuda.current_stream().wait_stream(side)
@@ -1929,7 +2050,7 @@ class EVEStream(object):
             k.prepare_graph_workspace(self.device)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            out = self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history, aoi, pupil)
+            out = self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history, aoi, pupil, luminance)
         m = self.model
         keep = (m.eye_net._packs, getattr(m.eye_net, '_stream_w', None), m.refine_net._packs if m.refine_net is not None else None)
         return {'graph': graph, 'inputs': static, 'outputs': out, 'keep': keep, 'eye_mask': eye_mask}

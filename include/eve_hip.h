@@ -1492,9 +1492,10 @@ int eve_gaze_aoi(long long B, int T, int A, const float* pog, const float* shape
  * Refused without a launch: a null carried buffer, B < 1, T < 0, capacity < 1, with T > 0 a null size or output, index products past
  * 31 bits, min_mm or max_mm not a finite number > 0 or min_mm >= max_mm, offset_rate outside (0, 1], max_speed_mm_s, max_gap_s,
  * cutoff_hz, light_tau_s, dilate_mm_s or constrict_mm_s not a finite number > 0, baseline_tau_s or min_amplitude_mm not a finite
- * number >= 0, fps not a finite number > 0 where frame_time is NULL and T > 0.  Not offered: luminance computed from the screen
- * capture (the covariate comes from the caller), non-causal blink padding and interpolation across gaps, foreshortening correction,
- * per-eye filtered traces, wavelet indices (IPA / LHIPA), per-fixation or per-AOI pupil means, a gradient.  (Additive: ABI v10.)   */
+ * number >= 0, fps not a finite number > 0 where frame_time is NULL and T > 0.  The covariate comes from the caller; eve_screen_luminance
+ * below computes one from the screen capture.  Not offered: non-causal blink padding and interpolation across gaps, foreshortening
+ * correction, per-eye filtered traces, wavelet indices (IPA / LHIPA), per-fixation or per-AOI pupil means, a gradient.
+ * (Additive: ABI v10.)                                                                                                            */
 int eve_pupil_track(long long B, int T, const float* size, const uint8_t* eye_valid /* may be NULL */,
                     const double* frame_time /* may be NULL */, const int* lengths /* may be NULL */, const int* reset /* may be NULL */,
                     const int* flush /* may be NULL */, const float* luminance /* may be NULL */,
@@ -1503,6 +1504,45 @@ int eve_pupil_track(long long B, int T, const float* size, const uint8_t* eye_va
                     double constrict_mm_s, double min_amplitude_mm, double* state, double* table, double* light, int capacity, double* store,
                     int* count, int* dropped, float* mm, float* raw_mm, float* velocity, float* change_mm, float* change_pct, uint8_t* valid,
                     uint8_t* eye_used, uint8_t* eye_reason, uint8_t* event, eve_stream_t stream);
+
+/* Screen luminance: the mean relative luminance of every delivered screen capture, over the whole visible region and over up to
+ * four concentric discs around a per-frame centre (the point of gaze) -- the light covariate of the pupil trace, computed per
+ * pixel at capture resolution from the surface where it lies, for B streams x T frames, frame n = b * T + f.  Everything is integer
+ * arithmetic up to one float64 division, so the device equals numpy bit for bit (tests/screen_luminance_ref.py) and the grid, the
+ * order of the sums and any split into bands do not change the result.
+ *   Per visible pixel the three 8-bit values (R, G, B) are read through the surface's address rule (eve_surface above) and, for
+ *   EVE_SURF_YUV, converted exactly as eve_screen_area_surface_to_nchw converts a pixel (the integer matrix, nearest chroma sample,
+ *   clamps).  Then y = (kr * response[0][R] + kg * response[1][G] + kb * response[2][B] + 32768) >> 16 in 32 unsigned bits, 0 .. 65535:
+ *   response [3][256] uint16 on the device is the display's linearisation (sRGB's EOTF scaled to 65535, a power law or a measured
+ *   curve), and kr, kg, kb >= 0 with kr + kg + kb == 65536 weigh the channels -- Rec.709: (13933, 46871, 4732) -- so the sum fits.
+ *   Frame n is DELIVERED iff lengths == NULL or f < clamp(lengths[b], 0, T).  An undelivered frame has every column 0 (mean NaN), and
+ *   its bytes are not read.
+ *   Column 0 is every visible pixel: sums[n][0] = sum of y, counts[n][0] = width * height.  Columns 1 .. R are the discs of radius
+ *   radii[k] capture pixels (a HOST array [R] read during the call; 1 .. 16384, strictly increasing) around the frame's centre,
+ *   quantised the overlay's way, in half pixels: qx = rint((centres[n][0] * sx) * 2) in float32, each product rounded, ties to even,
+ *   qy likewise with sy.  Pixel (X, Y) lies in disc k iff (2X + 1 - qx)^2 + (2Y + 1 - qy)^2 <= 4 r_k^2 in 64-bit integers; counts is
+ *   the number of VISIBLE pixels in the disc, so a disc that hangs off the edge counts what is on screen.  A frame's disc columns are
+ *   0 where centre_valid[n] == 0 (uint8 [B*T], NULL: every centre valid), a coordinate is not finite, or |qx| or |qy| > 2^20.  No
+ *   address is ever computed from a centre.
+ *   mean[n][k] = (float)((double)sums / ((double)counts * 65535.0)): a zero count gives NaN.
+ * The call zeroes sums and counts on the stream (capturable), then one workgroup per (frame, band of 32 rows) adds its 1 + R pairs
+ * with integer atomics -- 8-bit 4:2:0 keeps eve_screen_area_surface_to_nchw's wide loads under the same conditions, or its byte
+ * form; every other descriptor three byte loads per pixel -- and a second small kernel writes mean.  Kernel names (eve_last_kernel
+ * names the form that read the frames): screen_luminance_kernel<yuv420,true | false> and screen_luminance_kernel<generic,false>; the
+ * second kernel is screen_luminance_finish_kernel.  Refused without a launch, the message beginning "screen_luminance:": B < 1 or
+ * T < 1, R outside 0 .. 4, B * T * (1 + R) >= 2^31, what eve_eye_warp_surface_to_nchw refuses of the descriptor, width or height >
+ * 16384, a null src, response or output, weights that are negative or do not sum to 65536, radii outside 1 .. 16384 or not strictly
+ * increasing, radii or centres without R > 0 or R > 0 without them, sx or sy not a finite number > 0.  Not offered: continuous
+ * (eccentricity-weighted) kernels beyond concentric discs, per-AOI luminance, 10-bit arithmetic (P010 is read as its high byte),
+ * ambient light, the camera image's luminance, a gradient.  (Additive: ABI v10.)                                                 */
+int eve_screen_luminance(const eve_surface* surface, int matrix, long long B, int T, const uint8_t* src,
+                         const uint16_t* response /* device, [3][256] */, int kr, int kg, int kb,
+                         const int* lengths /* device [B], may be NULL */,
+                         int R, const int* radii /* HOST array [R], read during the call; NULL iff R == 0 */,
+                         const float* centres /* device [B*T][2], NULL iff R == 0 */, float sx, float sy,
+                         const uint8_t* centre_valid /* device [B*T], may be NULL */,
+                         unsigned long long* sums /* [B*T][1+R] */, int* counts /* [B*T][1+R] */, float* mean /* [B*T][1+R] */,
+                         eve_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,7 @@ three routes interleaved in one process:
 
     python tools/bench_screen_resize.py [--sizes 1920x1080 2560x1440] [--frames 1 32 240] [--channels 3] [--iters 20] [--rounds 5]
                                         [--markdown profiles/table.md] [--format rgb|bgr|nv12|i420|yuyv] [--surface]
+                                        [--luminance [--radii 60,200]]
 
 One JSON line per (size, N): per route the median over the rounds of the device time per call (events around `iters` calls), and
 for `area` and `clone` the rate N*IH*IW*C / time as a fraction of the 8 TB/s HBM peak (`clone` moves twice those bytes).  Every
@@ -30,7 +31,17 @@ One JSON line per (size, N) with each route's median, minimum and maximum over t
     linear       HipKernels.screen_area_fmt_to_nchw on the linearised NV12 frames: the launch the new one stands beside
     surface      HipKernels.screen_area_surface_to_nchw on the padded buffer (NV12: the vector form; P010: the generic form)
     copy+linear  what a caller had before: a torch de-pitch copy (P010: the high bytes) into byte-linear NV12, then `linear`;
-                 copy_only is that pass alone"""
+                 copy_only is that pass alone
+
+--luminance measures eve_screen_luminance (csrc/screen_luminance.hip) on --format rgb | nv12 | i420 | yuyv frames, or with --surface on
+NV12 in rows of 2048 bytes and 1088 coded rows, beside the resize of the SAME frames through the same SurfaceLayout, the two
+interleaved round by round in one process:
+
+    resize      HipKernels.screen_area_surface_to_nchw(buf, (72, 128), layout): the launch the new one stands beside
+    luminance   HipKernels.screen_luminance(buf, layout, ...): two memsets, the kernel and the finish kernel; --radii 60,200 adds discs
+                around random centres on the screen
+
+`bytes` is what the address rule names (the visible pixels' samples), and the rates are bytes / time over 8 TB/s."""
 import argparse
 import json
 import os
@@ -149,6 +160,59 @@ def bench_surface(args, k):
                 torch.cuda.empty_cache()
 
 
+def bench_luminance(args, k):
+    """The --luminance measurement: one JSON line per (size, N)."""
+    sys.path.insert(0, os.path.join(REPO, 'tools'))
+    from bench_eye_warp import format_frames, surface_pair
+    from eve_amd.data import SurfaceLayout, display_response
+    from eve_amd.kernels import LUM_REC709
+    radii = tuple(int(v) for v in args.radii.split(',')) if args.radii else ()
+    table = display_response().cuda()
+    for size in args.sizes:
+        IW, IH = (int(v) for v in size.lower().split('x'))
+        for N in args.frames:
+            torch.manual_seed(N + IW)
+            if args.surface:
+                fmt = 'nv12'
+                L, first, _ = surface_pair('nv12', (N,), IH, IW, 2048, 1088)
+                make = lambda: surface_pair('nv12', (N,), IH, IW, 2048, 1088)[1]
+            else:
+                fmt = args.format
+                L = SurfaceLayout(fmt, IW, IH)
+                make = (lambda: torch.randint(0, 256, (N, IH, IW, 3), dtype=torch.uint8, device='cuda')) if fmt == 'rgb' else \
+                    (lambda: format_frames(fmt, (N,), IH, IW))
+                first = make()
+            nbytes = N * IH * IW * {'rgb': 6, 'nv12': 3, 'i420': 3, 'yuyv': 4}[fmt] // 2
+            copies = max(2, min(64, -(-ROTATE_BYTES // first.numel())))
+            bufs = [first, make()]
+            bufs += [bufs[i % 2].clone() for i in range(copies - 2)]
+            bufs = [b.reshape(N, -1) for b in bufs]
+            centres = (torch.rand((N, 2), device='cuda') * torch.tensor([IW, IH], device='cuda')).contiguous() if radii else None
+            routes = {'resize': lambda i: k.screen_area_surface_to_nchw(bufs[i % copies], OUT_HW, L),
+                      'luminance': lambda i: k.screen_luminance(bufs[i % copies], L, table, LUM_REC709, N, 1, radii=radii, centres=centres)}
+            with torch.no_grad():
+                for fn in routes.values():               # warm up: code objects, allocator
+                    for i in range(3):
+                        fn(i)
+                torch.cuda.synchronize()
+                times = {name: [] for name in routes}
+                for _ in range(args.rounds):
+                    for name, fn in routes.items():
+                        times[name].append(device_ms(fn, args.iters))
+            res = {'size': size, 'N': N, 'format': fmt, 'surface': bool(args.surface), 'pitch': L.pitch, 'radii': list(radii), 'bytes': nbytes,
+                   'buffer_bytes': first.numel(), 'captures_rotated': copies}
+            for name, t in times.items():
+                res[name + '_us'] = round(1e3 * sorted(t)[len(t) // 2], 2)
+                res[name + '_us_min_max'] = [round(1e3 * min(t), 2), round(1e3 * max(t), 2)]
+                res[name + '_frac_of_8TBps'] = round(nbytes / (1e-6 * res[name + '_us']) / HBM_PEAK, 4)
+            res['luminance_over_resize'] = round(res['luminance_us'] / res['resize_us'], 3)
+            routes['luminance'](0)
+            res['kernel'] = k.lib.eve_last_kernel().decode()
+            print(json.dumps(res), flush=True)
+            del bufs, routes, first
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--sizes', nargs='+', default=['1920x1080', '2560x1440'])
@@ -159,10 +223,16 @@ def main():
     ap.add_argument('--markdown', default=None, help='also write the table to this file')
     ap.add_argument('--format', default='rgb', choices=('rgb', 'bgr', 'nv12', 'i420', 'yuyv'), help='the capture\'s layout (see above)')
     ap.add_argument('--surface', action='store_true', help='measure eve_screen_area_surface_to_nchw on padded NV12 / P010 surfaces instead (see above)')
+    ap.add_argument('--luminance', action='store_true', help='measure eve_screen_luminance beside the resize of the same frames (see above)')
+    ap.add_argument('--radii', default='', help='with --luminance: disc radii in capture pixels, e.g. 60,200')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit('bench_screen_resize: no GPU (a time is only measured on one)')
     k = default_kernels()
+    if args.luminance:
+        if args.format == 'bgr':
+            ap.error('--luminance takes --format rgb, nv12, i420 or yuyv, or --surface')
+        return bench_luminance(args, k)
     if args.surface:
         return bench_surface(args, k)
     if args.format in ('nv12', 'i420', 'yuyv'):

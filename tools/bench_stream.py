@@ -188,8 +188,12 @@ def main():
     ap.add_argument('--events', action='store_true', help='step with events=GazeEventSpec(fps=30): the gaze filter and the fixation / saccade events')
     ap.add_argument('--face', action='store_true', help='feed the face-landmark form (camera frames, landmarks, face_rig) in place of pre-cut patches')
     ap.add_argument('--gate', action='store_true', help='step with gate=EyeGateSpec(...), every criterion on (implies --face)')
+    ap.add_argument('--luminance', action='store_true', help='step with luminance=ScreenLuminanceSpec(radii_px=(60, 200)) feeding pupil=, against '
+                    'the same step with pupil= and an uploaded pupil_luminance (needs --screen)')
     args = ap.parse_args()
     args.face = args.face or args.gate
+    if args.luminance and (not args.screen or args.ragged or args.masked or args.events or args.gate or args.render):
+        ap.error('--luminance measures the uniform step on a capture: give it with --screen WxH alone')
     if args.gate and (args.ragged or args.masked or args.events):
         ap.error('--gate measures the gated step against the masked one itself: give it alone')
     if args.screen_format != 'rgb' and not args.screen:
@@ -259,6 +263,21 @@ def main():
                 plain_runs.append(round(device_ms(plain_step, args.steps), 4))
                 runs.append(round(device_ms(step, args.steps), 4))
             runs, plain_runs = sorted(runs), sorted(plain_runs)
+        elif args.luminance:                                 # pupil= with an uploaded covariate (what a caller had before), alternating
+            pupil = eve_amd.PupilSpec(fps=30)
+            lum_spec = eve_amd.ScreenLuminanceSpec(radii_px=(60, 200), to_pupil=(0.5, 0.0, 0.5))
+            uploaded = dict(clip, pupil_luminance=torch.rand((B, Tc), device='cuda'))
+            step = lambda: stream.step(clip, luminance=lum_spec, pupil=pupil)
+            plain_step = lambda: stream.step(uploaded, pupil=pupil)
+            for _ in range(3):
+                step()
+                plain_step()
+            torch.cuda.synchronize()
+            runs = []
+            for _ in range(max(1, args.repeat)):
+                plain_runs.append(round(device_ms(plain_step, args.steps), 4))
+                runs.append(round(device_ms(step, args.steps), 4))
+            runs, plain_runs = sorted(runs), sorted(plain_runs)
         elif args.gate:                                      # the same chunk's masked step, in windows that alternate with the timed ones
             masked_step = lambda: stream.step(clip, eye_mask=rng.random((B, Tc, 2)) >= 0.2, **extra)
             for _ in range(3):
@@ -288,6 +307,10 @@ def main():
                 res['plain_step_ms_runs'] = plain_runs
             res['events_kernel_us'] = events_kernel_us(clip, {k_: v.clone() for k_, v in step().items()}, extra['events'])
             res['launch_floor_us'] = launch_floor_us()
+        if args.luminance:
+            res['luminance'], res['uploaded_step_ms'] = True, plain_runs[len(plain_runs) // 2]
+            res['luminance_delta_us'] = round(1e3 * (res['step_ms'] - res['uploaded_step_ms']), 2)
+            res['uploaded_step_ms_runs'] = plain_runs
         if args.face:
             res['face'] = True
         if args.gate:
