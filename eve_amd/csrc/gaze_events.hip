@@ -10,7 +10,7 @@
 //   2  parallel   lane t forms its gaze vector, finds its predecessor sample -- the highest set bit below t in the wave's ballot of
 //                 the sample flags, the carried vector for the pass's first sample -- and computes the angle (sqrt, atan2) and velocity
 //   3  serial     lane 0: the I-VT state machine, the running fixation's sums, the store appends, the per-frame results into LDS
-//   4  parallel   lane t writes frame t's seven outputs
+//   4  parallel   lane t writes frame t's seven outputs, and for eve_gaze_events_ex its sample flag, time and gaze vector
 // The float64 atan2 is the one long dependency chain, and phase 2 keeps it off the serial path.  Float64 throughout, every operation
 // rounded on its own: the bits do not depend on this structure.  Every branch around a barrier or a ballot is uniform over the wave.
 #include "common.h"
@@ -71,7 +71,9 @@ __global__ __launch_bounds__(GE_WAVE) void gaze_events_kernel(const int T, const
                                                               int* __restrict__ dropped, float* __restrict__ filtered,
                                                               float* __restrict__ velocity, uint8_t* __restrict__ event,
                                                               int* __restrict__ fixation_id, float* __restrict__ fixation_px,
-                                                              float* __restrict__ fixation_ms, uint8_t* __restrict__ fixating) {
+                                                              float* __restrict__ fixation_ms, uint8_t* __restrict__ fixating,
+                                                              uint8_t* __restrict__ sample, double* __restrict__ sample_time,
+                                                              double* __restrict__ gaze_vector) {      // the last three: NULL, or _ex's
 #pragma clang fp contract(off)
     __shared__ double st[GE_STATE];
     __shared__ double s_x[GE_WAVE], s_y[GE_WAVE], s_sx[GE_WAVE], s_sy[GE_WAVE], s_e[3][GE_WAVE], s_tt[GE_WAVE], s_dt[GE_WAVE];
@@ -276,6 +278,13 @@ __global__ __launch_bounds__(GE_WAVE) void gaze_events_kernel(const int T, const
             fixation_px[n * 2 + 1] = (float)s_fy[lane];
             fixation_ms[n] = (float)s_ms[lane];
             fixating[n] = s_fixating[lane];
+            if (sample) sample[n] = (uint8_t)flag;
+            if (sample_time) sample_time[n] = flag != 0 ? s_tt[lane] : 0.0;
+            if (gaze_vector) {
+                gaze_vector[n * 3] = flag != 0 ? s_v[0][lane] : 0.0;
+                gaze_vector[n * 3 + 1] = flag != 0 ? s_v[1][lane] : 0.0;
+                gaze_vector[n * 3 + 2] = flag != 0 ? s_v[2][lane] : 0.0;
+            }
         }
         __syncthreads();
     }
@@ -296,12 +305,13 @@ __host__ bool ge_positive(const double x) { return x > 0.0 && x <= 1.79769313486
 
 using namespace eve;
 
-extern "C" int eve_gaze_events(long long B, int T, const float* pog, const float* origin, const float* inv_cam, const float* ppm,
-                               const double* frame_time, const uint8_t* valid, const int* lengths, const int* reset, const int* flush, double fps,
-                               double min_cutoff_hz, double beta, double d_cutoff_hz, int velocity_from_raw, double saccade_deg_s,
-                               double min_fixation_s, double max_gap_s, double* state, int F, double* store, int* count, int* dropped,
-                               float* filtered, float* velocity, uint8_t* event, int* fixation_id, float* fixation_px, float* fixation_ms,
-                               uint8_t* fixating, eve_stream_t stream) {
+// Both entries: the checks and the one launch.  sample, sample_time and gaze_vector: each NULL or eve_gaze_events_ex's output.
+static int ge_launch(long long B, int T, const float* pog, const float* origin, const float* inv_cam, const float* ppm, const double* frame_time,
+                     const uint8_t* valid, const int* lengths, const int* reset, const int* flush, double fps, double min_cutoff_hz, double beta,
+                     double d_cutoff_hz, int velocity_from_raw, double saccade_deg_s, double min_fixation_s, double max_gap_s, double* state,
+                     int F, double* store, int* count, int* dropped, float* filtered, float* velocity, uint8_t* event, int* fixation_id,
+                     float* fixation_px, float* fixation_ms, uint8_t* fixating, uint8_t* sample, double* sample_time, double* gaze_vector,
+                     eve_stream_t stream) {
     const char* why = nullptr;
     if (B <= 0 || T < 0 || F <= 0 || !state || !store || !count || !dropped) why = "bad arguments";
     else if (T > 0 && (!pog || !origin || !inv_cam || !ppm || !filtered || !velocity || !event || !fixation_id || !fixation_px || !fixation_ms ||
@@ -330,7 +340,30 @@ extern "C" int eve_gaze_events(long long B, int T, const float* pog, const float
     P.raw = velocity_from_raw ? 1 : 0;
     EVE_LAUNCH("gaze_events_kernel", gaze_events_kernel, dim3((unsigned)B), dim3(GE_WAVE), 0, (hipStream_t)stream, T, pog, origin, inv_cam, ppm,
                frame_time, valid, lengths, reset, flush, P, state, F, store, count, dropped, filtered, velocity, event, fixation_id, fixation_px,
-               fixation_ms, fixating);
+               fixation_ms, fixating, sample, sample_time, gaze_vector);
     EVE_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int eve_gaze_events(long long B, int T, const float* pog, const float* origin, const float* inv_cam, const float* ppm,
+                               const double* frame_time, const uint8_t* valid, const int* lengths, const int* reset, const int* flush, double fps,
+                               double min_cutoff_hz, double beta, double d_cutoff_hz, int velocity_from_raw, double saccade_deg_s,
+                               double min_fixation_s, double max_gap_s, double* state, int F, double* store, int* count, int* dropped,
+                               float* filtered, float* velocity, uint8_t* event, int* fixation_id, float* fixation_px, float* fixation_ms,
+                               uint8_t* fixating, eve_stream_t stream) {
+    return ge_launch(B, T, pog, origin, inv_cam, ppm, frame_time, valid, lengths, reset, flush, fps, min_cutoff_hz, beta, d_cutoff_hz,
+                     velocity_from_raw, saccade_deg_s, min_fixation_s, max_gap_s, state, F, store, count, dropped, filtered, velocity, event,
+                     fixation_id, fixation_px, fixation_ms, fixating, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int eve_gaze_events_ex(long long B, int T, const float* pog, const float* origin, const float* inv_cam, const float* ppm,
+                                  const double* frame_time, const uint8_t* valid, const int* lengths, const int* reset, const int* flush,
+                                  double fps, double min_cutoff_hz, double beta, double d_cutoff_hz, int velocity_from_raw,
+                                  double saccade_deg_s, double min_fixation_s, double max_gap_s, double* state, int F, double* store,
+                                  int* count, int* dropped, float* filtered, float* velocity, uint8_t* event, int* fixation_id,
+                                  float* fixation_px, float* fixation_ms, uint8_t* fixating, uint8_t* sample, double* sample_time,
+                                  double* gaze_vector, eve_stream_t stream) {
+    return ge_launch(B, T, pog, origin, inv_cam, ppm, frame_time, valid, lengths, reset, flush, fps, min_cutoff_hz, beta, d_cutoff_hz,
+                     velocity_from_raw, saccade_deg_s, min_fixation_s, max_gap_s, state, F, store, count, dropped, filtered, velocity, event,
+                     fixation_id, fixation_px, fixation_ms, fixating, sample, sample_time, gaze_vector, stream);
 }

@@ -980,6 +980,137 @@ def gaze_events(pog_px, o, inv_camera_transformation, pixels_per_millimeter, spe
     return out
 
 
+SACCADE_KEYS = ('saccade_id', 'saccade_ms')      # the per-frame results of the saccade stage
+SACCADE_STATE = 32                               # doubles per stream of eve_gaze_saccades' state row
+SACCADE_ROW = 16                                 # ... of its table row and of a stored saccade
+SACCADE_COLUMNS = ('id', 't_onset', 't_landing', 'n', 'x0', 'y0', 'x1', 'y1', 'amplitude_deg', 'peak_deg_s', 'mean_deg_s',
+                   'prev_fixation_id', 'next_fixation_id', 'missing')
+SACCADE_TABLE = ('accepted', 'sum_amp', 'sum_amp2', 'sum_peak', 'sum_amp_peak', 'sum_dur', 'sum_amp_dur', 'max_amp', 'max_peak', 'aborted',
+                 'small', 'short', 'long', 'interrupted')
+
+
+class SaccadeSpec(object):
+    """What EVEStream.step(chunk, events=..., saccades=spec) adds after the events stage (eve_gaze_saccades): the runs of saccade frames
+    become events with amplitude, duration, peak and mean velocity and the ids of the fixations on either side, in the EVEStream's
+    store, with a table of tallies (the sums behind the main sequence: main_sequence()).
+      min_amplitude_deg   a saccade whose onset and landing gaze vectors are less than this apart is tallied `small` and not stored
+      min_duration_s      one shorter than this (onset to landing) is tallied `short`
+      max_duration_s      one longer than this is tallied `long` (0.2 s: above any physiological saccade)
+      max_missing         one with more frames that were no sample inside it is tallied `interrupted`
+    The amplitude is that of the point the velocity is from: with GazeEventSpec(velocity_from='filtered'), the default, the
+    one-euro filter's lag shortens it; 'raw' gives the source's.  Instances compare and hash by value: the spec is part of a captured
+    graph's key.  Not offered: direction angles (the endpoints are there), curvature or path length, glissades and post-saccadic
+    oscillation, microsaccades, smooth pursuit, per-eye saccades, retroactive merging, gradients, EVE.forward."""
+
+    def __init__(self, min_amplitude_deg=0.5, min_duration_s=0.0, max_duration_s=0.2, max_missing=0):
+        number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and np.isfinite(v)
+        for name, v in (('min_amplitude_deg', min_amplitude_deg), ('min_duration_s', min_duration_s)):
+            if not number(v) or v < 0:
+                raise ValueError('SaccadeSpec: %s must be a finite number >= 0, got %r' % (name, v))
+        if not number(max_duration_s) or not max_duration_s > 0:
+            raise ValueError('SaccadeSpec: max_duration_s must be a finite number > 0, got %r' % (max_duration_s,))
+        if isinstance(max_missing, bool) or not isinstance(max_missing, (int, np.integer)) or not 0 <= max_missing <= 0x7fffffff:
+            raise ValueError('SaccadeSpec: max_missing must be an integer >= 0, got %r' % (max_missing,))
+        self.min_amplitude_deg, self.min_duration_s, self.max_duration_s = float(min_amplitude_deg), float(min_duration_s), float(max_duration_s)
+        self.max_missing = int(max_missing)
+
+    def key(self):
+        return (self.min_amplitude_deg, self.min_duration_s, self.max_duration_s, self.max_missing)
+
+    def __eq__(self, other):
+        return isinstance(other, SaccadeSpec) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'SaccadeSpec(min_amplitude_deg=%r, min_duration_s=%r, max_duration_s=%r, max_missing=%r)' % self.key()
+
+
+def saccade_buffers(S, capacity, device):
+    """-> (state float64 [S, 32], table float64 [S, 16], store float64 [S, capacity, 16], count and dropped int32 [S]) of S streams
+    that have seen nothing: what eve_gaze_saccades carries (include/eve_hip.h has the rows)."""
+    z = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=device)
+    return (z((S, SACCADE_STATE), torch.float64), z((S, SACCADE_ROW), torch.float64), z((S, capacity, SACCADE_ROW), torch.float64),
+            z((S,), torch.int32), z((S,), torch.int32))
+
+
+def saccade_stage(k, pog, res, spec, saccade_spec, buffers, lengths=None, reset=None):
+    """The one eve_gaze_saccades launch behind EVEStream.step and gaze_saccades: k the kernels, pog the events' source point [B, T, 2],
+    res gaze_events_ex's result, buffers the five carried tensors -> the two per-frame keys.  The point is the one the velocity is
+    from."""
+    point = pog if spec.velocity_from == 'raw' else res['PoG_px_filtered']
+    return k.gaze_saccades(res['sample'], res['sample_time'], res['gaze_vector'], point, res['gaze_event'], res['gaze_velocity'],
+                           res['fixation_id'], saccade_spec, *buffers, lengths=lengths, reset=reset)
+
+
+def gaze_saccades(pog_px, o, inv_camera_transformation, pixels_per_millimeter, spec, saccade_spec, frame_time=None, valid=None,
+                  saccade_capacity=256):
+    """The fixation / saccade events AND the saccades of S recorded streams, stand-alone and from fresh state: gaze_events' arguments
+    (spec a GazeEventSpec) plus saccade_spec, a SaccadeSpec.  One eve_gaze_events_ex and one eve_gaze_saccades launch.  -> the seven
+    per-frame keys of the events, saccade_id int32 [S, T] (-1 outside a saccade) and saccade_ms float32 [S, T], plus saccades
+    (float64 [S, saccade_capacity, 16], rows SACCADE_COLUMNS: id, t_onset, t_landing, n, x0, y0, x1, y1, amplitude_deg, peak_deg_s,
+    mean_deg_s, prev_fixation_id, next_fixation_id, missing, 0, 0), saccade_count and saccade_dropped (int32 [S]) and saccade_table
+    (float64 [S, 16], entries SACCADE_TABLE; main_sequence() reads it); the host does not wait.  A saccade still open at the clip's
+    end has no landing and is not stored.  Not offered: see SaccadeSpec."""
+    if not isinstance(spec, GazeEventSpec):
+        raise ValueError('gaze_saccades: spec must be an eve_amd.GazeEventSpec, got %s' % type(spec).__name__)
+    if not isinstance(saccade_spec, SaccadeSpec):
+        raise ValueError('gaze_saccades: saccade_spec must be an eve_amd.SaccadeSpec, got %s' % type(saccade_spec).__name__)
+    if not torch.is_tensor(pog_px) or pog_px.dtype != torch.float32 or pog_px.dim() != 3 or pog_px.shape[2] != 2 or pog_px.numel() == 0:
+        raise TypeError('gaze_saccades: pog_px must be float32 [S, T, 2], got %s %s' % (getattr(pog_px, 'dtype', type(pog_px)),
+                                                                                       tuple(getattr(pog_px, 'shape', ()))))
+    S, T = pog_px.shape[:2]
+    for name, t, shape in (('o', o, (S, T, 3)), ('inv_camera_transformation', inv_camera_transformation, (S, T, 4, 4)),
+                           ('pixels_per_millimeter', pixels_per_millimeter, (S, T, 2))):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != shape:
+            raise TypeError('gaze_saccades: %s must be float32 %s, got %s %s' % (name, list(shape), getattr(t, 'dtype', type(t)),
+                                                                                tuple(getattr(t, 'shape', ()))))
+    if frame_time is None and spec.fps is None:
+        raise ValueError('gaze_saccades: frame_time, or a spec with fps')
+    if frame_time is not None and (not torch.is_tensor(frame_time) or frame_time.dtype != torch.float64 or tuple(frame_time.shape) != (S, T)):
+        raise TypeError('gaze_saccades: frame_time must be float64 [%d, %d] seconds' % (S, T))
+    if valid is not None:
+        valid = _bool_rows(valid, (S, T), 'gaze_saccades: valid')
+    if isinstance(saccade_capacity, bool) or not isinstance(saccade_capacity, (int, np.integer)) or saccade_capacity < 1:
+        raise ValueError('gaze_saccades: saccade_capacity must be an integer >= 1, got %r' % (saccade_capacity,))
+    dev = pog_px.device
+    k = default_kernels()
+    z = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)
+    pog_px = pog_px.contiguous()
+    # (the fixation store is not returned -- gaze_events has it -- so one row per stream does)
+    res = k.gaze_events_ex(pog_px, o.contiguous(), inv_camera_transformation.contiguous(), pixels_per_millimeter.contiguous(), spec,
+                           z((S, 32), torch.float64), z((S, 1, 8), torch.float64), z((S,), torch.int32), z((S,), torch.int32),
+                           frame_time=None if frame_time is None else frame_time.contiguous(), valid=valid)
+    buffers = saccade_buffers(S, int(saccade_capacity), dev)
+    out = {k_: res[k_] for k_ in GAZE_EVENT_KEYS}
+    out.update(saccade_stage(k, pog_px, res, spec, saccade_spec, buffers))
+    out.update(saccades=buffers[2], saccade_count=buffers[3], saccade_dropped=buffers[4], saccade_table=buffers[1])
+    return out
+
+
+def main_sequence(table):
+    """The main sequence from the saccade table's sums, on the host in numpy: table float64 [S, 16] or [16] (EVEStream.saccade_table(),
+    gaze_saccades()['saccade_table']; a tensor is copied to the host, which waits) -> a dict of float64 [S] (or scalars): n, the two
+    least-squares lines duration_s = duration_intercept + duration_slope * amplitude_deg and peak_deg_s = peak_intercept + peak_slope *
+    amplitude_deg over the accepted saccades, mean_amplitude_deg, max_amplitude_deg and max_peak_deg_s.  The four coefficients are NaN
+    with fewer than 2 saccades or no spread in amplitude."""
+    t = table.detach().cpu().numpy() if torch.is_tensor(table) else np.asarray(table)
+    t = np.asarray(t, dtype=np.float64)
+    if t.shape[-1:] != (SACCADE_ROW,) or t.ndim not in (1, 2):
+        raise ValueError('main_sequence: table must be [S, 16] or [16], got %s' % (t.shape,))
+    n, sa, saa, sp, sap, sd, sad = (t[..., i] for i in range(7))
+    with np.errstate(all='ignore'):
+        det = n * saa - sa * sa
+        good = (n >= 2) & (det > 1e-12 * (n * saa))      # (equal amplitudes leave rounding noise, not a spread)
+        det = np.where(good, det, np.nan)
+        d_slope, p_slope = (n * sad - sa * sd) / det, (n * sap - sa * sp) / det
+        out = {'n': n.copy(), 'duration_slope': d_slope, 'duration_intercept': (sd - d_slope * sa) / n, 'peak_slope': p_slope,
+               'peak_intercept': (sp - p_slope * sa) / n, 'mean_amplitude_deg': np.where(n > 0, sa / n, np.nan),
+               'max_amplitude_deg': t[..., 7].copy(), 'max_peak_deg_s': t[..., 8].copy()}
+    return out
+
+
 GAZE_HISTORY_SOURCES = ('PoG_px_initial', 'PoG_px_final', 'PoG_px_filtered', 'fixation_px', 'heatmap_final')
 GAZE_HISTORY_MAX_AXIS = 2048
 

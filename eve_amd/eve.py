@@ -366,7 +366,7 @@ class EVE(nn.Module):
 
     def _predict_sequence(self, d, eye_states, refine_states, reset=None, return_heatmaps=False, lengths=None, masked=False,
                           eye_mask=None, pose_gate=None, face_state=None, render=None, calibration=None, events=None, gate=None,
-                          screen_calibration=None, history=None, aoi=None, pupil=None, luminance=None):
+                          screen_calibration=None, history=None, aoi=None, pupil=None, luminance=None, saccades=None):
         """The prediction part of forward() for one chunk of an EVEStream: eval only, no labels, no losses.  d: the chunk's
         inputs [B, Tc, ...] (not modified; camera_frame may be any one key of eye_net.EYE_FRAME_KEYS or camera_surface, and the screen any one
         key of refine_net.SCREEN_FRAME_KEYS or screen_surface; the eyes as patches, as camera_frame + {left,right}_eye_warp, or as camera_frame +
@@ -438,7 +438,12 @@ class EVE(nn.Module):
         'sy', 'table': the response table on the device}: one eve_screen_luminance launch, after the AOI stage and before the pupil
         stage, over the capture where it lies in d, the step's lengths and, for the discs, the masked plan's valid ANDed with the
         spec's valid_key; the result gains the spec's result_keys(), and with to_pupil and pupil= the covariate is the pupil stage's
-        luminance.  None issues no launch."""
+        luminance.  None issues no launch.
+        saccades: None, or EVEStream's saccade stage {'spec': a data.SaccadeSpec, 'state': float64 [B, 32], 'table': float64 [B, 16],
+        'store': float64 [B, S, 16], 'count', 'dropped': int32 [B]}, which needs events: the events launch is then eve_gaze_events_ex,
+        and one eve_gaze_saccades launch follows it, before the history stage, over that launch's sample flags, times and gaze vectors
+        (which stay internal), its labels, velocities and fixation ids and the point the velocity is from, with the step's lengths and
+        reset flags; the result gains saccade_id and saccade_ms.  None issues the launches a step without it issues."""
         assert not self.training, 'EVE._predict_sequence is eval-only'
         B = eye_input(d).shape[0]
         posed, faced = has_pose_form(d), face_landmarks_key(d) is not None
@@ -504,11 +509,20 @@ class EVE(nn.Module):
             out['heatmap_final'] = inter['heatmap_final']
         if events is not None:
             T = eye_input(d).shape[1]
-            out.update(default_kernels().gaze_events(
-                _f32(inter[events['source']], B, T, 2), _f32(d['o'], B, T, 3), _f32(d['inv_camera_transformation'], B, T, 4, 4),
+            k = default_kernels()
+            pog = _f32(inter[events['source']], B, T, 2)
+            res = (k.gaze_events if saccades is None else k.gaze_events_ex)(
+                pog, _f32(d['o'], B, T, 3), _f32(d['inv_camera_transformation'], B, T, 4, 4),
                 _f32(d['pixels_per_millimeter'], B, T, 2), events['spec'], events['state'], events['store'], events['count'], events['dropped'],
                 frame_time=d['frame_time'].contiguous() if 'frame_time' in d else None, valid=None if plan is None else plan['valid'],
-                lengths=lengths_b, reset=reset_b))
+                lengths=lengths_b, reset=reset_b)
+            if saccades is None:
+                out.update(res)
+            else:
+                from .data import GAZE_EVENT_KEYS, saccade_stage
+                out.update({k_: res[k_] for k_ in GAZE_EVENT_KEYS})
+                out.update(saccade_stage(k, pog, res, events['spec'], saccades['spec'],
+                                         [saccades[k_] for k_ in ('state', 'table', 'store', 'count', 'dropped')], lengths=lengths_b, reset=reset_b))
         if history is not None:
             self._gaze_history(d, inter, out, history, lengths_b, reset_b, plan)
         if aoi is not None:

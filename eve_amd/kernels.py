@@ -1171,6 +1171,108 @@ class HipKernels(object):
             *([self._p(out[k_]) for k_ in self.GAZE_EVENT_KEYS] if T else [None] * 7), self._stream()))
         return out
 
+    GAZE_EVENT_EX_KEYS = ('sample', 'sample_time', 'gaze_vector')
+
+    def gaze_events_ex(self, pog, origin, inv_cam, ppm, spec, state, store, count, dropped, frame_time=None, valid=None, lengths=None,
+                       reset=None, flush=None):
+        """gaze_events -- its arguments, its checks, its bits -- which also hands out what the launch computes on the way: -> a dict of
+        GAZE_EVENT_KEYS plus sample uint8 [B, T] (0 no sample, 1 a sample that restarts the chain, 2 a chained one), sample_time float64
+        [B, T] and gaze_vector float64 [B, T, 3] (zeros where sample is 0): what gaze_saccades consumes.  pog is not None: T >= 1
+        (include/eve_hip.h eve_gaze_events_ex)."""
+        ok = lambda t, dtype: torch.is_tensor(t) and t.dtype == dtype
+        got = lambda t: (getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ())))
+        if not ok(state, torch.float64) or state.dim() != 2 or state.shape[1] != 32 or state.shape[0] < 1:
+            raise TypeError('gaze_events_ex: state must be float64 [B, 32], got %s %s' % got(state))
+        B = state.shape[0]
+        if not ok(store, torch.float64) or store.dim() != 3 or store.shape[0] != B or store.shape[1] < 1 or store.shape[2] != 8:
+            raise TypeError('gaze_events_ex: store must be float64 [%d, F, 8], got %s %s' % ((B,) + got(store)))
+        F = store.shape[1]
+        if not ok(pog, torch.float32) or pog.dim() != 3 or pog.shape[0] != B or pog.shape[1] < 1 or pog.shape[2] != 2:
+            raise TypeError('gaze_events_ex: pog must be float32 [%d, T, 2], got %s %s' % ((B,) + got(pog)))
+        T = pog.shape[1]
+        tensors = [state, store, pog]
+        for name, t, dtype, shape, needed in (
+                ('count', count, torch.int32, (B,), True), ('dropped', dropped, torch.int32, (B,), True),
+                ('lengths', lengths, torch.int32, (B,), False), ('reset', reset, torch.int32, (B,), False),
+                ('flush', flush, torch.int32, (B,), False), ('origin', origin, torch.float32, (B, T, 3), True),
+                ('inv_cam', inv_cam, torch.float32, (B, T, 4, 4), True), ('ppm', ppm, torch.float32, (B, T, 2), True),
+                ('frame_time', frame_time, torch.float64, (B, T), False), ('valid', valid, torch.uint8, (B, T), False)):
+            if (t is not None or needed) and (not ok(t, dtype) or tuple(t.shape) != shape):
+                raise TypeError('gaze_events_ex: %s must be %s %s, got %s %s' % ((name, str(dtype).replace('torch.', ''), list(shape)) + got(t)))
+            if t is not None:
+                tensors.append(t)
+        if not all(t.is_contiguous() for t in tensors):
+            raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        if frame_time is None and spec.fps is None:
+            raise ValueError('gaze_events_ex: without frame_time the spec needs fps')
+        dev = state.device
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+        out = {'PoG_px_filtered': new((B, T, 2), torch.float32), 'gaze_velocity': new((B, T), torch.float32),
+               'gaze_event': new((B, T), torch.uint8), 'fixation_id': new((B, T), torch.int32),
+               'fixation_px': new((B, T, 2), torch.float32), 'fixation_ms': new((B, T), torch.float32),
+               'fixating': new((B, T), torch.uint8), 'sample': new((B, T), torch.uint8), 'sample_time': new((B, T), torch.float64),
+               'gaze_vector': new((B, T, 3), torch.float64)}
+        self._ck(self.lib.eve_gaze_events_ex(
+            B, T, self._p(pog), self._p(origin), self._p(inv_cam), self._p(ppm), self._p(frame_time), self._p(valid), self._p(lengths),
+            self._p(reset), self._p(flush), 0.0 if spec.fps is None else float(spec.fps), float(spec.min_cutoff_hz), float(spec.beta),
+            float(spec.d_cutoff_hz), 1 if spec.velocity_from == 'raw' else 0, float(spec.saccade_deg_s), float(spec.min_fixation_s),
+            float(spec.max_gap_s), self._p(state), F, self._p(store), self._p(count), self._p(dropped),
+            *[self._p(out[k_]) for k_ in self.GAZE_EVENT_KEYS + self.GAZE_EVENT_EX_KEYS], self._stream()))
+        return out
+
+    # ------------------------------------------------------------------ saccades as events
+    GAZE_SACCADE_KEYS = ('saccade_id', 'saccade_ms')
+
+    def gaze_saccades(self, sample, sample_time, gaze_vector, point, event, velocity, fixation_id, spec, state, table, store, count, dropped,
+                      lengths=None, reset=None):
+        """The saccades of B streams x T frames, cut from the events launch's labels: sample uint8 [B, T], sample_time float64 [B, T],
+        gaze_vector float64 [B, T, 3] (gaze_events_ex's), point float32 [B, T, 2] (the point the velocity is from), event uint8 [B, T],
+        velocity float32 [B, T], fixation_id int32 [B, T]; spec an eve_amd.SaccadeSpec (its numbers are the launch's scalars); state
+        float64 [B, 32], table float64 [B, 16], store float64 [B, S, 16], count and dropped int32 [B], UPDATED IN PLACE; lengths and reset
+        int32 [B], or None.  -> a dict of GAZE_SACCADE_KEYS: saccade_id int32 [B, T] (-1 outside a saccade), saccade_ms float32 [B, T].
+        sample None (then every frame input is None too): T = 0, a launch that only resets, -> {} (include/eve_hip.h
+        eve_gaze_saccades)."""
+        ok = lambda t, dtype: torch.is_tensor(t) and t.dtype == dtype
+        got = lambda t: (getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ())))
+        if not ok(state, torch.float64) or state.dim() != 2 or state.shape[1] != 32 or state.shape[0] < 1:
+            raise TypeError('gaze_saccades: state must be float64 [B, 32], got %s %s' % got(state))
+        B = state.shape[0]
+        if not ok(store, torch.float64) or store.dim() != 3 or store.shape[0] != B or store.shape[1] < 1 or store.shape[2] != 16:
+            raise TypeError('gaze_saccades: store must be float64 [%d, S, 16], got %s %s' % ((B,) + got(store)))
+        S = store.shape[1]
+        T = 0
+        if sample is not None:
+            if not ok(sample, torch.uint8) or sample.dim() != 2 or sample.shape[0] != B or sample.shape[1] < 1:
+                raise TypeError('gaze_saccades: sample must be uint8 [%d, T], got %s %s' % ((B,) + got(sample)))
+            T = sample.shape[1]
+        checks = [('table', table, torch.float64, (B, 16), True), ('count', count, torch.int32, (B,), True),
+                  ('dropped', dropped, torch.int32, (B,), True), ('lengths', lengths, torch.int32, (B,), False),
+                  ('reset', reset, torch.int32, (B,), False)]
+        if T:
+            checks += [('sample_time', sample_time, torch.float64, (B, T), True), ('gaze_vector', gaze_vector, torch.float64, (B, T, 3), True),
+                       ('point', point, torch.float32, (B, T, 2), True), ('event', event, torch.uint8, (B, T), True),
+                       ('velocity', velocity, torch.float32, (B, T), True), ('fixation_id', fixation_id, torch.int32, (B, T), True)]
+        elif any(t is not None for t in (sample_time, gaze_vector, point, event, velocity, fixation_id)):
+            raise TypeError('gaze_saccades: without sample (T = 0) there are no frame inputs')
+        tensors = [state, store] + ([sample] if T else [])
+        for name, t, dtype, shape, needed in checks:
+            if (t is not None or needed) and (not ok(t, dtype) or tuple(t.shape) != shape):
+                raise TypeError('gaze_saccades: %s must be %s %s, got %s %s' % ((name, str(dtype).replace('torch.', ''), list(shape)) + got(t)))
+            if t is not None:
+                tensors.append(t)
+        if not all(t.is_contiguous() for t in tensors):
+            raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        dev = state.device
+        out = {}
+        if T:
+            out = {'saccade_id': torch.empty((B, T), dtype=torch.int32, device=dev), 'saccade_ms': torch.empty((B, T), dtype=torch.float32, device=dev)}
+        self._ck(self.lib.eve_gaze_saccades(
+            B, T, self._p(sample), self._p(sample_time), self._p(gaze_vector), self._p(point), self._p(event), self._p(velocity),
+            self._p(fixation_id), self._p(lengths), self._p(reset), float(spec.min_amplitude_deg), float(spec.min_duration_s),
+            float(spec.max_duration_s), int(spec.max_missing), self._p(state), self._p(table), S, self._p(store), self._p(count),
+            self._p(dropped), *([self._p(out[k_]) for k_ in self.GAZE_SACCADE_KEYS] if T else [None] * 2), self._stream()))
+        return out
+
     # ------------------------------------------------------------------ the time-decayed gaze history
     def gaze_history_plan(self, P, screen_size, state, T, pog=None, frame_time=None, valid=None, valid_key=None, lengths=None, reset=None):
         """The time chain of the gaze history for B streams x T frames: P the launch's scalars (data.GazeHistorySpec.launch_params:

@@ -12,6 +12,8 @@ carried from one call to the next.
     fit = stream.fit_screen_calibration(model='affine')    # fit it on the device; later steps correct their output point
     out = stream.step(chunk, events=eve_amd.GazeEventSpec(fps=60))   # + the filtered PoG, gaze velocity, fixation / saccade events
     rows = stream.fixations()                              # the completed fixations of every stream (see "Gaze events" below)
+    out = stream.step(chunk, events=eve_amd.GazeEventSpec(fps=60), saccades=eve_amd.SaccadeSpec())   # + saccade_id, saccade_ms ("Saccades")
+    rows = stream.saccades()                               # the accepted saccades: amplitude, duration, peak velocity, the fixations around them
     out = stream.step(chunk, gate=eve_amd.EyeGateSpec(blink=eve_amd.BlinkSpec()))   # the mask made on the device (see "The eye gate" below)
     out = stream.step(chunk, history=eve_amd.GazeHistorySpec(fps=60))                # + the time-decayed map of where the gaze has been
     out = stream.step(dict(chunk, aoi_shapes=regions), aoi=eve_amd.AoiSpec(num_aois=8, fps=60))   # + which region is looked at ("Areas of interest")
@@ -104,6 +106,33 @@ device flags (get_event_state / set_event_state; get_state / set_state do not ho
 tests/gaze_events_ref.py states the arithmetic.  A step without events issues exactly the launches it always issued.  Not offered:
 dispersion (I-DT) or other classifiers, windowed velocity, merging of adjacent fixations and retroactive relabelling,
 smooth-pursuit and blink classes, per-eye events, gradients, EVE.forward.
+
+Saccades.  The events stage labels every frame, and only fixations leave it as events; saccades are the other half of every event
+detector -- amplitude, duration, peak and mean velocity, the link fixation -> saccade -> fixation that is the scan path, an "in
+saccade" flag for saccadic suppression, the main sequence -- and cannot be rebuilt from the step's results: the gaze vectors, the
+sample flags and the sample times live inside the events launch, and an open saccade has to survive chunk boundaries, ragged lengths,
+masked eyes and reset().  step(chunk, events=..., saccades=eve_amd.SaccadeSpec(...)) makes the events launch eve_gaze_events_ex, which
+hands those three out (same kernel, same bits; they stay internal), and adds one eve_gaze_saccades launch right after it, before the
+history stage, inside the graph.  A saccade opens at the sample before its first saccade frame and lands at its last; the next
+fixation frame closes and judges it: more than max_missing frames inside it that were no sample -> interrupted, longer than
+max_duration_s -> long, shorter than min_duration_s -> short, under min_amplitude_deg -> small, else accepted.  A gap, a restart of
+the chain and reset() abort it.  The result gains saccade_id int32 [B, Tc] (-1 outside; ids run on over reset() and are handed out at
+the onset, accepted or not) and saccade_ms float32 [B, Tc].  Per stream the launch keeps a float64 [B, 32] state row, a table float64
+[B, 16] (accepted, sum amp, sum amp^2, sum peak, sum amp*peak, sum dur, sum amp*dur, max amp, max peak, aborted, small, short, long,
+interrupted, 0, 0: the sums behind the main sequence, data.main_sequence()) and a store float64 [B, saccade_capacity, 16] (id, t_onset,
+t_landing, n, x0, y0, x1, y1, amplitude_deg, peak_deg_s, mean_deg_s, prev_fixation_id, next_fixation_id, missing, 0, 0; a full store
+drops and counts): saccades(), saccade_counts(), saccade_table(), clear_saccades(), get_saccade_state() / set_saccade_state();
+get_state() / set_state() do not hold them.  reset() aborts the open saccade and starts the row afresh through the same device flags
+(also before a step without saccades=); the id counter and the table stay.  There is no flush: an open saccade has no landing.  The
+amplitude is the angle at the eye between the onset's and the landing's gaze vectors, so it is that of the point the velocity is
+from: with velocity_from='filtered', the default, the one-euro filter's lag shortens it (8.9 / 9.2 / 9.5 degrees for a 10 degree
+saccade at 30 / 60 / 120 fps on the scan path of tests/test_gaze_events_host.py; 9.9 .. 10.0 with 'raw').  The fixation ids a row
+links to are the events stage's: a fixation that never reached min_fixation_s is in no store and still has its id.  An events step
+without saccades= moves the chain on without the stage; the stream remembers, and one launch with no frames starts every row afresh
+before the next saccades step.  Float64; tests/saccade_ref.py states the rules, and the device equals them bit for bit up to the
+amplitude's atan2.  A step without saccades= issues exactly the launches it always issued, eve_gaze_events included, and allocates
+nothing.  Not offered: direction angles (the endpoints are there), curvature or path length, glissades and post-saccadic
+oscillation, microsaccades, smooth pursuit, per-eye saccades, retroactive merging, gradients, EVE.forward.
 
 The eye gate.  The masked step keeps an unusable eye out of the states and the fused gaze, but it needs the mask, and what should
 veto an eye -- pose_valid, face_reproj_rms, face_inliers, the derived warps and head angles, a closed lid -- are results of the same
@@ -224,6 +253,7 @@ SampleStore = namedtuple('SampleStore', 'samples count dropped')
 StageBuffers = namedtuple('StageBuffers', 'state store count dropped')
 AoiBuffers = namedtuple('AoiBuffers', 'state table trans visits count dropped')      # what eve_gaze_aoi carries, per AoiSpec name
 PupilBuffers = namedtuple('PupilBuffers', 'state table light store count dropped')    # what eve_pupil_track carries, per PupilSpec name
+SaccadeBuffers = namedtuple('SaccadeBuffers', 'state table store count dropped')      # what eve_gaze_saccades carries
 
 
 def _module_key(m):
@@ -238,7 +268,7 @@ def _capacity(name, value):
 
 class EVEStream(object):
     def __init__(self, model, num_streams, use_graph=True, calibration_capacity=1024, fixation_capacity=256, blink_capacity=256,
-                 screen_calibration_capacity=1024, visit_capacity=256, episode_capacity=256):
+                 screen_calibration_capacity=1024, visit_capacity=256, episode_capacity=256, saccade_capacity=256):
         if model.training:
             raise ValueError('EVEStream runs inference only: call model.eval() first')
         self.model = model
@@ -281,6 +311,13 @@ class EVEStream(object):
         self.fixation_capacity = _capacity('fixation_capacity', fixation_capacity)
         self._events = None                      # made at the first events step or fixation call: (state, store, count, dropped)
         self._events_spec = None                 # the spec of the last events step: what closes a fixation outside a step
+        # saccades (step(chunk, events=..., saccades=spec)): the open saccade's state row, the table of tallies, the store of accepted
+        # saccades and its counters -- eve_gaze_saccades reads and writes them inside the step (and the graph).  _saccades_stale: the
+        # events chain has moved without the stage since, so the row is brought back in step before the next saccades step
+        self.saccade_capacity = _capacity('saccade_capacity', saccade_capacity)
+        self._saccades = None                    # made at the first saccades step or saccade call: (state, table, store, count, dropped)
+        self._saccades_spec = None               # the spec of the last saccades step: the scalars of a launch with no frames
+        self._saccades_stale = False
         # the eye gate (step(chunk, gate=spec)): each eye's blink state row, the store of completed blinks and its counters --
         # eve_eye_gate reads and writes them inside the step (and the graph)
         self.blink_capacity = _capacity('blink_capacity', blink_capacity)
@@ -304,7 +341,7 @@ class EVEStream(object):
         self._render_tables = {}                 # OverlaySpec.key() -> its marker table, int32 [M, 4] on the device
 
     # ------------------------------------------------------------------ state
-    _GROUPS = ('_calib_store', '_events', '_gate', '_screen_store')      # the attributes _group() may fill: None until first use
+    _GROUPS = ('_calib_store', '_events', '_gate', '_screen_store', '_saccades')      # the attributes _group() may fill: None until first use
 
     def _group(self, attr, kind, *buffers):
         """The lazily made buffer group self.<attr>, a `kind` namedtuple of zeroed device tensors, one per (shape, dtype) -- made at
@@ -318,7 +355,7 @@ class EVEStream(object):
         """Every tensor a step may write, as they exist now: what _capture's two warm-up steps must put back.  The recurrent states;
         the face-landmark form's head pose; kappa and its flags; both calibrations' sample stores and counters (the warm-up steps of
         a collecting graph would otherwise append every sample three times); the gaze events' state, store and counters (a capture
-        would otherwise tick the filter three times); the eye gate's ticks, baselines and blinks; every gaze history's time chain
+        would otherwise tick the filter three times); the saccades' state row, table, store and counters; the eye gate's ticks, baselines and blinks; every gaze history's time chain
         and map; every AOI spec's state row, tallies and visit store; every pupil spec's state row, table, light response and
         episode store.  A carried buffer that is not returned here corrupts its state under use_graph only, and only on the first
         step of a chunk shape: new ones are made by _group(), by _history_entry(), by _aoi_entry() or by _pupil_entry(), and are
@@ -346,7 +383,8 @@ class EVEStream(object):
         next step().  Resets requested before one step accumulate.  A stream that has run the eye gate (step(gate=...)) has both
         eyes' blink rows and its tick cleared; an eye closed at that moment stores no blink.  A stream that has run gaze events (step(events=...)) closes its
         open fixation into the store -- if it lasted min_fixation_s -- and starts its filter, its events and its frame count afresh,
-        by the same device flags; only its fixation id counter runs on, so ids stay unique within a recording.  The per-person calibration -- each eye's kappa and the
+        by the same device flags; only its fixation id counter runs on, so ids stay unique within a recording.  A stream that has run the saccade stage (step(saccades=...)) aborts its open saccade -- tallied, nothing
+        stored -- and starts that row afresh; its saccade id counter and its table run on.  The per-person calibration -- each eye's kappa and the
         sample store -- is not touched: it belongs to the person, not to the clip (clear_calibration,
         clear_calibration_samples); neither are the screen-space map and its sample store (clear_screen_calibration,
         clear_screen_calibration_samples)."""
@@ -614,6 +652,7 @@ class EVEStream(object):
         if tuple(state.shape) != (self.num_streams, 32):
             raise ValueError('set_event_state: state must be [%d, 32], got %s' % (self.num_streams, tuple(state.shape)))
         self._event_buffers()[0].copy_(state)
+        self._saccades_stale = self._saccades is not None      # (the saccade row no longer follows this chain)
 
     def _output_stage(self):
         """'final' with a RefineNet, else 'initial': the stage whose point of gaze PoG_px_<out> is the step's output -- what the
@@ -641,6 +680,76 @@ class EVEStream(object):
             self._check_chunk_tensor('frame_time', ft, (torch.float64,), (B, Tc))
         self._event_buffers()                    # allocated here, before any capture
         return {'spec': spec, 'source': source}
+
+    # ------------------------------------------------------------------ saccades
+    def _saccade_buffers(self):
+        B, S = self.num_streams, self.saccade_capacity
+        return self._group('_saccades', SaccadeBuffers, ((B, 32), torch.float64), ((B, 16), torch.float64), ((B, S, 16), torch.float64),
+                           ((B,), torch.int32), ((B,), torch.int32))
+
+    def _saccade_launch_spec(self):
+        from .data import SaccadeSpec
+        return self._saccades_spec if self._saccades_spec is not None else SaccadeSpec()
+
+    def _reset_saccade_rows(self, flags):
+        """One eve_gaze_saccades launch with no frames: the flagged streams' open saccades are aborted and their rows start afresh."""
+        default_kernels().gaze_saccades(None, None, None, None, None, None, None, self._saccade_launch_spec(), *self._saccade_buffers(),
+                                        reset=flags)
+
+    def saccades(self, streams=None):
+        """The accepted saccades of the given streams (None = all; indices or a bool mask), one numpy float64 [n, 16] array per stream
+        in index order, rows (id, t_onset, t_landing, n saccade frames, x0, y0, x1, y1, amplitude_deg, peak_deg_s, mean_deg_s,
+        prev_fixation_id, next_fixation_id, missing, 0, 0) in the order they landed; times in the clock of the steps, pixels of the
+        point the velocity is from.  The fixation ids are the events stage's: a fixation that never reached min_fixation_s is in no
+        fixation store, and still has the id a row links to.  This call waits for the device."""
+        m = self._stream_mask(streams, 'saccades')
+        _, _, store, count, _ = (t.cpu().numpy() for t in self._saccade_buffers())
+        return [store[b, :min(max(int(count[b]), 0), self.saccade_capacity)].copy() for b in np.flatnonzero(m)]
+
+    def saccade_counts(self):
+        """-> (count, dropped), int32 [B] device tensors (fresh): the accepted saccades each stream's store holds, and those a full
+        store (saccade_capacity) turned away."""
+        buffers = self._saccade_buffers()
+        return buffers.count.clone(), buffers.dropped.clone()
+
+    def saccade_table(self):
+        """The tallies, float64 [B, 16] (fresh): accepted, sum_amp, sum_amp2, sum_peak, sum_amp_peak, sum_dur, sum_amp_dur, max_amp,
+        max_peak, aborted, small, short, long, interrupted, 0, 0 (data.SACCADE_TABLE) -- degrees, degrees / second and seconds;
+        data.main_sequence() fits the main sequence from them."""
+        return self._saccade_buffers().table.clone()
+
+    def clear_saccades(self, streams=None, table=False):
+        """Empty the saccade store of the given streams (None = all) and their dropped counters; with table=True their tallies too.
+        The open saccade is state, not store: reset() ends it."""
+        m = self._device_mask(streams, 'clear_saccades')
+        buffers = self._saccade_buffers()
+        self._zero_where(m, buffers.count, buffers.dropped, *((buffers.table,) if table else ()))
+
+    def get_saccade_state(self):
+        """The saccade stage's carried state, float64 [B, 32] (fresh; include/eve_hip.h eve_gaze_saccades has the layout): the carried
+        previous sample, the open saccade, the id counter.  Resets not yet applied by a step are not reflected.  get_state() /
+        set_state() do not hold it."""
+        return self._saccade_buffers().state.clone()
+
+    def set_saccade_state(self, state):
+        """Load a state in get_saccade_state()'s layout, [B, 32] (converted to float64), e.g. beside set_event_state() to resume a
+        recording: the row is then taken to be in step with the events' row."""
+        state = torch.as_tensor(state, dtype=torch.float64).to(self.device)
+        if tuple(state.shape) != (self.num_streams, 32):
+            raise ValueError('set_saccade_state: state must be [%d, 32], got %s' % (self.num_streams, tuple(state.shape)))
+        self._saccade_buffers().state.copy_(state)
+        self._saccades_stale = False
+
+    def _check_saccades(self, spec, events):
+        """step()'s `saccades` checked -> the stage's plan.  Every refusal is a ValueError raised before anything is launched or
+        captured."""
+        from .data import SaccadeSpec
+        if not isinstance(spec, SaccadeSpec):
+            raise ValueError('step: saccades must be an eve_amd.SaccadeSpec, got %s' % type(spec).__name__)
+        if events is None:
+            raise ValueError('step: saccades cuts the events stage\'s labels into saccades: pass events= in the same step')
+        self._saccade_buffers()                  # allocated here, before any capture
+        return {'spec': spec}
 
     # ------------------------------------------------------------------ the gaze history
     def _history_entry(self, spec, P):
@@ -763,11 +872,13 @@ class EVEStream(object):
             e = self._history_entry(plan['spec'], plan['P'])
             plan['state'], plan['maps'] = e['state'], e['maps']
 
-    def _reset_idle_stages(self, events, gate, history, aoi=None, pupil=None):
-        """A reset before a step that does not run a stage which carries state (events, gate, history, aoi, pupil: None or this
-        step's plans): the stage's state of the flagged streams still ends."""
+    def _reset_idle_stages(self, events, gate, history, aoi=None, pupil=None, saccades=None):
+        """A reset before a step that does not run a stage which carries state (events, gate, history, aoi, pupil, saccades: None or
+        this step's plans): the stage's state of the flagged streams still ends."""
         flags = self._flags[:self.num_streams]
         k = default_kernels()
+        if saccades is None and self._saccades is not None:
+            self._reset_saccade_rows(flags)      # the open saccade is aborted and the row starts afresh: the launch with no frames
         if events is None and self._events is not None:
             # the gaze events' state ends its fixation and starts afresh: the launch with no frames
             k.gaze_events(None, None, None, None, self._closing_spec(), *self._events, reset=flags)
@@ -1420,7 +1531,7 @@ class EVEStream(object):
             self._pose_gate.fill_(self._pose_gate_host)              # a device value: the captured graphs read it, the host never waits
 
     def _run(self, chunk, return_heatmaps, ragged=False, eye_mask=None, masked=False, render=None, events=None, gate=None, history=None,
-             aoi=None, pupil=None, luminance=None):
+             aoi=None, pupil=None, luminance=None, saccades=None):
         """The one call of EVE._predict_sequence, eager or under capture.  render, events, gate, history, aoi, pupil, luminance: None or the plan of
         that stage's check.  A stage's keyword goes along only when the stage runs, and lengths, the mask's keywords and face_state only
         on a ragged, a masked and a face-landmark step: a step without them makes the call it always made."""
@@ -1450,6 +1561,8 @@ class EVEStream(object):
                                         'store': self._screen_samples() if 'screen_calibration_target' in chunk else None}
         if events is not None:
             kw['events'] = dict(events, **self._event_buffers()._asdict())
+        if saccades is not None:
+            kw['saccades'] = dict(saccades, **self._saccade_buffers()._asdict())
         if gate is not None:
             kw['gate'] = dict(gate, **self._gate_buffers()._asdict())
         return self.model._predict_sequence(chunk, self._eye, self._ref, **kw)
@@ -1596,7 +1709,7 @@ class EVEStream(object):
         return render
 
     def step(self, chunk, return_heatmaps=False, lengths=None, eye_mask=None, skip_invalid_pose=False, render=None, events=None, gate=None,
-             history=None, aoi=None, pupil=None, luminance=None):
+             history=None, aoi=None, pupil=None, luminance=None, saccades=None):
         """One chunk of every stream: chunk holds [B, Tc, ...] tensors on the model's device -- the eyes (below), {left,right}_h,
         {left,right}_o, {left,right}_R, head_R, camera_transformation, inv_camera_transformation, pixels_per_millimeter, millimeters_per_pixel, and screen_frame when the config loads screen content.  Returns the
         prediction keys of EVE(output_predictions=True) as [B, Tc, ...] tensors (heatmap_final [B, Tc, 1, H, W] on request).
@@ -1891,7 +2004,23 @@ class EVEStream(object):
         fixation_px as the source without events=, a name whose keys collide with the chunk's or the result's, radii that fall
         together at the capture's scale.  The spec by value is part of the graph's key; the stage carries no state.
         tests/screen_luminance_ref.py states the arithmetic, exact to the bit.  luminance=None issues exactly the launches the step
-        always issued."""
+        always issued.
+        saccades: None, or an eve_amd.SaccadeSpec, with events= in the same step (ValueError without, raised before anything is
+        launched) -- the events launch becomes eve_gaze_events_ex, which also hands out its sample flags, sample times and gaze
+        vectors (they stay internal), and one eve_gaze_saccades launch right after it, before the history stage and inside the
+        captured graph, cuts the runs of saccade frames into events (module docstring, "Saccades").  The result gains saccade_id
+        int32 [B, Tc] (-1 outside a saccade; a counter per stream that reset() leaves running, handed out at every onset whether the
+        saccade is accepted later or not) and saccade_ms float32 [B, Tc] (the time since the onset: the flag saccadic suppression
+        needs is saccade_id >= 0).  A saccade opens at the sample before its first saccade frame and lands at its last saccade frame;
+        it is judged when the next fixation frame arrives -- interrupted (more than max_missing frames inside it were no sample),
+        long, short, small, or accepted -- and an accepted one goes to the table and the store: saccades(), saccade_counts(),
+        saccade_table(), clear_saccades(), get_saccade_state() / set_saccade_state(), data.main_sequence().  A gap, a reset() and a
+        restart of the chain abort an open saccade (tallied, not stored); there is no flush: an open saccade has no landing.  The
+        amplitude is that of the point the velocity is from (GazeEventSpec.velocity_from).  The spec by value is part of the graph's
+        key; every other mode of the step combines with it.  After events steps without saccades= the stage's row is brought back in
+        step by one launch with no frames before the next saccades step: a saccade under way then is not reported.
+        tests/saccade_ref.py states the arithmetic.  saccades=None issues exactly the launches the step always issued,
+        eve_gaze_events included."""
         if self.model.training:
             raise ValueError('EVEStream runs inference only: the model was switched to training mode')
         B, Tc = eye_input(chunk).shape[:2]
@@ -1910,6 +2039,8 @@ class EVEStream(object):
         if gate is not None:
             gate = self._check_gate(chunk, gate, B, Tc)
         more = {} if gate is None else {'gate': gate}      # the keyword goes along only then: a step without it calls what it always did
+        if saccades is not None:
+            more['saccades'] = saccades = self._check_saccades(saccades, events)
         if history is not None:
             more['history'] = history = self._check_history(chunk, history, events, masked, B, Tc)
         if aoi is not None:
@@ -1935,8 +2066,15 @@ class EVEStream(object):
         self._upload_resets()
         if events is not None:
             self._events_spec = events['spec']
+        if saccades is not None:
+            self._saccades_spec = saccades['spec']
+            if self._saccades_stale:             # the events chain moved on without the stage: every row starts afresh, eagerly
+                self._reset_saccade_rows(torch.ones((B,), dtype=torch.int32, device=self.device))
+                self._saccades_stale = False
+        elif events is not None and self._saccades is not None:
+            self._saccades_stale = True
         if self._flags_set:
-            self._reset_idle_stages(events, gate, history, aoi, pupil)
+            self._reset_idle_stages(events, gate, history, aoi, pupil, saccades)
         with torch.no_grad():
             if self.use_graph:
                 entry = self._graph_for(chunk, bool(return_heatmaps), ragged, masked, render, events, **more)
@@ -1972,7 +2110,7 @@ class EVEStream(object):
         return tuple(_module_key(m) for m in (self.model.eye_net, self.model.refine_net) if m is not None)
 
     def _graph_key(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None, aoi=None,
-                   pupil=None, luminance=None):
+                   pupil=None, luminance=None, saccades=None):
         """What a captured graph is good for: the step's mode, both YUV matrices, both surface layouts (by value), the overlay
         (render: None or a _render_plan -- its OverlaySpec by value), with a face-landmark form eye_net.face_huber_px (a launch
         argument, so baked in), the gaze events (events: None or a _check_events plan -- its GazeEventSpec by value and its source;
@@ -1982,7 +2120,7 @@ class EVEStream(object):
         AoiSpec by value, its source and whether fixations are counted; aoi_shapes' shape is a chunk key), the pupillometry (pupil: None or a
         _check_pupil plan -- its PupilSpec by value; pupil_luminance's and pupil_baseline's presence are chunk keys), the screen luminance
         (luminance: None or a _check_luminance plan -- its ScreenLuminanceSpec by value and its source; the capture's shape is a chunk key and its
-        layout and matrix are RefineNet's), whether a calibration is applied (`calibrated`; a collecting step differs by its chunk keys), whether a screen-space map is applied (likewise), and every chunk tensor's key, shape and dtype -- which of the two landmark keys among them."""
+        layout and matrix are RefineNet's), the saccades (saccades: None or a _check_saccades plan -- its SaccadeSpec by value), whether a calibration is applied (`calibrated`; a collecting step differs by its chunk keys), whether a screen-space map is applied (likewise), and every chunk tensor's key, shape and dtype -- which of the two landmark keys among them."""
         ref = self.model.refine_net
         spec = None if render is None else render['spec'].key()
         layouts = (self.model.eye_net.camera_layout, None if ref is None else ref.screen_layout)
@@ -1997,10 +2135,11 @@ class EVEStream(object):
                                                                 for h in history),)) + \
             (() if aoi is None else (('aoi', aoi['spec'].key(), aoi['source'], aoi['use_fixations']),)) + \
             (() if pupil is None else (('pupil', pupil['spec'].key()),)) + \
-            (() if luminance is None else (('luminance', luminance['spec'].key(), luminance['source']),)) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
+            (() if luminance is None else (('luminance', luminance['spec'].key(), luminance['source']),)) + \
+            (() if saccades is None else (('saccades', saccades['spec'].key()),)) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
 
     def _graph_for(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None, aoi=None,
-                   pupil=None, luminance=None):
+                   pupil=None, luminance=None, saccades=None):
         wk = self._weights_key()
         if wk != self._graphs_key:               # new weights: new packs, new graphs (a replay never reads stale packs)
             self._graphs = {}
@@ -2014,6 +2153,8 @@ class EVEStream(object):
             more['pupil'] = pupil
         if luminance is not None:
             more['luminance'] = luminance
+        if saccades is not None:
+            more['saccades'] = saccades
         key = self._graph_key(chunk, return_heatmaps, ragged, masked, render, events, **more)
         entry = self._graphs.get(key)
         if entry is None:
@@ -2023,7 +2164,7 @@ class EVEStream(object):
         return entry
 
     def _capture(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None, aoi=None,
-                 pupil=None, luminance=None):
+                 pupil=None, luminance=None, saccades=None):
         """Capture one step for this chunk shape (train.Trainer._capture's recipe): inputs copied into fixed buffers, two eager
         warm-up steps off the default stream (packs, lazily built filters, allocator) with the carried states put back
         afterwards, the kernels' scratch allocated before the capture, one stream, no side branches.  A masked graph has one more
@@ -2040,7 +2181,7 @@ class EVEStream(object):
             carried = self._carried()
             snap = [t.clone() for t in carried]
             for _ in range(2):
-                self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history, aoi, pupil, luminance)
+                self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history, aoi, pupil, luminance, saccades)
             for t, s_ in zip(carried, snap):
                 t.copy_(s_)
         torch.cuda.current_stream().wait_stream(side)
@@ -2050,7 +2191,7 @@ class EVEStream(object):
             k.prepare_graph_workspace(self.device)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            out = self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history, aoi, pupil, luminance)
+            out = self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history, aoi, pupil, luminance, saccades)
         m = self.model
         keep = (m.eye_net._packs, getattr(m.eye_net, '_stream_w', None), m.refine_net._packs if m.refine_net is not None else None)
         return {'graph': graph, 'inputs': static, 'outputs': out, 'keep': keep, 'eye_mask': eye_mask}

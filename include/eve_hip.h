@@ -1277,6 +1277,69 @@ int eve_gaze_events(long long B, int T, const float* pog, const float* origin, c
                     int F, double* store, int* count, int* dropped, float* filtered, float* velocity, uint8_t* event, int* fixation_id,
                     float* fixation_px, float* fixation_ms, uint8_t* fixating, eve_stream_t stream);
 
+/* The same launch, which also hands out what it computes on the way: eve_gaze_events' arguments, arithmetic, state row and store,
+ * bit for bit (both entries launch gaze_events_kernel), plus three outputs, each of which may be NULL, written for every frame f < T:
+ *   sample [B*T] uint8: 0 the frame is no sample (the frames from lengths[b] on included), 1 a sample that restarts the chain (the
+ *   first after a reset, or more than max_gap_s after the last), 2 a sample chained to the one before (it has a velocity and a label);
+ *   sample_time [B*T] double: the t the launch used for the frame; gaze_vector [B*T][3] double: v, the vector behind the velocity.
+ *   Both are 0.0 where sample is 0.
+ * What eve_gaze_saccades consumes.  (Additive: ABI v10.)                                                                            */
+int eve_gaze_events_ex(long long B, int T, const float* pog, const float* origin, const float* inv_cam, const float* ppm,
+                       const double* frame_time /* may be NULL */, const uint8_t* valid /* may be NULL */, const int* lengths /* may be NULL */,
+                       const int* reset /* may be NULL */, const int* flush /* may be NULL */, double fps, double min_cutoff_hz, double beta,
+                       double d_cutoff_hz, int velocity_from_raw, double saccade_deg_s, double min_fixation_s, double max_gap_s, double* state,
+                       int F, double* store, int* count, int* dropped, float* filtered, float* velocity, uint8_t* event, int* fixation_id,
+                       float* fixation_px, float* fixation_ms, uint8_t* fixating, uint8_t* sample /* may be NULL */,
+                       double* sample_time /* may be NULL */, double* gaze_vector /* may be NULL */, eve_stream_t stream);
+
+/* Saccades as events: the runs of saccade frames that eve_gaze_events labels, cut into events with amplitude, duration, peak and mean
+ * velocity and the fixations on either side, for B streams x T frames, with the state carried in `state`, the tallies in `table` and
+ * the accepted saccades in `store` from one call to the next.  Float64, every operation rounded on its own (no contraction), in the
+ * order written here; tests/saccade_ref.py restates it in numpy.  One wavefront per stream, passes of 64 frames, the closings'
+ * atan2 across the lanes; the bits do not depend on that structure.
+ *   sample [B*T] uint8, sample_time [B*T] double, gaze_vector [B*T][3] double: eve_gaze_events_ex's outputs of the same frames;
+ *   point [B*T][2] float: the point the velocity is from (the filtered point, or the source with velocity_from_raw), widened to
+ *   double; event [B*T] uint8, velocity [B*T] float, fixation_id [B*T] int: that launch's labels; lengths [B] int (clamped to 0 ..
+ *   T) and reset [B] int: each may be NULL (T frames, no reset).
+ *   state [B][32] double, table [B][16] double, store [B][S][16] double, count [B] and dropped [B] int: read and UPDATED IN PLACE.
+ * The state row, an all-zero row being a fresh stream: 0 has_prev, 1-8 the carried previous sample -- 1 its time, 2-4 its gaze
+ * vector, 5-6 its point, 7 its event, 8 its fixation_id --, 9 open, 10 the open saccade's id, 11 next_id (the ids handed out so far),
+ * 12 t_onset, 13-15 the onset's gaze vector, 16-17 the onset's point, 18 n (its saccade frames), 19 peak, 20 missing, 21
+ * prev_fixation_id, 22-31 reserved (0).
+ * A stream with reset[b] != 0 first aborts its open saccade (table.aborted += 1, nothing stored) and zeroes its row except entry 11;
+ * the table stays.  Then frames f = 0 .. lengths[b] - 1 are walked in order (the later ones: id -1, ms 0, nothing moves).
+ *   sample 0: where a saccade is open, missing += 1.  Nothing else moves; id -1, ms 0.
+ *   sample 1, or sample 2 with an event other than 1 and 2 (which eve_gaze_events never writes): an open saccade is aborted.
+ *   sample 2, event 2: where none is open, has_prev != 0 and the carried sample's event is not 2 (it is only after a reset of this row
+ *   alone: nothing opens in the middle of a run), one opens -- id = next_id, next_id += 1 (accepted later or not), t_onset, the
+ *   onset's vector and point = the carried sample's, prev_fixation_id = its fixation_id where its event was 1, else -1, n = peak =
+ *   missing = 0.  Where one is open: n += 1, peak = velocity (widened) where that is > peak, saccade_id = id, saccade_ms = 1000 * (t -
+ *   t_onset).
+ *   sample 2, event 1: an open saccade closes.  Its landing is the carried sample (the last saccade frame): with p the onset's vector
+ *   and v the landing's, c = p x v (c0 = p1*v2 - p2*v1, ...), amplitude = atan2(sqrt((c0*c0 + c1*c1) + c2*c2), (p0*v0 + p1*v1) + p2*v2)
+ *   * 57.29577951308232 (deg), duration = t_landing - t_onset, mean = amplitude / duration, next_fixation_id = this frame's
+ *   fixation_id.  The first that holds decides: missing > max_missing: table.interrupted += 1; duration > max_duration_s: long;
+ *   duration < min_duration_s: short; not (amplitude >= min_amplitude_deg): small; else it is accepted: table.accepted += 1, sum_amp
+ *   += amplitude, sum_amp2 += amplitude*amplitude, sum_peak += peak, sum_amp_peak += amplitude*peak, sum_dur += duration, sum_amp_dur
+ *   += amplitude*duration, max_amp and max_peak take a larger value, and the row (id, t_onset, t_landing, n, x0, y0, x1, y1,
+ *   amplitude_deg, peak_deg_s, mean_deg_s, prev_fixation_id, next_fixation_id, missing, 0, 0) goes to store[b][count[b]] and count[b]
+ *   grows; with count[b] == S it is dropped and dropped[b] grows.
+ *   After every sample (1 or 2) it becomes the carried sample: has_prev = 1, its time, vector, point, event (0 for sample 1) and id.
+ * The table row: 0 accepted, 1 sum_amp, 2 sum_amp2, 3 sum_peak, 4 sum_amp_peak, 5 sum_dur, 6 sum_amp_dur, 7 max_amp, 8 max_peak,
+ * 9 aborted, 10 small, 11 short, 12 long, 13 interrupted, 14-15 reserved (0).  There is no flush: an open saccade has no landing.
+ * T = 0 is a call that only resets (the frame pointers may then be NULL).
+ * Outputs per frame: saccade_id [B*T] int (-1 outside a saccade), saccade_ms [B*T] float (rounded from double once; 0 outside).
+ * Kernel name gaze_saccades_kernel.  Refused without a launch: a null carried buffer, B < 1, T < 0, S < 1, with T > 0 a null frame
+ * input or output, index ranges past 31 bits, a threshold that is not finite, min_amplitude_deg < 0, max_duration_s <= 0,
+ * min_duration_s < 0, max_missing < 0.  Not offered: direction angles (the endpoints are there), curvature or path length, glissades
+ * and post-saccadic oscillation, microsaccades, smooth pursuit, per-eye saccades, retroactive merging, a gradient.  (Additive: ABI
+ * v10.)                                                                                                                             */
+int eve_gaze_saccades(long long B, int T, const uint8_t* sample, const double* sample_time, const double* gaze_vector, const float* point,
+                      const uint8_t* event, const float* velocity, const int* fixation_id, const int* lengths /* may be NULL */,
+                      const int* reset /* may be NULL */, double min_amplitude_deg, double min_duration_s, double max_duration_s,
+                      int max_missing, double* state, double* table, int S, double* store, int* count, int* dropped, int* saccade_id,
+                      float* saccade_ms, eve_stream_t stream);
+
 /* The eye gate: per frame and eye, is the eye usable?  One launch between the pose derivation and eve_stream_mask_plan turns the
  * results of the same step -- the pose flags, the solve's reprojection error and inlier count, the derived warps and head angles --
  * and the tracker's eyelid points into the mask the masked step consumes, and detects blinks with state carried in `state` from one
