@@ -4,7 +4,7 @@ kernels (libeve_hip.so, C ABI in include/eve_hip.h)."""
 from .config import HotPathConfig, get_config, reset_standalone_config  # noqa: F401
 from .eye_net import EyeNet  # noqa: F401
 
-__all__ = ['EyeNet', 'RefineNet', 'EVE', 'EVEStream', 'OverlaySpec', 'GazeEventSpec', 'SaccadeSpec', 'GazeHistorySpec', 'AoiSpec', 'PupilSpec', 'ScreenLuminanceSpec', 'EyeGateSpec', 'BlinkSpec', 'SurfaceLayout', 'screen_calibration_samples', 'fit_screen_map', 'evaluate_screen_map', 'apply_screen_map', 'get_config', 'HotPathConfig', 'reset_standalone_config']
+__all__ = ['EyeNet', 'RefineNet', 'EVE', 'EVEStream', 'OverlaySpec', 'GazeEventSpec', 'SaccadeSpec', 'PursuitSpec', 'GazeHistorySpec', 'AoiSpec', 'PupilSpec', 'ScreenLuminanceSpec', 'EyeGateSpec', 'BlinkSpec', 'SurfaceLayout', 'screen_calibration_samples', 'fit_screen_map', 'evaluate_screen_map', 'apply_screen_map', 'get_config', 'HotPathConfig', 'reset_standalone_config']
 
 
 def __getattr__(name):
@@ -26,6 +26,9 @@ def __getattr__(name):
     if name == 'SaccadeSpec':
         from .data import SaccadeSpec
         return SaccadeSpec
+    if name == 'PursuitSpec':
+        from .data import PursuitSpec
+        return PursuitSpec
     if name == 'GazeHistorySpec':
         from .data import GazeHistorySpec
         return GazeHistorySpec

@@ -212,6 +212,7 @@ SIGNATURES = {
     'eve_gaze_events': [L, I, P, P, P, P, P, P, P, P, P] + [ctypes.c_double] * 4 + [I] + [ctypes.c_double] * 3 + [P, I, P, P, P] + [P] * 8,
     'eve_gaze_events_ex': [L, I, P, P, P, P, P, P, P, P, P] + [ctypes.c_double] * 4 + [I] + [ctypes.c_double] * 3 + [P, I, P, P, P] + [P] * 11,
     'eve_gaze_saccades': [L, I] + [P] * 9 + [ctypes.c_double] * 3 + [I] + [P, P, I, P, P, P] + [P] * 3,
+    'eve_gaze_pursuits': [L, I] + [P] * 10 + [ctypes.c_double] * 7 + [I] + [P, P, I, P, P, P] + [P] * 7,
     'eve_eye_gate': [L, I, P, P, P, P, P, P, I, P, P, I, I, I, I, POINTER(EyeGateParams), P, I, P, P, P, P, P, P, P, P],
     'eve_gaze_history_plan': [L, I, P, P, P, P, P, P, ctypes.c_double, ctypes.c_double, I, ctypes.c_double, ctypes.c_double, I, I,
                               ctypes.c_double, ctypes.c_double, P, P, P, P],

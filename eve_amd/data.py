@@ -897,8 +897,8 @@ class GazeEventSpec(object):
       min_fixation_s   a fixation counts (`fixating`, the store) once it has lasted this long
       max_gap_s        two samples further apart than this are not connected: the filter and the fixation start afresh
     Instances compare and hash by value: the spec is part of a captured graph's key.  Not offered: dispersion (I-DT) or other
-    classifiers, windowed velocity, merging of adjacent fixations and retroactive relabelling, smooth-pursuit and blink classes,
-    per-eye events, gradients, EVE.forward."""
+    classifiers, windowed velocity, merging of adjacent fixations and retroactive relabelling, a blink class, per-eye events,
+    gradients, EVE.forward.  (Smooth pursuit, the third class, and its windowed velocity: PursuitSpec.)"""
 
     def __init__(self, source=None, fps=None, min_cutoff_hz=1.0, beta=0.007, d_cutoff_hz=1.0, velocity_from='filtered', saccade_deg_s=30.0,
                  min_fixation_s=0.06, max_gap_s=0.075):
@@ -943,8 +943,8 @@ def gaze_events(pog_px, o, inv_camera_transformation, pixels_per_millimeter, spe
     spec.fps) or float64 [S, T] seconds; valid None or bool / uint8 [S, T].  One eve_gaze_events launch, which also closes the
     fixations still open at the clip's end.  -> the seven per-frame keys of EVEStream.step(events=...) plus fixations (float64
     [S, fixation_capacity, 8], rows (id, t_start, t_last, n, cx, cy, rms_px, 0)), fixation_count and fixation_dropped (int32 [S]);
-    the host does not wait.  Not offered: dispersion classifiers, windowed velocity, merging of adjacent fixations, smooth-pursuit
-    and blink classes, per-eye events, gradients."""
+    the host does not wait.  Not offered: dispersion classifiers, windowed velocity, merging of adjacent fixations, a blink class,
+    per-eye events, gradients.  (Smooth pursuit: gaze_pursuits.)"""
     if not isinstance(spec, GazeEventSpec):
         raise ValueError('gaze_events: spec must be an eve_amd.GazeEventSpec, got %s' % type(spec).__name__)
     if not torch.is_tensor(pog_px) or pog_px.dtype != torch.float32 or pog_px.dim() != 3 or pog_px.shape[2] != 2 or pog_px.numel() == 0:
@@ -1000,7 +1000,7 @@ class SaccadeSpec(object):
     The amplitude is that of the point the velocity is from: with GazeEventSpec(velocity_from='filtered'), the default, the
     one-euro filter's lag shortens it; 'raw' gives the source's.  Instances compare and hash by value: the spec is part of a captured
     graph's key.  Not offered: direction angles (the endpoints are there), curvature or path length, glissades and post-saccadic
-    oscillation, microsaccades, smooth pursuit, per-eye saccades, retroactive merging, gradients, EVE.forward."""
+    oscillation, microsaccades, per-eye saccades, retroactive merging, gradients, EVE.forward.  (Smooth pursuit: PursuitSpec.)"""
 
     def __init__(self, min_amplitude_deg=0.5, min_duration_s=0.0, max_duration_s=0.2, max_missing=0):
         number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and np.isfinite(v)
@@ -1109,6 +1109,155 @@ def main_sequence(table):
                'peak_intercept': (sp - p_slope * sa) / n, 'mean_amplitude_deg': np.where(n > 0, sa / n, np.nan),
                'max_amplitude_deg': t[..., 7].copy(), 'max_peak_deg_s': t[..., 8].copy()}
     return out
+
+
+PURSUIT_KEYS = ('gaze_class', 'pursuit_id', 'pursuit_ms', 'gaze_velocity_windowed', 'gaze_straightness', 'pursuit_gain')
+PURSUIT_STATE = 320                              # doubles per stream of eve_gaze_pursuits' state row: 32 scalars + 32 ring entries of 9
+PURSUIT_TABLE_ROW = 16                           # ... of its table row
+PURSUIT_ROW = 20                                 # ... of a stored episode
+PURSUIT_COLUMNS = ('id', 't_onset', 't_end', 'n', 'x0', 'y0', 'x1', 'y1', 'amplitude_deg', 'direction_deg', 'mean_deg_s', 'peak_deg_s',
+                   'path_deg', 'fixation_id', 'missing', 'gain_n', 'mean_gain', 'mean_error_px')
+PURSUIT_TABLE = ('accepted', 'sum_dur', 'sum_amp', 'sum_path', 'sum_mean_v', 'max_peak', 'sum_gain', 'gain_n', 'aborted', 'small', 'short',
+                 'interrupted')
+
+
+class PursuitSpec(object):
+    """What EVEStream.step(chunk, events=..., pursuits=spec) adds after the events (and the saccade) stage (eve_gaze_pursuits): smooth
+    pursuit as the third gaze class.  Each fixation-labelled sample is looked at over a window of the chained samples before it; where
+    the gaze turned steadily and straight the frame is promoted to the pursuit class (gaze_class 3), and the runs of such frames
+    become episodes with amplitude, direction, mean and peak velocity, path length and -- with pursuit_target in the chunk -- gain and
+    position error, in the EVEStream's store, with a table of tallies (pursuit_summary()).
+      window_s            the window: the chained fixation samples of the last window_s seconds, at most 32 of them
+      min_window_s        a window shorter than this (after a saccade, a gap, a reset) decides nothing; <= window_s
+      pursuit_deg_s       the angle between the window's first and last gaze vector, over its time, must reach this (degrees / second)
+      min_straightness    ... and that angle over the window's path length (the sum of the events' velocities times their steps) this,
+                          in (0, 1]: fixational jitter wanders, pursuit goes straight
+      settle_s            the fixation samples this soon after a saccade frame stay out of the windows (the filter's creep after a landing)
+      min_duration_s      an episode shorter than this (onset to last sample) is tallied `short` and not stored
+      min_amplitude_deg   one whose onset and last gaze vectors are less than this apart is tallied `small`
+      max_missing         one with more frames that were no sample inside it is tallied `interrupted`
+    Pursuit wants the filtered point (GazeEventSpec(velocity_from='filtered'), the default): with 'raw', jitter lowers the
+    straightness and fragments the episodes at high frame rates (tests/pursuit_ref.py on an 8 degrees / second ramp with 0.1 degrees
+    of jitter at 120 fps: 8 fragments raw, 3 of them accepted and 5 short; one episode when filtered).  Instances compare and hash by value: the spec is part of a captured graph's key.  Not offered: hysteresis, or
+    merging episodes across catch-up saccades (the rows carry what a host merge needs: times, endpoints, the fixation id);
+    retroactive relabelling of the frames before a window fills; per-eye pursuit; vestibulo-ocular compensation; gradients;
+    EVE.forward."""
+
+    def __init__(self, window_s=0.2, min_window_s=0.1, pursuit_deg_s=3.0, min_straightness=0.7, settle_s=0.08, min_duration_s=0.15,
+                 min_amplitude_deg=1.0, max_missing=3):
+        number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and np.isfinite(v)
+        for name, v in (('window_s', window_s), ('min_window_s', min_window_s), ('pursuit_deg_s', pursuit_deg_s)):
+            if not number(v) or not v > 0:
+                raise ValueError('PursuitSpec: %s must be a finite number > 0, got %r' % (name, v))
+        if min_window_s > window_s:
+            raise ValueError('PursuitSpec: min_window_s must be <= window_s (%r), got %r' % (window_s, min_window_s))
+        if not number(min_straightness) or not 0 < min_straightness <= 1:
+            raise ValueError('PursuitSpec: min_straightness must lie in (0, 1], got %r' % (min_straightness,))
+        for name, v in (('settle_s', settle_s), ('min_duration_s', min_duration_s), ('min_amplitude_deg', min_amplitude_deg)):
+            if not number(v) or v < 0:
+                raise ValueError('PursuitSpec: %s must be a finite number >= 0, got %r' % (name, v))
+        if isinstance(max_missing, bool) or not isinstance(max_missing, (int, np.integer)) or not 0 <= max_missing <= 0x7fffffff:
+            raise ValueError('PursuitSpec: max_missing must be an integer >= 0, got %r' % (max_missing,))
+        self.window_s, self.min_window_s, self.pursuit_deg_s = float(window_s), float(min_window_s), float(pursuit_deg_s)
+        self.min_straightness, self.settle_s, self.min_duration_s = float(min_straightness), float(settle_s), float(min_duration_s)
+        self.min_amplitude_deg, self.max_missing = float(min_amplitude_deg), int(max_missing)
+
+    def key(self):
+        return (self.window_s, self.min_window_s, self.pursuit_deg_s, self.min_straightness, self.settle_s, self.min_duration_s,
+                self.min_amplitude_deg, self.max_missing)
+
+    def __eq__(self, other):
+        return isinstance(other, PursuitSpec) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return 'PursuitSpec(window_s=%r, min_window_s=%r, pursuit_deg_s=%r, min_straightness=%r, settle_s=%r, min_duration_s=%r, ' \
+               'min_amplitude_deg=%r, max_missing=%r)' % self.key()
+
+
+def pursuit_buffers(S, capacity, device):
+    """-> (state float64 [S, 320], table float64 [S, 16], store float64 [S, capacity, 20], count and dropped int32 [S]) of S streams
+    that have seen nothing: what eve_gaze_pursuits carries (include/eve_hip.h has the rows)."""
+    z = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=device)
+    return (z((S, PURSUIT_STATE), torch.float64), z((S, PURSUIT_TABLE_ROW), torch.float64), z((S, capacity, PURSUIT_ROW), torch.float64),
+            z((S,), torch.int32), z((S,), torch.int32))
+
+
+def pursuit_stage(k, pog, res, spec, pursuit_spec, buffers, target=None, lengths=None, reset=None):
+    """The one eve_gaze_pursuits launch behind EVEStream.step and gaze_pursuits: k the kernels, pog the events' source point [B, T, 2],
+    res gaze_events_ex's result, buffers the five carried tensors, target float32 [B, T, 2] or None -> the six per-frame keys.  The
+    point is the one the velocity is from, as for saccade_stage."""
+    point = pog if spec.velocity_from == 'raw' else res['PoG_px_filtered']
+    return k.gaze_pursuits(res['sample'], res['sample_time'], res['gaze_vector'], point, res['gaze_event'], res['gaze_velocity'],
+                           res['fixation_id'], pursuit_spec, *buffers, target=target, lengths=lengths, reset=reset)
+
+
+def gaze_pursuits(pog_px, o, inv_camera_transformation, pixels_per_millimeter, spec, pursuit_spec, frame_time=None, valid=None, target=None,
+                  pursuit_capacity=256):
+    """The fixation / saccade events AND the smooth pursuit of S recorded streams, stand-alone and from fresh state: gaze_events'
+    arguments (spec a GazeEventSpec) plus pursuit_spec, a PursuitSpec, and target, None or float32 [S, T, 2] (the pursued object's
+    screen position in pixels, NaN where there is none).  One eve_gaze_events_ex and one eve_gaze_pursuits launch.  -> the seven
+    per-frame keys of the events (unchanged: the pursuit frames are still fixation frames there), gaze_class uint8 [S, T] (0 none, 1
+    fixation, 2 saccade, 3 pursuit), pursuit_id int32 [S, T] (-1 outside an episode), pursuit_ms, gaze_velocity_windowed,
+    gaze_straightness and pursuit_gain float32 [S, T] (the last three NaN where undefined), plus pursuits (float64 [S,
+    pursuit_capacity, 20], rows PURSUIT_COLUMNS: id, t_onset, t_end, n, x0, y0, x1, y1, amplitude_deg, direction_deg (screen axes, y
+    down), mean_deg_s, peak_deg_s, path_deg, fixation_id, missing, gain_n, mean_gain, mean_error_px, 0, 0), pursuit_count and
+    pursuit_dropped (int32 [S]) and pursuit_table (float64 [S, 16], entries PURSUIT_TABLE; pursuit_summary() reads it); the host does
+    not wait.  An episode still open at the clip's end is not stored.  Not offered: see PursuitSpec."""
+    if not isinstance(spec, GazeEventSpec):
+        raise ValueError('gaze_pursuits: spec must be an eve_amd.GazeEventSpec, got %s' % type(spec).__name__)
+    if not isinstance(pursuit_spec, PursuitSpec):
+        raise ValueError('gaze_pursuits: pursuit_spec must be an eve_amd.PursuitSpec, got %s' % type(pursuit_spec).__name__)
+    if not torch.is_tensor(pog_px) or pog_px.dtype != torch.float32 or pog_px.dim() != 3 or pog_px.shape[2] != 2 or pog_px.numel() == 0:
+        raise TypeError('gaze_pursuits: pog_px must be float32 [S, T, 2], got %s %s' % (getattr(pog_px, 'dtype', type(pog_px)),
+                                                                                       tuple(getattr(pog_px, 'shape', ()))))
+    S, T = pog_px.shape[:2]
+    for name, t, shape in (('o', o, (S, T, 3)), ('inv_camera_transformation', inv_camera_transformation, (S, T, 4, 4)),
+                           ('pixels_per_millimeter', pixels_per_millimeter, (S, T, 2))):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != shape:
+            raise TypeError('gaze_pursuits: %s must be float32 %s, got %s %s' % (name, list(shape), getattr(t, 'dtype', type(t)),
+                                                                                tuple(getattr(t, 'shape', ()))))
+    if target is not None and (not torch.is_tensor(target) or target.dtype != torch.float32 or tuple(target.shape) != (S, T, 2)):
+        raise TypeError('gaze_pursuits: target must be float32 [%d, %d, 2], got %s %s' % (S, T, getattr(target, 'dtype', type(target)),
+                                                                                         tuple(getattr(target, 'shape', ()))))
+    if frame_time is None and spec.fps is None:
+        raise ValueError('gaze_pursuits: frame_time, or a spec with fps')
+    if frame_time is not None and (not torch.is_tensor(frame_time) or frame_time.dtype != torch.float64 or tuple(frame_time.shape) != (S, T)):
+        raise TypeError('gaze_pursuits: frame_time must be float64 [%d, %d] seconds' % (S, T))
+    if valid is not None:
+        valid = _bool_rows(valid, (S, T), 'gaze_pursuits: valid')
+    if isinstance(pursuit_capacity, bool) or not isinstance(pursuit_capacity, (int, np.integer)) or pursuit_capacity < 1:
+        raise ValueError('gaze_pursuits: pursuit_capacity must be an integer >= 1, got %r' % (pursuit_capacity,))
+    dev = pog_px.device
+    k = default_kernels()
+    z = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)
+    pog_px = pog_px.contiguous()
+    # (the fixation store is not returned -- gaze_events has it -- so one row per stream does)
+    res = k.gaze_events_ex(pog_px, o.contiguous(), inv_camera_transformation.contiguous(), pixels_per_millimeter.contiguous(), spec,
+                           z((S, 32), torch.float64), z((S, 1, 8), torch.float64), z((S,), torch.int32), z((S,), torch.int32),
+                           frame_time=None if frame_time is None else frame_time.contiguous(), valid=valid)
+    buffers = pursuit_buffers(S, int(pursuit_capacity), dev)
+    out = {k_: res[k_] for k_ in GAZE_EVENT_KEYS}
+    out.update(pursuit_stage(k, pog_px, res, spec, pursuit_spec, buffers, target=None if target is None else target.contiguous()))
+    out.update(pursuits=buffers[2], pursuit_count=buffers[3], pursuit_dropped=buffers[4], pursuit_table=buffers[1])
+    return out
+
+
+def pursuit_summary(table):
+    """The pursuit table's sums as means, on the host in numpy: table float64 [S, 16] or [16] (EVEStream.pursuit_table(),
+    gaze_pursuits()['pursuit_table']; a tensor is copied to the host, which waits) -> a dict of float64 [S] (or scalars): n (the
+    accepted episodes), pursuit_s (their total duration in seconds), mean_deg_s (the mean of the episodes' mean velocities), mean_gain
+    (over the samples with a defined gain) and max_peak_deg_s.  The two means are NaN where there is nothing to average."""
+    t = table.detach().cpu().numpy() if torch.is_tensor(table) else np.asarray(table)
+    t = np.asarray(t, dtype=np.float64)
+    if t.shape[-1:] != (PURSUIT_TABLE_ROW,) or t.ndim not in (1, 2):
+        raise ValueError('pursuit_summary: table must be [S, 16] or [16], got %s' % (t.shape,))
+    n, gain_n = t[..., 0], t[..., 7]
+    with np.errstate(all='ignore'):
+        return {'n': n.copy(), 'pursuit_s': t[..., 1].copy(), 'mean_deg_s': np.where(n > 0, t[..., 4] / n, np.nan),
+                'mean_gain': np.where(gain_n > 0, t[..., 6] / gain_n, np.nan), 'max_peak_deg_s': t[..., 5].copy()}
 
 
 GAZE_HISTORY_SOURCES = ('PoG_px_initial', 'PoG_px_final', 'PoG_px_filtered', 'fixation_px', 'heatmap_final')

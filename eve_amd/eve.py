@@ -366,7 +366,8 @@ class EVE(nn.Module):
 
     def _predict_sequence(self, d, eye_states, refine_states, reset=None, return_heatmaps=False, lengths=None, masked=False,
                           eye_mask=None, pose_gate=None, face_state=None, render=None, calibration=None, events=None, gate=None,
-                          screen_calibration=None, history=None, aoi=None, pupil=None, luminance=None, saccades=None):
+                          screen_calibration=None, history=None, aoi=None, pupil=None, luminance=None, saccades=None,
+                          pursuits=None):
         """The prediction part of forward() for one chunk of an EVEStream: eval only, no labels, no losses.  d: the chunk's
         inputs [B, Tc, ...] (not modified; camera_frame may be any one key of eye_net.EYE_FRAME_KEYS or camera_surface, and the screen any one
         key of refine_net.SCREEN_FRAME_KEYS or screen_surface; the eyes as patches, as camera_frame + {left,right}_eye_warp, or as camera_frame +
@@ -443,7 +444,12 @@ class EVE(nn.Module):
         'store': float64 [B, S, 16], 'count', 'dropped': int32 [B]}, which needs events: the events launch is then eve_gaze_events_ex,
         and one eve_gaze_saccades launch follows it, before the history stage, over that launch's sample flags, times and gaze vectors
         (which stay internal), its labels, velocities and fixation ids and the point the velocity is from, with the step's lengths and
-        reset flags; the result gains saccade_id and saccade_ms.  None issues the launches a step without it issues."""
+        reset flags; the result gains saccade_id and saccade_ms.  None issues the launches a step without it issues.
+        pursuits: None, or EVEStream's smooth-pursuit stage {'spec': a data.PursuitSpec, 'state': float64 [B, 320], 'table': float64
+        [B, 16], 'store': float64 [B, S, 20], 'count', 'dropped': int32 [B]}, which needs events: the events launch is then
+        eve_gaze_events_ex, and one eve_gaze_pursuits launch follows it (and the saccade launch, where there is one), before the
+        history stage, over the same inputs plus the chunk's optional pursuit_target float32 [B, Tc, 2]; the result gains
+        data.PURSUIT_KEYS.  None issues the launches a step without it issues."""
         assert not self.training, 'EVE._predict_sequence is eval-only'
         B = eye_input(d).shape[0]
         posed, faced = has_pose_form(d), face_landmarks_key(d) is not None
@@ -511,18 +517,23 @@ class EVE(nn.Module):
             T = eye_input(d).shape[1]
             k = default_kernels()
             pog = _f32(inter[events['source']], B, T, 2)
-            res = (k.gaze_events if saccades is None else k.gaze_events_ex)(
+            res = (k.gaze_events if saccades is None and pursuits is None else k.gaze_events_ex)(
                 pog, _f32(d['o'], B, T, 3), _f32(d['inv_camera_transformation'], B, T, 4, 4),
                 _f32(d['pixels_per_millimeter'], B, T, 2), events['spec'], events['state'], events['store'], events['count'], events['dropped'],
                 frame_time=d['frame_time'].contiguous() if 'frame_time' in d else None, valid=None if plan is None else plan['valid'],
                 lengths=lengths_b, reset=reset_b)
-            if saccades is None:
+            if saccades is None and pursuits is None:
                 out.update(res)
             else:
-                from .data import GAZE_EVENT_KEYS, saccade_stage
+                from .data import GAZE_EVENT_KEYS, pursuit_stage, saccade_stage
                 out.update({k_: res[k_] for k_ in GAZE_EVENT_KEYS})
-                out.update(saccade_stage(k, pog, res, events['spec'], saccades['spec'],
-                                         [saccades[k_] for k_ in ('state', 'table', 'store', 'count', 'dropped')], lengths=lengths_b, reset=reset_b))
+                carried = lambda stage: [stage[k_] for k_ in ('state', 'table', 'store', 'count', 'dropped')]
+                if saccades is not None:
+                    out.update(saccade_stage(k, pog, res, events['spec'], saccades['spec'], carried(saccades), lengths=lengths_b, reset=reset_b))
+                if pursuits is not None:
+                    target = _f32(d['pursuit_target'], B, T, 2) if 'pursuit_target' in d else None
+                    out.update(pursuit_stage(k, pog, res, events['spec'], pursuits['spec'], carried(pursuits), target=target, lengths=lengths_b,
+                                             reset=reset_b))
         if history is not None:
             self._gaze_history(d, inter, out, history, lengths_b, reset_b, plan)
         if aoi is not None:

@@ -1273,6 +1273,64 @@ class HipKernels(object):
             self._p(dropped), *([self._p(out[k_]) for k_ in self.GAZE_SACCADE_KEYS] if T else [None] * 2), self._stream()))
         return out
 
+    # ------------------------------------------------------------------ smooth pursuit
+    GAZE_PURSUIT_KEYS = ('gaze_class', 'pursuit_id', 'pursuit_ms', 'gaze_velocity_windowed', 'gaze_straightness', 'pursuit_gain')
+
+    def gaze_pursuits(self, sample, sample_time, gaze_vector, point, event, velocity, fixation_id, spec, state, table, store, count, dropped,
+                      target=None, lengths=None, reset=None):
+        """The smooth pursuit of B streams x T frames, found among the events launch's fixation frames: gaze_saccades' frame inputs
+        (sample uint8 [B, T], sample_time float64 [B, T], gaze_vector float64 [B, T, 3], point float32 [B, T, 2], event uint8 [B, T],
+        velocity float32 [B, T], fixation_id int32 [B, T]) plus target float32 [B, T, 2] or None (the pursued object's screen position,
+        NaN where there is none); spec an eve_amd.PursuitSpec (its numbers are the launch's scalars); state float64 [B, 320], table
+        float64 [B, 16], store float64 [B, S, 20], count and dropped int32 [B], UPDATED IN PLACE; lengths and reset int32 [B], or None.
+        -> a dict of GAZE_PURSUIT_KEYS: gaze_class uint8 [B, T] (0 none, 1 fixation, 2 saccade, 3 pursuit), pursuit_id int32 [B, T]
+        (-1 outside an episode), pursuit_ms, gaze_velocity_windowed, gaze_straightness and pursuit_gain float32 [B, T] (the last three
+        NaN where undefined).  sample None (then every frame input is None too): T = 0, a launch that only resets, -> {}
+        (include/eve_hip.h eve_gaze_pursuits)."""
+        ok = lambda t, dtype: torch.is_tensor(t) and t.dtype == dtype
+        got = lambda t: (getattr(t, 'dtype', type(t)), tuple(getattr(t, 'shape', ())))
+        if not ok(state, torch.float64) or state.dim() != 2 or state.shape[1] != 320 or state.shape[0] < 1:
+            raise TypeError('gaze_pursuits: state must be float64 [B, 320], got %s %s' % got(state))
+        B = state.shape[0]
+        if not ok(store, torch.float64) or store.dim() != 3 or store.shape[0] != B or store.shape[1] < 1 or store.shape[2] != 20:
+            raise TypeError('gaze_pursuits: store must be float64 [%d, S, 20], got %s %s' % ((B,) + got(store)))
+        S = store.shape[1]
+        T = 0
+        if sample is not None:
+            if not ok(sample, torch.uint8) or sample.dim() != 2 or sample.shape[0] != B or sample.shape[1] < 1:
+                raise TypeError('gaze_pursuits: sample must be uint8 [%d, T], got %s %s' % ((B,) + got(sample)))
+            T = sample.shape[1]
+        checks = [('table', table, torch.float64, (B, 16), True), ('count', count, torch.int32, (B,), True),
+                  ('dropped', dropped, torch.int32, (B,), True), ('lengths', lengths, torch.int32, (B,), False),
+                  ('reset', reset, torch.int32, (B,), False)]
+        if T:
+            checks += [('sample_time', sample_time, torch.float64, (B, T), True), ('gaze_vector', gaze_vector, torch.float64, (B, T, 3), True),
+                       ('point', point, torch.float32, (B, T, 2), True), ('event', event, torch.uint8, (B, T), True),
+                       ('velocity', velocity, torch.float32, (B, T), True), ('fixation_id', fixation_id, torch.int32, (B, T), True),
+                       ('target', target, torch.float32, (B, T, 2), False)]
+        elif any(t is not None for t in (sample_time, gaze_vector, point, event, velocity, fixation_id, target)):
+            raise TypeError('gaze_pursuits: without sample (T = 0) there are no frame inputs')
+        tensors = [state, store] + ([sample] if T else [])
+        for name, t, dtype, shape, needed in checks:
+            if (t is not None or needed) and (not ok(t, dtype) or tuple(t.shape) != shape):
+                raise TypeError('gaze_pursuits: %s must be %s %s, got %s %s' % ((name, str(dtype).replace('torch.', ''), list(shape)) + got(t)))
+            if t is not None:
+                tensors.append(t)
+        if not all(t.is_contiguous() for t in tensors):
+            raise RuntimeError('eve_amd: non-contiguous tensor handed to a kernel')
+        dev = state.device
+        out = {}
+        if T:
+            dtypes = (torch.uint8, torch.int32, torch.float32, torch.float32, torch.float32, torch.float32)
+            out = {k_: torch.empty((B, T), dtype=dt, device=dev) for k_, dt in zip(self.GAZE_PURSUIT_KEYS, dtypes)}
+        self._ck(self.lib.eve_gaze_pursuits(
+            B, T, self._p(sample), self._p(sample_time), self._p(gaze_vector), self._p(point), self._p(event), self._p(velocity),
+            self._p(fixation_id), self._p(target), self._p(lengths), self._p(reset), float(spec.window_s), float(spec.min_window_s),
+            float(spec.pursuit_deg_s), float(spec.min_straightness), float(spec.settle_s), float(spec.min_duration_s),
+            float(spec.min_amplitude_deg), int(spec.max_missing), self._p(state), self._p(table), S, self._p(store), self._p(count),
+            self._p(dropped), *([self._p(out[k_]) for k_ in self.GAZE_PURSUIT_KEYS] if T else [None] * 6), self._stream()))
+        return out
+
     # ------------------------------------------------------------------ the time-decayed gaze history
     def gaze_history_plan(self, P, screen_size, state, T, pog=None, frame_time=None, valid=None, valid_key=None, lengths=None, reset=None):
         """The time chain of the gaze history for B streams x T frames: P the launch's scalars (data.GazeHistorySpec.launch_params:

@@ -14,6 +14,8 @@ carried from one call to the next.
     rows = stream.fixations()                              # the completed fixations of every stream (see "Gaze events" below)
     out = stream.step(chunk, events=eve_amd.GazeEventSpec(fps=60), saccades=eve_amd.SaccadeSpec())   # + saccade_id, saccade_ms ("Saccades")
     rows = stream.saccades()                               # the accepted saccades: amplitude, duration, peak velocity, the fixations around them
+    out = stream.step(chunk, events=eve_amd.GazeEventSpec(fps=60), pursuits=eve_amd.PursuitSpec())   # + gaze_class, pursuit_id, ... ("Smooth pursuit")
+    rows = stream.pursuits()                               # the accepted pursuit episodes: amplitude, direction, velocities, path, gain
     out = stream.step(chunk, gate=eve_amd.EyeGateSpec(blink=eve_amd.BlinkSpec()))   # the mask made on the device (see "The eye gate" below)
     out = stream.step(chunk, history=eve_amd.GazeHistorySpec(fps=60))                # + the time-decayed map of where the gaze has been
     out = stream.step(dict(chunk, aoi_shapes=regions), aoi=eve_amd.AoiSpec(num_aois=8, fps=60))   # + which region is looked at ("Areas of interest")
@@ -105,7 +107,7 @@ events' state is a float64 [B, 32] row per stream, carried from step to step lik
 device flags (get_event_state / set_event_state; get_state / set_state do not hold it).  Float64 throughout;
 tests/gaze_events_ref.py states the arithmetic.  A step without events issues exactly the launches it always issued.  Not offered:
 dispersion (I-DT) or other classifiers, windowed velocity, merging of adjacent fixations and retroactive relabelling,
-smooth-pursuit and blink classes, per-eye events, gradients, EVE.forward.
+a blink class, per-eye events, gradients, EVE.forward.  (Smooth pursuit, the third class: "Smooth pursuit" below.)
 
 Saccades.  The events stage labels every frame, and only fixations leave it as events; saccades are the other half of every event
 detector -- amplitude, duration, peak and mean velocity, the link fixation -> saccade -> fixation that is the scan path, an "in
@@ -132,7 +134,34 @@ without saccades= moves the chain on without the stage; the stream remembers, an
 before the next saccades step.  Float64; tests/saccade_ref.py states the rules, and the device equals them bit for bit up to the
 amplitude's atan2.  A step without saccades= issues exactly the launches it always issued, eve_gaze_events included, and allocates
 nothing.  Not offered: direction angles (the endpoints are there), curvature or path length, glissades and post-saccadic
-oscillation, microsaccades, smooth pursuit, per-eye saccades, retroactive merging, gradients, EVE.forward.
+oscillation, microsaccades, per-eye saccades, retroactive merging, gradients, EVE.forward.
+
+Smooth pursuit.  EVE's stimuli include videos, and on a moving target the eye neither fixates nor jumps: it follows at 2 .. 30 degrees
+/ second, far below saccade_deg_s, so the events stage labels those frames fixations, fixation_px drifts behind the eye and
+fixations() stores "fixations" hundreds of pixels long.  step(chunk, events=..., pursuits=eve_amd.PursuitSpec(...)) adds the third
+class: the events launch is eve_gaze_events_ex (as for saccades=) and one eve_gaze_pursuits launch follows it -- after the saccade
+launch where there is one, before the history stage, inside the graph.  Per stream the launch keeps the run of chained fixation
+samples since the last saccade frame or restart (its last 32 in the state row; the samples of the first settle_s after a saccade
+stay out, for the filter's creep after a landing) and looks at every new one over the window of the last window_s seconds: the
+angle between the window's first and last gaze vector over its time (gaze_velocity_windowed), and that angle over the window's
+path length, the sum of the events' velocities times their steps (gaze_straightness: 1 for straight motion, near 0 for jitter).
+Where both reach their thresholds the frame is promoted: gaze_class 3 (else the events' label), pursuit_id, pursuit_ms.  The runs
+of such frames are episodes: one opens at its first frame's window start (never before the end of the episode before it), ends at
+its last frame, and is judged -- interrupted, short, small, or accepted -- when the next fixation frame that is no candidate, or a
+saccade frame, arrives; a restart of the chain and reset() abort it, and one open at a chunk's end goes on in the next chunk.
+Accepted episodes go to a table float64 [B, 16] (accepted, sum_dur, sum_amp, sum_path, sum_mean_v, max_peak, sum_gain, gain_n,
+aborted, small, short, interrupted, 0 ...: data.pursuit_summary()) and a store float64 [B, pursuit_capacity, 20] (id, t_onset, t_end,
+n, x0, y0, x1, y1, amplitude_deg, direction_deg, mean_deg_s, peak_deg_s, path_deg, fixation_id, missing, gain_n, mean_gain,
+mean_error_px, 0, 0): pursuits(), pursuit_counts(), pursuit_table(), clear_pursuits(), get_pursuit_state() / set_pursuit_state().
+With pursuit_target float32 [B, Tc, 2] in the chunk (the pursued object's screen position in pixels, NaN where none) every window
+also has a gain -- the eye's displacement projected on the target's, over the target's (pursuit_gain; 1 is perfect tracking) -- and
+the rows carry its mean and the mean distance to the target.  gaze_event, the fixation keys and the fixation store keep their bits:
+a row's fixation_id names the "fixation" the episode lies in, for a consumer to discount.  The frames before a window fills are not
+relabelled, so an episode's first min_window_s carry class 1 while its row's onset covers them.  Pursuit wants the filtered point:
+with velocity_from='raw' jitter lowers the straightness and fragments episodes at high frame rates.  Float64; tests/pursuit_ref.py
+states the rules, and the device equals them bit for bit up to the atan2 behind the angles.  A step without pursuits= issues exactly
+the launches it always issued and allocates nothing.  Not offered: hysteresis, or merging episodes across catch-up saccades (the rows
+carry what a host merge needs); retroactive relabelling; per-eye pursuit; vestibulo-ocular compensation; gradients; EVE.forward.
 
 The eye gate.  The masked step keeps an unusable eye out of the states and the fused gaze, but it needs the mask, and what should
 veto an eye -- pose_valid, face_reproj_rms, face_inliers, the derived warps and head angles, a closed lid -- are results of the same
@@ -254,6 +283,7 @@ StageBuffers = namedtuple('StageBuffers', 'state store count dropped')
 AoiBuffers = namedtuple('AoiBuffers', 'state table trans visits count dropped')      # what eve_gaze_aoi carries, per AoiSpec name
 PupilBuffers = namedtuple('PupilBuffers', 'state table light store count dropped')    # what eve_pupil_track carries, per PupilSpec name
 SaccadeBuffers = namedtuple('SaccadeBuffers', 'state table store count dropped')      # what eve_gaze_saccades carries
+PursuitBuffers = namedtuple('PursuitBuffers', 'state table store count dropped')      # what eve_gaze_pursuits carries
 
 
 def _module_key(m):
@@ -268,7 +298,8 @@ def _capacity(name, value):
 
 class EVEStream(object):
     def __init__(self, model, num_streams, use_graph=True, calibration_capacity=1024, fixation_capacity=256, blink_capacity=256,
-                 screen_calibration_capacity=1024, visit_capacity=256, episode_capacity=256, saccade_capacity=256):
+                 screen_calibration_capacity=1024, visit_capacity=256, episode_capacity=256, saccade_capacity=256,
+                 pursuit_capacity=256):
         if model.training:
             raise ValueError('EVEStream runs inference only: call model.eval() first')
         self.model = model
@@ -318,6 +349,13 @@ class EVEStream(object):
         self._saccades = None                    # made at the first saccades step or saccade call: (state, table, store, count, dropped)
         self._saccades_spec = None               # the spec of the last saccades step: the scalars of a launch with no frames
         self._saccades_stale = False
+        # smooth pursuit (step(chunk, events=..., pursuits=spec)): the run's ring and the open episode's state row, the table of tallies,
+        # the store of accepted episodes and its counters -- eve_gaze_pursuits reads and writes them inside the step (and the graph).
+        # _pursuits_stale: as _saccades_stale
+        self.pursuit_capacity = _capacity('pursuit_capacity', pursuit_capacity)
+        self._pursuits = None                    # made at the first pursuits step or pursuit call: (state, table, store, count, dropped)
+        self._pursuits_spec = None               # the spec of the last pursuits step: the scalars of a launch with no frames
+        self._pursuits_stale = False
         # the eye gate (step(chunk, gate=spec)): each eye's blink state row, the store of completed blinks and its counters --
         # eve_eye_gate reads and writes them inside the step (and the graph)
         self.blink_capacity = _capacity('blink_capacity', blink_capacity)
@@ -341,7 +379,7 @@ class EVEStream(object):
         self._render_tables = {}                 # OverlaySpec.key() -> its marker table, int32 [M, 4] on the device
 
     # ------------------------------------------------------------------ state
-    _GROUPS = ('_calib_store', '_events', '_gate', '_screen_store', '_saccades')      # the attributes _group() may fill: None until first use
+    _GROUPS = ('_calib_store', '_events', '_gate', '_screen_store', '_saccades', '_pursuits')      # the attributes _group() may fill: None until first use
 
     def _group(self, attr, kind, *buffers):
         """The lazily made buffer group self.<attr>, a `kind` namedtuple of zeroed device tensors, one per (shape, dtype) -- made at
@@ -355,7 +393,7 @@ class EVEStream(object):
         """Every tensor a step may write, as they exist now: what _capture's two warm-up steps must put back.  The recurrent states;
         the face-landmark form's head pose; kappa and its flags; both calibrations' sample stores and counters (the warm-up steps of
         a collecting graph would otherwise append every sample three times); the gaze events' state, store and counters (a capture
-        would otherwise tick the filter three times); the saccades' state row, table, store and counters; the eye gate's ticks, baselines and blinks; every gaze history's time chain
+        would otherwise tick the filter three times); the saccades' state row, table, store and counters; the pursuits' likewise; the eye gate's ticks, baselines and blinks; every gaze history's time chain
         and map; every AOI spec's state row, tallies and visit store; every pupil spec's state row, table, light response and
         episode store.  A carried buffer that is not returned here corrupts its state under use_graph only, and only on the first
         step of a chunk shape: new ones are made by _group(), by _history_entry(), by _aoi_entry() or by _pupil_entry(), and are
@@ -384,7 +422,8 @@ class EVEStream(object):
         eyes' blink rows and its tick cleared; an eye closed at that moment stores no blink.  A stream that has run gaze events (step(events=...)) closes its
         open fixation into the store -- if it lasted min_fixation_s -- and starts its filter, its events and its frame count afresh,
         by the same device flags; only its fixation id counter runs on, so ids stay unique within a recording.  A stream that has run the saccade stage (step(saccades=...)) aborts its open saccade -- tallied, nothing
-        stored -- and starts that row afresh; its saccade id counter and its table run on.  The per-person calibration -- each eye's kappa and the
+        stored -- and starts that row afresh; its saccade id counter and its table run on.  A stream that has run the pursuit stage (step(pursuits=...)) likewise aborts its open episode and empties its run; its
+        pursuit id counter and its table run on.  The per-person calibration -- each eye's kappa and the
         sample store -- is not touched: it belongs to the person, not to the clip (clear_calibration,
         clear_calibration_samples); neither are the screen-space map and its sample store (clear_screen_calibration,
         clear_screen_calibration_samples)."""
@@ -653,6 +692,7 @@ class EVEStream(object):
             raise ValueError('set_event_state: state must be [%d, 32], got %s' % (self.num_streams, tuple(state.shape)))
         self._event_buffers()[0].copy_(state)
         self._saccades_stale = self._saccades is not None      # (the saccade row no longer follows this chain)
+        self._pursuits_stale = self._pursuits is not None      # (nor does the pursuit row)
 
     def _output_stage(self):
         """'final' with a RefineNet, else 'initial': the stage whose point of gaze PoG_px_<out> is the step's output -- what the
@@ -750,6 +790,80 @@ class EVEStream(object):
             raise ValueError('step: saccades cuts the events stage\'s labels into saccades: pass events= in the same step')
         self._saccade_buffers()                  # allocated here, before any capture
         return {'spec': spec}
+
+    # ------------------------------------------------------------------ smooth pursuit
+    def _pursuit_buffers(self):
+        B, S = self.num_streams, self.pursuit_capacity
+        return self._group('_pursuits', PursuitBuffers, ((B, 320), torch.float64), ((B, 16), torch.float64), ((B, S, 20), torch.float64),
+                           ((B,), torch.int32), ((B,), torch.int32))
+
+    def _pursuit_launch_spec(self):
+        from .data import PursuitSpec
+        return self._pursuits_spec if self._pursuits_spec is not None else PursuitSpec()
+
+    def _reset_pursuit_rows(self, flags):
+        """One eve_gaze_pursuits launch with no frames: the flagged streams' open episodes are aborted and their rows start afresh."""
+        default_kernels().gaze_pursuits(None, None, None, None, None, None, None, self._pursuit_launch_spec(), *self._pursuit_buffers(),
+                                        reset=flags)
+
+    def pursuits(self, streams=None):
+        """The accepted pursuit episodes of the given streams (None = all; indices or a bool mask), one numpy float64 [n, 20] array per
+        stream in index order, rows (id, t_onset, t_end, n pursuit frames, x0, y0, x1, y1, amplitude_deg, direction_deg (screen axes, y
+        down), mean_deg_s, peak_deg_s, path_deg, fixation_id, missing, gain_n, mean_gain, mean_error_px, 0, 0: data.PURSUIT_COLUMNS) in
+        the order they ended; times in the clock of the steps, pixels of the point the velocity is from.  fixation_id is the events
+        stage's id of the "fixation" the episode lies in, so a consumer can discount that fixation; mean_gain and mean_error_px are NaN
+        where no sample had a target.  This call waits for the device."""
+        m = self._stream_mask(streams, 'pursuits')
+        _, _, store, count, _ = (t.cpu().numpy() for t in self._pursuit_buffers())
+        return [store[b, :min(max(int(count[b]), 0), self.pursuit_capacity)].copy() for b in np.flatnonzero(m)]
+
+    def pursuit_counts(self):
+        """-> (count, dropped), int32 [B] device tensors (fresh): the accepted episodes each stream's store holds, and those a full
+        store (pursuit_capacity) turned away."""
+        buffers = self._pursuit_buffers()
+        return buffers.count.clone(), buffers.dropped.clone()
+
+    def pursuit_table(self):
+        """The tallies, float64 [B, 16] (fresh): accepted, sum_dur, sum_amp, sum_path, sum_mean_v, max_peak, sum_gain, gain_n, aborted,
+        small, short, interrupted, 0 ... (data.PURSUIT_TABLE) -- seconds, degrees and degrees / second; data.pursuit_summary() reads
+        them."""
+        return self._pursuit_buffers().table.clone()
+
+    def clear_pursuits(self, streams=None, table=False):
+        """Empty the pursuit store of the given streams (None = all) and their dropped counters; with table=True their tallies too.
+        The open episode is state, not store: reset() ends it."""
+        m = self._device_mask(streams, 'clear_pursuits')
+        buffers = self._pursuit_buffers()
+        self._zero_where(m, buffers.count, buffers.dropped, *((buffers.table,) if table else ()))
+
+    def get_pursuit_state(self):
+        """The pursuit stage's carried state, float64 [B, 320] (fresh; include/eve_hip.h eve_gaze_pursuits has the layout): the run's
+        last samples, the open episode, the id counter.  Resets not yet applied by a step are not reflected.  get_state() /
+        set_state() do not hold it."""
+        return self._pursuit_buffers().state.clone()
+
+    def set_pursuit_state(self, state):
+        """Load a state in get_pursuit_state()'s layout, [B, 320] (converted to float64), e.g. beside set_event_state() to resume a
+        recording: the row is then taken to be in step with the events' row."""
+        state = torch.as_tensor(state, dtype=torch.float64).to(self.device)
+        if tuple(state.shape) != (self.num_streams, 320):
+            raise ValueError('set_pursuit_state: state must be [%d, 320], got %s' % (self.num_streams, tuple(state.shape)))
+        self._pursuit_buffers().state.copy_(state)
+        self._pursuits_stale = False
+
+    def _check_pursuits(self, chunk, spec, events, B, Tc):
+        """step()'s `pursuits` checked against the chunk -> the stage's plan.  Every refusal is a ValueError raised before anything is
+        launched or captured."""
+        from .data import PursuitSpec
+        if not isinstance(spec, PursuitSpec):
+            raise ValueError('step: pursuits must be an eve_amd.PursuitSpec, got %s' % type(spec).__name__)
+        if events is None:
+            raise ValueError('step: pursuits looks for smooth pursuit among the events stage\'s fixation frames: pass events= in the same step')
+        target = chunk.get('pursuit_target')
+        if target is not None:
+            self._check_chunk_tensor('pursuit_target', target, (torch.float32,), (B, Tc, 2))
+        self._pursuit_buffers()                  # allocated here, before any capture
+        return {'spec': spec, 'target': target is not None}
 
     # ------------------------------------------------------------------ the gaze history
     def _history_entry(self, spec, P):
@@ -872,13 +986,15 @@ class EVEStream(object):
             e = self._history_entry(plan['spec'], plan['P'])
             plan['state'], plan['maps'] = e['state'], e['maps']
 
-    def _reset_idle_stages(self, events, gate, history, aoi=None, pupil=None, saccades=None):
-        """A reset before a step that does not run a stage which carries state (events, gate, history, aoi, pupil, saccades: None or
-        this step's plans): the stage's state of the flagged streams still ends."""
+    def _reset_idle_stages(self, events, gate, history, aoi=None, pupil=None, saccades=None, pursuits=None):
+        """A reset before a step that does not run a stage which carries state (events, gate, history, aoi, pupil, saccades, pursuits: None
+        or this step's plans): the stage's state of the flagged streams still ends."""
         flags = self._flags[:self.num_streams]
         k = default_kernels()
         if saccades is None and self._saccades is not None:
             self._reset_saccade_rows(flags)      # the open saccade is aborted and the row starts afresh: the launch with no frames
+        if pursuits is None and self._pursuits is not None:
+            self._reset_pursuit_rows(flags)      # likewise the open pursuit episode
         if events is None and self._events is not None:
             # the gaze events' state ends its fixation and starts afresh: the launch with no frames
             k.gaze_events(None, None, None, None, self._closing_spec(), *self._events, reset=flags)
@@ -1531,7 +1647,7 @@ class EVEStream(object):
             self._pose_gate.fill_(self._pose_gate_host)              # a device value: the captured graphs read it, the host never waits
 
     def _run(self, chunk, return_heatmaps, ragged=False, eye_mask=None, masked=False, render=None, events=None, gate=None, history=None,
-             aoi=None, pupil=None, luminance=None, saccades=None):
+             aoi=None, pupil=None, luminance=None, saccades=None, pursuits=None):
         """The one call of EVE._predict_sequence, eager or under capture.  render, events, gate, history, aoi, pupil, luminance: None or the plan of
         that stage's check.  A stage's keyword goes along only when the stage runs, and lengths, the mask's keywords and face_state only
         on a ragged, a masked and a face-landmark step: a step without them makes the call it always made."""
@@ -1563,6 +1679,8 @@ class EVEStream(object):
             kw['events'] = dict(events, **self._event_buffers()._asdict())
         if saccades is not None:
             kw['saccades'] = dict(saccades, **self._saccade_buffers()._asdict())
+        if pursuits is not None:
+            kw['pursuits'] = dict(pursuits, **self._pursuit_buffers()._asdict())
         if gate is not None:
             kw['gate'] = dict(gate, **self._gate_buffers()._asdict())
         return self.model._predict_sequence(chunk, self._eye, self._ref, **kw)
@@ -1709,7 +1827,7 @@ class EVEStream(object):
         return render
 
     def step(self, chunk, return_heatmaps=False, lengths=None, eye_mask=None, skip_invalid_pose=False, render=None, events=None, gate=None,
-             history=None, aoi=None, pupil=None, luminance=None, saccades=None):
+             history=None, aoi=None, pupil=None, luminance=None, saccades=None, pursuits=None):
         """One chunk of every stream: chunk holds [B, Tc, ...] tensors on the model's device -- the eyes (below), {left,right}_h,
         {left,right}_o, {left,right}_R, head_R, camera_transformation, inv_camera_transformation, pixels_per_millimeter, millimeters_per_pixel, and screen_frame when the config loads screen content.  Returns the
         prediction keys of EVE(output_predictions=True) as [B, Tc, ...] tensors (heatmap_final [B, Tc, 1, H, W] on request).
@@ -2020,7 +2138,24 @@ class EVEStream(object):
         key; every other mode of the step combines with it.  After events steps without saccades= the stage's row is brought back in
         step by one launch with no frames before the next saccades step: a saccade under way then is not reported.
         tests/saccade_ref.py states the arithmetic.  saccades=None issues exactly the launches the step always issued,
-        eve_gaze_events included."""
+        eve_gaze_events included.
+        pursuits: None, or an eve_amd.PursuitSpec, with events= in the same step (ValueError without, raised before anything is
+        launched) -- smooth pursuit as the third gaze class (module docstring, "Smooth pursuit").  The events launch becomes
+        eve_gaze_events_ex, as for saccades=, and one eve_gaze_pursuits launch follows it (and the saccade launch, where there is
+        one), before the history stage and inside the captured graph.  The result gains gaze_class uint8 [B, Tc] (0 none, 1
+        fixation, 2 saccade, 3 pursuit; gaze_event and the fixation keys keep their bits), pursuit_id int32 [B, Tc] (-1 outside an
+        episode; a counter per stream that reset() leaves running), pursuit_ms float32 [B, Tc] (the time since the onset),
+        gaze_velocity_windowed and gaze_straightness float32 [B, Tc] (the window's degrees / second and its angle over its path; NaN
+        without a window) and pursuit_gain float32 [B, Tc] (NaN without a defined gain).  With pursuit_target in the chunk (float32
+        [B, Tc, 2]: the pursued object's position in actual_screen_size pixels, NaN where there is none; its presence is part of
+        the graph's key) the gain is the eye's displacement over the window projected on the target's, over the target's, and an
+        episode's row holds its mean and the mean distance to the target.  An episode ends at its last pursuit frame when a
+        fixation frame that is no candidate or a saccade frame arrives, and is judged then -- interrupted, short, small, or accepted
+        -- and an accepted one goes to the table and the store: pursuits(), pursuit_counts(), pursuit_table(), clear_pursuits(),
+        get_pursuit_state() / set_pursuit_state(), data.pursuit_summary().  A gap, a reset() and a restart of the chain abort an open
+        episode; one open at the end of a chunk goes on in the next.  After events steps without pursuits= the stage's row is
+        brought back in step by one launch with no frames before the next pursuits step.  tests/pursuit_ref.py states the
+        arithmetic.  pursuits=None issues exactly the launches the step always issued."""
         if self.model.training:
             raise ValueError('EVEStream runs inference only: the model was switched to training mode')
         B, Tc = eye_input(chunk).shape[:2]
@@ -2041,6 +2176,8 @@ class EVEStream(object):
         more = {} if gate is None else {'gate': gate}      # the keyword goes along only then: a step without it calls what it always did
         if saccades is not None:
             more['saccades'] = saccades = self._check_saccades(saccades, events)
+        if pursuits is not None:
+            more['pursuits'] = pursuits = self._check_pursuits(chunk, pursuits, events, B, Tc)
         if history is not None:
             more['history'] = history = self._check_history(chunk, history, events, masked, B, Tc)
         if aoi is not None:
@@ -2073,8 +2210,15 @@ class EVEStream(object):
                 self._saccades_stale = False
         elif events is not None and self._saccades is not None:
             self._saccades_stale = True
+        if pursuits is not None:
+            self._pursuits_spec = pursuits['spec']
+            if self._pursuits_stale:             # likewise: every pursuit row starts afresh, eagerly
+                self._reset_pursuit_rows(torch.ones((B,), dtype=torch.int32, device=self.device))
+                self._pursuits_stale = False
+        elif events is not None and self._pursuits is not None:
+            self._pursuits_stale = True
         if self._flags_set:
-            self._reset_idle_stages(events, gate, history, aoi, pupil, saccades)
+            self._reset_idle_stages(events, gate, history, aoi, pupil, saccades, pursuits)
         with torch.no_grad():
             if self.use_graph:
                 entry = self._graph_for(chunk, bool(return_heatmaps), ragged, masked, render, events, **more)
@@ -2110,7 +2254,7 @@ class EVEStream(object):
         return tuple(_module_key(m) for m in (self.model.eye_net, self.model.refine_net) if m is not None)
 
     def _graph_key(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None, aoi=None,
-                   pupil=None, luminance=None, saccades=None):
+                   pupil=None, luminance=None, saccades=None, pursuits=None):
         """What a captured graph is good for: the step's mode, both YUV matrices, both surface layouts (by value), the overlay
         (render: None or a _render_plan -- its OverlaySpec by value), with a face-landmark form eye_net.face_huber_px (a launch
         argument, so baked in), the gaze events (events: None or a _check_events plan -- its GazeEventSpec by value and its source;
@@ -2120,7 +2264,7 @@ class EVEStream(object):
         AoiSpec by value, its source and whether fixations are counted; aoi_shapes' shape is a chunk key), the pupillometry (pupil: None or a
         _check_pupil plan -- its PupilSpec by value; pupil_luminance's and pupil_baseline's presence are chunk keys), the screen luminance
         (luminance: None or a _check_luminance plan -- its ScreenLuminanceSpec by value and its source; the capture's shape is a chunk key and its
-        layout and matrix are RefineNet's), the saccades (saccades: None or a _check_saccades plan -- its SaccadeSpec by value), whether a calibration is applied (`calibrated`; a collecting step differs by its chunk keys), whether a screen-space map is applied (likewise), and every chunk tensor's key, shape and dtype -- which of the two landmark keys among them."""
+        layout and matrix are RefineNet's), the saccades (saccades: None or a _check_saccades plan -- its SaccadeSpec by value), the smooth pursuit (pursuits: None or a _check_pursuits plan -- its PursuitSpec by value and whether the chunk has pursuit_target), whether a calibration is applied (`calibrated`; a collecting step differs by its chunk keys), whether a screen-space map is applied (likewise), and every chunk tensor's key, shape and dtype -- which of the two landmark keys among them."""
         ref = self.model.refine_net
         spec = None if render is None else render['spec'].key()
         layouts = (self.model.eye_net.camera_layout, None if ref is None else ref.screen_layout)
@@ -2136,10 +2280,11 @@ class EVEStream(object):
             (() if aoi is None else (('aoi', aoi['spec'].key(), aoi['source'], aoi['use_fixations']),)) + \
             (() if pupil is None else (('pupil', pupil['spec'].key()),)) + \
             (() if luminance is None else (('luminance', luminance['spec'].key(), luminance['source']),)) + \
-            (() if saccades is None else (('saccades', saccades['spec'].key()),)) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
+            (() if saccades is None else (('saccades', saccades['spec'].key()),)) + \
+            (() if pursuits is None else (('pursuits', pursuits['spec'].key(), pursuits['target']),)) + tuple(sorted((k_, tuple(v.shape), v.dtype) for k_, v in chunk.items() if torch.is_tensor(v)))
 
     def _graph_for(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None, aoi=None,
-                   pupil=None, luminance=None, saccades=None):
+                   pupil=None, luminance=None, saccades=None, pursuits=None):
         wk = self._weights_key()
         if wk != self._graphs_key:               # new weights: new packs, new graphs (a replay never reads stale packs)
             self._graphs = {}
@@ -2155,6 +2300,8 @@ class EVEStream(object):
             more['luminance'] = luminance
         if saccades is not None:
             more['saccades'] = saccades
+        if pursuits is not None:
+            more['pursuits'] = pursuits
         key = self._graph_key(chunk, return_heatmaps, ragged, masked, render, events, **more)
         entry = self._graphs.get(key)
         if entry is None:
@@ -2164,7 +2311,7 @@ class EVEStream(object):
         return entry
 
     def _capture(self, chunk, return_heatmaps, ragged=False, masked=False, render=None, events=None, gate=None, history=None, aoi=None,
-                 pupil=None, luminance=None, saccades=None):
+                 pupil=None, luminance=None, saccades=None, pursuits=None):
         """Capture one step for this chunk shape (train.Trainer._capture's recipe): inputs copied into fixed buffers, two eager
         warm-up steps off the default stream (packs, lazily built filters, allocator) with the carried states put back
         afterwards, the kernels' scratch allocated before the capture, one stream, no side branches.  A masked graph has one more
@@ -2181,7 +2328,7 @@ class EVEStream(object):
             carried = self._carried()
             snap = [t.clone() for t in carried]
             for _ in range(2):
-                self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history, aoi, pupil, luminance, saccades)
+                self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history, aoi, pupil, luminance, saccades, pursuits)
             for t, s_ in zip(carried, snap):
                 t.copy_(s_)
         torch.cuda.current_stream().wait_stream(side)
@@ -2191,7 +2338,7 @@ class EVEStream(object):
             k.prepare_graph_workspace(self.device)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            out = self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history, aoi, pupil, luminance, saccades)
+            out = self._run(static, return_heatmaps, ragged, eye_mask, masked, render, events, gate, history, aoi, pupil, luminance, saccades, pursuits)
         m = self.model
         keep = (m.eye_net._packs, getattr(m.eye_net, '_stream_w', None), m.refine_net._packs if m.refine_net is not None else None)
         return {'graph': graph, 'inputs': static, 'outputs': out, 'keep': keep, 'eye_mask': eye_mask}

@@ -1269,7 +1269,7 @@ int eve_screen_calib_apply(long long B, int T, const float* px_in, const float* 
  * Refused without a launch: a null state, store or counter, with T > 0 a null frame input or output, B or F < 1, T < 0, index ranges
  * past 31 bits, fps not a finite number > 0 where frame_time is NULL and T > 0, a cutoff, threshold or time that is not a finite
  * number > 0, a beta that is not a finite number >= 0.  Not offered: dispersion (I-DT) classifiers, windowed velocity, merging of
- * adjacent fixations, smooth-pursuit and blink classes, per-eye events, a gradient.  (Additive: ABI v10.)                        */
+ * adjacent fixations, a blink class, per-eye events, a gradient (smooth pursuit: eve_gaze_pursuits).  (Additive: ABI v10.)        */
 int eve_gaze_events(long long B, int T, const float* pog, const float* origin, const float* inv_cam, const float* ppm,
                     const double* frame_time /* may be NULL */, const uint8_t* valid /* may be NULL */, const int* lengths /* may be NULL */,
                     const int* reset /* may be NULL */, const int* flush /* may be NULL */, double fps, double min_cutoff_hz, double beta,
@@ -1332,13 +1332,82 @@ int eve_gaze_events_ex(long long B, int T, const float* pog, const float* origin
  * Kernel name gaze_saccades_kernel.  Refused without a launch: a null carried buffer, B < 1, T < 0, S < 1, with T > 0 a null frame
  * input or output, index ranges past 31 bits, a threshold that is not finite, min_amplitude_deg < 0, max_duration_s <= 0,
  * min_duration_s < 0, max_missing < 0.  Not offered: direction angles (the endpoints are there), curvature or path length, glissades
- * and post-saccadic oscillation, microsaccades, smooth pursuit, per-eye saccades, retroactive merging, a gradient.  (Additive: ABI
- * v10.)                                                                                                                             */
+ * and post-saccadic oscillation, microsaccades, per-eye saccades, retroactive merging, a gradient (smooth pursuit:
+ * eve_gaze_pursuits).  (Additive: ABI v10.)                                                                                         */
 int eve_gaze_saccades(long long B, int T, const uint8_t* sample, const double* sample_time, const double* gaze_vector, const float* point,
                       const uint8_t* event, const float* velocity, const int* fixation_id, const int* lengths /* may be NULL */,
                       const int* reset /* may be NULL */, double min_amplitude_deg, double min_duration_s, double max_duration_s,
                       int max_missing, double* state, double* table, int S, double* store, int* count, int* dropped, int* saccade_id,
                       float* saccade_ms, eve_stream_t stream);
+
+/* Smooth pursuit, the third gaze class: among the frames that eve_gaze_events labels fixations, those in which the gaze turned
+ * steadily and straight over a window of the chained samples before them are promoted to the pursuit class and cut into episodes with
+ * amplitude, direction, mean and peak velocity, path length and, with a target, gain and position error, for B streams x T frames,
+ * with the state carried in `state`, the tallies in `table` and the accepted episodes in `store` from one call to the next.  Float64,
+ * every operation rounded on its own (no contraction), in the order written here; tests/pursuit_ref.py restates it in numpy.  One
+ * wavefront per stream, passes of 64 frames, the windows' and the closings' atan2 across the lanes; the bits do not depend on that
+ * structure.
+ *   sample, sample_time, gaze_vector, point, event, velocity, fixation_id, lengths, reset: as for eve_gaze_saccades; target [B*T][2]
+ *   float, may be NULL: the pursued object's screen position in the point's pixels, NaN where there is none (NULL: none anywhere),
+ *   widened to double.
+ *   state [B][320] double, table [B][16] double, store [B][S][20] double, count [B] and dropped [B] int: read and UPDATED IN PLACE.
+ * The state row, an all-zero row being a fresh stream: 32 scalars -- 0 ring_n, 1 seen_saccade (a saccade frame since the last
+ * restart), 2 t_saccade (the last one's time), 3 open, 4 the open episode's id, 5 next_id (the ids handed out so far), 6 t_onset,
+ * 7-9 the onset's gaze vector, 10-11 its point, 12 its cum, 13 n (the episode's pursuit frames), 14 peak, 15 missing, 16 fixation_id,
+ * 17 t_last, 18-20 the last sample's gaze vector, 21-22 its point, 23 its cum, 24 gain_sum, 25 gain_n, 26 err_sum, 27 has_end, 28
+ * t_end (the last closed episode's end, while has_end), 29-31 reserved (0) -- then the ring: 32 entries of 9 doubles (t, v0, v1, v2,
+ * cum, x, y, tx, ty), the first ring_n of them the run's last samples, oldest first, the others 0.  The RUN is the chained
+ * fixation-labelled samples since the last break; cum is the path length along it in degrees.
+ * A stream with reset[b] != 0 first aborts its open episode (table.aborted += 1, nothing stored) and zeroes its row except entry 5;
+ * the table stays.  Then frames f = 0 .. lengths[b] - 1 are walked in order (the later ones: class 0, id -1, ms 0, the rest NaN).
+ *   sample 0: where an episode is open, missing += 1.  Nothing else moves; class 0.
+ *   sample 1 (or sample 2 with an event other than 1 and 2, which eve_gaze_events never writes): an open episode is aborted, the run
+ *   is emptied, seen_saccade = has_end = 0, and the sample becomes the run's first entry with cum = 0.  Class 0.
+ *   sample 2, event 2: an open episode CLOSES (below); the run is emptied, has_end = 0, seen_saccade = 1, t_saccade = t.  Class 2.
+ *   sample 2, event 1: class 1 unless promoted.  With seen_saccade and t - t_saccade < settle_s the sample is not admitted to the run
+ *   (the one-euro filter's creep after a landing stays out of the windows).  Else it is appended with cum = cum_last + (double)
+ *   velocity * (t - t_last) (last: the run's entry before it; 0 for a first entry), and the ring keeps the last 32.  Its WINDOW
+ *   starts at entry j, found by stepping back from this entry while the entry before is in the ring (this one included: at most 31
+ *   steps) and t - t_that <= window_s.  With t - t_j < min_window_s there is no window: no promotion, the three window outputs NaN.
+ *   Else A = atan2(sqrt((c0*c0 + c1*c1) + c2*c2), (p0*v0 + p1*v1) + p2*v2) * 57.29577951308232 with p entry j's vector, v this
+ *   one's and c = p x v (eve_gaze_saccades' expression), w = A / (t - t_j), path = cum - cum_j, s = path > 0 ? A / path : 0, and the
+ *   frame is a CANDIDATE iff w >= pursuit_deg_s && s >= min_straightness.  Where tx, ty, tx_j, ty_j are all finite: dt = (tx - tx_j,
+ *   ty - ty_j), dg = (x - x_j, y - y_j), den = dtx*dtx + dty*dty, and where den > 0 the gain is defined: gain = (dgx*dtx + dgy*dty) /
+ *   den, err = sqrt((x - tx)*(x - tx) + (y - ty)*(y - ty)).
+ *   A candidate with no episode open opens one: id = next_id, next_id += 1 (accepted later or not); the onset is entry j -- with
+ *   has_end, the first entry from j on whose t > t_end (this entry if none), so that episodes never overlap --: t_onset, the onset's
+ *   vector, point and cum are that entry's; fixation_id is this frame's; n = peak = missing = gain_sum = gain_n = err_sum = 0.  Every
+ *   candidate then: n += 1, peak = w where that is > peak, the episode's last sample (t_last, vector, point, cum) = this one, with a
+ *   defined gain gain_sum += gain, err_sum += err, gain_n += 1; class 3, pursuit_id = id, pursuit_ms = 1000 * (t - t_onset).
+ *   A run sample that is no candidate CLOSES an open episode at its last sample.
+ *   Closing: has_end = 1, t_end = t_last, dur = t_last - t_onset, amplitude = the angle A between the onset's and the last vector,
+ *   direction = atan2(y1 - y0, x1 - x0) * 57.29577951308232 (screen axes, y down), path = cum_last - cum_onset.  The first that holds
+ *   decides: missing > max_missing: table.interrupted += 1; dur < min_duration_s: short; not (amplitude >= min_amplitude_deg): small;
+ *   else it is accepted: mean = amplitude / dur, table.accepted += 1, sum_dur += dur, sum_amp += amplitude, sum_path += path,
+ *   sum_mean_v += mean, max_peak takes a larger peak, sum_gain += gain_sum, gain_n += gain_n, and the row (id, t_onset, t_end, n, x0,
+ *   y0, x1, y1, amplitude_deg, direction_deg, mean_deg_s, peak_deg_s, path_deg, fixation_id, missing, gain_n, mean_gain = gain_sum /
+ *   gain_n, mean_error_px = err_sum / gain_n (both NaN with gain_n 0), 0, 0) goes to store[b][count[b]] and count[b] grows; with
+ *   count[b] == S it is dropped and dropped[b] grows.
+ * The table row: 0 accepted, 1 sum_dur, 2 sum_amp, 3 sum_path, 4 sum_mean_v, 5 max_peak, 6 sum_gain, 7 gain_n, 8 aborted, 9 small,
+ * 10 short, 11 interrupted, 12-15 reserved (0).  An episode open at the end of the frames stays open across calls; there is no flush.
+ * T = 0 is a call that only resets (the frame pointers may then be NULL).
+ * Outputs per frame, written for every f < T: gaze_class [B*T] uint8 (0 none, 1 fixation, 2 saccade, 3 pursuit), pursuit_id [B*T]
+ * int (-1 outside an episode), pursuit_ms [B*T] float (0 outside), gaze_velocity_windowed [B*T] float (w), gaze_straightness [B*T]
+ * float (s; both NaN without a window), pursuit_gain [B*T] float (NaN without a defined gain); each rounded from double once.
+ * Kernel name gaze_pursuits_kernel.  Refused without a launch: a null carried buffer, B < 1, T < 0, S < 1, with T > 0 a null frame
+ * input (target excepted) or output, index ranges past 31 bits, a parameter that is not finite, window_s <= 0, min_window_s <= 0 or
+ * > window_s, pursuit_deg_s <= 0, min_straightness outside (0, 1], settle_s < 0, min_duration_s < 0, min_amplitude_deg < 0,
+ * max_missing < 0.  Not offered: hysteresis, or merging episodes across catch-up saccades (the rows carry what a host merge needs);
+ * retroactive relabelling of the frames before a window fills; per-eye pursuit; vestibulo-ocular compensation; a gradient.  Pursuit
+ * wants the filtered point: with velocity_from_raw, jitter lowers the straightness and fragments episodes at high frame rates.
+ * (Additive: ABI v10.)                                                                                                              */
+int eve_gaze_pursuits(long long B, int T, const uint8_t* sample, const double* sample_time, const double* gaze_vector, const float* point,
+                      const uint8_t* event, const float* velocity, const int* fixation_id, const float* target /* may be NULL */,
+                      const int* lengths /* may be NULL */, const int* reset /* may be NULL */, double window_s, double min_window_s,
+                      double pursuit_deg_s, double min_straightness, double settle_s, double min_duration_s, double min_amplitude_deg,
+                      int max_missing, double* state, double* table, int S, double* store, int* count, int* dropped, uint8_t* gaze_class,
+                      int* pursuit_id, float* pursuit_ms, float* gaze_velocity_windowed, float* gaze_straightness, float* pursuit_gain,
+                      eve_stream_t stream);
 
 /* The eye gate: per frame and eye, is the eye usable?  One launch between the pose derivation and eve_stream_mask_plan turns the
  * results of the same step -- the pose flags, the solve's reprojection error and inlier count, the derived warps and head angles --
